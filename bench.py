@@ -3,13 +3,19 @@
 seq_len 2048, batch 8 per GPU) on N MI355X of one node.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full --dump-outputs bench_out
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one optimizer step with gradient_accumulation_steps=1: micro-batch forward + backward (HIP kernels) ->
 [N>1: per-layer RCCL all-reduce overlapped with backward + one scalar all-reduce] -> fused scale+AdamW kernel.
-Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line (contract in the task statement) with
-`roofline` (MFMA GEMM kernel family, HIP-event timed inside the timed region) and `cpu_baseline` (the CPU oracle timed on
-the host cores on a bounded sample; N=1 only).
+Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line (contract in the task statement).  A plain run
+does only what that headline line needs; `--full` adds `roofline` (MFMA GEMM kernel family, HIP-event timed inside the timed
+region) and `cpu_baseline` (the CPU oracle timed on the host cores on a bounded sample; N=1 only).
+
+`--dump-outputs DIR` writes what the last timed step computed, as float32 / float64 .npy files (about 23 MB): `loss.npy` and
+`tokens.npy` (the step's mean loss and label-token count), and a fixed sample of every parameter after the step (`params.npy`)
+and of AdamW's two moments (`adamw_exp_avg.npy`, `adamw_exp_avg_sq.npy`) — the same indices on every run, so two builds can be
+compared output for output.
 """
 from __future__ import annotations
 
@@ -229,6 +235,31 @@ def cpu_baseline(seed: int, warmup: int = 1, steps: int = 3) -> dict:
                       f"{cores} threads on {cpu_model_name()}", "loss": loss}
 
 
+DUMP_SAMPLE = 16_384  # elements per parameter in --dump-outputs (146 parameters of the 1B model: 1.9 M elements, 7.7 MB per float32 array)
+
+
+def dump_outputs(out_dir: str, model, opt, loss: float, n_tok: int) -> None:
+    """--dump-outputs: the last timed step's results as .npy files (module docstring).  The sample's indices follow from a fixed seed and
+    the parameter shapes alone, so every run with the same arguments reads the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss], dtype=np.float64))
+    np.save(os.path.join(out_dir, "tokens.npy"), np.array([n_tok], dtype=np.float64))
+    params = opt.param_groups[0]["params"]
+    state = opt.state_dict()["state"]  # index into `params` -> its exp_avg / exp_avg_sq (views of the optimizer's buffers, no copy)
+    rng = np.random.default_rng(42_831)
+    samples = {"params": [], "adamw_exp_avg": [], "adamw_exp_avg_sq": []}
+    for i, p in enumerate(params):
+        n = p.numel()
+        idx = torch.from_numpy(np.arange(n) if n <= DUMP_SAMPLE else np.sort(rng.integers(0, n, DUMP_SAMPLE))).to(p.device)
+        for key, t in (("params", p), ("adamw_exp_avg", state[i]["exp_avg"]), ("adamw_exp_avg_sq", state[i]["exp_avg_sq"])):
+            samples[key].append(t.detach().reshape(-1)[idx].float())
+    for key, parts in samples.items():
+        np.save(os.path.join(out_dir, f"{key}.npy"), torch.cat(parts).cpu().numpy())
+    print(f"[dump-outputs] {len(params)} parameters, {sum(x.numel() for x in samples['params'])} sampled elements each of params / "
+          f"exp_avg / exp_avg_sq -> {out_dir}", file=sys.stderr, flush=True)
+
+
 def self_launch(n: int) -> int:
     """`python bench.py --gpus N` without torchrun: start N fresh rank processes (one per GPU) through torch.distributed.run and
     relay rank 0's JSON line and the children's exit code.  Runs before this process has made any HIP call (a process that has
@@ -360,9 +391,16 @@ def main() -> int:
                     help="secondary line: the workload through Trainer.setup()/train() (the scripts/train_sft.py path) at grad-accum 1 and 4; "
                          "one GPU.  Not the headline line.")
     ap.add_argument("--cpt", action="store_true", help="with --through-trainer: the scripts/train_cpt.py path (conf/cpt.yaml; use --batch 16 --seq 768)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gemm-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-class GEMM timing with its roofline and the CPU baseline (each can be dropped again with the two "
+                         "options below); a plain run measures the headline line only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
+    ap.add_argument("--no-gemm-timing", action="store_true", help="with --full: no per-launch GEMM events, no roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's loss, token count and a fixed sample of the parameters and AdamW moments as .npy files")
     args = ap.parse_args()
+    if args.dump_outputs and args.through_trainer:
+        ap.error("--dump-outputs measures the plain step loop; it does not apply to --through-trainer")
 
     rank, world, local = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -434,7 +472,7 @@ def main() -> int:
         from ssi import ops as _ops
         _ops.set_gemm_tile_order(dynamic=os.environ["SSI_BENCH_TILE_ORDER"] == "dynamic")
     timer = GemmTimer()
-    if not args.no_gemm_timing and rank == 0:
+    if args.full and not args.no_gemm_timing and rank == 0:
         timer.install()
 
     ga = max(1, args.grad_accum)
@@ -468,7 +506,7 @@ def main() -> int:
             dist.barrier()
         torch.cuda.synchronize()
 
-    loss = float("nan")
+    loss, n_tok = float("nan"), 0
     for i in range(args.warmup):
         loss, _ = one_step(i)
     barrier()
@@ -477,10 +515,12 @@ def main() -> int:
         sync.timing, sync.bytes_reduced = True, 0
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss, _ = one_step(args.warmup + i)
+        loss, n_tok = one_step(args.warmup + i)
     barrier()
     elapsed = time.perf_counter() - t0
     timer.enabled = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, opt, loss, n_tok)
     if dp:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -547,7 +587,7 @@ def main() -> int:
                            "buckets": len(sync.buckets), "exposed_ms_per_step": sync.exposed_ms() / args.steps,
                            # per bucket: bytes, issue -> completion of its all-reduce, time the compute stream waited in front of it
                            "per_bucket": sync.bucket_report(args.steps)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(42_831)
             except Exception as e:  # the GPU number must still be reported

@@ -1,5 +1,5 @@
 """Recipe shared by the full-size parity tests, the committed config-A fixture and the script that made it (tests/golden/make_config_a.py):
-the seeded weights, the batch, and the per-parameter gradient SKETCH that lets a 2.5 MB file stand in for 5 GB of reference gradients.
+the seeded weights, the batch, and the per-parameter gradient SKETCH that lets 2.5 MB of files stand in for 5 GB of reference gradients.
 
 Why a fixture: the fp32 CPU oracle (oracle/llama_oracle.py) on BASELINE config A's batch (B = 8, S = 2048, full 1B model) takes 219 s of
 the GPU box's 16 host cores — more than half of the `pytest -m gpu` limit for one test.  The oracle side of that test now runs ONCE, by
@@ -10,13 +10,41 @@ any two tensors, ||sketch(a) - sketch(b)||^2 is an unbiased estimate of ||a - b|
 so `sketch_rel_error` reproduces the tests' per-parameter relative gradient error ||g - g_ref|| / ||g_ref|| to a few percent of itself."""
 import copy
 import hashlib
+import os
 
+import numpy as np
 import torch
 
 SKETCH_BUCKETS = 4096
 WEIGHT_SEED = 2024
 BATCH_SEED = 42_831
 NAMED = ("tok_embeddings.weight", "layers.0.attn.q_proj.weight", "layers.7.attn.k_proj.weight", "layers.15.mlp.w2.weight", "norm.scale")
+# The config-A fixture is config_a.npz plus its 146 x 4096 float32 sketches in row blocks of their own (config_a_sketches_<i>.npz): every
+# committed file stays under 1 MiB.
+SKETCH_PARTS = 3
+
+
+def _sketch_part_paths(path):
+    stem = os.path.splitext(path)[0]
+    return [f"{stem}_sketches_{i}.npz" for i in range(SKETCH_PARTS)]
+
+
+def save_config_a(path, sketches, **arrays):
+    np.savez_compressed(path, **arrays)
+    for part, rows in zip(_sketch_part_paths(path), np.array_split(sketches, SKETCH_PARTS)):
+        np.savez_compressed(part, sketches=rows)
+
+
+def load_config_a(path) -> dict:
+    """Every array of the fixture, the sketches joined again: one dict, as if the fixture were one file."""
+    with np.load(path) as g:
+        out = {k: g[k] for k in g.files}
+    parts = []
+    for part in _sketch_part_paths(path):
+        with np.load(part) as g:
+            parts.append(g["sketches"])
+    out["sketches"] = np.concatenate(parts)
+    return out
 
 
 def full_config(n_dsus=5000):

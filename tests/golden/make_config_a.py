@@ -9,7 +9,7 @@ Needs ~60 GB of host memory and ~4 minutes on 16 cores: run it on the GPU box's 
 
     gpurun -- 'python tests/golden/make_config_a.py --out gpurun_out/config_a.npz'
 
-and copy the result to tests/golden/.  tests/test_oracle_golden.py re-derives the recipe's digests on the CPU and checks the sketch
+and copy the result (config_a.npz and its config_a_sketches_<i>.npz parts) to tests/golden/.  tests/test_oracle_golden.py re-derives the recipe's digests on the CPU and checks the sketch
 arithmetic at a reduced size, so the fixture cannot drift from the code that reads it."""
 import argparse
 import os
@@ -73,14 +73,14 @@ def main():
     secs = time.time() - t1
     print(f"oracle: {secs:.0f} s, loss {fx['loss']:.6f}", flush=True)
     first = next(iter(sd))
-    np.savez_compressed(
+    fr.save_config_a(
         args.out, loss=fx["loss"], n_unshifted=fx["n_unshifted"], n_shifted=fx["n_shifted"], names=np.asarray(fx["names"]), norms=fx["norms"],
         sketches=fx["sketches"], **{"head/" + k: v for k, v in fx["heads"].items()},
         recipe_n_dsus=n_dsus, recipe_B=B, recipe_S=S, recipe_weight_seed=fr.WEIGHT_SEED, recipe_batch_seed=fr.BATCH_SEED,
         recipe_vocab=params["vocab_size"], recipe_first_tensor=first, digest_first_tensor_rows=fr.digest(sd[first][:64]),
         digest_tokens=fr.digest(batch["tokens"]), digest_labels=fr.digest(batch["labels"]), sketch_buckets=fr.SKETCH_BUCKETS,
         oracle_seconds=secs, oracle_threads=torch.get_num_threads(), torch_version=torch.__version__)
-    print(f"wrote {args.out} ({os.path.getsize(args.out) / 1e6:.1f} MB)")
+    print(f"wrote {args.out} and its sketch parts")
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 """GPU, >= 2 devices: the data-parallel step over RCCL (torch.distributed backend "nccl") — per-bucket all-reduce on a side stream
 during backward, scalar communicator, deferred embedding bucket, dynamic GEMM tile order — equals the single-process step over the
 union of the micro-batches.  Skipped on a one-GPU box (the driver's test box has one GPU); the same worker is rehearsed there by hand
-with two ranks sharing the GPU over gloo (see tests/workers/dp_step_worker.py)."""
+with two ranks sharing the GPU over gloo (see tests/workers/dp_step_worker.py).  Every rank is a fresh Python process started through
+subprocess, so the tests run the same whether or not an earlier test of the session has already opened the GPU in this one."""
 import json
 import os
 import socket
@@ -20,8 +21,6 @@ def test_rccl_step_on_every_gpu_equals_single_process_step(tmp_path):
     n_ranks = min(torch.cuda.device_count(), 8)  # every GPU of the node: the first multi-GPU box exercises the 8-rank communicator
     if n_ranks < 2:   # device_count() does not initialise the GPU
         pytest.skip("needs >= 2 GPUs")
-    if torch.cuda.is_initialized():
-        pytest.skip("this process already holds the GPU: ranks must be started from a process that has not touched it")
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
@@ -45,8 +44,6 @@ def test_single_rank_rccl_exchange_equals_the_plain_step(tmp_path):
     ordering and the protocol against the real library."""
     if torch.cuda.device_count() < 1:
         pytest.skip("needs a GPU")
-    if torch.cuda.is_initialized():
-        pytest.skip("this process already holds the GPU: the rank must be started from a process that has not touched it")
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
@@ -70,8 +67,6 @@ def test_single_rank_rccl_trainer_equals_the_plain_trainer(tmp_path, clip):
     same weights, bit for bit."""
     if torch.cuda.device_count() < 1:
         pytest.skip("needs a GPU")
-    if torch.cuda.is_initialized():
-        pytest.skip("this process already holds the GPU: the rank must be started from a process that has not touched it")
     worker = os.path.join(ROOT, "tests", "workers", "dp_trainer_worker.py")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("SSI_DIST_BACKEND", "SSI_LOCAL_DEVICE", "SSI_DP_SINGLE", "WORLD_SIZE", "RANK", "LOCAL_RANK"):

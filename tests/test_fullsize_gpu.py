@@ -180,10 +180,9 @@ def test_full_size_model_matches_the_cpu_oracle_at_config_a_through_the_committe
     named parameters.  The recipe's digests are re-derived first, so the file and the inputs built here cannot drift apart."""
     import os
 
-    import numpy as np
     import fullsize_recipe as fr
     from ssi.data import synthetic_batch
-    g = np.load(os.path.join(golden_dir, "config_a.npz"))
+    g = fr.load_config_a(os.path.join(golden_dir, "config_a.npz"))
     n_dsus, B, S = int(g["recipe_n_dsus"]), int(g["recipe_B"]), int(g["recipe_S"])
     assert (n_dsus, B, S) == (5000, 8, 2048) and int(g["recipe_weight_seed"]) == fr.WEIGHT_SEED and int(g["sketch_buckets"]) == fr.SKETCH_BUCKETS
     params = _full_config(n_dsus).parameters
