@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 8 /* 8: + ssi_ce_fwd_weighted (per-row loss weights: an accumulation window run as ONE batch keeps the reference's
+#define SSI_ABI_VERSION 9 /* 9: ssi_adamw_step takes its hyper-parameters in double (the coefficients of torch's fused AdamW)
+                           * 8: + ssi_ce_fwd_weighted (per-row loss weights: an accumulation window run as ONE batch keeps the reference's
                            *    per-micro-batch normalisation, ssi/data/window.py)
                            * 7: + ssi_set_attn_impl, ssi_attn_last_dispatch (no getenv on the launch path), ssi_attn_plan_* and ssi_attn_varlen_bwd_plan
                            *    (packed rows on the pipelined backward kernels, host-built work plan)
@@ -286,13 +287,14 @@ int ssi_scale_inplace(void* x, int64_t n, float scale, const float* scale_dev, i
 /* out[0] = sum(x^2) in fp32, deterministic two-stage; workspace >= ssi_sumsq_workspace_bytes(n) */
 int64_t ssi_sumsq_workspace_bytes(int64_t n);
 int ssi_sumsq(const void* x, int64_t n, int dtype, float* out, void* workspace, int64_t workspace_bytes, void* stream);
-/* Decoupled-weight-decay Adam on flat buffers, fp32 op-math, one rounding on store (torch fused AdamW semantics):
- *   g = grad * (grad_scale_dev ? *grad_scale_dev : 1);  p -= lr*wd*p;  m = m + (1-b1)(g-m);  v = b2 v + (1-b2) g g;
+/* Decoupled-weight-decay Adam on flat buffers, fp32 op-math, one rounding on store (torch fused AdamW semantics; the coefficients 1-lr*wd,
+ * 1-b1, b2, 1-b2, lr/bc1, 1/sqrt(bc2) computed in double, then rounded to fp32, as torch does):
+ *   g = grad * (grad_scale_dev ? *grad_scale_dev : 1);  p *= 1-lr*wd;  m = m + (1-b1)(g-m);  v = b2 v + (1-b2) g g;
  *   p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps),  bc1 = 1-b1^step, bc2 = 1-b2^step.  zero_grad bit 0: grad <- 0; bit 1 (ABI v7): the
  *   launch changes nothing when *grad_scale_dev is inf or NaN (1 / 0 label tokens of an accumulation window: the reference skips that window's
  *   optimizer step, ssi/trainer.py:399-403; an update issued before the host has read the count back skips by itself). */
-int ssi_adamw_step(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, float lr, float beta1,
-                   float beta2, float eps, float weight_decay, int64_t step, const float* grad_scale_dev, int zero_grad,
+int ssi_adamw_step(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, double lr, double beta1,
+                   double beta2, double eps, double weight_decay, int64_t step, const float* grad_scale_dev, int zero_grad,
                    int dtype, void* stream);
 
 #ifdef __cplusplus

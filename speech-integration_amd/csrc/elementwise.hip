@@ -599,8 +599,8 @@ extern "C" int ssi_sumsq(const void* x, int64_t n, int dtype, float* out, void* 
 
 template <typename T>
 __global__ __launch_bounds__(256) void adamw_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ m,
-                                                    T* __restrict__ v, int64_t n, float lr, float beta1, float beta2,
-                                                    float eps, float wd, float step_size, float inv_bc2_sqrt,
+                                                    T* __restrict__ v, int64_t n, float decay, float w1, float beta2,
+                                                    float w2, float eps, float step_size, float inv_bc2_sqrt,
                                                     const float* __restrict__ grad_scale_dev, int zero_grad) {
     constexpr int N = Vec16<T>::N;
     const float gs = grad_scale_dev ? *grad_scale_dev : 1.f;
@@ -613,9 +613,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(T* __restrict__ p, T* __rest
         for (int k = 0; k < N; ++k) {
             const float gr = gg.get(k) * gs;
             float pf = pp.get(k);
-            pf -= lr * wd * pf;
-            const float mf = mm.get(k) + (1.f - beta1) * (gr - mm.get(k));
-            const float vf = beta2 * vv.get(k) + (1.f - beta2) * gr * gr;
+            pf *= decay;
+            const float mf = mm.get(k) + w1 * (gr - mm.get(k));
+            const float vf = beta2 * vv.get(k) + w2 * gr * gr;
             const float denom = sqrtf(vf) * inv_bc2_sqrt + eps;
             pf -= step_size * mf / denom;
             pp.set(k, pf); mm.set(k, mf); vv.set(k, vf);
@@ -628,31 +628,35 @@ __global__ __launch_bounds__(256) void adamw_kernel(T* __restrict__ p, T* __rest
         const int64_t i = nvec * N + threadIdx.x;
         const float gr = to_f32<T>(g[i]) * gs;
         float pf = to_f32<T>(p[i]);
-        pf -= lr * wd * pf;
-        const float mf = to_f32<T>(m[i]) + (1.f - beta1) * (gr - to_f32<T>(m[i]));
-        const float vf = beta2 * to_f32<T>(v[i]) + (1.f - beta2) * gr * gr;
+        pf *= decay;
+        const float mf = to_f32<T>(m[i]) + w1 * (gr - to_f32<T>(m[i]));
+        const float vf = beta2 * to_f32<T>(v[i]) + w2 * gr * gr;
         pf -= step_size * mf / (sqrtf(vf) * inv_bc2_sqrt + eps);
         p[i] = from_f32<T>(pf); m[i] = from_f32<T>(mf); v[i] = from_f32<T>(vf);
         if (zero_grad) g[i] = from_f32<T>(0.f);
     }
 }
 
-extern "C" int ssi_adamw_step(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, float lr, float beta1,
-                              float beta2, float eps, float weight_decay, int64_t step, const float* grad_scale_dev,
+extern "C" int ssi_adamw_step(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, double lr, double beta1,
+                              double beta2, double eps, double weight_decay, int64_t step, const float* grad_scale_dev,
                               int zero_grad, int dtype, void* stream) {
     SSI_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n >= 0 && step >= 1);
     SSI_CHECK_ARG(((uintptr_t)param % 16) == 0 && ((uintptr_t)grad % 16) == 0 && ((uintptr_t)exp_avg % 16) == 0 &&
                   ((uintptr_t)exp_avg_sq % 16) == 0);
     if (n == 0) return SSI_OK;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    const float step_size = (float)((double)lr / bc1);
+    // every coefficient in double from the double hyper-parameters, then rounded once to fp32, as torch's fused AdamW does: 1 - (float)0.999
+    // is 1.3e-5 away from (float)(1 - 0.999), which moved ~0.5 % of the bf16 exp_avg_sq (and, through the cancellations of m, ~4 % of the
+    // exp_avg) a bf16 step away from the reference's within 7 steps
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const float step_size = (float)(lr / bc1);
     const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
     // 17 GB touched once: non-temporal accesses and as many short blocks as there are 16-byte vectors (no grid-stride loop at the model's
     // size: 608 k blocks).  tools/adamw_bench.py, 1.246 G bf16 parameters: 8192 long-lived blocks 5.5 TB/s, 32768 6.2, 131072 6.3, one vector
     // per thread 6.47 TB/s (2.70 ms); two vectors per thread with all eight loads in flight first: 6.1
     SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(adamw_kernel<T>, dim3(stream_grid(n / Vec16<T>::N + 1, 1 << 20)), dim3(256), 0,
                                                  (hipStream_t)stream, (T*)param, (T*)grad, (T*)exp_avg, (T*)exp_avg_sq, n,
-                                                 lr, beta1, beta2, eps, weight_decay, step_size, inv_bc2_sqrt,
+                                                 (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2,
+                                                 (float)(1.0 - beta2), (float)eps, step_size, inv_bc2_sqrt,
                                                  grad_scale_dev, zero_grad));
     SSI_LAUNCH_CHECK();
     return SSI_OK;

@@ -307,3 +307,28 @@ def test_host_threads_are_kept_within_the_cpu_share(monkeypatch):
         assert train_utils.limit_host_threads() == 6 and train_utils.usable_cpus() == 256
     finally:
         torch.set_num_threads(before)
+
+
+# ---- the bf16 distance of the optimizer parity tests (tests/bf16_dist.py) ----------------------------------------------
+def test_bf16_distance_on_hand_made_pairs():
+    from bf16_dist import bf16_distance, bf16_spacing
+    b = lambda *v: torch.tensor(v, dtype=torch.float64).to(torch.bfloat16)  # noqa: E731
+    # the grid: 1.0 -> 1 + 2**-7, 0.75 -> 2**-8 (the binade [0.5, 1)), 2**-130 (subnormal) and 0 -> 2**-133
+    assert bf16_spacing(b(1.0, -1.0, 0.75, 1024.0, 0.0, 2.0 ** -130)).tolist() == [2.0 ** -7, 2.0 ** -7, 2.0 ** -8, 8.0, 2.0 ** -133, 2.0 ** -133]
+    assert bf16_distance(b(1.0, -3.5, 0.0), b(1.0, -3.5, 0.0)) == (1.0, 0.0)
+    eq, d = bf16_distance(b(1.0, 2.0, 3.0, 4.0), b(1.0, 2.0, 3.0, 4.0 + 2 ** -5))       # one element one step off (spacing at 4 = 2**-5)
+    assert eq == 0.75 and d == 1.0
+    eq, d = bf16_distance(b(1.0 + 2 ** -6), b(1.0))                                      # two steps
+    assert eq == 0.0 and d == 2.0
+    eq, d = bf16_distance(b(1.0 - 2 ** -8), b(1.0))                                      # one step below 1: half a step of the grid AT 1
+    assert d == 0.5
+    assert bf16_distance(b(-0.0), b(0.0)) == (0.0, 0.0)                                 # equal values, different bits
+    # across zero: 1e-6 and -1e-6 are ~2**9 steps of their own grid apart, one step of an update of lr = 2e-4 rounded to bf16
+    lr = 2e-4
+    x, ref = b(-1e-6, 0.5), b(1e-6, 0.5)
+    assert bf16_distance(x, ref)[1] > 2 ** 8
+    eq, d = bf16_distance(x, ref, floor=lr * 2 ** -7)
+    assert eq == 0.5 and d == pytest.approx(float(ref[0].double() * 2) / (lr * 2 ** -7), rel=1e-12) and d < 2
+    # the floor is per element when it is a tensor, and never refines a grid coarser than itself
+    eq, d = bf16_distance(b(-1e-6, 0.5 + 2 ** -8), b(1e-6, 0.5), floor=torch.tensor([1.0, 1e-9], dtype=torch.float64))
+    assert d == 1.0

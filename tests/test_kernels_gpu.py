@@ -265,34 +265,307 @@ def test_count_tokens_matches_reference_counts(ops):
     assert ct_gpu(empty, r, 0) == {"text": 0, "dsu": 0, "modality": 0, "special_text": 0, "total": 0}
 
 
+ADAMW = dict(lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01)   # the reference's optimizer settings (conf/training.yaml)
+
+
+def _adamw(ops, p, g, m, v, step, gs, **kw):
+    ops.adamw_step(p, g, m, v, lr=ADAMW["lr"], beta1=ADAMW["betas"][0], beta2=ADAMW["betas"][1], eps=ADAMW["eps"],
+                   weight_decay=ADAMW["weight_decay"], step=step, grad_scale_dev=gs, **kw)
+
+
+def _fused_adamw(p0, m0=None, v0=None, step0=0):
+    """The reference's optimizer, torch.optim.AdamW(fused=True), on CPU tensors of p0's dtype; ``m0`` / ``v0``: moments preloaded at step
+    ``step0``."""
+    p = p0.clone().requires_grad_(True)
+    opt = torch.optim.AdamW([p], fused=True, **ADAMW)
+    if m0 is not None:
+        opt.state[p] = {"step": torch.tensor(float(step0)), "exp_avg": m0.clone(), "exp_avg_sq": v0.clone()}
+    return p, opt
+
+
+def _adamw_distances(p, m, v, ref_p, opt, g_max):
+    """bf16_distance of the kernel's p / exp_avg / exp_avg_sq against the fused reference's (floors: see tests/bf16_dist.py; ``g_max``: the
+    largest |scaled gradient| of each element over the steps so far)."""
+    from bf16_dist import bf16_distance
+    st = opt.state[ref_p]
+    return (bf16_distance(p, ref_p, floor=ADAMW["lr"] * 2 ** -7),
+            bf16_distance(m, st["exp_avg"], floor=(1 - ADAMW["betas"][0]) * g_max.double() * 2 ** -7),
+            bf16_distance(v, st["exp_avg_sq"]))
+
+
+def _bf16_grads(n, steps, seed):
+    """A gradient that changes from step to step around a fixed direction (as a training gradient does), bf16, before the 1/tokens scale."""
+    base = rnd(n, seed=seed, scale=50.0)
+    return [(base + rnd(n, seed=seed + 1 + t, scale=25.0)).to(torch.bfloat16) for t in range(steps)]
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_adamw_scale_sumsq(ops, dtype):
-    n = 100_003  # odd tail
-    p0, g0 = rnd(n, seed=15), rnd(n, seed=16, scale=50.0)
-    ref_p = p0.clone().requires_grad_(True)
-    opt = torch.optim.AdamW([ref_p], lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01)
-    p, m, v = p0.to(dtype).to(DEV), torch.zeros(n, dtype=dtype, device=DEV), torch.zeros(n, dtype=dtype, device=DEV)
-    gs = torch.tensor([1 / 50.0], dtype=torch.float32, device=DEV)
-    for step in range(1, 4):
-        gstep = g0 * (1 + 0.1 * step)
-        ref_p.grad = (gstep / 50.0).clone()
-        opt.step()
-        g = gstep.to(dtype).to(DEV)
-        ops.adamw_step(p, g, m, v, lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, step=step, grad_scale_dev=gs, zero_grad=True)
-        assert (g == 0).all()
+    """K13 against torch.optim.AdamW(fused=True) on CPU tensors of the same dtype (the reference's optimizer), with a power-of-two gradient
+    scale: folding the scale into the kernel and rounding g * s first then agree, and so must every step's p, exp_avg and exp_avg_sq."""
     if dtype == torch.float32:
-        torch.testing.assert_close(p.cpu(), ref_p.detach(), rtol=0, atol=2e-6)
-        torch.testing.assert_close(m.cpu(), opt.state[ref_p]["exp_avg"], rtol=1e-4, atol=1e-6)
-        torch.testing.assert_close(v.cpu(), opt.state[ref_p]["exp_avg_sq"], rtol=1e-4, atol=1e-7)
+        n = 100_003  # odd tail
+        p0, g0 = rnd(n, seed=15), rnd(n, seed=16, scale=50.0)
+        ref_p, opt = _fused_adamw(p0)
+        p, m, v = p0.to(DEV), torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)
+        gs = torch.tensor([1 / 50.0], dtype=torch.float32, device=DEV)
+        for step in range(1, 4):
+            gstep = g0 * (1 + 0.1 * step)
+            ref_p.grad = gstep * torch.tensor(1 / 50.0)
+            opt.step()
+            g = gstep.to(DEV)
+            _adamw(ops, p, g, m, v, step, gs, zero_grad=True)
+            assert (g == 0).all()
+        st = opt.state[ref_p]
+        need = {k: float(((a.cpu() - b).abs() - at).clamp_min(0).div(b.abs()).nan_to_num(0.0).max())
+                for k, a, b, at in (("m", m, st["exp_avg"], 1e-6), ("v", v, st["exp_avg_sq"], 1e-7))}
+        print("adamw fp32 vs fused: max |p - p_ref|", float((p.cpu() - ref_p.detach()).abs().max()), "rtol needed at the atol:", need)
+        # measured (MI355X): max |p - p_ref| 7.2e-7; m and v within the atol everywhere (no rtol needed)
+        torch.testing.assert_close(p.cpu(), ref_p.detach(), rtol=0, atol=1.5e-6)
+        torch.testing.assert_close(m.cpu(), st["exp_avg"], rtol=1e-6, atol=1e-6)
+        torch.testing.assert_close(v.cpu(), st["exp_avg_sq"], rtol=1e-6, atol=1e-7)
     else:
-        torch.testing.assert_close(p.cpu().float(), ref_p.detach(), rtol=0, atol=2e-2)
+        n, steps = 1_000_003, 6
+        grads = _bf16_grads(n, steps, seed=20)
+        p0 = rnd(n, seed=19, scale=0.02).to(dtype)
+        ref_p, opt = _fused_adamw(p0)
+        p, m, v = p0.to(DEV), torch.zeros(n, dtype=dtype, device=DEV), torch.zeros(n, dtype=dtype, device=DEV)
+        s = torch.tensor(2.0 ** -6)
+        gs = s.reshape(1).to(DEV)
+        gmax = torch.zeros(n)
+        for step, gb in enumerate(grads, 1):
+            st = opt.state[ref_p]
+            # one step from the reference's own state (its p / m / v before this step): the kernel's arithmetic alone
+            one = [t.detach().to(DEV).clone() for t in (ref_p, st["exp_avg"], st["exp_avg_sq"])] if step > 1 else [p0.to(DEV), m.clone(), v.clone()]
+            ref_p.grad = gb.clone()
+            ref_p.grad *= s          # torchtune scale_grads: p.grad *= scaler, exact for a power of two
+            opt.step()
+            gmax = torch.maximum(gmax, ref_p.grad.float().abs())
+            _adamw(ops, *one[:1], gb.to(DEV), *one[1:], step, gs)
+            _adamw(ops, p, gb.to(DEV), m, v, step, gs)
+            d1 = _adamw_distances(*one, ref_p, opt, gmax)
+            (eqp, dp), (eqm, dm), (eqv, dv) = _adamw_distances(p, m, v, ref_p, opt, gmax)
+            print(f"adamw bf16 exact scale, step {step}: bit-equal p {eqp:.6f} m {eqm:.6f} v {eqv:.6f}; steps p {dp:.3g} m {dm:.3g} v {dv:.3g}; "
+                  f"one step from the reference's state {d1}")
+            # measured (MI355X, 1 M elements, steps 1..6): one step from the same state: >= 99.995 % bit-equal, at most 1 step (m: 100 %).  Along
+            # the whole trajectory p >= 99.996 %, m 100 %, v >= 99.987 % (1 step); p up to 2.75 steps at step 6, on small weights where the unit
+            # is the floor lr * 2**-7: one-step differences carried and met again.  Bounds: the issue's 99.9 %, 2 x the trajectory's p distance
+            assert all(d <= 1.0 and eq >= 0.9999 for eq, d in d1), (step, d1)
+            assert dp <= 5.5 and dm <= 1.0 and dv <= 1.0, (step, dp, dm, dv)
+            assert min(eqp, eqm, eqv) >= 0.999, (step, eqp, eqm, eqv)
     x = rnd(n, dtype=dtype, seed=17)
     out = torch.empty(1, dtype=torch.float32, device=DEV)
     ops.sumsq(x.to(DEV), out)
-    assert out.item() == pytest.approx(float(x.float().pow(2).sum()), rel=1e-5)
+    assert out.item() == pytest.approx(float(x.double().pow(2).sum()), rel=1e-5)
     xs = x.to(DEV)
     ops.scale_(xs, 0.5, torch.tensor([4.0], device=DEV))
     torch.testing.assert_close(xs.cpu().float(), (x.float() * 2.0).to(dtype).float(), rtol=0, atol=0)
+
+
+def test_adamw_bf16_in_the_reference_order(ops):
+    """The reference rounds g * (1 / tokens) to bf16 (``p.grad *= s``) and then steps; K13 multiplies in fp32 inside the update (the fold of
+    scale_grads into the optimizer).  With a scale that is no power of two the two differ: bounded here by the measured distance, and the fold
+    is shown to be no further than the reference from an fp64 AdamW on the unrounded scaled gradient (the fold)."""
+    from bf16_dist import bf16_distance
+    n, steps = 1_000_003, 7
+    grads = _bf16_grads(n, steps, seed=30)
+    p0 = rnd(n, seed=29, scale=0.02).to(torch.bfloat16)
+    ref_p, opt = _fused_adamw(p0)
+    p, m, v = p0.to(DEV), torch.zeros(n, dtype=torch.bfloat16, device=DEV), torch.zeros(n, dtype=torch.bfloat16, device=DEV)
+    s = torch.tensor(1 / 3001)
+    gs = s.reshape(1).to(DEV)
+    b1, b2 = ADAMW["betas"]
+    lr, wd, eps = ADAMW["lr"], ADAMW["weight_decay"], ADAMW["eps"]
+    p64, m64, v64 = p0.double(), torch.zeros(n, dtype=torch.float64), torch.zeros(n, dtype=torch.float64)
+    gmax = torch.zeros(n)
+    for step, gb in enumerate(grads, 1):
+        ref_p.grad = gb.clone()
+        ref_p.grad *= s
+        opt.step()
+        gmax = torch.maximum(gmax, ref_p.grad.float().abs())
+        _adamw(ops, p, gb.to(DEV), m, v, step, gs)
+        g64 = gb.double() * float(s)
+        p64 *= 1 - lr * wd
+        m64 = b1 * m64 + (1 - b1) * g64
+        v64 = b2 * v64 + (1 - b2) * g64 * g64
+        p64 -= lr / (1 - b1 ** step) * m64 / (v64.sqrt() / math.sqrt(1 - b2 ** step) + eps)
+    (eqp, dp), (eqm, dm), (eqv, dv) = _adamw_distances(p, m, v, ref_p, opt, gmax)
+    print(f"adamw bf16, scale 1/3001, after {steps} steps: bit-equal p {eqp:.6f} m {eqm:.6f} v {eqv:.6f}; steps p {dp:.3g} m {dm:.3g} v {dv:.3g}")
+    st = opt.state[ref_p]
+    err = {}
+    for name, k, r, x64 in (("p", p, ref_p.detach(), p64), ("m", m, st["exp_avg"], m64), ("v", v, st["exp_avg_sq"], v64)):
+        err[name] = (float((k.cpu().double() - x64).norm() / x64.norm()), float((r.double() - x64).norm() / x64.norm()))
+    print("adamw bf16, scale 1/3001: relative L2 distance from fp64 AdamW (kernel, reference):", err)
+    # measured (MI355X, 1 M elements, 7 steps): bit-equal p 95.62 %, m 72.78 %, v 65.42 %; at most 10 steps in p (small weights, where the
+    # floor lr * 2**-7 is the unit: each step's one-step differences of m and v move the update by ~1 % of lr), 3.2 in m, 4 in v.  Bounds:
+    # 2 x the measured mismatch fractions and distances
+    assert eqp >= 0.912 and eqm >= 0.455 and eqv >= 0.308, (eqp, eqm, eqv)
+    assert dp <= 20.0 and dm <= 6.5 and dv <= 8.0, (dp, dm, dv)
+    # relative L2 distance from fp64, measured (kernel vs reference): p 8.70289e-3 vs 8.70356e-3, m 2.6182e-3 vs 2.7267e-3, v 2.7974e-3 vs 3.1270e-3
+    for name, (k, r) in err.items():
+        assert k <= r, (name, k, r)   # the fold rounds once where the reference rounds twice
+
+
+def test_adamw_bf16_at_step_1000(ops):
+    """Steps 1000 and 1001 from realistic moments (bias corrections far from their first-step values), preloaded on both sides."""
+    n = 1_000_003
+    g1, g2 = _bf16_grads(n, 2, seed=40)
+    s = torch.tensor(2.0 ** -6)
+    gtyp = 50.0 * s.item()
+    p0 = rnd(n, seed=43, scale=0.02).to(torch.bfloat16)
+    m0 = rnd(n, seed=44, scale=0.3 * gtyp).to(torch.bfloat16)
+    v0 = (rnd(n, seed=45, scale=gtyp).abs() + 0.05 * gtyp).square().to(torch.bfloat16)
+    ref_p, opt = _fused_adamw(p0, m0, v0, step0=999)
+    p, m, v = p0.to(DEV), m0.to(DEV), v0.to(DEV)
+    for step, gb in ((1000, g1), (1001, g2)):
+        ref_p.grad = gb.clone()
+        ref_p.grad *= s
+        opt.step()
+        assert float(opt.state[ref_p]["step"]) == step
+        _adamw(ops, p, gb.to(DEV), m, v, step, s.reshape(1).to(DEV))
+        (eqp, dp), (eqm, dm), (eqv, dv) = _adamw_distances(p, m, v, ref_p, opt, torch.maximum(ref_p.grad.float().abs(), m0.float().abs() * 10))
+        print(f"adamw bf16 step {step}: bit-equal p {eqp:.6f} m {eqm:.6f} v {eqv:.6f}; steps p {dp:.3g} m {dm:.3g} v {dv:.3g}")
+        assert max(dp, dm, dv) <= 1.0 and min(eqp, eqm, eqv) >= 0.999, (step, eqp, eqm, eqv, dp, dm, dv)
+    assert not torch.equal(p.cpu(), p0)
+
+
+def _guarded(n, fill, dtype=torch.bfloat16):
+    """``fill`` (n values) at [8, 8 + n) of a buffer of n + 24 guard values (the neighbouring buckets of HipAdamW's flat buffer); 16-B aligned."""
+    buf = rnd(n + 24, seed=n % 1000 + 50, scale=3.0).to(dtype)
+    buf[8:8 + n] = fill
+    return buf.to(DEV)
+
+
+@pytest.mark.parametrize("n", [1, 7, 8, 9, 100_003])
+def test_adamw_tails_and_bucket_slices(ops, n):
+    """A slice buf[8:8+n] of a larger buffer, as HipAdamW updates each bucket: the n elements (all tail for n < 8, exactly one vector for 8,
+    a vector and a tail of 1 for 9) follow the fused reference, the guards on both sides stay bit-identical."""
+    from bf16_dist import bf16_distance
+    grads = _bf16_grads(n, 2, seed=60)
+    p0 = rnd(n, seed=61, scale=0.02).to(torch.bfloat16)
+    ref_p, opt = _fused_adamw(p0)
+    bufs = [_guarded(n, x) for x in (p0, grads[0], torch.zeros(n), torch.zeros(n))]
+    before = [b.clone() for b in bufs]
+    p, g, m, v = (b[8:8 + n] for b in bufs)
+    s = torch.tensor(2.0 ** -6)
+    for step, gb in enumerate(grads, 1):
+        g.copy_(gb.to(DEV))
+        ref_p.grad = gb.clone()
+        ref_p.grad *= s
+        opt.step()
+        _adamw(ops, p, g, m, v, step, s.reshape(1).to(DEV))
+        for b, b0 in zip(bufs, before):
+            assert torch.equal(b[:8].view(torch.int16), b0[:8].view(torch.int16)) and torch.equal(b[8 + n:].view(torch.int16), b0[8 + n:].view(torch.int16)), "guards"
+        (eqp, dp), (eqm, dm), (eqv, dv) = _adamw_distances(p, m, v, ref_p, opt, ref_p.grad.float().abs())
+        assert max(dp, dm, dv) <= 1.0, (step, dp, dm, dv)
+        if n > 1000:
+            assert min(eqp, eqm, eqv) >= 0.999, (step, eqp, eqm, eqv)
+    assert bf16_distance(p.cpu(), p0)[0] < 0.5   # the weights did move
+    assert torch.equal(g.cpu(), grads[1])  # no zeroing requested: g unchanged
+
+
+def test_adamw_flag_bits(ops):
+    """zero_grad bit 0: g exactly zero inside the range, the neighbours untouched; without it g is unchanged.  Bit 1 (skip_nonfinite_scale) with
+    an inf or NaN scale: p, m, v and g unchanged bit for bit, even with bit 0 set; with a finite scale the update happens."""
+    n = 1003
+    g0 = _bf16_grads(n, 1, seed=70)[0]
+    p0 = rnd(n, seed=71, scale=0.02)
+    m0, v0 = rnd(n, seed=72, scale=0.2), rnd(n, seed=73, scale=0.5).square()
+    mk = lambda: [_guarded(n, x) for x in (p0, g0, m0, v0)]  # noqa: E731
+    bits = lambda t: t.cpu().view(torch.int16)               # noqa: E731
+    s = torch.tensor([2.0 ** -6], device=DEV)
+    bufs = mk()
+    before = [bits(b) for b in bufs]
+    _adamw(ops, *(b[8:8 + n] for b in bufs), 3, s, zero_grad=True)
+    g = bits(bufs[1])
+    assert bool((bufs[1][8:8 + n] == 0).all()) and torch.equal(g[:8], before[1][:8]) and torch.equal(g[8 + n:], before[1][8 + n:])
+    assert not torch.equal(bits(bufs[0]), before[0])
+    bufs = mk()
+    _adamw(ops, *(b[8:8 + n] for b in bufs), 3, s, zero_grad=False)
+    assert torch.equal(bits(bufs[1]), before[1])
+    for bad in (float("inf"), float("-inf"), float("nan")):
+        bufs = mk()
+        _adamw(ops, *(b[8:8 + n] for b in bufs), 3, torch.tensor([bad], device=DEV), zero_grad=True, skip_nonfinite_scale=True)
+        for b, b0 in zip(bufs, before):
+            assert torch.equal(bits(b), b0), bad
+    bufs = mk()
+    _adamw(ops, *(b[8:8 + n] for b in bufs), 3, s, zero_grad=True, skip_nonfinite_scale=True)
+    assert not torch.equal(bits(bufs[0]), before[0]) and bool((bufs[1][8:8 + n] == 0).all())
+
+
+def test_adamw_beyond_2gib_of_offset(ops):
+    """One step over 1.1 G bf16 elements (2.2 GB per buffer, 8.8 GB in all: element offsets past 2**30, byte offsets past 2**31, a tail of 3):
+    three windows — the start, one straddling byte offset 2**31, the end — against the fused reference on their own (AdamW is element-wise)."""
+    n, w = 1_100_000_003, 1 << 20
+    gen = torch.Generator(device=DEV).manual_seed(80)
+    p, g, m, v = (torch.empty(n, dtype=torch.bfloat16, device=DEV) for _ in range(4))
+    chunk = 1 << 27
+    for lo in range(0, n, chunk):
+        hi = min(n, lo + chunk)
+        p[lo:hi] = torch.randn(hi - lo, generator=gen, device=DEV) * 0.02
+        g[lo:hi] = torch.randn(hi - lo, generator=gen, device=DEV) * 50.0
+        m[lo:hi] = torch.randn(hi - lo, generator=gen, device=DEV) * 0.2
+        v[lo:hi] = torch.randn(hi - lo, generator=gen, device=DEV).square() * 0.5 + 0.01
+    windows = [(0, w), ((1 << 30) - w // 2, (1 << 30) + w // 2 + 5), (n - w, n)]
+    saved = [[t[lo:hi].cpu() for t in (p, g, m, v)] for lo, hi in windows]
+    s = torch.tensor(2.0 ** -6)
+    _adamw(ops, p, g, m, v, 5, s.reshape(1).to(DEV))
+    torch.cuda.synchronize()
+    try:
+        for (lo, hi), (p0, g0, m0, v0) in zip(windows, saved):
+            ref_p, opt = _fused_adamw(p0, m0, v0, step0=4)
+            ref_p.grad = g0.clone()
+            ref_p.grad *= s
+            opt.step()
+            (eqp, dp), (eqm, dm), (eqv, dv) = _adamw_distances(p[lo:hi], m[lo:hi], v[lo:hi], ref_p, opt, torch.maximum(ref_p.grad.float().abs(), m0.float().abs() * 10))
+            print(f"adamw 1.1 G, window [{lo}, {hi}): bit-equal p {eqp:.6f} m {eqm:.6f} v {eqv:.6f}; steps p {dp:.3g} m {dm:.3g} v {dv:.3g}")
+            assert max(dp, dm, dv) <= 1.0 and min(eqp, eqm, eqv) >= 0.999, (lo, eqp, eqm, eqv, dp, dm, dv)
+            assert torch.equal(g[lo:hi].cpu(), g0)
+    finally:
+        del p, g, m, v
+        torch.cuda.empty_cache()
+
+
+def test_sumsq_at_the_headline_size(ops):
+    """K12 (the clip norm's sum of squares) over the headline model's flat buffer length + a tail of 5, values of mixed magnitudes
+    (2**-12 .. 2**4 times a normal draw), against an fp64 sum taken chunk by chunk on the device."""
+    n = 1_246_058_496 + 5
+    gen = torch.Generator(device=DEV).manual_seed(90)
+    x = torch.empty(n, dtype=torch.bfloat16, device=DEV)
+    ref = 0.0
+    chunk = 1 << 26
+    try:
+        for lo in range(0, n, chunk):
+            hi = min(n, lo + chunk)
+            c = torch.randn(hi - lo, generator=gen, device=DEV) * torch.exp2(torch.rand(hi - lo, generator=gen, device=DEV) * 16 - 12)
+            x[lo:hi] = c
+            ref += float(x[lo:hi].double().square().sum())
+        out = torch.empty(1, dtype=torch.float32, device=DEV)
+        ops.sumsq(x, out)
+        rel = abs(out.item() - ref) / ref
+        print(f"sumsq 1.246 G: {out.item():.9g} vs fp64 {ref:.9g}, relative {rel:.3g}")
+        assert rel <= 6e-6, rel   # measured (MI355X): 3.1e-6
+    finally:
+        del x
+        torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n", [1, 5, 8, 9])
+def test_sumsq_and_scale_on_tails(ops, dtype, n):
+    """K12 and K11 where the tail path does the work (n < one vector), exactly one vector (8 bf16 / twice 4 fp32), a vector and a tail of 1;
+    ssi_scale_inplace on a slice leaves its neighbours alone."""
+    x = rnd(n, dtype=dtype, seed=100 + n, scale=3.0)
+    out = torch.full((1,), float("nan"), dtype=torch.float32, device=DEV)
+    buf = _guarded(n, x, dtype)
+    ops.sumsq(buf[8:8 + n], out)
+    assert out.item() == pytest.approx(float(x.double().square().sum()), rel=1e-6)
+    before = buf.clone()
+    ops.scale_(buf[8:8 + n], 1 / 3)
+    ops.scale_(buf[8:8 + n], 1.0, torch.tensor([-2.0], device=DEV))
+    want = ((x.float() * torch.tensor(1 / 3)).to(dtype).float() * -2.0).to(dtype)
+    assert torch.equal(buf[8:8 + n].cpu(), want)
+    assert torch.equal(buf[:8], before[:8]) and torch.equal(buf[8 + n:], before[8 + n:])
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -793,9 +1066,10 @@ PLAN_CASES = [
 @pytest.mark.parametrize("fused_rope,split_all", [(False, False), (True, False), (True, True)], ids=["plain-epilogue", "fused-rope", "fused-rope-every-chunk-split"])
 def test_attention_plan_kernels_on_packed_rows(ops, B, S, H, KV, rows, fused_rope, split_all, attn_impl):
     """Round 5: packed rows on the pipelined backward kernels (document-aware forms: attn_bwd_dq2_kernel<0, true>, attn_bwd_dkv2_kernel<true>)
-    from a host-built work plan (ssi_attn_plan_build): against torch SDPA with the dense block mask in fp32, against the plan-less call (the
-    round-1..3 kernels: another order of the fp32 sums), reproducible, the dispatch asserted; with the fused RoPE backward the positions are
-    document-relative (the plan's assumption).  Documents must not leak: perturbing one leaves the others' gradients bit-identical.
+    from a host-built work plan (ssi_attn_plan_build): in every case and mode against fp32 torch SDPA run document by document (the forward's
+    output and lse too; with the fused RoPE backward the SDPA gradients of q and k go through the transpose of the rotation, at
+    document-relative positions, the plan's assumption), against the plan-less call (the round-1..3 kernels: another order of the fp32 sums),
+    reproducible, the dispatch asserted.  Documents must not leak: perturbing one leaves the others' gradients bit-identical.
     ``split_all``: every dK/dV chunk split over the query heads (2 x 2 or 4 x 1 heads alternating; the builder does this to chunks heavier than
     the chip's share per compute unit): fp32 partial sums + the reduction pass, and — with 1 or 2 heads per workgroup — tile counts that are
     no multiple of 4, i.e. the dummy tiles that pad a loop to whole trips."""
@@ -835,11 +1109,14 @@ def test_attention_plan_kernels_on_packed_rows(ops, B, S, H, KV, rows, fused_rop
         assert (used & want) == (want if plan_ is not None else 0), hex(used)
         if plan_ is not None:
             assert bool(used & _lib.ATTN_USED_HEAD_SPLIT) == (plan_.workspace_bytes > 0), hex(used)
+        fwd.append((out.cpu().float(), lse.cpu()))
         return d.cpu().float()
 
+    fwd = []
     prev = ops.set_impl(_lib.IMPL_MFMA)
     try:
         new, new2, old = run(qkv.to(DEV), plan), run(qkv.to(DEV), plan), run(qkv.to(DEV), None)
+        out_new, lse_new = fwd[0]
         n0 = rows[0][0]
         if n0 < S:
             pert = qkv.clone()
@@ -855,12 +1132,64 @@ def test_attention_plan_kernels_on_packed_rows(ops, B, S, H, KV, rows, fused_rop
         assert float((a - b).abs().max()) <= 2.0 ** -7 * float(a.abs().max()), f"{name}: more than a bf16 step apart"
     if n0 < S:
         assert torch.equal(newp[n0:], new[n0:]) and not torch.equal(newp[:n0], new[:n0]), "documents leak into each other"
-    if not fused_rope and B * S <= 8192:
-        qr = qkv.float().clone().requires_grad_(True)
-        _sdpa_block_ref(qr, B, S, H, KV, hd, rows).backward(do.float())
-        scale = float(qr.grad.abs().max())
-        assert float((new - qr.grad).abs().max()) <= 3e-2 * scale
-        assert float((new - qr.grad).norm() / qr.grad.norm()) <= 1.5e-2
+    ref = _plan_reference(qkv, do, B, S, H, KV, hd, rows)
+    torch.testing.assert_close(out_new, ref["out"], rtol=2e-2, atol=2e-2)
+    lse_err = float((lse_new - ref["lse"]).abs().max())
+    torch.testing.assert_close(lse_new, ref["lse"], rtol=0, atol=4e-6)   # measured (MI355X): at most 1.9e-6 (1 x 11520)
+    want = ref["dqkv"]
+    if fused_rope:  # the kernel returns dq / dk in pre-RoPE space: the SDPA gradients through the transpose of the rotation, dV as it is
+        want = _rope_transpose_of_grads(want, table.cpu(), rows, H, KV, hd)
+    scale = float(want.abs().max())
+    rel = {name: float((new[:, lo:hi] - want[:, lo:hi]).norm() / want[:, lo:hi].norm())
+           for name, lo, hi in (("dq", 0, H * hd), ("dk", H * hd, (H + KV) * hd), ("dv", (H + KV) * hd, (H + 2 * KV) * hd))}
+    print(f"plan {B}x{S} {H}/{KV} fused_rope={fused_rope} split_all={split_all}: lse max-abs {lse_err:.3g}, grad max-abs / max "
+          f"{float((new - want).abs().max()) / scale:.3g}, relative L2 {float((new - want).norm() / want.norm()):.3g} {rel}")
+    assert float((new - want).abs().max()) <= 3e-2 * scale
+    assert float((new - want).norm() / want.norm()) <= 1.5e-2
+
+
+_PLAN_REFS = {}
+
+
+def _plan_reference(qkv, do, B, S, H, KV, hd, rows):
+    """fp32 reference of block-causal GQA attention, one causal SDPA call per document (no dense [S, S] mask), cached per case for the three
+    kernel modes: the output, the natural-log logsumexp of the scaled masked scores ([B, H, S], the layout of ``lse``) and d(q, k, v) with
+    respect to the (post-RoPE) inputs."""
+    key = (B, S, H, KV, tuple(tuple(r) for r in rows))
+    if key in _PLAN_REFS:
+        return _PLAN_REFS[key]
+    x = qkv.float().view(B, S, -1).clone().requires_grad_(True)
+    outs, lse = [], torch.empty(B, H, S)
+    for b, lens in enumerate(rows):
+        s0 = 0
+        for n in lens:
+            t = x[b, s0:s0 + n]
+            q = t[:, : H * hd].view(n, H, hd).transpose(0, 1)
+            k = t[:, H * hd:(H + KV) * hd].view(n, KV, hd).transpose(0, 1).repeat_interleave(H // KV, dim=0)
+            v = t[:, (H + KV) * hd:].view(n, KV, hd).transpose(0, 1).repeat_interleave(H // KV, dim=0)
+            outs.append(F.scaled_dot_product_attention(q[None], k[None], v[None], is_causal=True)[0].transpose(0, 1).reshape(n, H * hd))
+            with torch.no_grad():
+                sc = (q @ k.transpose(1, 2)) / math.sqrt(hd)
+                sc.masked_fill_(~torch.ones(n, n, dtype=torch.bool).tril(), float("-inf"))
+                lse[b, :, s0:s0 + n] = torch.logsumexp(sc, dim=-1)
+            s0 += n
+    out = torch.cat(outs)
+    out.backward(do.float())
+    _PLAN_REFS[key] = ref = {"out": out.detach(), "lse": lse.reshape(-1), "dqkv": x.grad.reshape(B * S, -1)}
+    return ref
+
+
+def _rope_transpose_of_grads(dqkv, table, rows, H, KV, hd):
+    """dq / dk mapped through the transpose of the rotation (autograd through the oracle's apply_rope at the document-relative positions: the
+    map is linear, so any z will do); dV unchanged."""
+    from oracle.llama_oracle import apply_rope
+    pos = torch.cat([torch.cat([torch.arange(n) for n in lens]) for lens in rows])
+    res = dqkv.clone()
+    for lo, nh in ((0, H), (H * hd, KV)):
+        g = dqkv[:, lo:lo + nh * hd].reshape(1, -1, nh, hd)
+        z = torch.zeros_like(g, requires_grad=True)
+        res[:, lo:lo + nh * hd] = torch.autograd.grad(apply_rope(z, table, pos), z, grad_outputs=g)[0].reshape(-1, nh * hd)
+    return res
 
 
 @pytest.mark.parametrize("B,S,H,KV", [(2, 2048, 32, 8), (8, 512, 8, 2), (3, 640, 4, 1)])

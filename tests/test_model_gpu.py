@@ -5,6 +5,7 @@ Tolerances (BASELINE.json north_star: loss/logits within 1e-3 relative, fp32):
   fp32 model : loss rel <= 1e-5, logits max-abs <= 1e-4 * max|logit|, gradients rel <= 2e-3 (sum-order differences)
   bf16 model : loss rel <= 1e-2 vs the fp32 oracle (reported), gradients checked by norm to 5e-2
 """
+import math
 import os
 
 import numpy as np
@@ -278,6 +279,73 @@ def test_trainer_three_steps_match_cpu_step_oracle(tmp_path, dtype_name, tol, ra
             # Adam's update is ~lr*sign(g) on the first real step: a near-zero gradient may flip sign with summation order
             assert float(diff.max()) <= 2 * 2 * 1e-3 + 1e-6 and float((diff > 2e-5).float().mean()) < 5e-3, k
     t.cleanup()
+
+
+@pytest.mark.parametrize("max_norm", [None, 1.0], ids=["no-clip", "clip"])
+def test_bf16_optimizer_chain_matches_torch_fused_adamw(max_norm):
+    """scale_grads -> clip_grad_norm_ -> HipAdamW.step on a bf16 HipLlamaDecoder (4 windows of real backward, a LambdaLR warm-up: the lr changes
+    every step) against the reference's chain on bf16 CPU copies of every parameter fed the model's gradients: ``p.grad *= s`` in bf16,
+    torch.nn.utils.clip_grad_norm_ (a bf16 norm, a bf16 coefficient), torch.optim.AdamW(fused=True).  Every parameter and both moments (through
+    ``optimizer.state[p]``) after each step, with tests/bf16_dist.py; the returned norm against the fp64 norm of the scaled gradients.  This pins
+    the flat-buffer views, the step count, ``param_groups`` lr and the fold of the scale and the clip coefficient into the kernel."""
+    from bf16_dist import bf16_distance
+    from oracle import hf_crosscheck as hx
+    from ssi.loss import CEWithChunkedOutputLoss, compute_loss
+    from ssi.optimizer import HipAdamW, clip_grad_norm_, scale_grads
+    model, _, params, _ = _build("small", torch.bfloat16)
+    _, b, s, seed = hx.CASES["small"]
+    hp = [p for _, p in model.named_parameters()]
+    names = [k for k, _ in model.named_parameters()]
+    ref = [p.detach().cpu().clone().requires_grad_(True) for p in hp]
+    hyper = dict(lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01)
+    opt = HipAdamW(model.parameters(), model=model, **hyper)
+    opt.state_dict()  # binds optimizer.state[p] to views of the flat moment buffers (as a checkpoint does)
+    ropt = torch.optim.AdamW(ref, fused=True, **hyper)
+    warm = lambda step: (step + 1) / 4  # noqa: E731
+    sched, rsched = torch.optim.lr_scheduler.LambdaLR(opt, warm), torch.optim.lr_scheduler.LambdaLR(ropt, warm)
+    loss_fn = CEWithChunkedOutputLoss()
+    worst = {"p": [1.0, 0.0], "m": [1.0, 0.0], "v": [1.0, 0.0], "norm": 0.0}
+    gmax = [torch.zeros(p.shape) for p in hp]
+    for w in range(4):
+        batch = hx.seeded_batch(params["vocab_size"], b, s, seed + 100 + w)
+        n = int((batch["labels"] != -100).sum())
+        loss = compute_loss(_to_dev(batch), model, loss_fn)
+        (loss * n).backward()
+        grads = [p.grad.detach().cpu().clone() for p in hp]
+        scale = torch.tensor(1 / n)
+        assert opt.param_groups[0]["lr"] == ropt.param_groups[0]["lr"] == pytest.approx(2e-4 * (w + 1) / 4)
+        scale_grads(model, scale)
+        if max_norm is not None:
+            total = float(clip_grad_norm_(model, max_norm))
+            norm64 = math.sqrt(sum(float((g.double() * float(scale)).square().sum()) for g in grads))
+            worst["norm"] = max(worst["norm"], abs(total - norm64) / norm64)
+            assert norm64 > max_norm   # the clip does clip
+        opt.step()
+        sched.step()
+        opt.zero_grad(set_to_none=True)
+        for r, g in zip(ref, grads):
+            r.grad = g.clone()
+            r.grad *= scale
+        if max_norm is not None:
+            torch.nn.utils.clip_grad_norm_(ref, max_norm)
+        ropt.step()
+        rsched.step()
+        for name, p, r, gm in zip(names, hp, ref, gmax):
+            gm.copy_(torch.maximum(gm, r.grad.float().abs()))
+            st, rst = opt.state[p], ropt.state[r]
+            assert float(st["step"]) == float(rst["step"]) == w + 1
+            for key, x, y, floor in (("p", p, r, hyper["lr"] * 2 ** -7), ("m", st["exp_avg"], rst["exp_avg"], 0.1 * gm.double() * 2 ** -7),
+                                     ("v", st["exp_avg_sq"], rst["exp_avg_sq"], 0.0)):
+                eq, d = bf16_distance(x, y, floor=floor)
+                worst[key] = [min(worst[key][0], eq), max(worst[key][1], d)]
+        ropt.zero_grad()
+    print(f"optimizer chain (max_norm {max_norm}), worst over 4 steps and {len(hp)} parameters: (bit-equal, steps)", worst)
+    # measured (MI355X), worst parameter and step: p 98.97 % bit-equal and 4 steps apart, m 47 % and 3.9 steps, v 37 % and 5 steps (the
+    # scale 1 / tokens is no power of two: the reference rounds g * s, and with clipping g * s * coef, to bf16 first — the fold's deviation,
+    # INTEGRATION.md); the norm 4.7e-8 from fp64.  Bounds: 2 x the measured mismatch and distances
+    assert worst["p"][0] >= 0.98 and worst["p"][1] <= 8.0, worst
+    assert worst["m"][1] <= 8.0 and worst["v"][1] <= 10.0, worst
+    assert worst["norm"] <= 1e-7, worst
 
 
 def itertools_islice(loader, n):
