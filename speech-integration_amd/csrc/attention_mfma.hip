@@ -493,13 +493,10 @@ __global__ __launch_bounds__(64 * ANW, ANW == 8 ? 1 : 2) void attn_bwd_dq_kernel
 
     // -DDQ_STAMP (debug build, tools/dkv_stamps.py dq): cycle totals of wave 0 per phase of a tile, left in the wave's first dq row
 #ifdef DQ_STAMP
-    unsigned long long qs_acc[6] = {0, 0, 0, 0, 0, 0};
-    unsigned long long qs_last = __builtin_readcyclecounter();
-    const unsigned long long qs_begin = qs_last;
+    PhaseStamps<true, 6> qs;
     int qs_tiles = 0;
-#define QSTAMP(i) { const unsigned long long now_ = __builtin_readcyclecounter(); qs_acc[i] += now_ - qs_last; qs_last = now_; }
 #else
-#define QSTAMP(i)
+    PhaseStamps<false, 6> qs;
 #endif
     KvTileDma<SWZ_DUAL, SWZ_ROW> kvdma;
     kvdma.init(kbase, ld, KV * HD, smem, wave, lane);
@@ -513,7 +510,7 @@ __global__ __launch_bounds__(64 * ANW, ANW == 8 ? 1 : 2) void attn_bwd_dq_kernel
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         ring_barrier();  // everybody's pieces landed; the slot of tile t-1 is free again
         if (t + 2 < nt) kvdma.tile(t + 2, ((BUF + 2) % 3) * 16384);
-        QSTAMP(0)  // wait + barrier + the 4 requests of tile t+2
+        qs.tick(0);  // wait + barrier + the 4 requests of tile t+2
         const int k0 = t * 64;
         if (k0 <= q0 + 31 && k0 + 63 >= ds_lo) {
 #ifdef DQ_STAMP
@@ -532,7 +529,7 @@ __global__ __launch_bounds__(64 * ANW, ANW == 8 ? 1 : 2) void attn_bwd_dq_kernel
 #ifdef DQ_STAMP
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #endif
-            QSTAMP(1)  // 16 row-fragment reads landed
+            qs.tick(1);  // 16 row-fragment reads landed
             f32x16 sacc[2], pacc[2];
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
@@ -546,14 +543,14 @@ __global__ __launch_bounds__(64 * ANW, ANW == 8 ? 1 : 2) void attn_bwd_dq_kernel
                     pacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr[kb][ks], dof[ks], pacc[kb], 0, 0, 0);
                 }
             __builtin_amdgcn_sched_barrier(0);
-            QSTAMP(2)  // 16 S / dP MFMAs issued
+            qs.tick(2);  // 16 S / dP MFMAs issued
             bf16x8 ktr[4][2];
 #pragma unroll
             for (int s = 0; s < 4; ++s)
 #pragma unroll
                 for (int db = 0; db < 2; ++db) ktr[s][db] = frag_tr<SWZ_DUAL>(kt, s * 16, db * 32, lane);
             __builtin_amdgcn_sched_barrier(0);
-            QSTAMP(3)  // 16 transposed reads issued
+            qs.tick(3);  // 16 transposed reads issued
             if (k0 + 63 > q0 || k0 < ds_hi) {  // edge tile: keys beyond the query or before its document contribute nothing
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
@@ -570,7 +567,7 @@ __global__ __launch_bounds__(64 * ANW, ANW == 8 ? 1 : 2) void attn_bwd_dq_kernel
 #pragma unroll
                     for (int r = 0; r < 16; ++r) sacc[kb][r] = __builtin_amdgcn_exp2f(sacc[kb][r] * LOG2E) * pacc[kb][r];
             }
-            QSTAMP(4)  // exponentials (includes waiting for S / dP)
+            qs.tick(4);  // exponentials (includes waiting for S / dP)
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const bf16x8 dsf = acc_frag(sacc[s >> 1], s & 1);
@@ -578,7 +575,7 @@ __global__ __launch_bounds__(64 * ANW, ANW == 8 ? 1 : 2) void attn_bwd_dq_kernel
                 for (int db = 0; db < 2; ++db)
                     dq[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ktr[s][db], dsf, dq[db], 0, 0, 0);
             }
-            QSTAMP(5)  // conversions + 8 dQ MFMAs issued
+            qs.tick(5);  // conversions + 8 dQ MFMAs issued
         }
     };
     TRACE_LOOP_BEGIN();
@@ -591,7 +588,7 @@ __global__ __launch_bounds__(64 * ANW, ANW == 8 ? 1 : 2) void attn_bwd_dq_kernel
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (see attn_fwd_kernel)
     bf16_t* drow = dqkv + (row0 + qg) * ld + (int64_t)head * HD;
 #ifdef DQ_STAMP
-    unsigned long long qs_total = __builtin_readcyclecounter() - qs_begin;
+    unsigned long long qs_total = __builtin_readcyclecounter() - qs.begin;
 #endif
     // rope != NULL: the gradient leaves in pre-RoPE space (backward of the rotation fused here, saves a pass over dqkv)
     const float* tb = rope ? rope + (int64_t)(positions ? positions[row0 + qg] : qg) * HD : nullptr;
@@ -610,7 +607,7 @@ __global__ __launch_bounds__(64 * ANW, ANW == 8 ? 1 : 2) void attn_bwd_dq_kernel
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) {
             float* dbg = reinterpret_cast<float*>(drow);
-            for (int i = 0; i < 6; ++i) dbg[i] = (float)qs_acc[i];
+            for (int i = 0; i < 6; ++i) dbg[i] = (float)qs.total[i];
             dbg[6] = (float)qs_total;
             dbg[7] = (float)qs_tiles;
             dbg[8] = (float)(nt - t_first);
@@ -906,12 +903,10 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq2_kernel(const bf16_t* __re
     // -DDQ2_STAMP (debug build, tools/attn_dq_check.py stamps): cycles of wave 0 per phase of an item, summed over the workgroup's items, left
     // in the first floats of its LAST item's first dq row (the lightest block of the group) together with the 100 MHz clock's count
 #ifdef DQ2_STAMP
-    unsigned long long stq_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long stq_last = __builtin_readcyclecounter();
-    const unsigned long long stq_begin = stq_last, stq_rt0 = __builtin_amdgcn_s_memrealtime();
-#define STAMPQ(i) { __builtin_amdgcn_sched_barrier(0); const unsigned long long now_ = __builtin_readcyclecounter(); stq_acc[i] += now_ - stq_last; stq_last = now_; __builtin_amdgcn_sched_barrier(0); }
+    PhaseStamps<true, 7, true> stq;
+    const unsigned long long stq_rt0 = __builtin_amdgcn_s_memrealtime();
 #else
-#define STAMPQ(i) {}
+    PhaseStamps<false, 7, true> stq;
 #endif
     // ---- before the first item: its rows, its lse -------------------------------------------------------------------------------------------
     // the first three key tiles of an item of nt tiles; behind the last tile the last tile is requested again (into a slot nobody reads), so
@@ -945,7 +940,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq2_kernel(const bf16_t* __re
         // everything this wave has asked for is there: the item's rows (asked for an item ago), its first three tiles (asked for in front of
         // the store of the item before), that store
         asm volatile("s_waitcnt vmcnt(0)" ::"v"(lq0), "v"(lq1) : "memory");
-        STAMPQ(0)
+        stq.tick(0);
         bf16x8 oraw[2][4];
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb)
@@ -1022,7 +1017,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq2_kernel(const bf16_t* __re
 #pragma unroll
             for (int db = 0; db < 2; ++db) ktrh[sI][db][0] = ktrh[sI][db][1] = s16x4{0, 0, 0, 0};  // the first period's dQ products add 0 * 0
         ring_cur = 0, ring_nxt = 16384, ring_n2 = 32768;
-        STAMPQ(1)
+        stq.tick(1);
 
         // ---- tile 0 is there for everybody (each wave waited for its own pieces above): row fragments of its first key block, transposed
         // fragments of the same, S^T / dP^T of unit 0
@@ -1038,7 +1033,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq2_kernel(const bf16_t* __re
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
 
-        STAMPQ(2)
+        stq.tick(2);
         int t = icur.t0;
         if constexpr (VARLEN) {
             // ---- packed rows: the document's first tile when it holds keys of the document before (dstart off the 64-row grid) and is not
@@ -1076,7 +1071,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq2_kernel(const bf16_t* __re
             ring_n2 = c;
         }
         MFMA_DRAIN();
-        STAMPQ(3)
+        stq.tick(3);
         // ---- the diagonal tile, masked; no tile behind it.  Written as a second LOOP (of one trip): straight-line code here would be entered
         // from the loop above or around it, the accumulation registers of the two ways in would meet at its entry, and hipcc moves them there.
         // Two loops in sequence keep their registers (as in attn_bwd_dkv2_kernel).
@@ -1093,7 +1088,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq2_kernel(const bf16_t* __re
         for (int i = 0; i < 4; ++i) dq_mfma(U3.par, U3.kb, U3.qb, i);
         __builtin_amdgcn_sched_barrier(0);
         MFMA_DRAIN();
-        STAMPQ(4)
+        stq.tick(4);
         // ---- the store.  Every request of this wave has landed (table rows; the next item's rows; the tiles asked for beyond the last) ...
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         ring_barrier();  // ... and every other wave's pieces of the table rows
@@ -1111,7 +1106,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq2_kernel(const bf16_t* __re
         ring_barrier();
         kv_rows(inxt.r0);
         request_first_tiles(inxt.t0, jn + 1);  // (behind the last item: its own once more — waited for at the end of the kernel)
-        STAMPQ(5)
+        stq.tick(5);
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
             bf16_t* drow = dqkv + (rw0 + qg[qb]) * ld + (int64_t)head * HD;
@@ -1128,14 +1123,14 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq2_kernel(const bf16_t* __re
                     if (mine) *reinterpret_cast<bf16x4*>(drow + db * 32 + 8 * gg + 4 * h) = v;
                 }
         }
-        STAMPQ(6)
+        stq.tick(6);
 #ifdef DQ2_STAMP
         if (it == n_items - 1 && wave == 0) {  // DEBUG BUILD ONLY: overwrites the first floats of the item's first dq row
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (lane == 0) {
                 float* dbg = reinterpret_cast<float*>(dqkv + (rw0 + q0) * ld + (int64_t)head * HD);
-                for (int i = 0; i < 7; ++i) dbg[i] = (float)stq_acc[i];
-                dbg[7] = (float)(__builtin_readcyclecounter() - stq_begin);
+                for (int i = 0; i < 7; ++i) dbg[i] = (float)stq.total[i];
+                dbg[7] = (float)(__builtin_readcyclecounter() - stq.begin);
                 dbg[8] = (float)(__builtin_amdgcn_s_memrealtime() - stq_rt0);
                 dbg[9] = (float)g;
             }
@@ -1257,13 +1252,10 @@ __global__ __launch_bounds__(256, DKV_WAVES) void attn_bwd_dkv_kernel(const bf16
     int cur_qt = 0;  // query tile of the step being computed (steps run in order too)
     // -DDKV_STAMP (debug build, tools/dkv_stamps.py): cycle totals of wave 0 per phase of a step, left in the workgroup's first dq row
 #ifdef DKV_STAMP
-    unsigned long long st_acc[7] = {0, 0, 0, 0, 0, 0, 0};
-    unsigned long long st_last = __builtin_readcyclecounter();
-    const unsigned long long st_begin = st_last;
+    PhaseStamps<true, 6> st;
     int st_steps = 0;
-#define STAMP(i) { const unsigned long long now_ = __builtin_readcyclecounter(); st_acc[i] += now_ - st_last; st_last = now_; }
 #else
-#define STAMP(i)
+    PhaseStamps<false, 6> st;
 #endif
     // one step on ring buffer BUF (compile-time, so every LDS address is a hoisted per-lane base + an immediate)
     auto do_step = [&](int step, auto buf_c) {
@@ -1281,7 +1273,7 @@ __global__ __launch_bounds__(256, DKV_WAVES) void attn_bwd_dkv_kernel(const bf16
             if (step + RING - 2 < n_steps) issue(step + RING - 2);
             if (step + RING - 1 < n_steps) issue(step + RING - 1);
         }
-        STAMP(0)  // wait + barrier + the two requests the barrier made room for
+        st.tick(0);  // wait + barrier + the two requests the barrier made room for
         if (q0 + 31 < key0 || q0 >= de_hi) return;  // wave-uniform: no query of the tile sees any key of this wave
 #ifdef DKV_STAMP
         ++st_steps;
@@ -1305,14 +1297,14 @@ __global__ __launch_bounds__(256, DKV_WAVES) void attn_bwd_dkv_kernel(const bf16
 #ifdef DKV_STAMP
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #endif
-        STAMP(1)  // row constants + fragment reads landed
+        st.tick(1);  // row constants + fragment reads landed
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qfr[ks], kf[ks], sacc, 0, 0, 0);
             pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dfr[ks], vf[ks], pacc, 0, 0, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
-        STAMP(2)  // S / dP MFMAs issued
+        st.tick(2);  // S / dP MFMAs issued
         bf16x8 dtr[2][2], qtr[2][2];
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2)
@@ -1322,7 +1314,7 @@ __global__ __launch_bounds__(256, DKV_WAVES) void attn_bwd_dkv_kernel(const bf16
                 qtr[s2][db] = frag_tr<SWZ_DUAL>(qt, s2 * 16, db * 32, lane);
             }
         __builtin_amdgcn_sched_barrier(0);
-        STAMP(3)  // transposed reads issued
+        st.tick(3);  // transposed reads issued
         if (q0 < key0 + 32 || q0 + 31 >= de_lo) {  // edge tile: keys beyond the query or of an earlier document contribute nothing
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -1340,7 +1332,7 @@ __global__ __launch_bounds__(256, DKV_WAVES) void attn_bwd_dkv_kernel(const bf16
                 pacc[r] *= p;
             }
         }
-        STAMP(4)  // exponentials (includes waiting for S / dP)
+        st.tick(4);  // exponentials (includes waiting for S / dP)
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             const bf16x8 pf = acc_frag(sacc, s2), dsf = acc_frag(pacc, s2);
@@ -1350,7 +1342,7 @@ __global__ __launch_bounds__(256, DKV_WAVES) void attn_bwd_dkv_kernel(const bf16
                 dk[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qtr[s2][db], dsf, dk[db], 0, 0, 0);
             }
         }
-        STAMP(5)  // conversions + dV / dK MFMAs issued
+        st.tick(5);  // conversions + dV / dK MFMAs issued
     };
 #pragma unroll
     for (int i = 0; i < RING - 2; ++i)
@@ -1380,8 +1372,8 @@ __global__ __launch_bounds__(256, DKV_WAVES) void attn_bwd_dkv_kernel(const bf16
 #ifdef DKV_STAMP
     if (lane == 0 && wave == 0) {  // DEBUG BUILD ONLY: overwrites the first floats of the workgroup's first dq row
         float* dbg = reinterpret_cast<float*>(dqkv + (row0 + kgrp * 128) * ld);
-        for (int i = 0; i < 6; ++i) dbg[i] = (float)st_acc[i];
-        dbg[6] = (float)(__builtin_readcyclecounter() - st_begin);
+        for (int i = 0; i < 6; ++i) dbg[i] = (float)st.total[i];
+        dbg[6] = (float)(__builtin_readcyclecounter() - st.begin);
         dbg[7] = (float)st_steps;
         dbg[8] = (float)n_steps;
     }
@@ -1665,24 +1657,14 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv2_kernel(const bf16_t* __r
     // -DDKV2_STAMP (debug build, tools/attn_dkv_check.py stamps): cycle totals of wave 0 per half-period, by kind of tile (with / without the
     // barrier), left in the first floats of the workgroup's first dq row.  The stamp waits for the LDS reads in flight: read shares, not lengths.
 #ifdef DKV2_STAMP
-    unsigned long long st2_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long st2_last = __builtin_readcyclecounter();
-    const unsigned long long st2_begin = st2_last;
-#define STAMP2(i) { __builtin_amdgcn_sched_barrier(0); const unsigned long long now_ = __builtin_readcyclecounter(); st2_acc[i] += now_ - st2_last; st2_last = now_; __builtin_amdgcn_sched_barrier(0); }
+    PhaseStamps<true, 8, true> st2;
 #else
-#define STAMP2(i) {}
+    PhaseStamps<false, 8, true> st2;
 #endif
 #ifdef DKV2_STAMP_GAPS  // debug build: cycles per GAP of the periods of a tile without barrier / requests (wave 0), 32 totals
-    unsigned long long sg_acc[32];
-    for (int i = 0; i < 32; ++i) sg_acc[i] = 0;
-    unsigned long long sg_last = __builtin_readcyclecounter();
-#define STAMPG(i) { __builtin_amdgcn_sched_barrier(0); const unsigned long long now_ = __builtin_readcyclecounter(); sg_acc[i] += now_ - sg_last; sg_last = now_; __builtin_amdgcn_sched_barrier(0); }
-#define STAMPG_RESET() { __builtin_amdgcn_sched_barrier(0); sg_last = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); }
-#define STAMPG_ON 1
+    PhaseStamps<true, 32, true> sg;
 #else
-#define STAMPG_ON 0
-#define STAMPG(i) {}
-#define STAMPG_RESET() {}
+    PhaseStamps<false, 32, true> sg;
 #endif
     // period A of tile t: SM of unit (t, 0);  MFMAs 0-7 = dV / dK of (t-1, 1), 8-15 = S / dP of (t, 1) — the products whose results the vector
     // ALU needs come LAST, so that at most ~1.4 S / dP register sets are live at any time (first-half S / dP put 296 registers in flight and the
@@ -1712,10 +1694,10 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv2_kernel(const bf16_t* __r
             if (m == 9) asm volatile("" ::"v"(rcl));
             if (m == 13) asm volatile("" ::"v"(rcd));
             __builtin_amdgcn_sched_barrier(0);
-            if (m == 7) STAMP2(decltype(sync_c)::value ? 0 : 4)
-            if (STAMPG_ON && !decltype(sync_c)::value && t % 4 == 3) STAMPG(m)
+            if (m == 7) st2.tick(decltype(sync_c)::value ? 0 : 4);
+            if (!decltype(sync_c)::value && t % 4 == 3) sg.tick(m);
         }
-        STAMP2(decltype(sync_c)::value ? 1 : 5)
+        st2.tick(decltype(sync_c)::value ? 1 : 5);
     };
     // period B of tile t: SM of unit (t, 1);  MFMAs 0-7 = dV / dK of (t, 0), 8-15 = S / dP of (t+1, 0);  row constants and row fragments of tile
     // t+1 under the first half (constants first: they are the C operands of MFMAs 8 and 9), the LDS-DMA requests of tiles t+RING-2, t+RING-1
@@ -1746,11 +1728,11 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv2_kernel(const bf16_t* __r
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (m == 7) STAMP2(decltype(issue_c)::value == 0 ? 2 : 6)
-            if (decltype(issue_c)::value == 3) STAMPG(16 + m)
+            if (m == 7) st2.tick(decltype(issue_c)::value == 0 ? 2 : 6);
+            if (decltype(issue_c)::value == 3) sg.tick(16 + m);
         }
-        STAMP2(decltype(issue_c)::value == 0 ? 3 : 7)
-        if (decltype(issue_c)::value == 2) STAMPG_RESET()
+        st2.tick(decltype(issue_c)::value == 0 ? 3 : 7);
+        if (decltype(issue_c)::value == 2) sg.reset();
     };
 
     // ---- prologue ---------------------------------------------------------------------------------------------------------------------------
@@ -1823,7 +1805,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv2_kernel(const bf16_t* __r
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_waitcnt vmcnt(0)" ::: "memory");  // results landed; no request of this wave is left in flight towards LDS
 #ifdef DKV2_STAMP
-    const unsigned long long st2_total = __builtin_readcyclecounter() - st2_begin;
+    const unsigned long long st2_total = __builtin_readcyclecounter() - st2.begin;
 #endif
 
     if constexpr (VARLEN) {
@@ -1870,7 +1852,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv2_kernel(const bf16_t* __r
 #ifdef DKV2_STAMP
     if (wave == 0 && lane == 0) {  // DEBUG BUILD ONLY: overwrites the first floats of the workgroup's first dq row
         float* dbg = reinterpret_cast<float*>(dqkv + (row0 + k0) * ld);
-        for (int i = 0; i < 8; ++i) dbg[i] = (float)st2_acc[i];
+        for (int i = 0; i < 8; ++i) dbg[i] = (float)st2.total[i];
         dbg[8] = (float)st2_total;
         dbg[9] = (float)n_steps;
         dbg[10] = (float)(k0 / 256);
@@ -1879,7 +1861,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv2_kernel(const bf16_t* __r
 #ifdef DKV2_STAMP_GAPS
     if (wave == 0 && lane == 0) {  // DEBUG BUILD ONLY
         float* dbg = reinterpret_cast<float*>(dqkv + (row0 + k0) * ld);
-        for (int i = 0; i < 32; ++i) dbg[i] = (float)sg_acc[i];
+        for (int i = 0; i < 32; ++i) dbg[i] = (float)sg.total[i];
         dbg[32] = (float)n_steps;
     }
 #endif

@@ -143,6 +143,28 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     return t;
 }
 
+// ---- debug-build cycle stamps ------------------------------------------------------------------------------------------
+// Cycle counter per phase of a kernel: tick(i) adds the cycles since the previous tick (or reset) to total[i].  A kernel declares
+// PhaseStamps<true, ...> under its own -D flag and PhaseStamps<false, ...> otherwise: that form is empty, the calls compile to nothing.
+// FENCED: scheduling barriers around each counter read, for the software-pipelined kernels (the read stays in the gap it is written in).
+template <bool ENABLED, int N, bool FENCED = false> struct PhaseStamps {
+    unsigned long long begin = __builtin_readcyclecounter(), last = begin, total[N] = {};
+    __device__ __forceinline__ void reset() {
+        if (FENCED) __builtin_amdgcn_sched_barrier(0);
+        last = __builtin_readcyclecounter();
+        if (FENCED) __builtin_amdgcn_sched_barrier(0);
+    }
+    __device__ __forceinline__ void tick(int i) {
+        const unsigned long long prev = last;
+        reset();
+        total[i] += last - prev;
+    }
+};
+template <int N, bool FENCED> struct PhaseStamps<false, N, FENCED> {
+    __device__ __forceinline__ void reset() {}
+    __device__ __forceinline__ void tick(int) {}
+};
+
 #define SSI_DISPATCH_DTYPE(dtype, ...)                           \
     do {                                                         \
         if ((dtype) == SSI_F32) {                                \

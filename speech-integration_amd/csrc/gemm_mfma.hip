@@ -479,13 +479,11 @@ int launch(int tiles_m, int tiles_n, int64_t K, const void* A, int64_t lda, cons
 //     2/3 of the 8-wave kernel's.  The MFMAs are inline asm with the accumulator tied in place: with the whole AGPR file in
 //     use the builtin form makes the allocator rotate accumulators through copies (hundreds of v_accvgpr moves per K-tile).
 //   * gridDim.x (= CUs) workgroups draw output tiles from a scheduler (per-XCD spans, see below) until none is left; the
-//     order in which tiles are handed out is the XCD-aware grouped order.  The global -> VGPR -> LDS operand stream runs three
-//     K-steps ahead of the MFMAs through two alternating register sets (every load has two full K-steps to land) and does
-//     not stop at tile boundaries: a tile's first operands arrive while the previous tile is still being multiplied.
-//   * One K-step = 8 blocks of 16 MFMAs.  Four fragment slots (4 x 16 rows x 32 k each) rotate so that each block fetches
-//     just the one set the next block is missing; the ds_write / buffer_load of the staging stream are spread one per
-//     ~4 MFMAs (a slot carrying a ds_write_b128 costs ~35 cycles instead of 16, so they must not bunch up); one raw
-//     s_barrier per K-step.  Measured: 2390 cycles per K-step against 2048 of pure MFMA issue.
+//     order in which tiles are handed out is the XCD-aware grouped order.  The HBM -> LDS operand stream (LDS-DMA, see the
+//     main loop below) runs two K-steps ahead of the MFMAs and does not stop at tile boundaries: a tile's first operands
+//     arrive while the previous tile is still being multiplied.
+//   * One K-step = two phases of 64 MFMAs, each on one k-half's fragments held in registers; the ds_reads of the next phase
+//     and the DMA issues ride at fixed MFMA slots (NT4_* below); two raw s_barriers per K-step.
 //   * Epilogue straight from registers: two v_permlane16_swap per tile pair give each lane 8 consecutive bf16 columns
 //     (16-B stores, 64 B per row per instruction); no LDS, so the operand stream keeps running underneath it.
 // Requires K % 128 == 0 and not both `accumulate` and R; other NT calls use the 8-wave kernel above.
@@ -497,7 +495,7 @@ int launch(int tiles_m, int tiles_n, int64_t K, const void* A, int64_t lda, cons
 #ifndef NT4_ST_AUX_BIG  // outputs far larger than the 256 MiB Infinity Cache (gate/up/act of the fused SwiGLU forward, 0.8 GB)
 #define NT4_ST_AUX_BIG 2
 #endif
-// schedule of the LDS-DMA loop (slots = MFMA indices inside a 64-MFMA phase): F1 reads every NT4_RS MFMAs from slot 0, barrier at NT4_BAR,
+// schedule of the main loop (slots = MFMA indices inside a 64-MFMA phase): F1 reads every NT4_RS MFMAs from slot 0, barrier at NT4_BAR,
 // NT4_NA pieces in phase A at NT4_A0 + i * NT4_SA, the other pieces in phase B at 3 + 5 i
 #ifndef NT4_RS
 #define NT4_RS 2
@@ -526,9 +524,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
 // PREV: 0 = C is overwritten, 1 = C += result (accumulate), 2 = C = R + result (residual)
 // SPLITK: a unit of work is (output tile, K-slice); the fp32 partial tile goes to the workspace in the accumulator's own layout
 //      (unit, wave, 16x16 tile, lane: every store is one contiguous KiB) and nt4_splitk_reduce_kernel finishes the tile
-// DMA (k-contiguous operands only): the operand stream goes HBM -> LDS by LDS-DMA (buffer_load ... lds, no staging registers, no
-//      ds_write) two K-steps ahead, and the registers hold a whole K-step of fragments instead (see the DMA main loop below)
-template <bool A_COL, bool B_COL, int EPI, int PREV, bool SPLITK, bool DMA, bool BATCHED = false>
+template <bool A_COL, bool B_COL, int EPI, int PREV, bool SPLITK, bool BATCHED>
 __device__ __forceinline__ void nt4_body(char* smem, int tiles_m, int tiles_n, int64_t K, const bf16_t* __restrict__ A,
                                          int64_t lda, const bf16_t* __restrict__ B, int64_t ldb,
                                          bf16_t* __restrict__ C, int64_t ldc, const bf16_t* __restrict__ R,
@@ -631,7 +627,7 @@ __device__ __forceinline__ void nt4_body(char* smem, int tiles_m, int tiles_n, i
         lnk = k_hi(t) - k_lo(t);
     };
     auto advance = [&]() {
-        if (++lkt == lnk) {  // the fetches run at most 3 K-steps ahead of the MFMAs: this is always the switch to tile `nxt`
+        if (++lkt == lnk) {  // the fetches run at most 2 K-steps ahead of the MFMAs: this is always the switch to tile `nxt`
             lkt = 0;
             if (nxt >= 0) set_load_tile(nxt);  // after the last tile: keep re-fetching valid memory, never consumed
         }
@@ -656,17 +652,9 @@ __device__ __forceinline__ void nt4_body(char* smem, int tiles_m, int tiles_n, i
         }
         return (int)(p * 32 * ldb * 2);
     };
-    const int st_row = (tid >> 3) * 128 + (((tid & 7) ^ ((tid >> 4) & 7)) * 16);
-    const int st_ofsA = A_COL ? tid * 16 : st_row, st_ofsB = B_COL ? tid * 16 : st_row;
-    auto gloadA = [&](u32x4& dst, int p) { dst = __builtin_amdgcn_raw_buffer_load_b128(make_rsrc(baseA + lkt * kstepA), (p & 1) ? offA1 : offA0, pieceA(p), 0); };
-    auto gloadB = [&](u32x4& dst, int p) { dst = __builtin_amdgcn_raw_buffer_load_b128(make_rsrc(baseB + lkt * kstepB), (p & 1) ? offB1 : offB0, pieceB(p), 0); };
-    auto lwriteA = [&](char* tile, int p, const u32x4& v) { *reinterpret_cast<u32x4*>(tile + st_ofsA + p * 4096) = v; };
-    auto lwriteB = [&](char* tile, int p, const u32x4& v) { *reinterpret_cast<u32x4*>(tile + st_ofsB + p * 4096) = v; };
-
-    bf16x8 S0[4], S1[4], S2[4], S3[4];  // fragment slots; roles rotate through one K-step (see body)
     // COL fragments: the address of 16-column group t (0..7) of a wave's operand is (group-0 address) XOR (t << 5) — the
     // swizzle only touches the three chunk bits that t occupies — so one per-lane base per operand serves all 8 groups; the
-    // XOR is redone per read (kept from being hoisted into 16 live registers by the asm in body).
+    // XOR is redone per read (kept from being hoisted into 16 live registers by the asm in dma_body).
     int trA = 0, trB = 0;
     if (A_COL || B_COL) {
         const int i16 = lane & 15, q = i16 >> 2, pp = i16 & 3, k0l = 8 * (lane >> 4) + q;
@@ -683,64 +671,9 @@ __device__ __forceinline__ void nt4_body(char* smem, int tiles_m, int tiles_n, i
         const s16x8 r = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
         return __builtin_bit_cast(bf16x8, r);
     };
-    auto rdA1 = [&](bf16x8& dst, const char* la, int half, int kh, int i) {
-        if (A_COL) dst = rd_tr(la, trA, half * 4 + i, kh);
-        else dst = read_frag<false>(la, wm * NT4_WM + (half * 4 + i) * 16, kh, lane);
-    };
-    auto rdB1 = [&](bf16x8& dst, const char* lb, int half, int kh, int j) {
-        if (B_COL) dst = rd_tr(lb, trB, half * 4 + j, kh);
-        else dst = read_frag<false>(lb, wn * NT4_WN + (half * 4 + j) * 16, kh, lane);
-    };
-    // one block = 16 MFMAs (4 m-tiles of slot a x 4 n-tiles of slot b); extra(q) is issued right after MFMA q and pinned there.
-    // zero_c: the block is the first to touch its 16 accumulator tiles in this output tile (C operand = 0, no zero fill).
-    auto blk = [&](const bf16x8 (&a)[4], int ah, const bf16x8 (&b)[4], int bh, auto zero_c, auto extra) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int i = q >> 2, j = q & 3;
-            if (decltype(zero_c)::value)
-                asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(acc[bh * 4 + j][ah * 4 + i]) : "v"(b[j]), "v"(a[i]));
-            else
-                asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[bh * 4 + j][ah * 4 + i]) : "v"(b[j]), "v"(a[i]));
-            extra(q);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
     using F_ = std::false_type;
-    // entry: S0 = A rows-lo k-lo, S1 = B cols-lo k-lo of this K-step (LDS buffer cur = K-step parity); (xa, xb) hold the next K-step
-    auto body = [&](auto cur_c, u32x4 (&xa)[8], u32x4 (&xb)[8], auto first) {
-        constexpr int cur = decltype(cur_c)::value;
-        if (A_COL) asm volatile("" : "+v"(trA));
-        if (B_COL) asm volatile("" : "+v"(trB));
-        const char* la = tileA(cur);
-        const char* lb = tileB(cur);
-        char* na = tileA(cur ^ 1);
-        char* nb = tileB(cur ^ 1);
-        // staging piece pc (0..7 = A, 8..15 = B) of the next K-step: registers -> idle LDS buffer in block pc/3, slot
-        // 4 + 4*(pc%3); its register is refilled (K-step +3) two slots later
-        auto stg = [&](int b, int q) {
-            if (q < 4 || (q & 1)) return;
-            const int pc = b * 3 + ((q - 4) >> 2);
-            if (pc >= 16) return;
-            if ((q & 3) == 0) {
-                if (pc < 8) lwriteA(na, pc, xa[pc]); else lwriteB(nb, pc - 8, xb[pc - 8]);
-            } else {
-                if (pc < 8) gloadA(xa[pc], pc); else gloadB(xb[pc - 8], pc - 8);
-            }
-        };
-        blk(S0, 0, S1, 0, first, [&](int q) { if (q < 4) rdB1(S2[q], lb, 1, 0, q); else stg(0, q); });
-        blk(S0, 0, S2, 1, first, [&](int q) { if (q < 4) rdA1(S3[q], la, 1, 0, q); else stg(1, q); });
-        blk(S3, 1, S2, 1, first, [&](int q) { if (q < 4) rdA1(S0[q], la, 0, 1, q); else stg(2, q); });
-        blk(S3, 1, S1, 0, first, [&](int q) { if (q < 4) rdB1(S2[q], lb, 0, 1, q); else stg(3, q); });
-        blk(S0, 0, S2, 0, F_{}, [&](int q) { if (q < 4) rdB1(S1[q], lb, 1, 1, q); else stg(4, q); });
-        blk(S0, 0, S1, 1, F_{}, [&](int q) { if (q < 4) rdA1(S3[q], la, 1, 1, q); else stg(5, q); });
-        advance();
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // next K-step visible; every wave has read all of this one
-        blk(S3, 1, S1, 1, F_{}, [&](int q) { if (q < 4) rdA1(S0[q], na, 0, 0, q); });
-        blk(S3, 1, S2, 0, F_{}, [&](int q) { if (q < 4) rdB1(S1[q], nb, 0, 0, q); });
-    };
-    u32x4 ra0[8], rb0[8], ra1[8], rb1[8];
-    // ---- DMA main loop (NT form) ---------------------------------------------------------------------------------------------
-    // LDS: the same two [A | B] buffers and the same swizzled row image as the register-staged path, but filled by LDS-DMA: a
+    // ---- main loop ---------------------------------------------------------------------------------------------------------
+    // LDS: two [A | B] buffers filled by LDS-DMA (buffer_load ... lds: no staging registers, no ds_write).  k-contiguous operand: a
     // piece = one wave-instruction = 8 rows x 128 B, lane-linear in LDS, the 16-byte-chunk swizzle applied to the per-lane SOURCE
     // address.  Per K-step and wave: 128 MFMAs, 32 ds_read_b128, 16 DMA issues, two barriers; nothing else touches a VGPR.
     //   registers : F0 = the 8 A + 8 B fragments of the k-half 0 of this K-step, F1 = those of k-half 1 (128 VGPRs)
@@ -772,7 +705,7 @@ __device__ __forceinline__ void nt4_body(char* smem, int tiles_m, int tiles_n, i
     u32x4 rsA, rsB;  // buffer resources of the K-step being fetched (set once per K-step by dma_src)
     auto dma_src = [&]() { rsA = rsrc_words(baseA + lkt * kstepA); rsB = rsrc_words(baseB + lkt * kstepB); };
     // k-contiguous operand: 8 rows x 128 B per piece, swizzled source chunk (dofA / dofB); k-strided operand: 2 k-rows x 512 B per piece with
-    // the register path's own source offsets (its LDS image is lane-linear already)
+    // the offA* / offB* source offsets (its LDS image is lane-linear already)
     auto dma_go = [&](int d) {
         if (d < 8) asm volatile("buffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(A_COL ? ((d & 1) ? offA1 : offA0) : dofA), "s"(rsA), "s"(pieceA(d)) : "memory");
         else asm volatile("buffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(B_COL ? ((d & 1) ? offB1 : offB0) : dofB), "s"(rsB), "s"(pieceB(d - 8)) : "memory");
@@ -849,46 +782,22 @@ __device__ __forceinline__ void nt4_body(char* smem, int tiles_m, int tiles_n, i
             }
         });
     };
-    if constexpr (DMA) {
-        set_load_tile(cur >= 0 ? cur : 0);
-        if (nk_total == 0) return;
-        dma_src();
-#pragma unroll
-        for (int d = 0; d < 16; ++d) dma(0, d);
-        advance();
-        dma_src();
-#pragma unroll
-        for (int d = 0; d < 16; ++d) dma(1, d);
-        advance();
-        asm volatile("s_waitcnt vmcnt(16)\n\ts_barrier" ::: "memory");  // K-step 0 is in LDS
-#pragma unroll
-        for (int r = 0; r < 8; ++r) F0B[r] = fragB(tileB(0), r, 0);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) F0A[r] = fragA(tileA(0), r, 0);
-        if (cur >= 0 && !dynamic) nxt = receive_tile();
-    } else {
-    auto fetch_step = [&](u32x4 (&xa)[8], u32x4 (&xb)[8]) {
-#pragma unroll
-        for (int p = 0; p < 8; ++p) gloadA(xa[p], p);
-#pragma unroll
-        for (int p = 0; p < 8; ++p) gloadB(xb[p], p);
-        advance();
-    };
     set_load_tile(cur >= 0 ? cur : 0);
     if (nk_total == 0) return;  // (never: keeps the scheduler state below out of a degenerate launch)
-    fetch_step(ra0, rb0);
+    dma_src();
 #pragma unroll
-    for (int p = 0; p < 8; ++p) lwriteA(tileA(0), p, ra0[p]);
+    for (int d = 0; d < 16; ++d) dma(0, d);
+    advance();
+    dma_src();
 #pragma unroll
-    for (int p = 0; p < 8; ++p) lwriteB(tileB(0), p, rb0[p]);
-    fetch_step(ra1, rb1);
-    fetch_step(ra0, rb0);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    for (int d = 0; d < 16; ++d) dma(1, d);
+    advance();
+    asm volatile("s_waitcnt vmcnt(16)\n\ts_barrier" ::: "memory");  // K-step 0 is in LDS
 #pragma unroll
-    for (int q = 0; q < 4; ++q) { rdA1(S0[q], tileA(0), 0, 0, q); rdB1(S1[q], tileB(0), 0, 0, q); }
+    for (int r = 0; r < 8; ++r) F0B[r] = fragB(tileB(0), r, 0);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) F0A[r] = fragA(tileA(0), r, 0);
     if (cur >= 0 && !dynamic) nxt = receive_tile();
-
-    }
     const float al = alpha * (alpha_dev ? *alpha_dev : 1.f);
     const int g = lane >> 4;
     while (cur >= 0) {
@@ -900,20 +809,11 @@ __device__ __forceinline__ void nt4_body(char* smem, int tiles_m, int tiles_n, i
         // the tile after next is requested now and read after the epilogue: the answer is the oldest vector-memory operation in
         // flight, so the counted waits of the K-steps below retire it (asking later would mean waiting for the epilogue's stores)
         if (nxt >= 0) request_tile();
-        if constexpr (DMA) {
-            dma_body(B0_{}, std::true_type{});
+        dma_body(B0_{}, std::true_type{});
+        dma_body(B1_{}, F_{});
+        for (int kt = 2; kt < nk; kt += 2) {
+            dma_body(B0_{}, F_{});
             dma_body(B1_{}, F_{});
-            for (int kt = 2; kt < nk; kt += 2) {
-                dma_body(B0_{}, F_{});
-                dma_body(B1_{}, F_{});
-            }
-        } else {
-            body(B0_{}, ra1, rb1, std::true_type{});
-            body(B1_{}, ra0, rb0, F_{});
-            for (int kt = 2; kt < nk; kt += 2) {
-                body(B0_{}, ra1, rb1, F_{});
-                body(B1_{}, ra0, rb0, F_{});
-            }
         }
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");  // the asm MFMAs are opaque to the hazard recogniser: let the last results land
         // ---- epilogue: acc[j][i] holds C[m = wm*128 + i*16 + (lane&15)][n = wn*128 + j*16 + (lane>>4)*4 + r] -------------
@@ -1143,18 +1043,12 @@ __device__ __forceinline__ void nt4_body(char* smem, int tiles_m, int tiles_n, i
         else epilogue(std::true_type{});
         }
         cur = nxt;
-        if (cur >= 0) nxt = receive_tile();
-        // the first fragments of the next tile (its K-step 0 sits in LDS buffer 0) are read again here rather than kept live
-        // across the epilogue (the DMA path keeps its F0 live: it has no staging registers to make room for)
-        if constexpr (!DMA) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { rdA1(S0[q], tileA(0), 0, 0, q); rdB1(S1[q], tileB(0), 0, 0, q); }
-        }
+        if (cur >= 0) nxt = receive_tile();  // F0 of the next tile's K-step 0 (read in the last phase B) stays live across the epilogue
     }
     // Behind its last tile the fetch cursor kept requesting (valid memory, never consumed): those LDS-DMA requests must have landed before
     // the workgroup ends — its LDS goes to whichever workgroup the CU runs next.  (Also waits for the last epilogue's stores: the kernel's
     // end waits for them anyway.)
-    if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // the last workgroup to get here clears the scheduler slot for the launch that uses it next
     if (dynamic && tid == 0 && atomicAdd(&sched[8], 1) == G - 1) {  // plain stores: nobody reads the slot before this kernel has ended
         volatile int* vs = sched;
@@ -1163,17 +1057,7 @@ __device__ __forceinline__ void nt4_body(char* smem, int tiles_m, int tiles_n, i
     }
 }
 
-template <bool A_COL, bool B_COL, int EPI, int PREV, bool SPLITK = false>
-__global__ __launch_bounds__(NT4_THREADS, 1) void gemm_nt4_kernel(int tiles_m, int tiles_n, int64_t K, const bf16_t* __restrict__ A,
-                                                                  int64_t lda, const bf16_t* __restrict__ B, int64_t ldb,
-                                                                  bf16_t* __restrict__ C, int64_t ldc, const bf16_t* __restrict__ R,
-                                                                  float alpha, const float* __restrict__ alpha_dev, EpiArgs ea, int slot,
-                                                                  int splits, float* __restrict__ slabs) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    nt4_body<A_COL, B_COL, EPI, PREV, SPLITK, false>(smem, tiles_m, tiles_n, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, ea, slot, splits, slabs);
-}
-
-// the LDS-DMA main loop (same tile walk, scheduler and epilogues); BATCHED: several problems of one shape in one launch (EpiArgs::batch)
+// BATCHED: several problems of one shape in one launch (EpiArgs::batch)
 template <bool A_COL, bool B_COL, int EPI, int PREV, bool SPLITK = false, bool BATCHED = false>
 __global__ __launch_bounds__(NT4_THREADS, 1) void gemm_nt4dma_kernel(int tiles_m, int tiles_n, int64_t K, const bf16_t* __restrict__ A,
                                                                      int64_t lda, const bf16_t* __restrict__ B, int64_t ldb,
@@ -1181,7 +1065,7 @@ __global__ __launch_bounds__(NT4_THREADS, 1) void gemm_nt4dma_kernel(int tiles_m
                                                                      float alpha, const float* __restrict__ alpha_dev, EpiArgs ea, int slot,
                                                                      int splits, float* __restrict__ slabs) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    nt4_body<A_COL, B_COL, EPI, PREV, SPLITK, true, BATCHED>(smem, tiles_m, tiles_n, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, ea, slot, splits, slabs);
+    nt4_body<A_COL, B_COL, EPI, PREV, SPLITK, BATCHED>(smem, tiles_m, tiles_n, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, ea, slot, splits, slabs);
 }
 
 // Finishes split-K tiles: one wave per (output tile, wave of the GEMM workgroup, m-tile i, 64-column duo).  Sums the K-slices'
@@ -1248,15 +1132,12 @@ __global__ __launch_bounds__(256) void nt4_splitk_reduce_kernel(const float* __r
     finish(hi, base + 8 * ldc);
 }
 
-template <bool A_COL, bool B_COL, int EPI, int PREV, bool SPLITK = false, bool DMA = false, bool BATCHED = false>
+template <bool A_COL, bool B_COL, int EPI, int PREV, bool SPLITK = false, bool BATCHED = false>
 int launch_nt4(int tiles_m, int tiles_n, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                const void* R, float alpha, const float* alpha_dev, hipStream_t st, EpiArgs ea = EpiArgs{nullptr, 0, nullptr, 0, 0},
                int splits = 1, float* slabs = nullptr) {
-    void (*kern)(int, int, int64_t, const bf16_t*, int64_t, const bf16_t*, int64_t, bf16_t*, int64_t, const bf16_t*, float, const float*, EpiArgs, int, int,
-                 float*);
-    static_assert(!BATCHED || (DMA && !SPLITK && EPI == EPI_PLAIN), "batched form: LDS-DMA loop, plain epilogue, no split-K");
-    if constexpr (DMA) kern = gemm_nt4dma_kernel<A_COL, B_COL, EPI, PREV, SPLITK, BATCHED>;
-    else kern = gemm_nt4_kernel<A_COL, B_COL, EPI, PREV, SPLITK>;
+    static_assert(!BATCHED || (!SPLITK && EPI == EPI_PLAIN), "batched form: plain epilogue, no split-K");
+    auto kern = gemm_nt4dma_kernel<A_COL, B_COL, EPI, PREV, SPLITK, BATCHED>;
     // one-time set-up per instantiation as C++11 thread-safe statics: the forward thread and autograd's backward thread may both be the
     // first to launch a given form
     static const hipError_t attr_rc = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, NT4_LDS_BYTES);
@@ -1275,22 +1156,21 @@ int launch_nt4(int tiles_m, int tiles_n, int64_t K, const void* A, int64_t lda, 
     return SSI_OK;
 }
 
-// Main loop of the persistent kernel per operand form: 1 = LDS-DMA (default: +7..15 % on every form of the step, profiles/r02_*), 0 = the
-// register-staged loop (kept for A/B builds: -DSSI_NT_DMA=0 -DSSI_NN_DMA=0 -DSSI_TN_DMA=0)
-#ifndef SSI_NT_DMA
-#define SSI_NT_DMA 1
-#endif
-constexpr bool NT_DMA = SSI_NT_DMA != 0;
-#ifndef SSI_NN_DMA
-#define SSI_NN_DMA 1
-#endif
-#ifndef SSI_TN_DMA
-#define SSI_TN_DMA 1
-#endif
-constexpr bool NN_DMA = SSI_NN_DMA != 0, TN_DMA = SSI_TN_DMA != 0;
 bool nt4_ok(int64_t K) { return K % (2 * BK) == 0 && K >= 4 * BK && ssi_get_impl() != SSI_IMPL_MFMA_WG8; }
 // buffer-load offsets are 32-bit: a tile's rows (k-contiguous) or one K-step's k-rows (k-strided) must stay within 2 GiB
 bool nt4_ld_ok(int64_t lda, int64_t ldb) { return 256 * lda * 2 < (1LL << 31) && 256 * ldb * 2 < (1LL << 31); }
+
+// one operand form of ssi_gemm: the persistent kernel where it applies (PREV = accumulate / residual / plain), else the 8-wave kernel
+template <bool A_COL, bool B_COL>
+int gemm_form(int tm, int tn, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const void* R,
+              float alpha, const float* alpha_dev, int accumulate, hipStream_t st) {
+    if (nt4_ok(K) && nt4_ld_ok(lda, ldb) && !(accumulate && R)) {
+        if (accumulate) return launch_nt4<A_COL, B_COL, EPI_PLAIN, 1>(tm, tn, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, st);
+        if (R) return launch_nt4<A_COL, B_COL, EPI_PLAIN, 2>(tm, tn, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, st);
+        return launch_nt4<A_COL, B_COL, EPI_PLAIN, 0>(tm, tn, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, st);
+    }
+    return launch<A_COL, B_COL, false>(tm, tn, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, accumulate, st);
+}
 
 }  // namespace
 
@@ -1312,47 +1192,29 @@ int ssi_gemm_mfma_bf16(int layout, int64_t M, int64_t N, int64_t K, const void* 
                        int accumulate, void* stream) {
     const int tm = (int)(M / BM), tn = (int)(N / BN);
     auto st = (hipStream_t)stream;
-#define GO(AC, BC) return launch<AC, BC, false>(tm, tn, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, accumulate, st)
+#define GO(AC, BC) return gemm_form<AC, BC>(tm, tn, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, accumulate, st)
     switch (layout) {
-        case SSI_GEMM_NT:
-            if (nt4_ok(K) && nt4_ld_ok(lda, ldb) && !(accumulate && R)) {
-                if (accumulate) return launch_nt4<false, false, EPI_PLAIN, 1, false, NT_DMA>(tm, tn, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, st);
-                if (R) return launch_nt4<false, false, EPI_PLAIN, 2, false, NT_DMA>(tm, tn, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, st);
-                return launch_nt4<false, false, EPI_PLAIN, 0, false, NT_DMA>(tm, tn, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, st);
-            }
-            GO(false, false);
-        case SSI_GEMM_NN:
-            if (nt4_ok(K) && nt4_ld_ok(lda, ldb) && !(accumulate && R)) {
-                if (accumulate) return launch_nt4<false, true, EPI_PLAIN, 1, false, NN_DMA>(tm, tn, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, st);
-                if (R) return launch_nt4<false, true, EPI_PLAIN, 2, false, NN_DMA>(tm, tn, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, st);
-                return launch_nt4<false, true, EPI_PLAIN, 0, false, NN_DMA>(tm, tn, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, st);
-            }
-            GO(false, true);
-        case SSI_GEMM_TN:
-            if (nt4_ok(K) && nt4_ld_ok(lda, ldb) && !(accumulate && R)) {
-                if (accumulate) return launch_nt4<true, true, EPI_PLAIN, 1, false, TN_DMA>(tm, tn, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, st);
-                if (R) return launch_nt4<true, true, EPI_PLAIN, 2, false, TN_DMA>(tm, tn, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, st);
-                return launch_nt4<true, true, EPI_PLAIN, 0, false, TN_DMA>(tm, tn, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, st);
-            }
-            GO(true, true);
+        case SSI_GEMM_NT: GO(false, false);
+        case SSI_GEMM_NN: GO(false, true);
+        case SSI_GEMM_TN: GO(true, true);
     }
 #undef GO
     return SSI_ERR_ARG;
 }
 
-// `batch` problems of one shape in one launch of the persistent kernel: the weight-gradient form (TN) on the LDS-DMA loop, no residual;
+// `batch` problems of one shape in one launch of the persistent kernel: the weight-gradient form (TN), no residual;
 // false = not taken, the caller loops over ssi_gemm
 bool ssi_gemm_mfma_bf16_batched(int layout, int batch, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, int64_t bsA, const void* B,
                                 int64_t ldb, int64_t bsB, void* C, int64_t ldc, int64_t bsC, float alpha, const float* alpha_dev, int accumulate,
                                 void* stream, int* rc) {
-    if (layout != SSI_GEMM_TN || !TN_DMA || !nt4_ok(K) || !nt4_ld_ok(lda, ldb) || (bsA | bsB | bsC) % 8 || (M / BM) * (N / BN) * batch > (1LL << 30))
+    if (layout != SSI_GEMM_TN || !nt4_ok(K) || !nt4_ld_ok(lda, ldb) || (bsA | bsB | bsC) % 8 || (M / BM) * (N / BN) * batch > (1LL << 30))
         return false;
     const int tm = (int)(M / BM), tn = (int)(N / BN);
     auto st = (hipStream_t)stream;
     EpiArgs ea{nullptr, 0, nullptr, 0, 0};
     ea.batch = batch; ea.bsA = bsA; ea.bsB = bsB; ea.bsC = bsC;
-    *rc = accumulate ? launch_nt4<true, true, EPI_PLAIN, 1, false, true, true>(tm, tn, K, A, lda, B, ldb, C, ldc, nullptr, alpha, alpha_dev, st, ea)
-                     : launch_nt4<true, true, EPI_PLAIN, 0, false, true, true>(tm, tn, K, A, lda, B, ldb, C, ldc, nullptr, alpha, alpha_dev, st, ea);
+    *rc = accumulate ? launch_nt4<true, true, EPI_PLAIN, 1, false, true>(tm, tn, K, A, lda, B, ldb, C, ldc, nullptr, alpha, alpha_dev, st, ea)
+                     : launch_nt4<true, true, EPI_PLAIN, 0, false, true>(tm, tn, K, A, lda, B, ldb, C, ldc, nullptr, alpha, alpha_dev, st, ea);
     return true;
 }
 
@@ -1368,9 +1230,9 @@ int ssi_gemm_mfma_bf16_splitk(int layout, int64_t M, int64_t N, int64_t K, const
     if (nt4_ok(K) && nt4_ld_ok(lda, ldb) && !(R && accumulate) && K / BK / splits >= 6 && ldc % 8 == 0) {
         const EpiArgs none{nullptr, 0, nullptr, 0, 0};
         int rc = SSI_ERR_ARG;
-        if (layout == SSI_GEMM_TN) rc = launch_nt4<true, true, EPI_PLAIN, 0, true, TN_DMA>(tm, tn, K, A, lda, B, ldb, C, ldc, nullptr, 1.f, nullptr, st, none, splits, slabs);
-        else if (layout == SSI_GEMM_NT) rc = launch_nt4<false, false, EPI_PLAIN, 0, true, NT_DMA>(tm, tn, K, A, lda, B, ldb, C, ldc, nullptr, 1.f, nullptr, st, none, splits, slabs);
-        else if (layout == SSI_GEMM_NN) rc = launch_nt4<false, true, EPI_PLAIN, 0, true, NN_DMA>(tm, tn, K, A, lda, B, ldb, C, ldc, nullptr, 1.f, nullptr, st, none, splits, slabs);
+        if (layout == SSI_GEMM_TN) rc = launch_nt4<true, true, EPI_PLAIN, 0, true>(tm, tn, K, A, lda, B, ldb, C, ldc, nullptr, 1.f, nullptr, st, none, splits, slabs);
+        else if (layout == SSI_GEMM_NT) rc = launch_nt4<false, false, EPI_PLAIN, 0, true>(tm, tn, K, A, lda, B, ldb, C, ldc, nullptr, 1.f, nullptr, st, none, splits, slabs);
+        else if (layout == SSI_GEMM_NN) rc = launch_nt4<false, true, EPI_PLAIN, 0, true>(tm, tn, K, A, lda, B, ldb, C, ldc, nullptr, 1.f, nullptr, st, none, splits, slabs);
         if (rc) return rc;
         hipLaunchKernelGGL(nt4_splitk_reduce_kernel, dim3((unsigned)ssi_cdiv((int64_t)tm * tn * 64, 4)), dim3(256), 0, st, slabs, splits, tm, tn,
                            (bf16_t*)C, ldc, (const bf16_t*)R, alpha, alpha_dev, accumulate);
@@ -1394,7 +1256,7 @@ bool ssi_gemm_rope_mfma(int64_t M, int64_t N, int64_t K, const void* A, int64_t 
     if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) return false;
     EpiArgs ea{nullptr, 0, nullptr, 0, 0};
     ea.rope = rope; ea.pos = positions; ea.seq = seq; ea.rot_cols = rot_cols;
-    *rc = launch_nt4<false, false, EPI_ROPE, 0, false, NT_DMA>((int)(M / BM), (int)(N / BN), K, A, lda, B, ldb, C, ldc, nullptr, 1.f, nullptr,
+    *rc = launch_nt4<false, false, EPI_ROPE, 0, false>((int)(M / BM), (int)(N / BN), K, A, lda, B, ldb, C, ldc, nullptr, 1.f, nullptr,
                                                 (hipStream_t)stream, ea);
     return true;
 }
@@ -1412,7 +1274,7 @@ int ssi_gemm_swiglu_fwd_mfma(int64_t M, int64_t inter, int64_t K, const void* X,
                              void* GU, int64_t ldgu, void* ACT, int64_t ldact, void* stream) {
     EpiArgs ea{(bf16_t*)ACT, ldact, nullptr, 0, inter};
     if (nt4_ok(K))
-        return launch_nt4<false, false, EPI_SWIGLU_FWD, 0, false, NT_DMA>((int)(M / BM), (int)(2 * inter / BN), K, X, ldx, W13, ldw, GU, ldgu, nullptr, 1.f, nullptr,
+        return launch_nt4<false, false, EPI_SWIGLU_FWD, 0, false>((int)(M / BM), (int)(2 * inter / BN), K, X, ldx, W13, ldw, GU, ldgu, nullptr, 1.f, nullptr,
                                              (hipStream_t)stream, ea);
     // output tiles: 256 rows x (128 gate + 128 up) columns -> tiles_n = 2I / 256
     return launch<false, false, false, EPI_SWIGLU_FWD>((int)(M / BM), (int)(2 * inter / BN), K, X, ldx, W13, ldw, GU, ldgu, nullptr, 1.f,
@@ -1426,11 +1288,11 @@ int ssi_gemm_swiglu_bwd_mfma(int layout, int64_t M, int64_t inter, int64_t K, co
     const int tm = (int)(M / BM), tn = (int)(inter / BN);
     if (layout == SSI_GEMM_NN) {
         if (nt4_ok(K) && nt4_ld_ok(lddy, ldw))
-            return launch_nt4<false, true, EPI_SWIGLU_BWD, 0, false, NN_DMA>(tm, tn, K, DY, lddy, W2, ldw, DGU, lddgu, nullptr, 1.f, nullptr, (hipStream_t)stream, ea);
+            return launch_nt4<false, true, EPI_SWIGLU_BWD, 0, false>(tm, tn, K, DY, lddy, W2, ldw, DGU, lddgu, nullptr, 1.f, nullptr, (hipStream_t)stream, ea);
         return SSI_ERR_UNSUPPORTED;
     }
     if (nt4_ok(K) && nt4_ld_ok(lddy, ldw))
-        return launch_nt4<false, false, EPI_SWIGLU_BWD, 0, false, NT_DMA>(tm, tn, K, DY, lddy, W2, ldw, DGU, lddgu, nullptr, 1.f, nullptr, (hipStream_t)stream, ea);
+        return launch_nt4<false, false, EPI_SWIGLU_BWD, 0, false>(tm, tn, K, DY, lddy, W2, ldw, DGU, lddgu, nullptr, 1.f, nullptr, (hipStream_t)stream, ea);
     return launch<false, false, false, EPI_SWIGLU_BWD>(tm, tn, K, DY, lddy, W2, ldw, DGU, lddgu, nullptr, 1.f, nullptr, 0, (hipStream_t)stream, 1,
                                                        nullptr, ea);
 }

@@ -158,11 +158,6 @@ class HipLlamaDecoder(nn.Module):
         self._flat_numel = off
         self._flat = torch.zeros(off, dtype=dtype, device=device)
         self._flat_grad = torch.zeros(off, dtype=dtype, device=device)
-        # [in, out] copies of the weights named by `dgrad_transposed`: their data-gradient GEMMs dX = dY W then run in the
-        # k-contiguous operand form; refreshed lazily after the weights change (one transpose launch per weight per optimizer step)
-        self._wt: dict[str, Tensor] = {}
-        self._wt_key: Optional[tuple] = None
-        self._hip_epoch = 0  # bumped by kernels that modify the weights in place (fused AdamW)
         self._grad_views: dict[str, Tensor] = {}
         # Layers whose attention-projection weight gradients share one batched launch (0 / 1 = every layer on its own, split-K).  8 at the
         # 1B shape: 8 x 64 and 8 x 96 output tiles = 2 and 3 full rounds of the 256 CUs.
@@ -276,64 +271,22 @@ class HipLlamaDecoder(nn.Module):
                     p.copy_(src.to(device=self.device, dtype=self.dtype))
         return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
 
-    # Data gradients dX = dY W run on the untransposed weights (NN form of the persistent GEMM).  `dgrad_transposed` names weights whose
-    # data gradient should instead run in the k-contiguous (NT) form on an [in, out] copy refreshed after every optimizer step: none
-    # by default.  Measured inside the step (profiles/r02_b, bench.py per-class GEMM timing): W13's data gradient takes 0.701 ms as NN
-    # and 0.696 ms as NT, while the 16 transposes cost 0.75 ms — alone on the GPU the NN form looks 17 % slower (913 vs 779 us), but in the
-    # step its A operand has just been written and is served from the Infinity Cache.  SSI_DGRAD_NT=1: copies of every 2-D weight.
-    dgrad_transposed: tuple = {"1": ("emb", "wqkv", "wo", "w13", "w2"), "w13": ("w13",)}.get(os.environ.get("SSI_DGRAD_NT", ""), ())
-
-    @property
-    def transposed_weight_copies(self) -> bool:
-        return len(self.dgrad_transposed) > 0
-
-    @transposed_weight_copies.setter
-    def transposed_weight_copies(self, on: bool) -> None:  # tests: all weights or none
-        self.dgrad_transposed = ("emb", "wqkv", "wo", "w13", "w2") if on else ()
-        self._wt, self._wt_key = {}, None
-
-    def _has_t(self, name: str) -> bool:
-        return name.rsplit(".", 1)[-1] in self.dgrad_transposed and self._mfma_shapes()
-
-    def _view_t(self, name: str) -> Tensor:
-        return self._wt[name]
-
-    def _ensure_transposed(self) -> None:
-        """Refresh the [in, out] copies if any weight changed since the last refresh."""
-        if not self.dgrad_transposed or not self._mfma_shapes():
-            return
-        key = (self._flat._version, self._hip_epoch)
-        if key == self._wt_key:
-            return
-        for name, (o, shape) in self._slices.items():
-            if len(shape) == 2 and self._has_t(name):
-                if name not in self._wt:
-                    self._wt[name] = torch.empty((shape[1], shape[0]), dtype=self.dtype, device=self.device)
-                ops.transpose(self._view(name), self._wt[name])
-        self._wt_key = key
-
     def attach_grads(self) -> None:
         """Point every ``p.grad`` at its slice of the flat gradient buffer (idempotent)."""
         for p, name, rows in self._param_src:
             if p.grad is None:
                 p.grad = self._view(name, rows, self._flat_grad)
 
-    # SSI_ZERO_GRADS=1 (A/B runs): the round-1 protocol — AdamW zeroes the buffer in its pass and every backward accumulates
-    always_accumulate = os.environ.get("SSI_ZERO_GRADS", "0") == "1"
-
     def zero_grad(self, set_to_none: bool = True) -> None:
         """With ``set_to_none`` (torch's default) no memory is touched: the next backward overwrites the buffer.  Only a caller who
         keeps the ``p.grad`` views and wants to read zeros pays for a memset."""
-        if set_to_none and not self.always_accumulate:
+        if set_to_none:
             self._grads_stale = self._grads_stale or self._grads_dirty
             for p, _, _ in self._param_src:
                 p.grad = None
         elif self._grads_dirty or self._grads_stale:
             self._flat_grad.zero_()
             self._grads_stale = False
-        if set_to_none and self.always_accumulate:
-            for p, _, _ in self._param_src:
-                p.grad = None
         self._grads_dirty = False
         self._emb_grad_written = False  # a head backward whose decoder backward never ran (exception in between) leaves it set
         self.pending_grad_scale = None
@@ -346,8 +299,6 @@ class HipLlamaDecoder(nn.Module):
         the model.  Every ``p.grad is None`` therefore opens a new window whatever the flag says — ``torch``'s own meaning of "no
         gradient yet".  Some ``None`` and some not (a caller cleared a subset): those parameters' slices are zeroed and the backward adds,
         which is what autograd's accumulation would give."""
-        if self.always_accumulate:
-            return True
         if not self._grads_dirty:
             return False
         dropped = [(p, name, rows) for p, name, rows in self._param_src if p.grad is None]
@@ -453,31 +404,11 @@ class HipLlamaDecoder(nn.Module):
             return None
         return attn_plan.plan_from_input_pos(input_pos, self.num_heads, self.num_kv_heads, force=force)
 
-    # SSI_PLAIN_PLAN=1 (A/B runs): plain causal rows with a work plan too instead of the dispatcher's fixed patterns.  Measured and left off:
-    # 0.2-0.3 % slower in the step at 8 x 2048, 2 x 2048, 16 x 768 and 8 x 4096 (profiles/LAB_NOTES.md, round 5) — equal rows need no balancing
-    plan_plain_rows = os.environ.get("SSI_PLAIN_PLAN", "0") == "1"
-
-    def _plain_rows_plan(self, B: int, S: int, device):
-        """Work plan for plain causal rows — every row one document — built once per batch shape and kept on the device: the attention
-        backward's persistent dQ workgroups then take their query blocks by load (the host's longest-processing-time assignment) and dK / dV
-        chunks heavier than the chip's share per compute unit are split over the query heads, whatever B and S are."""
-        cache = self.__dict__.setdefault("_plain_plans", {})
-        key = (B, S, str(device))
-        if key not in cache:
-            from . import attn_plan
-            plan = None
-            if self.head_dim == 64 and self.num_heads == 4 * self.num_kv_heads and S % 128 == 0:
-                plan = attn_plan.plan_from_seq_lens([[S]] * B, self.num_heads, self.num_kv_heads)
-            cache[key] = plan.to_device(device, non_blocking=False) if plan is not None else None
-        return cache[key]
-
     def _forward_hidden(self, tokens: Tensor, save: bool, input_pos: Optional[Tensor] = None, attn_plan=None) -> Tensor:
         B, S = tokens.shape
         pos = ds = de = None
         self.position_errors = None
         plan = None
-        if input_pos is None and save and self.plan_plain_rows and self._mfma_shapes():
-            plan = self._plain_rows_plan(B, S, tokens.device)
         if input_pos is not None and save:
             if attn_plan is None and not input_pos.is_cuda:  # host positions: the plan costs no device sync (the trainer's prefetch thread
                 attn_plan = self.build_attn_plan(input_pos)   # brings one along with the batch instead)
@@ -560,7 +491,6 @@ class HipLlamaDecoder(nn.Module):
                 ops.gemm(GEMM_TN, dy, x, g, accumulate=acc)
 
         sync = self.grad_sync if (self.grad_sync is not None and self.sync_this_backward) else None
-        self._ensure_transposed()
         # who hears that a bucket's gradients are final: the data-parallel exchange, and / or an optimizer that updates the bucket's parameters
         # under the rest of this backward (HipAdamW.overlap_with_backward, one shot: set for the window's last backward)
         listener, self.bucket_listener = (self.bucket_listener if self.sync_this_backward else None), None
@@ -593,11 +523,9 @@ class HipLlamaDecoder(nn.Module):
             ops.gemm_batched(GEMM_TN, dqkv_all[:n], xn1_all[l_lo:l_lo + n], g_qkv, accumulate=acc)
 
         def dgrad(dy: Tensor, name: str, dx: Tensor) -> None:
-            """dx = dy @ W  (W = [out, in]); NT form on the [in, out] copy where one is kept."""
-            if self._has_t(name):
-                self._gemm(GEMM_NT, dy, self._view_t(name), dx)
-            else:
-                self._gemm(GEMM_NN, dy, self._view(name), dx)
+            """dx = dy @ W  (W = [out, in]) on the untransposed weights: NN form of the persistent GEMM.  In the step its A operand has just
+            been written and is served from the Infinity Cache, which makes it as fast as the k-contiguous form on a transposed copy."""
+            self._gemm(GEMM_NN, dy, self._view(name), dx)
 
         # small micro-batches: dK / dV per query head + a reduction, in a workspace of the arena (0 bytes = the launch fills the chip as it is)
         ws_bytes = ops.attn_bwd_workspace_bytes(B, S, H, KV, hd, dt) if T > 0 else 0
@@ -616,10 +544,8 @@ class HipLlamaDecoder(nn.Module):
             # MLP: h_out = hmid + act @ w2^T
             wgrad(dh, act, f"L{l}.w2")
             dgu = A.get("dgu", (T, 2 * I), dt)
-            if self._has_t(f"L{l}.w2"):  # d act = dh W2 never reaches memory: the SwiGLU backward rides in the GEMM epilogue
-                ops.gemm_swiglu_bwd(GEMM_NT, dh, self._view_t(f"L{l}.w2"), gu, dgu, None)
-            else:
-                ops.gemm_swiglu_bwd(GEMM_NN, dh, self._view(f"L{l}.w2"), gu, dgu, A.get("dact", (T, I), dt))
+            # d act = dh W2 never reaches memory: the SwiGLU backward rides in the GEMM epilogue
+            ops.gemm_swiglu_bwd(GEMM_NN, dh, self._view(f"L{l}.w2"), gu, dgu, A.get("dact", (T, I), dt))
             dxn = A.get("dxn", (T, D), dt)
             dgrad(dgu, f"L{l}.w13", dxn)
             wgrad(dgu, xn2, f"L{l}.w13")
@@ -673,11 +599,7 @@ class HipLlamaDecoder(nn.Module):
         self._finish_pending_exchange()  # before anything may touch the gradient buffer (see _backward_hidden)
         acc = self._window_accumulates()
         d_hn = self._arena.get("d_hn", (T, D), self.dtype)
-        self._ensure_transposed()
-        if self._has_t("emb"):
-            ops.gemm(GEMM_NT, dlogits, self._view_t("emb"), d_hn, alpha_dev=alpha_dev)
-        else:
-            ops.gemm(GEMM_NN, dlogits, self._view("emb"), d_hn, alpha_dev=alpha_dev)
+        ops.gemm(GEMM_NN, dlogits, self._view("emb"), d_hn, alpha_dev=alpha_dev)
         g_emb = self._view("emb", None, self._flat_grad)
         # dE = dlogits^T hn has vocab_pad / 256 x D / 256 output tiles (521 x 8 = 4168 at V = 133 258): 16 full rounds of the 256 CUs and a
         # 17th with 72 tiles, each a full K = T contraction (~360 us with 184 CUs idle).  The rows of the last partial round go to a second
@@ -725,6 +647,26 @@ class HipLlamaDecoder(nn.Module):
             raise _lib.HipLibraryError("tokens must live on the GPU (no CPU fallback)")
         return tokens
 
+    def _right_pad(self, tokens: Tensor, input_pos: Optional[Tensor], labels: Optional[Tensor] = None,
+                   ignore_index: int = CROSS_ENTROPY_IGNORE_IDX, weights: Optional[Tensor] = None):
+        """Right-pad a [B, S] batch to ``padded_seq_len`` (inert under causal attention): tokens with 0, labels with ``ignore_index``, loss
+        weights with 1; positions continue the row's last document (as PackedDataset pads a pack), clamped to the RoPE table."""
+        B, S = tokens.shape
+        n = self.padded_seq_len(B, S) - S
+        if n == 0:
+            return tokens, input_pos, labels, weights
+        dev = tokens.device
+        pad_t = torch.zeros(B, n, dtype=tokens.dtype, device=dev)
+        tokens = torch.cat([tokens, pad_t], dim=1)
+        if labels is not None:
+            labels = torch.cat([labels, torch.full_like(pad_t, ignore_index)], dim=1)
+        if weights is not None:
+            weights = torch.cat([weights, torch.ones(B, n, dtype=torch.float32, device=dev)], dim=1)
+        if input_pos is not None:
+            cont = input_pos[:, -1:].to(dev) + torch.arange(1, n + 1, device=dev)
+            input_pos = torch.cat([input_pos.to(dev), cont.clamp_(max=self._rope.shape[0] - 1)], dim=1)
+        return tokens, input_pos, labels, weights
+
     def forward_hidden(self, tokens: Tensor, input_pos: Optional[Tensor] = None, attn_plan=None) -> Tensor:
         """Final-normed hidden states [B, S, D] (autograd-aware)."""
         B, S = tokens.shape
@@ -739,12 +681,8 @@ class HipLlamaDecoder(nn.Module):
         SURVEY.md Appendix A.4); else one fp32 [B, S, V] tensor — as torchtune's ``TransformerDecoder.forward``."""
         tokens = self._check_inputs(tokens, mask, encoder_input, encoder_mask, input_pos)
         B, S0 = tokens.shape
-        S = self.padded_seq_len(B, S0)
-        if S != S0:  # right-pad to whole MFMA tiles (inert under causal attention), slice the logits back below
-            tokens = torch.cat([tokens, torch.zeros(B, S - S0, dtype=tokens.dtype, device=tokens.device)], dim=1)
-            if input_pos is not None:
-                cont = input_pos[:, -1:].to(tokens.device) + torch.arange(1, S - S0 + 1, device=tokens.device)
-                input_pos = torch.cat([input_pos.to(tokens.device), cont.clamp_(max=self._rope.shape[0] - 1)], dim=1)
+        tokens, input_pos, _, _ = self._right_pad(tokens, input_pos)  # to whole MFMA tiles; the logits are sliced back below
+        S = tokens.shape[1]
         hn = self.forward_hidden(tokens, input_pos).view(B * S, self.embed_dim)
         if torch.is_grad_enabled() and self.training:
             logits = _HeadLogitsFn.apply(self, hn, self._anchor)
@@ -765,21 +703,11 @@ class HipLlamaDecoder(nn.Module):
         ``loss_weights`` (fp32 ``[B, S]``, >= 0, aligned with ``shifted_labels``): the result is ``sum_i w_i nll_i / n_valid`` — how an
         accumulation window that runs as one batch keeps the reference's per-micro-batch normalisation (``ssi/data/window.py``)."""
         tokens = self._check_inputs(tokens, None, None, None, input_pos)
-        B, S = tokens.shape
         if loss_weights is not None:
             if loss_weights.shape != tokens.shape:
                 raise ValueError(f"loss_weights {tuple(loss_weights.shape)} vs tokens {tuple(tokens.shape)}")
             loss_weights = loss_weights.to(device=tokens.device, dtype=torch.float32)
-        Sp = self.padded_seq_len(B, S)
-        if Sp != S:
-            pad_t = torch.zeros(B, Sp - S, dtype=tokens.dtype, device=tokens.device)
-            tokens = torch.cat([tokens, pad_t], dim=1)
-            shifted_labels = torch.cat([shifted_labels, torch.full_like(pad_t, ignore_index)], dim=1)
-            if loss_weights is not None:
-                loss_weights = torch.cat([loss_weights, torch.ones(B, Sp - S, dtype=torch.float32, device=tokens.device)], dim=1)
-            if input_pos is not None:  # the tail continues the last document (as PackedDataset pads a pack)
-                cont = input_pos[:, -1:].to(tokens.device) + torch.arange(1, Sp - S + 1, device=tokens.device)
-                input_pos = torch.cat([input_pos.to(tokens.device), cont.clamp_(max=self._rope.shape[0] - 1)], dim=1)
+        tokens, input_pos, shifted_labels, loss_weights = self._right_pad(tokens, input_pos, shifted_labels, ignore_index, loss_weights)
         labels = shifted_labels.reshape(-1).contiguous()
         weights = None if loss_weights is None else loss_weights.reshape(-1).contiguous()
         if torch.is_grad_enabled() and self.training:

@@ -61,12 +61,12 @@ class HipAdamW(torch.optim.Optimizer):
         GEMMs.  ``grad_scale_dev`` = the factor ``scale_grads`` would apply afterwards (1 / the window's token count; a DEVICE scalar, so no
         read-back is needed before the backward); ``step()`` then only joins the side stream and counts the step.  The arithmetic per element is
         the one of ``step()`` — same kernel, same scale, same step number — so the parameters come out bit for bit the same.  Not armed (returns
-        False: the plain ``step()`` does all the work) under data parallelism (the buckets are still being reduced), with the round-1
-        zero-and-accumulate protocol, or when gradients are to be clipped (the global norm needs every gradient first): the caller decides
-        the latter by not calling this.  A window without a single label leaves a non-finite scale: the kernel then changes nothing, and the
-        caller, who learns of the empty window at its read-back, must not call ``step()`` — exactly the reference's skip."""
+        False: the plain ``step()`` does all the work) under data parallelism (the buckets are still being reduced), or when gradients
+        are to be clipped (the global norm needs every gradient first): the caller decides the latter by not calling this.  A window
+        without a single label leaves a non-finite scale: the kernel then changes nothing, and the caller, who learns of the empty window
+        at its read-back, must not call ``step()`` — exactly the reference's skip."""
         m = self.model
-        if getattr(m, "grad_sync", None) is not None or m.always_accumulate or not m._flat.is_cuda:
+        if getattr(m, "grad_sync", None) is not None or not m._flat.is_cuda:
             return False
         if self._side is None:
             self._side = torch.cuda.Stream(device=m._flat.device)
@@ -116,7 +116,6 @@ class HipAdamW(torch.optim.Optimizer):
                                    grad_scale_dev=a["scale"], zero_grad=False)
                 pos = max(pos, hi)
             m.pending_grad_scale = None  # (scale_grads of the caller: already applied, bucket by bucket)
-            m._hip_epoch += 1
             if self._views_ready:
                 for st in self.state.values():
                     st["step"].fill_(float(self._step_count))
@@ -136,7 +135,7 @@ class HipAdamW(torch.optim.Optimizer):
             if hi > lo:
                 ops.adamw_step(m._flat[lo:hi], m._flat_grad[lo:hi], self._exp_avg[lo:hi], self._exp_avg_sq[lo:hi], lr=float(g["lr"]),
                                beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"],
-                               step=self._step_count, grad_scale_dev=m.pending_grad_scale, zero_grad=m.always_accumulate)
+                               step=self._step_count, grad_scale_dev=m.pending_grad_scale, zero_grad=False)
 
         sync = getattr(m, "grad_sync", None)
         tail = sync.deferred_range() if sync is not None and hasattr(sync, "deferred_range") else None
@@ -153,9 +152,6 @@ class HipAdamW(torch.optim.Optimizer):
         # the gradients are NOT zeroed (2.5 GB of writes per step for nothing) and the window is NOT closed here: as with torch.optim, a
         # backward that follows a step without a zero_grad in between accumulates; zero_grad (this optimizer's, the model's, or a foreign
         # one that drops every p.grad) ends the window, and the first backward after it overwrites the buffer (model protocol)
-        if m.always_accumulate:  # SSI_ZERO_GRADS=1 (round-1 protocol): the kernel has just zeroed the buffer, a memset in zero_grad would do it twice
-            m._grads_dirty = m._grads_stale = False
-        m._hip_epoch += 1  # weights changed behind torch's version counter
         if self._views_ready:
             for st in self.state.values():
                 st["step"].fill_(float(self._step_count))

@@ -68,7 +68,6 @@ for t in range(trials):
         model._flat.copy_(p0)
         opt._exp_avg.zero_(); opt._exp_avg_sq.zero_()
     opt._step_count = 0
-    model._hip_epoch += 1
     ls = []
     for st in range(steps):
         rows, n_dev = [], None
