@@ -203,9 +203,11 @@ int ssi_swiglu_bwd(const void* dact, const void* gu, void* dgu, int64_t rows, in
 
 /* ---- K3/K6/K7/K8/K10  dense GEMMs (F.linear and its autograd) ------------------------------------------------------- */
 /* C = (accumulate ? C : 0) + alpha * (alpha_dev ? *alpha_dev : 1) * op(A) op(B) + (R ? R : 0)
- * A, B, C, R share `dtype`; accumulation is fp32.  R (residual) has C's shape and ldc.  The MFMA path needs
- * dtype == SSI_BF16, M % 256 == 0, N % 256 == 0, K % 64 == 0 and 16-byte aligned rows; otherwise the generic path runs
- * (or SSI_ERR_UNSUPPORTED if SSI_IMPL_MFMA was forced). */
+ * A, B, C, R share `dtype`; accumulation is fp32.  R (residual) has C's shape and ldc.  The bf16 MFMA path needs
+ * dtype == SSI_BF16, M % 256 == 0, N % 256 == 0, K % 64 == 0 and 16-byte aligned rows.  The fp32 MFMA path (fp32-input
+ * matrix instruction, exact fp32) needs dtype == SSI_F32 and N % 128 == 0; M and K are arbitrary, and it returns the
+ * same bits as the generic path: one fmaf chain per element, k ascending from 0.  Otherwise the generic path runs (or
+ * SSI_ERR_UNSUPPORTED if SSI_IMPL_MFMA / SSI_IMPL_MFMA_WG8 was forced). */
 int ssi_gemm(int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb,
              void* C, int64_t ldc, const void* R, float alpha, const float* alpha_dev, int accumulate, int dtype,
              void* stream);

@@ -1,6 +1,6 @@
-// Generic GEMM: any shape, fp32 or bf16 storage, fp32 accumulate on the vector ALUs.  This is the fp32 parity path
-// (dtype=fp32 is a supported reference config, /root/reference/ssi/constants.py:25) and the fallback for shapes the
-// MFMA kernel (gemm_mfma.hip) does not take.  64x64 output tile per 256-thread block, 4x4 outputs per thread, BK=16.
+// Generic GEMM: any shape, fp32 or bf16 storage, fp32 accumulate on the vector ALUs.  This is the fallback for shapes the
+// MFMA kernels (gemm_mfma.hip, gemm_f32_mfma.hip) do not take, and the yardstick the fp32 MFMA kernel is held to bit for bit
+// (dtype=fp32 is a supported reference config, /root/reference/ssi/constants.py:25).  64x64 output tile per 256-thread block, 4x4 outputs per thread, BK=16.
 #include "common_hip.h"
 #include <atomic>
 
@@ -13,6 +13,12 @@ bool ssi_gemm_mfma_supported(int layout, int64_t M, int64_t N, int64_t K, const 
 int ssi_gemm_mfma_bf16_splitk(int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
                               int64_t ldb, void* C, int64_t ldc, const void* R, float alpha, const float* alpha_dev,
                               int accumulate, int splits, float* slabs, void* stream);
+
+int ssi_gemm_f32_mfma(int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb,
+                      void* C, int64_t ldc, const void* R, float alpha, const float* alpha_dev, int accumulate,
+                      void* stream);  // gemm_f32_mfma.hip
+bool ssi_gemm_f32_mfma_supported(int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
+                                 int64_t ldb, const void* C, int64_t ldc, const void* R);
 
 // process-wide switch (tests, A/B runs): atomic so that the forward thread and autograd's backward thread never race on it
 static std::atomic<int> g_impl{SSI_IMPL_AUTO};
@@ -107,12 +113,15 @@ extern "C" int ssi_gemm(int layout, int64_t M, int64_t N, int64_t K, const void*
     else if (layout == SSI_GEMM_NN) { SSI_CHECK_ARG(lda >= K && ldb >= N); sam = lda; sak = 1;   sbk = ldb; sbn = 1; }
     else                            { SSI_CHECK_ARG(lda >= M && ldb >= N); sam = 1;   sak = lda; sbk = ldb; sbn = 1; }
 
-    const bool mfma_ok = dtype == SSI_BF16 && ssi_gemm_mfma_supported(layout, M, N, K, A, lda, B, ldb, C, ldc, R);
+    const bool f32_ok = dtype == SSI_F32 && ssi_gemm_f32_mfma_supported(layout, M, N, K, A, lda, B, ldb, C, ldc, R);
+    const bool mfma_ok = f32_ok || (dtype == SSI_BF16 && ssi_gemm_mfma_supported(layout, M, N, K, A, lda, B, ldb, C, ldc, R));
     if ((g_impl == SSI_IMPL_MFMA || g_impl == SSI_IMPL_MFMA_WG8) && !mfma_ok) {
         ssi_set_error("ssi_gemm: MFMA path forced but shape/dtype unsupported (M=%lld N=%lld K=%lld dtype=%d)",
                       (long long)M, (long long)N, (long long)K, dtype);
         return SSI_ERR_UNSUPPORTED;
     }
+    if (f32_ok && g_impl != SSI_IMPL_GENERIC)  // same bits as the generic kernel below (one k-ordered fmaf chain per element)
+        return ssi_gemm_f32_mfma(layout, M, N, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, accumulate, stream);
     if (mfma_ok && g_impl != SSI_IMPL_GENERIC)
         return ssi_gemm_mfma_bf16(layout, M, N, K, A, lda, B, ldb, C, ldc, R, alpha, alpha_dev, accumulate, stream);
 
