@@ -8,19 +8,6 @@
 // `padded_collate_packed`), a key is seen by the queries j <= i < doc_end.
 #include "common_hip.h"
 
-int ssi_get_impl();
-bool ssi_attn_mfma_supported(int64_t ld, int64_t batch, int64_t seq, int n_heads, int n_kv, int head_dim, int dtype);
-int ssi_attn_fwd_mfma(const void* qkv, int64_t ld, void* out, float* lse, const int32_t* doc_start, int64_t batch, int64_t seq,
-                      int n_heads, int n_kv, void* stream);
-int ssi_attn_bwd_mfma(const void* qkv, int64_t ld, const void* out, const void* dout, const float* lse, void* dqkv,
-                      float* delta, const int32_t* doc_start, const int32_t* doc_end, const float* rope, int64_t table_len,
-                      const int32_t* positions, int64_t batch, int64_t seq, int n_heads, int n_kv, void* workspace, int64_t workspace_bytes,
-                      const int32_t* plan_dev, const int32_t* host_plan_header, void* stream);
-void ssi_attn_note_dispatch(int v);
-int64_t ssi_attn_mfma_bwd_workspace_bytes(int64_t batch, int64_t seq, int n_heads, int n_kv);
-extern "C" int ssi_rope_inplace(void* x, int64_t ld, int64_t rows, int64_t seq_len, int n_heads_rot, int head_dim, const float* table,
-                                int64_t table_len, const int32_t* positions, int inverse, int dtype, void* stream);
-
 template <typename T, int HD>
 __device__ __forceinline__ void load_row(const T* p, float (&r)[HD]) {
     constexpr int N = Vec16<T>::N;

@@ -165,6 +165,53 @@ template <int N, bool FENCED> struct PhaseStamps<false, N, FENCED> {
     __device__ __forceinline__ void tick(int) {}
 };
 
+// ---- internal functions: defined in one .hip file, called from another ------------------------------------------------
+// Declared here ONCE; the defining file includes this header too, so the compiler holds the definition to the declaration.
+// (C++ linkage: none of these is part of the ABI in include/ssi_hip.h.)
+int ssi_get_impl();  // gemm_generic.hip: the value of ssi_set_impl
+
+// gemm_mfma.hip: bf16 GEMMs on the matrix cores.  The bool forms return false when the shape is not theirs (the caller falls back to the
+// unfused path); *rc then carries nothing.
+bool ssi_gemm_mfma_supported(int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
+                             int64_t ldb, const void* C, int64_t ldc, const void* R);
+int ssi_gemm_mfma_bf16(int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
+                       int64_t ldb, void* C, int64_t ldc, const void* R, float alpha, const float* alpha_dev,
+                       int accumulate, void* stream);
+int ssi_gemm_mfma_bf16_splitk(int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
+                              int64_t ldb, void* C, int64_t ldc, const void* R, float alpha, const float* alpha_dev,
+                              int accumulate, int splits, float* slabs, void* stream);
+bool ssi_gemm_mfma_bf16_batched(int layout, int batch, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, int64_t bsA, const void* B,
+                                int64_t ldb, int64_t bsB, void* C, int64_t ldc, int64_t bsC, float alpha, const float* alpha_dev, int accumulate,
+                                void* stream, int* rc);
+void ssi_gemm_mfma_set_dynamic_tiles(int on);
+bool ssi_gemm_rope_mfma(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                        const float* rope, const int32_t* positions, int64_t seq, int64_t rot_cols, void* stream, int* rc);
+bool ssi_gemm_swiglu_supported(int64_t M, int64_t inter, int64_t K, const void* p0, const void* p1, const void* p2, const void* p3,
+                               int64_t ld0, int64_t ld1, int64_t ld2, int64_t ld3);
+int ssi_gemm_swiglu_fwd_mfma(int64_t M, int64_t inter, int64_t K, const void* X, int64_t ldx, const void* W13, int64_t ldw,
+                             void* GU, int64_t ldgu, void* ACT, int64_t ldact, void* stream);
+int ssi_gemm_swiglu_bwd_mfma(int layout, int64_t M, int64_t inter, int64_t K, const void* DY, int64_t lddy, const void* W2, int64_t ldw,
+                             const void* GU, int64_t ldgu, void* DGU, int64_t lddgu, void* stream);
+bool ssi_gemm_swiglu_bwd_nn_supported(int64_t K, int64_t lddy, int64_t ldw);
+
+// gemm_f32_mfma.hip: fp32 GEMMs on the fp32-input matrix instructions
+bool ssi_gemm_f32_mfma_supported(int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
+                                 int64_t ldb, const void* C, int64_t ldc, const void* R);
+int ssi_gemm_f32_mfma(int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb,
+                      void* C, int64_t ldc, const void* R, float alpha, const float* alpha_dev, int accumulate,
+                      void* stream);
+
+// attention_mfma.hip and the kernel files it includes
+bool ssi_attn_mfma_supported(int64_t ld, int64_t batch, int64_t seq, int n_heads, int n_kv, int head_dim, int dtype);
+void ssi_attn_note_dispatch(int v);
+int ssi_attn_bwd_mfma(const void* qkv, int64_t ld, const void* out, const void* dout, const float* lse, void* dqkv,
+                      float* delta, const int32_t* doc_start, const int32_t* doc_end, const float* rope, int64_t table_len,
+                      const int32_t* positions, int64_t batch, int64_t seq, int n_heads, int n_kv, void* workspace, int64_t workspace_bytes,
+                      const int32_t* plan_dev, const int32_t* host_plan_header, void* stream);
+int ssi_attn_fwd_mfma(const void* qkv, int64_t ld, void* out, float* lse, const int32_t* doc_start, int64_t batch, int64_t seq,
+                      int n_heads, int n_kv, void* stream);                                              // attn_fwd.h
+int64_t ssi_attn_mfma_bwd_workspace_bytes(int64_t batch, int64_t seq, int n_heads, int n_kv);            // attn_bwd_dkv.h
+
 #define SSI_DISPATCH_DTYPE(dtype, ...)                           \
     do {                                                         \
         if ((dtype) == SSI_F32) {                                \

@@ -4,22 +4,6 @@
 #include "common_hip.h"
 #include <atomic>
 
-int ssi_gemm_mfma_bf16(int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
-                       int64_t ldb, void* C, int64_t ldc, const void* R, float alpha, const float* alpha_dev,
-                       int accumulate, void* stream);  // gemm_mfma.hip
-bool ssi_gemm_mfma_supported(int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
-                             int64_t ldb, const void* C, int64_t ldc, const void* R);
-
-int ssi_gemm_mfma_bf16_splitk(int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
-                              int64_t ldb, void* C, int64_t ldc, const void* R, float alpha, const float* alpha_dev,
-                              int accumulate, int splits, float* slabs, void* stream);
-
-int ssi_gemm_f32_mfma(int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb,
-                      void* C, int64_t ldc, const void* R, float alpha, const float* alpha_dev, int accumulate,
-                      void* stream);  // gemm_f32_mfma.hip
-bool ssi_gemm_f32_mfma_supported(int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
-                                 int64_t ldb, const void* C, int64_t ldc, const void* R);
-
 // process-wide switch (tests, A/B runs): atomic so that the forward thread and autograd's backward thread never race on it
 static std::atomic<int> g_impl{SSI_IMPL_AUTO};
 extern "C" int ssi_set_impl(int impl) {
@@ -28,7 +12,6 @@ extern "C" int ssi_set_impl(int impl) {
 }
 int ssi_get_impl() { return g_impl.load(std::memory_order_relaxed); }
 
-void ssi_gemm_mfma_set_dynamic_tiles(int on);
 extern "C" int ssi_set_gemm_tile_order(int mode) {
     if (mode != SSI_TILES_STATIC && mode != SSI_TILES_DYNAMIC) { ssi_set_error("ssi_set_gemm_tile_order: mode %d", mode); return SSI_ERR_ARG; }
     ssi_gemm_mfma_set_dynamic_tiles(mode == SSI_TILES_DYNAMIC);
@@ -139,9 +122,6 @@ extern "C" int ssi_gemm(int layout, int64_t M, int64_t N, int64_t K, const void*
 // square projections (dW_o: 64 output tiles, dW_qkv: 96) of several LAYERS, deferred by the model until a group of layers has finished
 // its backward, fill the chip as one launch at full K instead of a split-K launch + reduction per layer.  Shapes the persistent MFMA kernel
 // does not take run as `batch` ssi_gemm calls.
-bool ssi_gemm_mfma_bf16_batched(int layout, int batch, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, int64_t bsA, const void* B,
-                                int64_t ldb, int64_t bsB, void* C, int64_t ldc, int64_t bsC, float alpha, const float* alpha_dev, int accumulate,
-                                void* stream, int* rc);
 extern "C" int ssi_gemm_batched(int layout, int batch, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, int64_t strideA,
                                 const void* B, int64_t ldb, int64_t strideB, void* C, int64_t ldc, int64_t strideC, float alpha,
                                 const float* alpha_dev, int accumulate, int dtype, void* stream) {
@@ -190,11 +170,6 @@ extern "C" int ssi_gemm_splitk(int layout, int64_t M, int64_t N, int64_t K, cons
 }
 
 // ---- QKV projection + RoPE (K3 + K4): C = A B^T, then the interleaved rotation on the first rot_heads heads of every row --------
-bool ssi_gemm_rope_mfma(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
-                        const float* rope, const int32_t* positions, int64_t seq, int64_t rot_cols, void* stream, int* rc);
-extern "C" int ssi_rope_inplace(void* x, int64_t ld, int64_t rows, int64_t seq_len, int n_heads_rot, int head_dim, const float* table,
-                                int64_t table_len, const int32_t* positions, int inverse, int dtype, void* stream);
-
 extern "C" int ssi_gemm_rope(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                              int64_t seq_len, int n_heads_rot, int head_dim, const float* rope_table, int64_t table_len,
                              const int32_t* positions, int dtype, void* stream) {
@@ -210,14 +185,6 @@ extern "C" int ssi_gemm_rope(int64_t M, int64_t N, int64_t K, const void* A, int
 }
 
 // ---- fused SwiGLU GEMMs (K7 of SURVEY.md §2.3: FeedForward w2(silu(w1 x) * w3 x) and its backward) -------------------------
-bool ssi_gemm_swiglu_supported(int64_t M, int64_t inter, int64_t K, const void* p0, const void* p1, const void* p2, const void* p3,
-                               int64_t ld0, int64_t ld1, int64_t ld2, int64_t ld3);
-int ssi_gemm_swiglu_fwd_mfma(int64_t M, int64_t inter, int64_t K, const void* X, int64_t ldx, const void* W13, int64_t ldw,
-                             void* GU, int64_t ldgu, void* ACT, int64_t ldact, void* stream);
-int ssi_gemm_swiglu_bwd_mfma(int layout, int64_t M, int64_t inter, int64_t K, const void* DY, int64_t lddy, const void* W2, int64_t ldw,
-                             const void* GU, int64_t ldgu, void* DGU, int64_t lddgu, void* stream);
-bool ssi_gemm_swiglu_bwd_nn_supported(int64_t K, int64_t lddy, int64_t ldw);
-
 extern "C" int ssi_gemm_swiglu_fwd(int64_t M, int64_t inter, int64_t K, const void* X, int64_t ldx, const void* W13, int64_t ldw,
                                    void* GU, int64_t ldgu, void* ACT, int64_t ldact, int dtype, void* stream) {
     SSI_CHECK_ARG(X && W13 && GU && ACT && M >= 0 && inter > 0 && K > 0 && ldgu >= 2 * inter && ldact >= inter);

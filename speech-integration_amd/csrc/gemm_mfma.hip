@@ -21,8 +21,6 @@
 #include <atomic>
 #include <type_traits>
 
-int ssi_get_impl();
-
 namespace {
 
 constexpr int BM = 256, BN = 256, BK = 64;

@@ -19,7 +19,11 @@ from torch import Tensor
 
 from . import _lib
 
-HEADER_WORDS = 16
+# The header words and item sizes this module decodes, named after ``csrc/attn_plan.h`` (the format's one definition; ``tests/test_attn_plan.py``
+# holds what is decoded here against the documents a plan was built from).
+W_N_DKV_ITEMS, W_DKV_OFF, W_N_DQ_GROUPS, W_DQ_OFF, W_DQ_GROUP_WORDS = 1, 2, 3, 4, 5
+W_BATCH, W_SEQ, W_N_HEADS, W_N_KV, W_N_DOCS = 6, 7, 8, 9, 11
+DKV_ITEM_WORDS, DQ_ITEM_WORDS = 8, 4   # a dK/dV item; a dQ item and the head of a dQ group (whose first word is its item count)
 
 
 class AttnPlan:
@@ -28,33 +32,37 @@ class AttnPlan:
     is_attn_plan = True
 
     def __init__(self, host: Tensor, dev: Optional[Tensor] = None) -> None:
-        assert host.dtype == torch.int32 and not host.is_cuda and host.is_contiguous() and host.numel() >= HEADER_WORDS
+        assert host.dtype == torch.int32 and not host.is_cuda and host.is_contiguous() and host.numel() >= _lib.ATTN_PLAN_HEADER
         self.host, self.dev = host, dev
 
     @property
     def batch(self) -> int:
-        return int(self.host[6])
+        return int(self.host[W_BATCH])
 
     @property
     def seq(self) -> int:
-        return int(self.host[7])
+        return int(self.host[W_SEQ])
 
     @property
     def n_dkv_items(self) -> int:
-        return int(self.host[1])
+        return int(self.host[W_N_DKV_ITEMS])
 
     @property
     def n_dq_groups(self) -> int:
-        return int(self.host[3])
+        return int(self.host[W_N_DQ_GROUPS])
 
     @property
     def workspace_bytes(self) -> int:
         """What the backward needs in its workspace for this plan: fp32 partial rows of the dK/dV chunks split over the query heads."""
-        return int(self.host[15]) * int(self.host[9]) * 256 * 128 * 4
+        return int(_lib.load().ssi_attn_plan_workspace_bytes(self.host.data_ptr()))
+
+    @property
+    def n_docs(self) -> int:
+        return int(self.host[W_N_DOCS])
 
     def matches(self, batch: int, seq: int, n_heads: int, n_kv: int) -> bool:
         h = self.host
-        return int(h[6]) == batch and int(h[7]) == seq and int(h[8]) == n_heads and int(h[9]) == n_kv
+        return int(h[W_BATCH]) == batch and int(h[W_SEQ]) == seq and int(h[W_N_HEADS]) == n_heads and int(h[W_N_KV]) == n_kv
 
     def to_device(self, device, non_blocking: bool = True) -> "AttnPlan":
         if self.dev is not None and self.dev.device == torch.device(device):
@@ -67,18 +75,17 @@ class AttnPlan:
     def dq_groups(self) -> list[list[tuple[int, int, int, int]]]:
         """(row, query block start, document start, document end) per item, per persistent workgroup — for tests and reports."""
         h = self.host.tolist()
-        off, stride = h[4], h[5]
         out = []
-        for g in range(h[3]):
-            base = off + g * stride
-            n = h[base]
-            out.append([tuple(h[base + 4 + 4 * i: base + 8 + 4 * i]) for i in range(n)])
+        for g in range(h[W_N_DQ_GROUPS]):
+            base = h[W_DQ_OFF] + g * h[W_DQ_GROUP_WORDS]
+            items = base + DQ_ITEM_WORDS   # behind the group's head
+            out.append([tuple(h[items + DQ_ITEM_WORDS * i: items + DQ_ITEM_WORDS * (i + 1)]) for i in range(h[base])])
         return out
 
     def dkv_items(self, with_heads: bool = False) -> list[tuple]:
         """(row, first key, document start, document end) per dK/dV workgroup; ``with_heads``: + (first query head, query heads, partial slot)."""
         h = self.host.tolist()
-        return [tuple(h[h[2] + 8 * i: h[2] + 8 * i + (7 if with_heads else 4)]) for i in range(h[1])]
+        return [tuple(h[h[W_DKV_OFF] + DKV_ITEM_WORDS * i: h[W_DKV_OFF] + DKV_ITEM_WORDS * i + (7 if with_heads else 4)]) for i in range(h[W_N_DKV_ITEMS])]
 
 
 def documents_from_input_pos(input_pos: Tensor) -> Optional[tuple[Tensor, Tensor, Tensor]]:

@@ -155,38 +155,25 @@ def attn_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, dqkv: Tensor, 
     ``plan`` (``ssi.attn_plan.AttnPlan`` on the device, packed rows only): the pipelined kernels take the documents' work from it."""
     assert qkv.stride(1) == 1 and dqkv.stride() == qkv.stride() and out.is_contiguous() and dout.is_contiguous()
     assert delta.dtype == torch.float32 and delta.numel() >= batch * n_heads * seq
-    ds, de = _doc_ptrs(doc_start, doc_end, batch * seq)
-    if workspace is not None or plan is not None:
-        assert workspace is None or (workspace.is_contiguous() and workspace.dtype == torch.uint8)
-        assert rope_table is None or (rope_table.dtype == torch.float32 and rope_table.is_contiguous() and rope_table.shape[1] * 2 == head_dim)
-        assert positions is None or (positions.dtype == torch.int32 and positions.numel() == batch * seq)
-        ws_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
-        table_len = rope_table.shape[0] if rope_table is not None else 0
-        if plan is not None:
-            assert plan.dev is not None and plan.dev.device == qkv.device and plan.matches(batch, seq, n_heads, n_kv)
-            assert ds is not None or (positions is None and int(plan.host[11]) == batch), "a plan for plain rows has one document per row"
-            if ws_bytes < plan.workspace_bytes:  # fp32 partial rows of the dK/dV chunks the plan splits over the query heads
-                workspace = _byte_ws(plan.workspace_bytes, qkv)
-                ws_bytes = workspace.numel()
-            check(_lib.load().ssi_attn_varlen_bwd_plan(ptr(qkv), qkv.stride(0), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), ptr(delta), ds, de,
-                                                       ptr(rope_table), table_len, ptr(positions), batch, seq, n_heads, n_kv, head_dim,
-                                                       dtype_code(qkv.dtype), ptr(workspace), ws_bytes, ptr(plan.dev), plan.host.data_ptr(),
-                                                       stream_ptr()), "ssi_attn_varlen_bwd_plan")
-            return
-        check(_lib.load().ssi_attn_varlen_bwd_ws(ptr(qkv), qkv.stride(0), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), ptr(delta), ds, de,
-                                                 ptr(rope_table), table_len, ptr(positions), batch,
-                                                 seq, n_heads, n_kv, head_dim, dtype_code(qkv.dtype), ptr(workspace), ws_bytes, stream_ptr()),
-              "ssi_attn_varlen_bwd_ws")
-        return
-    if rope_table is None:
-        check(_lib.load().ssi_attn_varlen_bwd(ptr(qkv), qkv.stride(0), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), ptr(delta), ds, de, batch,
-                                              seq, n_heads, n_kv, head_dim, dtype_code(qkv.dtype), stream_ptr()), "ssi_attn_varlen_bwd")
-        return
-    assert rope_table.dtype == torch.float32 and rope_table.is_contiguous() and rope_table.shape[1] * 2 == head_dim
+    assert workspace is None or (workspace.is_contiguous() and workspace.dtype == torch.uint8)
+    assert rope_table is None or (rope_table.dtype == torch.float32 and rope_table.is_contiguous() and rope_table.shape[1] * 2 == head_dim)
     assert positions is None or (positions.dtype == torch.int32 and positions.numel() == batch * seq)
-    check(_lib.load().ssi_attn_varlen_bwd_rope(ptr(qkv), qkv.stride(0), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), ptr(delta), ds, de,
-                                               ptr(rope_table), rope_table.shape[0], ptr(positions), batch, seq, n_heads, n_kv, head_dim,
-                                               dtype_code(qkv.dtype), stream_ptr()), "ssi_attn_varlen_bwd_rope")
+    ds, de = _doc_ptrs(doc_start, doc_end, batch * seq)
+    ws_bytes = workspace.numel() if workspace is not None else 0
+    table_len = rope_table.shape[0] if rope_table is not None else 0
+    plan_dev = plan_header = None
+    if plan is not None:
+        assert plan.dev is not None and plan.dev.device == qkv.device and plan.matches(batch, seq, n_heads, n_kv)
+        assert ds is not None or (positions is None and plan.n_docs == batch), "a plan for plain rows has one document per row"
+        if ws_bytes < plan.workspace_bytes:  # fp32 partial rows of the dK/dV chunks the plan splits over the query heads
+            workspace = _byte_ws(plan.workspace_bytes, qkv)
+            ws_bytes = workspace.numel()
+        plan_dev, plan_header = ptr(plan.dev), plan.host.data_ptr()
+    # the widest entry; ssi_attn_bwd, ssi_attn_varlen_bwd, _rope and _ws are this one with NULL / 0 for what the caller did not bring
+    check(_lib.load().ssi_attn_varlen_bwd_plan(ptr(qkv), qkv.stride(0), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), ptr(delta), ds, de,
+                                               ptr(rope_table), table_len, ptr(positions), batch, seq, n_heads, n_kv, head_dim,
+                                               dtype_code(qkv.dtype), ptr(workspace), ws_bytes, plan_dev, plan_header, stream_ptr()),
+          "ssi_attn_varlen_bwd_plan")
 
 
 def swiglu_fwd(gu: Tensor, act: Tensor) -> None:

@@ -1380,6 +1380,54 @@ def test_attention_backward_with_fused_rope_backward(ops, packed):
             assert float(diff.max()) <= 2 ** -7 * float(two.float().abs().max()) and float((diff > 0).float().mean()) < 0.05
 
 
+@pytest.mark.parametrize("shape", ["mfma_bf16", "generic_fp32"])
+@pytest.mark.parametrize("entry", ["ssi_attn_bwd", "ssi_attn_varlen_bwd", "ssi_attn_varlen_bwd_rope", "ssi_attn_varlen_bwd_ws"])
+def test_attention_backward_narrow_entries_match_ops(ops, entry, shape):
+    """The narrower backward entries of the C ABI, called directly (``ops.attn_bwd`` goes through ``ssi_attn_varlen_bwd_plan`` alone),
+    give bit for bit what ``ops.attn_bwd`` gives on the same inputs: dqkv and delta.  One MFMA shape (bf16, 4 query heads per kv head, S a
+    multiple of 128) and one shape of the generic fp32 kernels each; ``_rope`` with documents and positions, ``_ws`` with the workspace
+    ``ssi_attn_bwd_workspace_bytes`` asks for (the head-split dK / dV form at the MFMA shape)."""
+    from ssi import _lib
+    from ssi.model import llama3_rope_table
+    lib = _lib.load()
+    if shape == "mfma_bf16":
+        B, S, H, KV, hd, dtype, rows = 2, 256, 8, 2, 64, torch.bfloat16, [[100, 37, 119], [64, 192]]
+    else:
+        B, S, H, KV, hd, dtype, rows = 2, 48, 4, 2, 64, torch.float32, [[20, 28], [48]]
+    qkv = rnd(B * S, (H + 2 * KV) * hd, dtype=dtype, seed=97).to(DEV)
+    do = rnd(B * S, H * hd, dtype=dtype, seed=98).to(DEV)
+    ds = de = pos = table = ws = None
+    if entry != "ssi_attn_bwd":
+        ds, de = (t.to(DEV) for t in _doc_arrays(rows, S))
+    if entry in ("ssi_attn_varlen_bwd_rope", "ssi_attn_varlen_bwd_ws"):
+        table = llama3_rope_table(hd, 512, 500_000, 32).to(DEV)
+        pos = torch.cat([torch.cat([torch.arange(n) for n in lens]) for lens in rows]).to(torch.int32).to(DEV)
+    if entry == "ssi_attn_varlen_bwd_ws":
+        need = ops.attn_bwd_workspace_bytes(B, S, H, KV, hd, dtype)
+        assert (need > 0) == (shape == "mfma_bf16")
+        ws = torch.empty(max(need, 64), dtype=torch.uint8, device=DEV)
+    out = torch.empty(B * S, H * hd, dtype=dtype, device=DEV)
+    lse = torch.empty(B * H * S, dtype=torch.float32, device=DEV)
+    ops.attn_fwd(qkv, out, lse, B, S, H, KV, hd, ds, de)
+    ref, ref_delta = torch.full_like(qkv, float("nan")), torch.zeros_like(lse)
+    ops.attn_bwd(qkv, out, do, lse, ref, ref_delta, B, S, H, KV, hd, ds, de, rope_table=table, positions=pos, workspace=ws)
+    assert bool(lib.ssi_attn_last_dispatch() & 0x10000) == (shape == "mfma_bf16")   # which family ran
+    got, delta = torch.full_like(qkv, float("nan")), torch.zeros_like(lse)
+    p, head = _lib.ptr, (_lib.ptr(qkv), qkv.stride(0), _lib.ptr(out), _lib.ptr(do), _lib.ptr(lse), _lib.ptr(got), _lib.ptr(delta))
+    dims, st = (B, S, H, KV, hd, _lib.dtype_code(dtype)), _lib.stream_ptr()
+    if entry == "ssi_attn_bwd":
+        rc = lib.ssi_attn_bwd(*head, *dims, st)
+    elif entry == "ssi_attn_varlen_bwd":
+        rc = lib.ssi_attn_varlen_bwd(*head, p(ds), p(de), *dims, st)
+    elif entry == "ssi_attn_varlen_bwd_rope":
+        rc = lib.ssi_attn_varlen_bwd_rope(*head, p(ds), p(de), p(table), table.shape[0], p(pos), *dims, st)
+    else:
+        rc = lib.ssi_attn_varlen_bwd_ws(*head, p(ds), p(de), p(table), table.shape[0], p(pos), *dims, p(ws), ws.numel(), st)
+    _lib.check(rc, entry)
+    assert torch.isfinite(ref).all() and bool(ref_delta.any())
+    assert torch.equal(got, ref) and torch.equal(delta, ref_delta)
+
+
 @pytest.mark.parametrize("layout", [0, 1, 2])
 @pytest.mark.parametrize("splits", [2, 3, 8])
 def test_gemm_splitk_matches_direct(ops, layout, splits):

@@ -13,7 +13,12 @@ Rules
       to the next workgroup of the CU by then (the round-4 race of attn_bwd_dq2_kernel).
 
 ``python tools/kernel_lint.py [lib]`` prints one line per kernel and exits 1 on a violation; ``tests/test_kernel_listing.py``
-runs the same checks in the CPU suite."""
+runs the same checks in the CPU suite.
+
+``python tools/kernel_lint.py [lib] --against OTHER_LIB`` compares the two libraries' gfx950 kernels instead (has a change MOVED device
+code or CHANGED it?): the same kernel names on both sides, per kernel the same instruction stream (mnemonic and operands; branch targets as
+offsets within the kernel) and the same VGPR / AGPR / SGPR counts, LDS bytes and private segment size in the code-object notes.  Exits 1 on
+any difference.  Which translation unit a kernel sits in is not compared."""
 from __future__ import annotations
 
 import os
@@ -50,6 +55,7 @@ class Kernel:
     addr: int
     ins: list[Ins] = field(default_factory=list)
     scratch_bytes: int = 0
+    notes: dict = field(default_factory=dict)
 
 
 def extract(lib: str, workdir: str) -> list[str]:
@@ -60,17 +66,26 @@ def extract(lib: str, workdir: str) -> list[str]:
     return sorted(os.path.join(workdir, f) for f in os.listdir(workdir) if f.endswith("gfx950"))
 
 
-def scratch_sizes(co: str) -> dict[str, int]:
+NOTE_KEYS = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size")
+
+
+def kernel_notes(co: str) -> dict[str, dict[str, int]]:
+    """NOTE_KEYS of every kernel of a code object, by kernel name."""
     notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
-    out, name = {}, None
-    for line in notes.splitlines():   # kernel-level keys are sorted: .name directly in front of .private_segment_fixed_size
-        m = re.match(r"\s+\.name:\s+(\S+)", line)
+    out, cur = {}, {}
+    for line in notes.splitlines() + ["  - ."]:   # a kernel's entry: a list item at indent 2, its own keys at indent 4 (arguments lie deeper)
+        m = re.match(r"  [- ] \.(\w+):\s+(\S+)", line)
+        if line.startswith("  - ."):
+            if "name" in cur:
+                out[cur["name"]] = {k: int(cur.get(k, 0)) for k in NOTE_KEYS}
+            cur = {}
         if m:
-            name = m.group(1)
-        m2 = re.match(r"\s+\.private_segment_fixed_size:\s+(\d+)", line)
-        if m2 and name:
-            out[name] = int(m2.group(1))
+            cur[m.group(1)] = m.group(2)
     return out
+
+
+def scratch_sizes(co: str) -> dict[str, int]:
+    return {name: n["private_segment_fixed_size"] for name, n in kernel_notes(co).items()}
 
 
 def disassemble(co: str) -> list[Kernel]:
@@ -197,13 +212,44 @@ def lint_kernel(k: Kernel) -> list[str]:
     return errs
 
 
+def kernels_of(co: str) -> list[Kernel]:
+    notes = kernel_notes(co)
+    ks = [k for k in disassemble(co) if k.name in notes]   # (symbols without a kernel descriptor are not kernels)
+    for k in ks:
+        k.notes = notes[k.name]
+        k.scratch_bytes = k.notes["private_segment_fixed_size"]
+    return ks
+
+
+def compare(lib: str, other: str) -> tuple[list[str], int]:
+    """Differences between the gfx950 kernels of two libraries, and how many kernels `lib` has."""
+    def load(path: str) -> dict[str, Kernel]:
+        with tempfile.TemporaryDirectory() as wd:
+            return {k.name: k for co in extract(path, wd) for k in kernels_of(co)}
+
+    def stream(k: Kernel) -> list[tuple]:
+        return [(i.op, i.args, None if i.target is None else i.target - k.addr) for i in k.ins]
+
+    a, b = load(lib), load(other)
+    diffs = [f"{n}: only in {lib}" for n in sorted(set(a) - set(b))] + [f"{n}: only in {other}" for n in sorted(set(b) - set(a))]
+    if len(a) != len(b):
+        diffs.append(f"kernel count {len(a)} against {len(b)}")
+    for n in sorted(set(a) & set(b)):
+        if a[n].notes != b[n].notes:
+            diffs.append(f"{n}: notes {a[n].notes} against {b[n].notes}")
+        sa, sb = stream(a[n]), stream(b[n])
+        if sa != sb:
+            first = next((j for j, (x, y) in enumerate(zip(sa, sb)) if x != y), min(len(sa), len(sb)))
+            diffs.append(f"{n}: {len(sa)} against {len(sb)} instructions, first difference at instruction {first}: "
+                         f"{sa[first] if first < len(sa) else None} against {sb[first] if first < len(sb) else None}")
+    return diffs, len(a)
+
+
 def lint(lib: str = DEFAULT_LIB) -> tuple[list[str], dict[str, dict]]:
     errs, report = [], {}
     with tempfile.TemporaryDirectory() as wd:
         for co in extract(lib, wd):
-            sizes = scratch_sizes(co)
-            for k in disassemble(co):
-                k.scratch_bytes = sizes.get(k.name, 0)
+            for k in kernels_of(co):
                 e = lint_kernel(k)
                 errs += e
                 report[k.name] = {"instructions": len(k.ins), "scratch": k.scratch_bytes, "mfma": sum(1 for i in k.ins if i.op.startswith("v_mfma")),
@@ -212,7 +258,19 @@ def lint(lib: str = DEFAULT_LIB) -> tuple[list[str], dict[str, dict]]:
 
 
 if __name__ == "__main__":
-    lib = sys.argv[1] if len(sys.argv) > 1 else DEFAULT_LIB
+    argv = sys.argv[1:]
+    against = None
+    if "--against" in argv:
+        j = argv.index("--against")
+        against = argv[j + 1]
+        del argv[j:j + 2]
+    lib = argv[0] if argv else DEFAULT_LIB
+    if against:
+        diffs, n = compare(lib, against)
+        for d in diffs:
+            print("DIFFERENT", d)
+        print(f"{n} gfx950 kernels in {lib}: {'no difference' if not diffs else str(len(diffs)) + ' differences'} against {against}")
+        sys.exit(1 if diffs else 0)
     errs, report = lint(lib)
     for name, r in sorted(report.items()):
         if r["mfma"] or r["lds_dma"] or r["scratch"]:
