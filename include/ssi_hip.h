@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 9 /* 9: ssi_adamw_step takes its hyper-parameters in double (the coefficients of torch's fused AdamW)
+#define SSI_ABI_VERSION 10 /* 10: + ssi_ce_fwd_metrics, ssi_ce_metrics_reduce (dev-set loss and top-k accuracy per token type)
+                           * 9: ssi_adamw_step takes its hyper-parameters in double (the coefficients of torch's fused AdamW)
                            * 8: + ssi_ce_fwd_weighted (per-row loss weights: an accumulation window run as ONE batch keeps the reference's
                            *    per-micro-batch normalisation, ssi/data/window.py)
                            * 7: + ssi_set_attn_impl, ssi_attn_last_dispatch (no getenv on the launch path), ssi_attn_plan_* and ssi_attn_varlen_bwd_plan
@@ -262,6 +263,23 @@ int ssi_ce_reduce(const float* row_loss, const int64_t* labels, int64_t rows, in
  * ratio per row here.  In the register-resident bf16 kernel the weight is an additive term of the exponent: no cost per element. */
 int ssi_ce_fwd_weighted(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
                         int64_t ignore_index, float* row_loss, float* row_lse, int write_grad, int dtype, void* stream);
+/* Forward-only ssi_ce_fwd_weighted that also ranks the label (ABI v10; the dev set's loss and accuracy per token type, ssi/eval.py).  The logits
+ * are read only.  row_loss and row_lse (NULL ok) are what ssi_ce_fwd_weighted(..., write_grad = 0) writes on the same inputs, bit for bit: the
+ * same form (register-resident bf16 rows or the generic kernel) is chosen by the same predicate, with the same order of max, exp-sum and lse.
+ *   row_nll[r]  = lse - logit[label], WITHOUT row_weight (per-type metrics are plain token-level sums);
+ *   row_rank[r] = #{c < vocab : x[c] > x[label]} + #{c < label : x[c] == x[label]}: the label's position in a stable descending sort of
+ *                 the row, compared on the stored values (an exact integer).  rank == 0 <=> argmax(row) == label with torch's
+ *                 first-occurrence rule; rank < k <=> top-k.
+ * A row whose label is ignored or outside [0, vocab): row_nll = 0, row_rank = -1.  Pad columns [vocab, ld) never count.  The rank of a row
+ * with NaN logits is unspecified (its loss is NaN).  One compare-and-count pass over the row registers and an integer block sum per row. */
+int ssi_ce_fwd_metrics(const void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
+                       int64_t ignore_index, float* row_loss, float* row_lse, float* row_nll, int32_t* row_rank, int dtype, void* stream);
+/* Per-type sums of what ssi_ce_fwd_metrics wrote.  ranges: n_ranges (<= 8) inclusive [lo, hi] pairs as in ssi_count_tokens, matched against
+ * the LABEL.  out: double [n_ranges + 1][4] = {n_labels, sum nll, n(rank == 0), n(rank < topk)}; rows 0..n_ranges-1 are the ranges, the last
+ * row is every valid label (also those in no range).  A row counts iff row_rank >= 0.  fp64 sums in a fixed order, no atomics: bitwise
+ * reproducible.  accumulate != 0 adds to what out holds (one device accumulator per dev set, one read-back); 0 overwrites.  One workgroup. */
+int ssi_ce_metrics_reduce(const float* row_nll, const int32_t* row_rank, const int64_t* labels, int64_t rows, const int64_t* ranges,
+                          int n_ranges, int topk, int accumulate, double* out, void* stream);
 
 /* ---- K8 + K9 as one entry per direction: tied LM head (TiedLinear over tok_embeddings, ssi/loss.py:8-14) + chunked CE (trainer.py:300) ----
  * fwd: logits_ws[rows, vocab_pad] = hidden[rows, dim] table[vocab_pad, dim]^T (table rows >= vocab are zero padding), then ssi_ce_fwd

@@ -433,3 +433,269 @@ extern "C" int ssi_ce_reduce(const float* row_loss, const int64_t* labels, int64
     SSI_LAUNCH_CHECK();
     return SSI_OK;
 }
+
+// =====================================================================================================================
+// K9m forward-only cross-entropy that also ranks the label (ssi_ce_fwd_metrics): the dev set's per-token-type loss, top-1 and top-k.
+//   rank[r] = #{c < vocab : x[c] > x[label]} + #{c < label : x[c] == x[label]}  — the label's position in a stable descending sort of
+//   the row; rank == 0 <=> argmax(row) == label under the first-occurrence rule.  Compares on the stored values: an exact integer.
+// Kernels of their own (not a template parameter of the two above): the instantiations the training step launches stay what they were.
+// The max, the exp-sum and the lse are the statements of those kernels in their order: row_loss and row_lse agree bit for bit.
+// =====================================================================================================================
+// block-wide integer sum for blockDim.x <= 1024; `red` is >= 16 ints of LDS; result broadcast to all threads
+__device__ __forceinline__ int block_sum_i32(int v, int* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
+    __syncthreads();
+    if (l == 0) red[w] = v;
+    __syncthreads();
+    int t = (l < nw) ? red[l] : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+    return t;
+}
+
+template <typename T>
+__global__ __launch_bounds__(512) void ce_fwd_metrics_kernel(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                             int64_t vocab, int64_t ignore_index, float* __restrict__ row_loss,
+                                                             float* __restrict__ row_lse, float* __restrict__ row_nll,
+                                                             int32_t* __restrict__ row_rank, const float* __restrict__ row_weight) {
+    constexpr int N = Vec16<T>::N;
+    __shared__ float red[16];
+    __shared__ int redi[16];
+    const int64_t row = blockIdx.x;
+    const T* lr = logits + row * ld;
+    const int64_t label = labels[row];
+    const bool valid = label != ignore_index && label >= 0 && label < vocab;
+    const int64_t nvec = ld / N;
+    if (!valid) {  // block-uniform
+        if (threadIdx.x == 0) { row_loss[row] = 0.f; if (row_lse) row_lse[row] = 0.f; row_nll[row] = 0.f; row_rank[row] = -1; }
+        return;
+    }
+    float m = -INFINITY, s = 0.f;
+    for (int64_t v = threadIdx.x; v < nvec; v += 512) {
+        Vec16<T> a = load16(lr + v * N);
+        float lm = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < N; ++i) if (v * N + i < vocab) lm = fmaxf(lm, a.get(i));
+        if (lm > m) { s *= expf(m - lm); m = lm; }
+#pragma unroll
+        for (int i = 0; i < N; ++i) if (v * N + i < vocab) s += expf(a.get(i) - m);
+    }
+    const float gm = block_max(m, red);
+    s = (m == -INFINITY) ? 0.f : s * expf(m - gm);
+    const float gs = block_sum(s, red);
+    const float lse = gm + logf(gs);
+    const float w = row_weight ? row_weight[row] : 1.f;
+    const float xl = to_f32<T>(lr[label]);  // block-uniform address; the logits are read-only here
+    // second pass over the row (from L2, as the gradient pass of ce_fwd_kernel): pad columns [vocab, ld) never count
+    int cnt = 0;
+    for (int64_t v = threadIdx.x; v < nvec; v += 512) {
+        Vec16<T> a = load16(lr + v * N);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const int64_t c = v * N + i;
+            const float x = a.get(i);
+            cnt += (int)(c < vocab) & ((int)(x > xl) | ((int)(x == xl) & (int)(c < label)));  // bitwise: no branch per element
+        }
+    }
+    cnt = block_sum_i32(cnt, redi);
+    if (threadIdx.x == 0) {
+        row_loss[row] = w * (lse - xl);
+        if (row_lse) row_lse[row] = lse;
+        row_nll[row] = lse - xl;
+        row_rank[row] = cnt;
+    }
+}
+
+// The register-resident row form of ce_row_bf16_kernel<NCH, false> (same launch shape, same walk over the rows, the next row's loads where
+// they are there) with one more pass over the packed registers: compare with the label's logit and count.  Every lane needs that logit
+// before the pass; the label is workgroup-uniform and nothing is overwritten here, so each lane loads it itself from one address.  The pad
+// columns are -inf in the registers and lie above every valid label: they are neither greater than a logit nor tie below the label.
+template <int NCH>
+__global__ __launch_bounds__(1024, 4) void ce_row_bf16_metrics_kernel(const bf16_t* __restrict__ logits, int64_t ld,
+                                                                      const int64_t* __restrict__ labels, int64_t rows, int64_t vocab,
+                                                                      int64_t ignore_index, float* __restrict__ row_loss,
+                                                                      float* __restrict__ row_lse, float* __restrict__ row_nll,
+                                                                      int32_t* __restrict__ row_rank, const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    __shared__ int redi[16];
+    constexpr float LOG2E = 1.44269504088896340736f;
+    constexpr int CHUNK = 8192;
+    const int tid = threadIdx.x;
+    const int voff = tid * 16;
+    const int col0 = tid * 8;
+    const int row_bytes = (int)(ld * 2);
+    const int vocab_i = (int)vocab;
+    u32x4 x[NCH];
+    auto is_valid = [&](int64_t label) { return label != ignore_index && label >= 0 && label < vocab; };
+    auto rsrc_of = [&](int64_t row) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(logits) + row * ld, 0, row_bytes, 0x00020000u); };
+    auto lo = [](unsigned u) { return __builtin_bit_cast(float, u << 16); };
+    auto hi = [](unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); };
+    auto opaque = [&]() {  // as in ce_row_bf16_kernel: each pass re-derives its floats from the packed registers
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int d = 0; d < 4; ++d) asm volatile("" : "+v"(x[c][d]));
+    };
+    int64_t row = blockIdx.x;
+    if (row >= rows) return;
+    {
+        const __amdgpu_buffer_rsrc_t r0 = rsrc_of(row);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) x[c] = __builtin_amdgcn_raw_buffer_load_b128(r0, voff, c * CHUNK * 2, 0);
+    }
+    for (; row < rows; row += gridDim.x) {
+        const int64_t next = row + gridDim.x;
+        const int64_t label = labels[row];
+        const bool valid = is_valid(label);
+        const float w = row_weight ? row_weight[row] : 1.f;
+#pragma unroll
+        for (int c = (NCH >= 2 ? NCH - 2 : 0); c < NCH; ++c) {
+            const int left = vocab_i - c * CHUNK - col0;
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                if (2 * d >= left) x[c][d] = (x[c][d] & 0xffff0000u) | 0x0000ff80u;
+                if (2 * d + 1 >= left) x[c][d] = (x[c][d] & 0x0000ffffu) | 0xff800000u;
+            }
+        }
+        if (valid) {  // workgroup-uniform; reads the row registers only
+            const float xl = (float)logits[row * ld + label];
+            float m = -INFINITY;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c)
+#pragma unroll
+                for (int d = 0; d < 4; ++d) m = fmaxf(m, fmaxf(lo(x[c][d]), hi(x[c][d])));
+            const float gm = block_max(m, red);
+            opaque();
+            const float nm = -gm * LOG2E;
+            float s = 0.f;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c)
+#pragma unroll
+                for (int d = 0; d < 4; ++d)
+                    s += __builtin_amdgcn_exp2f(fmaf(lo(x[c][d]), LOG2E, nm)) + __builtin_amdgcn_exp2f(fmaf(hi(x[c][d]), LOG2E, nm));
+            const float gs = block_sum(s, red);
+            const float lse = gm + logf(gs);
+            opaque();
+            // ---- the rank pass: element e of chunk c is column c * CHUNK + col0 + e; it ties BELOW the label iff e < below - c * CHUNK
+            const int below = (int)label - col0;
+            int cnt = 0;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                const int b = below - c * CHUNK;
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {
+                    const float a0 = lo(x[c][d]), a1 = hi(x[c][d]);
+                    // bitwise on purpose: || and && became a branch per element, and the row spilled
+                    cnt += (int)(a0 > xl) | ((int)(a0 == xl) & (int)(2 * d < b));
+                    cnt += (int)(a1 > xl) | ((int)(a1 == xl) & (int)(2 * d + 1 < b));
+                }
+            }
+            cnt = block_sum_i32(cnt, redi);
+            if (tid == 0) {
+                row_loss[row] = w * (lse - xl);
+                if (row_lse) row_lse[row] = lse;
+                row_nll[row] = lse - xl;
+                row_rank[row] = cnt;
+            }
+        } else if (tid == 0) {
+            row_loss[row] = 0.f;
+            if (row_lse) row_lse[row] = 0.f;
+            row_nll[row] = 0.f;
+            row_rank[row] = -1;
+        }
+        opaque();
+        // each register takes the next row's chunk (past the last row: this row again), one chunk at a time as in ce_row_bf16_kernel
+        const __amdgpu_buffer_rsrc_t rn = rsrc_of(next < rows ? next : row);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            x[c] = __builtin_amdgcn_raw_buffer_load_b128(rn, voff, c * CHUNK * 2, 2 /* nt */);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+
+extern "C" int ssi_ce_fwd_metrics(const void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
+                                  int64_t ignore_index, float* row_loss, float* row_lse, float* row_nll, int32_t* row_rank, int dtype,
+                                  void* stream) {
+    SSI_CHECK_ARG(logits && labels && row_loss && row_nll && row_rank && rows >= 0 && vocab > 0 && ld >= vocab && ld % 8 == 0);
+    if (rows == 0) return SSI_OK;
+    const int64_t chunks = ssi_cdiv(ld, 8192);
+    // the predicate of ssi_ce_fwd_weighted: the same inputs take the same form there and here
+    const bool row_form = dtype == SSI_BF16 && ((uintptr_t)logits & 15) == 0 && ld - vocab < 8192 && ld * 2 < (1LL << 31) &&
+                          (chunks <= 4 || chunks == 8 || (chunks >= 16 && chunks <= 18));
+    if (row_form) {
+        const dim3 grid((unsigned)(rows < ce_num_cus() ? rows : ce_num_cus()));
+#define SSI_CE_ROW_METRICS(N)                                                                                                          \
+    case N:                                                                                                                            \
+        hipLaunchKernelGGL((ce_row_bf16_metrics_kernel<N>), grid, dim3(1024), 0, (hipStream_t)stream, (const bf16_t*)logits, ld, labels, \
+                           rows, vocab, ignore_index, row_loss, row_lse, row_nll, row_rank, row_weight);                               \
+        break
+        switch ((int)chunks) {
+            SSI_CE_ROW_METRICS(1); SSI_CE_ROW_METRICS(2); SSI_CE_ROW_METRICS(3); SSI_CE_ROW_METRICS(4); SSI_CE_ROW_METRICS(8);
+            SSI_CE_ROW_METRICS(16); SSI_CE_ROW_METRICS(17); SSI_CE_ROW_METRICS(18);
+        }
+#undef SSI_CE_ROW_METRICS
+        SSI_LAUNCH_CHECK();
+        return SSI_OK;
+    }
+    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(ce_fwd_metrics_kernel<T>, dim3((unsigned)rows), dim3(512), 0, (hipStream_t)stream,
+                                                 (const T*)logits, ld, labels, vocab, ignore_index, row_loss, row_lse, row_nll, row_rank,
+                                                 row_weight));
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+// Per-type sums of the rows ssi_ce_fwd_metrics wrote.  One workgroup; output row j (a range, or j == n_ranges: every valid label) is one
+// walk over the rows in thread-strided order and one fixed tree over the lanes and the 16 waves, in fp64: bitwise reproducible, no atomics.
+// The counts ride the same tree as doubles (exact below 2^53).
+#define SSI_CE_MAX_RANGES 8  // as ssi_count_tokens
+__global__ __launch_bounds__(1024) void ce_metrics_reduce_kernel(const float* __restrict__ row_nll, const int32_t* __restrict__ row_rank,
+                                                                 const int64_t* __restrict__ labels, int64_t rows,
+                                                                 const int64_t* __restrict__ ranges, int n_ranges, int topk, int accumulate,
+                                                                 double* __restrict__ out) {
+    __shared__ double red[4][16];
+    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+    for (int j = 0; j <= n_ranges; ++j) {
+        const bool all = j == n_ranges;
+        const int64_t lo = all ? 0 : ranges[2 * j], hi = all ? 0 : ranges[2 * j + 1];
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int64_t r = threadIdx.x; r < rows; r += 1024) {
+            const int rank = row_rank[r];
+            const int64_t l = labels[r];
+            if (rank >= 0 && (all || (l >= lo && l <= hi))) {
+                acc[0] += 1.0;
+                acc[1] += (double)row_nll[r];
+                acc[2] += rank == 0 ? 1.0 : 0.0;
+                acc[3] += rank < topk ? 1.0 : 0.0;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_xor(acc[q], o, 64);
+        __syncthreads();  // the previous j's read of red is over
+        if (ln == 0) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) red[q][wv] = acc[q];
+        }
+        __syncthreads();
+        if (threadIdx.x < 4) {
+            double t = 0.0;
+            for (int i = 0; i < 16; ++i) t += red[threadIdx.x][i];
+            double* dst = out + 4 * j + threadIdx.x;
+            *dst = accumulate ? *dst + t : t;
+        }
+    }
+}
+
+extern "C" int ssi_ce_metrics_reduce(const float* row_nll, const int32_t* row_rank, const int64_t* labels, int64_t rows, const int64_t* ranges,
+                                     int n_ranges, int topk, int accumulate, double* out, void* stream) {
+    SSI_CHECK_ARG(out && rows >= 0 && rows < (1LL << 31) && (rows == 0 || (row_nll && row_rank && labels)) && n_ranges >= 0 &&
+                  n_ranges <= SSI_CE_MAX_RANGES && (ranges || n_ranges == 0) && topk >= 1);
+    hipLaunchKernelGGL(ce_metrics_reduce_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, row_nll, row_rank, labels, rows, ranges, n_ranges,
+                       topk, accumulate, out);
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}

@@ -47,6 +47,92 @@ def _joined(data_dev, model, loss_fn, device: torch.device, join_batches: int, m
     return stream
 
 
+class LabelMetrics:
+    """Per-token-type sums over the labels of a dev set, kept on the device (not in the reference): ``acc`` is fp64 ``[n_types + 1, 4]`` =
+    {n_labels, sum nll, n(rank == 0), n(rank < topk)}; its rows are ``token_type_ranges`` in order, then ``all`` (every valid label, also one
+    that lies in no range).  The type is that of the LABEL, the token being predicted.  ``rank`` is the label's position in a stable descending
+    sort of its logits row (``#{x > x[label]} + #{c < label: x[c] == x[label]}``): 0 iff ``argmax(row) == label`` with torch's first-occurrence
+    rule.  ``HipLlamaDecoder.fused_loss(label_metrics=...)`` adds to ``acc`` from its cross-entropy launch (``ssi_ce_fwd_metrics``,
+    ``ssi_ce_metrics_reduce``); ``add_logits`` is the same arithmetic in plain torch for any other model."""
+
+    def __init__(self, token_type_ranges: dict[str, tuple[int, int]], topk: int, device: torch.device):
+        if "all" in token_type_ranges:
+            raise ValueError("'all' is reserved for the row over every valid label")
+        if int(topk) < 1:
+            raise ValueError(f"topk must be >= 1 (got {topk})")
+        self.names = list(token_type_ranges)
+        self.topk = int(topk)
+        self.ranges_dev = torch.tensor([v for lohi in token_type_ranges.values() for v in lohi], dtype=torch.int64, device=device)
+        self.acc = torch.zeros(len(self.names) + 1, 4, dtype=torch.float64, device=device)
+
+    def add_logits(self, logits, labels: torch.Tensor, ignore_index: int) -> None:
+        """``logits``: ``[..., V]`` or the list of chunks along dim 1 that ``model(...)`` returns; ``labels``: the shifted labels, same leading shape."""
+        if isinstance(logits, (list, tuple)):
+            logits = torch.cat(list(logits), dim=1)
+        x = logits.reshape(-1, logits.size(-1))
+        labels = labels.reshape(-1).to(x.device)
+        vocab = x.size(-1)
+        valid = (labels != ignore_index) & (labels >= 0) & (labels < vocab)
+        x, lab = x[valid].float(), labels[valid]
+        xl = x.gather(1, lab[:, None])
+        nll = (torch.logsumexp(x, dim=1) - xl[:, 0]).double()
+        below = torch.arange(vocab, device=x.device)[None, :] < lab[:, None]
+        rank = ((x > xl) | ((x == xl) & below)).sum(dim=1)
+        lo, hi = self.ranges_dev.view(-1, 2)[:, 0], self.ranges_dev.view(-1, 2)[:, 1]
+        member = (lab[None, :] >= lo.to(x.device)[:, None]) & (lab[None, :] <= hi.to(x.device)[:, None])
+        member = torch.cat([member, torch.ones_like(lab, dtype=torch.bool)[None, :]]).double()  # [n_types + 1, n_valid]
+        cols = torch.stack([torch.ones_like(nll), nll, (rank == 0).double(), (rank < self.topk).double()], dim=1)
+        self.acc += (member @ cols).to(self.acc.device)
+
+    def result(self) -> dict[str, float | int]:
+        """``dev_n_labels.<type>`` for every type and ``all``; ``dev_loss.<type>``, ``dev_acc.<type>``, ``dev_acc_top<k>.<type>`` (token-level: sum / n
+        over the whole dev set) only where there are labels — no NaN reaches the log record.  One device read-back."""
+        out: dict[str, float | int] = {}
+        for name, (n, nll, top1, topk) in zip(self.names + ["all"], self.acc.tolist()):
+            out[f"dev_n_labels.{name}"] = int(n)
+            if n > 0:
+                out[f"dev_loss.{name}"] = nll / n
+                out[f"dev_acc.{name}"] = top1 / n
+                out[f"dev_acc_top{self.topk}.{name}"] = topk / n
+        return out
+
+
+def compute_dataset_metrics(model, data_dev, loss_fn: Callable, epoch: int, global_step: int, steps_per_epoch: int, device: torch.device, *,
+                            token_type_ranges: dict[str, tuple[int, int]], topk: int = 5, join_batches: int = 0, max_tokens: int = 32768,
+                            pad_id: int = 0, prefetch: int = 2) -> dict[str, float | int]:
+    """``compute_dataset_loss`` plus loss and top-1 / top-k accuracy per token type of the label (not in the reference).  ``dev_loss`` is the
+    float ``compute_dataset_loss`` returns on the same data and settings, bit for bit: the same loop, the same launches but for the
+    cross-entropy kernel, which also ranks each label in its row (``LabelMetrics``).  The per-type values are token-level sums over the whole dev
+    set, so — unlike the reference's ``dev_loss`` — they do not depend on how it is batched or joined.  Under data parallelism the accumulator
+    is all-reduced beside the two scalars."""
+    from .data.unpad import loss_inputs
+    dev_loss_running = torch.zeros((), dtype=torch.float64, device=device)
+    num_tokens_dev = torch.zeros((), dtype=torch.float64, device=device)
+    metrics = LabelMetrics(token_type_ranges, topk, device)
+    joinable = join_batches > 1 and hasattr(model, "fused_loss") and hasattr(model, "padded_seq_len")
+    batches = _joined(data_dev, model, loss_fn, device, join_batches, max_tokens, pad_id, prefetch) if joinable else data_dev
+    model.eval()
+    with torch.inference_mode():
+        for i_dev, dev_batch in enumerate(batches):
+            batch_to_device(dev_batch, device)
+            n_b = (dev_batch["labels"] != loss_fn.ignore_index).sum()
+            dev_loss_running += compute_loss(loss_inputs(dev_batch), model, loss_fn, label_metrics=metrics).double() * n_b
+            num_tokens_dev += n_b
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        both = torch.stack([dev_loss_running, num_tokens_dev])
+        dist.all_reduce(both)
+        dist.all_reduce(metrics.acc)
+        dev_loss_running, num_tokens_dev = both[0], both[1]
+    model.train()
+    out: dict[str, float | int] = {"dev_loss": float((dev_loss_running / num_tokens_dev).item())}
+    out.update(metrics.result())
+    k = metrics.topk
+    per_type = " | ".join(f"{name}: loss {out[f'dev_loss.{name}']:.4f} acc {out[f'dev_acc.{name}']:.4f} top{k} {out[f'dev_acc_top{k}.{name}']:.4f}"
+                          for name in metrics.names + ["all"] if out[f"dev_n_labels.{name}"])
+    LOGGER.info(f"Epoch {epoch + 1:03d} | Global Step {global_step} | Dev Loss: {out['dev_loss']:.4f}" + (f" | {per_type}" if per_type else ""))
+    return out
+
+
 def compute_dataset_loss(model, data_dev, loss_fn: Callable, epoch: int, global_step: int, steps_per_epoch: int,
                          device: torch.device, *, join_batches: int = 0, max_tokens: int = 32768, pad_id: int = 0, prefetch: int = 2) -> float:
     """The reference's signature; the keyword arguments are this build's (``join_batches`` <= 1: every dev batch on its own, as the reference)."""

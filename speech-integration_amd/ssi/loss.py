@@ -63,7 +63,9 @@ class _CrossEntropyFn(torch.autograd.Function):
         return work[:, : ctx.vocab], None, None
 
 
-def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable) -> Tensor:
+def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metrics=None) -> Tensor:
+    """``label_metrics`` (``ssi.eval.LabelMetrics``, forward-only, not in the reference): loss and top-k hits of the shifted labels are added to it
+    per token type — by the cross-entropy kernel on the fused route, in plain torch from the logits on the literal one.  The loss is unchanged."""
     labels = batch["labels"]
     ignore_index = loss_fn.ignore_index
     labels = torch.hstack((labels[..., 1:], torch.full_like(labels[..., -1:], ignore_index)))  # new tensor: batch untouched
@@ -75,6 +77,8 @@ def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable) -> Tensor:
             extra["attn_plan"] = batch["attn_plan"]
         if batch.get("loss_weights") is not None:  # an accumulation window run as one batch (ssi/data/window.py): weights per SHIFTED label
             extra["loss_weights"] = batch["loss_weights"]
+        if label_metrics is not None:
+            extra["label_metrics"] = label_metrics
         return model.fused_loss(batch["tokens"], labels, ignore_index, input_pos=batch.get("input_pos"), **extra)
     if batch.get("loss_weights") is not None:
         raise ValueError("loss_weights need the fused LM head + cross-entropy of the HIP decoder (model.fused_loss)")
@@ -85,6 +89,8 @@ def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable) -> Tensor:
         encoder_mask=batch.get("encoder_mask"),
         input_pos=batch.get("input_pos"),
     )
+    if label_metrics is not None:
+        label_metrics.add_logits(logits, labels, ignore_index)
     if not isinstance(logits, list):
         labels = labels.reshape(-1)
         logits = logits.reshape(-1, logits.size(-1))

@@ -694,14 +694,21 @@ class HipLlamaDecoder(nn.Module):
         return logits.float()
 
     def fused_loss(self, tokens: Tensor, shifted_labels: Tensor, ignore_index: int = CROSS_ENTROPY_IGNORE_IDX,
-                   input_pos: Optional[Tensor] = None, attn_plan=None, loss_weights: Optional[Tensor] = None) -> Tensor:
+                   input_pos: Optional[Tensor] = None, attn_plan=None, loss_weights: Optional[Tensor] = None,
+                   label_metrics=None) -> Tensor:
         """Mean NLL over non-ignored (already shifted) labels with the LM head + CE fused: equals
         ``CEWithChunkedOutputLoss()(model(tokens, input_pos=...), shifted_labels)`` of the reference for any chunk count.
         ``input_pos`` ([B, S], restarting at 0 with every document): packed rows, block-causal attention.  ``attn_plan``
         (``build_attn_plan(input_pos)`` made on the host beside the batch): the attention backward then runs its pipelined kernels on the
         packed rows; without one (and with ``input_pos`` on the device) the round-1..3 kernels run — same results to rounding.
         ``loss_weights`` (fp32 ``[B, S]``, >= 0, aligned with ``shifted_labels``): the result is ``sum_i w_i nll_i / n_valid`` — how an
-        accumulation window that runs as one batch keeps the reference's per-micro-batch normalisation (``ssi/data/window.py``)."""
+        accumulation window that runs as one batch keeps the reference's per-micro-batch normalisation (``ssi/data/window.py``).
+        ``label_metrics`` (``ssi.eval.LabelMetrics``; forward-only calls): the cross-entropy launch also ranks every label in its row and the
+        per-type sums of nll, top-1 and top-k hits are ADDED to ``label_metrics.acc`` on the device (``ssi_ce_fwd_metrics`` +
+        ``ssi_ce_metrics_reduce``); the returned loss is bit-identical with and without it.  ``None``: exactly the launches of before."""
+        if label_metrics is not None and torch.is_grad_enabled() and self.training:
+            raise RuntimeError("fused_loss(label_metrics=...) is forward-only (the dev set): call it under torch.no_grad() / inference_mode() "
+                               "or on model.eval(); the training step's cross-entropy kernel does not rank labels")
         tokens = self._check_inputs(tokens, None, None, None, input_pos)
         if loss_weights is not None:
             if loss_weights.shape != tokens.shape:
@@ -713,17 +720,24 @@ class HipLlamaDecoder(nn.Module):
         if torch.is_grad_enabled() and self.training:
             return _FusedLossFn.apply(self, tokens, labels, ignore_index, self._anchor, input_pos, attn_plan, weights)
         hn = self._forward_hidden(tokens, save=False, input_pos=input_pos)
-        return self._ce_forward(hn, labels, ignore_index, write_grad=False, weights=weights)[0]
+        return self._ce_forward(hn, labels, ignore_index, write_grad=False, weights=weights, label_metrics=label_metrics)[0]
 
     def _ce_forward(self, hn: Tensor, labels: Tensor, ignore_index: int, write_grad: bool,
-                    weights: Optional[Tensor] = None) -> tuple[Tensor, Tensor, Tensor]:
+                    weights: Optional[Tensor] = None, label_metrics=None) -> tuple[Tensor, Tensor, Tensor]:
         """Tied head + cross-entropy: (mean loss, stats, logits buffer — which holds softmax - onehot when ``write_grad``).  The same
         three launches as the one-call ABI entry ``ssi_lmhead_ce_fwd`` (``ops.lmhead_ce_fwd``), issued one by one here so that ``bench.py``
         can time the head GEMM on its own."""
         T = hn.shape[0]
         logits = self._head_logits(hn, "logits" if write_grad else "logits.x")
         row_loss = self._arena.get("row_loss" if write_grad else "row_loss.x", (T,), torch.float32)
-        ops.ce_fwd(logits, labels, self.vocab_size, ignore_index, row_loss, None, write_grad, row_weight=weights)
+        if label_metrics is None:
+            ops.ce_fwd(logits, labels, self.vocab_size, ignore_index, row_loss, None, write_grad, row_weight=weights)
+        else:  # forward-only (fused_loss refuses it under grad): the same row losses, plus nll and rank of every label, summed per type
+            assert not write_grad
+            row_nll = self._arena.get("row_nll.x", (T,), torch.float32)
+            row_rank = self._arena.get("row_rank.x", (T,), torch.int32)
+            ops.ce_fwd_metrics(logits, labels, self.vocab_size, ignore_index, row_loss, None, row_nll, row_rank, row_weight=weights)
+            ops.ce_metrics_reduce(row_nll, row_rank, labels, label_metrics.ranges_dev, label_metrics.topk, label_metrics.acc, accumulate=True)
         out = torch.empty(4, dtype=torch.float32, device=self.device)
         ops.ce_reduce(row_loss, labels, self.vocab_size, ignore_index, out)
         self.label_errors = out[3]  # device scalar: labels outside [0, vocab); the trainer folds it into its one read-back and raises

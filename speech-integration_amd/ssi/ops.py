@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
 __all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "swiglu_fwd",
-           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "set_impl", "set_attn_impl", "attn_last_dispatch",
+           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
 
@@ -320,6 +320,34 @@ def ce_reduce(row_loss: Tensor, labels: Tensor, vocab: int, ignore_index: int, o
     assert out.dtype == torch.float32 and out.numel() >= 4 and labels.is_contiguous()
     check(_lib.load().ssi_ce_reduce(ptr(row_loss), ptr(labels), labels.numel(), vocab, ignore_index, ptr(out), stream_ptr()),
           "ssi_ce_reduce")
+
+
+def ce_fwd_metrics(logits: Tensor, labels: Tensor, vocab: int, ignore_index: int, row_loss: Tensor, row_lse: Tensor | None, row_nll: Tensor,
+                   row_rank: Tensor, row_weight: Tensor | None = None) -> None:
+    """Forward-only ``ce_fwd`` (``write_grad=False``; ``row_loss`` and ``row_lse`` bit for bit) that also writes the unweighted ``row_nll`` (fp32)
+    and ``row_rank`` (int32): the label's position in a stable descending sort of its row, -1 for an ignored or out-of-range label."""
+    assert logits.dim() == 2 and logits.stride(1) == 1 and labels.dtype == torch.int64 and labels.is_contiguous()
+    rows = logits.shape[0]
+    assert labels.numel() == rows and row_loss.dtype == torch.float32 and row_loss.numel() >= rows
+    assert row_lse is None or (row_lse.dtype == torch.float32 and row_lse.numel() >= rows)
+    assert row_nll.dtype == torch.float32 and row_nll.is_contiguous() and row_nll.numel() >= rows
+    assert row_rank.dtype == torch.int32 and row_rank.is_contiguous() and row_rank.numel() >= rows
+    assert row_weight is None or (row_weight.dtype == torch.float32 and row_weight.is_contiguous() and row_weight.numel() == rows
+                                  and row_weight.device == logits.device)
+    check(_lib.load().ssi_ce_fwd_metrics(ptr(logits), logits.stride(0), ptr(labels), ptr(row_weight), rows, vocab, ignore_index, ptr(row_loss),
+                                         ptr(row_lse), ptr(row_nll), ptr(row_rank), dtype_code(logits.dtype), stream_ptr()), "ssi_ce_fwd_metrics")
+
+
+def ce_metrics_reduce(row_nll: Tensor, row_rank: Tensor, labels: Tensor, ranges: Tensor, topk: int, out: Tensor, accumulate: bool = False) -> None:
+    """``out`` (fp64 ``[n_ranges + 1, 4]``) = per label range, and last for every valid label: n_labels, sum nll, n(rank == 0), n(rank < topk).
+    ``ranges``: int64 inclusive ``[lo, hi]`` pairs as for ``count_tokens``.  ``accumulate``: add to what ``out`` holds."""
+    n_ranges, rows = ranges.numel() // 2, labels.numel()
+    assert row_nll.dtype == torch.float32 and row_nll.is_contiguous() and row_nll.numel() >= rows
+    assert row_rank.dtype == torch.int32 and row_rank.is_contiguous() and row_rank.numel() >= rows
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and ranges.dtype == torch.int64 and ranges.is_contiguous()
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= 4 * (n_ranges + 1) and topk >= 1
+    check(_lib.load().ssi_ce_metrics_reduce(ptr(row_nll), ptr(row_rank), ptr(labels), rows, ptr(ranges), n_ranges, int(topk), int(accumulate),
+                                            ptr(out), stream_ptr()), "ssi_ce_metrics_reduce")
 
 
 def lmhead_ce_fwd(hidden: Tensor, table: Tensor, labels: Tensor, vocab: int, ignore_index: int, logits_ws: Tensor, row_loss: Tensor,

@@ -37,7 +37,7 @@ from . import __version__
 from .constants import DEBUGGING_TAG, MODEL_KEY, SEED
 from .distributed import GradSync, all_reduce_scalars, get_world_size_and_rank, init_distributed
 from .data.unpad import loss_inputs
-from .eval import batch_to_device, compute_dataset_loss
+from .eval import batch_to_device, compute_dataset_loss, compute_dataset_metrics
 from .llama_configs import configllama3_2_1b
 from .loss import CEWithChunkedOutputLoss, compute_loss
 from .lr_schedule import get_lr, setup_lr_scheduler
@@ -133,6 +133,7 @@ class Trainer:
         self._lagged: list[dict[str, Any]] = []                # windows whose read-back is on its way (``_optimizer_step_lagged``)
         self._lag_buffers: list[Tensor] = []                   # page-locked buffers of finished read-backs, reused
         self._t_last_arrival = 0.0                             # when the previous window's results were seen on the host
+        self.dev_metrics: dict[str, Any] | None = None         # per-token-type keys of the last evaluation (``eval_token_metrics``)
         for name in self._FILLED_BY_SETUP:
             setattr(self, name, None)
         for name, zero in self._COUNTERS.items():
@@ -617,12 +618,18 @@ class Trainer:
         self._log_metrics(epoch, iter_idx, mean_loss)
 
     def _evaluate(self) -> float:
-        return compute_dataset_loss(self.model, self.data_dev, self.loss_fn,
-                                    epoch=self.global_step // self.geometry.steps_per_epoch, global_step=self.global_step,
-                                    steps_per_epoch=self.geometry.steps_per_epoch, device=self.device,
-                                    join_batches=int(self.cfg.get("eval_join_batches", 16) or 0) if self.cfg.get("padding_free", True) else 0,
-                                    max_tokens=int(self.cfg.get("fused_window_max_tokens", 32768)), pad_id=int(getattr(self.tokenizer, "pad_id", 0) or 0),
-                                    prefetch=int(self.cfg.get("prefetch_batches", 2) or 0))
+        """The dev loss; with ``eval_token_metrics`` the per-token-type keys of the same pass are left in ``self.dev_metrics`` for the log record."""
+        kwargs = dict(epoch=self.global_step // self.geometry.steps_per_epoch, global_step=self.global_step,
+                      steps_per_epoch=self.geometry.steps_per_epoch, device=self.device,
+                      join_batches=int(self.cfg.get("eval_join_batches", 16) or 0) if self.cfg.get("padding_free", True) else 0,
+                      max_tokens=int(self.cfg.get("fused_window_max_tokens", 32768)), pad_id=int(getattr(self.tokenizer, "pad_id", 0) or 0),
+                      prefetch=int(self.cfg.get("prefetch_batches", 2) or 0))
+        self.dev_metrics = None
+        if not self.cfg.get("eval_token_metrics", False):
+            return compute_dataset_loss(self.model, self.data_dev, self.loss_fn, **kwargs)
+        self.dev_metrics = compute_dataset_metrics(self.model, self.data_dev, self.loss_fn, token_type_ranges=self.token_type_ranges,
+                                                   topk=int(self.cfg.get("eval_topk", 5)), **kwargs)
+        return self.dev_metrics["dev_loss"]
 
     def _log_metrics(self, epoch: int, iter_idx: int, loss_to_log: float, snapshot: dict[str, Any] | None = None) -> None:
         """One console line per optimizer step; the metric record (same keys as the reference logs to W&B, ``trainer.py:440-475``) every
@@ -656,6 +663,8 @@ class Trainer:
             record["grad_norm"] = None if snapshot["grad_norm"] is None else float(snapshot["grad_norm"])
         if dev_loss is not None:
             record["dev_loss"] = dev_loss
+            if self.dev_metrics is not None:  # eval_token_metrics: dev_loss.<type>, dev_acc.<type>, dev_acc_top<k>.<type>, dev_n_labels.<type>
+                record.update(self.dev_metrics)
         if self.rank == 0:
             self.wandb_logger.log_dict(record, step=step)
 

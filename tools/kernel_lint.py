@@ -31,7 +31,8 @@ from dataclasses import dataclass, field
 LLVM = "/opt/rocm/lib/llvm/bin"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT_LIB = os.path.join(ROOT, "speech-integration_amd", "libssi_hip.so")
-NO_SCRATCH = ("attn_bwd_dq2_kernel", "attn_bwd_dkv2_kernel", "attn_fwd_kernel", "gemm_nt4dma_kernel", "gemm_f32_mfma_kernel")
+NO_SCRATCH = ("attn_bwd_dq2_kernel", "attn_bwd_dkv2_kernel", "attn_fwd_kernel", "gemm_nt4dma_kernel", "gemm_f32_mfma_kernel",
+              "ce_row_bf16_metrics_kernel", "ce_fwd_metrics_kernel")
 PINNED_LOOPS = ("attn_bwd_dq2_kernel", "attn_bwd_dkv2_kernel")   # kernels whose main loops are inline-asm MFMAs on pinned register classes
 MAIN_LOOP_MFMAS = 32
 
@@ -228,7 +229,10 @@ def compare(lib: str, other: str) -> tuple[list[str], int]:
             return {k.name: k for co in extract(path, wd) for k in kernels_of(co)}
 
     def stream(k: Kernel) -> list[tuple]:
-        return [(i.op, i.args, None if i.target is None else i.target - k.addr) for i in k.ins]
+        ins = list(k.ins)
+        while ins and ins[-1].op == "s_nop":  # fill between the last s_endpgm and the next symbol or the end of the section: not the kernel's code
+            ins.pop()
+        return [(i.op, i.args, None if i.target is None else i.target - k.addr) for i in ins]
 
     a, b = load(lib), load(other)
     diffs = [f"{n}: only in {lib}" for n in sorted(set(a) - set(b))] + [f"{n}: only in {other}" for n in sorted(set(b) - set(a))]
