@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 10 /* 10: + ssi_ce_fwd_metrics, ssi_ce_metrics_reduce (dev-set loss and top-k accuracy per token type)
+#define SSI_ABI_VERSION 11 /* 11: + ssi_adamw_step_sr, ssi_round_bf16_sr (bf16 AdamW whose three stores round stochastically, counter-based)
+                           * 10: + ssi_ce_fwd_metrics, ssi_ce_metrics_reduce (dev-set loss and top-k accuracy per token type)
                            * 9: ssi_adamw_step takes its hyper-parameters in double (the coefficients of torch's fused AdamW)
                            * 8: + ssi_ce_fwd_weighted (per-row loss weights: an accumulation window run as ONE batch keeps the reference's
                            *    per-micro-batch normalisation, ssi/data/window.py)
@@ -316,6 +317,24 @@ int ssi_sumsq(const void* x, int64_t n, int dtype, float* out, void* workspace, 
 int ssi_adamw_step(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, double lr, double beta1,
                    double beta2, double eps, double weight_decay, int64_t step, const float* grad_scale_dev, int zero_grad,
                    int dtype, void* stream);
+/* ssi_adamw_step with STOCHASTIC rounding of the three bf16 stores (ABI v11; not in the reference, off by default: HipAdamW's
+ * stochastic_rounding).  Same arguments, coefficients, fp32 arithmetic, flag bits and tail handling; dtype must be SSI_BF16, step < 2^32,
+ * elem_offset % 8 == 0.  The rounding, on the bit pattern u of the fp32 value x with 16 random bits r:
+ *   exponent of u all ones (inf, NaN): the round-to-nearest conversion;  otherwise t = u + r and the result is t >> 16, or u >> 16 where t
+ *   would have an all-ones exponent (a finite value is never carried into inf).
+ * So a value bf16 holds exactly (+-0 included) never changes, anything else becomes one of its two bf16 neighbours, the one away from zero
+ * with probability (u & 0xFFFF) / 65536.  The bits are stateless: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9,
+ * 0xBB67AE85) with key (seed & 0xFFFFFFFF, seed >> 32) and counter (j & 0xFFFFFFFF, j >> 32, step, tensor), where e = elem_offset + i is
+ * the GLOBAL index of element i (its place in the model's flat buffer, not in the slice of this launch), j = e >> 3, and tensor is 0 for
+ * param, 1 for exp_avg, 2 for exp_avg_sq; with output words w0..w3 and k = e & 7, r = (w[k >> 1] >> 16 (k & 1)) & 0xFFFF.  The same (seed,
+ * step, e, tensor) gives the same bits in every launch: a buffer updated in slices, on any rank, before or after a resume, comes out the
+ * same bit for bit. */
+int ssi_adamw_step_sr(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, double lr, double beta1, double beta2,
+                      double eps, double weight_decay, int64_t step, const float* grad_scale_dev, int zero_grad, int dtype,
+                      uint64_t seed, int64_t elem_offset, void* stream);
+/* The rounding of ssi_adamw_step_sr on its own, an fp32 -> bf16 cast: dst[i] = sr_bf16(src[i], bits of (seed, step, elem_offset + i, tensor)).
+ * src and dst 16-byte aligned, 0 <= step < 2^32, tensor >= 0, elem_offset % 8 == 0. */
+int ssi_round_bf16_sr(const float* src, void* dst, int64_t n, uint64_t seed, int64_t step, int tensor, int64_t elem_offset, void* stream);
 
 #ifdef __cplusplus
 }

@@ -663,6 +663,139 @@ extern "C" int ssi_adamw_step(void* param, void* grad, void* exp_avg, void* exp_
 }
 
 // =====================================================================================================================
+// K13s AdamW with stochastic rounding of the three bf16 stores (ABI v11; opt-in, HipAdamW(stochastic_rounding=True)).  Round-to-nearest
+// drops every update below half a bf16 step: v * 0.999 rounds back to v for every bf16 v, and a weight at 1.0 never moves at lr 2e-4
+// (profiles/LAB_NOTES.md).  The rounding is defined on the bit pattern and the random bits come from a counter-based generator keyed by
+// (seed, step, global element index, tensor): no state, the same bits in every launch, on every rank and after every resume.
+// =====================================================================================================================
+struct Philox4 { uint32_t w[4]; };
+
+// Philox4x32-10 (Salmon et al., SC'11): ten rounds of two 32x32->64 multiplies, the key bumped by the Weyl constants between rounds
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return Philox4{{c0, c1, c2, c3}};
+}
+
+// the 64 random bits of tensor `tensor` for the 8-element vector j (= global element index >> 3) at optimizer step `step`
+__device__ __forceinline__ Philox4 sr_bits(int64_t j, uint32_t step, uint32_t tensor, uint64_t seed) {
+    return philox4x32_10((uint32_t)j, (uint32_t)((uint64_t)j >> 32), step, tensor, (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+// fp32 -> bf16 bit pattern, element k of its vector: add 16 random bits below the bf16 mantissa and truncate, so the neighbour away from zero
+// is taken with probability (low 16 bits) / 65536 and a value bf16 holds is never changed.  inf / NaN: the round-to-nearest conversion; a
+// finite value is never carried into inf.
+__device__ __forceinline__ unsigned short sr_bf16(float x, const Philox4& b, int k) {
+    const uint32_t u = __float_as_uint(x);
+    if ((u & 0x7F800000u) == 0x7F800000u) return __builtin_bit_cast(unsigned short, (bf16_t)x);
+    const uint32_t t = u + ((b.w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu);
+    return (unsigned short)(((t & 0x7F800000u) == 0x7F800000u ? u : t) >> 16);
+}
+__device__ __forceinline__ bf16_t sr_bf16_value(float x, const Philox4& b, int k) { return __builtin_bit_cast(bf16_t, sr_bf16(x, b, k)); }
+
+// adamw_kernel<bf16_t> with the three stores rounded by sr_bf16: the fp32 arithmetic is that kernel's, expression for expression
+__global__ __launch_bounds__(256) void adamw_sr_kernel(bf16_t* __restrict__ p, bf16_t* __restrict__ g, bf16_t* __restrict__ m,
+                                                       bf16_t* __restrict__ v, int64_t n, float decay, float w1, float beta2, float w2,
+                                                       float eps, float step_size, float inv_bc2_sqrt,
+                                                       const float* __restrict__ grad_scale_dev, int zero_grad, uint64_t seed,
+                                                       uint32_t step, int64_t vec_offset) {
+    using T = bf16_t;
+    constexpr int N = Vec16<T>::N;
+    static_assert(N == 8, "one Philox call per tensor covers the 8 elements of a 16-byte vector");
+    const float gs = grad_scale_dev ? *grad_scale_dev : 1.f;
+    if ((zero_grad & 2) && !(fabsf(gs) < INFINITY)) return;
+    zero_grad &= 1;
+    const int64_t nvec = n / N;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+        Vec16<T> pp = load16_nt(p + i * N), gg = load16_nt(g + i * N), mm = load16_nt(m + i * N), vv = load16_nt(v + i * N);
+        const Philox4 rp = sr_bits(vec_offset + i, step, 0, seed), rm = sr_bits(vec_offset + i, step, 1, seed),
+                      rv = sr_bits(vec_offset + i, step, 2, seed);
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const float gr = gg.get(k) * gs;
+            float pf = pp.get(k);
+            pf *= decay;
+            const float mf = mm.get(k) + w1 * (gr - mm.get(k));
+            const float vf = beta2 * vv.get(k) + w2 * gr * gr;
+            const float denom = sqrtf(vf) * inv_bc2_sqrt + eps;
+            pf -= step_size * mf / denom;
+            pp.v[k] = sr_bf16_value(pf, rp, k); mm.v[k] = sr_bf16_value(mf, rm, k); vv.v[k] = sr_bf16_value(vf, rv, k);
+            if (zero_grad) gg.set(k, 0.f);
+        }
+        store16_nt(p + i * N, pp); store16_nt(m + i * N, mm); store16_nt(v + i * N, vv);
+        if (zero_grad) store16_nt(g + i * N, gg);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n - nvec * N)) {
+        const int k = threadIdx.x;   // the slice starts on a vector boundary of the global index, so the tail is the head of vector vec_offset + nvec
+        const int64_t i = nvec * N + k;
+        const float gr = to_f32<T>(g[i]) * gs;
+        float pf = to_f32<T>(p[i]);
+        pf *= decay;
+        const float mf = to_f32<T>(m[i]) + w1 * (gr - to_f32<T>(m[i]));
+        const float vf = beta2 * to_f32<T>(v[i]) + w2 * gr * gr;
+        pf -= step_size * mf / (sqrtf(vf) * inv_bc2_sqrt + eps);
+        p[i] = sr_bf16_value(pf, sr_bits(vec_offset + nvec, step, 0, seed), k);
+        m[i] = sr_bf16_value(mf, sr_bits(vec_offset + nvec, step, 1, seed), k);
+        v[i] = sr_bf16_value(vf, sr_bits(vec_offset + nvec, step, 2, seed), k);
+        if (zero_grad) g[i] = from_f32<T>(0.f);
+    }
+}
+
+extern "C" int ssi_adamw_step_sr(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, double lr, double beta1,
+                                 double beta2, double eps, double weight_decay, int64_t step, const float* grad_scale_dev,
+                                 int zero_grad, int dtype, uint64_t seed, int64_t elem_offset, void* stream) {
+    SSI_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n >= 0 && step >= 1 && step < ((int64_t)1 << 32));
+    SSI_CHECK_ARG(((uintptr_t)param % 16) == 0 && ((uintptr_t)grad % 16) == 0 && ((uintptr_t)exp_avg % 16) == 0 &&
+                  ((uintptr_t)exp_avg_sq % 16) == 0);
+    SSI_CHECK_ARG(dtype == SSI_BF16);   // fp32 storage has nothing to round
+    SSI_CHECK_ARG(elem_offset >= 0 && elem_offset % 8 == 0);
+    if (n == 0) return SSI_OK;
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);   // the coefficients of ssi_adamw_step
+    const float step_size = (float)(lr / bc1);
+    const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+    hipLaunchKernelGGL(adamw_sr_kernel, dim3(stream_grid(n / 8 + 1, 1 << 20)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)param,
+                       (bf16_t*)grad, (bf16_t*)exp_avg, (bf16_t*)exp_avg_sq, n, (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1),
+                       (float)beta2, (float)(1.0 - beta2), (float)eps, step_size, inv_bc2_sqrt, grad_scale_dev, zero_grad, seed,
+                       (uint32_t)step, elem_offset / 8);
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+// the rounding of adamw_sr_kernel on its own: dst[i] = sr_bf16(src[i]) with the bits of (seed, step, elem_offset + i, tensor)
+__global__ __launch_bounds__(256) void round_bf16_sr_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, int64_t n, uint64_t seed,
+                                                            uint32_t step, uint32_t tensor, int64_t vec_offset) {
+    const int64_t nvec = n / 8;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+        const Vec16<float> a = load16(src + i * 8), b = load16(src + i * 8 + 4);
+        const Philox4 r = sr_bits(vec_offset + i, step, tensor, seed);
+        Vec16<bf16_t> o;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o.v[k] = sr_bf16_value(k < 4 ? a.get(k) : b.get(k - 4), r, k);
+        store16(dst + i * 8, o);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n - nvec * 8)) {
+        const int k = threadIdx.x;
+        dst[nvec * 8 + k] = sr_bf16_value(src[nvec * 8 + k], sr_bits(vec_offset + nvec, step, tensor, seed), k);
+    }
+}
+
+extern "C" int ssi_round_bf16_sr(const float* src, void* dst, int64_t n, uint64_t seed, int64_t step, int tensor, int64_t elem_offset,
+                                 void* stream) {
+    SSI_CHECK_ARG(src && dst && n >= 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0);
+    SSI_CHECK_ARG(step >= 0 && step < ((int64_t)1 << 32) && tensor >= 0 && elem_offset >= 0 && elem_offset % 8 == 0);
+    if (n == 0) return SSI_OK;
+    hipLaunchKernelGGL(round_bf16_sr_kernel, dim3(stream_grid(n / 8 + 1, 1 << 20)), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, n,
+                       seed, (uint32_t)step, (uint32_t)tensor, elem_offset / 8);
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+// =====================================================================================================================
 // 2-D transpose dst[c][r] = src[r][c] (64 x 64 tiles through LDS; 16-B global accesses on both sides).  Used once per
 // optimizer step to refresh the [in, out] copies of the projection weights, so that the data-gradient GEMMs
 // dX = dY W run in the k-contiguous (NT) operand form instead of the transposed-read form.

@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
 __all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "swiglu_fwd",
-           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "set_impl", "set_attn_impl", "attn_last_dispatch",
+           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "round_bf16_sr", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
 
@@ -403,12 +403,28 @@ def sumsq(x: Tensor, out: Tensor, workspace: Tensor | None = None) -> None:
 
 def adamw_step(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, *, lr: float, beta1: float, beta2: float,
                eps: float, weight_decay: float, step: int, grad_scale_dev: Tensor | None = None,
-               zero_grad: bool = False, skip_nonfinite_scale: bool = False) -> None:
+               zero_grad: bool = False, skip_nonfinite_scale: bool = False, sr_seed: int | None = None, elem_offset: int = 0) -> None:
     """``skip_nonfinite_scale``: the launch changes nothing when ``*grad_scale_dev`` is inf or NaN (1 / 0 label tokens: the reference skips such
-    a window's optimizer step; an update issued before the host knows the count must do the same by itself)."""
+    a window's optimizer step; an update issued before the host knows the count must do the same by itself).  ``sr_seed`` (bf16 only): the three
+    stores round stochastically (``ssi_adamw_step_sr``) with the random bits of ``(sr_seed, step, elem_offset + i, tensor)`` — ``elem_offset``
+    is the place of the slice's first element in the whole buffer, a multiple of 8; without a seed it is not used."""
     assert param.is_contiguous() and grad.is_contiguous() and exp_avg.is_contiguous() and exp_avg_sq.is_contiguous()
     assert param.numel() == grad.numel() == exp_avg.numel() == exp_avg_sq.numel()
     assert param.dtype == grad.dtype == exp_avg.dtype == exp_avg_sq.dtype
+    flags = int(zero_grad) | (2 if skip_nonfinite_scale else 0)
+    if sr_seed is not None:
+        check(_lib.load().ssi_adamw_step_sr(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), lr, beta1, beta2,
+                                            eps, weight_decay, step, ptr(grad_scale_dev), flags, dtype_code(param.dtype),
+                                            int(sr_seed) & 0xFFFFFFFFFFFFFFFF, elem_offset, stream_ptr()), "ssi_adamw_step_sr")
+        return
     check(_lib.load().ssi_adamw_step(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), lr, beta1, beta2,
-                                     eps, weight_decay, step, ptr(grad_scale_dev), int(zero_grad) | (2 if skip_nonfinite_scale else 0), dtype_code(param.dtype),
+                                     eps, weight_decay, step, ptr(grad_scale_dev), flags, dtype_code(param.dtype),
                                      stream_ptr()), "ssi_adamw_step")
+
+
+def round_bf16_sr(src: Tensor, dst: Tensor, *, seed: int, step: int, tensor: int, elem_offset: int = 0) -> None:
+    """fp32 -> bf16 by the stochastic rounding of ``adamw_step(sr_seed=...)``: the bits of ``(seed, step, elem_offset + i, tensor)``."""
+    assert src.is_contiguous() and dst.is_contiguous() and src.numel() == dst.numel()
+    assert src.dtype == torch.float32 and dst.dtype == torch.bfloat16
+    check(_lib.load().ssi_round_bf16_sr(ptr(src), ptr(dst), src.numel(), int(seed) & 0xFFFFFFFFFFFFFFFF, step, tensor, elem_offset,
+                                        stream_ptr()), "ssi_round_bf16_sr")

@@ -5,7 +5,8 @@
 kernel over the model's flat parameter / gradient / moment buffers: decoupled weight decay, fp32 op-math, a single
 rounding on store — the semantics of ``torch.optim.AdamW(fused=True)`` (K13), with ``scale_grads`` (K11) and the
 clip coefficient (K12) folded in as a device-side gradient multiplier.  The gradient buffer is not zeroed: the first backward of the
-next accumulation window overwrites it (``HipLlamaDecoder`` gradient-buffer protocol)."""
+next accumulation window overwrites it (``HipLlamaDecoder`` gradient-buffer protocol).  ``stochastic_rounding`` (bf16 only, off by default,
+not in the reference) rounds the three stores stochastically instead of to nearest, with stateless counter-based random bits."""
 
 from __future__ import annotations
 
@@ -20,7 +21,8 @@ from . import ops
 
 class HipAdamW(torch.optim.Optimizer):
     def __init__(self, params: Iterable, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-2, amsgrad: bool = False, fused: bool | None = None, *, model=None, **unused: Any):
+                 weight_decay: float = 1e-2, amsgrad: bool = False, fused: bool | None = None, *, model=None,
+                 stochastic_rounding: bool = False, stochastic_rounding_seed: int | None = None, **unused: Any):
         if amsgrad:
             raise NotImplementedError("amsgrad=True is not supported (reference default: false, conf/training.yaml:8)")
         if unused:
@@ -32,6 +34,18 @@ class HipAdamW(torch.optim.Optimizer):
         super().__init__(params, defaults)
         if len(self.param_groups) != 1:
             raise NotImplementedError("one param group expected (the reference passes model.parameters())")
+        # Stochastic rounding of the bf16 stores (not in the reference; off by default).  Round-to-nearest drops every update below half a
+        # bf16 step: exp_avg_sq * 0.999 rounds back for every bf16 value, and a weight at 1.0 never moves at lr 2e-4.  The random bits are a
+        # pure function of (seed, step, element index in the flat buffer, tensor): slices, ranks and resumes all see the same ones.  Flag
+        # and seed belong to the run's configuration, not to the optimizer state: they are kept out of ``param_groups``, which
+        # ``load_state_dict`` replaces wholesale, so a state saved either way loads into a run configured either way.
+        if stochastic_rounding and model._flat.dtype != torch.bfloat16:
+            raise ValueError(f"stochastic_rounding=true needs dtype=bf16: it rounds AdamW's bf16 stores, and the model's parameters are {model._flat.dtype}")
+        if stochastic_rounding:
+            from .constants import SEED
+            self._sr_seed = int(SEED if stochastic_rounding_seed is None else stochastic_rounding_seed)   # the same on every rank
+        else:
+            self._sr_seed = None
         self.model = model
         model._hip_optimizer = weakref.ref(self)  # scale_grads / clip_grad_norm_ may defer their factor only while THIS optimizer consumes it
         self._exp_avg = torch.zeros_like(model._flat)
@@ -85,7 +99,7 @@ class HipAdamW(torch.optim.Optimizer):
             self._side.wait_event(ev)
             ops.adamw_step(m._flat[lo:hi], m._flat_grad[lo:hi], self._exp_avg[lo:hi], self._exp_avg_sq[lo:hi], lr=float(g["lr"]),
                            beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"], step=a["step"],
-                           grad_scale_dev=a["scale"], zero_grad=False, skip_nonfinite_scale=True)
+                           grad_scale_dev=a["scale"], zero_grad=False, skip_nonfinite_scale=True, sr_seed=self._sr_seed, elem_offset=lo)
         a["done"].append((lo, hi))
 
     def cancel_overlap(self) -> None:
@@ -113,7 +127,7 @@ class HipAdamW(torch.optim.Optimizer):
                 if lo > pos:  # a gap between buckets (none in HipLlamaDecoder's layout): the plain update, same scale
                     ops.adamw_step(m._flat[pos:lo], m._flat_grad[pos:lo], self._exp_avg[pos:lo], self._exp_avg_sq[pos:lo], lr=float(g["lr"]),
                                    beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"], step=self._step_count,
-                                   grad_scale_dev=a["scale"], zero_grad=False)
+                                   grad_scale_dev=a["scale"], zero_grad=False, sr_seed=self._sr_seed, elem_offset=pos)
                 pos = max(pos, hi)
             m.pending_grad_scale = None  # (scale_grads of the caller: already applied, bucket by bucket)
             if self._views_ready:
@@ -135,7 +149,8 @@ class HipAdamW(torch.optim.Optimizer):
             if hi > lo:
                 ops.adamw_step(m._flat[lo:hi], m._flat_grad[lo:hi], self._exp_avg[lo:hi], self._exp_avg_sq[lo:hi], lr=float(g["lr"]),
                                beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"],
-                               step=self._step_count, grad_scale_dev=m.pending_grad_scale, zero_grad=False)
+                               step=self._step_count, grad_scale_dev=m.pending_grad_scale, zero_grad=False, sr_seed=self._sr_seed,
+                               elem_offset=lo)
 
         sync = getattr(m, "grad_sync", None)
         tail = sync.deferred_range() if sync is not None and hasattr(sync, "deferred_range") else None
@@ -200,9 +215,15 @@ def _to_container(node):
 
 def setup_optimizer(cfg, model, optimizer_state_dict: dict[str, Any] | None = None) -> torch.optim.Optimizer:
     optimizer_kwargs = _to_container(cfg.optimizer)
+    stochastic = bool(optimizer_kwargs.pop("stochastic_rounding", False))   # (both keys are this project's, not torch's)
+    sr_seed = optimizer_kwargs.pop("stochastic_rounding_seed", None)
     if hasattr(model, "_flat"):
-        optimizer = HipAdamW(model.parameters(), model=model, **optimizer_kwargs)
+        optimizer = HipAdamW(model.parameters(), model=model, stochastic_rounding=stochastic, stochastic_rounding_seed=sr_seed,
+                             **optimizer_kwargs)
     else:  # foreign module (tests with stand-in models): the reference's own choice
+        if stochastic:
+            raise ValueError("optimizer.stochastic_rounding=true needs the HIP decoder (HipAdamW on its flat buffers); "
+                             f"{type(model).__name__} is updated by torch.optim.AdamW, which has no such rounding")
         optimizer_kwargs.pop("fused", None)
         optimizer = torch.optim.AdamW(model.parameters(), **optimizer_kwargs)
     if optimizer_state_dict is not None:
