@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 11 /* 11: + ssi_adamw_step_sr, ssi_round_bf16_sr (bf16 AdamW whose three stores round stochastically, counter-based)
+#define SSI_ABI_VERSION 12 /* 12: + ssi_ce_fwd_z (cross-entropy with the auxiliary z-loss z * log^2 Z in its gradient; opt-in)
+                           * 11: + ssi_adamw_step_sr, ssi_round_bf16_sr (bf16 AdamW whose three stores round stochastically, counter-based)
                            * 10: + ssi_ce_fwd_metrics, ssi_ce_metrics_reduce (dev-set loss and top-k accuracy per token type)
                            * 9: ssi_adamw_step takes its hyper-parameters in double (the coefficients of torch's fused AdamW)
                            * 8: + ssi_ce_fwd_weighted (per-row loss weights: an accumulation window run as ONE batch keeps the reference's
@@ -264,6 +265,19 @@ int ssi_ce_reduce(const float* row_loss, const int64_t* labels, int64_t rows, in
  * ratio per row here.  In the register-resident bf16 kernel the weight is an additive term of the exponent: no cost per element. */
 int ssi_ce_fwd_weighted(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
                         int64_t ignore_index, float* row_loss, float* row_lse, int write_grad, int dtype, void* stream);
+/* ssi_ce_fwd_weighted with the auxiliary z-loss z_coeff * log^2 Z (ABI v12; not in the reference, off by default: the trainer's z_loss_coeff).
+ * With lse = logsumexp(logits[r, 0:vocab]), p = softmax and w = row_weight[r] (NULL: 1), for a row with a valid label:
+ *   row_loss[r] = w (lse - logit[label])      what ssi_ce_fwd_weighted writes, bit for bit (row_lse too, NULL ok): the same form is chosen by the
+ *                                             same predicate, with the same order of max, exp-sum and lse;
+ *   row_z[r]    = w (lse lse)                 fp32, in this order, WITHOUT z_coeff (required);
+ *   gradient    = w (f p - onehot(label)),    f = 1 + 2 z_coeff lse   (if write_grad; over the logits, pad columns 0).
+ * A row whose label is ignored or outside [0, vocab): row_loss = row_z = 0 and a zero gradient row.  The batch objective is
+ * (sum row_loss + z_coeff sum row_z) / n_valid: run ssi_ce_reduce on row_loss and again on row_z (out[1] is the fixed-order sum).
+ * z_coeff must be finite and >= 0 (SSI_ERR_ARG otherwise); z_coeff == 0 gives the gradient of ssi_ce_fwd_weighted bit for bit (row_z is still
+ * written).  f may be zero or negative (lse < -1 / (2 z_coeff)): in the register-resident bf16 kernel |f| is an additive term of the exponent,
+ * like the weight, and the sign is one XOR per packed register — one store per row and four integer operations per 8 columns more. */
+int ssi_ce_fwd_z(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab, int64_t ignore_index,
+                 float z_coeff, float* row_loss, float* row_lse, float* row_z, int write_grad, int dtype, void* stream);
 /* Forward-only ssi_ce_fwd_weighted that also ranks the label (ABI v10; the dev set's loss and accuracy per token type, ssi/eval.py).  The logits
  * are read only.  row_loss and row_lse (NULL ok) are what ssi_ce_fwd_weighted(..., write_grad = 0) writes on the same inputs, bit for bit: the
  * same form (register-resident bf16 rows or the generic kernel) is chosen by the same predicate, with the same order of max, exp-sum and lse.

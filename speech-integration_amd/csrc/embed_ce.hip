@@ -435,6 +435,229 @@ extern "C" int ssi_ce_reduce(const float* row_loss, const int64_t* labels, int64
 }
 
 // =====================================================================================================================
+// K9z cross-entropy with the auxiliary z-loss z * log^2 Z (ssi_ce_fwd_z; opt-in, z_loss_coeff of the trainer).  Per valid row, with
+// lse = log Z, p = softmax and the row's weight w:
+//   row_loss = w (lse - x[label])  (unchanged)     row_z = w (lse lse)  (the coefficient is applied by the caller)
+//   grad[c]  = w (f p[c] - [c == label]),  f = 1 + 2 z lse      (d/dx of lse - x[label] + z lse^2: d lse / dx = p)
+// Kernels of their own, as the metrics ones below: the instantiations the plain entries launch stay what they were.  The max, the exp-sum
+// and the lse are the statements of ce_fwd_kernel / ce_row_bf16_kernel in their order: row_loss and row_lse agree bit for bit, and with
+// z = 0 (f = 1 exactly) so does the gradient.
+// =====================================================================================================================
+template <typename T>
+__global__ __launch_bounds__(512) void ce_fwd_z_kernel(T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                       int64_t vocab, int64_t ignore_index, float two_z, float* __restrict__ row_loss,
+                                                       float* __restrict__ row_lse, float* __restrict__ row_z, int write_grad,
+                                                       const float* __restrict__ row_weight) {
+    constexpr int N = Vec16<T>::N;
+    __shared__ float red[16];
+    const int64_t row = blockIdx.x;
+    T* lr = logits + row * ld;
+    const int64_t label = labels[row];
+    const bool valid = label != ignore_index && label >= 0 && label < vocab;
+    const int64_t nvec = ld / N;
+    if (!valid) {  // block-uniform
+        if (threadIdx.x == 0) { row_loss[row] = 0.f; if (row_lse) row_lse[row] = 0.f; row_z[row] = 0.f; }
+        if (write_grad) {
+            Vec16<T> z;
+#pragma unroll
+            for (int i = 0; i < N; ++i) z.set(i, 0.f);
+            for (int64_t v = threadIdx.x; v < nvec; v += 512) store16(lr + v * N, z);
+        }
+        return;
+    }
+    float m = -INFINITY, s = 0.f;
+    for (int64_t v = threadIdx.x; v < nvec; v += 512) {
+        Vec16<T> a = load16(lr + v * N);
+        float lm = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < N; ++i) if (v * N + i < vocab) lm = fmaxf(lm, a.get(i));
+        if (lm > m) { s *= expf(m - lm); m = lm; }
+#pragma unroll
+        for (int i = 0; i < N; ++i) if (v * N + i < vocab) s += expf(a.get(i) - m);
+    }
+    const float gm = block_max(m, red);
+    s = (m == -INFINITY) ? 0.f : s * expf(m - gm);
+    const float gs = block_sum(s, red);
+    const float lse = gm + logf(gs);
+    const float w = row_weight ? row_weight[row] : 1.f;
+    if (threadIdx.x == 0) {
+        row_loss[row] = w * (lse - to_f32<T>(lr[label]));
+        if (row_lse) row_lse[row] = lse;
+        row_z[row] = w * (lse * lse);
+    }
+    if (!write_grad) return;
+    const float f = fmaf(two_z, lse, 1.f);  // any sign: lse < -1 / (2 z) makes it negative, and the plain multiply below carries that
+    __syncthreads();  // lr[label] read above must precede the overwrite below
+    for (int64_t v = threadIdx.x; v < nvec; v += 512) {
+        Vec16<T> a = load16(lr + v * N), o;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const int64_t c = v * N + i;
+            float g = 0.f;
+            if (c < vocab) g = w * (f * expf(a.get(i) - lse) - (c == label ? 1.f : 0.f));
+            o.set(i, g);
+        }
+        store16(lr + v * N, o);
+    }
+}
+
+// The register-resident form: ce_row_bf16_kernel statement for statement, plus one scalar per row.  |f| rides in the exponent's additive
+// term beside log2 w (f = 0: log2 0 = -inf, every exp2 gives 0 — the row is -w on the label and 0 elsewhere).  The SIGN of f is applied to
+// the packed result: the row computes  w |f| p - sign(f) w [c == label]  and, for f < 0, flips the sign bit of all eight bf16 of a
+// register (4 XORs per chunk with a per-row mask that is 0 otherwise; round-to-nearest-even is symmetric in the sign, so this IS the
+// rounding of w (f p - onehot)).  No branch per chunk: the body stays straight-line and the row stays in its registers.  (For f < 0 the
+// columns whose gradient is 0 — pads, underflows — hold -0.)
+template <int NCH, bool write_grad>
+__global__ __launch_bounds__(1024, 4) void ce_row_bf16_z_kernel(bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                                int64_t rows, int64_t vocab, int64_t ignore_index, float two_z,
+                                                                float* __restrict__ row_loss, float* __restrict__ row_lse,
+                                                                float* __restrict__ row_z, const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    constexpr float LOG2E = 1.44269504088896340736f;
+    constexpr int CHUNK = 8192;
+    const int tid = threadIdx.x;
+    const int voff = tid * 16;
+    const int col0 = tid * 8;
+    const int row_bytes = (int)(ld * 2);
+    const int vocab_i = (int)vocab;
+    u32x4 x[NCH];
+    auto is_valid = [&](int64_t label) { return label != ignore_index && label >= 0 && label < vocab; };
+    auto rsrc_of = [&](int64_t row) { return __builtin_amdgcn_make_buffer_rsrc(logits + row * ld, 0, row_bytes, 0x00020000u); };
+    auto lo = [](unsigned u) { return __builtin_bit_cast(float, u << 16); };
+    auto hi = [](unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); };
+    auto opaque = [&]() {  // as in ce_row_bf16_kernel: each pass re-derives its floats from the packed registers
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int d = 0; d < 4; ++d) asm volatile("" : "+v"(x[c][d]));
+    };
+    int64_t row = blockIdx.x;
+    if (row >= rows) return;
+    {
+        const __amdgpu_buffer_rsrc_t r0 = rsrc_of(row);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) x[c] = __builtin_amdgcn_raw_buffer_load_b128(r0, voff, c * CHUNK * 2, 0);
+    }
+    for (; row < rows; row += gridDim.x) {
+        const int64_t next = row + gridDim.x;
+        const int64_t label = labels[row];
+        const bool valid = is_valid(label);
+        const float w = row_weight ? row_weight[row] : 1.f;
+        const float log2w = row_weight ? __log2f(w) : 0.f;
+        const __amdgpu_buffer_rsrc_t rs = rsrc_of(row);
+#pragma unroll
+        for (int c = (NCH >= 2 ? NCH - 2 : 0); c < NCH; ++c) {
+            const int left = vocab_i - c * CHUNK - col0;
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                if (2 * d >= left) x[c][d] = (x[c][d] & 0xffff0000u) | 0x0000ff80u;
+                if (2 * d + 1 >= left) x[c][d] = (x[c][d] & 0x0000ffffu) | 0xff800000u;
+            }
+        }
+        float nl = -INFINITY;  // ignored / out-of-range label: every exp2 below gives 0 -> zero gradient row
+        float wl = w;          // what the label column subtracts BEFORE the sign flip: sign(f) w
+        unsigned flip = 0u;    // sign bits of the two bf16 of a packed dword, set iff f < 0
+        if (valid) {           // workgroup-uniform; reads the row registers only
+            float xl = 0.f;
+            if (tid == 0) xl = (float)logits[row * ld + label];
+            float m = -INFINITY;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c)
+#pragma unroll
+                for (int d = 0; d < 4; ++d) m = fmaxf(m, fmaxf(lo(x[c][d]), hi(x[c][d])));
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the label logit has landed before any wave overwrites it (ce_row_bf16_kernel)
+            const float gm = block_max(m, red);
+            opaque();
+            const float nm = -gm * LOG2E;
+            float s = 0.f;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c)
+#pragma unroll
+                for (int d = 0; d < 4; ++d)
+                    s += __builtin_amdgcn_exp2f(fmaf(lo(x[c][d]), LOG2E, nm)) + __builtin_amdgcn_exp2f(fmaf(hi(x[c][d]), LOG2E, nm));
+            const float gs = block_sum(s, red);
+            const float lse = gm + logf(gs);
+            if (tid == 0) {
+                row_loss[row] = w * (lse - xl);
+                if (row_lse) row_lse[row] = lse;
+                row_z[row] = w * (lse * lse);
+            }
+            const float f = fmaf(two_z, lse, 1.f);
+            nl = (-lse * LOG2E + log2w) + __log2f(fabsf(f));  // z = 0: f = 1 and the last term an exact 0 — the nl of ce_row_bf16_kernel
+            if (f < 0.f) { wl = -w; flip = 0x80008000u; }
+        } else if (tid == 0) {
+            row_loss[row] = 0.f;
+            if (row_lse) row_lse[row] = 0.f;
+            row_z[row] = 0.f;
+        }
+        opaque();
+        const int hot = valid ? (int)label - col0 : -(1 << 30);
+        const __amdgpu_buffer_rsrc_t rn = rsrc_of(next < rows ? next : row);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            if (write_grad) {
+                float g[8];
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {
+                    g[2 * d] = __builtin_amdgcn_exp2f(fmaf(lo(x[c][d]), LOG2E, nl));
+                    g[2 * d + 1] = __builtin_amdgcn_exp2f(fmaf(hi(x[c][d]), LOG2E, nl));
+                }
+                const int h = hot - c * CHUNK;
+                if ((unsigned)h < 8u) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) if (e == h) g[e] -= wl;
+                }
+                bf16x8 ob;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) ob[e] = (bf16_t)g[e];
+                u32x4 o = __builtin_bit_cast(u32x4, ob);
+#pragma unroll
+                for (int d = 0; d < 4; ++d) o[d] ^= flip;
+                __builtin_amdgcn_raw_buffer_store_b128(o, rs, voff, c * CHUNK * 2, 2 /* nt: streamed once */);
+            }
+            x[c] = __builtin_amdgcn_raw_buffer_load_b128(rn, voff, c * CHUNK * 2, 2 /* nt */);
+            __builtin_amdgcn_sched_barrier(0);  // one chunk at a time, as in ce_row_bf16_kernel
+        }
+    }
+}
+
+extern "C" int ssi_ce_fwd_z(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
+                            int64_t ignore_index, float z_coeff, float* row_loss, float* row_lse, float* row_z, int write_grad, int dtype,
+                            void* stream) {
+    SSI_CHECK_ARG(logits && labels && row_loss && row_z && rows >= 0 && vocab > 0 && ld >= vocab && ld % 8 == 0);
+    if (!(z_coeff >= 0.f) || !(z_coeff <= 3.0e38f)) {  // NaN fails the first test, +inf the second
+        ssi_set_error("ce_fwd_z: z_coeff must be finite and >= 0, got %g", (double)z_coeff);
+        return SSI_ERR_ARG;
+    }
+    if (rows == 0) return SSI_OK;
+    const float two_z = 2.f * z_coeff;
+    const int64_t chunks = ssi_cdiv(ld, 8192);
+    // the predicate of ssi_ce_fwd_weighted: the same inputs take the same form there and here
+    const bool row_form = dtype == SSI_BF16 && ((uintptr_t)logits & 15) == 0 && ld - vocab < 8192 && ld * 2 < (1LL << 31) &&
+                          (chunks <= 4 || chunks == 8 || (chunks >= 16 && chunks <= 18));
+    if (row_form) {
+        const dim3 grid((unsigned)(rows < ce_num_cus() ? rows : ce_num_cus()));
+#define SSI_CE_ROW_Z(N)                                                                                                                       \
+    case N:                                                                                                                                   \
+        if (write_grad) hipLaunchKernelGGL((ce_row_bf16_z_kernel<N, true>), grid, dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits, ld, labels, \
+                                           rows, vocab, ignore_index, two_z, row_loss, row_lse, row_z, row_weight);                           \
+        else hipLaunchKernelGGL((ce_row_bf16_z_kernel<N, false>), grid, dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits, ld, labels, rows,    \
+                                vocab, ignore_index, two_z, row_loss, row_lse, row_z, row_weight);                                            \
+        break
+        switch ((int)chunks) {
+            SSI_CE_ROW_Z(1); SSI_CE_ROW_Z(2); SSI_CE_ROW_Z(3); SSI_CE_ROW_Z(4); SSI_CE_ROW_Z(8); SSI_CE_ROW_Z(16); SSI_CE_ROW_Z(17); SSI_CE_ROW_Z(18);
+        }
+#undef SSI_CE_ROW_Z
+        SSI_LAUNCH_CHECK();
+        return SSI_OK;
+    }
+    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(ce_fwd_z_kernel<T>, dim3((unsigned)rows), dim3(512), 0, (hipStream_t)stream, (T*)logits, ld,
+                                                 labels, vocab, ignore_index, two_z, row_loss, row_lse, row_z, write_grad, row_weight));
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+// =====================================================================================================================
 // K9m forward-only cross-entropy that also ranks the label (ssi_ce_fwd_metrics): the dev set's per-token-type loss, top-1 and top-k.
 //   rank[r] = #{c < vocab : x[c] > x[label]} + #{c < label : x[c] == x[label]}  — the label's position in a stable descending sort of
 //   the row; rank == 0 <=> argmax(row) == label under the first-occurrence rule.  Compares on the stored values: an exact integer.

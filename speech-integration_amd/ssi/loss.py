@@ -7,6 +7,7 @@ decoder and ``loss_fn`` is :class:`CEWithChunkedOutputLoss`, the LM head and the
 
 from __future__ import annotations
 
+import math
 from collections.abc import Callable
 
 import torch
@@ -63,9 +64,24 @@ class _CrossEntropyFn(torch.autograd.Function):
         return work[:, : ctx.vocab], None, None
 
 
-def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metrics=None) -> Tensor:
+def _z_term(logits, labels: Tensor, ignore_index: int) -> Tensor:
+    """``sum over valid labels of logsumexp(logits.float())^2 / n_valid`` in plain torch (the literal route's z-loss, coefficient not applied);
+    ``logits``: one ``[B, S, V]`` tensor or the list of its chunks along ``S``."""
+    chunks = logits if isinstance(logits, (list, tuple)) else [logits]
+    lse = torch.cat([torch.logsumexp(c.float(), dim=-1) for c in chunks], dim=1)
+    valid = labels != ignore_index
+    return (lse * lse * valid).sum() / valid.sum()
+
+
+def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metrics=None, z_loss_coeff: float = 0.0) -> Tensor:
     """``label_metrics`` (``ssi.eval.LabelMetrics``, forward-only, not in the reference): loss and top-k hits of the shifted labels are added to it
-    per token type — by the cross-entropy kernel on the fused route, in plain torch from the logits on the literal one.  The loss is unchanged."""
+    per token type — by the cross-entropy kernel on the fused route, in plain torch from the logits on the literal one.  The loss is unchanged.
+    ``z_loss_coeff`` (not in the reference; finite, >= 0): ``> 0`` adds the auxiliary z-loss ``z sum_i w_i logsumexp(logits_i)^2 / n_valid`` —
+    inside the cross-entropy kernel on the fused route (``model.fused_loss``), in plain torch on the literal one.  Either route then leaves
+    the two parts on the model as ``last_ce_loss`` and ``last_z_loss`` (detached scalars).  ``0.0``: exactly the loss of before."""
+    z_loss_coeff = float(z_loss_coeff)
+    if not (math.isfinite(z_loss_coeff) and z_loss_coeff >= 0.0):
+        raise ValueError(f"z_loss_coeff must be finite and >= 0, got {z_loss_coeff!r}")
     labels = batch["labels"]
     ignore_index = loss_fn.ignore_index
     labels = torch.hstack((labels[..., 1:], torch.full_like(labels[..., -1:], ignore_index)))  # new tensor: batch untouched
@@ -79,6 +95,8 @@ def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metri
             extra["loss_weights"] = batch["loss_weights"]
         if label_metrics is not None:
             extra["label_metrics"] = label_metrics
+        if z_loss_coeff > 0.0:
+            extra["z_loss_coeff"] = z_loss_coeff
         return model.fused_loss(batch["tokens"], labels, ignore_index, input_pos=batch.get("input_pos"), **extra)
     if batch.get("loss_weights") is not None:
         raise ValueError("loss_weights need the fused LM head + cross-entropy of the HIP decoder (model.fused_loss)")
@@ -91,9 +109,13 @@ def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metri
     )
     if label_metrics is not None:
         label_metrics.add_logits(logits, labels, ignore_index)
+    z_part = z_loss_coeff * _z_term(logits, labels, ignore_index) if z_loss_coeff > 0.0 else None
     if not isinstance(logits, list):
         labels = labels.reshape(-1)
         logits = logits.reshape(-1, logits.size(-1))
     loss = loss_fn(logits, labels)
     del logits
+    if z_part is not None:
+        model.last_ce_loss, model.last_z_loss = loss.detach(), z_part.detach()
+        loss = loss + z_part
     return loss

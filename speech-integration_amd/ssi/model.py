@@ -239,6 +239,8 @@ class HipLlamaDecoder(nn.Module):
         self._grads_stale = False
         self._emb_grad_written = False
         self.label_errors: Optional[Tensor] = None        # device count of out-of-range labels seen by the last fused loss
+        self.last_ce_loss: Optional[Tensor] = None        # device scalars of the last fused loss with z_loss_coeff > 0: its cross-entropy part ...
+        self.last_z_loss: Optional[Tensor] = None         # ... and its z part (coefficient applied, same normalisation)
         self.bucket_listener = None                       # callable(name, lo, hi) for the NEXT gradient-exchanging backward (see _backward_hidden)
         self.position_errors: Optional[Tensor] = None     # device count of input_pos entries outside the RoPE table in the last forward
         self.grad_sync = None                             # optional ssi.distributed.GradSync
@@ -695,7 +697,7 @@ class HipLlamaDecoder(nn.Module):
 
     def fused_loss(self, tokens: Tensor, shifted_labels: Tensor, ignore_index: int = CROSS_ENTROPY_IGNORE_IDX,
                    input_pos: Optional[Tensor] = None, attn_plan=None, loss_weights: Optional[Tensor] = None,
-                   label_metrics=None) -> Tensor:
+                   label_metrics=None, z_loss_coeff: float = 0.0) -> Tensor:
         """Mean NLL over non-ignored (already shifted) labels with the LM head + CE fused: equals
         ``CEWithChunkedOutputLoss()(model(tokens, input_pos=...), shifted_labels)`` of the reference for any chunk count.
         ``input_pos`` ([B, S], restarting at 0 with every document): packed rows, block-causal attention.  ``attn_plan``
@@ -705,7 +707,18 @@ class HipLlamaDecoder(nn.Module):
         accumulation window that runs as one batch keeps the reference's per-micro-batch normalisation (``ssi/data/window.py``).
         ``label_metrics`` (``ssi.eval.LabelMetrics``; forward-only calls): the cross-entropy launch also ranks every label in its row and the
         per-type sums of nll, top-1 and top-k hits are ADDED to ``label_metrics.acc`` on the device (``ssi_ce_fwd_metrics`` +
-        ``ssi_ce_metrics_reduce``); the returned loss is bit-identical with and without it.  ``None``: exactly the launches of before."""
+        ``ssi_ce_metrics_reduce``); the returned loss is bit-identical with and without it.  ``None``: exactly the launches of before.
+        ``z_loss_coeff`` (not in the reference; finite, >= 0): the auxiliary z-loss ``z mean(log^2 Z)`` that keeps the softmax normaliser of
+        the extended vocabulary near 1.  ``> 0``: the result is ``(sum_i w_i nll_i + z sum_i w_i lse_i^2) / n_valid`` (same weights and divisor
+        for both terms), its gradient comes from the same cross-entropy launch (``ssi_ce_fwd_z``), and two device scalars are left on the
+        model as ``label_errors`` is: ``last_ce_loss`` (the cross-entropy part, what a call without the coefficient returns) and
+        ``last_z_loss`` (the z part, coefficient applied).  Under grad and without; not together with ``label_metrics`` (the dev set's
+        metrics are plain cross-entropy).  ``0.0``: exactly the launches of before."""
+        z_loss_coeff = float(z_loss_coeff)
+        if not (math.isfinite(z_loss_coeff) and z_loss_coeff >= 0.0):
+            raise ValueError(f"z_loss_coeff must be finite and >= 0, got {z_loss_coeff!r}")
+        if z_loss_coeff > 0.0 and label_metrics is not None:
+            raise ValueError("fused_loss: z_loss_coeff and label_metrics do not combine in one call (the dev set's metrics are plain cross-entropy)")
         if label_metrics is not None and torch.is_grad_enabled() and self.training:
             raise RuntimeError("fused_loss(label_metrics=...) is forward-only (the dev set): call it under torch.no_grad() / inference_mode() "
                                "or on model.eval(); the training step's cross-entropy kernel does not rank labels")
@@ -718,18 +731,30 @@ class HipLlamaDecoder(nn.Module):
         labels = shifted_labels.reshape(-1).contiguous()
         weights = None if loss_weights is None else loss_weights.reshape(-1).contiguous()
         if torch.is_grad_enabled() and self.training:
-            return _FusedLossFn.apply(self, tokens, labels, ignore_index, self._anchor, input_pos, attn_plan, weights)
+            return _FusedLossFn.apply(self, tokens, labels, ignore_index, self._anchor, input_pos, attn_plan, weights, z_loss_coeff)
         hn = self._forward_hidden(tokens, save=False, input_pos=input_pos)
-        return self._ce_forward(hn, labels, ignore_index, write_grad=False, weights=weights, label_metrics=label_metrics)[0]
+        return self._ce_forward(hn, labels, ignore_index, write_grad=False, weights=weights, label_metrics=label_metrics,
+                                z_loss_coeff=z_loss_coeff)[0]
 
     def _ce_forward(self, hn: Tensor, labels: Tensor, ignore_index: int, write_grad: bool,
-                    weights: Optional[Tensor] = None, label_metrics=None) -> tuple[Tensor, Tensor, Tensor]:
+                    weights: Optional[Tensor] = None, label_metrics=None, z_loss_coeff: float = 0.0) -> tuple[Tensor, Tensor, Tensor]:
         """Tied head + cross-entropy: (mean loss, stats, logits buffer — which holds softmax - onehot when ``write_grad``).  The same
         three launches as the one-call ABI entry ``ssi_lmhead_ce_fwd`` (``ops.lmhead_ce_fwd``), issued one by one here so that ``bench.py``
-        can time the head GEMM on its own."""
+        can time the head GEMM on its own.  ``z_loss_coeff > 0``: the z form of the cross-entropy launch (the buffer then holds
+        ``f softmax - onehot``, ``f = 1 + 2 z lse``) and a second reduce over its ``row_z``; the loss returned is the sum of both parts."""
         T = hn.shape[0]
         logits = self._head_logits(hn, "logits" if write_grad else "logits.x")
         row_loss = self._arena.get("row_loss" if write_grad else "row_loss.x", (T,), torch.float32)
+        if z_loss_coeff > 0.0:
+            assert label_metrics is None
+            row_z = self._arena.get("row_z" if write_grad else "row_z.x", (T,), torch.float32)
+            ops.ce_fwd_z(logits, labels, self.vocab_size, ignore_index, z_loss_coeff, row_loss, None, row_z, write_grad, row_weight=weights)
+            out = torch.empty(8, dtype=torch.float32, device=self.device)
+            ops.ce_reduce(row_loss, labels, self.vocab_size, ignore_index, out[:4])
+            ops.ce_reduce(row_z, labels, self.vocab_size, ignore_index, out[4:])  # the same labels: the same n_valid divides both parts
+            self.label_errors = out[3]
+            self.last_ce_loss, self.last_z_loss = out[0], out[4] * z_loss_coeff
+            return out[0] + self.last_z_loss, out[:4], logits
         if label_metrics is None:
             ops.ce_fwd(logits, labels, self.vocab_size, ignore_index, row_loss, None, write_grad, row_weight=weights)
         else:  # forward-only (fused_loss refuses it under grad): the same row losses, plus nll and rank of every label, summed per type
@@ -780,9 +805,9 @@ class _FusedLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model: HipLlamaDecoder, tokens: Tensor, labels: Tensor, ignore_index: int, anchor: Tensor,
-                input_pos: Optional[Tensor] = None, attn_plan=None, weights: Optional[Tensor] = None) -> Tensor:
+                input_pos: Optional[Tensor] = None, attn_plan=None, weights: Optional[Tensor] = None, z_loss_coeff: float = 0.0) -> Tensor:
         hn = model._forward_hidden(tokens, save=True, input_pos=input_pos, attn_plan=attn_plan)
-        loss, stats, dlogits = model._ce_forward(hn, labels, ignore_index, write_grad=True, weights=weights)
+        loss, stats, dlogits = model._ce_forward(hn, labels, ignore_index, write_grad=True, weights=weights, z_loss_coeff=z_loss_coeff)
         ctx.model, ctx.gen = model, model._fwd_generation
         ctx.save_for_backward(hn, stats, dlogits)
         return loss.clone()
@@ -794,11 +819,12 @@ class _FusedLossFn(torch.autograd.Function):
         if m._saved is None or m._saved["gen"] != ctx.gen:  # checked BEFORE the head backward touches the gradient buffer
             raise RuntimeError("HipLlamaDecoder: backward called for a forward whose activations were overwritten; "
                                "run backward before the next training forward")
-        # d loss / d logits = (softmax - onehot) / n_valid ; the 1/n_valid and the upstream scalar ride in alpha_dev
+        # d loss / d logits = (softmax - onehot) / n_valid ; the 1/n_valid and the upstream scalar ride in alpha_dev (with a z-loss the buffer
+        # holds (f softmax - onehot): both parts of the objective share the divisor)
         alpha = (grad_out.to(torch.float32).reshape(1) / stats[2:3]).contiguous()
         d_hn = m._head_backward(dlogits, hn, alpha)
         m._backward_hidden(d_hn, ctx.gen)
-        return None, None, None, None, torch.zeros_like(m._anchor), None, None, None
+        return None, None, None, None, torch.zeros_like(m._anchor), None, None, None, None
 
 
 # --------------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ device-side result so the trainer can fold it into its single per-micro-batch sy
 from __future__ import annotations
 
 import logging
+import math
 import os
 from typing import Any
 
@@ -101,6 +102,9 @@ def validate_train_cfg(cfg) -> None:
     if cfg.save_steps % cfg.eval_steps:
         raise ValueError(f"save_steps ({cfg.save_steps}) must be a multiple of eval_steps ({cfg.eval_steps}): a checkpoint is "
                          "written only at steps that also evaluate")
+    z = cfg.get("z_loss_coeff", 0.0)
+    if isinstance(z, bool) or not isinstance(z, (int, float)) or not math.isfinite(z) or z < 0:
+        raise ValueError(f"config field 'z_loss_coeff' must be a finite number >= 0, got {z!r}")
 
 
 # training_state.pt (schema v1): key in the file -> name under which the trainer consumes it

@@ -1,22 +1,33 @@
-"""Cross-entropy kernel alone at the step's shape: T = 16384 rows, V = 133258 (ld 133376), bf16, gradient in place."""
-import sys, torch
+"""Cross-entropy kernel alone at the step's shape: T = 16384 rows, V = 133258 (ld 133376), bf16, gradient in place.
+``--z COEFF``: the z-loss form (``ops.ce_fwd_z``, ``ssi_ce_fwd_z``) with that coefficient instead of ``ops.ce_fwd``."""
+import argparse, sys, torch
 sys.path.insert(0, 'speech-integration_amd')
 from ssi import ops
+ap = argparse.ArgumentParser()
+ap.add_argument("--z", type=float, default=None, metavar="COEFF", help="time ce_fwd_z with this coefficient (default: ce_fwd)")
+ap.add_argument("--reps", type=int, default=10)
+args = ap.parse_args()
 T, V, LD = 16384, 133258, 133376
 logits = (torch.randn(T, LD, device='cuda') * 2).bfloat16()
 labels = torch.randint(0, V, (T,), device='cuda')
 labels[::7] = -100
-row_loss = torch.empty(T, device='cuda'); row_lse = torch.empty(T, device='cuda')
+row_loss = torch.empty(T, device='cuda'); row_lse = torch.empty(T, device='cuda'); row_z = torch.empty(T, device='cuda')
 work = logits.clone()
 def run():
-    ops.ce_fwd(work, labels, V, -100, row_loss, row_lse, write_grad=True)
+    if args.z is None:
+        ops.ce_fwd(work, labels, V, -100, row_loss, row_lse, write_grad=True)
+    else:
+        ops.ce_fwd_z(work, labels, V, -100, args.z, row_loss, row_lse, row_z, write_grad=True)
 for _ in range(3):
     work.copy_(logits); run()
 torch.cuda.synchronize()
 s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-tot = 0.0
-for _ in range(10):
+ms = []
+for _ in range(args.reps):
     work.copy_(logits)
     s.record(); run(); e.record(); torch.cuda.synchronize()
-    tot += s.elapsed_time(e)
-print(f"ce_fwd {tot / 10:.3f} ms  ({3 * T * LD * 2 / (tot / 10) / 1e9:.2f} TB/s at 3 passes, {2 * T * LD * 2 / (tot / 10) / 1e9:.2f} at 2)  loss {float(row_loss.sum()):.4f}")
+    ms.append(s.elapsed_time(e))
+mean = sum(ms) / len(ms)
+name = "ce_fwd" if args.z is None else f"ce_fwd_z({args.z:g})"
+print(f"{name} {mean:.3f} ms  (min {min(ms):.3f}, max {max(ms):.3f} of {len(ms)}; {3 * T * LD * 2 / mean / 1e9:.2f} TB/s at 3 passes, "
+      f"{2 * T * LD * 2 / mean / 1e9:.2f} at 2)  loss {float(row_loss.sum()):.4f}" + ("" if args.z is None else f"  z {float(row_z.sum()):.4f}"))
