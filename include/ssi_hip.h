@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 12 /* 12: + ssi_ce_fwd_z (cross-entropy with the auxiliary z-loss z * log^2 Z in its gradient; opt-in)
+#define SSI_ABI_VERSION 13 /* 13: + ssi_seq_score_reduce (per-sequence sums of what ssi_ce_fwd_metrics wrote: likelihood scoring of packed rows)
+                           * 12: + ssi_ce_fwd_z (cross-entropy with the auxiliary z-loss z * log^2 Z in its gradient; opt-in)
                            * 11: + ssi_adamw_step_sr, ssi_round_bf16_sr (bf16 AdamW whose three stores round stochastically, counter-based)
                            * 10: + ssi_ce_fwd_metrics, ssi_ce_metrics_reduce (dev-set loss and top-k accuracy per token type)
                            * 9: ssi_adamw_step takes its hyper-parameters in double (the coefficients of torch's fused AdamW)
@@ -295,6 +296,15 @@ int ssi_ce_fwd_metrics(const void* logits, int64_t ld, const int64_t* labels, co
  * reproducible.  accumulate != 0 adds to what out holds (one device accumulator per dev set, one read-back); 0 overwrites.  One workgroup. */
 int ssi_ce_metrics_reduce(const float* row_nll, const int32_t* row_rank, const int64_t* labels, int64_t rows, const int64_t* ranges,
                           int n_ranges, int topk, int accumulate, double* out, void* stream);
+/* Per-sequence sums of what ssi_ce_fwd_metrics wrote.  Sequence i covers the flat positions [seq_start[i], seq_end[i]) of row_nll / row_rank
+ * (device arrays of n_seq int64 each; the kernel clamps seq_end to [0, rows] and seq_start to [0, seq_end]).  Sequences need not tile the
+ * rows, may overlap and need not be sorted.  out: double [n_seq][4] = {n_labels, sum nll, n(rank == 0), n(rank < topk)}, overwritten; a
+ * position counts iff row_rank >= 0 (the predicate of ssi_ce_metrics_reduce); an empty sequence gives four zeros.  One wave per sequence,
+ * four per workgroup: fp64 per lane in position order, one fixed xor tree over the 64 lanes, no atomics, no LDS — bitwise reproducible and
+ * independent of n_seq and of where the sequence lies.  n_seq == 0 launches nothing.  SSI_ERR_ARG: topk < 1, rows >= 2^31, n_seq >= 2^31,
+ * a null pointer beside a non-zero size. */
+int ssi_seq_score_reduce(const float* row_nll, const int32_t* row_rank, int64_t rows, const int64_t* seq_start, const int64_t* seq_end,
+                         int64_t n_seq, int topk, double* out, void* stream);
 
 /* ---- K8 + K9 as one entry per direction: tied LM head (TiedLinear over tok_embeddings, ssi/loss.py:8-14) + chunked CE (trainer.py:300) ----
  * fwd: logits_ws[rows, vocab_pad] = hidden[rows, dim] table[vocab_pad, dim]^T (table rows >= vocab are zero padding), then ssi_ce_fwd

@@ -922,3 +922,48 @@ extern "C" int ssi_ce_metrics_reduce(const float* row_nll, const int32_t* row_ra
     SSI_LAUNCH_CHECK();
     return SSI_OK;
 }
+
+// Per-sequence sums of the rows ssi_ce_fwd_metrics wrote (ssi_seq_score_reduce): sequence i is the flat positions [seq_start[i], seq_end[i]),
+// clamped to [0, rows].  One wave per sequence, four per workgroup: the lanes stride over consecutive positions, each lane sums in fp64 in
+// position order, then one fixed xor tree over the 64 lanes.  No atomics, no LDS: a sequence's four numbers depend on its own positions
+// only — not on n_seq, not on which wave or workgroup took it.  The counts ride the tree as doubles (exact below 2^53).
+__global__ __launch_bounds__(256) void seq_score_reduce_kernel(const float* __restrict__ row_nll, const int32_t* __restrict__ row_rank,
+                                                               int64_t rows, const int64_t* __restrict__ seq_start,
+                                                               const int64_t* __restrict__ seq_end, int64_t n_seq, int topk,
+                                                               double* __restrict__ out) {
+    const int ln = threadIdx.x & 63;
+    const int64_t seq = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (seq >= n_seq) return;  // wave-uniform
+    int64_t end = seq_end[seq], start = seq_start[seq];
+    end = end < 0 ? 0 : (end > rows ? rows : end);
+    start = start < 0 ? 0 : (start > end ? end : start);
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t r = start + ln; r < end; r += 64) {
+        const int rank = row_rank[r];
+        if (rank >= 0) {
+            acc[0] += 1.0;
+            acc[1] += (double)row_nll[r];
+            acc[2] += rank == 0 ? 1.0 : 0.0;
+            acc[3] += rank < topk ? 1.0 : 0.0;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_xor(acc[q], o, 64);
+    if (ln == 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) out[4 * seq + q] = acc[q];
+    }
+}
+
+extern "C" int ssi_seq_score_reduce(const float* row_nll, const int32_t* row_rank, int64_t rows, const int64_t* seq_start,
+                                    const int64_t* seq_end, int64_t n_seq, int topk, double* out, void* stream) {
+    SSI_CHECK_ARG(rows >= 0 && rows < (1LL << 31) && n_seq >= 0 && n_seq < (1LL << 31) && topk >= 1 && (rows == 0 || (row_nll && row_rank)) &&
+                  (n_seq == 0 || (seq_start && seq_end && out)));
+    if (n_seq == 0) return SSI_OK;
+    hipLaunchKernelGGL(seq_score_reduce_kernel, dim3((unsigned)ssi_cdiv(n_seq, 4)), dim3(256), 0, (hipStream_t)stream, row_nll, row_rank, rows,
+                       seq_start, seq_end, n_seq, topk, out);
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}

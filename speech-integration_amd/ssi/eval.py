@@ -97,6 +97,61 @@ class LabelMetrics:
         return out
 
 
+class SeqScores:
+    """Per-sequence sums over the labels of ONE batch (not in the reference; the sibling of ``LabelMetrics``): ``out`` is fp64 ``[n_seq, 4]`` =
+    {n_labels, sum nll, n(rank == 0), n(rank < topk)}, row i over the shifted-label positions ``[start_i, end_i)`` of batch row ``row_i``;
+    it is OVERWRITTEN, so a caller hands every batch its own slice of one result tensor and reads back once.  ``spans``: host integer triples
+    ``(row, start, end)`` (a list, or an int64 ``[n_seq, 3]`` tensor — one already on the device is used as it is, which is how a prefetched
+    batch carries it).  Positions are those of the batch as the caller built it: ``HipLlamaDecoder.fused_loss(seq_scores=...)`` makes the flat
+    offsets after its own right-padding (``ssi_ce_fwd_metrics`` + ``ssi_seq_score_reduce``); ``add_logits`` is the same arithmetic in plain
+    torch for any other model.  ``keep_rows``: also leave ``row_nll`` (fp32 ``[rows, row_len]``, 0 where the label is ignored) on the object."""
+
+    def __init__(self, spans, topk: int, out: torch.Tensor, keep_rows: bool = False):
+        if int(topk) < 1:
+            raise ValueError(f"topk must be >= 1 (got {topk})")
+        spans = spans if torch.is_tensor(spans) else torch.tensor([tuple(int(v) for v in t) for t in spans], dtype=torch.int64).reshape(-1, 3)
+        if spans.dim() != 2 or spans.size(1) != 3 or spans.dtype != torch.int64:
+            raise ValueError("spans must be int64 triples (row, start, end)")
+        if out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 4 * spans.size(0):
+            raise ValueError(f"out must be a contiguous float64 [{spans.size(0)}, 4] tensor")
+        self.spans, self.topk, self.out, self.keep_rows = spans, int(topk), out, bool(keep_rows)
+        self.row_nll: torch.Tensor | None = None
+        self.row_len = 0
+
+    def flat_spans(self, row_len: int, device) -> tuple[torch.Tensor, torch.Tensor]:
+        """Device int64 ``(start, end)`` of every sequence in a ``[rows, row_len]`` batch laid out flat: ``row * row_len + pos``."""
+        sp = self.spans.to(device)
+        base = sp[:, 0] * int(row_len)
+        return (base + sp[:, 1]).contiguous(), (base + sp[:, 2]).contiguous()
+
+    def add_logits(self, logits, labels: torch.Tensor, ignore_index: int) -> None:
+        """``logits``: ``[B, S, V]`` or the list of chunks along dim 1 that ``model(...)`` returns; ``labels``: the shifted labels ``[B, S]``.  The
+        rank rule of ``LabelMetrics.add_logits``; fp64 sums per sequence."""
+        if isinstance(logits, (list, tuple)):
+            logits = torch.cat(list(logits), dim=1)
+        B, S = labels.shape[0], labels.shape[-1]
+        x = logits.reshape(-1, logits.size(-1))
+        labels = labels.reshape(-1).to(x.device)
+        vocab = x.size(-1)
+        valid = (labels != ignore_index) & (labels >= 0) & (labels < vocab)
+        xv, lab = x[valid].float(), labels[valid]
+        xl = xv.gather(1, lab[:, None])
+        nll = torch.logsumexp(xv, dim=1) - xl[:, 0]
+        below = torch.arange(vocab, device=x.device)[None, :] < lab[:, None]
+        rank = ((xv > xl) | ((xv == xl) & below)).sum(dim=1)
+        cols = torch.zeros(B * S, 4, dtype=torch.float64, device=x.device)
+        cols[valid] = torch.stack([torch.ones_like(nll).double(), nll.double(), (rank == 0).double(), (rank < self.topk).double()], dim=1)
+        start, end = self.flat_spans(S, "cpu")
+        end = end.clamp(0, B * S)
+        start = torch.minimum(start.clamp(min=0), end)
+        sums = [cols[a:b].sum(dim=0) for a, b in zip(start.tolist(), end.tolist())]
+        self.out.view(-1, 4).copy_(torch.stack(sums) if sums else cols[:0])
+        if self.keep_rows:
+            row_nll = torch.zeros(B * S, dtype=torch.float32, device=x.device)
+            row_nll[valid] = nll
+            self.row_nll, self.row_len = row_nll, S
+
+
 def compute_dataset_metrics(model, data_dev, loss_fn: Callable, epoch: int, global_step: int, steps_per_epoch: int, device: torch.device, *,
                             token_type_ranges: dict[str, tuple[int, int]], topk: int = 5, join_batches: int = 0, max_tokens: int = 32768,
                             pad_id: int = 0, prefetch: int = 2) -> dict[str, float | int]:

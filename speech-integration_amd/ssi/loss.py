@@ -73,15 +73,21 @@ def _z_term(logits, labels: Tensor, ignore_index: int) -> Tensor:
     return (lse * lse * valid).sum() / valid.sum()
 
 
-def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metrics=None, z_loss_coeff: float = 0.0) -> Tensor:
+def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metrics=None, z_loss_coeff: float = 0.0,
+                 seq_scores=None) -> Tensor:
     """``label_metrics`` (``ssi.eval.LabelMetrics``, forward-only, not in the reference): loss and top-k hits of the shifted labels are added to it
     per token type — by the cross-entropy kernel on the fused route, in plain torch from the logits on the literal one.  The loss is unchanged.
     ``z_loss_coeff`` (not in the reference; finite, >= 0): ``> 0`` adds the auxiliary z-loss ``z sum_i w_i logsumexp(logits_i)^2 / n_valid`` —
     inside the cross-entropy kernel on the fused route (``model.fused_loss``), in plain torch on the literal one.  Either route then leaves
-    the two parts on the model as ``last_ce_loss`` and ``last_z_loss`` (detached scalars).  ``0.0``: exactly the loss of before."""
+    the two parts on the model as ``last_ce_loss`` and ``last_z_loss`` (detached scalars).  ``0.0``: exactly the loss of before.
+    ``seq_scores`` (``ssi.eval.SeqScores``, forward-only, not in the reference): the sums of nll and top-k hits of the shifted labels over each
+    of its sequences ``(row, start, end)`` of this batch are written to its ``out`` — by ``ssi_seq_score_reduce`` on the fused route, in
+    plain torch from the logits on the literal one.  The loss is unchanged.  Not together with ``z_loss_coeff > 0``."""
     z_loss_coeff = float(z_loss_coeff)
     if not (math.isfinite(z_loss_coeff) and z_loss_coeff >= 0.0):
         raise ValueError(f"z_loss_coeff must be finite and >= 0, got {z_loss_coeff!r}")
+    if z_loss_coeff > 0.0 and seq_scores is not None:
+        raise ValueError("compute_loss: z_loss_coeff and seq_scores do not combine in one call (a sequence's score is plain cross-entropy)")
     labels = batch["labels"]
     ignore_index = loss_fn.ignore_index
     labels = torch.hstack((labels[..., 1:], torch.full_like(labels[..., -1:], ignore_index)))  # new tensor: batch untouched
@@ -97,6 +103,8 @@ def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metri
             extra["label_metrics"] = label_metrics
         if z_loss_coeff > 0.0:
             extra["z_loss_coeff"] = z_loss_coeff
+        if seq_scores is not None:
+            extra["seq_scores"] = seq_scores
         return model.fused_loss(batch["tokens"], labels, ignore_index, input_pos=batch.get("input_pos"), **extra)
     if batch.get("loss_weights") is not None:
         raise ValueError("loss_weights need the fused LM head + cross-entropy of the HIP decoder (model.fused_loss)")
@@ -109,6 +117,8 @@ def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metri
     )
     if label_metrics is not None:
         label_metrics.add_logits(logits, labels, ignore_index)
+    if seq_scores is not None:
+        seq_scores.add_logits(logits, labels, ignore_index)
     z_part = z_loss_coeff * _z_term(logits, labels, ignore_index) if z_loss_coeff > 0.0 else None
     if not isinstance(logits, list):
         labels = labels.reshape(-1)

@@ -697,7 +697,7 @@ class HipLlamaDecoder(nn.Module):
 
     def fused_loss(self, tokens: Tensor, shifted_labels: Tensor, ignore_index: int = CROSS_ENTROPY_IGNORE_IDX,
                    input_pos: Optional[Tensor] = None, attn_plan=None, loss_weights: Optional[Tensor] = None,
-                   label_metrics=None, z_loss_coeff: float = 0.0) -> Tensor:
+                   label_metrics=None, z_loss_coeff: float = 0.0, seq_scores=None) -> Tensor:
         """Mean NLL over non-ignored (already shifted) labels with the LM head + CE fused: equals
         ``CEWithChunkedOutputLoss()(model(tokens, input_pos=...), shifted_labels)`` of the reference for any chunk count.
         ``input_pos`` ([B, S], restarting at 0 with every document): packed rows, block-causal attention.  ``attn_plan``
@@ -713,7 +713,12 @@ class HipLlamaDecoder(nn.Module):
         for both terms), its gradient comes from the same cross-entropy launch (``ssi_ce_fwd_z``), and two device scalars are left on the
         model as ``label_errors`` is: ``last_ce_loss`` (the cross-entropy part, what a call without the coefficient returns) and
         ``last_z_loss`` (the z part, coefficient applied).  Under grad and without; not together with ``label_metrics`` (the dev set's
-        metrics are plain cross-entropy).  ``0.0``: exactly the launches of before."""
+        metrics are plain cross-entropy).  ``0.0``: exactly the launches of before.
+        ``seq_scores`` (``ssi.eval.SeqScores``; forward-only calls): the sums of nll, top-1 and top-k hits over each of its sequences
+        ``(row, start, end)`` of THIS batch are written to ``seq_scores.out`` (``ssi_ce_fwd_metrics`` + ``ssi_seq_score_reduce``).  Its positions
+        are those of ``tokens`` as passed; the flat offsets ``row * S_padded + pos`` are made here, after the right-padding.  Combines with
+        ``label_metrics`` (one cross-entropy launch feeds both reduces), not with ``z_loss_coeff > 0``; the returned loss is bit-identical
+        with and without it.  ``None``: exactly the launches of before."""
         z_loss_coeff = float(z_loss_coeff)
         if not (math.isfinite(z_loss_coeff) and z_loss_coeff >= 0.0):
             raise ValueError(f"z_loss_coeff must be finite and >= 0, got {z_loss_coeff!r}")
@@ -721,6 +726,11 @@ class HipLlamaDecoder(nn.Module):
             raise ValueError("fused_loss: z_loss_coeff and label_metrics do not combine in one call (the dev set's metrics are plain cross-entropy)")
         if label_metrics is not None and torch.is_grad_enabled() and self.training:
             raise RuntimeError("fused_loss(label_metrics=...) is forward-only (the dev set): call it under torch.no_grad() / inference_mode() "
+                               "or on model.eval(); the training step's cross-entropy kernel does not rank labels")
+        if z_loss_coeff > 0.0 and seq_scores is not None:
+            raise ValueError("fused_loss: z_loss_coeff and seq_scores do not combine in one call (a sequence's score is plain cross-entropy)")
+        if seq_scores is not None and torch.is_grad_enabled() and self.training:
+            raise RuntimeError("fused_loss(seq_scores=...) is forward-only (scoring): call it under torch.no_grad() / inference_mode() "
                                "or on model.eval(); the training step's cross-entropy kernel does not rank labels")
         tokens = self._check_inputs(tokens, None, None, None, input_pos)
         if loss_weights is not None:
@@ -733,20 +743,23 @@ class HipLlamaDecoder(nn.Module):
         if torch.is_grad_enabled() and self.training:
             return _FusedLossFn.apply(self, tokens, labels, ignore_index, self._anchor, input_pos, attn_plan, weights, z_loss_coeff)
         hn = self._forward_hidden(tokens, save=False, input_pos=input_pos)
+        seq = None if seq_scores is None else (seq_scores, tokens.shape[1])
         return self._ce_forward(hn, labels, ignore_index, write_grad=False, weights=weights, label_metrics=label_metrics,
-                                z_loss_coeff=z_loss_coeff)[0]
+                                z_loss_coeff=z_loss_coeff, seq_scores=seq)[0]
 
     def _ce_forward(self, hn: Tensor, labels: Tensor, ignore_index: int, write_grad: bool,
-                    weights: Optional[Tensor] = None, label_metrics=None, z_loss_coeff: float = 0.0) -> tuple[Tensor, Tensor, Tensor]:
+                    weights: Optional[Tensor] = None, label_metrics=None, z_loss_coeff: float = 0.0,
+                    seq_scores=None) -> tuple[Tensor, Tensor, Tensor]:
         """Tied head + cross-entropy: (mean loss, stats, logits buffer — which holds softmax - onehot when ``write_grad``).  The same
         three launches as the one-call ABI entry ``ssi_lmhead_ce_fwd`` (``ops.lmhead_ce_fwd``), issued one by one here so that ``bench.py``
         can time the head GEMM on its own.  ``z_loss_coeff > 0``: the z form of the cross-entropy launch (the buffer then holds
-        ``f softmax - onehot``, ``f = 1 + 2 z lse``) and a second reduce over its ``row_z``; the loss returned is the sum of both parts."""
+        ``f softmax - onehot``, ``f = 1 + 2 z lse``) and a second reduce over its ``row_z``; the loss returned is the sum of both parts.
+        ``seq_scores``: ``(ssi.eval.SeqScores, padded row length)``."""
         T = hn.shape[0]
         logits = self._head_logits(hn, "logits" if write_grad else "logits.x")
         row_loss = self._arena.get("row_loss" if write_grad else "row_loss.x", (T,), torch.float32)
         if z_loss_coeff > 0.0:
-            assert label_metrics is None
+            assert label_metrics is None and seq_scores is None
             row_z = self._arena.get("row_z" if write_grad else "row_z.x", (T,), torch.float32)
             ops.ce_fwd_z(logits, labels, self.vocab_size, ignore_index, z_loss_coeff, row_loss, None, row_z, write_grad, row_weight=weights)
             out = torch.empty(8, dtype=torch.float32, device=self.device)
@@ -755,14 +768,21 @@ class HipLlamaDecoder(nn.Module):
             self.label_errors = out[3]
             self.last_ce_loss, self.last_z_loss = out[0], out[4] * z_loss_coeff
             return out[0] + self.last_z_loss, out[:4], logits
-        if label_metrics is None:
+        if label_metrics is None and seq_scores is None:
             ops.ce_fwd(logits, labels, self.vocab_size, ignore_index, row_loss, None, write_grad, row_weight=weights)
-        else:  # forward-only (fused_loss refuses it under grad): the same row losses, plus nll and rank of every label, summed per type
+        else:  # forward-only (fused_loss refuses it under grad): the same row losses, plus nll and rank of every label, summed per type / sequence
             assert not write_grad
             row_nll = self._arena.get("row_nll.x", (T,), torch.float32)
             row_rank = self._arena.get("row_rank.x", (T,), torch.int32)
             ops.ce_fwd_metrics(logits, labels, self.vocab_size, ignore_index, row_loss, None, row_nll, row_rank, row_weight=weights)
-            ops.ce_metrics_reduce(row_nll, row_rank, labels, label_metrics.ranges_dev, label_metrics.topk, label_metrics.acc, accumulate=True)
+            if label_metrics is not None:
+                ops.ce_metrics_reduce(row_nll, row_rank, labels, label_metrics.ranges_dev, label_metrics.topk, label_metrics.acc, accumulate=True)
+            if seq_scores is not None:
+                scores, row_len = seq_scores
+                start, end = scores.flat_spans(row_len, self.device)
+                ops.seq_score_reduce(row_nll, row_rank, T, start, end, scores.topk, scores.out)
+                if scores.keep_rows:
+                    scores.row_nll, scores.row_len = row_nll.clone(), row_len
         out = torch.empty(4, dtype=torch.float32, device=self.device)
         ops.ce_reduce(row_loss, labels, self.vocab_size, ignore_index, out)
         self.label_errors = out[3]  # device scalar: labels outside [0, vocab); the trainer folds it into its one read-back and raises

@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
 __all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "swiglu_fwd",
-           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "round_bf16_sr", "set_impl", "set_attn_impl", "attn_last_dispatch",
+           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "round_bf16_sr", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
 
@@ -364,6 +364,18 @@ def ce_metrics_reduce(row_nll: Tensor, row_rank: Tensor, labels: Tensor, ranges:
     assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= 4 * (n_ranges + 1) and topk >= 1
     check(_lib.load().ssi_ce_metrics_reduce(ptr(row_nll), ptr(row_rank), ptr(labels), rows, ptr(ranges), n_ranges, int(topk), int(accumulate),
                                             ptr(out), stream_ptr()), "ssi_ce_metrics_reduce")
+
+
+def seq_score_reduce(row_nll: Tensor, row_rank: Tensor, rows: int, seq_start: Tensor, seq_end: Tensor, topk: int, out: Tensor) -> None:
+    """``out`` (fp64 ``[n_seq, 4]``, overwritten) = per sequence n_labels, sum nll, n(rank == 0), n(rank < topk) over the flat positions
+    ``[seq_start[i], seq_end[i])`` (int64 device tensors; clamped to ``[0, rows]``) of what ``ce_fwd_metrics`` wrote."""
+    n_seq = seq_start.numel()
+    assert row_nll.dtype == torch.float32 and row_nll.is_contiguous() and row_nll.numel() >= rows
+    assert row_rank.dtype == torch.int32 and row_rank.is_contiguous() and row_rank.numel() >= rows
+    assert seq_start.dtype == torch.int64 and seq_start.is_contiguous() and seq_end.dtype == torch.int64 and seq_end.is_contiguous()
+    assert seq_end.numel() == n_seq and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= 4 * n_seq
+    check(_lib.load().ssi_seq_score_reduce(ptr(row_nll), ptr(row_rank), int(rows), ptr(seq_start), ptr(seq_end), n_seq, int(topk), ptr(out),
+                                           stream_ptr()), "ssi_seq_score_reduce")
 
 
 def lmhead_ce_fwd(hidden: Tensor, table: Tensor, labels: Tensor, vocab: int, ignore_index: int, logits_ws: Tensor, row_loss: Tensor,

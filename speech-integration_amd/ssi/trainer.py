@@ -134,6 +134,7 @@ class Trainer:
         self._lag_buffers: list[Tensor] = []                   # page-locked buffers of finished read-backs, reused
         self._t_last_arrival = 0.0                             # when the previous window's results were seen on the host
         self.dev_metrics: dict[str, Any] | None = None         # per-token-type keys of the last evaluation (``eval_token_metrics``)
+        self.dev_pairs: dict[str, Any] | None = None           # dev_pair_acc, dev_pair_acc_mean, dev_pair_n of the last evaluation (``eval_pairs``)
         self.z_loss_coeff = 0.0                                # ``z_loss_coeff`` of the config (``setup``); 0: no z-loss anywhere
         self._z_loss_running = 0.0                             # the window's z part (x valid labels), beside ``loss_running``
         for name in self._FILLED_BY_SETUP:
@@ -638,7 +639,11 @@ class Trainer:
         self._log_metrics(epoch, iter_idx, mean_loss, z_loss_to_log=self._z_loss_running / window_tokens)
 
     def _evaluate(self) -> float:
-        """The dev loss; with ``eval_token_metrics`` the per-token-type keys of the same pass are left in ``self.dev_metrics`` for the log record."""
+        """The dev loss; with ``eval_token_metrics`` the per-token-type keys of the same pass are left in ``self.dev_metrics`` for the log record;
+        with ``eval_pairs`` (a JSONL file of scored pairs, ``ssi.score.score_file``) the pair accuracies in ``self.dev_pairs``."""
+        self.dev_pairs = None
+        if self.cfg.get("eval_pairs"):
+            self.dev_pairs = self._score_pairs(str(self.cfg.eval_pairs))
         kwargs = dict(epoch=self.global_step // self.geometry.steps_per_epoch, global_step=self.global_step,
                       steps_per_epoch=self.geometry.steps_per_epoch, device=self.device,
                       join_batches=int(self.cfg.get("eval_join_batches", 16) or 0) if self.cfg.get("padding_free", True) else 0,
@@ -650,6 +655,19 @@ class Trainer:
         self.dev_metrics = compute_dataset_metrics(self.model, self.data_dev, self.loss_fn, token_type_ranges=self.token_type_ranges,
                                                    topk=int(self.cfg.get("eval_topk", 5)), **kwargs)
         return self.dev_metrics["dev_loss"]
+
+    def _score_pairs(self, path: str) -> dict[str, Any]:
+        """Every rank scores the whole file: the same forward on the same weights gives the same numbers everywhere, so there is no collective
+        (and no rank waits in one while another raises)."""
+        from .score import score_file
+        tok_len = self.cfg.get("tokenizer").get("max_seq_len") if self.cfg.get("tokenizer") is not None else None
+        summary = score_file(self.model, self.tokenizer, path, None, device=self.device, row_len=int(tok_len or 2048),
+                             topk=int(self.cfg.get("eval_topk", 5)), loss_fn=self.loss_fn)
+        out: dict[str, Any] = {"dev_pair_n": summary.get("pair_n", 0)}
+        if out["dev_pair_n"]:  # a file without pairs reports its count alone: no NaN reaches the log record
+            out.update(dev_pair_acc=summary["pair_acc"], dev_pair_acc_mean=summary["pair_acc_mean"])
+        LOGGER.info(f"Global Step {self.global_step} | Dev pairs: " + " | ".join(f"{k}: {v}" for k, v in out.items()))
+        return out
 
     def _log_metrics(self, epoch: int, iter_idx: int, loss_to_log: float, snapshot: dict[str, Any] | None = None,
                      z_loss_to_log: float = 0.0) -> None:
@@ -690,6 +708,8 @@ class Trainer:
             record["dev_loss"] = dev_loss
             if self.dev_metrics is not None:  # eval_token_metrics: dev_loss.<type>, dev_acc.<type>, dev_acc_top<k>.<type>, dev_n_labels.<type>
                 record.update(self.dev_metrics)
+            if self.dev_pairs is not None:  # eval_pairs: dev_pair_acc, dev_pair_acc_mean, dev_pair_n
+                record.update(self.dev_pairs)
         if self.rank == 0:
             self.wandb_logger.log_dict(record, step=step)
 
