@@ -121,6 +121,11 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+__device__ __forceinline__ double wave_sum_f64(double v) {  // the same fixed xor tree in fp64
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 // block-wide sum for blockDim.x <= 1024; `red` is >= 16 floats of LDS; result broadcast to all threads
 __device__ __forceinline__ float block_sum(float v, float* red) {
     v = wave_sum(v);
@@ -140,6 +145,19 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     __syncthreads();
     float t = (l < nw) ? red[l] : -INFINITY;
     t = wave_max(t);
+    return t;
+}
+// block-wide integer sum for blockDim.x <= 1024; `red` is >= 16 ints of LDS; result broadcast to all threads
+__device__ __forceinline__ int block_sum_i32(int v, int* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
+    __syncthreads();
+    if (l == 0) red[w] = v;
+    __syncthreads();
+    int t = (l < nw) ? red[l] : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
     return t;
 }
 

@@ -185,30 +185,39 @@ extern "C" int ssi_embed_bwd(const int64_t* tokens, const void* dout, void* dtab
 }
 
 // =====================================================================================================================
-// K9 cross-entropy: one 512-thread block per row of [rows, ld] logits; fp32 online log-sum-exp; optional in-place
-// gradient  softmax - onehot.  Pass 2 re-reads the row (266 KB at V=133 258) from L2/Infinity Cache.
+// K9 cross-entropy over rows of [rows, ld] logits, three entries:
+//   ssi_ce_fwd(_weighted)  row_loss = w (lse - x[label]), row_lse; optional in-place gradient  w (softmax - onehot)
+//   ssi_ce_fwd_z           + the auxiliary z-loss z * log^2 Z (opt-in, z_loss_coeff of the trainer).  With lse = log Z and p = softmax:
+//                          row_z = w (lse lse)  (the coefficient is applied by the caller)
+//                          grad[c] = w (f p[c] - [c == label]),  f = 1 + 2 z lse      (d/dx of lse - x[label] + z lse^2: d lse / dx = p)
+//   ssi_ce_fwd_metrics     forward only, + row_nll = lse - x[label] and the label's rank (the dev set's per-token-type loss, top-1, top-k):
+//                          rank[r] = #{c < vocab : x[c] > x[label]} + #{c < label : x[c] == x[label]}  — the label's position in a stable
+//                          descending sort of the row; rank == 0 <=> argmax(row) == label under the first-occurrence rule.  Compares on
+//                          the stored values: an exact integer.
+// Each entry has kernels of its own in two forms — generic (any dtype and shape; one 512-thread block per row, fp32 online log-sum-exp,
+// the gradient or the rank from a second read of the row out of L2 / Infinity Cache) and register-resident bf16 rows (the training step's
+// form) — so the instantiations an entry launches do not depend on what the other entries need.  Kernels of their own, ONE body: the
+// generic kernels are built from the pieces below and the three row kernels wrap ce_row_bf16_body, so the max, the exp-sum and the lse
+// are the same statements whatever the entry: row_loss and row_lse agree bit for bit across the three, and with z = 0 (f = 1 exactly) so
+// does the gradient.
 // =====================================================================================================================
-template <typename T>
-__global__ __launch_bounds__(512) void ce_fwd_kernel(T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                     int64_t vocab, int64_t ignore_index, float* __restrict__ row_loss,
-                                                     float* __restrict__ row_lse, int write_grad, const float* __restrict__ row_weight) {
+// a row takes part iff its label is not ignored AND inside [0, vocab)
+__device__ __forceinline__ bool ce_label_valid(int64_t label, int64_t vocab, int64_t ignore_index) {
+    return label != ignore_index && label >= 0 && label < vocab;
+}
+
+// ---- generic form: the pieces (512 threads) ----------------------------------------------------------------------------------------------
+template <typename T> __device__ __forceinline__ void ce_zero_row(T* lr, int64_t nvec) {
     constexpr int N = Vec16<T>::N;
-    __shared__ float red[16];
-    const int64_t row = blockIdx.x;
-    T* lr = logits + row * ld;
-    const int64_t label = labels[row];
-    const bool valid = label != ignore_index && label >= 0 && label < vocab;
-    const int64_t nvec = ld / N;
-    if (!valid) {  // block-uniform
-        if (threadIdx.x == 0) { row_loss[row] = 0.f; if (row_lse) row_lse[row] = 0.f; }
-        if (write_grad) {
-            Vec16<T> z;
+    Vec16<T> z;
 #pragma unroll
-            for (int i = 0; i < N; ++i) z.set(i, 0.f);
-            for (int64_t v = threadIdx.x; v < nvec; v += 512) store16(lr + v * N, z);
-        }
-        return;
-    }
+    for (int i = 0; i < N; ++i) z.set(i, 0.f);
+    for (int64_t v = threadIdx.x; v < nvec; v += 512) store16(lr + v * N, z);
+}
+
+// online log-sum-exp over the columns [0, vocab) of one row
+template <typename T> __device__ __forceinline__ float ce_row_lse(const T* lr, int64_t nvec, int64_t vocab, float* red) {
+    constexpr int N = Vec16<T>::N;
     float m = -INFINITY, s = 0.f;
     for (int64_t v = threadIdx.x; v < nvec; v += 512) {
         Vec16<T> a = load16(lr + v * N);
@@ -222,7 +231,45 @@ __global__ __launch_bounds__(512) void ce_fwd_kernel(T* __restrict__ logits, int
     const float gm = block_max(m, red);
     s = (m == -INFINITY) ? 0.f : s * expf(m - gm);
     const float gs = block_sum(s, red);
-    const float lse = gm + logf(gs);
+    return gm + logf(gs);
+}
+
+// in-place gradient of one row: w (f p - onehot) with the z-loss factor f, w (p - onehot) without (no multiply by 1); pad columns 0.  f may have
+// any sign: lse < -1 / (2 z) makes it negative, and the plain multiply carries that
+template <bool WITH_F, typename T>
+__device__ __forceinline__ void ce_grad_row(T* lr, int64_t nvec, int64_t vocab, int64_t label, float lse, float w, float f) {
+    constexpr int N = Vec16<T>::N;
+    for (int64_t v = threadIdx.x; v < nvec; v += 512) {
+        Vec16<T> a = load16(lr + v * N), o;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const int64_t c = v * N + i;
+            float g = 0.f;
+            if (c < vocab) {
+                if constexpr (WITH_F) g = w * (f * expf(a.get(i) - lse) - (c == label ? 1.f : 0.f));
+                else g = w * (expf(a.get(i) - lse) - (c == label ? 1.f : 0.f));
+            }
+            o.set(i, g);
+        }
+        store16(lr + v * N, o);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(512) void ce_fwd_kernel(T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                     int64_t vocab, int64_t ignore_index, float* __restrict__ row_loss,
+                                                     float* __restrict__ row_lse, int write_grad, const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    const int64_t row = blockIdx.x;
+    T* lr = logits + row * ld;
+    const int64_t label = labels[row];
+    const int64_t nvec = ld / Vec16<T>::N;
+    if (!ce_label_valid(label, vocab, ignore_index)) {  // block-uniform
+        if (threadIdx.x == 0) { row_loss[row] = 0.f; if (row_lse) row_lse[row] = 0.f; }
+        if (write_grad) ce_zero_row(lr, nvec);
+        return;
+    }
+    const float lse = ce_row_lse(lr, nvec, vocab, red);
     const float w = row_weight ? row_weight[row] : 1.f;  // weighted rows (ssi_ce_fwd_weighted): loss and gradient of the row times w
     if (threadIdx.x == 0) {
         row_loss[row] = w * (lse - to_f32<T>(lr[label]));
@@ -230,32 +277,36 @@ __global__ __launch_bounds__(512) void ce_fwd_kernel(T* __restrict__ logits, int
     }
     if (!write_grad) return;
     __syncthreads();  // lr[label] read above must precede the overwrite below
-    for (int64_t v = threadIdx.x; v < nvec; v += 512) {
-        Vec16<T> a = load16(lr + v * N), o;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const int64_t c = v * N + i;
-            float g = 0.f;
-            if (c < vocab) g = w * (expf(a.get(i) - lse) - (c == label ? 1.f : 0.f));
-            o.set(i, g);
-        }
-        store16(lr + v * N, o);
-    }
+    ce_grad_row<false>(lr, nvec, vocab, label, lse, w, 1.f);
 }
 
-// bf16 rows held in registers (the training step's form): one 1024-thread workgroup per CU walks rows; a row of NCH x 8192 logits
-// (NCH = 17: 139 264 >= 133 376) lives in NCH 16-byte registers per thread, so the log-sum-exp and the gradient both come from ONE
-// read of the row: 2 passes over the logits (read + write back = 8.7 GB at T = 16 384, V = 133 258) instead of the 3 of
-// ce_fwd_kernel above (13.1 GB).  A register's next-row load is issued as soon as its gradient has been stored, so the next row
-// streams in under the stores and the exps of the current one.  NCH = ceil(ld / 8192) exactly and ld - vocab < 8192: only the last
-// two chunks can hold columns that are not vocabulary.  Straight-line body (the only branches are workgroup-uniform and read-only
-// on the row registers): with per-chunk branches hipcc spills the row.
-template <int NCH, bool write_grad>
-__global__ __launch_bounds__(1024, 4) void ce_row_bf16_kernel(bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                              int64_t rows, int64_t vocab, int64_t ignore_index,
-                                                              float* __restrict__ row_loss, float* __restrict__ row_lse,
-                                                              const float* __restrict__ row_weight) {
-    __shared__ float red[16];
+// ---- bf16 rows held in registers (the training step's form) -------------------------------------------------------------------------------
+// One 1024-thread workgroup per CU walks rows; a row of NCH x 8192 logits (NCH = 17: 139 264 >= 133 376) lives in NCH 16-byte registers
+// per thread, so the log-sum-exp and the gradient both come from ONE read of the row: 2 passes over the logits (read + write back = 8.7 GB
+// at T = 16 384, V = 133 258) instead of the 3 of ce_fwd_kernel above (13.1 GB).  A register's next-row load is issued as soon as its
+// gradient has been stored, so the next row streams in under the stores and the exps of the current one.  NCH = ceil(ld / 8192) exactly
+// and ld - vocab < 8192: only the last two chunks can hold columns that are not vocabulary.  Straight-line body (the only branches are
+// workgroup-uniform and read-only on the row registers): with per-chunk branches hipcc spills the row.
+//
+// The body of all three row kernels; what an entry adds sits behind `if constexpr` on MODE, and the kernels pass nullptr / 0 for what is
+// not theirs:
+//   CE_Z        one scalar per row.  |f| rides in the exponent's additive term beside log2 w (f = 0: log2 0 = -inf, every exp2 gives 0 —
+//               the row is -w on the label and 0 elsewhere).  The SIGN of f is applied to the packed result: the row computes
+//               w |f| p - sign(f) w [c == label]  and, for f < 0, flips the sign bit of all eight bf16 of a register (4 XORs per chunk with
+//               a per-row mask that is 0 otherwise; round-to-nearest-even is symmetric in the sign, so this IS the rounding of
+//               w (f p - onehot)).  No branch per chunk.  (For f < 0 the columns whose gradient is 0 — pads, underflows — hold -0.)
+//   CE_METRICS  no gradient (write_grad is false) and one more pass over the packed registers: compare with the label's logit and count.
+//               Every lane needs that logit before the pass; the label is workgroup-uniform and nothing is overwritten here, so each
+//               lane loads it itself from one address and nothing has to wait for it to land.  The pad columns are -inf in the
+//               registers and lie above every valid label: they are neither greater than a logit nor tie below the label.
+enum CeMode { CE_PLAIN, CE_Z, CE_METRICS };
+
+template <int NCH, CeMode MODE, bool write_grad>
+__device__ __forceinline__ void ce_row_bf16_body(bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels, int64_t rows,
+                                                 int64_t vocab, int64_t ignore_index, float two_z, float* __restrict__ row_loss,
+                                                 float* __restrict__ row_lse, float* __restrict__ row_z, float* __restrict__ row_nll,
+                                                 int32_t* __restrict__ row_rank, const float* __restrict__ row_weight, float* red, int* redi) {
+    static_assert(MODE != CE_METRICS || !write_grad, "the metrics form writes no gradient");
     constexpr float LOG2E = 1.44269504088896340736f;
     constexpr int CHUNK = 8192;                      // columns per chunk: 1024 threads x 8 bf16
     const int tid = threadIdx.x;
@@ -264,11 +315,10 @@ __global__ __launch_bounds__(1024, 4) void ce_row_bf16_kernel(bf16_t* __restrict
     const int row_bytes = (int)(ld * 2);             // buffer bound: loads beyond the row return 0, stores beyond it are dropped
     const int vocab_i = (int)vocab;
     u32x4 x[NCH];
-    auto is_valid = [&](int64_t label) { return label != ignore_index && label >= 0 && label < vocab; };
     auto rsrc_of = [&](int64_t row) { return __builtin_amdgcn_make_buffer_rsrc(logits + row * ld, 0, row_bytes, 0x00020000u); };
     auto lo = [](unsigned u) { return __builtin_bit_cast(float, u << 16); };
     auto hi = [](unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); };
-    // the three passes each re-derive the fp32 values from the packed registers: without this opaque touch the compiler keeps all
+    // the passes each re-derive the fp32 values from the packed registers: without this opaque touch the compiler keeps all
     // 8 x NCH converted floats alive across the passes and spills
     auto opaque = [&]() {
 #pragma unroll
@@ -286,14 +336,14 @@ __global__ __launch_bounds__(1024, 4) void ce_row_bf16_kernel(bf16_t* __restrict
     for (; row < rows; row += gridDim.x) {
         const int64_t next = row + gridDim.x;
         const int64_t label = labels[row];
-        const bool valid = is_valid(label);
+        const bool valid = ce_label_valid(label, vocab, ignore_index);
         // a weighted row (ssi_ce_fwd_weighted): w * exp(x - lse) = exp2(x log2e - lse log2e + log2 w) — the weight rides in the exponent's
         // additive term at no cost per element; w = 1 (and no weights) adds an exact 0
         const float w = row_weight ? row_weight[row] : 1.f;
         const float log2w = row_weight ? __log2f(w) : 0.f;
         const __amdgpu_buffer_rsrc_t rs = rsrc_of(row);
         // columns that are not vocabulary (the pad columns [vocab, ld), and beyond the row where the loads returned 0) become -inf
-        // once, in the registers: max, exp-sum and gradient (exp2(-inf) = 0) then need no column test at all
+        // once, in the registers: max, exp-sum, gradient (exp2(-inf) = 0) and rank then need no column test at all
 #pragma unroll
         for (int c = (NCH >= 2 ? NCH - 2 : 0); c < NCH; ++c) {
             const int left = vocab_i - c * CHUNK - col0;  // real columns from this lane's first one on
@@ -304,9 +354,11 @@ __global__ __launch_bounds__(1024, 4) void ce_row_bf16_kernel(bf16_t* __restrict
             }
         }
         float nl = -INFINITY;  // ignored / out-of-range label: every exp2 below gives 0 -> zero gradient row
+        float wl = w;          // what the label column subtracts BEFORE the sign flip: sign(f) w  (CE_Z; w otherwise)
+        unsigned flip = 0u;    // sign bits of the two bf16 of a packed dword, set iff f < 0  (CE_Z)
         if (valid) {           // workgroup-uniform; reads the row registers only
-            float xl = 0.f;
-            if (tid == 0) xl = (float)logits[row * ld + label];  // before this row's gradient is written (program order of one thread)
+            float xl = 0.f;    // before this row's gradient is written (program order of one thread)
+            if (MODE == CE_METRICS || tid == 0) xl = (float)logits[row * ld + label];
             float m = -INFINITY;
 #pragma unroll
             for (int c = 0; c < NCH; ++c)
@@ -314,7 +366,7 @@ __global__ __launch_bounds__(1024, 4) void ce_row_bf16_kernel(bf16_t* __restrict
                 for (int d = 0; d < 4; ++d) m = fmaxf(m, fmaxf(lo(x[c][d]), hi(x[c][d])));
             // thread 0's label logit must have LANDED before any wave may overwrite that address with the gradient: the barrier inside
             // block_max only orders issue.  Free here: the row registers the max just consumed were the only other loads in flight.
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if constexpr (MODE != CE_METRICS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             const float gm = block_max(m, red);
             opaque();
             const float nm = -gm * LOG2E;
@@ -326,272 +378,46 @@ __global__ __launch_bounds__(1024, 4) void ce_row_bf16_kernel(bf16_t* __restrict
                     s += __builtin_amdgcn_exp2f(fmaf(lo(x[c][d]), LOG2E, nm)) + __builtin_amdgcn_exp2f(fmaf(hi(x[c][d]), LOG2E, nm));
             const float gs = block_sum(s, red);
             const float lse = gm + logf(gs);
+            int cnt = 0;
+            if constexpr (MODE == CE_METRICS) {
+                opaque();
+                // ---- the rank pass: element e of chunk c is column c * CHUNK + col0 + e; it ties BELOW the label iff e < below - c * CHUNK
+                const int below = (int)label - col0;
+#pragma unroll
+                for (int c = 0; c < NCH; ++c) {
+                    const int b = below - c * CHUNK;
+#pragma unroll
+                    for (int d = 0; d < 4; ++d) {
+                        const float a0 = lo(x[c][d]), a1 = hi(x[c][d]);
+                        // bitwise on purpose: || and && became a branch per element, and the row spilled
+                        cnt += (int)(a0 > xl) | ((int)(a0 == xl) & (int)(2 * d < b));
+                        cnt += (int)(a1 > xl) | ((int)(a1 == xl) & (int)(2 * d + 1 < b));
+                    }
+                }
+                cnt = block_sum_i32(cnt, redi);
+            }
             if (tid == 0) {
                 row_loss[row] = w * (lse - xl);
                 if (row_lse) row_lse[row] = lse;
+                if constexpr (MODE == CE_Z) row_z[row] = w * (lse * lse);
+                if constexpr (MODE == CE_METRICS) { row_nll[row] = lse - xl; row_rank[row] = cnt; }
             }
             nl = -lse * LOG2E + log2w;
+            if constexpr (MODE == CE_Z) {
+                const float f = fmaf(two_z, lse, 1.f);
+                nl += __log2f(fabsf(f));  // z = 0: f = 1 and this term an exact 0 — the nl of CE_PLAIN
+                if (f < 0.f) { wl = -w; flip = 0x80008000u; }
+            }
         } else if (tid == 0) {
             row_loss[row] = 0.f;
             if (row_lse) row_lse[row] = 0.f;
+            if constexpr (MODE == CE_Z) row_z[row] = 0.f;
+            if constexpr (MODE == CE_METRICS) { row_nll[row] = 0.f; row_rank[row] = -1; }
         }
         opaque();
         // ---- gradient softmax - onehot, written over the logits; each register then takes the next row's chunk (past the last row:
         // this row again — a few wasted loads at the very end instead of a branch around every load)
         const int hot = valid ? (int)label - col0 : -(1 << 30);  // the label's column relative to this lane's first column of chunk 0
-        const __amdgpu_buffer_rsrc_t rn = rsrc_of(next < rows ? next : row);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            if (write_grad) {
-                float g[8];
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    g[2 * d] = __builtin_amdgcn_exp2f(fmaf(lo(x[c][d]), LOG2E, nl));
-                    g[2 * d + 1] = __builtin_amdgcn_exp2f(fmaf(hi(x[c][d]), LOG2E, nl));
-                }
-                const int h = hot - c * CHUNK;
-                if ((unsigned)h < 8u) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) if (e == h) g[e] -= w;
-                }
-                bf16x8 ob;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) ob[e] = (bf16_t)g[e];
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ob), rs, voff, c * CHUNK * 2, 2 /* nt: streamed once */);
-            }
-            x[c] = __builtin_amdgcn_raw_buffer_load_b128(rn, voff, c * CHUNK * 2, 2 /* nt */);
-            __builtin_amdgcn_sched_barrier(0);  // one chunk at a time: a hoisted next-row load would need a register of its own
-        }
-    }
-}
-
-static int ce_num_cus() {
-    static const int n = [] {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        return cus;
-    }();  // thread-safe one-time initialisation (C++11 magic static)
-    return n;
-}
-
-extern "C" int ssi_ce_fwd_weighted(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
-                                   int64_t ignore_index, float* row_loss, float* row_lse, int write_grad, int dtype, void* stream) {
-    SSI_CHECK_ARG(logits && labels && row_loss && rows >= 0 && vocab > 0 && ld >= vocab && ld % 8 == 0);
-    if (rows == 0) return SSI_OK;
-    const int64_t chunks = ssi_cdiv(ld, 8192);
-    const bool row_form = dtype == SSI_BF16 && ((uintptr_t)logits & 15) == 0 && ld - vocab < 8192 && ld * 2 < (1LL << 31) &&
-                          (chunks <= 4 || chunks == 8 || (chunks >= 16 && chunks <= 18));
-    if (row_form) {
-        const dim3 grid((unsigned)(rows < ce_num_cus() ? rows : ce_num_cus()));
-#define SSI_CE_ROW(N)                                                                                                                       \
-    case N:                                                                                                                                 \
-        if (write_grad) hipLaunchKernelGGL((ce_row_bf16_kernel<N, true>), grid, dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits, ld, labels, \
-                                           rows, vocab, ignore_index, row_loss, row_lse, row_weight);                                       \
-        else hipLaunchKernelGGL((ce_row_bf16_kernel<N, false>), grid, dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits, ld, labels, rows,     \
-                                vocab, ignore_index, row_loss, row_lse, row_weight);                                                        \
-        break
-        switch ((int)chunks) {
-            SSI_CE_ROW(1); SSI_CE_ROW(2); SSI_CE_ROW(3); SSI_CE_ROW(4); SSI_CE_ROW(8); SSI_CE_ROW(16); SSI_CE_ROW(17); SSI_CE_ROW(18);
-        }
-#undef SSI_CE_ROW
-        SSI_LAUNCH_CHECK();
-        return SSI_OK;
-    }
-    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(ce_fwd_kernel<T>, dim3((unsigned)rows), dim3(512), 0, (hipStream_t)stream,
-                                                 (T*)logits, ld, labels, vocab, ignore_index, row_loss, row_lse, write_grad, row_weight));
-    SSI_LAUNCH_CHECK();
-    return SSI_OK;
-}
-
-extern "C" int ssi_ce_fwd(void* logits, int64_t ld, const int64_t* labels, int64_t rows, int64_t vocab,
-                          int64_t ignore_index, float* row_loss, float* row_lse, int write_grad, int dtype, void* stream) {
-    return ssi_ce_fwd_weighted(logits, ld, labels, nullptr, rows, vocab, ignore_index, row_loss, row_lse, write_grad, dtype, stream);
-}
-
-// The valid-label count uses the predicate of the row kernels (not ignored AND inside [0, vocab)); labels that are neither ignored
-// nor in range are counted in out[3] so that the caller can raise on its next host read-back (torch would device-assert).
-__global__ __launch_bounds__(1024) void ce_reduce_kernel(const float* __restrict__ row_loss, const int64_t* __restrict__ labels,
-                                                         int64_t rows, int64_t vocab, int64_t ignore_index, float* __restrict__ out) {
-    __shared__ float red[16];
-    float s = 0.f, c = 0.f, bad = 0.f;
-    for (int64_t r = threadIdx.x; r < rows; r += 1024) {
-        const int64_t l = labels[r];
-        const bool in_range = l >= 0 && l < vocab;
-        if (l != ignore_index && in_range) { s += row_loss[r]; c += 1.f; }
-        else if (l != ignore_index) bad += 1.f;
-    }
-    s = block_sum(s, red);
-    c = block_sum(c, red);
-    bad = block_sum(bad, red);
-    if (threadIdx.x == 0) { out[0] = s / c; out[1] = s; out[2] = c; out[3] = bad; }
-}
-
-extern "C" int ssi_ce_reduce(const float* row_loss, const int64_t* labels, int64_t rows, int64_t vocab, int64_t ignore_index,
-                             float* out, void* stream) {
-    SSI_CHECK_ARG(row_loss && labels && out && rows >= 0 && rows < (1LL << 24) && vocab > 0);
-    hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, row_loss, labels, rows, vocab, ignore_index, out);
-    SSI_LAUNCH_CHECK();
-    return SSI_OK;
-}
-
-// =====================================================================================================================
-// K9z cross-entropy with the auxiliary z-loss z * log^2 Z (ssi_ce_fwd_z; opt-in, z_loss_coeff of the trainer).  Per valid row, with
-// lse = log Z, p = softmax and the row's weight w:
-//   row_loss = w (lse - x[label])  (unchanged)     row_z = w (lse lse)  (the coefficient is applied by the caller)
-//   grad[c]  = w (f p[c] - [c == label]),  f = 1 + 2 z lse      (d/dx of lse - x[label] + z lse^2: d lse / dx = p)
-// Kernels of their own, as the metrics ones below: the instantiations the plain entries launch stay what they were.  The max, the exp-sum
-// and the lse are the statements of ce_fwd_kernel / ce_row_bf16_kernel in their order: row_loss and row_lse agree bit for bit, and with
-// z = 0 (f = 1 exactly) so does the gradient.
-// =====================================================================================================================
-template <typename T>
-__global__ __launch_bounds__(512) void ce_fwd_z_kernel(T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                       int64_t vocab, int64_t ignore_index, float two_z, float* __restrict__ row_loss,
-                                                       float* __restrict__ row_lse, float* __restrict__ row_z, int write_grad,
-                                                       const float* __restrict__ row_weight) {
-    constexpr int N = Vec16<T>::N;
-    __shared__ float red[16];
-    const int64_t row = blockIdx.x;
-    T* lr = logits + row * ld;
-    const int64_t label = labels[row];
-    const bool valid = label != ignore_index && label >= 0 && label < vocab;
-    const int64_t nvec = ld / N;
-    if (!valid) {  // block-uniform
-        if (threadIdx.x == 0) { row_loss[row] = 0.f; if (row_lse) row_lse[row] = 0.f; row_z[row] = 0.f; }
-        if (write_grad) {
-            Vec16<T> z;
-#pragma unroll
-            for (int i = 0; i < N; ++i) z.set(i, 0.f);
-            for (int64_t v = threadIdx.x; v < nvec; v += 512) store16(lr + v * N, z);
-        }
-        return;
-    }
-    float m = -INFINITY, s = 0.f;
-    for (int64_t v = threadIdx.x; v < nvec; v += 512) {
-        Vec16<T> a = load16(lr + v * N);
-        float lm = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < N; ++i) if (v * N + i < vocab) lm = fmaxf(lm, a.get(i));
-        if (lm > m) { s *= expf(m - lm); m = lm; }
-#pragma unroll
-        for (int i = 0; i < N; ++i) if (v * N + i < vocab) s += expf(a.get(i) - m);
-    }
-    const float gm = block_max(m, red);
-    s = (m == -INFINITY) ? 0.f : s * expf(m - gm);
-    const float gs = block_sum(s, red);
-    const float lse = gm + logf(gs);
-    const float w = row_weight ? row_weight[row] : 1.f;
-    if (threadIdx.x == 0) {
-        row_loss[row] = w * (lse - to_f32<T>(lr[label]));
-        if (row_lse) row_lse[row] = lse;
-        row_z[row] = w * (lse * lse);
-    }
-    if (!write_grad) return;
-    const float f = fmaf(two_z, lse, 1.f);  // any sign: lse < -1 / (2 z) makes it negative, and the plain multiply below carries that
-    __syncthreads();  // lr[label] read above must precede the overwrite below
-    for (int64_t v = threadIdx.x; v < nvec; v += 512) {
-        Vec16<T> a = load16(lr + v * N), o;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const int64_t c = v * N + i;
-            float g = 0.f;
-            if (c < vocab) g = w * (f * expf(a.get(i) - lse) - (c == label ? 1.f : 0.f));
-            o.set(i, g);
-        }
-        store16(lr + v * N, o);
-    }
-}
-
-// The register-resident form: ce_row_bf16_kernel statement for statement, plus one scalar per row.  |f| rides in the exponent's additive
-// term beside log2 w (f = 0: log2 0 = -inf, every exp2 gives 0 — the row is -w on the label and 0 elsewhere).  The SIGN of f is applied to
-// the packed result: the row computes  w |f| p - sign(f) w [c == label]  and, for f < 0, flips the sign bit of all eight bf16 of a
-// register (4 XORs per chunk with a per-row mask that is 0 otherwise; round-to-nearest-even is symmetric in the sign, so this IS the
-// rounding of w (f p - onehot)).  No branch per chunk: the body stays straight-line and the row stays in its registers.  (For f < 0 the
-// columns whose gradient is 0 — pads, underflows — hold -0.)
-template <int NCH, bool write_grad>
-__global__ __launch_bounds__(1024, 4) void ce_row_bf16_z_kernel(bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                                int64_t rows, int64_t vocab, int64_t ignore_index, float two_z,
-                                                                float* __restrict__ row_loss, float* __restrict__ row_lse,
-                                                                float* __restrict__ row_z, const float* __restrict__ row_weight) {
-    __shared__ float red[16];
-    constexpr float LOG2E = 1.44269504088896340736f;
-    constexpr int CHUNK = 8192;
-    const int tid = threadIdx.x;
-    const int voff = tid * 16;
-    const int col0 = tid * 8;
-    const int row_bytes = (int)(ld * 2);
-    const int vocab_i = (int)vocab;
-    u32x4 x[NCH];
-    auto is_valid = [&](int64_t label) { return label != ignore_index && label >= 0 && label < vocab; };
-    auto rsrc_of = [&](int64_t row) { return __builtin_amdgcn_make_buffer_rsrc(logits + row * ld, 0, row_bytes, 0x00020000u); };
-    auto lo = [](unsigned u) { return __builtin_bit_cast(float, u << 16); };
-    auto hi = [](unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); };
-    auto opaque = [&]() {  // as in ce_row_bf16_kernel: each pass re-derives its floats from the packed registers
-#pragma unroll
-        for (int c = 0; c < NCH; ++c)
-#pragma unroll
-            for (int d = 0; d < 4; ++d) asm volatile("" : "+v"(x[c][d]));
-    };
-    int64_t row = blockIdx.x;
-    if (row >= rows) return;
-    {
-        const __amdgpu_buffer_rsrc_t r0 = rsrc_of(row);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) x[c] = __builtin_amdgcn_raw_buffer_load_b128(r0, voff, c * CHUNK * 2, 0);
-    }
-    for (; row < rows; row += gridDim.x) {
-        const int64_t next = row + gridDim.x;
-        const int64_t label = labels[row];
-        const bool valid = is_valid(label);
-        const float w = row_weight ? row_weight[row] : 1.f;
-        const float log2w = row_weight ? __log2f(w) : 0.f;
-        const __amdgpu_buffer_rsrc_t rs = rsrc_of(row);
-#pragma unroll
-        for (int c = (NCH >= 2 ? NCH - 2 : 0); c < NCH; ++c) {
-            const int left = vocab_i - c * CHUNK - col0;
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-                if (2 * d >= left) x[c][d] = (x[c][d] & 0xffff0000u) | 0x0000ff80u;
-                if (2 * d + 1 >= left) x[c][d] = (x[c][d] & 0x0000ffffu) | 0xff800000u;
-            }
-        }
-        float nl = -INFINITY;  // ignored / out-of-range label: every exp2 below gives 0 -> zero gradient row
-        float wl = w;          // what the label column subtracts BEFORE the sign flip: sign(f) w
-        unsigned flip = 0u;    // sign bits of the two bf16 of a packed dword, set iff f < 0
-        if (valid) {           // workgroup-uniform; reads the row registers only
-            float xl = 0.f;
-            if (tid == 0) xl = (float)logits[row * ld + label];
-            float m = -INFINITY;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c)
-#pragma unroll
-                for (int d = 0; d < 4; ++d) m = fmaxf(m, fmaxf(lo(x[c][d]), hi(x[c][d])));
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the label logit has landed before any wave overwrites it (ce_row_bf16_kernel)
-            const float gm = block_max(m, red);
-            opaque();
-            const float nm = -gm * LOG2E;
-            float s = 0.f;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c)
-#pragma unroll
-                for (int d = 0; d < 4; ++d)
-                    s += __builtin_amdgcn_exp2f(fmaf(lo(x[c][d]), LOG2E, nm)) + __builtin_amdgcn_exp2f(fmaf(hi(x[c][d]), LOG2E, nm));
-            const float gs = block_sum(s, red);
-            const float lse = gm + logf(gs);
-            if (tid == 0) {
-                row_loss[row] = w * (lse - xl);
-                if (row_lse) row_lse[row] = lse;
-                row_z[row] = w * (lse * lse);
-            }
-            const float f = fmaf(two_z, lse, 1.f);
-            nl = (-lse * LOG2E + log2w) + __log2f(fabsf(f));  // z = 0: f = 1 and the last term an exact 0 — the nl of ce_row_bf16_kernel
-            if (f < 0.f) { wl = -w; flip = 0x80008000u; }
-        } else if (tid == 0) {
-            row_loss[row] = 0.f;
-            if (row_lse) row_lse[row] = 0.f;
-            row_z[row] = 0.f;
-        }
-        opaque();
-        const int hot = valid ? (int)label - col0 : -(1 << 30);
         const __amdgpu_buffer_rsrc_t rn = rsrc_of(next < rows ? next : row);
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
@@ -611,14 +437,143 @@ __global__ __launch_bounds__(1024, 4) void ce_row_bf16_z_kernel(bf16_t* __restri
 #pragma unroll
                 for (int e = 0; e < 8; ++e) ob[e] = (bf16_t)g[e];
                 u32x4 o = __builtin_bit_cast(u32x4, ob);
+                if constexpr (MODE == CE_Z) {
 #pragma unroll
-                for (int d = 0; d < 4; ++d) o[d] ^= flip;
+                    for (int d = 0; d < 4; ++d) o[d] ^= flip;
+                }
                 __builtin_amdgcn_raw_buffer_store_b128(o, rs, voff, c * CHUNK * 2, 2 /* nt: streamed once */);
             }
             x[c] = __builtin_amdgcn_raw_buffer_load_b128(rn, voff, c * CHUNK * 2, 2 /* nt */);
-            __builtin_amdgcn_sched_barrier(0);  // one chunk at a time, as in ce_row_bf16_kernel
+            __builtin_amdgcn_sched_barrier(0);  // one chunk at a time: a hoisted next-row load would need a register of its own
         }
     }
+}
+
+template <int NCH, bool write_grad>
+__global__ __launch_bounds__(1024, 4) void ce_row_bf16_kernel(bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                              int64_t rows, int64_t vocab, int64_t ignore_index,
+                                                              float* __restrict__ row_loss, float* __restrict__ row_lse,
+                                                              const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    ce_row_bf16_body<NCH, CE_PLAIN, write_grad>(logits, ld, labels, rows, vocab, ignore_index, 0.f, row_loss, row_lse, nullptr, nullptr, nullptr,
+                                                row_weight, red, nullptr);
+}
+
+// ---- host side: which form an input takes, and the chunk counts the row form is instantiated for --------------------------------------
+static int ce_num_cus() {
+    static const int n = [] {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        return cus;
+    }();  // thread-safe one-time initialisation (C++11 magic static)
+    return n;
+}
+
+// the one predicate of the three entries: the same inputs take the same form in each
+static bool ce_row_form(int dtype, const void* logits, int64_t ld, int64_t vocab) {
+    const int64_t chunks = ssi_cdiv(ld, 8192);
+    return dtype == SSI_BF16 && ((uintptr_t)logits & 15) == 0 && ld - vocab < 8192 && ld * 2 < (1LL << 31) &&
+           (chunks <= 4 || chunks == 8 || (chunks >= 16 && chunks <= 18));
+}
+static dim3 ce_row_grid(int64_t rows) { return dim3((unsigned)(rows < ce_num_cus() ? rows : ce_num_cus())); }
+
+// runs the statement(s) with N = ceil(ld / 8192) as a constant, for the chunk counts ce_row_form admits (as SSI_DISPATCH_DTYPE does with T)
+#define SSI_CE_CHUNKS_CASE(n, ...) case n: { constexpr int N = n; __VA_ARGS__; } break;
+#define SSI_CE_DISPATCH_CHUNKS(ld, ...)                                                                                                 \
+    switch ((int)ssi_cdiv(ld, 8192)) {                                                                                                  \
+        SSI_CE_CHUNKS_CASE(1, __VA_ARGS__) SSI_CE_CHUNKS_CASE(2, __VA_ARGS__) SSI_CE_CHUNKS_CASE(3, __VA_ARGS__)                        \
+        SSI_CE_CHUNKS_CASE(4, __VA_ARGS__) SSI_CE_CHUNKS_CASE(8, __VA_ARGS__) SSI_CE_CHUNKS_CASE(16, __VA_ARGS__)                       \
+        SSI_CE_CHUNKS_CASE(17, __VA_ARGS__) SSI_CE_CHUNKS_CASE(18, __VA_ARGS__)                                                         \
+    }
+
+extern "C" int ssi_ce_fwd_weighted(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
+                                   int64_t ignore_index, float* row_loss, float* row_lse, int write_grad, int dtype, void* stream) {
+    SSI_CHECK_ARG(logits && labels && row_loss && rows >= 0 && vocab > 0 && ld >= vocab && ld % 8 == 0);
+    if (rows == 0) return SSI_OK;
+    if (ce_row_form(dtype, logits, ld, vocab)) {
+        SSI_CE_DISPATCH_CHUNKS(ld,
+            if (write_grad) hipLaunchKernelGGL((ce_row_bf16_kernel<N, true>), ce_row_grid(rows), dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits,
+                                               ld, labels, rows, vocab, ignore_index, row_loss, row_lse, row_weight);
+            else hipLaunchKernelGGL((ce_row_bf16_kernel<N, false>), ce_row_grid(rows), dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits, ld,
+                                    labels, rows, vocab, ignore_index, row_loss, row_lse, row_weight));
+        SSI_LAUNCH_CHECK();
+        return SSI_OK;
+    }
+    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(ce_fwd_kernel<T>, dim3((unsigned)rows), dim3(512), 0, (hipStream_t)stream,
+                                                 (T*)logits, ld, labels, vocab, ignore_index, row_loss, row_lse, write_grad, row_weight));
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+extern "C" int ssi_ce_fwd(void* logits, int64_t ld, const int64_t* labels, int64_t rows, int64_t vocab,
+                          int64_t ignore_index, float* row_loss, float* row_lse, int write_grad, int dtype, void* stream) {
+    return ssi_ce_fwd_weighted(logits, ld, labels, nullptr, rows, vocab, ignore_index, row_loss, row_lse, write_grad, dtype, stream);
+}
+
+// The valid-label count uses the predicate of the row kernels; labels that are neither ignored nor in range are counted in out[3] so that
+// the caller can raise on its next host read-back (torch would device-assert).
+__global__ __launch_bounds__(1024) void ce_reduce_kernel(const float* __restrict__ row_loss, const int64_t* __restrict__ labels,
+                                                         int64_t rows, int64_t vocab, int64_t ignore_index, float* __restrict__ out) {
+    __shared__ float red[16];
+    float s = 0.f, c = 0.f, bad = 0.f;
+    for (int64_t r = threadIdx.x; r < rows; r += 1024) {
+        const int64_t l = labels[r];
+        if (ce_label_valid(l, vocab, ignore_index)) { s += row_loss[r]; c += 1.f; }
+        else if (l != ignore_index) bad += 1.f;
+    }
+    s = block_sum(s, red);
+    c = block_sum(c, red);
+    bad = block_sum(bad, red);
+    if (threadIdx.x == 0) { out[0] = s / c; out[1] = s; out[2] = c; out[3] = bad; }
+}
+
+extern "C" int ssi_ce_reduce(const float* row_loss, const int64_t* labels, int64_t rows, int64_t vocab, int64_t ignore_index,
+                             float* out, void* stream) {
+    SSI_CHECK_ARG(row_loss && labels && out && rows >= 0 && rows < (1LL << 24) && vocab > 0);
+    hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, row_loss, labels, rows, vocab, ignore_index, out);
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+// =====================================================================================================================
+// K9z the kernels of ssi_ce_fwd_z (see K9)
+// =====================================================================================================================
+template <typename T>
+__global__ __launch_bounds__(512) void ce_fwd_z_kernel(T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                       int64_t vocab, int64_t ignore_index, float two_z, float* __restrict__ row_loss,
+                                                       float* __restrict__ row_lse, float* __restrict__ row_z, int write_grad,
+                                                       const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    const int64_t row = blockIdx.x;
+    T* lr = logits + row * ld;
+    const int64_t label = labels[row];
+    const int64_t nvec = ld / Vec16<T>::N;
+    if (!ce_label_valid(label, vocab, ignore_index)) {  // block-uniform
+        if (threadIdx.x == 0) { row_loss[row] = 0.f; if (row_lse) row_lse[row] = 0.f; row_z[row] = 0.f; }
+        if (write_grad) ce_zero_row(lr, nvec);
+        return;
+    }
+    const float lse = ce_row_lse(lr, nvec, vocab, red);
+    const float w = row_weight ? row_weight[row] : 1.f;
+    if (threadIdx.x == 0) {
+        row_loss[row] = w * (lse - to_f32<T>(lr[label]));
+        if (row_lse) row_lse[row] = lse;
+        row_z[row] = w * (lse * lse);
+    }
+    if (!write_grad) return;
+    const float f = fmaf(two_z, lse, 1.f);
+    __syncthreads();  // lr[label] read above must precede the overwrite below
+    ce_grad_row<true>(lr, nvec, vocab, label, lse, w, f);
+}
+
+template <int NCH, bool write_grad>
+__global__ __launch_bounds__(1024, 4) void ce_row_bf16_z_kernel(bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                                int64_t rows, int64_t vocab, int64_t ignore_index, float two_z,
+                                                                float* __restrict__ row_loss, float* __restrict__ row_lse,
+                                                                float* __restrict__ row_z, const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    ce_row_bf16_body<NCH, CE_Z, write_grad>(logits, ld, labels, rows, vocab, ignore_index, two_z, row_loss, row_lse, row_z, nullptr, nullptr,
+                                            row_weight, red, nullptr);
 }
 
 extern "C" int ssi_ce_fwd_z(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
@@ -631,23 +586,12 @@ extern "C" int ssi_ce_fwd_z(void* logits, int64_t ld, const int64_t* labels, con
     }
     if (rows == 0) return SSI_OK;
     const float two_z = 2.f * z_coeff;
-    const int64_t chunks = ssi_cdiv(ld, 8192);
-    // the predicate of ssi_ce_fwd_weighted: the same inputs take the same form there and here
-    const bool row_form = dtype == SSI_BF16 && ((uintptr_t)logits & 15) == 0 && ld - vocab < 8192 && ld * 2 < (1LL << 31) &&
-                          (chunks <= 4 || chunks == 8 || (chunks >= 16 && chunks <= 18));
-    if (row_form) {
-        const dim3 grid((unsigned)(rows < ce_num_cus() ? rows : ce_num_cus()));
-#define SSI_CE_ROW_Z(N)                                                                                                                       \
-    case N:                                                                                                                                   \
-        if (write_grad) hipLaunchKernelGGL((ce_row_bf16_z_kernel<N, true>), grid, dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits, ld, labels, \
-                                           rows, vocab, ignore_index, two_z, row_loss, row_lse, row_z, row_weight);                           \
-        else hipLaunchKernelGGL((ce_row_bf16_z_kernel<N, false>), grid, dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits, ld, labels, rows,    \
-                                vocab, ignore_index, two_z, row_loss, row_lse, row_z, row_weight);                                            \
-        break
-        switch ((int)chunks) {
-            SSI_CE_ROW_Z(1); SSI_CE_ROW_Z(2); SSI_CE_ROW_Z(3); SSI_CE_ROW_Z(4); SSI_CE_ROW_Z(8); SSI_CE_ROW_Z(16); SSI_CE_ROW_Z(17); SSI_CE_ROW_Z(18);
-        }
-#undef SSI_CE_ROW_Z
+    if (ce_row_form(dtype, logits, ld, vocab)) {
+        SSI_CE_DISPATCH_CHUNKS(ld,
+            if (write_grad) hipLaunchKernelGGL((ce_row_bf16_z_kernel<N, true>), ce_row_grid(rows), dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits,
+                                               ld, labels, rows, vocab, ignore_index, two_z, row_loss, row_lse, row_z, row_weight);
+            else hipLaunchKernelGGL((ce_row_bf16_z_kernel<N, false>), ce_row_grid(rows), dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits, ld,
+                                    labels, rows, vocab, ignore_index, two_z, row_loss, row_lse, row_z, row_weight));
         SSI_LAUNCH_CHECK();
         return SSI_OK;
     }
@@ -658,26 +602,8 @@ extern "C" int ssi_ce_fwd_z(void* logits, int64_t ld, const int64_t* labels, con
 }
 
 // =====================================================================================================================
-// K9m forward-only cross-entropy that also ranks the label (ssi_ce_fwd_metrics): the dev set's per-token-type loss, top-1 and top-k.
-//   rank[r] = #{c < vocab : x[c] > x[label]} + #{c < label : x[c] == x[label]}  — the label's position in a stable descending sort of
-//   the row; rank == 0 <=> argmax(row) == label under the first-occurrence rule.  Compares on the stored values: an exact integer.
-// Kernels of their own (not a template parameter of the two above): the instantiations the training step launches stay what they were.
-// The max, the exp-sum and the lse are the statements of those kernels in their order: row_loss and row_lse agree bit for bit.
+// K9m the kernels of ssi_ce_fwd_metrics (see K9), and the reductions over the rows they wrote
 // =====================================================================================================================
-// block-wide integer sum for blockDim.x <= 1024; `red` is >= 16 ints of LDS; result broadcast to all threads
-__device__ __forceinline__ int block_sum_i32(int v, int* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
-    __syncthreads();
-    if (l == 0) red[w] = v;
-    __syncthreads();
-    int t = (l < nw) ? red[l] : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-    return t;
-}
-
 template <typename T>
 __global__ __launch_bounds__(512) void ce_fwd_metrics_kernel(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
                                                              int64_t vocab, int64_t ignore_index, float* __restrict__ row_loss,
@@ -689,26 +615,12 @@ __global__ __launch_bounds__(512) void ce_fwd_metrics_kernel(const T* __restrict
     const int64_t row = blockIdx.x;
     const T* lr = logits + row * ld;
     const int64_t label = labels[row];
-    const bool valid = label != ignore_index && label >= 0 && label < vocab;
     const int64_t nvec = ld / N;
-    if (!valid) {  // block-uniform
+    if (!ce_label_valid(label, vocab, ignore_index)) {  // block-uniform
         if (threadIdx.x == 0) { row_loss[row] = 0.f; if (row_lse) row_lse[row] = 0.f; row_nll[row] = 0.f; row_rank[row] = -1; }
         return;
     }
-    float m = -INFINITY, s = 0.f;
-    for (int64_t v = threadIdx.x; v < nvec; v += 512) {
-        Vec16<T> a = load16(lr + v * N);
-        float lm = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < N; ++i) if (v * N + i < vocab) lm = fmaxf(lm, a.get(i));
-        if (lm > m) { s *= expf(m - lm); m = lm; }
-#pragma unroll
-        for (int i = 0; i < N; ++i) if (v * N + i < vocab) s += expf(a.get(i) - m);
-    }
-    const float gm = block_max(m, red);
-    s = (m == -INFINITY) ? 0.f : s * expf(m - gm);
-    const float gs = block_sum(s, red);
-    const float lse = gm + logf(gs);
+    const float lse = ce_row_lse(lr, nvec, vocab, red);
     const float w = row_weight ? row_weight[row] : 1.f;
     const float xl = to_f32<T>(lr[label]);  // block-uniform address; the logits are read-only here
     // second pass over the row (from L2, as the gradient pass of ce_fwd_kernel): pad columns [vocab, ld) never count
@@ -731,10 +643,6 @@ __global__ __launch_bounds__(512) void ce_fwd_metrics_kernel(const T* __restrict
     }
 }
 
-// The register-resident row form of ce_row_bf16_kernel<NCH, false> (same launch shape, same walk over the rows, the next row's loads where
-// they are there) with one more pass over the packed registers: compare with the label's logit and count.  Every lane needs that logit
-// before the pass; the label is workgroup-uniform and nothing is overwritten here, so each lane loads it itself from one address.  The pad
-// columns are -inf in the registers and lie above every valid label: they are neither greater than a logit nor tie below the label.
 template <int NCH>
 __global__ __launch_bounds__(1024, 4) void ce_row_bf16_metrics_kernel(const bf16_t* __restrict__ logits, int64_t ld,
                                                                       const int64_t* __restrict__ labels, int64_t rows, int64_t vocab,
@@ -743,100 +651,8 @@ __global__ __launch_bounds__(1024, 4) void ce_row_bf16_metrics_kernel(const bf16
                                                                       int32_t* __restrict__ row_rank, const float* __restrict__ row_weight) {
     __shared__ float red[16];
     __shared__ int redi[16];
-    constexpr float LOG2E = 1.44269504088896340736f;
-    constexpr int CHUNK = 8192;
-    const int tid = threadIdx.x;
-    const int voff = tid * 16;
-    const int col0 = tid * 8;
-    const int row_bytes = (int)(ld * 2);
-    const int vocab_i = (int)vocab;
-    u32x4 x[NCH];
-    auto is_valid = [&](int64_t label) { return label != ignore_index && label >= 0 && label < vocab; };
-    auto rsrc_of = [&](int64_t row) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(logits) + row * ld, 0, row_bytes, 0x00020000u); };
-    auto lo = [](unsigned u) { return __builtin_bit_cast(float, u << 16); };
-    auto hi = [](unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); };
-    auto opaque = [&]() {  // as in ce_row_bf16_kernel: each pass re-derives its floats from the packed registers
-#pragma unroll
-        for (int c = 0; c < NCH; ++c)
-#pragma unroll
-            for (int d = 0; d < 4; ++d) asm volatile("" : "+v"(x[c][d]));
-    };
-    int64_t row = blockIdx.x;
-    if (row >= rows) return;
-    {
-        const __amdgpu_buffer_rsrc_t r0 = rsrc_of(row);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) x[c] = __builtin_amdgcn_raw_buffer_load_b128(r0, voff, c * CHUNK * 2, 0);
-    }
-    for (; row < rows; row += gridDim.x) {
-        const int64_t next = row + gridDim.x;
-        const int64_t label = labels[row];
-        const bool valid = is_valid(label);
-        const float w = row_weight ? row_weight[row] : 1.f;
-#pragma unroll
-        for (int c = (NCH >= 2 ? NCH - 2 : 0); c < NCH; ++c) {
-            const int left = vocab_i - c * CHUNK - col0;
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-                if (2 * d >= left) x[c][d] = (x[c][d] & 0xffff0000u) | 0x0000ff80u;
-                if (2 * d + 1 >= left) x[c][d] = (x[c][d] & 0x0000ffffu) | 0xff800000u;
-            }
-        }
-        if (valid) {  // workgroup-uniform; reads the row registers only
-            const float xl = (float)logits[row * ld + label];
-            float m = -INFINITY;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c)
-#pragma unroll
-                for (int d = 0; d < 4; ++d) m = fmaxf(m, fmaxf(lo(x[c][d]), hi(x[c][d])));
-            const float gm = block_max(m, red);
-            opaque();
-            const float nm = -gm * LOG2E;
-            float s = 0.f;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c)
-#pragma unroll
-                for (int d = 0; d < 4; ++d)
-                    s += __builtin_amdgcn_exp2f(fmaf(lo(x[c][d]), LOG2E, nm)) + __builtin_amdgcn_exp2f(fmaf(hi(x[c][d]), LOG2E, nm));
-            const float gs = block_sum(s, red);
-            const float lse = gm + logf(gs);
-            opaque();
-            // ---- the rank pass: element e of chunk c is column c * CHUNK + col0 + e; it ties BELOW the label iff e < below - c * CHUNK
-            const int below = (int)label - col0;
-            int cnt = 0;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                const int b = below - c * CHUNK;
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    const float a0 = lo(x[c][d]), a1 = hi(x[c][d]);
-                    // bitwise on purpose: || and && became a branch per element, and the row spilled
-                    cnt += (int)(a0 > xl) | ((int)(a0 == xl) & (int)(2 * d < b));
-                    cnt += (int)(a1 > xl) | ((int)(a1 == xl) & (int)(2 * d + 1 < b));
-                }
-            }
-            cnt = block_sum_i32(cnt, redi);
-            if (tid == 0) {
-                row_loss[row] = w * (lse - xl);
-                if (row_lse) row_lse[row] = lse;
-                row_nll[row] = lse - xl;
-                row_rank[row] = cnt;
-            }
-        } else if (tid == 0) {
-            row_loss[row] = 0.f;
-            if (row_lse) row_lse[row] = 0.f;
-            row_nll[row] = 0.f;
-            row_rank[row] = -1;
-        }
-        opaque();
-        // each register takes the next row's chunk (past the last row: this row again), one chunk at a time as in ce_row_bf16_kernel
-        const __amdgpu_buffer_rsrc_t rn = rsrc_of(next < rows ? next : row);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            x[c] = __builtin_amdgcn_raw_buffer_load_b128(rn, voff, c * CHUNK * 2, 2 /* nt */);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
+    ce_row_bf16_body<NCH, CE_METRICS, false>(const_cast<bf16_t*>(logits), ld, labels, rows, vocab, ignore_index, 0.f, row_loss, row_lse, nullptr,
+                                             row_nll, row_rank, row_weight, red, redi);
 }
 
 extern "C" int ssi_ce_fwd_metrics(const void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
@@ -844,22 +660,10 @@ extern "C" int ssi_ce_fwd_metrics(const void* logits, int64_t ld, const int64_t*
                                   void* stream) {
     SSI_CHECK_ARG(logits && labels && row_loss && row_nll && row_rank && rows >= 0 && vocab > 0 && ld >= vocab && ld % 8 == 0);
     if (rows == 0) return SSI_OK;
-    const int64_t chunks = ssi_cdiv(ld, 8192);
-    // the predicate of ssi_ce_fwd_weighted: the same inputs take the same form there and here
-    const bool row_form = dtype == SSI_BF16 && ((uintptr_t)logits & 15) == 0 && ld - vocab < 8192 && ld * 2 < (1LL << 31) &&
-                          (chunks <= 4 || chunks == 8 || (chunks >= 16 && chunks <= 18));
-    if (row_form) {
-        const dim3 grid((unsigned)(rows < ce_num_cus() ? rows : ce_num_cus()));
-#define SSI_CE_ROW_METRICS(N)                                                                                                          \
-    case N:                                                                                                                            \
-        hipLaunchKernelGGL((ce_row_bf16_metrics_kernel<N>), grid, dim3(1024), 0, (hipStream_t)stream, (const bf16_t*)logits, ld, labels, \
-                           rows, vocab, ignore_index, row_loss, row_lse, row_nll, row_rank, row_weight);                               \
-        break
-        switch ((int)chunks) {
-            SSI_CE_ROW_METRICS(1); SSI_CE_ROW_METRICS(2); SSI_CE_ROW_METRICS(3); SSI_CE_ROW_METRICS(4); SSI_CE_ROW_METRICS(8);
-            SSI_CE_ROW_METRICS(16); SSI_CE_ROW_METRICS(17); SSI_CE_ROW_METRICS(18);
-        }
-#undef SSI_CE_ROW_METRICS
+    if (ce_row_form(dtype, logits, ld, vocab)) {
+        SSI_CE_DISPATCH_CHUNKS(ld, hipLaunchKernelGGL((ce_row_bf16_metrics_kernel<N>), ce_row_grid(rows), dim3(1024), 0, (hipStream_t)stream,
+                                                      (const bf16_t*)logits, ld, labels, rows, vocab, ignore_index, row_loss, row_lse, row_nll,
+                                                      row_rank, row_weight));
         SSI_LAUNCH_CHECK();
         return SSI_OK;
     }
@@ -870,9 +674,17 @@ extern "C" int ssi_ce_fwd_metrics(const void* logits, int64_t ld, const int64_t*
     return SSI_OK;
 }
 
+// The two reductions below sum the same four numbers over ranked rows (rank >= 0: the rows ssi_ce_fwd_metrics gave a valid label), in fp64;
+// the counts ride as doubles (exact below 2^53).
+__device__ __forceinline__ void ce_metrics_add(double (&acc)[4], int rank, float nll, int topk) {
+    acc[0] += 1.0;
+    acc[1] += (double)nll;
+    acc[2] += rank == 0 ? 1.0 : 0.0;
+    acc[3] += rank < topk ? 1.0 : 0.0;
+}
+
 // Per-type sums of the rows ssi_ce_fwd_metrics wrote.  One workgroup; output row j (a range, or j == n_ranges: every valid label) is one
 // walk over the rows in thread-strided order and one fixed tree over the lanes and the 16 waves, in fp64: bitwise reproducible, no atomics.
-// The counts ride the same tree as doubles (exact below 2^53).
 #define SSI_CE_MAX_RANGES 8  // as ssi_count_tokens
 __global__ __launch_bounds__(1024) void ce_metrics_reduce_kernel(const float* __restrict__ row_nll, const int32_t* __restrict__ row_rank,
                                                                  const int64_t* __restrict__ labels, int64_t rows,
@@ -887,17 +699,10 @@ __global__ __launch_bounds__(1024) void ce_metrics_reduce_kernel(const float* __
         for (int64_t r = threadIdx.x; r < rows; r += 1024) {
             const int rank = row_rank[r];
             const int64_t l = labels[r];
-            if (rank >= 0 && (all || (l >= lo && l <= hi))) {
-                acc[0] += 1.0;
-                acc[1] += (double)row_nll[r];
-                acc[2] += rank == 0 ? 1.0 : 0.0;
-                acc[3] += rank < topk ? 1.0 : 0.0;
-            }
+            if (rank >= 0 && (all || (l >= lo && l <= hi))) ce_metrics_add(acc, rank, row_nll[r], topk);
         }
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_xor(acc[q], o, 64);
+        for (int q = 0; q < 4; ++q) acc[q] = wave_sum_f64(acc[q]);
         __syncthreads();  // the previous j's read of red is over
         if (ln == 0) {
 #pragma unroll
@@ -926,7 +731,7 @@ extern "C" int ssi_ce_metrics_reduce(const float* row_nll, const int32_t* row_ra
 // Per-sequence sums of the rows ssi_ce_fwd_metrics wrote (ssi_seq_score_reduce): sequence i is the flat positions [seq_start[i], seq_end[i]),
 // clamped to [0, rows].  One wave per sequence, four per workgroup: the lanes stride over consecutive positions, each lane sums in fp64 in
 // position order, then one fixed xor tree over the 64 lanes.  No atomics, no LDS: a sequence's four numbers depend on its own positions
-// only — not on n_seq, not on which wave or workgroup took it.  The counts ride the tree as doubles (exact below 2^53).
+// only — not on n_seq, not on which wave or workgroup took it.
 __global__ __launch_bounds__(256) void seq_score_reduce_kernel(const float* __restrict__ row_nll, const int32_t* __restrict__ row_rank,
                                                                int64_t rows, const int64_t* __restrict__ seq_start,
                                                                const int64_t* __restrict__ seq_end, int64_t n_seq, int topk,
@@ -940,17 +745,10 @@ __global__ __launch_bounds__(256) void seq_score_reduce_kernel(const float* __re
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     for (int64_t r = start + ln; r < end; r += 64) {
         const int rank = row_rank[r];
-        if (rank >= 0) {
-            acc[0] += 1.0;
-            acc[1] += (double)row_nll[r];
-            acc[2] += rank == 0 ? 1.0 : 0.0;
-            acc[3] += rank < topk ? 1.0 : 0.0;
-        }
+        if (rank >= 0) ce_metrics_add(acc, rank, row_nll[r], topk);
     }
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_xor(acc[q], o, 64);
+    for (int q = 0; q < 4; ++q) acc[q] = wave_sum_f64(acc[q]);
     if (ln == 0) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) out[4 * seq + q] = acc[q];

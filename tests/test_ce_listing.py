@@ -1,6 +1,7 @@
-"""CPU, on the BUILT library: the z-loss cross-entropy kernels (``ssi_ce_fwd_z``) are there once for every form its dispatch can launch — the
-register-resident rows for every chunk count of the switch, with and without the gradient, and the generic kernel in both dtypes — none of
-them uses scratch (a spilled row is the one way the register-resident kernel silently loses its point), and nothing else is instantiated.
+"""CPU, on the BUILT library: the cross-entropy kernels of the three entries (``ssi_ce_fwd_weighted``, ``ssi_ce_fwd_z``, ``ssi_ce_fwd_metrics``)
+are there once for every form their dispatch can launch — the register-resident rows for every chunk count of the one switch they share,
+the plain and the z form with and without the gradient, and the generic kernels in both dtypes — none of them uses scratch (a spilled row
+is the one way the register-resident kernel silently loses its point: it would still be correct), and nothing else is instantiated.
 From the report of ``tools/kernel_lint.py``; no instruction is inspected here."""
 import os
 import sys
@@ -14,7 +15,7 @@ LLVM = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 pytestmark = pytest.mark.skipif(not (os.path.exists(LIB) and os.path.exists(LLVM)), reason="needs the built library and llvm-objdump")
 
-ROW_CHUNKS = (1, 2, 3, 4, 8, 16, 17, 18)   # the switch of ssi_ce_fwd_z (that of ssi_ce_fwd_weighted)
+ROW_CHUNKS = (1, 2, 3, 4, 8, 16, 17, 18)   # SSI_CE_DISPATCH_CHUNKS, the switch of the three entries
 
 
 @pytest.fixture(scope="module")
@@ -37,9 +38,21 @@ def test_every_dispatched_z_kernel_is_in_the_library_once_without_scratch(report
     assert not [e for e in errs if "z_kernel" in e], errs
 
 
+def test_every_dispatched_metrics_kernel_is_in_the_library_without_scratch(report):
+    errs, rep = report
+    wanted = [f"ce_row_bf16_metrics_kernelILi{n}EE" for n in ROW_CHUNKS] + ["ce_fwd_metrics_kernelIfE", "ce_fwd_metrics_kernelIDF16bE",
+                                                                           "ce_metrics_reduce_kernel"]
+    for must in wanted:
+        hit = [n for n in rep if must in n]
+        assert len(hit) == 1, f"{must}: {hit}"
+        assert rep[hit[0]]["scratch"] == 0, (hit[0], rep[hit[0]])
+    assert len([n for n in rep if "ce_row_bf16_metrics_kernel" in n]) == len(ROW_CHUNKS)   # nothing instantiated that is never launched
+    assert not [e for e in errs if "metrics_kernel" in e], errs                              # (they are on the lint's no-scratch list too)
+
+
 def test_the_plain_and_the_metrics_kernels_are_the_ones_of_before(report):
-    """The z forms are kernels of their own: the counts the other cross-entropy listings rely on are unchanged, and none of those kernels
-    has scratch either."""
+    """The z and the metrics forms are kernels of their own: the counts of the plain kernels are what they were without them, and none of
+    the cross-entropy kernels has scratch."""
     _, rep = report
     assert len([n for n in rep if "ce_row_bf16_kernel" in n]) == 2 * len(ROW_CHUNKS)
     assert len([n for n in rep if "ce_row_bf16_metrics_kernel" in n]) == len(ROW_CHUNKS)

@@ -1,10 +1,12 @@
 """Cross-entropy kernel alone at the step's shape: T = 16384 rows, V = 133258 (ld 133376), bf16, gradient in place.
-``--z COEFF``: the z-loss form (``ops.ce_fwd_z``, ``ssi_ce_fwd_z``) with that coefficient instead of ``ops.ce_fwd``."""
+``--z COEFF``: the z-loss form (``ops.ce_fwd_z``, ``ssi_ce_fwd_z``) with that coefficient instead of ``ops.ce_fwd``.
+``--metrics``: the label-rank form (``ops.ce_fwd_metrics``, ``ssi_ce_fwd_metrics``; forward only: one pass over the logits)."""
 import argparse, sys, torch
 sys.path.insert(0, 'speech-integration_amd')
 from ssi import ops
 ap = argparse.ArgumentParser()
 ap.add_argument("--z", type=float, default=None, metavar="COEFF", help="time ce_fwd_z with this coefficient (default: ce_fwd)")
+ap.add_argument("--metrics", action="store_true", help="time ce_fwd_metrics")
 ap.add_argument("--reps", type=int, default=10)
 args = ap.parse_args()
 T, V, LD = 16384, 133258, 133376
@@ -12,9 +14,12 @@ logits = (torch.randn(T, LD, device='cuda') * 2).bfloat16()
 labels = torch.randint(0, V, (T,), device='cuda')
 labels[::7] = -100
 row_loss = torch.empty(T, device='cuda'); row_lse = torch.empty(T, device='cuda'); row_z = torch.empty(T, device='cuda')
+row_nll = torch.empty(T, device='cuda'); row_rank = torch.empty(T, device='cuda', dtype=torch.int32)
 work = logits.clone()
 def run():
-    if args.z is None:
+    if args.metrics:
+        ops.ce_fwd_metrics(work, labels, V, -100, row_loss, row_lse, row_nll, row_rank)
+    elif args.z is None:
         ops.ce_fwd(work, labels, V, -100, row_loss, row_lse, write_grad=True)
     else:
         ops.ce_fwd_z(work, labels, V, -100, args.z, row_loss, row_lse, row_z, write_grad=True)
@@ -28,6 +33,6 @@ for _ in range(args.reps):
     s.record(); run(); e.record(); torch.cuda.synchronize()
     ms.append(s.elapsed_time(e))
 mean = sum(ms) / len(ms)
-name = "ce_fwd" if args.z is None else f"ce_fwd_z({args.z:g})"
+name = "ce_fwd_metrics" if args.metrics else "ce_fwd" if args.z is None else f"ce_fwd_z({args.z:g})"
 print(f"{name} {mean:.3f} ms  (min {min(ms):.3f}, max {max(ms):.3f} of {len(ms)}; {3 * T * LD * 2 / mean / 1e9:.2f} TB/s at 3 passes, "
-      f"{2 * T * LD * 2 / mean / 1e9:.2f} at 2)  loss {float(row_loss.sum()):.4f}" + ("" if args.z is None else f"  z {float(row_z.sum()):.4f}"))
+      f"{2 * T * LD * 2 / mean / 1e9:.2f} at 2)  loss {float(row_loss.sum()):.4f}" + ("" if args.z is None or args.metrics else f"  z {float(row_z.sum()):.4f}") + (f"  top-1 {int((row_rank == 0).sum())}" if args.metrics else ""))
