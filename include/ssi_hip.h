@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 13 /* 13: + ssi_seq_score_reduce (per-sequence sums of what ssi_ce_fwd_metrics wrote: likelihood scoring of packed rows)
+#define SSI_ABI_VERSION 14 /* 14: + ssi_ce_fwd_smooth (label smoothing inside the cross-entropy kernels, beside the z-loss; opt-in)
+                           * 13: + ssi_seq_score_reduce (per-sequence sums of what ssi_ce_fwd_metrics wrote: likelihood scoring of packed rows)
                            * 12: + ssi_ce_fwd_z (cross-entropy with the auxiliary z-loss z * log^2 Z in its gradient; opt-in)
                            * 11: + ssi_adamw_step_sr, ssi_round_bf16_sr (bf16 AdamW whose three stores round stochastically, counter-based)
                            * 10: + ssi_ce_fwd_metrics, ssi_ce_metrics_reduce (dev-set loss and top-k accuracy per token type)
@@ -279,6 +280,23 @@ int ssi_ce_fwd_weighted(void* logits, int64_t ld, const int64_t* labels, const f
  * like the weight, and the sign is one XOR per packed register — one store per row and four integer operations per 8 columns more. */
 int ssi_ce_fwd_z(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab, int64_t ignore_index,
                  float z_coeff, float* row_loss, float* row_lse, float* row_z, int write_grad, int dtype, void* stream);
+/* ssi_ce_fwd_z with label smoothing (ABI v14; not in the reference, off by default: the trainer's label_smoothing): the target distribution is
+ * (1 - e) onehot(label) + e / vocab, e = smoothing.  With lse, p, w as above, f = 1 + 2 z_coeff lse, and sx = the fp32 sum of logit[c] over
+ * c < vocab in a fixed order, for a row with a valid label:
+ *   row_loss[r], row_lse[r]  what ssi_ce_fwd_weighted writes, bit for bit (row_lse NULL ok);
+ *   row_z[r]    = w (lse lse)                     what ssi_ce_fwd_z writes; may be NULL only when z_coeff == 0;
+ *   row_u[r]    = w (lse - sx / (float)vocab)     the uniform part, WITHOUT the coefficient (required);
+ *   gradient    = w (f p[c] - (1 - e) [c == label]) - wu  on the real columns, wu = w * (smoothing / (float)vocab) and 1 - e = 1.f - smoothing
+ *                 in fp32 in this order (a column whose p underflows holds exactly the rounding of -wu); pad columns stay 0.
+ * A row whose label is ignored or outside [0, vocab): row_loss = row_u = row_z = 0 and a zero gradient row.  The batch objective is
+ * ((1 - e) sum row_loss + e sum row_u + z_coeff sum row_z) / n_valid, the loss of torch's cross_entropy(label_smoothing = e) plus the z part: one
+ * ssi_ce_reduce per sum.  smoothing must be finite and in [0, 1), z_coeff finite and >= 0 (SSI_ERR_ARG otherwise).  smoothing == 0 gives the
+ * buffer, row_loss, row_lse and row_z of ssi_ce_fwd_z(z_coeff) bit for bit (minus an exact 0, times an exact 1: no branch), and with
+ * z_coeff == 0 as well the buffer of ssi_ce_fwd_weighted.  In the register-resident bf16 kernel: one plain sum over the row registers beside
+ * the exp-sum, one more block reduction per row, and one subtract per column. */
+int ssi_ce_fwd_smooth(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
+                      int64_t ignore_index, float smoothing, float z_coeff, float* row_loss, float* row_lse, float* row_u, float* row_z,
+                      int write_grad, int dtype, void* stream);
 /* Forward-only ssi_ce_fwd_weighted that also ranks the label (ABI v10; the dev set's loss and accuracy per token type, ssi/eval.py).  The logits
  * are read only.  row_loss and row_lse (NULL ok) are what ssi_ce_fwd_weighted(..., write_grad = 0) writes on the same inputs, bit for bit: the
  * same form (register-resident bf16 rows or the generic kernel) is chosen by the same predicate, with the same order of max, exp-sum and lse.

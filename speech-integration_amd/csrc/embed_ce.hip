@@ -185,11 +185,14 @@ extern "C" int ssi_embed_bwd(const int64_t* tokens, const void* dout, void* dtab
 }
 
 // =====================================================================================================================
-// K9 cross-entropy over rows of [rows, ld] logits, three entries:
+// K9 cross-entropy over rows of [rows, ld] logits, four entries:
 //   ssi_ce_fwd(_weighted)  row_loss = w (lse - x[label]), row_lse; optional in-place gradient  w (softmax - onehot)
 //   ssi_ce_fwd_z           + the auxiliary z-loss z * log^2 Z (opt-in, z_loss_coeff of the trainer).  With lse = log Z and p = softmax:
 //                          row_z = w (lse lse)  (the coefficient is applied by the caller)
 //                          grad[c] = w (f p[c] - [c == label]),  f = 1 + 2 z lse      (d/dx of lse - x[label] + z lse^2: d lse / dx = p)
+//   ssi_ce_fwd_smooth      ssi_ce_fwd_z + label smoothing e (opt-in, label_smoothing of the trainer): the target is (1 - e) onehot + e / vocab.
+//                          row_u = w (lse - mean_c x[c])  (the uniform part; the caller forms (1 - e) row_loss + e row_u)
+//                          grad[c] = w (f p[c] - (1 - e) [c == label]) - w (e / vocab)
 //   ssi_ce_fwd_metrics     forward only, + row_nll = lse - x[label] and the label's rank (the dev set's per-token-type loss, top-1, top-k):
 //                          rank[r] = #{c < vocab : x[c] > x[label]} + #{c < label : x[c] == x[label]}  — the label's position in a stable
 //                          descending sort of the row; rank == 0 <=> argmax(row) == label under the first-occurrence rule.  Compares on
@@ -197,9 +200,9 @@ extern "C" int ssi_embed_bwd(const int64_t* tokens, const void* dout, void* dtab
 // Each entry has kernels of its own in two forms — generic (any dtype and shape; one 512-thread block per row, fp32 online log-sum-exp,
 // the gradient or the rank from a second read of the row out of L2 / Infinity Cache) and register-resident bf16 rows (the training step's
 // form) — so the instantiations an entry launches do not depend on what the other entries need.  Kernels of their own, ONE body: the
-// generic kernels are built from the pieces below and the three row kernels wrap ce_row_bf16_body, so the max, the exp-sum and the lse
-// are the same statements whatever the entry: row_loss and row_lse agree bit for bit across the three, and with z = 0 (f = 1 exactly) so
-// does the gradient.
+// generic kernels are built from the pieces below and the four row kernels wrap ce_row_bf16_body, so the max, the exp-sum and the lse
+// are the same statements whatever the entry: row_loss and row_lse agree bit for bit across the four, and with z = 0 (f = 1 exactly) and
+// e = 0 (times an exact 1, minus an exact 0) so does the gradient.
 // =====================================================================================================================
 // a row takes part iff its label is not ignored AND inside [0, vocab)
 __device__ __forceinline__ bool ce_label_valid(int64_t label, int64_t vocab, int64_t ignore_index) {
@@ -255,6 +258,41 @@ __device__ __forceinline__ void ce_grad_row(T* lr, int64_t nvec, int64_t vocab, 
     }
 }
 
+// plain fp32 sum over the columns [0, vocab) of one row, in a fixed order (per-thread stride, then the block's tree)
+template <typename T> __device__ __forceinline__ float ce_row_sum(const T* lr, int64_t nvec, int64_t vocab, float* red) {
+    constexpr int N = Vec16<T>::N;
+    float s = 0.f;
+    for (int64_t v = threadIdx.x; v < nvec; v += 512) {
+        Vec16<T> a = load16(lr + v * N);
+#pragma unroll
+        for (int i = 0; i < N; ++i) if (v * N + i < vocab) s += a.get(i);
+    }
+    return block_sum(s, red);
+}
+
+// ce_grad_row<true> with label smoothing: w (f p - ome onehot) - wu on the real columns, ome = 1 - e and wu = w (e / vocab); pad columns 0.
+// e = 0: ome = 1 and wu = 0 exactly — the values of ce_grad_row<true>
+template <typename T>
+__device__ __forceinline__ void ce_grad_row_smooth(T* lr, int64_t nvec, int64_t vocab, int64_t label, float lse, float w, float f, float ome,
+                                                   float wu) {
+    constexpr int N = Vec16<T>::N;
+    for (int64_t v = threadIdx.x; v < nvec; v += 512) {
+        Vec16<T> a = load16(lr + v * N), o;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const int64_t c = v * N + i;
+            float g = 0.f;
+            if (c < vocab) {
+                float wt = w * (f * expf(a.get(i) - lse) - (c == label ? ome : 0.f));
+                asm volatile("" : "+v"(wt));  // no fma across here: the product is rounded before wu leaves it, as in the register form
+                g = wt - wu;
+            }
+            o.set(i, g);
+        }
+        store16(lr + v * N, o);
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(512) void ce_fwd_kernel(T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
                                                      int64_t vocab, int64_t ignore_index, float* __restrict__ row_loss,
@@ -288,25 +326,34 @@ __global__ __launch_bounds__(512) void ce_fwd_kernel(T* __restrict__ logits, int
 // and ld - vocab < 8192: only the last two chunks can hold columns that are not vocabulary.  Straight-line body (the only branches are
 // workgroup-uniform and read-only on the row registers): with per-chunk branches hipcc spills the row.
 //
-// The body of all three row kernels; what an entry adds sits behind `if constexpr` on MODE, and the kernels pass nullptr / 0 for what is
+// The body of all four row kernels; what an entry adds sits behind `if constexpr` on MODE, and the kernels pass nullptr / 0 for what is
 // not theirs:
 //   CE_Z        one scalar per row.  |f| rides in the exponent's additive term beside log2 w (f = 0: log2 0 = -inf, every exp2 gives 0 —
 //               the row is -w on the label and 0 elsewhere).  The SIGN of f is applied to the packed result: the row computes
 //               w |f| p - sign(f) w [c == label]  and, for f < 0, flips the sign bit of all eight bf16 of a register (4 XORs per chunk with
 //               a per-row mask that is 0 otherwise; round-to-nearest-even is symmetric in the sign, so this IS the rounding of
 //               w (f p - onehot)).  No branch per chunk.  (For f < 0 the columns whose gradient is 0 — pads, underflows — hold -0.)
+//   CE_SMOOTH   CE_Z and two more scalars per row (every CE_Z statement runs; z = 0 makes them the exact no-ops they already are).  The
+//               label column subtracts wl = sign(f) w (1 - e) and every REAL column sign(f) wu, wu = w (e / vocab), both before the
+//               sign flip: the row computes  w |f| p - wl [c == label] - sign(f) wu.  Only the last two chunks can hold columns that are
+//               not vocabulary; there the constant is selected per element with the `left` compare of the masking loop (a v_cndmask, no
+//               branch), elsewhere it is subtracted unconditionally.  The same select keeps the -inf of the pads out of the plain sum of
+//               the row (row_u), one more pass over the packed registers.  e = 0: minus an exact 0, times an exact 1 — CE_Z bit for bit.
 //   CE_METRICS  no gradient (write_grad is false) and one more pass over the packed registers: compare with the label's logit and count.
 //               Every lane needs that logit before the pass; the label is workgroup-uniform and nothing is overwritten here, so each
 //               lane loads it itself from one address and nothing has to wait for it to land.  The pad columns are -inf in the
 //               registers and lie above every valid label: they are neither greater than a logit nor tie below the label.
-enum CeMode { CE_PLAIN, CE_Z, CE_METRICS };
+enum CeMode { CE_PLAIN, CE_Z, CE_SMOOTH, CE_METRICS };
 
 template <int NCH, CeMode MODE, bool write_grad>
 __device__ __forceinline__ void ce_row_bf16_body(bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels, int64_t rows,
-                                                 int64_t vocab, int64_t ignore_index, float two_z, float* __restrict__ row_loss,
-                                                 float* __restrict__ row_lse, float* __restrict__ row_z, float* __restrict__ row_nll,
-                                                 int32_t* __restrict__ row_rank, const float* __restrict__ row_weight, float* red, int* redi) {
+                                                 int64_t vocab, int64_t ignore_index, float two_z, float ome, float e_over_v,
+                                                 float* __restrict__ row_loss, float* __restrict__ row_lse, float* __restrict__ row_z,
+                                                 float* __restrict__ row_u, float* __restrict__ row_nll, int32_t* __restrict__ row_rank,
+                                                 const float* __restrict__ row_weight, float* red, int* redi) {
     static_assert(MODE != CE_METRICS || !write_grad, "the metrics form writes no gradient");
+    constexpr bool WITH_F = MODE == CE_Z || MODE == CE_SMOOTH;  // the z-loss factor f and its sign flip
+    constexpr bool SMOOTH = MODE == CE_SMOOTH;                  // ome = 1 - e, e_over_v = e / vocab (0 and unused otherwise)
     constexpr float LOG2E = 1.44269504088896340736f;
     constexpr int CHUNK = 8192;                      // columns per chunk: 1024 threads x 8 bf16
     const int tid = threadIdx.x;
@@ -354,8 +401,9 @@ __device__ __forceinline__ void ce_row_bf16_body(bf16_t* __restrict__ logits, in
             }
         }
         float nl = -INFINITY;  // ignored / out-of-range label: every exp2 below gives 0 -> zero gradient row
-        float wl = w;          // what the label column subtracts BEFORE the sign flip: sign(f) w  (CE_Z; w otherwise)
-        unsigned flip = 0u;    // sign bits of the two bf16 of a packed dword, set iff f < 0  (CE_Z)
+        float wl = w;          // what the label column subtracts BEFORE the sign flip: sign(f) w  (CE_Z; w otherwise), times 1 - e (CE_SMOOTH)
+        float wus = 0.f;       // what every real column subtracts BEFORE the sign flip: sign(f) w (e / vocab)  (CE_SMOOTH; 0 on a row without a label)
+        unsigned flip = 0u;    // sign bits of the two bf16 of a packed dword, set iff f < 0  (CE_Z, CE_SMOOTH)
         if (valid) {           // workgroup-uniform; reads the row registers only
             float xl = 0.f;    // before this row's gradient is written (program order of one thread)
             if (MODE == CE_METRICS || tid == 0) xl = (float)logits[row * ld + label];
@@ -378,6 +426,23 @@ __device__ __forceinline__ void ce_row_bf16_body(bf16_t* __restrict__ logits, in
                     s += __builtin_amdgcn_exp2f(fmaf(lo(x[c][d]), LOG2E, nm)) + __builtin_amdgcn_exp2f(fmaf(hi(x[c][d]), LOG2E, nm));
             const float gs = block_sum(s, red);
             const float lse = gm + logf(gs);
+            float gsx = 0.f;
+            if constexpr (SMOOTH) {
+                opaque();
+                // ---- the plain sum of the real columns, a pass of its own (fused into the exp-sum pass, the row spilled): the pads are -inf
+                // in the registers, select 0 for them
+                float sx = 0.f;
+#pragma unroll
+                for (int c = 0; c < NCH; ++c) {
+                    const int left = vocab_i - c * CHUNK - col0;  // as in the masking loop; read in the last two chunks only
+#pragma unroll
+                    for (int d = 0; d < 4; ++d) {
+                        if (c < NCH - 2) sx += lo(x[c][d]) + hi(x[c][d]);
+                        else sx += (2 * d < left ? lo(x[c][d]) : 0.f) + (2 * d + 1 < left ? hi(x[c][d]) : 0.f);
+                    }
+                }
+                gsx = block_sum(sx, red);
+            }
             int cnt = 0;
             if constexpr (MODE == CE_METRICS) {
                 opaque();
@@ -400,18 +465,24 @@ __device__ __forceinline__ void ce_row_bf16_body(bf16_t* __restrict__ logits, in
                 row_loss[row] = w * (lse - xl);
                 if (row_lse) row_lse[row] = lse;
                 if constexpr (MODE == CE_Z) row_z[row] = w * (lse * lse);
+                if constexpr (SMOOTH) {
+                    if (row_z) row_z[row] = w * (lse * lse);
+                    row_u[row] = w * (lse - gsx / (float)vocab_i);
+                }
                 if constexpr (MODE == CE_METRICS) { row_nll[row] = lse - xl; row_rank[row] = cnt; }
             }
             nl = -lse * LOG2E + log2w;
-            if constexpr (MODE == CE_Z) {
+            if constexpr (WITH_F) {
                 const float f = fmaf(two_z, lse, 1.f);
                 nl += __log2f(fabsf(f));  // z = 0: f = 1 and this term an exact 0 — the nl of CE_PLAIN
-                if (f < 0.f) { wl = -w; flip = 0x80008000u; }
+                if constexpr (SMOOTH) { wl = w * ome; wus = w * e_over_v; }  // e = 0: w and 0, exactly
+                if (f < 0.f) { wl = -wl; wus = -wus; flip = 0x80008000u; }
             }
         } else if (tid == 0) {
             row_loss[row] = 0.f;
             if (row_lse) row_lse[row] = 0.f;
             if constexpr (MODE == CE_Z) row_z[row] = 0.f;
+            if constexpr (SMOOTH) { if (row_z) row_z[row] = 0.f; row_u[row] = 0.f; }
             if constexpr (MODE == CE_METRICS) { row_nll[row] = 0.f; row_rank[row] = -1; }
         }
         opaque();
@@ -433,11 +504,16 @@ __device__ __forceinline__ void ce_row_bf16_body(bf16_t* __restrict__ logits, in
 #pragma unroll
                     for (int e = 0; e < 8; ++e) if (e == h) g[e] -= wl;
                 }
+                if constexpr (SMOOTH) {  // after the label's term: a column whose p underflowed holds the rounding of -wu
+                    const int left = vocab_i - c * CHUNK - col0;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) g[e] -= (c < NCH - 2 || e < left) ? wus : 0.f;
+                }
                 bf16x8 ob;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) ob[e] = (bf16_t)g[e];
                 u32x4 o = __builtin_bit_cast(u32x4, ob);
-                if constexpr (MODE == CE_Z) {
+                if constexpr (WITH_F) {
 #pragma unroll
                     for (int d = 0; d < 4; ++d) o[d] ^= flip;
                 }
@@ -455,8 +531,8 @@ __global__ __launch_bounds__(1024, 4) void ce_row_bf16_kernel(bf16_t* __restrict
                                                               float* __restrict__ row_loss, float* __restrict__ row_lse,
                                                               const float* __restrict__ row_weight) {
     __shared__ float red[16];
-    ce_row_bf16_body<NCH, CE_PLAIN, write_grad>(logits, ld, labels, rows, vocab, ignore_index, 0.f, row_loss, row_lse, nullptr, nullptr, nullptr,
-                                                row_weight, red, nullptr);
+    ce_row_bf16_body<NCH, CE_PLAIN, write_grad>(logits, ld, labels, rows, vocab, ignore_index, 0.f, 1.f, 0.f, row_loss, row_lse, nullptr, nullptr,
+                                                nullptr, nullptr, row_weight, red, nullptr);
 }
 
 // ---- host side: which form an input takes, and the chunk counts the row form is instantiated for --------------------------------------
@@ -572,8 +648,8 @@ __global__ __launch_bounds__(1024, 4) void ce_row_bf16_z_kernel(bf16_t* __restri
                                                                 float* __restrict__ row_loss, float* __restrict__ row_lse,
                                                                 float* __restrict__ row_z, const float* __restrict__ row_weight) {
     __shared__ float red[16];
-    ce_row_bf16_body<NCH, CE_Z, write_grad>(logits, ld, labels, rows, vocab, ignore_index, two_z, row_loss, row_lse, row_z, nullptr, nullptr,
-                                            row_weight, red, nullptr);
+    ce_row_bf16_body<NCH, CE_Z, write_grad>(logits, ld, labels, rows, vocab, ignore_index, two_z, 1.f, 0.f, row_loss, row_lse, row_z, nullptr,
+                                            nullptr, nullptr, row_weight, red, nullptr);
 }
 
 extern "C" int ssi_ce_fwd_z(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
@@ -597,6 +673,84 @@ extern "C" int ssi_ce_fwd_z(void* logits, int64_t ld, const int64_t* labels, con
     }
     SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(ce_fwd_z_kernel<T>, dim3((unsigned)rows), dim3(512), 0, (hipStream_t)stream, (T*)logits, ld,
                                                  labels, vocab, ignore_index, two_z, row_loss, row_lse, row_z, write_grad, row_weight));
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+// =====================================================================================================================
+// K9s the kernels of ssi_ce_fwd_smooth (see K9)
+// =====================================================================================================================
+template <typename T>
+__global__ __launch_bounds__(512) void ce_fwd_smooth_kernel(T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                            int64_t vocab, int64_t ignore_index, float two_z, float ome, float e_over_v,
+                                                            float* __restrict__ row_loss, float* __restrict__ row_lse,
+                                                            float* __restrict__ row_z, float* __restrict__ row_u, int write_grad,
+                                                            const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    const int64_t row = blockIdx.x;
+    T* lr = logits + row * ld;
+    const int64_t label = labels[row];
+    const int64_t nvec = ld / Vec16<T>::N;
+    if (!ce_label_valid(label, vocab, ignore_index)) {  // block-uniform
+        if (threadIdx.x == 0) { row_loss[row] = 0.f; if (row_lse) row_lse[row] = 0.f; if (row_z) row_z[row] = 0.f; row_u[row] = 0.f; }
+        if (write_grad) ce_zero_row(lr, nvec);
+        return;
+    }
+    const float lse = ce_row_lse(lr, nvec, vocab, red);
+    const float sx = ce_row_sum(lr, nvec, vocab, red);
+    const float w = row_weight ? row_weight[row] : 1.f;
+    if (threadIdx.x == 0) {
+        row_loss[row] = w * (lse - to_f32<T>(lr[label]));
+        if (row_lse) row_lse[row] = lse;
+        if (row_z) row_z[row] = w * (lse * lse);
+        row_u[row] = w * (lse - sx / (float)vocab);
+    }
+    if (!write_grad) return;
+    const float f = fmaf(two_z, lse, 1.f);
+    __syncthreads();  // lr[label] read above must precede the overwrite below
+    ce_grad_row_smooth(lr, nvec, vocab, label, lse, w, f, ome, w * e_over_v);
+}
+
+template <int NCH, bool write_grad>
+__global__ __launch_bounds__(1024, 4) void ce_row_bf16_smooth_kernel(bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                                     int64_t rows, int64_t vocab, int64_t ignore_index, float two_z, float ome,
+                                                                     float e_over_v, float* __restrict__ row_loss, float* __restrict__ row_lse,
+                                                                     float* __restrict__ row_z, float* __restrict__ row_u,
+                                                                     const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    ce_row_bf16_body<NCH, CE_SMOOTH, write_grad>(logits, ld, labels, rows, vocab, ignore_index, two_z, ome, e_over_v, row_loss, row_lse, row_z,
+                                                 row_u, nullptr, nullptr, row_weight, red, nullptr);
+}
+
+extern "C" int ssi_ce_fwd_smooth(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
+                                 int64_t ignore_index, float smoothing, float z_coeff, float* row_loss, float* row_lse, float* row_u,
+                                 float* row_z, int write_grad, int dtype, void* stream) {
+    SSI_CHECK_ARG(logits && labels && row_loss && row_u && rows >= 0 && vocab > 0 && ld >= vocab && ld % 8 == 0);
+    if (!(smoothing >= 0.f) || !(smoothing < 1.f)) {  // NaN fails the first test
+        ssi_set_error("ce_fwd_smooth: smoothing must be finite and in [0, 1), got %g", (double)smoothing);
+        return SSI_ERR_ARG;
+    }
+    if (!(z_coeff >= 0.f) || !(z_coeff <= 3.0e38f)) {  // NaN fails the first test, +inf the second
+        ssi_set_error("ce_fwd_smooth: z_coeff must be finite and >= 0, got %g", (double)z_coeff);
+        return SSI_ERR_ARG;
+    }
+    SSI_CHECK_ARG(row_z || z_coeff == 0.f);
+    if (rows == 0) return SSI_OK;
+    const float two_z = 2.f * z_coeff;
+    const float ome = 1.f - smoothing, e_over_v = smoothing / (float)vocab;  // fp32, in this order: the kernels form w * ome and w * e_over_v
+    if (ce_row_form(dtype, logits, ld, vocab)) {
+        SSI_CE_DISPATCH_CHUNKS(ld,
+            if (write_grad) hipLaunchKernelGGL((ce_row_bf16_smooth_kernel<N, true>), ce_row_grid(rows), dim3(1024), 0, (hipStream_t)stream,
+                                               (bf16_t*)logits, ld, labels, rows, vocab, ignore_index, two_z, ome, e_over_v, row_loss, row_lse, row_z,
+                                               row_u, row_weight);
+            else hipLaunchKernelGGL((ce_row_bf16_smooth_kernel<N, false>), ce_row_grid(rows), dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits, ld,
+                                    labels, rows, vocab, ignore_index, two_z, ome, e_over_v, row_loss, row_lse, row_z, row_u, row_weight));
+        SSI_LAUNCH_CHECK();
+        return SSI_OK;
+    }
+    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(ce_fwd_smooth_kernel<T>, dim3((unsigned)rows), dim3(512), 0, (hipStream_t)stream, (T*)logits, ld,
+                                                 labels, vocab, ignore_index, two_z, ome, e_over_v, row_loss, row_lse, row_z, row_u, write_grad,
+                                                 row_weight));
     SSI_LAUNCH_CHECK();
     return SSI_OK;
 }
@@ -651,8 +805,8 @@ __global__ __launch_bounds__(1024, 4) void ce_row_bf16_metrics_kernel(const bf16
                                                                       int32_t* __restrict__ row_rank, const float* __restrict__ row_weight) {
     __shared__ float red[16];
     __shared__ int redi[16];
-    ce_row_bf16_body<NCH, CE_METRICS, false>(const_cast<bf16_t*>(logits), ld, labels, rows, vocab, ignore_index, 0.f, row_loss, row_lse, nullptr,
-                                             row_nll, row_rank, row_weight, red, redi);
+    ce_row_bf16_body<NCH, CE_METRICS, false>(const_cast<bf16_t*>(logits), ld, labels, rows, vocab, ignore_index, 0.f, 1.f, 0.f, row_loss, row_lse,
+                                             nullptr, nullptr, row_nll, row_rank, row_weight, red, redi);
 }
 
 extern "C" int ssi_ce_fwd_metrics(const void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,

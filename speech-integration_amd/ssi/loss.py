@@ -73,8 +73,17 @@ def _z_term(logits, labels: Tensor, ignore_index: int) -> Tensor:
     return (lse * lse * valid).sum() / valid.sum()
 
 
+def _uniform_term(logits, labels: Tensor, ignore_index: int) -> Tensor:
+    """``sum over valid labels of (logsumexp(x) - mean(x)) / n_valid``, ``x = logits.float()``, in plain torch (the literal route's label
+    smoothing: the cross-entropy against the uniform distribution, coefficient not applied); ``logits`` as for ``_z_term``."""
+    chunks = logits if isinstance(logits, (list, tuple)) else [logits]
+    u = torch.cat([torch.logsumexp(c.float(), dim=-1) - c.float().mean(dim=-1) for c in chunks], dim=1)
+    valid = labels != ignore_index
+    return (u * valid).sum() / valid.sum()
+
+
 def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metrics=None, z_loss_coeff: float = 0.0,
-                 seq_scores=None) -> Tensor:
+                 seq_scores=None, label_smoothing: float = 0.0) -> Tensor:
     """``label_metrics`` (``ssi.eval.LabelMetrics``, forward-only, not in the reference): loss and top-k hits of the shifted labels are added to it
     per token type — by the cross-entropy kernel on the fused route, in plain torch from the logits on the literal one.  The loss is unchanged.
     ``z_loss_coeff`` (not in the reference; finite, >= 0): ``> 0`` adds the auxiliary z-loss ``z sum_i w_i logsumexp(logits_i)^2 / n_valid`` —
@@ -82,7 +91,18 @@ def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metri
     the two parts on the model as ``last_ce_loss`` and ``last_z_loss`` (detached scalars).  ``0.0``: exactly the loss of before.
     ``seq_scores`` (``ssi.eval.SeqScores``, forward-only, not in the reference): the sums of nll and top-k hits of the shifted labels over each
     of its sequences ``(row, start, end)`` of this batch are written to its ``out`` — by ``ssi_seq_score_reduce`` on the fused route, in
-    plain torch from the logits on the literal one.  The loss is unchanged.  Not together with ``z_loss_coeff > 0``."""
+    plain torch from the logits on the literal one.  The loss is unchanged.  Not together with ``z_loss_coeff > 0``.
+    ``label_smoothing`` (not in the reference; finite, in ``[0, 1)``): ``e > 0`` makes the objective that of
+    ``F.cross_entropy(label_smoothing=e)``, ``(1 - e) ce + e mean_i (logsumexp(logits_i) - mean_c logits_ic)`` (+ the z part) — inside the
+    cross-entropy kernel on the fused route, in plain torch on the literal one.  Either route leaves ``last_ce_loss`` (the plain
+    cross-entropy) and ``last_smooth_loss`` (``e`` x the uniform part) on the model.  Not together with ``label_metrics`` or ``seq_scores``.
+    ``0.0``: exactly the loss of before."""
+    label_smoothing = float(label_smoothing)
+    if not (math.isfinite(label_smoothing) and 0.0 <= label_smoothing < 1.0):
+        raise ValueError(f"label_smoothing must be finite and in [0, 1), got {label_smoothing!r}")
+    if label_smoothing > 0.0 and (label_metrics is not None or seq_scores is not None):
+        raise ValueError("compute_loss: label_smoothing does not combine with label_metrics or seq_scores in one call (dev-set metrics and "
+                         "sequence scores are plain cross-entropy)")
     z_loss_coeff = float(z_loss_coeff)
     if not (math.isfinite(z_loss_coeff) and z_loss_coeff >= 0.0):
         raise ValueError(f"z_loss_coeff must be finite and >= 0, got {z_loss_coeff!r}")
@@ -105,6 +125,8 @@ def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metri
             extra["z_loss_coeff"] = z_loss_coeff
         if seq_scores is not None:
             extra["seq_scores"] = seq_scores
+        if label_smoothing > 0.0:
+            extra["label_smoothing"] = label_smoothing
         return model.fused_loss(batch["tokens"], labels, ignore_index, input_pos=batch.get("input_pos"), **extra)
     if batch.get("loss_weights") is not None:
         raise ValueError("loss_weights need the fused LM head + cross-entropy of the HIP decoder (model.fused_loss)")
@@ -120,12 +142,17 @@ def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metri
     if seq_scores is not None:
         seq_scores.add_logits(logits, labels, ignore_index)
     z_part = z_loss_coeff * _z_term(logits, labels, ignore_index) if z_loss_coeff > 0.0 else None
+    u_part = label_smoothing * _uniform_term(logits, labels, ignore_index) if label_smoothing > 0.0 else None
     if not isinstance(logits, list):
         labels = labels.reshape(-1)
         logits = logits.reshape(-1, logits.size(-1))
     loss = loss_fn(logits, labels)
     del logits
+    ce = loss
+    if u_part is not None:
+        model.last_ce_loss, model.last_smooth_loss = ce.detach(), u_part.detach()
+        loss = (1.0 - label_smoothing) * ce + u_part
     if z_part is not None:
-        model.last_ce_loss, model.last_z_loss = loss.detach(), z_part.detach()
+        model.last_ce_loss, model.last_z_loss = ce.detach(), z_part.detach()
         loss = loss + z_part
     return loss

@@ -241,6 +241,7 @@ class HipLlamaDecoder(nn.Module):
         self.label_errors: Optional[Tensor] = None        # device count of out-of-range labels seen by the last fused loss
         self.last_ce_loss: Optional[Tensor] = None        # device scalars of the last fused loss with z_loss_coeff > 0: its cross-entropy part ...
         self.last_z_loss: Optional[Tensor] = None         # ... and its z part (coefficient applied, same normalisation)
+        self.last_smooth_loss: Optional[Tensor] = None    # label_smoothing > 0: e x the uniform part (same normalisation); last_ce_loss is set too
         self.bucket_listener = None                       # callable(name, lo, hi) for the NEXT gradient-exchanging backward (see _backward_hidden)
         self.position_errors: Optional[Tensor] = None     # device count of input_pos entries outside the RoPE table in the last forward
         self.grad_sync = None                             # optional ssi.distributed.GradSync
@@ -697,7 +698,7 @@ class HipLlamaDecoder(nn.Module):
 
     def fused_loss(self, tokens: Tensor, shifted_labels: Tensor, ignore_index: int = CROSS_ENTROPY_IGNORE_IDX,
                    input_pos: Optional[Tensor] = None, attn_plan=None, loss_weights: Optional[Tensor] = None,
-                   label_metrics=None, z_loss_coeff: float = 0.0, seq_scores=None) -> Tensor:
+                   label_metrics=None, z_loss_coeff: float = 0.0, seq_scores=None, label_smoothing: float = 0.0) -> Tensor:
         """Mean NLL over non-ignored (already shifted) labels with the LM head + CE fused: equals
         ``CEWithChunkedOutputLoss()(model(tokens, input_pos=...), shifted_labels)`` of the reference for any chunk count.
         ``input_pos`` ([B, S], restarting at 0 with every document): packed rows, block-causal attention.  ``attn_plan``
@@ -718,7 +719,20 @@ class HipLlamaDecoder(nn.Module):
         ``(row, start, end)`` of THIS batch are written to ``seq_scores.out`` (``ssi_ce_fwd_metrics`` + ``ssi_seq_score_reduce``).  Its positions
         are those of ``tokens`` as passed; the flat offsets ``row * S_padded + pos`` are made here, after the right-padding.  Combines with
         ``label_metrics`` (one cross-entropy launch feeds both reduces), not with ``z_loss_coeff > 0``; the returned loss is bit-identical
-        with and without it.  ``None``: exactly the launches of before."""
+        with and without it.  ``None``: exactly the launches of before.
+        ``label_smoothing`` (not in the reference; finite, in ``[0, 1)``): ``e > 0`` trains against ``(1 - e) onehot + e / vocab``, the loss of
+        ``F.cross_entropy(label_smoothing=e)``.  The result is ``((1 - e) sum_i w_i nll_i + e sum_i w_i u_i + z sum_i w_i lse_i^2) / n_valid``
+        with ``u_i = lse_i - mean_c logits[i, c]``; its gradient comes from one cross-entropy launch (``ssi_ce_fwd_smooth``, with whatever
+        ``z_loss_coeff`` is).  Left on the model: ``last_ce_loss`` (what a call without the option returns), ``last_smooth_loss``
+        (``e`` x the mean of ``u``) and, with a z-loss, ``last_z_loss``.  Not together with ``label_metrics`` or ``seq_scores`` (plain
+        cross-entropy both).  ``0.0``: exactly the launches of before."""
+        label_smoothing = float(label_smoothing)
+        if not (math.isfinite(label_smoothing) and 0.0 <= label_smoothing < 1.0):
+            raise ValueError(f"label_smoothing must be finite and in [0, 1), got {label_smoothing!r}")
+        if label_smoothing > 0.0 and label_metrics is not None:
+            raise ValueError("fused_loss: label_smoothing and label_metrics do not combine in one call (the dev set's metrics are plain cross-entropy)")
+        if label_smoothing > 0.0 and seq_scores is not None:
+            raise ValueError("fused_loss: label_smoothing and seq_scores do not combine in one call (a sequence's score is plain cross-entropy)")
         z_loss_coeff = float(z_loss_coeff)
         if not (math.isfinite(z_loss_coeff) and z_loss_coeff >= 0.0):
             raise ValueError(f"z_loss_coeff must be finite and >= 0, got {z_loss_coeff!r}")
@@ -741,23 +755,43 @@ class HipLlamaDecoder(nn.Module):
         labels = shifted_labels.reshape(-1).contiguous()
         weights = None if loss_weights is None else loss_weights.reshape(-1).contiguous()
         if torch.is_grad_enabled() and self.training:
-            return _FusedLossFn.apply(self, tokens, labels, ignore_index, self._anchor, input_pos, attn_plan, weights, z_loss_coeff)
+            return _FusedLossFn.apply(self, tokens, labels, ignore_index, self._anchor, input_pos, attn_plan, weights, z_loss_coeff, label_smoothing)
         hn = self._forward_hidden(tokens, save=False, input_pos=input_pos)
         seq = None if seq_scores is None else (seq_scores, tokens.shape[1])
         return self._ce_forward(hn, labels, ignore_index, write_grad=False, weights=weights, label_metrics=label_metrics,
-                                z_loss_coeff=z_loss_coeff, seq_scores=seq)[0]
+                                z_loss_coeff=z_loss_coeff, seq_scores=seq, label_smoothing=label_smoothing)[0]
 
     def _ce_forward(self, hn: Tensor, labels: Tensor, ignore_index: int, write_grad: bool,
                     weights: Optional[Tensor] = None, label_metrics=None, z_loss_coeff: float = 0.0,
-                    seq_scores=None) -> tuple[Tensor, Tensor, Tensor]:
+                    seq_scores=None, label_smoothing: float = 0.0) -> tuple[Tensor, Tensor, Tensor]:
         """Tied head + cross-entropy: (mean loss, stats, logits buffer — which holds softmax - onehot when ``write_grad``).  The same
         three launches as the one-call ABI entry ``ssi_lmhead_ce_fwd`` (``ops.lmhead_ce_fwd``), issued one by one here so that ``bench.py``
         can time the head GEMM on its own.  ``z_loss_coeff > 0``: the z form of the cross-entropy launch (the buffer then holds
         ``f softmax - onehot``, ``f = 1 + 2 z lse``) and a second reduce over its ``row_z``; the loss returned is the sum of both parts.
+        ``label_smoothing > 0``: the smoothing form (``ssi_ce_fwd_smooth``, which carries the z-loss too; the buffer then holds
+        ``f softmax - (1 - e) onehot - e / vocab``) and one more reduce over its ``row_u``.
         ``seq_scores``: ``(ssi.eval.SeqScores, padded row length)``."""
         T = hn.shape[0]
         logits = self._head_logits(hn, "logits" if write_grad else "logits.x")
         row_loss = self._arena.get("row_loss" if write_grad else "row_loss.x", (T,), torch.float32)
+        if label_smoothing > 0.0:
+            assert label_metrics is None and seq_scores is None
+            z_on = z_loss_coeff > 0.0
+            row_u = self._arena.get("row_u" if write_grad else "row_u.x", (T,), torch.float32)
+            row_z = self._arena.get("row_z" if write_grad else "row_z.x", (T,), torch.float32) if z_on else None
+            ops.ce_fwd_smooth(logits, labels, self.vocab_size, ignore_index, label_smoothing, z_loss_coeff, row_loss, None, row_u, row_z,
+                              write_grad, row_weight=weights)
+            out = torch.empty(12 if z_on else 8, dtype=torch.float32, device=self.device)
+            ops.ce_reduce(row_loss, labels, self.vocab_size, ignore_index, out[:4])
+            ops.ce_reduce(row_u, labels, self.vocab_size, ignore_index, out[4:8])  # the same labels: the same n_valid divides every part
+            self.label_errors = out[3]
+            self.last_ce_loss, self.last_smooth_loss = out[0], out[4] * label_smoothing
+            loss = out[0] * (1.0 - label_smoothing) + self.last_smooth_loss
+            if z_on:
+                ops.ce_reduce(row_z, labels, self.vocab_size, ignore_index, out[8:])
+                self.last_z_loss = out[8] * z_loss_coeff
+                loss = loss + self.last_z_loss
+            return loss, out[:4], logits
         if z_loss_coeff > 0.0:
             assert label_metrics is None and seq_scores is None
             row_z = self._arena.get("row_z" if write_grad else "row_z.x", (T,), torch.float32)
@@ -825,9 +859,11 @@ class _FusedLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model: HipLlamaDecoder, tokens: Tensor, labels: Tensor, ignore_index: int, anchor: Tensor,
-                input_pos: Optional[Tensor] = None, attn_plan=None, weights: Optional[Tensor] = None, z_loss_coeff: float = 0.0) -> Tensor:
+                input_pos: Optional[Tensor] = None, attn_plan=None, weights: Optional[Tensor] = None, z_loss_coeff: float = 0.0,
+                label_smoothing: float = 0.0) -> Tensor:
         hn = model._forward_hidden(tokens, save=True, input_pos=input_pos, attn_plan=attn_plan)
-        loss, stats, dlogits = model._ce_forward(hn, labels, ignore_index, write_grad=True, weights=weights, z_loss_coeff=z_loss_coeff)
+        loss, stats, dlogits = model._ce_forward(hn, labels, ignore_index, write_grad=True, weights=weights, z_loss_coeff=z_loss_coeff,
+                                                 label_smoothing=label_smoothing)
         ctx.model, ctx.gen = model, model._fwd_generation
         ctx.save_for_backward(hn, stats, dlogits)
         return loss.clone()
@@ -840,11 +876,11 @@ class _FusedLossFn(torch.autograd.Function):
             raise RuntimeError("HipLlamaDecoder: backward called for a forward whose activations were overwritten; "
                                "run backward before the next training forward")
         # d loss / d logits = (softmax - onehot) / n_valid ; the 1/n_valid and the upstream scalar ride in alpha_dev (with a z-loss the buffer
-        # holds (f softmax - onehot): both parts of the objective share the divisor)
+        # holds (f softmax - onehot), with label smoothing (f softmax - (1 - e) onehot - e / vocab): every part of the objective shares the divisor)
         alpha = (grad_out.to(torch.float32).reshape(1) / stats[2:3]).contiguous()
         d_hn = m._head_backward(dlogits, hn, alpha)
         m._backward_hidden(d_hn, ctx.gen)
-        return None, None, None, None, torch.zeros_like(m._anchor), None, None, None, None
+        return None, None, None, None, torch.zeros_like(m._anchor), None, None, None, None, None
 
 
 # --------------------------------------------------------------------------------------------------------------------

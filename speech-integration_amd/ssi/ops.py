@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
 __all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "swiglu_fwd",
-           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "round_bf16_sr", "set_impl", "set_attn_impl", "attn_last_dispatch",
+           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "round_bf16_sr", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
 
@@ -329,6 +329,25 @@ def ce_fwd_z(logits: Tensor, labels: Tensor, vocab: int, ignore_index: int, z_co
                                   and row_weight.device == logits.device)
     check(_lib.load().ssi_ce_fwd_z(ptr(logits), logits.stride(0), ptr(labels), ptr(row_weight), rows, vocab, ignore_index, float(z_coeff),
                                    ptr(row_loss), ptr(row_lse), ptr(row_z), int(write_grad), dtype_code(logits.dtype), stream_ptr()), "ssi_ce_fwd_z")
+
+
+def ce_fwd_smooth(logits: Tensor, labels: Tensor, vocab: int, ignore_index: int, smoothing: float, z_coeff: float, row_loss: Tensor,
+                  row_lse: Tensor | None, row_u: Tensor, row_z: Tensor | None, write_grad: bool, row_weight: Tensor | None = None) -> None:
+    """``ce_fwd_z`` with label smoothing ``e = smoothing`` in ``[0, 1)`` (``ssi_ce_fwd_smooth``): ``row_loss``, ``row_lse`` and ``row_z`` are those
+    of ``ce_fwd_z`` bit for bit (``row_z`` may be ``None`` when ``z_coeff == 0``), ``row_u[r] = w_r (lse_r - mean_c x[r, c])`` (fp32, the
+    coefficient NOT applied; 0 for an ignored or out-of-range label), and the gradient row is
+    ``w (f softmax - (1 - e) onehot) - w e / vocab`` on the real columns.  ``smoothing == 0``: the gradient of ``ce_fwd_z`` bit for bit."""
+    assert logits.dim() == 2 and logits.stride(1) == 1 and labels.dtype == torch.int64 and labels.is_contiguous()
+    rows = logits.shape[0]
+    assert labels.numel() == rows and row_loss.dtype == torch.float32 and row_loss.numel() >= rows
+    assert row_lse is None or (row_lse.dtype == torch.float32 and row_lse.numel() >= rows)
+    assert row_u.dtype == torch.float32 and row_u.is_contiguous() and row_u.numel() >= rows
+    assert row_z is None or (row_z.dtype == torch.float32 and row_z.is_contiguous() and row_z.numel() >= rows)
+    assert row_weight is None or (row_weight.dtype == torch.float32 and row_weight.is_contiguous() and row_weight.numel() == rows
+                                  and row_weight.device == logits.device)
+    check(_lib.load().ssi_ce_fwd_smooth(ptr(logits), logits.stride(0), ptr(labels), ptr(row_weight), rows, vocab, ignore_index, float(smoothing),
+                                        float(z_coeff), ptr(row_loss), ptr(row_lse), ptr(row_u), ptr(row_z), int(write_grad),
+                                        dtype_code(logits.dtype), stream_ptr()), "ssi_ce_fwd_smooth")
 
 
 def ce_reduce(row_loss: Tensor, labels: Tensor, vocab: int, ignore_index: int, out: Tensor) -> None:

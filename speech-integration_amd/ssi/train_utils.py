@@ -105,6 +105,9 @@ def validate_train_cfg(cfg) -> None:
     z = cfg.get("z_loss_coeff", 0.0)
     if isinstance(z, bool) or not isinstance(z, (int, float)) or not math.isfinite(z) or z < 0:
         raise ValueError(f"config field 'z_loss_coeff' must be a finite number >= 0, got {z!r}")
+    e = cfg.get("label_smoothing", 0.0)
+    if isinstance(e, bool) or not isinstance(e, (int, float)) or not math.isfinite(e) or not 0 <= e < 1:
+        raise ValueError(f"config field 'label_smoothing' must be a finite number in [0, 1), got {e!r}")
 
 
 # training_state.pt (schema v1): key in the file -> name under which the trainer consumes it

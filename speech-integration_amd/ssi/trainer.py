@@ -137,6 +137,8 @@ class Trainer:
         self.dev_pairs: dict[str, Any] | None = None           # dev_pair_acc, dev_pair_acc_mean, dev_pair_n of the last evaluation (``eval_pairs``)
         self.z_loss_coeff = 0.0                                # ``z_loss_coeff`` of the config (``setup``); 0: no z-loss anywhere
         self._z_loss_running = 0.0                             # the window's z part (x valid labels), beside ``loss_running``
+        self.label_smoothing = 0.0                             # ``label_smoothing`` of the config (``setup``); 0: plain cross-entropy
+        self._smooth_loss_running = 0.0                        # the window's uniform part (e applied, x valid labels), beside ``_z_loss_running``
         for name in self._FILLED_BY_SETUP:
             setattr(self, name, None)
         for name, zero in self._COUNTERS.items():
@@ -165,6 +167,8 @@ class Trainer:
             self._loss_running += float(host[len(kinds) + 2])
             if self.z_loss_coeff > 0.0:
                 self._z_loss_running += float(host[len(kinds) + 3])
+            if self.label_smoothing > 0.0:
+                self._smooth_loss_running += float(host[len(kinds) + 3 + int(self.z_loss_coeff > 0.0)])
             # ids outside the vocabulary: torch's embedding / cross_entropy would device-assert (the HIP kernels write zeros and count);
             # the token-type ranges partition [0, V), so a token outside them shows up as a short sum; positions beyond the RoPE table are
             # clamped by the kernel and counted
@@ -205,6 +209,7 @@ class Trainer:
     def setup(self) -> None:
         validate_train_cfg(self.cfg)
         self.z_loss_coeff = float(self.cfg.get("z_loss_coeff", 0.0))
+        self.label_smoothing = float(self.cfg.get("label_smoothing", 0.0))
         set_seed(seed=SEED, debug_mode=self.cfg.get("debug_mode"))
         self.device = get_device(self.cfg.device)
         self.dtype = get_dtype(self.cfg.dtype)
@@ -451,19 +456,28 @@ class Trainer:
         self.fused_micro_batches += int(batch.get("micro_batches", 0))  # micro-batches that arrived joined into one batch (ssi/data/window.py)
         # (not in the reference) z_loss_coeff > 0: the objective gains the z-loss; its two parts are left on the model as scalars, and the
         # loss that is logged stays the cross-entropy part.  Only here: the dev loss never sees the coefficient
-        z_on = self.z_loss_coeff > 0.0
+        # label_smoothing > 0 (not in the reference either): the same with the uniform part, ``last_smooth_loss``; both may be on at once
+        z_on, smooth_on = self.z_loss_coeff > 0.0, self.label_smoothing > 0.0
         z_kw = {"z_loss_coeff": self.z_loss_coeff} if z_on else {}
+        if smooth_on:
+            z_kw["label_smoothing"] = self.label_smoothing
         loss_batch = compute_loss(loss_inputs(batch), self.model, self.loss_fn, **z_kw) * n_valid  # mean over SHIFTED x UNSHIFTED count
         loss_batch.backward()
-        z_batch = None
+        z_batch = smooth_batch = None
+        if z_on or smooth_on:
+            loss_batch = self.model.last_ce_loss.detach() * n_valid
         if z_on:
-            loss_batch, z_batch = self.model.last_ce_loss.detach() * n_valid, self.model.last_z_loss.detach() * n_valid
+            z_batch = self.model.last_z_loss.detach() * n_valid
+        if smooth_on:
+            smooth_batch = self.model.last_smooth_loss.detach() * n_valid
         if on_gpu:
             zero = torch.zeros(1, dtype=torch.float64, device=tokens.device)
             errs = [getattr(self.model, "label_errors", None), getattr(self.model, "position_errors", None)]
             errs = [zero if e is None else e.detach().to(torch.float64).reshape(1) for e in errs]
-            # row = [count per token type ..., total (non-pad), valid labels, loss x valid labels, (z-loss x valid labels,) bad labels, bad positions]
-            parts = [loss_batch.detach().to(torch.float64).reshape(1)] + ([z_batch.to(torch.float64).reshape(1)] if z_on else [])
+            # row = [count per token type ..., total (non-pad), valid labels, loss x valid labels, (z-loss x valid labels,)
+            #        (smoothing part x valid labels,) bad labels, bad positions]
+            parts = ([loss_batch.detach().to(torch.float64).reshape(1)] + ([z_batch.to(torch.float64).reshape(1)] if z_on else [])
+                     + ([smooth_batch.to(torch.float64).reshape(1)] if smooth_on else []))
             row = torch.cat((counts_dev.to(torch.float64), *parts, *errs))
             self._pending_readbacks.append((row, tokens.numel()))
             return
@@ -474,6 +488,8 @@ class Trainer:
         self._loss_running += float(loss_batch.item())
         if z_on:
             self._z_loss_running += float(z_batch.item())
+        if smooth_on:
+            self._smooth_loss_running += float(smooth_batch.item())
 
     def _arm_optimizer(self, n_valid: Tensor, last_of_window: bool) -> None:
         """Round 5: AdamW under the window's last backward (``HipAdamW.overlap_with_backward``).  The window's token count — the divisor of
@@ -509,12 +525,15 @@ class Trainer:
             # per-type totals must be too: every rank adds what the OTHER ranks saw in this window)
             kinds = sorted(self._type_counts_window)
             summed = all_reduce_scalars([self.num_tokens_step, self.loss_running, float(sum(self._bad_inputs_window.values())),
-                                         *(self._type_counts_window[k] for k in kinds), *([self._z_loss_running] if self.z_loss_coeff > 0.0 else [])],
+                                         *(self._type_counts_window[k] for k in kinds), *([self._z_loss_running] if self.z_loss_coeff > 0.0 else []),
+                                         *([self._smooth_loss_running] if self.label_smoothing > 0.0 else [])],
                                         self.device, group=self.grad_sync.scalar_group)
             self.num_tokens_step, self.loss_running = int(round(summed[0])), float(summed[1])
             if self.z_loss_coeff > 0.0:
                 self._z_loss_running = float(summed[3 + len(kinds)])
-            for k, v in zip(kinds, summed[3:]):
+            if self.label_smoothing > 0.0:
+                self._smooth_loss_running = float(summed[3 + len(kinds) + int(self.z_loss_coeff > 0.0)])
+            for k, v in zip(kinds, summed[3:]):  # (zip stops at the kinds: the z and smoothing sums ride behind them)
                 self.token_type_counts_total[k] += int(round(v)) - self._type_counts_window[k]
             self.grad_sync.finish(defer_last=self.cfg.clip_grad_norm is None)  # the embedding bucket lands under the AdamW of the rest
             if summed[2] > 0:  # every rank sees the same sum, so every rank raises (after its reductions have drained)
@@ -594,7 +613,7 @@ class Trainer:
             self._lag_buffers.append(e["host"])
             kinds = list(self.token_type_ranges)
             bad: defaultdict[str, int] = defaultdict(int)
-            loss_sum, z_sum, n_valid_device = 0.0, 0.0, 0
+            loss_sum, z_sum, smooth_sum, n_valid_device = 0.0, 0.0, 0.0, 0
             for host_row, n_positions in zip(rows, e["positions"]):
                 counts = {tt: int(c) for tt, c in zip(kinds + ["total"], host_row)}
                 for tt, c in counts.items():
@@ -603,6 +622,8 @@ class Trainer:
                 loss_sum += float(host_row[len(kinds) + 2])
                 if self.z_loss_coeff > 0.0:
                     z_sum += float(host_row[len(kinds) + 3])
+                if self.label_smoothing > 0.0:
+                    smooth_sum += float(host_row[len(kinds) + 3 + int(self.z_loss_coeff > 0.0)])
                 bad["labels outside [0, vocab_size)"] += int(host_row[-2])
                 bad["token ids outside [0, vocab_size)"] += n_positions - sum(counts[tt] for tt in kinds)
                 bad["input_pos entries outside the RoPE table"] += int(host_row[-1])
@@ -614,7 +635,8 @@ class Trainer:
             mean_loss = loss_sum / e["window_tokens"]
             if self._loss_log is not None:
                 self._loss_log.append(mean_loss)
-            self._log_metrics(e["epoch"], e["iter_idx"], mean_loss, snapshot=e, z_loss_to_log=z_sum / e["window_tokens"])
+            self._log_metrics(e["epoch"], e["iter_idx"], mean_loss, snapshot=e, z_loss_to_log=z_sum / e["window_tokens"],
+                              smooth_loss_to_log=smooth_sum / e["window_tokens"])
 
     def _apply_window(self, window_tokens: int) -> None:
         """Gradients of the window -> parameters: mean over the window's (global) unshifted token count, optional global-norm clip, AdamW,
@@ -636,7 +658,8 @@ class Trainer:
         mean_loss = self.loss_running / window_tokens
         if self._loss_log is not None:
             self._loss_log.append(mean_loss)
-        self._log_metrics(epoch, iter_idx, mean_loss, z_loss_to_log=self._z_loss_running / window_tokens)
+        self._log_metrics(epoch, iter_idx, mean_loss, z_loss_to_log=self._z_loss_running / window_tokens,
+                          smooth_loss_to_log=self._smooth_loss_running / window_tokens)
 
     def _evaluate(self) -> float:
         """The dev loss; with ``eval_token_metrics`` the per-token-type keys of the same pass are left in ``self.dev_metrics`` for the log record;
@@ -670,12 +693,13 @@ class Trainer:
         return out
 
     def _log_metrics(self, epoch: int, iter_idx: int, loss_to_log: float, snapshot: dict[str, Any] | None = None,
-                     z_loss_to_log: float = 0.0) -> None:
+                     z_loss_to_log: float = 0.0, smooth_loss_to_log: float = 0.0) -> None:
         """One console line per optimizer step; the metric record (same keys as the reference logs to W&B, ``trainer.py:440-475``) every
         ``log_interval`` steps from rank 0; the dev loss joins it on steps that evaluate.  ``snapshot``: the step's values as they were when
         its window closed (``_optimizer_step_lagged`` logs a step after the next one has been launched); without one, the current state.
         ``loss`` is always the cross-entropy part; with ``z_loss_coeff > 0`` the record also carries ``z_loss`` (coefficient applied, the
-        same normalisation), and ``dev_loss`` stays the plain cross-entropy."""
+        same normalisation), with ``label_smoothing > 0`` ``smooth_loss`` (likewise: ``objective = (1 - e) loss + smooth_loss + z_loss``), and
+        ``dev_loss`` stays the plain cross-entropy."""
         if snapshot is None:
             now = self._t_last_arrival = time.perf_counter()
             snapshot = {"global_step": self.global_step, "window_tokens": self.num_tokens_step, "lr": get_lr(self.optimizer), "now": now,
@@ -701,6 +725,8 @@ class Trainer:
         }
         if self.z_loss_coeff > 0.0:
             record["z_loss"] = z_loss_to_log
+        if self.label_smoothing > 0.0:
+            record["smooth_loss"] = smooth_loss_to_log
         record.update({f"n_tokens.{kind}": n for kind, n in type_counts.items()})
         if self.cfg.clip_grad_norm is not None:
             record["grad_norm"] = None if snapshot["grad_norm"] is None else float(snapshot["grad_norm"])
@@ -720,7 +746,7 @@ class Trainer:
 
     def _reset_step_accumulators(self) -> None:
         self.loss_running, self.num_tokens_step, self.max_seq_len_step = 0.0, 0, 0
-        self._z_loss_running = 0.0
+        self._z_loss_running = self._smooth_loss_running = 0.0
         self._window_valid_dev, self._window_valid_host = None, 0
         self.t_step_start = time.perf_counter()
 

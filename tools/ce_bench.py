@@ -1,11 +1,13 @@
 """Cross-entropy kernel alone at the step's shape: T = 16384 rows, V = 133258 (ld 133376), bf16, gradient in place.
 ``--z COEFF``: the z-loss form (``ops.ce_fwd_z``, ``ssi_ce_fwd_z``) with that coefficient instead of ``ops.ce_fwd``.
+``--smooth E``: the label-smoothing form (``ops.ce_fwd_smooth``, ``ssi_ce_fwd_smooth``) with that smoothing, and ``--z`` (default 0) as its z.
 ``--metrics``: the label-rank form (``ops.ce_fwd_metrics``, ``ssi_ce_fwd_metrics``; forward only: one pass over the logits)."""
 import argparse, sys, torch
 sys.path.insert(0, 'speech-integration_amd')
 from ssi import ops
 ap = argparse.ArgumentParser()
 ap.add_argument("--z", type=float, default=None, metavar="COEFF", help="time ce_fwd_z with this coefficient (default: ce_fwd)")
+ap.add_argument("--smooth", type=float, default=None, metavar="E", help="time ce_fwd_smooth with this smoothing (and --z, default 0)")
 ap.add_argument("--metrics", action="store_true", help="time ce_fwd_metrics")
 ap.add_argument("--reps", type=int, default=10)
 args = ap.parse_args()
@@ -14,11 +16,14 @@ logits = (torch.randn(T, LD, device='cuda') * 2).bfloat16()
 labels = torch.randint(0, V, (T,), device='cuda')
 labels[::7] = -100
 row_loss = torch.empty(T, device='cuda'); row_lse = torch.empty(T, device='cuda'); row_z = torch.empty(T, device='cuda')
+row_u = torch.empty(T, device='cuda')
 row_nll = torch.empty(T, device='cuda'); row_rank = torch.empty(T, device='cuda', dtype=torch.int32)
 work = logits.clone()
 def run():
     if args.metrics:
         ops.ce_fwd_metrics(work, labels, V, -100, row_loss, row_lse, row_nll, row_rank)
+    elif args.smooth is not None:
+        ops.ce_fwd_smooth(work, labels, V, -100, args.smooth, args.z or 0.0, row_loss, row_lse, row_u, row_z, write_grad=True)
     elif args.z is None:
         ops.ce_fwd(work, labels, V, -100, row_loss, row_lse, write_grad=True)
     else:
@@ -33,6 +38,8 @@ for _ in range(args.reps):
     s.record(); run(); e.record(); torch.cuda.synchronize()
     ms.append(s.elapsed_time(e))
 mean = sum(ms) / len(ms)
-name = "ce_fwd_metrics" if args.metrics else "ce_fwd" if args.z is None else f"ce_fwd_z({args.z:g})"
+name = ("ce_fwd_metrics" if args.metrics else f"ce_fwd_smooth({args.smooth:g}, z {args.z or 0.0:g})" if args.smooth is not None
+        else "ce_fwd" if args.z is None else f"ce_fwd_z({args.z:g})")
 print(f"{name} {mean:.3f} ms  (min {min(ms):.3f}, max {max(ms):.3f} of {len(ms)}; {3 * T * LD * 2 / mean / 1e9:.2f} TB/s at 3 passes, "
-      f"{2 * T * LD * 2 / mean / 1e9:.2f} at 2)  loss {float(row_loss.sum()):.4f}" + ("" if args.z is None or args.metrics else f"  z {float(row_z.sum()):.4f}") + (f"  top-1 {int((row_rank == 0).sum())}" if args.metrics else ""))
+      f"{2 * T * LD * 2 / mean / 1e9:.2f} at 2)  loss {float(row_loss.sum()):.4f}" + ("" if args.z is None or args.metrics else f"  z {float(row_z.sum()):.4f}")
+      + ("" if args.smooth is None or args.metrics else f"  u {float(row_u.sum()):.4f}") + (f"  top-1 {int((row_rank == 0).sum())}" if args.metrics else ""))
