@@ -197,13 +197,16 @@ extern "C" int ssi_embed_bwd(const int64_t* tokens, const void* dout, void* dtab
 //                          rank[r] = #{c < vocab : x[c] > x[label]} + #{c < label : x[c] == x[label]}  — the label's position in a stable
 //                          descending sort of the row; rank == 0 <=> argmax(row) == label under the first-occurrence rule.  Compares on
 //                          the stored values: an exact integer.
-// Each entry has kernels of its own in two forms — generic (any dtype and shape; one 512-thread block per row, fp32 online log-sum-exp,
-// the gradient or the rank from a second read of the row out of L2 / Infinity Cache) and register-resident bf16 rows (the training step's
-// form) — so the instantiations an entry launches do not depend on what the other entries need.  Kernels of their own, ONE body: the
-// generic kernels are built from the pieces below and the four row kernels wrap ce_row_bf16_body, so the max, the exp-sum and the lse
-// are the same statements whatever the entry: row_loss and row_lse agree bit for bit across the four, and with z = 0 (f = 1 exactly) and
-// e = 0 (times an exact 1, minus an exact 0) so does the gradient.
+// Two forms — generic (any dtype and shape; one 512-thread block per row, fp32 online log-sum-exp, the gradient or the rank from a second
+// read of the row out of L2 / Infinity Cache) and register-resident bf16 rows (the training step's form) — and in each form ONE body
+// templated on the entry's CeMode, ce_generic_body and ce_row_bf16_body: what an entry adds sits behind `if constexpr`, so the max, the
+// exp-sum and the lse are the same statements whatever the entry: row_loss and row_lse agree bit for bit across the four, and with z = 0
+// (f = 1 exactly) and e = 0 (times an exact 1, minus an exact 0) so does the gradient.  The __global__ kernels are wrappers, one per entry
+// and form, that pass nullptr / 0 for what is not theirs: the instantiations an entry launches do not depend on what the other entries
+// need.  On the host the four entries share one launcher, ce_fwd_launch<MODE>; an entry keeps its own pointer and coefficient checks.
 // =====================================================================================================================
+enum CeMode { CE_PLAIN, CE_Z, CE_SMOOTH, CE_METRICS };
+
 // a row takes part iff its label is not ignored AND inside [0, vocab)
 __device__ __forceinline__ bool ce_label_valid(int64_t label, int64_t vocab, int64_t ignore_index) {
     return label != ignore_index && label >= 0 && label < vocab;
@@ -237,27 +240,6 @@ template <typename T> __device__ __forceinline__ float ce_row_lse(const T* lr, i
     return gm + logf(gs);
 }
 
-// in-place gradient of one row: w (f p - onehot) with the z-loss factor f, w (p - onehot) without (no multiply by 1); pad columns 0.  f may have
-// any sign: lse < -1 / (2 z) makes it negative, and the plain multiply carries that
-template <bool WITH_F, typename T>
-__device__ __forceinline__ void ce_grad_row(T* lr, int64_t nvec, int64_t vocab, int64_t label, float lse, float w, float f) {
-    constexpr int N = Vec16<T>::N;
-    for (int64_t v = threadIdx.x; v < nvec; v += 512) {
-        Vec16<T> a = load16(lr + v * N), o;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const int64_t c = v * N + i;
-            float g = 0.f;
-            if (c < vocab) {
-                if constexpr (WITH_F) g = w * (f * expf(a.get(i) - lse) - (c == label ? 1.f : 0.f));
-                else g = w * (expf(a.get(i) - lse) - (c == label ? 1.f : 0.f));
-            }
-            o.set(i, g);
-        }
-        store16(lr + v * N, o);
-    }
-}
-
 // plain fp32 sum over the columns [0, vocab) of one row, in a fixed order (per-thread stride, then the block's tree)
 template <typename T> __device__ __forceinline__ float ce_row_sum(const T* lr, int64_t nvec, int64_t vocab, float* red) {
     constexpr int N = Vec16<T>::N;
@@ -270,11 +252,30 @@ template <typename T> __device__ __forceinline__ float ce_row_sum(const T* lr, i
     return block_sum(s, red);
 }
 
-// ce_grad_row<true> with label smoothing: w (f p - ome onehot) - wu on the real columns, ome = 1 - e and wu = w (e / vocab); pad columns 0.
-// e = 0: ome = 1 and wu = 0 exactly — the values of ce_grad_row<true>
-template <typename T>
-__device__ __forceinline__ void ce_grad_row_smooth(T* lr, int64_t nvec, int64_t vocab, int64_t label, float lse, float w, float f, float ome,
-                                                   float wu) {
+// the label's rank in its row (see K9): pad columns [vocab, ld) never count
+template <typename T> __device__ __forceinline__ int ce_rank_row(const T* lr, int64_t nvec, int64_t vocab, int64_t label, float xl, int* redi) {
+    constexpr int N = Vec16<T>::N;
+    int cnt = 0;
+    for (int64_t v = threadIdx.x; v < nvec; v += 512) {
+        Vec16<T> a = load16(lr + v * N);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const int64_t c = v * N + i;
+            const float x = a.get(i);
+            cnt += (int)(c < vocab) & ((int)(x > xl) | ((int)(x == xl) & (int)(c < label)));  // bitwise: no branch per element
+        }
+    }
+    return block_sum_i32(cnt, redi);
+}
+
+// in-place gradient of one row, pad columns 0:
+//   CE_PLAIN   w (p - onehot): no multiply by 1
+//   CE_Z       w (f p - onehot) with the z-loss factor f (ome = 1).  f may have any sign: lse < -1 / (2 z) makes it negative, and the plain
+//              multiply carries that
+//   CE_SMOOTH  w (f p - ome onehot) - wu on the real columns, ome = 1 - e and wu = w (e / vocab).  e = 0: ome = 1 and wu = 0 exactly — the
+//              values of CE_Z
+template <CeMode MODE, typename T>
+__device__ __forceinline__ void ce_grad_row(T* lr, int64_t nvec, int64_t vocab, int64_t label, float lse, float w, float f, float ome, float wu) {
     constexpr int N = Vec16<T>::N;
     for (int64_t v = threadIdx.x; v < nvec; v += 512) {
         Vec16<T> a = load16(lr + v * N), o;
@@ -283,13 +284,57 @@ __device__ __forceinline__ void ce_grad_row_smooth(T* lr, int64_t nvec, int64_t 
             const int64_t c = v * N + i;
             float g = 0.f;
             if (c < vocab) {
-                float wt = w * (f * expf(a.get(i) - lse) - (c == label ? ome : 0.f));
-                asm volatile("" : "+v"(wt));  // no fma across here: the product is rounded before wu leaves it, as in the register form
-                g = wt - wu;
+                if constexpr (MODE == CE_PLAIN) g = w * (expf(a.get(i) - lse) - (c == label ? 1.f : 0.f));
+                else g = w * (f * expf(a.get(i) - lse) - (c == label ? ome : 0.f));
+                if constexpr (MODE == CE_SMOOTH) {
+                    asm volatile("" : "+v"(g));  // no fma across here: the product is rounded before wu leaves it, as in the register form
+                    g -= wu;
+                }
             }
             o.set(i, g);
         }
         store16(lr + v * N, o);
+    }
+}
+
+// The body of all four generic kernels, one block per row; the kernels pass nullptr / 0 for what is not theirs (ome = 1 for CE_Z).  A row
+// without a valid label skips the passes and keeps lse = xl = sx = 0, w = 1, cnt = -1: every output below is then an exact 0, the rank -1.
+template <typename T, CeMode MODE>
+__device__ __forceinline__ void ce_generic_body(T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels, int64_t vocab,
+                                                int64_t ignore_index, float two_z, float ome, float e_over_v, float* __restrict__ row_loss,
+                                                float* __restrict__ row_lse, float* __restrict__ row_z, float* __restrict__ row_u,
+                                                float* __restrict__ row_nll, int32_t* __restrict__ row_rank, int write_grad,
+                                                const float* __restrict__ row_weight, float* red, int* redi) {
+    const int64_t row = blockIdx.x;
+    T* lr = logits + row * ld;
+    const int64_t label = labels[row];
+    const int64_t nvec = ld / Vec16<T>::N;
+    const bool valid = ce_label_valid(label, vocab, ignore_index);  // block-uniform
+    float lse = 0.f, sx = 0.f, w = 1.f, xl = 0.f;
+    int cnt = -1;
+    if (valid) {
+        lse = ce_row_lse(lr, nvec, vocab, red);
+        if constexpr (MODE == CE_SMOOTH) sx = ce_row_sum(lr, nvec, vocab, red);
+        w = row_weight ? row_weight[row] : 1.f;  // weighted rows: loss and gradient of the row times w
+        if (MODE == CE_METRICS || threadIdx.x == 0) xl = to_f32<T>(lr[label]);  // block-uniform address
+        if constexpr (MODE == CE_METRICS) cnt = ce_rank_row(lr, nvec, vocab, label, xl, redi);  // a second pass over the row (from L2, as the gradient's)
+    }
+    if (threadIdx.x == 0) {
+        row_loss[row] = w * (lse - xl);
+        if (row_lse) row_lse[row] = lse;
+        if constexpr (MODE == CE_Z) row_z[row] = w * (lse * lse);
+        if constexpr (MODE == CE_SMOOTH) {
+            if (row_z) row_z[row] = w * (lse * lse);
+            row_u[row] = w * (lse - sx / (float)vocab);
+        }
+        if constexpr (MODE == CE_METRICS) { row_nll[row] = lse - xl; row_rank[row] = cnt; }
+    }
+    if constexpr (MODE != CE_METRICS) {  // the metrics form is forward only: it never writes the row
+        if (!write_grad) return;
+        if (!valid) { ce_zero_row(lr, nvec); return; }
+        const float f = fmaf(two_z, lse, 1.f);
+        __syncthreads();  // lr[label] read above must precede the overwrite below
+        ce_grad_row<MODE>(lr, nvec, vocab, label, lse, w, f, ome, w * e_over_v);
     }
 }
 
@@ -298,24 +343,40 @@ __global__ __launch_bounds__(512) void ce_fwd_kernel(T* __restrict__ logits, int
                                                      int64_t vocab, int64_t ignore_index, float* __restrict__ row_loss,
                                                      float* __restrict__ row_lse, int write_grad, const float* __restrict__ row_weight) {
     __shared__ float red[16];
-    const int64_t row = blockIdx.x;
-    T* lr = logits + row * ld;
-    const int64_t label = labels[row];
-    const int64_t nvec = ld / Vec16<T>::N;
-    if (!ce_label_valid(label, vocab, ignore_index)) {  // block-uniform
-        if (threadIdx.x == 0) { row_loss[row] = 0.f; if (row_lse) row_lse[row] = 0.f; }
-        if (write_grad) ce_zero_row(lr, nvec);
-        return;
-    }
-    const float lse = ce_row_lse(lr, nvec, vocab, red);
-    const float w = row_weight ? row_weight[row] : 1.f;  // weighted rows (ssi_ce_fwd_weighted): loss and gradient of the row times w
-    if (threadIdx.x == 0) {
-        row_loss[row] = w * (lse - to_f32<T>(lr[label]));
-        if (row_lse) row_lse[row] = lse;
-    }
-    if (!write_grad) return;
-    __syncthreads();  // lr[label] read above must precede the overwrite below
-    ce_grad_row<false>(lr, nvec, vocab, label, lse, w, 1.f);
+    ce_generic_body<T, CE_PLAIN>(logits, ld, labels, vocab, ignore_index, 0.f, 1.f, 0.f, row_loss, row_lse, nullptr, nullptr, nullptr, nullptr,
+                                 write_grad, row_weight, red, nullptr);
+}
+
+template <typename T>
+__global__ __launch_bounds__(512) void ce_fwd_z_kernel(T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                       int64_t vocab, int64_t ignore_index, float two_z, float* __restrict__ row_loss,
+                                                       float* __restrict__ row_lse, float* __restrict__ row_z, int write_grad,
+                                                       const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    ce_generic_body<T, CE_Z>(logits, ld, labels, vocab, ignore_index, two_z, 1.f, 0.f, row_loss, row_lse, row_z, nullptr, nullptr, nullptr,
+                             write_grad, row_weight, red, nullptr);
+}
+
+template <typename T>
+__global__ __launch_bounds__(512) void ce_fwd_smooth_kernel(T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                            int64_t vocab, int64_t ignore_index, float two_z, float ome, float e_over_v,
+                                                            float* __restrict__ row_loss, float* __restrict__ row_lse,
+                                                            float* __restrict__ row_z, float* __restrict__ row_u, int write_grad,
+                                                            const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    ce_generic_body<T, CE_SMOOTH>(logits, ld, labels, vocab, ignore_index, two_z, ome, e_over_v, row_loss, row_lse, row_z, row_u, nullptr, nullptr,
+                                  write_grad, row_weight, red, nullptr);
+}
+
+template <typename T>
+__global__ __launch_bounds__(512) void ce_fwd_metrics_kernel(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                             int64_t vocab, int64_t ignore_index, float* __restrict__ row_loss,
+                                                             float* __restrict__ row_lse, float* __restrict__ row_nll,
+                                                             int32_t* __restrict__ row_rank, const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    __shared__ int redi[16];
+    ce_generic_body<T, CE_METRICS>(const_cast<T*>(logits), ld, labels, vocab, ignore_index, 0.f, 1.f, 0.f, row_loss, row_lse, nullptr, nullptr,
+                                   row_nll, row_rank, 0, row_weight, red, redi);
 }
 
 // ---- bf16 rows held in registers (the training step's form) -------------------------------------------------------------------------------
@@ -343,7 +404,6 @@ __global__ __launch_bounds__(512) void ce_fwd_kernel(T* __restrict__ logits, int
 //               Every lane needs that logit before the pass; the label is workgroup-uniform and nothing is overwritten here, so each
 //               lane loads it itself from one address and nothing has to wait for it to land.  The pad columns are -inf in the
 //               registers and lie above every valid label: they are neither greater than a logit nor tie below the label.
-enum CeMode { CE_PLAIN, CE_Z, CE_SMOOTH, CE_METRICS };
 
 template <int NCH, CeMode MODE, bool write_grad>
 __device__ __forceinline__ void ce_row_bf16_body(bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels, int64_t rows,
@@ -535,6 +595,39 @@ __global__ __launch_bounds__(1024, 4) void ce_row_bf16_kernel(bf16_t* __restrict
                                                 nullptr, nullptr, row_weight, red, nullptr);
 }
 
+template <int NCH, bool write_grad>
+__global__ __launch_bounds__(1024, 4) void ce_row_bf16_z_kernel(bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                                int64_t rows, int64_t vocab, int64_t ignore_index, float two_z,
+                                                                float* __restrict__ row_loss, float* __restrict__ row_lse,
+                                                                float* __restrict__ row_z, const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    ce_row_bf16_body<NCH, CE_Z, write_grad>(logits, ld, labels, rows, vocab, ignore_index, two_z, 1.f, 0.f, row_loss, row_lse, row_z, nullptr,
+                                            nullptr, nullptr, row_weight, red, nullptr);
+}
+
+template <int NCH, bool write_grad>
+__global__ __launch_bounds__(1024, 4) void ce_row_bf16_smooth_kernel(bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                                     int64_t rows, int64_t vocab, int64_t ignore_index, float two_z, float ome,
+                                                                     float e_over_v, float* __restrict__ row_loss, float* __restrict__ row_lse,
+                                                                     float* __restrict__ row_z, float* __restrict__ row_u,
+                                                                     const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    ce_row_bf16_body<NCH, CE_SMOOTH, write_grad>(logits, ld, labels, rows, vocab, ignore_index, two_z, ome, e_over_v, row_loss, row_lse, row_z,
+                                                 row_u, nullptr, nullptr, row_weight, red, nullptr);
+}
+
+template <int NCH>
+__global__ __launch_bounds__(1024, 4) void ce_row_bf16_metrics_kernel(const bf16_t* __restrict__ logits, int64_t ld,
+                                                                      const int64_t* __restrict__ labels, int64_t rows, int64_t vocab,
+                                                                      int64_t ignore_index, float* __restrict__ row_loss,
+                                                                      float* __restrict__ row_lse, float* __restrict__ row_nll,
+                                                                      int32_t* __restrict__ row_rank, const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    __shared__ int redi[16];
+    ce_row_bf16_body<NCH, CE_METRICS, false>(const_cast<bf16_t*>(logits), ld, labels, rows, vocab, ignore_index, 0.f, 1.f, 0.f, row_loss, row_lse,
+                                             nullptr, nullptr, row_nll, row_rank, row_weight, red, redi);
+}
+
 // ---- host side: which form an input takes, and the chunk counts the row form is instantiated for --------------------------------------
 static int ce_num_cus() {
     static const int n = [] {
@@ -545,7 +638,7 @@ static int ce_num_cus() {
     return n;
 }
 
-// the one predicate of the three entries: the same inputs take the same form in each
+// the one predicate of the four entries: the same inputs take the same form in each
 static bool ce_row_form(int dtype, const void* logits, int64_t ld, int64_t vocab) {
     const int64_t chunks = ssi_cdiv(ld, 8192);
     return dtype == SSI_BF16 && ((uintptr_t)logits & 15) == 0 && ld - vocab < 8192 && ld * 2 < (1LL << 31) &&
@@ -562,28 +655,120 @@ static dim3 ce_row_grid(int64_t rows) { return dim3((unsigned)(rows < ce_num_cus
         SSI_CE_CHUNKS_CASE(17, __VA_ARGS__) SSI_CE_CHUNKS_CASE(18, __VA_ARGS__)                                                         \
     }
 
-extern "C" int ssi_ce_fwd_weighted(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
-                                   int64_t ignore_index, float* row_loss, float* row_lse, int write_grad, int dtype, void* stream) {
-    SSI_CHECK_ARG(logits && labels && row_loss && rows >= 0 && vocab > 0 && ld >= vocab && ld % 8 == 0);
-    if (rows == 0) return SSI_OK;
-    if (ce_row_form(dtype, logits, ld, vocab)) {
-        SSI_CE_DISPATCH_CHUNKS(ld,
-            if (write_grad) hipLaunchKernelGGL((ce_row_bf16_kernel<N, true>), ce_row_grid(rows), dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits,
-                                               ld, labels, rows, vocab, ignore_index, row_loss, row_lse, row_weight);
-            else hipLaunchKernelGGL((ce_row_bf16_kernel<N, false>), ce_row_grid(rows), dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits, ld,
-                                    labels, rows, vocab, ignore_index, row_loss, row_lse, row_weight));
-        SSI_LAUNCH_CHECK();
-        return SSI_OK;
+// what a launch needs, whatever the entry: the entries' common arguments first, then what only some of them have
+struct CeArgs {
+    void* logits; int64_t ld; const int64_t* labels; const float* row_weight; int64_t rows, vocab, ignore_index;
+    float *row_loss, *row_lse; int write_grad, dtype; hipStream_t stream;
+    float two_z = 0.f, ome = 1.f, e_over_v = 0.f;  // CE_Z, CE_SMOOTH: 2 z;  CE_SMOOTH: 1 - e, e / vocab
+    float *row_z = nullptr, *row_u = nullptr;      // CE_Z, CE_SMOOTH;  CE_SMOOTH
+    float* row_nll = nullptr; int32_t* row_rank = nullptr;  // CE_METRICS
+};
+
+// the row kernel of MODE with its own parameter list
+template <CeMode MODE, int NCH, bool write_grad> static void ce_launch_row(const CeArgs& a) {
+    const dim3 grid = ce_row_grid(a.rows), block(1024);
+    bf16_t* logits = (bf16_t*)a.logits;
+    if constexpr (MODE == CE_PLAIN)
+        hipLaunchKernelGGL((ce_row_bf16_kernel<NCH, write_grad>), grid, block, 0, a.stream, logits, a.ld, a.labels, a.rows, a.vocab, a.ignore_index,
+                           a.row_loss, a.row_lse, a.row_weight);
+    else if constexpr (MODE == CE_Z)
+        hipLaunchKernelGGL((ce_row_bf16_z_kernel<NCH, write_grad>), grid, block, 0, a.stream, logits, a.ld, a.labels, a.rows, a.vocab, a.ignore_index,
+                           a.two_z, a.row_loss, a.row_lse, a.row_z, a.row_weight);
+    else if constexpr (MODE == CE_SMOOTH)
+        hipLaunchKernelGGL((ce_row_bf16_smooth_kernel<NCH, write_grad>), grid, block, 0, a.stream, logits, a.ld, a.labels, a.rows, a.vocab,
+                           a.ignore_index, a.two_z, a.ome, a.e_over_v, a.row_loss, a.row_lse, a.row_z, a.row_u, a.row_weight);
+    else
+        hipLaunchKernelGGL((ce_row_bf16_metrics_kernel<NCH>), grid, block, 0, a.stream, (const bf16_t*)logits, a.ld, a.labels, a.rows, a.vocab,
+                           a.ignore_index, a.row_loss, a.row_lse, a.row_nll, a.row_rank, a.row_weight);
+}
+
+// the generic kernel of MODE, likewise
+template <CeMode MODE, typename T> static void ce_launch_generic(const CeArgs& a) {
+    const dim3 grid((unsigned)a.rows), block(512);
+    T* logits = (T*)a.logits;
+    if constexpr (MODE == CE_PLAIN)
+        hipLaunchKernelGGL(ce_fwd_kernel<T>, grid, block, 0, a.stream, logits, a.ld, a.labels, a.vocab, a.ignore_index, a.row_loss, a.row_lse,
+                           a.write_grad, a.row_weight);
+    else if constexpr (MODE == CE_Z)
+        hipLaunchKernelGGL(ce_fwd_z_kernel<T>, grid, block, 0, a.stream, logits, a.ld, a.labels, a.vocab, a.ignore_index, a.two_z, a.row_loss,
+                           a.row_lse, a.row_z, a.write_grad, a.row_weight);
+    else if constexpr (MODE == CE_SMOOTH)
+        hipLaunchKernelGGL(ce_fwd_smooth_kernel<T>, grid, block, 0, a.stream, logits, a.ld, a.labels, a.vocab, a.ignore_index, a.two_z, a.ome,
+                           a.e_over_v, a.row_loss, a.row_lse, a.row_z, a.row_u, a.write_grad, a.row_weight);
+    else
+        hipLaunchKernelGGL(ce_fwd_metrics_kernel<T>, grid, block, 0, a.stream, (const T*)logits, a.ld, a.labels, a.vocab, a.ignore_index, a.row_loss,
+                           a.row_lse, a.row_nll, a.row_rank, a.row_weight);
+}
+
+// what the four entries share: the common argument check, the form the input takes, the launch
+template <CeMode MODE> static int ce_fwd_launch(const CeArgs& a) {
+    SSI_CHECK_ARG(a.logits && a.labels && a.row_loss && a.rows >= 0 && a.vocab > 0 && a.ld >= a.vocab && a.ld % 8 == 0);
+    if (a.rows == 0) return SSI_OK;
+    if (ce_row_form(a.dtype, a.logits, a.ld, a.vocab)) {
+        SSI_CE_DISPATCH_CHUNKS(a.ld,
+            if (a.write_grad) ce_launch_row<MODE, N, true>(a);  // (never so for CE_METRICS, whose one kernel ignores the flag)
+            else ce_launch_row<MODE, N, false>(a));
+    } else {
+        SSI_DISPATCH_DTYPE(a.dtype, ce_launch_generic<MODE, T>(a));
     }
-    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(ce_fwd_kernel<T>, dim3((unsigned)rows), dim3(512), 0, (hipStream_t)stream,
-                                                 (T*)logits, ld, labels, vocab, ignore_index, row_loss, row_lse, write_grad, row_weight));
     SSI_LAUNCH_CHECK();
     return SSI_OK;
+}
+
+static bool ce_z_coeff_ok(float z) { return z >= 0.f && z <= 3.0e38f; }  // NaN fails the first test, +inf the second
+
+extern "C" int ssi_ce_fwd_weighted(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
+                                   int64_t ignore_index, float* row_loss, float* row_lse, int write_grad, int dtype, void* stream) {
+    return ce_fwd_launch<CE_PLAIN>(CeArgs{logits, ld, labels, row_weight, rows, vocab, ignore_index, row_loss, row_lse, write_grad, dtype, (hipStream_t)stream});
 }
 
 extern "C" int ssi_ce_fwd(void* logits, int64_t ld, const int64_t* labels, int64_t rows, int64_t vocab,
                           int64_t ignore_index, float* row_loss, float* row_lse, int write_grad, int dtype, void* stream) {
     return ssi_ce_fwd_weighted(logits, ld, labels, nullptr, rows, vocab, ignore_index, row_loss, row_lse, write_grad, dtype, stream);
+}
+
+extern "C" int ssi_ce_fwd_z(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
+                            int64_t ignore_index, float z_coeff, float* row_loss, float* row_lse, float* row_z, int write_grad, int dtype,
+                            void* stream) {
+    SSI_CHECK_ARG(row_z);
+    if (!ce_z_coeff_ok(z_coeff)) {
+        ssi_set_error("ce_fwd_z: z_coeff must be finite and >= 0, got %g", (double)z_coeff);
+        return SSI_ERR_ARG;
+    }
+    CeArgs a{logits, ld, labels, row_weight, rows, vocab, ignore_index, row_loss, row_lse, write_grad, dtype, (hipStream_t)stream};
+    a.two_z = 2.f * z_coeff;
+    a.row_z = row_z;
+    return ce_fwd_launch<CE_Z>(a);
+}
+
+extern "C" int ssi_ce_fwd_smooth(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
+                                 int64_t ignore_index, float smoothing, float z_coeff, float* row_loss, float* row_lse, float* row_u,
+                                 float* row_z, int write_grad, int dtype, void* stream) {
+    SSI_CHECK_ARG(row_u);
+    if (!(smoothing >= 0.f) || !(smoothing < 1.f)) {  // NaN fails the first test
+        ssi_set_error("ce_fwd_smooth: smoothing must be finite and in [0, 1), got %g", (double)smoothing);
+        return SSI_ERR_ARG;
+    }
+    if (!ce_z_coeff_ok(z_coeff)) {
+        ssi_set_error("ce_fwd_smooth: z_coeff must be finite and >= 0, got %g", (double)z_coeff);
+        return SSI_ERR_ARG;
+    }
+    SSI_CHECK_ARG(row_z || z_coeff == 0.f);
+    CeArgs a{logits, ld, labels, row_weight, rows, vocab, ignore_index, row_loss, row_lse, write_grad, dtype, (hipStream_t)stream};
+    a.two_z = 2.f * z_coeff;
+    a.ome = 1.f - smoothing, a.e_over_v = smoothing / (float)vocab;  // fp32, in this order: the kernels form w * ome and w * e_over_v
+    a.row_z = row_z, a.row_u = row_u;
+    return ce_fwd_launch<CE_SMOOTH>(a);
+}
+
+extern "C" int ssi_ce_fwd_metrics(const void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
+                                  int64_t ignore_index, float* row_loss, float* row_lse, float* row_nll, int32_t* row_rank, int dtype,
+                                  void* stream) {
+    SSI_CHECK_ARG(row_nll && row_rank);
+    // the metrics kernels take the logits as const again: this form writes no gradient
+    CeArgs a{const_cast<void*>(logits), ld, labels, row_weight, rows, vocab, ignore_index, row_loss, row_lse, 0, dtype, (hipStream_t)stream};
+    a.row_nll = row_nll, a.row_rank = row_rank;
+    return ce_fwd_launch<CE_METRICS>(a);
 }
 
 // The valid-label count uses the predicate of the row kernels; labels that are neither ignored nor in range are counted in out[3] so that
@@ -612,222 +797,8 @@ extern "C" int ssi_ce_reduce(const float* row_loss, const int64_t* labels, int64
 }
 
 // =====================================================================================================================
-// K9z the kernels of ssi_ce_fwd_z (see K9)
+// K9m the reductions over the rows ssi_ce_fwd_metrics wrote
 // =====================================================================================================================
-template <typename T>
-__global__ __launch_bounds__(512) void ce_fwd_z_kernel(T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                       int64_t vocab, int64_t ignore_index, float two_z, float* __restrict__ row_loss,
-                                                       float* __restrict__ row_lse, float* __restrict__ row_z, int write_grad,
-                                                       const float* __restrict__ row_weight) {
-    __shared__ float red[16];
-    const int64_t row = blockIdx.x;
-    T* lr = logits + row * ld;
-    const int64_t label = labels[row];
-    const int64_t nvec = ld / Vec16<T>::N;
-    if (!ce_label_valid(label, vocab, ignore_index)) {  // block-uniform
-        if (threadIdx.x == 0) { row_loss[row] = 0.f; if (row_lse) row_lse[row] = 0.f; row_z[row] = 0.f; }
-        if (write_grad) ce_zero_row(lr, nvec);
-        return;
-    }
-    const float lse = ce_row_lse(lr, nvec, vocab, red);
-    const float w = row_weight ? row_weight[row] : 1.f;
-    if (threadIdx.x == 0) {
-        row_loss[row] = w * (lse - to_f32<T>(lr[label]));
-        if (row_lse) row_lse[row] = lse;
-        row_z[row] = w * (lse * lse);
-    }
-    if (!write_grad) return;
-    const float f = fmaf(two_z, lse, 1.f);
-    __syncthreads();  // lr[label] read above must precede the overwrite below
-    ce_grad_row<true>(lr, nvec, vocab, label, lse, w, f);
-}
-
-template <int NCH, bool write_grad>
-__global__ __launch_bounds__(1024, 4) void ce_row_bf16_z_kernel(bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                                int64_t rows, int64_t vocab, int64_t ignore_index, float two_z,
-                                                                float* __restrict__ row_loss, float* __restrict__ row_lse,
-                                                                float* __restrict__ row_z, const float* __restrict__ row_weight) {
-    __shared__ float red[16];
-    ce_row_bf16_body<NCH, CE_Z, write_grad>(logits, ld, labels, rows, vocab, ignore_index, two_z, 1.f, 0.f, row_loss, row_lse, row_z, nullptr,
-                                            nullptr, nullptr, row_weight, red, nullptr);
-}
-
-extern "C" int ssi_ce_fwd_z(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
-                            int64_t ignore_index, float z_coeff, float* row_loss, float* row_lse, float* row_z, int write_grad, int dtype,
-                            void* stream) {
-    SSI_CHECK_ARG(logits && labels && row_loss && row_z && rows >= 0 && vocab > 0 && ld >= vocab && ld % 8 == 0);
-    if (!(z_coeff >= 0.f) || !(z_coeff <= 3.0e38f)) {  // NaN fails the first test, +inf the second
-        ssi_set_error("ce_fwd_z: z_coeff must be finite and >= 0, got %g", (double)z_coeff);
-        return SSI_ERR_ARG;
-    }
-    if (rows == 0) return SSI_OK;
-    const float two_z = 2.f * z_coeff;
-    if (ce_row_form(dtype, logits, ld, vocab)) {
-        SSI_CE_DISPATCH_CHUNKS(ld,
-            if (write_grad) hipLaunchKernelGGL((ce_row_bf16_z_kernel<N, true>), ce_row_grid(rows), dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits,
-                                               ld, labels, rows, vocab, ignore_index, two_z, row_loss, row_lse, row_z, row_weight);
-            else hipLaunchKernelGGL((ce_row_bf16_z_kernel<N, false>), ce_row_grid(rows), dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits, ld,
-                                    labels, rows, vocab, ignore_index, two_z, row_loss, row_lse, row_z, row_weight));
-        SSI_LAUNCH_CHECK();
-        return SSI_OK;
-    }
-    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(ce_fwd_z_kernel<T>, dim3((unsigned)rows), dim3(512), 0, (hipStream_t)stream, (T*)logits, ld,
-                                                 labels, vocab, ignore_index, two_z, row_loss, row_lse, row_z, write_grad, row_weight));
-    SSI_LAUNCH_CHECK();
-    return SSI_OK;
-}
-
-// =====================================================================================================================
-// K9s the kernels of ssi_ce_fwd_smooth (see K9)
-// =====================================================================================================================
-template <typename T>
-__global__ __launch_bounds__(512) void ce_fwd_smooth_kernel(T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                            int64_t vocab, int64_t ignore_index, float two_z, float ome, float e_over_v,
-                                                            float* __restrict__ row_loss, float* __restrict__ row_lse,
-                                                            float* __restrict__ row_z, float* __restrict__ row_u, int write_grad,
-                                                            const float* __restrict__ row_weight) {
-    __shared__ float red[16];
-    const int64_t row = blockIdx.x;
-    T* lr = logits + row * ld;
-    const int64_t label = labels[row];
-    const int64_t nvec = ld / Vec16<T>::N;
-    if (!ce_label_valid(label, vocab, ignore_index)) {  // block-uniform
-        if (threadIdx.x == 0) { row_loss[row] = 0.f; if (row_lse) row_lse[row] = 0.f; if (row_z) row_z[row] = 0.f; row_u[row] = 0.f; }
-        if (write_grad) ce_zero_row(lr, nvec);
-        return;
-    }
-    const float lse = ce_row_lse(lr, nvec, vocab, red);
-    const float sx = ce_row_sum(lr, nvec, vocab, red);
-    const float w = row_weight ? row_weight[row] : 1.f;
-    if (threadIdx.x == 0) {
-        row_loss[row] = w * (lse - to_f32<T>(lr[label]));
-        if (row_lse) row_lse[row] = lse;
-        if (row_z) row_z[row] = w * (lse * lse);
-        row_u[row] = w * (lse - sx / (float)vocab);
-    }
-    if (!write_grad) return;
-    const float f = fmaf(two_z, lse, 1.f);
-    __syncthreads();  // lr[label] read above must precede the overwrite below
-    ce_grad_row_smooth(lr, nvec, vocab, label, lse, w, f, ome, w * e_over_v);
-}
-
-template <int NCH, bool write_grad>
-__global__ __launch_bounds__(1024, 4) void ce_row_bf16_smooth_kernel(bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                                     int64_t rows, int64_t vocab, int64_t ignore_index, float two_z, float ome,
-                                                                     float e_over_v, float* __restrict__ row_loss, float* __restrict__ row_lse,
-                                                                     float* __restrict__ row_z, float* __restrict__ row_u,
-                                                                     const float* __restrict__ row_weight) {
-    __shared__ float red[16];
-    ce_row_bf16_body<NCH, CE_SMOOTH, write_grad>(logits, ld, labels, rows, vocab, ignore_index, two_z, ome, e_over_v, row_loss, row_lse, row_z,
-                                                 row_u, nullptr, nullptr, row_weight, red, nullptr);
-}
-
-extern "C" int ssi_ce_fwd_smooth(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
-                                 int64_t ignore_index, float smoothing, float z_coeff, float* row_loss, float* row_lse, float* row_u,
-                                 float* row_z, int write_grad, int dtype, void* stream) {
-    SSI_CHECK_ARG(logits && labels && row_loss && row_u && rows >= 0 && vocab > 0 && ld >= vocab && ld % 8 == 0);
-    if (!(smoothing >= 0.f) || !(smoothing < 1.f)) {  // NaN fails the first test
-        ssi_set_error("ce_fwd_smooth: smoothing must be finite and in [0, 1), got %g", (double)smoothing);
-        return SSI_ERR_ARG;
-    }
-    if (!(z_coeff >= 0.f) || !(z_coeff <= 3.0e38f)) {  // NaN fails the first test, +inf the second
-        ssi_set_error("ce_fwd_smooth: z_coeff must be finite and >= 0, got %g", (double)z_coeff);
-        return SSI_ERR_ARG;
-    }
-    SSI_CHECK_ARG(row_z || z_coeff == 0.f);
-    if (rows == 0) return SSI_OK;
-    const float two_z = 2.f * z_coeff;
-    const float ome = 1.f - smoothing, e_over_v = smoothing / (float)vocab;  // fp32, in this order: the kernels form w * ome and w * e_over_v
-    if (ce_row_form(dtype, logits, ld, vocab)) {
-        SSI_CE_DISPATCH_CHUNKS(ld,
-            if (write_grad) hipLaunchKernelGGL((ce_row_bf16_smooth_kernel<N, true>), ce_row_grid(rows), dim3(1024), 0, (hipStream_t)stream,
-                                               (bf16_t*)logits, ld, labels, rows, vocab, ignore_index, two_z, ome, e_over_v, row_loss, row_lse, row_z,
-                                               row_u, row_weight);
-            else hipLaunchKernelGGL((ce_row_bf16_smooth_kernel<N, false>), ce_row_grid(rows), dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits, ld,
-                                    labels, rows, vocab, ignore_index, two_z, ome, e_over_v, row_loss, row_lse, row_z, row_u, row_weight));
-        SSI_LAUNCH_CHECK();
-        return SSI_OK;
-    }
-    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(ce_fwd_smooth_kernel<T>, dim3((unsigned)rows), dim3(512), 0, (hipStream_t)stream, (T*)logits, ld,
-                                                 labels, vocab, ignore_index, two_z, ome, e_over_v, row_loss, row_lse, row_z, row_u, write_grad,
-                                                 row_weight));
-    SSI_LAUNCH_CHECK();
-    return SSI_OK;
-}
-
-// =====================================================================================================================
-// K9m the kernels of ssi_ce_fwd_metrics (see K9), and the reductions over the rows they wrote
-// =====================================================================================================================
-template <typename T>
-__global__ __launch_bounds__(512) void ce_fwd_metrics_kernel(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                             int64_t vocab, int64_t ignore_index, float* __restrict__ row_loss,
-                                                             float* __restrict__ row_lse, float* __restrict__ row_nll,
-                                                             int32_t* __restrict__ row_rank, const float* __restrict__ row_weight) {
-    constexpr int N = Vec16<T>::N;
-    __shared__ float red[16];
-    __shared__ int redi[16];
-    const int64_t row = blockIdx.x;
-    const T* lr = logits + row * ld;
-    const int64_t label = labels[row];
-    const int64_t nvec = ld / N;
-    if (!ce_label_valid(label, vocab, ignore_index)) {  // block-uniform
-        if (threadIdx.x == 0) { row_loss[row] = 0.f; if (row_lse) row_lse[row] = 0.f; row_nll[row] = 0.f; row_rank[row] = -1; }
-        return;
-    }
-    const float lse = ce_row_lse(lr, nvec, vocab, red);
-    const float w = row_weight ? row_weight[row] : 1.f;
-    const float xl = to_f32<T>(lr[label]);  // block-uniform address; the logits are read-only here
-    // second pass over the row (from L2, as the gradient pass of ce_fwd_kernel): pad columns [vocab, ld) never count
-    int cnt = 0;
-    for (int64_t v = threadIdx.x; v < nvec; v += 512) {
-        Vec16<T> a = load16(lr + v * N);
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const int64_t c = v * N + i;
-            const float x = a.get(i);
-            cnt += (int)(c < vocab) & ((int)(x > xl) | ((int)(x == xl) & (int)(c < label)));  // bitwise: no branch per element
-        }
-    }
-    cnt = block_sum_i32(cnt, redi);
-    if (threadIdx.x == 0) {
-        row_loss[row] = w * (lse - xl);
-        if (row_lse) row_lse[row] = lse;
-        row_nll[row] = lse - xl;
-        row_rank[row] = cnt;
-    }
-}
-
-template <int NCH>
-__global__ __launch_bounds__(1024, 4) void ce_row_bf16_metrics_kernel(const bf16_t* __restrict__ logits, int64_t ld,
-                                                                      const int64_t* __restrict__ labels, int64_t rows, int64_t vocab,
-                                                                      int64_t ignore_index, float* __restrict__ row_loss,
-                                                                      float* __restrict__ row_lse, float* __restrict__ row_nll,
-                                                                      int32_t* __restrict__ row_rank, const float* __restrict__ row_weight) {
-    __shared__ float red[16];
-    __shared__ int redi[16];
-    ce_row_bf16_body<NCH, CE_METRICS, false>(const_cast<bf16_t*>(logits), ld, labels, rows, vocab, ignore_index, 0.f, 1.f, 0.f, row_loss, row_lse,
-                                             nullptr, nullptr, row_nll, row_rank, row_weight, red, redi);
-}
-
-extern "C" int ssi_ce_fwd_metrics(const void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
-                                  int64_t ignore_index, float* row_loss, float* row_lse, float* row_nll, int32_t* row_rank, int dtype,
-                                  void* stream) {
-    SSI_CHECK_ARG(logits && labels && row_loss && row_nll && row_rank && rows >= 0 && vocab > 0 && ld >= vocab && ld % 8 == 0);
-    if (rows == 0) return SSI_OK;
-    if (ce_row_form(dtype, logits, ld, vocab)) {
-        SSI_CE_DISPATCH_CHUNKS(ld, hipLaunchKernelGGL((ce_row_bf16_metrics_kernel<N>), ce_row_grid(rows), dim3(1024), 0, (hipStream_t)stream,
-                                                      (const bf16_t*)logits, ld, labels, rows, vocab, ignore_index, row_loss, row_lse, row_nll,
-                                                      row_rank, row_weight));
-        SSI_LAUNCH_CHECK();
-        return SSI_OK;
-    }
-    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(ce_fwd_metrics_kernel<T>, dim3((unsigned)rows), dim3(512), 0, (hipStream_t)stream,
-                                                 (const T*)logits, ld, labels, vocab, ignore_index, row_loss, row_lse, row_nll, row_rank,
-                                                 row_weight));
-    SSI_LAUNCH_CHECK();
-    return SSI_OK;
-}
-
 // The two reductions below sum the same four numbers over ranked rows (rank >= 0: the rows ssi_ce_fwd_metrics gave a valid label), in fp64;
 // the counts ride as doubles (exact below 2^53).
 __device__ __forceinline__ void ce_metrics_add(double (&acc)[4], int rank, float nll, int topk) {

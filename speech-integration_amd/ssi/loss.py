@@ -82,6 +82,29 @@ def _uniform_term(logits, labels: Tensor, ignore_index: int) -> Tensor:
     return (u * valid).sum() / valid.sum()
 
 
+def check_loss_options(who: str, label_smoothing: float, z_loss_coeff: float, label_metrics=None, seq_scores=None,
+                       under_grad: bool = False) -> tuple[float, float]:
+    """The rules of the loss options, said once for ``compute_loss`` and ``model.fused_loss`` (``who``): both coefficients as floats in their
+    ranges; neither combines with ``label_metrics`` or ``seq_scores`` (dev-set metrics and sequence scores are plain cross-entropy); and, with
+    ``under_grad`` (a training forward of the fused route), those two forward-only forms are refused."""
+    e, z = float(label_smoothing), float(z_loss_coeff)
+    if not (math.isfinite(e) and 0.0 <= e < 1.0):
+        raise ValueError(f"label_smoothing must be finite and in [0, 1), got {e!r}")
+    if not (math.isfinite(z) and z >= 0.0):
+        raise ValueError(f"z_loss_coeff must be finite and >= 0, got {z!r}")
+    plain = [(name, what) for name, given, what in (("label_metrics", label_metrics, "the dev set's metrics are"),
+                                                    ("seq_scores", seq_scores, "a sequence's score is")) if given is not None]
+    if plain:
+        name, what = plain[0]
+        for coeff, value in (("label_smoothing", e), ("z_loss_coeff", z)):
+            if value > 0.0:
+                raise ValueError(f"{who}: {coeff} and {name} do not combine in one call ({what} plain cross-entropy)")
+        if under_grad:
+            raise RuntimeError(f"{who}({name}=...) is forward-only: call it under torch.no_grad() / inference_mode() or on model.eval(); "
+                               "the training step's cross-entropy kernel does not rank labels")
+    return e, z
+
+
 def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metrics=None, z_loss_coeff: float = 0.0,
                  seq_scores=None, label_smoothing: float = 0.0) -> Tensor:
     """``label_metrics`` (``ssi.eval.LabelMetrics``, forward-only, not in the reference): loss and top-k hits of the shifted labels are added to it
@@ -97,17 +120,7 @@ def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metri
     cross-entropy kernel on the fused route, in plain torch on the literal one.  Either route leaves ``last_ce_loss`` (the plain
     cross-entropy) and ``last_smooth_loss`` (``e`` x the uniform part) on the model.  Not together with ``label_metrics`` or ``seq_scores``.
     ``0.0``: exactly the loss of before."""
-    label_smoothing = float(label_smoothing)
-    if not (math.isfinite(label_smoothing) and 0.0 <= label_smoothing < 1.0):
-        raise ValueError(f"label_smoothing must be finite and in [0, 1), got {label_smoothing!r}")
-    if label_smoothing > 0.0 and (label_metrics is not None or seq_scores is not None):
-        raise ValueError("compute_loss: label_smoothing does not combine with label_metrics or seq_scores in one call (dev-set metrics and "
-                         "sequence scores are plain cross-entropy)")
-    z_loss_coeff = float(z_loss_coeff)
-    if not (math.isfinite(z_loss_coeff) and z_loss_coeff >= 0.0):
-        raise ValueError(f"z_loss_coeff must be finite and >= 0, got {z_loss_coeff!r}")
-    if z_loss_coeff > 0.0 and seq_scores is not None:
-        raise ValueError("compute_loss: z_loss_coeff and seq_scores do not combine in one call (a sequence's score is plain cross-entropy)")
+    label_smoothing, z_loss_coeff = check_loss_options("compute_loss", label_smoothing, z_loss_coeff, label_metrics, seq_scores)
     labels = batch["labels"]
     ignore_index = loss_fn.ignore_index
     labels = torch.hstack((labels[..., 1:], torch.full_like(labels[..., -1:], ignore_index)))  # new tensor: batch untouched

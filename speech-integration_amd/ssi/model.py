@@ -33,6 +33,7 @@ from torch import Tensor, nn
 from . import _lib, ops
 from .constants import CROSS_ENTROPY_IGNORE_IDX, PRECISION_STR_TO_DTYPE
 from .llama_configs import ConfigLlama3_2
+from .loss import check_loss_options
 from .ops import GEMM_NN, GEMM_NT, GEMM_TN
 
 LOGGER = logging.getLogger(__name__)
@@ -726,26 +727,8 @@ class HipLlamaDecoder(nn.Module):
         ``z_loss_coeff`` is).  Left on the model: ``last_ce_loss`` (what a call without the option returns), ``last_smooth_loss``
         (``e`` x the mean of ``u``) and, with a z-loss, ``last_z_loss``.  Not together with ``label_metrics`` or ``seq_scores`` (plain
         cross-entropy both).  ``0.0``: exactly the launches of before."""
-        label_smoothing = float(label_smoothing)
-        if not (math.isfinite(label_smoothing) and 0.0 <= label_smoothing < 1.0):
-            raise ValueError(f"label_smoothing must be finite and in [0, 1), got {label_smoothing!r}")
-        if label_smoothing > 0.0 and label_metrics is not None:
-            raise ValueError("fused_loss: label_smoothing and label_metrics do not combine in one call (the dev set's metrics are plain cross-entropy)")
-        if label_smoothing > 0.0 and seq_scores is not None:
-            raise ValueError("fused_loss: label_smoothing and seq_scores do not combine in one call (a sequence's score is plain cross-entropy)")
-        z_loss_coeff = float(z_loss_coeff)
-        if not (math.isfinite(z_loss_coeff) and z_loss_coeff >= 0.0):
-            raise ValueError(f"z_loss_coeff must be finite and >= 0, got {z_loss_coeff!r}")
-        if z_loss_coeff > 0.0 and label_metrics is not None:
-            raise ValueError("fused_loss: z_loss_coeff and label_metrics do not combine in one call (the dev set's metrics are plain cross-entropy)")
-        if label_metrics is not None and torch.is_grad_enabled() and self.training:
-            raise RuntimeError("fused_loss(label_metrics=...) is forward-only (the dev set): call it under torch.no_grad() / inference_mode() "
-                               "or on model.eval(); the training step's cross-entropy kernel does not rank labels")
-        if z_loss_coeff > 0.0 and seq_scores is not None:
-            raise ValueError("fused_loss: z_loss_coeff and seq_scores do not combine in one call (a sequence's score is plain cross-entropy)")
-        if seq_scores is not None and torch.is_grad_enabled() and self.training:
-            raise RuntimeError("fused_loss(seq_scores=...) is forward-only (scoring): call it under torch.no_grad() / inference_mode() "
-                               "or on model.eval(); the training step's cross-entropy kernel does not rank labels")
+        label_smoothing, z_loss_coeff = check_loss_options("fused_loss", label_smoothing, z_loss_coeff, label_metrics, seq_scores,
+                                                           under_grad=torch.is_grad_enabled() and self.training)
         tokens = self._check_inputs(tokens, None, None, None, input_pos)
         if loss_weights is not None:
             if loss_weights.shape != tokens.shape:
@@ -771,44 +754,26 @@ class HipLlamaDecoder(nn.Module):
         ``label_smoothing > 0``: the smoothing form (``ssi_ce_fwd_smooth``, which carries the z-loss too; the buffer then holds
         ``f softmax - (1 - e) onehot - e / vocab``) and one more reduce over its ``row_u``.
         ``seq_scores``: ``(ssi.eval.SeqScores, padded row length)``."""
-        T = hn.shape[0]
-        logits = self._head_logits(hn, "logits" if write_grad else "logits.x")
-        row_loss = self._arena.get("row_loss" if write_grad else "row_loss.x", (T,), torch.float32)
-        if label_smoothing > 0.0:
+        T, e, z = hn.shape[0], label_smoothing, z_loss_coeff
+        sfx = "" if write_grad else ".x"
+        logits = self._head_logits(hn, "logits" + sfx)
+        row_loss = self._arena.get("row_loss" + sfx, (T,), torch.float32)
+        row_u = self._arena.get("row_u" + sfx, (T,), torch.float32) if e > 0.0 else None
+        row_z = self._arena.get("row_z" + sfx, (T,), torch.float32) if z > 0.0 else None
+        common = (logits, labels, self.vocab_size, ignore_index)
+        if e > 0.0 or z > 0.0:
             assert label_metrics is None and seq_scores is None
-            z_on = z_loss_coeff > 0.0
-            row_u = self._arena.get("row_u" if write_grad else "row_u.x", (T,), torch.float32)
-            row_z = self._arena.get("row_z" if write_grad else "row_z.x", (T,), torch.float32) if z_on else None
-            ops.ce_fwd_smooth(logits, labels, self.vocab_size, ignore_index, label_smoothing, z_loss_coeff, row_loss, None, row_u, row_z,
-                              write_grad, row_weight=weights)
-            out = torch.empty(12 if z_on else 8, dtype=torch.float32, device=self.device)
-            ops.ce_reduce(row_loss, labels, self.vocab_size, ignore_index, out[:4])
-            ops.ce_reduce(row_u, labels, self.vocab_size, ignore_index, out[4:8])  # the same labels: the same n_valid divides every part
-            self.label_errors = out[3]
-            self.last_ce_loss, self.last_smooth_loss = out[0], out[4] * label_smoothing
-            loss = out[0] * (1.0 - label_smoothing) + self.last_smooth_loss
-            if z_on:
-                ops.ce_reduce(row_z, labels, self.vocab_size, ignore_index, out[8:])
-                self.last_z_loss = out[8] * z_loss_coeff
-                loss = loss + self.last_z_loss
-            return loss, out[:4], logits
-        if z_loss_coeff > 0.0:
-            assert label_metrics is None and seq_scores is None
-            row_z = self._arena.get("row_z" if write_grad else "row_z.x", (T,), torch.float32)
-            ops.ce_fwd_z(logits, labels, self.vocab_size, ignore_index, z_loss_coeff, row_loss, None, row_z, write_grad, row_weight=weights)
-            out = torch.empty(8, dtype=torch.float32, device=self.device)
-            ops.ce_reduce(row_loss, labels, self.vocab_size, ignore_index, out[:4])
-            ops.ce_reduce(row_z, labels, self.vocab_size, ignore_index, out[4:])  # the same labels: the same n_valid divides both parts
-            self.label_errors = out[3]
-            self.last_ce_loss, self.last_z_loss = out[0], out[4] * z_loss_coeff
-            return out[0] + self.last_z_loss, out[:4], logits
-        if label_metrics is None and seq_scores is None:
-            ops.ce_fwd(logits, labels, self.vocab_size, ignore_index, row_loss, None, write_grad, row_weight=weights)
+        if e > 0.0:
+            ops.ce_fwd_smooth(*common, e, z, row_loss, None, row_u, row_z, write_grad, row_weight=weights)
+        elif z > 0.0:
+            ops.ce_fwd_z(*common, z, row_loss, None, row_z, write_grad, row_weight=weights)
+        elif label_metrics is None and seq_scores is None:
+            ops.ce_fwd(*common, row_loss, None, write_grad, row_weight=weights)
         else:  # forward-only (fused_loss refuses it under grad): the same row losses, plus nll and rank of every label, summed per type / sequence
             assert not write_grad
             row_nll = self._arena.get("row_nll.x", (T,), torch.float32)
             row_rank = self._arena.get("row_rank.x", (T,), torch.int32)
-            ops.ce_fwd_metrics(logits, labels, self.vocab_size, ignore_index, row_loss, None, row_nll, row_rank, row_weight=weights)
+            ops.ce_fwd_metrics(*common, row_loss, None, row_nll, row_rank, row_weight=weights)
             if label_metrics is not None:
                 ops.ce_metrics_reduce(row_nll, row_rank, labels, label_metrics.ranges_dev, label_metrics.topk, label_metrics.acc, accumulate=True)
             if seq_scores is not None:
@@ -817,10 +782,21 @@ class HipLlamaDecoder(nn.Module):
                 ops.seq_score_reduce(row_nll, row_rank, T, start, end, scores.topk, scores.out)
                 if scores.keep_rows:
                     scores.row_nll, scores.row_len = row_nll.clone(), row_len
-        out = torch.empty(4, dtype=torch.float32, device=self.device)
-        ops.ce_reduce(row_loss, labels, self.vocab_size, ignore_index, out)
+        # one reduce per part of the objective, over the same labels: the same n_valid divides every part.  (row buffer, coefficient, attribute)
+        parts = [(row_loss, None, "last_ce_loss")] + [(buf, c, name) for buf, c, name in ((row_u, e, "last_smooth_loss"), (row_z, z, "last_z_loss"))
+                                                       if buf is not None]
+        out = torch.empty(4 * len(parts), dtype=torch.float32, device=self.device)
+        for i, (buf, coeff, name) in enumerate(parts):
+            ops.ce_reduce(buf, labels, self.vocab_size, ignore_index, out[4 * i:4 * i + 4])
+            if len(parts) > 1:  # (a plain call leaves the attributes of the last call with an option as they are)
+                setattr(self, name, out[4 * i] if coeff is None else out[4 * i] * coeff)
         self.label_errors = out[3]  # device scalar: labels outside [0, vocab); the trainer folds it into its one read-back and raises
-        return out[0], out, logits
+        loss = out[0]
+        if e > 0.0:
+            loss = out[0] * (1.0 - e) + self.last_smooth_loss
+        if z > 0.0:
+            loss = loss + self.last_z_loss
+        return loss, out[:4], logits
 
 
 class _DecoderFn(torch.autograd.Function):

@@ -300,17 +300,27 @@ def transpose(src: Tensor, dst: Tensor) -> None:
                                     dtype_code(src.dtype), stream_ptr()), "ssi_transpose")
 
 
+def _row_buf_ok(t: Tensor, rows: int, dtype: torch.dtype = torch.float32) -> bool:
+    return t.dtype == dtype and t.is_contiguous() and t.numel() >= rows
+
+
+def _ce_rows(logits: Tensor, labels: Tensor, row_loss: Tensor, row_lse: Tensor | None, row_weight: Tensor | None) -> int:
+    """What the ``ce_fwd*`` wrappers ask of the arguments they share; the row count."""
+    assert logits.dim() == 2 and logits.stride(1) == 1 and labels.dtype == torch.int64 and labels.is_contiguous()
+    rows = logits.shape[0]
+    assert labels.numel() == rows and _row_buf_ok(row_loss, rows) and (row_lse is None or _row_buf_ok(row_lse, rows))
+    assert row_weight is None or (_row_buf_ok(row_weight, rows) and row_weight.numel() == rows and row_weight.device == logits.device)
+    return rows
+
+
 def ce_fwd(logits: Tensor, labels: Tensor, vocab: int, ignore_index: int, row_loss: Tensor, row_lse: Tensor | None,
            write_grad: bool, row_weight: Tensor | None = None) -> None:
     """``row_weight`` (fp32, one per row, >= 0; ``ssi_ce_fwd_weighted``): loss and gradient of row r times ``row_weight[r]``."""
-    assert logits.dim() == 2 and logits.stride(1) == 1 and labels.dtype == torch.int64 and labels.is_contiguous()
-    rows = logits.shape[0]
-    assert labels.numel() == rows and row_loss.dtype == torch.float32 and row_loss.numel() >= rows
+    rows = _ce_rows(logits, labels, row_loss, row_lse, row_weight)
     if row_weight is None:
         check(_lib.load().ssi_ce_fwd(ptr(logits), logits.stride(0), ptr(labels), rows, vocab, ignore_index, ptr(row_loss),
                                      ptr(row_lse), int(write_grad), dtype_code(logits.dtype), stream_ptr()), "ssi_ce_fwd")
         return
-    assert row_weight.dtype == torch.float32 and row_weight.is_contiguous() and row_weight.numel() == rows and row_weight.device == logits.device
     check(_lib.load().ssi_ce_fwd_weighted(ptr(logits), logits.stride(0), ptr(labels), ptr(row_weight), rows, vocab, ignore_index, ptr(row_loss),
                                           ptr(row_lse), int(write_grad), dtype_code(logits.dtype), stream_ptr()), "ssi_ce_fwd_weighted")
 
@@ -320,13 +330,8 @@ def ce_fwd_z(logits: Tensor, labels: Tensor, vocab: int, ignore_index: int, z_co
     """``ce_fwd`` with the auxiliary z-loss ``z_coeff * log^2 Z`` in the gradient (``ssi_ce_fwd_z``): ``row_loss`` and ``row_lse`` are those of
     ``ce_fwd`` bit for bit, ``row_z[r] = w_r lse_r^2`` (fp32, the coefficient NOT applied; 0 for an ignored or out-of-range label), and the
     gradient row is ``w (f softmax - onehot)`` with ``f = 1 + 2 z_coeff lse``.  ``z_coeff == 0``: the gradient of ``ce_fwd`` bit for bit."""
-    assert logits.dim() == 2 and logits.stride(1) == 1 and labels.dtype == torch.int64 and labels.is_contiguous()
-    rows = logits.shape[0]
-    assert labels.numel() == rows and row_loss.dtype == torch.float32 and row_loss.numel() >= rows
-    assert row_lse is None or (row_lse.dtype == torch.float32 and row_lse.numel() >= rows)
-    assert row_z.dtype == torch.float32 and row_z.is_contiguous() and row_z.numel() >= rows
-    assert row_weight is None or (row_weight.dtype == torch.float32 and row_weight.is_contiguous() and row_weight.numel() == rows
-                                  and row_weight.device == logits.device)
+    rows = _ce_rows(logits, labels, row_loss, row_lse, row_weight)
+    assert _row_buf_ok(row_z, rows)
     check(_lib.load().ssi_ce_fwd_z(ptr(logits), logits.stride(0), ptr(labels), ptr(row_weight), rows, vocab, ignore_index, float(z_coeff),
                                    ptr(row_loss), ptr(row_lse), ptr(row_z), int(write_grad), dtype_code(logits.dtype), stream_ptr()), "ssi_ce_fwd_z")
 
@@ -337,14 +342,8 @@ def ce_fwd_smooth(logits: Tensor, labels: Tensor, vocab: int, ignore_index: int,
     of ``ce_fwd_z`` bit for bit (``row_z`` may be ``None`` when ``z_coeff == 0``), ``row_u[r] = w_r (lse_r - mean_c x[r, c])`` (fp32, the
     coefficient NOT applied; 0 for an ignored or out-of-range label), and the gradient row is
     ``w (f softmax - (1 - e) onehot) - w e / vocab`` on the real columns.  ``smoothing == 0``: the gradient of ``ce_fwd_z`` bit for bit."""
-    assert logits.dim() == 2 and logits.stride(1) == 1 and labels.dtype == torch.int64 and labels.is_contiguous()
-    rows = logits.shape[0]
-    assert labels.numel() == rows and row_loss.dtype == torch.float32 and row_loss.numel() >= rows
-    assert row_lse is None or (row_lse.dtype == torch.float32 and row_lse.numel() >= rows)
-    assert row_u.dtype == torch.float32 and row_u.is_contiguous() and row_u.numel() >= rows
-    assert row_z is None or (row_z.dtype == torch.float32 and row_z.is_contiguous() and row_z.numel() >= rows)
-    assert row_weight is None or (row_weight.dtype == torch.float32 and row_weight.is_contiguous() and row_weight.numel() == rows
-                                  and row_weight.device == logits.device)
+    rows = _ce_rows(logits, labels, row_loss, row_lse, row_weight)
+    assert _row_buf_ok(row_u, rows) and (row_z is None or _row_buf_ok(row_z, rows))
     check(_lib.load().ssi_ce_fwd_smooth(ptr(logits), logits.stride(0), ptr(labels), ptr(row_weight), rows, vocab, ignore_index, float(smoothing),
                                         float(z_coeff), ptr(row_loss), ptr(row_lse), ptr(row_u), ptr(row_z), int(write_grad),
                                         dtype_code(logits.dtype), stream_ptr()), "ssi_ce_fwd_smooth")
@@ -361,14 +360,8 @@ def ce_fwd_metrics(logits: Tensor, labels: Tensor, vocab: int, ignore_index: int
                    row_rank: Tensor, row_weight: Tensor | None = None) -> None:
     """Forward-only ``ce_fwd`` (``write_grad=False``; ``row_loss`` and ``row_lse`` bit for bit) that also writes the unweighted ``row_nll`` (fp32)
     and ``row_rank`` (int32): the label's position in a stable descending sort of its row, -1 for an ignored or out-of-range label."""
-    assert logits.dim() == 2 and logits.stride(1) == 1 and labels.dtype == torch.int64 and labels.is_contiguous()
-    rows = logits.shape[0]
-    assert labels.numel() == rows and row_loss.dtype == torch.float32 and row_loss.numel() >= rows
-    assert row_lse is None or (row_lse.dtype == torch.float32 and row_lse.numel() >= rows)
-    assert row_nll.dtype == torch.float32 and row_nll.is_contiguous() and row_nll.numel() >= rows
-    assert row_rank.dtype == torch.int32 and row_rank.is_contiguous() and row_rank.numel() >= rows
-    assert row_weight is None or (row_weight.dtype == torch.float32 and row_weight.is_contiguous() and row_weight.numel() == rows
-                                  and row_weight.device == logits.device)
+    rows = _ce_rows(logits, labels, row_loss, row_lse, row_weight)
+    assert _row_buf_ok(row_nll, rows) and _row_buf_ok(row_rank, rows, torch.int32)
     check(_lib.load().ssi_ce_fwd_metrics(ptr(logits), logits.stride(0), ptr(labels), ptr(row_weight), rows, vocab, ignore_index, ptr(row_loss),
                                          ptr(row_lse), ptr(row_nll), ptr(row_rank), dtype_code(logits.dtype), stream_ptr()), "ssi_ce_fwd_metrics")
 

@@ -113,6 +113,43 @@ def resume_position(global_step: int, steps_per_epoch: int, gradient_accumulatio
     return epochs_run, steps_into_epoch * int(gradient_accumulation_steps)
 
 
+# The auxiliary parts of the objective: (name in the metric record, config key = Trainer attribute = ``compute_loss`` keyword).  A part is
+# active when its coefficient is > 0; the model leaves it as ``last_<name>``; the order here is the order everywhere below.
+AUX_PARTS = (("z_loss", "z_loss_coeff"), ("smooth_loss", "label_smoothing"))
+
+
+# The read-back row of one micro-batch, fp64, described here and nowhere else:
+#   [count per token kind ..., total (non-pad), valid labels, loss x valid labels, (active part x valid labels ...,) bad labels, bad positions]
+def build_row(counts: Tensor, loss: Tensor, aux: dict[str, Tensor], bad_labels: Tensor, bad_positions: Tensor, parts: tuple[str, ...]) -> Tensor:
+    """``counts``: per kind ..., total, valid labels, as ``count_token_types_async`` leaves them; every other piece a scalar tensor."""
+    scalars = (loss, *(aux[name] for name in parts), bad_labels, bad_positions)
+    return torch.cat((counts.to(torch.float64), *(t.detach().to(torch.float64).reshape(1) for t in scalars)))
+
+
+def split_row(host: list[float], kinds: list[str], parts: tuple[str, ...]):
+    """A row of ``build_row`` on the host -> ``(counts by kind and "total", n_valid, loss, aux by part, bad_labels, bad_positions)``."""
+    assert len(host) == len(kinds) + 5 + len(parts), (len(host), kinds, parts)
+    it = iter(host)
+    counts = {tt: int(next(it)) for tt in (*kinds, "total")}
+    n_valid, loss = int(next(it)), float(next(it))
+    aux = {name: float(next(it)) for name in parts}
+    return counts, n_valid, loss, aux, int(next(it)), int(next(it))
+
+
+# The window's scalars that data-parallel ranks sum in one collective: [tokens, loss, refused ids, count per kind ..., active part ...]
+def pack_window_scalars(n_tokens: int, loss: float, n_bad: int, type_counts: dict[str, int], aux: dict[str, float], parts: tuple[str, ...]) -> list[float]:
+    return [float(n_tokens), float(loss), float(n_bad), *(float(type_counts[k]) for k in sorted(type_counts)), *(float(aux[name]) for name in parts)]
+
+
+def unpack_window_scalars(values: list[float], kinds: list[str], parts: tuple[str, ...]):
+    """``pack_window_scalars`` after the sum -> ``(n_tokens, loss, n_bad, type_counts, aux)``; ``kinds``: the sorted keys that were packed."""
+    assert len(values) == 3 + len(kinds) + len(parts), (len(values), kinds, parts)
+    it = iter(values)
+    n_tokens, loss, n_bad = int(round(next(it))), float(next(it)), int(round(next(it)))
+    type_counts = {k: int(round(next(it))) for k in kinds}
+    return n_tokens, loss, n_bad, type_counts, {name: float(next(it)) for name in parts}
+
+
 class Trainer:
     """Usage (as the reference): ``t = Trainer(cfg); t.setup(); t.train(); t.cleanup()``."""
 
@@ -136,9 +173,9 @@ class Trainer:
         self.dev_metrics: dict[str, Any] | None = None         # per-token-type keys of the last evaluation (``eval_token_metrics``)
         self.dev_pairs: dict[str, Any] | None = None           # dev_pair_acc, dev_pair_acc_mean, dev_pair_n of the last evaluation (``eval_pairs``)
         self.z_loss_coeff = 0.0                                # ``z_loss_coeff`` of the config (``setup``); 0: no z-loss anywhere
-        self._z_loss_running = 0.0                             # the window's z part (x valid labels), beside ``loss_running``
         self.label_smoothing = 0.0                             # ``label_smoothing`` of the config (``setup``); 0: plain cross-entropy
-        self._smooth_loss_running = 0.0                        # the window's uniform part (e applied, x valid labels), beside ``_z_loss_running``
+        self._aux_parts: tuple[str, ...] = ()                  # the active ones of ``AUX_PARTS``, by name (``setup``)
+        self._aux_running: dict[str, float] = {}               # the window's sum of each (coefficient applied, x valid labels), beside ``loss_running``
         for name in self._FILLED_BY_SETUP:
             setattr(self, name, None)
         for name, zero in self._COUNTERS.items():
@@ -157,26 +194,38 @@ class Trainer:
             return
         pending, self._pending_readbacks = self._pending_readbacks, []
         rows = torch.stack([row for row, _ in pending]).tolist()  # the window's one host sync
+        counts, n_valid, self._loss_running, bad = self._add_rows(rows, [n for _, n in pending], self._loss_running, self._aux_running)
+        self._num_tokens_step += n_valid
+        for tt, c in counts.items():
+            self._type_counts_window[tt] += c
+        for what, n in bad.items():
+            self._bad_inputs_window[what] += n
+        if self.grad_sync is None:  # alone: fail here; data parallel: at the window's scalar all-reduce, on EVERY rank (a rank that raised
+            self._raise_on_bad_inputs(self._bad_inputs_window)  # alone would leave the others blocked in their collectives)
+
+    def _add_rows(self, rows: list[list[float]], positions: list[int], loss: float, aux: dict[str, float]):
+        """Host rows of micro-batches (``split_row``; ``positions``: token positions in each) into the cumulative token-type counts, onto
+        ``loss`` and into ``aux``, row by row: ``(their counts by kind, their valid labels, loss, the ids the kernels refused by kind)``."""
         kinds = list(self.token_type_ranges)
-        for host, (_, n_positions) in zip(rows, pending):
-            counts = {tt: int(c) for tt, c in zip(kinds + ["total"], host)}
+        counts_sum: defaultdict[str, int] = defaultdict(int)
+        bad: defaultdict[str, int] = defaultdict(int)
+        n_valid_sum = 0
+        for host, n_positions in zip(rows, positions):
+            counts, n_valid, row_loss, row_aux, bad_labels, bad_positions = split_row(host, kinds, self._aux_parts)
             for tt, c in counts.items():
                 self._token_type_counts_total[tt] += c
-                self._type_counts_window[tt] += c
-            self._num_tokens_step += int(host[len(kinds) + 1])
-            self._loss_running += float(host[len(kinds) + 2])
-            if self.z_loss_coeff > 0.0:
-                self._z_loss_running += float(host[len(kinds) + 3])
-            if self.label_smoothing > 0.0:
-                self._smooth_loss_running += float(host[len(kinds) + 3 + int(self.z_loss_coeff > 0.0)])
+                counts_sum[tt] += c
+            n_valid_sum += n_valid
+            loss += row_loss
+            for name, v in row_aux.items():
+                aux[name] += v
             # ids outside the vocabulary: torch's embedding / cross_entropy would device-assert (the HIP kernels write zeros and count);
             # the token-type ranges partition [0, V), so a token outside them shows up as a short sum; positions beyond the RoPE table are
             # clamped by the kernel and counted
-            self._bad_inputs_window["labels outside [0, vocab_size)"] += int(host[-2])
-            self._bad_inputs_window["token ids outside [0, vocab_size)"] += n_positions - sum(counts[tt] for tt in kinds)
-            self._bad_inputs_window["input_pos entries outside the RoPE table"] += int(host[-1])
-        if self.grad_sync is None:  # alone: fail here; data parallel: at the window's scalar all-reduce, on EVERY rank (a rank that raised
-            self._raise_on_bad_inputs(self._bad_inputs_window)  # alone would leave the others blocked in their collectives)
+            bad["labels outside [0, vocab_size)"] += bad_labels
+            bad["token ids outside [0, vocab_size)"] += n_positions - sum(counts[tt] for tt in kinds)
+            bad["input_pos entries outside the RoPE table"] += bad_positions
+        return counts_sum, n_valid_sum, loss, bad
 
     @property
     def num_tokens_step(self) -> int:
@@ -210,6 +259,8 @@ class Trainer:
         validate_train_cfg(self.cfg)
         self.z_loss_coeff = float(self.cfg.get("z_loss_coeff", 0.0))
         self.label_smoothing = float(self.cfg.get("label_smoothing", 0.0))
+        self._aux_parts = tuple(name for name, key in AUX_PARTS if getattr(self, key) > 0.0)
+        self._aux_running = dict.fromkeys(self._aux_parts, 0.0)
         set_seed(seed=SEED, debug_mode=self.cfg.get("debug_mode"))
         self.device = get_device(self.cfg.device)
         self.dtype = get_dtype(self.cfg.dtype)
@@ -457,28 +508,16 @@ class Trainer:
         # (not in the reference) z_loss_coeff > 0: the objective gains the z-loss; its two parts are left on the model as scalars, and the
         # loss that is logged stays the cross-entropy part.  Only here: the dev loss never sees the coefficient
         # label_smoothing > 0 (not in the reference either): the same with the uniform part, ``last_smooth_loss``; both may be on at once
-        z_on, smooth_on = self.z_loss_coeff > 0.0, self.label_smoothing > 0.0
-        z_kw = {"z_loss_coeff": self.z_loss_coeff} if z_on else {}
-        if smooth_on:
-            z_kw["label_smoothing"] = self.label_smoothing
-        loss_batch = compute_loss(loss_inputs(batch), self.model, self.loss_fn, **z_kw) * n_valid  # mean over SHIFTED x UNSHIFTED count
+        options = {key: getattr(self, key) for name, key in AUX_PARTS if name in self._aux_parts}
+        loss_batch = compute_loss(loss_inputs(batch), self.model, self.loss_fn, **options) * n_valid  # mean over SHIFTED x UNSHIFTED count
         loss_batch.backward()
-        z_batch = smooth_batch = None
-        if z_on or smooth_on:
+        aux_batch = {name: getattr(self.model, "last_" + name).detach() * n_valid for name in self._aux_parts}
+        if aux_batch:
             loss_batch = self.model.last_ce_loss.detach() * n_valid
-        if z_on:
-            z_batch = self.model.last_z_loss.detach() * n_valid
-        if smooth_on:
-            smooth_batch = self.model.last_smooth_loss.detach() * n_valid
         if on_gpu:
             zero = torch.zeros(1, dtype=torch.float64, device=tokens.device)
             errs = [getattr(self.model, "label_errors", None), getattr(self.model, "position_errors", None)]
-            errs = [zero if e is None else e.detach().to(torch.float64).reshape(1) for e in errs]
-            # row = [count per token type ..., total (non-pad), valid labels, loss x valid labels, (z-loss x valid labels,)
-            #        (smoothing part x valid labels,) bad labels, bad positions]
-            parts = ([loss_batch.detach().to(torch.float64).reshape(1)] + ([z_batch.to(torch.float64).reshape(1)] if z_on else [])
-                     + ([smooth_batch.to(torch.float64).reshape(1)] if smooth_on else []))
-            row = torch.cat((counts_dev.to(torch.float64), *parts, *errs))
+            row = build_row(counts_dev, loss_batch, aux_batch, *(zero if e is None else e for e in errs), self._aux_parts)
             self._pending_readbacks.append((row, tokens.numel()))
             return
         for tt, c in counts_host.items():
@@ -486,10 +525,8 @@ class Trainer:
             self._type_counts_window[tt] += c
         self._num_tokens_step += int(n_valid.item())
         self._loss_running += float(loss_batch.item())
-        if z_on:
-            self._z_loss_running += float(z_batch.item())
-        if smooth_on:
-            self._smooth_loss_running += float(smooth_batch.item())
+        for name, part in aux_batch.items():
+            self._aux_running[name] += float(part.item())
 
     def _arm_optimizer(self, n_valid: Tensor, last_of_window: bool) -> None:
         """Round 5: AdamW under the window's last backward (``HipAdamW.overlap_with_backward``).  The window's token count — the divisor of
@@ -523,22 +560,17 @@ class Trainer:
         if self.grad_sync is not None:
             # one small collective: token count, running loss and the window's token-type counts (tokens_total is global, so the
             # per-type totals must be too: every rank adds what the OTHER ranks saw in this window)
-            kinds = sorted(self._type_counts_window)
-            summed = all_reduce_scalars([self.num_tokens_step, self.loss_running, float(sum(self._bad_inputs_window.values())),
-                                         *(self._type_counts_window[k] for k in kinds), *([self._z_loss_running] if self.z_loss_coeff > 0.0 else []),
-                                         *([self._smooth_loss_running] if self.label_smoothing > 0.0 else [])],
-                                        self.device, group=self.grad_sync.scalar_group)
-            self.num_tokens_step, self.loss_running = int(round(summed[0])), float(summed[1])
-            if self.z_loss_coeff > 0.0:
-                self._z_loss_running = float(summed[3 + len(kinds)])
-            if self.label_smoothing > 0.0:
-                self._smooth_loss_running = float(summed[3 + len(kinds) + int(self.z_loss_coeff > 0.0)])
-            for k, v in zip(kinds, summed[3:]):  # (zip stops at the kinds: the z and smoothing sums ride behind them)
-                self.token_type_counts_total[k] += int(round(v)) - self._type_counts_window[k]
+            mine = pack_window_scalars(self.num_tokens_step, self.loss_running, sum(self._bad_inputs_window.values()), self._type_counts_window,
+                                       self._aux_running, self._aux_parts)
+            summed = all_reduce_scalars(mine, self.device, group=self.grad_sync.scalar_group)
+            self.num_tokens_step, self.loss_running, bad_anywhere, type_counts, self._aux_running = unpack_window_scalars(
+                summed, sorted(self._type_counts_window), self._aux_parts)
+            for k, n in type_counts.items():
+                self.token_type_counts_total[k] += n - self._type_counts_window[k]
             self.grad_sync.finish(defer_last=self.cfg.clip_grad_norm is None)  # the embedding bucket lands under the AdamW of the rest
-            if summed[2] > 0:  # every rank sees the same sum, so every rank raises (after its reductions have drained)
+            if bad_anywhere > 0:  # every rank sees the same sum, so every rank raises (after its reductions have drained)
                 self.grad_sync.finish_deferred()
-                self._raise_on_bad_inputs(self._bad_inputs_window, anywhere=int(round(summed[2])))
+                self._raise_on_bad_inputs(self._bad_inputs_window, anywhere=bad_anywhere)
         self._type_counts_window.clear()
         self._bad_inputs_window.clear()
         window_tokens = self.num_tokens_step
@@ -611,22 +643,8 @@ class Trainer:
             n_rows, width = e["shape"]
             rows = e["host"][:n_rows * width].view(n_rows, width).tolist()
             self._lag_buffers.append(e["host"])
-            kinds = list(self.token_type_ranges)
-            bad: defaultdict[str, int] = defaultdict(int)
-            loss_sum, z_sum, smooth_sum, n_valid_device = 0.0, 0.0, 0.0, 0
-            for host_row, n_positions in zip(rows, e["positions"]):
-                counts = {tt: int(c) for tt, c in zip(kinds + ["total"], host_row)}
-                for tt, c in counts.items():
-                    self._token_type_counts_total[tt] += c
-                n_valid_device += int(host_row[len(kinds) + 1])
-                loss_sum += float(host_row[len(kinds) + 2])
-                if self.z_loss_coeff > 0.0:
-                    z_sum += float(host_row[len(kinds) + 3])
-                if self.label_smoothing > 0.0:
-                    smooth_sum += float(host_row[len(kinds) + 3 + int(self.z_loss_coeff > 0.0)])
-                bad["labels outside [0, vocab_size)"] += int(host_row[-2])
-                bad["token ids outside [0, vocab_size)"] += n_positions - sum(counts[tt] for tt in kinds)
-                bad["input_pos entries outside the RoPE table"] += int(host_row[-1])
+            aux_sum = dict.fromkeys(self._aux_parts, 0.0)
+            _, n_valid_device, loss_sum, bad = self._add_rows(rows, e["positions"], 0.0, aux_sum)
             self._raise_on_bad_inputs(bad)
             if n_valid_device != e["window_tokens"]:
                 raise RuntimeError(f"the device counted {n_valid_device} valid labels in a window the host counted {e['window_tokens']} in")
@@ -635,8 +653,7 @@ class Trainer:
             mean_loss = loss_sum / e["window_tokens"]
             if self._loss_log is not None:
                 self._loss_log.append(mean_loss)
-            self._log_metrics(e["epoch"], e["iter_idx"], mean_loss, snapshot=e, z_loss_to_log=z_sum / e["window_tokens"],
-                              smooth_loss_to_log=smooth_sum / e["window_tokens"])
+            self._log_metrics(e["epoch"], e["iter_idx"], mean_loss, snapshot=e, aux={name: v / e["window_tokens"] for name, v in aux_sum.items()})
 
     def _apply_window(self, window_tokens: int) -> None:
         """Gradients of the window -> parameters: mean over the window's (global) unshifted token count, optional global-norm clip, AdamW,
@@ -658,8 +675,7 @@ class Trainer:
         mean_loss = self.loss_running / window_tokens
         if self._loss_log is not None:
             self._loss_log.append(mean_loss)
-        self._log_metrics(epoch, iter_idx, mean_loss, z_loss_to_log=self._z_loss_running / window_tokens,
-                          smooth_loss_to_log=self._smooth_loss_running / window_tokens)
+        self._log_metrics(epoch, iter_idx, mean_loss, aux={name: v / window_tokens for name, v in self._aux_running.items()})
 
     def _evaluate(self) -> float:
         """The dev loss; with ``eval_token_metrics`` the per-token-type keys of the same pass are left in ``self.dev_metrics`` for the log record;
@@ -693,13 +709,13 @@ class Trainer:
         return out
 
     def _log_metrics(self, epoch: int, iter_idx: int, loss_to_log: float, snapshot: dict[str, Any] | None = None,
-                     z_loss_to_log: float = 0.0, smooth_loss_to_log: float = 0.0) -> None:
+                     aux: dict[str, float] | None = None) -> None:
         """One console line per optimizer step; the metric record (same keys as the reference logs to W&B, ``trainer.py:440-475``) every
         ``log_interval`` steps from rank 0; the dev loss joins it on steps that evaluate.  ``snapshot``: the step's values as they were when
         its window closed (``_optimizer_step_lagged`` logs a step after the next one has been launched); without one, the current state.
-        ``loss`` is always the cross-entropy part; with ``z_loss_coeff > 0`` the record also carries ``z_loss`` (coefficient applied, the
-        same normalisation), with ``label_smoothing > 0`` ``smooth_loss`` (likewise: ``objective = (1 - e) loss + smooth_loss + z_loss``), and
-        ``dev_loss`` stays the plain cross-entropy."""
+        ``loss`` is always the cross-entropy part; ``aux`` holds the active auxiliary parts by name: with ``z_loss_coeff > 0`` the record also
+        carries ``z_loss`` (coefficient applied, the same normalisation), with ``label_smoothing > 0`` ``smooth_loss`` (likewise:
+        ``objective = (1 - e) loss + smooth_loss + z_loss``), and ``dev_loss`` stays the plain cross-entropy."""
         if snapshot is None:
             now = self._t_last_arrival = time.perf_counter()
             snapshot = {"global_step": self.global_step, "window_tokens": self.num_tokens_step, "lr": get_lr(self.optimizer), "now": now,
@@ -723,10 +739,7 @@ class Trainer:
             "train_clock_time": (self.wall_clock_offset + snapshot["now"] - self.t_train_start) / 3600.0,
             "max_seq_len_step": snapshot["max_seq_len_step"],
         }
-        if self.z_loss_coeff > 0.0:
-            record["z_loss"] = z_loss_to_log
-        if self.label_smoothing > 0.0:
-            record["smooth_loss"] = smooth_loss_to_log
+        record.update({name: aux[name] for name in self._aux_parts})
         record.update({f"n_tokens.{kind}": n for kind, n in type_counts.items()})
         if self.cfg.clip_grad_norm is not None:
             record["grad_norm"] = None if snapshot["grad_norm"] is None else float(snapshot["grad_norm"])
@@ -746,7 +759,7 @@ class Trainer:
 
     def _reset_step_accumulators(self) -> None:
         self.loss_running, self.num_tokens_step, self.max_seq_len_step = 0.0, 0, 0
-        self._z_loss_running = self._smooth_loss_running = 0.0
+        self._aux_running = dict.fromkeys(self._aux_parts, 0.0)
         self._window_valid_dev, self._window_valid_host = None, 0
         self.t_step_start = time.perf_counter()
 

@@ -1,6 +1,6 @@
 """Bits of the cross-entropy kernels, for comparing two builds of the library: one SHA-256 per case over every output buffer of ``ce_fwd``
-(``write_grad`` 0 and 1, with and without row weights), ``ce_fwd_z`` (z = 0, 1e-4, 0.5), ``ce_fwd_metrics``, ``ce_reduce``,
-``ce_metrics_reduce`` and ``seq_score_reduce``.  Inputs come from the CPU with fixed seeds, so two runs that print the same digests computed
+(``write_grad`` 0 and 1, with and without row weights), ``ce_fwd_z`` (z = 0, 1e-4, 0.5), ``ce_fwd_smooth`` (e = 0, 0.1 at each of these z, and
+once without a ``row_z`` at z = 0), ``ce_fwd_metrics``, ``ce_reduce``, ``ce_metrics_reduce`` and ``seq_score_reduce``: all four entries.  Inputs come from the CPU with fixed seeds, so two runs that print the same digests computed
 the same bits:  tools/lib_ab.sh "python tools/ce_digest.py" default variants/libssi_<other>.so
 
 Cases: ``make_inputs`` of tests/test_ce_z_gpu.py at its ``SHAPES`` (24 rows: ignored, out-of-range and end labels, weights of 0 and 1; the
@@ -23,6 +23,7 @@ DEV = "cuda"
 BF16 = torch.bfloat16
 OTHER_CHUNKS = [(20_000, 20_480), (32_000, 32_768), (65_000, 65_536), (131_000, 131_072), (147_000, 147_456)]   # 3, 4, 8, 16, 18 chunks
 Z_COEFFS = (0.0, 1e-4, 0.5)
+SMOOTHINGS = (0.0, 0.1)
 TOPK = 5
 
 
@@ -70,6 +71,13 @@ def digest(vocab, logits, labels, w):
                 work, loss, lse, rz = logits.to(DEV), buf(), buf(), buf()
                 ops.ce_fwd_z(work, dlabels, vocab, -100, z, loss, lse, rz, wg, row_weight=weights)
                 add(work, loss, lse, rz)
+                for e in SMOOTHINGS:
+                    work, loss, lse, ru, rz = logits.to(DEV), buf(), buf(), buf(), buf()
+                    ops.ce_fwd_smooth(work, dlabels, vocab, -100, e, z, loss, lse, ru, rz, wg, row_weight=weights)
+                    add(work, loss, lse, ru, rz)
+            work, loss, lse, ru = logits.to(DEV), buf(), buf(), buf()
+            ops.ce_fwd_smooth(work, dlabels, vocab, -100, SMOOTHINGS[-1], 0.0, loss, lse, ru, None, wg, row_weight=weights)   # z = 0 needs no row_z
+            add(work, loss, lse, ru)
         work, loss, lse, nll, rank = logits.to(DEV), buf(), buf(), buf(), buf(torch.int32)
         ops.ce_fwd_metrics(work, dlabels, vocab, -100, loss, lse, nll, rank, row_weight=weights)
         add(work, loss, lse, nll, rank)
