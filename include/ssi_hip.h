@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 14 /* 14: + ssi_ce_fwd_smooth (label smoothing inside the cross-entropy kernels, beside the z-loss; opt-in)
+#define SSI_ABI_VERSION 15 /* 15: + ssi_ce_fwd_kl (KL against a frozen teacher's logits inside the cross-entropy kernels; opt-in)
+                           * 14: + ssi_ce_fwd_smooth (label smoothing inside the cross-entropy kernels, beside the z-loss; opt-in)
                            * 13: + ssi_seq_score_reduce (per-sequence sums of what ssi_ce_fwd_metrics wrote: likelihood scoring of packed rows)
                            * 12: + ssi_ce_fwd_z (cross-entropy with the auxiliary z-loss z * log^2 Z in its gradient; opt-in)
                            * 11: + ssi_adamw_step_sr, ssi_round_bf16_sr (bf16 AdamW whose three stores round stochastically, counter-based)
@@ -297,6 +298,28 @@ int ssi_ce_fwd_z(void* logits, int64_t ld, const int64_t* labels, const float* r
 int ssi_ce_fwd_smooth(void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,
                       int64_t ignore_index, float smoothing, float z_coeff, float* row_loss, float* row_lse, float* row_u, float* row_z,
                       int write_grad, int dtype, void* stream);
+/* ssi_ce_fwd_weighted with a penalty kl_coeff * KL(teacher || student) on the row's distribution (ABI v15; not in the reference, off by default:
+ * the trainer's teacher_kl_coeff).  `teacher` is a second [rows, ld_teacher] buffer of the same dtype, the logits of a frozen model on the same
+ * rows; it is read only and must not be `logits`.  `teacher_lse[r]` is its log-sum-exp over [0, vocab): an INPUT, what
+ * ssi_ce_fwd(teacher, ..., write_grad = 0, row_lse = teacher_lse) writes with the same labels (0 on a row without a valid label, skipped here).
+ * With x, lse, p, w as above, t the teacher row, q = exp(t - teacher_lse[r]), k = row_kl_weight[r] (NULL: w) and b = kl_coeff, for a row with
+ * a valid label:
+ *   row_loss[r], row_lse[r]  what ssi_ce_fwd_weighted writes, bit for bit (row_lse NULL ok): the same statements for max, exp-sum and lse;
+ *   row_kl[r]   = k sum_c q[c] ((t[c] - x[c]) - (teacher_lse[r] - lse))     = k KL(q || p), fp32, WITHOUT kl_coeff (required);
+ *   gradient    = (w + b k) p[c] - w [c == label] - b k q[c]                (if write_grad; over the logits, pad columns [vocab, ld) exactly 0).
+ * A row whose label is ignored or outside [0, vocab): row_loss = row_kl = 0 and a zero gradient row — the KL term lives on labelled rows only,
+ * so one n_valid divides every part.  The batch objective is (sum row_loss + kl_coeff sum row_kl) / n_valid: one ssi_ce_reduce per sum.
+ * kl_coeff must be finite and >= 0; NULL teacher, teacher_lse or row_kl, teacher == logits, ld_teacher < vocab or not a multiple of 8:
+ * SSI_ERR_ARG.  kl_coeff == 0 gives the buffer of ssi_ce_fwd_weighted bit for bit (minus an exact 0; row_kl is still written).  The pad columns
+ * of either buffer may hold anything.  bf16 buffers that both meet the register form's conditions, with ld_teacher == ld, take it: the student
+ * row lives in registers as before, and with both lse known ONE pass over the teacher row (16 bytes per lane and chunk, three chunks in
+ * flight) gives row_kl and the gradient — no second row in registers, no online rescaling.  Everything else takes the generic form, which sums
+ * row_kl in fp64 and takes the rounding of the two fp32 lse out of it: with Q = exp(t - teacher_lse[r]), S = sum Q and SP = sum exp(x - lse) (both 1
+ * up to that rounding), row_kl = k (sum_c Q[c] (t[c] - x[c]) / S - (teacher_lse[r] - lse) - log S + log SP), rounded to fp32 once.  Traffic:
+ * student read + write, teacher read twice (once by the lse launch, once here). */
+int ssi_ce_fwd_kl(void* logits, int64_t ld, const void* teacher, int64_t ld_teacher, const float* teacher_lse, const int64_t* labels,
+                  const float* row_weight, const float* row_kl_weight, int64_t rows, int64_t vocab, int64_t ignore_index, float kl_coeff,
+                  float* row_loss, float* row_lse, float* row_kl, int write_grad, int dtype, void* stream);
 /* Forward-only ssi_ce_fwd_weighted that also ranks the label (ABI v10; the dev set's loss and accuracy per token type, ssi/eval.py).  The logits
  * are read only.  row_loss and row_lse (NULL ok) are what ssi_ce_fwd_weighted(..., write_grad = 0) writes on the same inputs, bit for bit: the
  * same form (register-resident bf16 rows or the generic kernel) is chosen by the same predicate, with the same order of max, exp-sum and lse.

@@ -185,7 +185,7 @@ extern "C" int ssi_embed_bwd(const int64_t* tokens, const void* dout, void* dtab
 }
 
 // =====================================================================================================================
-// K9 cross-entropy over rows of [rows, ld] logits, four entries:
+// K9 cross-entropy over rows of [rows, ld] logits, five entries:
 //   ssi_ce_fwd(_weighted)  row_loss = w (lse - x[label]), row_lse; optional in-place gradient  w (softmax - onehot)
 //   ssi_ce_fwd_z           + the auxiliary z-loss z * log^2 Z (opt-in, z_loss_coeff of the trainer).  With lse = log Z and p = softmax:
 //                          row_z = w (lse lse)  (the coefficient is applied by the caller)
@@ -197,15 +197,28 @@ extern "C" int ssi_embed_bwd(const int64_t* tokens, const void* dout, void* dtab
 //                          rank[r] = #{c < vocab : x[c] > x[label]} + #{c < label : x[c] == x[label]}  — the label's position in a stable
 //                          descending sort of the row; rank == 0 <=> argmax(row) == label under the first-occurrence rule.  Compares on
 //                          the stored values: an exact integer.
+//   ssi_ce_fwd_kl          ssi_ce_fwd_weighted + b KL(teacher || student) against a frozen teacher's logits (opt-in, teacher_kl_coeff of the
+//                          trainer).  With t the teacher row, tlse its lse (an input: a forward-only ssi_ce_fwd on the teacher buffer),
+//                          q = exp(t - tlse), k the row's KL weight and bk = b k:
+//                          row_kl = k sum_c q[c] ((t[c] - x[c]) - (tlse - lse))  (the coefficient is applied by the caller)
+//                          grad[c] = (w + bk) p[c] - w [c == label] - bk q[c]
 // Two forms — generic (any dtype and shape; one 512-thread block per row, fp32 online log-sum-exp, the gradient or the rank from a second
 // read of the row out of L2 / Infinity Cache) and register-resident bf16 rows (the training step's form) — and in each form ONE body
 // templated on the entry's CeMode, ce_generic_body and ce_row_bf16_body: what an entry adds sits behind `if constexpr`, so the max, the
-// exp-sum and the lse are the same statements whatever the entry: row_loss and row_lse agree bit for bit across the four, and with z = 0
-// (f = 1 exactly) and e = 0 (times an exact 1, minus an exact 0) so does the gradient.  The __global__ kernels are wrappers, one per entry
+// exp-sum and the lse are the same statements whatever the entry: row_loss and row_lse agree bit for bit across the five, and with z = 0
+// (f = 1 exactly), e = 0 (times an exact 1, minus an exact 0) and b = 0 (minus an exact 0) so does the gradient.  The __global__ kernels are wrappers, one per entry
 // and form, that pass nullptr / 0 for what is not theirs: the instantiations an entry launches do not depend on what the other entries
-// need.  On the host the four entries share one launcher, ce_fwd_launch<MODE>; an entry keeps its own pointer and coefficient checks.
+// need.  On the host the five entries share one launcher, ce_fwd_launch<MODE>; an entry keeps its own pointer and coefficient checks.
 // =====================================================================================================================
-enum CeMode { CE_PLAIN, CE_Z, CE_SMOOTH, CE_METRICS };
+enum CeMode { CE_PLAIN, CE_Z, CE_SMOOTH, CE_METRICS, CE_KL };
+
+// what only CE_KL has (ssi_ce_fwd_kl): the frozen teacher's logits, their lse per row from a forward-only ssi_ce_fwd on that buffer, the
+// per-row weight k of the KL term (nullptr: the row's w), the coefficient b, and where row_kl goes.  One struct, defaulted: the bodies take it
+// last and the other four modes never name it.
+struct CeKl {
+    const void* teacher = nullptr; int64_t ld_teacher = 0; const float* teacher_lse = nullptr; const float* row_kl_weight = nullptr;
+    float beta = 0.f; float* row_kl = nullptr;
+};
 
 // a row takes part iff its label is not ignored AND inside [0, vocab)
 __device__ __forceinline__ bool ce_label_valid(int64_t label, int64_t vocab, int64_t ignore_index) {
@@ -297,14 +310,51 @@ __device__ __forceinline__ void ce_grad_row(T* lr, int64_t nvec, int64_t vocab, 
     }
 }
 
-// The body of all four generic kernels, one block per row; the kernels pass nullptr / 0 for what is not theirs (ome = 1 for CE_Z).  A row
+// CE_KL: one pass over the student row and the teacher row (both from L2 / Infinity Cache after the lse passes) gives, if write_grad, the
+// in-place gradient  w (p - onehot) + bk (p - q)  = (w + bk) p - w onehot - bk q,  bk = beta k, q = exp(t - tlse)  (bk = 0: plus an exact 0,
+// the values of CE_PLAIN), and this thread's share of three sums in fp64:
+//   acc[0] = sum_c Q[c] (t[c] - x[c]),   acc[1] = S = sum_c Q[c],  Q = exp(t - tlse),   acc[2] = SP = sum_c exp(x[c] - lse)
+// S and SP are what the two fp32 lse leave of the rows' normalisers (1 up to the rounding of each lse, 2.4e-7 at an lse of 6): the caller forms
+//   KL(q || p) = acc[0] / S - (tlse - lse) - log S + log SP
+// which is  sum_c q[c] ((t[c] - x[c]) - (tlse - lse))  with the two roundings taken out — this form is not the step's, and a KL of 1e-3
+// against a teacher close to the student is then good to 1e-8 where the plain sum stops at the lse's 3e-7.  The teacher row is read up to ITS
+// OWN ld (nvec_t vectors; both lds cover the vocabulary) and never written.
+template <typename T>
+__device__ __forceinline__ void ce_kl_row(T* lr, const T* tr, int64_t nvec, int64_t nvec_t, int64_t vocab, int64_t label, float lse, float tlse,
+                                          float w, float bk, int write_grad, double (&acc)[3]) {
+    constexpr int N = Vec16<T>::N;
+    acc[0] = acc[1] = acc[2] = 0.0;
+    for (int64_t v = threadIdx.x; v < nvec; v += 512) {
+        Vec16<T> a = load16(lr + v * N), o;
+        Vec16<T> b = a;  // beyond the teacher's row: columns that are not vocabulary, never read below
+        if (v < nvec_t) b = load16(tr + v * N);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const int64_t c = v * N + i;
+            float g = 0.f;
+            if (c < vocab) {
+                const float x = a.get(i), t = b.get(i);
+                const float p = expf(x - lse), q = expf(t - tlse);
+                const double Q = exp((double)t - (double)tlse);
+                acc[0] += Q * ((double)t - (double)x);
+                acc[1] += Q;
+                acc[2] += exp((double)x - (double)lse);
+                g = w * (p - (c == label ? 1.f : 0.f)) + bk * (p - q);
+            }
+            o.set(i, g);
+        }
+        if (write_grad) store16(lr + v * N, o);
+    }
+}
+
+// The body of all five generic kernels, one block per row; the kernels pass nullptr / 0 for what is not theirs (ome = 1 for CE_Z).  A row
 // without a valid label skips the passes and keeps lse = xl = sx = 0, w = 1, cnt = -1: every output below is then an exact 0, the rank -1.
 template <typename T, CeMode MODE>
 __device__ __forceinline__ void ce_generic_body(T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels, int64_t vocab,
                                                 int64_t ignore_index, float two_z, float ome, float e_over_v, float* __restrict__ row_loss,
                                                 float* __restrict__ row_lse, float* __restrict__ row_z, float* __restrict__ row_u,
                                                 float* __restrict__ row_nll, int32_t* __restrict__ row_rank, int write_grad,
-                                                const float* __restrict__ row_weight, float* red, int* redi) {
+                                                const float* __restrict__ row_weight, float* red, int* redi, const CeKl& kl = CeKl{}) {
     const int64_t row = blockIdx.x;
     T* lr = logits + row * ld;
     const int64_t label = labels[row];
@@ -329,7 +379,33 @@ __device__ __forceinline__ void ce_generic_body(T* __restrict__ logits, int64_t 
         }
         if constexpr (MODE == CE_METRICS) { row_nll[row] = lse - xl; row_rank[row] = cnt; }
     }
-    if constexpr (MODE != CE_METRICS) {  // the metrics form is forward only: it never writes the row
+    if constexpr (MODE == CE_KL) {  // its one pass runs forward-only too: row_kl comes from it
+        if (!valid) {
+            if (threadIdx.x == 0) kl.row_kl[row] = 0.f;
+            if (write_grad) ce_zero_row(lr, nvec);
+            return;
+        }
+        const float kw = kl.row_kl_weight ? kl.row_kl_weight[row] : w;
+        __syncthreads();  // lr[label] read above must precede the overwrite below
+        const float tlse = kl.teacher_lse[row];
+        double acc[3];
+        ce_kl_row<T>(lr, (const T*)kl.teacher + row * kl.ld_teacher, nvec, kl.ld_teacher / Vec16<T>::N, vocab, label, lse, tlse, w, kl.beta * kw,
+                     write_grad, acc);
+        __shared__ double redd[3][8];  // one slot per wave of the 512 threads; fixed order: the lanes' xor tree, then the waves in turn
+#pragma unroll
+        for (int q = 0; q < 3; ++q) acc[q] = wave_sum_f64(acc[q]);
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) redd[q][threadIdx.x >> 6] = acc[q];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double sum[3] = {0.0, 0.0, 0.0};
+            for (int q = 0; q < 3; ++q)
+                for (int i = 0; i < 8; ++i) sum[q] += redd[q][i];
+            kl.row_kl[row] = kw * (float)(sum[0] / sum[1] - ((double)tlse - (double)lse) - log(sum[1]) + log(sum[2]));
+        }
+    } else if constexpr (MODE != CE_METRICS) {  // the metrics form is forward only: it never writes the row
         if (!write_grad) return;
         if (!valid) { ce_zero_row(lr, nvec); return; }
         const float f = fmaf(two_z, lse, 1.f);
@@ -379,6 +455,16 @@ __global__ __launch_bounds__(512) void ce_fwd_metrics_kernel(const T* __restrict
                                    row_nll, row_rank, 0, row_weight, red, redi);
 }
 
+template <typename T>
+__global__ __launch_bounds__(512) void ce_kl_generic_kernel(T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                            int64_t vocab, int64_t ignore_index, CeKl kl, float* __restrict__ row_loss,
+                                                            float* __restrict__ row_lse, int write_grad,
+                                                            const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    ce_generic_body<T, CE_KL>(logits, ld, labels, vocab, ignore_index, 0.f, 1.f, 0.f, row_loss, row_lse, nullptr, nullptr, nullptr, nullptr,
+                              write_grad, row_weight, red, nullptr, kl);
+}
+
 // ---- bf16 rows held in registers (the training step's form) -------------------------------------------------------------------------------
 // One 1024-thread workgroup per CU walks rows; a row of NCH x 8192 logits (NCH = 17: 139 264 >= 133 376) lives in NCH 16-byte registers
 // per thread, so the log-sum-exp and the gradient both come from ONE read of the row: 2 passes over the logits (read + write back = 8.7 GB
@@ -387,7 +473,7 @@ __global__ __launch_bounds__(512) void ce_fwd_metrics_kernel(const T* __restrict
 // and ld - vocab < 8192: only the last two chunks can hold columns that are not vocabulary.  Straight-line body (the only branches are
 // workgroup-uniform and read-only on the row registers): with per-chunk branches hipcc spills the row.
 //
-// The body of all four row kernels; what an entry adds sits behind `if constexpr` on MODE, and the kernels pass nullptr / 0 for what is
+// The body of all five row kernels; what an entry adds sits behind `if constexpr` on MODE, and the kernels pass nullptr / 0 for what is
 // not theirs:
 //   CE_Z        one scalar per row.  |f| rides in the exponent's additive term beside log2 w (f = 0: log2 0 = -inf, every exp2 gives 0 —
 //               the row is -w on the label and 0 elsewhere).  The SIGN of f is applied to the packed result: the row computes
@@ -404,14 +490,23 @@ __global__ __launch_bounds__(512) void ce_fwd_metrics_kernel(const T* __restrict
 //               Every lane needs that logit before the pass; the label is workgroup-uniform and nothing is overwritten here, so each
 //               lane loads it itself from one address and nothing has to wait for it to land.  The pad columns are -inf in the
 //               registers and lie above every valid label: they are neither greater than a logit nor tie below the label.
+//   CE_KL       the teacher's row never lives in registers: with both lse known, the gradient loop reads the teacher's 16 bytes of this lane
+//               and chunk (same buffer addressing; ld_teacher == ld), forms q = exp2(t log2e - tlse log2e) and adds q ((t - x) - (tlse - lse))
+//               to the lane's share of row_kl; the gradient is  exp2(x log2e + nl) - w [c == label] - bk q  with log2 (w + bk) in nl beside
+//               -lse log2e, bk = beta k.  TD teacher chunks are in flight ahead of the one in use, in a ring of TD registers.  The pads are
+//               -inf in the row registers (t - x = inf, 0 inf = NaN) and 0 where the teacher's load lay beyond the row: in the last two
+//               chunks q and the product are selected per element with the `left` compare.  bk = 0: minus an exact 0 — CE_PLAIN bit for
+//               bit.  A row without a label: q = exp2(-inf) = 0 and bk = 0.  Forward-only the loop still runs, for row_kl, and stores nothing.
 
 template <int NCH, CeMode MODE, bool write_grad>
 __device__ __forceinline__ void ce_row_bf16_body(bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels, int64_t rows,
                                                  int64_t vocab, int64_t ignore_index, float two_z, float ome, float e_over_v,
                                                  float* __restrict__ row_loss, float* __restrict__ row_lse, float* __restrict__ row_z,
                                                  float* __restrict__ row_u, float* __restrict__ row_nll, int32_t* __restrict__ row_rank,
-                                                 const float* __restrict__ row_weight, float* red, int* redi) {
+                                                 const float* __restrict__ row_weight, float* red, int* redi, const CeKl& kl = CeKl{}) {
     static_assert(MODE != CE_METRICS || !write_grad, "the metrics form writes no gradient");
+    constexpr bool KL = MODE == CE_KL;
+    constexpr int TD = NCH < 3 ? NCH : 3;            // CE_KL: teacher chunks in flight
     constexpr bool WITH_F = MODE == CE_Z || MODE == CE_SMOOTH;  // the z-loss factor f and its sign flip
     constexpr bool SMOOTH = MODE == CE_SMOOTH;                  // ome = 1 - e, e_over_v = e / vocab (0 and unused otherwise)
     constexpr float LOG2E = 1.44269504088896340736f;
@@ -423,6 +518,7 @@ __device__ __forceinline__ void ce_row_bf16_body(bf16_t* __restrict__ logits, in
     const int vocab_i = (int)vocab;
     u32x4 x[NCH];
     auto rsrc_of = [&](int64_t row) { return __builtin_amdgcn_make_buffer_rsrc(logits + row * ld, 0, row_bytes, 0x00020000u); };
+    [[maybe_unused]] u32x4 tq[TD];                   // CE_KL: the ring of teacher chunks
     auto lo = [](unsigned u) { return __builtin_bit_cast(float, u << 16); };
     auto hi = [](unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); };
     // the passes each re-derive the fp32 values from the packed registers: without this opaque touch the compiler keeps all
@@ -447,8 +543,15 @@ __device__ __forceinline__ void ce_row_bf16_body(bf16_t* __restrict__ logits, in
         // a weighted row (ssi_ce_fwd_weighted): w * exp(x - lse) = exp2(x log2e - lse log2e + log2 w) — the weight rides in the exponent's
         // additive term at no cost per element; w = 1 (and no weights) adds an exact 0
         const float w = row_weight ? row_weight[row] : 1.f;
-        const float log2w = row_weight ? __log2f(w) : 0.f;
+        float log2w = row_weight ? __log2f(w) : 0.f;
         const __amdgpu_buffer_rsrc_t rs = rsrc_of(row);
+        // CE_KL: the row's k and bk = beta k; w + bk rides in the exponent where w does (beta = 0: w + 0 k = w)
+        [[maybe_unused]] float kw = 0.f, bk = 0.f, dl = 0.f, nq = -INFINITY, klacc = 0.f;
+        [[maybe_unused]] __amdgpu_buffer_rsrc_t rt = rs;
+        if constexpr (KL) {
+            kw = kl.row_kl_weight ? kl.row_kl_weight[row] : w;
+            rt = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>((const bf16_t*)kl.teacher) + row * ld, 0, row_bytes, 0x00020000u);
+        }
         // columns that are not vocabulary (the pad columns [vocab, ld), and beyond the row where the loads returned 0) become -inf
         // once, in the registers: max, exp-sum, gradient (exp2(-inf) = 0) and rank then need no column test at all
 #pragma unroll
@@ -476,6 +579,10 @@ __device__ __forceinline__ void ce_row_bf16_body(bf16_t* __restrict__ logits, in
             // block_max only orders issue.  Free here: the row registers the max just consumed were the only other loads in flight.
             if constexpr (MODE != CE_METRICS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             const float gm = block_max(m, red);
+            if constexpr (KL) {  // the first teacher chunks fly under the exp-sum pass (issued after the wait above, which they would lengthen)
+#pragma unroll
+                for (int i = 0; i < TD; ++i) tq[i] = __builtin_amdgcn_raw_buffer_load_b128(rt, voff, i * CHUNK * 2, 2 /* nt */);
+            }
             opaque();
             const float nm = -gm * LOG2E;
             float s = 0.f;
@@ -531,19 +638,32 @@ __device__ __forceinline__ void ce_row_bf16_body(bf16_t* __restrict__ logits, in
                 }
                 if constexpr (MODE == CE_METRICS) { row_nll[row] = lse - xl; row_rank[row] = cnt; }
             }
-            nl = -lse * LOG2E + log2w;
+            if constexpr (KL) {
+                const float tlse = kl.teacher_lse[row];
+                bk = kl.beta * kw;
+                log2w = __log2f(w + bk);
+                dl = tlse - lse;
+                nq = -tlse * LOG2E;
+            }
+            nl = fmaf(-lse, LOG2E, log2w);  // (said as the fma it is compiled to: every mode forms the same nl, whatever else uses lse)
             if constexpr (WITH_F) {
                 const float f = fmaf(two_z, lse, 1.f);
                 nl += __log2f(fabsf(f));  // z = 0: f = 1 and this term an exact 0 — the nl of CE_PLAIN
                 if constexpr (SMOOTH) { wl = w * ome; wus = w * e_over_v; }  // e = 0: w and 0, exactly
                 if (f < 0.f) { wl = -wl; wus = -wus; flip = 0x80008000u; }
             }
-        } else if (tid == 0) {
+        } else {
+            if constexpr (KL) {  // no teacher loads for this row: defined values for the loop, whose q is exp2(-inf) = 0
+#pragma unroll
+                for (int i = 0; i < TD; ++i) tq[i] = u32x4{0u, 0u, 0u, 0u};
+            }
+            if (tid == 0) {
             row_loss[row] = 0.f;
             if (row_lse) row_lse[row] = 0.f;
             if constexpr (MODE == CE_Z) row_z[row] = 0.f;
             if constexpr (SMOOTH) { if (row_z) row_z[row] = 0.f; row_u[row] = 0.f; }
             if constexpr (MODE == CE_METRICS) { row_nll[row] = 0.f; row_rank[row] = -1; }
+            }
         }
         opaque();
         // ---- gradient softmax - onehot, written over the logits; each register then takes the next row's chunk (past the last row:
@@ -552,7 +672,36 @@ __device__ __forceinline__ void ce_row_bf16_body(bf16_t* __restrict__ logits, in
         const __amdgpu_buffer_rsrc_t rn = rsrc_of(next < rows ? next : row);
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
-            if (write_grad) {
+            if constexpr (KL) {
+                const u32x4 tc = tq[c % TD];
+                const int left = vocab_i - c * CHUNK - col0;  // as in the masking loop; read in the last two chunks only
+                const int h = hot - c * CHUNK;
+                float g[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float xe = (e & 1) ? hi(x[c][e >> 1]) : lo(x[c][e >> 1]);
+                    const float te = (e & 1) ? hi(tc[e >> 1]) : lo(tc[e >> 1]);
+                    float q = __builtin_amdgcn_exp2f(fmaf(te, LOG2E, nq));
+                    float term = q * ((te - xe) - dl);
+                    if (c >= NCH - 2) {  // a pad column or beyond the row: neither its q nor its NaN / inf product counts
+                        q = e < left ? q : 0.f;
+                        term = e < left ? term : 0.f;
+                    }
+                    klacc += term;
+                    if (write_grad) {
+                        const float pe = __builtin_amdgcn_exp2f(fmaf(xe, LOG2E, nl)) - (e == h ? wl : 0.f);
+                        g[e] = pe - bk * q;
+                    }
+                }
+                if (write_grad) {
+                    bf16x8 ob;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) ob[e] = (bf16_t)g[e];
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ob), rs, voff, c * CHUNK * 2, 2 /* nt: streamed once */);
+                }
+                // this ring register takes the teacher chunk TD ahead (valid or not: the loads of a row without a label are never used)
+                if (c + TD < NCH) tq[c % TD] = __builtin_amdgcn_raw_buffer_load_b128(rt, voff, (c + TD) * CHUNK * 2, 2 /* nt */);
+            } else if (write_grad) {
                 float g[8];
 #pragma unroll
                 for (int d = 0; d < 4; ++d) {
@@ -581,6 +730,10 @@ __device__ __forceinline__ void ce_row_bf16_body(bf16_t* __restrict__ logits, in
             }
             x[c] = __builtin_amdgcn_raw_buffer_load_b128(rn, voff, c * CHUNK * 2, 2 /* nt */);
             __builtin_amdgcn_sched_barrier(0);  // one chunk at a time: a hoisted next-row load would need a register of its own
+        }
+        if constexpr (KL) {  // the lanes' shares of row_kl, summed under the next row's loads
+            const float skl = block_sum(klacc, red);
+            if (tid == 0) kl.row_kl[row] = valid ? kw * skl : 0.f;
         }
     }
 }
@@ -616,6 +769,16 @@ __global__ __launch_bounds__(1024, 4) void ce_row_bf16_smooth_kernel(bf16_t* __r
                                                  row_u, nullptr, nullptr, row_weight, red, nullptr);
 }
 
+template <int NCH, bool write_grad>
+__global__ __launch_bounds__(1024, 4) void ce_kl_row_bf16_kernel(bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                                 int64_t rows, int64_t vocab, int64_t ignore_index, CeKl kl,
+                                                                 float* __restrict__ row_loss, float* __restrict__ row_lse,
+                                                                 const float* __restrict__ row_weight) {
+    __shared__ float red[16];
+    ce_row_bf16_body<NCH, CE_KL, write_grad>(logits, ld, labels, rows, vocab, ignore_index, 0.f, 1.f, 0.f, row_loss, row_lse, nullptr, nullptr,
+                                             nullptr, nullptr, row_weight, red, nullptr, kl);
+}
+
 template <int NCH>
 __global__ __launch_bounds__(1024, 4) void ce_row_bf16_metrics_kernel(const bf16_t* __restrict__ logits, int64_t ld,
                                                                       const int64_t* __restrict__ labels, int64_t rows, int64_t vocab,
@@ -638,7 +801,7 @@ static int ce_num_cus() {
     return n;
 }
 
-// the one predicate of the four entries: the same inputs take the same form in each
+// the one predicate of the five entries: the same inputs take the same form in each
 static bool ce_row_form(int dtype, const void* logits, int64_t ld, int64_t vocab) {
     const int64_t chunks = ssi_cdiv(ld, 8192);
     return dtype == SSI_BF16 && ((uintptr_t)logits & 15) == 0 && ld - vocab < 8192 && ld * 2 < (1LL << 31) &&
@@ -662,6 +825,7 @@ struct CeArgs {
     float two_z = 0.f, ome = 1.f, e_over_v = 0.f;  // CE_Z, CE_SMOOTH: 2 z;  CE_SMOOTH: 1 - e, e / vocab
     float *row_z = nullptr, *row_u = nullptr;      // CE_Z, CE_SMOOTH;  CE_SMOOTH
     float* row_nll = nullptr; int32_t* row_rank = nullptr;  // CE_METRICS
+    CeKl kl;                                                // CE_KL
 };
 
 // the row kernel of MODE with its own parameter list
@@ -674,6 +838,9 @@ template <CeMode MODE, int NCH, bool write_grad> static void ce_launch_row(const
     else if constexpr (MODE == CE_Z)
         hipLaunchKernelGGL((ce_row_bf16_z_kernel<NCH, write_grad>), grid, block, 0, a.stream, logits, a.ld, a.labels, a.rows, a.vocab, a.ignore_index,
                            a.two_z, a.row_loss, a.row_lse, a.row_z, a.row_weight);
+    else if constexpr (MODE == CE_KL)
+        hipLaunchKernelGGL((ce_kl_row_bf16_kernel<NCH, write_grad>), grid, block, 0, a.stream, logits, a.ld, a.labels, a.rows, a.vocab, a.ignore_index,
+                           a.kl, a.row_loss, a.row_lse, a.row_weight);
     else if constexpr (MODE == CE_SMOOTH)
         hipLaunchKernelGGL((ce_row_bf16_smooth_kernel<NCH, write_grad>), grid, block, 0, a.stream, logits, a.ld, a.labels, a.rows, a.vocab,
                            a.ignore_index, a.two_z, a.ome, a.e_over_v, a.row_loss, a.row_lse, a.row_z, a.row_u, a.row_weight);
@@ -692,6 +859,9 @@ template <CeMode MODE, typename T> static void ce_launch_generic(const CeArgs& a
     else if constexpr (MODE == CE_Z)
         hipLaunchKernelGGL(ce_fwd_z_kernel<T>, grid, block, 0, a.stream, logits, a.ld, a.labels, a.vocab, a.ignore_index, a.two_z, a.row_loss,
                            a.row_lse, a.row_z, a.write_grad, a.row_weight);
+    else if constexpr (MODE == CE_KL)
+        hipLaunchKernelGGL(ce_kl_generic_kernel<T>, grid, block, 0, a.stream, logits, a.ld, a.labels, a.vocab, a.ignore_index, a.kl, a.row_loss,
+                           a.row_lse, a.write_grad, a.row_weight);
     else if constexpr (MODE == CE_SMOOTH)
         hipLaunchKernelGGL(ce_fwd_smooth_kernel<T>, grid, block, 0, a.stream, logits, a.ld, a.labels, a.vocab, a.ignore_index, a.two_z, a.ome,
                            a.e_over_v, a.row_loss, a.row_lse, a.row_z, a.row_u, a.write_grad, a.row_weight);
@@ -700,11 +870,14 @@ template <CeMode MODE, typename T> static void ce_launch_generic(const CeArgs& a
                            a.row_lse, a.row_nll, a.row_rank, a.row_weight);
 }
 
-// what the four entries share: the common argument check, the form the input takes, the launch
+// what the five entries share: the common argument check, the form the input takes, the launch
 template <CeMode MODE> static int ce_fwd_launch(const CeArgs& a) {
     SSI_CHECK_ARG(a.logits && a.labels && a.row_loss && a.rows >= 0 && a.vocab > 0 && a.ld >= a.vocab && a.ld % 8 == 0);
     if (a.rows == 0) return SSI_OK;
-    if (ce_row_form(a.dtype, a.logits, a.ld, a.vocab)) {
+    bool row_form = ce_row_form(a.dtype, a.logits, a.ld, a.vocab);
+    // CE_KL: the row form reads the teacher with the student's addressing; any other pair of buffers takes the generic form
+    if constexpr (MODE == CE_KL) row_form = row_form && a.kl.ld_teacher == a.ld && ce_row_form(a.dtype, a.kl.teacher, a.kl.ld_teacher, a.vocab);
+    if (row_form) {
         SSI_CE_DISPATCH_CHUNKS(a.ld,
             if (a.write_grad) ce_launch_row<MODE, N, true>(a);  // (never so for CE_METRICS, whose one kernel ignores the flag)
             else ce_launch_row<MODE, N, false>(a));
@@ -759,6 +932,19 @@ extern "C" int ssi_ce_fwd_smooth(void* logits, int64_t ld, const int64_t* labels
     a.ome = 1.f - smoothing, a.e_over_v = smoothing / (float)vocab;  // fp32, in this order: the kernels form w * ome and w * e_over_v
     a.row_z = row_z, a.row_u = row_u;
     return ce_fwd_launch<CE_SMOOTH>(a);
+}
+
+extern "C" int ssi_ce_fwd_kl(void* logits, int64_t ld, const void* teacher, int64_t ld_teacher, const float* teacher_lse, const int64_t* labels,
+                             const float* row_weight, const float* row_kl_weight, int64_t rows, int64_t vocab, int64_t ignore_index,
+                             float kl_coeff, float* row_loss, float* row_lse, float* row_kl, int write_grad, int dtype, void* stream) {
+    SSI_CHECK_ARG(teacher && teacher_lse && row_kl && teacher != logits && ld_teacher >= vocab && ld_teacher % 8 == 0);
+    if (!ce_z_coeff_ok(kl_coeff)) {
+        ssi_set_error("ce_fwd_kl: kl_coeff must be finite and >= 0, got %g", (double)kl_coeff);
+        return SSI_ERR_ARG;
+    }
+    CeArgs a{logits, ld, labels, row_weight, rows, vocab, ignore_index, row_loss, row_lse, write_grad, dtype, (hipStream_t)stream};
+    a.kl = CeKl{teacher, ld_teacher, teacher_lse, row_kl_weight, kl_coeff, row_kl};
+    return ce_fwd_launch<CE_KL>(a);
 }
 
 extern "C" int ssi_ce_fwd_metrics(const void* logits, int64_t ld, const int64_t* labels, const float* row_weight, int64_t rows, int64_t vocab,

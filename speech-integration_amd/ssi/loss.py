@@ -82,12 +82,46 @@ def _uniform_term(logits, labels: Tensor, ignore_index: int) -> Tensor:
     return (u * valid).sum() / valid.sum()
 
 
+def kl_range_mask(labels: Tensor, ranges) -> Tensor | None:
+    """Where the KL term against the teacher lives: a bool tensor shaped like the (shifted) ``labels``, true where the label id lies in one of
+    the inclusive ``(lo, hi)`` pairs of ``ranges`` (as ``get_token_type_ranges`` gives them); ``None`` for ``ranges=None`` — every labelled
+    position.  A few elementwise ops on the labels' device, no sync."""
+    if ranges is None:
+        return None
+    mask = torch.zeros_like(labels, dtype=torch.bool)
+    for lo, hi in ranges:
+        mask |= (labels >= int(lo)) & (labels <= int(hi))
+    return mask
+
+
+def _kl_term(logits, teacher_logits, labels: Tensor, ignore_index: int, ranges) -> Tensor:
+    """``sum over valid labels (inside ``ranges``) of KL(softmax(teacher_i) || softmax(logits_i)) / n_valid`` in plain torch (the literal
+    route's teacher term, coefficient not applied); both logits as for ``_z_term``, chunked or not.  In fp64: against a teacher close to the
+    model a row's KL is a small difference of two log-sum-exps, and their fp32 rounding (2.4e-7 at an lse of 6) would be 1e-4 of it."""
+    x = torch.cat(list(logits), dim=1) if isinstance(logits, (list, tuple)) else logits
+    t = torch.cat(list(teacher_logits), dim=1) if isinstance(teacher_logits, (list, tuple)) else teacher_logits
+    kl = torch.nn.functional.kl_div(torch.log_softmax(x.double(), dim=-1), torch.log_softmax(t.double(), dim=-1), log_target=True,
+                                    reduction="none").sum(dim=-1)
+    valid = labels != ignore_index
+    inside = kl_range_mask(labels, ranges)
+    return (kl * (valid if inside is None else valid & inside)).sum() / valid.sum()
+
+
 def check_loss_options(who: str, label_smoothing: float, z_loss_coeff: float, label_metrics=None, seq_scores=None,
-                       under_grad: bool = False) -> tuple[float, float]:
+                       under_grad: bool = False, teacher_kl_coeff: float = 0.0) -> tuple[float, float]:
     """The rules of the loss options, said once for ``compute_loss`` and ``model.fused_loss`` (``who``): both coefficients as floats in their
     ranges; neither combines with ``label_metrics`` or ``seq_scores`` (dev-set metrics and sequence scores are plain cross-entropy); and, with
-    ``under_grad`` (a training forward of the fused route), those two forward-only forms are refused."""
-    e, z = float(label_smoothing), float(z_loss_coeff)
+    ``under_grad`` (a training forward of the fused route), those two forward-only forms are refused.  ``teacher_kl_coeff`` (finite, >= 0):
+    ``> 0`` combines with none of the four — the KL term has a cross-entropy kernel form of its own, without the z-loss and the smoothing."""
+    e, z, b = float(label_smoothing), float(z_loss_coeff), float(teacher_kl_coeff)
+    if not (math.isfinite(b) and b >= 0.0):
+        raise ValueError(f"teacher_kl_coeff must be finite and >= 0, got {b!r}")
+    if b > 0.0:
+        for name, on in (("label_metrics", label_metrics is not None), ("seq_scores", seq_scores is not None), ("z_loss_coeff", z > 0.0),
+                         ("label_smoothing", e > 0.0)):
+            if on:
+                raise ValueError(f"{who}: teacher_kl_coeff and {name} do not combine in one call (the KL term against the teacher has a "
+                                 "cross-entropy form of its own)")
     if not (math.isfinite(e) and 0.0 <= e < 1.0):
         raise ValueError(f"label_smoothing must be finite and in [0, 1), got {e!r}")
     if not (math.isfinite(z) and z >= 0.0):
@@ -106,7 +140,7 @@ def check_loss_options(who: str, label_smoothing: float, z_loss_coeff: float, la
 
 
 def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metrics=None, z_loss_coeff: float = 0.0,
-                 seq_scores=None, label_smoothing: float = 0.0) -> Tensor:
+                 seq_scores=None, label_smoothing: float = 0.0, teacher=None, teacher_kl_coeff: float = 0.0, teacher_kl_ranges=None) -> Tensor:
     """``label_metrics`` (``ssi.eval.LabelMetrics``, forward-only, not in the reference): loss and top-k hits of the shifted labels are added to it
     per token type — by the cross-entropy kernel on the fused route, in plain torch from the logits on the literal one.  The loss is unchanged.
     ``z_loss_coeff`` (not in the reference; finite, >= 0): ``> 0`` adds the auxiliary z-loss ``z sum_i w_i logsumexp(logits_i)^2 / n_valid`` —
@@ -119,8 +153,18 @@ def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metri
     ``F.cross_entropy(label_smoothing=e)``, ``(1 - e) ce + e mean_i (logsumexp(logits_i) - mean_c logits_ic)`` (+ the z part) — inside the
     cross-entropy kernel on the fused route, in plain torch on the literal one.  Either route leaves ``last_ce_loss`` (the plain
     cross-entropy) and ``last_smooth_loss`` (``e`` x the uniform part) on the model.  Not together with ``label_metrics`` or ``seq_scores``.
-    ``0.0``: exactly the loss of before."""
-    label_smoothing, z_loss_coeff = check_loss_options("compute_loss", label_smoothing, z_loss_coeff, label_metrics, seq_scores)
+    ``0.0``: exactly the loss of before.
+    ``teacher`` with ``teacher_kl_coeff`` (not in the reference; finite, >= 0): ``b > 0`` adds ``b sum_i k_i KL(teacher_i || model_i) / n_valid``
+    on the next-token distributions against a frozen second model run on the same batch — inside the cross-entropy kernel on the fused route
+    (``model.fused_loss``), in plain torch on ``teacher(...)`` logits on the literal one.  ``teacher_kl_ranges`` (inclusive ``(lo, hi)`` label-id
+    pairs, or ``None``: every labelled position) says where the term lives.  Either route leaves ``last_ce_loss`` and ``last_kl_loss``
+    (coefficient applied) on the model; the teacher gets no gradient.  Not together with the four options above.  ``0.0``: exactly the loss
+    of before, and the teacher is not run."""
+    label_smoothing, z_loss_coeff = check_loss_options("compute_loss", label_smoothing, z_loss_coeff, label_metrics, seq_scores,
+                                                       teacher_kl_coeff=teacher_kl_coeff)
+    teacher_kl_coeff = float(teacher_kl_coeff)
+    if teacher_kl_coeff > 0.0 and teacher is None:
+        raise ValueError("compute_loss: teacher_kl_coeff > 0 needs a teacher")
     labels = batch["labels"]
     ignore_index = loss_fn.ignore_index
     labels = torch.hstack((labels[..., 1:], torch.full_like(labels[..., -1:], ignore_index)))  # new tensor: batch untouched
@@ -140,6 +184,8 @@ def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metri
             extra["seq_scores"] = seq_scores
         if label_smoothing > 0.0:
             extra["label_smoothing"] = label_smoothing
+        if teacher_kl_coeff > 0.0:
+            extra.update(teacher=teacher, teacher_kl_coeff=teacher_kl_coeff, teacher_kl_ranges=teacher_kl_ranges)
         return model.fused_loss(batch["tokens"], labels, ignore_index, input_pos=batch.get("input_pos"), **extra)
     if batch.get("loss_weights") is not None:
         raise ValueError("loss_weights need the fused LM head + cross-entropy of the HIP decoder (model.fused_loss)")
@@ -156,6 +202,13 @@ def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metri
         seq_scores.add_logits(logits, labels, ignore_index)
     z_part = z_loss_coeff * _z_term(logits, labels, ignore_index) if z_loss_coeff > 0.0 else None
     u_part = label_smoothing * _uniform_term(logits, labels, ignore_index) if label_smoothing > 0.0 else None
+    kl_part = None
+    if teacher_kl_coeff > 0.0:
+        with torch.no_grad():
+            teacher_logits = teacher(tokens=batch["tokens"], mask=batch.get("mask"), encoder_input=batch.get("encoder_input"),
+                                     encoder_mask=batch.get("encoder_mask"), input_pos=batch.get("input_pos"))
+        kl_part = (teacher_kl_coeff * _kl_term(logits, teacher_logits, labels, ignore_index, teacher_kl_ranges)).float()
+        del teacher_logits
     if not isinstance(logits, list):
         labels = labels.reshape(-1)
         logits = logits.reshape(-1, logits.size(-1))
@@ -168,4 +221,7 @@ def compute_loss(batch: dict[str, Tensor], model, loss_fn: Callable, label_metri
     if z_part is not None:
         model.last_ce_loss, model.last_z_loss = ce.detach(), z_part.detach()
         loss = loss + z_part
+    if kl_part is not None:
+        model.last_ce_loss, model.last_kl_loss = ce.detach(), kl_part.detach()
+        loss = loss + kl_part
     return loss

@@ -33,7 +33,7 @@ from torch import Tensor, nn
 from . import _lib, ops
 from .constants import CROSS_ENTROPY_IGNORE_IDX, PRECISION_STR_TO_DTYPE
 from .llama_configs import ConfigLlama3_2
-from .loss import check_loss_options
+from .loss import check_loss_options, kl_range_mask
 from .ops import GEMM_NN, GEMM_NT, GEMM_TN
 
 LOGGER = logging.getLogger(__name__)
@@ -699,7 +699,8 @@ class HipLlamaDecoder(nn.Module):
 
     def fused_loss(self, tokens: Tensor, shifted_labels: Tensor, ignore_index: int = CROSS_ENTROPY_IGNORE_IDX,
                    input_pos: Optional[Tensor] = None, attn_plan=None, loss_weights: Optional[Tensor] = None,
-                   label_metrics=None, z_loss_coeff: float = 0.0, seq_scores=None, label_smoothing: float = 0.0) -> Tensor:
+                   label_metrics=None, z_loss_coeff: float = 0.0, seq_scores=None, label_smoothing: float = 0.0,
+                   teacher: Optional["HipLlamaDecoder"] = None, teacher_kl_coeff: float = 0.0, teacher_kl_ranges=None) -> Tensor:
         """Mean NLL over non-ignored (already shifted) labels with the LM head + CE fused: equals
         ``CEWithChunkedOutputLoss()(model(tokens, input_pos=...), shifted_labels)`` of the reference for any chunk count.
         ``input_pos`` ([B, S], restarting at 0 with every document): packed rows, block-causal attention.  ``attn_plan``
@@ -726,9 +727,24 @@ class HipLlamaDecoder(nn.Module):
         with ``u_i = lse_i - mean_c logits[i, c]``; its gradient comes from one cross-entropy launch (``ssi_ce_fwd_smooth``, with whatever
         ``z_loss_coeff`` is).  Left on the model: ``last_ce_loss`` (what a call without the option returns), ``last_smooth_loss``
         (``e`` x the mean of ``u``) and, with a z-loss, ``last_z_loss``.  Not together with ``label_metrics`` or ``seq_scores`` (plain
-        cross-entropy both).  ``0.0``: exactly the launches of before."""
+        cross-entropy both).  ``0.0``: exactly the launches of before.
+        ``teacher`` with ``teacher_kl_coeff`` (not in the reference; finite, >= 0): ``b > 0`` adds the penalty ``b KL(teacher || student)`` on
+        the next-token distribution against a frozen second ``HipLlamaDecoder`` of the same vocabulary, padding, device and dtype — what keeps
+        a fully fine-tuned model near its starting point, or distils a better checkpoint.  The teacher runs forward-only on the same padded
+        batch into ITS OWN arena (no gradient, nothing saved), a forward-only ``ssi_ce_fwd`` gives its lse per row, and ``ssi_ce_fwd_kl`` takes
+        the place of the cross-entropy launch: the result is ``(sum_i w_i nll_i + b sum_i k_i KL_i) / n_valid`` and the buffer holds the whole
+        objective's gradient.  ``teacher_kl_ranges`` (inclusive ``(lo, hi)`` label-id pairs, as ``get_token_type_ranges`` gives them): ``k_i = w_i``
+        where the shifted label lies in one of them and 0 elsewhere, made on the device without a sync; ``None``: every labelled row.  Left on
+        the model: ``last_ce_loss`` (what a call without the option returns) and ``last_kl_loss`` (coefficient applied, the same ``n_valid``).
+        Under grad and without.  Not together with ``label_metrics``, ``seq_scores``, ``z_loss_coeff > 0`` or ``label_smoothing > 0``: folding
+        the KL term into the z and smoothing forms of the kernel is left for later.  ``0.0``: exactly the launches of before; the teacher is
+        not run."""
         label_smoothing, z_loss_coeff = check_loss_options("fused_loss", label_smoothing, z_loss_coeff, label_metrics, seq_scores,
-                                                           under_grad=torch.is_grad_enabled() and self.training)
+                                                           under_grad=torch.is_grad_enabled() and self.training,
+                                                           teacher_kl_coeff=teacher_kl_coeff)
+        teacher_kl_coeff = float(teacher_kl_coeff)
+        if teacher is not None or teacher_kl_coeff > 0.0:
+            self._check_teacher(teacher)
         tokens = self._check_inputs(tokens, None, None, None, input_pos)
         if loss_weights is not None:
             if loss_weights.shape != tokens.shape:
@@ -737,22 +753,49 @@ class HipLlamaDecoder(nn.Module):
         tokens, input_pos, shifted_labels, loss_weights = self._right_pad(tokens, input_pos, shifted_labels, ignore_index, loss_weights)
         labels = shifted_labels.reshape(-1).contiguous()
         weights = None if loss_weights is None else loss_weights.reshape(-1).contiguous()
+        kl = None
+        if teacher_kl_coeff > 0.0:  # (teacher logits, their lse per row, coefficient, k per row or None) — the teacher's pass comes first
+            inside = kl_range_mask(labels, teacher_kl_ranges)
+            kl_weights = None if inside is None else (inside.to(torch.float32) if weights is None else weights * inside)
+            kl = (*teacher._teacher_rows(tokens, input_pos, labels, ignore_index), teacher_kl_coeff, kl_weights)
         if torch.is_grad_enabled() and self.training:
-            return _FusedLossFn.apply(self, tokens, labels, ignore_index, self._anchor, input_pos, attn_plan, weights, z_loss_coeff, label_smoothing)
+            return _FusedLossFn.apply(self, tokens, labels, ignore_index, self._anchor, input_pos, attn_plan, weights, z_loss_coeff, label_smoothing,
+                                      kl)
         hn = self._forward_hidden(tokens, save=False, input_pos=input_pos)
         seq = None if seq_scores is None else (seq_scores, tokens.shape[1])
         return self._ce_forward(hn, labels, ignore_index, write_grad=False, weights=weights, label_metrics=label_metrics,
-                                z_loss_coeff=z_loss_coeff, seq_scores=seq, label_smoothing=label_smoothing)[0]
+                                z_loss_coeff=z_loss_coeff, seq_scores=seq, label_smoothing=label_smoothing, kl=kl)[0]
+
+    def _check_teacher(self, teacher) -> None:
+        if not isinstance(teacher, HipLlamaDecoder) or teacher is self:
+            raise ValueError("fused_loss: teacher must be another HipLlamaDecoder")
+        for what in ("vocab_size", "vocab_pad", "device", "dtype"):
+            if getattr(teacher, what) != getattr(self, what):
+                raise ValueError(f"fused_loss: the teacher's {what} is {getattr(teacher, what)!r}, the model's {getattr(self, what)!r}")
+
+    @torch.no_grad()
+    def _teacher_rows(self, tokens: Tensor, input_pos: Optional[Tensor], labels: Tensor, ignore_index: int) -> tuple[Tensor, Tensor]:
+        """This model as a frozen teacher on an already right-padded batch: (logits ``[T, vocab_pad]``, their lse per row), forward-only, in
+        this model's own arena.  The lse is a launch of the existing forward-only cross-entropy kernel on the buffer: it reads the row once
+        into registers, and ``ssi_ce_fwd_kl`` then needs no online rescaling and no second row in registers."""
+        hn = self._forward_hidden(tokens, save=False, input_pos=input_pos)
+        logits = self._head_logits(hn, "logits.t")
+        T = hn.shape[0]
+        row_lse = self._arena.get("row_lse.t", (T,), torch.float32)
+        ops.ce_fwd(logits, labels, self.vocab_size, ignore_index, self._arena.get("row_loss.t", (T,), torch.float32), row_lse, False)
+        return logits, row_lse
 
     def _ce_forward(self, hn: Tensor, labels: Tensor, ignore_index: int, write_grad: bool,
                     weights: Optional[Tensor] = None, label_metrics=None, z_loss_coeff: float = 0.0,
-                    seq_scores=None, label_smoothing: float = 0.0) -> tuple[Tensor, Tensor, Tensor]:
+                    seq_scores=None, label_smoothing: float = 0.0, kl=None) -> tuple[Tensor, Tensor, Tensor]:
         """Tied head + cross-entropy: (mean loss, stats, logits buffer — which holds softmax - onehot when ``write_grad``).  The same
         three launches as the one-call ABI entry ``ssi_lmhead_ce_fwd`` (``ops.lmhead_ce_fwd``), issued one by one here so that ``bench.py``
         can time the head GEMM on its own.  ``z_loss_coeff > 0``: the z form of the cross-entropy launch (the buffer then holds
         ``f softmax - onehot``, ``f = 1 + 2 z lse``) and a second reduce over its ``row_z``; the loss returned is the sum of both parts.
         ``label_smoothing > 0``: the smoothing form (``ssi_ce_fwd_smooth``, which carries the z-loss too; the buffer then holds
         ``f softmax - (1 - e) onehot - e / vocab``) and one more reduce over its ``row_u``.
+        ``kl``: ``(teacher logits, teacher lse, coefficient b, k per row or None)``: the KL form (``ssi_ce_fwd_kl``; the buffer then holds
+        ``(w + b k) softmax - w onehot - b k q``) and one more reduce over its ``row_kl``.
         ``seq_scores``: ``(ssi.eval.SeqScores, padded row length)``."""
         T, e, z = hn.shape[0], label_smoothing, z_loss_coeff
         sfx = "" if write_grad else ".x"
@@ -760,10 +803,16 @@ class HipLlamaDecoder(nn.Module):
         row_loss = self._arena.get("row_loss" + sfx, (T,), torch.float32)
         row_u = self._arena.get("row_u" + sfx, (T,), torch.float32) if e > 0.0 else None
         row_z = self._arena.get("row_z" + sfx, (T,), torch.float32) if z > 0.0 else None
+        row_kl = self._arena.get("row_kl" + sfx, (T,), torch.float32) if kl is not None else None
         common = (logits, labels, self.vocab_size, ignore_index)
-        if e > 0.0 or z > 0.0:
+        if e > 0.0 or z > 0.0 or kl is not None:
             assert label_metrics is None and seq_scores is None
-        if e > 0.0:
+        if kl is not None:
+            assert e == 0.0 and z == 0.0
+            t_logits, t_lse, b, kl_weights = kl
+            ops.ce_fwd_kl(logits, t_logits, t_lse, labels, self.vocab_size, ignore_index, b, row_loss, None, row_kl, write_grad,
+                          row_weight=weights, row_kl_weight=kl_weights)
+        elif e > 0.0:
             ops.ce_fwd_smooth(*common, e, z, row_loss, None, row_u, row_z, write_grad, row_weight=weights)
         elif z > 0.0:
             ops.ce_fwd_z(*common, z, row_loss, None, row_z, write_grad, row_weight=weights)
@@ -783,7 +832,8 @@ class HipLlamaDecoder(nn.Module):
                 if scores.keep_rows:
                     scores.row_nll, scores.row_len = row_nll.clone(), row_len
         # one reduce per part of the objective, over the same labels: the same n_valid divides every part.  (row buffer, coefficient, attribute)
-        parts = [(row_loss, None, "last_ce_loss")] + [(buf, c, name) for buf, c, name in ((row_u, e, "last_smooth_loss"), (row_z, z, "last_z_loss"))
+        parts = [(row_loss, None, "last_ce_loss")] + [(buf, c, name) for buf, c, name in ((row_u, e, "last_smooth_loss"), (row_z, z, "last_z_loss"),
+                                                                            (row_kl, kl[2] if kl is not None else 0.0, "last_kl_loss"))
                                                        if buf is not None]
         out = torch.empty(4 * len(parts), dtype=torch.float32, device=self.device)
         for i, (buf, coeff, name) in enumerate(parts):
@@ -796,6 +846,8 @@ class HipLlamaDecoder(nn.Module):
             loss = out[0] * (1.0 - e) + self.last_smooth_loss
         if z > 0.0:
             loss = loss + self.last_z_loss
+        if kl is not None:
+            loss = loss + self.last_kl_loss
         return loss, out[:4], logits
 
 
@@ -836,10 +888,10 @@ class _FusedLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model: HipLlamaDecoder, tokens: Tensor, labels: Tensor, ignore_index: int, anchor: Tensor,
                 input_pos: Optional[Tensor] = None, attn_plan=None, weights: Optional[Tensor] = None, z_loss_coeff: float = 0.0,
-                label_smoothing: float = 0.0) -> Tensor:
+                label_smoothing: float = 0.0, kl=None) -> Tensor:
         hn = model._forward_hidden(tokens, save=True, input_pos=input_pos, attn_plan=attn_plan)
         loss, stats, dlogits = model._ce_forward(hn, labels, ignore_index, write_grad=True, weights=weights, z_loss_coeff=z_loss_coeff,
-                                                 label_smoothing=label_smoothing)
+                                                 label_smoothing=label_smoothing, kl=kl)
         ctx.model, ctx.gen = model, model._fwd_generation
         ctx.save_for_backward(hn, stats, dlogits)
         return loss.clone()
@@ -856,7 +908,7 @@ class _FusedLossFn(torch.autograd.Function):
         alpha = (grad_out.to(torch.float32).reshape(1) / stats[2:3]).contiguous()
         d_hn = m._head_backward(dlogits, hn, alpha)
         m._backward_hidden(d_hn, ctx.gen)
-        return None, None, None, None, torch.zeros_like(m._anchor), None, None, None, None, None
+        return None, None, None, None, torch.zeros_like(m._anchor), None, None, None, None, None, None
 
 
 # --------------------------------------------------------------------------------------------------------------------

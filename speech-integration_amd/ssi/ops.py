@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
 __all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "swiglu_fwd",
-           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "round_bf16_sr", "set_impl", "set_attn_impl", "attn_last_dispatch",
+           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "round_bf16_sr", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
 
@@ -347,6 +347,23 @@ def ce_fwd_smooth(logits: Tensor, labels: Tensor, vocab: int, ignore_index: int,
     check(_lib.load().ssi_ce_fwd_smooth(ptr(logits), logits.stride(0), ptr(labels), ptr(row_weight), rows, vocab, ignore_index, float(smoothing),
                                         float(z_coeff), ptr(row_loss), ptr(row_lse), ptr(row_u), ptr(row_z), int(write_grad),
                                         dtype_code(logits.dtype), stream_ptr()), "ssi_ce_fwd_smooth")
+
+
+def ce_fwd_kl(logits: Tensor, teacher: Tensor, teacher_lse: Tensor, labels: Tensor, vocab: int, ignore_index: int, kl_coeff: float,
+              row_loss: Tensor, row_lse: Tensor | None, row_kl: Tensor, write_grad: bool, row_weight: Tensor | None = None,
+              row_kl_weight: Tensor | None = None) -> None:
+    """``ce_fwd`` with ``kl_coeff * KL(teacher || student)`` in the gradient (``ssi_ce_fwd_kl``).  ``teacher`` holds a frozen model's logits on the
+    same rows (same dtype and device, its own row stride; read only) and ``teacher_lse`` what ``ce_fwd(teacher, ..., write_grad=False)`` wrote as
+    ``row_lse`` with the same labels.  ``row_loss`` and ``row_lse`` are those of ``ce_fwd`` bit for bit, ``row_kl[r] = k_r KL(q_r || p_r)`` (fp32,
+    the coefficient NOT applied; 0 for an ignored or out-of-range label) with ``k = row_kl_weight`` (``None``: the row's ``row_weight``), and the
+    gradient row is ``(w + b k) softmax - w onehot - b k q``.  ``kl_coeff == 0``: the gradient of ``ce_fwd`` bit for bit."""
+    rows = _ce_rows(logits, labels, row_loss, row_lse, row_weight)
+    assert teacher.dim() == 2 and teacher.stride(1) == 1 and teacher.shape == logits.shape and teacher.dtype == logits.dtype
+    assert teacher.device == logits.device and _row_buf_ok(teacher_lse, rows) and _row_buf_ok(row_kl, rows)
+    assert row_kl_weight is None or (_row_buf_ok(row_kl_weight, rows) and row_kl_weight.numel() == rows and row_kl_weight.device == logits.device)
+    check(_lib.load().ssi_ce_fwd_kl(ptr(logits), logits.stride(0), ptr(teacher), teacher.stride(0), ptr(teacher_lse), ptr(labels), ptr(row_weight),
+                                    ptr(row_kl_weight), rows, vocab, ignore_index, float(kl_coeff), ptr(row_loss), ptr(row_lse), ptr(row_kl),
+                                    int(write_grad), dtype_code(logits.dtype), stream_ptr()), "ssi_ce_fwd_kl")
 
 
 def ce_reduce(row_loss: Tensor, labels: Tensor, vocab: int, ignore_index: int, out: Tensor) -> None:

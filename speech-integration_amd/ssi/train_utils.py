@@ -108,6 +108,20 @@ def validate_train_cfg(cfg) -> None:
     e = cfg.get("label_smoothing", 0.0)
     if isinstance(e, bool) or not isinstance(e, (int, float)) or not math.isfinite(e) or not 0 <= e < 1:
         raise ValueError(f"config field 'label_smoothing' must be a finite number in [0, 1), got {e!r}")
+    b = cfg.get("teacher_kl_coeff", 0.0)
+    if isinstance(b, bool) or not isinstance(b, (int, float)) or not math.isfinite(b) or b < 0:
+        raise ValueError(f"config field 'teacher_kl_coeff' must be a finite number >= 0, got {b!r}")
+    if b > 0:
+        for name, value in (("z_loss_coeff", z), ("label_smoothing", e)):
+            if value > 0:
+                raise ValueError(f"config fields 'teacher_kl_coeff' and '{name}' do not combine: the KL term against the teacher has a "
+                                 "cross-entropy form of its own, without the z-loss and the smoothing")
+    kinds = cfg.get("teacher_kl_token_types")
+    if kinds is not None and (isinstance(kinds, (str, bytes)) or not all(isinstance(k, str) for k in kinds) or len(kinds) == 0):
+        raise ValueError(f"config field 'teacher_kl_token_types' must be null or a non-empty list of token type names, got {kinds!r}")
+    d = cfg.get("teacher_checkpoint_dir")
+    if d is not None and not isinstance(d, (str, os.PathLike)):
+        raise ValueError(f"config field 'teacher_checkpoint_dir' must be null or a path, got {d!r}")
 
 
 # training_state.pt (schema v1): key in the file -> name under which the trainer consumes it

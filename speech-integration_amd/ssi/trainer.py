@@ -116,6 +116,8 @@ def resume_position(global_step: int, steps_per_epoch: int, gradient_accumulatio
 # The auxiliary parts of the objective: (name in the metric record, config key = Trainer attribute = ``compute_loss`` keyword).  A part is
 # active when its coefficient is > 0; the model leaves it as ``last_<name>``; the order here is the order everywhere below.
 AUX_PARTS = (("z_loss", "z_loss_coeff"), ("smooth_loss", "label_smoothing"))
+# ... and the part that needs a second, frozen model (``Trainer.teacher``): same shape, after the two above wherever parts are listed
+TEACHER_PARTS = (("kl_loss", "teacher_kl_coeff"),)
 
 
 # The read-back row of one micro-batch, fp64, described here and nowhere else:
@@ -174,7 +176,10 @@ class Trainer:
         self.dev_pairs: dict[str, Any] | None = None           # dev_pair_acc, dev_pair_acc_mean, dev_pair_n of the last evaluation (``eval_pairs``)
         self.z_loss_coeff = 0.0                                # ``z_loss_coeff`` of the config (``setup``); 0: no z-loss anywhere
         self.label_smoothing = 0.0                             # ``label_smoothing`` of the config (``setup``); 0: plain cross-entropy
-        self._aux_parts: tuple[str, ...] = ()                  # the active ones of ``AUX_PARTS``, by name (``setup``)
+        self.teacher_kl_coeff = 0.0                            # ``teacher_kl_coeff`` of the config (``setup``); 0: no teacher is built
+        self.teacher = None                                    # the frozen model of the KL term (``_setup_teacher``): never optimised, wrapped or saved
+        self.teacher_kl_ranges: list[tuple[int, int]] | None = None  # label-id ranges of ``teacher_kl_token_types`` (None: every labelled position)
+        self._aux_parts: tuple[str, ...] = ()                  # the active ones of ``AUX_PARTS + TEACHER_PARTS``, by name (``setup``)
         self._aux_running: dict[str, float] = {}               # the window's sum of each (coefficient applied, x valid labels), beside ``loss_running``
         for name in self._FILLED_BY_SETUP:
             setattr(self, name, None)
@@ -259,7 +264,8 @@ class Trainer:
         validate_train_cfg(self.cfg)
         self.z_loss_coeff = float(self.cfg.get("z_loss_coeff", 0.0))
         self.label_smoothing = float(self.cfg.get("label_smoothing", 0.0))
-        self._aux_parts = tuple(name for name, key in AUX_PARTS if getattr(self, key) > 0.0)
+        self.teacher_kl_coeff = float(self.cfg.get("teacher_kl_coeff", 0.0))
+        self._aux_parts = tuple(name for name, key in AUX_PARTS + TEACHER_PARTS if getattr(self, key) > 0.0)
         self._aux_running = dict.fromkeys(self._aux_parts, 0.0)
         set_seed(seed=SEED, debug_mode=self.cfg.get("debug_mode"))
         self.device = get_device(self.cfg.device)
@@ -302,14 +308,47 @@ class Trainer:
         ck = {k: self.cfg.checkpointer[k] for k in self.cfg.checkpointer}
         self.checkpointer = make_checkpointer(**ck, model_expectations=self._llama_config.checkpoint_expectations)
         self._ckpt_dict = self.checkpointer.load_checkpoint()
-        self.model = setup_llama3_2_1b(cfg=self.cfg, llama_config=self._llama_config,
-                                       model_state_dict=self._ckpt_dict.get(MODEL_KEY), dtype_default=self.dtype,
-                                       device_default=self.device)
-        if self._ckpt_dict.get(MODEL_KEY) is None:
-            from .checkpoint import random_init_
-            random_init_(self.model, seed=SEED)
-        self.model.to(device=self.device)
+        self.model = self._build_model(self._ckpt_dict.get(MODEL_KEY))
         self.model.train()
+        if self.teacher_kl_coeff > 0.0:
+            self._setup_teacher(ck)
+
+    def _build_model(self, state_dict):
+        model = setup_llama3_2_1b(cfg=self.cfg, llama_config=self._llama_config, model_state_dict=state_dict, dtype_default=self.dtype,
+                                  device_default=self.device)
+        if state_dict is None:
+            from .checkpoint import random_init_
+            random_init_(model, seed=SEED)
+        model.to(device=self.device)
+        return model
+
+    def _setup_teacher(self, ck: dict) -> None:
+        """(not in the reference) The frozen model of ``teacher_kl_coeff``: built as the model is, from the weights under
+        ``teacher_checkpoint_dir`` (null: ``checkpointer.checkpoint_dir``, the directory this run's initial weights come from), in ``eval()``.
+        Only ``_train_step`` sees it: the optimizer, the data-parallel exchange and the checkpointer never do."""
+        from .checkpoint import make_checkpointer
+        kinds = self.cfg.get("teacher_kl_token_types")
+        if kinds is not None:
+            ranges = get_token_type_ranges(llama_config=self._llama_config)
+            unknown = [k for k in kinds if k not in ranges]
+            if unknown:
+                raise ValueError(f"teacher_kl_token_types names {unknown}: the token types of this vocabulary are {list(ranges)}")
+            self.teacher_kl_ranges = [tuple(ranges[k]) for k in kinds]
+        own = self.cfg.get("teacher_checkpoint_dir")
+        tk = {k: v for k, v in ck.items() if k != "training_state_checkpoint"}
+        if own is not None:
+            tk["checkpoint_dir"] = own
+            tk.pop("checkpoint_files", None)
+            tk.pop("config_json", None)
+        try:
+            sd = make_checkpointer(**tk, model_expectations=self._llama_config.checkpoint_expectations).load_checkpoint().get(MODEL_KEY)
+        except FileNotFoundError as err:
+            raise FileNotFoundError(f"teacher_kl_coeff > 0 needs the teacher's weights under teacher_checkpoint_dir "
+                                    f"(null: checkpointer.checkpoint_dir) = {tk.get('checkpoint_dir')!r}: {err}") from err
+        self.teacher = self._build_model(sd)
+        self.teacher.eval()
+        for p in self.teacher.parameters():
+            p.requires_grad_(False)
 
     def _setup_tokenizer(self) -> None:
         from .tokenizer import setup_llama3_tokenizer
@@ -508,7 +547,10 @@ class Trainer:
         # (not in the reference) z_loss_coeff > 0: the objective gains the z-loss; its two parts are left on the model as scalars, and the
         # loss that is logged stays the cross-entropy part.  Only here: the dev loss never sees the coefficient
         # label_smoothing > 0 (not in the reference either): the same with the uniform part, ``last_smooth_loss``; both may be on at once
-        options = {key: getattr(self, key) for name, key in AUX_PARTS if name in self._aux_parts}
+        # teacher_kl_coeff > 0 (not in the reference either): the KL term against the frozen teacher, ``last_kl_loss``; on its own
+        options = {key: getattr(self, key) for name, key in AUX_PARTS + TEACHER_PARTS if name in self._aux_parts}
+        if self.teacher is not None:
+            options.update(teacher=self.teacher, teacher_kl_ranges=self.teacher_kl_ranges)
         loss_batch = compute_loss(loss_inputs(batch), self.model, self.loss_fn, **options) * n_valid  # mean over SHIFTED x UNSHIFTED count
         loss_batch.backward()
         aux_batch = {name: getattr(self.model, "last_" + name).detach() * n_valid for name in self._aux_parts}
