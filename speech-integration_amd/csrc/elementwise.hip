@@ -68,39 +68,6 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const T* __restrict__ 
     }
 }
 
-// =====================================================================================================================
-template <typename T>
-__global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const T* __restrict__ x, const T* __restrict__ scale,
-                                                          T* __restrict__ y, float* __restrict__ rstd_out,
-                                                          int64_t rows, int dim, float eps) {
-    constexpr int N = Vec16<T>::N;
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const T* xr = x + row * dim;
-    T* yr = y + row * dim;
-    const int nvec = dim / N;
-    float ss = 0.f;
-    for (int v = lane; v < nvec; v += 64) {
-        Vec16<T> a = load16(xr + v * N);
-#pragma unroll
-        for (int i = 0; i < N; ++i) { float f = a.get(i); ss += f * f; }
-    }
-    ss = wave_sum(ss);
-    const float rstd = rsqrtf(ss / (float)dim + eps);
-    if (lane == 0 && rstd_out) rstd_out[row] = rstd;
-    for (int v = lane; v < nvec; v += 64) {
-        Vec16<T> a = load16(xr + v * N), w = load16(scale + v * N), o;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            // (x32 * rstd).type_as(x) * scale : round to storage type before the scale multiply
-            float xn = to_f32<T>(from_f32<T>(a.get(i) * rstd));
-            o.set(i, xn * w.get(i));
-        }
-        store16(yr + v * N, o);
-    }
-}
-
 // K2 RMSNorm backward.  Per wave: a strided set of rows; dscale partial sums kept per lane-column in registers and
 // reduced over the block's 4 waves through LDS, then written as one partial row per block.
 template <typename T, int MAXV>
