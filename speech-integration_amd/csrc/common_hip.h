@@ -69,12 +69,17 @@ template <typename T> __device__ __forceinline__ void ssi_swiglu_bwd_elem(float 
     dgate = (df * uf) * (sig * t);
 }
 
-// One RoPE pair, shared by ssi_rope_inplace and the QKV GEMM epilogue (same reason for switching contraction off; it is also
-// what the reference's unfused torch expression computes)
+// One RoPE pair, shared by ssi_rope_inplace and the QKV GEMM epilogue, which must agree bit for bit.  The library is built with
+// -ffp-contract=fast, under which the backend fuses a multiply into an add whatever the pragma says, and WHICH of the two products it
+// fuses depended on the surrounding code: the row kernel rounded x0 s and fused x1 c, the GEMM epilogue rounded x1 c and fused x0 s, and
+// o1 differed by one bf16 ulp in a few elements per million.  The fusion is therefore written out, in the form the GEMM epilogue has
+// always been compiled to (the training step runs that kernel; its results are unchanged bit for bit): both products with x1 are rounded,
+// both products with x0 are fused.
 __device__ __forceinline__ void ssi_rope_pair(float x0, float x1, float c, float s, float& o0, float& o1) {
 #pragma clang fp contract(off)
-    o0 = x0 * c - x1 * s;
-    o1 = x1 * c + x0 * s;
+    const float x1s = x1 * s, x1c = x1 * c;
+    o0 = __builtin_fmaf(x0, c, -x1s);
+    o1 = __builtin_fmaf(x0, s, x1c);
 }
 
 // 16-byte vector of storage elements: 4 floats or 8 bf16

@@ -242,7 +242,8 @@ def gemm_splitk(layout: int, a: Tensor, b: Tensor, c: Tensor, splits: int, works
     K = a.shape[1] if layout in (GEMM_NT, GEMM_NN) else a.shape[0]
     assert a.stride(1) == 1 and b.stride(1) == 1 and c.stride(1) == 1 and a.dtype == b.dtype == c.dtype
     if residual is not None:
-        assert residual.shape == c.shape and residual.stride() == c.stride() and residual.dtype == c.dtype and not accumulate
+        # together with `accumulate` the C entry takes the 8-wave scheme, whose reduction pass adds both (as the unsplit form does)
+        assert residual.shape == c.shape and residual.stride() == c.stride() and residual.dtype == c.dtype
     check(_lib.load().ssi_gemm_splitk(layout, M, N, K, ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(c), c.stride(0), ptr(residual),
                                       alpha, ptr(alpha_dev), int(accumulate), dtype_code(c.dtype), splits, ptr(workspace),
                                       workspace.numel() * workspace.element_size(), stream_ptr()), "ssi_gemm_splitk")
