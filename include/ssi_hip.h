@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 15 /* 15: + ssi_ce_fwd_kl (KL against a frozen teacher's logits inside the cross-entropy kernels; opt-in)
+#define SSI_ABI_VERSION 16 /* 16: + ssi_adamw_step_seg (AdamW over segments of the flat buffers with their own lr, weight decay and frozen flag; opt-in)
+                           * 15: + ssi_ce_fwd_kl (KL against a frozen teacher's logits inside the cross-entropy kernels; opt-in)
                            * 14: + ssi_ce_fwd_smooth (label smoothing inside the cross-entropy kernels, beside the z-loss; opt-in)
                            * 13: + ssi_seq_score_reduce (per-sequence sums of what ssi_ce_fwd_metrics wrote: likelihood scoring of packed rows)
                            * 12: + ssi_ce_fwd_z (cross-entropy with the auxiliary z-loss z * log^2 Z in its gradient; opt-in)
@@ -400,6 +401,23 @@ int ssi_adamw_step_sr(void* param, void* grad, void* exp_avg, void* exp_avg_sq, 
 /* The rounding of ssi_adamw_step_sr on its own, an fp32 -> bf16 cast: dst[i] = sr_bf16(src[i], bits of (seed, step, elem_offset + i, tensor)).
  * src and dst 16-byte aligned, 0 <= step < 2^32, tensor >= 0, elem_offset % 8 == 0. */
 int ssi_round_bf16_sr(const float* src, void* dst, int64_t n, uint64_t seed, int64_t step, int tensor, int64_t elem_offset, void* stream);
+/* AdamW over SEGMENTS of the flat buffers in one launch (ABI v16; not in the reference, opt-in: HipAdamW's param_segments).  Segment s covers
+ * the local elements [seg_end[s-1], seg_end[s]) with seg_end[-1] = 0 and has its own lr, weight decay and frozen flag.  seg_end, seg_lr,
+ * seg_weight_decay and seg_frozen are HOST arrays of n_segs entries, read during the call only: the table travels in the kernel arguments,
+ * the library allocates nothing on the device and enqueues no copy.  The ends are strictly ascending, every end but the last is a multiple of
+ * 8 (a 16-byte vector lies in one segment), the last equals n: anything else is SSI_ERR_ARG.  n_segs > SSI_ADAMW_MAX_SEGS is
+ * SSI_ERR_UNSUPPORTED (the caller splits the launch at a segment end), as is n >= 2^35 - 8.
+ *   A non-frozen element comes out bit for bit as the plain entry would leave it (the _sr one when stochastic != 0) when launched on that
+ * segment's slice alone with seg_lr[s], seg_weight_decay[s] and elem_offset + seg_end[s-1]: (float)(1 - lr wd) and (float)(lr / bc1) are
+ * computed per segment in double, and the random bits are a function of the global element index.  A FROZEN element is neither read nor
+ * written in any of the four buffers (its gradient may hold NaN; zero_grad bit 0 leaves it alone); frozen segments at either end of the slice
+ * are not launched over, an all-frozen table launches nothing.  zero_grad bit 1 makes the whole launch a no-op on a non-finite scale.
+ * stochastic != 0 needs SSI_BF16, step < 2^32 and elem_offset % 8 == 0; otherwise seed and elem_offset are not used. */
+#define SSI_ADAMW_MAX_SEGS 128
+int ssi_adamw_step_seg(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, const int64_t* seg_end, const double* seg_lr,
+                       const double* seg_weight_decay, const int32_t* seg_frozen, int n_segs, double beta1, double beta2, double eps,
+                       int64_t step, const float* grad_scale_dev, int zero_grad, int dtype, int stochastic, uint64_t seed,
+                       int64_t elem_offset, void* stream);
 
 #ifdef __cplusplus
 }

@@ -733,6 +733,198 @@ extern "C" int ssi_adamw_step_sr(void* param, void* grad, void* exp_avg, void* e
     return SSI_OK;
 }
 
+// =====================================================================================================================
+// K13g AdamW over SEGMENTS of the flat buffers (ABI v16; opt-in, HipAdamW(param_segments=...)): consecutive element ranges with their own
+// lr, weight decay and frozen flag in ONE launch.  The table travels by value in the kernel arguments (no device allocation, no copy
+// enqueued).  Segment ends are multiples of 8 elements (all but the last), so a 16-byte vector never straddles one: the table is kept in
+// UNITS of 8 elements, 32 bits per end.  A block finds the segment of its first unit with wave-uniform indices only (scalar loads, two
+// dependent rounds: 8 coarse ends, then the 16 ends of one chunk), walks the segments that reach into its 256 vectors (one, almost always)
+// and lets every lane keep the coefficients of the segment its vector lies in.  A lane of a frozen segment issues no load and no store.  The
+// fp32 arithmetic is adamw_kernel's, expression for expression, and the random bits are adamw_sr_kernel's: a function of the global index.
+// =====================================================================================================================
+struct AdamwSegTable {
+    uint32_t end8[SSI_ADAMW_MAX_SEGS];        // exclusive end of segment s in units of 8 elements (the last: rounded up); unused: 0xFFFFFFFF
+    float decay[SSI_ADAMW_MAX_SEGS];          // (float)(1 - lr * weight_decay)
+    float step_size[SSI_ADAMW_MAX_SEGS];      // (float)(lr / bc1)
+    uint32_t coarse[SSI_ADAMW_MAX_SEGS / 16]; // end8[16 k + 15]
+    uint32_t frozen[SSI_ADAMW_MAX_SEGS / 32]; // bit s: segment s is frozen
+    int n_segs;
+};
+
+// coefficients of the segment unit `u` lies in, for a block whose vectors cover the units [ub0, ub1]; false: frozen (or past the last end)
+__device__ __forceinline__ bool adamw_seg_lookup(const AdamwSegTable& t, uint32_t ub0, uint32_t ub1, uint32_t u, float& decay, float& step_size) {
+    int c = 0;
+#pragma unroll
+    for (int k = 0; k < SSI_ADAMW_MAX_SEGS / 16 - 1; ++k) c += ub0 >= t.coarse[k] ? 1 : 0;
+    int s = 16 * c;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s += ub0 >= t.end8[16 * c + k] ? 1 : 0;
+    uint32_t start = s ? t.end8[s - 1] : 0u;
+    bool active = false;
+    for (; s < t.n_segs && start <= ub1; ++s) {   // every index here is wave-uniform: the lanes only select
+        const uint32_t end = t.end8[s];
+        if (u >= start && u < end) {
+            decay = t.decay[s];
+            step_size = t.step_size[s];
+            active = !((t.frozen[s >> 5] >> (s & 31)) & 1u);
+        }
+        start = end;
+    }
+    return active;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void adamw_seg_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ m, T* __restrict__ v, int64_t n,
+                                                        const AdamwSegTable tab, float w1, float beta2, float w2, float eps, float inv_bc2_sqrt,
+                                                        const float* __restrict__ grad_scale_dev, int zero_grad) {
+    constexpr int N = Vec16<T>::N;
+    const float gs = grad_scale_dev ? *grad_scale_dev : 1.f;
+    if ((zero_grad & 2) && !(fabsf(gs) < INFINITY)) return;  // bit 1: a non-finite scale changes nothing
+    zero_grad &= 1;
+    const int64_t nvec = n / N;
+    for (int64_t b = (int64_t)blockIdx.x * 256; b < nvec; b += (int64_t)gridDim.x * 256) {
+        const int64_t i = b + threadIdx.x;
+        float decay = 0.f, step_size = 0.f;
+        const bool active = adamw_seg_lookup(tab, (uint32_t)((b * N) >> 3), (uint32_t)(((b + 255) * N) >> 3), (uint32_t)((i * N) >> 3), decay, step_size);
+        if (!active || i >= nvec) continue;
+        Vec16<T> pp = load16_nt(p + i * N), gg = load16_nt(g + i * N), mm = load16_nt(m + i * N), vv = load16_nt(v + i * N);
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const float gr = gg.get(k) * gs;
+            float pf = pp.get(k);
+            pf *= decay;
+            const float mf = mm.get(k) + w1 * (gr - mm.get(k));
+            const float vf = beta2 * vv.get(k) + w2 * gr * gr;
+            const float denom = sqrtf(vf) * inv_bc2_sqrt + eps;
+            pf -= step_size * mf / denom;
+            pp.set(k, pf); mm.set(k, mf); vv.set(k, vf);
+            if (zero_grad) gg.set(k, 0.f);
+        }
+        store16_nt(p + i * N, pp); store16_nt(m + i * N, mm); store16_nt(v + i * N, vv);
+        if (zero_grad) store16_nt(g + i * N, gg);
+    }
+    const int last = tab.n_segs - 1;   // the ragged tail belongs to the last segment
+    if (blockIdx.x == 0 && threadIdx.x < (n - nvec * N) && !((tab.frozen[last >> 5] >> (last & 31)) & 1u)) {
+        const float decay = tab.decay[last], step_size = tab.step_size[last];
+        const int64_t i = nvec * N + threadIdx.x;
+        const float gr = to_f32<T>(g[i]) * gs;
+        float pf = to_f32<T>(p[i]);
+        pf *= decay;
+        const float mf = to_f32<T>(m[i]) + w1 * (gr - to_f32<T>(m[i]));
+        const float vf = beta2 * to_f32<T>(v[i]) + w2 * gr * gr;
+        pf -= step_size * mf / (sqrtf(vf) * inv_bc2_sqrt + eps);
+        p[i] = from_f32<T>(pf); m[i] = from_f32<T>(mf); v[i] = from_f32<T>(vf);
+        if (zero_grad) g[i] = from_f32<T>(0.f);
+    }
+}
+
+// adamw_seg_kernel<bf16_t> with the three stores rounded by sr_bf16, as adamw_sr_kernel is to adamw_kernel
+__global__ __launch_bounds__(256) void adamw_seg_sr_kernel(bf16_t* __restrict__ p, bf16_t* __restrict__ g, bf16_t* __restrict__ m,
+                                                           bf16_t* __restrict__ v, int64_t n, const AdamwSegTable tab, float w1, float beta2,
+                                                           float w2, float eps, float inv_bc2_sqrt, const float* __restrict__ grad_scale_dev,
+                                                           int zero_grad, uint64_t seed, uint32_t step, int64_t vec_offset) {
+    using T = bf16_t;
+    constexpr int N = Vec16<T>::N;
+    static_assert(N == 8, "one Philox call per tensor covers the 8 elements of a 16-byte vector");
+    const float gs = grad_scale_dev ? *grad_scale_dev : 1.f;
+    if ((zero_grad & 2) && !(fabsf(gs) < INFINITY)) return;
+    zero_grad &= 1;
+    const int64_t nvec = n / N;
+    for (int64_t b = (int64_t)blockIdx.x * 256; b < nvec; b += (int64_t)gridDim.x * 256) {
+        const int64_t i = b + threadIdx.x;
+        float decay = 0.f, step_size = 0.f;
+        const bool active = adamw_seg_lookup(tab, (uint32_t)b, (uint32_t)(b + 255), (uint32_t)i, decay, step_size);
+        if (!active || i >= nvec) continue;
+        Vec16<T> pp = load16_nt(p + i * N), gg = load16_nt(g + i * N), mm = load16_nt(m + i * N), vv = load16_nt(v + i * N);
+        const Philox4 rp = sr_bits(vec_offset + i, step, 0, seed), rm = sr_bits(vec_offset + i, step, 1, seed),
+                      rv = sr_bits(vec_offset + i, step, 2, seed);
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const float gr = gg.get(k) * gs;
+            float pf = pp.get(k);
+            pf *= decay;
+            const float mf = mm.get(k) + w1 * (gr - mm.get(k));
+            const float vf = beta2 * vv.get(k) + w2 * gr * gr;
+            const float denom = sqrtf(vf) * inv_bc2_sqrt + eps;
+            pf -= step_size * mf / denom;
+            pp.v[k] = sr_bf16_value(pf, rp, k); mm.v[k] = sr_bf16_value(mf, rm, k); vv.v[k] = sr_bf16_value(vf, rv, k);
+            if (zero_grad) gg.set(k, 0.f);
+        }
+        store16_nt(p + i * N, pp); store16_nt(m + i * N, mm); store16_nt(v + i * N, vv);
+        if (zero_grad) store16_nt(g + i * N, gg);
+    }
+    const int last = tab.n_segs - 1;
+    if (blockIdx.x == 0 && threadIdx.x < (n - nvec * N) && !((tab.frozen[last >> 5] >> (last & 31)) & 1u)) {
+        const float decay = tab.decay[last], step_size = tab.step_size[last];
+        const int k = threadIdx.x;   // the tail is the head of vector vec_offset + nvec of the global index
+        const int64_t i = nvec * N + k;
+        const float gr = to_f32<T>(g[i]) * gs;
+        float pf = to_f32<T>(p[i]);
+        pf *= decay;
+        const float mf = to_f32<T>(m[i]) + w1 * (gr - to_f32<T>(m[i]));
+        const float vf = beta2 * to_f32<T>(v[i]) + w2 * gr * gr;
+        pf -= step_size * mf / (sqrtf(vf) * inv_bc2_sqrt + eps);
+        p[i] = sr_bf16_value(pf, sr_bits(vec_offset + nvec, step, 0, seed), k);
+        m[i] = sr_bf16_value(mf, sr_bits(vec_offset + nvec, step, 1, seed), k);
+        v[i] = sr_bf16_value(vf, sr_bits(vec_offset + nvec, step, 2, seed), k);
+        if (zero_grad) g[i] = from_f32<T>(0.f);
+    }
+}
+
+extern "C" int ssi_adamw_step_seg(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, const int64_t* seg_end,
+                                  const double* seg_lr, const double* seg_weight_decay, const int32_t* seg_frozen, int n_segs,
+                                  double beta1, double beta2, double eps, int64_t step, const float* grad_scale_dev, int zero_grad,
+                                  int dtype, int stochastic, uint64_t seed, int64_t elem_offset, void* stream) {
+    SSI_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n >= 0 && step >= 1);
+    SSI_CHECK_ARG(((uintptr_t)param % 16) == 0 && ((uintptr_t)grad % 16) == 0 && ((uintptr_t)exp_avg % 16) == 0 &&
+                  ((uintptr_t)exp_avg_sq % 16) == 0);
+    SSI_CHECK_ARG(seg_end && seg_lr && seg_weight_decay && seg_frozen && n_segs >= 1);
+    SSI_CHECK_ARG(dtype == SSI_F32 || dtype == SSI_BF16);
+    if (stochastic) SSI_CHECK_ARG(dtype == SSI_BF16 && step < ((int64_t)1 << 32) && elem_offset >= 0 && elem_offset % 8 == 0);
+    if (n_segs > SSI_ADAMW_MAX_SEGS) { ssi_set_error("adamw_step_seg: %d segments, at most %d per launch", n_segs, SSI_ADAMW_MAX_SEGS); return SSI_ERR_UNSUPPORTED; }
+    SSI_CHECK_ARG(seg_end[n_segs - 1] == n);
+    if (n == 0) { SSI_CHECK_ARG(n_segs == 1); return SSI_OK; }
+    for (int s = 0; s < n_segs; ++s) {
+        SSI_CHECK_ARG(seg_end[s] > (s ? seg_end[s - 1] : 0));            // strictly ascending
+        SSI_CHECK_ARG(s == n_segs - 1 || seg_end[s] % 8 == 0);           // a 16-byte vector lies in ONE segment
+    }
+    if (n >= ((int64_t)1 << 35) - 8) { ssi_set_error("adamw_step_seg: n = %lld is beyond the 32-bit unit index", (long long)n); return SSI_ERR_UNSUPPORTED; }
+    // frozen segments at either end are not launched over at all: the launch covers [first trainable start, last trainable end)
+    int s0 = 0, s1 = n_segs;
+    while (s0 < n_segs && seg_frozen[s0]) ++s0;
+    if (s0 == n_segs) return SSI_OK;
+    while (seg_frozen[s1 - 1]) --s1;
+    const int64_t lo = s0 ? seg_end[s0 - 1] : 0, nn = seg_end[s1 - 1] - lo;
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);   // the coefficients of ssi_adamw_step
+    const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+    AdamwSegTable tab;
+    for (int s = 0; s < SSI_ADAMW_MAX_SEGS; ++s) { tab.end8[s] = 0xFFFFFFFFu; tab.decay[s] = 1.f; tab.step_size[s] = 0.f; }
+    for (int k = 0; k < SSI_ADAMW_MAX_SEGS / 32; ++k) tab.frozen[k] = 0u;
+    tab.n_segs = s1 - s0;
+    for (int s = s0; s < s1; ++s) {
+        const int j = s - s0;
+        tab.end8[j] = (uint32_t)((seg_end[s] - lo + 7) / 8);
+        tab.decay[j] = (float)(1.0 - seg_lr[s] * seg_weight_decay[s]);
+        tab.step_size[j] = (float)(seg_lr[s] / bc1);
+        if (seg_frozen[s]) tab.frozen[j >> 5] |= 1u << (j & 31);
+    }
+    for (int k = 0; k < SSI_ADAMW_MAX_SEGS / 16; ++k) tab.coarse[k] = tab.end8[16 * k + 15];
+    const size_t esz = dtype == SSI_BF16 ? 2 : 4;   // lo is a multiple of 8 elements: the 16-byte alignment holds
+    char *pp = (char*)param + lo * esz, *gp = (char*)grad + lo * esz, *mp = (char*)exp_avg + lo * esz, *vp = (char*)exp_avg_sq + lo * esz;
+    if (stochastic) {
+        hipLaunchKernelGGL(adamw_seg_sr_kernel, dim3(stream_grid(nn / 8 + 1, 1 << 20)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)pp,
+                           (bf16_t*)gp, (bf16_t*)mp, (bf16_t*)vp, nn, tab, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                           (float)eps, inv_bc2_sqrt, grad_scale_dev, zero_grad, seed, (uint32_t)step, (elem_offset + lo) / 8);
+    } else {
+        SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(adamw_seg_kernel<T>, dim3(stream_grid(nn / Vec16<T>::N + 1, 1 << 20)), dim3(256), 0,
+                                                     (hipStream_t)stream, (T*)pp, (T*)gp, (T*)mp, (T*)vp, nn, tab, (float)(1.0 - beta1),
+                                                     (float)beta2, (float)(1.0 - beta2), (float)eps, inv_bc2_sqrt, grad_scale_dev,
+                                                     zero_grad));
+    }
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
 // the rounding of adamw_sr_kernel on its own: dst[i] = sr_bf16(src[i]) with the bits of (seed, step, elem_offset + i, tensor)
 __global__ __launch_bounds__(256) void round_bf16_sr_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, int64_t n, uint64_t seed,
                                                             uint32_t step, uint32_t tensor, int64_t vec_offset) {

@@ -278,8 +278,64 @@ class HipLlamaDecoder(nn.Module):
     def attach_grads(self) -> None:
         """Point every ``p.grad`` at its slice of the flat gradient buffer (idempotent)."""
         for p, name, rows in self._param_src:
-            if p.grad is None:
+            if p.grad is None and p.requires_grad:   # (a frozen parameter has no gradient)
                 p.grad = self._view(name, rows, self._flat_grad)
+
+    # ---- frozen ranges (ssi/param_groups.py; set by HipAdamW) -------------------------------------------------------------
+    def set_frozen(self, segments) -> None:
+        """Tell the backward which element ranges of the flat buffer no optimizer will read (``segments``: consecutive ranges with a
+        ``frozen`` flag, or None for none).  A weight-gradient launch is skipped when, and only when, every element it writes is frozen;
+        a frozen range of the gradient buffer is unspecified from then on, and nothing may read it.  A parameter that is frozen as a whole
+        gets ``requires_grad = False`` and ``grad = None``; a partly frozen one (the embedding with some trainable rows) keeps its ``grad``
+        view, whose frozen rows mean nothing.  The norm scales' gradients ride in ``rmsnorm_bwd`` with ``dx`` and are written regardless."""
+        frozen: list[tuple[int, int]] = []
+        for s in segments or ():
+            if s.frozen:
+                if frozen and frozen[-1][1] == s.start:
+                    frozen[-1] = (frozen[-1][0], s.end)
+                else:
+                    frozen.append((s.start, s.end))
+        self._frozen_ranges = frozen
+        for p, name, rows in self._param_src:
+            o, shape = self._slices[name]
+            cols = 1
+            for d in shape[1:]:
+                cols *= d
+            lo, hi = (o, o + shape[0] * cols) if rows is None else (o + rows[0] * cols, o + rows[1] * cols)
+            is_frozen = self._range_frozen(lo, hi)
+            p.requires_grad_(not is_frozen)
+            if is_frozen:
+                p.grad = None
+        # rows of the tied embedding whose gradient the head has to compute: a 256-aligned span around the trainable ones
+        D, e_hi = self.embed_dim, self.vocab_pad * self.embed_dim
+        self._emb_frozen = self._range_frozen(0, e_hi)
+        self._emb_span: Optional[tuple[int, int]] = None
+        if frozen and not self._emb_frozen:
+            pos, first, last = 0, None, 0   # first and one-past-last trainable element of the embedding
+            for lo, hi in frozen + [(e_hi, e_hi)]:
+                if lo > pos and pos < e_hi:
+                    first, last = (pos if first is None else first), min(lo, e_hi)
+                pos = max(pos, hi)
+            r0, r1 = first // D // 256 * 256, min(_align(-(-last // D), 256), self.vocab_pad)
+            if (r0, r1) != (0, self.vocab_pad):
+                self._emb_span = (r0, r1)
+
+    _frozen_ranges: list = []
+    _emb_frozen = False
+    _emb_span = None
+
+    def _range_frozen(self, lo: int, hi: int) -> bool:
+        return any(a <= lo and hi <= b for a, b in self._frozen_ranges)
+
+    def _slice_frozen(self, name: str, count: int = 1, stride: int = 0) -> bool:
+        """Is every element of the slice ``name`` (and of the ``count - 1`` slices that follow it ``stride`` elements apart) frozen?"""
+        if not self._frozen_ranges:
+            return False
+        o, shape = self._slices[name]
+        n = 1
+        for d in shape:
+            n *= d
+        return all(self._range_frozen(o + k * stride, o + k * stride + n) for k in range(count))
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         """With ``set_to_none`` (torch's default) no memory is touched: the next backward overwrites the buffer.  Only a caller who
@@ -305,10 +361,11 @@ class HipLlamaDecoder(nn.Module):
         which is what autograd's accumulation would give."""
         if not self._grads_dirty:
             return False
-        dropped = [(p, name, rows) for p, name, rows in self._param_src if p.grad is None]
+        live = [(p, name, rows) for p, name, rows in self._param_src if p.requires_grad]   # (a frozen parameter's grad is always None)
+        dropped = [(p, name, rows) for p, name, rows in live if p.grad is None]
         if not dropped:
             return True
-        if len(dropped) == len(self._param_src):
+        if len(dropped) == len(live):
             self._grads_dirty, self._grads_stale, self._emb_grad_written = False, True, False
             self.pending_grad_scale = None
             return False
@@ -486,6 +543,8 @@ class HipLlamaDecoder(nn.Module):
 
         def wgrad(dy: Tensor, x: Tensor, name: str) -> None:
             """dW += dy^T x; split over K = tokens when the [out, in] grid cannot fill the chip (square projections)."""
+            if self._slice_frozen(name):
+                return   # nobody reads this gradient (set_frozen)
             g = gv(name)
             splits = ops.splitk_choice(g.shape[0], g.shape[1], T) if (dt == torch.bfloat16 and T % 64 == 0) else 1
             if splits > 1:
@@ -523,8 +582,10 @@ class HipLlamaDecoder(nn.Module):
             n = min(Gp, L - l_lo)
             g_o = torch.as_strided(G, (n, D, H * hd), (lstride, H * hd, 1), self._slices[f"L{l_lo}.wo"][0])
             g_qkv = torch.as_strided(G, (n, self.qkv_dim, D), (lstride, D, 1), self._slices[f"L{l_lo}.wqkv"][0])
-            ops.gemm_batched(GEMM_TN, dhmid_all[:n], att_all[l_lo:l_lo + n], g_o, accumulate=acc)
-            ops.gemm_batched(GEMM_TN, dqkv_all[:n], xn1_all[l_lo:l_lo + n], g_qkv, accumulate=acc)
+            if not self._slice_frozen(f"L{l_lo}.wo", n, lstride):      # (skipped only when the whole group's weights are frozen)
+                ops.gemm_batched(GEMM_TN, dhmid_all[:n], att_all[l_lo:l_lo + n], g_o, accumulate=acc)
+            if not self._slice_frozen(f"L{l_lo}.wqkv", n, lstride):
+                ops.gemm_batched(GEMM_TN, dqkv_all[:n], xn1_all[l_lo:l_lo + n], g_qkv, accumulate=acc)
 
         def dgrad(dy: Tensor, name: str, dx: Tensor) -> None:
             """dx = dy @ W  (W = [out, in]) on the untransposed weights: NN form of the persistent GEMM.  In the step its A operand has just
@@ -577,9 +638,10 @@ class HipLlamaDecoder(nn.Module):
             if l % self._bucket_group == 0:
                 announce(f"attn.{l}")
         ws_e = A.get("ws.emb", (max(_lib.load().ssi_embed_bwd_workspace_bytes(self.vocab_size), 16),), torch.uint8)
-        if not acc and not self._emb_grad_written:  # backward through the hidden states only (no tied head in front): the scatter-add
-            gv("emb").zero_()                       # below touches only the rows of this batch's tokens
-        ops.embed_bwd(tok, dh, gv("emb"), self.vocab_size, ws_e)
+        if not self._emb_frozen:
+            if not acc and not self._emb_grad_written:  # backward through the hidden states only (no tied head in front): the scatter-add
+                gv("emb").zero_()                       # below touches only the rows of this batch's tokens
+            ops.embed_bwd(tok, dh, gv("emb"), self.vocab_size, ws_e)
         self._grads_dirty, self._grads_stale, self._emb_grad_written = True, False, False
         announce("emb")
         self._saved = None
@@ -609,7 +671,14 @@ class HipLlamaDecoder(nn.Module):
         # 17th with 72 tiles, each a full K = T contraction (~360 us with 184 CUs idle).  The rows of the last partial round go to a second
         # launch that also splits K, so that the tail occupies the chip for a third of a tile's time.
         rows_main = self._head_wgrad_main_rows(T)
-        if rows_main:
+        if self._emb_frozen:
+            pass   # every row is frozen: no weight gradient at all (set_frozen)
+        elif self._emb_span is not None:
+            # only some rows are trainable: dE for a 256-aligned span around them, one plain launch on the strided operand the tail launch
+            # below uses (about 20 row tiles instead of 521 with the new vocabulary rows alone); the rows outside stay unspecified
+            r0, r1 = self._emb_span
+            ops.gemm(GEMM_TN, dlogits[:, r0:r1], hn, g_emb[r0:r1], alpha_dev=alpha_dev, accumulate=acc)
+        elif rows_main:
             Vp = self.vocab_pad
             ops.gemm(GEMM_TN, dlogits[:, :rows_main], hn, g_emb[:rows_main], alpha_dev=alpha_dev, accumulate=acc)
             tail, splits = Vp - rows_main, self._head_wgrad_tail_splits

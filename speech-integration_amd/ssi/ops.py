@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
 __all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "swiglu_fwd",
-           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "round_bf16_sr", "set_impl", "set_attn_impl", "attn_last_dispatch",
+           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
 
@@ -478,6 +478,40 @@ def adamw_step(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor,
     check(_lib.load().ssi_adamw_step(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), lr, beta1, beta2,
                                      eps, weight_decay, step, ptr(grad_scale_dev), flags, dtype_code(param.dtype),
                                      stream_ptr()), "ssi_adamw_step")
+
+
+def adamw_step_seg(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, *, seg_end, seg_lr, seg_weight_decay, seg_frozen,
+                   beta1: float, beta2: float, eps: float, step: int, grad_scale_dev: Tensor | None = None, zero_grad: bool = False,
+                   skip_nonfinite_scale: bool = False, sr_seed: int | None = None, elem_offset: int = 0) -> None:
+    """``adamw_step`` over consecutive segments of the buffers in one launch (``ssi_adamw_step_seg``): segment ``s`` covers the elements
+    ``[seg_end[s-1], seg_end[s])`` (``seg_end[-1] = 0``; ends ascending, multiples of 8 but the last, which is ``numel``) and runs at
+    ``seg_lr[s]`` / ``seg_weight_decay[s]``, or is left alone — neither read nor written — where ``seg_frozen[s]``.  The four sequences are
+    host values.  More than ``_lib.ADAMW_MAX_SEGS`` segments become several launches, split at segment ends; the result is the same."""
+    assert param.is_contiguous() and grad.is_contiguous() and exp_avg.is_contiguous() and exp_avg_sq.is_contiguous()
+    assert param.numel() == grad.numel() == exp_avg.numel() == exp_avg_sq.numel()
+    assert param.dtype == grad.dtype == exp_avg.dtype == exp_avg_sq.dtype
+    n_segs = len(seg_end)
+    assert n_segs >= 1 and len(seg_lr) == len(seg_weight_decay) == len(seg_frozen) == n_segs
+    flags = int(zero_grad) | (2 if skip_nonfinite_scale else 0)
+    lib, cap = _lib.load(), _lib.ADAMW_MAX_SEGS
+    param, grad, exp_avg, exp_avg_sq = param.view(-1), grad.view(-1), exp_avg.view(-1), exp_avg_sq.view(-1)
+    if param.numel() == 0 and n_segs == 1 and int(seg_end[0]) == 0:
+        return   # (an empty tensor has no address to hand over)
+    for a in range(0, n_segs, cap):
+        b = min(a + cap, n_segs)
+        lo, hi = (int(seg_end[a - 1]) if a else 0), int(seg_end[b - 1])
+        if hi < lo or (a and hi == lo):
+            raise ValueError(f"adamw_step_seg: segment ends must ascend (segments {a}..{b})")
+        k = b - a
+        ends = (_lib.c_int64 * k)(*[int(e) - lo for e in seg_end[a:b]])
+        lrs = (_lib.c_double * k)(*[float(x) for x in seg_lr[a:b]])
+        wds = (_lib.c_double * k)(*[float(x) for x in seg_weight_decay[a:b]])
+        frz = (_lib.c_int32 * k)(*[1 if x else 0 for x in seg_frozen[a:b]])
+        sl = slice(lo, hi) if (a or b < n_segs) else slice(None)   # (one launch: the whole buffers, so that a wrong last end is the library's error)
+        check(lib.ssi_adamw_step_seg(ptr(param[sl]), ptr(grad[sl]), ptr(exp_avg[sl]), ptr(exp_avg_sq[sl]), param[sl].numel(), ends, lrs, wds, frz, k,
+                                     beta1, beta2, eps, step, ptr(grad_scale_dev), flags, dtype_code(param.dtype), int(sr_seed is not None),
+                                     (int(sr_seed) & 0xFFFFFFFFFFFFFFFF) if sr_seed is not None else 0, elem_offset + lo, stream_ptr()),
+              "ssi_adamw_step_seg")
 
 
 def round_bf16_sr(src: Tensor, dst: Tensor, *, seed: int, step: int, tensor: int, elem_offset: int = 0) -> None:

@@ -6,7 +6,9 @@ kernel over the model's flat parameter / gradient / moment buffers: decoupled we
 rounding on store — the semantics of ``torch.optim.AdamW(fused=True)`` (K13), with ``scale_grads`` (K11) and the
 clip coefficient (K12) folded in as a device-side gradient multiplier.  The gradient buffer is not zeroed: the first backward of the
 next accumulation window overwrites it (``HipLlamaDecoder`` gradient-buffer protocol).  ``stochastic_rounding`` (bf16 only, off by default,
-not in the reference) rounds the three stores stochastically instead of to nearest, with stateless counter-based random bits."""
+not in the reference) rounds the three stores stochastically instead of to nearest, with stateless counter-based random bits.
+``param_segments`` (config key ``param_groups``, null by default, not in the reference; ``ssi/param_groups.py``) gives consecutive ranges of
+the flat buffer their own lr scale, weight decay or a frozen flag: the step is still one launch, of the segmented kernel."""
 
 from __future__ import annotations
 
@@ -17,12 +19,14 @@ import torch
 from torch import Tensor
 
 from . import ops
+from .param_groups import check_segments, model_layout, resolve, trainable_ranges
+from .param_groups import clip as clip_segments
 
 
 class HipAdamW(torch.optim.Optimizer):
     def __init__(self, params: Iterable, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, amsgrad: bool = False, fused: bool | None = None, *, model=None,
-                 stochastic_rounding: bool = False, stochastic_rounding_seed: int | None = None, **unused: Any):
+                 stochastic_rounding: bool = False, stochastic_rounding_seed: int | None = None, param_segments=None, **unused: Any):
         if amsgrad:
             raise NotImplementedError("amsgrad=True is not supported (reference default: false, conf/training.yaml:8)")
         if unused:
@@ -46,6 +50,13 @@ class HipAdamW(torch.optim.Optimizer):
             self._sr_seed = int(SEED if stochastic_rounding_seed is None else stochastic_rounding_seed)   # the same on every rank
         else:
             self._sr_seed = None
+        # Parameter segments (not in the reference; ssi/param_groups.py): consecutive ranges of the flat buffer with their own lr scale, weight
+        # decay and frozen flag, applied by ssi_adamw_step_seg in the launches below.  Like the rounding they belong to the run's configuration:
+        # ``param_groups`` stays the one torch group, and a state saved under one rule set loads under another (a frozen range's moments
+        # simply stay what they were).  The model learns what is frozen, and skips those weight-gradient launches.
+        self._segments = None if param_segments is None else check_segments(param_segments, model._flat.numel())
+        if self._segments is not None or getattr(model, "_frozen_ranges", None):   # (without segments: only to undo an earlier optimizer's)
+            model.set_frozen(self._segments)
         self.model = model
         model._hip_optimizer = weakref.ref(self)  # scale_grads / clip_grad_norm_ may defer their factor only while THIS optimizer consumes it
         self._exp_avg = torch.zeros_like(model._flat)
@@ -54,6 +65,26 @@ class HipAdamW(torch.optim.Optimizer):
         self._views_ready = False
         self._side = None    # stream of the updates that run under the backward (overlap_with_backward)
         self._armed = None
+
+    def _update(self, lo: int, hi: int, g: dict, step: int, scale: Tensor | None, skip_nonfinite_scale: bool = False) -> None:
+        """AdamW on the elements ``[lo, hi)`` of the flat buffers: the plain kernel, or with segments the segmented one on those that reach
+        into the slice (nothing at all where every one of them is frozen)."""
+        m = self.model
+        bufs = (m._flat[lo:hi], m._flat_grad[lo:hi], self._exp_avg[lo:hi], self._exp_avg_sq[lo:hi])
+        if self._segments is None:
+            ops.adamw_step(*bufs, lr=float(g["lr"]), beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"],
+                           step=step, grad_scale_dev=scale, zero_grad=False, skip_nonfinite_scale=skip_nonfinite_scale,
+                           sr_seed=self._sr_seed, elem_offset=lo)
+            return
+        segs = clip_segments(self._segments, lo, hi)
+        if all(s.frozen for s in segs):
+            return
+        lr, wd = float(g["lr"]), float(g["weight_decay"])
+        ops.adamw_step_seg(*bufs, seg_end=[s.end - lo for s in segs], seg_lr=[lr * s.lr_scale for s in segs],
+                           seg_weight_decay=[wd if s.weight_decay is None else s.weight_decay for s in segs],
+                           seg_frozen=[s.frozen for s in segs], beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], step=step,
+                           grad_scale_dev=scale, zero_grad=False, skip_nonfinite_scale=skip_nonfinite_scale, sr_seed=self._sr_seed,
+                           elem_offset=lo)
 
     def _ensure_state_views(self) -> None:
         if self._views_ready:
@@ -97,9 +128,7 @@ class HipAdamW(torch.optim.Optimizer):
         ev.record(cur)
         with torch.cuda.stream(self._side):
             self._side.wait_event(ev)
-            ops.adamw_step(m._flat[lo:hi], m._flat_grad[lo:hi], self._exp_avg[lo:hi], self._exp_avg_sq[lo:hi], lr=float(g["lr"]),
-                           beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"], step=a["step"],
-                           grad_scale_dev=a["scale"], zero_grad=False, skip_nonfinite_scale=True, sr_seed=self._sr_seed, elem_offset=lo)
+            self._update(lo, hi, g, a["step"], a["scale"], skip_nonfinite_scale=True)
         a["done"].append((lo, hi))
 
     def cancel_overlap(self) -> None:
@@ -125,9 +154,7 @@ class HipAdamW(torch.optim.Optimizer):
             pos, n = 0, m._flat.numel()
             for lo, hi in covered + [(n, n)]:
                 if lo > pos:  # a gap between buckets (none in HipLlamaDecoder's layout): the plain update, same scale
-                    ops.adamw_step(m._flat[pos:lo], m._flat_grad[pos:lo], self._exp_avg[pos:lo], self._exp_avg_sq[pos:lo], lr=float(g["lr"]),
-                                   beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"], step=self._step_count,
-                                   grad_scale_dev=a["scale"], zero_grad=False, sr_seed=self._sr_seed, elem_offset=pos)
+                    self._update(pos, lo, g, self._step_count, a["scale"])
                 pos = max(pos, hi)
             m.pending_grad_scale = None  # (scale_grads of the caller: already applied, bucket by bucket)
             if self._views_ready:
@@ -135,7 +162,7 @@ class HipAdamW(torch.optim.Optimizer):
                     st["step"].fill_(float(self._step_count))
             return loss
         self._armed = None
-        if all(p.grad is None for p, _, _ in m._param_src):
+        if all(p.grad is None for p, _, _ in m._param_src if p.requires_grad):   # (a frozen parameter never has a gradient)
             # no backward since the last zero_grad (skipped or failed micro-batches): torch.optim.AdamW skips parameters without a
             # gradient; the never-zeroed buffer still holds the LAST window's gradients, which must not be applied a second time
             sync = getattr(m, "grad_sync", None)
@@ -147,10 +174,7 @@ class HipAdamW(torch.optim.Optimizer):
 
         def update(lo: int, hi: int) -> None:
             if hi > lo:
-                ops.adamw_step(m._flat[lo:hi], m._flat_grad[lo:hi], self._exp_avg[lo:hi], self._exp_avg_sq[lo:hi], lr=float(g["lr"]),
-                               beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"],
-                               step=self._step_count, grad_scale_dev=m.pending_grad_scale, zero_grad=False, sr_seed=self._sr_seed,
-                               elem_offset=lo)
+                self._update(lo, hi, g, self._step_count, m.pending_grad_scale)
 
         sync = getattr(m, "grad_sync", None)
         tail = sync.deferred_range() if sync is not None and hasattr(sync, "deferred_range") else None
@@ -213,8 +237,16 @@ def _to_container(node):
         return dict(node)
 
 
-def setup_optimizer(cfg, model, optimizer_state_dict: dict[str, Any] | None = None) -> torch.optim.Optimizer:
+def setup_optimizer(cfg, model, optimizer_state_dict: dict[str, Any] | None = None, *,
+                    token_type_ranges: dict[str, tuple[int, int]] | None = None) -> torch.optim.Optimizer:
     optimizer_kwargs = _to_container(cfg.optimizer)
+    rules = cfg.get("param_groups") if hasattr(cfg, "get") else None   # (top level: the rules name parameters, not optimizer arguments)
+    if rules is not None:
+        if not hasattr(model, "_flat"):
+            raise ValueError(f"param_groups needs the HIP decoder (ranges of its flat parameter buffer); {type(model).__name__} has none")
+        rules = [_to_container(r) if not isinstance(r, dict) else r for r in rules]
+        layout, total = model_layout(model)
+        optimizer_kwargs["param_segments"] = resolve(rules, layout, total, token_type_ranges)
     stochastic = bool(optimizer_kwargs.pop("stochastic_rounding", False))   # (both keys are this project's, not torch's)
     sr_seed = optimizer_kwargs.pop("stochastic_rounding_seed", None)
     if hasattr(model, "_flat"):
@@ -274,7 +306,19 @@ def clip_grad_norm_(model, max_norm: float) -> Tensor:
     if sync is not None and hasattr(sync, "finish_deferred"):
         sync.finish_deferred()  # the norm reads every gradient
     out = torch.empty(1, dtype=torch.float32, device=model._flat_grad.device)
-    ops.sumsq(model._flat_grad, out)
+    opt = _hip_optimizer_of(model)
+    if opt is not None and opt._segments is not None:
+        # frozen ranges of the gradient buffer are unspecified (nothing writes them): the norm is over the trainable ranges only, one sum
+        # per maximal range, added in ascending order
+        ranges = trainable_ranges(opt._segments)
+        parts = torch.zeros(max(len(ranges), 1), dtype=torch.float32, device=out.device)
+        for k, (lo, hi) in enumerate(ranges):
+            ops.sumsq(model._flat_grad[lo:hi], parts[k:k + 1])
+        out = parts[0:1].clone()
+        for k in range(1, len(ranges)):
+            out = out + parts[k:k + 1]
+    else:
+        ops.sumsq(model._flat_grad, out)
     scale = model.pending_grad_scale if model.pending_grad_scale is not None else torch.ones_like(out)
     total_norm = out.sqrt() * scale.abs()
     coef = torch.clamp(float(max_norm) / (total_norm + 1e-6), max=1.0)

@@ -122,6 +122,10 @@ def validate_train_cfg(cfg) -> None:
     d = cfg.get("teacher_checkpoint_dir")
     if d is not None and not isinstance(d, (str, os.PathLike)):
         raise ValueError(f"config field 'teacher_checkpoint_dir' must be null or a path, got {d!r}")
+    rules = cfg.get("param_groups")   # (the rules themselves are checked against the model's layout: ssi/param_groups.py)
+    if rules is not None and (isinstance(rules, (str, bytes)) or not hasattr(rules, "__len__") or hasattr(rules, "keys") or len(rules) == 0
+                              or not all(hasattr(r, "keys") for r in rules)):
+        raise ValueError(f"config field 'param_groups' must be null or a non-empty list of mappings, got {rules!r}")
 
 
 # training_state.pt (schema v1): key in the file -> name under which the trainer consumes it

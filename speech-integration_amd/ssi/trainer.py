@@ -387,7 +387,14 @@ class Trainer:
             self.consumed_samples = self._resume_state["consumed_samples"]
 
     def _setup_optimizer(self) -> None:
-        self.optimizer = setup_optimizer(self.cfg, self.model, self._resume_state["optimizer_state"] if self._resume_state else None)
+        self.optimizer = setup_optimizer(self.cfg, self.model, self._resume_state["optimizer_state"] if self._resume_state else None,
+                                         token_type_ranges=self.token_type_ranges)
+        segments = getattr(self.optimizer, "_segments", None)
+        if segments is not None:   # (not in the reference) param_groups: what the rules resolved to
+            from .param_groups import describe
+            trainable = sum(s.end - s.start for s in segments if not s.frozen)
+            LOGGER.info(f"param_groups: {trainable} of {sum(s.end - s.start for s in segments)} elements of the flat parameter buffer are "
+                        f"trainable, in {len(segments)} segments: {describe(segments)}")
         self.lr_scheduler = setup_lr_scheduler(cfg=self.cfg, optimizer=self.optimizer, global_step=self.global_step - 1,
                                                num_training_steps=self.cfg.max_steps)
         if self._resume_state and self.lr_scheduler is not None:
