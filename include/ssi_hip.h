@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 16 /* 16: + ssi_adamw_step_seg (AdamW over segments of the flat buffers with their own lr, weight decay and frozen flag; opt-in)
+#define SSI_ABI_VERSION 17 /* 17: + ssi_ema_update (fp32 exponential moving average of the flat parameter buffer, one pass chained to AdamW; opt-in)
+                           * 16: + ssi_adamw_step_seg (AdamW over segments of the flat buffers with their own lr, weight decay and frozen flag; opt-in)
                            * 15: + ssi_ce_fwd_kl (KL against a frozen teacher's logits inside the cross-entropy kernels; opt-in)
                            * 14: + ssi_ce_fwd_smooth (label smoothing inside the cross-entropy kernels, beside the z-loss; opt-in)
                            * 13: + ssi_seq_score_reduce (per-sequence sums of what ssi_ce_fwd_metrics wrote: likelihood scoring of packed rows)
@@ -418,6 +419,18 @@ int ssi_adamw_step_seg(void* param, void* grad, void* exp_avg, void* exp_avg_sq,
                        const double* seg_weight_decay, const int32_t* seg_frozen, int n_segs, double beta1, double beta2, double eps,
                        int64_t step, const float* grad_scale_dev, int zero_grad, int dtype, int stochastic, uint64_t seed,
                        int64_t elem_offset, void* stream);
+/* Exponential moving average of the parameters, kept in fp32 (ABI v17; not in the reference, opt-in: HipAdamW's ema_decay).  Per element, in
+ * fp32, with p = (float)param[i] (exact for bf16):
+ *     ema[i] = __builtin_fmaf(decay, ema[i] - p, p)
+ * the subtraction correctly rounded, then ONE fused multiply-add.  decay == 0 gives ema = p exactly, and ema == p is an exact fixed point: the
+ * average of a frozen or converged weight never drifts by rounding.  ema is fp32 whatever `dtype`, which is that of param (SSI_BF16 or
+ * SSI_F32).  0 <= decay < 1, anything else (NaN included) is SSI_ERR_ARG.  guard_dev may be NULL; otherwise the launch changes nothing when
+ * *guard_dev is inf or NaN — the test of zero_grad bit 1 in ssi_adamw_step, !(fabsf(g) < INFINITY): pass AdamW's grad_scale_dev, and an
+ * accumulation window without a label moves neither the parameters nor their average.  ema and param 16-byte aligned; n is arbitrary (the
+ * tail after the last vector of 8 is handled in the kernel); n == 0 is success without a launch.  One pure HBM pass: per element 2 B (bf16)
+ * or 4 B read of param, 4 B read and 4 B written of ema. */
+int ssi_ema_update(void* ema /* fp32 */, const void* param, int64_t n, float decay, const float* guard_dev,
+                   int dtype /* of param: SSI_BF16 | SSI_F32 */, void* stream);
 
 #ifdef __cplusplus
 }

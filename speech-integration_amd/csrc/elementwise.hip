@@ -955,6 +955,54 @@ extern "C" int ssi_round_bf16_sr(const float* src, void* dst, int64_t n, uint64_
 }
 
 // =====================================================================================================================
+// K13e fp32 exponential moving average of the parameters (ABI v17; opt-in, HipAdamW(ema_decay=...)): one more pure HBM pass over the flat
+// buffer, chained to the AdamW launch on the same stream.  ema = fma(decay, ema - p, p): the subtraction rounded, then ONE fused
+// multiply-add, written out (the library is built with -ffp-contract=fast, see ssi_rope_pair).  decay == 0 gives p exactly and ema == p is
+// an exact fixed point: the average of a frozen or converged weight never drifts by rounding.  8 elements per thread and trip: one 16-byte
+// load of bf16 parameters (two of fp32), two 16-byte loads and two 16-byte stores of the average; no LDS, no scratch, no atomics.
+// =====================================================================================================================
+__device__ __forceinline__ float ema_elem(float decay, float e, float p) {
+    const float d = e - p;
+    return __builtin_fmaf(decay, d, p);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const T* __restrict__ p, int64_t n, float decay,
+                                                         const float* __restrict__ guard_dev) {
+    if (guard_dev && !(fabsf(*guard_dev) < INFINITY)) return;  // the test of adamw_kernel's zero_grad bit 1: AdamW changed nothing, nor does the average
+    const int64_t nvec = n / 8;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+        Vec16<float> e0 = load16_nt(ema + i * 8), e1 = load16_nt(ema + i * 8 + 4);
+        if constexpr (Vec16<T>::N == 8) {
+            const Vec16<T> pp = load16_nt(p + i * 8);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { e0.v[k] = ema_elem(decay, e0.v[k], pp.get(k)); e1.v[k] = ema_elem(decay, e1.v[k], pp.get(k + 4)); }
+        } else {
+            const Vec16<T> p0 = load16_nt(p + i * 8), p1 = load16_nt(p + i * 8 + 4);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { e0.v[k] = ema_elem(decay, e0.v[k], p0.get(k)); e1.v[k] = ema_elem(decay, e1.v[k], p1.get(k)); }
+        }
+        store16_nt(ema + i * 8, e0); store16_nt(ema + i * 8 + 4, e1);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n - nvec * 8)) {
+        const int64_t i = nvec * 8 + threadIdx.x;
+        ema[i] = ema_elem(decay, ema[i], to_f32<T>(p[i]));
+    }
+}
+
+extern "C" int ssi_ema_update(void* ema, const void* param, int64_t n, float decay, const float* guard_dev, int dtype, void* stream) {
+    SSI_CHECK_ARG(n >= 0);
+    if (!(decay >= 0.f && decay < 1.f)) { ssi_set_error("ema_update: decay = %g, must be in [0, 1)", (double)decay); return SSI_ERR_ARG; }
+    if (n == 0) return SSI_OK;
+    SSI_CHECK_ARG(ema && param && ((uintptr_t)ema % 16) == 0 && ((uintptr_t)param % 16) == 0);
+    // 8 elements per thread; the grid is adamw_kernel's for bf16: one trip per thread up to 2^20 blocks (2^31 elements), the stride loop beyond
+    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(ema_update_kernel<T>, dim3(stream_grid(n / 8 + 1, 1 << 20)), dim3(256), 0, (hipStream_t)stream,
+                                                 (float*)ema, (const T*)param, n, decay, guard_dev));
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+// =====================================================================================================================
 // 2-D transpose dst[c][r] = src[r][c] (64 x 64 tiles through LDS; 16-B global accesses on both sides).  Used once per
 // optimizer step to refresh the [in, out] copies of the projection weights, so that the data-gradient GEMMs
 // dX = dY W run in the k-contiguous (NT) operand form instead of the transposed-read form.

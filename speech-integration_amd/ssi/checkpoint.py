@@ -93,6 +93,9 @@ def random_init_(model, seed: int, std: float = 0.02) -> None:
                 flat[r0:r0 + blk.shape[0]].copy_(blk.to(p.dtype))
 
 
+EMA_STATE_FILENAME = "ema_state.safetensors"   # the fp32 parameter averages of a run with ema_decay, beside training_state.pt
+
+
 class TuneCheckpointer:
     def __init__(self, checkpoint_dir: str | None = None, checkpoint_files: Any = None, config_json: Any = None,
                  output_dir: str | None = None, training_state_checkpoint: str | None = None, safe_serialization: bool = True,
@@ -123,11 +126,34 @@ class TuneCheckpointer:
         return out
 
     def save_model_checkpoint(self, state_dict: dict[str, torch.Tensor], global_step: int) -> str:
+        return self._save_model_file(state_dict, os.path.join(str(self.output_dir), f"step_{global_step}"))
+
+    @staticmethod
+    def _save_model_file(state_dict: dict[str, torch.Tensor], d: str) -> str:
         from safetensors.torch import save_file
-        d = os.path.join(str(self.output_dir), f"step_{global_step}")
         os.makedirs(d, exist_ok=True)
         path = os.path.join(d, MODEL_FILENAME)
         save_file({k: v.detach().to("cpu").contiguous() for k, v in state_dict.items()}, path)
+        return path
+
+    def save_ema_checkpoint(self, model_state_dict: dict[str, torch.Tensor], ema_state_dict: dict[str, torch.Tensor], global_step: int) -> str:
+        """(not in the reference; a run with ``ema_decay``) ``model_state_dict``: the averaged weights in the model's dtype, written under
+        ``step_N/ema/`` in exactly the format ``step_N/`` has — a model directory of its own.  ``ema_state_dict``: the fp32 averages by
+        state-dict name, written to ``ema_state.safetensors`` beside ``training_state.pt`` (overwritten by every save, as that file is)."""
+        d = self._save_ema_model(model_state_dict, global_step)
+        self._save_ema_state(ema_state_dict)
+        return d
+
+    def _save_ema_model(self, model_state_dict: dict[str, torch.Tensor], global_step: int) -> str:
+        d = os.path.join(str(self.output_dir), f"step_{global_step}", "ema")
+        self._save_model_file(model_state_dict, d)
+        return d
+
+    def _save_ema_state(self, ema_state_dict: dict[str, torch.Tensor]) -> str:
+        from safetensors.torch import save_file
+        os.makedirs(str(self.output_dir), exist_ok=True)
+        path = os.path.join(str(self.output_dir), EMA_STATE_FILENAME)
+        save_file({k: v.detach().to("cpu", torch.float32).contiguous() for k, v in ema_state_dict.items()}, path)
         return path
 
     def save_training_state(self, optimizer_state_dict, lr_scheduler_state_dict, global_step: int, seed: int,
@@ -351,6 +377,9 @@ class FullModelHFCheckpointer(TuneCheckpointer):
             if f.is_file() and not f.name.endswith(skip):
                 shutil.copy2(f, output_dir / f.name)
         return output_dir
+
+    def _save_ema_model(self, model_state_dict: dict[str, torch.Tensor], global_step: int) -> str:
+        return str(self.save_model_checkpoint(model_state_dict, global_step, output_dir=self._out_dir / f"step_{global_step}" / "ema"))
 
 
 def make_checkpointer(**kwargs: Any):

@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
 __all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "swiglu_fwd",
-           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "set_impl", "set_attn_impl", "attn_last_dispatch",
+           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "ema_update", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
 
@@ -520,3 +520,13 @@ def round_bf16_sr(src: Tensor, dst: Tensor, *, seed: int, step: int, tensor: int
     assert src.dtype == torch.float32 and dst.dtype == torch.bfloat16
     check(_lib.load().ssi_round_bf16_sr(ptr(src), ptr(dst), src.numel(), int(seed) & 0xFFFFFFFFFFFFFFFF, step, tensor, elem_offset,
                                         stream_ptr()), "ssi_round_bf16_sr")
+
+
+def ema_update(ema: Tensor, param: Tensor, *, decay: float, guard_dev: Tensor | None = None) -> None:
+    """``ema = fma(decay, ema - param, param)`` per element in fp32 (``ssi_ema_update``): the running average of ``param`` (bf16 or fp32) in the
+    fp32 ``ema``.  ``guard_dev``: the launch changes nothing when ``*guard_dev`` is inf or NaN (``adamw_step``'s ``skip_nonfinite_scale``)."""
+    if ema.dtype != torch.float32:
+        raise TypeError(f"ema_update: the average is kept in fp32, not {ema.dtype}")
+    assert ema.is_contiguous() and param.is_contiguous() and ema.numel() == param.numel()
+    check(_lib.load().ssi_ema_update(ptr(ema), ptr(param), ema.numel(), float(decay), ptr(guard_dev), dtype_code(param.dtype), stream_ptr()),
+          "ssi_ema_update")

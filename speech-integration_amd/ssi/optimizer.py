@@ -8,10 +8,15 @@ clip coefficient (K12) folded in as a device-side gradient multiplier.  The grad
 next accumulation window overwrites it (``HipLlamaDecoder`` gradient-buffer protocol).  ``stochastic_rounding`` (bf16 only, off by default,
 not in the reference) rounds the three stores stochastically instead of to nearest, with stateless counter-based random bits.
 ``param_segments`` (config key ``param_groups``, null by default, not in the reference; ``ssi/param_groups.py``) gives consecutive ranges of
-the flat buffer their own lr scale, weight decay or a frozen flag: the step is still one launch, of the segmented kernel."""
+the flat buffer their own lr scale, weight decay or a frozen flag: the step is still one launch, of the segmented kernel.
+``ema_decay`` (config key of the same name, null by default, not in the reference) keeps an fp32 exponential moving average of the flat
+parameter buffer, one more HIP pass chained to every AdamW launch; ``ema_weights()`` evaluates on it, ``ema_state_dict()`` saves it."""
 
 from __future__ import annotations
 
+import contextlib
+import math
+import struct
 import weakref
 from typing import Any, Iterable
 
@@ -23,10 +28,21 @@ from .param_groups import check_segments, model_layout, resolve, trainable_range
 from .param_groups import clip as clip_segments
 
 
+def ema_decay_at(step: int, ema_decay: float, warmup: bool = True) -> float:
+    """The decay of the parameter average at the 1-based optimizer ``step``: ``ema_decay``, or with ``warmup`` ``min(ema_decay, (1 + step) /
+    (10 + step))`` — the first steps do not pin the average to the initial weights (step 1 keeps 2/11 of them, step 10 11/20).  Computed in
+    double and rounded to fp32 once, the value the kernel takes.  A function of the step alone: a resume needs no extra state."""
+    d = float(ema_decay)
+    if warmup:
+        d = min(d, (1.0 + int(step)) / (10.0 + int(step)))
+    return struct.unpack("f", struct.pack("f", d))[0]
+
+
 class HipAdamW(torch.optim.Optimizer):
     def __init__(self, params: Iterable, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, amsgrad: bool = False, fused: bool | None = None, *, model=None,
-                 stochastic_rounding: bool = False, stochastic_rounding_seed: int | None = None, param_segments=None, **unused: Any):
+                 stochastic_rounding: bool = False, stochastic_rounding_seed: int | None = None, param_segments=None,
+                 ema_decay: float | None = None, ema_warmup: bool = True, **unused: Any):
         if amsgrad:
             raise NotImplementedError("amsgrad=True is not supported (reference default: false, conf/training.yaml:8)")
         if unused:
@@ -65,6 +81,20 @@ class HipAdamW(torch.optim.Optimizer):
         self._views_ready = False
         self._side = None    # stream of the updates that run under the backward (overlap_with_backward)
         self._armed = None
+        # Exponential moving average of the parameters (not in the reference; off by default): fp32, the size of the flat buffer (+4 bytes per
+        # parameter: 5.0 GB at the 1B shape), started from the parameters as they are now and moved by one ssi_ema_update launch behind every
+        # AdamW launch of ``_update`` — so it follows the plain step, the segmented one, the deferred bucket under data parallelism and the
+        # buckets updated under the backward alike.  A bf16 run's iterates carry bf16 rounding noise; their fp32 average removes most of it.
+        # Like the rounding and the segments, flag and decay belong to the run's configuration, not to ``state_dict()``.
+        self._ema, self._ema_stash = None, None
+        self._ema_decay, self._ema_warmup = None, bool(ema_warmup)
+        if ema_decay is not None:
+            d = ema_decay
+            if isinstance(d, bool) or not isinstance(d, (int, float)) or not math.isfinite(d) or not 0 <= ema_decay_at(1, d, False) < 1:
+                raise ValueError(f"ema_decay must be null or a finite number in [0, 1) (as fp32), got {d!r}")
+            self._ema_decay = float(d)
+            self._ema = model._flat.to(torch.float32, copy=True)
+        self._ema_ranges = None if self._segments is None else trainable_ranges(self._segments)
 
     def _update(self, lo: int, hi: int, g: dict, step: int, scale: Tensor | None, skip_nonfinite_scale: bool = False) -> None:
         """AdamW on the elements ``[lo, hi)`` of the flat buffers: the plain kernel, or with segments the segmented one on those that reach
@@ -75,6 +105,7 @@ class HipAdamW(torch.optim.Optimizer):
             ops.adamw_step(*bufs, lr=float(g["lr"]), beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"],
                            step=step, grad_scale_dev=scale, zero_grad=False, skip_nonfinite_scale=skip_nonfinite_scale,
                            sr_seed=self._sr_seed, elem_offset=lo)
+            self._update_ema(lo, hi, step, scale, skip_nonfinite_scale)
             return
         segs = clip_segments(self._segments, lo, hi)
         if all(s.frozen for s in segs):
@@ -85,6 +116,70 @@ class HipAdamW(torch.optim.Optimizer):
                            seg_frozen=[s.frozen for s in segs], beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], step=step,
                            grad_scale_dev=scale, zero_grad=False, skip_nonfinite_scale=skip_nonfinite_scale, sr_seed=self._sr_seed,
                            elem_offset=lo)
+        self._update_ema(lo, hi, step, scale, skip_nonfinite_scale)
+
+    def _update_ema(self, lo: int, hi: int, step: int, scale: Tensor | None, skip_nonfinite_scale: bool) -> None:
+        """The average of the elements ``[lo, hi)`` follows their AdamW launch on the same stream: with segments one launch per maximal
+        trainable range inside the slice — a frozen element's average is never read or written and stays its initial value."""
+        if self._ema is None:
+            return
+        decay = ema_decay_at(step, self._ema_decay, self._ema_warmup)
+        guard = scale if skip_nonfinite_scale else None
+        for a, b in ([(lo, hi)] if self._ema_ranges is None else self._ema_ranges):
+            a, b = max(a, lo), min(b, hi)
+            if b > a:
+                ops.ema_update(self._ema[a:b], self.model._flat[a:b], decay=decay, guard_dev=guard)
+
+    # ---- the averaged weights ----------------------------------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside, the model holds the average rounded to nearest in its dtype (evaluate, save); on exit — also on an exception — the
+        parameters are back bit for bit.  Costs one stash of the flat buffer in the model's dtype for the time inside.  Not nestable, and not
+        while an overlap is armed (its updates would land in the swapped buffer)."""
+        if self._ema is None:
+            raise RuntimeError("ema_weights() needs an optimizer built with ema_decay")
+        if self._ema_stash is not None:
+            raise RuntimeError("ema_weights() is already active: it does not nest")
+        if self._armed is not None:
+            raise RuntimeError("ema_weights() while overlap_with_backward is armed: step() or cancel_overlap() first")
+        m = self.model
+        if self._side is not None:
+            torch.cuda.current_stream(m._flat.device).wait_stream(self._side)
+        self._ema_stash = m._flat.clone()
+        try:
+            with torch.no_grad():
+                m._flat.copy_(self._ema)
+            yield self
+        finally:
+            with torch.no_grad():
+                m._flat.copy_(self._ema_stash)
+            self._ema_stash = None
+
+    def _ema_views(self) -> dict[str, Tensor]:
+        if self._ema is None:
+            raise RuntimeError("the optimizer was built without ema_decay: there is no average")
+        m = self.model
+        names = {id(p): n for n, p in m.named_parameters()}
+        if self._side is not None:
+            torch.cuda.current_stream(m._flat.device).wait_stream(self._side)
+        return {names[id(p)]: m._view(name, rows, self._ema) for p, name, rows in m._param_src}
+
+    def ema_state_dict(self) -> dict[str, Tensor]:
+        """The fp32 averages by state-dict name (copies)."""
+        return {k: v.detach().clone() for k, v in self._ema_views().items()}
+
+    def load_ema_state_dict(self, sd) -> None:
+        """Strict on names and shapes; values are taken as fp32."""
+        own = self._ema_views()
+        missing, unexpected = [k for k in own if k not in sd], [k for k in sd if k not in own]
+        if missing or unexpected:
+            raise RuntimeError(f"Error(s) in loading the EMA state: missing keys {missing}, unexpected keys {unexpected}")
+        for k, v in own.items():
+            if tuple(sd[k].shape) != tuple(v.shape):
+                raise RuntimeError(f"size mismatch for {k}: EMA state {tuple(sd[k].shape)} vs model {tuple(v.shape)}")
+        with torch.no_grad():
+            for k, v in own.items():
+                v.copy_(sd[k].to(device=v.device, dtype=torch.float32))
 
     def _ensure_state_views(self) -> None:
         if self._views_ready:
@@ -221,6 +316,8 @@ class HipAdamW(torch.optim.Optimizer):
             step = int(float(st["step"]))
             st["step"] = torch.tensor(float(step))
         self._step_count = step
+        if self._ema is not None:   # the average restarts from what the model now holds; load_ema_state_dict puts a saved one back
+            self._ema.copy_(m._flat)
 
 
 def _to_container(node):
@@ -249,10 +346,15 @@ def setup_optimizer(cfg, model, optimizer_state_dict: dict[str, Any] | None = No
         optimizer_kwargs["param_segments"] = resolve(rules, layout, total, token_type_ranges)
     stochastic = bool(optimizer_kwargs.pop("stochastic_rounding", False))   # (both keys are this project's, not torch's)
     sr_seed = optimizer_kwargs.pop("stochastic_rounding_seed", None)
+    ema_decay = cfg.get("ema_decay") if hasattr(cfg, "get") else None   # (top level, with ema_warmup: the average is the run's, not AdamW's)
+    ema_warmup = cfg.get("ema_warmup", True) if hasattr(cfg, "get") else True
     if hasattr(model, "_flat"):
         optimizer = HipAdamW(model.parameters(), model=model, stochastic_rounding=stochastic, stochastic_rounding_seed=sr_seed,
-                             **optimizer_kwargs)
+                             ema_decay=ema_decay, ema_warmup=bool(ema_warmup), **optimizer_kwargs)
     else:  # foreign module (tests with stand-in models): the reference's own choice
+        if ema_decay is not None:
+            raise ValueError("ema_decay needs the HIP decoder (HipAdamW averages its flat parameter buffer); "
+                             f"{type(model).__name__} is updated by torch.optim.AdamW, which keeps no average")
         if stochastic:
             raise ValueError("optimizer.stochastic_rounding=true needs the HIP decoder (HipAdamW on its flat buffers); "
                              f"{type(model).__name__} is updated by torch.optim.AdamW, which has no such rounding")

@@ -126,6 +126,13 @@ def validate_train_cfg(cfg) -> None:
     if rules is not None and (isinstance(rules, (str, bytes)) or not hasattr(rules, "__len__") or hasattr(rules, "keys") or len(rules) == 0
                               or not all(hasattr(r, "keys") for r in rules)):
         raise ValueError(f"config field 'param_groups' must be null or a non-empty list of mappings, got {rules!r}")
+    d = cfg.get("ema_decay")
+    if d is not None and (isinstance(d, bool) or not isinstance(d, (int, float)) or not math.isfinite(d) or not 0 <= d < 1):
+        raise ValueError(f"config field 'ema_decay' must be null or a finite number in [0, 1), got {d!r}")
+    for name in ("ema_warmup", "ema_eval"):
+        value = cfg.get(name, True)
+        if not isinstance(value, bool):
+            raise ValueError(f"config field '{name}' must be true or false, got {value!r}")
 
 
 # training_state.pt (schema v1): key in the file -> name under which the trainer consumes it

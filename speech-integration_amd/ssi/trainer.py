@@ -399,6 +399,22 @@ class Trainer:
                                                num_training_steps=self.cfg.max_steps)
         if self._resume_state and self.lr_scheduler is not None:
             self.lr_scheduler.load_state_dict(self._resume_state["lr_scheduler_state"])
+        self._resume_ema()
+
+    def _resume_ema(self) -> None:
+        """(not in the reference) ``ema_decay`` on a resumed run: the fp32 averages of ``ema_state.safetensors`` beside the training state; without
+        that file (a state written by a run without the average) the average starts from the loaded weights."""
+        if self.cfg.get("ema_decay") is None or not self._resume_state:
+            return
+        from .checkpoint import EMA_STATE_FILENAME
+        path = os.path.join(os.path.dirname(os.path.abspath(str(self.checkpointer.training_state_checkpoint))), EMA_STATE_FILENAME)
+        if os.path.isfile(path):
+            from safetensors.torch import load_file
+            self.optimizer.load_ema_state_dict(load_file(path))
+            LOGGER.info(f"ema_decay: fp32 averages restored from {path}")
+        else:
+            LOGGER.warning(f"ema_decay is set but there is no {EMA_STATE_FILENAME} beside {self.checkpointer.training_state_checkpoint}: "
+                           "the parameter average starts from the loaded weights")
 
     def _setup_loss(self) -> None:
         self.loss_fn = CEWithChunkedOutputLoss()
@@ -732,17 +748,34 @@ class Trainer:
         self.dev_pairs = None
         if self.cfg.get("eval_pairs"):
             self.dev_pairs = self._score_pairs(str(self.cfg.eval_pairs))
-        kwargs = dict(epoch=self.global_step // self.geometry.steps_per_epoch, global_step=self.global_step,
-                      steps_per_epoch=self.geometry.steps_per_epoch, device=self.device,
-                      join_batches=int(self.cfg.get("eval_join_batches", 16) or 0) if self.cfg.get("padding_free", True) else 0,
-                      max_tokens=int(self.cfg.get("fused_window_max_tokens", 32768)), pad_id=int(getattr(self.tokenizer, "pad_id", 0) or 0),
-                      prefetch=int(self.cfg.get("prefetch_batches", 2) or 0))
+        kwargs = self._eval_kwargs()
         self.dev_metrics = None
         if not self.cfg.get("eval_token_metrics", False):
             return compute_dataset_loss(self.model, self.data_dev, self.loss_fn, **kwargs)
         self.dev_metrics = compute_dataset_metrics(self.model, self.data_dev, self.loss_fn, token_type_ranges=self.token_type_ranges,
                                                    topk=int(self.cfg.get("eval_topk", 5)), **kwargs)
         return self.dev_metrics["dev_loss"]
+
+    def _eval_kwargs(self) -> dict[str, Any]:
+        return dict(epoch=self.global_step // self.geometry.steps_per_epoch, global_step=self.global_step,
+                    steps_per_epoch=self.geometry.steps_per_epoch, device=self.device,
+                    join_batches=int(self.cfg.get("eval_join_batches", 16) or 0) if self.cfg.get("padding_free", True) else 0,
+                    max_tokens=int(self.cfg.get("fused_window_max_tokens", 32768)), pad_id=int(getattr(self.tokenizer, "pad_id", 0) or 0),
+                    prefetch=int(self.cfg.get("prefetch_batches", 2) or 0))
+
+    def _evaluate_ema(self) -> float | None:
+        """(not in the reference) ``ema_decay`` with ``ema_eval``: the dev loss once more, on the averaged weights (``HipAdamW.ema_weights``) — the
+        same ``compute_dataset_loss`` call; token metrics and pairs are not repeated.  The host generators are put back afterwards (a loader
+        draws its base seed from torch's when it is iterated), so the run goes on exactly as one without the average.  None: not configured."""
+        if self.cfg.get("ema_decay") is None or not self.cfg.get("ema_eval", True):
+            return None
+        from .checkpoint import restore_rng_states, save_rng_states
+        rng = save_rng_states()
+        with self.optimizer.ema_weights():
+            value = compute_dataset_loss(self.model, self.data_dev, self.loss_fn, **self._eval_kwargs())
+        restore_rng_states(rng)
+        LOGGER.info(f"Global Step {self.global_step} | Dev Loss on the averaged weights (ema_decay={self.cfg.get('ema_decay')}): {value:.4f}")
+        return value
 
     def _score_pairs(self, path: str) -> dict[str, Any]:
         """Every rank scores the whole file: the same forward on the same weights gives the same numbers everywhere, so there is no collective
@@ -764,7 +797,8 @@ class Trainer:
         its window closed (``_optimizer_step_lagged`` logs a step after the next one has been launched); without one, the current state.
         ``loss`` is always the cross-entropy part; ``aux`` holds the active auxiliary parts by name: with ``z_loss_coeff > 0`` the record also
         carries ``z_loss`` (coefficient applied, the same normalisation), with ``label_smoothing > 0`` ``smooth_loss`` (likewise:
-        ``objective = (1 - e) loss + smooth_loss + z_loss``), and ``dev_loss`` stays the plain cross-entropy."""
+        ``objective = (1 - e) loss + smooth_loss + z_loss``), and ``dev_loss`` stays the plain cross-entropy.  With ``ema_decay`` and
+        ``ema_eval`` a step that evaluates also carries ``dev_loss_ema``, the same dev loss on the averaged weights."""
         if snapshot is None:
             now = self._t_last_arrival = time.perf_counter()
             snapshot = {"global_step": self.global_step, "window_tokens": self.num_tokens_step, "lr": get_lr(self.optimizer), "now": now,
@@ -776,6 +810,7 @@ class Trainer:
         LOGGER.info(f"Epoch {epoch + 1:03d} | Iteration {iter_idx:0{width}d} / {self.geometry.batches_per_epoch} | Global Step {step} | "
                     f"Loss: {loss_to_log:.4f} | Tokens (num_tokens_step): {snapshot['window_tokens']}" + (f" | {per_type}" if per_type else ""))
         dev_loss = self._evaluate() if step % self.cfg.eval_steps == 0 else None
+        dev_loss_ema = self._evaluate_ema() if dev_loss is not None else None
         if step % self.cfg.log_interval:
             return
         ranks = self.world_size if (self.grad_sync is not None and self.world_size) else 1  # num_tokens_step is global under DP
@@ -798,6 +833,8 @@ class Trainer:
                 record.update(self.dev_metrics)
             if self.dev_pairs is not None:  # eval_pairs: dev_pair_acc, dev_pair_acc_mean, dev_pair_n
                 record.update(self.dev_pairs)
+            if dev_loss_ema is not None:  # ema_decay + ema_eval: the same dev loss on the averaged weights
+                record["dev_loss_ema"] = dev_loss_ema
         if self.rank == 0:
             self.wandb_logger.log_dict(record, step=step)
 
@@ -827,6 +864,12 @@ class Trainer:
             global_step=self.global_step, seed=SEED, training_hparams=self._data_position_hparams(), consumed_samples=self.consumed_samples,
             cumulative_metrics={"tokens_train_total": self.tokens_train_total, "token_type_counts": dict(self.token_type_counts_total),
                                 "wall_clock_seconds": elapsed})
+        if self.cfg.get("ema_decay") is not None:
+            # (not in the reference) the averaged weights, rounded to the model's dtype, as a checkpoint of their own under step_N/ema/ — it loads
+            # like any other (checkpointer.checkpoint_dir=.../step_N/ema) — and the fp32 averages beside training_state.pt for an exact resume
+            ema_state = self.optimizer.ema_state_dict()
+            with self.optimizer.ema_weights():
+                self.checkpointer.save_ema_checkpoint(self.model.state_dict(), ema_state, self.global_step)
 
     # === Cleanup =========================================================================================================
     def cleanup(self) -> None:
