@@ -497,7 +497,7 @@ extern "C" int ssi_doc_ranges(const int64_t* input_pos, int64_t batch, int64_t s
 }
 
 // =====================================================================================================================
-// K11 scale_grads, K12 sum of squares (for clip_grad_norm_), K13 AdamW — flat-buffer streaming kernels
+// K11 scale_grads, K12 sum of squares (for clip_grad_norm_) — flat-buffer streaming kernels (K13 AdamW follows its rounding and its table)
 // =====================================================================================================================
 template <typename T>
 __global__ __launch_bounds__(256) void scale_kernel(T* __restrict__ x, int64_t n, float scale, const float* scale_dev) {
@@ -564,71 +564,6 @@ extern "C" int ssi_sumsq(const void* x, int64_t n, int dtype, float* out, void* 
     return SSI_OK;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void adamw_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ m,
-                                                    T* __restrict__ v, int64_t n, float decay, float w1, float beta2,
-                                                    float w2, float eps, float step_size, float inv_bc2_sqrt,
-                                                    const float* __restrict__ grad_scale_dev, int zero_grad) {
-    constexpr int N = Vec16<T>::N;
-    const float gs = grad_scale_dev ? *grad_scale_dev : 1.f;
-    if ((zero_grad & 2) && !(fabsf(gs) < INFINITY)) return;  // bit 1: a non-finite scale (an accumulation window without a label) changes nothing
-    zero_grad &= 1;
-    const int64_t nvec = n / N;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
-        Vec16<T> pp = load16_nt(p + i * N), gg = load16_nt(g + i * N), mm = load16_nt(m + i * N), vv = load16_nt(v + i * N);
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            const float gr = gg.get(k) * gs;
-            float pf = pp.get(k);
-            pf *= decay;
-            const float mf = mm.get(k) + w1 * (gr - mm.get(k));
-            const float vf = beta2 * vv.get(k) + w2 * gr * gr;
-            const float denom = sqrtf(vf) * inv_bc2_sqrt + eps;
-            pf -= step_size * mf / denom;
-            pp.set(k, pf); mm.set(k, mf); vv.set(k, vf);
-            if (zero_grad) gg.set(k, 0.f);
-        }
-        store16_nt(p + i * N, pp); store16_nt(m + i * N, mm); store16_nt(v + i * N, vv);
-        if (zero_grad) store16_nt(g + i * N, gg);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n - nvec * N)) {
-        const int64_t i = nvec * N + threadIdx.x;
-        const float gr = to_f32<T>(g[i]) * gs;
-        float pf = to_f32<T>(p[i]);
-        pf *= decay;
-        const float mf = to_f32<T>(m[i]) + w1 * (gr - to_f32<T>(m[i]));
-        const float vf = beta2 * to_f32<T>(v[i]) + w2 * gr * gr;
-        pf -= step_size * mf / (sqrtf(vf) * inv_bc2_sqrt + eps);
-        p[i] = from_f32<T>(pf); m[i] = from_f32<T>(mf); v[i] = from_f32<T>(vf);
-        if (zero_grad) g[i] = from_f32<T>(0.f);
-    }
-}
-
-extern "C" int ssi_adamw_step(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, double lr, double beta1,
-                              double beta2, double eps, double weight_decay, int64_t step, const float* grad_scale_dev,
-                              int zero_grad, int dtype, void* stream) {
-    SSI_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n >= 0 && step >= 1);
-    SSI_CHECK_ARG(((uintptr_t)param % 16) == 0 && ((uintptr_t)grad % 16) == 0 && ((uintptr_t)exp_avg % 16) == 0 &&
-                  ((uintptr_t)exp_avg_sq % 16) == 0);
-    if (n == 0) return SSI_OK;
-    // every coefficient in double from the double hyper-parameters, then rounded once to fp32, as torch's fused AdamW does: 1 - (float)0.999
-    // is 1.3e-5 away from (float)(1 - 0.999), which moved ~0.5 % of the bf16 exp_avg_sq (and, through the cancellations of m, ~4 % of the
-    // exp_avg) a bf16 step away from the reference's within 7 steps
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    const float step_size = (float)(lr / bc1);
-    const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-    // 17 GB touched once: non-temporal accesses and as many short blocks as there are 16-byte vectors (no grid-stride loop at the model's
-    // size: 608 k blocks).  tools/adamw_bench.py, 1.246 G bf16 parameters: 8192 long-lived blocks 5.5 TB/s, 32768 6.2, 131072 6.3, one vector
-    // per thread 6.47 TB/s (2.70 ms); two vectors per thread with all eight loads in flight first: 6.1
-    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(adamw_kernel<T>, dim3(stream_grid(n / Vec16<T>::N + 1, 1 << 20)), dim3(256), 0,
-                                                 (hipStream_t)stream, (T*)param, (T*)grad, (T*)exp_avg, (T*)exp_avg_sq, n,
-                                                 (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2,
-                                                 (float)(1.0 - beta2), (float)eps, step_size, inv_bc2_sqrt,
-                                                 grad_scale_dev, zero_grad));
-    SSI_LAUNCH_CHECK();
-    return SSI_OK;
-}
-
 // =====================================================================================================================
 // K13s AdamW with stochastic rounding of the three bf16 stores (ABI v11; opt-in, HipAdamW(stochastic_rounding=True)).  Round-to-nearest
 // drops every update below half a bf16 step: v * 0.999 rounds back to v for every bf16 v, and a weight at 1.0 never moves at lr 2e-4
@@ -665,74 +600,6 @@ __device__ __forceinline__ unsigned short sr_bf16(float x, const Philox4& b, int
 }
 __device__ __forceinline__ bf16_t sr_bf16_value(float x, const Philox4& b, int k) { return __builtin_bit_cast(bf16_t, sr_bf16(x, b, k)); }
 
-// adamw_kernel<bf16_t> with the three stores rounded by sr_bf16: the fp32 arithmetic is that kernel's, expression for expression
-__global__ __launch_bounds__(256) void adamw_sr_kernel(bf16_t* __restrict__ p, bf16_t* __restrict__ g, bf16_t* __restrict__ m,
-                                                       bf16_t* __restrict__ v, int64_t n, float decay, float w1, float beta2, float w2,
-                                                       float eps, float step_size, float inv_bc2_sqrt,
-                                                       const float* __restrict__ grad_scale_dev, int zero_grad, uint64_t seed,
-                                                       uint32_t step, int64_t vec_offset) {
-    using T = bf16_t;
-    constexpr int N = Vec16<T>::N;
-    static_assert(N == 8, "one Philox call per tensor covers the 8 elements of a 16-byte vector");
-    const float gs = grad_scale_dev ? *grad_scale_dev : 1.f;
-    if ((zero_grad & 2) && !(fabsf(gs) < INFINITY)) return;
-    zero_grad &= 1;
-    const int64_t nvec = n / N;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
-        Vec16<T> pp = load16_nt(p + i * N), gg = load16_nt(g + i * N), mm = load16_nt(m + i * N), vv = load16_nt(v + i * N);
-        const Philox4 rp = sr_bits(vec_offset + i, step, 0, seed), rm = sr_bits(vec_offset + i, step, 1, seed),
-                      rv = sr_bits(vec_offset + i, step, 2, seed);
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            const float gr = gg.get(k) * gs;
-            float pf = pp.get(k);
-            pf *= decay;
-            const float mf = mm.get(k) + w1 * (gr - mm.get(k));
-            const float vf = beta2 * vv.get(k) + w2 * gr * gr;
-            const float denom = sqrtf(vf) * inv_bc2_sqrt + eps;
-            pf -= step_size * mf / denom;
-            pp.v[k] = sr_bf16_value(pf, rp, k); mm.v[k] = sr_bf16_value(mf, rm, k); vv.v[k] = sr_bf16_value(vf, rv, k);
-            if (zero_grad) gg.set(k, 0.f);
-        }
-        store16_nt(p + i * N, pp); store16_nt(m + i * N, mm); store16_nt(v + i * N, vv);
-        if (zero_grad) store16_nt(g + i * N, gg);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n - nvec * N)) {
-        const int k = threadIdx.x;   // the slice starts on a vector boundary of the global index, so the tail is the head of vector vec_offset + nvec
-        const int64_t i = nvec * N + k;
-        const float gr = to_f32<T>(g[i]) * gs;
-        float pf = to_f32<T>(p[i]);
-        pf *= decay;
-        const float mf = to_f32<T>(m[i]) + w1 * (gr - to_f32<T>(m[i]));
-        const float vf = beta2 * to_f32<T>(v[i]) + w2 * gr * gr;
-        pf -= step_size * mf / (sqrtf(vf) * inv_bc2_sqrt + eps);
-        p[i] = sr_bf16_value(pf, sr_bits(vec_offset + nvec, step, 0, seed), k);
-        m[i] = sr_bf16_value(mf, sr_bits(vec_offset + nvec, step, 1, seed), k);
-        v[i] = sr_bf16_value(vf, sr_bits(vec_offset + nvec, step, 2, seed), k);
-        if (zero_grad) g[i] = from_f32<T>(0.f);
-    }
-}
-
-extern "C" int ssi_adamw_step_sr(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, double lr, double beta1,
-                                 double beta2, double eps, double weight_decay, int64_t step, const float* grad_scale_dev,
-                                 int zero_grad, int dtype, uint64_t seed, int64_t elem_offset, void* stream) {
-    SSI_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n >= 0 && step >= 1 && step < ((int64_t)1 << 32));
-    SSI_CHECK_ARG(((uintptr_t)param % 16) == 0 && ((uintptr_t)grad % 16) == 0 && ((uintptr_t)exp_avg % 16) == 0 &&
-                  ((uintptr_t)exp_avg_sq % 16) == 0);
-    SSI_CHECK_ARG(dtype == SSI_BF16);   // fp32 storage has nothing to round
-    SSI_CHECK_ARG(elem_offset >= 0 && elem_offset % 8 == 0);
-    if (n == 0) return SSI_OK;
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);   // the coefficients of ssi_adamw_step
-    const float step_size = (float)(lr / bc1);
-    const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-    hipLaunchKernelGGL(adamw_sr_kernel, dim3(stream_grid(n / 8 + 1, 1 << 20)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)param,
-                       (bf16_t*)grad, (bf16_t*)exp_avg, (bf16_t*)exp_avg_sq, n, (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1),
-                       (float)beta2, (float)(1.0 - beta2), (float)eps, step_size, inv_bc2_sqrt, grad_scale_dev, zero_grad, seed,
-                       (uint32_t)step, elem_offset / 8);
-    SSI_LAUNCH_CHECK();
-    return SSI_OK;
-}
-
 // =====================================================================================================================
 // K13g AdamW over SEGMENTS of the flat buffers (ABI v16; opt-in, HipAdamW(param_segments=...)): consecutive element ranges with their own
 // lr, weight decay and frozen flag in ONE launch.  The table travels by value in the kernel arguments (no device allocation, no copy
@@ -740,7 +607,7 @@ extern "C" int ssi_adamw_step_sr(void* param, void* grad, void* exp_avg, void* e
 // UNITS of 8 elements, 32 bits per end.  A block finds the segment of its first unit with wave-uniform indices only (scalar loads, two
 // dependent rounds: 8 coarse ends, then the 16 ends of one chunk), walks the segments that reach into its 256 vectors (one, almost always)
 // and lets every lane keep the coefficients of the segment its vector lies in.  A lane of a frozen segment issues no load and no store.  The
-// fp32 arithmetic is adamw_kernel's, expression for expression, and the random bits are adamw_sr_kernel's: a function of the global index.
+// random bits are a function of the global element index, so a segment is bit-equal to the plain kernel run on it alone.
 // =====================================================================================================================
 struct AdamwSegTable {
     uint32_t end8[SSI_ADAMW_MAX_SEGS];        // exclusive end of segment s in units of 8 elements (the last: rounded up); unused: 0xFFFFFFFF
@@ -773,111 +640,166 @@ __device__ __forceinline__ bool adamw_seg_lookup(const AdamwSegTable& t, uint32_
     return active;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void adamw_seg_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ m, T* __restrict__ v, int64_t n,
-                                                        const AdamwSegTable tab, float w1, float beta2, float w2, float eps, float inv_bc2_sqrt,
-                                                        const float* __restrict__ grad_scale_dev, int zero_grad) {
+// =====================================================================================================================
+// K13 AdamW: ONE element function and ONE body behind the four kernels.  SR: the three stores round stochastically; SEG: decay and step_size
+// come per segment from the table.  Built with -ffp-contract=fast, the variants agree bit for bit because the arithmetic is written once.
+// =====================================================================================================================
+struct AdamwCoef { float w1, beta2, w2, eps, inv_bc2_sqrt; };           // what every element of a launch shares
+struct AdamwSr { uint64_t seed; uint32_t step; int64_t vec_offset; };   // SR: the generator's key and the slice's first vector in the global index
+
+// fp32 -> storage, element k of its vector: to nearest, or (SR) by the vector's random bits b
+template <typename T, bool SR> __device__ __forceinline__ T adamw_rounded(float x, const Philox4& b, int k) {
+    if constexpr (SR) return sr_bf16_value(x, b, k);
+    else return from_f32<T>(x);
+}
+
+__device__ __forceinline__ void adamw_elem(float& pf, float& mf, float& vf, float gr, float decay, float step_size, const AdamwCoef& c) {
+    pf *= decay;
+    mf = mf + c.w1 * (gr - mf);
+    vf = c.beta2 * vf + c.w2 * gr * gr;
+    const float denom = sqrtf(vf) * c.inv_bc2_sqrt + c.eps;
+    pf -= step_size * mf / denom;
+}
+
+template <typename T, bool SEG, bool SR>
+__device__ __forceinline__ void adamw_body(T* __restrict__ p, T* __restrict__ g, T* __restrict__ m, T* __restrict__ v, int64_t n,
+                                           const AdamwSegTable* tab, float decay, float step_size, const AdamwCoef c,
+                                           const float* __restrict__ grad_scale_dev, int zero_grad, const AdamwSr sr) {
     constexpr int N = Vec16<T>::N;
+    static_assert(!SR || N == 8, "one Philox call per tensor covers the 8 elements of a 16-byte vector");
     const float gs = grad_scale_dev ? *grad_scale_dev : 1.f;
-    if ((zero_grad & 2) && !(fabsf(gs) < INFINITY)) return;  // bit 1: a non-finite scale changes nothing
+    if ((zero_grad & 2) && !(fabsf(gs) < INFINITY)) return;  // bit 1: a non-finite scale (an accumulation window without a label) changes nothing
     zero_grad &= 1;
     const int64_t nvec = n / N;
-    for (int64_t b = (int64_t)blockIdx.x * 256; b < nvec; b += (int64_t)gridDim.x * 256) {
-        const int64_t i = b + threadIdx.x;
-        float decay = 0.f, step_size = 0.f;
-        const bool active = adamw_seg_lookup(tab, (uint32_t)((b * N) >> 3), (uint32_t)(((b + 255) * N) >> 3), (uint32_t)((i * N) >> 3), decay, step_size);
-        if (!active || i >= nvec) continue;
+    // one vector per thread and trip.  Plain: b is the thread's vector.  SEG: b is the block's first vector, which the lookup needs wave-uniform
+    for (int64_t b = (int64_t)blockIdx.x * 256 + (SEG ? 0 : threadIdx.x); b < nvec; b += (int64_t)gridDim.x * 256) {
+        const int64_t i = SEG ? b + threadIdx.x : b;
+        if constexpr (SEG) {
+            const bool active = adamw_seg_lookup(*tab, (uint32_t)((b * N) >> 3), (uint32_t)(((b + 255) * N) >> 3), (uint32_t)((i * N) >> 3), decay, step_size);
+            if (!active || i >= nvec) continue;
+        }
         Vec16<T> pp = load16_nt(p + i * N), gg = load16_nt(g + i * N), mm = load16_nt(m + i * N), vv = load16_nt(v + i * N);
+        // one generator call per tensor and vector; only the SR stores read the bits, so without SR none is compiled
+        const Philox4 rp = sr_bits(sr.vec_offset + i, sr.step, 0, sr.seed), rm = sr_bits(sr.vec_offset + i, sr.step, 1, sr.seed),
+                      rv = sr_bits(sr.vec_offset + i, sr.step, 2, sr.seed);
 #pragma unroll
         for (int k = 0; k < N; ++k) {
-            const float gr = gg.get(k) * gs;
-            float pf = pp.get(k);
-            pf *= decay;
-            const float mf = mm.get(k) + w1 * (gr - mm.get(k));
-            const float vf = beta2 * vv.get(k) + w2 * gr * gr;
-            const float denom = sqrtf(vf) * inv_bc2_sqrt + eps;
-            pf -= step_size * mf / denom;
-            pp.set(k, pf); mm.set(k, mf); vv.set(k, vf);
+            float pf = pp.get(k), mf = mm.get(k), vf = vv.get(k);
+            adamw_elem(pf, mf, vf, gg.get(k) * gs, decay, step_size, c);
+            pp.v[k] = adamw_rounded<T, SR>(pf, rp, k); mm.v[k] = adamw_rounded<T, SR>(mf, rm, k); vv.v[k] = adamw_rounded<T, SR>(vf, rv, k);
             if (zero_grad) gg.set(k, 0.f);
         }
         store16_nt(p + i * N, pp); store16_nt(m + i * N, mm); store16_nt(v + i * N, vv);
         if (zero_grad) store16_nt(g + i * N, gg);
     }
-    const int last = tab.n_segs - 1;   // the ragged tail belongs to the last segment
-    if (blockIdx.x == 0 && threadIdx.x < (n - nvec * N) && !((tab.frozen[last >> 5] >> (last & 31)) & 1u)) {
-        const float decay = tab.decay[last], step_size = tab.step_size[last];
-        const int64_t i = nvec * N + threadIdx.x;
-        const float gr = to_f32<T>(g[i]) * gs;
-        float pf = to_f32<T>(p[i]);
-        pf *= decay;
-        const float mf = to_f32<T>(m[i]) + w1 * (gr - to_f32<T>(m[i]));
-        const float vf = beta2 * to_f32<T>(v[i]) + w2 * gr * gr;
-        pf -= step_size * mf / (sqrtf(vf) * inv_bc2_sqrt + eps);
-        p[i] = from_f32<T>(pf); m[i] = from_f32<T>(mf); v[i] = from_f32<T>(vf);
+    if (blockIdx.x == 0 && threadIdx.x < (n - nvec * N)) {
+        if constexpr (SEG) {
+            const int last = tab->n_segs - 1;   // the ragged tail belongs to the last segment
+            if ((tab->frozen[last >> 5] >> (last & 31)) & 1u) return;
+            decay = tab->decay[last];
+            step_size = tab->step_size[last];
+        }
+        const int k = threadIdx.x;   // SR: the slice starts on a vector boundary of the global index, so the tail is the head of vector vec_offset + nvec
+        const int64_t i = nvec * N + k;
+        float pf = to_f32<T>(p[i]), mf = to_f32<T>(m[i]), vf = to_f32<T>(v[i]);
+        adamw_elem(pf, mf, vf, to_f32<T>(g[i]) * gs, decay, step_size, c);
+        p[i] = adamw_rounded<T, SR>(pf, sr_bits(sr.vec_offset + nvec, sr.step, 0, sr.seed), k);
+        m[i] = adamw_rounded<T, SR>(mf, sr_bits(sr.vec_offset + nvec, sr.step, 1, sr.seed), k);
+        v[i] = adamw_rounded<T, SR>(vf, sr_bits(sr.vec_offset + nvec, sr.step, 2, sr.seed), k);
         if (zero_grad) g[i] = from_f32<T>(0.f);
     }
 }
 
-// adamw_seg_kernel<bf16_t> with the three stores rounded by sr_bf16, as adamw_sr_kernel is to adamw_kernel
+template <typename T>
+__global__ __launch_bounds__(256) void adamw_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ m,
+                                                    T* __restrict__ v, int64_t n, float decay, float w1, float beta2,
+                                                    float w2, float eps, float step_size, float inv_bc2_sqrt,
+                                                    const float* __restrict__ grad_scale_dev, int zero_grad) {
+    adamw_body<T, false, false>(p, g, m, v, n, nullptr, decay, step_size, AdamwCoef{w1, beta2, w2, eps, inv_bc2_sqrt}, grad_scale_dev, zero_grad, AdamwSr{});
+}
+
+__global__ __launch_bounds__(256) void adamw_sr_kernel(bf16_t* __restrict__ p, bf16_t* __restrict__ g, bf16_t* __restrict__ m,
+                                                       bf16_t* __restrict__ v, int64_t n, float decay, float w1, float beta2, float w2,
+                                                       float eps, float step_size, float inv_bc2_sqrt,
+                                                       const float* __restrict__ grad_scale_dev, int zero_grad, uint64_t seed,
+                                                       uint32_t step, int64_t vec_offset) {
+    adamw_body<bf16_t, false, true>(p, g, m, v, n, nullptr, decay, step_size, AdamwCoef{w1, beta2, w2, eps, inv_bc2_sqrt}, grad_scale_dev, zero_grad,
+                                    AdamwSr{seed, step, vec_offset});
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void adamw_seg_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ m, T* __restrict__ v, int64_t n,
+                                                        const AdamwSegTable tab, float w1, float beta2, float w2, float eps, float inv_bc2_sqrt,
+                                                        const float* __restrict__ grad_scale_dev, int zero_grad) {
+    adamw_body<T, true, false>(p, g, m, v, n, &tab, 0.f, 0.f, AdamwCoef{w1, beta2, w2, eps, inv_bc2_sqrt}, grad_scale_dev, zero_grad, AdamwSr{});
+}
+
 __global__ __launch_bounds__(256) void adamw_seg_sr_kernel(bf16_t* __restrict__ p, bf16_t* __restrict__ g, bf16_t* __restrict__ m,
                                                            bf16_t* __restrict__ v, int64_t n, const AdamwSegTable tab, float w1, float beta2,
                                                            float w2, float eps, float inv_bc2_sqrt, const float* __restrict__ grad_scale_dev,
                                                            int zero_grad, uint64_t seed, uint32_t step, int64_t vec_offset) {
-    using T = bf16_t;
-    constexpr int N = Vec16<T>::N;
-    static_assert(N == 8, "one Philox call per tensor covers the 8 elements of a 16-byte vector");
-    const float gs = grad_scale_dev ? *grad_scale_dev : 1.f;
-    if ((zero_grad & 2) && !(fabsf(gs) < INFINITY)) return;
-    zero_grad &= 1;
-    const int64_t nvec = n / N;
-    for (int64_t b = (int64_t)blockIdx.x * 256; b < nvec; b += (int64_t)gridDim.x * 256) {
-        const int64_t i = b + threadIdx.x;
-        float decay = 0.f, step_size = 0.f;
-        const bool active = adamw_seg_lookup(tab, (uint32_t)b, (uint32_t)(b + 255), (uint32_t)i, decay, step_size);
-        if (!active || i >= nvec) continue;
-        Vec16<T> pp = load16_nt(p + i * N), gg = load16_nt(g + i * N), mm = load16_nt(m + i * N), vv = load16_nt(v + i * N);
-        const Philox4 rp = sr_bits(vec_offset + i, step, 0, seed), rm = sr_bits(vec_offset + i, step, 1, seed),
-                      rv = sr_bits(vec_offset + i, step, 2, seed);
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            const float gr = gg.get(k) * gs;
-            float pf = pp.get(k);
-            pf *= decay;
-            const float mf = mm.get(k) + w1 * (gr - mm.get(k));
-            const float vf = beta2 * vv.get(k) + w2 * gr * gr;
-            const float denom = sqrtf(vf) * inv_bc2_sqrt + eps;
-            pf -= step_size * mf / denom;
-            pp.v[k] = sr_bf16_value(pf, rp, k); mm.v[k] = sr_bf16_value(mf, rm, k); vv.v[k] = sr_bf16_value(vf, rv, k);
-            if (zero_grad) gg.set(k, 0.f);
-        }
-        store16_nt(p + i * N, pp); store16_nt(m + i * N, mm); store16_nt(v + i * N, vv);
-        if (zero_grad) store16_nt(g + i * N, gg);
-    }
-    const int last = tab.n_segs - 1;
-    if (blockIdx.x == 0 && threadIdx.x < (n - nvec * N) && !((tab.frozen[last >> 5] >> (last & 31)) & 1u)) {
-        const float decay = tab.decay[last], step_size = tab.step_size[last];
-        const int k = threadIdx.x;   // the tail is the head of vector vec_offset + nvec of the global index
-        const int64_t i = nvec * N + k;
-        const float gr = to_f32<T>(g[i]) * gs;
-        float pf = to_f32<T>(p[i]);
-        pf *= decay;
-        const float mf = to_f32<T>(m[i]) + w1 * (gr - to_f32<T>(m[i]));
-        const float vf = beta2 * to_f32<T>(v[i]) + w2 * gr * gr;
-        pf -= step_size * mf / (sqrtf(vf) * inv_bc2_sqrt + eps);
-        p[i] = sr_bf16_value(pf, sr_bits(vec_offset + nvec, step, 0, seed), k);
-        m[i] = sr_bf16_value(mf, sr_bits(vec_offset + nvec, step, 1, seed), k);
-        v[i] = sr_bf16_value(vf, sr_bits(vec_offset + nvec, step, 2, seed), k);
-        if (zero_grad) g[i] = from_f32<T>(0.f);
-    }
+    adamw_body<bf16_t, true, true>(p, g, m, v, n, &tab, 0.f, 0.f, AdamwCoef{w1, beta2, w2, eps, inv_bc2_sqrt}, grad_scale_dev, zero_grad,
+                                   AdamwSr{seed, step, vec_offset});
+}
+
+static int adamw_check_buffers(const void* param, const void* grad, const void* exp_avg, const void* exp_avg_sq, int64_t n, int64_t step) {
+    SSI_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n >= 0 && step >= 1);
+    SSI_CHECK_ARG(((uintptr_t)param % 16) == 0 && ((uintptr_t)grad % 16) == 0 && ((uintptr_t)exp_avg % 16) == 0 &&
+                  ((uintptr_t)exp_avg_sq % 16) == 0);
+    return SSI_OK;
+}
+
+// A step's coefficients: every one in double from the double hyper-parameters, then rounded once to fp32, as torch's fused AdamW does:
+// 1 - (float)0.999 is 1.3e-5 away from (float)(1 - 0.999), which moved ~0.5 % of the bf16 exp_avg_sq (and, through the cancellations of m,
+// ~4 % of the exp_avg) a bf16 step away from the reference's within 7 steps
+struct AdamwStep {
+    double bc1;   // 1 - beta1^step, kept in double for step_size
+    AdamwCoef c;
+    AdamwStep(double beta1, double beta2, double eps, int64_t step)
+        : bc1(1.0 - pow(beta1, (double)step)),
+          c{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)(1.0 / sqrt(1.0 - pow(beta2, (double)step)))} {}
+    float decay(double lr, double weight_decay) const { return (float)(1.0 - lr * weight_decay); }
+    float step_size(double lr) const { return (float)(lr / bc1); }
+};
+
+// 17 GB touched once: non-temporal accesses and as many short blocks as there are 16-byte vectors (no grid-stride loop at the model's
+// size: 608 k blocks).  tools/adamw_bench.py, 1.246 G bf16 parameters: 8192 long-lived blocks 5.5 TB/s, 32768 6.2, 131072 6.3, one vector
+// per thread 6.47 TB/s (2.70 ms); two vectors per thread with all eight loads in flight first: 6.1
+template <typename T> static dim3 adamw_grid(int64_t n) { return dim3(stream_grid(n / Vec16<T>::N + 1, 1 << 20)); }
+
+extern "C" int ssi_adamw_step(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, double lr, double beta1,
+                              double beta2, double eps, double weight_decay, int64_t step, const float* grad_scale_dev,
+                              int zero_grad, int dtype, void* stream) {
+    if (const int rc = adamw_check_buffers(param, grad, exp_avg, exp_avg_sq, n, step)) return rc;
+    if (n == 0) return SSI_OK;
+    const AdamwStep s(beta1, beta2, eps, step);
+    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(adamw_kernel<T>, adamw_grid<T>(n), dim3(256), 0, (hipStream_t)stream, (T*)param, (T*)grad,
+                                                 (T*)exp_avg, (T*)exp_avg_sq, n, s.decay(lr, weight_decay), s.c.w1, s.c.beta2, s.c.w2, s.c.eps,
+                                                 s.step_size(lr), s.c.inv_bc2_sqrt, grad_scale_dev, zero_grad));
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+extern "C" int ssi_adamw_step_sr(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, double lr, double beta1,
+                                 double beta2, double eps, double weight_decay, int64_t step, const float* grad_scale_dev,
+                                 int zero_grad, int dtype, uint64_t seed, int64_t elem_offset, void* stream) {
+    if (const int rc = adamw_check_buffers(param, grad, exp_avg, exp_avg_sq, n, step)) return rc;
+    SSI_CHECK_ARG(dtype == SSI_BF16);   // fp32 storage has nothing to round
+    SSI_CHECK_ARG(step < ((int64_t)1 << 32) && elem_offset >= 0 && elem_offset % 8 == 0);
+    if (n == 0) return SSI_OK;
+    const AdamwStep s(beta1, beta2, eps, step);
+    hipLaunchKernelGGL(adamw_sr_kernel, adamw_grid<bf16_t>(n), dim3(256), 0, (hipStream_t)stream, (bf16_t*)param, (bf16_t*)grad,
+                       (bf16_t*)exp_avg, (bf16_t*)exp_avg_sq, n, s.decay(lr, weight_decay), s.c.w1, s.c.beta2, s.c.w2, s.c.eps, s.step_size(lr),
+                       s.c.inv_bc2_sqrt, grad_scale_dev, zero_grad, seed, (uint32_t)step, elem_offset / 8);
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
 }
 
 extern "C" int ssi_adamw_step_seg(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, const int64_t* seg_end,
                                   const double* seg_lr, const double* seg_weight_decay, const int32_t* seg_frozen, int n_segs,
                                   double beta1, double beta2, double eps, int64_t step, const float* grad_scale_dev, int zero_grad,
                                   int dtype, int stochastic, uint64_t seed, int64_t elem_offset, void* stream) {
-    SSI_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n >= 0 && step >= 1);
-    SSI_CHECK_ARG(((uintptr_t)param % 16) == 0 && ((uintptr_t)grad % 16) == 0 && ((uintptr_t)exp_avg % 16) == 0 &&
-                  ((uintptr_t)exp_avg_sq % 16) == 0);
+    if (const int rc = adamw_check_buffers(param, grad, exp_avg, exp_avg_sq, n, step)) return rc;
     SSI_CHECK_ARG(seg_end && seg_lr && seg_weight_decay && seg_frozen && n_segs >= 1);
     SSI_CHECK_ARG(dtype == SSI_F32 || dtype == SSI_BF16);
     if (stochastic) SSI_CHECK_ARG(dtype == SSI_BF16 && step < ((int64_t)1 << 32) && elem_offset >= 0 && elem_offset % 8 == 0);
@@ -895,8 +817,7 @@ extern "C" int ssi_adamw_step_seg(void* param, void* grad, void* exp_avg, void* 
     if (s0 == n_segs) return SSI_OK;
     while (seg_frozen[s1 - 1]) --s1;
     const int64_t lo = s0 ? seg_end[s0 - 1] : 0, nn = seg_end[s1 - 1] - lo;
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);   // the coefficients of ssi_adamw_step
-    const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+    const AdamwStep st(beta1, beta2, eps, step);
     AdamwSegTable tab;
     for (int s = 0; s < SSI_ADAMW_MAX_SEGS; ++s) { tab.end8[s] = 0xFFFFFFFFu; tab.decay[s] = 1.f; tab.step_size[s] = 0.f; }
     for (int k = 0; k < SSI_ADAMW_MAX_SEGS / 32; ++k) tab.frozen[k] = 0u;
@@ -904,22 +825,21 @@ extern "C" int ssi_adamw_step_seg(void* param, void* grad, void* exp_avg, void* 
     for (int s = s0; s < s1; ++s) {
         const int j = s - s0;
         tab.end8[j] = (uint32_t)((seg_end[s] - lo + 7) / 8);
-        tab.decay[j] = (float)(1.0 - seg_lr[s] * seg_weight_decay[s]);
-        tab.step_size[j] = (float)(seg_lr[s] / bc1);
+        tab.decay[j] = st.decay(seg_lr[s], seg_weight_decay[s]);
+        tab.step_size[j] = st.step_size(seg_lr[s]);
         if (seg_frozen[s]) tab.frozen[j >> 5] |= 1u << (j & 31);
     }
     for (int k = 0; k < SSI_ADAMW_MAX_SEGS / 16; ++k) tab.coarse[k] = tab.end8[16 * k + 15];
     const size_t esz = dtype == SSI_BF16 ? 2 : 4;   // lo is a multiple of 8 elements: the 16-byte alignment holds
     char *pp = (char*)param + lo * esz, *gp = (char*)grad + lo * esz, *mp = (char*)exp_avg + lo * esz, *vp = (char*)exp_avg_sq + lo * esz;
     if (stochastic) {
-        hipLaunchKernelGGL(adamw_seg_sr_kernel, dim3(stream_grid(nn / 8 + 1, 1 << 20)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)pp,
-                           (bf16_t*)gp, (bf16_t*)mp, (bf16_t*)vp, nn, tab, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
-                           (float)eps, inv_bc2_sqrt, grad_scale_dev, zero_grad, seed, (uint32_t)step, (elem_offset + lo) / 8);
+        hipLaunchKernelGGL(adamw_seg_sr_kernel, adamw_grid<bf16_t>(nn), dim3(256), 0, (hipStream_t)stream, (bf16_t*)pp, (bf16_t*)gp, (bf16_t*)mp,
+                           (bf16_t*)vp, nn, tab, st.c.w1, st.c.beta2, st.c.w2, st.c.eps, st.c.inv_bc2_sqrt, grad_scale_dev, zero_grad, seed,
+                           (uint32_t)step, (elem_offset + lo) / 8);
     } else {
-        SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(adamw_seg_kernel<T>, dim3(stream_grid(nn / Vec16<T>::N + 1, 1 << 20)), dim3(256), 0,
-                                                     (hipStream_t)stream, (T*)pp, (T*)gp, (T*)mp, (T*)vp, nn, tab, (float)(1.0 - beta1),
-                                                     (float)beta2, (float)(1.0 - beta2), (float)eps, inv_bc2_sqrt, grad_scale_dev,
-                                                     zero_grad));
+        SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(adamw_seg_kernel<T>, adamw_grid<T>(nn), dim3(256), 0, (hipStream_t)stream, (T*)pp, (T*)gp,
+                                                     (T*)mp, (T*)vp, nn, tab, st.c.w1, st.c.beta2, st.c.w2, st.c.eps, st.c.inv_bc2_sqrt,
+                                                     grad_scale_dev, zero_grad));
     }
     SSI_LAUNCH_CHECK();
     return SSI_OK;

@@ -459,6 +459,14 @@ def sumsq(x: Tensor, out: Tensor, workspace: Tensor | None = None) -> None:
                         workspace.numel() * workspace.element_size(), stream_ptr()), "ssi_sumsq")
 
 
+def _adamw_flags(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, zero_grad: bool, skip_nonfinite_scale: bool) -> int:
+    """The AdamW entries' ``zero_grad`` argument, after the checks on the four buffers that they share."""
+    assert param.is_contiguous() and grad.is_contiguous() and exp_avg.is_contiguous() and exp_avg_sq.is_contiguous()
+    assert param.numel() == grad.numel() == exp_avg.numel() == exp_avg_sq.numel()
+    assert param.dtype == grad.dtype == exp_avg.dtype == exp_avg_sq.dtype
+    return int(zero_grad) | (2 if skip_nonfinite_scale else 0)
+
+
 def adamw_step(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, *, lr: float, beta1: float, beta2: float,
                eps: float, weight_decay: float, step: int, grad_scale_dev: Tensor | None = None,
                zero_grad: bool = False, skip_nonfinite_scale: bool = False, sr_seed: int | None = None, elem_offset: int = 0) -> None:
@@ -466,10 +474,7 @@ def adamw_step(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor,
     a window's optimizer step; an update issued before the host knows the count must do the same by itself).  ``sr_seed`` (bf16 only): the three
     stores round stochastically (``ssi_adamw_step_sr``) with the random bits of ``(sr_seed, step, elem_offset + i, tensor)`` — ``elem_offset``
     is the place of the slice's first element in the whole buffer, a multiple of 8; without a seed it is not used."""
-    assert param.is_contiguous() and grad.is_contiguous() and exp_avg.is_contiguous() and exp_avg_sq.is_contiguous()
-    assert param.numel() == grad.numel() == exp_avg.numel() == exp_avg_sq.numel()
-    assert param.dtype == grad.dtype == exp_avg.dtype == exp_avg_sq.dtype
-    flags = int(zero_grad) | (2 if skip_nonfinite_scale else 0)
+    flags = _adamw_flags(param, grad, exp_avg, exp_avg_sq, zero_grad, skip_nonfinite_scale)
     if sr_seed is not None:
         check(_lib.load().ssi_adamw_step_sr(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), lr, beta1, beta2,
                                             eps, weight_decay, step, ptr(grad_scale_dev), flags, dtype_code(param.dtype),
@@ -487,12 +492,9 @@ def adamw_step_seg(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Ten
     ``[seg_end[s-1], seg_end[s])`` (``seg_end[-1] = 0``; ends ascending, multiples of 8 but the last, which is ``numel``) and runs at
     ``seg_lr[s]`` / ``seg_weight_decay[s]``, or is left alone — neither read nor written — where ``seg_frozen[s]``.  The four sequences are
     host values.  More than ``_lib.ADAMW_MAX_SEGS`` segments become several launches, split at segment ends; the result is the same."""
-    assert param.is_contiguous() and grad.is_contiguous() and exp_avg.is_contiguous() and exp_avg_sq.is_contiguous()
-    assert param.numel() == grad.numel() == exp_avg.numel() == exp_avg_sq.numel()
-    assert param.dtype == grad.dtype == exp_avg.dtype == exp_avg_sq.dtype
+    flags = _adamw_flags(param, grad, exp_avg, exp_avg_sq, zero_grad, skip_nonfinite_scale)
     n_segs = len(seg_end)
     assert n_segs >= 1 and len(seg_lr) == len(seg_weight_decay) == len(seg_frozen) == n_segs
-    flags = int(zero_grad) | (2 if skip_nonfinite_scale else 0)
     lib, cap = _lib.load(), _lib.ADAMW_MAX_SEGS
     param, grad, exp_avg, exp_avg_sq = param.view(-1), grad.view(-1), exp_avg.view(-1), exp_avg_sq.view(-1)
     if param.numel() == 0 and n_segs == 1 and int(seg_end[0]) == 0:

@@ -105,17 +105,16 @@ class HipAdamW(torch.optim.Optimizer):
             ops.adamw_step(*bufs, lr=float(g["lr"]), beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"],
                            step=step, grad_scale_dev=scale, zero_grad=False, skip_nonfinite_scale=skip_nonfinite_scale,
                            sr_seed=self._sr_seed, elem_offset=lo)
-            self._update_ema(lo, hi, step, scale, skip_nonfinite_scale)
-            return
-        segs = clip_segments(self._segments, lo, hi)
-        if all(s.frozen for s in segs):
-            return
-        lr, wd = float(g["lr"]), float(g["weight_decay"])
-        ops.adamw_step_seg(*bufs, seg_end=[s.end - lo for s in segs], seg_lr=[lr * s.lr_scale for s in segs],
-                           seg_weight_decay=[wd if s.weight_decay is None else s.weight_decay for s in segs],
-                           seg_frozen=[s.frozen for s in segs], beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], step=step,
-                           grad_scale_dev=scale, zero_grad=False, skip_nonfinite_scale=skip_nonfinite_scale, sr_seed=self._sr_seed,
-                           elem_offset=lo)
+        else:
+            segs = clip_segments(self._segments, lo, hi)
+            if all(s.frozen for s in segs):
+                return   # nothing launched, the average untouched
+            lr, wd = float(g["lr"]), float(g["weight_decay"])
+            ops.adamw_step_seg(*bufs, seg_end=[s.end - lo for s in segs], seg_lr=[lr * s.lr_scale for s in segs],
+                               seg_weight_decay=[wd if s.weight_decay is None else s.weight_decay for s in segs],
+                               seg_frozen=[s.frozen for s in segs], beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], step=step,
+                               grad_scale_dev=scale, zero_grad=False, skip_nonfinite_scale=skip_nonfinite_scale, sr_seed=self._sr_seed,
+                               elem_offset=lo)
         self._update_ema(lo, hi, step, scale, skip_nonfinite_scale)
 
     def _update_ema(self, lo: int, hi: int, step: int, scale: Tensor | None, skip_nonfinite_scale: bool) -> None:
