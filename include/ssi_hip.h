@@ -259,7 +259,9 @@ int ssi_ce_fwd(void* logits, int64_t ld, const int64_t* labels, int64_t rows, in
                float* row_loss, float* row_lse, int write_grad, int dtype, void* stream);
 /* bf16 rows of up to 196 608 columns are held in registers by one workgroup per CU: the log-sum-exp and the gradient come from ONE
  * read of the row (2 passes over the logits, not 3).  A label that is neither `ignore_index` nor inside [0, vocab) gives a zero
- * loss and a zero gradient row here and is COUNTED by ssi_ce_reduce (out[3]): the caller raises when it next reads back. */
+ * loss and a zero gradient row here and is COUNTED by ssi_ce_reduce (out[3]): the caller raises when it next reads back.
+ * All five ssi_ce_fwd* entries move the rows 16 bytes at a time in either form: `logits` (and the `teacher` of ssi_ce_fwd_kl) must be
+ * 16-byte aligned, SSI_ERR_ARG otherwise and nothing is launched (ld % 8 == 0 then aligns every row). */
 /* out[0] = sum(row_loss) / n_valid (NaN if n_valid == 0, as the reference), out[1] = sum(row_loss), out[2] = n_valid (labels that
  * are not ignored and lie in [0, vocab) — the predicate ssi_ce_fwd uses), out[3] = number of out-of-range labels.  out: 4 floats. */
 int ssi_ce_reduce(const float* row_loss, const int64_t* labels, int64_t rows, int64_t vocab, int64_t ignore_index, float* out,

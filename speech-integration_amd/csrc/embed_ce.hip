@@ -873,6 +873,10 @@ template <CeMode MODE, typename T> static void ce_launch_generic(const CeArgs& a
 // what the five entries share: the common argument check, the form the input takes, the launch
 template <CeMode MODE> static int ce_fwd_launch(const CeArgs& a) {
     SSI_CHECK_ARG(a.logits && a.labels && a.row_loss && a.rows >= 0 && a.vocab > 0 && a.ld >= a.vocab && a.ld % 8 == 0);
+    // both forms read and write the rows 16 bytes at a time (the generic form too: load16 / store16): a base that is not 16-byte aligned is
+    // refused here, before anything is launched.  With ld % 8 == 0 every row of an aligned base is aligned.
+    SSI_CHECK_ARG(((uintptr_t)a.logits & 15) == 0);
+    if constexpr (MODE == CE_KL) SSI_CHECK_ARG(((uintptr_t)a.kl.teacher & 15) == 0);
     if (a.rows == 0) return SSI_OK;
     bool row_form = ce_row_form(a.dtype, a.logits, a.ld, a.vocab);
     // CE_KL: the row form reads the teacher with the student's addressing; any other pair of buffers takes the generic form
