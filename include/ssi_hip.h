@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 17 /* 17: + ssi_ema_update (fp32 exponential moving average of the flat parameter buffer, one pass chained to AdamW; opt-in)
+#define SSI_ABI_VERSION 18 /* 18: + ssi_kv_store, ssi_attn_decode (greedy generation: a K/V cache and single-query attention over it; nothing else calls them)
+                           * 17: + ssi_ema_update (fp32 exponential moving average of the flat parameter buffer, one pass chained to AdamW; opt-in)
                            * 16: + ssi_adamw_step_seg (AdamW over segments of the flat buffers with their own lr, weight decay and frozen flag; opt-in)
                            * 15: + ssi_ce_fwd_kl (KL against a frozen teacher's logits inside the cross-entropy kernels; opt-in)
                            * 14: + ssi_ce_fwd_smooth (label smoothing inside the cross-entropy kernels, beside the z-loss; opt-in)
@@ -203,6 +204,36 @@ int ssi_attn_varlen_bwd_plan(const void* qkv, int64_t ld, const void* out, const
                              int64_t table_len, const int32_t* positions, int64_t batch, int64_t seq, int n_heads, int n_kv,
                              int head_dim, int dtype, void* workspace, int64_t workspace_bytes, const int32_t* plan,
                              const int32_t* host_plan_header, void* stream);
+
+/* ---- Generation (ABI v18; the reference generates with vLLM, scripts/generate.py): K/V cache and one decode step's attention -------------
+ * The cache of one layer is two buffers of the model's dtype, k_cache and v_cache, each [n_slots, cap, n_kv * head_dim] row-major; K is
+ * stored AFTER RoPE, as it sits in qkv.  Both entries: head_dim a multiple of 8 up to 128 and 1 to 8 query heads per kv head, anything
+ * else SSI_ERR_UNSUPPORTED; qkv and the caches 16-byte aligned with ld * sizeof(element) a multiple of 16 (SSI_ERR_ARG otherwise). */
+/* cache[dest[r]] = the k / v columns of qkv row r; dest[r] = slot * cap + position, -1 = skip the row.
+ * A dest outside [0, n_dest) other than -1 is skipped and COUNTED into *n_bad (may be NULL), like n_clamped of ssi_doc_ranges.
+ * Distinct rows must have distinct dest (caller's contract).  Bit-exact copy, 16 bytes per lane. */
+int ssi_kv_store(const void* qkv, int64_t ld, const int64_t* dest, int64_t rows, int64_t n_dest, void* k_cache, void* v_cache,
+                 int n_heads, int n_kv, int head_dim, int32_t* n_bad, int dtype, void* stream);
+
+/* out[r, h, :] = softmax_j(q[r,h]·K[slot[r], j, h / g] / sqrt(head_dim)) · V[slot[r], j, h / g],  j < kv_len[r],  g = n_heads / n_kv.
+ * q = columns [0, n_heads*head_dim) of qkv row r.  slot[r] < 0 or kv_len[r] <= 0: the out row is zeros, lse -inf.
+ * kv_len is clamped to cap; slot >= n_slots is SSI_ERR-free on the device: the row is zeros and *n_bad (may be NULL) counts it once.
+ * out: [rows, n_heads * head_dim].  lse (NULL ok): fp32 [rows, n_heads], natural log.
+ * Arithmetic: the header's rule — scores, max, exp-sum and the P·V accumulation in fp32, ONE rounding on the store.  Unlike the training
+ * kernels (ssi_attn_*), which feed P to the matrix cores in the storage type, P is NOT rounded to bf16 on the way.  The scores are taken in
+ * base 2: q is multiplied by (float)(log2(e) / sqrt(head_dim)) once, exp is v_exp_f32.
+ * One workgroup of 4 waves per (row, kv head); the g query heads of a group share every K / V line; no split over workgroups, no
+ * workspace, no second pass.  A key's head_dim elements lie on LPK lanes of 16 bytes (LPK = head_dim * sizeof(element) / 16 rounded up to
+ * a power of two), a wave holds 64 / LPK keys per load and takes chunks of 2 loads = 128 / LPK keys, chunk c going to wave c % 4
+ * (bf16, head_dim 64: chunks of 16 keys, 64 keys per round of the workgroup; fp32, head_dim 64: 8 and 32).  Each lane keeps the running
+ * (max, sum, acc) of its key slot; the key slots of a wave are merged by an xor tree with the lower slot first, the waves through LDS in
+ * the order 0..3: the result for a row depends on that row's inputs only — not on rows, not on the row's place, not on other slots.
+ * Dispatch: ONE kernel form, instantiated per dtype and for G = 1, 2, 4, 8 query-head registers (g = 3 runs G = 4, g = 5..7 run G = 8; the
+ * surplus heads repeat the last one and are not stored).  There is no specialised head_dim form, so ssi_set_impl has nothing to choose here.
+ * Traffic per row: kv_len * 2 * n_kv * head_dim elements, read once. */
+int ssi_attn_decode(const void* qkv, int64_t ld, const void* k_cache, const void* v_cache, int64_t n_slots, int64_t cap,
+                    const int32_t* slot, const int32_t* kv_len, void* out, float* lse, int64_t rows, int n_heads, int n_kv,
+                    int head_dim, int32_t* n_bad, int dtype, void* stream);
 
 /* ---- K7  SwiGLU elementwise (torchtune FeedForward: w2(silu(w1 x) * w3 x)) ------------------------------------------ */
 /* gu: [rows, 2*inter] = [gate | up]; act[rows, inter] = silu(gate) * up */

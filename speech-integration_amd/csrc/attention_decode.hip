@@ -1,0 +1,256 @@
+// Generation (ABI v18): the K/V cache of a decode step.  ssi_kv_store scatters the k / v columns of qkv rows into the cache,
+// ssi_attn_decode is single-query attention of one new token per sequence over that sequence's cached keys.
+//
+// The cache of one layer: k_cache and v_cache, each [n_slots, cap, n_kv * head_dim] in the model's dtype, K after RoPE (as it sits in qkv).
+#include "common_hip.h"
+#include <math.h>
+
+namespace {
+
+// =====================================================================================================================
+// ssi_kv_store: one 16-byte vector per lane.  A row of qkv holds its k heads and, right behind them, its v heads: vector c of the
+// row's 2 * n_kv * head_dim cache elements goes to k_cache for c < half and to v_cache otherwise.
+// =====================================================================================================================
+template <typename T>
+__global__ __launch_bounds__(256) void kv_store_kernel(const T* __restrict__ qkv, int64_t ld, const int64_t* __restrict__ dest, int64_t rows,
+                                                       int64_t n_dest, T* __restrict__ kc, T* __restrict__ vc, int q_cols, int kv_cols,
+                                                       int32_t* __restrict__ n_bad) {
+    constexpr int VEC = Vec16<T>::N;
+    const int half = kv_cols / VEC;                       // vectors of one row of one cache
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t r = i / (2 * half);
+    if (r >= rows) return;
+    const int c = (int)(i - r * (2 * half));
+    const int64_t d = dest[r];
+    if (d == -1) return;
+    if (d < 0 || d >= n_dest) {
+        if (c == 0 && n_bad) atomicAdd(n_bad, 1);         // integer: exact whatever the order
+        return;
+    }
+    const Vec16<T> x = load16<T>(qkv + r * ld + q_cols + (int64_t)c * VEC);
+    T* dst = (c < half ? kc : vc) + d * kv_cols + (int64_t)(c < half ? c : c - half) * VEC;
+    store16<T>(dst, x);
+}
+
+// =====================================================================================================================
+// ssi_attn_decode: one workgroup per (row, kv head), 4 waves.  The G query heads of the group share every K / V line.
+//
+// Lanes: a key's head_dim elements are spread over LPK = 2^lpk_log2 lanes, 16 bytes each (lanes whose columns lie past head_dim idle:
+// head_dim / VEC need not be a power of two), so a wave holds KPW = 64 / LPK keys per load.  A wave takes key CHUNKS of U * KPW keys,
+// chunk c going to wave c % 4; inside a chunk key slot s of load u holds key  base + u * KPW + s.  Every lane keeps the running
+// (max, exp-sum, P.V) of its key slot in fp32 — scores in base 2: q is scaled by log2(e) / sqrt(head_dim) once —
+// and the states are merged in a FIXED order: the key slots of a wave by an xor tree (the lower slot's state first), the four waves
+// through LDS in the order 0, 1, 2, 3.  P is never rounded to the storage type.  A row's result depends on that row's inputs only.
+// =====================================================================================================================
+constexpr int DEC_WAVES = 4, DEC_U = 2, DEC_MAX_HD = 128;
+
+__device__ __forceinline__ float dec_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+// weight of a partial state with maximum m in a merged state with maximum mn >= m (an empty state has m = -inf, also when mn is -inf)
+__device__ __forceinline__ float dec_weight(float m, float mn) { return m == -INFINITY ? 0.f : dec_exp2(m - mn); }
+
+template <typename T, int G>
+__global__ __launch_bounds__(256) void kv_decode_kernel(const T* __restrict__ qkv, int64_t ld, const T* __restrict__ kc, const T* __restrict__ vc,
+                                                        int64_t n_slots, int cap, const int32_t* __restrict__ slot,
+                                                        const int32_t* __restrict__ kv_len, T* __restrict__ out, float* __restrict__ lse,
+                                                        int n_heads, int n_kv, int hd, int g, int lpk_log2, float qscale,
+                                                        int32_t* __restrict__ n_bad) {
+    constexpr int VEC = Vec16<T>::N;
+    __shared__ float s_m[DEC_WAVES][G], s_l[DEC_WAVES][G];
+    __shared__ float s_acc[DEC_WAVES][G][DEC_MAX_HD];
+    const int64_t r = blockIdx.x;
+    const int kvh = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int h0 = kvh * g;
+    const int sl = slot[r];
+    int n = kv_len[r];
+    n = n < cap ? n : cap;
+    T* orow = out + (r * n_heads + h0) * hd;
+    if (sl < 0 || sl >= n_slots || n <= 0) {              // (uniform over the workgroup)
+        for (int i = tid; i < g * hd; i += 256) orow[i] = from_f32<T>(0.f);
+        if (lse && tid < g) lse[r * n_heads + h0 + tid] = -INFINITY;
+        if (sl >= n_slots && kvh == 0 && tid == 0 && n_bad) atomicAdd(n_bad, 1);
+        return;
+    }
+    const int lpk = 1 << lpk_log2, kpw = 64 >> lpk_log2;
+    const int sub = lane & (lpk - 1), kslot = lane >> lpk_log2, col = sub * VEC;
+    const bool active = col < hd;
+
+    float q[G][VEC], acc[G][VEC], m[G], l[G];
+#pragma unroll
+    for (int h = 0; h < G; ++h) {
+        const int hh = h < g ? h : g - 1;                 // heads past g repeat the last one and are not stored
+        Vec16<T> x = {};
+        if (active) x = load16<T>(qkv + r * ld + (int64_t)(h0 + hh) * hd + col);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            q[h][v] = active ? x.get(v) * qscale : 0.f;
+            acc[h][v] = 0.f;
+        }
+        m[h] = -INFINITY;
+        l[h] = 0.f;
+    }
+
+    const int64_t kv_cols = (int64_t)n_kv * hd;
+    const T* kbase = kc + ((int64_t)sl * cap * n_kv + kvh) * hd + col;
+    const T* vbase = vc + ((int64_t)sl * cap * n_kv + kvh) * hd + col;
+    const int chunk = kpw * DEC_U;
+    for (int base = wave * chunk; base < n; base += DEC_WAVES * chunk) {
+        Vec16<T> kx[DEC_U] = {}, vx[DEC_U] = {};
+        bool have[DEC_U];
+#pragma unroll
+        for (int u = 0; u < DEC_U; ++u) {                 // every load of the chunk is issued before the first use
+            const int j = base + u * kpw + kslot;
+            have[u] = j < n;
+            if (have[u] && active) {
+                kx[u] = load16_nt<T>(kbase + (int64_t)j * kv_cols);
+                vx[u] = load16_nt<T>(vbase + (int64_t)j * kv_cols);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < DEC_U; ++u) {
+            const bool ld_ok = have[u] && active;
+            float kf[VEC], vf[VEC];
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                kf[v] = ld_ok ? kx[u].get(v) : 0.f;
+                vf[v] = ld_ok ? vx[u].get(v) : 0.f;
+            }
+            float s[G];
+#pragma unroll
+            for (int h = 0; h < G; ++h) {
+                float d = 0.f;
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) d = __builtin_fmaf(q[h][v], kf[v], d);
+                s[h] = d;
+            }
+            for (int o = lpk >> 1; o > 0; o >>= 1) {      // (every lane of the wave takes part: the trip count is uniform)
+#pragma unroll
+                for (int h = 0; h < G; ++h) s[h] += __shfl_xor(s[h], o, 64);
+            }
+            if (have[u]) {
+#pragma unroll
+                for (int h = 0; h < G; ++h) {
+                    const float mn = fmaxf(m[h], s[h]);
+                    const float a = dec_exp2(m[h] - mn);  // (-inf - finite = -inf: 0)
+                    const float p = dec_exp2(s[h] - mn);
+                    l[h] = __builtin_fmaf(l[h], a, p);
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) acc[h][v] = __builtin_fmaf(p, vf[v], acc[h][v] * a);
+                    m[h] = mn;
+                }
+            }
+        }
+    }
+
+    // the key slots of the wave: xor tree, the state of the lower slot first in every sum (all lanes then hold the same bits)
+    for (int o = lpk; o < 64; o <<= 1) {
+        const bool low = (lane & o) == 0;
+#pragma unroll
+        for (int h = 0; h < G; ++h) {
+            const float mo = __shfl_xor(m[h], o, 64), lo = __shfl_xor(l[h], o, 64);
+            const float m0 = low ? m[h] : mo, m1 = low ? mo : m[h];
+            const float mn = fmaxf(m0, m1);
+            const float e0 = dec_weight(m0, mn), e1 = dec_weight(m1, mn);
+            l[h] = __builtin_fmaf(low ? lo : l[h], e1, (low ? l[h] : lo) * e0);
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                const float ao = __shfl_xor(acc[h][v], o, 64);
+                acc[h][v] = __builtin_fmaf(low ? ao : acc[h][v], e1, (low ? acc[h][v] : ao) * e0);
+            }
+            m[h] = mn;
+        }
+    }
+    if (kslot == 0 && active) {
+#pragma unroll
+        for (int h = 0; h < G; ++h) {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) s_acc[wave][h][col + v] = acc[h][v];
+            if (sub == 0) {
+                s_m[wave][h] = m[h];
+                s_l[wave][h] = l[h];
+            }
+        }
+    }
+    __syncthreads();
+    // the four waves, in order
+    for (int i = tid; i < g * hd; i += 256) {
+        const int h = i / hd, d = i - h * hd;
+        float mn = s_m[0][h];
+#pragma unroll
+        for (int w = 1; w < DEC_WAVES; ++w) mn = fmaxf(mn, s_m[w][h]);
+        float L = 0.f, O = 0.f;
+#pragma unroll
+        for (int w = 0; w < DEC_WAVES; ++w) {
+            const float e = dec_weight(s_m[w][h], mn);
+            L = __builtin_fmaf(s_l[w][h], e, L);
+            O = __builtin_fmaf(s_acc[w][h][d], e, O);
+        }
+        orow[i] = from_f32<T>(O / L);
+        if (lse && d == 0) lse[r * n_heads + h0 + h] = (mn + log2f(L)) * 0.69314718055994531f;
+    }
+}
+
+template <typename T, int G>
+void launch_decode(const void* qkv, int64_t ld, const void* kc, const void* vc, int64_t n_slots, int64_t cap, const int32_t* slot,
+                   const int32_t* kv_len, void* out, float* lse, int64_t rows, int n_heads, int n_kv, int hd, int32_t* n_bad, void* stream) {
+    const int lanes = hd / Vec16<T>::N;
+    int lpk_log2 = 0;
+    while ((1 << lpk_log2) < lanes) ++lpk_log2;
+    const float qscale = (float)(1.4426950408889634 / sqrt((double)hd));
+    hipLaunchKernelGGL((kv_decode_kernel<T, G>), dim3((unsigned)rows, (unsigned)n_kv), dim3(256), 0, (hipStream_t)stream, (const T*)qkv, ld,
+                       (const T*)kc, (const T*)vc, n_slots, (int)cap, slot, kv_len, (T*)out, lse, n_heads, n_kv, hd, n_heads / n_kv, lpk_log2,
+                       qscale, n_bad);
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// head geometry both entries accept
+int check_geometry(const char* who, int n_heads, int n_kv, int head_dim) {
+    if (n_heads < 1 || n_kv < 1 || head_dim < 1) { ssi_set_error("%s: n_heads, n_kv and head_dim must be positive", who); return SSI_ERR_ARG; }
+    if (n_heads % n_kv || n_heads / n_kv > 8 || head_dim % 8 || head_dim > DEC_MAX_HD || n_kv > 65535) {
+        ssi_set_error("%s: unsupported head geometry (n_heads %d, n_kv %d, head_dim %d): head_dim a multiple of 8 up to %d, 1 to 8 query heads "
+                      "per kv head", who, n_heads, n_kv, head_dim, DEC_MAX_HD);
+        return SSI_ERR_UNSUPPORTED;
+    }
+    return SSI_OK;
+}
+
+}  // namespace
+
+extern "C" int ssi_kv_store(const void* qkv, int64_t ld, const int64_t* dest, int64_t rows, int64_t n_dest, void* k_cache, void* v_cache,
+                            int n_heads, int n_kv, int head_dim, int32_t* n_bad, int dtype, void* stream) {
+    SSI_CHECK_ARG(rows >= 0 && n_dest >= 0 && (dtype == SSI_F32 || dtype == SSI_BF16));
+    if (int rc = check_geometry("ssi_kv_store", n_heads, n_kv, head_dim)) return rc;
+    if (rows == 0) return SSI_OK;
+    const int64_t esize = dtype == SSI_BF16 ? 2 : 4, q_cols = (int64_t)n_heads * head_dim, kv_cols = (int64_t)n_kv * head_dim;
+    SSI_CHECK_ARG(qkv && dest && k_cache && v_cache && ld >= q_cols + 2 * kv_cols && rows < (1LL << 31));
+    SSI_CHECK_ARG(aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache) && (ld * esize) % 16 == 0);
+    const int64_t vecs = rows * (2 * kv_cols / (16 / esize));
+    SSI_CHECK_ARG(ssi_cdiv(vecs, 256) < (1LL << 31));
+    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(kv_store_kernel<T>, dim3((unsigned)ssi_cdiv(vecs, 256)), dim3(256), 0, (hipStream_t)stream,
+                                                 (const T*)qkv, ld, dest, rows, n_dest, (T*)k_cache, (T*)v_cache, (int)q_cols, (int)kv_cols, n_bad));
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+extern "C" int ssi_attn_decode(const void* qkv, int64_t ld, const void* k_cache, const void* v_cache, int64_t n_slots, int64_t cap,
+                               const int32_t* slot, const int32_t* kv_len, void* out, float* lse, int64_t rows, int n_heads, int n_kv,
+                               int head_dim, int32_t* n_bad, int dtype, void* stream) {
+    SSI_CHECK_ARG(rows >= 0 && n_slots >= 0 && cap >= 0 && cap < (1LL << 31) && (dtype == SSI_F32 || dtype == SSI_BF16));
+    if (int rc = check_geometry("ssi_attn_decode", n_heads, n_kv, head_dim)) return rc;
+    if (rows == 0) return SSI_OK;
+    const int64_t esize = dtype == SSI_BF16 ? 2 : 4;
+    SSI_CHECK_ARG(qkv && slot && kv_len && out && rows < (1LL << 31) && ld >= (int64_t)n_heads * head_dim);
+    SSI_CHECK_ARG((k_cache && v_cache) || n_slots * cap == 0);
+    SSI_CHECK_ARG(aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache) && (ld * esize) % 16 == 0);
+    const int g = n_heads / n_kv;
+#define SSI_DECODE_G(GG) launch_decode<T, GG>(qkv, ld, k_cache, v_cache, n_slots, cap, slot, kv_len, out, lse, rows, n_heads, n_kv, head_dim, n_bad, stream)
+    SSI_DISPATCH_DTYPE(dtype, {
+        if (g == 1) SSI_DECODE_G(1);
+        else if (g == 2) SSI_DECODE_G(2);
+        else if (g <= 4) SSI_DECODE_G(4);
+        else SSI_DECODE_G(8);
+    });
+#undef SSI_DECODE_G
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}

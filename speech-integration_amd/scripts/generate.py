@@ -1,0 +1,61 @@
+#!/usr/bin/env python
+"""Greedy generation entry point (the reference's scripts/generate.py runs vLLM): a generations JSONL the reference's scripts/wer.py reads.
+    python scripts/generate.py speech.n_dsus=5000 gen.input=prompts.jsonl gen.output_dir=out [key=value ...]
+    python scripts/generate.py speech.n_dsus=5000 data=sft/<dataset> gen.split=dev gen.output_dir=out
+"""
+import logging
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+try:  # real Hydra if the environment has it, else the built-in composer with the same decorator shape
+    import hydra
+    main_decorator = hydra.main
+except ImportError:
+    from ssi.config import main as main_decorator
+
+from ssi.generate import check_greedy, generate_file
+
+LOGGER = logging.getLogger(__name__)
+
+
+def split_prompts(cfg, tokenizer) -> tuple[list, list]:
+    """The prompts of ``cfg.data[cfg.gen.split]`` through ``SFTDataset(inference=True)``: an empty assistant message to be continued."""
+    from ssi.data.sft import SFTDataset
+    if cfg.get("data") is None:
+        raise ValueError("generate: gen.input or a data config (data=sft/...)")
+    node = cfg.data[cfg.gen.split].dataset
+    kw = {k: node[k] for k in node if k not in ("inference", "fixed_len")}
+    data = SFTDataset(model_tokenizer=tokenizer, inference=True, **kw)
+    prompts = [list(data[i]["tokens"]) for i in range(len(data))]
+    return list(range(len(prompts))), prompts
+
+
+@main_decorator(config_path="../conf", config_name="generate", version_base=None)
+def main(cfg):
+    check_greedy(cfg.sampling_params)          # before anything is loaded
+    from ssi.model import get_device, get_dtype
+    from ssi.train_utils import resolve_n_dsus
+    from ssi.trainer import Trainer
+    resolve_n_dsus(cfg)
+    t = Trainer(cfg)  # model, tokenizer and checkpointer as a training run sets them up; no optimizer, no data loaders
+    t.device, t.dtype = get_device(cfg.device), get_dtype(cfg.dtype)
+    t._setup_model()
+    t._setup_tokenizer()
+    os.makedirs(str(cfg.gen.output_dir), exist_ok=True)
+    out_path = os.path.join(str(cfg.gen.output_dir), str(cfg.gen.output_filename))
+    ids = prompts = None
+    if cfg.gen.get("input") is None:
+        ids, prompts = split_prompts(cfg, t.tokenizer)
+    stop = cfg.sampling_params.get("stop_token_ids")
+    summary = generate_file(t.model, t.tokenizer, None if prompts is not None else str(cfg.gen.input), out_path,
+                            max_new_tokens=int(cfg.sampling_params.max_tokens), stop_token_ids=None if stop is None else [int(s) for s in stop],
+                            tokenizer_decoding={k: cfg.tokenizer_decoding[k] for k in cfg.tokenizer_decoding}, prompts=prompts, ids=ids,
+                            batch_size=int(cfg.gen.batch_size), logprobs=bool(cfg.gen.logprobs), device=t.device)
+    LOGGER.info(" | ".join(f"{k}: {v}" for k, v in summary.items()) + f" | wrote {out_path}")
+    return summary
+
+
+if __name__ == "__main__":
+    main()

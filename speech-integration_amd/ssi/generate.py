@@ -1,0 +1,209 @@
+"""Greedy generation on the HIP decoder (the reference generates with vLLM, ``scripts/generate.py``: greedy, ``n = 1``): what turns a
+checkpoint into the transcripts the reference's ``scripts/wer.py`` scores.
+
+``generate`` sorts the prompts by length and runs them in static groups of ``batch_size``: one ``prefill`` per group (the packed forward
+of the dev loss and of ``ssi.score``, block-causal over the prompts, every layer's K / V scattered into a cache by ``ssi_kv_store``), then
+``decode_step`` per new token (one row per sequence on the training step's GEMMs, ``ssi_attn_decode`` over the cache).  A finished row
+goes inert — its slot is masked to -1, so it costs no attention and writes no cache — and the group ends when every row has finished or
+at ``max_new_tokens``; whether every row has finished is read back every ``READBACK_EVERY`` steps, not every step.
+
+Out of scope: sampling, beam search, continuous batching (refilling freed slots), generation under data parallelism, a skinny GEMM for
+small batches, and WER itself (its text normaliser is the reference's dependency; the JSONL written here is what its ``wer.py`` reads)."""
+
+from __future__ import annotations
+
+import json
+import logging
+from collections.abc import Sequence
+from dataclasses import dataclass
+from typing import Any
+
+import torch
+from torch import Tensor
+
+from . import ops
+from .constants import CROSS_ENTROPY_IGNORE_IDX
+
+LOGGER = logging.getLogger(__name__)
+
+__all__ = ["Generation", "READBACK_EVERY", "plan_groups", "generate", "generate_file", "output_record", "check_greedy"]
+
+READBACK_EVERY = 8    # decode steps between two read-backs of "has every row of the group finished?"
+
+
+@dataclass
+class Generation:
+    """``token_ids``: the generated tokens, INCLUDING the stop token that ended it; ``finish_reason``: ``"stop"`` or ``"length"``;
+    ``stop_reason``: the stop token's id, or None; ``cumulative_logprob``: the sum of the chosen tokens' log-probabilities (natural log;
+    None without ``logprobs=True``); ``prompt_len``: tokens in the prompt."""
+    token_ids: list[int]
+    finish_reason: str
+    stop_reason: int | None
+    cumulative_logprob: float | None
+    prompt_len: int
+
+
+def plan_groups(lengths: Sequence[int], batch_size: int) -> list[list[int]]:
+    """The static groups: prompt indices by rising length (ties by index), ``batch_size`` at a time.  Host only and deterministic."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
+    order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
+    return [order[a:a + batch_size] for a in range(0, len(order), batch_size)]
+
+
+def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_ids: Sequence[int], pad_id: int, batch_size: int = 256,
+             logprobs: bool = False, device: torch.device | str | None = None) -> list[Generation]:
+    """Greedy continuation of every prompt (1-D integer sequences), results in INPUT order.  The token of a step is ``argmax`` over the real
+    columns ``[:, :vocab_size]`` of the step's logits, with torch's first-occurrence rule.  ``pad_id`` fills the rows that have finished.
+    ``logprobs=True``: the forward-only ``ops.ce_fwd_metrics`` runs on the step's logits with the chosen token as label, which gives its
+    log-probability with no new kernel; the label's rank it also writes must be 0 on every live row (``RuntimeError`` otherwise).
+    Refused before any launch (``ValueError``): an empty prompt, a prompt that with ``max_new_tokens`` exceeds the model's RoPE table or
+    ``max_seq_len``."""
+    max_new_tokens, batch_size = int(max_new_tokens), int(batch_size)
+    if max_new_tokens < 1:
+        raise ValueError(f"max_new_tokens must be >= 1 (got {max_new_tokens})")
+    device = torch.device(device) if device is not None else model.device
+    if device != model.device:
+        raise ValueError(f"generate: device {device} is not the model's ({model.device})")
+    seqs = [torch.as_tensor(p, dtype=torch.int64).reshape(-1) for p in prompts]
+    lens = [int(s.numel()) for s in seqs]
+    if not seqs:
+        return []
+    groups = plan_groups(lens, batch_size)
+    n_slots, cap = min(batch_size, len(seqs)), max(lens) + max_new_tokens
+    model.check_generation_lengths(lens, max_new_tokens, len(seqs), cap)      # every prompt, before the first launch
+    stop = torch.tensor(sorted({int(t) for t in stop_token_ids}), dtype=torch.int64, device=device)
+    results: list[Generation | None] = [None] * len(seqs)
+    was_training = bool(model.training)
+    model.eval()
+    try:
+        with torch.inference_mode():
+            cache = model.new_kv_cache(n_slots, cap)
+            for group in groups:
+                for i, g in zip(group, _generate_group(model, cache, [seqs[i] for i in group], max_new_tokens, stop, int(pad_id), logprobs)):
+                    results[i] = g
+    finally:
+        if was_training:
+            model.train()
+    return results  # type: ignore[return-value]
+
+
+def _generate_group(model, cache, seqs: list[Tensor], max_new_tokens: int, stop: Tensor, pad_id: int, logprobs: bool) -> list[Generation]:
+    n, dev, V = len(seqs), model.device, model.vocab_size
+    logits = model.prefill(cache, seqs, max_new_tokens=max_new_tokens)
+    alive = torch.ones(n, dtype=torch.bool, device=dev)
+    own_slot = torch.arange(n, dtype=torch.int32, device=dev)
+    no_slot = torch.full_like(own_slot, -1)
+    out = torch.full((n, max_new_tokens), pad_id, dtype=torch.int64, device=dev)
+    n_gen = torch.zeros(n, dtype=torch.int64, device=dev)
+    stop_tok = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    cum = torch.zeros(n, dtype=torch.float64, device=dev)
+    not_top = torch.zeros(1, dtype=torch.int64, device=dev)
+    if logprobs:
+        row_loss, row_nll = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+        row_rank = torch.empty(n, dtype=torch.int32, device=dev)
+    for t in range(max_new_tokens):
+        tok = logits[:, :V].argmax(dim=-1)
+        if logprobs:
+            labels = torch.where(alive, tok, torch.full_like(tok, CROSS_ENTROPY_IGNORE_IDX))
+            ops.ce_fwd_metrics(logits, labels, V, CROSS_ENTROPY_IGNORE_IDX, row_loss, None, row_nll, row_rank)
+            cum -= torch.where(alive, row_nll, torch.zeros_like(row_nll)).double()
+            not_top += (alive & (row_rank != 0)).sum()      # the free self-check: the chosen token is the row's first
+        out[:, t] = torch.where(alive, tok, out[:, t])
+        n_gen += alive
+        stopped = alive & torch.isin(tok, stop)
+        stop_tok = torch.where(stopped, tok, stop_tok)
+        alive = alive & ~stopped
+        if t + 1 == max_new_tokens:
+            break
+        if (t + 1) % READBACK_EVERY == 0 and not bool(alive.any()):   # the read-back
+            break
+        logits = model.decode_step(cache, torch.where(alive, tok, torch.zeros_like(tok)), torch.where(alive, own_slot, no_slot))
+    host_out, host_n, host_stop, host_cum = out.cpu(), n_gen.cpu().tolist(), stop_tok.cpu().tolist(), cum.cpu().tolist()
+    if int(cache.errors) != 0:
+        raise RuntimeError(f"generate: the K/V cache kernels refused {int(cache.errors)} rows (a destination or a slot outside the cache)")
+    if int(not_top) != 0:
+        raise RuntimeError(f"generate: on {int(not_top)} rows the chosen token was not ranked first by ce_fwd_metrics")
+    return [Generation(token_ids=host_out[i, :host_n[i]].tolist(), finish_reason="stop" if host_stop[i] >= 0 else "length",
+                       stop_reason=host_stop[i] if host_stop[i] >= 0 else None, cumulative_logprob=host_cum[i] if logprobs else None,
+                       prompt_len=int(seqs[i].numel())) for i in range(n)]
+
+
+# ---- JSONL in, JSONL out ---------------------------------------------------------------------------------------------------------
+def output_record(item_id: Any, prompt_ids: Sequence[int], gen: Generation, tokenizer, decoding: dict | None = None) -> dict[str, Any]:
+    """One output line in the shape of the reference's generations file: ``outputs`` is a list with ONE entry (greedy, ``n = 1``) whose
+    ``text`` is what the reference's ``extract_texts_from_generations_jsonl`` reads."""
+    decoding = dict(decoding or {})
+    special = {v: k for k, v in getattr(tokenizer, "special_tokens", {}).items()}
+    return {"id": item_id, "prompt_token_ids": [int(t) for t in prompt_ids], "prompt": tokenizer.decode(list(prompt_ids), **decoding),
+            "outputs": [{"index": 0, "text": tokenizer.decode(gen.token_ids, **decoding), "token_ids": gen.token_ids,
+                         "cumulative_logprob": gen.cumulative_logprob, "finish_reason": gen.finish_reason, "stop_reason": gen.stop_reason,
+                         "stop_reason_text": special.get(gen.stop_reason) if gen.stop_reason is not None else None}]}
+
+
+def _read_prompts(tokenizer, in_path: str) -> tuple[list[Any], list[list[int]]]:
+    ids, prompts = [], []
+    with open(in_path, encoding="utf-8") as f:
+        for ln, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            item = json.loads(line)
+            if ("prompt_tokens" in item) == ("prompt" in item):
+                raise ValueError(f"{in_path}:{ln}: an item needs exactly one of 'prompt_tokens' and 'prompt'")
+            if "prompt_tokens" in item:
+                toks = [int(t) for t in item["prompt_tokens"]]
+            else:
+                toks = list(tokenizer.encode(item["prompt"], add_bos=True, add_eos=False))
+            ids.append(item.get("id", len(ids)))
+            prompts.append(toks)
+    return ids, prompts
+
+
+def default_stop_token_ids(tokenizer) -> list[int]:
+    """``[eom_id, eot_id, eos_id]``, as the reference sets them when the configuration names none."""
+    return [int(tokenizer.eom_id), int(tokenizer.eot_id), int(tokenizer.eos_id)]
+
+
+def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_new_tokens: int, stop_token_ids: Sequence[int] | None = None,
+                  tokenizer_decoding: dict | None = None, prompts: Sequence[Sequence[int]] | None = None, ids: Sequence[Any] | None = None,
+                  **kw) -> dict[str, Any]:
+    """JSONL in, JSONL out, in the style of ``score_file``.  Every input line: ``id`` and exactly one of ``prompt_tokens`` (ids, taken as they
+    are) and ``prompt`` (the tokenizer's ``encode`` with BOS and without EOS).  ``in_path=None``: the prompts (and ids) come as arguments —
+    how ``scripts/generate.py`` hands over a data split.  Every output line: ``id``, ``prompt_token_ids``, ``prompt`` and ``outputs``, a list
+    with one entry holding ``index, text, token_ids, cumulative_logprob, finish_reason, stop_reason, stop_reason_text``, in INPUT order.
+    ``stop_token_ids`` default to the tokenizer's ``[eom_id, eot_id, eos_id]``; ``pad_id`` to the tokenizer's; ``kw`` goes to ``generate``.
+    Returns ``{"items", "generated_tokens", "stopped"}``."""
+    if in_path is not None:
+        ids, prompts = _read_prompts(tokenizer, in_path)
+    elif prompts is None:
+        raise ValueError("generate_file: an input file or prompts")
+    else:
+        prompts = [[int(t) for t in p] for p in prompts]
+        ids = list(ids) if ids is not None else list(range(len(prompts)))
+    if stop_token_ids is None:
+        stop_token_ids = default_stop_token_ids(tokenizer)
+    kw.setdefault("pad_id", int(getattr(tokenizer, "pad_id", 0) or 0))
+    gens = generate(model, prompts, max_new_tokens=max_new_tokens, stop_token_ids=stop_token_ids, **kw)
+    with open(out_path, "w", encoding="utf-8") as f:
+        for item_id, p, g in zip(ids, prompts, gens):
+            f.write(json.dumps(output_record(item_id, p, g, tokenizer, tokenizer_decoding), ensure_ascii=False) + "\n")
+    return {"items": len(gens), "generated_tokens": sum(len(g.token_ids) for g in gens),
+            "stopped": sum(g.finish_reason == "stop" for g in gens)}
+
+
+# ---- what the script accepts of the reference's sampling_params ------------------------------------------------------------------
+GREEDY = {"n": 1, "temperature": 0.0, "top_p": 1.0, "top_k": -1, "presence_penalty": 0.0, "frequency_penalty": 0.0, "repetition_penalty": 1.0}
+
+
+def check_greedy(sampling_params) -> None:
+    """``NotImplementedError`` for anything but greedy decoding of one sequence: ``temperature != 0``, ``top_p != 1``, ``top_k != -1``, a
+    penalty off its default, ``n != 1`` (the reference pins its WER to greedy, too).  ``max_tokens`` and ``stop_token_ids`` are free; a key
+    this module does not know is refused as well."""
+    for key in sampling_params:
+        if key in ("max_tokens", "stop_token_ids"):
+            continue
+        if key not in GREEDY:
+            raise NotImplementedError(f"sampling_params.{key} is not supported: generation is greedy")
+        value = sampling_params[key]
+        if value is None or float(value) != float(GREEDY[key]):
+            raise NotImplementedError(f"sampling_params.{key} = {value!r}: only greedy decoding is built ({key} = {GREEDY[key]!r})")

@@ -98,6 +98,24 @@ class _Arena:
         return sum(t.numel() * t.element_size() for t in self.buf.values())
 
 
+class KVCache:
+    """What ``HipLlamaDecoder.new_kv_cache`` returns: ``k`` and ``v`` ``[layers, n_slots, cap, n_kv * head_dim]`` in the model's dtype (K
+    after RoPE), ``lengths`` (int32 ``[n_slots]`` on the device: tokens cached per slot) and ``errors`` (int32 ``[1]`` on the device: K / V
+    rows or slots the kernels refused — out-of-range destinations, a slot at its cap; 0 in a correct run, read it with whatever is read
+    back anyway)."""
+
+    def __init__(self, k: Tensor, v: Tensor, lengths: Tensor, errors: Tensor) -> None:
+        self.k, self.v, self.lengths, self.errors = k, v, lengths, errors
+
+    @property
+    def n_slots(self) -> int:
+        return self.k.shape[1]
+
+    @property
+    def cap(self) -> int:
+        return self.k.shape[2]
+
+
 class HipLlamaDecoder(nn.Module):
     def __init__(self, vocab_size: int, num_layers: int, num_heads: int, num_kv_heads: int, embed_dim: int,
                  max_seq_len: int, intermediate_dim: int, attn_dropout: float = 0.0, norm_eps: float = 1e-5,
@@ -465,7 +483,9 @@ class HipLlamaDecoder(nn.Module):
             return None
         return attn_plan.plan_from_input_pos(input_pos, self.num_heads, self.num_kv_heads, force=force)
 
-    def _forward_hidden(self, tokens: Tensor, save: bool, input_pos: Optional[Tensor] = None, attn_plan=None) -> Tensor:
+    def _forward_hidden(self, tokens: Tensor, save: bool, input_pos: Optional[Tensor] = None, attn_plan=None, kv_sink=None) -> Tensor:
+        """``kv_sink`` (``prefill``): ``(KVCache, dest)`` with ``dest`` int64 ``[B * S]`` on the device — after every layer's QKV projection
+        the k / v columns of row t are stored at ``dest[t]`` of that layer's cache (-1: not stored).  ``None``: not one launch more."""
         B, S = tokens.shape
         pos = ds = de = None
         self.position_errors = None
@@ -501,6 +521,8 @@ class HipLlamaDecoder(nn.Module):
             ops.rmsnorm_fwd(h, self._view(f"L{l}.sa_norm"), xn1, rstd1, self.norm_eps)
             qkv = A.get(f"qkv.{sfx}", (T, self.qkv_dim), dt)
             ops.gemm_rope(xn1, self._view(f"L{l}.wqkv"), qkv, S, H + KV, hd, self._rope, positions=pos)  # RoPE in the GEMM epilogue
+            if kv_sink is not None:
+                ops.kv_store(qkv, kv_sink[1], kv_sink[0].k[l], kv_sink[0].v[l], H, KV, hd, n_bad=kv_sink[0].errors)
             att = A.get("att.all", (L, T, H * hd), dt)[l] if save else A.get("att.x", (T, H * hd), dt)
             lse = A.get(f"lse.{sfx}", (B * H * S,), torch.float32)
             ops.attn_fwd(qkv, att, lse, B, S, H, KV, hd, ds, de)
@@ -646,6 +668,143 @@ class HipLlamaDecoder(nn.Module):
         announce("emb")
         self._saved = None
         self.attach_grads()
+
+    # ---- generation: K/V cache, prefill, decode step (ssi/generate.py drives them) --------------------------------------------
+    def new_kv_cache(self, n_slots: int, cap: int) -> "KVCache":
+        """A K/V cache for ``n_slots`` sequences of up to ``cap`` tokens: plain tensors owned by the caller (not arena buffers; the model
+        keeps no reference).  Nothing is allocated for generation before this is called."""
+        n_slots, cap = int(n_slots), int(cap)
+        if n_slots < 1 or cap < 1:
+            raise ValueError(f"new_kv_cache: n_slots and cap must be >= 1 (got {n_slots}, {cap})")
+        shape = (self.num_layers, n_slots, cap, self.num_kv_heads * self.head_dim)
+        return KVCache(torch.zeros(shape, dtype=self.dtype, device=self.device), torch.zeros(shape, dtype=self.dtype, device=self.device),
+                       torch.zeros(n_slots, dtype=torch.int32, device=self.device), torch.zeros(1, dtype=torch.int32, device=self.device))
+
+    def check_generation_lengths(self, prompt_lens, max_new_tokens: int, n_slots: int, cap: int) -> None:
+        """The host refusals of generation, before any launch."""
+        if len(prompt_lens) > n_slots:
+            raise ValueError(f"{len(prompt_lens)} prompts for {n_slots} cache slots")
+        max_new_tokens = int(max_new_tokens)
+        if max_new_tokens < 0:
+            raise ValueError(f"max_new_tokens = {max_new_tokens}")
+        for i, n in enumerate(prompt_lens):
+            if n < 1:
+                raise ValueError(f"prompt {i} is empty")
+            for what, limit in (("the cache's cap", cap), ("the RoPE table", self._rope.shape[0]), ("max_seq_len", self.max_seq_len)):
+                if n + max_new_tokens > limit:
+                    raise ValueError(f"prompt {i}: {n} tokens + {max_new_tokens} new ones exceed {what} ({limit})")
+
+    PREFILL_ROW_LEN = 2048        # prompts are packed into rows of this many positions ...
+    PREFILL_ROWS_PER_BATCH = 8    # ... and run this many rows at a time
+
+    @torch.no_grad()
+    def prefill(self, cache: "KVCache", prompts, max_new_tokens: int = 0) -> Tensor:
+        """Prompt ``i`` (a 1-D integer sequence) fills slot ``i`` of ``cache``: the prompts are packed into rows on the host
+        (``ssi.score.pack_for_scoring``, ``input_pos`` restarting with every prompt as in ``scoring_batches``), the packed forward the dev
+        loss and ``ssi.score`` use runs block-causal over them with every layer's K / V scattered into the cache, and the final norm's
+        rows of the prompts' LAST tokens alone go through the tied head.  Returns ``[n_prompts, vocab_pad]`` logits (fresh tensor) and
+        sets the cache's lengths; slots beyond the prompts are emptied.  ``max_new_tokens``: what ``decode_step`` will add, checked here
+        against the cap, the RoPE table and ``max_seq_len`` (``ValueError`` before any launch)."""
+        from .score import pack_for_scoring
+        seqs = [torch.as_tensor(p, dtype=torch.int64).reshape(-1) for p in prompts]
+        lens = [int(s.numel()) for s in seqs]
+        n, cap = len(seqs), cache.cap
+        self._check_cache(cache)
+        self.check_generation_lengths(lens, max_new_tokens, cache.n_slots, cap)
+        if n == 0:
+            raise ValueError("prefill: no prompts")
+        # rows of PREFILL_ROW_LEN positions; one shorter row where all the prompts together need less, a longer one for a longer prompt
+        row_len = min(max(min(self.PREFILL_ROW_LEN, sum(lens)), max(lens)), self._rope.shape[0])
+        rows = pack_for_scoring(lens, row_len)
+        mfma = self._mfma_shapes()
+        n_pad = _align(n, VOCAB_ALIGN) if mfma else n
+        dev = self.device
+        hlast = torch.zeros((n_pad, self.embed_dim), dtype=self.dtype, device=dev)   # (pad rows: zeros)
+        for b0 in range(0, len(rows), self.PREFILL_ROWS_PER_BATCH):
+            chunk = rows[b0:b0 + self.PREFILL_ROWS_PER_BATCH]
+            tokens = torch.zeros(len(chunk), row_len, dtype=torch.int64)
+            input_pos = torch.empty(len(chunk), row_len, dtype=torch.int64)
+            dest = torch.full((len(chunk), row_len), -1, dtype=torch.int64)
+            last_at, last_of = [], []
+            for r, members in enumerate(chunk):
+                at = 0
+                for i in members:
+                    k = lens[i]
+                    tokens[r, at:at + k] = seqs[i]
+                    input_pos[r, at:at + k] = torch.arange(k)
+                    dest[r, at:at + k] = i * cap + torch.arange(k)
+                    last_at.append((r, at + k - 1))
+                    last_of.append(i)
+                    at += k
+                input_pos[r, at:] = torch.arange(row_len - at)      # the tail: a document of its own, stored nowhere
+            tokens, input_pos, dest = tokens.to(dev), input_pos.to(dev), dest.to(dev)
+            tokens, input_pos, _, _ = self._right_pad(tokens, input_pos)
+            S = tokens.shape[1]
+            if S > row_len:
+                dest = torch.cat([dest, torch.full((len(chunk), S - row_len), -1, dtype=torch.int64, device=dev)], dim=1)
+            hn = self._forward_hidden(tokens, save=False, input_pos=input_pos, kv_sink=(cache, dest.reshape(-1).contiguous()))
+            src = torch.tensor([r * S + c for r, c in last_at], dtype=torch.int64).to(dev)
+            hlast.index_copy_(0, torch.tensor(last_of, dtype=torch.int64).to(dev), hn.index_select(0, src))
+        cache.lengths.zero_()
+        cache.lengths[:n] = torch.tensor(lens, dtype=torch.int32).to(dev)
+        return self._head_logits(hlast)[:n]
+
+    def _check_cache(self, cache: "KVCache") -> None:
+        want = (self.num_layers, cache.n_slots, cache.cap, self.num_kv_heads * self.head_dim)
+        for t in (cache.k, cache.v):
+            if tuple(t.shape) != want or t.dtype != self.dtype or t.device != self.device:
+                raise ValueError(f"the K/V cache is not this model's: {tuple(t.shape)} {t.dtype} on {t.device}, expected {want} {self.dtype} on {self.device}")
+
+    @torch.no_grad()
+    def decode_step(self, cache: "KVCache", tokens: Tensor, slots: Tensor) -> Tensor:
+        """One new token per live sequence: ``tokens`` (int64 ``[rows]``) and ``slots`` (int32 ``[rows]``; -1 = an inert row: no attention,
+        no cache write, a zero attention row) on the device.  Row r runs at position ``cache.lengths[slots[r]]``: its K / V go there, it
+        attends over the ``length + 1`` keys of its slot, and the length advances — all on the device, nothing is read back.  Returns the
+        ``[rows, vocab_pad]`` logits (fresh tensor).  On the MFMA shapes the rows are padded to a multiple of 256 with inert rows, which
+        makes every GEMM of the step one of the training step's tiles; all activations live in arena buffers of their own (``*.g``), so a
+        step may run between a training forward and its backward.  A slot whose length has reached the cap is not written (its K / V
+        would land in the next slot) and is counted in ``cache.errors``; ``prefill`` refuses what would get there."""
+        self._check_cache(cache)
+        if tokens.dim() != 1 or tokens.dtype != torch.int64 or slots.shape != tokens.shape or slots.dtype != torch.int32:
+            raise ValueError("decode_step: tokens is int64 [rows], slots int32 [rows]")
+        if not tokens.is_cuda or not slots.is_cuda:
+            raise _lib.HipLibraryError("decode_step: tokens and slots must live on the GPU (no CPU fallback)")
+        n = tokens.numel()
+        R = _align(max(n, 1), VOCAB_ALIGN) if self._mfma_shapes() else n
+        D, I, L = self.embed_dim, self.intermediate_dim, self.num_layers
+        H, KV, hd, dt, A, dev = self.num_heads, self.num_kv_heads, self.head_dim, self.dtype, self._arena, self.device
+        tok = torch.zeros(R, dtype=torch.int64, device=dev)          # pad rows: token 0, slot -1, position 0
+        slot = torch.full((R,), -1, dtype=torch.int32, device=dev)
+        tok[:n] = tokens
+        slot[:n] = slots
+        live = slot >= 0
+        length = torch.where(live, cache.lengths[slot.clamp(min=0).long()], torch.zeros_like(slot))
+        full = live & (length >= cache.cap)
+        cache.errors += full.sum().to(torch.int32)
+        write = live & ~full
+        dest = torch.where(write, slot.long() * cache.cap + length.long(), torch.full_like(slot, -1, dtype=torch.int64))
+        pos = length.clamp(max=self._rope.shape[0] - 1).contiguous()
+        kv_len = torch.where(live, length + 1, torch.zeros_like(length)).contiguous()
+        h = A.get("h0.g", (R, D), dt)
+        ops.embed_fwd(tok, self._view("emb"), h, self.vocab_size)
+        xn, rstd = A.get("xn.g", (R, D), dt), A.get("rstd.g", (R,), torch.float32)
+        qkv, att = A.get("qkv.g", (R, self.qkv_dim), dt), A.get("att.g", (R, H * hd), dt)
+        hmid, gu, act = A.get("hmid.g", (R, D), dt), A.get("gu.g", (R, 2 * I), dt), A.get("act.g", (R, I), dt)
+        for l in range(L):
+            ops.rmsnorm_fwd(h, self._view(f"L{l}.sa_norm"), xn, rstd, self.norm_eps)
+            ops.gemm_rope(xn, self._view(f"L{l}.wqkv"), qkv, R, H + KV, hd, self._rope, positions=pos)
+            ops.kv_store(qkv, dest, cache.k[l], cache.v[l], H, KV, hd, n_bad=cache.errors)
+            ops.attn_decode(qkv, cache.k[l], cache.v[l], slot, kv_len, att, None, H, KV, hd, n_bad=cache.errors)
+            self._gemm(GEMM_NT, att, self._view(f"L{l}.wo"), hmid, residual=h)
+            ops.rmsnorm_fwd(hmid, self._view(f"L{l}.mlp_norm"), xn, rstd, self.norm_eps)
+            ops.gemm_swiglu_fwd(xn, self._view(f"L{l}.w13"), gu, act)
+            hnext = A.get(f"h{1 + (l & 1)}.g", (R, D), dt)
+            self._gemm(GEMM_NT, act, self._view(f"L{l}.w2"), hnext, residual=hmid)
+            h = hnext
+        ops.rmsnorm_fwd(h, self.norm.scale, xn, rstd, self.norm_eps)
+        logits = self._head_logits(xn)
+        cache.lengths.index_add_(0, slot.clamp(min=0).long(), write.to(torch.int32))
+        return logits[:n]
 
     # ---- tied LM head ------------------------------------------------------------------------------------------------
     def _head_logits(self, hn: Tensor, arena_name: Optional[str] = None) -> Tensor:

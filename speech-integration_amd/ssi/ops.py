@@ -10,7 +10,7 @@ from torch import Tensor
 from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
-__all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "swiglu_fwd",
+__all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "swiglu_fwd",
            "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "ema_update", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
@@ -174,6 +174,56 @@ def attn_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, dqkv: Tensor, 
                                                ptr(rope_table), table_len, ptr(positions), batch, seq, n_heads, n_kv, head_dim,
                                                dtype_code(qkv.dtype), ptr(workspace), ws_bytes, plan_dev, plan_header, stream_ptr()),
           "ssi_attn_varlen_bwd_plan")
+
+
+def _kv_cache_ok(k_cache: Tensor, v_cache: Tensor, like: Tensor, n_kv: int, head_dim: int) -> None:
+    for c in (k_cache, v_cache):
+        if c.dim() != 3 or c.shape[2] != n_kv * head_dim or not c.is_contiguous() or c.dtype != like.dtype or c.device != like.device:
+            raise _lib.HipLibraryError(f"a K/V cache is a contiguous [n_slots, cap, {n_kv * head_dim}] tensor of the dtype and device of qkv "
+                                       f"(got {tuple(c.shape)}, {c.dtype}, {c.device})")
+    if k_cache.shape != v_cache.shape:
+        raise _lib.HipLibraryError(f"k_cache {tuple(k_cache.shape)} and v_cache {tuple(v_cache.shape)} differ")
+
+
+def kv_store(qkv: Tensor, dest: Tensor, k_cache: Tensor, v_cache: Tensor, n_heads: int, n_kv: int, head_dim: int,
+             n_bad: Tensor | None = None) -> None:
+    """``cache[dest[r]]`` = the k / v columns of row ``r`` of ``qkv`` ([rows, ld], q | k | v heads); the caches are
+    ``[n_slots, cap, n_kv * head_dim]`` and ``dest[r] = slot * cap + position`` (int64; -1 skips the row).  A ``dest`` outside the cache is
+    skipped and counted into ``n_bad`` (int32 [1], zeroed by the caller).  ``ssi_kv_store``: a bit-exact copy."""
+    ptr(qkv)
+    if qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] < (n_heads + 2 * n_kv) * head_dim:
+        raise _lib.HipLibraryError(f"kv_store: qkv must be [rows, >= {(n_heads + 2 * n_kv) * head_dim}] with unit inner stride (got {tuple(qkv.shape)})")
+    _kv_cache_ok(k_cache, v_cache, qkv, n_kv, head_dim)
+    if dest.dtype != torch.int64 or not dest.is_contiguous() or dest.numel() != qkv.shape[0] or dest.device != qkv.device:
+        raise _lib.HipLibraryError("kv_store: dest is one int64 per row of qkv, on its device")
+    if n_bad is not None and (n_bad.dtype != torch.int32 or n_bad.numel() != 1 or n_bad.device != qkv.device):
+        raise _lib.HipLibraryError("kv_store: n_bad is one int32 on the device of qkv")
+    check(_lib.load().ssi_kv_store(ptr(qkv), qkv.stride(0), ptr(dest), qkv.shape[0], k_cache.shape[0] * k_cache.shape[1], ptr(k_cache), ptr(v_cache),
+                                   n_heads, n_kv, head_dim, ptr(n_bad), dtype_code(qkv.dtype), stream_ptr()), "ssi_kv_store")
+
+
+def attn_decode(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, slot: Tensor, kv_len: Tensor, out: Tensor, lse: Tensor | None, n_heads: int,
+                n_kv: int, head_dim: int, n_bad: Tensor | None = None) -> None:
+    """Single-query GQA attention of row ``r`` of ``qkv`` (its q heads) over the first ``kv_len[r]`` cached keys of slot ``slot[r]`` (int32
+    each): ``out`` [rows, n_heads * head_dim], ``lse`` (fp32 [rows, n_heads], optional).  ``slot < 0`` or ``kv_len <= 0``: a zero row;
+    ``slot >= n_slots``: a zero row, counted into ``n_bad`` (int32 [1]).  ``ssi_attn_decode``: fp32 throughout, one rounding on the store."""
+    ptr(qkv)
+    if qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] < n_heads * head_dim:
+        raise _lib.HipLibraryError(f"attn_decode: qkv must be [rows, >= {n_heads * head_dim}] with unit inner stride (got {tuple(qkv.shape)})")
+    rows = qkv.shape[0]
+    _kv_cache_ok(k_cache, v_cache, qkv, n_kv, head_dim)
+    for name, t in (("slot", slot), ("kv_len", kv_len)):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != rows or t.device != qkv.device:
+            raise _lib.HipLibraryError(f"attn_decode: {name} is one int32 per row of qkv, on its device")
+    if out.dtype != qkv.dtype or not out.is_contiguous() or out.numel() != rows * n_heads * head_dim or out.device != qkv.device:
+        raise _lib.HipLibraryError(f"attn_decode: out must be a contiguous [rows, {n_heads * head_dim}] tensor of the dtype and device of qkv")
+    if lse is not None and (lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() < rows * n_heads or lse.device != qkv.device):
+        raise _lib.HipLibraryError("attn_decode: lse is fp32 [rows, n_heads] on the device of qkv")
+    if n_bad is not None and (n_bad.dtype != torch.int32 or n_bad.numel() != 1 or n_bad.device != qkv.device):
+        raise _lib.HipLibraryError("attn_decode: n_bad is one int32 on the device of qkv")
+    check(_lib.load().ssi_attn_decode(ptr(qkv), qkv.stride(0), ptr(k_cache), ptr(v_cache), k_cache.shape[0], k_cache.shape[1], ptr(slot),
+                                      ptr(kv_len), ptr(out), ptr(lse), rows, n_heads, n_kv, head_dim, ptr(n_bad), dtype_code(qkv.dtype),
+                                      stream_ptr()), "ssi_attn_decode")
 
 
 def swiglu_fwd(gu: Tensor, act: Tensor) -> None:

@@ -1,0 +1,212 @@
+"""What greedy generation costs at the 1B shape (Llama-3.2-1B + 5000 DSUs, bf16, random weights): 256 prompts of about 1000 tokens, 256 new
+tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute] [--json profiles/generate.json]
+
+run        prefill time, milliseconds per decode step (event time over all steps, host gaps included), generated tokens per second, and a
+           self-check: the first generated token of every prompt against the argmax of a plain full forward of that prompt alone (with
+           random weights the logits are nearly flat, so a token that differs must at least be a near-tie within the two runs' own difference).
+steps      decode steps only, on a cache filled with random numbers at the same lengths: the part that runs under
+           ``rocprofv3 --kernel-trace --stats`` in a run of its own, so that a step's kernel time splits into attention (kv_decode_kernel),
+           the cache write (kv_store_kernel) and the rest.  Kernels launched fewer times than there are steps are set-up, not step.
+recompute  for context, the only thing the code could do before: re-running the full forward for every new token (8 prompts, 4 tokens).
+all        the three as child processes, each under its own ``timeout``, chained with ``&&``; then the results and the floor from traffic
+           alone (weights read once per step, the cache read once per step) are merged into --json."""
+import argparse, csv, glob, json, os, statistics, subprocess, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, 'speech-integration_amd')
+sys.path.insert(0, PKG)
+
+ap = argparse.ArgumentParser()
+ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute'])
+ap.add_argument('--prompts', type=int, default=256)
+ap.add_argument('--prompt-len', type=int, default=1000)
+ap.add_argument('--new', type=int, default=256)
+ap.add_argument('--trace-steps', type=int, default=32)
+ap.add_argument('--json', default=None)
+ap.add_argument('--workdir', default=os.path.join(ROOT, 'prof_out', 'generate_bench'))
+args = ap.parse_args()
+HBM_TB_S = (5.4, 6.4)   # what the README records for the AdamW and EMA passes
+
+
+def build_model():
+    import copy
+    import torch
+    from ssi.llama_configs import configllama3_2_1b
+    from ssi.model import HipLlamaDecoder
+    c = copy.deepcopy(configllama3_2_1b)
+    c.n_dsus = 5000
+    torch.manual_seed(0)
+    m = HipLlamaDecoder(**c.parameters, dtype=torch.bfloat16, device='cuda', rope_cache_len=4096)
+    with torch.no_grad():
+        flat = m._flat.float().normal_(0.0, 0.02).to(torch.bfloat16)
+        m._flat.copy_(flat)
+        del flat
+        m._view('emb')[m.vocab_size:].zero_()            # the pad rows of the table stay zero
+        for p, name, _ in m._param_src:
+            if name.endswith('norm'):
+                p.fill_(1.0)
+    m.eval()
+    return m
+
+
+def make_prompts(vocab):
+    import torch
+    g = torch.Generator().manual_seed(1)
+    lens = torch.randint(args.prompt_len - 100, args.prompt_len + 101, (args.prompts,), generator=g).tolist()
+    return [torch.randint(0, vocab, (n,), generator=g) for n in lens]
+
+
+def traffic(model, lengths, steps):
+    """Bytes a decode step has to read: every weight once, and the cached K and V of every live sequence (mean over the steps)."""
+    per_token = 2 * model.num_layers * model.num_kv_heads * model.head_dim * 2
+    cached = sum(lengths) + len(lengths) * (steps - 1) / 2
+    return {'weights_GB': round(model._flat_numel * 2 / 1e9, 3), 'cache_bytes_per_token': per_token, 'cache_GB_mean_step': round(per_token * cached / 1e9, 3)}
+
+
+def part_run():
+    import torch
+    from ssi.generate import generate
+    model = build_model()
+    prompts = make_prompts(model.vocab_size)
+    lens = [p.numel() for p in prompts]
+    V, n = model.vocab_size, len(prompts)
+    with torch.inference_mode():
+        generate(model, [p[:64] for p in prompts[:8]], max_new_tokens=4, stop_token_ids=[], pad_id=0)     # warm-up: library, arena
+        cache = model.new_kv_cache(n, max(lens) + args.new)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        own = torch.arange(n, dtype=torch.int32, device='cuda')
+        torch.cuda.synchronize()
+        ev[0].record()
+        logits = model.prefill(cache, prompts, max_new_tokens=args.new)
+        first = logits[:, :V].argmax(-1)
+        ev[1].record()
+        tok = first
+        for _ in range(args.new - 1):
+            tok = model.decode_step(cache, tok, own)[:, :V].argmax(-1)
+        ev[2].record()
+        torch.cuda.synchronize()
+        prefill_ms, decode_ms = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+        assert int(cache.errors) == 0
+        del cache
+        torch.cuda.empty_cache()
+        t0 = time.perf_counter()
+        gens = generate(model, prompts, max_new_tokens=args.new, stop_token_ids=[], pad_id=0)
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        assert [g.token_ids[0] for g in gens] == first.tolist()
+        # self-check against the plain full forward, one prompt at a time.  The two runs sum in another order (a prompt packed among others
+        # against a row of its own), so their bf16 logits differ a little everywhere: `noise` is the largest such difference, and a first
+        # token that differs is a near-tie if the full forward's lead of its own choice over the generated one is within twice that
+        same, gap, noise = 0, 0.0, 0.0
+        for i, p in enumerate(prompts):
+            row = model(tokens=p[None].cuda())[0, -1]
+            scale = float(row.abs().max())
+            noise = max(noise, float((logits[i, :V].float() - row).abs().max()) / scale)
+            best = int(row.argmax())
+            if best == int(first[i]):
+                same += 1
+            else:
+                gap = max(gap, float(row[best] - row[int(first[i])]) / scale)
+    steps = args.new - 1
+    tr = traffic(model, lens, steps)
+    step_ms = decode_ms / steps
+    floor = [(tr['weights_GB'] + tr['cache_GB_mean_step']) / bw for bw in HBM_TB_S]      # GB / (TB/s) = ms
+    out = {'geometry': f'Llama-3.2-1B + 5000 DSUs, bf16, random weights; {n} prompts of {min(lens)}..{max(lens)} tokens (mean {sum(lens) / n:.0f}), {args.new} new tokens each',
+           'prefill_ms': round(prefill_ms, 1), 'prefill_tokens_per_s': round(sum(lens) / prefill_ms * 1e3), 'decode_steps': steps,
+           'decode_ms_per_step_event': round(step_ms, 3), 'generated_tokens_per_s_decode_only': round(n * steps / decode_ms * 1e3),
+           'generated_tokens_per_s_with_prefill': round(n * args.new / (prefill_ms + decode_ms) * 1e3),
+           'generate_call_wall_s': round(wall, 2), 'generate_call_tokens_per_s': round(n * args.new / wall),
+           'sum_prompt_tokens': sum(lens), 'traffic_per_step': tr, 'floor_ms_per_step_at_5.4_and_6.4_TB_s': [round(f, 3) for f in floor],
+           'step_over_floor': [round(step_ms / f, 2) for f in floor],
+           'self_check': {'prompts': n, 'first_token_equals_full_forward_argmax': same, 'differs': n - same,
+                          'largest_lead_lost_over_absmax': round(gap, 5), 'largest_logit_difference_between_the_two_runs_over_absmax': round(noise, 5),
+                          'every_difference_is_a_near_tie': gap <= 2 * noise}}
+    print(json.dumps(out, indent=1), flush=True)
+    return out
+
+
+def part_steps():
+    import torch
+    model = build_model()
+    lens = [p.numel() for p in make_prompts(model.vocab_size)]
+    n, V = len(lens), model.vocab_size
+    with torch.inference_mode():
+        cache = model.new_kv_cache(n, max(lens) + args.new)
+        cache.k.normal_()
+        cache.v.normal_()
+        cache.lengths.copy_(torch.tensor(lens, dtype=torch.int32))
+        own = torch.arange(n, dtype=torch.int32, device='cuda')
+        tok = torch.zeros(n, dtype=torch.int64, device='cuda')
+        for _ in range(args.trace_steps):
+            tok = model.decode_step(cache, tok, own)[:, :V].argmax(-1)
+        torch.cuda.synchronize()
+        assert int(cache.errors) == 0
+    print(f'{args.trace_steps} decode steps done', flush=True)
+
+
+def part_recompute():
+    import torch
+    model = build_model()
+    g = torch.Generator().manual_seed(2)
+    B, S, new = 8, args.prompt_len, 4
+    toks = torch.randint(0, model.vocab_size, (B, S), generator=g).cuda()
+    with torch.inference_mode():
+        model(tokens=toks[:, :64])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(new):
+            nxt = model(tokens=toks)[:, -1].argmax(-1)
+            toks = torch.cat([toks, nxt[:, None]], dim=1)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+    out = {'what': f'full forward of all {B} x ~{S} tokens for every new token (no cache): what the code before this change could do',
+           'ms_per_new_token_of_a_batch_of_8': round(dt / new * 1e3, 1), 'generated_tokens_per_s': round(B * new / dt, 1)}
+    print(json.dumps(out, indent=1), flush=True)
+    return out
+
+
+def split_trace(stats_csv, steps):
+    rows = [r for r in csv.DictReader(open(stats_csv)) if int(r['Calls']) >= steps]
+    ms = lambda sel: sum(float(r['TotalDurationNs']) for r in rows if sel(r['Name'])) / 1e6 / steps  # noqa: E731
+    att, store = ms(lambda n: 'kv_decode_kernel' in n), ms(lambda n: 'kv_store_kernel' in n)
+    total = ms(lambda n: True)
+    top = sorted(rows, key=lambda r: -float(r['TotalDurationNs']))[:8]
+    return {'steps_traced': steps, 'kernel_ms_per_step': round(total, 3), 'attention_ms_per_step': round(att, 3), 'kv_store_ms_per_step': round(store, 4),
+            'rest_ms_per_step': round(total - att - store, 3),
+            'largest_kernels': [{'name': r['Name'][:90], 'calls': int(r['Calls']), 'ms_per_step': round(float(r['TotalDurationNs']) / 1e6 / steps, 3)} for r in top]}
+
+
+if args.part == 'run':
+    res = part_run()
+elif args.part == 'steps':
+    part_steps()
+    res = None
+elif args.part == 'recompute':
+    res = part_recompute()
+else:
+    wd = args.workdir
+    os.makedirs(wd, exist_ok=True)
+    me = os.path.abspath(__file__)
+    common = f'--prompts {args.prompts} --prompt-len {args.prompt_len} --new {args.new} --trace-steps {args.trace_steps}'
+    cmd = (f'set -o pipefail; timeout -k 10 540 python {me} --part run {common} --json {wd}/run.json > {wd}/run.log 2>&1'
+           f' && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d {wd}/trace -- python {me} --part steps {common} > {wd}/trace.log 2>&1'
+           f' && timeout -k 10 300 python {me} --part recompute {common} --json {wd}/recompute.json > {wd}/recompute.log 2>&1')
+    rc = subprocess.run(['bash', '-c', cmd]).returncode
+    if rc != 0:
+        sys.exit(f'a step failed (exit status {rc}); see the logs under {wd}')
+    res = json.load(open(f'{wd}/run.json'))
+    stats = sorted(glob.glob(f'{wd}/trace/**/*kernel_stats.csv', recursive=True))
+    res['kernel_trace'] = split_trace(stats[-1], args.trace_steps)
+    tr, kt = res['traffic_per_step'], res['kernel_trace']
+    # the traced steps start at the prompts' lengths; the event time above is the mean over all steps, whose cache is a little longer
+    traced_GB = tr['cache_bytes_per_token'] * (res['sum_prompt_tokens'] + args.prompts * (args.trace_steps - 1) / 2) / 1e9
+    kt['cache_GB_per_traced_step'] = round(traced_GB, 3)
+    kt['attention_TB_per_s'] = round(traced_GB / kt['attention_ms_per_step'], 2)
+    kt['kernel_floor_ms_at_5.4_and_6.4_TB_s'] = [round((tr['weights_GB'] + traced_GB) / bw, 3) for bw in HBM_TB_S]
+    kt['kernel_ms_over_floor'] = [round(kt['kernel_ms_per_step'] / f, 2) for f in kt['kernel_floor_ms_at_5.4_and_6.4_TB_s']]
+    res['recompute_for_context'] = json.load(open(f'{wd}/recompute.json'))
+    print(json.dumps(res, indent=1))
+
+if args.json and res is not None:
+    with open(args.json, 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
