@@ -182,18 +182,9 @@ template <int ROWS, int NTHR> struct TileStage {
 // waits for the prefetches of the LATER tiles as well and turns a ring of N tiles into a ring of one.  With the asm form the only
 // waits are the counted ones written out next to the ring barriers.  A request = one wave-instruction: lane l's 16 (or 4) bytes at
 // rsrc base + voff(l) + soff go to LDS byte M0 + 16 l (4 l); the bank swizzle of a tile image is therefore applied on the per-lane
-// SOURCE offset.  The buffer form keeps the per-lane part of the address a constant 32-bit VGPR and the moving part a scalar.
+// SOURCE offset.  The buffer form keeps the per-lane part of the address a constant 32-bit VGPR and the moving part a scalar
+// (resource: buffer_rsrc in common_hip.h).
 typedef __attribute__((address_space(3))) char lds_c;
-constexpr unsigned BUF_RSRC_WORD3 = 0x00020000u;  // raw buffer, 32-bit data format
-__device__ __forceinline__ u32x4 buffer_rsrc(const void* base) {  // stride 0, 2 GiB window
-    const uint64_t a = (uint64_t)(uintptr_t)base;
-    u32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((unsigned)a);
-    r[1] = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);
-    r[2] = 0x7fffffffu;
-    r[3] = BUF_RSRC_WORD3;
-    return r;
-}
 __device__ __forceinline__ void dma16(unsigned lds_dst, unsigned voff, u32x4 rs, unsigned soff) {
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_dst), "v"(voff), "s"(rs), "s"(soff) : "memory");
 }

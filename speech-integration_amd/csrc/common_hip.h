@@ -166,6 +166,23 @@ __device__ __forceinline__ int block_sum_i32(int v, int* red) {
     return t;
 }
 
+// ---- buffer resources ----------------------------------------------------------------------------------------------------
+// Raw buffer over `base`: stride 0, 2 GiB window, 32-bit data format (gfx9 family).  buffer_rsrc: the four words in SGPRs, for the inline-asm
+// LDS-DMA requests (attn_mfma.h, gemm_nt4.h); buffer_rsrc_of: the compiler's resource type, for the raw_buffer_load / _store builtins.
+constexpr unsigned BUF_RSRC_WORD3 = 0x00020000u;
+__device__ __forceinline__ u32x4 buffer_rsrc(const void* base) {
+    const uint64_t a = (uint64_t)(uintptr_t)base;
+    u32x4 r;
+    r[0] = __builtin_amdgcn_readfirstlane((unsigned)a);
+    r[1] = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);
+    r[2] = 0x7fffffffu;
+    r[3] = BUF_RSRC_WORD3;
+    return r;
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc_of(const void* p) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, BUF_RSRC_WORD3);
+}
+
 // ---- debug-build cycle stamps ------------------------------------------------------------------------------------------
 // Cycle counter per phase of a kernel: tick(i) adds the cycles since the previous tick (or reset) to total[i].  A kernel declares
 // PhaseStamps<true, ...> under its own -D flag and PhaseStamps<false, ...> otherwise: that form is empty, the calls compile to nothing.

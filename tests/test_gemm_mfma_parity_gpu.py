@@ -1,4 +1,4 @@
-"""Parity of the bf16 MFMA GEMM (csrc/gemm_mfma.hip and its dispatcher in csrc/gemm_generic.hip) at every dispatch branch and K-loop edge:
+"""Parity of the bf16 MFMA GEMM (csrc/gemm_mfma.hip with its kernel files gemm_wg8.h and gemm_nt4.h, and its dispatcher in csrc/gemm_generic.hip) at every dispatch branch and K-loop edge:
 the 8-wave and the persistent main loops in the NT, NN and TN operand forms, the four epilogues (plain, RoPE, SwiGLU forward / backward), both
 split-K schemes with their reduction kernels, the batched form and both tile orders.
 
@@ -23,7 +23,8 @@ Every reference is computed on the CPU in float64 from the same seeded inputs an
      (about half an ulp of extra error per rounding) misses the bound at once; integers below 256 cannot see that.
 
 Which kernel a call lands on follows the dispatcher: the persistent kernel takes K % 128 == 0, K >= 256 unless IMPL_MFMA_WG8 is set, both
-`accumulate` and a residual are given, or a leading dimension exceeds its 32-bit offsets; split-K goes to the persistent kernel when every slice has
+`accumulate` and a residual are given, or a leading dimension (for the fused SwiGLU forward also the distance from the gate rows to the up rows
+of w13) exceeds its 32-bit offsets; split-K goes to the persistent kernel when every slice has
 at least 6 K-steps.  `check` prints, for every comparison of kind 3, the largest error as a fraction of its bound; the module prints the worst per
 family at its end (pytest -s)."""
 import pytest
@@ -430,6 +431,32 @@ def test_gemm_nt_leading_dimension_beyond_the_32_bit_offsets_takes_the_8wave_ker
         ops.gemm(NT, a, B.t().contiguous().to(DEV), c)
     check_bits(c, r16(S), "gemm[NT, lda = 2^22]")
     untouched(cbuf, [(slice(None), slice(8, 8 + N))], "gemm[NT, lda = 2^22]")
+    del big
+
+
+@pytest.mark.parametrize("inter,ldw", [(256, 2 ** 22), (512, 2 ** 21)], ids=["tile-rows", "up-rows"])
+def test_gemm_swiglu_forward_w13_beyond_the_32_bit_offsets_takes_the_8wave_kernel(ops, lib, inter, ldw):
+    """gemm_swiglu_fwd, M = K = 256, w13 the first 256 columns of an uninitialised [2 inter, ldw] buffer (4 GiB), the smallest shapes at which
+    each of the two limits of the persistent kernel's 32-bit loader offsets is passed: at (256, 2^22) 256 rows span 2^31 bytes (nt4_ld_ok is
+    false); at (512, 2^21) they do not, but the up rows' distance (inter + 128) ldw 2 = 2.7e9 >= 2^31.  Only the window is written; gu is exact
+    on integers and act equals ops.swiglu_fwd(gu) bit for bit.  The dispatch rule (nt4_takes in csrc/gemm_mfma.hip) sends both to the 8-wave
+    kernel, which addresses with 64 bits.  Before that rule existed this entry checked neither limit and the persistent kernel's offsets
+    wrapped: these cases are not to be run on a checkout older than the rule."""
+    M = K = 256
+    X, W, S, _ = operands(M, 2 * inter, K, True, 90 + inter)
+    big = torch.empty(2 * inter, ldw, dtype=BF, device=DEV)
+    w13 = big[:, :K]
+    w13.copy_(W.t())
+    assert 256 * ldw * 2 >= 2 ** 31 or (inter + 128) * ldw * 2 >= 2 ** 31
+    gu = torch.full((M, 2 * inter), SENTINEL, dtype=BF, device=DEV)
+    act = torch.full((M, inter), SENTINEL, dtype=BF, device=DEV)
+    with impl(ops, lib.IMPL_MFMA):
+        ops.gemm_swiglu_fwd(X.to(DEV), w13, gu, act)
+    tag = f"gemm_swiglu_fwd[inter = {inter}, ldw = {ldw}]"
+    check_bits(gu, r16(S), tag + " gu")
+    act_ref = torch.full_like(act, SENTINEL)
+    ops.swiglu_fwd(gu, act_ref)
+    check_bits(act, act_ref, tag + " act against ops.swiglu_fwd(gu)")
     del big
 
 

@@ -46,7 +46,8 @@ def test_the_lint_saw_the_kernels_it_is_meant_for(report):
 
 def test_the_lint_catches_a_missing_drain():
     """The checker itself on a hand-made listing: an LDS-DMA request in a loop whose exit path has no vmcnt(0) is reported, the same
-    listing with the wait is clean; a copy of an accumulation register inside a self-looping MFMA block is reported."""
+    listing with the wait is clean; a copy of an accumulation register inside a self-looping MFMA block is reported; the comparison of two
+    builds reads the literal of a pc-relative address computation as "pc-relative" and every other literal as it stands."""
     import kernel_lint as kl
     def kernel(name, ops):
         k = kl.Kernel(name, 0)
@@ -63,3 +64,9 @@ def test_the_lint_catches_a_missing_drain():
     assert any(e.startswith("R2") for e in kl.lint_kernel(k2))
     k3 = kernel("attn_bwd_dq2_kernel_x", loop + [("s_cbranch_scc1", "0", 0), ("s_endpgm", "", None)])
     assert not kl.lint_kernel(k3)
+    # --against: the distance from a kernel to a global moves when a neighbouring kernel changes size; any other literal is the kernel's own
+    def pcrel(lit, other):
+        return kernel("k_pc", [("s_getpc_b64", "s[14:15]", None), ("s_add_u32", f"s14, s14, {lit}", None), ("s_addc_u32", "s15, s15, 0", None),
+                               ("s_add_u32", f"s4, s4, {other}", None), ("s_endpgm", "", None)])
+    assert kl.stream(pcrel("0xb14dc", "0x40")) == kl.stream(pcrel("0xb44dc", "0x40"))
+    assert kl.stream(pcrel("0xb14dc", "0x40")) != kl.stream(pcrel("0xb14dc", "0x44"))

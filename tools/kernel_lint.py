@@ -17,7 +17,7 @@ runs the same checks in the CPU suite.
 
 ``python tools/kernel_lint.py [lib] --against OTHER_LIB`` compares the two libraries' gfx950 kernels instead (has a change MOVED device
 code or CHANGED it?): the same kernel names on both sides, per kernel the same instruction stream (mnemonic and operands; branch targets as
-offsets within the kernel) and the same VGPR / AGPR / SGPR counts, LDS bytes and private segment size in the code-object notes.  Exits 1 on
+offsets within the kernel, the literals of pc-relative address computations as "pc-relative") and the same VGPR / AGPR / SGPR counts, LDS bytes and private segment size in the code-object notes.  Exits 1 on
 any difference.  Which translation unit a kernel sits in is not compared."""
 from __future__ import annotations
 
@@ -223,17 +223,36 @@ def kernels_of(co: str) -> list[Kernel]:
     return ks
 
 
+def stream(k: Kernel) -> list[tuple]:
+    """A kernel's instructions as compared by --against: (mnemonic, operands, branch target as an offset within the kernel).  The literal of
+    a pc-relative address computation (s_getpc_b64 s[n:n+1], then s_add_u32 sn, sn, LIT and s_addc_u32 sn+1, sn+1, LIT within the next
+    four instructions: the distance to a global such as g_nt4_sched) reads "pc-relative": it moves when a NEIGHBOURING kernel changes size."""
+    ins = list(k.ins)
+    while ins and ins[-1].op == "s_nop":  # fill between the last s_endpgm and the next symbol or the end of the section: not the kernel's code
+        ins.pop()
+    out, pc, since = [], None, 0
+    for i in ins:
+        args = i.args
+        if i.op == "s_getpc_b64":
+            m = re.fullmatch(r"s\[(\d+):(\d+)\]", args.strip())
+            pc, since = ((f"s{m.group(1)}", f"s{m.group(2)}") if m else None), 0
+        elif pc:
+            since += 1
+            if i.op == "s_add_u32" and args.startswith(f"{pc[0]}, {pc[0]}, "):
+                args = f"{pc[0]}, {pc[0]}, pc-relative"
+            elif i.op == "s_addc_u32" and args.startswith(f"{pc[1]}, {pc[1]}, "):
+                args, pc = f"{pc[1]}, {pc[1]}, pc-relative", None
+            if since >= 4:
+                pc = None
+        out.append((i.op, args, None if i.target is None else i.target - k.addr))
+    return out
+
+
 def compare(lib: str, other: str) -> tuple[list[str], int]:
     """Differences between the gfx950 kernels of two libraries, and how many kernels `lib` has."""
     def load(path: str) -> dict[str, Kernel]:
         with tempfile.TemporaryDirectory() as wd:
             return {k.name: k for co in extract(path, wd) for k in kernels_of(co)}
-
-    def stream(k: Kernel) -> list[tuple]:
-        ins = list(k.ins)
-        while ins and ins[-1].op == "s_nop":  # fill between the last s_endpgm and the next symbol or the end of the section: not the kernel's code
-            ins.pop()
-        return [(i.op, i.args, None if i.target is None else i.target - k.addr) for i in ins]
 
     a, b = load(lib), load(other)
     diffs = [f"{n}: only in {lib}" for n in sorted(set(a) - set(b))] + [f"{n}: only in {other}" for n in sorted(set(b) - set(a))]

@@ -2,7 +2,8 @@
 # Build a variant of the library for an in-run A/B: tools/variant.sh <name> <file.hip> <extra hipcc flags...>  ->  variants/libssi_<name>.so
 # (only <file.hip> is recompiled with the flags; the other objects are the in-tree ones).  Use with SSI_HIP_LIB=$PWD/variants/libssi_<name>.so
 # <file.hip> is one of the Makefile's SRCS; the source list and the compile flags are the Makefile's (make print-SRCS / print-CXXFLAGS / ...).
-# A flag read by an attention kernel file (attn_fwd.h, attn_bwd_dq.h, attn_bwd_dkv.h) goes on their translation unit, attention_mfma.hip.
+# A flag read by an attention kernel file (attn_fwd.h, attn_bwd_dq.h, attn_bwd_dkv.h) goes on their translation unit, attention_mfma.hip;
+# one read by a bf16 GEMM kernel file (gemm_mfma.h, gemm_wg8.h, gemm_nt4.h) on theirs, gemm_mfma.hip.
 set -e
 name=$1; src=$2; shift 2
 cd "$(dirname "$0")/../speech-integration_amd/csrc"
