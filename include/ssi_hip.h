@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 18 /* 18: + ssi_kv_store, ssi_attn_decode (greedy generation: a K/V cache and single-query attention over it; nothing else calls them)
+#define SSI_ABI_VERSION 19 /* 19: + ssi_decode_select (constrained greedy decoding: the allowed argmax of a row, its log-probability and its rank in one pass; opt-in)
+                           * 18: + ssi_kv_store, ssi_attn_decode (greedy generation: a K/V cache and single-query attention over it; nothing else calls them)
                            * 17: + ssi_ema_update (fp32 exponential moving average of the flat parameter buffer, one pass chained to AdamW; opt-in)
                            * 16: + ssi_adamw_step_seg (AdamW over segments of the flat buffers with their own lr, weight decay and frozen flag; opt-in)
                            * 15: + ssi_ce_fwd_kl (KL against a frozen teacher's logits inside the cross-entropy kernels; opt-in)
@@ -234,6 +235,32 @@ int ssi_kv_store(const void* qkv, int64_t ld, const int64_t* dest, int64_t rows,
 int ssi_attn_decode(const void* qkv, int64_t ld, const void* k_cache, const void* v_cache, int64_t n_slots, int64_t cap,
                     const int32_t* slot, const int32_t* kv_len, void* out, float* lse, int64_t rows, int n_heads, int n_kv,
                     int head_dim, int32_t* n_bad, int dtype, void* stream);
+
+/* The token of a decode step under a constraint (ABI v19; vLLM's allowed_token_ids and min_tokens, which the reference's generation can set):
+ * the greedy choice among the ALLOWED columns of every row of logits [rows, ld], with its log-probability and its rank under the row's
+ * UNCONSTRAINED distribution.  The logits are read only.
+ * allow / allow_early: bit masks of ceil(vocab / 32) words, bit c % 32 of word c / 32 set = column c may be chosen; either may be NULL = every
+ * real column.  Row r uses allow_early when n_generated != NULL && n_generated[r] < min_new, else allow (the host builds allow_early as allow
+ * without the stop tokens: a row cannot end before it holds min_new tokens).
+ *   token[r]   = the smallest allowed c < vocab whose stored value is the maximum over the allowed columns (torch's first-occurrence argmax of
+ *                the masked row);
+ *   logprob[r] = x[token] - log sum_{c < vocab} exp x[c], the sum over ALL real columns, allowed or not: comparable across constraint settings,
+ *                and what ssi_ce_fwd_metrics gives as -row_nll with the token as label;
+ *   rank[r]    = #{c < vocab : x[c] > x[token]} + #{c < token : x[c] == x[token]} over all real columns, on the stored values: row_rank of
+ *                ssi_ce_fwd_metrics with the token as label.  rank == 0 <=> the constraint did not change the choice.
+ * logprob and rank may be NULL.  A row whose mask has no bit set below vocab: token = -1, logprob = 0, rank = -1.  token is ALWAYS an allowed
+ * column or -1, also on a row with NaN or +-inf logits (it is the next step's embedding index); what else such a row returns is unspecified.
+ * Pad columns [vocab, ld) never count, whatever they hold.
+ * Arithmetic: the header's rule — max, exp-sum and log in fp32, ONE rounding on the store: a term of the sum is exp2(fma(x, log2 e, nm)) with
+ * nm = fl(-max log2 e) (v_exp_f32), logprob = fl(x[token] - fl(max + logf(sum))).
+ * One workgroup of 256 threads per row, no workspace, no atomics.  The row is walked twice (max and allowed argmax; exp-sum and rank), 16-byte
+ * loads when logits and ld * sizeof(element) are 16-byte aligned and a scalar tail over the last vocab % (16 / sizeof(element)) columns, scalar
+ * loads throughout otherwise.  (value, column) pairs are merged in a fixed order with the lower column winning: a thread meets its columns in
+ * rising order, the threads of a wave by an xor tree, the four waves in the order 0..3; the exp-sum by the same trees.  A row's result depends
+ * on that row and the masks only — not on rows, not on the row's place, not on other rows.
+ * SSI_ERR_ARG: null logits or token, vocab < 1, ld < vocab, vocab >= 2^31, rows >= 2^31, min_new < 0.  rows == 0 launches nothing. */
+int ssi_decode_select(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow, const uint32_t* allow_early,
+                      const int32_t* n_generated, int32_t min_new, int64_t* token, float* logprob, int32_t* rank, int dtype, void* stream);
 
 /* ---- K7  SwiGLU elementwise (torchtune FeedForward: w2(silu(w1 x) * w3 x)) ------------------------------------------ */
 /* gu: [rows, 2*inter] = [gate | up]; act[rows, inter] = silu(gate) * up */

@@ -1,0 +1,208 @@
+// Constrained greedy decoding (ABI v19): ssi_decode_select picks a row's token among the ALLOWED columns and reports, under the row's
+// unconstrained distribution, that token's log-probability and its rank.  One launch per decode step, the logits read only.
+//
+// A workgroup of 4 waves takes one row and walks it twice (the 267 KB row of the flagship vocabulary stays in L2 between the walks):
+//   walk 1  the maximum over ALL real columns, and the best (value, column) over the allowed ones;
+//   walk 2  sum exp(x - max) over all real columns and the count of columns ranked before the chosen one.
+// Both walks give a thread the same columns in the same order: 16-byte vectors v = tid, tid + 256, ... of the columns [0, vocab - vocab % VEC)
+// when the row is 16-byte aligned, then single columns tid, tid + 256, ... of what is left (every column when it is not).  A thread meets
+// its columns in rising order, so "take on >" keeps the first occurrence; threads are merged by a fixed xor tree and the four waves in the
+// order 0, 1, 2, 3 with the lower column winning a tie.  A row's result depends on that row and the masks only.
+// NaN: no comparison with a NaN holds, so a NaN column is neither the maximum nor chosen while any allowed column holds a number.
+#include "common_hip.h"
+#include <math.h>
+
+namespace {
+
+constexpr int SEL_THREADS = 256, SEL_WAVES = SEL_THREADS / 64, SEL_UNROLL = 8;
+constexpr float SEL_LOG2E = 1.44269504088896340736f;
+
+// Is `b` (value, column) better than `a`?  A column of -1 is "none yet"; the lower column wins between equal values.
+__device__ __forceinline__ bool sel_better(float av, int ai, float bv, int bi) {
+    return bi >= 0 && (ai < 0 || bv > av || (bv == av && bi < ai));
+}
+
+// bits c % 32 .. c % 32 + n - 1 of word c / 32 (n <= 8 and c % n == 0: one word); NULL = every column
+__device__ __forceinline__ uint32_t sel_mask_bits(const uint32_t* __restrict__ mask, int c) {
+    return mask ? mask[c >> 5] >> (c & 31) : 0xffffffffu;
+}
+
+// One walk over the 16-byte vectors v = tid, tid + 256, ... < nvec of a row, SEL_UNROLL vectors per trip, each with the mask bits of its
+// columns.  The loads of the NEXT trip are issued before the current one is worked on (one wave per SIMD: nothing else hides the latency),
+// and they are UNCONDITIONAL, their index clamped to the last vector: behind a guard hipcc waits for every load in flight before the next
+// use.  Whole trips run without a predicate; the last, partial one tests v < nvec around work that touches no memory.  f(first column,
+// vector, mask bits from that column on) sees a thread's vectors in rising order.
+template <typename T, bool MASKED, typename F>
+__device__ __forceinline__ void sel_walk(const T* __restrict__ x, const uint32_t* __restrict__ mask, int nvec, int tid, F&& f) {
+    constexpr int VEC = Vec16<T>::N, TRIP = SEL_THREADS * SEL_UNROLL;
+    if (nvec <= 0) return;
+    Vec16<T> cur[SEL_UNROLL], nxt[SEL_UNROLL];
+    uint32_t cur_bits[SEL_UNROLL], nxt_bits[SEL_UNROLL];
+    auto fetch = [&](Vec16<T>* q, uint32_t* b, int v0) {
+#pragma unroll
+        for (int u = 0; u < SEL_UNROLL; ++u) {
+            const int v = min(v0 + u * SEL_THREADS, nvec - 1);
+            q[u] = load16<T>(x + (int64_t)v * VEC);
+            b[u] = MASKED ? mask[(v * VEC) >> 5] >> ((v * VEC) & 31) : 0xffffffffu;
+        }
+    };
+    fetch(cur, cur_bits, tid);
+    int v0 = tid;
+    for (int t = nvec / TRIP; t > 0; --t, v0 += TRIP) {
+        fetch(nxt, nxt_bits, v0 + TRIP);
+#pragma unroll
+        for (int u = 0; u < SEL_UNROLL; ++u) f((v0 + u * SEL_THREADS) * VEC, cur[u], cur_bits[u]);
+#pragma unroll
+        for (int u = 0; u < SEL_UNROLL; ++u) {
+            cur[u] = nxt[u];
+            cur_bits[u] = nxt_bits[u];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < SEL_UNROLL; ++u) {
+        const int v = v0 + u * SEL_THREADS;
+        if (v < nvec) f(v * VEC, cur[u], cur_bits[u]);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(SEL_THREADS) void decode_select_kernel(const T* __restrict__ logits, int64_t ld, int vocab,
+                                                                    const uint32_t* __restrict__ allow, const uint32_t* __restrict__ allow_early,
+                                                                    const int32_t* __restrict__ n_generated, int32_t min_new,
+                                                                    int64_t* __restrict__ token, float* __restrict__ logprob,
+                                                                    int32_t* __restrict__ rank, int vec_ok) {
+    constexpr int VEC = Vec16<T>::N;
+    __shared__ float s_f[16];
+    __shared__ int s_i[16];
+    const int64_t r = blockIdx.x;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const T* __restrict__ x = logits + r * ld;
+    const bool early = n_generated != nullptr && n_generated[r] < min_new;
+    const uint32_t* __restrict__ mask = early ? allow_early : allow;
+    const int nvec = vec_ok ? vocab / VEC : 0;            // 16-byte vectors of the row; the columns from nvec * VEC on are walked singly
+    const int tail0 = nvec * VEC;
+
+    // ---- walk 1: the row's maximum, and the best allowed (value, column) ---------------------------------------------------------
+    float gm = -INFINITY, bv = -INFINITY;
+    int bi = -1;
+    auto best = [&](int c0, const Vec16<T>& xv, uint32_t bits) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {                   // selects, no branches: the compiler otherwise jumps around every element
+            const float f = xv.get(e);
+            gm = fmaxf(gm, f);
+            const bool take = ((bits & (1u << e)) != 0) & (f > bv);
+            bv = take ? f : bv;
+            bi = take ? c0 + e : bi;
+        }
+    };
+    if (mask) sel_walk<T, true>(x, mask, nvec, tid, best);
+    else sel_walk<T, false>(x, mask, nvec, tid, best);
+    for (int c = tail0 + tid; c < vocab; c += SEL_THREADS) {
+        const float f = to_f32<T>(x[c]);
+        gm = fmaxf(gm, f);
+        const bool take = ((sel_mask_bits(mask, c) & 1u) != 0) & (f > bv);
+        bv = take ? f : bv;
+        bi = take ? c : bi;
+    }
+    gm = wave_max(gm);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {                    // the fixed xor tree over (value, column) pairs
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (sel_better(bv, bi, ov, oi)) {
+            bv = ov;
+            bi = oi;
+        }
+    }
+    if (lane == 0) {
+        s_f[wave] = gm;
+        s_f[4 + wave] = bv;
+        s_i[wave] = bi;
+    }
+    __syncthreads();
+    gm = fmaxf(fmaxf(s_f[0], s_f[1]), fmaxf(s_f[2], s_f[3]));
+    bv = s_f[4];
+    bi = s_i[0];
+#pragma unroll
+    for (int w = 1; w < SEL_WAVES; ++w) {                 // the four waves, in order (every thread does the same: no broadcast needed)
+        if (sel_better(bv, bi, s_f[4 + w], s_i[w])) {
+            bv = s_f[4 + w];
+            bi = s_i[w];
+        }
+    }
+    if (bi < 0) {
+        // No allowed column holds a value above -inf (uniform over the workgroup): every allowed one is -inf or NaN, or none is allowed.  The
+        // token is then the FIRST allowed column, which is what "the first maximum" means on a row of -inf; a NaN is never chosen above.
+        int first = 0x7fffffff;
+        if (!mask) {
+            first = 0;
+        } else {
+            for (int w = tid; w < (vocab + 31) / 32; w += SEL_THREADS) {
+                const uint32_t bits = mask[w];
+                const int c = w * 32 + __builtin_ctz(bits | 0x80000000u);
+                if (bits != 0 && c < vocab && c < first) first = c;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
+        __syncthreads();
+        if (lane == 0) s_i[wave] = first;
+        __syncthreads();
+        first = min(min(s_i[0], s_i[1]), min(s_i[2], s_i[3]));
+        bi = first == 0x7fffffff ? -1 : first;
+    }
+    if (bi < 0) {                                         // nothing allowed below vocab (uniform over the workgroup)
+        if (tid == 0) {
+            token[r] = -1;
+            if (logprob) logprob[r] = 0.f;
+            if (rank) rank[r] = -1;
+        }
+        return;
+    }
+    if (tid == 0) token[r] = bi;
+    if (!logprob && !rank) return;
+
+    // ---- walk 2: the exp-sum over all real columns and the rank of the chosen one --------------------------------------------------
+    // A term is exp2(fma(x, log2 e, nm)) with nm = fl(-max log2 e): one v_exp_f32 per column, as the register form of the cross-entropy does.
+    const float xt = to_f32<T>(x[bi]);
+    const float nm = -gm * SEL_LOG2E;
+    float s = 0.f;
+    int before = 0;
+    sel_walk<T, false>(x, nullptr, nvec, tid, [&](int c0, const Vec16<T>& xv, uint32_t) {
+        const int eb = bi - c0;                           // the elements e < eb of this vector lie before the chosen column
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const float f = xv.get(e);
+            s += __builtin_amdgcn_exp2f(__builtin_fmaf(f, SEL_LOG2E, nm));
+            before += (int)((f > xt) | ((f == xt) & (e < eb)));      // (| and & on purpose: selects, no branches)
+        }
+    });
+    for (int c = tail0 + tid; c < vocab; c += SEL_THREADS) {
+        const float f = to_f32<T>(x[c]);
+        s += __builtin_amdgcn_exp2f(__builtin_fmaf(f, SEL_LOG2E, nm));
+        before += (int)((f > xt) | ((f == xt) & (c < bi)));
+    }
+    s = block_sum(s, s_f + 8);
+    before = block_sum_i32(before, s_i + 8);
+    if (tid == 0) {
+        if (logprob) logprob[r] = xt - (gm + logf(s));
+        if (rank) rank[r] = before;
+    }
+}
+
+}  // namespace
+
+extern "C" int ssi_decode_select(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow, const uint32_t* allow_early,
+                                 const int32_t* n_generated, int32_t min_new, int64_t* token, float* logprob, int32_t* rank, int dtype,
+                                 void* stream) {
+    SSI_CHECK_ARG(rows >= 0 && rows < (1LL << 31) && (dtype == SSI_F32 || dtype == SSI_BF16));
+    SSI_CHECK_ARG(logits && token && vocab >= 1 && ld >= vocab && vocab < (1LL << 31) && min_new >= 0);
+    if (rows == 0) return SSI_OK;
+    const int64_t esize = dtype == SSI_BF16 ? 2 : 4;
+    const int vec_ok = ((uintptr_t)logits & 15) == 0 && (ld * esize) % 16 == 0;
+    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(decode_select_kernel<T>, dim3((unsigned)rows), dim3(SEL_THREADS), 0, (hipStream_t)stream,
+                                                 (const T*)logits, ld, (int)vocab, allow, allow_early, n_generated, min_new, token, logprob, rank,
+                                                 vec_ok));
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}

@@ -32,6 +32,19 @@ def split_prompts(cfg, tokenizer) -> tuple[list, list]:
     return list(range(len(prompts))), prompts
 
 
+def allowed_tokens(cfg, token_type_ranges: dict, vocab_size: int):
+    """The union of ``gen.allowed_token_types`` (kinds of ``get_token_type_ranges``) and ``sampling_params.allowed_token_ids`` as a bool mask
+    over the vocabulary; None when neither is set."""
+    from ssi.generate import allowed_mask
+    kinds, ids = cfg.gen.get("allowed_token_types"), cfg.sampling_params.get("allowed_token_ids")
+    if kinds is None and ids is None:
+        return None
+    unknown = [k for k in kinds or [] if k not in token_type_ranges]
+    if unknown:
+        raise ValueError(f"gen.allowed_token_types names {unknown}: the token types of this vocabulary are {list(token_type_ranges)}")
+    return allowed_mask(vocab_size, ids=[int(t) for t in ids or []], ranges=[tuple(token_type_ranges[k]) for k in kinds or []])
+
+
 @main_decorator(config_path="../conf", config_name="generate", version_base=None)
 def main(cfg):
     check_greedy(cfg.sampling_params)          # before anything is loaded
@@ -49,10 +62,16 @@ def main(cfg):
     if cfg.gen.get("input") is None:
         ids, prompts = split_prompts(cfg, t.tokenizer)
     stop = cfg.sampling_params.get("stop_token_ids")
+    constraints = {}          # with the defaults the call below is the unconstrained one
+    allowed = allowed_tokens(cfg, t.token_type_ranges, int(t.model.vocab_size))
+    if allowed is not None:
+        constraints["allowed_token_ids"] = allowed
+    if int(cfg.sampling_params.get("min_tokens") or 0) > 0:
+        constraints["min_new_tokens"] = int(cfg.sampling_params.min_tokens)
     summary = generate_file(t.model, t.tokenizer, None if prompts is not None else str(cfg.gen.input), out_path,
                             max_new_tokens=int(cfg.sampling_params.max_tokens), stop_token_ids=None if stop is None else [int(s) for s in stop],
                             tokenizer_decoding={k: cfg.tokenizer_decoding[k] for k in cfg.tokenizer_decoding}, prompts=prompts, ids=ids,
-                            batch_size=int(cfg.gen.batch_size), logprobs=bool(cfg.gen.logprobs), device=t.device)
+                            batch_size=int(cfg.gen.batch_size), logprobs=bool(cfg.gen.logprobs), device=t.device, **constraints)
     LOGGER.info(" | ".join(f"{k}: {v}" for k, v in summary.items()) + f" | wrote {out_path}")
     return summary
 

@@ -7,6 +7,11 @@ of the dev loss and of ``ssi.score``, block-causal over the prompts, every layer
 goes inert — its slot is masked to -1, so it costs no attention and writes no cache — and the group ends when every row has finished or
 at ``max_new_tokens``; whether every row has finished is read back every ``READBACK_EVERY`` steps, not every step.
 
+Constraints (vLLM's ``allowed_token_ids`` and ``min_tokens``; both keep decoding greedy): with ``allowed_token_ids`` or ``min_new_tokens`` the
+token of a step is the first maximum among the ALLOWED columns, from ``ssi_decode_select`` — one launch that also gives the token's
+log-probability under the unconstrained distribution and its rank there (0: the constraint did not bind).  The stop tokens are always allowed;
+none of them can be one of a row's first ``min_new_tokens`` tokens.  Without either argument the loop is the unconstrained one, launch for launch.
+
 Out of scope: sampling, beam search, continuous batching (refilling freed slots), generation under data parallelism, a skinny GEMM for
 small batches, and WER itself (its text normaliser is the reference's dependency; the JSONL written here is what its ``wer.py`` reads)."""
 
@@ -26,7 +31,7 @@ from .constants import CROSS_ENTROPY_IGNORE_IDX
 
 LOGGER = logging.getLogger(__name__)
 
-__all__ = ["Generation", "READBACK_EVERY", "plan_groups", "generate", "generate_file", "output_record", "check_greedy"]
+__all__ = ["Generation", "READBACK_EVERY", "plan_groups", "allowed_mask", "generate", "generate_file", "output_record", "check_greedy"]
 
 READBACK_EVERY = 8    # decode steps between two read-backs of "has every row of the group finished?"
 
@@ -35,12 +40,14 @@ READBACK_EVERY = 8    # decode steps between two read-backs of "has every row of
 class Generation:
     """``token_ids``: the generated tokens, INCLUDING the stop token that ended it; ``finish_reason``: ``"stop"`` or ``"length"``;
     ``stop_reason``: the stop token's id, or None; ``cumulative_logprob``: the sum of the chosen tokens' log-probabilities (natural log;
-    None without ``logprobs=True``); ``prompt_len``: tokens in the prompt."""
+    None without ``logprobs=True``); ``prompt_len``: tokens in the prompt; ``n_constrained``: the steps at which the constraint changed the
+    choice (the chosen token was not the row's unconstrained first), None when no constraint was given."""
     token_ids: list[int]
     finish_reason: str
     stop_reason: int | None
     cumulative_logprob: float | None
     prompt_len: int
+    n_constrained: int | None = None
 
 
 def plan_groups(lengths: Sequence[int], batch_size: int) -> list[list[int]]:
@@ -51,15 +58,84 @@ def plan_groups(lengths: Sequence[int], batch_size: int) -> list[list[int]]:
     return [order[a:a + batch_size] for a in range(0, len(order), batch_size)]
 
 
+def allowed_mask(vocab_size: int, ids: Sequence[int] = (), ranges: Sequence[tuple[int, int]] = ()) -> Tensor:
+    """Bool ``[vocab_size]``: True at every id of ``ids`` and of the inclusive ``(first, last)`` pairs of ``ranges`` (as
+    ``get_token_type_ranges`` gives them).  ``ValueError`` for anything outside ``[0, vocab_size)``."""
+    mask = torch.zeros(int(vocab_size), dtype=torch.bool)
+    for first, last in ranges:
+        first, last = int(first), int(last)
+        if not 0 <= first <= last < vocab_size:
+            raise ValueError(f"allowed_mask: the range ({first}, {last}) is not inside the vocabulary [0, {vocab_size})")
+        mask[first:last + 1] = True
+    ids = [int(t) for t in ids]
+    bad = [t for t in ids if not 0 <= t < vocab_size]
+    if bad:
+        raise ValueError(f"allowed_mask: ids outside the vocabulary [0, {vocab_size}): {bad[:8]}")
+    if ids:
+        mask[torch.tensor(ids, dtype=torch.int64)] = True
+    return mask
+
+
+def _mask_words(mask: Tensor) -> Tensor:
+    """The bit mask ``ssi_decode_select`` reads: int32 words, bit ``c % 32`` of word ``c // 32`` = ``mask[c]``."""
+    words = (mask.numel() + 31) // 32
+    bits = torch.zeros(words * 32, dtype=torch.int64)
+    bits[:mask.numel()] = mask.to(torch.int64)
+    w = (bits.view(words, 32) << torch.arange(32, dtype=torch.int64)).sum(1)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+
+
+@dataclass
+class _Constraint:
+    """What a constrained loop needs on the device: the allowed set after ``min_new`` tokens and before (``early``: without the stop tokens;
+    None when ``min_new == 0``), as bool vectors for the self-check and as the kernel's bit masks."""
+    allow: Tensor
+    allow_words: Tensor
+    early: Tensor | None
+    early_words: Tensor | None
+    min_new: int
+
+
+def _constraint_masks(vocab_size: int, allowed_token_ids, min_new_tokens: int, stop_token_ids: Sequence[int]) -> tuple[Tensor, Tensor] | None:
+    """The host checks of ``allowed_token_ids`` / ``min_new_tokens``: (allowed with the stop tokens, allowed without them) as bool vectors on
+    the CPU, or None when neither argument is set.  Every refusal is a ``ValueError``."""
+    if min_new_tokens < 0:
+        raise ValueError(f"min_new_tokens must be >= 0 (got {min_new_tokens})")
+    if allowed_token_ids is None and min_new_tokens == 0:
+        return None
+    if allowed_token_ids is None:
+        allow = torch.ones(vocab_size, dtype=torch.bool)
+    elif isinstance(allowed_token_ids, Tensor) and allowed_token_ids.dtype == torch.bool:
+        if tuple(allowed_token_ids.shape) != (vocab_size,):
+            raise ValueError(f"allowed_token_ids as a mask is bool [{vocab_size}] (got {tuple(allowed_token_ids.shape)})")
+        allow = allowed_token_ids.detach().cpu().clone()
+    else:
+        allow = allowed_mask(vocab_size, ids=[int(t) for t in allowed_token_ids])
+    if not bool(allow.any()):
+        raise ValueError("allowed_token_ids allows no token")
+    stops = allowed_mask(vocab_size, ids=[int(t) for t in stop_token_ids])
+    early = allow & ~stops
+    if min_new_tokens > 0 and not bool(early.any()):
+        raise ValueError(f"min_new_tokens = {min_new_tokens}, but nothing is allowed besides the stop tokens")
+    return allow | stops, early
+
+
 def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_ids: Sequence[int], pad_id: int, batch_size: int = 256,
-             logprobs: bool = False, device: torch.device | str | None = None) -> list[Generation]:
+             logprobs: bool = False, device: torch.device | str | None = None, allowed_token_ids: Sequence[int] | Tensor | None = None,
+             min_new_tokens: int = 0) -> list[Generation]:
     """Greedy continuation of every prompt (1-D integer sequences), results in INPUT order.  The token of a step is ``argmax`` over the real
     columns ``[:, :vocab_size]`` of the step's logits, with torch's first-occurrence rule.  ``pad_id`` fills the rows that have finished.
     ``logprobs=True``: the forward-only ``ops.ce_fwd_metrics`` runs on the step's logits with the chosen token as label, which gives its
     log-probability with no new kernel; the label's rank it also writes must be 0 on every live row (``RuntimeError`` otherwise).
+    ``allowed_token_ids`` (ids, or a bool ``[vocab_size]`` mask; the stop tokens are always added) and ``min_new_tokens`` (no stop token among
+    a row's first so many tokens): the token of a step, the first included, is ``ops.decode_select``'s — the first maximum among the allowed
+    columns — and with ``logprobs=True`` the sum is of that kernel's log-probabilities, which are over ALL columns (``ops.ce_fwd_metrics`` is
+    not launched); the self-check is "every live row's token is >= 0 and allowed".  With neither, nothing of the above runs.
     Refused before any launch (``ValueError``): an empty prompt, a prompt that with ``max_new_tokens`` exceeds the model's RoPE table or
-    ``max_seq_len``."""
-    max_new_tokens, batch_size = int(max_new_tokens), int(batch_size)
+    ``max_seq_len``; ``min_new_tokens < 0``, an allowed or stop id outside the vocabulary (under a constraint), an empty allowed set,
+    ``min_new_tokens > 0`` with nothing allowed besides the stop tokens."""
+    max_new_tokens, batch_size, min_new_tokens = int(max_new_tokens), int(batch_size), int(min_new_tokens)
+    masks = _constraint_masks(int(model.vocab_size), allowed_token_ids, min_new_tokens, stop_token_ids)
     if max_new_tokens < 1:
         raise ValueError(f"max_new_tokens must be >= 1 (got {max_new_tokens})")
     device = torch.device(device) if device is not None else model.device
@@ -79,8 +155,13 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
     try:
         with torch.inference_mode():
             cache = model.new_kv_cache(n_slots, cap)
+            con = None
+            if masks is not None:
+                allow, early = (m.to(device) for m in masks)
+                con = _Constraint(allow, _mask_words(masks[0]).to(device), early if min_new_tokens else None,
+                                  _mask_words(masks[1]).to(device) if min_new_tokens else None, min_new_tokens)
             for group in groups:
-                for i, g in zip(group, _generate_group(model, cache, [seqs[i] for i in group], max_new_tokens, stop, int(pad_id), logprobs)):
+                for i, g in zip(group, _generate_group(model, cache, [seqs[i] for i in group], max_new_tokens, stop, int(pad_id), logprobs, con)):
                     results[i] = g
     finally:
         if was_training:
@@ -88,23 +169,40 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
     return results  # type: ignore[return-value]
 
 
-def _generate_group(model, cache, seqs: list[Tensor], max_new_tokens: int, stop: Tensor, pad_id: int, logprobs: bool) -> list[Generation]:
+def _generate_group(model, cache, seqs: list[Tensor], max_new_tokens: int, stop: Tensor, pad_id: int, logprobs: bool,
+                    con: _Constraint | None = None) -> list[Generation]:
     n, dev, V = len(seqs), model.device, model.vocab_size
     logits = model.prefill(cache, seqs, max_new_tokens=max_new_tokens)
     alive = torch.ones(n, dtype=torch.bool, device=dev)
     own_slot = torch.arange(n, dtype=torch.int32, device=dev)
     no_slot = torch.full_like(own_slot, -1)
     out = torch.full((n, max_new_tokens), pad_id, dtype=torch.int64, device=dev)
-    n_gen = torch.zeros(n, dtype=torch.int64, device=dev)
+    n_gen = torch.zeros(n, dtype=torch.int64 if con is None else torch.int32, device=dev)     # (int32: what ssi_decode_select reads)
     stop_tok = torch.full((n,), -1, dtype=torch.int64, device=dev)
     cum = torch.zeros(n, dtype=torch.float64, device=dev)
     not_top = torch.zeros(1, dtype=torch.int64, device=dev)
-    if logprobs:
+    if con is not None:
+        tok = torch.empty(n, dtype=torch.int64, device=dev)
+        row_lp = torch.empty(n, dtype=torch.float32, device=dev) if logprobs else None
+        row_rank = torch.empty(n, dtype=torch.int32, device=dev)
+        n_con = torch.zeros(n, dtype=torch.int64, device=dev)
+    elif logprobs:
         row_loss, row_nll = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
         row_rank = torch.empty(n, dtype=torch.int32, device=dev)
     for t in range(max_new_tokens):
-        tok = logits[:, :V].argmax(dim=-1)
-        if logprobs:
+        if con is not None:
+            ops.decode_select(logits, V, tok, row_lp, row_rank, allow=con.allow_words, allow_early=con.early_words,
+                              n_generated=n_gen if con.min_new else None, min_new=con.min_new)
+            at = tok.clamp(min=0)
+            ok = con.allow[at] if con.early is None else torch.where(n_gen < con.min_new, con.early[at], con.allow[at])
+            not_top += (alive & ((tok < 0) | ~ok)).sum()    # the self-check: the chosen token exists and is allowed
+            n_con += alive & (row_rank != 0)
+            if logprobs:
+                cum += torch.where(alive, row_lp, torch.zeros_like(row_lp)).double()
+            tok = at.clone()                                # (a new tensor per step, as argmax gives; never a negative embedding index)
+        else:
+            tok = logits[:, :V].argmax(dim=-1)
+        if con is None and logprobs:
             labels = torch.where(alive, tok, torch.full_like(tok, CROSS_ENTROPY_IGNORE_IDX))
             ops.ce_fwd_metrics(logits, labels, V, CROSS_ENTROPY_IGNORE_IDX, row_loss, None, row_nll, row_rank)
             cum -= torch.where(alive, row_nll, torch.zeros_like(row_nll)).double()
@@ -122,11 +220,14 @@ def _generate_group(model, cache, seqs: list[Tensor], max_new_tokens: int, stop:
     host_out, host_n, host_stop, host_cum = out.cpu(), n_gen.cpu().tolist(), stop_tok.cpu().tolist(), cum.cpu().tolist()
     if int(cache.errors) != 0:
         raise RuntimeError(f"generate: the K/V cache kernels refused {int(cache.errors)} rows (a destination or a slot outside the cache)")
+    if int(not_top) != 0 and con is not None:
+        raise RuntimeError(f"generate: on {int(not_top)} rows decode_select chose no token or one that is not allowed")
     if int(not_top) != 0:
         raise RuntimeError(f"generate: on {int(not_top)} rows the chosen token was not ranked first by ce_fwd_metrics")
+    host_con = n_con.cpu().tolist() if con is not None else [None] * n
     return [Generation(token_ids=host_out[i, :host_n[i]].tolist(), finish_reason="stop" if host_stop[i] >= 0 else "length",
                        stop_reason=host_stop[i] if host_stop[i] >= 0 else None, cumulative_logprob=host_cum[i] if logprobs else None,
-                       prompt_len=int(seqs[i].numel())) for i in range(n)]
+                       prompt_len=int(seqs[i].numel()), n_constrained=host_con[i]) for i in range(n)]
 
 
 # ---- JSONL in, JSONL out ---------------------------------------------------------------------------------------------------------
@@ -172,7 +273,8 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     how ``scripts/generate.py`` hands over a data split.  Every output line: ``id``, ``prompt_token_ids``, ``prompt`` and ``outputs``, a list
     with one entry holding ``index, text, token_ids, cumulative_logprob, finish_reason, stop_reason, stop_reason_text``, in INPUT order.
     ``stop_token_ids`` default to the tokenizer's ``[eom_id, eot_id, eos_id]``; ``pad_id`` to the tokenizer's; ``kw`` goes to ``generate``.
-    Returns ``{"items", "generated_tokens", "stopped"}``."""
+    Returns ``{"items", "generated_tokens", "stopped"}``, and under a constraint (``allowed_token_ids`` / ``min_new_tokens`` in ``kw``) also
+    ``"constrained_tokens"``: the tokens the constraint changed, over all items."""
     if in_path is not None:
         ids, prompts = _read_prompts(tokenizer, in_path)
     elif prompts is None:
@@ -187,8 +289,11 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     with open(out_path, "w", encoding="utf-8") as f:
         for item_id, p, g in zip(ids, prompts, gens):
             f.write(json.dumps(output_record(item_id, p, g, tokenizer, tokenizer_decoding), ensure_ascii=False) + "\n")
-    return {"items": len(gens), "generated_tokens": sum(len(g.token_ids) for g in gens),
-            "stopped": sum(g.finish_reason == "stop" for g in gens)}
+    summary = {"items": len(gens), "generated_tokens": sum(len(g.token_ids) for g in gens),
+               "stopped": sum(g.finish_reason == "stop" for g in gens)}
+    if kw.get("allowed_token_ids") is not None or int(kw.get("min_new_tokens", 0)) != 0:
+        summary["constrained_tokens"] = sum(g.n_constrained or 0 for g in gens)
+    return summary
 
 
 # ---- what the script accepts of the reference's sampling_params ------------------------------------------------------------------
@@ -197,10 +302,22 @@ GREEDY = {"n": 1, "temperature": 0.0, "top_p": 1.0, "top_k": -1, "presence_penal
 
 def check_greedy(sampling_params) -> None:
     """``NotImplementedError`` for anything but greedy decoding of one sequence: ``temperature != 0``, ``top_p != 1``, ``top_k != -1``, a
-    penalty off its default, ``n != 1`` (the reference pins its WER to greedy, too).  ``max_tokens`` and ``stop_token_ids`` are free; a key
-    this module does not know is refused as well."""
+    penalty off its default, ``n != 1`` (the reference pins its WER to greedy, too).  ``max_tokens`` and ``stop_token_ids`` are free;
+    ``min_tokens`` (an integer >= 0) and ``allowed_token_ids`` (null or a list of integers) keep decoding greedy and pass (``ValueError`` for
+    another value); a key this module does not know is refused as well."""
     for key in sampling_params:
         if key in ("max_tokens", "stop_token_ids"):
+            continue
+        if key == "min_tokens":
+            value = sampling_params[key]
+            if isinstance(value, bool) or not isinstance(value, int) or value < 0:
+                raise ValueError(f"sampling_params.min_tokens = {value!r}: an integer >= 0")
+            continue
+        if key == "allowed_token_ids":
+            value = sampling_params[key]
+            if value is not None and (isinstance(value, (str, bytes)) or not hasattr(value, "__iter__")
+                                      or any(isinstance(t, bool) or not isinstance(t, int) for t in value)):
+                raise ValueError(f"sampling_params.allowed_token_ids = {value!r}: null or a list of integers")
             continue
         if key not in GREEDY:
             raise NotImplementedError(f"sampling_params.{key} is not supported: generation is greedy")

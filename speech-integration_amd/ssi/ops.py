@@ -10,7 +10,7 @@ from torch import Tensor
 from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
-__all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "swiglu_fwd",
+__all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "decode_select", "swiglu_fwd",
            "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "ema_update", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
@@ -224,6 +224,29 @@ def attn_decode(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, slot: Tensor, kv_
     check(_lib.load().ssi_attn_decode(ptr(qkv), qkv.stride(0), ptr(k_cache), ptr(v_cache), k_cache.shape[0], k_cache.shape[1], ptr(slot),
                                       ptr(kv_len), ptr(out), ptr(lse), rows, n_heads, n_kv, head_dim, ptr(n_bad), dtype_code(qkv.dtype),
                                       stream_ptr()), "ssi_attn_decode")
+
+
+def decode_select(logits: Tensor, vocab: int, token: Tensor, logprob: Tensor | None = None, rank: Tensor | None = None, *,
+                  allow: Tensor | None = None, allow_early: Tensor | None = None, n_generated: Tensor | None = None, min_new: int = 0) -> None:
+    """The constrained greedy token of every row of ``logits`` ([rows, ld], unit inner stride; read only): ``token`` (int64) = the first
+    allowed column below ``vocab`` that holds the maximum over the allowed columns, ``logprob`` (fp32, optional) = its log-probability over ALL
+    real columns, ``rank`` (int32, optional) = its position in a stable descending sort of the row (0: the constraint did not bind).  ``allow``
+    / ``allow_early``: int32 bit masks of ``ceil(vocab / 32)`` words (bit ``c % 32`` of word ``c // 32``), ``None`` = every column; row ``r``
+    takes ``allow_early`` while ``n_generated[r] < min_new`` (int32 per row).  A row with nothing allowed: -1 / 0 / -1.  ``ssi_decode_select``."""
+    ptr(logits)
+    if logits.dim() != 2 or logits.stride(1) != 1 or not 1 <= vocab <= logits.shape[1]:
+        raise _lib.HipLibraryError(f"decode_select: logits must be [rows, >= vocab] with unit inner stride (got {tuple(logits.shape)}, vocab {vocab})")
+    rows, words = logits.shape[0], (vocab + 31) // 32
+    for name, t, dtype in (("token", token, torch.int64), ("logprob", logprob, torch.float32), ("rank", rank, torch.int32),
+                           ("n_generated", n_generated, torch.int32)):
+        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.numel() != rows or t.device != logits.device):
+            raise _lib.HipLibraryError(f"decode_select: {name} is one {dtype} per row of logits, on its device")
+    for name, t in (("allow", allow), ("allow_early", allow_early)):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != words or t.device != logits.device):
+            raise _lib.HipLibraryError(f"decode_select: {name} is {words} int32 words (one bit per column) on the device of logits")
+    check(_lib.load().ssi_decode_select(ptr(logits), logits.stride(0), rows, int(vocab), ptr(allow), ptr(allow_early), ptr(n_generated),
+                                        int(min_new), ptr(token), ptr(logprob), ptr(rank), dtype_code(logits.dtype), stream_ptr()),
+          "ssi_decode_select")
 
 
 def swiglu_fwd(gu: Tensor, act: Tensor) -> None:

@@ -1,5 +1,5 @@
 """What greedy generation costs at the 1B shape (Llama-3.2-1B + 5000 DSUs, bf16, random weights): 256 prompts of about 1000 tokens, 256 new
-tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute] [--json profiles/generate.json]
+tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained] [--json profiles/generate.json]
 
 run        prefill time, milliseconds per decode step (event time over all steps, host gaps included), generated tokens per second, and a
            self-check: the first generated token of every prompt against the argmax of a plain full forward of that prompt alone (with
@@ -8,6 +8,12 @@ steps      decode steps only, on a cache filled with random numbers at the same 
            ``rocprofv3 --kernel-trace --stats`` in a run of its own, so that a step's kernel time splits into attention (kv_decode_kernel),
            the cache write (kv_store_kernel) and the rest.  Kernels launched fewer times than there are steps are set-up, not step.
 recompute  for context, the only thing the code could do before: re-running the full forward for every new token (8 prompts, 4 tokens).
+constrained  (not part of ``all``; python tools/generate_bench.py --part constrained --json profiles/generate_constrained.json) what constrained
+           decoding costs, ONE process alternating the forms over ``--rounds`` rounds, median and min..max of the rounds: ``ssi_decode_select``
+           alone on [prompts, vocab_pad] bf16 logits against a torch restatement (masked_fill + argmax + log_softmax gather), on one buffer (what
+           the caches hold) and rotating over buffers larger than the caches together; and a decode step whose token comes from the kernel
+           (``--allowed-types``, ``--min-new-tokens``) against the unconstrained step (argmax + the forward-only cross-entropy for the
+           log-probability) and the step without log-probabilities, on a cache filled with random numbers at the same lengths.
 all        the three as child processes, each under its own ``timeout``, chained with ``&&``; then the results and the floor from traffic
            alone (weights read once per step, the cache read once per step) are merged into --json."""
 import argparse, csv, glob, json, os, statistics, subprocess, sys, time
@@ -16,12 +22,15 @@ PKG = os.path.join(ROOT, 'speech-integration_amd')
 sys.path.insert(0, PKG)
 
 ap = argparse.ArgumentParser()
-ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute'])
+ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained'])
 ap.add_argument('--prompts', type=int, default=256)
 ap.add_argument('--prompt-len', type=int, default=1000)
 ap.add_argument('--new', type=int, default=256)
 ap.add_argument('--trace-steps', type=int, default=32)
 ap.add_argument('--json', default=None)
+ap.add_argument('--allowed-types', default='text,special_text', help='constrained: kinds of get_token_type_ranges, comma-separated')
+ap.add_argument('--min-new-tokens', type=int, default=0, help='constrained: rows below it take the mask without the stop tokens')
+ap.add_argument('--rounds', type=int, default=7)
 ap.add_argument('--workdir', default=os.path.join(ROOT, 'prof_out', 'generate_bench'))
 args = ap.parse_args()
 HBM_TB_S = (5.4, 6.4)   # what the README records for the AdamW and EMA passes
@@ -164,6 +173,128 @@ def part_recompute():
     return out
 
 
+def spread(xs, digits=2):
+    return {'median': round(statistics.median(xs), digits), 'min': round(min(xs), digits), 'max': round(max(xs), digits)}
+
+
+def part_constrained():
+    import copy
+    import torch
+    from ssi import ops
+    from ssi.constants import CROSS_ENTROPY_IGNORE_IDX as IGNORE
+    from ssi.generate import _mask_words, allowed_mask
+    from ssi.llama_configs import configllama3_2_1b
+    from ssi.train_utils import get_token_type_ranges
+    c = copy.deepcopy(configllama3_2_1b)
+    c.n_dsus = 5000
+    ranges = get_token_type_ranges(c)
+    kinds = [k for k in args.allowed_types.split(',') if k]
+    model = build_model()
+    n, V, ld = args.prompts, model.vocab_size, model.vocab_pad
+    allow = allowed_mask(V, ranges=[ranges[k] for k in kinds])
+    first_special = ranges['special_text'][0]
+    stops = allowed_mask(V, ids=[first_special + k for k in (1, 8, 9)])      # end_of_text, eom, eot: the tokenizer's default stop tokens
+    allow, early = allow | stops, allow & ~stops
+    allow_dev, allow_w, early_w = allow.cuda(), _mask_words(allow).cuda(), _mask_words(early).cuda()
+    min_new = args.min_new_tokens
+    n_gen = torch.zeros(n, dtype=torch.int32, device='cuda')
+    tok = torch.empty(n, dtype=torch.int64, device='cuda')
+    lp, nll, loss = (torch.empty(n, dtype=torch.float32, device='cuda') for _ in range(3))
+    rk = torch.empty(n, dtype=torch.int32, device='cuda')
+
+    def kernel(x):
+        ops.decode_select(x, V, tok, lp, rk, allow=allow_w, allow_early=early_w if min_new else None, n_generated=n_gen if min_new else None,
+                          min_new=min_new)
+        return tok
+
+    def restated(x):
+        masked = x[:, :V].masked_fill(~allow_dev, float('-inf'))
+        t = masked.argmax(-1)
+        return t, torch.log_softmax(x[:, :V].float(), -1).gather(1, t[:, None])[:, 0]
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(reps):
+            fn(i)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3        # us per call
+
+    res = {'geometry': f'[{n}, {ld}] bf16 logits, vocab {V}; allowed {kinds} + 3 stop tokens = {int(allow.sum())} ids; min_new_tokens {min_new}; '
+                       f'{args.rounds} rounds alternating the forms in one process'}
+    with torch.inference_mode():
+        g = torch.Generator(device='cuda').manual_seed(3)
+        bufs = [torch.randn(n, ld, generator=g, device='cuda').mul_(3).to(torch.bfloat16) for _ in range(8)]      # 8 x 68 MB: beyond L2 + MALL
+        t_k, l_k = kernel(bufs[0]).clone(), lp.clone()
+        t_r, l_r = restated(bufs[0])
+        res['self_check'] = {'tokens_equal_the_restatement': bool(torch.equal(t_k, t_r)),
+                             'largest_logprob_difference': float((l_k - l_r).abs().max())}
+        forms = {'decode_select_one_buffer_us': lambda i: kernel(bufs[0]), 'torch_restatement_one_buffer_us': lambda i: restated(bufs[0]),
+                 'decode_select_rotating_buffers_us': lambda i: kernel(bufs[i % 8]), 'torch_restatement_rotating_buffers_us': lambda i: restated(bufs[i % 8])}
+        for fn in forms.values():
+            timed(fn, 8)
+        got = {k: [] for k in forms}
+        for _ in range(args.rounds):
+            for k, fn in forms.items():
+                got[k].append(timed(fn, 40))
+        res['kernel_alone'] = {k: spread(v) for k, v in got.items()}
+        res['kernel_alone']['row_bytes_read_once_MB'] = round(n * V * 2 / 1e6, 1)
+        res['kernel_alone']['decode_select_TB_per_s_counting_one_read'] = {k: round(n * V * 2 / 1e6 / res['kernel_alone'][k]['median'], 2)
+                                                                           for k in ('decode_select_one_buffer_us', 'decode_select_rotating_buffers_us')}
+        del bufs
+        torch.cuda.empty_cache()
+
+        # a decode step, on a cache of random numbers at the prompts' lengths (every block of steps starts from the same lengths)
+        lens = torch.tensor([p.numel() for p in make_prompts(V)], dtype=torch.int32)
+        steps = args.trace_steps
+        cache = model.new_kv_cache(n, int(lens.max()) + steps + 1)
+        cache.k.normal_()
+        cache.v.normal_()
+        own = torch.arange(n, dtype=torch.int32, device='cuda')
+        alive = torch.ones(n, dtype=torch.bool, device='cuda')
+
+        def step_plain(t):
+            return model.decode_step(cache, t, own)[:, :V].argmax(-1)
+
+        def step_logprob(t):
+            x = model.decode_step(cache, t, own)
+            t = x[:, :V].argmax(-1)
+            ops.ce_fwd_metrics(x, torch.where(alive, t, torch.full_like(t, IGNORE)), V, IGNORE, loss, None, nll, rk)
+            return t
+
+        def step_constrained(t):
+            return kernel(model.decode_step(cache, t, own)).clone()
+
+        def block(step):
+            cache.lengths.copy_(lens)
+            t = torch.zeros(n, dtype=torch.int64, device='cuda')
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(steps):
+                t = step(t)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / steps
+
+        sforms = {'unconstrained_argmax_only_ms': step_plain, 'unconstrained_with_logprob_ms': step_logprob, 'constrained_ms': step_constrained}
+        for fn in sforms.values():
+            block(fn)
+        got = {k: [] for k in sforms}
+        for _ in range(args.rounds):
+            for k, fn in sforms.items():
+                got[k].append(block(fn))
+        assert int(cache.errors) == 0
+        st = {k: spread(v, 4) for k, v in got.items()}
+        st['steps_per_block'] = steps
+        st['constrained_minus_unconstrained_with_logprob_ms'] = round(st['constrained_ms']['median'] - st['unconstrained_with_logprob_ms']['median'], 4)
+        st['unconstrained_with_logprob_spread_ms'] = round(st['unconstrained_with_logprob_ms']['max'] - st['unconstrained_with_logprob_ms']['min'], 4)
+        res['decode_step'] = st
+    print(json.dumps(res, indent=1), flush=True)
+    return res
+
+
 def split_trace(stats_csv, steps):
     rows = [r for r in csv.DictReader(open(stats_csv)) if int(r['Calls']) >= steps]
     ms = lambda sel: sum(float(r['TotalDurationNs']) for r in rows if sel(r['Name'])) / 1e6 / steps  # noqa: E731
@@ -182,6 +313,8 @@ elif args.part == 'steps':
     res = None
 elif args.part == 'recompute':
     res = part_recompute()
+elif args.part == 'constrained':
+    res = part_constrained()
 else:
     wd = args.workdir
     os.makedirs(wd, exist_ok=True)
