@@ -25,7 +25,9 @@ import os
 
 import logging
 import math
-from typing import Any, Optional
+from collections import namedtuple
+from dataclasses import make_dataclass
+from typing import Any, Optional, Sequence
 
 import torch
 from torch import Tensor, nn
@@ -80,9 +82,7 @@ class _Arena:
         self.buf: dict[str, Tensor] = {}
 
     def get(self, name: str, shape: tuple, dtype: torch.dtype) -> Tensor:
-        n = 1
-        for s in shape:
-            n *= s
+        n = math.prod(shape)
         t = self.buf.get(name)
         if t is None or t.dtype != dtype or t.numel() < n:
             # a buffer that has to GROW (ragged batches: the packed length differs from batch to batch) takes a quarter more than asked, so
@@ -114,6 +114,13 @@ class KVCache:
     @property
     def cap(self) -> int:
         return self.k.shape[2]
+
+
+# One decoder layer's activation tensors, views of arena storage; ``HipLlamaDecoder._layer_bufs`` names and shapes them.  The final norm is the
+# record of "layer" ``num_layers``: ``h_in`` its input, ``xn1`` its output, ``rstd1`` its rstd, the rest None.  ``lse`` is None in a decode step.
+_LayerBufs = namedtuple("_LayerBufs", "h_in xn1 rstd1 qkv att lse hmid xn2 rstd2 gu act h_out", defaults=(None,) * 9)
+# What a training forward leaves for its backward; ``h_last`` / ``rstdf``: input (without layers: the embedding's output) and rstd of the final norm.
+_Saved = make_dataclass("_Saved", "tok B S gen pos ds de plan layers h_last rstdf".split())
 
 
 class HipLlamaDecoder(nn.Module):
@@ -154,11 +161,8 @@ class HipLlamaDecoder(nn.Module):
 
         def take(name: str, shape: tuple) -> None:
             nonlocal off
-            n = 1
-            for s in shape:
-                n *= s
             self._slices[name] = (off, shape)
-            off += _align(n, 8)
+            off += _align(math.prod(shape), 8)
 
         # [E_pad | attention weights of every layer: L0.wqkv, L0.wo, L1.wqkv, ... | L0: w13, w2, sa_norm, mlp_norm | L1: ... | norm].
         # The attention projections sit together, one layer after the other at a fixed stride: their weight gradients (64 and 96 output
@@ -199,10 +203,7 @@ class HipLlamaDecoder(nn.Module):
         # ---- torchtune-named parameters as views ------------------------------------------------------------------
         def view(name: str, rows: Optional[tuple[int, int]] = None, buf: Optional[Tensor] = None) -> Tensor:
             o, shape = self._slices[name]
-            n = 1
-            for s in shape:
-                n *= s
-            t = (self._flat if buf is None else buf)[o:o + n].view(shape)
+            t = (self._flat if buf is None else buf)[o:o + math.prod(shape)].view(shape)
             return t if rows is None else t[rows[0]:rows[1]]
 
         self._view = view
@@ -247,7 +248,7 @@ class HipLlamaDecoder(nn.Module):
         self._rope = llama3_rope_table(self.head_dim, cache_len, rope_base, scale_factor).to(device)
         self._arena = _Arena(device)
         self._anchor = torch.zeros(1, dtype=torch.float32, device=device, requires_grad=True)
-        self._saved: Optional[dict] = None       # activations of the forward awaiting its backward
+        self._saved: Optional[_Saved] = None     # activations of the forward awaiting its backward
         self._fwd_generation = 0
         self.pending_grad_scale: Optional[Tensor] = None  # lazy scale_grads (device fp32 scalar), consumed by the optimizer
         # Gradient buffer protocol: nothing zeroes the 2.5 GB buffer between optimizer steps.  `_grads_dirty` = the buffer holds the
@@ -316,9 +317,7 @@ class HipLlamaDecoder(nn.Module):
         self._frozen_ranges = frozen
         for p, name, rows in self._param_src:
             o, shape = self._slices[name]
-            cols = 1
-            for d in shape[1:]:
-                cols *= d
+            cols = math.prod(shape[1:])
             lo, hi = (o, o + shape[0] * cols) if rows is None else (o + rows[0] * cols, o + rows[1] * cols)
             is_frozen = self._range_frozen(lo, hi)
             p.requires_grad_(not is_frozen)
@@ -350,9 +349,7 @@ class HipLlamaDecoder(nn.Module):
         if not self._frozen_ranges:
             return False
         o, shape = self._slices[name]
-        n = 1
-        for d in shape:
-            n *= d
+        n = math.prod(shape)
         return all(self._range_frozen(o + k * stride, o + k * stride + n) for k in range(count))
 
     def zero_grad(self, set_to_none: bool = True) -> None:
@@ -416,6 +413,9 @@ class HipLlamaDecoder(nn.Module):
         g = 256 // math.gcd(batch, 256)
         g = max(g, 128)  # 128: the MFMA attention kernels walk 128-key groups (a ragged batch maximum would otherwise drop to the
         return _align(seq, g)  # generic attention kernels, 5x slower end to end)
+
+    def _padded_rows(self, n: int) -> int:  # n rows that are not sequences (prefill's last tokens, a decode step) as whole MFMA tiles
+        return _align(max(n, 1), VOCAB_ALIGN) if self._mfma_shapes() else n
 
     # ---- forward: decoder stack --------------------------------------------------------------------------------------
     @staticmethod
@@ -487,9 +487,7 @@ class HipLlamaDecoder(nn.Module):
         """``kv_sink`` (``prefill``): ``(KVCache, dest)`` with ``dest`` int64 ``[B * S]`` on the device — after every layer's QKV projection
         the k / v columns of row t are stored at ``dest[t]`` of that layer's cache (-1: not stored).  ``None``: not one launch more."""
         B, S = tokens.shape
-        pos = ds = de = None
-        self.position_errors = None
-        plan = None
+        pos = ds = de = plan = self.position_errors = None
         if input_pos is not None and save:
             if attn_plan is None and not input_pos.is_cuda:  # host positions: the plan costs no device sync (the trainer's prefetch thread
                 attn_plan = self.build_attn_plan(input_pos)   # brings one along with the batch instead)
@@ -505,59 +503,81 @@ class HipLlamaDecoder(nn.Module):
             # and the clamped positions are COUNTED (position_errors): the trainer raises on them from its one read-back per micro-batch
             self.position_errors = torch.zeros(1, dtype=torch.int32, device=tokens.device)
             pos, ds, de = ops.doc_ranges(input_pos.to(tokens.device), self._rope.shape[0] - 1, self.position_errors)  # one launch
-        T, D, I = B * S, self.embed_dim, self.intermediate_dim
-        H, KV, hd, dt, A = self.num_heads, self.num_kv_heads, self.head_dim, self.dtype, self._arena
+        H, KV, hd = self.num_heads, self.num_kv_heads, self.head_dim
         if pos is None and S > self._rope.shape[0]:  # implicit positions 0 .. S-1; with input_pos the table is indexed by (clamped) positions
             raise ValueError(f"sequence length {S} exceeds the RoPE cache ({self._rope.shape[0]})")
         tok = tokens.reshape(-1).contiguous()
-        L = self.num_layers
-        # a forward that saves nothing (eval, no_grad) writes ".x" buffers only: it may run between a training forward and its backward
-        h = A.get("h0" if save else "h0.x", (T, D), dt)
-        ops.embed_fwd(tok, self._view("emb"), h, self.vocab_size)
-        for l in range(L):
-            sfx = f"{l}" if save else "x"
-            xn1 = A.get("xn1.all", (L, T, D), dt)[l] if save else A.get("xn1.x", (T, D), dt)  # saved per layer in ONE buffer: batched wgrads
-            rstd1 = A.get(f"rstd1.{sfx}", (T,), torch.float32)
-            ops.rmsnorm_fwd(h, self._view(f"L{l}.sa_norm"), xn1, rstd1, self.norm_eps)
-            qkv = A.get(f"qkv.{sfx}", (T, self.qkv_dim), dt)
-            ops.gemm_rope(xn1, self._view(f"L{l}.wqkv"), qkv, S, H + KV, hd, self._rope, positions=pos)  # RoPE in the GEMM epilogue
+        if save:  # the last saving forward's records hold views of arena storage, and a buffer that has to grow can be freed before the larger
+            self._saved = None  # one is requested (_Arena.get) only if nothing refers to it: dropped BEFORE this forward asks the arena for anything
+
+        def attend(l: int, b: _LayerBufs) -> None:
             if kv_sink is not None:
-                ops.kv_store(qkv, kv_sink[1], kv_sink[0].k[l], kv_sink[0].v[l], H, KV, hd, n_bad=kv_sink[0].errors)
-            att = A.get("att.all", (L, T, H * hd), dt)[l] if save else A.get("att.x", (T, H * hd), dt)
-            lse = A.get(f"lse.{sfx}", (B * H * S,), torch.float32)
-            ops.attn_fwd(qkv, att, lse, B, S, H, KV, hd, ds, de)
-            hmid = A.get(f"hmid.{sfx}", (T, D), dt)
-            self._gemm(GEMM_NT, att, self._view(f"L{l}.wo"), hmid, residual=h)
-            xn2 = A.get(f"xn2.{sfx}", (T, D), dt)
-            rstd2 = A.get(f"rstd2.{sfx}", (T,), torch.float32)
-            ops.rmsnorm_fwd(hmid, self._view(f"L{l}.mlp_norm"), xn2, rstd2, self.norm_eps)
-            gu = A.get(f"gu.{sfx}", (T, 2 * I), dt)
-            act = A.get(f"act.{sfx}", (T, I), dt)
-            ops.gemm_swiglu_fwd(xn2, self._view(f"L{l}.w13"), gu, act)  # SwiGLU rides in the GEMM epilogue
-            hn_name = f"h{l + 1}" if save else f"hx{l & 1}"
-            hnext = A.get(hn_name, (T, D), dt)
-            self._gemm(GEMM_NT, act, self._view(f"L{l}.w2"), hnext, residual=hmid)
-            h = hnext
-        hn = A.get("hn" if save else "hn.x", (T, D), dt)
-        rstdf = A.get("rstdf" if save else "rstdf.x", (T,), torch.float32)
-        ops.rmsnorm_fwd(h, self.norm.scale, hn, rstdf, self.norm_eps)
+                ops.kv_store(b.qkv, kv_sink[1], kv_sink[0].k[l], kv_sink[0].v[l], H, KV, hd, n_bad=kv_sink[0].errors)
+            ops.attn_fwd(b.qkv, b.att, b.lse, B, S, H, KV, hd, ds, de)
+
+        layers, final = self._run_stack("train" if save else "x", tok, B, S, S, pos, attend)  # (eval, no_grad: the ".x" buffers only)
         if save:
             self._fwd_generation += 1
-            self._saved = {"tok": tok, "B": B, "S": S, "gen": self._fwd_generation, "pos": pos, "ds": ds, "de": de, "plan": plan}
-        return hn
+            self._saved = _Saved(tok, B, S, self._fwd_generation, pos, ds, de, plan, layers, final.h_in, final.rstd1)
+        return final.xn1
+
+    def _layer_bufs(self, mode: str, l: int, rows: int, B: int, S: int, below: Sequence[_LayerBufs] = ()) -> _LayerBufs:
+        """THE table of the stack's activation buffers, the only place that names and shapes them: layer ``l``'s record for ``rows = B * S``.
+        ``"train"``: a set per layer, kept for the backward (``qkv.{l}`` ..., ``h0``, ``h{l+1}``; ``xn1`` / ``att`` of all layers in ONE buffer
+        each: the batched weight gradients read a group of layers at a stride).  ``"x"`` (eval, teacher, prefill): one set (``qkv.x`` ...),
+        ``hx0`` / ``hx1`` in turn.  ``"g"`` (``decode_step``): one set (``qkv.g`` ...), ONE norm output and rstd (``xn.g``, ``rstd.g``), no lse,
+        ``h1.g`` / ``h2.g`` in turn.  The modes share no buffer: a forward of one may run between a training forward and its backward.
+        ``below``: the records of layers ``0 .. l - 1``.  In modes ``x`` and ``g`` nothing but ``h_out`` of layers 1 and 2 is looked up again."""
+        if mode != "train" and 3 <= l < self.num_layers:
+            return below[l - 2]   # (the two h buffers take turns: what layer l - 2 read and wrote)
+        A, dt, f32, L, train = self._arena, self.dtype, torch.float32, self.num_layers, mode == "train"
+        D, I, Q = self.embed_dim, self.intermediate_dim, self.num_heads * self.head_dim
+        nm = (lambda s: f"{s}.{l}") if train else (lambda s: f"{s}.x") if mode == "x" else (lambda s: s.rstrip("12") + ".g")
+        h_in = below[-1].h_out if below else A.get("h0" if train else nm("h0"), (rows, D), dt)
+        if l == L:
+            return _LayerBufs(h_in, A.get("hn" if train else "xn.g" if mode == "g" else "hn.x", (rows, D), dt),
+                              A.get("rstdf" if train else "rstd.g" if mode == "g" else "rstdf.x", (rows,), f32))
+        h_out = A.get(f"h{l + 1}" if train else f"hx{l & 1}" if mode == "x" else f"h{1 + (l & 1)}.g", (rows, D), dt)
+        if below and not train:
+            return below[-1]._replace(h_in=h_in, h_out=h_out)
+        xn1 = A.get("xn1.all", (L, rows, D), dt)[l] if train else A.get(nm("xn1"), (rows, D), dt)
+        att = A.get("att.all", (L, rows, Q), dt)[l] if train else A.get(nm("att"), (rows, Q), dt)
+        lse = None if mode == "g" else A.get(nm("lse"), (B * self.num_heads * S,), f32)
+        return _LayerBufs(h_in, xn1, A.get(nm("rstd1"), (rows,), f32), A.get(nm("qkv"), (rows, self.qkv_dim), dt), att, lse,
+                          A.get(nm("hmid"), (rows, D), dt), A.get(nm("xn2"), (rows, D), dt), A.get(nm("rstd2"), (rows,), f32),
+                          A.get(nm("gu"), (rows, 2 * I), dt), A.get(nm("act"), (rows, I), dt), h_out)
+
+    def _run_stack(self, mode: str, tok: Tensor, B: int, S: int, seq_len: int, pos: Optional[Tensor], attend) -> tuple[list, _LayerBufs]:
+        """Embedding, every layer, final norm on ``mode``'s buffers -> (the layers' records, the final norm's).  ``attend(l, record)``: the one step
+        in which a forward and a decode step differ.  RoPE (rows of ``seq_len`` positions, or ``pos``) and SwiGLU ride in their GEMMs' epilogues."""
+        layers, b = [], self._layer_bufs(mode, 0, B * S, B, S)
+        ops.embed_fwd(tok, self._view("emb"), b.h_in, self.vocab_size)
+        for l in range(self.num_layers):
+            layers.append(b)
+            ops.rmsnorm_fwd(b.h_in, self._view(f"L{l}.sa_norm"), b.xn1, b.rstd1, self.norm_eps)
+            ops.gemm_rope(b.xn1, self._view(f"L{l}.wqkv"), b.qkv, seq_len, self.num_heads + self.num_kv_heads, self.head_dim, self._rope, positions=pos)
+            attend(l, b)
+            self._gemm(GEMM_NT, b.att, self._view(f"L{l}.wo"), b.hmid, residual=b.h_in)
+            ops.rmsnorm_fwd(b.hmid, self._view(f"L{l}.mlp_norm"), b.xn2, b.rstd2, self.norm_eps)
+            ops.gemm_swiglu_fwd(b.xn2, self._view(f"L{l}.w13"), b.gu, b.act)
+            self._gemm(GEMM_NT, b.act, self._view(f"L{l}.w2"), b.h_out, residual=b.hmid)
+            b = self._layer_bufs(mode, l + 1, B * S, B, S, layers)
+        ops.rmsnorm_fwd(b.h_in, self.norm.scale, b.xn1, b.rstd1, self.norm_eps)
+        return layers, b
 
     # ---- backward: decoder stack -------------------------------------------------------------------------------------
-    def _backward_hidden(self, d_hn: Tensor, gen: int) -> None:
-        sv = self._saved
-        if sv is None or sv["gen"] != gen:
+    def _saved_for(self, gen: int) -> _Saved:  # the one stale-forward check: the decoder backward's, and the fused loss's before its head
+        if (sv := self._saved) is None or sv.gen != gen:
             raise RuntimeError("HipLlamaDecoder: backward called for a forward whose activations were overwritten; "
                                "run backward before the next training forward")
-        B, S, tok = sv["B"], sv["S"], sv["tok"]
-        pos, ds, de, plan = sv["pos"], sv["ds"], sv["de"], sv.get("plan")
+        return sv
+
+    def _backward_hidden(self, d_hn: Tensor, gen: int) -> None:
+        sv = self._saved_for(gen)
+        B, S, tok, pos, ds, de, plan = sv.B, sv.S, sv.tok, sv.pos, sv.ds, sv.de, sv.plan
         T, D, I = B * S, self.embed_dim, self.intermediate_dim
         H, KV, hd, dt, A = self.num_heads, self.num_kv_heads, self.head_dim, self.dtype, self._arena
-        L = self.num_layers
-        G = self._flat_grad
+        L, G = self.num_layers, self._flat_grad
         self._finish_pending_exchange()   # first: _window_accumulates() may zero slices of the buffer a deferred bucket is still reduced into
         acc = self._window_accumulates()  # False: first backward of the window, every gradient is written, not added
         gv = lambda name: self._view(name, None, G)  # noqa: E731
@@ -595,19 +615,20 @@ class HipLlamaDecoder(nn.Module):
             raise RuntimeError("wgrad_group was changed after construction: the data-parallel buckets were laid out for the old grouping")
         defer = (Gp > 1 and dt == torch.bfloat16 and self._mfma_shapes() and T % 128 == 0 and T >= 256
                  and ops.splitk_choice(D, H * hd, T) > 1 and ops.splitk_choice(self.qkv_dim, D, T) > 1)
-        xn1_all, att_all = A.get("xn1.all", (L, T, D), dt), A.get("att.all", (L, T, H * hd), dt)
         if defer:
             dhmid_all, dqkv_all = A.get("dh.b.all", (Gp, T, D), dt), A.get("dqkv.all", (Gp, T, self.qkv_dim), dt)
             lstride = (self._slices["L1.wqkv"][0] - self._slices["L0.wqkv"][0]) if L > 1 else 0
 
         def flush_attention_wgrads(l_lo: int) -> None:
             n = min(Gp, L - l_lo)
+            # att and xn1 of layers l_lo .. l_lo + n - 1: the saving forward keeps every layer's in ONE buffer, one after the other (_layer_bufs)
+            att_n, xn1_n = (x.as_strided((n, *x.shape), (x.numel(), *x.stride())) for x in (sv.layers[l_lo].att, sv.layers[l_lo].xn1))
             g_o = torch.as_strided(G, (n, D, H * hd), (lstride, H * hd, 1), self._slices[f"L{l_lo}.wo"][0])
             g_qkv = torch.as_strided(G, (n, self.qkv_dim, D), (lstride, D, 1), self._slices[f"L{l_lo}.wqkv"][0])
             if not self._slice_frozen(f"L{l_lo}.wo", n, lstride):      # (skipped only when the whole group's weights are frozen)
-                ops.gemm_batched(GEMM_TN, dhmid_all[:n], att_all[l_lo:l_lo + n], g_o, accumulate=acc)
+                ops.gemm_batched(GEMM_TN, dhmid_all[:n], att_n, g_o, accumulate=acc)
             if not self._slice_frozen(f"L{l_lo}.wqkv", n, lstride):
-                ops.gemm_batched(GEMM_TN, dqkv_all[:n], xn1_all[l_lo:l_lo + n], g_qkv, accumulate=acc)
+                ops.gemm_batched(GEMM_TN, dqkv_all[:n], xn1_n, g_qkv, accumulate=acc)
 
         def dgrad(dy: Tensor, name: str, dx: Tensor) -> None:
             """dx = dy @ W  (W = [out, in]) on the untransposed weights: NN form of the persistent GEMM.  In the step its A operand has just
@@ -620,40 +641,34 @@ class HipLlamaDecoder(nn.Module):
             ws_bytes = max(ws_bytes, plan.workspace_bytes)
         attn_ws = A.get("ws.attn", (ws_bytes,), torch.uint8) if ws_bytes else None
         dh = A.get("dh.a", (T, D), dt)
-        ops.rmsnorm_bwd(d_hn, A.get(f"h{L}", (T, D), dt), self.norm.scale, A.get("rstdf", (T,), torch.float32), None, dh,
-                        gv("norm"), ws, accumulate=acc)
+        ops.rmsnorm_bwd(d_hn, sv.h_last, self.norm.scale, sv.rstdf, None, dh, gv("norm"), ws, accumulate=acc)
         announce("norm")
         for l in reversed(range(L)):
-            xn1, xn2 = xn1_all[l], A.get(f"xn2.{l}", (T, D), dt)
-            qkv, att = A.get(f"qkv.{l}", (T, self.qkv_dim), dt), att_all[l]
-            hmid, gu, act = A.get(f"hmid.{l}", (T, D), dt), A.get(f"gu.{l}", (T, 2 * I), dt), A.get(f"act.{l}", (T, I), dt)
-            h_in = A.get(f"h{l}", (T, D), dt)
+            b = sv.layers[l]
             # MLP: h_out = hmid + act @ w2^T
-            wgrad(dh, act, f"L{l}.w2")
+            wgrad(dh, b.act, f"L{l}.w2")
             dgu = A.get("dgu", (T, 2 * I), dt)
             # d act = dh W2 never reaches memory: the SwiGLU backward rides in the GEMM epilogue
-            ops.gemm_swiglu_bwd(GEMM_NN, dh, self._view(f"L{l}.w2"), gu, dgu, A.get("dact", (T, I), dt))
+            ops.gemm_swiglu_bwd(GEMM_NN, dh, self._view(f"L{l}.w2"), b.gu, dgu, A.get("dact", (T, I), dt))
             dxn = A.get("dxn", (T, D), dt)
             dgrad(dgu, f"L{l}.w13", dxn)
-            wgrad(dgu, xn2, f"L{l}.w13")
+            wgrad(dgu, b.xn2, f"L{l}.w13")
             dhmid = dhmid_all[l % Gp] if defer else A.get("dh.b", (T, D), dt)
-            ops.rmsnorm_bwd(dxn, hmid, self._view(f"L{l}.mlp_norm"), A.get(f"rstd2.{l}", (T,), torch.float32), dh, dhmid,
-                            gv(f"L{l}.mlp_norm"), ws, accumulate=acc)
+            ops.rmsnorm_bwd(dxn, b.hmid, self._view(f"L{l}.mlp_norm"), b.rstd2, dh, dhmid, gv(f"L{l}.mlp_norm"), ws, accumulate=acc)
             # attention: hmid = h_in + att @ wo^T
             datt = A.get("datt", (T, H * hd), dt)
             dgrad(dhmid, f"L{l}.wo", datt)
             if not defer:
-                wgrad(dhmid, att, f"L{l}.wo")
+                wgrad(dhmid, b.att, f"L{l}.wo")
             dqkv = dqkv_all[l % Gp] if defer else A.get("dqkv", (T, self.qkv_dim), dt)
             delta = A.get("delta", (B * H * S,), torch.float32)
             # attention backward with the backward of the RoPE rotation fused into its epilogues: dqkv arrives in pre-RoPE space
-            ops.attn_bwd(qkv, att, datt, A.get(f"lse.{l}", (B * H * S,), torch.float32), dqkv, delta, B, S, H, KV, hd, ds, de,
+            ops.attn_bwd(b.qkv, b.att, datt, b.lse, dqkv, delta, B, S, H, KV, hd, ds, de,
                          rope_table=self._rope, positions=pos, workspace=attn_ws, plan=plan)
             dgrad(dqkv, f"L{l}.wqkv", dxn)
             if not defer:
-                wgrad(dqkv, xn1, f"L{l}.wqkv")
-            ops.rmsnorm_bwd(dxn, h_in, self._view(f"L{l}.sa_norm"), A.get(f"rstd1.{l}", (T,), torch.float32), dhmid, dh,
-                            gv(f"L{l}.sa_norm"), ws, accumulate=acc)
+                wgrad(dqkv, b.xn1, f"L{l}.wqkv")
+            ops.rmsnorm_bwd(dxn, b.h_in, self._view(f"L{l}.sa_norm"), b.rstd1, dhmid, dh, gv(f"L{l}.sa_norm"), ws, accumulate=acc)
             announce(f"L{l}.mlp")
             if defer and l % Gp == 0:
                 flush_attention_wgrads(l)
@@ -666,7 +681,7 @@ class HipLlamaDecoder(nn.Module):
             ops.embed_bwd(tok, dh, gv("emb"), self.vocab_size, ws_e)
         self._grads_dirty, self._grads_stale, self._emb_grad_written = True, False, False
         announce("emb")
-        self._saved = None
+        self._saved = None   # (with it go the records' references to arena storage: a buffer that grows next can be freed first, _Arena.get)
         self.attach_grads()
 
     # ---- generation: K/V cache, prefill, decode step (ssi/generate.py drives them) --------------------------------------------
@@ -700,12 +715,12 @@ class HipLlamaDecoder(nn.Module):
     @torch.no_grad()
     def prefill(self, cache: "KVCache", prompts, max_new_tokens: int = 0) -> Tensor:
         """Prompt ``i`` (a 1-D integer sequence) fills slot ``i`` of ``cache``: the prompts are packed into rows on the host
-        (``ssi.score.pack_for_scoring``, ``input_pos`` restarting with every prompt as in ``scoring_batches``), the packed forward the dev
+        (``ssi.score.prefill_batches``: first-fit decreasing, ``input_pos`` restarting with every prompt), the packed forward the dev
         loss and ``ssi.score`` use runs block-causal over them with every layer's K / V scattered into the cache, and the final norm's
         rows of the prompts' LAST tokens alone go through the tied head.  Returns ``[n_prompts, vocab_pad]`` logits (fresh tensor) and
         sets the cache's lengths; slots beyond the prompts are emptied.  ``max_new_tokens``: what ``decode_step`` will add, checked here
         against the cap, the RoPE table and ``max_seq_len`` (``ValueError`` before any launch)."""
-        from .score import pack_for_scoring
+        from .score import prefill_batches
         seqs = [torch.as_tensor(p, dtype=torch.int64).reshape(-1) for p in prompts]
         lens = [int(s.numel()) for s in seqs]
         n, cap = len(seqs), cache.cap
@@ -715,36 +730,17 @@ class HipLlamaDecoder(nn.Module):
             raise ValueError("prefill: no prompts")
         # rows of PREFILL_ROW_LEN positions; one shorter row where all the prompts together need less, a longer one for a longer prompt
         row_len = min(max(min(self.PREFILL_ROW_LEN, sum(lens)), max(lens)), self._rope.shape[0])
-        rows = pack_for_scoring(lens, row_len)
-        mfma = self._mfma_shapes()
-        n_pad = _align(n, VOCAB_ALIGN) if mfma else n
         dev = self.device
-        hlast = torch.zeros((n_pad, self.embed_dim), dtype=self.dtype, device=dev)   # (pad rows: zeros)
-        for b0 in range(0, len(rows), self.PREFILL_ROWS_PER_BATCH):
-            chunk = rows[b0:b0 + self.PREFILL_ROWS_PER_BATCH]
-            tokens = torch.zeros(len(chunk), row_len, dtype=torch.int64)
-            input_pos = torch.empty(len(chunk), row_len, dtype=torch.int64)
-            dest = torch.full((len(chunk), row_len), -1, dtype=torch.int64)
-            last_at, last_of = [], []
-            for r, members in enumerate(chunk):
-                at = 0
-                for i in members:
-                    k = lens[i]
-                    tokens[r, at:at + k] = seqs[i]
-                    input_pos[r, at:at + k] = torch.arange(k)
-                    dest[r, at:at + k] = i * cap + torch.arange(k)
-                    last_at.append((r, at + k - 1))
-                    last_of.append(i)
-                    at += k
-                input_pos[r, at:] = torch.arange(row_len - at)      # the tail: a document of its own, stored nowhere
+        hlast = torch.zeros((self._padded_rows(n), self.embed_dim), dtype=self.dtype, device=dev)   # (pad rows: zeros)
+        for tokens, input_pos, dest, last_at, last_of in prefill_batches(seqs, cap, row_len, self.PREFILL_ROWS_PER_BATCH):
             tokens, input_pos, dest = tokens.to(dev), input_pos.to(dev), dest.to(dev)
             tokens, input_pos, _, _ = self._right_pad(tokens, input_pos)
-            S = tokens.shape[1]
-            if S > row_len:
-                dest = torch.cat([dest, torch.full((len(chunk), S - row_len), -1, dtype=torch.int64, device=dev)], dim=1)
+            B, S = tokens.shape
+            if S > row_len:   # the padding is stored nowhere either, and a last token keeps its column in the longer rows
+                dest = torch.cat([dest, torch.full((B, S - row_len), -1, dtype=torch.int64, device=dev)], dim=1)
+                last_at = last_at + last_at // row_len * (S - row_len)
             hn = self._forward_hidden(tokens, save=False, input_pos=input_pos, kv_sink=(cache, dest.reshape(-1).contiguous()))
-            src = torch.tensor([r * S + c for r, c in last_at], dtype=torch.int64).to(dev)
-            hlast.index_copy_(0, torch.tensor(last_of, dtype=torch.int64).to(dev), hn.index_select(0, src))
+            hlast.index_copy_(0, last_of.to(dev), hn.index_select(0, last_at.to(dev)))
         cache.lengths.zero_()
         cache.lengths[:n] = torch.tensor(lens, dtype=torch.int32).to(dev)
         return self._head_logits(hlast)[:n]
@@ -770,9 +766,8 @@ class HipLlamaDecoder(nn.Module):
         if not tokens.is_cuda or not slots.is_cuda:
             raise _lib.HipLibraryError("decode_step: tokens and slots must live on the GPU (no CPU fallback)")
         n = tokens.numel()
-        R = _align(max(n, 1), VOCAB_ALIGN) if self._mfma_shapes() else n
-        D, I, L = self.embed_dim, self.intermediate_dim, self.num_layers
-        H, KV, hd, dt, A, dev = self.num_heads, self.num_kv_heads, self.head_dim, self.dtype, self._arena, self.device
+        R = self._padded_rows(n)
+        H, KV, hd, dev = self.num_heads, self.num_kv_heads, self.head_dim, self.device
         tok = torch.zeros(R, dtype=torch.int64, device=dev)          # pad rows: token 0, slot -1, position 0
         slot = torch.full((R,), -1, dtype=torch.int32, device=dev)
         tok[:n] = tokens
@@ -785,24 +780,12 @@ class HipLlamaDecoder(nn.Module):
         dest = torch.where(write, slot.long() * cache.cap + length.long(), torch.full_like(slot, -1, dtype=torch.int64))
         pos = length.clamp(max=self._rope.shape[0] - 1).contiguous()
         kv_len = torch.where(live, length + 1, torch.zeros_like(length)).contiguous()
-        h = A.get("h0.g", (R, D), dt)
-        ops.embed_fwd(tok, self._view("emb"), h, self.vocab_size)
-        xn, rstd = A.get("xn.g", (R, D), dt), A.get("rstd.g", (R,), torch.float32)
-        qkv, att = A.get("qkv.g", (R, self.qkv_dim), dt), A.get("att.g", (R, H * hd), dt)
-        hmid, gu, act = A.get("hmid.g", (R, D), dt), A.get("gu.g", (R, 2 * I), dt), A.get("act.g", (R, I), dt)
-        for l in range(L):
-            ops.rmsnorm_fwd(h, self._view(f"L{l}.sa_norm"), xn, rstd, self.norm_eps)
-            ops.gemm_rope(xn, self._view(f"L{l}.wqkv"), qkv, R, H + KV, hd, self._rope, positions=pos)
-            ops.kv_store(qkv, dest, cache.k[l], cache.v[l], H, KV, hd, n_bad=cache.errors)
-            ops.attn_decode(qkv, cache.k[l], cache.v[l], slot, kv_len, att, None, H, KV, hd, n_bad=cache.errors)
-            self._gemm(GEMM_NT, att, self._view(f"L{l}.wo"), hmid, residual=h)
-            ops.rmsnorm_fwd(hmid, self._view(f"L{l}.mlp_norm"), xn, rstd, self.norm_eps)
-            ops.gemm_swiglu_fwd(xn, self._view(f"L{l}.w13"), gu, act)
-            hnext = A.get(f"h{1 + (l & 1)}.g", (R, D), dt)
-            self._gemm(GEMM_NT, act, self._view(f"L{l}.w2"), hnext, residual=hmid)
-            h = hnext
-        ops.rmsnorm_fwd(h, self.norm.scale, xn, rstd, self.norm_eps)
-        logits = self._head_logits(xn)
+
+        def attend(l: int, b: _LayerBufs) -> None:
+            ops.kv_store(b.qkv, dest, cache.k[l], cache.v[l], H, KV, hd, n_bad=cache.errors)
+            ops.attn_decode(b.qkv, cache.k[l], cache.v[l], slot, kv_len, b.att, None, H, KV, hd, n_bad=cache.errors)
+
+        logits = self._head_logits(self._run_stack("g", tok, R, 1, R, pos, attend)[1].xn1)   # R rows of one position each; RoPE by ``pos``
         cache.lengths.index_add_(0, slot.clamp(min=0).long(), write.to(torch.int32))
         return logits[:n]
 
@@ -1128,9 +1111,7 @@ class _FusedLossFn(torch.autograd.Function):
     def backward(ctx, grad_out: Tensor):
         hn, stats, dlogits = ctx.saved_tensors
         m = ctx.model
-        if m._saved is None or m._saved["gen"] != ctx.gen:  # checked BEFORE the head backward touches the gradient buffer
-            raise RuntimeError("HipLlamaDecoder: backward called for a forward whose activations were overwritten; "
-                               "run backward before the next training forward")
+        m._saved_for(ctx.gen)  # a stale forward raises BEFORE the head backward touches the gradient buffer
         # d loss / d logits = (softmax - onehot) / n_valid ; the 1/n_valid and the upstream scalar ride in alpha_dev (with a z-loss the buffer
         # holds (f softmax - onehot), with label smoothing (f softmax - (1 - e) onehot - e / vocab): every part of the objective shares the divisor)
         alpha = (grad_out.to(torch.float32).reshape(1) / stats[2:3]).contiguous()
@@ -1157,7 +1138,6 @@ def get_device(device: Any = None) -> torch.device:
         device = "cuda" if torch.cuda.is_available() else "cpu"
     dev = torch.device(device)
     if dev.type == "cuda" and dev.index is None:
-        import os
         dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         torch.cuda.set_device(dev)
     return dev

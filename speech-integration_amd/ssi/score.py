@@ -27,7 +27,7 @@ from .loss import CEWithChunkedOutputLoss, compute_loss
 
 LOGGER = logging.getLogger(__name__)
 
-__all__ = ["SequenceScores", "pack_for_scoring", "scoring_batches", "score_sequences", "pair_accuracy", "score_file"]
+__all__ = ["SequenceScores", "pack_for_scoring", "scoring_batches", "prefill_batches", "score_sequences", "pair_accuracy", "score_file"]
 
 
 @dataclass
@@ -70,6 +70,24 @@ def pack_for_scoring(lengths: Sequence[int], row_len: int) -> list[list[int]]:
     return rows
 
 
+def _place_rows(sequences: list[Tensor], chunk: list[list[int]], row_len: int, pad_id: int) -> tuple[Tensor, Tensor, list[tuple[int, int, int, int]]]:
+    """The placement loop of every packed host batch: ``chunk``'s rows (``pack_for_scoring``'s) as int64 ``tokens`` (``pad_id`` on the tail) and
+    ``input_pos`` (restarting at 0 with every sequence and on the tail), and ``(row, start, length, index)`` of every sequence as they lie."""
+    tokens = torch.full((len(chunk), row_len), pad_id, dtype=torch.int64)
+    input_pos = torch.empty(len(chunk), row_len, dtype=torch.int64)
+    placed = []
+    for r, members in enumerate(chunk):
+        at = 0
+        for i in members:
+            n = sequences[i].numel()
+            tokens[r, at:at + n] = sequences[i]
+            input_pos[r, at:at + n] = torch.arange(n)
+            placed.append((r, at, n, i))
+            at += n
+        input_pos[r, at:] = torch.arange(row_len - at)     # the tail: a document of its own
+    return tokens, input_pos, placed
+
+
 def scoring_batches(sequences: list[Tensor], score_from: list[int], rows: list[list[int]], row_len: int, rows_per_batch: int, pad_id: int,
                     ignore_index: int = CROSS_ENTROPY_IGNORE_IDX, dense_mask: bool = False, token_logprobs: bool = False):
     """The packed host batches of ``score_sequences``, one at a time (``sequences``: int64 tensors; ``rows``: ``pack_for_scoring``'s).
@@ -79,37 +97,39 @@ def scoring_batches(sequences: list[Tensor], score_from: list[int], rows: list[l
     ``seq_spans``: per sequence ``(row in the batch, start, end)`` in SHIFTED-label positions; ``seq_index``: which input sequence each is."""
     for b0 in range(0, len(rows), rows_per_batch):
         chunk = rows[b0:b0 + rows_per_batch]
-        tokens = torch.full((len(chunk), row_len), pad_id, dtype=torch.int64)
+        tokens, input_pos, placed = _place_rows(sequences, chunk, row_len, pad_id)
         labels = torch.full((len(chunk), row_len), ignore_index, dtype=torch.int64)
-        input_pos = torch.empty(len(chunk), row_len, dtype=torch.int64)
-        spans, index, seq_lens, tok_pos = [], [], [], []
-        for r, members in enumerate(chunk):
-            at, lens = 0, []
-            for i in members:
-                n, sf = sequences[i].numel(), score_from[i]
-                tokens[r, at:at + n] = sequences[i]
-                labels[r, at + sf:at + n] = sequences[i][sf:]
-                input_pos[r, at:at + n] = torch.arange(n)
-                lo, hi = at + min(sf, n) - 1, at + n - 1      # the label of position p sits at p - 1 after the shift
-                spans.append((r, max(lo, 0), max(hi, lo, 0)))
-                index.append(i)
-                if token_logprobs:
-                    tok_pos.append(torch.stack([torch.full((max(hi - lo, 0),), r, dtype=torch.int64), torch.arange(lo, max(hi, lo))], dim=1))
-                if n:
-                    lens.append(n)
-                at += n
-            input_pos[r, at:] = torch.arange(row_len - at)     # the tail: a document of its own
-            if at < row_len:
-                lens.append(row_len - at)
-            seq_lens.append(torch.tensor(lens, dtype=torch.int64))
+        spans, tok_pos = [], []
+        for r, at, n, i in placed:
+            sf = score_from[i]
+            labels[r, at + sf:at + n] = sequences[i][sf:]
+            lo, hi = at + min(sf, n) - 1, at + n - 1      # the label of position p sits at p - 1 after the shift
+            spans.append((r, max(lo, 0), max(hi, lo, 0)))
+            if token_logprobs:
+                tok_pos.append(torch.stack([torch.full((max(hi - lo, 0),), r, dtype=torch.int64), torch.arange(lo, max(hi, lo))], dim=1))
         batch: dict[str, Any] = {"tokens": tokens, "labels": labels, "input_pos": input_pos,
-                                 "seq_spans": torch.tensor(spans, dtype=torch.int64).reshape(-1, 3), "seq_index": index}
+                                 "seq_spans": torch.tensor(spans, dtype=torch.int64).reshape(-1, 3), "seq_index": [p[3] for p in placed]}
         if token_logprobs:
             batch["tok_pos"] = torch.cat(tok_pos) if tok_pos else torch.zeros(0, 2, dtype=torch.int64)
         if dense_mask:                                         # a model that takes the dense block-causal mask instead of input_pos alone
             from .data.packed import packed_block_causal_mask
-            batch["mask"] = packed_block_causal_mask(seq_lens)
+            docs = [[n for r, _, n, _ in placed if r == k and n] for k in range(len(chunk))]   # per row: its documents' lengths, then the tail's
+            batch["mask"] = packed_block_causal_mask([torch.tensor(d + [row_len - sum(d)] * (sum(d) < row_len), dtype=torch.int64) for d in docs])
         yield batch
+
+
+def prefill_batches(sequences: list[Tensor], cap: int, row_len: int, rows_per_batch: int):
+    """The packed host batches of ``HipLlamaDecoder.prefill``, one at a time (prompt ``i`` fills slot ``i`` of a K/V cache of ``cap`` positions per
+    slot): ``tokens`` and ``input_pos`` as ``scoring_batches`` makes them with ``pad_id=0``; ``dest`` (int64, same shape): where a position's K / V
+    go, ``slot * cap + position``, -1 on the tail; and per prompt of the batch the flat position of its LAST token and its index (int64 tensors)."""
+    rows = pack_for_scoring([s.numel() for s in sequences], row_len)
+    for b0 in range(0, len(rows), rows_per_batch):
+        tokens, input_pos, placed = _place_rows(sequences, rows[b0:b0 + rows_per_batch], row_len, 0)
+        dest = torch.full_like(tokens, -1)
+        for r, at, n, i in placed:
+            dest[r, at:at + n] = i * cap + torch.arange(n)
+        last = torch.tensor([r * row_len + at + n - 1 for r, at, n, _ in placed], dtype=torch.int64)
+        yield tokens, input_pos, dest, last, torch.tensor([p[3] for p in placed], dtype=torch.int64)
 
 
 def score_sequences(model, sequences: Sequence[Any], *, score_from: Sequence[int] | None = None, pad_id: int, device: torch.device | str,
