@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 19 /* 19: + ssi_decode_select (constrained greedy decoding: the allowed argmax of a row, its log-probability and its rank in one pass; opt-in)
+#define SSI_ABI_VERSION 20 /* 20: + ssi_attn_decode_beam, ssi_topk_logprob (beam search: decode attention through an ancestry table, the k best allowed columns of a row; opt-in)
+                           * 19: + ssi_decode_select (constrained greedy decoding: the allowed argmax of a row, its log-probability and its rank in one pass; opt-in)
                            * 18: + ssi_kv_store, ssi_attn_decode (greedy generation: a K/V cache and single-query attention over it; nothing else calls them)
                            * 17: + ssi_ema_update (fp32 exponential moving average of the flat parameter buffer, one pass chained to AdamW; opt-in)
                            * 16: + ssi_adamw_step_seg (AdamW over segments of the flat buffers with their own lr, weight decay and frozen flag; opt-in)
@@ -235,6 +236,40 @@ int ssi_kv_store(const void* qkv, int64_t ld, const int64_t* dest, int64_t rows,
 int ssi_attn_decode(const void* qkv, int64_t ld, const void* k_cache, const void* v_cache, int64_t n_slots, int64_t cap,
                     const int32_t* slot, const int32_t* kv_len, void* out, float* lse, int64_t rows, int n_heads, int n_kv,
                     int head_dim, int32_t* n_bad, int dtype, void* stream);
+
+/* ssi_attn_decode over the concatenation of two key ranges (ABI v20, beam search): row r attends to
+ *   keys j in [0, prompt_len[r])  of the PROMPT cache [n_pslots, cap_p, n_kv * head_dim], slot prompt_slot[r], then
+ *   keys i in [0, gen_len[r])     of the BEAM cache   [n_bslots, cap_b, n_kv * head_dim], slot anc[r * ld_anc + i], position i
+ * (anc: int32 [rows, ld_anc] on the device, the ancestry of the row's hypothesis: which beam slot holds its generated position i).  The beams
+ * of a prompt share the prompt's K / V and every generated position before they diverged; nothing is copied after a reorder.
+ * prompt_len is clamped to [0, cap_p], gen_len to [0, min(cap_b, ld_anc)].  prompt_slot[r] < 0, or no key at all: a zero row and lse -inf.
+ * An index outside its cache — prompt_slot[r] >= n_pslots, anc[r, i] outside [0, n_bslots) — is checked BEFORE any address is formed from it:
+ * the keys it names are skipped, and the row is counted ONCE into *n_bad (may be NULL); a row whose keys were all skipped is zeros, lse -inf.
+ * Dtypes, geometries, alignment, arithmetic, lanes, chunks, wave assignment and the fixed merge order are ssi_attn_decode's, walked over the
+ * concatenated key index 0 .. prompt_len + gen_len: the two kernels share the row body, and out and lse are BIT-EQUAL to ssi_attn_decode on a
+ * cache in which the row's keys lie one behind the other.  One workgroup per (row, kv head): each beam of a prompt reads the prompt's K / V
+ * itself.  Same 8 forms (dtype x G = 1, 2, 4, 8).  ssi_kv_store fills the beam cache unchanged (dest = r * cap_b + t). */
+int ssi_attn_decode_beam(const void* qkv, int64_t ld, const void* pk_cache, const void* pv_cache, int64_t n_pslots, int64_t cap_p,
+                         const void* bk_cache, const void* bv_cache, int64_t n_bslots, int64_t cap_b, const int32_t* prompt_slot,
+                         const int32_t* prompt_len, const int32_t* gen_len, const int32_t* anc, int64_t ld_anc, void* out, float* lse,
+                         int64_t rows, int n_heads, int n_kv, int head_dim, int32_t* n_bad, int dtype, void* stream);
+
+/* The k best allowed continuations of every row of logits [rows, ld] with their log-probabilities (ABI v20, beam search).  Logits read only.
+ * mask: ssi_decode_select's bit mask (mask_words = ceil(vocab / 32) int32 words, bit c % 32 of word c / 32), or NULL with mask_words 0 = every
+ * real column.
+ *   idx[r, j], j < k : the columns of the k largest STORED values among the allowed columns below vocab, by value descending, the lower column
+ *                      first among equal values (-0 equals +0); a NaN ranks below every number, -inf included.  Exact: values are compared as
+ *                      stored, nothing is rounded.  Fewer than k allowed columns: the rest are -1.
+ *   lse[r]           : log sum_{c < vocab} exp x[c] over ALL real columns, allowed or not (NULL ok) — ssi_decode_select's normaliser, term for
+ *                      term: exp2(fma(x, log2 e, nm)), nm = fl(-max log2 e), lse = fl(max + logf(sum)).
+ *   lp[r, j]         : fl(x[idx] - lse); -inf where idx is -1.  On a row holding NaN or an infinity lse and lp are unspecified; idx is not.
+ * One workgroup of 256 threads per row, two walks (max and per-thread sorted lists of K = 1, 2, 4 or 8 candidates in registers; exp-sum), then k
+ * rounds that pick the best list head by ssi_decode_select's fixed tree.  No workspace, no atomics; a row's result depends on that row and the
+ * mask only.  idx[r, 0] is ssi_decode_select's token on the same inputs.
+ * SSI_ERR_ARG before any launch: k outside 1..8, a NULL mask with mask_words != 0 or a mask with another length, null logits / idx / lp,
+ * vocab < 1, ld < vocab, vocab or rows >= 2^31.  rows == 0 launches nothing. */
+int ssi_topk_logprob(const void* logits, int64_t ld, int64_t rows, int64_t vocab, int k, const uint32_t* mask, int64_t mask_words,
+                     int32_t* idx, float* lp, float* lse, int dtype, void* stream);
 
 /* The token of a decode step under a constraint (ABI v19; vLLM's allowed_token_ids and min_tokens, which the reference's generation can set):
  * the greedy choice among the ALLOWED columns of every row of logits [rows, ld], with its log-probability and its rank under the row's

@@ -48,30 +48,30 @@ __device__ __forceinline__ float dec_exp2(float x) { return __builtin_amdgcn_exp
 // weight of a partial state with maximum m in a merged state with maximum mn >= m (an empty state has m = -inf, also when mn is -inf)
 __device__ __forceinline__ float dec_weight(float m, float mn) { return m == -INFINITY ? 0.f : dec_exp2(m - mn); }
 
-template <typename T, int G>
-__global__ __launch_bounds__(256) void kv_decode_kernel(const T* __restrict__ qkv, int64_t ld, const T* __restrict__ kc, const T* __restrict__ vc,
-                                                        int64_t n_slots, int cap, const int32_t* __restrict__ slot,
-                                                        const int32_t* __restrict__ kv_len, T* __restrict__ out, float* __restrict__ lse,
-                                                        int n_heads, int n_kv, int hd, int g, int lpk_log2, float qscale,
-                                                        int32_t* __restrict__ n_bad) {
+// Where a lane stands in its wave: the key slot it serves and the 16 bytes (columns col .. col + VEC - 1) of that key's lines it holds.
+struct DecLane {
+    int lpk, kpw, sub, kslot, col;
+};
+template <typename T>
+__device__ __forceinline__ DecLane dec_lane(int lpk_log2, int hd) {
+    const int lane = threadIdx.x & 63, lpk = 1 << lpk_log2;
+    const int sub = lane & (lpk - 1);
+    return {lpk, 64 >> lpk_log2, sub, lane >> lpk_log2, sub * Vec16<T>::N};
+}
+
+// One (row, kv head) of single-query attention over the keys 0 .. n - 1, the body both decode kernels share: the key walk, the per-key update
+// and the two merges.  ``keys.exists(j)`` says whether key j is there — one that is not is skipped and leaves the state as it was —
+// and ``keys.lines(j, kp, vp)`` names the lane's 16 bytes of its K and V lines.  CAN_SKIP: a row all of whose keys were skipped is zeros with lse -inf (without
+// it the caller promises n > 0 keys that all exist).  ``qrow``: the row's first query head of this kv head; ``lse`` (may be null) takes the
+// heads' values from ``lse[lse_at]`` on.
+template <typename T, int G, bool CAN_SKIP, typename Keys>
+__device__ __forceinline__ void dec_row(const T* __restrict__ qrow, int n, T* __restrict__ orow, float* __restrict__ lse, int64_t lse_at, int hd,
+                                        int g, const DecLane& at, float qscale, const Keys& keys) {
     constexpr int VEC = Vec16<T>::N;
     __shared__ float s_m[DEC_WAVES][G], s_l[DEC_WAVES][G];
     __shared__ float s_acc[DEC_WAVES][G][DEC_MAX_HD];
-    const int64_t r = blockIdx.x;
-    const int kvh = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int h0 = kvh * g;
-    const int sl = slot[r];
-    int n = kv_len[r];
-    n = n < cap ? n : cap;
-    T* orow = out + (r * n_heads + h0) * hd;
-    if (sl < 0 || sl >= n_slots || n <= 0) {              // (uniform over the workgroup)
-        for (int i = tid; i < g * hd; i += 256) orow[i] = from_f32<T>(0.f);
-        if (lse && tid < g) lse[r * n_heads + h0 + tid] = -INFINITY;
-        if (sl >= n_slots && kvh == 0 && tid == 0 && n_bad) atomicAdd(n_bad, 1);
-        return;
-    }
-    const int lpk = 1 << lpk_log2, kpw = 64 >> lpk_log2;
-    const int sub = lane & (lpk - 1), kslot = lane >> lpk_log2, col = sub * VEC;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int lpk = at.lpk, kpw = at.kpw, sub = at.sub, kslot = at.kslot, col = at.col;
     const bool active = col < hd;
 
     float q[G][VEC], acc[G][VEC], m[G], l[G];
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void kv_decode_kernel(const T* __restrict__ qk
     for (int h = 0; h < G; ++h) {
         const int hh = h < g ? h : g - 1;                 // heads past g repeat the last one and are not stored
         Vec16<T> x = {};
-        if (active) x = load16<T>(qkv + r * ld + (int64_t)(h0 + hh) * hd + col);
+        if (active) x = load16<T>(qrow + (int64_t)hh * hd + col);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
             q[h][v] = active ? x.get(v) * qscale : 0.f;
@@ -89,9 +89,6 @@ __global__ __launch_bounds__(256) void kv_decode_kernel(const T* __restrict__ qk
         l[h] = 0.f;
     }
 
-    const int64_t kv_cols = (int64_t)n_kv * hd;
-    const T* kbase = kc + ((int64_t)sl * cap * n_kv + kvh) * hd + col;
-    const T* vbase = vc + ((int64_t)sl * cap * n_kv + kvh) * hd + col;
     const int chunk = kpw * DEC_U;
     for (int base = wave * chunk; base < n; base += DEC_WAVES * chunk) {
         Vec16<T> kx[DEC_U] = {}, vx[DEC_U] = {};
@@ -100,9 +97,12 @@ __global__ __launch_bounds__(256) void kv_decode_kernel(const T* __restrict__ qk
         for (int u = 0; u < DEC_U; ++u) {                 // every load of the chunk is issued before the first use
             const int j = base + u * kpw + kslot;
             have[u] = j < n;
+            if (CAN_SKIP) have[u] = have[u] && keys.exists(j);
             if (have[u] && active) {
-                kx[u] = load16_nt<T>(kbase + (int64_t)j * kv_cols);
-                vx[u] = load16_nt<T>(vbase + (int64_t)j * kv_cols);
+                const T *kp, *vp;
+                keys.lines(j, kp, vp);
+                kx[u] = load16_nt<T>(kp);
+                vx[u] = load16_nt<T>(vp);
             }
         }
 #pragma unroll
@@ -184,8 +184,119 @@ __global__ __launch_bounds__(256) void kv_decode_kernel(const T* __restrict__ qk
             L = __builtin_fmaf(s_l[w][h], e, L);
             O = __builtin_fmaf(s_acc[w][h][d], e, O);
         }
-        orow[i] = from_f32<T>(O / L);
-        if (lse && d == 0) lse[r * n_heads + h0 + h] = (mn + log2f(L)) * 0.69314718055994531f;
+        const bool none = CAN_SKIP && !(L > 0.f);         // every key was skipped
+        orow[i] = from_f32<T>(none ? 0.f : O / L);
+        if (lse && d == 0) lse[lse_at + h] = none ? -INFINITY : (mn + log2f(L)) * 0.69314718055994531f;
+    }
+}
+
+// the keys of one cache slot, one behind the other
+template <typename T>
+struct SlotKeys {
+    const T *kbase, *vbase;                               // key 0, the lane's columns
+    int64_t kv_cols;
+    __device__ __forceinline__ bool exists(int) const { return true; }
+    __device__ __forceinline__ void lines(int j, const T*& kp, const T*& vp) const {
+        kp = kbase + (int64_t)j * kv_cols;
+        vp = vbase + (int64_t)j * kv_cols;
+    }
+};
+
+template <typename T, int G>
+__global__ __launch_bounds__(256) void kv_decode_kernel(const T* __restrict__ qkv, int64_t ld, const T* __restrict__ kc, const T* __restrict__ vc,
+                                                        int64_t n_slots, int cap, const int32_t* __restrict__ slot,
+                                                        const int32_t* __restrict__ kv_len, T* __restrict__ out, float* __restrict__ lse,
+                                                        int n_heads, int n_kv, int hd, int g, int lpk_log2, float qscale,
+                                                        int32_t* __restrict__ n_bad) {
+    const int64_t r = blockIdx.x;
+    const int kvh = blockIdx.y, tid = threadIdx.x;
+    const int h0 = kvh * g;
+    const int sl = slot[r];
+    int n = kv_len[r];
+    n = n < cap ? n : cap;
+    T* orow = out + (r * n_heads + h0) * hd;
+    if (sl < 0 || sl >= n_slots || n <= 0) {              // (uniform over the workgroup)
+        for (int i = tid; i < g * hd; i += 256) orow[i] = from_f32<T>(0.f);
+        if (lse && tid < g) lse[r * n_heads + h0 + tid] = -INFINITY;
+        if (sl >= n_slots && kvh == 0 && tid == 0 && n_bad) atomicAdd(n_bad, 1);
+        return;
+    }
+    const DecLane at = dec_lane<T>(lpk_log2, hd);
+    const int64_t kv_cols = (int64_t)n_kv * hd;
+    const T* kbase = kc + ((int64_t)sl * cap * n_kv + kvh) * hd + at.col;
+    const T* vbase = vc + ((int64_t)sl * cap * n_kv + kvh) * hd + at.col;
+    dec_row<T, G, false>(qkv + r * ld + (int64_t)h0 * hd, n, orow, lse, r * n_heads + h0, hd, g, at, qscale, SlotKeys<T>{kbase, vbase, kv_cols});
+}
+
+// =====================================================================================================================
+// ssi_attn_decode_beam (ABI v20): the same row over the concatenation of two key ranges — the np keys of a PROMPT cache slot, then ng keys of a
+// BEAM cache read through an ancestry table: generated position i of row r lies in beam slot anc[r, i], at position i.  Key j of the walk
+// is prompt key j for j < np and generated key j - np otherwise, so chunks, waves and merges are those of kv_decode_kernel on a cache that
+// holds the row's keys one behind the other, and so are the bits.  An index outside its cache is never turned into an address: the key is
+// skipped, and the row is counted once.
+// =====================================================================================================================
+// prompt keys 0 .. np - 1 of one prompt cache slot, then generated keys: position i of the beam cache slot the ancestry names
+template <typename T>
+struct BeamKeys {
+    const T *pk, *pv;                                     // prompt key 0, the lane's columns (never used when !p_ok)
+    const T *bk, *bv;                                     // the beam cache
+    const int32_t* arow;                                  // the row's ancestry
+    int64_t kv_cols, head_at;                             // elements per cached position; the lane's columns within one
+    int np, cap_b, n_bslots;
+    bool p_ok;
+    __device__ __forceinline__ bool exists(int j) const {
+        if (j < np) return p_ok;
+        const int a = arow[j - np];
+        return a >= 0 && a < n_bslots;                    // checked before any address is formed from it
+    }
+    __device__ __forceinline__ void lines(int j, const T*& kp, const T*& vp) const {   // (only for a key that exists)
+        if (j < np) {
+            kp = pk + (int64_t)j * kv_cols;
+            vp = pv + (int64_t)j * kv_cols;
+        } else {
+            const int i = j - np;
+            const int64_t off = ((int64_t)arow[i] * cap_b + i) * kv_cols + head_at;
+            kp = bk + off;
+            vp = bv + off;
+        }
+    }
+};
+
+template <typename T, int G>
+__global__ __launch_bounds__(256) void beam_decode_kernel(const T* __restrict__ qkv, int64_t ld, const T* __restrict__ pk, const T* __restrict__ pv,
+                                                          int64_t n_pslots, int cap_p, const T* __restrict__ bk, const T* __restrict__ bv,
+                                                          int64_t n_bslots, int cap_b, const int32_t* __restrict__ prompt_slot,
+                                                          const int32_t* __restrict__ prompt_len, const int32_t* __restrict__ gen_len,
+                                                          const int32_t* __restrict__ anc, int64_t ld_anc, T* __restrict__ out,
+                                                          float* __restrict__ lse, int n_heads, int n_kv, int hd, int g, int lpk_log2, float qscale,
+                                                          int32_t* __restrict__ n_bad) {
+    const int64_t r = blockIdx.x;
+    const int kvh = blockIdx.y, tid = threadIdx.x;
+    const int h0 = kvh * g;
+    const int sl = prompt_slot[r];
+    int np = prompt_len[r], ng = gen_len[r];
+    np = np < cap_p ? np : cap_p;
+    np = np > 0 ? np : 0;
+    ng = ng < cap_b ? ng : cap_b;
+    ng = (int64_t)ng < ld_anc ? ng : (int)ld_anc;
+    ng = ng > 0 ? ng : 0;
+    T* orow = out + (r * n_heads + h0) * hd;
+    if (sl < 0 || np + ng <= 0) {                         // (uniform over the workgroup)
+        for (int i = tid; i < g * hd; i += 256) orow[i] = from_f32<T>(0.f);
+        if (lse && tid < g) lse[r * n_heads + h0 + tid] = -INFINITY;
+        return;
+    }
+    const bool p_ok = sl < n_pslots;
+    const int64_t kv_cols = (int64_t)n_kv * hd;
+    const DecLane at = dec_lane<T>(lpk_log2, hd);
+    const int64_t pbase = ((int64_t)(p_ok ? sl : 0) * cap_p * n_kv + kvh) * hd + at.col;
+    const BeamKeys<T> keys{pk + pbase, pv + pbase, bk, bv, anc + r * ld_anc, kv_cols, (int64_t)kvh * hd + at.col, np, cap_b, (int)n_bslots, p_ok};
+    dec_row<T, G, true>(qkv + r * ld + (int64_t)h0 * hd, np + ng, orow, lse, r * n_heads + h0, hd, g, at, qscale, keys);
+    if (kvh == 0 && n_bad) {                              // once per row (every kv head meets the same indices): the ancestry alone once more
+        bool bad = !p_ok && np > 0;
+        for (int i = tid; i < ng; i += 256) bad |= !keys.exists(np + i);
+        const int any = __syncthreads_or(bad ? 1 : 0);
+        if (tid == 0 && any) atomicAdd(n_bad, 1);
     }
 }
 
@@ -199,6 +310,20 @@ void launch_decode(const void* qkv, int64_t ld, const void* kc, const void* vc, 
     hipLaunchKernelGGL((kv_decode_kernel<T, G>), dim3((unsigned)rows, (unsigned)n_kv), dim3(256), 0, (hipStream_t)stream, (const T*)qkv, ld,
                        (const T*)kc, (const T*)vc, n_slots, (int)cap, slot, kv_len, (T*)out, lse, n_heads, n_kv, hd, n_heads / n_kv, lpk_log2,
                        qscale, n_bad);
+}
+
+template <typename T, int G>
+void launch_decode_beam(const void* qkv, int64_t ld, const void* pk, const void* pv, int64_t n_pslots, int64_t cap_p, const void* bk, const void* bv,
+                        int64_t n_bslots, int64_t cap_b, const int32_t* prompt_slot, const int32_t* prompt_len, const int32_t* gen_len,
+                        const int32_t* anc, int64_t ld_anc, void* out, float* lse, int64_t rows, int n_heads, int n_kv, int hd, int32_t* n_bad,
+                        void* stream) {
+    const int lanes = hd / Vec16<T>::N;
+    int lpk_log2 = 0;
+    while ((1 << lpk_log2) < lanes) ++lpk_log2;
+    const float qscale = (float)(1.4426950408889634 / sqrt((double)hd));
+    hipLaunchKernelGGL((beam_decode_kernel<T, G>), dim3((unsigned)rows, (unsigned)n_kv), dim3(256), 0, (hipStream_t)stream, (const T*)qkv, ld,
+                       (const T*)pk, (const T*)pv, n_pslots, (int)cap_p, (const T*)bk, (const T*)bv, n_bslots, (int)cap_b, prompt_slot, prompt_len,
+                       gen_len, anc, ld_anc, (T*)out, lse, n_heads, n_kv, hd, n_heads / n_kv, lpk_log2, qscale, n_bad);
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -244,6 +369,35 @@ extern "C" int ssi_attn_decode(const void* qkv, int64_t ld, const void* k_cache,
     SSI_CHECK_ARG(aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache) && (ld * esize) % 16 == 0);
     const int g = n_heads / n_kv;
 #define SSI_DECODE_G(GG) launch_decode<T, GG>(qkv, ld, k_cache, v_cache, n_slots, cap, slot, kv_len, out, lse, rows, n_heads, n_kv, head_dim, n_bad, stream)
+    SSI_DISPATCH_DTYPE(dtype, {
+        if (g == 1) SSI_DECODE_G(1);
+        else if (g == 2) SSI_DECODE_G(2);
+        else if (g <= 4) SSI_DECODE_G(4);
+        else SSI_DECODE_G(8);
+    });
+#undef SSI_DECODE_G
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+extern "C" int ssi_attn_decode_beam(const void* qkv, int64_t ld, const void* pk_cache, const void* pv_cache, int64_t n_pslots, int64_t cap_p,
+                                    const void* bk_cache, const void* bv_cache, int64_t n_bslots, int64_t cap_b, const int32_t* prompt_slot,
+                                    const int32_t* prompt_len, const int32_t* gen_len, const int32_t* anc, int64_t ld_anc, void* out, float* lse,
+                                    int64_t rows, int n_heads, int n_kv, int head_dim, int32_t* n_bad, int dtype, void* stream) {
+    SSI_CHECK_ARG(rows >= 0 && n_pslots >= 0 && cap_p >= 0 && n_bslots >= 0 && cap_b >= 0 && ld_anc >= 0 && (dtype == SSI_F32 || dtype == SSI_BF16));
+    SSI_CHECK_ARG(cap_p + cap_b < (1LL << 31) && n_bslots < (1LL << 31));
+    if (int rc = check_geometry("ssi_attn_decode_beam", n_heads, n_kv, head_dim)) return rc;
+    if (rows == 0) return SSI_OK;
+    const int64_t esize = dtype == SSI_BF16 ? 2 : 4;
+    SSI_CHECK_ARG(qkv && prompt_slot && prompt_len && gen_len && out && rows < (1LL << 31) && ld >= (int64_t)n_heads * head_dim);
+    SSI_CHECK_ARG((pk_cache && pv_cache) || n_pslots * cap_p == 0);
+    SSI_CHECK_ARG((bk_cache && bv_cache && anc) || n_bslots * cap_b * ld_anc == 0);
+    SSI_CHECK_ARG(aligned16(qkv) && aligned16(pk_cache) && aligned16(pv_cache) && aligned16(bk_cache) && aligned16(bv_cache) && (ld * esize) % 16 == 0);
+    const int g = n_heads / n_kv;
+    const int64_t cap_b_eff = (bk_cache && bv_cache && anc) ? cap_b : 0, n_ps_eff = (pk_cache && pv_cache) ? n_pslots : 0;
+#define SSI_DECODE_G(GG)                                                                                                                          \
+    launch_decode_beam<T, GG>(qkv, ld, pk_cache, pv_cache, n_ps_eff, cap_p, bk_cache, bv_cache, n_bslots, cap_b_eff, prompt_slot, prompt_len, gen_len, \
+                              anc, ld_anc, out, lse, rows, n_heads, n_kv, head_dim, n_bad, stream)
     SSI_DISPATCH_DTYPE(dtype, {
         if (g == 1) SSI_DECODE_G(1);
         else if (g == 2) SSI_DECODE_G(2);

@@ -190,7 +190,158 @@ __global__ __launch_bounds__(SEL_THREADS) void decode_select_kernel(const T* __r
     }
 }
 
+// =====================================================================================================================
+// ssi_topk_logprob (ABI v20, beam search): the k best allowed columns of a row with their log-probabilities, and the row's log-normaliser.
+//
+// The two walks of decode_select_kernel.  Walk 1 takes the maximum over all real columns and keeps, per thread, the K best allowed (key,
+// column) pairs it met, sorted, in registers (compile-time indices only: no scratch).  The key of a value orders the stored numbers as
+// unsigned integers: NaN below every number, -0 with +0, nothing at 0 (an empty place).  A thread meets its columns in rising order, so a
+// new pair enters only above a strictly smaller key and the lower column stays ahead among equals.  Then k rounds pick the best head of
+// the 256 lists — the xor tree and the wave order of decode_select_kernel, the lower column winning a tie — and the owner pops it.  Walk 2 is
+// that kernel's exp-sum, term for term, so lse has its rounding points and lp = fl(x - lse) its bound.
+// =====================================================================================================================
+__device__ __forceinline__ uint32_t topk_key(float f) {
+    const uint32_t b = __float_as_uint(f);
+    uint32_t k = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    k = f == 0.f ? 0x80000000u : k;
+    return f != f ? 1u : k;
+}
+
+// is (bk, bi) ahead of (ak, ai)?  Key 0 is "none".
+__device__ __forceinline__ bool topk_ahead(uint32_t ak, int ai, uint32_t bk, int bi) { return bk > ak || (bk == ak && bk != 0 && bi < ai); }
+
+template <typename T, int K>
+__global__ __launch_bounds__(SEL_THREADS) void topk_logprob_kernel(const T* __restrict__ logits, int64_t ld, int vocab, int k,
+                                                                   const uint32_t* __restrict__ mask, int32_t* __restrict__ idx,
+                                                                   float* __restrict__ lp, float* __restrict__ lse, int vec_ok) {
+    constexpr int VEC = Vec16<T>::N;
+    __shared__ float s_f[16];
+    __shared__ int s_i[16];
+    __shared__ uint32_t s_k[SEL_WAVES];
+    const int64_t r = blockIdx.x;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const T* __restrict__ x = logits + r * ld;
+    const int nvec = vec_ok ? vocab / VEC : 0;
+    const int tail0 = nvec * VEC;
+
+    // ---- walk 1 ------------------------------------------------------------------------------------------------------------------
+    float gm = -INFINITY;
+    uint32_t key[K];
+    int at[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        key[i] = 0u;
+        at[i] = -1;
+    }
+    auto visit = [&](int c, float f, bool allowed) {
+        gm = fmaxf(gm, f);
+        const uint32_t nk = topk_key(f);
+        if (allowed && nk > key[K - 1]) {                 // (rare once the lists have filled: a wave skips the insertion when no lane takes it)
+#pragma unroll
+            for (int i = K - 1; i > 0; --i) {             // every place the new pair passes takes what stood above it, the first one the pair
+                const bool up = nk > key[i], up_prev = nk > key[i - 1];
+                at[i] = up ? (up_prev ? at[i - 1] : c) : at[i];
+                key[i] = up ? (up_prev ? key[i - 1] : nk) : key[i];
+            }
+            at[0] = nk > key[0] ? c : at[0];
+            key[0] = nk > key[0] ? nk : key[0];
+        }
+    };
+    auto visit_vec = [&](int c0, const Vec16<T>& xv, uint32_t bits) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) visit(c0 + e, xv.get(e), (bits & (1u << e)) != 0);
+    };
+    if (mask) sel_walk<T, true>(x, mask, nvec, tid, visit_vec);
+    else sel_walk<T, false>(x, mask, nvec, tid, visit_vec);
+    for (int c = tail0 + tid; c < vocab; c += SEL_THREADS) visit(c, to_f32<T>(x[c]), (sel_mask_bits(mask, c) & 1u) != 0);
+    gm = wave_max(gm);
+    if (lane == 0) s_f[wave] = gm;
+    __syncthreads();
+    gm = fmaxf(fmaxf(s_f[0], s_f[1]), fmaxf(s_f[2], s_f[3]));
+
+    // ---- the k best heads, one per round ------------------------------------------------------------------------------------------
+    int my_idx = -1;                                      // thread j < k keeps result j
+    for (int j = 0; j < k; ++j) {
+        uint32_t bk = key[0];
+        int bi = at[0];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t ok = (uint32_t)__shfl_xor((int)bk, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (topk_ahead(bk, bi, ok, oi)) {
+                bk = ok;
+                bi = oi;
+            }
+        }
+        __syncthreads();                                  // (the previous round's reads of s_k / s_i are over)
+        if (lane == 0) {
+            s_k[wave] = bk;
+            s_i[wave] = bi;
+        }
+        __syncthreads();
+        bk = s_k[0];
+        bi = s_i[0];
+#pragma unroll
+        for (int w = 1; w < SEL_WAVES; ++w) {
+            if (topk_ahead(bk, bi, s_k[w], s_i[w])) {
+                bk = s_k[w];
+                bi = s_i[w];
+            }
+        }
+        if (bk == 0u) bi = -1;                            // nothing allowed is left (uniform over the workgroup)
+        if (tid == j) my_idx = bi;
+        if (bi >= 0 && at[0] == bi) {                     // the owner pops its head (columns are distinct)
+#pragma unroll
+            for (int i = 0; i + 1 < K; ++i) {
+                key[i] = key[i + 1];
+                at[i] = at[i + 1];
+            }
+            key[K - 1] = 0u;
+            at[K - 1] = -1;
+        }
+    }
+
+    // ---- walk 2: decode_select_kernel's exp-sum over all real columns --------------------------------------------------------------
+    const float nm = -gm * SEL_LOG2E;
+    float s = 0.f;
+    sel_walk<T, false>(x, nullptr, nvec, tid, [&](int, const Vec16<T>& xv, uint32_t) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) s += __builtin_amdgcn_exp2f(__builtin_fmaf(xv.get(e), SEL_LOG2E, nm));
+    });
+    for (int c = tail0 + tid; c < vocab; c += SEL_THREADS) s += __builtin_amdgcn_exp2f(__builtin_fmaf(to_f32<T>(x[c]), SEL_LOG2E, nm));
+    s = block_sum(s, s_f + 8);
+    const float row_lse = gm + logf(s);
+    if (tid == 0 && lse) lse[r] = row_lse;
+    if (tid < k) {
+        idx[r * k + tid] = my_idx;
+        lp[r * k + tid] = my_idx >= 0 ? to_f32<T>(x[my_idx]) - row_lse : -INFINITY;
+    }
+}
+
 }  // namespace
+
+extern "C" int ssi_topk_logprob(const void* logits, int64_t ld, int64_t rows, int64_t vocab, int k, const uint32_t* mask, int64_t mask_words,
+                                int32_t* idx, float* lp, float* lse, int dtype, void* stream) {
+    SSI_CHECK_ARG(rows >= 0 && rows < (1LL << 31) && (dtype == SSI_F32 || dtype == SSI_BF16));
+    SSI_CHECK_ARG(k >= 1 && k <= 8);
+    SSI_CHECK_ARG(logits && idx && lp && vocab >= 1 && ld >= vocab && vocab < (1LL << 31));
+    SSI_CHECK_ARG(mask ? mask_words == (vocab + 31) / 32 : mask_words == 0);
+    if (rows == 0) return SSI_OK;
+    const int64_t esize = dtype == SSI_BF16 ? 2 : 4;
+    const int vec_ok = ((uintptr_t)logits & 15) == 0 && (ld * esize) % 16 == 0;
+#define SSI_TOPK_K(KK)                                                                                                                        \
+    hipLaunchKernelGGL((topk_logprob_kernel<T, KK>), dim3((unsigned)rows), dim3(SEL_THREADS), 0, (hipStream_t)stream, (const T*)logits, ld, \
+                       (int)vocab, k, mask, idx, lp, lse, vec_ok)
+    SSI_DISPATCH_DTYPE(dtype, {
+        if (k == 1) SSI_TOPK_K(1);
+        else if (k == 2) SSI_TOPK_K(2);
+        else if (k <= 4) SSI_TOPK_K(4);
+        else SSI_TOPK_K(8);
+    });
+#undef SSI_TOPK_K
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
 
 extern "C" int ssi_decode_select(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow, const uint32_t* allow_early,
                                  const int32_t* n_generated, int32_t min_new, int64_t* token, float* logprob, int32_t* rank, int dtype,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Greedy generation entry point (the reference's scripts/generate.py runs vLLM): a generations JSONL the reference's scripts/wer.py reads.
+"""Generation entry point, greedy or (gen.beam_width > 1) beam search (the reference's scripts/generate.py runs vLLM): a generations JSONL the reference's scripts/wer.py reads.
     python scripts/generate.py speech.n_dsus=5000 gen.input=prompts.jsonl gen.output_dir=out [key=value ...]
     python scripts/generate.py speech.n_dsus=5000 data=sft/<dataset> gen.split=dev gen.output_dir=out
 """
@@ -68,6 +68,9 @@ def main(cfg):
         constraints["allowed_token_ids"] = allowed
     if int(cfg.sampling_params.get("min_tokens") or 0) > 0:
         constraints["min_new_tokens"] = int(cfg.sampling_params.min_tokens)
+    if int(cfg.gen.get("beam_width") or 1) != 1:          # beam search: gen.* keys, not sampling_params (which stay greedy, n = 1)
+        constraints.update(beam_width=int(cfg.gen.beam_width), length_penalty=float(cfg.gen.get("length_penalty", 1.0)),
+                           n_best=int(cfg.gen.get("n_best", 1)))
     summary = generate_file(t.model, t.tokenizer, None if prompts is not None else str(cfg.gen.input), out_path,
                             max_new_tokens=int(cfg.sampling_params.max_tokens), stop_token_ids=None if stop is None else [int(s) for s in stop],
                             tokenizer_decoding={k: cfg.tokenizer_decoding[k] for k in cfg.tokenizer_decoding}, prompts=prompts, ids=ids,

@@ -12,7 +12,14 @@ token of a step is the first maximum among the ALLOWED columns, from ``ssi_decod
 log-probability under the unconstrained distribution and its rank there (0: the constraint did not bind).  The stop tokens are always allowed;
 none of them can be one of a row's first ``min_new_tokens`` tokens.  Without either argument the loop is the unconstrained one, launch for launch.
 
-Out of scope: sampling, beam search, continuous batching (refilling freed slots), generation under data parallelism, a skinny GEMM for
+Beam search (``beam_search``; ``gen.beam_width`` in ``conf/generate.yaml`` — not a ``sampling_params`` key, as vLLM keeps ``BeamSearchParams``
+apart): ``beam_width`` hypotheses per prompt are rows of one decode step.  They share the prompt's K / V and every generated position before
+they diverged: ``decode_step_beam`` writes a row's K / V into a beam cache at (row, step) and reads through an ancestry table
+(``ssi_attn_decode_beam``), so a reorder copies the small table and never the cache.  The ``beam_width`` best allowed continuations of a
+row and the row's log-normaliser come from ``ssi_topk_logprob``; the bookkeeping of a step is a few ``[n_seq, ...]`` torch ops on the device.
+
+Out of scope: sampling (``n``, ``best_of`` stay refused), ``beam_width > 8``, sharing the prompt's K / V read among a prompt's beams, beam
+search under data parallelism, continuous batching (refilling freed slots), paged caches, generation under data parallelism, a skinny GEMM for
 small batches, and WER itself (its text normaliser is the reference's dependency; the JSONL written here is what its ``wer.py`` reads)."""
 
 from __future__ import annotations
@@ -31,9 +38,11 @@ from .constants import CROSS_ENTROPY_IGNORE_IDX
 
 LOGGER = logging.getLogger(__name__)
 
-__all__ = ["Generation", "READBACK_EVERY", "plan_groups", "allowed_mask", "generate", "generate_file", "output_record", "check_greedy"]
+__all__ = ["Generation", "READBACK_EVERY", "MAX_BEAM_WIDTH", "plan_groups", "allowed_mask", "generate", "beam_search", "generate_file", "output_record",
+           "check_greedy"]
 
 READBACK_EVERY = 8    # decode steps between two read-backs of "has every row of the group finished?"
+MAX_BEAM_WIDTH = 8    # the k of ssi_topk_logprob
 
 
 @dataclass
@@ -41,13 +50,15 @@ class Generation:
     """``token_ids``: the generated tokens, INCLUDING the stop token that ended it; ``finish_reason``: ``"stop"`` or ``"length"``;
     ``stop_reason``: the stop token's id, or None; ``cumulative_logprob``: the sum of the chosen tokens' log-probabilities (natural log;
     None without ``logprobs=True``); ``prompt_len``: tokens in the prompt; ``n_constrained``: the steps at which the constraint changed the
-    choice (the chosen token was not the row's unconstrained first), None when no constraint was given."""
+    choice (the chosen token was not the row's unconstrained first), None when no constraint was given; ``score`` (``beam_search`` only):
+    ``cumulative_logprob / len(token_ids) ** length_penalty``, what the hypotheses of a prompt are ordered by."""
     token_ids: list[int]
     finish_reason: str
     stop_reason: int | None
     cumulative_logprob: float | None
     prompt_len: int
     n_constrained: int | None = None
+    score: float | None = None
 
 
 def plan_groups(lengths: Sequence[int], batch_size: int) -> list[list[int]]:
@@ -230,16 +241,185 @@ def _generate_group(model, cache, seqs: list[Tensor], max_new_tokens: int, stop:
                        prompt_len=int(seqs[i].numel()), n_constrained=host_con[i]) for i in range(n)]
 
 
+# ---- beam search -----------------------------------------------------------------------------------------------------------------
+def _check_beam(beam_width, length_penalty, n_best) -> tuple[int, float, int]:
+    """The ranges of the three beam arguments (``ValueError``): ``1 <= n_best <= beam_width <= MAX_BEAM_WIDTH``, ``length_penalty`` finite, >= 0."""
+    for name, v in (("beam_width", beam_width), ("n_best", n_best)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{name} = {v!r}: an integer")
+    if not 1 <= beam_width <= MAX_BEAM_WIDTH:
+        raise ValueError(f"beam_width = {beam_width}: 1 to {MAX_BEAM_WIDTH}")
+    if not 1 <= n_best <= beam_width:
+        raise ValueError(f"n_best = {n_best}: 1 to beam_width ({beam_width})")
+    if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float)) or not 0.0 <= float(length_penalty) < float("inf"):
+        raise ValueError(f"length_penalty = {length_penalty!r}: a finite number >= 0")
+    return beam_width, float(length_penalty), n_best
+
+
+def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_tokens: int, stop_token_ids: Sequence[int], pad_id: int,
+                length_penalty: float = 1.0, n_best: int = 1, allowed_token_ids: Sequence[int] | Tensor | None = None, min_new_tokens: int = 0,
+                batch_size: int = 256) -> list[list[Generation]]:
+    """The ``n_best <= beam_width <= 8`` best hypotheses of every prompt, best first, in INPUT order; ``cumulative_logprob`` (the sum of the
+    tokens' log-probabilities under the unconstrained distribution) and ``score`` are always set.  A group holds ``batch_size // beam_width``
+    prompts, so a step is at most ``batch_size`` rows.  The rules, with ``W = beam_width``:
+
+    1. At step ``t`` a prompt has live beams ``b = 0..`` with fp32 scores ``s_b``; one beam with score 0 at ``t = 0`` (the prefill's logits row).
+    2. Continuations: the ``W`` best triples ``(s_b + lp, b, token)`` over the live beams' allowed NON-stop tokens, by score descending, then
+       beam ascending, then token ascending (``ops.topk_logprob`` with ``k = W`` per row under the allowed-minus-stops mask).
+    3. Finishers: for every live beam and stop token ``s_b + (x[stop] - lse)``; none while ``t < min_new_tokens``.
+    4. Continuations and finishers are merged in the same order.  Every finisher among the first ``W`` entries joins the prompt's pool: final
+       score ``score / (t + 1) ** length_penalty``, ``finish_reason`` ``"stop"``, the stop token included.
+    5. The ``W`` continuations become the next beams.
+    6. A prompt is done when its pool holds at least ``W`` hypotheses.  After ``max_new_tokens`` the live beams join it with ``"length"`` and
+       ``s / max_new_tokens ** length_penalty``.
+    7. The result: the pool by final score descending (stable in the order of joining), cut to ``n_best``.
+
+    Refused before any launch (``ValueError``): the three beam arguments outside their ranges, and everything ``generate`` refuses."""
+    W, length_penalty, n_best = _check_beam(beam_width, length_penalty, n_best)
+    max_new_tokens, batch_size, min_new_tokens, V = int(max_new_tokens), int(batch_size), int(min_new_tokens), int(model.vocab_size)
+    masks = _constraint_masks(V, allowed_token_ids, min_new_tokens, stop_token_ids)
+    stops = allowed_mask(V, ids=[int(t) for t in stop_token_ids])
+    cont = (masks[1] if masks is not None else ~stops)
+    if not bool(cont.any()):
+        raise ValueError("beam_search: nothing is allowed besides the stop tokens")
+    if max_new_tokens < 1:
+        raise ValueError(f"max_new_tokens must be >= 1 (got {max_new_tokens})")
+    if batch_size < W:
+        raise ValueError(f"batch_size = {batch_size} holds no prompt of beam_width = {W}")
+    seqs = [torch.as_tensor(p, dtype=torch.int64).reshape(-1) for p in prompts]
+    lens = [int(s.numel()) for s in seqs]
+    if not seqs:
+        return []
+    per_group = batch_size // W
+    groups = plan_groups(lens, per_group)
+    n_slots = min(per_group, len(seqs))
+    model.check_generation_lengths(lens, max_new_tokens, len(seqs), max(lens) + max_new_tokens)      # every prompt, before the first launch
+    device = model.device
+    stop = torch.tensor(sorted({int(t) for t in stop_token_ids}), dtype=torch.int64, device=device)
+    results: list[list[Generation] | None] = [None] * len(seqs)
+    was_training = bool(model.training)
+    model.eval()
+    try:
+        with torch.inference_mode():
+            pcache, bcache = model.new_kv_cache(n_slots, max(lens)), model.new_kv_cache(n_slots * W, max_new_tokens)
+            cont_words = _mask_words(cont).to(device)
+            for group in groups:
+                found = _beam_group(model, pcache, bcache, [seqs[i] for i in group], W, max_new_tokens, stop, int(pad_id), length_penalty, n_best,
+                                    cont_words, min_new_tokens)
+                for i, g in zip(group, found):
+                    results[i] = g
+    finally:
+        if was_training:
+            model.train()
+    return results  # type: ignore[return-value]
+
+
+def _beam_group(model, pcache, bcache, seqs: list[Tensor], W: int, max_new: int, stop: Tensor, pad_id: int, length_penalty: float, n_best: int,
+                cont_words: Tensor, min_new: int) -> list[list[Generation]]:
+    """One group: row ``s * W + b`` is beam ``b`` of prompt ``s``.  Everything of a step stays on the device."""
+    n, dev, V, S = len(seqs), model.device, int(model.vocab_size), int(stop.numel())
+    R, P, NEG = n * W, 2 * W, float("-inf")     # a pool never holds more than (W - 1) + W hypotheses; place P takes what is not stored
+    i64, f32 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float32, device=dev)
+    logits = model.prefill(pcache, seqs)
+    own = torch.arange(R, dtype=torch.int32, device=dev)
+    seq_of = own // W
+    plen = torch.tensor([int(s.numel()) for s in seqs], dtype=torch.int32).to(dev).repeat_interleave(W)
+    scores = torch.full((n, W), NEG, **f32)
+    scores[:, 0] = 0.0
+    hist = torch.full((R, max_new), pad_id, **i64)
+    anc = torch.zeros((R, max_new), dtype=torch.int32, device=dev)
+    pool_score, pool_raw = torch.full((n, P + 1), NEG, **f32), torch.zeros((n, P + 1), **f32)
+    pool_len, pool_stop = torch.zeros((n, P + 1), **i64), torch.full((n, P + 1), -1, **i64)
+    pool_tok = torch.full((n, P + 1, max_new), pad_id, **i64)
+    count, done = torch.zeros(n, **i64), torch.zeros(n, dtype=torch.bool, device=dev)
+    idx, lp, lse = torch.empty((R, W), dtype=torch.int32, device=dev), torch.empty((R, W), **f32), torch.empty(R, **f32)
+    beam_of = torch.cat([torch.arange(W, **i64).repeat_interleave(W), torch.arange(W, **i64).repeat_interleave(S)]).expand(n, -1)
+    is_fin = torch.cat([torch.zeros(W * W, dtype=torch.bool, device=dev), torch.ones(W * S, dtype=torch.bool, device=dev)]).expand(n, -1)
+    place = torch.arange(W * W + W * S, **i64)
+
+    def join(who: Tensor, final: Tensor, raw: Tensor, length: int, stop_tok: Tensor, beams: Tensor, last_tok: Tensor | None, at: int) -> None:
+        """The entries ``who`` (bool ``[n, m]``) join their prompts' pools, in the order of their columns."""
+        nonlocal count
+        dest = torch.where(who, count[:, None] + who.cumsum(1) - 1, torch.full_like(beams, P))
+        pool_score.scatter_(1, dest, final)
+        pool_raw.scatter_(1, dest, raw)
+        pool_len.scatter_(1, dest, torch.full_like(dest, length))
+        pool_stop.scatter_(1, dest, stop_tok)
+        toks = hist.view(n, W, max_new).gather(1, beams[:, :, None].expand(-1, -1, max_new))
+        if last_tok is not None:
+            toks[:, :, at] = last_tok
+        pool_tok.scatter_(1, dest[:, :, None].expand(-1, -1, max_new), toks)
+        count = count + who.sum(1)
+
+    for t in range(max_new):
+        rows = n if t == 0 else R                       # step 0 reads the prefill's row of every prompt: its one beam
+        ops.topk_logprob(logits, V, W, idx[:rows], lp[:rows], lse[:rows], mask=cont_words)
+        fin_lp = logits[:, stop].float() - lse[:rows, None]
+        nb = rows // n
+        c_tok, c_lp, fin_lp = idx[:rows].long().view(n, nb, W), lp[:rows].view(n, nb, W), fin_lp.view(n, nb, S)
+        c_sc = torch.where(c_tok >= 0, scores[:, :, None] + c_lp, torch.full_like(scores, NEG)[:, :, None])      # ([n, 1, W] spreads over the beams)
+        f_sc = scores[:, :, None] + fin_lp if t >= min_new else torch.full((n, W, S), NEG, **f32)
+        sc = torch.cat([c_sc.reshape(n, W * W), f_sc.reshape(n, W * S)], dim=1)
+        sc = torch.where(sc.isnan(), torch.full_like(sc, NEG), sc)
+        tk = torch.cat([c_tok.expand(n, W, W).reshape(n, W * W), stop.expand(n, W, S).reshape(n, W * S)], dim=1)
+        # the order of rules 2 and 4: (beam, token) ascending first, then a stable sort by score descending
+        o = torch.argsort(beam_of * V + tk.clamp(min=0), dim=1, stable=True)
+        sc, o2 = torch.sort(sc.gather(1, o), dim=1, descending=True, stable=True)
+        o = o.gather(1, o2)
+        tk, bm, fin = tk.gather(1, o), beam_of.gather(1, o), is_fin.gather(1, o)
+        valid = sc > NEG
+        who = fin & valid & (place < W) & ~done[:, None]
+        join(who[:, :W], sc[:, :W] / float((t + 1) ** length_penalty), sc[:, :W], t + 1, tk[:, :W], bm[:, :W], tk[:, :W], t)
+        is_cont = ~fin & valid
+        nth = is_cont.cumsum(1) - 1
+        dest = torch.where(is_cont & (nth < W), nth, torch.full_like(nth, W))
+        new_sc = torch.full((n, W + 1), NEG, **f32).scatter_(1, dest, sc)[:, :W].contiguous()
+        parent = torch.zeros((n, W + 1), **i64).scatter_(1, dest, bm)[:, :W].contiguous()
+        new_tok = torch.zeros((n, W + 1), **i64).scatter_(1, dest, tk)[:, :W].contiguous()
+        done = done | (count >= W)
+        live = (new_sc > NEG) & ~done[:, None]
+        scores = torch.where(live, new_sc, torch.full_like(new_sc, NEG))
+        prow = (torch.arange(n, **i64)[:, None] * W + parent).view(R)
+        hist = hist.index_select(0, prow)
+        hist[:, t] = torch.where(live.view(R), new_tok.view(R), torch.full_like(prow, pad_id))
+        if t + 1 == max_new:
+            break
+        if (t + 1) % READBACK_EVERY == 0 and bool(done.all()):      # the read-back
+            break
+        anc = anc.index_select(0, prow)
+        anc[:, t] = own
+        logits = model.decode_step_beam(pcache, bcache, torch.where(live, new_tok, torch.zeros_like(new_tok)).view(R),
+                                        torch.where(live.view(R), seq_of, torch.full_like(seq_of, -1)), plen, anc, t)
+    live = scores > NEG                                 # what is still alive after max_new tokens ends by length (none in a group that ended early)
+    all_beams = torch.arange(W, **i64).expand(n, W)
+    join(live & ~done[:, None], scores / float(max_new ** length_penalty), scores, max_new, torch.full((n, W), -1, **i64), all_beams, None, 0)
+    best, order = torch.sort(pool_score[:, :P], dim=1, descending=True, stable=True)
+    h_score, h_raw = best.cpu().tolist(), pool_raw[:, :P].gather(1, order).cpu().tolist()
+    h_len, h_stop = pool_len[:, :P].gather(1, order).cpu().tolist(), pool_stop[:, :P].gather(1, order).cpu().tolist()
+    h_tok, h_count = pool_tok[:, :P].gather(1, order[:, :, None].expand(-1, -1, max_new)).cpu(), count.cpu().tolist()
+    errors = int(pcache.errors) + int(bcache.errors)
+    if errors != 0:
+        raise RuntimeError(f"beam_search: the K/V cache kernels refused {errors} rows (a destination, a slot or an ancestry entry outside its cache)")
+    out = []
+    for s in range(n):
+        out.append([Generation(token_ids=h_tok[s, j, :h_len[s][j]].tolist(), finish_reason="stop" if h_stop[s][j] >= 0 else "length",
+                               stop_reason=h_stop[s][j] if h_stop[s][j] >= 0 else None, cumulative_logprob=h_raw[s][j],
+                               prompt_len=int(seqs[s].numel()), score=h_score[s][j]) for j in range(min(n_best, h_count[s]))])
+    return out
+
+
 # ---- JSONL in, JSONL out ---------------------------------------------------------------------------------------------------------
-def output_record(item_id: Any, prompt_ids: Sequence[int], gen: Generation, tokenizer, decoding: dict | None = None) -> dict[str, Any]:
+def output_record(item_id: Any, prompt_ids: Sequence[int], gen: "Generation | Sequence[Generation]", tokenizer, decoding: dict | None = None) -> dict[str, Any]:
     """One output line in the shape of the reference's generations file: ``outputs`` is a list with ONE entry (greedy, ``n = 1``) whose
-    ``text`` is what the reference's ``extract_texts_from_generations_jsonl`` reads."""
+    ``text`` is what the reference's ``extract_texts_from_generations_jsonl`` reads — or, for a list of hypotheses (beam search with
+    ``n_best``), one entry each, ``index`` 0.. in the list's order (best first)."""
     decoding = dict(decoding or {})
     special = {v: k for k, v in getattr(tokenizer, "special_tokens", {}).items()}
+    gens = [gen] if isinstance(gen, Generation) else list(gen)
     return {"id": item_id, "prompt_token_ids": [int(t) for t in prompt_ids], "prompt": tokenizer.decode(list(prompt_ids), **decoding),
-            "outputs": [{"index": 0, "text": tokenizer.decode(gen.token_ids, **decoding), "token_ids": gen.token_ids,
-                         "cumulative_logprob": gen.cumulative_logprob, "finish_reason": gen.finish_reason, "stop_reason": gen.stop_reason,
-                         "stop_reason_text": special.get(gen.stop_reason) if gen.stop_reason is not None else None}]}
+            "outputs": [{"index": j, "text": tokenizer.decode(g.token_ids, **decoding), "token_ids": g.token_ids,
+                         "cumulative_logprob": g.cumulative_logprob, "finish_reason": g.finish_reason, "stop_reason": g.stop_reason,
+                         "stop_reason_text": special.get(g.stop_reason) if g.stop_reason is not None else None} for j, g in enumerate(gens)]}
 
 
 def _read_prompts(tokenizer, in_path: str) -> tuple[list[Any], list[list[int]]]:
@@ -274,7 +454,10 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     with one entry holding ``index, text, token_ids, cumulative_logprob, finish_reason, stop_reason, stop_reason_text``, in INPUT order.
     ``stop_token_ids`` default to the tokenizer's ``[eom_id, eot_id, eos_id]``; ``pad_id`` to the tokenizer's; ``kw`` goes to ``generate``.
     Returns ``{"items", "generated_tokens", "stopped"}``, and under a constraint (``allowed_token_ids`` / ``min_new_tokens`` in ``kw``) also
-    ``"constrained_tokens"``: the tokens the constraint changed, over all items."""
+    ``"constrained_tokens"``: the tokens the constraint changed, over all items.
+    ``beam_width > 1`` in ``kw`` (with ``length_penalty``, ``n_best``): ``beam_search`` instead of ``generate``; ``outputs`` then holds ``n_best``
+    entries, ``index`` 0.., best first, the summary counts every written hypothesis and gains ``"beam_width"``.  ``beam_width = 1`` (the default)
+    is the greedy path: nothing of beam search runs."""
     if in_path is not None:
         ids, prompts = _read_prompts(tokenizer, in_path)
     elif prompts is None:
@@ -285,6 +468,10 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     if stop_token_ids is None:
         stop_token_ids = default_stop_token_ids(tokenizer)
     kw.setdefault("pad_id", int(getattr(tokenizer, "pad_id", 0) or 0))
+    beam = {k: kw.pop(k) for k in ("beam_width", "length_penalty", "n_best") if k in kw}
+    if int(beam.get("beam_width", 1)) != 1:
+        return _beam_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, beam, kw)
+    _check_beam(1, beam.get("length_penalty", 1.0), beam.get("n_best", 1))      # (n_best > 1 needs a beam)
     gens = generate(model, prompts, max_new_tokens=max_new_tokens, stop_token_ids=stop_token_ids, **kw)
     with open(out_path, "w", encoding="utf-8") as f:
         for item_id, p, g in zip(ids, prompts, gens):
@@ -294,6 +481,22 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     if kw.get("allowed_token_ids") is not None or int(kw.get("min_new_tokens", 0)) != 0:
         summary["constrained_tokens"] = sum(g.n_constrained or 0 for g in gens)
     return summary
+
+
+def _beam_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, beam: dict, kw: dict) -> dict[str, Any]:
+    """``generate_file`` with ``beam_width > 1``.  ``logprobs`` is not an option here (every hypothesis carries its log-probability), and
+    ``device`` must be the model's, as ``generate`` asks."""
+    kw = dict(kw)
+    kw.pop("logprobs", None)
+    device = kw.pop("device", None)
+    if device is not None and torch.device(device) != model.device:
+        raise ValueError(f"generate: device {device} is not the model's ({model.device})")
+    found = beam_search(model, prompts, max_new_tokens=max_new_tokens, stop_token_ids=stop_token_ids, **beam, **kw)
+    with open(out_path, "w", encoding="utf-8") as f:
+        for item_id, p, g in zip(ids, prompts, found):
+            f.write(json.dumps(output_record(item_id, p, g, tokenizer, tokenizer_decoding), ensure_ascii=False) + "\n")
+    return {"items": len(found), "generated_tokens": sum(len(g.token_ids) for gs in found for g in gs),
+            "stopped": sum(g.finish_reason == "stop" for gs in found for g in gs), "beam_width": int(beam["beam_width"])}
 
 
 # ---- what the script accepts of the reference's sampling_params ------------------------------------------------------------------

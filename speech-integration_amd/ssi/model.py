@@ -789,6 +789,46 @@ class HipLlamaDecoder(nn.Module):
         cache.lengths.index_add_(0, slot.clamp(min=0).long(), write.to(torch.int32))
         return logits[:n]
 
+    @torch.no_grad()
+    def decode_step_beam(self, prompt_cache: "KVCache", beam_cache: "KVCache", tokens: Tensor, prompt_slot: Tensor, prompt_len: Tensor,
+                         anc: Tensor, t: int) -> Tensor:
+        """Step ``t`` of beam search: row ``r`` (one hypothesis) runs ``tokens[r]`` at position ``prompt_len[r] + t``.  Its K / V go to the beam
+        cache at ``(r, t)``, and it attends over the ``prompt_len[r]`` keys of slot ``prompt_slot[r]`` of the prompt cache (what ``prefill``
+        filled; read only here) and the generated positions ``i <= t`` of the beam cache at slots ``anc[r, i]`` — ``anc`` (int32
+        ``[rows, >= t + 1]``, contiguous) is the hypothesis' ancestry and the caller has set ``anc[r, t] = r``.  ``prompt_slot[r] = -1``: an inert
+        row.  Everything on the device; rows padded to whole tiles and activations in the ``*.g`` buffers, as ``decode_step``.  Neither cache's
+        ``lengths`` are read or changed; refused indices are counted in ``beam_cache.errors``.  Returns ``[rows, vocab_pad]`` logits (fresh)."""
+        self._check_cache(prompt_cache)
+        self._check_cache(beam_cache)
+        n, t = tokens.numel(), int(t)
+        if tokens.dim() != 1 or tokens.dtype != torch.int64 or any(x.shape != tokens.shape or x.dtype != torch.int32 for x in (prompt_slot, prompt_len)):
+            raise ValueError("decode_step_beam: tokens is int64 [rows], prompt_slot and prompt_len int32 [rows]")
+        if anc.dim() != 2 or anc.dtype != torch.int32 or anc.shape[0] != n or not anc.is_contiguous():
+            raise ValueError("decode_step_beam: anc is a contiguous int32 [rows, width]")
+        if not 0 <= t < min(beam_cache.cap, anc.shape[1]) or n > beam_cache.n_slots:
+            raise ValueError(f"decode_step_beam: step {t} of {n} rows does not fit a beam cache of {beam_cache.n_slots} slots x {beam_cache.cap} "
+                             f"and an ancestry of width {anc.shape[1]}")
+        if not all(x.is_cuda for x in (tokens, prompt_slot, prompt_len, anc)):
+            raise _lib.HipLibraryError("decode_step_beam: tokens, prompt_slot, prompt_len and anc must live on the GPU (no CPU fallback)")
+        R = self._padded_rows(n)
+        H, KV, hd, dev = self.num_heads, self.num_kv_heads, self.head_dim, self.device
+        tok = torch.zeros(R, dtype=torch.int64, device=dev)           # pad rows: token 0, slot -1, position 0
+        slot = torch.full((R,), -1, dtype=torch.int32, device=dev)
+        plen = torch.zeros(R, dtype=torch.int32, device=dev)
+        anc_r = torch.zeros((R, anc.shape[1]), dtype=torch.int32, device=dev)
+        tok[:n], slot[:n], plen[:n], anc_r[:n] = tokens, prompt_slot, prompt_len, anc
+        live = slot >= 0
+        dest = torch.where(live, torch.arange(R, dtype=torch.int64, device=dev) * beam_cache.cap + t, torch.full((R,), -1, dtype=torch.int64, device=dev))
+        pos = torch.where(live, plen + t, torch.zeros_like(plen)).clamp(max=self._rope.shape[0] - 1).contiguous()
+        gen_len = torch.where(live, torch.full_like(plen, t + 1), torch.zeros_like(plen))
+
+        def attend(l: int, b: _LayerBufs) -> None:
+            ops.kv_store(b.qkv, dest, beam_cache.k[l], beam_cache.v[l], H, KV, hd, n_bad=beam_cache.errors)
+            ops.attn_decode_beam(b.qkv, prompt_cache.k[l], prompt_cache.v[l], beam_cache.k[l], beam_cache.v[l], slot, plen, gen_len, anc_r, b.att,
+                                 None, H, KV, hd, n_bad=beam_cache.errors)
+
+        return self._head_logits(self._run_stack("g", tok, R, 1, R, pos, attend)[1].xn1)[:n]
+
     # ---- tied LM head ------------------------------------------------------------------------------------------------
     def _head_logits(self, hn: Tensor, arena_name: Optional[str] = None) -> Tensor:
         """logits [T, vocab_pad] = hn E^T.  Callers of the public ``forward`` get a FRESH tensor (as torchtune returns): logits kept

@@ -10,7 +10,7 @@ from torch import Tensor
 from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
-__all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "decode_select", "swiglu_fwd",
+__all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "attn_decode_beam", "decode_select", "topk_logprob", "swiglu_fwd",
            "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "ema_update", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
@@ -247,6 +247,55 @@ def decode_select(logits: Tensor, vocab: int, token: Tensor, logprob: Tensor | N
     check(_lib.load().ssi_decode_select(ptr(logits), logits.stride(0), rows, int(vocab), ptr(allow), ptr(allow_early), ptr(n_generated),
                                         int(min_new), ptr(token), ptr(logprob), ptr(rank), dtype_code(logits.dtype), stream_ptr()),
           "ssi_decode_select")
+
+
+def attn_decode_beam(qkv: Tensor, pk_cache: Tensor, pv_cache: Tensor, bk_cache: Tensor, bv_cache: Tensor, prompt_slot: Tensor, prompt_len: Tensor,
+                     gen_len: Tensor, anc: Tensor, out: Tensor, lse: Tensor | None, n_heads: int, n_kv: int, head_dim: int,
+                     n_bad: Tensor | None = None) -> None:
+    """``attn_decode`` of row ``r`` over two key ranges, one behind the other: the first ``prompt_len[r]`` keys of slot ``prompt_slot[r]`` of the
+    prompt cache ``[n_pslots, cap_p, n_kv * head_dim]``, then ``gen_len[r]`` keys of the beam cache ``[n_bslots, cap_b, n_kv * head_dim]``,
+    generated position ``i`` from slot ``anc[r, i]`` (int32 ``[rows, ld_anc]``, unit inner stride).  ``prompt_slot < 0``: a zero row.  A
+    ``prompt_slot`` or ``anc`` entry outside its cache is never dereferenced: its keys are skipped and the row is counted once into ``n_bad``.
+    ``ssi_attn_decode_beam``: bit-equal to ``attn_decode`` on a cache that holds the row's keys contiguously."""
+    ptr(qkv)
+    if qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] < n_heads * head_dim:
+        raise _lib.HipLibraryError(f"attn_decode_beam: qkv must be [rows, >= {n_heads * head_dim}] with unit inner stride (got {tuple(qkv.shape)})")
+    rows = qkv.shape[0]
+    _kv_cache_ok(pk_cache, pv_cache, qkv, n_kv, head_dim)
+    _kv_cache_ok(bk_cache, bv_cache, qkv, n_kv, head_dim)
+    for name, t in (("prompt_slot", prompt_slot), ("prompt_len", prompt_len), ("gen_len", gen_len)):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != rows or t.device != qkv.device:
+            raise _lib.HipLibraryError(f"attn_decode_beam: {name} is one int32 per row of qkv, on its device")
+    if anc.dtype != torch.int32 or anc.dim() != 2 or anc.shape[0] != rows or not anc.is_contiguous() or anc.device != qkv.device:
+        raise _lib.HipLibraryError("attn_decode_beam: anc is a contiguous int32 [rows, ld_anc] tensor on the device of qkv")
+    if out.dtype != qkv.dtype or not out.is_contiguous() or out.numel() != rows * n_heads * head_dim or out.device != qkv.device:
+        raise _lib.HipLibraryError(f"attn_decode_beam: out must be a contiguous [rows, {n_heads * head_dim}] tensor of the dtype and device of qkv")
+    if lse is not None and (lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() < rows * n_heads or lse.device != qkv.device):
+        raise _lib.HipLibraryError("attn_decode_beam: lse is fp32 [rows, n_heads] on the device of qkv")
+    if n_bad is not None and (n_bad.dtype != torch.int32 or n_bad.numel() != 1 or n_bad.device != qkv.device):
+        raise _lib.HipLibraryError("attn_decode_beam: n_bad is one int32 on the device of qkv")
+    check(_lib.load().ssi_attn_decode_beam(ptr(qkv), qkv.stride(0), ptr(pk_cache), ptr(pv_cache), pk_cache.shape[0], pk_cache.shape[1],
+                                           ptr(bk_cache), ptr(bv_cache), bk_cache.shape[0], bk_cache.shape[1], ptr(prompt_slot), ptr(prompt_len),
+                                           ptr(gen_len), ptr(anc), anc.shape[1], ptr(out), ptr(lse), rows, n_heads, n_kv, head_dim, ptr(n_bad),
+                                           dtype_code(qkv.dtype), stream_ptr()), "ssi_attn_decode_beam")
+
+
+def topk_logprob(logits: Tensor, vocab: int, k: int, idx: Tensor, lp: Tensor, lse: Tensor | None = None, *, mask: Tensor | None = None) -> None:
+    """The ``k`` (1..8) best allowed columns of every row of ``logits`` ([rows, ld], unit inner stride; read only): ``idx`` (int32 ``[rows, k]``)
+    by stored value descending, ties to the lower column, NaN below every number, -1 where fewer than ``k`` columns are allowed; ``lp`` (fp32
+    ``[rows, k]``) = ``x[idx] - lse``, -inf at -1; ``lse`` (fp32 ``[rows]``, optional) the log-normaliser over ALL real columns ``[0, vocab)``.
+    ``mask``: ``decode_select``'s int32 bit mask of ``ceil(vocab / 32)`` words, ``None`` = every column.  ``ssi_topk_logprob``."""
+    ptr(logits)
+    if logits.dim() != 2 or logits.stride(1) != 1 or not 1 <= vocab <= logits.shape[1]:
+        raise _lib.HipLibraryError(f"topk_logprob: logits must be [rows, >= vocab] with unit inner stride (got {tuple(logits.shape)}, vocab {vocab})")
+    rows, words, k = logits.shape[0], (vocab + 31) // 32, int(k)
+    for name, t, dtype, n in (("idx", idx, torch.int32, rows * k), ("lp", lp, torch.float32, rows * k), ("lse", lse, torch.float32, rows)):
+        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.numel() != n or t.device != logits.device):
+            raise _lib.HipLibraryError(f"topk_logprob: {name} is a contiguous {dtype} tensor of {n} elements on the device of logits")
+    if mask is not None and (mask.dtype != torch.int32 or not mask.is_contiguous() or mask.numel() != words or mask.device != logits.device):
+        raise _lib.HipLibraryError(f"topk_logprob: mask is {words} int32 words (one bit per column) on the device of logits")
+    check(_lib.load().ssi_topk_logprob(ptr(logits), logits.stride(0), rows, int(vocab), k, ptr(mask), 0 if mask is None else mask.numel(),
+                                       ptr(idx), ptr(lp), ptr(lse), dtype_code(logits.dtype), stream_ptr()), "ssi_topk_logprob")
 
 
 def swiglu_fwd(gu: Tensor, act: Tensor) -> None:

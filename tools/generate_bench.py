@@ -1,5 +1,5 @@
 """What greedy generation costs at the 1B shape (Llama-3.2-1B + 5000 DSUs, bf16, random weights): 256 prompts of about 1000 tokens, 256 new
-tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained] [--json profiles/generate.json]
+tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained|beam] [--json profiles/generate.json]
 
 run        prefill time, milliseconds per decode step (event time over all steps, host gaps included), generated tokens per second, and a
            self-check: the first generated token of every prompt against the argmax of a plain full forward of that prompt alone (with
@@ -14,6 +14,12 @@ constrained  (not part of ``all``; python tools/generate_bench.py --part constra
            the caches hold) and rotating over buffers larger than the caches together; and a decode step whose token comes from the kernel
            (``--allowed-types``, ``--min-new-tokens``) against the unconstrained step (argmax + the forward-only cross-entropy for the
            log-probability) and the step without log-probabilities, on a cache filled with random numbers at the same lengths.
+beam       (not part of ``all``; python tools/generate_bench.py --part beam --json profiles/generate_beam.json) what beam search costs, ONE process
+           alternating the forms over ``--rounds`` rounds, median and min..max: ``ssi_topk_logprob`` alone (k = ``--beam-width``, the stop tokens
+           masked) against ``ssi_decode_select`` and a torch restatement; ``ssi_attn_decode_beam`` alone (``--prompts / --beam-width`` prompts x
+           ``--beam-width`` beams, a random ancestry, rotating over the layers' caches) against ``ssi_attn_decode`` on the materialised cache,
+           with their outputs compared bit for bit; a beam decode step (``decode_step_beam`` + ``ssi_topk_logprob``) against the greedy step
+           (``decode_step`` + argmax) at the same rows and key counts; and one ``beam_search`` call end to end.
 all        the three as child processes, each under its own ``timeout``, chained with ``&&``; then the results and the floor from traffic
            alone (weights read once per step, the cache read once per step) are merged into --json."""
 import argparse, csv, glob, json, os, statistics, subprocess, sys, time
@@ -22,7 +28,7 @@ PKG = os.path.join(ROOT, 'speech-integration_amd')
 sys.path.insert(0, PKG)
 
 ap = argparse.ArgumentParser()
-ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained'])
+ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained', 'beam'])
 ap.add_argument('--prompts', type=int, default=256)
 ap.add_argument('--prompt-len', type=int, default=1000)
 ap.add_argument('--new', type=int, default=256)
@@ -31,6 +37,7 @@ ap.add_argument('--json', default=None)
 ap.add_argument('--allowed-types', default='text,special_text', help='constrained: kinds of get_token_type_ranges, comma-separated')
 ap.add_argument('--min-new-tokens', type=int, default=0, help='constrained: rows below it take the mask without the stop tokens')
 ap.add_argument('--rounds', type=int, default=7)
+ap.add_argument('--beam-width', type=int, default=4)
 ap.add_argument('--workdir', default=os.path.join(ROOT, 'prof_out', 'generate_bench'))
 args = ap.parse_args()
 HBM_TB_S = (5.4, 6.4)   # what the README records for the AdamW and EMA passes
@@ -295,6 +302,180 @@ def part_constrained():
     return res
 
 
+def part_beam():
+    import torch
+    from ssi import ops
+    from ssi.generate import _mask_words, allowed_mask, beam_search
+    model = build_model()
+    W, n, V, ld, L = args.beam_width, args.prompts, model.vocab_size, model.vocab_pad, model.num_layers
+    H, KV, hd = model.num_heads, model.num_kv_heads, model.head_dim
+    n_seq = n // W
+    R = n_seq * W
+    prompts = make_prompts(V)[:n_seq]
+    lens = torch.tensor([p.numel() for p in prompts], dtype=torch.int32)
+    stops = [V - 3, V - 2, V - 1]
+    cont_w = _mask_words(~allowed_mask(V, ids=stops)).cuda()
+    dev = dict(device='cuda')
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(reps):
+            fn(i)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3        # us per call
+
+    def rounds_of(forms, reps):
+        for fn in forms.values():
+            timed(fn, 4)
+        got = {k: [] for k in forms}
+        for _ in range(args.rounds):
+            for k, fn in forms.items():
+                got[k].append(timed(fn, reps))
+        return {k: spread(v) for k, v in got.items()}
+
+    res = {'geometry': f'Llama-3.2-1B + 5000 DSUs, bf16, random weights; {n_seq} prompts of {int(lens.min())}..{int(lens.max())} tokens x beam_width {W} = {R} rows; '
+                       f'[{R}, {ld}] logits, vocab {V}; {args.rounds} rounds alternating the forms in one process'}
+    with torch.inference_mode():
+        # ---- top-k alone -------------------------------------------------------------------------------------------------------------
+        g = torch.Generator(device='cuda').manual_seed(3)
+        bufs = [torch.randn(R, ld, generator=g, **dev).mul_(3).to(torch.bfloat16) for _ in range(8)]      # 8 x 68 MB: beyond L2 + MALL
+        idx, lp, lse = torch.empty((R, W), dtype=torch.int32, **dev), torch.empty((R, W), **dev), torch.empty(R, **dev)
+        tok, slp, rk = torch.empty(R, dtype=torch.int64, **dev), torch.empty(R, **dev), torch.empty(R, dtype=torch.int32, **dev)
+        allow_dev = ~allowed_mask(V, ids=stops).cuda()
+
+        def restated(x):
+            masked = x[:, :V].float().masked_fill(~allow_dev, float('-inf'))
+            top = masked.topk(W, dim=-1)
+            return top.indices, top.values - torch.logsumexp(x[:, :V].float(), -1, keepdim=True)
+
+        ops.topk_logprob(bufs[0], V, W, idx, lp, lse, mask=cont_w)
+        r_idx, r_lp = restated(bufs[0])
+        same = idx.long() == r_idx                      # (torch.topk does not promise the lower column among equal bf16 values)
+        res['topk_self_check'] = {'idx_equal_torch_topk': int(same.sum()), 'of': int(same.numel()),
+                                  'values_equal_where_idx_differs': bool(torch.equal(bufs[0].gather(1, idx.long())[~same], bufs[0].gather(1, r_idx)[~same])),
+                                  'largest_logprob_difference': float((lp - r_lp).abs().max())}
+        forms = {'topk_logprob_one_buffer_us': lambda i: ops.topk_logprob(bufs[0], V, W, idx, lp, lse, mask=cont_w),
+                 'decode_select_one_buffer_us': lambda i: ops.decode_select(bufs[0], V, tok, slp, rk, allow=cont_w),
+                 'torch_restatement_one_buffer_us': lambda i: restated(bufs[0]),
+                 'topk_logprob_rotating_buffers_us': lambda i: ops.topk_logprob(bufs[i % 8], V, W, idx, lp, lse, mask=cont_w),
+                 'decode_select_rotating_buffers_us': lambda i: ops.decode_select(bufs[i % 8], V, tok, slp, rk, allow=cont_w),
+                 'torch_restatement_rotating_buffers_us': lambda i: restated(bufs[i % 8])}
+        res['topk_alone'] = rounds_of(forms, 40)
+        res['topk_alone']['k'] = W
+        res['topk_alone']['row_bytes_read_once_MB'] = round(R * V * 2 / 1e6, 1)
+        del bufs
+        torch.cuda.empty_cache()
+
+        # ---- attention alone: every layer's caches in turn, generated position t = half of --new --------------------------------------
+        t_mid = args.new // 2
+        pcache, bcache = model.new_kv_cache(n_seq, int(lens.max())), model.new_kv_cache(R, t_mid + args.trace_steps + 1)
+        for c in (pcache, bcache):
+            c.k.normal_()
+            c.v.normal_()
+        own = torch.arange(R, dtype=torch.int32, **dev)
+        seq_of = own // W
+        plen = lens.cuda().repeat_interleave(W)
+        width = t_mid + args.trace_steps + 1
+        anc = (seq_of[:, None] * W + torch.randint(0, W, (R, width), generator=g, **dev)).to(torch.int32).contiguous()
+        gen_len = torch.full((R,), t_mid, dtype=torch.int32, **dev)
+        kv_len = (plen + gen_len).contiguous()
+        cap = int(kv_len.max())
+        mk = torch.zeros((L, R, cap, KV * hd), dtype=torch.bfloat16, **dev)
+        mv = torch.zeros_like(mk)
+        for r in range(R):                              # the materialised cache: the row's prompt keys, then its ancestry's
+            s, a, b = int(seq_of[r]), int(plen[r]), int(plen[r]) + t_mid
+            mk[:, r, :a], mv[:, r, :a] = pcache.k[:, s, :a], pcache.v[:, s, :a]
+            pos = torch.arange(t_mid, **dev)
+            mk[:, r, a:b], mv[:, r, a:b] = bcache.k[:, anc[r, :t_mid].long(), pos], bcache.v[:, anc[r, :t_mid].long(), pos]
+        qkv = torch.randn(R, (H + 2 * KV) * hd, generator=g, **dev).to(torch.bfloat16)
+        o_b, o_c = torch.empty((R, H * hd), dtype=torch.bfloat16, **dev), torch.empty((R, H * hd), dtype=torch.bfloat16, **dev)
+        l_b, l_c = torch.empty((R, H), **dev), torch.empty((R, H), **dev)
+        bad = torch.zeros(1, dtype=torch.int32, **dev)
+
+        def beam_attn(i, lse_out=None):
+            l = i % L
+            ops.attn_decode_beam(qkv, pcache.k[l], pcache.v[l], bcache.k[l], bcache.v[l], seq_of, plen, gen_len, anc, o_b, lse_out, H, KV, hd, n_bad=bad)
+
+        def cont_attn(i, lse_out=None):
+            l = i % L
+            ops.attn_decode(qkv, mk[l], mv[l], own, kv_len, o_c, lse_out, H, KV, hd, n_bad=bad)
+
+        beam_attn(3, l_b)
+        cont_attn(3, l_c)
+        res['attention_self_check'] = {'out_bit_equal': bool(torch.equal(o_b, o_c)), 'lse_bit_equal': bool(torch.equal(l_b, l_c)), 'n_bad': int(bad)}
+        res['attention_alone'] = rounds_of({'attn_decode_beam_us': beam_attn, 'attn_decode_materialised_us': cont_attn}, 2 * L)
+        keys = int(kv_len.sum())
+        per_key = 2 * KV * hd * 2
+        res['attention_alone'].update({'layers_rotated': L, 'keys_walked_per_launch': keys, 'GB_walked_per_launch': round(keys * per_key / 1e9, 3),
+                                       'GB_distinct_per_launch_beam': round((int(lens.sum()) + R * t_mid) * per_key / 1e9, 3)})
+        for k in ('attn_decode_beam_us', 'attn_decode_materialised_us'):
+            res['attention_alone'][k.replace('_us', '_TB_per_s_walked')] = round(keys * per_key / 1e6 / res['attention_alone'][k]['median'], 2)
+        del mk, mv
+        torch.cuda.empty_cache()
+
+        # ---- a decode step: the same rows and key counts in both forms -------------------------------------------------------------------
+        steps = args.trace_steps
+        gcache = model.new_kv_cache(R, int(lens.max()) + t_mid + steps + 1)
+        gcache.k.normal_()
+        gcache.v.normal_()
+        start = (plen + t_mid).contiguous()
+
+        def greedy_block():
+            gcache.lengths.copy_(start)
+            t = torch.zeros(R, dtype=torch.int64, **dev)
+            for _ in range(steps):
+                t = model.decode_step(gcache, t, own)[:, :V].argmax(-1)
+
+        def beam_block():
+            t = torch.zeros(R, dtype=torch.int64, **dev)
+            for j in range(steps):
+                x = model.decode_step_beam(pcache, bcache, t, seq_of, plen, anc, t_mid + j)
+                ops.topk_logprob(x, V, W, idx, lp, lse, mask=cont_w)
+                t = idx[:, 0].long()
+
+        def block_ms(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / steps
+
+        sforms = {'greedy_step_ms': greedy_block, 'beam_step_ms': beam_block}
+        for fn in sforms.values():
+            block_ms(fn)
+        got = {k: [] for k in sforms}
+        for _ in range(args.rounds):
+            for k, fn in sforms.items():
+                got[k].append(block_ms(fn))
+        assert int(gcache.errors) == 0 and int(bcache.errors) == 0 and int(pcache.errors) == 0
+        st = {k: spread(v, 4) for k, v in got.items()}
+        st.update({'steps_per_block': steps, 'generated_position_at_block_start': t_mid,
+                   'beam_minus_greedy_ms': round(st['beam_step_ms']['median'] - st['greedy_step_ms']['median'], 4),
+                   'greedy_spread_ms': round(st['greedy_step_ms']['max'] - st['greedy_step_ms']['min'], 4)})
+        res['decode_step'] = st
+        del gcache, pcache, bcache
+        torch.cuda.empty_cache()
+
+    # ---- one call, end to end (its own bookkeeping and read-backs included) ---------------------------------------------------------------
+    beam_search(model, [p[:64] for p in prompts[:4]], beam_width=W, max_new_tokens=4, stop_token_ids=stops, pad_id=0)      # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    found = beam_search(model, prompts, beam_width=W, max_new_tokens=args.new, stop_token_ids=stops, pad_id=0, n_best=W, batch_size=n)
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    n_tok = sum(len(h.token_ids) for hs in found for h in hs)
+    res['beam_search_call'] = {'prompts': n_seq, 'beam_width': W, 'max_new_tokens': args.new, 'wall_s': round(wall, 2),
+                               'hypotheses': sum(len(hs) for hs in found), 'tokens_in_hypotheses': n_tok,
+                               'ended_by_length': sum(h.finish_reason == 'length' for hs in found for h in hs),
+                               'ms_per_step_with_prefill_and_bookkeeping': round(wall / args.new * 1e3, 3)}
+    print(json.dumps(res, indent=1), flush=True)
+    return res
+
+
 def split_trace(stats_csv, steps):
     rows = [r for r in csv.DictReader(open(stats_csv)) if int(r['Calls']) >= steps]
     ms = lambda sel: sum(float(r['TotalDurationNs']) for r in rows if sel(r['Name'])) / 1e6 / steps  # noqa: E731
@@ -315,6 +496,8 @@ elif args.part == 'recompute':
     res = part_recompute()
 elif args.part == 'constrained':
     res = part_constrained()
+elif args.part == 'beam':
+    res = part_beam()
 else:
     wd = args.workdir
     os.makedirs(wd, exist_ok=True)
