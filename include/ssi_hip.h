@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 20 /* 20: + ssi_attn_decode_beam, ssi_topk_logprob (beam search: decode attention through an ancestry table, the k best allowed columns of a row; opt-in)
+#define SSI_ABI_VERSION 21 /* 21: + ssi_decode_sample (sampled decoding: temperature, top-k, top-p and a seeded Gumbel-max draw of a row's token in one launch; opt-in)
+                           * 20: + ssi_attn_decode_beam, ssi_topk_logprob (beam search: decode attention through an ancestry table, the k best allowed columns of a row; opt-in)
                            * 19: + ssi_decode_select (constrained greedy decoding: the allowed argmax of a row, its log-probability and its rank in one pass; opt-in)
                            * 18: + ssi_kv_store, ssi_attn_decode (greedy generation: a K/V cache and single-query attention over it; nothing else calls them)
                            * 17: + ssi_ema_update (fp32 exponential moving average of the flat parameter buffer, one pass chained to AdamW; opt-in)
@@ -296,6 +297,38 @@ int ssi_topk_logprob(const void* logits, int64_t ld, int64_t rows, int64_t vocab
  * SSI_ERR_ARG: null logits or token, vocab < 1, ld < vocab, vocab >= 2^31, rows >= 2^31, min_new < 0.  rows == 0 launches nothing. */
 int ssi_decode_select(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow, const uint32_t* allow_early,
                       const int32_t* n_generated, int32_t min_new, int64_t* token, float* logprob, int32_t* rank, int dtype, void* stream);
+
+/* The sampled token of a decode step (ABI v21; vLLM's temperature, top_k, top_p and seed): a draw from softmax(x / T) of every row of logits
+ * [rows, ld], restricted by ssi_decode_select's masks, top-k and top-p, as a pure function of (seed, sequence[r], step) and the row.  The logits
+ * are read only.  Per row, on the STORED values, with the mask the row takes (allow_early while n_generated[r] < min_new; NULL = every column):
+ *   A  = the allowed columns below vocab.  Values are ordered as ssi_topk_logprob orders them: NaN below every number, -0 with +0.
+ *   K  = {c in A : x_c >= tk}, tk the top_k-th largest value of A counted with multiplicity, when 0 < top_k < |A| (ties at the threshold all
+ *        stay: vLLM's `logits < kth` mask); K = A when top_k <= 0 or top_k >= |A|.
+ *   P  = {c in K : x_c >= tp} when top_p < 1: with w_c = exp((x_c - m) / T), m = max_K x, Z = sum_K w and M(v) = sum_{c in K, x_c >= v} w_c,
+ *        tp is the largest value v occurring in K with M(v) >= top_p Z — the fewest whole value classes, from the top, that reach top_p, after
+ *        top-k and renormalised over K (vLLM's order).  The class of the maximum is always kept.  P = K when top_p >= 1.
+ *   token[r]   = argmax_{c in P} (x_c / T + G_c), the lowest column on a tie (Gumbel-max: exactly a draw from softmax(x / T) over P), with
+ *                G_c = -ln(-ln u_c), u_c = (2 (w_c >> 9) + 1) 2^-24, w_c word c & 3 of Philox4x32-10 with counter (c >> 2, step, sequence[r],
+ *                0x53414D50) and key (seed low word, seed high word).  u is an odd multiple of 2^-24, exact in fp32: G lies in [-2.82, 16.64].
+ *                A NaN or -inf column is never drawn while a column of A holds a number above -inf; when none does, the token is the FIRST
+ *                allowed column (ssi_decode_select's rule) and P is that column alone.
+ *   logprob[r] = x[token] - log sum_{c < vocab} exp x[c] over ALL real columns at T = 1: ssi_decode_select's, term for term (NULL ok).
+ *   n_kept[r]  = |P| (NULL ok).
+ * A row with nothing allowed below vocab: token = -1, logprob = 0, n_kept = -1.  A +inf in an allowed column makes the masses of top-p
+ * meaningless (P is then K); the token is still an allowed column.
+ * Arithmetic: the score is fma(x, fl(1 / T), G) with -ln u = -logf(u) below 1/2 and -log1pf(u - 1) from there on (u - 1 is exact).  A mass is
+ * exp2(fma(x, sc, nm)), sc = fl(log2 e / T), nm = fl(-m sc) (a NaN counts 0), times 2^40 and truncated to an integer; masses are summed as
+ * 64-bit integers (LDS atomics: the order of arrival cannot matter), and M(v) >= top_p Z is the integer compare M >= ceil(top_p Z) with the
+ * product in fp64.
+ * One workgroup of 256 threads per row; no workspace.  Walks of the row: 2 (the maxima; exp-sum and draw) with top_k <= 0 and top_p >= 1; with
+ * either, a radix select on the values' unsigned order adds 8-bit passes of LDS histograms (counts and masses): 2 passes per threshold for
+ * bf16, 4 for fp32.  In the draw a column's logarithms are skipped where the largest G its word's leading ones allow cannot lift it above a score
+ * already reached, which cannot change the result.  A row's outputs depend on that row, the masks and the scalars only.
+ * SSI_ERR_ARG before any launch: temperature not finite or <= 0, top_p outside (0, 1], a NULL sequence, and everything ssi_decode_select
+ * refuses.  rows == 0 launches nothing. */
+int ssi_decode_sample(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow, const uint32_t* allow_early,
+                      const int32_t* n_generated, int32_t min_new, double temperature, int64_t top_k, double top_p, uint64_t seed, uint32_t step,
+                      const uint32_t* sequence, int64_t* token, float* logprob, int32_t* n_kept, int dtype, void* stream);
 
 /* ---- K7  SwiGLU elementwise (torchtune FeedForward: w2(silu(w1 x) * w3 x)) ------------------------------------------ */
 /* gu: [rows, 2*inter] = [gate | up]; act[rows, inter] = silu(gate) * up */

@@ -166,6 +166,21 @@ __device__ __forceinline__ int block_sum_i32(int v, int* red) {
     return t;
 }
 
+// ---- counter-based random bits ---------------------------------------------------------------------------------------------
+struct Philox4 { uint32_t w[4]; };
+
+// Philox4x32-10 (Salmon et al., SC'11): ten rounds of two 32x32->64 multiplies, the key bumped by the Weyl constants between rounds
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return Philox4{{c0, c1, c2, c3}};
+}
+
 // ---- buffer resources ----------------------------------------------------------------------------------------------------
 // Raw buffer over `base`: stride 0, 2 GiB window, 32-bit data format (gfx9 family).  buffer_rsrc: the four words in SGPRs, for the inline-asm
 // LDS-DMA requests (attn_mfma.h, gemm_nt4.h); buffer_rsrc_of: the compiler's resource type, for the raw_buffer_load / _store builtins.

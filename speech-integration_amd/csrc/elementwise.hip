@@ -570,20 +570,7 @@ extern "C" int ssi_sumsq(const void* x, int64_t n, int dtype, float* out, void* 
 // (profiles/LAB_NOTES.md).  The rounding is defined on the bit pattern and the random bits come from a counter-based generator keyed by
 // (seed, step, global element index, tensor): no state, the same bits in every launch, on every rank and after every resume.
 // =====================================================================================================================
-struct Philox4 { uint32_t w[4]; };
-
-// Philox4x32-10 (Salmon et al., SC'11): ten rounds of two 32x32->64 multiplies, the key bumped by the Weyl constants between rounds
-__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return Philox4{{c0, c1, c2, c3}};
-}
-
+// (Philox4x32-10 itself is in common_hip.h: the sampler of decode_sample.hip draws from it, too.)
 // the 64 random bits of tensor `tensor` for the 8-element vector j (= global element index >> 3) at optimizer step `step`
 __device__ __forceinline__ Philox4 sr_bits(int64_t j, uint32_t step, uint32_t tensor, uint64_t seed) {
     return philox4x32_10((uint32_t)j, (uint32_t)((uint64_t)j >> 32), step, tensor, (uint32_t)seed, (uint32_t)(seed >> 32));

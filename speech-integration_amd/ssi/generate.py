@@ -18,7 +18,14 @@ they diverged: ``decode_step_beam`` writes a row's K / V into a beam cache at (r
 (``ssi_attn_decode_beam``), so a reorder copies the small table and never the cache.  The ``beam_width`` best allowed continuations of a
 row and the row's log-normaliser come from ``ssi_topk_logprob``; the bookkeeping of a step is a few ``[n_seq, ...]`` torch ops on the device.
 
-Out of scope: sampling (``n``, ``best_of`` stay refused), ``beam_width > 8``, sharing the prompt's K / V read among a prompt's beams, beam
+Sampling (``sample``; ``gen.sample`` in ``conf/generate.yaml``): the token of a step is ``ssi_decode_sample``'s — a draw from
+``softmax(x / temperature)`` over the allowed columns that top-k and then top-p keep, by Gumbel-max on counter-based random bits keyed by
+``(seed, sequence, step)`` with ``sequence = prompt index in input order * n + sample index``.  How the prompts were grouped, sorted and batched
+never enters the bits.  ``n = 1`` runs ``generate``'s loop; ``n`` in 2..8 runs a prompt's samples as rows of ``decode_step_beam`` with the identity
+ancestry, so the prompt is prefilled once and its K / V are shared as beams share them.
+
+Out of scope: repetition, presence and frequency penalties, per-request sampling parameters within one launch, ``n > 8`` and ``best_of``, sampling
+inside beam search, ``beam_width > 8``, sharing the prompt's K / V read among a prompt's beams, beam
 search under data parallelism, continuous batching (refilling freed slots), paged caches, generation under data parallelism, a skinny GEMM for
 small batches, and WER itself (its text normaliser is the reference's dependency; the JSONL written here is what its ``wer.py`` reads)."""
 
@@ -38,11 +45,12 @@ from .constants import CROSS_ENTROPY_IGNORE_IDX
 
 LOGGER = logging.getLogger(__name__)
 
-__all__ = ["Generation", "READBACK_EVERY", "MAX_BEAM_WIDTH", "plan_groups", "allowed_mask", "generate", "beam_search", "generate_file", "output_record",
-           "check_greedy"]
+__all__ = ["Generation", "READBACK_EVERY", "MAX_BEAM_WIDTH", "MAX_SAMPLES", "plan_groups", "allowed_mask", "generate", "beam_search", "sample",
+           "generate_file", "output_record", "check_greedy", "check_sampling"]
 
 READBACK_EVERY = 8    # decode steps between two read-backs of "has every row of the group finished?"
 MAX_BEAM_WIDTH = 8    # the k of ssi_topk_logprob
+MAX_SAMPLES = 8       # samples per prompt of ``sample``: the rows of a prompt in ``decode_step_beam``, as many as beams
 
 
 @dataclass
@@ -51,7 +59,8 @@ class Generation:
     ``stop_reason``: the stop token's id, or None; ``cumulative_logprob``: the sum of the chosen tokens' log-probabilities (natural log;
     None without ``logprobs=True``); ``prompt_len``: tokens in the prompt; ``n_constrained``: the steps at which the constraint changed the
     choice (the chosen token was not the row's unconstrained first), None when no constraint was given; ``score`` (``beam_search`` only):
-    ``cumulative_logprob / len(token_ids) ** length_penalty``, what the hypotheses of a prompt are ordered by."""
+    ``cumulative_logprob / len(token_ids) ** length_penalty``, what the hypotheses of a prompt are ordered by; ``n_kept_mean`` (``sample``
+    only): the mean over the generated tokens of the size of the set each was drawn from (after the mask, top-k and top-p)."""
     token_ids: list[int]
     finish_reason: str
     stop_reason: int | None
@@ -59,6 +68,7 @@ class Generation:
     prompt_len: int
     n_constrained: int | None = None
     score: float | None = None
+    n_kept_mean: float | None = None
 
 
 def plan_groups(lengths: Sequence[int], batch_size: int) -> list[list[int]]:
@@ -408,6 +418,145 @@ def _beam_group(model, pcache, bcache, seqs: list[Tensor], W: int, max_new: int,
     return out
 
 
+# ---- sampling --------------------------------------------------------------------------------------------------------------------
+def _check_sample(n, temperature, top_k, top_p, seed) -> tuple[int, float, int, float, int]:
+    """The ranges of the sampling arguments (``ValueError``)."""
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= MAX_SAMPLES:
+        raise ValueError(f"n = {n!r}: an integer from 1 to {MAX_SAMPLES}")
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not 0.0 < float(temperature) < float("inf"):
+        raise ValueError(f"temperature = {temperature!r}: a finite number > 0 (greedy decoding is generate, not temperature 0)")
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0.0 < float(top_p) <= 1.0:
+        raise ValueError(f"top_p = {top_p!r}: a number in (0, 1]")
+    if isinstance(top_k, bool) or not isinstance(top_k, int):
+        raise ValueError(f"top_k = {top_k!r}: an integer (<= 0: no top-k)")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed = {seed!r}: an integer in [0, 2^64)")
+    return n, float(temperature), top_k, float(top_p), seed
+
+
+def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top_k: int = -1, top_p: float = 1.0, seed: int, max_new_tokens: int,
+           stop_token_ids: Sequence[int], pad_id: int, batch_size: int = 256, allowed_token_ids: Sequence[int] | Tensor | None = None,
+           min_new_tokens: int = 0) -> list[list[Generation]]:
+    """``n`` (1..8) sampled continuations of every prompt, in INPUT order and per prompt in sample order; ``cumulative_logprob`` (the tokens'
+    log-probabilities under the unconstrained distribution at temperature 1, what ``ssi.score`` assigns) and ``n_kept_mean`` are always set.
+    The token of a step is ``ops.decode_sample``'s with ``step`` the loop index and ``sequence = prompt index * n + sample index``: a pure function
+    of ``(seed, sequence, step)`` and the row's logits, so ``batch_size``, the grouping and the order of the prompts never enter the random bits.
+    ``top_k <= 0``: no top-k; ties at either threshold stay; top-p acts after top-k on the renormalised rest (vLLM's order).
+    ``n = 1``: ``generate``'s loop (``prefill``, ``decode_step``).  ``n > 1``: a group holds ``batch_size // n`` prompts; the prompt is prefilled
+    once, its logits row repeated ``n`` times at step 0, and the samples run as rows of ``decode_step_beam`` with the identity ancestry.  The
+    self-check per live row: the token is >= 0, allowed, and drawn from a set of at least one column (``RuntimeError``).
+    Refused before any launch (``ValueError``): ``n`` outside 1..8, ``temperature`` not finite or <= 0 (greedy decoding is ``generate``), ``top_p``
+    outside (0, 1], a non-integer ``top_k``, a negative ``seed``, and everything ``generate`` refuses."""
+    n, temperature, top_k, top_p, seed = _check_sample(n, temperature, top_k, top_p, seed)
+    max_new_tokens, batch_size, min_new_tokens, V = int(max_new_tokens), int(batch_size), int(min_new_tokens), int(model.vocab_size)
+    masks = _constraint_masks(V, allowed_token_ids, min_new_tokens, stop_token_ids)
+    if max_new_tokens < 1:
+        raise ValueError(f"max_new_tokens must be >= 1 (got {max_new_tokens})")
+    if batch_size < n:
+        raise ValueError(f"batch_size = {batch_size} holds no prompt of n = {n}")
+    seqs = [torch.as_tensor(p, dtype=torch.int64).reshape(-1) for p in prompts]
+    lens = [int(s.numel()) for s in seqs]
+    if not seqs:
+        return []
+    if len(seqs) * n > 2 ** 32:
+        raise ValueError(f"{len(seqs)} prompts x {n} samples do not fit the 32-bit sequence number")
+    per_group = batch_size // n
+    groups = plan_groups(lens, per_group)
+    n_slots = min(per_group, len(seqs))
+    model.check_generation_lengths(lens, max_new_tokens, len(seqs), max(lens) + max_new_tokens)      # every prompt, before the first launch
+    device = model.device
+    stop = torch.tensor(sorted({int(t) for t in stop_token_ids}), dtype=torch.int64, device=device)
+    draw = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+    results: list[list[Generation] | None] = [None] * len(seqs)
+    was_training = bool(model.training)
+    model.eval()
+    try:
+        with torch.inference_mode():
+            if n == 1:
+                caches = (model.new_kv_cache(n_slots, max(lens) + max_new_tokens),)
+            else:
+                caches = (model.new_kv_cache(n_slots, max(lens)), model.new_kv_cache(n_slots * n, max_new_tokens))
+            con = None
+            if masks is not None:
+                allow, early = (m.to(device) for m in masks)
+                con = _Constraint(allow, _mask_words(masks[0]).to(device), early if min_new_tokens else None,
+                                  _mask_words(masks[1]).to(device) if min_new_tokens else None, min_new_tokens)
+            for group in groups:
+                found = _sample_group(model, caches, [seqs[i] for i in group], group, n, draw, max_new_tokens, stop, int(pad_id), con)
+                for i, g in zip(group, found):
+                    results[i] = g
+    finally:
+        if was_training:
+            model.train()
+    return results  # type: ignore[return-value]
+
+
+def _sample_group(model, caches, seqs: list[Tensor], index: list[int], n: int, draw: dict, max_new: int, stop: Tensor, pad_id: int,
+                  con: _Constraint | None) -> list[list[Generation]]:
+    """One group: row ``s * n + j`` is sample ``j`` of the group's prompt ``s``, whose place in the input is ``index[s]``."""
+    n_p, dev, V = len(seqs), model.device, int(model.vocab_size)
+    R = n_p * n
+    if n == 1:
+        logits = model.prefill(caches[0], seqs, max_new_tokens=max_new)
+    else:
+        logits = model.prefill(caches[0], seqs)[:n_p].repeat_interleave(n, dim=0)      # step 0: the prompt's row, once per sample
+    number = (torch.tensor(index, dtype=torch.int64) * n).repeat_interleave(n) + torch.arange(n, dtype=torch.int64).repeat(n_p)
+    sequence = torch.where(number >= 2 ** 31, number - 2 ** 32, number).to(torch.int32).to(dev)      # (the kernel reads it as unsigned)
+    own = torch.arange(R, dtype=torch.int32, device=dev)
+    no_slot = torch.full_like(own, -1)
+    seq_of = own // n
+    plen = torch.tensor([int(s.numel()) for s in seqs], dtype=torch.int32).to(dev).repeat_interleave(n)
+    anc = own[:, None].expand(R, max_new).contiguous() if n > 1 else None              # the identity ancestry: a sample reads its own rows
+    alive = torch.ones(R, dtype=torch.bool, device=dev)
+    out = torch.full((R, max_new), pad_id, dtype=torch.int64, device=dev)
+    n_gen = torch.zeros(R, dtype=torch.int32, device=dev)
+    stop_tok = torch.full((R,), -1, dtype=torch.int64, device=dev)
+    cum = torch.zeros(R, dtype=torch.float64, device=dev)
+    kept_sum = torch.zeros(R, dtype=torch.int64, device=dev)
+    bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    tok = torch.empty(R, dtype=torch.int64, device=dev)
+    row_lp = torch.empty(R, dtype=torch.float32, device=dev)
+    row_kept = torch.empty(R, dtype=torch.int32, device=dev)
+    for t in range(max_new):
+        if con is None:
+            ops.decode_sample(logits, V, tok, row_lp, row_kept, step=t, sequence=sequence, **draw)
+            ok = torch.ones_like(alive)
+        else:
+            ops.decode_sample(logits, V, tok, row_lp, row_kept, step=t, sequence=sequence, allow=con.allow_words, allow_early=con.early_words,
+                              n_generated=n_gen if con.min_new else None, min_new=con.min_new, **draw)
+            at = tok.clamp(min=0)
+            ok = con.allow[at] if con.early is None else torch.where(n_gen < con.min_new, con.early[at], con.allow[at])
+        bad += (alive & ((tok < 0) | ~ok | (row_kept < 1))).sum()      # the self-check
+        cum += torch.where(alive, row_lp, torch.zeros_like(row_lp)).double()
+        kept_sum += torch.where(alive, row_kept, torch.zeros_like(row_kept))
+        new = tok.clamp(min=0)                                  # (a new tensor per step; never a negative embedding index)
+        out[:, t] = torch.where(alive, new, out[:, t])
+        n_gen += alive
+        stopped = alive & torch.isin(new, stop)
+        stop_tok = torch.where(stopped, new, stop_tok)
+        alive = alive & ~stopped
+        if t + 1 == max_new:
+            break
+        if (t + 1) % READBACK_EVERY == 0 and not bool(alive.any()):   # the read-back
+            break
+        if n == 1:
+            logits = model.decode_step(caches[0], torch.where(alive, new, torch.zeros_like(new)), torch.where(alive, own, no_slot))
+        else:
+            logits = model.decode_step_beam(caches[0], caches[1], torch.where(alive, new, torch.zeros_like(new)),
+                                            torch.where(alive, seq_of, no_slot), plen, anc, t)
+    host_out, host_n, host_stop, host_cum = out.cpu(), n_gen.cpu().tolist(), stop_tok.cpu().tolist(), cum.cpu().tolist()
+    host_kept = kept_sum.cpu().tolist()
+    errors = sum(int(c.errors) for c in caches)
+    if errors != 0:
+        raise RuntimeError(f"sample: the K/V cache kernels refused {errors} rows (a destination, a slot or an ancestry entry outside its cache)")
+    if int(bad) != 0:
+        raise RuntimeError(f"sample: on {int(bad)} rows decode_sample chose no token, one that is not allowed, or kept no column")
+    return [[Generation(token_ids=host_out[r, :host_n[r]].tolist(), finish_reason="stop" if host_stop[r] >= 0 else "length",
+                        stop_reason=host_stop[r] if host_stop[r] >= 0 else None, cumulative_logprob=host_cum[r],
+                        prompt_len=int(seqs[s].numel()), n_kept_mean=host_kept[r] / max(host_n[r], 1))
+             for r in range(s * n, s * n + n)] for s in range(n_p)]
+
+
 # ---- JSONL in, JSONL out ---------------------------------------------------------------------------------------------------------
 def output_record(item_id: Any, prompt_ids: Sequence[int], gen: "Generation | Sequence[Generation]", tokenizer, decoding: dict | None = None) -> dict[str, Any]:
     """One output line in the shape of the reference's generations file: ``outputs`` is a list with ONE entry (greedy, ``n = 1``) whose
@@ -457,7 +606,10 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     ``"constrained_tokens"``: the tokens the constraint changed, over all items.
     ``beam_width > 1`` in ``kw`` (with ``length_penalty``, ``n_best``): ``beam_search`` instead of ``generate``; ``outputs`` then holds ``n_best``
     entries, ``index`` 0.., best first, the summary counts every written hypothesis and gains ``"beam_width"``.  ``beam_width = 1`` (the default)
-    is the greedy path: nothing of beam search runs."""
+    is the greedy path: nothing of beam search runs.
+    ``sample=True`` in ``kw`` (with ``temperature``, ``seed`` and optionally ``n``, ``top_k``, ``top_p``): ``sample`` instead; ``outputs`` holds ``n``
+    entries, ``index`` 0.. in sample order, and the summary gains ``"sampled": True``, ``"n"`` and ``"kept_tokens_mean"`` (the mean over all generated
+    tokens of the size of the set each was drawn from).  Not together with ``beam_width > 1``."""
     if in_path is not None:
         ids, prompts = _read_prompts(tokenizer, in_path)
     elif prompts is None:
@@ -469,6 +621,13 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
         stop_token_ids = default_stop_token_ids(tokenizer)
     kw.setdefault("pad_id", int(getattr(tokenizer, "pad_id", 0) or 0))
     beam = {k: kw.pop(k) for k in ("beam_width", "length_penalty", "n_best") if k in kw}
+    draw = {k: kw.pop(k) for k in ("sample", "n", "temperature", "top_k", "top_p", "seed") if k in kw}
+    if draw.pop("sample", False):
+        if int(beam.get("beam_width", 1)) != 1:
+            raise ValueError("generate_file: sample together with beam_width > 1 (sampling inside beam search is not built)")
+        return _sample_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, draw, kw)
+    if draw:
+        raise ValueError(f"generate_file: {sorted(draw)} without sample=True")
     if int(beam.get("beam_width", 1)) != 1:
         return _beam_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, beam, kw)
     _check_beam(1, beam.get("length_penalty", 1.0), beam.get("n_best", 1))      # (n_best > 1 needs a beam)
@@ -499,6 +658,23 @@ def _beam_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_to
             "stopped": sum(g.finish_reason == "stop" for gs in found for g in gs), "beam_width": int(beam["beam_width"])}
 
 
+def _sample_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, draw: dict, kw: dict) -> dict[str, Any]:
+    """``generate_file`` with ``sample=True``.  ``logprobs`` is not an option here (every sample carries its log-probability)."""
+    kw = dict(kw)
+    kw.pop("logprobs", None)
+    device = kw.pop("device", None)
+    if device is not None and torch.device(device) != model.device:
+        raise ValueError(f"generate: device {device} is not the model's ({model.device})")
+    found = sample(model, prompts, max_new_tokens=max_new_tokens, stop_token_ids=stop_token_ids, **draw, **kw)
+    with open(out_path, "w", encoding="utf-8") as f:
+        for item_id, p, g in zip(ids, prompts, found):
+            f.write(json.dumps(output_record(item_id, p, g, tokenizer, tokenizer_decoding), ensure_ascii=False) + "\n")
+    tokens = sum(len(g.token_ids) for gs in found for g in gs)
+    kept = sum((g.n_kept_mean or 0.0) * len(g.token_ids) for gs in found for g in gs)
+    return {"items": len(found), "generated_tokens": tokens, "stopped": sum(g.finish_reason == "stop" for gs in found for g in gs),
+            "sampled": True, "n": int(draw.get("n", 1)), "kept_tokens_mean": kept / max(tokens, 1)}
+
+
 # ---- what the script accepts of the reference's sampling_params ------------------------------------------------------------------
 GREEDY = {"n": 1, "temperature": 0.0, "top_p": 1.0, "top_k": -1, "presence_penalty": 0.0, "frequency_penalty": 0.0, "repetition_penalty": 1.0}
 
@@ -527,3 +703,24 @@ def check_greedy(sampling_params) -> None:
         value = sampling_params[key]
         if value is None or float(value) != float(GREEDY[key]):
             raise NotImplementedError(f"sampling_params.{key} = {value!r}: only greedy decoding is built ({key} = {GREEDY[key]!r})")
+
+
+SAMPLING_KEYS = ("n", "temperature", "top_k", "top_p")
+
+
+def check_sampling(sampling_params) -> dict[str, Any]:
+    """What ``gen.sample: true`` accepts of ``sampling_params``: ``temperature > 0``, an integer ``top_k``, ``top_p`` in (0, 1] and ``n`` in
+    1..8, besides what ``check_greedy`` lets through.  Still ``NotImplementedError``: a penalty off its default, ``best_of``, an unknown key.
+    ``ValueError``: ``temperature = 0`` (that is greedy decoding: ``gen.sample: false``) and every value outside its range.  Returns the four
+    sampling arguments of ``sample`` (``n`` 1, ``top_k`` -1 and ``top_p`` 1 where the key is absent; ``temperature`` must be there)."""
+    check_greedy({k: sampling_params[k] for k in sampling_params if k not in SAMPLING_KEYS})
+    got = {k: sampling_params[k] for k in SAMPLING_KEYS if k in sampling_params}
+    if got.get("temperature") is None:
+        raise ValueError("sampling_params.temperature: gen.sample needs a temperature > 0")
+    if not isinstance(got["temperature"], bool) and isinstance(got["temperature"], (int, float)) and float(got["temperature"]) == 0.0:
+        raise ValueError("sampling_params.temperature = 0 is greedy decoding: gen.sample=false")
+    top_p = got.get("top_p", 1.0)
+    if isinstance(top_p, int) and not isinstance(top_p, bool):
+        top_p = float(top_p)
+    n, temperature, top_k, top_p, _ = _check_sample(got.get("n", 1), got["temperature"], got.get("top_k", -1), top_p, 0)
+    return {"n": n, "temperature": temperature, "top_k": top_k, "top_p": top_p}

@@ -10,7 +10,7 @@ from torch import Tensor
 from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
-__all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "attn_decode_beam", "decode_select", "topk_logprob", "swiglu_fwd",
+__all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "attn_decode_beam", "decode_select", "decode_sample", "topk_logprob", "swiglu_fwd",
            "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "ema_update", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
@@ -247,6 +247,34 @@ def decode_select(logits: Tensor, vocab: int, token: Tensor, logprob: Tensor | N
     check(_lib.load().ssi_decode_select(ptr(logits), logits.stride(0), rows, int(vocab), ptr(allow), ptr(allow_early), ptr(n_generated),
                                         int(min_new), ptr(token), ptr(logprob), ptr(rank), dtype_code(logits.dtype), stream_ptr()),
           "ssi_decode_select")
+
+
+def decode_sample(logits: Tensor, vocab: int, token: Tensor, logprob: Tensor | None = None, n_kept: Tensor | None = None, *, temperature: float,
+                  top_k: int = -1, top_p: float = 1.0, seed: int, step: int, sequence: Tensor, allow: Tensor | None = None,
+                  allow_early: Tensor | None = None, n_generated: Tensor | None = None, min_new: int = 0) -> None:
+    """The sampled token of every row of ``logits`` ([rows, ld], unit inner stride; read only): ``token`` (int64) = a draw from
+    ``softmax(x / temperature)`` over the allowed columns below ``vocab`` that top-k (``top_k <= 0``: off; ties at the threshold stay) and then
+    top-p (``top_p = 1``: off) keep, by Gumbel-max on Philox bits keyed by ``(seed, sequence[r], step)`` — a pure function of those and the row;
+    ``logprob`` (fp32, optional) = the token's log-probability over ALL real columns at temperature 1 (``decode_select``'s); ``n_kept`` (int32,
+    optional) = the size of the set drawn from.  ``sequence``: one int32 per row, read as unsigned.  The masks, ``n_generated`` and ``min_new``
+    are ``decode_select``'s.  A row with nothing allowed: -1 / 0 / -1.  ``ssi_decode_sample``."""
+    ptr(logits)
+    if logits.dim() != 2 or logits.stride(1) != 1 or not 1 <= vocab <= logits.shape[1]:
+        raise _lib.HipLibraryError(f"decode_sample: logits must be [rows, >= vocab] with unit inner stride (got {tuple(logits.shape)}, vocab {vocab})")
+    rows, words = logits.shape[0], (vocab + 31) // 32
+    for name, t, dtype in (("token", token, torch.int64), ("logprob", logprob, torch.float32), ("n_kept", n_kept, torch.int32),
+                           ("n_generated", n_generated, torch.int32), ("sequence", sequence, torch.int32)):
+        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.numel() != rows or t.device != logits.device):
+            raise _lib.HipLibraryError(f"decode_sample: {name} is one {dtype} per row of logits, on its device")
+    for name, t in (("allow", allow), ("allow_early", allow_early)):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != words or t.device != logits.device):
+            raise _lib.HipLibraryError(f"decode_sample: {name} is {words} int32 words (one bit per column) on the device of logits")
+    if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(step) < 2 ** 32:
+        raise _lib.HipLibraryError(f"decode_sample: seed is in [0, 2^64) and step in [0, 2^32) (got {seed}, {step})")
+    top_k = max(-1, min(int(top_k), 2 ** 62))
+    check(_lib.load().ssi_decode_sample(ptr(logits), logits.stride(0), rows, int(vocab), ptr(allow), ptr(allow_early), ptr(n_generated),
+                                        int(min_new), float(temperature), top_k, float(top_p), int(seed), int(step), ptr(sequence), ptr(token),
+                                        ptr(logprob), ptr(n_kept), dtype_code(logits.dtype), stream_ptr()), "ssi_decode_sample")
 
 
 def attn_decode_beam(qkv: Tensor, pk_cache: Tensor, pv_cache: Tensor, bk_cache: Tensor, bv_cache: Tensor, prompt_slot: Tensor, prompt_len: Tensor,

@@ -1,5 +1,5 @@
 """What greedy generation costs at the 1B shape (Llama-3.2-1B + 5000 DSUs, bf16, random weights): 256 prompts of about 1000 tokens, 256 new
-tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained|beam] [--json profiles/generate.json]
+tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained|beam|sample] [--json profiles/generate.json]
 
 run        prefill time, milliseconds per decode step (event time over all steps, host gaps included), generated tokens per second, and a
            self-check: the first generated token of every prompt against the argmax of a plain full forward of that prompt alone (with
@@ -20,6 +20,12 @@ beam       (not part of ``all``; python tools/generate_bench.py --part beam --js
            ``--beam-width`` beams, a random ancestry, rotating over the layers' caches) against ``ssi_attn_decode`` on the materialised cache,
            with their outputs compared bit for bit; a beam decode step (``decode_step_beam`` + ``ssi_topk_logprob``) against the greedy step
            (``decode_step`` + argmax) at the same rows and key counts; and one ``beam_search`` call end to end.
+sample     (not part of ``all``; python tools/generate_bench.py --part sample --json profiles/generate_sample.json) what sampling costs, ONE process
+           alternating the forms over ``--rounds`` rounds, median and min..max: ``ssi_decode_sample`` alone on [prompts, vocab_pad] bf16 logits in
+           three settings (temperature only; top_k = 50; top_p = 0.9) against ``ssi_decode_select`` and a torch restatement (sort, cumsum, a
+           Gumbel argmax), with the walks of the row each setting makes and what reading the row once costs; a sampled decode step
+           (``decode_step`` + ``ssi_decode_sample`` at top_k 50, top_p 0.9) against the greedy step with log-probabilities; and one ``sample``
+           call with ``n = 4``.
 all        the three as child processes, each under its own ``timeout``, chained with ``&&``; then the results and the floor from traffic
            alone (weights read once per step, the cache read once per step) are merged into --json."""
 import argparse, csv, glob, json, os, statistics, subprocess, sys, time
@@ -28,7 +34,7 @@ PKG = os.path.join(ROOT, 'speech-integration_amd')
 sys.path.insert(0, PKG)
 
 ap = argparse.ArgumentParser()
-ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained', 'beam'])
+ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained', 'beam', 'sample'])
 ap.add_argument('--prompts', type=int, default=256)
 ap.add_argument('--prompt-len', type=int, default=1000)
 ap.add_argument('--new', type=int, default=256)
@@ -476,6 +482,143 @@ def part_beam():
     return res
 
 
+def part_sample():
+    import torch
+    from ssi import ops
+    from ssi.constants import CROSS_ENTROPY_IGNORE_IDX as IGNORE
+    from ssi.generate import sample
+    model = build_model()
+    n, V, ld = args.prompts, model.vocab_size, model.vocab_pad
+    dev = dict(device='cuda')
+    T = 0.8
+    settings = {'temperature_only': dict(top_k=-1, top_p=1.0), 'top_k_50': dict(top_k=50, top_p=1.0), 'top_p_0.9': dict(top_k=-1, top_p=0.9),
+                'top_k_50_top_p_0.9': dict(top_k=50, top_p=0.9)}
+    walks = {'temperature_only': 2, 'top_k_50': 4, 'top_p_0.9': 4, 'top_k_50_top_p_0.9': 6}       # bf16: 2 radix passes per threshold
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(reps):
+            fn(i)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3        # us per call
+
+    res = {'geometry': f'[{n}, {ld}] bf16 logits (3 randn), vocab {V}, temperature {T}; {args.rounds} rounds alternating the forms in one process'}
+    with torch.inference_mode():
+        g = torch.Generator(device='cuda').manual_seed(3)
+        x = torch.randn(n, ld, generator=g, **dev).mul_(3).to(torch.bfloat16)
+        tok, lp, kept = torch.empty(n, dtype=torch.int64, **dev), torch.empty(n, **dev), torch.empty(n, dtype=torch.int32, **dev)
+        rk = torch.empty(n, dtype=torch.int32, **dev)
+        seqs = torch.arange(n, dtype=torch.int32, **dev)
+
+        def kernel(s, step=0, logits=None):
+            ops.decode_sample(x if logits is None else logits, V, tok, lp, kept, temperature=T, seed=1, step=step, sequence=seqs, **settings[s])
+            return tok
+
+        def restated(s):
+            """torch: sort, the top-k cut, cumsum for the top-p cut, a Gumbel argmax over what is left (torch's own random bits)."""
+            k, p = settings[s]['top_k'], settings[s]['top_p']
+            v, idx = torch.sort(x[:, :V].float() / T, dim=-1, descending=True)
+            if k > 0:
+                v = v.masked_fill(v < v[:, k - 1:k], float('-inf'))
+            if p < 1.0:
+                pr = torch.softmax(v, -1)
+                v = v.masked_fill((pr.cumsum(-1) - pr) >= p, float('-inf'))
+            gum = -torch.log(-torch.log(torch.rand_like(v).clamp_(1e-7, 1 - 1e-7)))
+            t = idx.gather(1, (v + gum).argmax(-1, keepdim=True))[:, 0]
+            return t, torch.log_softmax(x[:, :V].float(), -1).gather(1, t[:, None])[:, 0]
+
+        check = {}
+        for s in settings:
+            kernel(s)
+            k, p = settings[s]['top_k'], settings[s]['top_p']
+            v = torch.sort(x[:, :V].float(), dim=-1, descending=True).values
+            want = torch.full((n,), V, dtype=torch.int64, **dev) if k <= 0 else (v >= v[:, k - 1:k]).sum(-1)
+            check[s] = {'n_kept_mean': round(float(kept.float().mean()), 1), 'n_kept_equals_torch_count_without_top_p': bool(torch.equal(kept.long(), want)) if p >= 1.0 else None,
+                        'tokens_in_range': bool(((tok >= 0) & (tok < V)).all())}
+        res['self_check'] = check
+        forms = {f'decode_sample_{s}_us': (lambda i, s=s: kernel(s, i)) for s in settings}
+        forms['decode_select_us'] = lambda i: ops.decode_select(x, V, tok, lp, rk)
+        forms.update({f'torch_restatement_{s}_us': (lambda i, s=s: restated(s)) for s in ('temperature_only', 'top_k_50', 'top_p_0.9')})
+        for fn in forms.values():
+            timed(fn, 4)
+        got = {k: [] for k in forms}
+        for _ in range(args.rounds):
+            for k, fn in forms.items():
+                got[k].append(timed(fn, 20))
+        ka = {k: spread(v) for k, v in got.items()}
+        per_walk = ka['decode_select_us']['median'] / 2
+        ka['row_bytes_read_once_MB'] = round(n * V * 2 / 1e6, 1)
+        ka['reading_the_rows_once_us_at_5.4_and_6.4_TB_s'] = [round(n * V * 2 / 1e6 / bw, 1) for bw in HBM_TB_S]
+        ka['decode_select_per_walk_us'] = round(per_walk, 2)
+        ka['walks'] = walks
+        ka['over_walks_times_select_per_walk'] = {s: round(ka[f'decode_sample_{s}_us']['median'] / (walks[s] * per_walk), 2) for s in settings}
+        res['kernel_alone'] = ka
+
+        # a decode step, on a cache of random numbers at the prompts' lengths (every block of steps starts from the same lengths)
+        lens = torch.tensor([p.numel() for p in make_prompts(V)], dtype=torch.int32)
+        steps = args.trace_steps
+        cache = model.new_kv_cache(n, int(lens.max()) + steps + 1)
+        cache.k.normal_()
+        cache.v.normal_()
+        own = torch.arange(n, dtype=torch.int32, **dev)
+        loss, nll = torch.empty(n, **dev), torch.empty(n, **dev)
+
+        def step_greedy(t, j):
+            xx = model.decode_step(cache, t, own)
+            t = xx[:, :V].argmax(-1)
+            ops.ce_fwd_metrics(xx, t, V, IGNORE, loss, None, nll, rk)
+            return t
+
+        def step_sampled(t, j):
+            return kernel('top_k_50_top_p_0.9', j, model.decode_step(cache, t, own)).clone()
+
+        def block(step):
+            cache.lengths.copy_(lens)
+            t = torch.zeros(n, dtype=torch.int64, **dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for j in range(steps):
+                t = step(t, j)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / steps
+
+        sforms = {'greedy_with_logprob_ms': step_greedy, 'sampled_top_k_50_top_p_0.9_ms': step_sampled}
+        for fn in sforms.values():
+            block(fn)
+        got = {k: [] for k in sforms}
+        for _ in range(args.rounds):
+            for k, fn in sforms.items():
+                got[k].append(block(fn))
+        assert int(cache.errors) == 0
+        st = {k: spread(v, 4) for k, v in got.items()}
+        st.update({'steps_per_block': steps, 'sampled_minus_greedy_ms': round(st['sampled_top_k_50_top_p_0.9_ms']['median'] - st['greedy_with_logprob_ms']['median'], 4),
+                   'greedy_spread_ms': round(st['greedy_with_logprob_ms']['max'] - st['greedy_with_logprob_ms']['min'], 4)})
+        res['decode_step'] = st
+        del cache
+        torch.cuda.empty_cache()
+
+    # ---- one call with n = 4, end to end ---------------------------------------------------------------------------------------------------
+    prompts = make_prompts(V)[:n // 4]
+    kw = dict(n=4, temperature=T, top_k=50, top_p=0.9, seed=1, stop_token_ids=[], pad_id=0)
+    sample(model, [p[:64] for p in prompts[:4]], max_new_tokens=4, **kw)      # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    found = sample(model, prompts, max_new_tokens=args.new, batch_size=n, **kw)
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    n_tok = sum(len(h.token_ids) for hs in found for h in hs)
+    res['sample_call'] = {'prompts': len(prompts), 'n': 4, 'max_new_tokens': args.new, 'wall_s': round(wall, 2), 'generated_tokens': n_tok,
+                          'generated_tokens_per_s': round(n_tok / wall), 'ms_per_step_with_prefill_and_bookkeeping': round(wall / args.new * 1e3, 3),
+                          'distinct_samples_per_prompt_mean': round(sum(len({tuple(h.token_ids) for h in hs}) for hs in found) / len(found), 2),
+                          'kept_tokens_mean': round(sum(h.n_kept_mean * len(h.token_ids) for hs in found for h in hs) / max(n_tok, 1), 2)}
+    print(json.dumps(res, indent=1), flush=True)
+    return res
+
+
 def split_trace(stats_csv, steps):
     rows = [r for r in csv.DictReader(open(stats_csv)) if int(r['Calls']) >= steps]
     ms = lambda sel: sum(float(r['TotalDurationNs']) for r in rows if sel(r['Name'])) / 1e6 / steps  # noqa: E731
@@ -498,6 +641,8 @@ elif args.part == 'constrained':
     res = part_constrained()
 elif args.part == 'beam':
     res = part_beam()
+elif args.part == 'sample':
+    res = part_sample()
 else:
     wd = args.workdir
     os.makedirs(wd, exist_ok=True)
