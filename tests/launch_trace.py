@@ -44,6 +44,16 @@ class Tracer:
             for name in ("k", "v", "lengths", "errors"):
                 yield "cache." + name, getattr(c, name)
 
+    def locate(self, v):
+        """(region name, element offset) of a tensor that starts inside one of the watched buffers, else None."""
+        if v.numel():
+            p = v.data_ptr()
+            for where, base in self._regions():
+                lo = base.data_ptr()
+                if base.device == v.device and lo <= p < lo + base.numel() * base.element_size():
+                    return where, (p - lo) // v.element_size()
+        return None
+
     def _enc(self, v):
         if v is None or isinstance(v, (bool, int, str)):
             return v
@@ -51,18 +61,23 @@ class Tracer:
             return v.hex()
         if isinstance(v, torch.Tensor):
             shape, dtype = list(v.shape), str(v.dtype)
-            if v.is_cuda and v.numel():
-                p = v.data_ptr()
-                for where, base in self._regions():
-                    lo = base.data_ptr()
-                    if lo <= p < lo + base.numel() * base.element_size():
-                        return [where, (p - lo) // v.element_size(), shape, list(v.stride()), dtype]
+            at = self.locate(v)
+            if at is not None:
+                return [at[0], at[1], shape, list(v.stride()), dtype]
             return ["ext", shape, dtype]
         if isinstance(v, (list, tuple)):
             return [self._enc(x) for x in v]
         if isinstance(v, (torch.dtype, torch.device)):
             return str(v)
         return {"object": type(v).__name__}
+
+    def traced(self, name, fn, args, kw):
+        """One call into ``ssi.ops``: its entry, then the call (``call``: where tests/step_stages.py keeps the tensors' values as well)."""
+        self.entries.append([name, [self._enc(a) for a in args], {k: self._enc(x) for k, x in kw.items()}])
+        return self.call(name, fn, args, kw)
+
+    def call(self, name, fn, args, kw):
+        return fn(*args, **kw)
 
     @contextlib.contextmanager
     def scenario(self, caches=()):
@@ -74,8 +89,7 @@ class Tracer:
 
         def wrap(name, fn):
             def traced(*args, **kw):
-                self.entries.append([name, [self._enc(a) for a in args], {k: self._enc(x) for k, x in kw.items()}])
-                return fn(*args, **kw)
+                return self.traced(name, fn, args, kw)
             return traced
 
         try:
