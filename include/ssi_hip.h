@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 21 /* 21: + ssi_decode_sample (sampled decoding: temperature, top-k, top-p and a seeded Gumbel-max draw of a row's token in one launch; opt-in)
+#define SSI_ABI_VERSION 22 /* 22: + ssi_decode_select_pen, ssi_decode_sample_pen (repetition, frequency and presence penalties inside the two selection kernels; opt-in)
+                           * 21: + ssi_decode_sample (sampled decoding: temperature, top-k, top-p and a seeded Gumbel-max draw of a row's token in one launch; opt-in)
                            * 20: + ssi_attn_decode_beam, ssi_topk_logprob (beam search: decode attention through an ancestry table, the k best allowed columns of a row; opt-in)
                            * 19: + ssi_decode_select (constrained greedy decoding: the allowed argmax of a row, its log-probability and its rank in one pass; opt-in)
                            * 18: + ssi_kv_store, ssi_attn_decode (greedy generation: a K/V cache and single-query attention over it; nothing else calls them)
@@ -329,6 +330,53 @@ int ssi_decode_select(const void* logits, int64_t ld, int64_t rows, int64_t voca
 int ssi_decode_sample(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow, const uint32_t* allow_early,
                       const int32_t* n_generated, int32_t min_new, double temperature, int64_t top_k, double top_p, uint64_t seed, uint32_t step,
                       const uint32_t* sequence, int64_t* token, float* logprob, int32_t* n_kept, int dtype, void* stream);
+
+/* ssi_decode_select and ssi_decode_sample under vLLM's repetition, frequency and presence penalties (ABI v22; `apply_penalties`).  For row r
+ *   H   = the token ids of the row's prompt and of its generated tokens so far,
+ *   n_c = the number of times c occurs among the GENERATED tokens only,
+ * and the penalised value of column c, formed in fp32 from the stored value x_c wherever it is used and never stored, is
+ *   a_c = 1 for c outside H;  fl(1 / r), rounded once from the double quotient on the host, for c in H with x_c > 0;  fl(r) for c in H
+ *         otherwise (0, the negatives and NaN: vLLM's where(x > 0, x / r, x * r));
+ *   t_c = fma(f, (float)n_c, n_c > 0 ? p : 0)     (0 when n_c == 0);
+ *   y_c = fma(x_c, a_c, -t_c)                     (a column outside H is not touched: y_c is x_c),
+ * with r = repetition_penalty (finite, > 0), f = frequency_penalty and p = presence_penalty (both in [-2, 2]).  The two fmas are the only
+ * roundings.  x fl(1 / r) differs from vLLM's x / r by at most one ulp of the factor (half an ulp from rounding 1 / r, half from the product
+ * against the quotient).  With r = 1, f = 0, p = 0, y_c == x_c bit for bit.
+ * Everything that SELECTS uses y in place of x, everything that REPORTS stays on x:
+ *   ssi_decode_select_pen: token = the first maximum of y over the allowed columns (the first allowed column on a row without a number);
+ *     logprob = x[token] - lse(x) over all real columns, term for term ssi_decode_select's; rank = the token's rank in the RAW row, 0
+ *     exactly when neither the mask nor the penalties changed the choice.
+ *   ssi_decode_sample_pen: A, K, P, the masses and the score fma(y, fl(1 / T), G) are on y (penalties come before temperature, top-k and
+ *     top-p: vLLM's order); logprob stays on x at T = 1; n_kept = |P|; the Philox counter, tag and u are ssi_decode_sample's.  y is an fp32
+ *     value whatever the storage, so the radix select runs on the 32-bit key: 4 passes per threshold for bf16 logits, too.
+ * History: prompt_ids is int32 [n_prompts, ld_prompt]; row r reads the first prompt_len[line] ids (clamped to [0, ld_prompt]) of line
+ * prompt_row ? prompt_row[r] : r — the n samples of a prompt share one line, as they share its K / V.  gen_ids is int64 [rows, ld_gen] (the
+ * generation loop's output tensor); row r reads its first n_generated[r] entries (clamped to [0, ld_gen]), so n_generated is required here;
+ * it also picks allow_early as in the plain entries.  An id outside [0, vocab), or a line outside [0, n_prompts), is tested BEFORE any
+ * address is formed from it: it is skipped (the line: the whole prompt), and the row is counted ONCE in *n_bad (NULL ok) —
+ * ssi_attn_decode_beam's rule.
+ * Per workgroup (one row, 256 threads), before the first walk, in dynamic LDS: a bit mask of ceil(vocab / 32) words ("c is in H", LDS
+ * atomicOr) and an open-addressing table of Hs (token + 1, count) pairs, slot = token mod Hs, linear probing, Hs = the smallest power of two
+ * >= 2 ld_gen and >= 64 (LDS atomicCAS / atomicAdd: integer sums, no order).  A walk reads the bits of a 16-byte vector with one LDS load and
+ * looks a column up (O(1) expected) only where its bit is set.  The dynamic LDS is
+ *   ssi_decode_penalty_lds_bytes(vocab, ld_gen) = 4 ceil(vocab / 32) + 8 Hs      (20 768 bytes at vocab 133 376, ld_gen 256)
+ * and at most SSI_DECODE_PENALTY_LDS_MAX (64 KB less 8 KB for the kernels' static LDS); more is SSI_ERR_UNSUPPORTED before the launch.
+ * SSI_ERR_ARG before any launch: r not finite or <= 0; f or p not finite or outside [-2, 2]; a NULL n_generated or prompt_len; a NULL gen_ids
+ * with ld_gen > 0 or a NULL prompt_ids with ld_prompt > 0; ld_gen < 0, ld_prompt < 0, n_prompts < 1; and everything the plain entry refuses.
+ * rows == 0 launches nothing.  No workspace, no scratch; a row's outputs depend on that row, its history, the masks and the scalars only. */
+#define SSI_DECODE_PENALTY_LDS_MAX 57344
+int64_t ssi_decode_penalty_lds_bytes(int64_t vocab, int64_t ld_gen);
+int ssi_decode_select_pen(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow, const uint32_t* allow_early,
+                          const int32_t* n_generated, int32_t min_new, int64_t* token, float* logprob, int32_t* rank,
+                          const int32_t* prompt_ids, int64_t ld_prompt, const int32_t* prompt_len, const int32_t* prompt_row, int64_t n_prompts,
+                          const int64_t* gen_ids, int64_t ld_gen, double repetition_penalty, double frequency_penalty, double presence_penalty,
+                          int32_t* n_bad, int dtype, void* stream);
+int ssi_decode_sample_pen(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow, const uint32_t* allow_early,
+                          const int32_t* n_generated, int32_t min_new, double temperature, int64_t top_k, double top_p, uint64_t seed,
+                          uint32_t step, const uint32_t* sequence, int64_t* token, float* logprob, int32_t* n_kept,
+                          const int32_t* prompt_ids, int64_t ld_prompt, const int32_t* prompt_len, const int32_t* prompt_row, int64_t n_prompts,
+                          const int64_t* gen_ids, int64_t ld_gen, double repetition_penalty, double frequency_penalty, double presence_penalty,
+                          int32_t* n_bad, int dtype, void* stream);
 
 /* ---- K7  SwiGLU elementwise (torchtune FeedForward: w2(silu(w1 x) * w3 x)) ------------------------------------------ */
 /* gu: [rows, 2*inter] = [gate | up]; act[rows, inter] = silu(gate) * up */

@@ -15,7 +15,9 @@
 //               the digit at which the target is crossed;
 //   last walk   the exp-sum over all real columns, term for term ssi_decode_select's, the draw among the kept columns and their count.
 // No scratch, no workspace, no sort; a row's outputs depend on that row, the masks and the scalars only.
-#include "decode_walk.h"
+// ssi_decode_sample_pen (ABI v22) runs the same body with everything that selects on the penalised values of decode_penalty.h: fp32 numbers
+// whatever the storage, so its radix select takes the 32-bit key (4 passes per threshold for bf16, too).
+#include "decode_penalty.h"
 
 namespace {
 
@@ -31,6 +33,14 @@ template <> struct SmpKey<float> {
 template <> struct SmpKey<bf16_t> {
     static constexpr int BITS = 16;
     static __device__ __forceinline__ uint32_t of(float f) { return topk_key(f) >> 16; }
+};
+// The key of what is selected on: a penalised value is an fp32 number whatever the storage, so its key has 32 bits.
+template <typename T, typename Pen> struct SmpSel {
+    static constexpr int BITS = Pen::ON ? 32 : SmpKey<T>::BITS;
+    static __device__ __forceinline__ uint32_t of(float f) {
+        if constexpr (Pen::ON) return topk_key(f);
+        else return SmpKey<T>::of(f);
+    }
 };
 
 // exp((x - m) / T) in fixed point: sc = fl(log2 e / T), nm = fl(-m sc).  A NaN (a NaN column, or inf - inf) and -inf count 0.
@@ -66,29 +76,30 @@ struct SmpHist {
 
 // One radix pass: the histogram over the digit (key >> shift) & 255 of the allowed columns whose key is >= floor and whose higher digits
 // equal prefix (0 in the first pass, where there are none), then the suffix sums.
-template <typename T>
+template <typename T, typename Pen>
 __device__ __forceinline__ void smp_pass(const T* __restrict__ x, const uint32_t* __restrict__ mask, int nvec, int vocab, int tid, int shift,
-                                         uint32_t prefix, uint32_t floor, bool want_mass, float sc, float nm, SmpHist& h) {
+                                         uint32_t prefix, uint32_t floor, bool want_mass, float sc, float nm, SmpHist& h, const Pen& pen) {
     constexpr int VEC = Vec16<T>::N;
     __syncthreads();                                      // (the previous pass's reads of the suffix sums are over)
     h.cnt[tid] = 0u;
     h.mass[tid] = 0ull;
     __syncthreads();
     auto visit = [&](float f, bool allowed) {
-        const uint32_t key = SmpKey<T>::of(f);
+        const uint32_t key = SmpSel<T, Pen>::of(f);
         if (allowed && key >= floor && ((key >> shift) >> 8) == prefix) {
             const uint32_t d = (key >> shift) & 255u;
             atomicAdd(&h.cnt[d], 1u);
             if (want_mass) atomicAdd(&h.mass[d], smp_mass(f, sc, nm));
         }
     };
-    auto visit_vec = [&](int, const Vec16<T>& xv, uint32_t bits) {
+    auto visit_vec = [&](int c0, const Vec16<T>& xv, uint32_t bits) {
+        const PenVec<T, Pen> y(pen, c0, xv);
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) visit(xv.get(e), (bits & (1u << e)) != 0);
+        for (int e = 0; e < VEC; ++e) visit(y.get(e, xv.get(e)), (bits & (1u << e)) != 0);
     };
     if (mask) sel_walk<T, true>(x, mask, nvec, tid, visit_vec);
     else sel_walk<T, false>(x, mask, nvec, tid, visit_vec);
-    for (int c = nvec * VEC + tid; c < vocab; c += SEL_THREADS) visit(to_f32<T>(x[c]), (sel_mask_bits(mask, c) & 1u) != 0);
+    for (int c = nvec * VEC + tid; c < vocab; c += SEL_THREADS) visit(pen.y(c, to_f32<T>(x[c])), (sel_mask_bits(mask, c) & 1u) != 0);
     __syncthreads();
     uint32_t sc_ = 0u;
     unsigned long long sm_ = 0ull;
@@ -116,15 +127,16 @@ __device__ __forceinline__ int smp_find(bool ok, int tid, SmpHist& h) {
     return max(max(max(h.hi[0], h.hi[1]), max(h.hi[2], h.hi[3])), 0);
 }
 
-template <typename T>
-__global__ __launch_bounds__(SEL_THREADS) void decode_sample_kernel(const T* __restrict__ logits, int64_t ld, int vocab,
-                                                                    const uint32_t* __restrict__ allow, const uint32_t* __restrict__ allow_early,
-                                                                    const int32_t* __restrict__ n_generated, int32_t min_new, float inv_t,
-                                                                    float sc, int top_k, double top_p, uint32_t seed_lo, uint32_t seed_hi,
-                                                                    uint32_t step, const uint32_t* __restrict__ sequence,
-                                                                    int64_t* __restrict__ token, float* __restrict__ logprob,
-                                                                    int32_t* __restrict__ n_kept, int vec_ok) {
-    constexpr int VEC = Vec16<T>::N, BITS = SmpKey<T>::BITS;
+// The row body of ssi_decode_sample and of ssi_decode_sample_pen: `pen` says what a column's value is wherever the token is DRAWN (the allowed
+// maximum, the keys, the masses, the score; PenNone: the stored one); the row's maximum, the exp-sum and the log-probability stay on the
+// stored values.
+template <typename T, typename Pen>
+__device__ __forceinline__ void sample_row(const T* logits, int64_t ld, int vocab, const uint32_t* allow,
+                                           const uint32_t* allow_early, const int32_t* n_generated, int32_t min_new,
+                                           float inv_t, float sc, int top_k, double top_p, uint32_t seed_lo, uint32_t seed_hi, uint32_t step,
+                                           const uint32_t* sequence, int64_t* token, float* logprob,
+                                           int32_t* n_kept, int vec_ok, const Pen& pen) {
+    constexpr int VEC = Vec16<T>::N, BITS = SmpSel<T, Pen>::BITS;
     __shared__ float s_f[16];
     __shared__ int s_i[16];
     __shared__ SmpHist h;
@@ -140,12 +152,13 @@ __global__ __launch_bounds__(SEL_THREADS) void decode_sample_kernel(const T* __r
 
     // ---- walk 1: the maximum over all real columns and over the allowed ones (fmaxf passes a NaN by) -------------------------------
     float gm = -INFINITY, am = -INFINITY;
-    auto maxima = [&](int, const Vec16<T>& xv, uint32_t bits) {
+    auto maxima = [&](int c0, const Vec16<T>& xv, uint32_t bits) {
+        const PenVec<T, Pen> y(pen, c0, xv);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             const float f = xv.get(e);
             gm = fmaxf(gm, f);
-            am = fmaxf(am, (bits & (1u << e)) ? f : -INFINITY);
+            am = fmaxf(am, (bits & (1u << e)) ? y.get(e, f) : -INFINITY);
         }
     };
     if (mask) sel_walk<T, true>(x, mask, nvec, tid, maxima);
@@ -153,7 +166,7 @@ __global__ __launch_bounds__(SEL_THREADS) void decode_sample_kernel(const T* __r
     for (int c = tail0 + tid; c < vocab; c += SEL_THREADS) {
         const float f = to_f32<T>(x[c]);
         gm = fmaxf(gm, f);
-        am = fmaxf(am, (sel_mask_bits(mask, c) & 1u) ? f : -INFINITY);
+        am = fmaxf(am, (sel_mask_bits(mask, c) & 1u) ? pen.y(c, f) : -INFINITY);
     }
     gm = wave_max(gm);
     am = wave_max(am);
@@ -205,7 +218,7 @@ __global__ __launch_bounds__(SEL_THREADS) void decode_sample_kernel(const T* __r
         if (top_k > 0) {
             uint32_t prefix = 0u, target = (uint32_t)top_k;
             for (int shift = BITS - 8; shift >= 0; shift -= 8) {
-                smp_pass<T>(x, mask, nvec, vocab, tid, shift, prefix, 0u, by_p, sc, nm, h);
+                smp_pass<T>(x, mask, nvec, vocab, tid, shift, prefix, 0u, by_p, sc, nm, h, pen);
                 if (shift == BITS - 8 && (uint32_t)top_k >= h.ccnt[0]) {      // top_k >= |A|: K = A
                     z = h.cmass[0];
                     prefix = 0u;
@@ -224,7 +237,7 @@ __global__ __launch_bounds__(SEL_THREADS) void decode_sample_kernel(const T* __r
             uint32_t prefix = 0u;
             unsigned long long target = 0ull;
             for (int shift = BITS - 8; shift >= 0; shift -= 8) {
-                smp_pass<T>(x, mask, nvec, vocab, tid, shift, prefix, floor, true, sc, nm, h);
+                smp_pass<T>(x, mask, nvec, vocab, tid, shift, prefix, floor, true, sc, nm, h, pen);
                 if (shift == BITS - 8) {
                     if (!have_z) z = h.cmass[0];
                     target = (unsigned long long)ceil(top_p * (double)z);
@@ -260,11 +273,12 @@ __global__ __launch_bounds__(SEL_THREADS) void decode_sample_kernel(const T* __r
     };
     auto last_vec = [&](int c0, const Vec16<T>& xv, uint32_t bits) {
         uint32_t kb = 0u;
+        const PenVec<T, Pen> y(pen, c0, xv);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             const float f = xv.get(e);
             s += __builtin_amdgcn_exp2f(__builtin_fmaf(f, SEL_LOG2E, nm_all));
-            kb |= (uint32_t)(drawn & ((bits & (1u << e)) != 0) & (SmpKey<T>::of(f) >= tau)) << e;
+            kb |= (uint32_t)(drawn & ((bits & (1u << e)) != 0) & (SmpSel<T, Pen>::of(y.get(e, f)) >= tau)) << e;
         }
         kept += __builtin_popcount(kb);
         if (kb && ((c0 / (VEC * SEL_THREADS)) & 3) == 0)  // every fourth round, where something is kept: the best score reached so far, given and taken
@@ -275,20 +289,22 @@ __global__ __launch_bounds__(SEL_THREADS) void decode_sample_kernel(const T* __r
                 const Philox4 p = philox4x32_10((uint32_t)(c0 >> 2) + q, step, seq, SMP_TAG, seed_lo, seed_hi);
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    if (kb & (1u << (4 * q + j))) draw(c0 + 4 * q + j, xv.get(4 * q + j), p.w[j]);
+                    if (kb & (1u << (4 * q + j))) draw(c0 + 4 * q + j, y.get(4 * q + j, xv.get(4 * q + j)), p.w[j]);
             }
         }
     };
-    if (mask) sel_walk<T, true>(x, mask, nvec, tid, last_vec);
-    else sel_walk<T, false>(x, mask, nvec, tid, last_vec);
+    constexpr int LAST_UNROLL = Pen::ON ? SEL_UNROLL / 2 : SEL_UNROLL;      // (the penalised draw holds y beside x: fewer vectors in flight, no spill)
+    if (mask) sel_walk<T, true, LAST_UNROLL>(x, mask, nvec, tid, last_vec);
+    else sel_walk<T, false, LAST_UNROLL>(x, mask, nvec, tid, last_vec);
     for (int c = tail0 + tid; c < vocab; c += SEL_THREADS) {
         const float f = to_f32<T>(x[c]);
         s += __builtin_amdgcn_exp2f(__builtin_fmaf(f, SEL_LOG2E, nm_all));
-        if (drawn && (sel_mask_bits(mask, c) & 1u) && SmpKey<T>::of(f) >= tau) {
+        const float yc = pen.y(c, f);
+        if (drawn && (sel_mask_bits(mask, c) & 1u) && SmpSel<T, Pen>::of(yc) >= tau) {
             ++kept;
             const Philox4 p = philox4x32_10((uint32_t)(c >> 2), step, seq, SMP_TAG, seed_lo, seed_hi);
             const uint32_t word = (c & 3) == 0 ? p.w[0] : (c & 3) == 1 ? p.w[1] : (c & 3) == 2 ? p.w[2] : p.w[3];
-            draw(c, f, word);
+            draw(c, yc, word);
         }
     }
     if (drawn) {
@@ -326,6 +342,33 @@ __global__ __launch_bounds__(SEL_THREADS) void decode_sample_kernel(const T* __r
     }
 }
 
+template <typename T>
+__global__ __launch_bounds__(SEL_THREADS) void decode_sample_kernel(const T* __restrict__ logits, int64_t ld, int vocab,
+                                                                    const uint32_t* __restrict__ allow, const uint32_t* __restrict__ allow_early,
+                                                                    const int32_t* __restrict__ n_generated, int32_t min_new, float inv_t,
+                                                                    float sc, int top_k, double top_p, uint32_t seed_lo, uint32_t seed_hi,
+                                                                    uint32_t step, const uint32_t* __restrict__ sequence,
+                                                                    int64_t* __restrict__ token, float* __restrict__ logprob,
+                                                                    int32_t* __restrict__ n_kept, int vec_ok) {
+    sample_row<T>(logits, ld, vocab, allow, allow_early, n_generated, min_new, inv_t, sc, top_k, top_p, seed_lo, seed_hi, step, sequence, token,
+                  logprob, n_kept, vec_ok, PenNone{});
+}
+
+// ssi_decode_sample_pen (ABI v22): the row's history is built in dynamic LDS first (decode_penalty.h), then the same body draws on y.
+template <typename T>
+__global__ __launch_bounds__(SEL_THREADS) void sample_pen_kernel(const T* __restrict__ logits, int64_t ld, int vocab,
+                                                                 const uint32_t* __restrict__ allow, const uint32_t* __restrict__ allow_early,
+                                                                 const int32_t* __restrict__ n_generated, int32_t min_new, float inv_t, float sc,
+                                                                 int top_k, double top_p, uint32_t seed_lo, uint32_t seed_hi, uint32_t step,
+                                                                 const uint32_t* __restrict__ sequence, int64_t* __restrict__ token,
+                                                                 float* __restrict__ logprob, int32_t* __restrict__ n_kept, int vec_ok,
+                                                                 PenArgs pa) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t pen_lds[];
+    const PenOn pen = pen_build(pa, n_generated, blockIdx.x, vocab, threadIdx.x, pen_lds);
+    sample_row<T>(logits, ld, vocab, allow, allow_early, n_generated, min_new, inv_t, sc, top_k, top_p, seed_lo, seed_hi, step, sequence, token,
+                  logprob, n_kept, vec_ok, pen);
+}
+
 }  // namespace
 
 extern "C" int ssi_decode_sample(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow, const uint32_t* allow_early,
@@ -345,6 +388,34 @@ extern "C" int ssi_decode_sample(const void* logits, int64_t ld, int64_t rows, i
     SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(decode_sample_kernel<T>, dim3((unsigned)rows), dim3(SEL_THREADS), 0, (hipStream_t)stream,
                                                  (const T*)logits, ld, (int)vocab, allow, allow_early, n_generated, min_new, inv_t, sc, k, top_p,
                                                  (uint32_t)seed, (uint32_t)(seed >> 32), step, sequence, token, logprob, n_kept, vec_ok));
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+extern "C" int ssi_decode_sample_pen(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow, const uint32_t* allow_early,
+                                     const int32_t* n_generated, int32_t min_new, double temperature, int64_t top_k, double top_p, uint64_t seed,
+                                     uint32_t step, const uint32_t* sequence, int64_t* token, float* logprob, int32_t* n_kept,
+                                     const int32_t* prompt_ids, int64_t ld_prompt, const int32_t* prompt_len, const int32_t* prompt_row,
+                                     int64_t n_prompts, const int64_t* gen_ids, int64_t ld_gen, double repetition_penalty, double frequency_penalty,
+                                     double presence_penalty, int32_t* n_bad, int dtype, void* stream) {
+    SSI_CHECK_ARG(rows >= 0 && rows < (1LL << 31) && (dtype == SSI_F32 || dtype == SSI_BF16));
+    SSI_CHECK_ARG(logits && token && vocab >= 1 && ld >= vocab && vocab < (1LL << 31) && min_new >= 0);
+    SSI_CHECK_ARG(temperature > 0.0 && temperature < (double)INFINITY);
+    SSI_CHECK_ARG(top_p > 0.0 && top_p <= 1.0);
+    SSI_CHECK_ARG(sequence != nullptr);
+    PenArgs pa;
+    const int rc = pen_check(pa, vocab, n_generated, prompt_ids, ld_prompt, prompt_len, prompt_row, n_prompts, gen_ids, ld_gen,
+                             repetition_penalty, frequency_penalty, presence_penalty, n_bad);
+    if (rc != SSI_OK) return rc;
+    if (rows == 0) return SSI_OK;
+    const int64_t esize = dtype == SSI_BF16 ? 2 : 4;
+    const int vec_ok = ((uintptr_t)logits & 15) == 0 && (ld * esize) % 16 == 0;
+    const int k = top_k <= 0 || top_k >= vocab ? 0 : (int)top_k;
+    const float inv_t = (float)(1.0 / temperature), sc = (float)(1.44269504088896340736 / temperature);
+    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(sample_pen_kernel<T>, dim3((unsigned)rows), dim3(SEL_THREADS),
+                                                 (size_t)pen_lds_bytes(vocab, ld_gen), (hipStream_t)stream, (const T*)logits, ld, (int)vocab, allow,
+                                                 allow_early, n_generated, min_new, inv_t, sc, k, top_p, (uint32_t)seed, (uint32_t)(seed >> 32), step,
+                                                 sequence, token, logprob, n_kept, vec_ok, pa));
     SSI_LAUNCH_CHECK();
     return SSI_OK;
 }

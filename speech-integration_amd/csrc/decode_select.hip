@@ -9,16 +9,18 @@
 // its columns in rising order, so "take on >" keeps the first occurrence; threads are merged by a fixed xor tree and the four waves in the
 // order 0, 1, 2, 3 with the lower column winning a tie.  A row's result depends on that row and the masks only.
 // NaN: no comparison with a NaN holds, so a NaN column is neither the maximum nor chosen while any allowed column holds a number.
-#include "decode_walk.h"
+// ssi_decode_select_pen (ABI v22) runs the same body with the token chosen on the penalised values of decode_penalty.h.
+#include "decode_penalty.h"
 
 namespace {
 
-template <typename T>
-__global__ __launch_bounds__(SEL_THREADS) void decode_select_kernel(const T* __restrict__ logits, int64_t ld, int vocab,
-                                                                    const uint32_t* __restrict__ allow, const uint32_t* __restrict__ allow_early,
-                                                                    const int32_t* __restrict__ n_generated, int32_t min_new,
-                                                                    int64_t* __restrict__ token, float* __restrict__ logprob,
-                                                                    int32_t* __restrict__ rank, int vec_ok) {
+// The row body of ssi_decode_select and of ssi_decode_select_pen: `pen` says what a column's value is where the token is CHOSEN (PenNone: the
+// stored one); the maximum, the exp-sum and the rank stay on the stored values.
+template <typename T, typename Pen>
+__device__ __forceinline__ void select_row(const T* logits, int64_t ld, int vocab, const uint32_t* allow,
+                                           const uint32_t* allow_early, const int32_t* n_generated, int32_t min_new,
+                                           int64_t* token, float* logprob, int32_t* rank, int vec_ok,
+                                           const Pen& pen) {
     constexpr int VEC = Vec16<T>::N;
     __shared__ float s_f[16];
     __shared__ int s_i[16];
@@ -34,20 +36,23 @@ __global__ __launch_bounds__(SEL_THREADS) void decode_select_kernel(const T* __r
     float gm = -INFINITY, bv = -INFINITY;
     int bi = -1;
     auto best = [&](int c0, const Vec16<T>& xv, uint32_t bits) {
+        const PenVec<T, Pen> y(pen, c0, xv);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {                   // selects, no branches: the compiler otherwise jumps around every element
             const float f = xv.get(e);
             gm = fmaxf(gm, f);
-            const bool take = ((bits & (1u << e)) != 0) & (f > bv);
-            bv = take ? f : bv;
+            const float v = y.get(e, f);
+            const bool take = ((bits & (1u << e)) != 0) & (v > bv);
+            bv = take ? v : bv;
             bi = take ? c0 + e : bi;
         }
     };
     if (mask) sel_walk<T, true>(x, mask, nvec, tid, best);
     else sel_walk<T, false>(x, mask, nvec, tid, best);
     for (int c = tail0 + tid; c < vocab; c += SEL_THREADS) {
-        const float f = to_f32<T>(x[c]);
-        gm = fmaxf(gm, f);
+        const float xc = to_f32<T>(x[c]);
+        gm = fmaxf(gm, xc);
+        const float f = pen.y(c, xc);
         const bool take = ((sel_mask_bits(mask, c) & 1u) != 0) & (f > bv);
         bv = take ? f : bv;
         bi = take ? c : bi;
@@ -136,6 +141,27 @@ __global__ __launch_bounds__(SEL_THREADS) void decode_select_kernel(const T* __r
         if (logprob) logprob[r] = xt - (gm + logf(s));
         if (rank) rank[r] = before;
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(SEL_THREADS) void decode_select_kernel(const T* __restrict__ logits, int64_t ld, int vocab,
+                                                                    const uint32_t* __restrict__ allow, const uint32_t* __restrict__ allow_early,
+                                                                    const int32_t* __restrict__ n_generated, int32_t min_new,
+                                                                    int64_t* __restrict__ token, float* __restrict__ logprob,
+                                                                    int32_t* __restrict__ rank, int vec_ok) {
+    select_row<T>(logits, ld, vocab, allow, allow_early, n_generated, min_new, token, logprob, rank, vec_ok, PenNone{});
+}
+
+// ssi_decode_select_pen (ABI v22): the row's history is built in dynamic LDS first (decode_penalty.h), then the same body chooses on y.
+template <typename T>
+__global__ __launch_bounds__(SEL_THREADS) void select_pen_kernel(const T* __restrict__ logits, int64_t ld, int vocab,
+                                                                 const uint32_t* __restrict__ allow, const uint32_t* __restrict__ allow_early,
+                                                                 const int32_t* __restrict__ n_generated, int32_t min_new,
+                                                                 int64_t* __restrict__ token, float* __restrict__ logprob,
+                                                                 int32_t* __restrict__ rank, int vec_ok, PenArgs pa) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t pen_lds[];
+    const PenOn pen = pen_build(pa, n_generated, blockIdx.x, vocab, threadIdx.x, pen_lds);
+    select_row<T>(logits, ld, vocab, allow, allow_early, n_generated, min_new, token, logprob, rank, vec_ok, pen);
 }
 
 // =====================================================================================================================
@@ -296,6 +322,31 @@ extern "C" int ssi_decode_select(const void* logits, int64_t ld, int64_t rows, i
     SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(decode_select_kernel<T>, dim3((unsigned)rows), dim3(SEL_THREADS), 0, (hipStream_t)stream,
                                                  (const T*)logits, ld, (int)vocab, allow, allow_early, n_generated, min_new, token, logprob, rank,
                                                  vec_ok));
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+extern "C" int64_t ssi_decode_penalty_lds_bytes(int64_t vocab, int64_t ld_gen) {
+    return vocab >= 1 && vocab < (1LL << 31) && ld_gen >= 0 && ld_gen < (1LL << 30) ? pen_lds_bytes(vocab, ld_gen) : -1;
+}
+
+extern "C" int ssi_decode_select_pen(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow, const uint32_t* allow_early,
+                                     const int32_t* n_generated, int32_t min_new, int64_t* token, float* logprob, int32_t* rank,
+                                     const int32_t* prompt_ids, int64_t ld_prompt, const int32_t* prompt_len, const int32_t* prompt_row,
+                                     int64_t n_prompts, const int64_t* gen_ids, int64_t ld_gen, double repetition_penalty, double frequency_penalty,
+                                     double presence_penalty, int32_t* n_bad, int dtype, void* stream) {
+    SSI_CHECK_ARG(rows >= 0 && rows < (1LL << 31) && (dtype == SSI_F32 || dtype == SSI_BF16));
+    SSI_CHECK_ARG(logits && token && vocab >= 1 && ld >= vocab && vocab < (1LL << 31) && min_new >= 0);
+    PenArgs pa;
+    const int rc = pen_check(pa, vocab, n_generated, prompt_ids, ld_prompt, prompt_len, prompt_row, n_prompts, gen_ids, ld_gen,
+                             repetition_penalty, frequency_penalty, presence_penalty, n_bad);
+    if (rc != SSI_OK) return rc;
+    if (rows == 0) return SSI_OK;
+    const int64_t esize = dtype == SSI_BF16 ? 2 : 4;
+    const int vec_ok = ((uintptr_t)logits & 15) == 0 && (ld * esize) % 16 == 0;
+    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(select_pen_kernel<T>, dim3((unsigned)rows), dim3(SEL_THREADS),
+                                                 (size_t)pen_lds_bytes(vocab, ld_gen), (hipStream_t)stream, (const T*)logits, ld, (int)vocab, allow,
+                                                 allow_early, n_generated, min_new, token, logprob, rank, vec_ok, pa));
     SSI_LAUNCH_CHECK();
     return SSI_OK;
 }

@@ -24,15 +24,15 @@ __device__ __forceinline__ uint32_t sel_mask_bits(const uint32_t* __restrict__ m
 // and they are UNCONDITIONAL, their index clamped to the last vector: behind a guard hipcc waits for every load in flight before the next
 // use.  Whole trips run without a predicate; the last, partial one tests v < nvec around work that touches no memory.  f(first column,
 // vector, mask bits from that column on) sees a thread's vectors in rising order.
-template <typename T, bool MASKED, typename F>
+template <typename T, bool MASKED, int UNROLL = SEL_UNROLL, typename F>
 __device__ __forceinline__ void sel_walk(const T* __restrict__ x, const uint32_t* __restrict__ mask, int nvec, int tid, F&& f) {
-    constexpr int VEC = Vec16<T>::N, TRIP = SEL_THREADS * SEL_UNROLL;
+    constexpr int VEC = Vec16<T>::N, TRIP = SEL_THREADS * UNROLL;
     if (nvec <= 0) return;
-    Vec16<T> cur[SEL_UNROLL], nxt[SEL_UNROLL];
-    uint32_t cur_bits[SEL_UNROLL], nxt_bits[SEL_UNROLL];
+    Vec16<T> cur[UNROLL], nxt[UNROLL];
+    uint32_t cur_bits[UNROLL], nxt_bits[UNROLL];
     auto fetch = [&](Vec16<T>* q, uint32_t* b, int v0) {
 #pragma unroll
-        for (int u = 0; u < SEL_UNROLL; ++u) {
+        for (int u = 0; u < UNROLL; ++u) {
             const int v = min(v0 + u * SEL_THREADS, nvec - 1);
             q[u] = load16<T>(x + (int64_t)v * VEC);
             b[u] = MASKED ? mask[(v * VEC) >> 5] >> ((v * VEC) & 31) : 0xffffffffu;
@@ -43,15 +43,15 @@ __device__ __forceinline__ void sel_walk(const T* __restrict__ x, const uint32_t
     for (int t = nvec / TRIP; t > 0; --t, v0 += TRIP) {
         fetch(nxt, nxt_bits, v0 + TRIP);
 #pragma unroll
-        for (int u = 0; u < SEL_UNROLL; ++u) f((v0 + u * SEL_THREADS) * VEC, cur[u], cur_bits[u]);
+        for (int u = 0; u < UNROLL; ++u) f((v0 + u * SEL_THREADS) * VEC, cur[u], cur_bits[u]);
 #pragma unroll
-        for (int u = 0; u < SEL_UNROLL; ++u) {
+        for (int u = 0; u < UNROLL; ++u) {
             cur[u] = nxt[u];
             cur_bits[u] = nxt_bits[u];
         }
     }
 #pragma unroll
-    for (int u = 0; u < SEL_UNROLL; ++u) {
+    for (int u = 0; u < UNROLL; ++u) {
         const int v = v0 + u * SEL_THREADS;
         if (v < nvec) f(v * VEC, cur[u], cur_bits[u]);
     }

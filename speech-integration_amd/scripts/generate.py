@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Generation entry point, greedy, (gen.beam_width > 1) beam search or (gen.sample=true) sampling (the reference's scripts/generate.py runs vLLM): a generations JSONL the reference's scripts/wer.py reads.
+"""Generation entry point, greedy, (gen.beam_width > 1) beam search or (gen.sample=true) sampling, either of the outer two under (gen.penalties=true) repetition, frequency and presence penalties (the reference's scripts/generate.py runs vLLM): a generations JSONL the reference's scripts/wer.py reads.
     python scripts/generate.py speech.n_dsus=5000 gen.input=prompts.jsonl gen.output_dir=out [key=value ...]
     python scripts/generate.py speech.n_dsus=5000 data=sft/<dataset> gen.split=dev gen.output_dir=out
 """
@@ -15,7 +15,7 @@ try:  # real Hydra if the environment has it, else the built-in composer with th
 except ImportError:
     from ssi.config import main as main_decorator
 
-from ssi.generate import check_greedy, check_sampling, generate_file
+from ssi.generate import check_greedy, check_penalties, check_sampling, generate_file
 
 LOGGER = logging.getLogger(__name__)
 
@@ -50,9 +50,15 @@ def main(cfg):
     sampled = bool(cfg.gen.get("sample") or False)          # everything below: before anything is loaded
     if sampled and int(cfg.gen.get("beam_width") or 1) != 1:
         raise ValueError("gen.sample=true together with gen.beam_width > 1: sampling inside beam search is not built")
-    draw = dict(check_sampling(cfg.sampling_params), sample=True, seed=int(cfg.gen.get("seed") or 0)) if sampled else {}
+    penalties, params = {}, cfg.sampling_params
+    if bool(cfg.gen.get("penalties") or False):              # without it every refusal of a penalty below is what it was
+        if int(cfg.gen.get("beam_width") or 1) != 1:
+            raise ValueError("gen.penalties=true together with gen.beam_width > 1: beam search takes no penalties")
+        penalties = check_penalties(params)
+        params = {k: params[k] for k in params if k not in penalties}
+    draw = dict(check_sampling(params), sample=True, seed=int(cfg.gen.get("seed") or 0)) if sampled else {}
     if not sampled:
-        check_greedy(cfg.sampling_params)
+        check_greedy(params)
     from ssi.model import get_device, get_dtype
     from ssi.train_utils import resolve_n_dsus
     from ssi.trainer import Trainer
@@ -77,6 +83,7 @@ def main(cfg):
         constraints.update(beam_width=int(cfg.gen.beam_width), length_penalty=float(cfg.gen.get("length_penalty", 1.0)),
                            n_best=int(cfg.gen.get("n_best", 1)))
     constraints.update(draw)          # gen.sample: the sampling_params that check_sampling let through, and gen.seed
+    constraints.update(penalties)     # gen.penalties: the three values check_penalties let through
     summary = generate_file(t.model, t.tokenizer, None if prompts is not None else str(cfg.gen.input), out_path,
                             max_new_tokens=int(cfg.sampling_params.max_tokens), stop_token_ids=None if stop is None else [int(s) for s in stop],
                             tokenizer_decoding={k: cfg.tokenizer_decoding[k] for k in cfg.tokenizer_decoding}, prompts=prompts, ids=ids,

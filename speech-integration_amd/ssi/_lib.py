@@ -20,7 +20,8 @@ SSI_F32, SSI_BF16 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 IMPL_AUTO, IMPL_GENERIC, IMPL_MFMA, IMPL_MFMA_WG8 = 0, 1, 2, 3
 TILES_STATIC, TILES_DYNAMIC = 0, 1
-ABI_VERSION = 21
+ABI_VERSION = 22
+DECODE_PENALTY_LDS_MAX = 57344
 ADAMW_MAX_SEGS = 128
 ATTN_KERNEL_DQ, ATTN_KERNEL_DKV = 0, 1
 ATTN_MODE_AUTO, ATTN_MODE_OLD, ATTN_MODE_NEW, ATTN_MODE_NO_HEAD_SPLIT = 0, 1, 2, 3
@@ -64,6 +65,11 @@ PROTOTYPES = {
     "ssi_decode_select": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, c_int32, _P, _P, _P, c_int, _P]),
     "ssi_decode_sample": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, c_int32, c_double, c_int64, c_double, c_uint64, c_uint32, _P, _P, _P, _P,
                                   c_int, _P]),
+    "ssi_decode_penalty_lds_bytes": (c_int64, [c_int64, c_int64]),
+    "ssi_decode_select_pen": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, c_int32, _P, _P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64,
+                                      c_double, c_double, c_double, _P, c_int, _P]),
+    "ssi_decode_sample_pen": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, c_int32, c_double, c_int64, c_double, c_uint64, c_uint32, _P, _P, _P,
+                                      _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_double, c_double, c_double, _P, c_int, _P]),
     "ssi_attn_decode_beam": (c_int, [_P, c_int64, _P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_int64, _P, _P, c_int64,
                                      c_int, c_int, c_int, _P, c_int, _P]),
     "ssi_topk_logprob": (c_int, [_P, c_int64, c_int64, c_int64, c_int, _P, c_int64, _P, _P, _P, c_int, _P]),

@@ -24,7 +24,12 @@ Sampling (``sample``; ``gen.sample`` in ``conf/generate.yaml``): the token of a 
 never enters the bits.  ``n = 1`` runs ``generate``'s loop; ``n`` in 2..8 runs a prompt's samples as rows of ``decode_step_beam`` with the identity
 ancestry, so the prompt is prefilled once and its K / V are shared as beams share them.
 
-Out of scope: repetition, presence and frequency penalties, per-request sampling parameters within one launch, ``n > 8`` and ``best_of``, sampling
+Penalties (vLLM's ``repetition_penalty``, ``frequency_penalty`` and ``presence_penalty``; arguments of ``generate`` and ``sample``,
+``gen.penalties`` in ``conf/generate.yaml``): with any of them off its neutral value the token of a step comes from ``ssi_decode_select_pen`` /
+``ssi_decode_sample_pen``, which choose on the penalised row — built in the kernel from the group's prompt table and the loop's own output
+tensor, never stored — and report the log-probability (and the rank) of the raw one.  With all three neutral nothing of this runs.
+
+Out of scope: per-request sampling parameters within one launch, ``n > 8`` and ``best_of``, sampling
 inside beam search, ``beam_width > 8``, sharing the prompt's K / V read among a prompt's beams, beam
 search under data parallelism, continuous batching (refilling freed slots), paged caches, generation under data parallelism, a skinny GEMM for
 small batches, and WER itself (its text normaliser is the reference's dependency; the JSONL written here is what its ``wer.py`` reads)."""
@@ -46,7 +51,7 @@ from .constants import CROSS_ENTROPY_IGNORE_IDX
 LOGGER = logging.getLogger(__name__)
 
 __all__ = ["Generation", "READBACK_EVERY", "MAX_BEAM_WIDTH", "MAX_SAMPLES", "plan_groups", "allowed_mask", "generate", "beam_search", "sample",
-           "generate_file", "output_record", "check_greedy", "check_sampling"]
+           "generate_file", "output_record", "check_greedy", "check_sampling", "check_penalties"]
 
 READBACK_EVERY = 8    # decode steps between two read-backs of "has every row of the group finished?"
 MAX_BEAM_WIDTH = 8    # the k of ssi_topk_logprob
@@ -58,7 +63,8 @@ class Generation:
     """``token_ids``: the generated tokens, INCLUDING the stop token that ended it; ``finish_reason``: ``"stop"`` or ``"length"``;
     ``stop_reason``: the stop token's id, or None; ``cumulative_logprob``: the sum of the chosen tokens' log-probabilities (natural log;
     None without ``logprobs=True``); ``prompt_len``: tokens in the prompt; ``n_constrained``: the steps at which the constraint changed the
-    choice (the chosen token was not the row's unconstrained first), None when no constraint was given; ``score`` (``beam_search`` only):
+    choice (the chosen token was not the row's unconstrained first), None when no constraint was given — penalties count there: under
+    ``generate`` with a penalty set it is the steps at which the mask OR the penalties changed the choice; ``score`` (``beam_search`` only):
     ``cumulative_logprob / len(token_ids) ** length_penalty``, what the hypotheses of a prompt are ordered by; ``n_kept_mean`` (``sample``
     only): the mean over the generated tokens of the size of the set each was drawn from (after the mask, top-k and top-p)."""
     token_ids: list[int]
@@ -141,9 +147,42 @@ def _constraint_masks(vocab_size: int, allowed_token_ids, min_new_tokens: int, s
     return allow | stops, early
 
 
+@dataclass
+class _Penalty:
+    r: float
+    f: float
+    p: float
+
+
+def _check_penalties(repetition_penalty, frequency_penalty, presence_penalty) -> _Penalty | None:
+    """The ranges of the three penalties (``ValueError``): ``repetition_penalty`` finite and > 0, the other two in [-2, 2].  None when all
+    three are neutral (1, 0, 0): nothing of the penalised path then runs."""
+    def number(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or abs(v) == float("inf"):
+            raise ValueError(f"{name} = {v!r}: a finite number")
+        return float(v)
+    r, f, p = number("repetition_penalty", repetition_penalty), number("frequency_penalty", frequency_penalty), number("presence_penalty", presence_penalty)
+    if not r > 0.0:
+        raise ValueError(f"repetition_penalty = {r!r}: a finite number > 0")
+    for name, v in (("frequency_penalty", f), ("presence_penalty", p)):
+        if not -2.0 <= v <= 2.0:
+            raise ValueError(f"{name} = {v!r}: a number in [-2, 2]")
+    return None if (r, f, p) == (1.0, 0.0, 0.0) else _Penalty(r, f, p)
+
+
+def _prompt_table(seqs: list[Tensor], dev) -> tuple[Tensor, Tensor]:
+    """A group's prompts as the penalised kernels read them: int32 ``[len(seqs), longest]`` (zero-filled) and the int32 lengths."""
+    lens = [int(s.numel()) for s in seqs]
+    table = torch.zeros((len(seqs), max(lens)), dtype=torch.int32)
+    for i, s in enumerate(seqs):
+        table[i, :lens[i]] = s.to(torch.int32)
+    return table.to(dev), torch.tensor(lens, dtype=torch.int32).to(dev)
+
+
 def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_ids: Sequence[int], pad_id: int, batch_size: int = 256,
              logprobs: bool = False, device: torch.device | str | None = None, allowed_token_ids: Sequence[int] | Tensor | None = None,
-             min_new_tokens: int = 0) -> list[Generation]:
+             min_new_tokens: int = 0, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
+             presence_penalty: float = 0.0) -> list[Generation]:
     """Greedy continuation of every prompt (1-D integer sequences), results in INPUT order.  The token of a step is ``argmax`` over the real
     columns ``[:, :vocab_size]`` of the step's logits, with torch's first-occurrence rule.  ``pad_id`` fills the rows that have finished.
     ``logprobs=True``: the forward-only ``ops.ce_fwd_metrics`` runs on the step's logits with the chosen token as label, which gives its
@@ -152,10 +191,15 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
     a row's first so many tokens): the token of a step, the first included, is ``ops.decode_select``'s — the first maximum among the allowed
     columns — and with ``logprobs=True`` the sum is of that kernel's log-probabilities, which are over ALL columns (``ops.ce_fwd_metrics`` is
     not launched); the self-check is "every live row's token is >= 0 and allowed".  With neither, nothing of the above runs.
-    Refused before any launch (``ValueError``): an empty prompt, a prompt that with ``max_new_tokens`` exceeds the model's RoPE table or
+    ``repetition_penalty``, ``frequency_penalty``, ``presence_penalty`` (vLLM's; neutral at 1, 0, 0): with any of them set the token of a step
+    is ``ops.decode_select_pen``'s — the first allowed maximum of the penalised row, with NULL masks when there is no constraint — in place of
+    ``argmax`` and the cross-entropy launch; the log-probabilities stay those of the raw row, and ``n_constrained`` counts the steps whose
+    token was not the raw row's first.  An id the kernel had to skip (outside the vocabulary) is a ``RuntimeError`` at the end of the group.
+    Refused before any launch (``ValueError``): a penalty outside its range, an empty prompt, a prompt that with ``max_new_tokens`` exceeds the model's RoPE table or
     ``max_seq_len``; ``min_new_tokens < 0``, an allowed or stop id outside the vocabulary (under a constraint), an empty allowed set,
     ``min_new_tokens > 0`` with nothing allowed besides the stop tokens."""
     max_new_tokens, batch_size, min_new_tokens = int(max_new_tokens), int(batch_size), int(min_new_tokens)
+    pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
     masks = _constraint_masks(int(model.vocab_size), allowed_token_ids, min_new_tokens, stop_token_ids)
     if max_new_tokens < 1:
         raise ValueError(f"max_new_tokens must be >= 1 (got {max_new_tokens})")
@@ -182,7 +226,8 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
                 con = _Constraint(allow, _mask_words(masks[0]).to(device), early if min_new_tokens else None,
                                   _mask_words(masks[1]).to(device) if min_new_tokens else None, min_new_tokens)
             for group in groups:
-                for i, g in zip(group, _generate_group(model, cache, [seqs[i] for i in group], max_new_tokens, stop, int(pad_id), logprobs, con)):
+                for i, g in zip(group, _generate_group(model, cache, [seqs[i] for i in group], max_new_tokens, stop, int(pad_id), logprobs, con,
+                                                          *(() if pen is None else (pen,)))):
                     results[i] = g
     finally:
         if was_training:
@@ -191,31 +236,42 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
 
 
 def _generate_group(model, cache, seqs: list[Tensor], max_new_tokens: int, stop: Tensor, pad_id: int, logprobs: bool,
-                    con: _Constraint | None = None) -> list[Generation]:
+                    con: _Constraint | None = None, pen: _Penalty | None = None) -> list[Generation]:
     n, dev, V = len(seqs), model.device, model.vocab_size
+    chosen = con is not None or pen is not None       # the token comes from a selection kernel, not from argmax
     logits = model.prefill(cache, seqs, max_new_tokens=max_new_tokens)
     alive = torch.ones(n, dtype=torch.bool, device=dev)
     own_slot = torch.arange(n, dtype=torch.int32, device=dev)
     no_slot = torch.full_like(own_slot, -1)
     out = torch.full((n, max_new_tokens), pad_id, dtype=torch.int64, device=dev)
-    n_gen = torch.zeros(n, dtype=torch.int64 if con is None else torch.int32, device=dev)     # (int32: what ssi_decode_select reads)
+    n_gen = torch.zeros(n, dtype=torch.int32 if chosen else torch.int64, device=dev)     # (int32: what ssi_decode_select reads)
     stop_tok = torch.full((n,), -1, dtype=torch.int64, device=dev)
     cum = torch.zeros(n, dtype=torch.float64, device=dev)
     not_top = torch.zeros(1, dtype=torch.int64, device=dev)
-    if con is not None:
+    if chosen:
         tok = torch.empty(n, dtype=torch.int64, device=dev)
         row_lp = torch.empty(n, dtype=torch.float32, device=dev) if logprobs else None
         row_rank = torch.empty(n, dtype=torch.int32, device=dev)
         n_con = torch.zeros(n, dtype=torch.int64, device=dev)
+        if pen is not None:
+            ptab, plen = _prompt_table(seqs, dev)
+            n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
     elif logprobs:
         row_loss, row_nll = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
         row_rank = torch.empty(n, dtype=torch.int32, device=dev)
     for t in range(max_new_tokens):
-        if con is not None:
-            ops.decode_select(logits, V, tok, row_lp, row_rank, allow=con.allow_words, allow_early=con.early_words,
-                              n_generated=n_gen if con.min_new else None, min_new=con.min_new)
+        if chosen:
+            masks = {} if con is None else dict(allow=con.allow_words, allow_early=con.early_words, min_new=con.min_new)
+            if pen is None:
+                ops.decode_select(logits, V, tok, row_lp, row_rank, n_generated=n_gen if con.min_new else None, **masks)
+            else:
+                ops.decode_select_pen(logits, V, tok, row_lp, row_rank, prompt_ids=ptab, prompt_len=plen, gen_ids=out, n_generated=n_gen,
+                                      repetition_penalty=pen.r, frequency_penalty=pen.f, presence_penalty=pen.p, n_bad=n_bad, **masks)
             at = tok.clamp(min=0)
-            ok = con.allow[at] if con.early is None else torch.where(n_gen < con.min_new, con.early[at], con.allow[at])
+            if con is None:
+                ok = torch.ones_like(alive)
+            else:
+                ok = con.allow[at] if con.early is None else torch.where(n_gen < con.min_new, con.early[at], con.allow[at])
             not_top += (alive & ((tok < 0) | ~ok)).sum()    # the self-check: the chosen token exists and is allowed
             n_con += alive & (row_rank != 0)
             if logprobs:
@@ -223,7 +279,7 @@ def _generate_group(model, cache, seqs: list[Tensor], max_new_tokens: int, stop:
             tok = at.clone()                                # (a new tensor per step, as argmax gives; never a negative embedding index)
         else:
             tok = logits[:, :V].argmax(dim=-1)
-        if con is None and logprobs:
+        if not chosen and logprobs:
             labels = torch.where(alive, tok, torch.full_like(tok, CROSS_ENTROPY_IGNORE_IDX))
             ops.ce_fwd_metrics(logits, labels, V, CROSS_ENTROPY_IGNORE_IDX, row_loss, None, row_nll, row_rank)
             cum -= torch.where(alive, row_nll, torch.zeros_like(row_nll)).double()
@@ -241,11 +297,13 @@ def _generate_group(model, cache, seqs: list[Tensor], max_new_tokens: int, stop:
     host_out, host_n, host_stop, host_cum = out.cpu(), n_gen.cpu().tolist(), stop_tok.cpu().tolist(), cum.cpu().tolist()
     if int(cache.errors) != 0:
         raise RuntimeError(f"generate: the K/V cache kernels refused {int(cache.errors)} rows (a destination or a slot outside the cache)")
-    if int(not_top) != 0 and con is not None:
+    if pen is not None and int(n_bad) != 0:
+        raise RuntimeError(f"generate: on {int(n_bad)} row-steps the penalised selection met an id outside the vocabulary in the row's history")
+    if int(not_top) != 0 and chosen:
         raise RuntimeError(f"generate: on {int(not_top)} rows decode_select chose no token or one that is not allowed")
     if int(not_top) != 0:
         raise RuntimeError(f"generate: on {int(not_top)} rows the chosen token was not ranked first by ce_fwd_metrics")
-    host_con = n_con.cpu().tolist() if con is not None else [None] * n
+    host_con = n_con.cpu().tolist() if chosen else [None] * n
     return [Generation(token_ids=host_out[i, :host_n[i]].tolist(), finish_reason="stop" if host_stop[i] >= 0 else "length",
                        stop_reason=host_stop[i] if host_stop[i] >= 0 else None, cumulative_logprob=host_cum[i] if logprobs else None,
                        prompt_len=int(seqs[i].numel()), n_constrained=host_con[i]) for i in range(n)]
@@ -268,7 +326,8 @@ def _check_beam(beam_width, length_penalty, n_best) -> tuple[int, float, int]:
 
 def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_tokens: int, stop_token_ids: Sequence[int], pad_id: int,
                 length_penalty: float = 1.0, n_best: int = 1, allowed_token_ids: Sequence[int] | Tensor | None = None, min_new_tokens: int = 0,
-                batch_size: int = 256) -> list[list[Generation]]:
+                batch_size: int = 256, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
+                presence_penalty: float = 0.0) -> list[list[Generation]]:
     """The ``n_best <= beam_width <= 8`` best hypotheses of every prompt, best first, in INPUT order; ``cumulative_logprob`` (the sum of the
     tokens' log-probabilities under the unconstrained distribution) and ``score`` are always set.  A group holds ``batch_size // beam_width``
     prompts, so a step is at most ``batch_size`` rows.  The rules, with ``W = beam_width``:
@@ -284,8 +343,11 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
        ``s / max_new_tokens ** length_penalty``.
     7. The result: the pool by final score descending (stable in the order of joining), cut to ``n_best``.
 
-    Refused before any launch (``ValueError``): the three beam arguments outside their ranges, and everything ``generate`` refuses."""
+    Refused before any launch (``ValueError``): the three beam arguments outside their ranges, a penalty off its neutral value (vLLM's beam
+    search ignores them, and ``ssi_topk_logprob`` knows none), and everything ``generate`` refuses."""
     W, length_penalty, n_best = _check_beam(beam_width, length_penalty, n_best)
+    if _check_penalties(repetition_penalty, frequency_penalty, presence_penalty) is not None:
+        raise ValueError("beam_search: repetition, frequency and presence penalties are not part of beam search")
     max_new_tokens, batch_size, min_new_tokens, V = int(max_new_tokens), int(batch_size), int(min_new_tokens), int(model.vocab_size)
     masks = _constraint_masks(V, allowed_token_ids, min_new_tokens, stop_token_ids)
     stops = allowed_mask(V, ids=[int(t) for t in stop_token_ids])
@@ -436,7 +498,8 @@ def _check_sample(n, temperature, top_k, top_p, seed) -> tuple[int, float, int, 
 
 def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top_k: int = -1, top_p: float = 1.0, seed: int, max_new_tokens: int,
            stop_token_ids: Sequence[int], pad_id: int, batch_size: int = 256, allowed_token_ids: Sequence[int] | Tensor | None = None,
-           min_new_tokens: int = 0) -> list[list[Generation]]:
+           min_new_tokens: int = 0, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
+           presence_penalty: float = 0.0) -> list[list[Generation]]:
     """``n`` (1..8) sampled continuations of every prompt, in INPUT order and per prompt in sample order; ``cumulative_logprob`` (the tokens'
     log-probabilities under the unconstrained distribution at temperature 1, what ``ssi.score`` assigns) and ``n_kept_mean`` are always set.
     The token of a step is ``ops.decode_sample``'s with ``step`` the loop index and ``sequence = prompt index * n + sample index``: a pure function
@@ -445,9 +508,13 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
     ``n = 1``: ``generate``'s loop (``prefill``, ``decode_step``).  ``n > 1``: a group holds ``batch_size // n`` prompts; the prompt is prefilled
     once, its logits row repeated ``n`` times at step 0, and the samples run as rows of ``decode_step_beam`` with the identity ancestry.  The
     self-check per live row: the token is >= 0, allowed, and drawn from a set of at least one column (``RuntimeError``).
+    ``repetition_penalty``, ``frequency_penalty``, ``presence_penalty``: with any of them off its neutral value the step's token is
+    ``ops.decode_sample_pen``'s, drawn on the penalised row (penalties before temperature, top-k and top-p); the ``n`` samples of a prompt share
+    one line of the group's prompt table.  The log-probabilities stay those of the raw row.
     Refused before any launch (``ValueError``): ``n`` outside 1..8, ``temperature`` not finite or <= 0 (greedy decoding is ``generate``), ``top_p``
     outside (0, 1], a non-integer ``top_k``, a negative ``seed``, and everything ``generate`` refuses."""
     n, temperature, top_k, top_p, seed = _check_sample(n, temperature, top_k, top_p, seed)
+    pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
     max_new_tokens, batch_size, min_new_tokens, V = int(max_new_tokens), int(batch_size), int(min_new_tokens), int(model.vocab_size)
     masks = _constraint_masks(V, allowed_token_ids, min_new_tokens, stop_token_ids)
     if max_new_tokens < 1:
@@ -482,7 +549,8 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
                 con = _Constraint(allow, _mask_words(masks[0]).to(device), early if min_new_tokens else None,
                                   _mask_words(masks[1]).to(device) if min_new_tokens else None, min_new_tokens)
             for group in groups:
-                found = _sample_group(model, caches, [seqs[i] for i in group], group, n, draw, max_new_tokens, stop, int(pad_id), con)
+                found = _sample_group(model, caches, [seqs[i] for i in group], group, n, draw, max_new_tokens, stop, int(pad_id), con,
+                                      *(() if pen is None else (pen,)))
                 for i, g in zip(group, found):
                     results[i] = g
     finally:
@@ -492,7 +560,7 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
 
 
 def _sample_group(model, caches, seqs: list[Tensor], index: list[int], n: int, draw: dict, max_new: int, stop: Tensor, pad_id: int,
-                  con: _Constraint | None) -> list[list[Generation]]:
+                  con: _Constraint | None, pen: _Penalty | None = None) -> list[list[Generation]]:
     """One group: row ``s * n + j`` is sample ``j`` of the group's prompt ``s``, whose place in the input is ``index[s]``."""
     n_p, dev, V = len(seqs), model.device, int(model.vocab_size)
     R = n_p * n
@@ -517,13 +585,22 @@ def _sample_group(model, caches, seqs: list[Tensor], index: list[int], n: int, d
     tok = torch.empty(R, dtype=torch.int64, device=dev)
     row_lp = torch.empty(R, dtype=torch.float32, device=dev)
     row_kept = torch.empty(R, dtype=torch.int32, device=dev)
+    if pen is not None:
+        ptab, ptab_len = _prompt_table(seqs, dev)
+        n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        hist = dict(prompt_ids=ptab, prompt_len=ptab_len, prompt_row=seq_of, gen_ids=out, repetition_penalty=pen.r, frequency_penalty=pen.f,
+                    presence_penalty=pen.p, n_bad=n_bad)
     for t in range(max_new):
-        if con is None:
+        masks = {} if con is None else dict(allow=con.allow_words, allow_early=con.early_words, min_new=con.min_new)
+        if pen is not None:
+            ops.decode_sample_pen(logits, V, tok, row_lp, row_kept, step=t, sequence=sequence, n_generated=n_gen, **hist, **masks, **draw)
+        elif con is None:
             ops.decode_sample(logits, V, tok, row_lp, row_kept, step=t, sequence=sequence, **draw)
+        else:
+            ops.decode_sample(logits, V, tok, row_lp, row_kept, step=t, sequence=sequence, n_generated=n_gen if con.min_new else None, **masks, **draw)
+        if con is None:
             ok = torch.ones_like(alive)
         else:
-            ops.decode_sample(logits, V, tok, row_lp, row_kept, step=t, sequence=sequence, allow=con.allow_words, allow_early=con.early_words,
-                              n_generated=n_gen if con.min_new else None, min_new=con.min_new, **draw)
             at = tok.clamp(min=0)
             ok = con.allow[at] if con.early is None else torch.where(n_gen < con.min_new, con.early[at], con.allow[at])
         bad += (alive & ((tok < 0) | ~ok | (row_kept < 1))).sum()      # the self-check
@@ -549,6 +626,8 @@ def _sample_group(model, caches, seqs: list[Tensor], index: list[int], n: int, d
     errors = sum(int(c.errors) for c in caches)
     if errors != 0:
         raise RuntimeError(f"sample: the K/V cache kernels refused {errors} rows (a destination, a slot or an ancestry entry outside its cache)")
+    if pen is not None and int(n_bad) != 0:
+        raise RuntimeError(f"sample: on {int(n_bad)} row-steps the penalised selection met an id outside the vocabulary in the row's history")
     if int(bad) != 0:
         raise RuntimeError(f"sample: on {int(bad)} rows decode_sample chose no token, one that is not allowed, or kept no column")
     return [[Generation(token_ids=host_out[r, :host_n[r]].tolist(), finish_reason="stop" if host_stop[r] >= 0 else "length",
@@ -609,7 +688,9 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     is the greedy path: nothing of beam search runs.
     ``sample=True`` in ``kw`` (with ``temperature``, ``seed`` and optionally ``n``, ``top_k``, ``top_p``): ``sample`` instead; ``outputs`` holds ``n``
     entries, ``index`` 0.. in sample order, and the summary gains ``"sampled": True``, ``"n"`` and ``"kept_tokens_mean"`` (the mean over all generated
-    tokens of the size of the set each was drawn from).  Not together with ``beam_width > 1``."""
+    tokens of the size of the set each was drawn from).  Not together with ``beam_width > 1``.
+    ``repetition_penalty``, ``frequency_penalty``, ``presence_penalty`` in ``kw`` go to ``generate`` / ``sample`` (``beam_search`` refuses them off
+    their neutral values); when any is set the summary gains the three values, and on the greedy path ``"constrained_tokens"``."""
     if in_path is not None:
         ids, prompts = _read_prompts(tokenizer, in_path)
     elif prompts is None:
@@ -621,11 +702,13 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
         stop_token_ids = default_stop_token_ids(tokenizer)
     kw.setdefault("pad_id", int(getattr(tokenizer, "pad_id", 0) or 0))
     beam = {k: kw.pop(k) for k in ("beam_width", "length_penalty", "n_best") if k in kw}
+    pen = _check_penalties(kw.get("repetition_penalty", 1.0), kw.get("frequency_penalty", 0.0), kw.get("presence_penalty", 0.0))
+    pen_summary = {} if pen is None else {"repetition_penalty": pen.r, "frequency_penalty": pen.f, "presence_penalty": pen.p}
     draw = {k: kw.pop(k) for k in ("sample", "n", "temperature", "top_k", "top_p", "seed") if k in kw}
     if draw.pop("sample", False):
         if int(beam.get("beam_width", 1)) != 1:
             raise ValueError("generate_file: sample together with beam_width > 1 (sampling inside beam search is not built)")
-        return _sample_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, draw, kw)
+        return dict(_sample_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, draw, kw), **pen_summary)
     if draw:
         raise ValueError(f"generate_file: {sorted(draw)} without sample=True")
     if int(beam.get("beam_width", 1)) != 1:
@@ -637,8 +720,9 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
             f.write(json.dumps(output_record(item_id, p, g, tokenizer, tokenizer_decoding), ensure_ascii=False) + "\n")
     summary = {"items": len(gens), "generated_tokens": sum(len(g.token_ids) for g in gens),
                "stopped": sum(g.finish_reason == "stop" for g in gens)}
-    if kw.get("allowed_token_ids") is not None or int(kw.get("min_new_tokens", 0)) != 0:
+    if kw.get("allowed_token_ids") is not None or int(kw.get("min_new_tokens", 0)) != 0 or pen is not None:
         summary["constrained_tokens"] = sum(g.n_constrained or 0 for g in gens)
+    summary.update(pen_summary)
     return summary
 
 
@@ -706,6 +790,20 @@ def check_greedy(sampling_params) -> None:
 
 
 SAMPLING_KEYS = ("n", "temperature", "top_k", "top_p")
+PENALTY_KEYS = {"repetition_penalty": 1.0, "frequency_penalty": 0.0, "presence_penalty": 0.0}
+
+
+def check_penalties(sampling_params) -> dict[str, float]:
+    """What ``gen.penalties: true`` accepts of ``sampling_params``: ``repetition_penalty`` finite and > 0, ``frequency_penalty`` and
+    ``presence_penalty`` in [-2, 2] (``ValueError`` otherwise; an absent key or null is the neutral value).  Returns the three as the keyword
+    arguments of ``generate`` / ``sample``; the caller hands the rest of ``sampling_params``, without these keys, to ``check_greedy`` or
+    ``check_sampling`` unchanged."""
+    got = {k: (sampling_params[k] if k in sampling_params and sampling_params[k] is not None else v) for k, v in PENALTY_KEYS.items()}
+    try:
+        _check_penalties(got["repetition_penalty"], got["frequency_penalty"], got["presence_penalty"])
+    except ValueError as e:
+        raise ValueError(f"sampling_params.{e}") from None
+    return {k: float(v) for k, v in got.items()}
 
 
 def check_sampling(sampling_params) -> dict[str, Any]:

@@ -10,7 +10,7 @@ from torch import Tensor
 from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
-__all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "attn_decode_beam", "decode_select", "decode_sample", "topk_logprob", "swiglu_fwd",
+__all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "attn_decode_beam", "decode_select", "decode_sample", "decode_select_pen", "decode_sample_pen", "decode_penalty_lds_bytes", "topk_logprob", "swiglu_fwd",
            "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "ema_update", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
@@ -275,6 +275,104 @@ def decode_sample(logits: Tensor, vocab: int, token: Tensor, logprob: Tensor | N
     check(_lib.load().ssi_decode_sample(ptr(logits), logits.stride(0), rows, int(vocab), ptr(allow), ptr(allow_early), ptr(n_generated),
                                         int(min_new), float(temperature), top_k, float(top_p), int(seed), int(step), ptr(sequence), ptr(token),
                                         ptr(logprob), ptr(n_kept), dtype_code(logits.dtype), stream_ptr()), "ssi_decode_sample")
+
+
+def decode_penalty_lds_bytes(vocab: int, ld_gen: int) -> int:
+    """The dynamic LDS a penalised selection launch needs: ``4 ceil(vocab / 32) + 8 Hs`` bytes, ``Hs`` the smallest power of two ``>= 2 ld_gen``
+    and ``>= 64`` (the header's formula).  A launch is refused above ``_lib.DECODE_PENALTY_LDS_MAX``."""
+    hs = 64
+    while hs < 2 * int(ld_gen):
+        hs *= 2
+    return 4 * ((int(vocab) + 31) // 32) + 8 * hs
+
+
+def _penalty_args(what: str, logits: Tensor, vocab: int, n_generated: Tensor | None, prompt_ids: Tensor | None, prompt_len: Tensor,
+                  prompt_row: Tensor | None, gen_ids: Tensor | None, repetition_penalty: float, frequency_penalty: float, presence_penalty: float,
+                  n_bad: Tensor | None):
+    """The checks and the trailing C arguments the two penalised wrappers share."""
+    rows, dev = logits.shape[0], logits.device
+    if n_generated is None:
+        raise _lib.HipLibraryError(f"{what}: n_generated is required (how many of a row's gen_ids count)")
+    if prompt_ids is not None and (prompt_ids.dtype != torch.int32 or prompt_ids.dim() != 2 or not prompt_ids.is_contiguous() or prompt_ids.device != dev):
+        raise _lib.HipLibraryError(f"{what}: prompt_ids is a contiguous int32 [n_prompts, ld_prompt] on the device of logits")
+    n_prompts = prompt_ids.shape[0] if prompt_ids is not None else prompt_len.numel()
+    ld_prompt = prompt_ids.shape[1] if prompt_ids is not None else 0
+    if prompt_len.dtype != torch.int32 or not prompt_len.is_contiguous() or prompt_len.numel() != n_prompts or prompt_len.device != dev:
+        raise _lib.HipLibraryError(f"{what}: prompt_len is one int32 per line of prompt_ids, on the device of logits")
+    if prompt_row is None and n_prompts != rows:
+        raise _lib.HipLibraryError(f"{what}: without prompt_row there is one prompt line per row ({n_prompts} lines, {rows} rows)")
+    if prompt_row is not None and (prompt_row.dtype != torch.int32 or not prompt_row.is_contiguous() or prompt_row.numel() != rows or prompt_row.device != dev):
+        raise _lib.HipLibraryError(f"{what}: prompt_row is one int32 per row of logits, on its device")
+    if gen_ids is not None and (gen_ids.dtype != torch.int64 or gen_ids.dim() != 2 or gen_ids.shape[0] != rows or gen_ids.stride(1) != 1
+                                or gen_ids.stride(0) < gen_ids.shape[1] or gen_ids.device != dev):
+        raise _lib.HipLibraryError(f"{what}: gen_ids is int64 [rows, ld_gen] with unit inner stride, on the device of logits")
+    if gen_ids is not None and gen_ids.shape[1] != gen_ids.stride(0) and rows > 1:
+        raise _lib.HipLibraryError(f"{what}: gen_ids must be contiguous (row stride {gen_ids.stride(0)} for {gen_ids.shape[1]} columns)")
+    ld_gen = gen_ids.shape[1] if gen_ids is not None else 0
+    if n_bad is not None and (n_bad.dtype != torch.int32 or n_bad.numel() != 1 or n_bad.device != dev):
+        raise _lib.HipLibraryError(f"{what}: n_bad is one int32 on the device of logits")
+    need = decode_penalty_lds_bytes(vocab, ld_gen)
+    if need > _lib.DECODE_PENALTY_LDS_MAX:
+        raise _lib.HipLibraryError(f"{what}: vocab {vocab} with ld_gen {ld_gen} needs {need} bytes of LDS; at most {_lib.DECODE_PENALTY_LDS_MAX}")
+    return (ptr(prompt_ids), ld_prompt, ptr(prompt_len), ptr(prompt_row), n_prompts, ptr(gen_ids), ld_gen, float(repetition_penalty),
+            float(frequency_penalty), float(presence_penalty), ptr(n_bad))
+
+
+def decode_select_pen(logits: Tensor, vocab: int, token: Tensor, logprob: Tensor | None = None, rank: Tensor | None = None, *,
+                      prompt_ids: Tensor | None, prompt_len: Tensor, prompt_row: Tensor | None = None, gen_ids: Tensor | None,
+                      n_generated: Tensor, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0, presence_penalty: float = 0.0,
+                      n_bad: Tensor | None = None, allow: Tensor | None = None, allow_early: Tensor | None = None, min_new: int = 0) -> None:
+    """``decode_select`` under vLLM's penalties: the token is the first allowed maximum of the PENALISED row ``y`` (the header's definition:
+    ``y = fma(x, a, -t)`` on the columns of the row's history, ``x`` elsewhere), ``logprob`` and ``rank`` stay those of the raw row, so ``rank``
+    is 0 exactly when neither the mask nor the penalties changed the choice.  History: ``prompt_ids`` int32 ``[n_prompts, ld_prompt]`` with
+    ``prompt_len`` per line, row ``r`` reading line ``prompt_row[r]`` (``None``: line ``r``); ``gen_ids`` int64 ``[rows, ld_gen]`` of which row
+    ``r`` reads its first ``n_generated[r]`` entries (int32, required).  ``n_bad`` (int32 ``[1]``, optional) counts the rows that held an id or a
+    line out of range, which are skipped.  ``ssi_decode_select_pen``."""
+    ptr(logits)
+    if logits.dim() != 2 or logits.stride(1) != 1 or not 1 <= vocab <= logits.shape[1]:
+        raise _lib.HipLibraryError(f"decode_select_pen: logits must be [rows, >= vocab] with unit inner stride (got {tuple(logits.shape)}, vocab {vocab})")
+    rows, words = logits.shape[0], (vocab + 31) // 32
+    for name, t, dtype in (("token", token, torch.int64), ("logprob", logprob, torch.float32), ("rank", rank, torch.int32),
+                           ("n_generated", n_generated, torch.int32)):
+        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.numel() != rows or t.device != logits.device):
+            raise _lib.HipLibraryError(f"decode_select_pen: {name} is one {dtype} per row of logits, on its device")
+    for name, t in (("allow", allow), ("allow_early", allow_early)):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != words or t.device != logits.device):
+            raise _lib.HipLibraryError(f"decode_select_pen: {name} is {words} int32 words (one bit per column) on the device of logits")
+    tail = _penalty_args("decode_select_pen", logits, int(vocab), n_generated, prompt_ids, prompt_len, prompt_row, gen_ids, repetition_penalty,
+                         frequency_penalty, presence_penalty, n_bad)
+    check(_lib.load().ssi_decode_select_pen(ptr(logits), logits.stride(0), rows, int(vocab), ptr(allow), ptr(allow_early), ptr(n_generated),
+                                            int(min_new), ptr(token), ptr(logprob), ptr(rank), *tail, dtype_code(logits.dtype), stream_ptr()),
+          "ssi_decode_select_pen")
+
+
+def decode_sample_pen(logits: Tensor, vocab: int, token: Tensor, logprob: Tensor | None = None, n_kept: Tensor | None = None, *, temperature: float,
+                      top_k: int = -1, top_p: float = 1.0, seed: int, step: int, sequence: Tensor, prompt_ids: Tensor | None, prompt_len: Tensor,
+                      prompt_row: Tensor | None = None, gen_ids: Tensor | None, n_generated: Tensor, repetition_penalty: float = 1.0,
+                      frequency_penalty: float = 0.0, presence_penalty: float = 0.0, n_bad: Tensor | None = None, allow: Tensor | None = None,
+                      allow_early: Tensor | None = None, min_new: int = 0) -> None:
+    """``decode_sample`` under vLLM's penalties: the allowed set, top-k, top-p, the masses and the Gumbel-max score are all taken on the
+    PENALISED row ``y`` (penalties before temperature: vLLM's order); ``logprob`` stays that of the raw row at temperature 1.  The random bits
+    are ``decode_sample``'s.  The history arguments are ``decode_select_pen``'s.  ``ssi_decode_sample_pen``."""
+    ptr(logits)
+    if logits.dim() != 2 or logits.stride(1) != 1 or not 1 <= vocab <= logits.shape[1]:
+        raise _lib.HipLibraryError(f"decode_sample_pen: logits must be [rows, >= vocab] with unit inner stride (got {tuple(logits.shape)}, vocab {vocab})")
+    rows, words = logits.shape[0], (vocab + 31) // 32
+    for name, t, dtype in (("token", token, torch.int64), ("logprob", logprob, torch.float32), ("n_kept", n_kept, torch.int32),
+                           ("n_generated", n_generated, torch.int32), ("sequence", sequence, torch.int32)):
+        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.numel() != rows or t.device != logits.device):
+            raise _lib.HipLibraryError(f"decode_sample_pen: {name} is one {dtype} per row of logits, on its device")
+    for name, t in (("allow", allow), ("allow_early", allow_early)):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != words or t.device != logits.device):
+            raise _lib.HipLibraryError(f"decode_sample_pen: {name} is {words} int32 words (one bit per column) on the device of logits")
+    if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(step) < 2 ** 32:
+        raise _lib.HipLibraryError(f"decode_sample_pen: seed is in [0, 2^64) and step in [0, 2^32) (got {seed}, {step})")
+    top_k = max(-1, min(int(top_k), 2 ** 62))
+    tail = _penalty_args("decode_sample_pen", logits, int(vocab), n_generated, prompt_ids, prompt_len, prompt_row, gen_ids, repetition_penalty,
+                         frequency_penalty, presence_penalty, n_bad)
+    check(_lib.load().ssi_decode_sample_pen(ptr(logits), logits.stride(0), rows, int(vocab), ptr(allow), ptr(allow_early), ptr(n_generated),
+                                            int(min_new), float(temperature), top_k, float(top_p), int(seed), int(step), ptr(sequence), ptr(token),
+                                            ptr(logprob), ptr(n_kept), *tail, dtype_code(logits.dtype), stream_ptr()), "ssi_decode_sample_pen")
 
 
 def attn_decode_beam(qkv: Tensor, pk_cache: Tensor, pv_cache: Tensor, bk_cache: Tensor, bv_cache: Tensor, prompt_slot: Tensor, prompt_len: Tensor,

@@ -1,5 +1,5 @@
 """What greedy generation costs at the 1B shape (Llama-3.2-1B + 5000 DSUs, bf16, random weights): 256 prompts of about 1000 tokens, 256 new
-tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained|beam|sample] [--json profiles/generate.json]
+tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained|beam|sample|penalty] [--json profiles/generate.json]
 
 run        prefill time, milliseconds per decode step (event time over all steps, host gaps included), generated tokens per second, and a
            self-check: the first generated token of every prompt against the argmax of a plain full forward of that prompt alone (with
@@ -20,6 +20,9 @@ beam       (not part of ``all``; python tools/generate_bench.py --part beam --js
            ``--beam-width`` beams, a random ancestry, rotating over the layers' caches) against ``ssi_attn_decode`` on the materialised cache,
            with their outputs compared bit for bit; a beam decode step (``decode_step_beam`` + ``ssi_topk_logprob``) against the greedy step
            (``decode_step`` + argmax) at the same rows and key counts; and one ``beam_search`` call end to end.
+penalty    (not part of ``all``; python tools/generate_bench.py --part penalty --json profiles/generate_penalty.json) what the repetition, frequency
+           and presence penalties cost inside the two selection kernels, ONE process: every penalised kernel against its plain kernel on the
+           same logits, the plain sampler on fp32 logits beside it, a torch restatement, and a penalised decode step against the plain one.
 sample     (not part of ``all``; python tools/generate_bench.py --part sample --json profiles/generate_sample.json) what sampling costs, ONE process
            alternating the forms over ``--rounds`` rounds, median and min..max: ``ssi_decode_sample`` alone on [prompts, vocab_pad] bf16 logits in
            three settings (temperature only; top_k = 50; top_p = 0.9) against ``ssi_decode_select`` and a torch restatement (sort, cumsum, a
@@ -34,8 +37,9 @@ PKG = os.path.join(ROOT, 'speech-integration_amd')
 sys.path.insert(0, PKG)
 
 ap = argparse.ArgumentParser()
-ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained', 'beam', 'sample'])
+ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained', 'beam', 'sample', 'penalty'])
 ap.add_argument('--prompts', type=int, default=256)
+ap.add_argument('--penalty-generated', type=int, default=128, help='penalty: generated tokens in every row\'s history')
 ap.add_argument('--prompt-len', type=int, default=1000)
 ap.add_argument('--new', type=int, default=256)
 ap.add_argument('--trace-steps', type=int, default=32)
@@ -619,6 +623,157 @@ def part_sample():
     return res
 
 
+def part_penalty():
+    """What the repetition, frequency and presence penalties cost inside the two selection kernels, ONE process: each penalised kernel against
+    its plain kernel on the same logits (greedy; temperature only; top-k 50; top-p 0.9; both), the plain sampler on fp32 logits for the
+    settings whose bf16 radix passes double under penalties, a torch restatement (count scatter, the three passes over a copy, then the
+    selection), and a penalised greedy decode step of the model against the plain one."""
+    import torch
+    from ssi import ops
+    from ssi.constants import CROSS_ENTROPY_IGNORE_IDX as IGNORE
+    model = build_model()
+    n, V, ld = args.prompts, model.vocab_size, model.vocab_pad
+    dev = dict(device='cuda')
+    T, pen = 0.8, dict(repetition_penalty=1.3, frequency_penalty=0.5, presence_penalty=0.5)
+    n_hist, ld_gen = args.penalty_generated, 256
+    settings = {'temperature_only': dict(top_k=-1, top_p=1.0), 'top_k_50': dict(top_k=50, top_p=1.0), 'top_p_0.9': dict(top_k=-1, top_p=0.9),
+                'top_k_50_top_p_0.9': dict(top_k=50, top_p=0.9)}
+    thresholds = {'temperature_only': 0, 'top_k_50': 1, 'top_p_0.9': 1, 'top_k_50_top_p_0.9': 2}
+    walks_plain = {s: 2 + 2 * t for s, t in thresholds.items()}           # bf16 keys: 2 radix passes per threshold
+    walks_pen = {s: 2 + 4 * t for s, t in thresholds.items()}             # the penalised value is fp32: 4 passes per threshold
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(reps):
+            fn(i)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3        # us per call
+
+    res = {'geometry': f'[{n}, {ld}] bf16 logits (3 randn), vocab {V}; per row a prompt of {args.prompt_len} ids and {n_hist} generated ids (ld_gen {ld_gen}); '
+                       f'penalties {pen}; temperature {T}; {args.rounds} rounds alternating the forms in one process',
+           'dynamic_lds_bytes': ops.decode_penalty_lds_bytes(V, ld_gen)}
+    with torch.inference_mode():
+        g = torch.Generator(device='cuda').manual_seed(3)
+        x = torch.randn(n, ld, generator=g, **dev).mul_(3).to(torch.bfloat16)
+        x32 = x.float()
+        tok, lp, kept = torch.empty(n, dtype=torch.int64, **dev), torch.empty(n, **dev), torch.empty(n, dtype=torch.int32, **dev)
+        rk = torch.empty(n, dtype=torch.int32, **dev)
+        seqs = torch.arange(n, dtype=torch.int32, **dev)
+        pid = torch.randint(0, V, (n, args.prompt_len), generator=g, **dev).to(torch.int32)
+        plen = torch.full((n,), args.prompt_len, dtype=torch.int32, **dev)
+        gid = torch.randint(0, V, (n, ld_gen), generator=g, **dev)
+        gid[:, 1:n_hist:4] = gid[:, 0:1]                                  # a loop: every fourth generated token is the row's first
+        top = x[:, :V].float().topk(8, dim=-1).indices
+        gid[:, 2:18:2] = top                                              # and the row's largest columns are in the history, so the choice moves
+        n_gen = torch.full((n,), n_hist, dtype=torch.int32, **dev)
+        n_bad = torch.zeros(1, dtype=torch.int32, **dev)
+        hist = dict(prompt_ids=pid, prompt_len=plen, gen_ids=gid, n_generated=n_gen, n_bad=n_bad, **pen)
+
+        def torch_penalised():
+            """vLLM's apply_penalties in torch: the count scatter, the seen mask, and three passes over a copy of the logits."""
+            cnt = torch.zeros(n, V, dtype=torch.int32, **dev).scatter_add_(1, gid[:, :n_hist], torch.ones(n, n_hist, dtype=torch.int32, **dev))
+            seen = (cnt > 0).scatter_(1, pid.long(), True)
+            y = x[:, :V].float()
+            y = torch.where(seen, torch.where(y > 0, y / pen['repetition_penalty'], y * pen['repetition_penalty']), y)
+            y = y - pen['frequency_penalty'] * cnt
+            return y - pen['presence_penalty'] * (cnt > 0)
+
+        def torch_greedy(i):
+            t = torch_penalised().argmax(-1)
+            return t, torch.log_softmax(x[:, :V].float(), -1).gather(1, t[:, None])[:, 0]
+
+        def torch_sampled(i, s='top_k_50'):
+            k = settings[s]['top_k']
+            v, idx = torch.sort(torch_penalised() / T, dim=-1, descending=True)
+            v = v.masked_fill(v < v[:, k - 1:k], float('-inf'))
+            gum = -torch.log(-torch.log(torch.rand_like(v).clamp_(1e-7, 1 - 1e-7)))
+            return idx.gather(1, (v + gum).argmax(-1, keepdim=True))[:, 0]
+
+        ops.decode_select_pen(x, V, tok, lp, rk, **hist)
+        want = torch_greedy(0)[0]
+        res['self_check'] = {'greedy_tokens_equal_torch_restatement': round(float((tok == want).float().mean()), 4),
+                             'rows_whose_choice_the_penalties_changed': int((rk != 0).sum()), 'n_bad': int(n_bad)}
+        forms = {'decode_select_us': lambda i: ops.decode_select(x, V, tok, lp, rk),
+                 'decode_select_pen_us': lambda i: ops.decode_select_pen(x, V, tok, lp, rk, **hist),
+                 'decode_select_fp32_logits_us': lambda i: ops.decode_select(x32, V, tok, lp, rk)}
+        for s, kw in settings.items():
+            forms[f'decode_sample_{s}_us'] = lambda i, kw=kw: ops.decode_sample(x, V, tok, lp, kept, temperature=T, seed=1, step=i, sequence=seqs, **kw)
+            forms[f'decode_sample_pen_{s}_us'] = lambda i, kw=kw: ops.decode_sample_pen(x, V, tok, lp, kept, temperature=T, seed=1, step=i,
+                                                                                         sequence=seqs, **kw, **hist)
+            if thresholds[s]:
+                forms[f'decode_sample_fp32_logits_{s}_us'] = lambda i, kw=kw: ops.decode_sample(x32, V, tok, lp, kept, temperature=T, seed=1, step=i,
+                                                                                                sequence=seqs, **kw)
+        forms['torch_restatement_greedy_us'] = torch_greedy
+        forms['torch_restatement_top_k_50_us'] = torch_sampled
+        for fn in forms.values():
+            timed(fn, 3)
+        got = {k: [] for k in forms}
+        for _ in range(args.rounds):
+            for k, fn in forms.items():
+                got[k].append(timed(fn, 4 if k.startswith('torch') else 20))
+        ka = {k: spread(v) for k, v in got.items()}
+        per_walk = ka['decode_select_us']['median'] / 2
+        ka['decode_select_per_walk_us'] = round(per_walk, 2)
+        ka['decode_select_fp32_logits_per_walk_us'] = round(ka['decode_select_fp32_logits_us']['median'] / 2, 2)
+        ka['walks_plain'], ka['walks_penalised'] = walks_plain, walks_pen
+        ka['select_pen_minus_select_us'] = round(ka['decode_select_pen_us']['median'] - ka['decode_select_us']['median'], 2)
+        ka['penalised_over_walks_times_plain_per_walk'] = dict(
+            {'greedy': round(ka['decode_select_pen_us']['median'] / (2 * per_walk), 2)},
+            **{s: round(ka[f'decode_sample_pen_{s}_us']['median'] / (walks_pen[s] * per_walk), 2) for s in settings})
+        ka['penalised_over_plain'] = dict({'greedy': round(ka['decode_select_pen_us']['median'] / ka['decode_select_us']['median'], 2)},
+                                          **{s: round(ka[f'decode_sample_pen_{s}_us']['median'] / ka[f'decode_sample_{s}_us']['median'], 2) for s in settings})
+        ka['penalised_bf16_over_plain_fp32_logits'] = {s: round(ka[f'decode_sample_pen_{s}_us']['median'] / ka[f'decode_sample_fp32_logits_{s}_us']['median'], 2)
+                                                       for s in settings if thresholds[s]}
+        res['kernel_alone'] = ka
+
+        lens = torch.tensor([p.numel() for p in make_prompts(V)], dtype=torch.int32)
+        steps = args.trace_steps
+        cache = model.new_kv_cache(n, int(lens.max()) + steps + 1)
+        cache.k.normal_()
+        cache.v.normal_()
+        own = torch.arange(n, dtype=torch.int32, **dev)
+        loss, nll = torch.empty(n, **dev), torch.empty(n, **dev)
+
+        def step_greedy(t, j):
+            xx = model.decode_step(cache, t, own)
+            t = xx[:, :V].argmax(-1)
+            ops.ce_fwd_metrics(xx, t, V, IGNORE, loss, None, nll, rk)
+            return t
+
+        def step_penalised(t, j):
+            ops.decode_select_pen(model.decode_step(cache, t, own), V, tok, lp, rk, **hist)
+            return tok.clone()
+
+        def block(step):
+            cache.lengths.copy_(lens)
+            t = torch.zeros(n, dtype=torch.int64, **dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for j in range(steps):
+                t = step(t, j)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / steps
+
+        sforms = {'greedy_with_logprob_ms': step_greedy, 'penalised_greedy_with_logprob_ms': step_penalised}
+        for fn in sforms.values():
+            block(fn)
+        got = {k: [] for k in sforms}
+        for _ in range(args.rounds):
+            for k, fn in sforms.items():
+                got[k].append(block(fn))
+        assert int(cache.errors) == 0 and int(n_bad) == 0
+        st = {k: spread(v, 4) for k, v in got.items()}
+        st.update({'steps_per_block': steps, 'penalised_minus_greedy_ms': round(st['penalised_greedy_with_logprob_ms']['median'] - st['greedy_with_logprob_ms']['median'], 4),
+                   'greedy_spread_ms': round(st['greedy_with_logprob_ms']['max'] - st['greedy_with_logprob_ms']['min'], 4)})
+        res['decode_step'] = st
+    print(json.dumps(res, indent=1), flush=True)
+    return res
+
+
 def split_trace(stats_csv, steps):
     rows = [r for r in csv.DictReader(open(stats_csv)) if int(r['Calls']) >= steps]
     ms = lambda sel: sum(float(r['TotalDurationNs']) for r in rows if sel(r['Name'])) / 1e6 / steps  # noqa: E731
@@ -643,6 +798,8 @@ elif args.part == 'beam':
     res = part_beam()
 elif args.part == 'sample':
     res = part_sample()
+elif args.part == 'penalty':
+    res = part_penalty()
 else:
     wd = args.workdir
     os.makedirs(wd, exist_ok=True)
