@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 22 /* 22: + ssi_decode_select_pen, ssi_decode_sample_pen (repetition, frequency and presence penalties inside the two selection kernels; opt-in)
+#define SSI_ABI_VERSION 23 /* 23: + ssi_sumsq_groups, ssi_adamw_step_seg_gscale (per-group gradient norms of the flat buffer in one pass, a per-segment device gradient scale in the segmented AdamW; opt-in)
+                           * 22: + ssi_decode_select_pen, ssi_decode_sample_pen (repetition, frequency and presence penalties inside the two selection kernels; opt-in)
                            * 21: + ssi_decode_sample (sampled decoding: temperature, top-k, top-p and a seeded Gumbel-max draw of a row's token in one launch; opt-in)
                            * 20: + ssi_attn_decode_beam, ssi_topk_logprob (beam search: decode attention through an ancestry table, the k best allowed columns of a row; opt-in)
                            * 19: + ssi_decode_select (constrained greedy decoding: the allowed argmax of a row, its log-probability and its rank in one pass; opt-in)
@@ -595,6 +596,45 @@ int ssi_adamw_step_seg(void* param, void* grad, void* exp_avg, void* exp_avg_sq,
                        const double* seg_weight_decay, const int32_t* seg_frozen, int n_segs, double beta1, double beta2, double eps,
                        int64_t step, const float* grad_scale_dev, int zero_grad, int dtype, int stochastic, uint64_t seed,
                        int64_t elem_offset, void* stream);
+/* ssi_adamw_step_seg with one more gradient factor per segment, read on the DEVICE (ABI v23; not in the reference, opt-in: HipAdamW's
+ * grad_groups with a clip rule).  seg_scale_dev is a device array of n_segs floats, never NULL (NULL is SSI_ERR_ARG).  For a non-frozen
+ * segment s the effective factor is
+ *     gs_s = grad_scale_dev ? fl(*grad_scale_dev * seg_scale_dev[s]) : seg_scale_dev[s]
+ * one correctly rounded fp32 product, computed once per segment, and every element of the segment comes out BIT FOR BIT as ssi_adamw_step
+ * (ssi_adamw_step_sr when stochastic != 0) would leave it when launched on that segment's slice alone with grad_scale_dev = &gs_s, seg_lr[s],
+ * seg_weight_decay[s] and elem_offset + seg_end[s-1].  A segment whose gs_s is not finite -- the test of zero_grad bit 1, !(fabsf(gs_s) <
+ * INFINITY) -- is treated as frozen for this launch: neither read nor written in any of the four buffers (a group whose norm overflowed skips
+ * its step and nobody else's).  zero_grad bit 1 still makes the whole launch a no-op on a non-finite *grad_scale_dev.  Everything else is
+ * ssi_adamw_step_seg's: the host arrays, the frozen flag, frozen segments at either end not launched over, SSI_ADAMW_MAX_SEGS, the tail. */
+int ssi_adamw_step_seg_gscale(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, const int64_t* seg_end, const double* seg_lr,
+                              const double* seg_weight_decay, const int32_t* seg_frozen, int n_segs, double beta1, double beta2, double eps,
+                              int64_t step, const float* grad_scale_dev, int zero_grad, int dtype, int stochastic, uint64_t seed,
+                              int64_t elem_offset, const float* seg_scale_dev, void* stream);
+/* Sums of squares of GROUPS of segments of a flat buffer in one pass (ABI v23; not in the reference, opt-in: HipAdamW's grad_groups).
+ * Segment s covers the elements [seg_end[s-1], seg_end[s]) with seg_end[-1] = 0 and belongs to group seg_group[s] in [0, n_groups), or to
+ * none (-1).  seg_end and seg_group are HOST arrays of n_segs entries, read during the call only, with ssi_adamw_step_seg's conventions:
+ * ends strictly ascending, every end but the last a multiple of 8, the last equal to n; the table travels in the kernel arguments, the
+ * library allocates nothing on the device and enqueues no copy.
+ *   out[g] (device, n_groups floats) = sum over the elements of all segments of group g of (float)x * (float)x, accumulated in fp32; a
+ * group without a segment gets 0.  out is written, not accumulated into.  A segment with group -1 is NOT READ at all (a frozen range of the
+ * gradient buffer is unspecified and may hold NaN).  n == 0 (one segment with end 0) and an all-skipped table succeed with out zeroed.
+ *   n_segs > SSI_SUMSQ_MAX_SEGS or n_groups > SSI_SUMSQ_MAX_GROUPS is SSI_ERR_UNSUPPORTED (as is n >= 2^35 - 8); a group id outside
+ * [-1, n_groups) or bad ends SSI_ERR_ARG; workspace_bytes < ssi_sumsq_groups_workspace_bytes(n, n_segs, n_groups) SSI_ERR_WORKSPACE.
+ *   Properties (tests/test_sumsq_groups_gpu.py):
+ *   1. Reproducible: the same inputs give the same bits in every launch.  No float atomics: each block owns a contiguous run of 256-vector
+ *      tiles, keeps per-thread sums, reduces them by a fixed tree per group, writes one slot per group to the workspace, and a second
+ *      kernel adds the slots in ascending block order.
+ *   2. Isolated: out[g] depends only on the elements of group g's segments and on the table.  No other element -- NaN and inf included, and
+ *      whatever a skipped segment holds -- changes a bit of it.
+ *   3. Bounded: against the sum in float64 of the same stored values, |out[g] - ref[g]| <= B ref[g] with B = D u / (1 - D u), u = 2^-24,
+ *      D = 1 + (T E + 1) + n_segs + 12 + 1 + 12: the square, the longest per-thread chain (T = ceil(ceil((n / E) / 256) / 2048) tiles per
+ *      block, E = 8 (bf16) or 4 (fp32) elements per 16-byte vector, + 1 for the ragged tail), the adds of a block's reduced sums into its
+ *      group slot (at most one per segment), the block tree (6 + 6 levels), the pairing of two slots and the final tree. */
+#define SSI_SUMSQ_MAX_SEGS 256
+#define SSI_SUMSQ_MAX_GROUPS 64
+int64_t ssi_sumsq_groups_workspace_bytes(int64_t n, int n_segs, int n_groups);
+int ssi_sumsq_groups(const void* x, int64_t n, int dtype, const int64_t* seg_end, const int32_t* seg_group, int n_segs, int n_groups,
+                     float* out /* device, [n_groups] */, void* workspace, int64_t workspace_bytes, void* stream);
 /* Exponential moving average of the parameters, kept in fp32 (ABI v17; not in the reference, opt-in: HipAdamW's ema_decay).  Per element, in
  * fp32, with p = (float)param[i] (exact for bf16):
  *     ema[i] = __builtin_fmaf(decay, ema[i] - p, p)

@@ -565,6 +565,170 @@ extern "C" int ssi_sumsq(const void* x, int64_t n, int dtype, float* out, void* 
 }
 
 // =====================================================================================================================
+// K12g sums of squares per GROUP of segments of a flat buffer (ABI v23; opt-in, HipAdamW(grad_groups=...)): one read of the buffer gives
+// every group's sum.  The table travels by value in the kernel arguments, in units of 8 elements like AdamwSegTable.  A block owns a
+// CONTIGUOUS run of 256-vector tiles; it finds the segment of its first unit ONCE with wave-uniform indices only (15 coarse ends, then the
+// 16 ends of one chunk) and walks forward from there, so a tile that lies inside one segment touches no table (a lookup per tile put two
+// dependent rounds of scalar loads in front of every vector load: 0.71 ms against ssi_sumsq's 0.44 on 1.246 G bf16 elements; the walk:
+// 0.42); a tile that segments end in walks those segments, the lanes only select.  ONE running sum per thread, that of the block's current
+// group.  When the group changes (a block-uniform event: at most once per segment of the block's run) the sum is reduced over the block by
+// the fixed xor tree and added, by thread 0, to the group's slot in LDS.  A lane of a skipped segment (group -1) issues no load.  No float
+// atomics anywhere: the per-block slots go to the workspace and the final kernel adds them in a fixed order, so the bits are the same in
+// every launch, and a group's sum is built from its own elements and exact zeros only.
+// =====================================================================================================================
+#define SSI_SUMSQ_GROUPS_BLOCKS 2048
+struct SumsqGroupTable {
+    uint32_t end8[SSI_SUMSQ_MAX_SEGS];         // exclusive end of segment s in units of 8 elements (the last: rounded up); unused: 0xFFFFFFFF
+    int32_t group[SSI_SUMSQ_MAX_SEGS];         // group of segment s, -1: not read
+    uint32_t coarse[SSI_SUMSQ_MAX_SEGS / 16];  // end8[16 k + 15]
+    int n_segs;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void sumsq_groups_partial_kernel(const T* __restrict__ x, int64_t n, const SumsqGroupTable tab,
+                                                                   int tiles_per_block, int n_groups, int tail_group,
+                                                                   float* __restrict__ part) {
+    constexpr int N = Vec16<T>::N;
+    __shared__ float red[16];
+    __shared__ float acc[SSI_SUMSQ_MAX_GROUPS];
+    if (threadIdx.x < SSI_SUMSQ_MAX_GROUPS) acc[threadIdx.x] = 0.f;   // (block_sum's barriers lie between this and thread 0's first add)
+    const int64_t nvec = n / N;
+    float s = 0.f;
+    int cur = -1;   // the group s belongs to; block-uniform
+    auto flush = [&]() {
+        if (cur >= 0) {
+            const float t = block_sum(s, red);
+            if (threadIdx.x == 0) acc[cur] += t;
+            s = 0.f;
+        }
+    };
+    const int64_t t0 = (int64_t)blockIdx.x * tiles_per_block;
+    // the segment of the block's first unit: one lookup per block; the tiles that follow walk forward from it
+    int sg = 0;
+    uint32_t seg_start = 0u, seg_end = 0xFFFFFFFFu;
+    int seg_g = -1;
+    if (t0 * 256 < nvec) {
+        const uint32_t ub = (uint32_t)((t0 * 256 * N) >> 3);
+        int c = 0;
+#pragma unroll
+        for (int j = 0; j < SSI_SUMSQ_MAX_SEGS / 16 - 1; ++j) c += ub >= tab.coarse[j] ? 1 : 0;
+        sg = 16 * c;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) sg += ub >= tab.end8[16 * c + j] ? 1 : 0;
+        seg_start = sg ? tab.end8[sg - 1] : 0u;
+        seg_end = tab.end8[sg];
+        seg_g = tab.group[sg];
+    }
+    auto add = [&](int64_t i) {
+        const Vec16<T> a = load16(x + i * N);
+#pragma unroll
+        for (int e = 0; e < N; ++e) { const float f = a.get(e); s += f * f; }
+    };
+    for (int k = 0; k < tiles_per_block; ++k) {
+        const int64_t b = (t0 + k) * 256;   // the tile's first vector
+        if (b >= nvec) break;
+        const int64_t i = b + threadIdx.x;
+        const uint32_t ub0 = (uint32_t)((b * N) >> 3), ub1 = (uint32_t)(((b + 255) * N) >> 3), u = (uint32_t)((i * N) >> 3);
+        while (ub0 >= seg_end && sg + 1 < tab.n_segs) {   // (every index here is wave-uniform: scalar loads, and only at a segment's end)
+            seg_start = seg_end;
+            ++sg;
+            seg_end = tab.end8[sg];
+            seg_g = tab.group[sg];
+        }
+        if (ub1 < seg_end) {   // the whole tile lies in one segment: no table access
+            if (seg_g >= 0) {
+                if (seg_g != cur) { flush(); cur = seg_g; }
+                if (i < nvec) add(i);
+            }
+            continue;
+        }
+        uint32_t start = seg_start;
+        for (int q = sg; q < tab.n_segs && start <= ub1; ++q) {   // the segments that reach into the tile: the lanes only select
+            const uint32_t end = tab.end8[q];
+            const int g = tab.group[q];
+            if (g >= 0) {
+                if (g != cur) { flush(); cur = g; }
+                if (u >= start && u < end && i < nvec) add(i);
+            }
+            start = end;
+        }
+    }
+    if (blockIdx.x == gridDim.x - 1 && tail_group >= 0) {   // the ragged tail belongs to the last segment
+        if (tail_group != cur) { flush(); cur = tail_group; }
+        if (threadIdx.x < (n - nvec * N)) {
+            const float f = to_f32<T>(x[nvec * N + threadIdx.x]);
+            s += f * f;
+        }
+    }
+    flush();
+    __syncthreads();
+    if ((int)threadIdx.x < n_groups) part[(int64_t)blockIdx.x * n_groups + threadIdx.x] = acc[threadIdx.x];
+}
+
+// one block per group: the per-block slots in ascending block order, two per thread, then the fixed tree; nb == 0 writes the zeros
+__global__ __launch_bounds__(1024) void sumsq_groups_final_kernel(const float* __restrict__ part, int nb, int n_groups, float* __restrict__ out) {
+    __shared__ float red[16];
+    const int g = blockIdx.x, t = threadIdx.x;
+    float s = t < nb ? part[(int64_t)t * n_groups + g] : 0.f;
+    if (t + 1024 < nb) s += part[(int64_t)(t + 1024) * n_groups + g];
+    s = block_sum(s, red);
+    if (t == 0) out[g] = s;
+}
+
+extern "C" int64_t ssi_sumsq_groups_workspace_bytes(int64_t, int, int n_groups) {
+    return (int64_t)SSI_SUMSQ_GROUPS_BLOCKS * (n_groups < 1 ? 1 : n_groups) * (int64_t)sizeof(float);
+}
+
+extern "C" int ssi_sumsq_groups(const void* x, int64_t n, int dtype, const int64_t* seg_end, const int32_t* seg_group, int n_segs,
+                                int n_groups, float* out, void* workspace, int64_t workspace_bytes, void* stream) {
+    SSI_CHECK_ARG(out && n >= 0 && (x || n == 0) && ((uintptr_t)x % 16) == 0 && seg_end && seg_group && n_segs >= 1 && n_groups >= 1);
+    SSI_CHECK_ARG(dtype == SSI_F32 || dtype == SSI_BF16);
+    if (n_segs > SSI_SUMSQ_MAX_SEGS) { ssi_set_error("sumsq_groups: %d segments, at most %d", n_segs, SSI_SUMSQ_MAX_SEGS); return SSI_ERR_UNSUPPORTED; }
+    if (n_groups > SSI_SUMSQ_MAX_GROUPS) { ssi_set_error("sumsq_groups: %d groups, at most %d", n_groups, SSI_SUMSQ_MAX_GROUPS); return SSI_ERR_UNSUPPORTED; }
+    SSI_CHECK_ARG(seg_end[n_segs - 1] == n);
+    if (n == 0) SSI_CHECK_ARG(n_segs == 1);
+    for (int s = 0; s < n_segs; ++s) {
+        SSI_CHECK_ARG(n == 0 || seg_end[s] > (s ? seg_end[s - 1] : 0));   // strictly ascending
+        SSI_CHECK_ARG(s == n_segs - 1 || seg_end[s] % 8 == 0);            // a 16-byte vector lies in ONE segment
+        SSI_CHECK_ARG(seg_group[s] >= -1 && seg_group[s] < n_groups);
+    }
+    if (n >= ((int64_t)1 << 35) - 8) { ssi_set_error("sumsq_groups: n = %lld is beyond the 32-bit unit index", (long long)n); return SSI_ERR_UNSUPPORTED; }
+    if (!workspace || workspace_bytes < ssi_sumsq_groups_workspace_bytes(n, n_segs, n_groups)) { ssi_set_error("sumsq_groups: workspace too small"); return SSI_ERR_WORKSPACE; }
+    // skipped segments at either end are not launched over: the launch covers [first read start, last read end)
+    int s0 = 0, s1 = n_segs;
+    while (s0 < n_segs && seg_group[s0] < 0) ++s0;
+    int nb = 0;
+    if (n > 0 && s0 < n_segs) {
+        while (seg_group[s1 - 1] < 0) --s1;
+        const int64_t lo = s0 ? seg_end[s0 - 1] : 0, nn = seg_end[s1 - 1] - lo;
+        SumsqGroupTable tab;
+        for (int s = 0; s < SSI_SUMSQ_MAX_SEGS; ++s) { tab.end8[s] = 0xFFFFFFFFu; tab.group[s] = -1; }
+        tab.n_segs = s1 - s0;
+        for (int s = s0; s < s1; ++s) {
+            tab.end8[s - s0] = (uint32_t)((seg_end[s] - lo + 7) / 8);
+            tab.group[s - s0] = seg_group[s];
+        }
+        for (int k = 0; k < SSI_SUMSQ_MAX_SEGS / 16; ++k) tab.coarse[k] = tab.end8[16 * k + 15];
+        const size_t esz = dtype == SSI_BF16 ? 2 : 4;   // lo is a multiple of 8 elements: the 16-byte alignment holds
+        const char* xp = (const char*)x + lo * esz;
+        const int per = dtype == SSI_BF16 ? 8 : 4;
+        const int64_t tiles = ssi_cdiv(nn / per, 256);
+        int64_t tpb = ssi_cdiv(tiles, SSI_SUMSQ_GROUPS_BLOCKS);
+        if (tpb < 1) tpb = 1;
+        nb = (int)ssi_cdiv(tiles, tpb);
+        if (nb < 1) nb = 1;
+        const int tail_group = (nn % per) ? seg_group[s1 - 1] : -1;   // (a tail exists only when the last segment is read: skipped ends are cut at multiples of 8)
+        SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(sumsq_groups_partial_kernel<T>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
+                                                     (const T*)xp, nn, tab, (int)tpb, n_groups, tail_group, (float*)workspace));
+        SSI_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(sumsq_groups_final_kernel, dim3((unsigned)n_groups), dim3(1024), 0, (hipStream_t)stream, (const float*)workspace, nb,
+                       n_groups, out);
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+// =====================================================================================================================
 // K13s AdamW with stochastic rounding of the three bf16 stores (ABI v11; opt-in, HipAdamW(stochastic_rounding=True)).  Round-to-nearest
 // drops every update below half a bf16 step: v * 0.999 rounds back to v for every bf16 v, and a weight at 1.0 never moves at lr 2e-4
 // (profiles/LAB_NOTES.md).  The rounding is defined on the bit pattern and the random bits come from a counter-based generator keyed by
@@ -605,8 +769,18 @@ struct AdamwSegTable {
     int n_segs;
 };
 
-// coefficients of the segment unit `u` lies in, for a block whose vectors cover the units [ub0, ub1]; false: frozen (or past the last end)
-__device__ __forceinline__ bool adamw_seg_lookup(const AdamwSegTable& t, uint32_t ub0, uint32_t ub1, uint32_t u, float& decay, float& step_size) {
+// the gradient factor of segment s under GS: one correctly rounded product of the launch's scale and the segment's DEVICE scale (a scalar load:
+// s is wave-uniform), or the segment's scale alone when the launch has none
+__device__ __forceinline__ float adamw_seg_gscale(const float* __restrict__ grad_scale_dev, float gs_launch, const float* __restrict__ seg_scale_dev, int s) {
+    const float ss = seg_scale_dev[s];
+    return grad_scale_dev ? gs_launch * ss : ss;
+}
+
+// coefficients of the segment unit `u` lies in, for a block whose vectors cover the units [ub0, ub1]; false: frozen (or past the last end).
+// GS: gs becomes the segment's gradient factor, and a segment whose factor is not finite counts as frozen
+template <bool GS>
+__device__ __forceinline__ bool adamw_seg_lookup(const AdamwSegTable& t, uint32_t ub0, uint32_t ub1, uint32_t u, float& decay, float& step_size,
+                                                 const float* __restrict__ grad_scale_dev, float gs_launch, const float* __restrict__ seg_scale_dev, float& gs) {
     int c = 0;
 #pragma unroll
     for (int k = 0; k < SSI_ADAMW_MAX_SEGS / 16 - 1; ++k) c += ub0 >= t.coarse[k] ? 1 : 0;
@@ -617,10 +791,13 @@ __device__ __forceinline__ bool adamw_seg_lookup(const AdamwSegTable& t, uint32_
     bool active = false;
     for (; s < t.n_segs && start <= ub1; ++s) {   // every index here is wave-uniform: the lanes only select
         const uint32_t end = t.end8[s];
+        [[maybe_unused]] float gs_s = 0.f;
+        if constexpr (GS) gs_s = adamw_seg_gscale(grad_scale_dev, gs_launch, seg_scale_dev, s);
         if (u >= start && u < end) {
             decay = t.decay[s];
             step_size = t.step_size[s];
             active = !((t.frozen[s >> 5] >> (s & 31)) & 1u);
+            if constexpr (GS) { gs = gs_s; active = active && fabsf(gs_s) < INFINITY; }
         }
         start = end;
     }
@@ -628,8 +805,8 @@ __device__ __forceinline__ bool adamw_seg_lookup(const AdamwSegTable& t, uint32_
 }
 
 // =====================================================================================================================
-// K13 AdamW: ONE element function and ONE body behind the four kernels.  SR: the three stores round stochastically; SEG: decay and step_size
-// come per segment from the table.  Built with -ffp-contract=fast, the variants agree bit for bit because the arithmetic is written once.
+// K13 AdamW: ONE element function and ONE body behind the seven kernels.  SR: the three stores round stochastically; SEG: decay and step_size
+// come per segment from the table; GS (ABI v23, with SEG): the gradient factor too, from a per-segment DEVICE scale.  Built with -ffp-contract=fast, the variants agree bit for bit because the arithmetic is written once.
 // =====================================================================================================================
 struct AdamwCoef { float w1, beta2, w2, eps, inv_bc2_sqrt; };           // what every element of a launch shares
 struct AdamwSr { uint64_t seed; uint32_t step; int64_t vec_offset; };   // SR: the generator's key and the slice's first vector in the global index
@@ -648,13 +825,16 @@ __device__ __forceinline__ void adamw_elem(float& pf, float& mf, float& vf, floa
     pf -= step_size * mf / denom;
 }
 
-template <typename T, bool SEG, bool SR>
+template <typename T, bool SEG, bool SR, bool GS = false>
 __device__ __forceinline__ void adamw_body(T* __restrict__ p, T* __restrict__ g, T* __restrict__ m, T* __restrict__ v, int64_t n,
                                            const AdamwSegTable* tab, float decay, float step_size, const AdamwCoef c,
-                                           const float* __restrict__ grad_scale_dev, int zero_grad, const AdamwSr sr) {
+                                           const float* __restrict__ grad_scale_dev, int zero_grad, const AdamwSr sr,
+                                           const float* __restrict__ seg_scale_dev = nullptr) {
     constexpr int N = Vec16<T>::N;
     static_assert(!SR || N == 8, "one Philox call per tensor covers the 8 elements of a 16-byte vector");
+    static_assert(!GS || SEG, "the device scale is per segment");
     const float gs = grad_scale_dev ? *grad_scale_dev : 1.f;
+    [[maybe_unused]] float gs_seg = gs;   // GS: the factor of the segment the lane's vector lies in, set by the lookup
     if ((zero_grad & 2) && !(fabsf(gs) < INFINITY)) return;  // bit 1: a non-finite scale (an accumulation window without a label) changes nothing
     zero_grad &= 1;
     const int64_t nvec = n / N;
@@ -662,7 +842,8 @@ __device__ __forceinline__ void adamw_body(T* __restrict__ p, T* __restrict__ g,
     for (int64_t b = (int64_t)blockIdx.x * 256 + (SEG ? 0 : threadIdx.x); b < nvec; b += (int64_t)gridDim.x * 256) {
         const int64_t i = SEG ? b + threadIdx.x : b;
         if constexpr (SEG) {
-            const bool active = adamw_seg_lookup(*tab, (uint32_t)((b * N) >> 3), (uint32_t)(((b + 255) * N) >> 3), (uint32_t)((i * N) >> 3), decay, step_size);
+            const bool active = adamw_seg_lookup<GS>(*tab, (uint32_t)((b * N) >> 3), (uint32_t)(((b + 255) * N) >> 3), (uint32_t)((i * N) >> 3), decay,
+                                                     step_size, grad_scale_dev, gs, seg_scale_dev, gs_seg);
             if (!active || i >= nvec) continue;
         }
         Vec16<T> pp = load16_nt(p + i * N), gg = load16_nt(g + i * N), mm = load16_nt(m + i * N), vv = load16_nt(v + i * N);
@@ -672,7 +853,7 @@ __device__ __forceinline__ void adamw_body(T* __restrict__ p, T* __restrict__ g,
 #pragma unroll
         for (int k = 0; k < N; ++k) {
             float pf = pp.get(k), mf = mm.get(k), vf = vv.get(k);
-            adamw_elem(pf, mf, vf, gg.get(k) * gs, decay, step_size, c);
+            adamw_elem(pf, mf, vf, gg.get(k) * (GS ? gs_seg : gs), decay, step_size, c);
             pp.v[k] = adamw_rounded<T, SR>(pf, rp, k); mm.v[k] = adamw_rounded<T, SR>(mf, rm, k); vv.v[k] = adamw_rounded<T, SR>(vf, rv, k);
             if (zero_grad) gg.set(k, 0.f);
         }
@@ -685,11 +866,15 @@ __device__ __forceinline__ void adamw_body(T* __restrict__ p, T* __restrict__ g,
             if ((tab->frozen[last >> 5] >> (last & 31)) & 1u) return;
             decay = tab->decay[last];
             step_size = tab->step_size[last];
+            if constexpr (GS) {
+                gs_seg = adamw_seg_gscale(grad_scale_dev, gs, seg_scale_dev, last);
+                if (!(fabsf(gs_seg) < INFINITY)) return;
+            }
         }
         const int k = threadIdx.x;   // SR: the slice starts on a vector boundary of the global index, so the tail is the head of vector vec_offset + nvec
         const int64_t i = nvec * N + k;
         float pf = to_f32<T>(p[i]), mf = to_f32<T>(m[i]), vf = to_f32<T>(v[i]);
-        adamw_elem(pf, mf, vf, to_f32<T>(g[i]) * gs, decay, step_size, c);
+        adamw_elem(pf, mf, vf, to_f32<T>(g[i]) * (GS ? gs_seg : gs), decay, step_size, c);
         p[i] = adamw_rounded<T, SR>(pf, sr_bits(sr.vec_offset + nvec, sr.step, 0, sr.seed), k);
         m[i] = adamw_rounded<T, SR>(mf, sr_bits(sr.vec_offset + nvec, sr.step, 1, sr.seed), k);
         v[i] = adamw_rounded<T, SR>(vf, sr_bits(sr.vec_offset + nvec, sr.step, 2, sr.seed), k);
@@ -727,6 +912,24 @@ __global__ __launch_bounds__(256) void adamw_seg_sr_kernel(bf16_t* __restrict__ 
                                                            int zero_grad, uint64_t seed, uint32_t step, int64_t vec_offset) {
     adamw_body<bf16_t, true, true>(p, g, m, v, n, &tab, 0.f, 0.f, AdamwCoef{w1, beta2, w2, eps, inv_bc2_sqrt}, grad_scale_dev, zero_grad,
                                    AdamwSr{seed, step, vec_offset});
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void adamw_gscale_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ m, T* __restrict__ v, int64_t n,
+                                                           const AdamwSegTable tab, float w1, float beta2, float w2, float eps, float inv_bc2_sqrt,
+                                                           const float* __restrict__ grad_scale_dev, int zero_grad,
+                                                           const float* __restrict__ seg_scale_dev) {
+    adamw_body<T, true, false, true>(p, g, m, v, n, &tab, 0.f, 0.f, AdamwCoef{w1, beta2, w2, eps, inv_bc2_sqrt}, grad_scale_dev, zero_grad, AdamwSr{},
+                                     seg_scale_dev);
+}
+
+__global__ __launch_bounds__(256) void adamw_gscale_sr_kernel(bf16_t* __restrict__ p, bf16_t* __restrict__ g, bf16_t* __restrict__ m,
+                                                              bf16_t* __restrict__ v, int64_t n, const AdamwSegTable tab, float w1, float beta2,
+                                                              float w2, float eps, float inv_bc2_sqrt, const float* __restrict__ grad_scale_dev,
+                                                              int zero_grad, uint64_t seed, uint32_t step, int64_t vec_offset,
+                                                              const float* __restrict__ seg_scale_dev) {
+    adamw_body<bf16_t, true, true, true>(p, g, m, v, n, &tab, 0.f, 0.f, AdamwCoef{w1, beta2, w2, eps, inv_bc2_sqrt}, grad_scale_dev, zero_grad,
+                                         AdamwSr{seed, step, vec_offset}, seg_scale_dev);
 }
 
 static int adamw_check_buffers(const void* param, const void* grad, const void* exp_avg, const void* exp_avg_sq, int64_t n, int64_t step) {
@@ -782,10 +985,11 @@ extern "C" int ssi_adamw_step_sr(void* param, void* grad, void* exp_avg, void* e
     return SSI_OK;
 }
 
-extern "C" int ssi_adamw_step_seg(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, const int64_t* seg_end,
-                                  const double* seg_lr, const double* seg_weight_decay, const int32_t* seg_frozen, int n_segs,
-                                  double beta1, double beta2, double eps, int64_t step, const float* grad_scale_dev, int zero_grad,
-                                  int dtype, int stochastic, uint64_t seed, int64_t elem_offset, void* stream) {
+// the segmented launch; seg_scale_dev: NULL (ssi_adamw_step_seg) or the per-segment device scales (ssi_adamw_step_seg_gscale)
+static int adamw_step_seg_launch(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, const int64_t* seg_end,
+                                 const double* seg_lr, const double* seg_weight_decay, const int32_t* seg_frozen, int n_segs,
+                                 double beta1, double beta2, double eps, int64_t step, const float* grad_scale_dev, int zero_grad,
+                                 int dtype, int stochastic, uint64_t seed, int64_t elem_offset, const float* seg_scale_dev, void* stream) {
     if (const int rc = adamw_check_buffers(param, grad, exp_avg, exp_avg_sq, n, step)) return rc;
     SSI_CHECK_ARG(seg_end && seg_lr && seg_weight_decay && seg_frozen && n_segs >= 1);
     SSI_CHECK_ARG(dtype == SSI_F32 || dtype == SSI_BF16);
@@ -819,7 +1023,18 @@ extern "C" int ssi_adamw_step_seg(void* param, void* grad, void* exp_avg, void* 
     for (int k = 0; k < SSI_ADAMW_MAX_SEGS / 16; ++k) tab.coarse[k] = tab.end8[16 * k + 15];
     const size_t esz = dtype == SSI_BF16 ? 2 : 4;   // lo is a multiple of 8 elements: the 16-byte alignment holds
     char *pp = (char*)param + lo * esz, *gp = (char*)grad + lo * esz, *mp = (char*)exp_avg + lo * esz, *vp = (char*)exp_avg_sq + lo * esz;
-    if (stochastic) {
+    if (seg_scale_dev) {   // the scales of the segments the launch covers
+        const float* ssd = seg_scale_dev + s0;
+        if (stochastic) {
+            hipLaunchKernelGGL(adamw_gscale_sr_kernel, adamw_grid<bf16_t>(nn), dim3(256), 0, (hipStream_t)stream, (bf16_t*)pp, (bf16_t*)gp, (bf16_t*)mp,
+                               (bf16_t*)vp, nn, tab, st.c.w1, st.c.beta2, st.c.w2, st.c.eps, st.c.inv_bc2_sqrt, grad_scale_dev, zero_grad, seed,
+                               (uint32_t)step, (elem_offset + lo) / 8, ssd);
+        } else {
+            SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(adamw_gscale_kernel<T>, adamw_grid<T>(nn), dim3(256), 0, (hipStream_t)stream, (T*)pp, (T*)gp,
+                                                         (T*)mp, (T*)vp, nn, tab, st.c.w1, st.c.beta2, st.c.w2, st.c.eps, st.c.inv_bc2_sqrt,
+                                                         grad_scale_dev, zero_grad, ssd));
+        }
+    } else if (stochastic) {
         hipLaunchKernelGGL(adamw_seg_sr_kernel, adamw_grid<bf16_t>(nn), dim3(256), 0, (hipStream_t)stream, (bf16_t*)pp, (bf16_t*)gp, (bf16_t*)mp,
                            (bf16_t*)vp, nn, tab, st.c.w1, st.c.beta2, st.c.w2, st.c.eps, st.c.inv_bc2_sqrt, grad_scale_dev, zero_grad, seed,
                            (uint32_t)step, (elem_offset + lo) / 8);
@@ -830,6 +1045,23 @@ extern "C" int ssi_adamw_step_seg(void* param, void* grad, void* exp_avg, void* 
     }
     SSI_LAUNCH_CHECK();
     return SSI_OK;
+}
+
+extern "C" int ssi_adamw_step_seg(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, const int64_t* seg_end,
+                                  const double* seg_lr, const double* seg_weight_decay, const int32_t* seg_frozen, int n_segs,
+                                  double beta1, double beta2, double eps, int64_t step, const float* grad_scale_dev, int zero_grad,
+                                  int dtype, int stochastic, uint64_t seed, int64_t elem_offset, void* stream) {
+    return adamw_step_seg_launch(param, grad, exp_avg, exp_avg_sq, n, seg_end, seg_lr, seg_weight_decay, seg_frozen, n_segs, beta1, beta2, eps, step,
+                                 grad_scale_dev, zero_grad, dtype, stochastic, seed, elem_offset, nullptr, stream);
+}
+
+extern "C" int ssi_adamw_step_seg_gscale(void* param, void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, const int64_t* seg_end,
+                                         const double* seg_lr, const double* seg_weight_decay, const int32_t* seg_frozen, int n_segs,
+                                         double beta1, double beta2, double eps, int64_t step, const float* grad_scale_dev, int zero_grad,
+                                         int dtype, int stochastic, uint64_t seed, int64_t elem_offset, const float* seg_scale_dev, void* stream) {
+    SSI_CHECK_ARG(seg_scale_dev && ((uintptr_t)seg_scale_dev % 4) == 0);
+    return adamw_step_seg_launch(param, grad, exp_avg, exp_avg_sq, n, seg_end, seg_lr, seg_weight_decay, seg_frozen, n_segs, beta1, beta2, eps, step,
+                                 grad_scale_dev, zero_grad, dtype, stochastic, seed, elem_offset, seg_scale_dev, stream);
 }
 
 // the rounding of adamw_sr_kernel on its own: dst[i] = sr_bf16(src[i]) with the bits of (seed, step, elem_offset + i, tensor)

@@ -20,9 +20,10 @@ SSI_F32, SSI_BF16 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 IMPL_AUTO, IMPL_GENERIC, IMPL_MFMA, IMPL_MFMA_WG8 = 0, 1, 2, 3
 TILES_STATIC, TILES_DYNAMIC = 0, 1
-ABI_VERSION = 22
+ABI_VERSION = 23
 DECODE_PENALTY_LDS_MAX = 57344
 ADAMW_MAX_SEGS = 128
+SUMSQ_MAX_SEGS, SUMSQ_MAX_GROUPS = 256, 64
 ATTN_KERNEL_DQ, ATTN_KERNEL_DKV = 0, 1
 ATTN_MODE_AUTO, ATTN_MODE_OLD, ATTN_MODE_NEW, ATTN_MODE_NO_HEAD_SPLIT = 0, 1, 2, 3
 ATTN_USED_DQ2, ATTN_USED_DKV2, ATTN_USED_HEAD_SPLIT, ATTN_USED_PLAN = 1, 2, 4, 8
@@ -109,6 +110,10 @@ PROTOTYPES = {
     "ssi_round_bf16_sr": (c_int, [_P, _P, c_int64, c_uint64, c_int64, c_int, c_int64, _P]),
     "ssi_adamw_step_seg": (c_int, [_P, _P, _P, _P, c_int64, _P, _P, _P, _P, c_int, c_double, c_double, c_double, c_int64, _P, c_int,
                                    c_int, c_int, c_uint64, c_int64, _P]),
+    "ssi_adamw_step_seg_gscale": (c_int, [_P, _P, _P, _P, c_int64, _P, _P, _P, _P, c_int, c_double, c_double, c_double, c_int64, _P, c_int,
+                                          c_int, c_int, c_uint64, c_int64, _P, _P]),
+    "ssi_sumsq_groups_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
+    "ssi_sumsq_groups": (c_int, [_P, c_int64, c_int, _P, _P, c_int, c_int, _P, _P, c_int64, _P]),
     "ssi_ema_update": (c_int, [_P, _P, c_int64, c_float, _P, c_int, _P]),
 }
 

@@ -707,6 +707,23 @@ def sumsq(x: Tensor, out: Tensor, workspace: Tensor | None = None) -> None:
                         workspace.numel() * workspace.element_size(), stream_ptr()), "ssi_sumsq")
 
 
+def sumsq_groups(x: Tensor, seg_end, seg_group, n_groups: int, out: Tensor, workspace: Tensor | None = None) -> None:
+    """``out[g]`` = the fp32 sum of squares of the elements of all segments of group ``g`` (``ssi_sumsq_groups``), for every group in one pass
+    over ``x``.  Segment ``s`` covers ``[seg_end[s-1], seg_end[s])`` (``adamw_step_seg``'s conventions) and belongs to group ``seg_group[s]`` in
+    ``[0, n_groups)``, or, with -1, to none: such a segment is not read.  Both sequences are host values; ``out`` is an fp32 device tensor of
+    ``n_groups`` elements, overwritten.  The same inputs give the same bits, and no element outside a group changes its sum."""
+    lib = _lib.load()
+    n_segs = len(seg_end)
+    assert x.is_contiguous() and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == n_groups and len(seg_group) == n_segs >= 1
+    need = lib.ssi_sumsq_groups_workspace_bytes(x.numel(), n_segs, n_groups)
+    if workspace is None:
+        workspace = _byte_ws(need, out)
+    ends = (_lib.c_int64 * n_segs)(*[int(e) for e in seg_end])
+    groups = (_lib.c_int32 * n_segs)(*[int(g) for g in seg_group])
+    check(lib.ssi_sumsq_groups(ptr(x) if x.numel() else None, x.numel(), dtype_code(x.dtype), ends, groups, n_segs, n_groups, ptr(out), ptr(workspace),
+                               workspace.numel() * workspace.element_size(), stream_ptr()), "ssi_sumsq_groups")
+
+
 def _adamw_flags(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, zero_grad: bool, skip_nonfinite_scale: bool) -> int:
     """The AdamW entries' ``zero_grad`` argument, after the checks on the four buffers that they share."""
     assert param.is_contiguous() and grad.is_contiguous() and exp_avg.is_contiguous() and exp_avg_sq.is_contiguous()
@@ -735,15 +752,21 @@ def adamw_step(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor,
 
 def adamw_step_seg(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, *, seg_end, seg_lr, seg_weight_decay, seg_frozen,
                    beta1: float, beta2: float, eps: float, step: int, grad_scale_dev: Tensor | None = None, zero_grad: bool = False,
-                   skip_nonfinite_scale: bool = False, sr_seed: int | None = None, elem_offset: int = 0) -> None:
+                   skip_nonfinite_scale: bool = False, sr_seed: int | None = None, elem_offset: int = 0,
+                   seg_scale_dev: Tensor | None = None) -> None:
     """``adamw_step`` over consecutive segments of the buffers in one launch (``ssi_adamw_step_seg``): segment ``s`` covers the elements
     ``[seg_end[s-1], seg_end[s])`` (``seg_end[-1] = 0``; ends ascending, multiples of 8 but the last, which is ``numel``) and runs at
     ``seg_lr[s]`` / ``seg_weight_decay[s]``, or is left alone — neither read nor written — where ``seg_frozen[s]``.  The four sequences are
-    host values.  More than ``_lib.ADAMW_MAX_SEGS`` segments become several launches, split at segment ends; the result is the same."""
+    host values.  More than ``_lib.ADAMW_MAX_SEGS`` segments become several launches, split at segment ends; the result is the same.
+    ``seg_scale_dev`` (an fp32 DEVICE tensor of one factor per segment; ``ssi_adamw_step_seg_gscale``): segment ``s`` sees its gradient times
+    ``fl(grad_scale_dev * seg_scale_dev[s])`` (``seg_scale_dev[s]`` alone without a ``grad_scale_dev``), and a segment whose factor is inf or
+    NaN is left alone like a frozen one.  The split launches take the slices of it that go with their segments."""
     flags = _adamw_flags(param, grad, exp_avg, exp_avg_sq, zero_grad, skip_nonfinite_scale)
     n_segs = len(seg_end)
     assert n_segs >= 1 and len(seg_lr) == len(seg_weight_decay) == len(seg_frozen) == n_segs
     lib, cap = _lib.load(), _lib.ADAMW_MAX_SEGS
+    if seg_scale_dev is not None:
+        assert seg_scale_dev.dtype == torch.float32 and seg_scale_dev.is_contiguous() and seg_scale_dev.numel() == n_segs
     param, grad, exp_avg, exp_avg_sq = param.view(-1), grad.view(-1), exp_avg.view(-1), exp_avg_sq.view(-1)
     if param.numel() == 0 and n_segs == 1 and int(seg_end[0]) == 0:
         return   # (an empty tensor has no address to hand over)
@@ -758,6 +781,12 @@ def adamw_step_seg(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Ten
         wds = (_lib.c_double * k)(*[float(x) for x in seg_weight_decay[a:b]])
         frz = (_lib.c_int32 * k)(*[1 if x else 0 for x in seg_frozen[a:b]])
         sl = slice(lo, hi) if (a or b < n_segs) else slice(None)   # (one launch: the whole buffers, so that a wrong last end is the library's error)
+        if seg_scale_dev is not None:
+            check(lib.ssi_adamw_step_seg_gscale(ptr(param[sl]), ptr(grad[sl]), ptr(exp_avg[sl]), ptr(exp_avg_sq[sl]), param[sl].numel(), ends, lrs, wds,
+                                                frz, k, beta1, beta2, eps, step, ptr(grad_scale_dev), flags, dtype_code(param.dtype),
+                                                int(sr_seed is not None), (int(sr_seed) & 0xFFFFFFFFFFFFFFFF) if sr_seed is not None else 0,
+                                                elem_offset + lo, ptr(seg_scale_dev[a:b]), stream_ptr()), "ssi_adamw_step_seg_gscale")
+            continue
         check(lib.ssi_adamw_step_seg(ptr(param[sl]), ptr(grad[sl]), ptr(exp_avg[sl]), ptr(exp_avg_sq[sl]), param[sl].numel(), ends, lrs, wds, frz, k,
                                      beta1, beta2, eps, step, ptr(grad_scale_dev), flags, dtype_code(param.dtype), int(sr_seed is not None),
                                      (int(sr_seed) & 0xFFFFFFFFFFFFFFFF) if sr_seed is not None else 0, elem_offset + lo, stream_ptr()),

@@ -10,7 +10,10 @@ not in the reference) rounds the three stores stochastically instead of to neare
 ``param_segments`` (config key ``param_groups``, null by default, not in the reference; ``ssi/param_groups.py``) gives consecutive ranges of
 the flat buffer their own lr scale, weight decay or a frozen flag: the step is still one launch, of the segmented kernel.
 ``ema_decay`` (config key of the same name, null by default, not in the reference) keeps an fp32 exponential moving average of the flat
-parameter buffer, one more HIP pass chained to every AdamW launch; ``ema_weights()`` evaluates on it, ``ema_state_dict()`` saves it."""
+parameter buffer, one more HIP pass chained to every AdamW launch; ``ema_weights()`` evaluates on it, ``ema_state_dict()`` saves it.
+``grad_groups`` (config key of the same name, null by default, not in the reference; ``ssi/grad_groups.py``) names groups of the flat gradient
+buffer: ``measure_grad_group_sums()`` gives every group's gradient norm in one HIP pass, and with a clip rule each group's coefficient rides
+into the segmented AdamW as a per-segment device scale."""
 
 from __future__ import annotations
 
@@ -42,7 +45,7 @@ class HipAdamW(torch.optim.Optimizer):
     def __init__(self, params: Iterable, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, amsgrad: bool = False, fused: bool | None = None, *, model=None,
                  stochastic_rounding: bool = False, stochastic_rounding_seed: int | None = None, param_segments=None,
-                 ema_decay: float | None = None, ema_warmup: bool = True, **unused: Any):
+                 ema_decay: float | None = None, ema_warmup: bool = True, grad_groups=None, **unused: Any):
         if amsgrad:
             raise NotImplementedError("amsgrad=True is not supported (reference default: false, conf/training.yaml:8)")
         if unused:
@@ -95,13 +98,74 @@ class HipAdamW(torch.optim.Optimizer):
             self._ema_decay = float(d)
             self._ema = model._flat.to(torch.float32, copy=True)
         self._ema_ranges = None if self._segments is None else trainable_ranges(self._segments)
+        # Gradient groups (not in the reference; off by default; ssi/grad_groups.py): a table of segments of the flat gradient buffer with their
+        # group, summed per group by ONE ssi_sumsq_groups launch in ``measure_grad_group_sums``; with a clip rule the groups' coefficients become the
+        # per-segment device scales of the segmented AdamW over the refined segments.  They belong to the run's configuration like the segments.
+        self._groups = grad_groups
+        self._group_sums = self._group_ws = self._group_coef = self._group_seg_index = None
+        self.group_values = None   # what the last measured window leaves for the log: {"norm": ..., ["clip", "skipped", ["ema"]]} device tensors
+        if grad_groups is not None:
+            if [s for s, _ in grad_groups.refined] != self._refined_base(grad_groups):
+                raise ValueError("grad_groups was resolved against other parameter segments than this optimizer's")
+            dev = model._flat.device
+            self._group_sums = torch.zeros(grad_groups.n_groups, dtype=torch.float32, device=dev)
+            if grad_groups.clip is not None:   # a frozen segment (group -1) takes the factor 1 appended behind the groups': it is never read
+                self._group_seg_index = torch.tensor([g if g >= 0 else grad_groups.n_groups for _, g in grad_groups.refined], dtype=torch.int64, device=dev)
+
+    def _refined_base(self, groups) -> list:
+        """The refined segments this optimizer expects of ``groups``: its own segments (or one over everything) cut at the group boundaries."""
+        from .grad_groups import refine
+        return [s for s, _ in refine(self._segments, (groups.names, groups.seg_end, groups.seg_group))]
+
+    # ---- gradient groups ---------------------------------------------------------------------------------------------------------------------
+    def measure_grad_group_sums(self) -> Tensor:
+        """ONE ``ssi_sumsq_groups`` launch over the flat gradient buffer: the fp32 sum of squares of every group (of the raw gradients: the
+        pending scale is not in them).  Under data parallelism the reductions are finished first, as ``clip_grad_norm_`` does."""
+        m, gg = self.model, self._groups
+        sync = getattr(m, "grad_sync", None)
+        if sync is not None and hasattr(sync, "finish_deferred"):
+            sync.finish_deferred()   # the norms read every gradient
+        if self._group_ws is None:   # (updates armed under the backward only READ the gradients: nothing to wait for)
+            from . import _lib
+            need = _lib.load().ssi_sumsq_groups_workspace_bytes(m._flat_grad.numel(), len(gg.seg_end), gg.n_groups)
+            self._group_ws = torch.empty(need, dtype=torch.uint8, device=m._flat.device)
+        ops.sumsq_groups(m._flat_grad, gg.seg_end, gg.seg_group, gg.n_groups, self._group_sums, workspace=self._group_ws)
+        return self._group_sums
+
+    def apply_grad_groups(self) -> dict[str, Tensor]:
+        """After ``measure_grad_group_sums`` and whatever changes the pending scale (the global clip): the groups' norms as AdamW will see
+        the gradients, and with a clip rule the coefficients the next ``step()`` applies.  Returns the window's values for the log."""
+        gg, scale = self._groups, self.model.pending_grad_scale
+        sums = self._group_sums
+        values = {"norm": sums.sqrt() if scale is None else sums.sqrt() * scale.reshape(()).abs()}
+        if gg.clip is not None:
+            coef = gg.clip.update(sums, scale)
+            self._group_coef = torch.cat([coef, torch.ones(1, dtype=torch.float32, device=coef.device)]).index_select(0, self._group_seg_index)
+            values["clip"], values["skipped"] = coef, gg.clip.skipped
+            if gg.clip.adaptive is not None:
+                values["ema"] = gg.clip.gamma
+        self.group_values = values
+        return values
 
     def _update(self, lo: int, hi: int, g: dict, step: int, scale: Tensor | None, skip_nonfinite_scale: bool = False) -> None:
         """AdamW on the elements ``[lo, hi)`` of the flat buffers: the plain kernel, or with segments the segmented one on those that reach
         into the slice (nothing at all where every one of them is frozen)."""
         m = self.model
         bufs = (m._flat[lo:hi], m._flat_grad[lo:hi], self._exp_avg[lo:hi], self._exp_avg_sq[lo:hi])
-        if self._segments is None:
+        if self._group_coef is not None:
+            refined = self._groups.refined
+            a = next(k for k, (s, _) in enumerate(refined) if s.end > lo)
+            b = next((k for k, (s, _) in enumerate(refined) if s.start >= hi), len(refined))
+            segs = clip_segments([s for s, _ in refined[a:b]], lo, hi)
+            if all(s.frozen for s in segs):
+                return
+            lr, wd = float(g["lr"]), float(g["weight_decay"])
+            ops.adamw_step_seg(*bufs, seg_end=[s.end - lo for s in segs], seg_lr=[lr * s.lr_scale for s in segs],
+                               seg_weight_decay=[wd if s.weight_decay is None else s.weight_decay for s in segs],
+                               seg_frozen=[s.frozen for s in segs], beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], step=step,
+                               grad_scale_dev=scale, zero_grad=False, skip_nonfinite_scale=skip_nonfinite_scale, sr_seed=self._sr_seed,
+                               elem_offset=lo, seg_scale_dev=self._group_coef[a:b])
+        elif self._segments is None:
             ops.adamw_step(*bufs, lr=float(g["lr"]), beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"],
                            step=step, grad_scale_dev=scale, zero_grad=False, skip_nonfinite_scale=skip_nonfinite_scale,
                            sr_seed=self._sr_seed, elem_offset=lo)
@@ -207,6 +271,8 @@ class HipAdamW(torch.optim.Optimizer):
         m = self.model
         if getattr(m, "grad_sync", None) is not None or not m._flat.is_cuda:
             return False
+        if self._groups is not None and self._groups.clip is not None:
+            return False   # a group's coefficient needs every gradient of the group first
         if self._side is None:
             self._side = torch.cuda.Stream(device=m._flat.device)
         self._armed = {"scale": grad_scale_dev.to(torch.float32).reshape(1), "done": [], "step": self._step_count + 1}
@@ -282,6 +348,7 @@ class HipAdamW(torch.optim.Optimizer):
             sync.finish_deferred()
             update(lo, hi)
         m.pending_grad_scale = None
+        self._group_coef = None   # (a window's coefficients are applied once)
         # the gradients are NOT zeroed (2.5 GB of writes per step for nothing) and the window is NOT closed here: as with torch.optim, a
         # backward that follows a step without a zero_grad in between accumulates; zero_grad (this optimizer's, the model's, or a foreign
         # one that drops every p.grad) ends the window, and the first backward after it overwrites the buffer (model protocol)
@@ -347,9 +414,16 @@ def setup_optimizer(cfg, model, optimizer_state_dict: dict[str, Any] | None = No
     sr_seed = optimizer_kwargs.pop("stochastic_rounding_seed", None)
     ema_decay = cfg.get("ema_decay") if hasattr(cfg, "get") else None   # (top level, with ema_warmup: the average is the run's, not AdamW's)
     ema_warmup = cfg.get("ema_warmup", True) if hasattr(cfg, "get") else True
+    groups = cfg.get("grad_groups") if hasattr(cfg, "get") else None   # (top level, beside param_groups: the same rule language)
+    if groups is not None:
+        if not hasattr(model, "_flat"):
+            raise ValueError(f"grad_groups needs the HIP decoder (ranges of its flat gradient buffer); {type(model).__name__} has none")
+        from .grad_groups import GradGroups
+        layout, total = model_layout(model)
+        groups = GradGroups.from_config(groups, layout, total, token_type_ranges, optimizer_kwargs.get("param_segments"), device=model._flat.device)
     if hasattr(model, "_flat"):
         optimizer = HipAdamW(model.parameters(), model=model, stochastic_rounding=stochastic, stochastic_rounding_seed=sr_seed,
-                             ema_decay=ema_decay, ema_warmup=bool(ema_warmup), **optimizer_kwargs)
+                             ema_decay=ema_decay, ema_warmup=bool(ema_warmup), grad_groups=groups, **optimizer_kwargs)
     else:  # foreign module (tests with stand-in models): the reference's own choice
         if ema_decay is not None:
             raise ValueError("ema_decay needs the HIP decoder (HipAdamW averages its flat parameter buffer); "
@@ -395,6 +469,19 @@ def scale_grads(model, scaler: Tensor | float) -> None:
     for p in model.parameters():
         if p.grad is not None:
             p.grad *= scaler.to(p.grad.device) if isinstance(scaler, Tensor) else scaler
+
+
+def clip_grad_norm_from_group_sums(model, max_norm: float, sums: Tensor) -> Tensor:
+    """``clip_grad_norm_`` when ``grad_groups`` has already summed the window's gradients per group: the global sum of squares is the fp32 sum
+    of the group sums in ascending group order (``other`` included: every trainable element), no second pass over the buffer."""
+    out = sums[0:1]
+    for k in range(1, sums.numel()):
+        out = out + sums[k:k + 1]
+    scale = model.pending_grad_scale if model.pending_grad_scale is not None else torch.ones_like(out)
+    total_norm = out.sqrt() * scale.abs()
+    coef = torch.clamp(float(max_norm) / (total_norm + 1e-6), max=1.0)
+    model.pending_grad_scale = scale * coef
+    return total_norm.reshape(())
 
 
 def clip_grad_norm_(model, max_norm: float) -> Tensor:

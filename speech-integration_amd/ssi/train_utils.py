@@ -126,6 +126,10 @@ def validate_train_cfg(cfg) -> None:
     if rules is not None and (isinstance(rules, (str, bytes)) or not hasattr(rules, "__len__") or hasattr(rules, "keys") or len(rules) == 0
                               or not all(hasattr(r, "keys") for r in rules)):
         raise ValueError(f"config field 'param_groups' must be null or a non-empty list of mappings, got {rules!r}")
+    groups = cfg.get("grad_groups")   # (the rules are matched against the model's layout later: ssi/grad_groups.py)
+    if groups is not None:
+        from .grad_groups import check_config
+        check_config(groups)
     d = cfg.get("ema_decay")
     if d is not None and (isinstance(d, bool) or not isinstance(d, (int, float)) or not math.isfinite(d) or not 0 <= d < 1):
         raise ValueError(f"config field 'ema_decay' must be null or a finite number in [0, 1), got {d!r}")

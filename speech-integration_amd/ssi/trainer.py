@@ -43,7 +43,7 @@ from .loss import CEWithChunkedOutputLoss, compute_loss
 from .lr_schedule import get_lr, setup_lr_scheduler
 from .metric_logging import WandBLoggerPatched as WandBLogger
 from .model import get_device, get_dtype, setup_llama3_2_1b
-from .optimizer import clip_grad_norm_, scale_grads, setup_optimizer
+from .optimizer import clip_grad_norm_, clip_grad_norm_from_group_sums, scale_grads, setup_optimizer
 from .train_utils import (count_token_types, count_token_types_async, get_token_type_ranges, limit_host_threads, resume_training_state,
                           validate_resume_hparams, validate_train_cfg)
 
@@ -395,6 +395,14 @@ class Trainer:
             trainable = sum(s.end - s.start for s in segments if not s.frozen)
             LOGGER.info(f"param_groups: {trainable} of {sum(s.end - s.start for s in segments)} elements of the flat parameter buffer are "
                         f"trainable, in {len(segments)} segments: {describe(segments)}")
+        self._grad_groups = getattr(self.optimizer, "_groups", None)   # (not in the reference) grad_groups: per-group gradient norms, clip
+        self._grad_group_values = None
+        if self._grad_groups is not None:
+            LOGGER.info(f"grad_groups: {self._grad_groups.describe()}"
+                        + ("" if self._grad_groups.clip is None else f"; clipped per group ({'adaptive' if self._grad_groups.clip.adaptive else 'fixed'})"))
+            saved = (self._resume_state or {}).get("cumulative_metrics", {}).get("grad_groups") if self._resume_state else None
+            if saved is not None and self._grad_groups.clip is not None:
+                self._grad_groups.clip.load_state_dict(saved)
         self.lr_scheduler = setup_lr_scheduler(cfg=self.cfg, optimizer=self.optimizer, global_step=self.global_step - 1,
                                                num_training_steps=self.cfg.max_steps)
         if self._resume_state and self.lr_scheduler is not None:
@@ -605,7 +613,8 @@ class Trainer:
         if not last_of_window:
             return
         total, self._window_valid_dev = self._window_valid_dev, None
-        if (self.cfg.get("adamw_under_backward", True) and self.cfg.clip_grad_norm is None and self.world_size == 1
+        per_group_clip = getattr(self, "_grad_groups", None) is not None and self._grad_groups.clip is not None   # needs every gradient first, too
+        if (self.cfg.get("adamw_under_backward", True) and self.cfg.clip_grad_norm is None and not per_group_clip and self.world_size == 1
                 and hasattr(self.optimizer, "overlap_with_backward")):
             self.optimizer.overlap_with_backward(1.0 / total.to(torch.float32))
 
@@ -682,6 +691,13 @@ class Trainer:
             self.tokens_train_total += window_tokens
             entry.update(global_step=self.global_step, lr=get_lr(self.optimizer), tokens_total=self.tokens_train_total,
                          max_seq_len_step=self.max_seq_len_step, grad_norm=self._grad_norm)  # (its clock is read when its copy arrives)
+            if getattr(self, "_grad_group_values", None) is not None:   # the groups' values join the entry's asynchronous copy: read when the entry is flushed
+                vals = self._grad_group_values
+                pinned = torch.empty(vals.shape, dtype=vals.dtype, pin_memory=True)
+                pinned.copy_(vals, non_blocking=True)
+                entry["arrived"] = torch.cuda.Event()
+                entry["arrived"].record()
+                entry["grad_groups"] = pinned
             now_due = (self.global_step % self.cfg.eval_steps == 0 or self.global_step % self.cfg.save_steps == 0
                        or self.global_step >= self.cfg.max_steps)
         else:
@@ -725,12 +741,28 @@ class Trainer:
         schedule.  On the HIP model the scale and the clip coefficient ride into the one-kernel AdamW (``ssi.optimizer``)."""
         scale_grads(self.model, torch.tensor(1 / window_tokens))
         max_norm = self.cfg.clip_grad_norm
-        if max_norm is not None:
-            self._grad_norm = clip_grad_norm_(self.model, max_norm=float(max_norm))
+        groups = getattr(self, "_grad_groups", None)
+        if groups is None:
+            if max_norm is not None:
+                self._grad_norm = clip_grad_norm_(self.model, max_norm=float(max_norm))
+        else:
+            # (not in the reference) grad_groups: ONE pass gives every group's sum of squares; the global norm, if it is wanted, is their sum;
+            # the groups' norms and coefficients then see the gradient as AdamW will, the global clip included
+            sums = self.optimizer.measure_grad_group_sums()
+            if max_norm is not None:
+                self._grad_norm = clip_grad_norm_from_group_sums(self.model, float(max_norm), sums)
+            values = self.optimizer.apply_grad_groups()
+            self._grad_group_values = torch.stack([values[k] for k in self._grad_group_keys()])
         self.optimizer.step()
         self.optimizer.zero_grad(set_to_none=True)
         if self.lr_scheduler is not None:
             self.lr_scheduler.step()
+
+    def _grad_group_keys(self) -> list[str]:
+        """The rows of ``_grad_group_values`` and their prefixes in the log record: grad_norm.<name>, under a clip rule grad_clip.<name> and
+        grad_skipped.<name>, in adaptive mode grad_norm_ema.<name>."""
+        clip = self._grad_groups.clip
+        return ["norm"] + ([] if clip is None else ["clip", "skipped"] + (["ema"] if clip.adaptive is not None else []))
 
     def _close_window(self, epoch: int, iter_idx: int, window_tokens: int) -> None:
         """Counters and the step's log record (``trainer.py:413-421``): one optimizer step consumed ga x batch x world samples."""
@@ -803,7 +835,7 @@ class Trainer:
             now = self._t_last_arrival = time.perf_counter()
             snapshot = {"global_step": self.global_step, "window_tokens": self.num_tokens_step, "lr": get_lr(self.optimizer), "now": now,
                         "step_seconds": now - self.t_step_start, "tokens_total": self.tokens_train_total,
-                        "max_seq_len_step": self.max_seq_len_step, "grad_norm": self._grad_norm}
+                        "max_seq_len_step": self.max_seq_len_step, "grad_norm": self._grad_norm, "grad_groups": getattr(self, "_grad_group_values", None)}
         step, type_counts = snapshot["global_step"], self._token_type_counts_total
         width = len(str(self.geometry.batches_per_epoch))
         per_type = " | ".join(f"Tokens ({kind}): {n}" for kind, n in type_counts.items())
@@ -827,6 +859,10 @@ class Trainer:
         record.update({f"n_tokens.{kind}": n for kind, n in type_counts.items()})
         if self.cfg.clip_grad_norm is not None:
             record["grad_norm"] = None if snapshot["grad_norm"] is None else float(snapshot["grad_norm"])
+        if getattr(self, "_grad_groups", None) is not None and snapshot.get("grad_groups") is not None:
+            prefix = {"norm": "grad_norm", "clip": "grad_clip", "skipped": "grad_skipped", "ema": "grad_norm_ema"}
+            for key, row in zip(self._grad_group_keys(), snapshot["grad_groups"].tolist()):
+                record.update({f"{prefix[key]}.{name}": value for name, value in zip(self._grad_groups.names, row)})
         if dev_loss is not None:
             record["dev_loss"] = dev_loss
             if self.dev_metrics is not None:  # eval_token_metrics: dev_loss.<type>, dev_acc.<type>, dev_acc_top<k>.<type>, dev_n_labels.<type>
@@ -863,13 +899,18 @@ class Trainer:
             lr_scheduler_state_dict=None if self.lr_scheduler is None else self.lr_scheduler.state_dict(),
             global_step=self.global_step, seed=SEED, training_hparams=self._data_position_hparams(), consumed_samples=self.consumed_samples,
             cumulative_metrics={"tokens_train_total": self.tokens_train_total, "token_type_counts": dict(self.token_type_counts_total),
-                                "wall_clock_seconds": elapsed})
+                                "wall_clock_seconds": elapsed, **self._grad_groups_state()})
         if self.cfg.get("ema_decay") is not None:
             # (not in the reference) the averaged weights, rounded to the model's dtype, as a checkpoint of their own under step_N/ema/ — it loads
             # like any other (checkpointer.checkpoint_dir=.../step_N/ema) — and the fp32 averages beside training_state.pt for an exact resume
             ema_state = self.optimizer.ema_state_dict()
             with self.optimizer.ema_weights():
                 self.checkpointer.save_ema_checkpoint(self.model.state_dict(), ema_state, self.global_step)
+
+    def _grad_groups_state(self) -> dict[str, Any]:
+        """(not in the reference) the clip rule's state by group name, stored with the cumulative values of the training state; nothing without one."""
+        groups = getattr(self, "_grad_groups", None)
+        return {} if groups is None or groups.clip is None else {"grad_groups": groups.clip.state_dict()}
 
     # === Cleanup =========================================================================================================
     def cleanup(self) -> None:
