@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 23 /* 23: + ssi_sumsq_groups, ssi_adamw_step_seg_gscale (per-group gradient norms of the flat buffer in one pass, a per-segment device gradient scale in the segmented AdamW; opt-in)
+#define SSI_ABI_VERSION 24 /* 24: + ssi_gemm_skinny, ssi_gemm_skinny_rope, ssi_gemm_skinny_swiglu (weight-streaming bf16 GEMMs for 1 to 64 rows: small-batch decoding; opt-in)
+                           * 23: + ssi_sumsq_groups, ssi_adamw_step_seg_gscale (per-group gradient norms of the flat buffer in one pass, a per-segment device gradient scale in the segmented AdamW; opt-in)
                            * 22: + ssi_decode_select_pen, ssi_decode_sample_pen (repetition, frequency and presence penalties inside the two selection kernels; opt-in)
                            * 21: + ssi_decode_sample (sampled decoding: temperature, top-k, top-p and a seeded Gumbel-max draw of a row's token in one launch; opt-in)
                            * 20: + ssi_attn_decode_beam, ssi_topk_logprob (beam search: decode attention through an ancestry table, the k best allowed columns of a row; opt-in)
@@ -420,6 +421,29 @@ int ssi_gemm_swiglu_fwd(int64_t M, int64_t inter, int64_t K, const void* X, int6
                         int64_t ldgu, void* ACT, int64_t ldact, int dtype, void* stream);
 int ssi_gemm_swiglu_bwd(int layout, int64_t M, int64_t inter, int64_t K, const void* DY, int64_t lddy, const void* W2, int64_t ldw,
                         const void* GU, int64_t ldgu, void* DGU, int64_t lddgu, void* dact_ws, int dtype, void* stream);
+
+/* ---- Skinny GEMMs (ABI v24; small-batch decoding: one prompt, n samples, a few beams) -----------------------------------------------------
+ * C[M, N] = A[M, K] W[N, K]^T (the NT layout), bf16 in and out, fp32 accumulation on v_mfma_f32_16x16x32_bf16, for 1 <= M <= 64: W is
+ * streamed once, no 256-row tile is filled.  A workgroup owns 16 weight rows (64 from N = 8192; SwiGLU: 32 gate + the 32 matching
+ * up rows) and every row of A, so A is read from L2 M / 16 (M / 64) times as often as W from HBM; its 8 or 4 waves share K in chunks of
+ * 64 and their partial sums are added in LDS in a fixed order — no atomics, no workspace, one launch.  The split depends on N alone: row r of C is BIT-EQUAL whatever M is and wherever r lies among the rows, and equal in every launch.  Rows >= M of A, R and positions are never read; nothing outside [M, N] of the outputs is written.
+ * Epilogues, with the rounding points of the 256-tile kernels they stand in for (on exactly representable data the results are bit-equal):
+ *   ssi_gemm_skinny         bf16(sum);  R != NULL ([M, N] at ldc): bf16(float(bf16(sum)) + R)                      = ssi_gemm(NT, ..., R)
+ *   ssi_gemm_skinny_rope    ssi_rope_inplace's rotation of heads [0, n_heads_rot) of the bf16-rounded row by positions[row] = ssi_gemm_rope;
+ *                           positions is required and clamped to [0, table_len - 1] ON THE DEVICE (no read-back, nothing indexed past the table)
+ *   ssi_gemm_skinny_swiglu  W13 = [gate rows | up rows]: ACT[M, I] = bf16(float(bf16(silu(gate))) * up) on the bf16-rounded gate and up
+ *                           = ssi_gemm_swiglu_fwd; GU[M, 2 I] = [gate | up] is written only when GU != NULL (a decode step reads it nowhere)
+ * SSI_ERR_UNSUPPORTED before any launch: dtype != SSI_BF16, M outside 0..64, N % 64, K % 64 (SwiGLU: I % 64), head_dim != 64, rotated
+ * columns beyond N.  SSI_ERR_ARG: a null pointer, a leading dimension below the row length, a base or a leading dimension that leaves rows
+ * off 16-byte boundaries.  M == 0 launches nothing. */
+#define SSI_GEMM_SKINNY_MAX_ROWS 64
+int ssi_gemm_skinny(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
+                    const void* R, int dtype, void* stream);
+int ssi_gemm_skinny_rope(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
+                         int n_heads_rot, int head_dim, const float* rope_table, int64_t table_len, const int32_t* positions, int dtype,
+                         void* stream);
+int ssi_gemm_skinny_swiglu(int64_t M, int64_t inter, int64_t K, const void* X, int64_t ldx, const void* W13, int64_t ldw, void* GU,
+                           int64_t ldgu, void* ACT, int64_t ldact, int dtype, void* stream);
 
 /* dst[c][r] = src[r][c] for a [rows, cols] matrix (both dims multiples of 8).  Keeps [in, out] copies of the projection
  * weights so that the data-gradient GEMMs use the k-contiguous operand form (refreshed once per optimizer step). */

@@ -179,10 +179,27 @@ def _prompt_table(seqs: list[Tensor], dev) -> tuple[Tensor, Tensor]:
     return table.to(dev), torch.tensor(lens, dtype=torch.int32).to(dev)
 
 
+def _separate(model, rows: int, small_batch: bool, report: dict | None = None) -> dict[str, bool]:
+    """The keyword ``prefill`` gets, once per group: a group that decodes on the skinny path prefills prompt by prompt, so that nothing of a
+    prompt's result depends on the prompts beside it; every other group's call is today's.  Such a group is counted in ``report`` (the
+    ``small_batch_groups`` of the run summary: what ran, counted where it ran)."""
+    if not (small_batch and model.takes_small_batch(rows, True)):
+        return {}
+    if report is not None:
+        report["small_batch_groups"] = report.get("small_batch_groups", 0) + 1
+    return {"separate": True}
+
+
+def _small(small_batch: bool, report: dict | None = None) -> dict:
+    """The keywords a decode step (or, with ``report``, a group) gets: none at all without the flag (the calls are then today's, argument for
+    argument)."""
+    return {} if not small_batch else {"small_batch": True} if report is None else {"small_batch": True, "report": report}
+
+
 def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_ids: Sequence[int], pad_id: int, batch_size: int = 256,
              logprobs: bool = False, device: torch.device | str | None = None, allowed_token_ids: Sequence[int] | Tensor | None = None,
              min_new_tokens: int = 0, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
-             presence_penalty: float = 0.0) -> list[Generation]:
+             presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None) -> list[Generation]:
     """Greedy continuation of every prompt (1-D integer sequences), results in INPUT order.  The token of a step is ``argmax`` over the real
     columns ``[:, :vocab_size]`` of the step's logits, with torch's first-occurrence rule.  ``pad_id`` fills the rows that have finished.
     ``logprobs=True``: the forward-only ``ops.ce_fwd_metrics`` runs on the step's logits with the chosen token as label, which gives its
@@ -195,6 +212,10 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
     is ``ops.decode_select_pen``'s — the first allowed maximum of the penalised row, with NULL masks when there is no constraint — in place of
     ``argmax`` and the cross-entropy launch; the log-probabilities stay those of the raw row, and ``n_constrained`` counts the steps whose
     token was not the raw row's first.  An id the kernel had to skip (outside the vocabulary) is a ``RuntimeError`` at the end of the group.
+    ``small_batch``: handed to every ``decode_step`` of every group; a group of 1 to ``model.skinny_max_rows`` rows then decodes unpadded on the
+    skinny GEMMs (``HipLlamaDecoder.takes_small_batch``), a larger one takes the tile path by itself.  A row's tokens and log-probabilities do
+    not depend on the rows beside it.  ``False``: not one launch or buffer differs.  ``small_batch_report`` (a dict, or None): every group that
+    took the skinny path adds 1 to its ``"small_batch_groups"``.
     Refused before any launch (``ValueError``): a penalty outside its range, an empty prompt, a prompt that with ``max_new_tokens`` exceeds the model's RoPE table or
     ``max_seq_len``; ``min_new_tokens < 0``, an allowed or stop id outside the vocabulary (under a constraint), an empty allowed set,
     ``min_new_tokens > 0`` with nothing allowed besides the stop tokens."""
@@ -227,7 +248,7 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
                                   _mask_words(masks[1]).to(device) if min_new_tokens else None, min_new_tokens)
             for group in groups:
                 for i, g in zip(group, _generate_group(model, cache, [seqs[i] for i in group], max_new_tokens, stop, int(pad_id), logprobs, con,
-                                                          *(() if pen is None else (pen,)))):
+                                                          *(() if pen is None else (pen,)), **_small(small_batch, small_batch_report))):
                     results[i] = g
     finally:
         if was_training:
@@ -236,10 +257,10 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
 
 
 def _generate_group(model, cache, seqs: list[Tensor], max_new_tokens: int, stop: Tensor, pad_id: int, logprobs: bool,
-                    con: _Constraint | None = None, pen: _Penalty | None = None) -> list[Generation]:
+                    con: _Constraint | None = None, pen: _Penalty | None = None, small_batch: bool = False, report: dict | None = None) -> list[Generation]:
     n, dev, V = len(seqs), model.device, model.vocab_size
     chosen = con is not None or pen is not None       # the token comes from a selection kernel, not from argmax
-    logits = model.prefill(cache, seqs, max_new_tokens=max_new_tokens)
+    logits = model.prefill(cache, seqs, max_new_tokens=max_new_tokens, **_separate(model, n, small_batch, report))
     alive = torch.ones(n, dtype=torch.bool, device=dev)
     own_slot = torch.arange(n, dtype=torch.int32, device=dev)
     no_slot = torch.full_like(own_slot, -1)
@@ -293,7 +314,7 @@ def _generate_group(model, cache, seqs: list[Tensor], max_new_tokens: int, stop:
             break
         if (t + 1) % READBACK_EVERY == 0 and not bool(alive.any()):   # the read-back
             break
-        logits = model.decode_step(cache, torch.where(alive, tok, torch.zeros_like(tok)), torch.where(alive, own_slot, no_slot))
+        logits = model.decode_step(cache, torch.where(alive, tok, torch.zeros_like(tok)), torch.where(alive, own_slot, no_slot), **_small(small_batch))
     host_out, host_n, host_stop, host_cum = out.cpu(), n_gen.cpu().tolist(), stop_tok.cpu().tolist(), cum.cpu().tolist()
     if int(cache.errors) != 0:
         raise RuntimeError(f"generate: the K/V cache kernels refused {int(cache.errors)} rows (a destination or a slot outside the cache)")
@@ -327,7 +348,7 @@ def _check_beam(beam_width, length_penalty, n_best) -> tuple[int, float, int]:
 def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_tokens: int, stop_token_ids: Sequence[int], pad_id: int,
                 length_penalty: float = 1.0, n_best: int = 1, allowed_token_ids: Sequence[int] | Tensor | None = None, min_new_tokens: int = 0,
                 batch_size: int = 256, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
-                presence_penalty: float = 0.0) -> list[list[Generation]]:
+                presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None) -> list[list[Generation]]:
     """The ``n_best <= beam_width <= 8`` best hypotheses of every prompt, best first, in INPUT order; ``cumulative_logprob`` (the sum of the
     tokens' log-probabilities under the unconstrained distribution) and ``score`` are always set.  A group holds ``batch_size // beam_width``
     prompts, so a step is at most ``batch_size`` rows.  The rules, with ``W = beam_width``:
@@ -344,7 +365,8 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
     7. The result: the pool by final score descending (stable in the order of joining), cut to ``n_best``.
 
     Refused before any launch (``ValueError``): the three beam arguments outside their ranges, a penalty off its neutral value (vLLM's beam
-    search ignores them, and ``ssi_topk_logprob`` knows none), and everything ``generate`` refuses."""
+    search ignores them, and ``ssi_topk_logprob`` knows none), and everything ``generate`` refuses.
+    ``small_batch``: handed to every ``decode_step_beam`` (``generate``'s rule, on the group's ``prompts * beam_width`` rows)."""
     W, length_penalty, n_best = _check_beam(beam_width, length_penalty, n_best)
     if _check_penalties(repetition_penalty, frequency_penalty, presence_penalty) is not None:
         raise ValueError("beam_search: repetition, frequency and presence penalties are not part of beam search")
@@ -377,7 +399,7 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
             cont_words = _mask_words(cont).to(device)
             for group in groups:
                 found = _beam_group(model, pcache, bcache, [seqs[i] for i in group], W, max_new_tokens, stop, int(pad_id), length_penalty, n_best,
-                                    cont_words, min_new_tokens)
+                                    cont_words, min_new_tokens, **_small(small_batch, small_batch_report))
                 for i, g in zip(group, found):
                     results[i] = g
     finally:
@@ -387,12 +409,12 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
 
 
 def _beam_group(model, pcache, bcache, seqs: list[Tensor], W: int, max_new: int, stop: Tensor, pad_id: int, length_penalty: float, n_best: int,
-                cont_words: Tensor, min_new: int) -> list[list[Generation]]:
+                cont_words: Tensor, min_new: int, small_batch: bool = False, report: dict | None = None) -> list[list[Generation]]:
     """One group: row ``s * W + b`` is beam ``b`` of prompt ``s``.  Everything of a step stays on the device."""
     n, dev, V, S = len(seqs), model.device, int(model.vocab_size), int(stop.numel())
     R, P, NEG = n * W, 2 * W, float("-inf")     # a pool never holds more than (W - 1) + W hypotheses; place P takes what is not stored
     i64, f32 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float32, device=dev)
-    logits = model.prefill(pcache, seqs)
+    logits = model.prefill(pcache, seqs, **_separate(model, R, small_batch, report))
     own = torch.arange(R, dtype=torch.int32, device=dev)
     seq_of = own // W
     plen = torch.tensor([int(s.numel()) for s in seqs], dtype=torch.int32).to(dev).repeat_interleave(W)
@@ -461,7 +483,7 @@ def _beam_group(model, pcache, bcache, seqs: list[Tensor], W: int, max_new: int,
         anc = anc.index_select(0, prow)
         anc[:, t] = own
         logits = model.decode_step_beam(pcache, bcache, torch.where(live, new_tok, torch.zeros_like(new_tok)).view(R),
-                                        torch.where(live.view(R), seq_of, torch.full_like(seq_of, -1)), plen, anc, t)
+                                        torch.where(live.view(R), seq_of, torch.full_like(seq_of, -1)), plen, anc, t, **_small(small_batch))
     live = scores > NEG                                 # what is still alive after max_new tokens ends by length (none in a group that ended early)
     all_beams = torch.arange(W, **i64).expand(n, W)
     join(live & ~done[:, None], scores / float(max_new ** length_penalty), scores, max_new, torch.full((n, W), -1, **i64), all_beams, None, 0)
@@ -499,7 +521,7 @@ def _check_sample(n, temperature, top_k, top_p, seed) -> tuple[int, float, int, 
 def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top_k: int = -1, top_p: float = 1.0, seed: int, max_new_tokens: int,
            stop_token_ids: Sequence[int], pad_id: int, batch_size: int = 256, allowed_token_ids: Sequence[int] | Tensor | None = None,
            min_new_tokens: int = 0, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
-           presence_penalty: float = 0.0) -> list[list[Generation]]:
+           presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None) -> list[list[Generation]]:
     """``n`` (1..8) sampled continuations of every prompt, in INPUT order and per prompt in sample order; ``cumulative_logprob`` (the tokens'
     log-probabilities under the unconstrained distribution at temperature 1, what ``ssi.score`` assigns) and ``n_kept_mean`` are always set.
     The token of a step is ``ops.decode_sample``'s with ``step`` the loop index and ``sequence = prompt index * n + sample index``: a pure function
@@ -512,7 +534,8 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
     ``ops.decode_sample_pen``'s, drawn on the penalised row (penalties before temperature, top-k and top-p); the ``n`` samples of a prompt share
     one line of the group's prompt table.  The log-probabilities stay those of the raw row.
     Refused before any launch (``ValueError``): ``n`` outside 1..8, ``temperature`` not finite or <= 0 (greedy decoding is ``generate``), ``top_p``
-    outside (0, 1], a non-integer ``top_k``, a negative ``seed``, and everything ``generate`` refuses."""
+    outside (0, 1], a non-integer ``top_k``, a negative ``seed``, and everything ``generate`` refuses.
+    ``small_batch``: handed to every decode step (``generate``'s rule, on the group's ``prompts * n`` rows)."""
     n, temperature, top_k, top_p, seed = _check_sample(n, temperature, top_k, top_p, seed)
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
     max_new_tokens, batch_size, min_new_tokens, V = int(max_new_tokens), int(batch_size), int(min_new_tokens), int(model.vocab_size)
@@ -550,7 +573,7 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
                                   _mask_words(masks[1]).to(device) if min_new_tokens else None, min_new_tokens)
             for group in groups:
                 found = _sample_group(model, caches, [seqs[i] for i in group], group, n, draw, max_new_tokens, stop, int(pad_id), con,
-                                      *(() if pen is None else (pen,)))
+                                      *(() if pen is None else (pen,)), **_small(small_batch, small_batch_report))
                 for i, g in zip(group, found):
                     results[i] = g
     finally:
@@ -560,14 +583,14 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
 
 
 def _sample_group(model, caches, seqs: list[Tensor], index: list[int], n: int, draw: dict, max_new: int, stop: Tensor, pad_id: int,
-                  con: _Constraint | None, pen: _Penalty | None = None) -> list[list[Generation]]:
+                  con: _Constraint | None, pen: _Penalty | None = None, small_batch: bool = False, report: dict | None = None) -> list[list[Generation]]:
     """One group: row ``s * n + j`` is sample ``j`` of the group's prompt ``s``, whose place in the input is ``index[s]``."""
     n_p, dev, V = len(seqs), model.device, int(model.vocab_size)
     R = n_p * n
     if n == 1:
-        logits = model.prefill(caches[0], seqs, max_new_tokens=max_new)
+        logits = model.prefill(caches[0], seqs, max_new_tokens=max_new, **_separate(model, R, small_batch, report))
     else:
-        logits = model.prefill(caches[0], seqs)[:n_p].repeat_interleave(n, dim=0)      # step 0: the prompt's row, once per sample
+        logits = model.prefill(caches[0], seqs, **_separate(model, R, small_batch, report))[:n_p].repeat_interleave(n, dim=0)      # step 0: the prompt's row, once per sample
     number = (torch.tensor(index, dtype=torch.int64) * n).repeat_interleave(n) + torch.arange(n, dtype=torch.int64).repeat(n_p)
     sequence = torch.where(number >= 2 ** 31, number - 2 ** 32, number).to(torch.int32).to(dev)      # (the kernel reads it as unsigned)
     own = torch.arange(R, dtype=torch.int32, device=dev)
@@ -617,10 +640,10 @@ def _sample_group(model, caches, seqs: list[Tensor], index: list[int], n: int, d
         if (t + 1) % READBACK_EVERY == 0 and not bool(alive.any()):   # the read-back
             break
         if n == 1:
-            logits = model.decode_step(caches[0], torch.where(alive, new, torch.zeros_like(new)), torch.where(alive, own, no_slot))
+            logits = model.decode_step(caches[0], torch.where(alive, new, torch.zeros_like(new)), torch.where(alive, own, no_slot), **_small(small_batch))
         else:
             logits = model.decode_step_beam(caches[0], caches[1], torch.where(alive, new, torch.zeros_like(new)),
-                                            torch.where(alive, seq_of, no_slot), plen, anc, t)
+                                            torch.where(alive, seq_of, no_slot), plen, anc, t, **_small(small_batch))
     host_out, host_n, host_stop, host_cum = out.cpu(), n_gen.cpu().tolist(), stop_tok.cpu().tolist(), cum.cpu().tolist()
     host_kept = kept_sum.cpu().tolist()
     errors = sum(int(c.errors) for c in caches)
@@ -690,7 +713,9 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     entries, ``index`` 0.. in sample order, and the summary gains ``"sampled": True``, ``"n"`` and ``"kept_tokens_mean"`` (the mean over all generated
     tokens of the size of the set each was drawn from).  Not together with ``beam_width > 1``.
     ``repetition_penalty``, ``frequency_penalty``, ``presence_penalty`` in ``kw`` go to ``generate`` / ``sample`` (``beam_search`` refuses them off
-    their neutral values); when any is set the summary gains the three values, and on the greedy path ``"constrained_tokens"``."""
+    their neutral values); when any is set the summary gains the three values, and on the greedy path ``"constrained_tokens"``.
+    ``small_batch=True`` in ``kw`` goes to whichever loop runs, and the summary gains ``"small_batch_groups"``: the number of groups that decoded on
+    the skinny path.  ``False`` (the default) is not passed on and adds no key."""
     if in_path is not None:
         ids, prompts = _read_prompts(tokenizer, in_path)
     elif prompts is None:
@@ -701,6 +726,16 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     if stop_token_ids is None:
         stop_token_ids = default_stop_token_ids(tokenizer)
     kw.setdefault("pad_id", int(getattr(tokenizer, "pad_id", 0) or 0))
+    if not kw.pop("small_batch", False):
+        return _run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, kw)
+    report = {"small_batch_groups": 0}          # counted by the loop, group by group, where the path is taken
+    summary = _run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding,
+                        dict(kw, small_batch=True, small_batch_report=report))
+    return dict(summary, **report)
+
+
+def _run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, kw: dict) -> dict[str, Any]:
+    """``generate_file`` behind its input handling: picks the loop (greedy, beam search, sampling), writes the lines, returns the summary."""
     beam = {k: kw.pop(k) for k in ("beam_width", "length_penalty", "n_best") if k in kw}
     pen = _check_penalties(kw.get("repetition_penalty", 1.0), kw.get("frequency_penalty", 0.0), kw.get("presence_penalty", 0.0))
     pen_summary = {} if pen is None else {"repetition_penalty": pen.r, "frequency_penalty": pen.f, "presence_penalty": pen.p}

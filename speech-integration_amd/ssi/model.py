@@ -417,6 +417,15 @@ class HipLlamaDecoder(nn.Module):
     def _padded_rows(self, n: int) -> int:  # n rows that are not sequences (prefill's last tokens, a decode step) as whole MFMA tiles
         return _align(max(n, 1), VOCAB_ALIGN) if self._mfma_shapes() else n
 
+    # the largest row count a ``small_batch`` decode step runs unpadded on the skinny GEMMs (at most ``_lib.GEMM_SKINNY_MAX_ROWS``); how the value
+    # was chosen: README, "Small-batch decoding"
+    skinny_max_rows = 64
+
+    def takes_small_batch(self, rows: int, small_batch: bool) -> bool:
+        """Does a decode step of ``rows`` rows with this flag run on the skinny GEMMs?  (The flag alone never does: fp32 models, shapes off the
+        MFMA path and more rows than the limit keep the tile path, launch for launch.)"""
+        return bool(small_batch) and self._mfma_shapes() and 1 <= rows <= min(self.skinny_max_rows, _lib.GEMM_SKINNY_MAX_ROWS)
+
     # ---- forward: decoder stack --------------------------------------------------------------------------------------
     @staticmethod
     def _document_ranges(input_pos: Tensor, max_pos: Optional[int] = None) -> tuple[Tensor, Tensor, Tensor]:
@@ -526,41 +535,52 @@ class HipLlamaDecoder(nn.Module):
         ``"train"``: a set per layer, kept for the backward (``qkv.{l}`` ..., ``h0``, ``h{l+1}``; ``xn1`` / ``att`` of all layers in ONE buffer
         each: the batched weight gradients read a group of layers at a stride).  ``"x"`` (eval, teacher, prefill): one set (``qkv.x`` ...),
         ``hx0`` / ``hx1`` in turn.  ``"g"`` (``decode_step``): one set (``qkv.g`` ...), ONE norm output and rstd (``xn.g``, ``rstd.g``), no lse,
-        ``h1.g`` / ``h2.g`` in turn.  The modes share no buffer: a forward of one may run between a training forward and its backward.
+        ``h1.g`` / ``h2.g`` in turn.  ``"s"`` (a small-batch ``decode_step``: unpadded rows, skinny GEMMs): ``"g"``'s set under names of its own
+        (``qkv.s`` ..., ``xn.s``, ``rstd.s``, ``h1.s`` / ``h2.s``; no ``gu``: nothing reads it in a decode step).  The modes share no buffer:
+        a forward of one may run between a training forward and its backward.
         ``below``: the records of layers ``0 .. l - 1``.  In modes ``x`` and ``g`` nothing but ``h_out`` of layers 1 and 2 is looked up again."""
         if mode != "train" and 3 <= l < self.num_layers:
             return below[l - 2]   # (the two h buffers take turns: what layer l - 2 read and wrote)
         A, dt, f32, L, train = self._arena, self.dtype, torch.float32, self.num_layers, mode == "train"
         D, I, Q = self.embed_dim, self.intermediate_dim, self.num_heads * self.head_dim
-        nm = (lambda s: f"{s}.{l}") if train else (lambda s: f"{s}.x") if mode == "x" else (lambda s: s.rstrip("12") + ".g")
+        nm = (lambda s: f"{s}.{l}") if train else (lambda s: f"{s}.x") if mode == "x" else (lambda s: s.rstrip("12") + "." + mode)
         h_in = below[-1].h_out if below else A.get("h0" if train else nm("h0"), (rows, D), dt)
         if l == L:
-            return _LayerBufs(h_in, A.get("hn" if train else "xn.g" if mode == "g" else "hn.x", (rows, D), dt),
-                              A.get("rstdf" if train else "rstd.g" if mode == "g" else "rstdf.x", (rows,), f32))
-        h_out = A.get(f"h{l + 1}" if train else f"hx{l & 1}" if mode == "x" else f"h{1 + (l & 1)}.g", (rows, D), dt)
+            return _LayerBufs(h_in, A.get("hn" if train else "hn.x" if mode == "x" else "xn." + mode, (rows, D), dt),
+                              A.get("rstdf" if train else "rstdf.x" if mode == "x" else "rstd." + mode, (rows,), f32))
+        h_out = A.get(f"h{l + 1}" if train else f"hx{l & 1}" if mode == "x" else f"h{1 + (l & 1)}.{mode}", (rows, D), dt)
         if below and not train:
             return below[-1]._replace(h_in=h_in, h_out=h_out)
         xn1 = A.get("xn1.all", (L, rows, D), dt)[l] if train else A.get(nm("xn1"), (rows, D), dt)
         att = A.get("att.all", (L, rows, Q), dt)[l] if train else A.get(nm("att"), (rows, Q), dt)
-        lse = None if mode == "g" else A.get(nm("lse"), (B * self.num_heads * S,), f32)
+        lse = None if mode in ("g", "s") else A.get(nm("lse"), (B * self.num_heads * S,), f32)
         return _LayerBufs(h_in, xn1, A.get(nm("rstd1"), (rows,), f32), A.get(nm("qkv"), (rows, self.qkv_dim), dt), att, lse,
                           A.get(nm("hmid"), (rows, D), dt), A.get(nm("xn2"), (rows, D), dt), A.get(nm("rstd2"), (rows,), f32),
-                          A.get(nm("gu"), (rows, 2 * I), dt), A.get(nm("act"), (rows, I), dt), h_out)
+                          None if mode == "s" else A.get(nm("gu"), (rows, 2 * I), dt), A.get(nm("act"), (rows, I), dt), h_out)
 
     def _run_stack(self, mode: str, tok: Tensor, B: int, S: int, seq_len: int, pos: Optional[Tensor], attend) -> tuple[list, _LayerBufs]:
         """Embedding, every layer, final norm on ``mode``'s buffers -> (the layers' records, the final norm's).  ``attend(l, record)``: the one step
-        in which a forward and a decode step differ.  RoPE (rows of ``seq_len`` positions, or ``pos``) and SwiGLU ride in their GEMMs' epilogues."""
+        in which a forward and a decode step differ.  RoPE (rows of ``seq_len`` positions, or ``pos``) and SwiGLU ride in their GEMMs' epilogues.
+        Mode ``"s"``: the four GEMMs are the skinny entries (1 to ``skinny_max_rows`` unpadded rows, ``pos`` required), everything else the same."""
+        if mode == "s":
+            qkv_gemm = lambda x, w, out: ops.gemm_skinny_rope(x, w, out, self.num_heads + self.num_kv_heads, self.head_dim, self._rope, pos)  # noqa: E731
+            res_gemm = lambda x, w, out, res: ops.gemm_skinny(x, w, out, residual=res)  # noqa: E731
+            mlp_gemm = lambda x, w, gu, act: ops.gemm_skinny_swiglu(x, w, None, act)  # noqa: E731
+        else:
+            qkv_gemm = lambda x, w, out: ops.gemm_rope(x, w, out, seq_len, self.num_heads + self.num_kv_heads, self.head_dim, self._rope, positions=pos)  # noqa: E731
+            res_gemm = lambda x, w, out, res: self._gemm(GEMM_NT, x, w, out, residual=res)  # noqa: E731
+            mlp_gemm = ops.gemm_swiglu_fwd
         layers, b = [], self._layer_bufs(mode, 0, B * S, B, S)
         ops.embed_fwd(tok, self._view("emb"), b.h_in, self.vocab_size)
         for l in range(self.num_layers):
             layers.append(b)
             ops.rmsnorm_fwd(b.h_in, self._view(f"L{l}.sa_norm"), b.xn1, b.rstd1, self.norm_eps)
-            ops.gemm_rope(b.xn1, self._view(f"L{l}.wqkv"), b.qkv, seq_len, self.num_heads + self.num_kv_heads, self.head_dim, self._rope, positions=pos)
+            qkv_gemm(b.xn1, self._view(f"L{l}.wqkv"), b.qkv)
             attend(l, b)
-            self._gemm(GEMM_NT, b.att, self._view(f"L{l}.wo"), b.hmid, residual=b.h_in)
+            res_gemm(b.att, self._view(f"L{l}.wo"), b.hmid, b.h_in)
             ops.rmsnorm_fwd(b.hmid, self._view(f"L{l}.mlp_norm"), b.xn2, b.rstd2, self.norm_eps)
-            ops.gemm_swiglu_fwd(b.xn2, self._view(f"L{l}.w13"), b.gu, b.act)
-            self._gemm(GEMM_NT, b.act, self._view(f"L{l}.w2"), b.h_out, residual=b.hmid)
+            mlp_gemm(b.xn2, self._view(f"L{l}.w13"), b.gu, b.act)
+            res_gemm(b.act, self._view(f"L{l}.w2"), b.h_out, b.hmid)
             b = self._layer_bufs(mode, l + 1, B * S, B, S, layers)
         ops.rmsnorm_fwd(b.h_in, self.norm.scale, b.xn1, b.rstd1, self.norm_eps)
         return layers, b
@@ -713,13 +733,16 @@ class HipLlamaDecoder(nn.Module):
     PREFILL_ROWS_PER_BATCH = 8    # ... and run this many rows at a time
 
     @torch.no_grad()
-    def prefill(self, cache: "KVCache", prompts, max_new_tokens: int = 0) -> Tensor:
+    def prefill(self, cache: "KVCache", prompts, max_new_tokens: int = 0, separate: bool = False) -> Tensor:
         """Prompt ``i`` (a 1-D integer sequence) fills slot ``i`` of ``cache``: the prompts are packed into rows on the host
         (``ssi.score.prefill_batches``: first-fit decreasing, ``input_pos`` restarting with every prompt), the packed forward the dev
         loss and ``ssi.score`` use runs block-causal over them with every layer's K / V scattered into the cache, and the final norm's
         rows of the prompts' LAST tokens alone go through the tied head.  Returns ``[n_prompts, vocab_pad]`` logits (fresh tensor) and
         sets the cache's lengths; slots beyond the prompts are emptied.  ``max_new_tokens``: what ``decode_step`` will add, checked here
-        against the cap, the RoPE table and ``max_seq_len`` (``ValueError`` before any launch)."""
+        against the cap, the RoPE table and ``max_seq_len`` (``ValueError`` before any launch).
+        ``separate`` (the small-batch loops): every prompt runs as a packed forward of its own, one row that starts at position 0.  Where a
+        prompt lies in a packed row, and how many rows the forward has (which picks the K split of its GEMMs), enter the bits of its K / V
+        and of its logits; prompt by prompt they are a function of the prompt alone, whatever else is in the group."""
         from .score import prefill_batches
         seqs = [torch.as_tensor(p, dtype=torch.int64).reshape(-1) for p in prompts]
         lens = [int(s.numel()) for s in seqs]
@@ -732,7 +755,17 @@ class HipLlamaDecoder(nn.Module):
         row_len = min(max(min(self.PREFILL_ROW_LEN, sum(lens)), max(lens)), self._rope.shape[0])
         dev = self.device
         hlast = torch.zeros((self._padded_rows(n), self.embed_dim), dtype=self.dtype, device=dev)   # (pad rows: zeros)
-        for tokens, input_pos, dest, last_at, last_of in prefill_batches(seqs, cap, row_len, self.PREFILL_ROWS_PER_BATCH):
+
+        def batches():
+            if not separate:
+                yield from prefill_batches(seqs, cap, row_len, self.PREFILL_ROWS_PER_BATCH)
+                return
+            for i, s in enumerate(seqs):   # slot 0 of a one-prompt plan is slot i of the cache
+                for tokens, input_pos, dest, last_at, last_of in prefill_batches([s], cap, min(lens[i], self._rope.shape[0]), 1):
+                    yield tokens, input_pos, torch.where(dest >= 0, dest + i * cap, dest), last_at, last_of + i
+
+        for tokens, input_pos, dest, last_at, last_of in batches():
+            row_len = tokens.shape[1]
             tokens, input_pos, dest = tokens.to(dev), input_pos.to(dev), dest.to(dev)
             tokens, input_pos, _, _ = self._right_pad(tokens, input_pos)
             B, S = tokens.shape
@@ -752,21 +785,25 @@ class HipLlamaDecoder(nn.Module):
                 raise ValueError(f"the K/V cache is not this model's: {tuple(t.shape)} {t.dtype} on {t.device}, expected {want} {self.dtype} on {self.device}")
 
     @torch.no_grad()
-    def decode_step(self, cache: "KVCache", tokens: Tensor, slots: Tensor) -> Tensor:
+    def decode_step(self, cache: "KVCache", tokens: Tensor, slots: Tensor, small_batch: bool = False) -> Tensor:
         """One new token per live sequence: ``tokens`` (int64 ``[rows]``) and ``slots`` (int32 ``[rows]``; -1 = an inert row: no attention,
         no cache write, a zero attention row) on the device.  Row r runs at position ``cache.lengths[slots[r]]``: its K / V go there, it
         attends over the ``length + 1`` keys of its slot, and the length advances — all on the device, nothing is read back.  Returns the
         ``[rows, vocab_pad]`` logits (fresh tensor).  On the MFMA shapes the rows are padded to a multiple of 256 with inert rows, which
         makes every GEMM of the step one of the training step's tiles; all activations live in arena buffers of their own (``*.g``), so a
         step may run between a training forward and its backward.  A slot whose length has reached the cap is not written (its K / V
-        would land in the next slot) and is counted in ``cache.errors``; ``prefill`` refuses what would get there."""
+        would land in the next slot) and is counted in ``cache.errors``; ``prefill`` refuses what would get there.
+        ``small_batch`` (with 1 to ``skinny_max_rows`` rows on the MFMA shapes; otherwise without effect): the rows are NOT padded, the layer
+        GEMMs and the head run on the weight-streaming skinny kernels and the activations live in the ``*.s`` buffers; norms, embedding,
+        ``kv_store`` and ``attn_decode`` are the same launches on fewer rows.  A row's logits do not depend on the rows beside it."""
         self._check_cache(cache)
         if tokens.dim() != 1 or tokens.dtype != torch.int64 or slots.shape != tokens.shape or slots.dtype != torch.int32:
             raise ValueError("decode_step: tokens is int64 [rows], slots int32 [rows]")
         if not tokens.is_cuda or not slots.is_cuda:
             raise _lib.HipLibraryError("decode_step: tokens and slots must live on the GPU (no CPU fallback)")
         n = tokens.numel()
-        R = self._padded_rows(n)
+        small = self.takes_small_batch(n, small_batch)
+        R = n if small else self._padded_rows(n)
         H, KV, hd, dev = self.num_heads, self.num_kv_heads, self.head_dim, self.device
         tok = torch.zeros(R, dtype=torch.int64, device=dev)          # pad rows: token 0, slot -1, position 0
         slot = torch.full((R,), -1, dtype=torch.int32, device=dev)
@@ -785,19 +822,20 @@ class HipLlamaDecoder(nn.Module):
             ops.kv_store(b.qkv, dest, cache.k[l], cache.v[l], H, KV, hd, n_bad=cache.errors)
             ops.attn_decode(b.qkv, cache.k[l], cache.v[l], slot, kv_len, b.att, None, H, KV, hd, n_bad=cache.errors)
 
-        logits = self._head_logits(self._run_stack("g", tok, R, 1, R, pos, attend)[1].xn1)   # R rows of one position each; RoPE by ``pos``
+        logits = self._head_logits(self._run_stack("s" if small else "g", tok, R, 1, R, pos, attend)[1].xn1, skinny=small)   # R rows of one position each; RoPE by ``pos``
         cache.lengths.index_add_(0, slot.clamp(min=0).long(), write.to(torch.int32))
         return logits[:n]
 
     @torch.no_grad()
     def decode_step_beam(self, prompt_cache: "KVCache", beam_cache: "KVCache", tokens: Tensor, prompt_slot: Tensor, prompt_len: Tensor,
-                         anc: Tensor, t: int) -> Tensor:
+                         anc: Tensor, t: int, small_batch: bool = False) -> Tensor:
         """Step ``t`` of beam search: row ``r`` (one hypothesis) runs ``tokens[r]`` at position ``prompt_len[r] + t``.  Its K / V go to the beam
         cache at ``(r, t)``, and it attends over the ``prompt_len[r]`` keys of slot ``prompt_slot[r]`` of the prompt cache (what ``prefill``
         filled; read only here) and the generated positions ``i <= t`` of the beam cache at slots ``anc[r, i]`` — ``anc`` (int32
         ``[rows, >= t + 1]``, contiguous) is the hypothesis' ancestry and the caller has set ``anc[r, t] = r``.  ``prompt_slot[r] = -1``: an inert
         row.  Everything on the device; rows padded to whole tiles and activations in the ``*.g`` buffers, as ``decode_step``.  Neither cache's
-        ``lengths`` are read or changed; refused indices are counted in ``beam_cache.errors``.  Returns ``[rows, vocab_pad]`` logits (fresh)."""
+        ``lengths`` are read or changed; refused indices are counted in ``beam_cache.errors``.  Returns ``[rows, vocab_pad]`` logits (fresh).
+        ``small_batch``: as in ``decode_step`` (unpadded rows, skinny GEMMs, ``*.s`` buffers, where ``takes_small_batch`` holds)."""
         self._check_cache(prompt_cache)
         self._check_cache(beam_cache)
         n, t = tokens.numel(), int(t)
@@ -810,7 +848,8 @@ class HipLlamaDecoder(nn.Module):
                              f"and an ancestry of width {anc.shape[1]}")
         if not all(x.is_cuda for x in (tokens, prompt_slot, prompt_len, anc)):
             raise _lib.HipLibraryError("decode_step_beam: tokens, prompt_slot, prompt_len and anc must live on the GPU (no CPU fallback)")
-        R = self._padded_rows(n)
+        small = self.takes_small_batch(n, small_batch)
+        R = n if small else self._padded_rows(n)
         H, KV, hd, dev = self.num_heads, self.num_kv_heads, self.head_dim, self.device
         tok = torch.zeros(R, dtype=torch.int64, device=dev)           # pad rows: token 0, slot -1, position 0
         slot = torch.full((R,), -1, dtype=torch.int32, device=dev)
@@ -827,10 +866,10 @@ class HipLlamaDecoder(nn.Module):
             ops.attn_decode_beam(b.qkv, prompt_cache.k[l], prompt_cache.v[l], beam_cache.k[l], beam_cache.v[l], slot, plen, gen_len, anc_r, b.att,
                                  None, H, KV, hd, n_bad=beam_cache.errors)
 
-        return self._head_logits(self._run_stack("g", tok, R, 1, R, pos, attend)[1].xn1)[:n]
+        return self._head_logits(self._run_stack("s" if small else "g", tok, R, 1, R, pos, attend)[1].xn1, skinny=small)[:n]
 
     # ---- tied LM head ------------------------------------------------------------------------------------------------
-    def _head_logits(self, hn: Tensor, arena_name: Optional[str] = None) -> Tensor:
+    def _head_logits(self, hn: Tensor, arena_name: Optional[str] = None, skinny: bool = False) -> Tensor:
         """logits [T, vocab_pad] = hn E^T.  Callers of the public ``forward`` get a FRESH tensor (as torchtune returns): logits kept
         from one batch must survive the next forward.  Only the fused loss passes an arena name (its buffer never leaves the model)."""
         T = hn.shape[0]
@@ -838,7 +877,10 @@ class HipLlamaDecoder(nn.Module):
             logits = torch.empty((T, self.vocab_pad), dtype=self.dtype, device=self.device)
         else:
             logits = self._arena.get(arena_name, (T, self.vocab_pad), self.dtype)
-        ops.gemm(GEMM_NT, hn, self._view("emb"), logits)
+        if skinny:   # (a small-batch decode step: 1 to skinny_max_rows rows)
+            ops.gemm_skinny(hn, self._view("emb"), logits)
+        else:
+            ops.gemm(GEMM_NT, hn, self._view("emb"), logits)
         return logits
 
     def _head_backward(self, dlogits: Tensor, hn: Tensor, alpha_dev: Optional[Tensor]) -> Tensor:

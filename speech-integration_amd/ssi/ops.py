@@ -10,7 +10,7 @@ from torch import Tensor
 from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
-__all__ = ["lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "attn_decode_beam", "decode_select", "decode_sample", "decode_select_pen", "decode_sample_pen", "decode_penalty_lds_bytes", "topk_logprob", "swiglu_fwd",
+__all__ = ["gemm_skinny", "gemm_skinny_rope", "gemm_skinny_swiglu", "lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "attn_decode_beam", "decode_select", "decode_sample", "decode_select_pen", "decode_sample_pen", "decode_penalty_lds_bytes", "topk_logprob", "swiglu_fwd",
            "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "ema_update", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
@@ -539,6 +539,41 @@ def gemm_swiglu_bwd(layout: int, dy: Tensor, w2: Tensor, gu: Tensor, dgu: Tensor
     check(_lib.load().ssi_gemm_swiglu_bwd(layout, M, inter, K, ptr(dy), dy.stride(0), ptr(w2), w2.stride(0), ptr(gu), gu.stride(0),
                                           ptr(dgu), dgu.stride(0), ptr(dact_ws), dtype_code(dy.dtype), stream_ptr()),
           "ssi_gemm_swiglu_bwd")
+
+
+def gemm_skinny(a: Tensor, w: Tensor, c: Tensor, *, residual: Tensor | None = None) -> None:
+    """c = a @ w^T (+ residual) for 1 to 64 rows of bf16: the weight-streaming kernel of small-batch decoding (``ssi_gemm``'s rounding points)."""
+    assert a.dim() == 2 and w.dim() == 2 and c.dim() == 2 and a.stride(1) == 1 and w.stride(1) == 1 and c.stride(1) == 1
+    M, K = a.shape
+    N = w.shape[0]
+    assert w.shape[1] == K and c.shape == (M, N) and a.dtype == w.dtype == c.dtype
+    if residual is not None:
+        assert residual.shape == c.shape and residual.stride() == c.stride() and residual.dtype == c.dtype
+    check(_lib.load().ssi_gemm_skinny(M, N, K, ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(c), c.stride(0), ptr(residual),
+                                      dtype_code(c.dtype), stream_ptr()), "ssi_gemm_skinny")
+
+
+def gemm_skinny_rope(a: Tensor, w: Tensor, c: Tensor, n_heads_rot: int, head_dim: int, table: Tensor, positions: Tensor) -> None:
+    """``gemm_skinny`` followed by ``rope_`` on the first ``n_heads_rot`` heads of every row, by ``positions`` (required), in one launch."""
+    assert a.dim() == 2 and w.dim() == 2 and c.dim() == 2 and a.stride(1) == 1 and w.stride(1) == 1 and c.stride(1) == 1
+    M, K = a.shape
+    N = w.shape[0]
+    assert w.shape[1] == K and c.shape == (M, N) and a.dtype == w.dtype == c.dtype
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.shape[1] * 2 == head_dim
+    assert positions.dtype == torch.int32 and positions.numel() == M and positions.is_contiguous()
+    check(_lib.load().ssi_gemm_skinny_rope(M, N, K, ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(c), c.stride(0), n_heads_rot, head_dim,
+                                           ptr(table), table.shape[0], ptr(positions), dtype_code(a.dtype), stream_ptr()), "ssi_gemm_skinny_rope")
+
+
+def gemm_skinny_swiglu(x: Tensor, w13: Tensor, gu: Tensor | None, act: Tensor) -> None:
+    """act = silu(gate) * up of ``x @ w13^T`` = [gate | up] for 1 to 64 rows, one launch; ``gu`` (``None``: not written) gets [gate | up]."""
+    M, K = x.shape
+    inter = act.shape[1]
+    assert w13.shape == (2 * inter, K) and act.shape[0] == M and x.stride(1) == 1 and w13.stride(1) == 1 and act.stride(1) == 1
+    assert gu is None or (gu.shape == (M, 2 * inter) and gu.stride(1) == 1 and gu.dtype == x.dtype)
+    assert x.dtype == w13.dtype == act.dtype
+    check(_lib.load().ssi_gemm_skinny_swiglu(M, inter, K, ptr(x), x.stride(0), ptr(w13), w13.stride(0), ptr(gu), 0 if gu is None else gu.stride(0),
+                                             ptr(act), act.stride(0), dtype_code(x.dtype), stream_ptr()), "ssi_gemm_skinny_swiglu")
 
 
 def transpose(src: Tensor, dst: Tensor) -> None:

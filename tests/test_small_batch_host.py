@@ -1,0 +1,194 @@
+"""CPU: the host side of small-batch decoding — the ABI names the three skinny entries, the ``small_batch`` argument reaches every decode step
+(and ``prefill``) of the groups that qualify and no other call, ``gen.small_batch`` is parsed and handed on, and the run summary gains
+``small_batch_groups`` only with the flag."""
+import importlib.util
+import json
+import os
+import re
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "speech-integration_amd")
+SKINNY = (("ssi_gemm_skinny", "gemm_skinny"), ("ssi_gemm_skinny_rope", "gemm_skinny_rope"), ("ssi_gemm_skinny_swiglu", "gemm_skinny_swiglu"))
+
+
+def test_the_abi_names_the_three_entries():
+    from ssi import _lib, ops
+    header = open(os.path.join(ROOT, "include", "ssi_hip.h")).read()
+    assert int(re.search(r"#define SSI_ABI_VERSION (\d+)", header).group(1)) >= 24 and _lib.ABI_VERSION >= 24
+    assert int(re.search(r"#define SSI_GEMM_SKINNY_MAX_ROWS (\d+)", header).group(1)) == _lib.GEMM_SKINNY_MAX_ROWS == 64
+    for name, wrapper in SKINNY:
+        args = re.search(rf"\bint {name}\((.*?)\);", header, re.S).group(1)
+        assert len(args.split(",")) == len(_lib.PROTOTYPES[name][1]), name
+        assert name in _lib.PROTOTYPES and wrapper in ops.__all__ and callable(getattr(ops, wrapper))
+    from ssi.model import HipLlamaDecoder
+    assert 1 <= HipLlamaDecoder.skinny_max_rows <= _lib.GEMM_SKINNY_MAX_ROWS
+
+
+def test_the_wrappers_refuse_cpu_tensors():
+    from ssi import _lib, ops
+    a, w, c = torch.zeros(2, 64, dtype=torch.bfloat16), torch.zeros(128, 64, dtype=torch.bfloat16), torch.zeros(2, 128, dtype=torch.bfloat16)
+    with pytest.raises(_lib.HipLibraryError, match="GPU"):
+        ops.gemm_skinny(a, w, c)
+    with pytest.raises(_lib.HipLibraryError, match="GPU"):
+        ops.gemm_skinny_rope(a, w, c, 1, 64, torch.zeros(8, 32, 2), torch.zeros(2, dtype=torch.int32))
+    with pytest.raises(_lib.HipLibraryError, match="GPU"):
+        ops.gemm_skinny_swiglu(a, w, None, torch.zeros(2, 64, dtype=torch.bfloat16))
+
+
+class _Cache:
+    def __init__(self, n_slots, cap):
+        self.n_slots, self.cap, self.errors = n_slots, cap, torch.zeros(1, dtype=torch.int32)
+
+
+class _Model(torch.nn.Module):
+    """What the loops touch of the model, on the CPU: uniform logits that prefer token 3, and a record of the keywords of every call."""
+    vocab_size, vocab_pad, skinny_max_rows = 16, 16, 64
+
+    def __init__(self, mfma=True):
+        super().__init__()
+        self.device, self.mfma, self.calls = torch.device("cpu"), mfma, []
+
+    def takes_small_batch(self, rows, small_batch):
+        return bool(small_batch) and self.mfma and 1 <= rows <= self.skinny_max_rows
+
+    def check_generation_lengths(self, *a):
+        pass
+
+    def new_kv_cache(self, n_slots, cap):
+        return _Cache(n_slots, cap)
+
+    def _logits(self, rows):
+        out = torch.zeros(rows, self.vocab_pad)
+        out[:, 3] = 5.0
+        return out
+
+    def prefill(self, cache, prompts, max_new_tokens=0, **kw):
+        self.calls.append(("prefill", len(prompts), kw))
+        return self._logits(len(prompts))
+
+    def decode_step(self, cache, tokens, slots, **kw):
+        self.calls.append(("decode_step", tokens.numel(), kw))
+        return self._logits(tokens.numel())
+
+
+def _greedy(model, n_prompts, **kw):
+    from ssi.generate import generate
+    model.calls.clear()
+    out = generate(model, [[1, 2]] * n_prompts, max_new_tokens=3, stop_token_ids=[], pad_id=0, **kw)
+    assert [g.token_ids for g in out] == [[3, 3, 3]] * n_prompts
+    return list(model.calls)
+
+
+def test_the_flag_reaches_every_step_of_every_group_and_no_call_without_it():
+    m = _Model()
+    plain = _greedy(m, 5)
+    assert plain and all(kw == {} for _, _, kw in plain)                  # today's calls, argument for argument
+    assert _greedy(m, 5, small_batch=False) == plain
+    flagged = _greedy(m, 5, small_batch=True)
+    assert [(n, r) for n, r, _ in flagged] == [(n, r) for n, r, _ in plain]
+    assert all(kw == ({"separate": True} if name == "prefill" else {"small_batch": True}) for name, _, kw in flagged)
+    # groups of 64 and of 6 rows with batch_size 64, then one of 70 rows: the flag goes to every step, the model decides per group
+    flagged = _greedy(m, 70, small_batch=True, batch_size=64)
+    assert [(n, r, kw) for n, r, kw in flagged if n == "prefill"] == [("prefill", 64, {"separate": True}), ("prefill", 6, {"separate": True})]
+    flagged = _greedy(m, 70, small_batch=True, batch_size=256)
+    assert [kw for n, _, kw in flagged if n == "prefill"] == [{}] and all(kw == {"small_batch": True} for n, _, kw in flagged if n == "decode_step")
+    # a model off the MFMA shapes: the flag is still handed down (the model ignores it), prefill stays packed
+    flagged = _greedy(_m := _Model(mfma=False), 5, small_batch=True)
+    assert [kw for n, _, kw in flagged if n == "prefill"] == [{}] and _m.takes_small_batch(5, True) is False
+
+
+def test_the_loop_counts_the_groups_that_took_the_path():
+    """``small_batch_report``: counted by the loop at each group's prefill, not derived a second time from the grouping."""
+    m = _Model()
+    for n, batch, want in ((70, 64, 2), (70, 256, 0), (1, 256, 1), (130, 64, 3)):
+        report = {}
+        _greedy(m, n, small_batch=True, batch_size=batch, small_batch_report=report)
+        assert report.get("small_batch_groups", 0) == want, (n, batch, report)
+        assert sum(kw == {"separate": True} for name, _, kw in m.calls if name == "prefill") == want
+    report = {}
+    _greedy(_Model(mfma=False), 5, small_batch=True, small_batch_report=report)
+    assert report == {}
+    report = {}
+    _greedy(m, 5, small_batch_report=report)                               # without the flag nothing is counted and nothing is passed
+    assert report == {} and all(kw == {} for _, _, kw in m.calls)
+
+
+class _Tok:
+    special_tokens = {"<|eot_id|>": 909}
+    eos_id, eom_id, eot_id, pad_id = 901, 908, 909, 904
+
+    def encode(self, text, add_bos=True, add_eos=True):
+        return ([900] if add_bos else []) + [ord(c) for c in text] + ([901] if add_eos else [])
+
+    def decode(self, ids, **kw):
+        return "".join(chr(t) for t in ids if t < 900)
+
+
+@pytest.mark.parametrize("path", ("greedy", "beam", "sample"))
+def test_the_summary_key_is_there_only_with_the_flag(tmp_path, monkeypatch, path):
+    from ssi import generate as G
+    seen = []
+
+    def one(p):
+        return G.Generation(token_ids=[65], finish_reason="length", stop_reason=None, cumulative_logprob=-1.0, prompt_len=len(p), n_kept_mean=1.0)
+
+    def loop(wrap):          # a loop that reports as the real ones do: it says itself how many groups took the path
+        def run(model, prompts, **kw):
+            seen.append(kw)
+            if "small_batch_report" in kw:
+                kw["small_batch_report"]["small_batch_groups"] += 7
+            return [wrap(one(p)) for p in prompts]
+        return run
+
+    monkeypatch.setattr(G, "generate", loop(lambda g: g))
+    monkeypatch.setattr(G, "beam_search", loop(lambda g: [g]))
+    monkeypatch.setattr(G, "sample", loop(lambda g: [g]))
+    extra = {"greedy": {}, "beam": {"beam_width": 4}, "sample": {"sample": True, "n": 2, "temperature": 0.7, "seed": 1}}[path]
+    prompts = [[900, 65]] * 20
+    out = tmp_path / "g.jsonl"
+    plain = G.generate_file(_Model(), _Tok(), None, str(out), max_new_tokens=2, prompts=prompts, batch_size=32, **extra)
+    assert "small_batch_groups" not in plain and "small_batch" not in seen[-1] and "small_batch_report" not in seen[-1]
+    off = G.generate_file(_Model(), _Tok(), None, str(out), max_new_tokens=2, prompts=prompts, batch_size=32, small_batch=False, **extra)
+    assert off == plain and "small_batch" not in seen[-1] and "small_batch_report" not in seen[-1]
+    lines_plain = out.read_text()
+    on = G.generate_file(_Model(), _Tok(), None, str(out), max_new_tokens=2, prompts=prompts, batch_size=32, small_batch=True, **extra)
+    assert seen[-1]["small_batch"] is True
+    assert on == dict(plain, small_batch_groups=7)                             # the loop's own count, handed through
+    assert out.read_text() == lines_plain                                      # no JSONL key
+    assert all(set(json.loads(l)) == {"id", "prompt_token_ids", "prompt", "outputs"} for l in lines_plain.splitlines())
+
+
+def test_gen_small_batch_is_parsed_and_handed_on(monkeypatch):
+    from ssi.config import compose
+    cfg = compose(os.path.join(PKG, "conf"), "generate", ["speech.n_dsus=5000", "gen.output_dir=out"])
+    assert cfg.gen.small_batch is False
+    cfg = compose(os.path.join(PKG, "conf"), "generate", ["speech.n_dsus=5000", "gen.output_dir=out", "gen.small_batch=true"])
+    assert cfg.gen.small_batch is True
+    spec = importlib.util.spec_from_file_location("generate_script_sb", os.path.join(PKG, "scripts", "generate.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    import ssi.trainer
+
+    class FakeTrainer:
+        token_type_ranges = {}
+
+        def __init__(self, cfg):
+            self.model, self.tokenizer = _Model(), _Tok()
+
+        def _setup_model(self):
+            pass
+
+        _setup_tokenizer = _setup_model
+
+    seen = []
+    monkeypatch.setattr(ssi.trainer, "Trainer", FakeTrainer)
+    monkeypatch.setattr(mod, "generate_file", lambda *a, **kw: seen.append(kw) or {"items": 0})
+    monkeypatch.setattr(os, "makedirs", lambda *a, **kw: None)
+    for flag, want in (("false", False), ("true", True)):
+        cfg = compose(os.path.join(PKG, "conf"), "generate", ["speech.n_dsus=5000", "gen.output_dir=out", "gen.input=in.jsonl", "device=cpu",
+                                                               f"gen.small_batch={flag}"])
+        mod.main(cfg)
+        assert ("small_batch" in seen[-1]) is want and seen[-1].get("small_batch", False) is want      # absent from the call without it

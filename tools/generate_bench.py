@@ -1,5 +1,5 @@
 """What greedy generation costs at the 1B shape (Llama-3.2-1B + 5000 DSUs, bf16, random weights): 256 prompts of about 1000 tokens, 256 new
-tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained|beam|sample|penalty] [--json profiles/generate.json]
+tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained|beam|sample|penalty|small_batch] [--json profiles/generate.json]
 
 run        prefill time, milliseconds per decode step (event time over all steps, host gaps included), generated tokens per second, and a
            self-check: the first generated token of every prompt against the argmax of a plain full forward of that prompt alone (with
@@ -29,6 +29,13 @@ sample     (not part of ``all``; python tools/generate_bench.py --part sample --
            Gumbel argmax), with the walks of the row each setting makes and what reading the row once costs; a sampled decode step
            (``decode_step`` + ``ssi_decode_sample`` at top_k 50, top_p 0.9) against the greedy step with log-probabilities; and one ``sample``
            call with ``n = 4``.
+small_batch (not part of ``all``; python tools/generate_bench.py --part small_batch --json profiles/generate_small_batch.json) what a decode step of
+           1, 8, 16, 32 and 64 rows costs, ONE process alternating the forms over ``--rounds`` rounds, median and min..max: each of the five GEMMs
+           of the 1B model (QKV + RoPE, output + residual, gate/up + SwiGLU, down + residual — walking the 16 layers' weights in turn — and the
+           tied head) on the skinny kernel and on the 256-tile kernel with the rows padded to 256, with the skinny kernel's weight bytes per
+           second; a whole ``decode_step`` on prompts of about ``--prompt-len`` tokens with ``small_batch`` on and off; and one
+           ``ssi.prompting.probe`` call of one prompt end to end.  ``--part small_batch_steps``: a few small-batch steps and nothing else, to be
+           run under a kernel trace.
 all        the three as child processes, each under its own ``timeout``, chained with ``&&``; then the results and the floor from traffic
            alone (weights read once per step, the cache read once per step) are merged into --json."""
 import argparse, csv, glob, json, os, statistics, subprocess, sys, time
@@ -37,7 +44,8 @@ PKG = os.path.join(ROOT, 'speech-integration_amd')
 sys.path.insert(0, PKG)
 
 ap = argparse.ArgumentParser()
-ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained', 'beam', 'sample', 'penalty'])
+ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained', 'beam', 'sample', 'penalty', 'small_batch', 'small_batch_steps'])
+ap.add_argument('--rows', type=int, default=1, help='small_batch_steps: rows of the traced steps')
 ap.add_argument('--prompts', type=int, default=256)
 ap.add_argument('--penalty-generated', type=int, default=128, help='penalty: generated tokens in every row\'s history')
 ap.add_argument('--prompt-len', type=int, default=1000)
@@ -774,6 +782,194 @@ def part_penalty():
     return res
 
 
+SMALL_ROWS = (1, 8, 16, 32, 64)
+
+
+def _small_cache(model, rows):
+    """A cache of ``rows`` prompts of about --prompt-len tokens, prefilled, with room for the measured steps."""
+    import torch
+    g = torch.Generator().manual_seed(1)
+    lens = torch.randint(args.prompt_len - 100, args.prompt_len + 101, (rows,), generator=g).tolist()
+    prompts = [torch.randint(0, model.vocab_size, (n,), generator=g) for n in lens]
+    cache = model.new_kv_cache(rows, max(lens) + 4096)
+    model.prefill(cache, prompts)
+    return cache, lens
+
+
+def part_small_batch():
+    import torch
+    from ssi import ops
+    from ssi.ops import GEMM_NT
+    from ssi.prompting import probe
+    model = build_model()
+    D, I, L, dev = model.embed_dim, model.intermediate_dim, model.num_layers, dict(device='cuda')
+    bf = torch.bfloat16
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(reps):
+            fn(i)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3        # us per call
+
+    res = {'geometry': f'1B shape, bf16; rows {list(SMALL_ROWS)}; {args.rounds} rounds alternating the forms in one process; the layer GEMMs walk the '
+                       f'{L} layers\' weights in turn (call i reads layer i % {L}), the head reads the one table',
+           'hbm_TB_per_s_of_the_adamw_and_ema_passes': list(HBM_TB_S)}
+    with torch.inference_mode():
+        g = torch.Generator(device='cuda').manual_seed(5)
+        x256 = {k: torch.randn(256, k, generator=g, **dev).mul_(0.5).to(bf) for k in (D, I)}
+        pos256 = torch.randint(0, 1000, (256,), generator=g, **dev).to(torch.int32)
+        W = lambda name: [model._view(f'L{l}.{name}') for l in range(L)]   # noqa: E731
+        wqkv, wo, w13, w2, emb = W('wqkv'), W('wo'), W('w13'), W('w2'), model._view('emb')
+        H = model.num_heads + model.num_kv_heads
+        out = {n: torch.empty(256, n, **dev, dtype=bf) for n in (model.qkv_dim, D, 2 * I, I, model.vocab_pad)}
+        res_in = torch.randn(256, D, generator=g, **dev).to(bf)
+        shapes = {
+            'qkv_rope_3072x2048': (model.qkv_dim * D * 2,
+                                   lambda m: (lambda i: ops.gemm_skinny_rope(x256[D][:m], wqkv[i % L], out[model.qkv_dim][:m], H, 64, model._rope, pos256[:m])),
+                                   lambda i: ops.gemm_rope(x256[D], wqkv[i % L], out[model.qkv_dim], 256, H, 64, model._rope, positions=pos256)),
+            'wo_residual_2048x2048': (D * D * 2,
+                                      lambda m: (lambda i: ops.gemm_skinny(x256[D][:m], wo[i % L], out[D][:m], residual=res_in[:m])),
+                                      lambda i: model._gemm(GEMM_NT, x256[D], wo[i % L], out[D], residual=res_in)),
+            'w13_swiglu_16384x2048': (2 * I * D * 2,
+                                      lambda m: (lambda i: ops.gemm_skinny_swiglu(x256[D][:m], w13[i % L], None, out[I][:m])),
+                                      lambda i: ops.gemm_swiglu_fwd(x256[D], w13[i % L], out[2 * I], out[I])),
+            'w2_residual_2048x8192': (D * I * 2,
+                                      lambda m: (lambda i: ops.gemm_skinny(x256[I][:m], w2[i % L], out[D][:m], residual=res_in[:m])),
+                                      lambda i: model._gemm(GEMM_NT, x256[I], w2[i % L], out[D], residual=res_in)),
+            'head_133376x2048': (model.vocab_pad * D * 2,
+                                 lambda m: (lambda i: ops.gemm_skinny(x256[D][:m], emb, out[model.vocab_pad][:m])),
+                                 lambda i: ops.gemm(GEMM_NT, x256[D], emb, out[model.vocab_pad])),
+        }
+        gemms = {}
+        for name, (wbytes, skinny_of, tiled) in shapes.items():
+            reps = 8 if name.startswith('head') else 64
+            forms = {f'skinny_M{m}_us': skinny_of(m) for m in SMALL_ROWS}
+            forms['tile_256_rows_us'] = tiled
+            for fn in forms.values():
+                timed(fn, 4)
+            rounds = {k: [] for k in forms}
+            for _ in range(args.rounds):
+                for k, fn in forms.items():
+                    rounds[k].append(timed(fn, reps))
+            entry = {k: spread(v) for k, v in rounds.items()}
+            entry['weight_MB'] = round(wbytes / 1e6, 2)
+            entry['skinny_weight_TB_per_s'] = {f'M{m}': round(wbytes / 1e6 / entry[f'skinny_M{m}_us']['median'], 2) for m in SMALL_ROWS}
+            entry['tile_over_skinny'] = {f'M{m}': round(entry['tile_256_rows_us']['median'] / entry[f'skinny_M{m}_us']['median'], 2) for m in SMALL_ROWS}
+            gemms[name] = entry
+        res['gemms'] = gemms
+        per_layer = lambda key: sum(gemms[n][key]['median'] for n in gemms if not n.startswith('head'))   # noqa: E731
+        res['gemm_us_per_step_from_the_parts'] = dict(
+            {f'skinny_M{m}': round(L * per_layer(f'skinny_M{m}_us') + gemms['head_133376x2048'][f'skinny_M{m}_us']['median'], 1) for m in SMALL_ROWS},
+            tile_256_rows=round(L * per_layer('tile_256_rows_us') + gemms['head_133376x2048']['tile_256_rows_us']['median'], 1))
+        del x256, out, res_in
+
+        # whole steps: the same cache state for both forms of a row count (the lengths are put back before every block of steps)
+        steps, st = 16, {}
+        for m in SMALL_ROWS:
+            cache, lens = _small_cache(model, m)
+            start = cache.lengths.clone()
+            tok = torch.randint(0, model.vocab_size, (m,), **dev)
+            slot = torch.arange(m, dtype=torch.int32, **dev)
+
+            def block(small):
+                cache.lengths.copy_(start)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    model.decode_step(cache, tok, slot, small_batch=small)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / steps * 1e3      # ms per step, host clock: what a loop sees
+
+            block(True), block(False)
+            rounds = {'small_batch_ms': [], 'padded_ms': []}
+            for _ in range(args.rounds):
+                rounds['small_batch_ms'].append(block(True))
+                rounds['padded_ms'].append(block(False))
+            e = {k: spread(v, 3) for k, v in rounds.items()}
+            e['prompt_tokens_mean'] = round(sum(lens) / m, 1)
+            e['padded_minus_small_batch_ms'] = round(e['padded_ms']['median'] - e['small_batch_ms']['median'], 3)
+            e['padded_spread_ms'] = round(e['padded_ms']['max'] - e['padded_ms']['min'], 3)
+            e['small_batch_wins_by_more_than_the_padded_spread'] = bool(e['padded_minus_small_batch_ms'] > e['padded_spread_ms'])
+            st[f'rows_{m}'] = e
+            assert int(cache.errors) == 0
+            del cache
+        res['decode_step'] = dict(st, steps_per_block=steps, clock='host, synchronised around a block of steps')
+        winners = [m for m in SMALL_ROWS if st[f'rows_{m}']['small_batch_wins_by_more_than_the_padded_spread']]
+        res['skinny_max_rows'] = {'rule': 'the largest measured row count at which the small-batch step beats the padded step by more than the padded '
+                                          'step\'s own min..max spread',
+                                  'padded_step': 'measured on THIS build, not on the parent commit: an inference from the padded step\'s launches and kernels being the parent\'s '
+                                                 '(kernel_lint --against the parent build, the recorded launch trace), not the parent\'s own measurement',
+                                  'qualifying_rows': winners, 'chosen': max(winners) if winners else None, 'model_attribute': model.skinny_max_rows}
+        # end to end: generate() of 8, 32 and 64 prompts, both ways.  With the flag a group also prefills prompt by prompt (one forward per
+        # prompt instead of the packed rows), which is what a last group of many prompts pays for the cheaper steps.
+        from ssi.generate import generate
+        e2e = {}
+        for n_p in (1, 8, 32, 64):
+            gen = torch.Generator().manual_seed(7)
+            lens = torch.randint(args.prompt_len - 100, args.prompt_len + 101, (n_p,), generator=gen).tolist()
+            prompts = [torch.randint(0, model.vocab_size, (n,), generator=gen) for n in lens]
+
+            def run(small, new):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                generate(model, prompts, max_new_tokens=new, stop_token_ids=[], pad_id=0, small_batch=small)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) * 1e3
+
+            run(True, 2), run(False, 2)
+            rounds = {'small_batch_ms': [], 'padded_ms': [], 'small_batch_prefill_and_1_step_ms': [], 'padded_prefill_and_1_step_ms': []}
+            for _ in range(3):
+                rounds['small_batch_ms'].append(run(True, args.new))
+                rounds['padded_ms'].append(run(False, args.new))
+                rounds['small_batch_prefill_and_1_step_ms'].append(run(True, 2))
+                rounds['padded_prefill_and_1_step_ms'].append(run(False, 2))
+            e = {k: spread(v, 1) for k, v in rounds.items()}
+            e['padded_over_small_batch'] = round(e['padded_ms']['median'] / e['small_batch_ms']['median'], 2)
+            e['prefill_extra_ms_per_prompt'] = round((e['small_batch_prefill_and_1_step_ms']['median'] - e['padded_prefill_and_1_step_ms']['median']) / n_p, 2)
+            e2e[f'prompts_{n_p}'] = e
+        res['generate_end_to_end'] = dict(e2e, new_tokens=args.new, rounds=3,
+                                          note='generate() of n prompts of about --prompt-len tokens, --new new tokens, host clock; with small_batch the group prefills prompt by prompt')
+        res['weights_floor_ms_at_5.4_and_6.4_TB_s'] = [round(model._flat_numel * 2 / 1e9 / bw, 3) for bw in HBM_TB_S]
+
+    class _Tok:                                                   # ids as text: the probe's host path without a tokenizer file
+        eos_id, eom_id, eot_id, pad_id, special_tokens = 1, 2, 3, 0, {}
+
+        def decode(self, ids, **kw):
+            return ' '.join(map(str, ids))
+
+    g = torch.Generator().manual_seed(2)
+    prompt = torch.randint(4, model.vocab_size, (args.prompt_len,), generator=g).tolist()
+    probe(model, _Tok(), [prompt], max_new_tokens=8, stop_token_ids=[])
+    times = []
+    for _ in range(args.rounds):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        found = probe(model, _Tok(), [prompt], max_new_tokens=args.new, stop_token_ids=[])
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+    n_new = len(found[0].generations[0].token_ids)
+    res['probe_one_prompt'] = {'prompt_tokens': len(prompt), 'new_tokens': n_new, 'call_ms': spread(times, 1),
+                               'ms_per_new_token_prefill_included': round(statistics.median(times) / n_new, 3)}
+    print(json.dumps(res, indent=1))
+    return res
+
+
+def part_small_batch_steps():
+    """--trace-steps small-batch decode steps of --rows rows, for a kernel trace in a run of its own."""
+    import torch
+    model = build_model()
+    with torch.inference_mode():
+        cache, _ = _small_cache(model, args.rows)
+        tok = torch.randint(0, model.vocab_size, (args.rows,), device='cuda')
+        slot = torch.arange(args.rows, dtype=torch.int32, device='cuda')
+        for _ in range(args.trace_steps):
+            model.decode_step(cache, tok, slot, small_batch=True)
+        torch.cuda.synchronize()
+
+
 def split_trace(stats_csv, steps):
     rows = [r for r in csv.DictReader(open(stats_csv)) if int(r['Calls']) >= steps]
     ms = lambda sel: sum(float(r['TotalDurationNs']) for r in rows if sel(r['Name'])) / 1e6 / steps  # noqa: E731
@@ -800,6 +996,11 @@ elif args.part == 'sample':
     res = part_sample()
 elif args.part == 'penalty':
     res = part_penalty()
+elif args.part == 'small_batch':
+    res = part_small_batch()
+elif args.part == 'small_batch_steps':
+    part_small_batch_steps()
+    res = None
 else:
     wd = args.workdir
     os.makedirs(wd, exist_ok=True)
