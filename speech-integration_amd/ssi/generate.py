@@ -1,11 +1,15 @@
-"""Greedy generation on the HIP decoder (the reference generates with vLLM, ``scripts/generate.py``: greedy, ``n = 1``): what turns a
-checkpoint into the transcripts the reference's ``scripts/wer.py`` scores.
+"""Generation on the HIP decoder — greedy, sampled and beam search (the reference generates with vLLM, ``scripts/generate.py``: greedy,
+``n = 1``): what turns a checkpoint into the transcripts the reference's ``scripts/wer.py`` scores.
 
 ``generate`` sorts the prompts by length and runs them in static groups of ``batch_size``: one ``prefill`` per group (the packed forward
 of the dev loss and of ``ssi.score``, block-causal over the prompts, every layer's K / V scattered into a cache by ``ssi_kv_store``), then
 ``decode_step`` per new token (one row per sequence on the training step's GEMMs, ``ssi_attn_decode`` over the cache).  A finished row
 goes inert — its slot is masked to -1, so it costs no attention and writes no cache — and the group ends when every row has finished or
 at ``max_new_tokens``; whether every row has finished is read back every ``READBACK_EVERY`` steps, not every step.
+
+The three entry points check their own arguments and share ``_run_groups``; ``generate`` and ``sample`` run a group in the one ``_token_loop``,
+given a chooser (``_Argmax``, ``_Select``, ``_Sample``: the step's tokens) and a stepper (``_own_slots``, ``_shared_prompt``: the next logits), each
+built per group.  Beam search is another algorithm and keeps a loop of its own, ``_beam_group``.
 
 Constraints (vLLM's ``allowed_token_ids`` and ``min_tokens``; both keep decoding greedy): with ``allowed_token_ids`` or ``min_new_tokens`` the
 token of a step is the first maximum among the ALLOWED columns, from ``ssi_decode_select`` — one launch that also gives the token's
@@ -21,7 +25,7 @@ row and the row's log-normaliser come from ``ssi_topk_logprob``; the bookkeeping
 Sampling (``sample``; ``gen.sample`` in ``conf/generate.yaml``): the token of a step is ``ssi_decode_sample``'s — a draw from
 ``softmax(x / temperature)`` over the allowed columns that top-k and then top-p keep, by Gumbel-max on counter-based random bits keyed by
 ``(seed, sequence, step)`` with ``sequence = prompt index in input order * n + sample index``.  How the prompts were grouped, sorted and batched
-never enters the bits.  ``n = 1`` runs ``generate``'s loop; ``n`` in 2..8 runs a prompt's samples as rows of ``decode_step_beam`` with the identity
+never enters the bits.  ``n = 1`` steps as ``generate`` does; ``n`` in 2..8 runs a prompt's samples as rows of ``decode_step_beam`` with the identity
 ancestry, so the prompt is prefilled once and its K / V are shared as beams share them.
 
 Penalties (vLLM's ``repetition_penalty``, ``frequency_penalty`` and ``presence_penalty``; arguments of ``generate`` and ``sample``,
@@ -31,8 +35,8 @@ tensor, never stored — and report the log-probability (and the rank) of the ra
 
 Out of scope: per-request sampling parameters within one launch, ``n > 8`` and ``best_of``, sampling
 inside beam search, ``beam_width > 8``, sharing the prompt's K / V read among a prompt's beams, beam
-search under data parallelism, continuous batching (refilling freed slots), paged caches, generation under data parallelism, a skinny GEMM for
-small batches, and WER itself (its text normaliser is the reference's dependency; the JSONL written here is what its ``wer.py`` reads)."""
+search under data parallelism, continuous batching (refilling freed slots), paged caches, generation under data parallelism, and WER
+itself (its text normaliser is the reference's dependency; the JSONL written here is what its ``wer.py`` reads)."""
 
 from __future__ import annotations
 
@@ -179,21 +183,237 @@ def _prompt_table(seqs: list[Tensor], dev) -> tuple[Tensor, Tensor]:
     return table.to(dev), torch.tensor(lens, dtype=torch.int32).to(dev)
 
 
-def _separate(model, rows: int, small_batch: bool, report: dict | None = None) -> dict[str, bool]:
-    """The keyword ``prefill`` gets, once per group: a group that decodes on the skinny path prefills prompt by prompt, so that nothing of a
-    prompt's result depends on the prompts beside it; every other group's call is today's.  Such a group is counted in ``report`` (the
-    ``small_batch_groups`` of the run summary: what ran, counted where it ran)."""
-    if not (small_batch and model.takes_small_batch(rows, True)):
-        return {}
+def _constraint(masks: tuple[Tensor, Tensor] | None, min_new: int, dev) -> _Constraint | None:
+    """What ``_constraint_masks`` returned, on the device (None stays None: no constraint)."""
+    if masks is None:
+        return None
+    allow, early = (m.to(dev) for m in masks)
+    return _Constraint(allow, _mask_words(masks[0]).to(dev), early if min_new else None, _mask_words(masks[1]).to(dev) if min_new else None, min_new)
+
+
+def _small_batch_kw(model, rows: int, small_batch: bool, report: dict | None) -> tuple[dict, dict]:
+    """The keywords of a group of ``rows`` rows, decided once per group: (``prefill``'s, a decode step's).  Without the flag both are empty — the
+    calls are then the plain ones, argument for argument.  With it every step gets ``small_batch``, and a group that decodes on the skinny path
+    prefills prompt by prompt (``separate``), so that nothing of a prompt's result depends on the prompts beside it; such a group is counted in
+    ``report`` (the ``small_batch_groups`` of the run summary: what ran, counted where it ran)."""
+    if not small_batch:
+        return {}, {}
+    if not model.takes_small_batch(rows, True):
+        return {}, {"small_batch": True}
     if report is not None:
         report["small_batch_groups"] = report.get("small_batch_groups", 0) + 1
-    return {"separate": True}
+    return {"separate": True}, {"small_batch": True}
 
 
-def _small(small_batch: bool, report: dict | None = None) -> dict:
-    """The keywords a decode step (or, with ``report``, a group) gets: none at all without the flag (the calls are then today's, argument for
-    argument)."""
-    return {} if not small_batch else {"small_batch": True} if report is None else {"small_batch": True, "report": report}
+def _run_groups(model, prompts: Sequence[Any], per_group: int, max_new_tokens: int, stop_token_ids: Sequence[int], masks, min_new: int,
+                open_caches, run_group) -> list:
+    """What ``generate``, ``sample`` and ``beam_search`` do alike once their own arguments are checked: the prompts as tensors, the groups of
+    ``per_group`` prompts, the length check (the last host check: every prompt, before the first launch), then under ``eval()`` and
+    ``inference_mode`` one ``open_caches(n_slots, longest prompt)``, the constraint of ``masks`` on the device (``con``), and per group
+    ``run_group(caches, con, seqs, index, stop)`` — ``index``: the prompts' places in the input, ``stop``: the stop tokens on the device —
+    which returns one result per prompt.  Results in INPUT order."""
+    seqs = [torch.as_tensor(p, dtype=torch.int64).reshape(-1) for p in prompts]
+    lens = [int(s.numel()) for s in seqs]
+    if not seqs:
+        return []
+    groups = plan_groups(lens, per_group)
+    model.check_generation_lengths(lens, max_new_tokens, len(seqs), max(lens) + max_new_tokens)
+    stop = torch.tensor(sorted({int(t) for t in stop_token_ids}), dtype=torch.int64, device=model.device)
+    results: list = [None] * len(seqs)
+    was_training = bool(model.training)
+    model.eval()
+    try:
+        with torch.inference_mode():
+            caches, con = open_caches(min(per_group, len(seqs)), max(lens)), _constraint(masks, min_new, model.device)
+            for group in groups:
+                for i, found in zip(group, run_group(caches, con, [seqs[i] for i in group], group, stop)):
+                    results[i] = found
+    finally:
+        if was_training:
+            model.train()
+    return results
+
+
+def _token_loop(choose, started, caches, refused: str, prompt_len: list[int], max_new: int, stop: Tensor, pad_id: int) -> list[Generation]:
+    """One group of ``generate`` or ``sample``, one row per entry of ``prompt_len``.  The loop owns which rows are alive, their tokens and
+    counts, the stop test and the read-back; ``choose(t, logits, alive, n_gen, out)`` gives the step's tokens (int64, >= 0) and ``started``
+    is the prefill's logits with the stepper, ``step(t, tokens, alive)``: the next logits.  At the end what the ``caches`` refused is an
+    error (``refused``: its message), then ``choose.finish`` raises its own and hands back the per-row fields it alone knows."""
+    rows, dev = len(prompt_len), stop.device
+    logits, step = started
+    alive = torch.ones(rows, dtype=torch.bool, device=dev)
+    out = torch.full((rows, max_new), pad_id, dtype=torch.int64, device=dev)
+    n_gen = torch.zeros(rows, dtype=torch.int32, device=dev)       # (int32: what the selection kernels read)
+    stop_tok = torch.full((rows,), -1, dtype=torch.int64, device=dev)
+    for t in range(max_new):
+        tok = choose(t, logits, alive, n_gen, out)
+        out[:, t] = torch.where(alive, tok, out[:, t])
+        n_gen += alive
+        stopped = alive & torch.isin(tok, stop)
+        stop_tok = torch.where(stopped, tok, stop_tok)
+        alive = alive & ~stopped
+        if t + 1 == max_new:
+            break
+        if (t + 1) % READBACK_EVERY == 0 and not bool(alive.any()):   # the read-back
+            break
+        logits = step(t, torch.where(alive, tok, torch.zeros_like(tok)), alive)
+    host_out, host_n, host_stop = out.cpu(), n_gen.cpu().tolist(), stop_tok.cpu().tolist()
+    errors = sum(int(c.errors) for c in caches)
+    if errors != 0:
+        raise RuntimeError(refused.format(errors))
+    extras = choose.finish(host_n)
+    return [Generation(token_ids=host_out[r, :host_n[r]].tolist(), finish_reason="stop" if host_stop[r] >= 0 else "length",
+                       stop_reason=host_stop[r] if host_stop[r] >= 0 else None, prompt_len=prompt_len[r], **extras[r]) for r in range(rows)]
+
+
+# ---- the choosers: the token of a step ---------------------------------------------------------------------------------------------
+class _Argmax:
+    """``generate`` without constraint or penalty: ``argmax`` over the real columns, torch's first-occurrence rule.  With ``logprobs`` the
+    forward-only ``ops.ce_fwd_metrics`` gives the token's log-probability, and its rank there is the free self-check."""
+
+    def __init__(self, model, rows: int, logprobs: bool):
+        dev = model.device
+        self.V, self.rows, self.logprobs = model.vocab_size, rows, logprobs
+        self.cum = torch.zeros(rows, dtype=torch.float64, device=dev)
+        self.not_top = torch.zeros(1, dtype=torch.int64, device=dev)
+        if logprobs:
+            self.row_loss, self.row_nll = torch.empty(rows, dtype=torch.float32, device=dev), torch.empty(rows, dtype=torch.float32, device=dev)
+            self.row_rank = torch.empty(rows, dtype=torch.int32, device=dev)
+
+    def __call__(self, t: int, logits: Tensor, alive: Tensor, n_gen: Tensor, out: Tensor) -> Tensor:
+        tok = logits[:, :self.V].argmax(dim=-1)
+        if self.logprobs:
+            labels = torch.where(alive, tok, torch.full_like(tok, CROSS_ENTROPY_IGNORE_IDX))
+            ops.ce_fwd_metrics(logits, labels, self.V, CROSS_ENTROPY_IGNORE_IDX, self.row_loss, None, self.row_nll, self.row_rank)
+            self.cum -= torch.where(alive, self.row_nll, torch.zeros_like(self.row_nll)).double()
+            self.not_top += (alive & (self.row_rank != 0)).sum()      # the free self-check: the chosen token is the row's first
+        return tok
+
+    def finish(self, host_n: list[int]) -> list[dict]:
+        if int(self.not_top) != 0:
+            raise RuntimeError(f"generate: on {int(self.not_top)} rows the chosen token was not ranked first by ce_fwd_metrics")
+        host_cum = self.cum.cpu().tolist() if self.logprobs else [None] * self.rows
+        return [dict(cumulative_logprob=c) for c in host_cum]
+
+
+class _Selection:
+    """What ``_Select`` and ``_Sample`` share: the token and log-probability buffers, the mask and penalty keywords of a launch, the self-check
+    "every live row's token is >= 0 and allowed", and the group's end.  ``who`` names the entry point in the messages; ``pen`` set: the
+    penalised kernel, on the group's prompt table (row ``r`` reads line ``prompt_row[r]``; None: line ``r``)."""
+
+    def __init__(self, who: str, model, seqs: list[Tensor], rows: int, con: _Constraint | None, pen: _Penalty | None, logprobs: bool = True,
+                 prompt_row: Tensor | None = None):
+        dev = model.device
+        self.who, self.V, self.con, self.hist = who, int(model.vocab_size), con, None
+        self.tok = torch.empty(rows, dtype=torch.int64, device=dev)
+        self.row_lp = torch.empty(rows, dtype=torch.float32, device=dev) if logprobs else None
+        self.cum = torch.zeros(rows, dtype=torch.float64, device=dev)
+        self.bad = torch.zeros(1, dtype=torch.int64, device=dev)
+        if pen is not None:
+            ptab, plen = _prompt_table(seqs, dev)
+            self.n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.hist = dict(prompt_ids=ptab, prompt_len=plen, **({} if prompt_row is None else {"prompt_row": prompt_row}),
+                             repetition_penalty=pen.r, frequency_penalty=pen.f, presence_penalty=pen.p, n_bad=self.n_bad)
+
+    def launch_kw(self, n_gen: Tensor, out: Tensor) -> dict:
+        """The mask and penalty keywords of a selection launch.  No constraint and no penalty: none at all; ``n_generated`` is None under a
+        constraint without ``min_new`` (nothing reads it then) and always there under a penalty, with the loop's tokens as ``gen_ids``."""
+        con = self.con
+        kw = {} if con is None else dict(n_generated=n_gen if con.min_new else None, allow=con.allow_words, allow_early=con.early_words, min_new=con.min_new)
+        return kw if self.hist is None else dict(kw, n_generated=n_gen, gen_ids=out, **self.hist)
+
+    def refused(self, at: Tensor, n_gen: Tensor) -> Tensor:
+        """Per row: the kernel chose no token, or one that is not allowed (``at``: the tokens clamped to >= 0)."""
+        none, con = self.tok < 0, self.con
+        if con is None:
+            return none
+        return none | ~(con.allow[at] if con.early is None else torch.where(n_gen < con.min_new, con.early[at], con.allow[at]))
+
+    def check(self) -> None:
+        if self.hist is not None and int(self.n_bad) != 0:
+            raise RuntimeError(f"{self.who}: on {int(self.n_bad)} row-steps the penalised selection met an id outside the vocabulary in the row's history")
+        if int(self.bad) != 0:
+            raise RuntimeError(f"{self.who}: on {int(self.bad)} rows {self.refusal}")
+
+
+class _Select(_Selection):
+    """``generate`` under a constraint or a penalty: ``ops.decode_select`` / ``ops.decode_select_pen`` — the first allowed maximum, its
+    log-probability over ALL columns and its rank in the raw row (not 0: the mask or the penalties changed the choice)."""
+    refusal = "decode_select chose no token or one that is not allowed"
+
+    def __init__(self, model, seqs: list[Tensor], con: _Constraint | None, pen: _Penalty | None, logprobs: bool):
+        super().__init__("generate", model, seqs, len(seqs), con, pen, logprobs)
+        self.row_rank = torch.empty(len(seqs), dtype=torch.int32, device=model.device)
+        self.n_con = torch.zeros(len(seqs), dtype=torch.int64, device=model.device)
+
+    def __call__(self, t: int, logits: Tensor, alive: Tensor, n_gen: Tensor, out: Tensor) -> Tensor:
+        select = ops.decode_select if self.hist is None else ops.decode_select_pen
+        select(logits, self.V, self.tok, self.row_lp, self.row_rank, **self.launch_kw(n_gen, out))
+        at = self.tok.clamp(min=0)                      # (a new tensor per step, as argmax gives; never a negative embedding index)
+        self.bad += (alive & self.refused(at, n_gen)).sum()
+        self.n_con += alive & (self.row_rank != 0)
+        if self.row_lp is not None:
+            self.cum += torch.where(alive, self.row_lp, torch.zeros_like(self.row_lp)).double()
+        return at
+
+    def finish(self, host_n: list[int]) -> list[dict]:
+        self.check()
+        host_cum = self.cum.cpu().tolist() if self.row_lp is not None else [None] * len(host_n)
+        return [dict(cumulative_logprob=c, n_constrained=k) for c, k in zip(host_cum, self.n_con.cpu().tolist())]
+
+
+class _Sample(_Selection):
+    """``sample``: ``ops.decode_sample`` / ``ops.decode_sample_pen`` with ``step`` the loop index and ``sequence`` the rows' numbers — row
+    ``s * n + j`` is sample ``j`` of the group's prompt ``s``, whose place in the input is ``index[s]``.  The self-check adds "drawn from a set of
+    at least one column"."""
+    refusal = "decode_sample chose no token, one that is not allowed, or kept no column"
+
+    def __init__(self, model, seqs: list[Tensor], index: list[int], n: int, draw: dict, con: _Constraint | None, pen: _Penalty | None):
+        dev, rows = model.device, len(seqs) * n
+        super().__init__("sample", model, seqs, rows, con, pen, prompt_row=torch.arange(rows, dtype=torch.int32, device=dev) // n if pen is not None else None)
+        number = (torch.tensor(index, dtype=torch.int64) * n).repeat_interleave(n) + torch.arange(n, dtype=torch.int64).repeat(len(seqs))
+        self.sequence = torch.where(number >= 2 ** 31, number - 2 ** 32, number).to(torch.int32).to(dev)      # (the kernel reads it as unsigned)
+        self.draw = draw
+        self.row_kept = torch.empty(rows, dtype=torch.int32, device=dev)
+        self.kept_sum = torch.zeros(rows, dtype=torch.int64, device=dev)
+
+    def __call__(self, t: int, logits: Tensor, alive: Tensor, n_gen: Tensor, out: Tensor) -> Tensor:
+        sample = ops.decode_sample if self.hist is None else ops.decode_sample_pen
+        sample(logits, self.V, self.tok, self.row_lp, self.row_kept, step=t, sequence=self.sequence, **self.launch_kw(n_gen, out), **self.draw)
+        at = self.tok.clamp(min=0)                      # (a new tensor per step; never a negative embedding index)
+        self.bad += (alive & (self.refused(at, n_gen) | (self.row_kept < 1))).sum()
+        self.cum += torch.where(alive, self.row_lp, torch.zeros_like(self.row_lp)).double()
+        self.kept_sum += torch.where(alive, self.row_kept, torch.zeros_like(self.row_kept))
+        return at
+
+    def finish(self, host_n: list[int]) -> list[dict]:
+        host_cum, host_kept = self.cum.cpu().tolist(), self.kept_sum.cpu().tolist()
+        self.check()
+        return [dict(cumulative_logprob=c, n_kept_mean=k / max(m, 1)) for c, k, m in zip(host_cum, host_kept, host_n)]
+
+
+# ---- the steppers: the next logits -------------------------------------------------------------------------------------------------
+def _own_slots(model, caches, seqs: list[Tensor], max_new: int, small_batch: bool, report: dict | None):
+    """Row ``r`` is prompt ``r`` and decodes on slot ``r`` of the one cache: ``prefill`` with room for the new tokens, then ``decode_step``.
+    Returns the prefill's logits and the stepper."""
+    prefill_kw, step_kw = _small_batch_kw(model, len(seqs), small_batch, report)
+    logits = model.prefill(caches[0], seqs, max_new_tokens=max_new, **prefill_kw)
+    own = torch.arange(len(seqs), dtype=torch.int32, device=model.device)
+    none = torch.full_like(own, -1)
+    return logits, lambda t, tokens, alive: model.decode_step(caches[0], tokens, torch.where(alive, own, none), **step_kw)
+
+
+def _shared_prompt(model, caches, seqs: list[Tensor], n: int, max_new: int, small_batch: bool, report: dict | None):
+    """Row ``s * n + j`` is continuation ``j`` of prompt ``s``: the prompt is prefilled once into the prompt cache, its logits row repeated
+    ``n`` times for step 0, and the rows run on ``decode_step_beam`` with the identity ancestry — a row reads its own generated positions."""
+    rows, dev = len(seqs) * n, model.device
+    prefill_kw, step_kw = _small_batch_kw(model, rows, small_batch, report)
+    logits = model.prefill(caches[0], seqs, **prefill_kw)[:len(seqs)].repeat_interleave(n, dim=0)
+    own = torch.arange(rows, dtype=torch.int32, device=dev)
+    seq_of, none = own // n, torch.full_like(own, -1)
+    plen = torch.tensor([int(s.numel()) for s in seqs], dtype=torch.int32).to(dev).repeat_interleave(n)
+    anc = own[:, None].expand(rows, max_new).contiguous()
+    return logits, lambda t, tokens, alive: model.decode_step_beam(*caches, tokens, torch.where(alive, seq_of, none), plen, anc, t, **step_kw)
 
 
 def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_ids: Sequence[int], pad_id: int, batch_size: int = 256,
@@ -227,107 +447,15 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
     device = torch.device(device) if device is not None else model.device
     if device != model.device:
         raise ValueError(f"generate: device {device} is not the model's ({model.device})")
-    seqs = [torch.as_tensor(p, dtype=torch.int64).reshape(-1) for p in prompts]
-    lens = [int(s.numel()) for s in seqs]
-    if not seqs:
-        return []
-    groups = plan_groups(lens, batch_size)
-    n_slots, cap = min(batch_size, len(seqs)), max(lens) + max_new_tokens
-    model.check_generation_lengths(lens, max_new_tokens, len(seqs), cap)      # every prompt, before the first launch
-    stop = torch.tensor(sorted({int(t) for t in stop_token_ids}), dtype=torch.int64, device=device)
-    results: list[Generation | None] = [None] * len(seqs)
-    was_training = bool(model.training)
-    model.eval()
-    try:
-        with torch.inference_mode():
-            cache = model.new_kv_cache(n_slots, cap)
-            con = None
-            if masks is not None:
-                allow, early = (m.to(device) for m in masks)
-                con = _Constraint(allow, _mask_words(masks[0]).to(device), early if min_new_tokens else None,
-                                  _mask_words(masks[1]).to(device) if min_new_tokens else None, min_new_tokens)
-            for group in groups:
-                for i, g in zip(group, _generate_group(model, cache, [seqs[i] for i in group], max_new_tokens, stop, int(pad_id), logprobs, con,
-                                                          *(() if pen is None else (pen,)), **_small(small_batch, small_batch_report))):
-                    results[i] = g
-    finally:
-        if was_training:
-            model.train()
-    return results  # type: ignore[return-value]
+    refused = "generate: the K/V cache kernels refused {} rows (a destination or a slot outside the cache)"
 
+    def run_group(caches, con, seqs: list[Tensor], index: list[int], stop: Tensor) -> list[Generation]:
+        started = _own_slots(model, caches, seqs, max_new_tokens, small_batch, small_batch_report)
+        choose = _Argmax(model, len(seqs), logprobs) if con is None and pen is None else _Select(model, seqs, con, pen, logprobs)
+        return _token_loop(choose, started, caches, refused, [int(s.numel()) for s in seqs], max_new_tokens, stop, int(pad_id))
 
-def _generate_group(model, cache, seqs: list[Tensor], max_new_tokens: int, stop: Tensor, pad_id: int, logprobs: bool,
-                    con: _Constraint | None = None, pen: _Penalty | None = None, small_batch: bool = False, report: dict | None = None) -> list[Generation]:
-    n, dev, V = len(seqs), model.device, model.vocab_size
-    chosen = con is not None or pen is not None       # the token comes from a selection kernel, not from argmax
-    logits = model.prefill(cache, seqs, max_new_tokens=max_new_tokens, **_separate(model, n, small_batch, report))
-    alive = torch.ones(n, dtype=torch.bool, device=dev)
-    own_slot = torch.arange(n, dtype=torch.int32, device=dev)
-    no_slot = torch.full_like(own_slot, -1)
-    out = torch.full((n, max_new_tokens), pad_id, dtype=torch.int64, device=dev)
-    n_gen = torch.zeros(n, dtype=torch.int32 if chosen else torch.int64, device=dev)     # (int32: what ssi_decode_select reads)
-    stop_tok = torch.full((n,), -1, dtype=torch.int64, device=dev)
-    cum = torch.zeros(n, dtype=torch.float64, device=dev)
-    not_top = torch.zeros(1, dtype=torch.int64, device=dev)
-    if chosen:
-        tok = torch.empty(n, dtype=torch.int64, device=dev)
-        row_lp = torch.empty(n, dtype=torch.float32, device=dev) if logprobs else None
-        row_rank = torch.empty(n, dtype=torch.int32, device=dev)
-        n_con = torch.zeros(n, dtype=torch.int64, device=dev)
-        if pen is not None:
-            ptab, plen = _prompt_table(seqs, dev)
-            n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
-    elif logprobs:
-        row_loss, row_nll = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
-        row_rank = torch.empty(n, dtype=torch.int32, device=dev)
-    for t in range(max_new_tokens):
-        if chosen:
-            masks = {} if con is None else dict(allow=con.allow_words, allow_early=con.early_words, min_new=con.min_new)
-            if pen is None:
-                ops.decode_select(logits, V, tok, row_lp, row_rank, n_generated=n_gen if con.min_new else None, **masks)
-            else:
-                ops.decode_select_pen(logits, V, tok, row_lp, row_rank, prompt_ids=ptab, prompt_len=plen, gen_ids=out, n_generated=n_gen,
-                                      repetition_penalty=pen.r, frequency_penalty=pen.f, presence_penalty=pen.p, n_bad=n_bad, **masks)
-            at = tok.clamp(min=0)
-            if con is None:
-                ok = torch.ones_like(alive)
-            else:
-                ok = con.allow[at] if con.early is None else torch.where(n_gen < con.min_new, con.early[at], con.allow[at])
-            not_top += (alive & ((tok < 0) | ~ok)).sum()    # the self-check: the chosen token exists and is allowed
-            n_con += alive & (row_rank != 0)
-            if logprobs:
-                cum += torch.where(alive, row_lp, torch.zeros_like(row_lp)).double()
-            tok = at.clone()                                # (a new tensor per step, as argmax gives; never a negative embedding index)
-        else:
-            tok = logits[:, :V].argmax(dim=-1)
-        if not chosen and logprobs:
-            labels = torch.where(alive, tok, torch.full_like(tok, CROSS_ENTROPY_IGNORE_IDX))
-            ops.ce_fwd_metrics(logits, labels, V, CROSS_ENTROPY_IGNORE_IDX, row_loss, None, row_nll, row_rank)
-            cum -= torch.where(alive, row_nll, torch.zeros_like(row_nll)).double()
-            not_top += (alive & (row_rank != 0)).sum()      # the free self-check: the chosen token is the row's first
-        out[:, t] = torch.where(alive, tok, out[:, t])
-        n_gen += alive
-        stopped = alive & torch.isin(tok, stop)
-        stop_tok = torch.where(stopped, tok, stop_tok)
-        alive = alive & ~stopped
-        if t + 1 == max_new_tokens:
-            break
-        if (t + 1) % READBACK_EVERY == 0 and not bool(alive.any()):   # the read-back
-            break
-        logits = model.decode_step(cache, torch.where(alive, tok, torch.zeros_like(tok)), torch.where(alive, own_slot, no_slot), **_small(small_batch))
-    host_out, host_n, host_stop, host_cum = out.cpu(), n_gen.cpu().tolist(), stop_tok.cpu().tolist(), cum.cpu().tolist()
-    if int(cache.errors) != 0:
-        raise RuntimeError(f"generate: the K/V cache kernels refused {int(cache.errors)} rows (a destination or a slot outside the cache)")
-    if pen is not None and int(n_bad) != 0:
-        raise RuntimeError(f"generate: on {int(n_bad)} row-steps the penalised selection met an id outside the vocabulary in the row's history")
-    if int(not_top) != 0 and chosen:
-        raise RuntimeError(f"generate: on {int(not_top)} rows decode_select chose no token or one that is not allowed")
-    if int(not_top) != 0:
-        raise RuntimeError(f"generate: on {int(not_top)} rows the chosen token was not ranked first by ce_fwd_metrics")
-    host_con = n_con.cpu().tolist() if chosen else [None] * n
-    return [Generation(token_ids=host_out[i, :host_n[i]].tolist(), finish_reason="stop" if host_stop[i] >= 0 else "length",
-                       stop_reason=host_stop[i] if host_stop[i] >= 0 else None, cumulative_logprob=host_cum[i] if logprobs else None,
-                       prompt_len=int(seqs[i].numel()), n_constrained=host_con[i]) for i in range(n)]
+    return _run_groups(model, prompts, batch_size, max_new_tokens, stop_token_ids, masks, min_new_tokens,
+                       lambda n_slots, longest: (model.new_kv_cache(n_slots, longest + max_new_tokens),), run_group)
 
 
 # ---- beam search -----------------------------------------------------------------------------------------------------------------
@@ -380,32 +508,15 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
         raise ValueError(f"max_new_tokens must be >= 1 (got {max_new_tokens})")
     if batch_size < W:
         raise ValueError(f"batch_size = {batch_size} holds no prompt of beam_width = {W}")
-    seqs = [torch.as_tensor(p, dtype=torch.int64).reshape(-1) for p in prompts]
-    lens = [int(s.numel()) for s in seqs]
-    if not seqs:
-        return []
-    per_group = batch_size // W
-    groups = plan_groups(lens, per_group)
-    n_slots = min(per_group, len(seqs))
-    model.check_generation_lengths(lens, max_new_tokens, len(seqs), max(lens) + max_new_tokens)      # every prompt, before the first launch
-    device = model.device
-    stop = torch.tensor(sorted({int(t) for t in stop_token_ids}), dtype=torch.int64, device=device)
-    results: list[list[Generation] | None] = [None] * len(seqs)
-    was_training = bool(model.training)
-    model.eval()
-    try:
-        with torch.inference_mode():
-            pcache, bcache = model.new_kv_cache(n_slots, max(lens)), model.new_kv_cache(n_slots * W, max_new_tokens)
-            cont_words = _mask_words(cont).to(device)
-            for group in groups:
-                found = _beam_group(model, pcache, bcache, [seqs[i] for i in group], W, max_new_tokens, stop, int(pad_id), length_penalty, n_best,
-                                    cont_words, min_new_tokens, **_small(small_batch, small_batch_report))
-                for i, g in zip(group, found):
-                    results[i] = g
-    finally:
-        if was_training:
-            model.train()
-    return results  # type: ignore[return-value]
+
+    def open_caches(n_slots: int, longest: int):
+        return model.new_kv_cache(n_slots, longest), model.new_kv_cache(n_slots * W, max_new_tokens), _mask_words(cont).to(model.device)
+
+    def run_group(caches, con, seqs: list[Tensor], index: list[int], stop: Tensor) -> list[list[Generation]]:
+        return _beam_group(model, *caches[:2], seqs, W, max_new_tokens, stop, int(pad_id), length_penalty, n_best, caches[2], min_new_tokens,
+                           small_batch, small_batch_report)
+
+    return _run_groups(model, prompts, batch_size // W, max_new_tokens, stop_token_ids, None, 0, open_caches, run_group)       # (its mask is cont)
 
 
 def _beam_group(model, pcache, bcache, seqs: list[Tensor], W: int, max_new: int, stop: Tensor, pad_id: int, length_penalty: float, n_best: int,
@@ -414,7 +525,8 @@ def _beam_group(model, pcache, bcache, seqs: list[Tensor], W: int, max_new: int,
     n, dev, V, S = len(seqs), model.device, int(model.vocab_size), int(stop.numel())
     R, P, NEG = n * W, 2 * W, float("-inf")     # a pool never holds more than (W - 1) + W hypotheses; place P takes what is not stored
     i64, f32 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float32, device=dev)
-    logits = model.prefill(pcache, seqs, **_separate(model, R, small_batch, report))
+    prefill_kw, step_kw = _small_batch_kw(model, R, small_batch, report)
+    logits = model.prefill(pcache, seqs, **prefill_kw)
     own = torch.arange(R, dtype=torch.int32, device=dev)
     seq_of = own // W
     plen = torch.tensor([int(s.numel()) for s in seqs], dtype=torch.int32).to(dev).repeat_interleave(W)
@@ -483,7 +595,7 @@ def _beam_group(model, pcache, bcache, seqs: list[Tensor], W: int, max_new: int,
         anc = anc.index_select(0, prow)
         anc[:, t] = own
         logits = model.decode_step_beam(pcache, bcache, torch.where(live, new_tok, torch.zeros_like(new_tok)).view(R),
-                                        torch.where(live.view(R), seq_of, torch.full_like(seq_of, -1)), plen, anc, t, **_small(small_batch))
+                                        torch.where(live.view(R), seq_of, torch.full_like(seq_of, -1)), plen, anc, t, **step_kw)
     live = scores > NEG                                 # what is still alive after max_new tokens ends by length (none in a group that ended early)
     all_beams = torch.arange(W, **i64).expand(n, W)
     join(live & ~done[:, None], scores / float(max_new ** length_penalty), scores, max_new, torch.full((n, W), -1, **i64), all_beams, None, 0)
@@ -527,7 +639,7 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
     The token of a step is ``ops.decode_sample``'s with ``step`` the loop index and ``sequence = prompt index * n + sample index``: a pure function
     of ``(seed, sequence, step)`` and the row's logits, so ``batch_size``, the grouping and the order of the prompts never enter the random bits.
     ``top_k <= 0``: no top-k; ties at either threshold stay; top-p acts after top-k on the renormalised rest (vLLM's order).
-    ``n = 1``: ``generate``'s loop (``prefill``, ``decode_step``).  ``n > 1``: a group holds ``batch_size // n`` prompts; the prompt is prefilled
+    ``n = 1``: ``generate``'s stepping (``prefill``, ``decode_step``).  ``n > 1``: a group holds ``batch_size // n`` prompts; the prompt is prefilled
     once, its logits row repeated ``n`` times at step 0, and the samples run as rows of ``decode_step_beam`` with the identity ancestry.  The
     self-check per live row: the token is >= 0, allowed, and drawn from a set of at least one column (``RuntimeError``).
     ``repetition_penalty``, ``frequency_penalty``, ``presence_penalty``: with any of them off its neutral value the step's token is
@@ -544,119 +656,26 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
         raise ValueError(f"max_new_tokens must be >= 1 (got {max_new_tokens})")
     if batch_size < n:
         raise ValueError(f"batch_size = {batch_size} holds no prompt of n = {n}")
-    seqs = [torch.as_tensor(p, dtype=torch.int64).reshape(-1) for p in prompts]
-    lens = [int(s.numel()) for s in seqs]
-    if not seqs:
-        return []
-    if len(seqs) * n > 2 ** 32:
-        raise ValueError(f"{len(seqs)} prompts x {n} samples do not fit the 32-bit sequence number")
-    per_group = batch_size // n
-    groups = plan_groups(lens, per_group)
-    n_slots = min(per_group, len(seqs))
-    model.check_generation_lengths(lens, max_new_tokens, len(seqs), max(lens) + max_new_tokens)      # every prompt, before the first launch
-    device = model.device
-    stop = torch.tensor(sorted({int(t) for t in stop_token_ids}), dtype=torch.int64, device=device)
+    if len(prompts) * n > 2 ** 32:
+        raise ValueError(f"{len(prompts)} prompts x {n} samples do not fit the 32-bit sequence number")
     draw = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
-    results: list[list[Generation] | None] = [None] * len(seqs)
-    was_training = bool(model.training)
-    model.eval()
-    try:
-        with torch.inference_mode():
-            if n == 1:
-                caches = (model.new_kv_cache(n_slots, max(lens) + max_new_tokens),)
-            else:
-                caches = (model.new_kv_cache(n_slots, max(lens)), model.new_kv_cache(n_slots * n, max_new_tokens))
-            con = None
-            if masks is not None:
-                allow, early = (m.to(device) for m in masks)
-                con = _Constraint(allow, _mask_words(masks[0]).to(device), early if min_new_tokens else None,
-                                  _mask_words(masks[1]).to(device) if min_new_tokens else None, min_new_tokens)
-            for group in groups:
-                found = _sample_group(model, caches, [seqs[i] for i in group], group, n, draw, max_new_tokens, stop, int(pad_id), con,
-                                      *(() if pen is None else (pen,)), **_small(small_batch, small_batch_report))
-                for i, g in zip(group, found):
-                    results[i] = g
-    finally:
-        if was_training:
-            model.train()
-    return results  # type: ignore[return-value]
+    refused = "sample: the K/V cache kernels refused {} rows (a destination, a slot or an ancestry entry outside its cache)"
 
-
-def _sample_group(model, caches, seqs: list[Tensor], index: list[int], n: int, draw: dict, max_new: int, stop: Tensor, pad_id: int,
-                  con: _Constraint | None, pen: _Penalty | None = None, small_batch: bool = False, report: dict | None = None) -> list[list[Generation]]:
-    """One group: row ``s * n + j`` is sample ``j`` of the group's prompt ``s``, whose place in the input is ``index[s]``."""
-    n_p, dev, V = len(seqs), model.device, int(model.vocab_size)
-    R = n_p * n
-    if n == 1:
-        logits = model.prefill(caches[0], seqs, max_new_tokens=max_new, **_separate(model, R, small_batch, report))
-    else:
-        logits = model.prefill(caches[0], seqs, **_separate(model, R, small_batch, report))[:n_p].repeat_interleave(n, dim=0)      # step 0: the prompt's row, once per sample
-    number = (torch.tensor(index, dtype=torch.int64) * n).repeat_interleave(n) + torch.arange(n, dtype=torch.int64).repeat(n_p)
-    sequence = torch.where(number >= 2 ** 31, number - 2 ** 32, number).to(torch.int32).to(dev)      # (the kernel reads it as unsigned)
-    own = torch.arange(R, dtype=torch.int32, device=dev)
-    no_slot = torch.full_like(own, -1)
-    seq_of = own // n
-    plen = torch.tensor([int(s.numel()) for s in seqs], dtype=torch.int32).to(dev).repeat_interleave(n)
-    anc = own[:, None].expand(R, max_new).contiguous() if n > 1 else None              # the identity ancestry: a sample reads its own rows
-    alive = torch.ones(R, dtype=torch.bool, device=dev)
-    out = torch.full((R, max_new), pad_id, dtype=torch.int64, device=dev)
-    n_gen = torch.zeros(R, dtype=torch.int32, device=dev)
-    stop_tok = torch.full((R,), -1, dtype=torch.int64, device=dev)
-    cum = torch.zeros(R, dtype=torch.float64, device=dev)
-    kept_sum = torch.zeros(R, dtype=torch.int64, device=dev)
-    bad = torch.zeros(1, dtype=torch.int64, device=dev)
-    tok = torch.empty(R, dtype=torch.int64, device=dev)
-    row_lp = torch.empty(R, dtype=torch.float32, device=dev)
-    row_kept = torch.empty(R, dtype=torch.int32, device=dev)
-    if pen is not None:
-        ptab, ptab_len = _prompt_table(seqs, dev)
-        n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        hist = dict(prompt_ids=ptab, prompt_len=ptab_len, prompt_row=seq_of, gen_ids=out, repetition_penalty=pen.r, frequency_penalty=pen.f,
-                    presence_penalty=pen.p, n_bad=n_bad)
-    for t in range(max_new):
-        masks = {} if con is None else dict(allow=con.allow_words, allow_early=con.early_words, min_new=con.min_new)
-        if pen is not None:
-            ops.decode_sample_pen(logits, V, tok, row_lp, row_kept, step=t, sequence=sequence, n_generated=n_gen, **hist, **masks, **draw)
-        elif con is None:
-            ops.decode_sample(logits, V, tok, row_lp, row_kept, step=t, sequence=sequence, **draw)
-        else:
-            ops.decode_sample(logits, V, tok, row_lp, row_kept, step=t, sequence=sequence, n_generated=n_gen if con.min_new else None, **masks, **draw)
-        if con is None:
-            ok = torch.ones_like(alive)
-        else:
-            at = tok.clamp(min=0)
-            ok = con.allow[at] if con.early is None else torch.where(n_gen < con.min_new, con.early[at], con.allow[at])
-        bad += (alive & ((tok < 0) | ~ok | (row_kept < 1))).sum()      # the self-check
-        cum += torch.where(alive, row_lp, torch.zeros_like(row_lp)).double()
-        kept_sum += torch.where(alive, row_kept, torch.zeros_like(row_kept))
-        new = tok.clamp(min=0)                                  # (a new tensor per step; never a negative embedding index)
-        out[:, t] = torch.where(alive, new, out[:, t])
-        n_gen += alive
-        stopped = alive & torch.isin(new, stop)
-        stop_tok = torch.where(stopped, new, stop_tok)
-        alive = alive & ~stopped
-        if t + 1 == max_new:
-            break
-        if (t + 1) % READBACK_EVERY == 0 and not bool(alive.any()):   # the read-back
-            break
+    def open_caches(n_slots: int, longest: int):
         if n == 1:
-            logits = model.decode_step(caches[0], torch.where(alive, new, torch.zeros_like(new)), torch.where(alive, own, no_slot), **_small(small_batch))
+            return (model.new_kv_cache(n_slots, longest + max_new_tokens),)
+        return model.new_kv_cache(n_slots, longest), model.new_kv_cache(n_slots * n, max_new_tokens)
+
+    def run_group(caches, con, seqs: list[Tensor], index: list[int], stop: Tensor) -> list[list[Generation]]:
+        if n == 1:          # no prompt to share: every row on its own slot, as ``generate``
+            started = _own_slots(model, caches, seqs, max_new_tokens, small_batch, small_batch_report)
         else:
-            logits = model.decode_step_beam(caches[0], caches[1], torch.where(alive, new, torch.zeros_like(new)),
-                                            torch.where(alive, seq_of, no_slot), plen, anc, t, **_small(small_batch))
-    host_out, host_n, host_stop, host_cum = out.cpu(), n_gen.cpu().tolist(), stop_tok.cpu().tolist(), cum.cpu().tolist()
-    host_kept = kept_sum.cpu().tolist()
-    errors = sum(int(c.errors) for c in caches)
-    if errors != 0:
-        raise RuntimeError(f"sample: the K/V cache kernels refused {errors} rows (a destination, a slot or an ancestry entry outside its cache)")
-    if pen is not None and int(n_bad) != 0:
-        raise RuntimeError(f"sample: on {int(n_bad)} row-steps the penalised selection met an id outside the vocabulary in the row's history")
-    if int(bad) != 0:
-        raise RuntimeError(f"sample: on {int(bad)} rows decode_sample chose no token, one that is not allowed, or kept no column")
-    return [[Generation(token_ids=host_out[r, :host_n[r]].tolist(), finish_reason="stop" if host_stop[r] >= 0 else "length",
-                        stop_reason=host_stop[r] if host_stop[r] >= 0 else None, cumulative_logprob=host_cum[r],
-                        prompt_len=int(seqs[s].numel()), n_kept_mean=host_kept[r] / max(host_n[r], 1))
-             for r in range(s * n, s * n + n)] for s in range(n_p)]
+            started = _shared_prompt(model, caches, seqs, n, max_new_tokens, small_batch, small_batch_report)
+        choose = _Sample(model, seqs, index, n, draw, con, pen)
+        found = _token_loop(choose, started, caches, refused, [int(s.numel()) for s in seqs for _ in range(n)], max_new_tokens, stop, int(pad_id))
+        return [found[s * n:s * n + n] for s in range(len(seqs))]
+
+    return _run_groups(model, prompts, batch_size // n, max_new_tokens, stop_token_ids, masks, min_new_tokens, open_caches, run_group)
 
 
 # ---- JSONL in, JSONL out ---------------------------------------------------------------------------------------------------------
@@ -735,63 +754,43 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
 
 
 def _run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, kw: dict) -> dict[str, Any]:
-    """``generate_file`` behind its input handling: picks the loop (greedy, beam search, sampling), writes the lines, returns the summary."""
+    """``generate_file`` behind its input handling: picks the loop (greedy, beam search, sampling), writes the lines, returns the summary.
+    Under beam search and sampling ``logprobs`` is not an option (every hypothesis and sample carries its log-probability), and ``device`` must
+    be the model's, as ``generate`` asks."""
+    kw = dict(kw)
     beam = {k: kw.pop(k) for k in ("beam_width", "length_penalty", "n_best") if k in kw}
     pen = _check_penalties(kw.get("repetition_penalty", 1.0), kw.get("frequency_penalty", 0.0), kw.get("presence_penalty", 0.0))
     pen_summary = {} if pen is None else {"repetition_penalty": pen.r, "frequency_penalty": pen.f, "presence_penalty": pen.p}
     draw = {k: kw.pop(k) for k in ("sample", "n", "temperature", "top_k", "top_p", "seed") if k in kw}
-    if draw.pop("sample", False):
-        if int(beam.get("beam_width", 1)) != 1:
-            raise ValueError("generate_file: sample together with beam_width > 1 (sampling inside beam search is not built)")
-        return dict(_sample_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, draw, kw), **pen_summary)
-    if draw:
+    sampled = bool(draw.pop("sample", False))
+    if draw and not sampled:
         raise ValueError(f"generate_file: {sorted(draw)} without sample=True")
-    if int(beam.get("beam_width", 1)) != 1:
-        return _beam_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, beam, kw)
-    _check_beam(1, beam.get("length_penalty", 1.0), beam.get("n_best", 1))      # (n_best > 1 needs a beam)
-    gens = generate(model, prompts, max_new_tokens=max_new_tokens, stop_token_ids=stop_token_ids, **kw)
+    beams = int(beam.get("beam_width", 1)) != 1
+    if sampled and beams:
+        raise ValueError("generate_file: sample together with beam_width > 1 (sampling inside beam search is not built)")
+    if not (sampled or beams):
+        _check_beam(1, beam.get("length_penalty", 1.0), beam.get("n_best", 1))      # (n_best > 1 needs a beam)
+    run, mode = (sample, draw) if sampled else (beam_search, beam) if beams else (generate, {})
+    if sampled or beams:
+        kw.pop("logprobs", None)
+        device = kw.pop("device", None)
+        if device is not None and torch.device(device) != model.device:
+            raise ValueError(f"generate: device {device} is not the model's ({model.device})")
+    found = run(model, prompts, max_new_tokens=max_new_tokens, stop_token_ids=stop_token_ids, **mode, **kw)
     with open(out_path, "w", encoding="utf-8") as f:
-        for item_id, p, g in zip(ids, prompts, gens):
+        for item_id, p, g in zip(ids, prompts, found):
             f.write(json.dumps(output_record(item_id, p, g, tokenizer, tokenizer_decoding), ensure_ascii=False) + "\n")
-    summary = {"items": len(gens), "generated_tokens": sum(len(g.token_ids) for g in gens),
-               "stopped": sum(g.finish_reason == "stop" for g in gens)}
-    if kw.get("allowed_token_ids") is not None or int(kw.get("min_new_tokens", 0)) != 0 or pen is not None:
+    gens = [g for gs in found for g in gs] if sampled or beams else found       # every written hypothesis or sample counts
+    tokens = sum(len(g.token_ids) for g in gens)
+    summary = {"items": len(found), "generated_tokens": tokens, "stopped": sum(g.finish_reason == "stop" for g in gens)}
+    if sampled:
+        kept = sum((g.n_kept_mean or 0.0) * len(g.token_ids) for g in gens)
+        summary.update(sampled=True, n=int(draw.get("n", 1)), kept_tokens_mean=kept / max(tokens, 1))
+    elif beams:
+        summary["beam_width"] = int(beam["beam_width"])
+    elif kw.get("allowed_token_ids") is not None or int(kw.get("min_new_tokens", 0)) != 0 or pen is not None:
         summary["constrained_tokens"] = sum(g.n_constrained or 0 for g in gens)
-    summary.update(pen_summary)
-    return summary
-
-
-def _beam_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, beam: dict, kw: dict) -> dict[str, Any]:
-    """``generate_file`` with ``beam_width > 1``.  ``logprobs`` is not an option here (every hypothesis carries its log-probability), and
-    ``device`` must be the model's, as ``generate`` asks."""
-    kw = dict(kw)
-    kw.pop("logprobs", None)
-    device = kw.pop("device", None)
-    if device is not None and torch.device(device) != model.device:
-        raise ValueError(f"generate: device {device} is not the model's ({model.device})")
-    found = beam_search(model, prompts, max_new_tokens=max_new_tokens, stop_token_ids=stop_token_ids, **beam, **kw)
-    with open(out_path, "w", encoding="utf-8") as f:
-        for item_id, p, g in zip(ids, prompts, found):
-            f.write(json.dumps(output_record(item_id, p, g, tokenizer, tokenizer_decoding), ensure_ascii=False) + "\n")
-    return {"items": len(found), "generated_tokens": sum(len(g.token_ids) for gs in found for g in gs),
-            "stopped": sum(g.finish_reason == "stop" for gs in found for g in gs), "beam_width": int(beam["beam_width"])}
-
-
-def _sample_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, draw: dict, kw: dict) -> dict[str, Any]:
-    """``generate_file`` with ``sample=True``.  ``logprobs`` is not an option here (every sample carries its log-probability)."""
-    kw = dict(kw)
-    kw.pop("logprobs", None)
-    device = kw.pop("device", None)
-    if device is not None and torch.device(device) != model.device:
-        raise ValueError(f"generate: device {device} is not the model's ({model.device})")
-    found = sample(model, prompts, max_new_tokens=max_new_tokens, stop_token_ids=stop_token_ids, **draw, **kw)
-    with open(out_path, "w", encoding="utf-8") as f:
-        for item_id, p, g in zip(ids, prompts, found):
-            f.write(json.dumps(output_record(item_id, p, g, tokenizer, tokenizer_decoding), ensure_ascii=False) + "\n")
-    tokens = sum(len(g.token_ids) for gs in found for g in gs)
-    kept = sum((g.n_kept_mean or 0.0) * len(g.token_ids) for gs in found for g in gs)
-    return {"items": len(found), "generated_tokens": tokens, "stopped": sum(g.finish_reason == "stop" for gs in found for g in gs),
-            "sampled": True, "n": int(draw.get("n", 1)), "kept_tokens_mean": kept / max(tokens, 1)}
+    return dict(summary, **pen_summary)       # (empty under beam search, which refuses a set penalty)
 
 
 # ---- what the script accepts of the reference's sampling_params ------------------------------------------------------------------

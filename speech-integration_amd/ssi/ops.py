@@ -226,6 +226,30 @@ def attn_decode(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, slot: Tensor, kv_
                                       stream_ptr()), "ssi_attn_decode")
 
 
+def _selection_rows(what: str, logits: Tensor, vocab: int, token: Tensor, logprob: Tensor | None, int32_rows, allow: Tensor | None,
+                    allow_early: Tensor | None) -> int:
+    """The checks the four selection wrappers share, under the wrapper's name ``what``: the logits, one entry per row of ``token`` (int64),
+    ``logprob`` (fp32) and every ``(name, tensor)`` of ``int32_rows``, and the two bit masks.  Returns the number of rows."""
+    ptr(logits)
+    if logits.dim() != 2 or logits.stride(1) != 1 or not 1 <= vocab <= logits.shape[1]:
+        raise _lib.HipLibraryError(f"{what}: logits must be [rows, >= vocab] with unit inner stride (got {tuple(logits.shape)}, vocab {vocab})")
+    rows, words = logits.shape[0], (vocab + 31) // 32
+    for name, t, dtype in (("token", token, torch.int64), ("logprob", logprob, torch.float32), *((name, t, torch.int32) for name, t in int32_rows)):
+        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.numel() != rows or t.device != logits.device):
+            raise _lib.HipLibraryError(f"{what}: {name} is one {dtype} per row of logits, on its device")
+    for name, t in (("allow", allow), ("allow_early", allow_early)):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != words or t.device != logits.device):
+            raise _lib.HipLibraryError(f"{what}: {name} is {words} int32 words (one bit per column) on the device of logits")
+    return rows
+
+
+def _draw_args(what: str, seed: int, step: int, top_k: int) -> int:
+    """The ranges of ``seed`` and ``step`` the two sampling wrappers share; returns ``top_k`` as the C entry takes it."""
+    if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(step) < 2 ** 32:
+        raise _lib.HipLibraryError(f"{what}: seed is in [0, 2^64) and step in [0, 2^32) (got {seed}, {step})")
+    return max(-1, min(int(top_k), 2 ** 62))
+
+
 def decode_select(logits: Tensor, vocab: int, token: Tensor, logprob: Tensor | None = None, rank: Tensor | None = None, *,
                   allow: Tensor | None = None, allow_early: Tensor | None = None, n_generated: Tensor | None = None, min_new: int = 0) -> None:
     """The constrained greedy token of every row of ``logits`` ([rows, ld], unit inner stride; read only): ``token`` (int64) = the first
@@ -233,17 +257,7 @@ def decode_select(logits: Tensor, vocab: int, token: Tensor, logprob: Tensor | N
     real columns, ``rank`` (int32, optional) = its position in a stable descending sort of the row (0: the constraint did not bind).  ``allow``
     / ``allow_early``: int32 bit masks of ``ceil(vocab / 32)`` words (bit ``c % 32`` of word ``c // 32``), ``None`` = every column; row ``r``
     takes ``allow_early`` while ``n_generated[r] < min_new`` (int32 per row).  A row with nothing allowed: -1 / 0 / -1.  ``ssi_decode_select``."""
-    ptr(logits)
-    if logits.dim() != 2 or logits.stride(1) != 1 or not 1 <= vocab <= logits.shape[1]:
-        raise _lib.HipLibraryError(f"decode_select: logits must be [rows, >= vocab] with unit inner stride (got {tuple(logits.shape)}, vocab {vocab})")
-    rows, words = logits.shape[0], (vocab + 31) // 32
-    for name, t, dtype in (("token", token, torch.int64), ("logprob", logprob, torch.float32), ("rank", rank, torch.int32),
-                           ("n_generated", n_generated, torch.int32)):
-        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.numel() != rows or t.device != logits.device):
-            raise _lib.HipLibraryError(f"decode_select: {name} is one {dtype} per row of logits, on its device")
-    for name, t in (("allow", allow), ("allow_early", allow_early)):
-        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != words or t.device != logits.device):
-            raise _lib.HipLibraryError(f"decode_select: {name} is {words} int32 words (one bit per column) on the device of logits")
+    rows = _selection_rows("decode_select", logits, vocab, token, logprob, (("rank", rank), ("n_generated", n_generated)), allow, allow_early)
     check(_lib.load().ssi_decode_select(ptr(logits), logits.stride(0), rows, int(vocab), ptr(allow), ptr(allow_early), ptr(n_generated),
                                         int(min_new), ptr(token), ptr(logprob), ptr(rank), dtype_code(logits.dtype), stream_ptr()),
           "ssi_decode_select")
@@ -258,20 +272,8 @@ def decode_sample(logits: Tensor, vocab: int, token: Tensor, logprob: Tensor | N
     ``logprob`` (fp32, optional) = the token's log-probability over ALL real columns at temperature 1 (``decode_select``'s); ``n_kept`` (int32,
     optional) = the size of the set drawn from.  ``sequence``: one int32 per row, read as unsigned.  The masks, ``n_generated`` and ``min_new``
     are ``decode_select``'s.  A row with nothing allowed: -1 / 0 / -1.  ``ssi_decode_sample``."""
-    ptr(logits)
-    if logits.dim() != 2 or logits.stride(1) != 1 or not 1 <= vocab <= logits.shape[1]:
-        raise _lib.HipLibraryError(f"decode_sample: logits must be [rows, >= vocab] with unit inner stride (got {tuple(logits.shape)}, vocab {vocab})")
-    rows, words = logits.shape[0], (vocab + 31) // 32
-    for name, t, dtype in (("token", token, torch.int64), ("logprob", logprob, torch.float32), ("n_kept", n_kept, torch.int32),
-                           ("n_generated", n_generated, torch.int32), ("sequence", sequence, torch.int32)):
-        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.numel() != rows or t.device != logits.device):
-            raise _lib.HipLibraryError(f"decode_sample: {name} is one {dtype} per row of logits, on its device")
-    for name, t in (("allow", allow), ("allow_early", allow_early)):
-        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != words or t.device != logits.device):
-            raise _lib.HipLibraryError(f"decode_sample: {name} is {words} int32 words (one bit per column) on the device of logits")
-    if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(step) < 2 ** 32:
-        raise _lib.HipLibraryError(f"decode_sample: seed is in [0, 2^64) and step in [0, 2^32) (got {seed}, {step})")
-    top_k = max(-1, min(int(top_k), 2 ** 62))
+    rows = _selection_rows("decode_sample", logits, vocab, token, logprob, (("n_kept", n_kept), ("n_generated", n_generated), ("sequence", sequence)), allow, allow_early)
+    top_k = _draw_args("decode_sample", seed, step, top_k)
     check(_lib.load().ssi_decode_sample(ptr(logits), logits.stride(0), rows, int(vocab), ptr(allow), ptr(allow_early), ptr(n_generated),
                                         int(min_new), float(temperature), top_k, float(top_p), int(seed), int(step), ptr(sequence), ptr(token),
                                         ptr(logprob), ptr(n_kept), dtype_code(logits.dtype), stream_ptr()), "ssi_decode_sample")
@@ -328,17 +330,7 @@ def decode_select_pen(logits: Tensor, vocab: int, token: Tensor, logprob: Tensor
     ``prompt_len`` per line, row ``r`` reading line ``prompt_row[r]`` (``None``: line ``r``); ``gen_ids`` int64 ``[rows, ld_gen]`` of which row
     ``r`` reads its first ``n_generated[r]`` entries (int32, required).  ``n_bad`` (int32 ``[1]``, optional) counts the rows that held an id or a
     line out of range, which are skipped.  ``ssi_decode_select_pen``."""
-    ptr(logits)
-    if logits.dim() != 2 or logits.stride(1) != 1 or not 1 <= vocab <= logits.shape[1]:
-        raise _lib.HipLibraryError(f"decode_select_pen: logits must be [rows, >= vocab] with unit inner stride (got {tuple(logits.shape)}, vocab {vocab})")
-    rows, words = logits.shape[0], (vocab + 31) // 32
-    for name, t, dtype in (("token", token, torch.int64), ("logprob", logprob, torch.float32), ("rank", rank, torch.int32),
-                           ("n_generated", n_generated, torch.int32)):
-        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.numel() != rows or t.device != logits.device):
-            raise _lib.HipLibraryError(f"decode_select_pen: {name} is one {dtype} per row of logits, on its device")
-    for name, t in (("allow", allow), ("allow_early", allow_early)):
-        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != words or t.device != logits.device):
-            raise _lib.HipLibraryError(f"decode_select_pen: {name} is {words} int32 words (one bit per column) on the device of logits")
+    rows = _selection_rows("decode_select_pen", logits, vocab, token, logprob, (("rank", rank), ("n_generated", n_generated)), allow, allow_early)
     tail = _penalty_args("decode_select_pen", logits, int(vocab), n_generated, prompt_ids, prompt_len, prompt_row, gen_ids, repetition_penalty,
                          frequency_penalty, presence_penalty, n_bad)
     check(_lib.load().ssi_decode_select_pen(ptr(logits), logits.stride(0), rows, int(vocab), ptr(allow), ptr(allow_early), ptr(n_generated),
@@ -354,20 +346,8 @@ def decode_sample_pen(logits: Tensor, vocab: int, token: Tensor, logprob: Tensor
     """``decode_sample`` under vLLM's penalties: the allowed set, top-k, top-p, the masses and the Gumbel-max score are all taken on the
     PENALISED row ``y`` (penalties before temperature: vLLM's order); ``logprob`` stays that of the raw row at temperature 1.  The random bits
     are ``decode_sample``'s.  The history arguments are ``decode_select_pen``'s.  ``ssi_decode_sample_pen``."""
-    ptr(logits)
-    if logits.dim() != 2 or logits.stride(1) != 1 or not 1 <= vocab <= logits.shape[1]:
-        raise _lib.HipLibraryError(f"decode_sample_pen: logits must be [rows, >= vocab] with unit inner stride (got {tuple(logits.shape)}, vocab {vocab})")
-    rows, words = logits.shape[0], (vocab + 31) // 32
-    for name, t, dtype in (("token", token, torch.int64), ("logprob", logprob, torch.float32), ("n_kept", n_kept, torch.int32),
-                           ("n_generated", n_generated, torch.int32), ("sequence", sequence, torch.int32)):
-        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.numel() != rows or t.device != logits.device):
-            raise _lib.HipLibraryError(f"decode_sample_pen: {name} is one {dtype} per row of logits, on its device")
-    for name, t in (("allow", allow), ("allow_early", allow_early)):
-        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != words or t.device != logits.device):
-            raise _lib.HipLibraryError(f"decode_sample_pen: {name} is {words} int32 words (one bit per column) on the device of logits")
-    if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(step) < 2 ** 32:
-        raise _lib.HipLibraryError(f"decode_sample_pen: seed is in [0, 2^64) and step in [0, 2^32) (got {seed}, {step})")
-    top_k = max(-1, min(int(top_k), 2 ** 62))
+    rows = _selection_rows("decode_sample_pen", logits, vocab, token, logprob, (("n_kept", n_kept), ("n_generated", n_generated), ("sequence", sequence)), allow, allow_early)
+    top_k = _draw_args("decode_sample_pen", seed, step, top_k)
     tail = _penalty_args("decode_sample_pen", logits, int(vocab), n_generated, prompt_ids, prompt_len, prompt_row, gen_ids, repetition_penalty,
                          frequency_penalty, presence_penalty, n_bad)
     check(_lib.load().ssi_decode_sample_pen(ptr(logits), logits.stride(0), rows, int(vocab), ptr(allow), ptr(allow_early), ptr(n_generated),
