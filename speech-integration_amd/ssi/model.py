@@ -423,8 +423,9 @@ class HipLlamaDecoder(nn.Module):
 
     def takes_small_batch(self, rows: int, small_batch: bool) -> bool:
         """Does a decode step of ``rows`` rows with this flag run on the skinny GEMMs?  (The flag alone never does: fp32 models, shapes off the
-        MFMA path and more rows than the limit keep the tile path, launch for launch.)"""
-        return bool(small_batch) and self._mfma_shapes() and 1 <= rows <= min(self.skinny_max_rows, _lib.GEMM_SKINNY_MAX_ROWS)
+        MFMA path, a head_dim other than 64 — the only one ``ssi_gemm_skinny_rope`` rotates — and more rows than the limit keep the tile
+        path, launch for launch.)"""
+        return bool(small_batch) and self._mfma_shapes() and self.head_dim == 64 and 1 <= rows <= min(self.skinny_max_rows, _lib.GEMM_SKINNY_MAX_ROWS)
 
     # ---- forward: decoder stack --------------------------------------------------------------------------------------
     @staticmethod
@@ -793,7 +794,7 @@ class HipLlamaDecoder(nn.Module):
         makes every GEMM of the step one of the training step's tiles; all activations live in arena buffers of their own (``*.g``), so a
         step may run between a training forward and its backward.  A slot whose length has reached the cap is not written (its K / V
         would land in the next slot) and is counted in ``cache.errors``; ``prefill`` refuses what would get there.
-        ``small_batch`` (with 1 to ``skinny_max_rows`` rows on the MFMA shapes; otherwise without effect): the rows are NOT padded, the layer
+        ``small_batch`` (with 1 to ``skinny_max_rows`` rows on the MFMA shapes with head_dim 64; otherwise without effect): the rows are NOT padded, the layer
         GEMMs and the head run on the weight-streaming skinny kernels and the activations live in the ``*.s`` buffers; norms, embedding,
         ``kv_store`` and ``attn_decode`` are the same launches on fewer rows.  A row's logits do not depend on the rows beside it."""
         self._check_cache(cache)

@@ -27,6 +27,37 @@ def test_the_abi_names_the_three_entries():
     assert 1 <= HipLlamaDecoder.skinny_max_rows <= _lib.GEMM_SKINNY_MAX_ROWS
 
 
+def _geometry(num_heads, num_kv_heads, embed_dim, intermediate_dim, dtype=torch.bfloat16):
+    """What ``HipLlamaDecoder._mfma_shapes`` and ``takes_small_batch`` read of a model (the model itself exists on a GPU only); the two methods
+    are the class's own."""
+    from ssi.model import HipLlamaDecoder
+
+    class Geometry:
+        _mfma_shapes, takes_small_batch, skinny_max_rows = HipLlamaDecoder._mfma_shapes, HipLlamaDecoder.takes_small_batch, HipLlamaDecoder.skinny_max_rows
+
+    g = Geometry()
+    g.dtype, g.num_heads, g.num_kv_heads, g.embed_dim, g.intermediate_dim = dtype, num_heads, num_kv_heads, embed_dim, intermediate_dim
+    g.head_dim = embed_dim // num_heads
+    g.qkv_dim = (num_heads + 2 * num_kv_heads) * g.head_dim
+    return g
+
+
+def test_only_head_dim_64_takes_the_small_batch_path():
+    """``ssi_gemm_skinny_rope`` rotates head_dim 64 and refuses every other: a bf16 model on the MFMA shapes with head_dim 128 (Llama-3.2-3B:
+    24 heads, 8 kv heads, D 3072, I 8192, and its small stand-in of tests/test_model_head_geometry_gpu.py) or 32 keeps the tile path at every
+    row count, the 1B geometry takes the skinny path for 1 to 64 rows."""
+    for heads, kv, D, I, hd in ((24, 8, 3072, 8192, 128), (6, 2, 768, 1024, 128), (16, 4, 512, 512, 32)):
+        g = _geometry(heads, kv, D, I)
+        assert g.head_dim == hd and g._mfma_shapes()
+        assert not any(g.takes_small_batch(rows, True) for rows in (1, 5, 64, 65))
+    for heads, kv, D, I in ((32, 8, 2048, 8192), (8, 2, 512, 512)):
+        g = _geometry(heads, kv, D, I)
+        assert g.head_dim == 64 and g._mfma_shapes()
+        assert [g.takes_small_batch(rows, True) for rows in (0, 1, 5, 64, 65)] == [False, True, True, True, False]
+        assert not g.takes_small_batch(5, False)
+        assert not _geometry(heads, kv, D, I, torch.float32).takes_small_batch(5, True)
+
+
 def test_the_wrappers_refuse_cpu_tensors():
     from ssi import _lib, ops
     a, w, c = torch.zeros(2, 64, dtype=torch.bfloat16), torch.zeros(128, 64, dtype=torch.bfloat16), torch.zeros(2, 128, dtype=torch.bfloat16)
