@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 24 /* 24: + ssi_gemm_skinny, ssi_gemm_skinny_rope, ssi_gemm_skinny_swiglu (weight-streaming bf16 GEMMs for 1 to 64 rows: small-batch decoding; opt-in)
+#define SSI_ABI_VERSION 25 /* 25: + ssi_attn_decode_split, ssi_attn_decode_beam_split, ssi_attn_decode_split_span, ssi_attn_decode_split_workspace (split-KV decode attention: the keys of a row over several workgroups, a merge launch behind them; opt-in)
+                           * 24: + ssi_gemm_skinny, ssi_gemm_skinny_rope, ssi_gemm_skinny_swiglu (weight-streaming bf16 GEMMs for 1 to 64 rows: small-batch decoding; opt-in)
                            * 23: + ssi_sumsq_groups, ssi_adamw_step_seg_gscale (per-group gradient norms of the flat buffer in one pass, a per-segment device gradient scale in the segmented AdamW; opt-in)
                            * 22: + ssi_decode_select_pen, ssi_decode_sample_pen (repetition, frequency and presence penalties inside the two selection kernels; opt-in)
                            * 21: + ssi_decode_sample (sampled decoding: temperature, top-k, top-p and a seeded Gumbel-max draw of a row's token in one launch; opt-in)
@@ -257,6 +258,42 @@ int ssi_attn_decode_beam(const void* qkv, int64_t ld, const void* pk_cache, cons
                          const void* bk_cache, const void* bv_cache, int64_t n_bslots, int64_t cap_b, const int32_t* prompt_slot,
                          const int32_t* prompt_len, const int32_t* gen_len, const int32_t* anc, int64_t ld_anc, void* out, float* lse,
                          int64_t rows, int n_heads, int n_kv, int head_dim, int32_t* n_bad, int dtype, void* stream);
+
+/* ---- Split-KV decode attention (ABI v25; few rows, long caches: one workgroup per (row, kv head) leaves most of the device idle) ---------------
+ * ssi_attn_decode / ssi_attn_decode_beam with the keys of a (row, kv head) split over workgroups.  THE DEFINITION, for a row with n keys (the
+ * slot form: min(kv_len, cap); the beam form: prompt_len + gen_len after their clamps, the concatenated index) and a span of `span` keys:
+ *   walk   grid (rows, n_kv, n_splits).  Workgroup z walks the keys [z * span, min((z + 1) * span, n)) exactly as the plain kernel walks a
+ *          cache that starts at key z * span — lanes, loads, chunks, waves, the xor tree and the four-wave merge placed relative to the split's
+ *          first key — and writes its merged, UNNORMALISED fp32 state per query head to workspace[r, h, z, :] = (O[head_dim], M, L).  A
+ *          workgroup with z * span >= n returns before it reads or writes anything.
+ *   merge  grid (rows, n_kv), behind the walk on the same stream.  It reads the S = ceil(n / span) partials z = 0 .. S - 1 of the row and no
+ *          other (the workspace is never zeroed), and applies the four-wave merge's formula in that order:
+ *              M = max_z M_z;   e_z = (M_z == -inf ? 0 : exp2(M_z - M));   L = fma(L_z, e_z, L);   O_d = fma(O_{z,d}, e_z, O_d)
+ *          then the plain kernel's finish: a row all of whose keys were skipped is zeros with lse -inf, otherwise out = O / L with ONE rounding
+ *          and lse = (M + log2 L) ln 2.  Dead rows (slot < 0, n <= 0, the slot form's slot >= n_slots) are zeros and -inf, written here.
+ * The kernel boundary is the only synchronisation between workgroups: no atomics on values, no ticket, no flag.
+ * It follows: a row with n <= span equals the plain entry by VALUE in out and lse (a zero may differ in sign); a row's result is a function of
+ * its own query, its own keys, n and span only (not of rows, its place, n_splits or its neighbours); with equal span the beam form equals the
+ * slot form on a cache that holds the row's keys one behind the other.  Against the plain entry a row with n > span differs by the merge order.
+ * span: a positive multiple of the form's ROUND of 8 loads = 512 / LPK keys (bf16, head_dim 64: 64; fp32, head_dim 64: 32; 16 to 512 over all
+ * forms).  n_splits in [1, 65535] with n_splits * span >= cap (the beam form: >= cap_p + min(cap_b, ld_anc)): no key can be dropped.
+ * workspace: caller-owned, 16-byte aligned, at least ssi_attn_decode_split_workspace bytes = rows * n_heads * n_splits * (head_dim + 2) * 4.
+ * Any of these violated: SSI_ERR_ARG before any launch.  Geometries, dtypes, alignment and every other argument: the plain entries'.
+ * Errors are counted as there, once per row: the slot outside the cache by the merge, an index outside its cache in the beam form by the
+ * z = 0, kv head 0 workgroup of the walk (over the row's whole ancestry).
+ * Forms: the walk per dtype x G = 1, 2, 4, 8 and per key source (16), the merge per dtype (2).  No LDS in the merge, no scratch anywhere. */
+/* the default span in keys of a form: max(128, the form's round) — 128 by measurement (README, "Split-KV decode attention"); 0: unsupported */
+int ssi_attn_decode_split_span(int head_dim, int dtype);
+int64_t ssi_attn_decode_split_workspace(int64_t rows, int n_heads, int head_dim, int64_t n_splits);
+int ssi_attn_decode_split(const void* qkv, int64_t ld, const void* k_cache, const void* v_cache, int64_t n_slots, int64_t cap,
+                          const int32_t* slot, const int32_t* kv_len, void* out, float* lse, int64_t rows, int n_heads, int n_kv,
+                          int head_dim, int32_t* n_bad, int64_t span, int64_t n_splits, void* workspace, int64_t workspace_bytes, int dtype,
+                          void* stream);
+int ssi_attn_decode_beam_split(const void* qkv, int64_t ld, const void* pk_cache, const void* pv_cache, int64_t n_pslots, int64_t cap_p,
+                               const void* bk_cache, const void* bv_cache, int64_t n_bslots, int64_t cap_b, const int32_t* prompt_slot,
+                               const int32_t* prompt_len, const int32_t* gen_len, const int32_t* anc, int64_t ld_anc, void* out, float* lse,
+                               int64_t rows, int n_heads, int n_kv, int head_dim, int32_t* n_bad, int64_t span, int64_t n_splits,
+                               void* workspace, int64_t workspace_bytes, int dtype, void* stream);
 
 /* The k best allowed continuations of every row of logits [rows, ld] with their log-probabilities (ABI v20, beam search).  Logits read only.
  * mask: ssi_decode_select's bit mask (mask_words = ceil(vocab / 32) int32 words, bit c % 32 of word c / 32), or NULL with mask_words 0 = every

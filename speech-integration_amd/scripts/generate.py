@@ -86,6 +86,8 @@ def main(cfg):
     constraints.update(penalties)     # gen.penalties: the three values check_penalties let through
     if bool(cfg.gen.get("small_batch") or False):          # gen.small_batch: groups of at most 64 rows on the skinny GEMMs; absent from the call otherwise
         constraints["small_batch"] = True
+    if bool(cfg.gen.get("split_kv") or False):             # gen.split_kv: the split-KV decode attention for groups of few rows; absent from the call otherwise
+        constraints["split_kv"] = True
     summary = generate_file(t.model, t.tokenizer, None if prompts is not None else str(cfg.gen.input), out_path,
                             max_new_tokens=int(cfg.sampling_params.max_tokens), stop_token_ids=None if stop is None else [int(s) for s in stop],
                             tokenizer_decoding={k: cfg.tokenizer_decoding[k] for k in cfg.tokenizer_decoding}, prompts=prompts, ids=ids,

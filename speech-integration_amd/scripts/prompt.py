@@ -35,6 +35,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--repetition-penalty", type=float, default=1.0)
     p.add_argument("--frequency-penalty", type=float, default=0.0)
     p.add_argument("--presence-penalty", type=float, default=0.0)
+    p.add_argument("--split-kv", action="store_true", help="split-KV decode attention: the keys of a row over several workgroups (long prompts)")
     p.add_argument("--jsonl", metavar="OUT", help="also write one record per prompt (the generations file's line format)")
     return p
 
@@ -102,7 +103,7 @@ def main(argv=None) -> int:
     prompts = prompts_of(args, tokenizer)
     found = probe(model, tokenizer, prompts, max_new_tokens=args.max_new_tokens, n=args.n, temperature=args.temperature, top_k=args.top_k,
                   top_p=args.top_p, seed=args.seed, repetition_penalty=args.repetition_penalty, frequency_penalty=args.frequency_penalty,
-                  presence_penalty=args.presence_penalty, tokenizer_decoding=decoding)
+                  presence_penalty=args.presence_penalty, tokenizer_decoding=decoding, split_kv=args.split_kv)
     for p in found:
         for text in p.texts:
             print(text)

@@ -191,18 +191,24 @@ def _constraint(masks: tuple[Tensor, Tensor] | None, min_new: int, dev) -> _Cons
     return _Constraint(allow, _mask_words(masks[0]).to(dev), early if min_new else None, _mask_words(masks[1]).to(dev) if min_new else None, min_new)
 
 
-def _small_batch_kw(model, rows: int, small_batch: bool, report: dict | None) -> tuple[dict, dict]:
-    """The keywords of a group of ``rows`` rows, decided once per group: (``prefill``'s, a decode step's).  Without the flag both are empty — the
-    calls are then the plain ones, argument for argument.  With it every step gets ``small_batch``, and a group that decodes on the skinny path
-    prefills prompt by prompt (``separate``), so that nothing of a prompt's result depends on the prompts beside it; such a group is counted in
-    ``report`` (the ``small_batch_groups`` of the run summary: what ran, counted where it ran)."""
-    if not small_batch:
-        return {}, {}
-    if not model.takes_small_batch(rows, True):
-        return {}, {"small_batch": True}
-    if report is not None:
-        report["small_batch_groups"] = report.get("small_batch_groups", 0) + 1
-    return {"separate": True}, {"small_batch": True}
+def _small_batch_kw(model, rows: int, small_batch: bool, report: dict | None, split_kv: bool = False) -> tuple[dict, dict]:
+    """The keywords of a group of ``rows`` rows, decided once per group: (``prefill``'s, a decode step's).  Without a flag both are empty — the
+    calls are then the plain ones, argument for argument.  With ``small_batch`` every step gets ``small_batch``, and a group that decodes on the
+    skinny path prefills prompt by prompt (``separate``), so that nothing of a prompt's result depends on the prompts beside it; such a group is
+    counted in ``report`` (the ``small_batch_groups`` of the run summary: what ran, counted where it ran).  ``split_kv`` likewise: every step
+    gets ``split_kv``, and a group whose steps take the split-KV attention (``HipLlamaDecoder.takes_split_kv``) prefills prompt by prompt and is
+    counted as one of the ``split_kv_groups``."""
+    prefill_kw, step_kw = {}, {}
+    for flag, on, takes in (("small_batch", small_batch, model.takes_small_batch if small_batch else None),
+                            ("split_kv", split_kv, model.takes_split_kv if split_kv else None)):
+        if not on:
+            continue
+        step_kw[flag] = True
+        if takes(rows, True):
+            prefill_kw = {"separate": True}
+            if report is not None:
+                report[flag + "_groups"] = report.get(flag + "_groups", 0) + 1
+    return prefill_kw, step_kw
 
 
 def _run_groups(model, prompts: Sequence[Any], per_group: int, max_new_tokens: int, stop_token_ids: Sequence[int], masks, min_new: int,
@@ -393,21 +399,21 @@ class _Sample(_Selection):
 
 
 # ---- the steppers: the next logits -------------------------------------------------------------------------------------------------
-def _own_slots(model, caches, seqs: list[Tensor], max_new: int, small_batch: bool, report: dict | None):
+def _own_slots(model, caches, seqs: list[Tensor], max_new: int, small_batch: bool, report: dict | None, split_kv: bool = False):
     """Row ``r`` is prompt ``r`` and decodes on slot ``r`` of the one cache: ``prefill`` with room for the new tokens, then ``decode_step``.
     Returns the prefill's logits and the stepper."""
-    prefill_kw, step_kw = _small_batch_kw(model, len(seqs), small_batch, report)
+    prefill_kw, step_kw = _small_batch_kw(model, len(seqs), small_batch, report, split_kv)
     logits = model.prefill(caches[0], seqs, max_new_tokens=max_new, **prefill_kw)
     own = torch.arange(len(seqs), dtype=torch.int32, device=model.device)
     none = torch.full_like(own, -1)
     return logits, lambda t, tokens, alive: model.decode_step(caches[0], tokens, torch.where(alive, own, none), **step_kw)
 
 
-def _shared_prompt(model, caches, seqs: list[Tensor], n: int, max_new: int, small_batch: bool, report: dict | None):
+def _shared_prompt(model, caches, seqs: list[Tensor], n: int, max_new: int, small_batch: bool, report: dict | None, split_kv: bool = False):
     """Row ``s * n + j`` is continuation ``j`` of prompt ``s``: the prompt is prefilled once into the prompt cache, its logits row repeated
     ``n`` times for step 0, and the rows run on ``decode_step_beam`` with the identity ancestry — a row reads its own generated positions."""
     rows, dev = len(seqs) * n, model.device
-    prefill_kw, step_kw = _small_batch_kw(model, rows, small_batch, report)
+    prefill_kw, step_kw = _small_batch_kw(model, rows, small_batch, report, split_kv)
     logits = model.prefill(caches[0], seqs, **prefill_kw)[:len(seqs)].repeat_interleave(n, dim=0)
     own = torch.arange(rows, dtype=torch.int32, device=dev)
     seq_of, none = own // n, torch.full_like(own, -1)
@@ -419,7 +425,8 @@ def _shared_prompt(model, caches, seqs: list[Tensor], n: int, max_new: int, smal
 def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_ids: Sequence[int], pad_id: int, batch_size: int = 256,
              logprobs: bool = False, device: torch.device | str | None = None, allowed_token_ids: Sequence[int] | Tensor | None = None,
              min_new_tokens: int = 0, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
-             presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None) -> list[Generation]:
+             presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None,
+             split_kv: bool = False) -> list[Generation]:
     """Greedy continuation of every prompt (1-D integer sequences), results in INPUT order.  The token of a step is ``argmax`` over the real
     columns ``[:, :vocab_size]`` of the step's logits, with torch's first-occurrence rule.  ``pad_id`` fills the rows that have finished.
     ``logprobs=True``: the forward-only ``ops.ce_fwd_metrics`` runs on the step's logits with the chosen token as label, which gives its
@@ -436,6 +443,10 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
     skinny GEMMs (``HipLlamaDecoder.takes_small_batch``), a larger one takes the tile path by itself.  A row's tokens and log-probabilities do
     not depend on the rows beside it.  ``False``: not one launch or buffer differs.  ``small_batch_report`` (a dict, or None): every group that
     took the skinny path adds 1 to its ``"small_batch_groups"``.
+    ``split_kv``: handed to every ``decode_step`` of every group; a group of 1 to ``model.split_max_rows`` rows then runs the split-KV decode
+    attention (``HipLlamaDecoder.takes_split_kv``) and prefills prompt by prompt, and adds 1 to ``"split_kv_groups"`` of ``small_batch_report``.
+    A row still depends on itself alone, but its bits depend on whether its group splits: tokens and ``cumulative_logprob`` are bit-equal among
+    groups on the same side of ``split_max_rows`` (as for ``skinny_max_rows``).  ``False``: not one launch or buffer differs.
     Refused before any launch (``ValueError``): a penalty outside its range, an empty prompt, a prompt that with ``max_new_tokens`` exceeds the model's RoPE table or
     ``max_seq_len``; ``min_new_tokens < 0``, an allowed or stop id outside the vocabulary (under a constraint), an empty allowed set,
     ``min_new_tokens > 0`` with nothing allowed besides the stop tokens."""
@@ -450,7 +461,7 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
     refused = "generate: the K/V cache kernels refused {} rows (a destination or a slot outside the cache)"
 
     def run_group(caches, con, seqs: list[Tensor], index: list[int], stop: Tensor) -> list[Generation]:
-        started = _own_slots(model, caches, seqs, max_new_tokens, small_batch, small_batch_report)
+        started = _own_slots(model, caches, seqs, max_new_tokens, small_batch, small_batch_report, split_kv)
         choose = _Argmax(model, len(seqs), logprobs) if con is None and pen is None else _Select(model, seqs, con, pen, logprobs)
         return _token_loop(choose, started, caches, refused, [int(s.numel()) for s in seqs], max_new_tokens, stop, int(pad_id))
 
@@ -476,7 +487,8 @@ def _check_beam(beam_width, length_penalty, n_best) -> tuple[int, float, int]:
 def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_tokens: int, stop_token_ids: Sequence[int], pad_id: int,
                 length_penalty: float = 1.0, n_best: int = 1, allowed_token_ids: Sequence[int] | Tensor | None = None, min_new_tokens: int = 0,
                 batch_size: int = 256, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
-                presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None) -> list[list[Generation]]:
+                presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None,
+             split_kv: bool = False) -> list[list[Generation]]:
     """The ``n_best <= beam_width <= 8`` best hypotheses of every prompt, best first, in INPUT order; ``cumulative_logprob`` (the sum of the
     tokens' log-probabilities under the unconstrained distribution) and ``score`` are always set.  A group holds ``batch_size // beam_width``
     prompts, so a step is at most ``batch_size`` rows.  The rules, with ``W = beam_width``:
@@ -494,7 +506,7 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
 
     Refused before any launch (``ValueError``): the three beam arguments outside their ranges, a penalty off its neutral value (vLLM's beam
     search ignores them, and ``ssi_topk_logprob`` knows none), and everything ``generate`` refuses.
-    ``small_batch``: handed to every ``decode_step_beam`` (``generate``'s rule, on the group's ``prompts * beam_width`` rows)."""
+    ``small_batch``, ``split_kv``: handed to every ``decode_step_beam`` (``generate``'s rules, on the group's ``prompts * beam_width`` rows)."""
     W, length_penalty, n_best = _check_beam(beam_width, length_penalty, n_best)
     if _check_penalties(repetition_penalty, frequency_penalty, presence_penalty) is not None:
         raise ValueError("beam_search: repetition, frequency and presence penalties are not part of beam search")
@@ -514,18 +526,18 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
 
     def run_group(caches, con, seqs: list[Tensor], index: list[int], stop: Tensor) -> list[list[Generation]]:
         return _beam_group(model, *caches[:2], seqs, W, max_new_tokens, stop, int(pad_id), length_penalty, n_best, caches[2], min_new_tokens,
-                           small_batch, small_batch_report)
+                           small_batch, small_batch_report, split_kv)
 
     return _run_groups(model, prompts, batch_size // W, max_new_tokens, stop_token_ids, None, 0, open_caches, run_group)       # (its mask is cont)
 
 
 def _beam_group(model, pcache, bcache, seqs: list[Tensor], W: int, max_new: int, stop: Tensor, pad_id: int, length_penalty: float, n_best: int,
-                cont_words: Tensor, min_new: int, small_batch: bool = False, report: dict | None = None) -> list[list[Generation]]:
+                cont_words: Tensor, min_new: int, small_batch: bool = False, report: dict | None = None, split_kv: bool = False) -> list[list[Generation]]:
     """One group: row ``s * W + b`` is beam ``b`` of prompt ``s``.  Everything of a step stays on the device."""
     n, dev, V, S = len(seqs), model.device, int(model.vocab_size), int(stop.numel())
     R, P, NEG = n * W, 2 * W, float("-inf")     # a pool never holds more than (W - 1) + W hypotheses; place P takes what is not stored
     i64, f32 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float32, device=dev)
-    prefill_kw, step_kw = _small_batch_kw(model, R, small_batch, report)
+    prefill_kw, step_kw = _small_batch_kw(model, R, small_batch, report, split_kv)
     logits = model.prefill(pcache, seqs, **prefill_kw)
     own = torch.arange(R, dtype=torch.int32, device=dev)
     seq_of = own // W
@@ -633,7 +645,8 @@ def _check_sample(n, temperature, top_k, top_p, seed) -> tuple[int, float, int, 
 def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top_k: int = -1, top_p: float = 1.0, seed: int, max_new_tokens: int,
            stop_token_ids: Sequence[int], pad_id: int, batch_size: int = 256, allowed_token_ids: Sequence[int] | Tensor | None = None,
            min_new_tokens: int = 0, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
-           presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None) -> list[list[Generation]]:
+           presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None,
+             split_kv: bool = False) -> list[list[Generation]]:
     """``n`` (1..8) sampled continuations of every prompt, in INPUT order and per prompt in sample order; ``cumulative_logprob`` (the tokens'
     log-probabilities under the unconstrained distribution at temperature 1, what ``ssi.score`` assigns) and ``n_kept_mean`` are always set.
     The token of a step is ``ops.decode_sample``'s with ``step`` the loop index and ``sequence = prompt index * n + sample index``: a pure function
@@ -647,7 +660,7 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
     one line of the group's prompt table.  The log-probabilities stay those of the raw row.
     Refused before any launch (``ValueError``): ``n`` outside 1..8, ``temperature`` not finite or <= 0 (greedy decoding is ``generate``), ``top_p``
     outside (0, 1], a non-integer ``top_k``, a negative ``seed``, and everything ``generate`` refuses.
-    ``small_batch``: handed to every decode step (``generate``'s rule, on the group's ``prompts * n`` rows)."""
+    ``small_batch``, ``split_kv``: handed to every decode step (``generate``'s rules, on the group's ``prompts * n`` rows)."""
     n, temperature, top_k, top_p, seed = _check_sample(n, temperature, top_k, top_p, seed)
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
     max_new_tokens, batch_size, min_new_tokens, V = int(max_new_tokens), int(batch_size), int(min_new_tokens), int(model.vocab_size)
@@ -668,9 +681,9 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
 
     def run_group(caches, con, seqs: list[Tensor], index: list[int], stop: Tensor) -> list[list[Generation]]:
         if n == 1:          # no prompt to share: every row on its own slot, as ``generate``
-            started = _own_slots(model, caches, seqs, max_new_tokens, small_batch, small_batch_report)
+            started = _own_slots(model, caches, seqs, max_new_tokens, small_batch, small_batch_report, split_kv)
         else:
-            started = _shared_prompt(model, caches, seqs, n, max_new_tokens, small_batch, small_batch_report)
+            started = _shared_prompt(model, caches, seqs, n, max_new_tokens, small_batch, small_batch_report, split_kv)
         choose = _Sample(model, seqs, index, n, draw, con, pen)
         found = _token_loop(choose, started, caches, refused, [int(s.numel()) for s in seqs for _ in range(n)], max_new_tokens, stop, int(pad_id))
         return [found[s * n:s * n + n] for s in range(len(seqs))]
@@ -734,7 +747,8 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     ``repetition_penalty``, ``frequency_penalty``, ``presence_penalty`` in ``kw`` go to ``generate`` / ``sample`` (``beam_search`` refuses them off
     their neutral values); when any is set the summary gains the three values, and on the greedy path ``"constrained_tokens"``.
     ``small_batch=True`` in ``kw`` goes to whichever loop runs, and the summary gains ``"small_batch_groups"``: the number of groups that decoded on
-    the skinny path.  ``False`` (the default) is not passed on and adds no key."""
+    the skinny path.  ``split_kv=True`` likewise, with ``"split_kv_groups"``: the groups that ran the split-KV decode attention.  ``False`` (the
+    default of both) is not passed on and adds no key."""
     if in_path is not None:
         ids, prompts = _read_prompts(tokenizer, in_path)
     elif prompts is None:
@@ -745,11 +759,12 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     if stop_token_ids is None:
         stop_token_ids = default_stop_token_ids(tokenizer)
     kw.setdefault("pad_id", int(getattr(tokenizer, "pad_id", 0) or 0))
-    if not kw.pop("small_batch", False):
+    flags = {flag: True for flag in ("small_batch", "split_kv") if kw.pop(flag, False)}
+    if not flags:
         return _run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, kw)
-    report = {"small_batch_groups": 0}          # counted by the loop, group by group, where the path is taken
+    report = {flag + "_groups": 0 for flag in flags}          # counted by the loop, group by group, where the path is taken
     summary = _run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding,
-                        dict(kw, small_batch=True, small_batch_report=report))
+                        dict(kw, small_batch_report=report, **flags))
     return dict(summary, **report)
 
 

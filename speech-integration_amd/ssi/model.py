@@ -427,6 +427,24 @@ class HipLlamaDecoder(nn.Module):
         path, launch for launch.)"""
         return bool(small_batch) and self._mfma_shapes() and self.head_dim == 64 and 1 <= rows <= min(self.skinny_max_rows, _lib.GEMM_SKINNY_MAX_ROWS)
 
+    # split-KV decode attention (``decode_step(..., split_kv=True)``): the span in keys a workgroup walks (None: the library's default for the
+    # model's head width and dtype, ``ssi_attn_decode_split_span``) and the largest LIVE row count that takes it; how the values were chosen:
+    # README, "Split-KV decode attention"
+    split_span: Optional[int] = None
+    split_max_rows = 16
+
+    def takes_split_kv(self, rows: int, split_kv: bool) -> bool:
+        """Does a decode step of ``rows`` live rows with this flag run the split-KV attention?  (Every dtype and head geometry the decode
+        attention serves; independent of ``small_batch``.)"""
+        return bool(split_kv) and 1 <= rows <= self.split_max_rows
+
+    def _split_kv(self, mode: str, rows: int, keys: int) -> dict:
+        """The keywords of a split attention launch of ``rows`` rows over caches of up to ``keys`` keys per row: the span, and the workspace from
+        the arena under a name of the step's buffer family."""
+        span = int(self.split_span or ops.attn_decode_split_span(self.head_dim, self.dtype))
+        n = ops.attn_decode_split_workspace(rows, self.num_heads, self.head_dim, keys, span)
+        return {"span": span, "workspace": self._arena.get("ws.splitkv." + mode, (n,), torch.float32)}
+
     # ---- forward: decoder stack --------------------------------------------------------------------------------------
     @staticmethod
     def _document_ranges(input_pos: Tensor, max_pos: Optional[int] = None) -> tuple[Tensor, Tensor, Tensor]:
@@ -786,7 +804,7 @@ class HipLlamaDecoder(nn.Module):
                 raise ValueError(f"the K/V cache is not this model's: {tuple(t.shape)} {t.dtype} on {t.device}, expected {want} {self.dtype} on {self.device}")
 
     @torch.no_grad()
-    def decode_step(self, cache: "KVCache", tokens: Tensor, slots: Tensor, small_batch: bool = False) -> Tensor:
+    def decode_step(self, cache: "KVCache", tokens: Tensor, slots: Tensor, small_batch: bool = False, split_kv: bool = False) -> Tensor:
         """One new token per live sequence: ``tokens`` (int64 ``[rows]``) and ``slots`` (int32 ``[rows]``; -1 = an inert row: no attention,
         no cache write, a zero attention row) on the device.  Row r runs at position ``cache.lengths[slots[r]]``: its K / V go there, it
         attends over the ``length + 1`` keys of its slot, and the length advances — all on the device, nothing is read back.  Returns the
@@ -796,7 +814,10 @@ class HipLlamaDecoder(nn.Module):
         would land in the next slot) and is counted in ``cache.errors``; ``prefill`` refuses what would get there.
         ``small_batch`` (with 1 to ``skinny_max_rows`` rows on the MFMA shapes with head_dim 64; otherwise without effect): the rows are NOT padded, the layer
         GEMMs and the head run on the weight-streaming skinny kernels and the activations live in the ``*.s`` buffers; norms, embedding,
-        ``kv_store`` and ``attn_decode`` are the same launches on fewer rows.  A row's logits do not depend on the rows beside it."""
+        ``kv_store`` and ``attn_decode`` are the same launches on fewer rows.  A row's logits do not depend on the rows beside it.
+        ``split_kv`` (with 1 to ``split_max_rows`` rows; otherwise without effect): ``attn_decode_split`` in place of ``attn_decode``, on the step's
+        rows, padded or not, with a span of ``split_span`` keys and a workspace ``ws.splitkv.g`` / ``.s`` from the arena.  A row's logits still
+        depend on that row alone, but differ in bits from the unsplit step's once its cache is longer than the span."""
         self._check_cache(cache)
         if tokens.dim() != 1 or tokens.dtype != torch.int64 or slots.shape != tokens.shape or slots.dtype != torch.int32:
             raise ValueError("decode_step: tokens is int64 [rows], slots int32 [rows]")
@@ -818,25 +839,31 @@ class HipLlamaDecoder(nn.Module):
         dest = torch.where(write, slot.long() * cache.cap + length.long(), torch.full_like(slot, -1, dtype=torch.int64))
         pos = length.clamp(max=self._rope.shape[0] - 1).contiguous()
         kv_len = torch.where(live, length + 1, torch.zeros_like(length)).contiguous()
+        mode = "s" if small else "g"
+        split = self._split_kv(mode, R, cache.cap) if self.takes_split_kv(n, split_kv) else None
 
         def attend(l: int, b: _LayerBufs) -> None:
             ops.kv_store(b.qkv, dest, cache.k[l], cache.v[l], H, KV, hd, n_bad=cache.errors)
-            ops.attn_decode(b.qkv, cache.k[l], cache.v[l], slot, kv_len, b.att, None, H, KV, hd, n_bad=cache.errors)
+            if split:
+                ops.attn_decode_split(b.qkv, cache.k[l], cache.v[l], slot, kv_len, b.att, None, H, KV, hd, n_bad=cache.errors, **split)
+            else:
+                ops.attn_decode(b.qkv, cache.k[l], cache.v[l], slot, kv_len, b.att, None, H, KV, hd, n_bad=cache.errors)
 
-        logits = self._head_logits(self._run_stack("s" if small else "g", tok, R, 1, R, pos, attend)[1].xn1, skinny=small)   # R rows of one position each; RoPE by ``pos``
+        logits = self._head_logits(self._run_stack(mode, tok, R, 1, R, pos, attend)[1].xn1, skinny=small)   # R rows of one position each; RoPE by ``pos``
         cache.lengths.index_add_(0, slot.clamp(min=0).long(), write.to(torch.int32))
         return logits[:n]
 
     @torch.no_grad()
     def decode_step_beam(self, prompt_cache: "KVCache", beam_cache: "KVCache", tokens: Tensor, prompt_slot: Tensor, prompt_len: Tensor,
-                         anc: Tensor, t: int, small_batch: bool = False) -> Tensor:
+                         anc: Tensor, t: int, small_batch: bool = False, split_kv: bool = False) -> Tensor:
         """Step ``t`` of beam search: row ``r`` (one hypothesis) runs ``tokens[r]`` at position ``prompt_len[r] + t``.  Its K / V go to the beam
         cache at ``(r, t)``, and it attends over the ``prompt_len[r]`` keys of slot ``prompt_slot[r]`` of the prompt cache (what ``prefill``
         filled; read only here) and the generated positions ``i <= t`` of the beam cache at slots ``anc[r, i]`` — ``anc`` (int32
         ``[rows, >= t + 1]``, contiguous) is the hypothesis' ancestry and the caller has set ``anc[r, t] = r``.  ``prompt_slot[r] = -1``: an inert
         row.  Everything on the device; rows padded to whole tiles and activations in the ``*.g`` buffers, as ``decode_step``.  Neither cache's
         ``lengths`` are read or changed; refused indices are counted in ``beam_cache.errors``.  Returns ``[rows, vocab_pad]`` logits (fresh).
-        ``small_batch``: as in ``decode_step`` (unpadded rows, skinny GEMMs, ``*.s`` buffers, where ``takes_small_batch`` holds)."""
+        ``small_batch``: as in ``decode_step`` (unpadded rows, skinny GEMMs, ``*.s`` buffers, where ``takes_small_batch`` holds).
+        ``split_kv``: as in ``decode_step`` (``attn_decode_beam_split`` in place of ``attn_decode_beam``, where ``takes_split_kv`` holds)."""
         self._check_cache(prompt_cache)
         self._check_cache(beam_cache)
         n, t = tokens.numel(), int(t)
@@ -861,13 +888,16 @@ class HipLlamaDecoder(nn.Module):
         dest = torch.where(live, torch.arange(R, dtype=torch.int64, device=dev) * beam_cache.cap + t, torch.full((R,), -1, dtype=torch.int64, device=dev))
         pos = torch.where(live, plen + t, torch.zeros_like(plen)).clamp(max=self._rope.shape[0] - 1).contiguous()
         gen_len = torch.where(live, torch.full_like(plen, t + 1), torch.zeros_like(plen))
+        mode = "s" if small else "g"
+        split = self._split_kv(mode, R, prompt_cache.cap + min(beam_cache.cap, anc.shape[1])) if self.takes_split_kv(n, split_kv) else None
 
         def attend(l: int, b: _LayerBufs) -> None:
             ops.kv_store(b.qkv, dest, beam_cache.k[l], beam_cache.v[l], H, KV, hd, n_bad=beam_cache.errors)
-            ops.attn_decode_beam(b.qkv, prompt_cache.k[l], prompt_cache.v[l], beam_cache.k[l], beam_cache.v[l], slot, plen, gen_len, anc_r, b.att,
-                                 None, H, KV, hd, n_bad=beam_cache.errors)
+            (ops.attn_decode_beam_split if split else ops.attn_decode_beam)(
+                b.qkv, prompt_cache.k[l], prompt_cache.v[l], beam_cache.k[l], beam_cache.v[l], slot, plen, gen_len, anc_r, b.att, None, H, KV, hd,
+                n_bad=beam_cache.errors, **(split or {}))
 
-        return self._head_logits(self._run_stack("s" if small else "g", tok, R, 1, R, pos, attend)[1].xn1, skinny=small)[:n]
+        return self._head_logits(self._run_stack(mode, tok, R, 1, R, pos, attend)[1].xn1, skinny=small)[:n]
 
     # ---- tied LM head ------------------------------------------------------------------------------------------------
     def _head_logits(self, hn: Tensor, arena_name: Optional[str] = None, skinny: bool = False) -> Tensor:

@@ -10,7 +10,7 @@ from torch import Tensor
 from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
-__all__ = ["gemm_skinny", "gemm_skinny_rope", "gemm_skinny_swiglu", "lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "attn_decode_beam", "decode_select", "decode_sample", "decode_select_pen", "decode_sample_pen", "decode_penalty_lds_bytes", "topk_logprob", "swiglu_fwd",
+__all__ = ["gemm_skinny", "gemm_skinny_rope", "gemm_skinny_swiglu", "lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "attn_decode_beam", "attn_decode_split", "attn_decode_beam_split", "attn_decode_split_span", "attn_decode_split_workspace", "decode_select", "decode_sample", "decode_select_pen", "decode_sample_pen", "decode_penalty_lds_bytes", "topk_logprob", "swiglu_fwd",
            "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "ema_update", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
@@ -202,28 +202,90 @@ def kv_store(qkv: Tensor, dest: Tensor, k_cache: Tensor, v_cache: Tensor, n_head
                                    n_heads, n_kv, head_dim, ptr(n_bad), dtype_code(qkv.dtype), stream_ptr()), "ssi_kv_store")
 
 
+def _decode_rows(what: str, qkv: Tensor, int32_rows, out: Tensor, lse: Tensor | None, n_heads: int, head_dim: int, n_bad: Tensor | None) -> int:
+    """The checks the decode-attention wrappers share, under the wrapper's name ``what``: the q rows, one int32 per row for every ``(name, tensor)``
+    of ``int32_rows``, ``out``, ``lse`` and ``n_bad``.  Returns the number of rows."""
+    ptr(qkv)
+    if qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] < n_heads * head_dim:
+        raise _lib.HipLibraryError(f"{what}: qkv must be [rows, >= {n_heads * head_dim}] with unit inner stride (got {tuple(qkv.shape)})")
+    rows = qkv.shape[0]
+    for name, t in int32_rows:
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != rows or t.device != qkv.device:
+            raise _lib.HipLibraryError(f"{what}: {name} is one int32 per row of qkv, on its device")
+    if out.dtype != qkv.dtype or not out.is_contiguous() or out.numel() != rows * n_heads * head_dim or out.device != qkv.device:
+        raise _lib.HipLibraryError(f"{what}: out must be a contiguous [rows, {n_heads * head_dim}] tensor of the dtype and device of qkv")
+    if lse is not None and (lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() < rows * n_heads or lse.device != qkv.device):
+        raise _lib.HipLibraryError(f"{what}: lse is fp32 [rows, n_heads] on the device of qkv")
+    if n_bad is not None and (n_bad.dtype != torch.int32 or n_bad.numel() != 1 or n_bad.device != qkv.device):
+        raise _lib.HipLibraryError(f"{what}: n_bad is one int32 on the device of qkv")
+    return rows
+
+
+def _slot_args(what: str, qkv: Tensor, k_cache: Tensor, v_cache: Tensor, slot: Tensor, kv_len: Tensor, out: Tensor, lse: Tensor | None,
+               n_heads: int, n_kv: int, head_dim: int, n_bad: Tensor | None) -> tuple:
+    """Checks and leading C arguments of ``attn_decode`` and its split form (up to ``n_bad``)."""
+    rows = _decode_rows(what, qkv, (("slot", slot), ("kv_len", kv_len)), out, lse, n_heads, head_dim, n_bad)
+    _kv_cache_ok(k_cache, v_cache, qkv, n_kv, head_dim)
+    return (ptr(qkv), qkv.stride(0), ptr(k_cache), ptr(v_cache), k_cache.shape[0], k_cache.shape[1], ptr(slot), ptr(kv_len), ptr(out), ptr(lse),
+            rows, n_heads, n_kv, head_dim, ptr(n_bad))
+
+
+def _beam_args(what: str, qkv: Tensor, pk_cache: Tensor, pv_cache: Tensor, bk_cache: Tensor, bv_cache: Tensor, prompt_slot: Tensor,
+               prompt_len: Tensor, gen_len: Tensor, anc: Tensor, out: Tensor, lse: Tensor | None, n_heads: int, n_kv: int, head_dim: int,
+               n_bad: Tensor | None) -> tuple:
+    """Checks and leading C arguments of ``attn_decode_beam`` and its split form (up to ``n_bad``)."""
+    rows = _decode_rows(what, qkv, (("prompt_slot", prompt_slot), ("prompt_len", prompt_len), ("gen_len", gen_len)), out, lse, n_heads, head_dim, n_bad)
+    _kv_cache_ok(pk_cache, pv_cache, qkv, n_kv, head_dim)
+    _kv_cache_ok(bk_cache, bv_cache, qkv, n_kv, head_dim)
+    if anc.dtype != torch.int32 or anc.dim() != 2 or anc.shape[0] != rows or not anc.is_contiguous() or anc.device != qkv.device:
+        raise _lib.HipLibraryError(f"{what}: anc is a contiguous int32 [rows, ld_anc] tensor on the device of qkv")
+    return (ptr(qkv), qkv.stride(0), ptr(pk_cache), ptr(pv_cache), pk_cache.shape[0], pk_cache.shape[1], ptr(bk_cache), ptr(bv_cache),
+            bk_cache.shape[0], bk_cache.shape[1], ptr(prompt_slot), ptr(prompt_len), ptr(gen_len), ptr(anc), anc.shape[1], ptr(out), ptr(lse),
+            rows, n_heads, n_kv, head_dim, ptr(n_bad))
+
+
+def _split_workspace(what: str, qkv: Tensor, workspace: Tensor, span: int) -> None:
+    """What a split wrapper refuses before anything else (and before the library is loaded): a workspace that is no contiguous fp32 tensor on the
+    device of ``qkv``, a span that is no positive integer."""
+    if not isinstance(workspace, Tensor) or workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.device != qkv.device:
+        raise _lib.HipLibraryError(f"{what}: workspace is a contiguous fp32 tensor on the device of qkv")
+    if int(span) != span or span < 1:
+        raise _lib.HipLibraryError(f"{what}: span is a positive number of keys (got {span})")
+
+
+def attn_decode_split_span(head_dim: int, dtype: torch.dtype) -> int:
+    """The library's default span in keys for this head width and storage type (``ssi_attn_decode_split_span``); 0: unsupported."""
+    return int(_lib.load().ssi_attn_decode_split_span(int(head_dim), dtype_code(dtype)))
+
+
+def attn_decode_split_workspace(rows: int, n_heads: int, head_dim: int, keys: int, span: int) -> int:
+    """fp32 ELEMENTS of the workspace of a split launch of ``rows`` rows whose caches hold up to ``keys`` keys per row."""
+    return int(_lib.load().ssi_attn_decode_split_workspace(int(rows), int(n_heads), int(head_dim), max(_cdiv(int(keys), int(span)), 1))) // 4
+
+
+def _cdiv(a: int, b: int) -> int:
+    return -(-a // b)
+
+
 def attn_decode(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, slot: Tensor, kv_len: Tensor, out: Tensor, lse: Tensor | None, n_heads: int,
                 n_kv: int, head_dim: int, n_bad: Tensor | None = None) -> None:
     """Single-query GQA attention of row ``r`` of ``qkv`` (its q heads) over the first ``kv_len[r]`` cached keys of slot ``slot[r]`` (int32
     each): ``out`` [rows, n_heads * head_dim], ``lse`` (fp32 [rows, n_heads], optional).  ``slot < 0`` or ``kv_len <= 0``: a zero row;
     ``slot >= n_slots``: a zero row, counted into ``n_bad`` (int32 [1]).  ``ssi_attn_decode``: fp32 throughout, one rounding on the store."""
-    ptr(qkv)
-    if qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] < n_heads * head_dim:
-        raise _lib.HipLibraryError(f"attn_decode: qkv must be [rows, >= {n_heads * head_dim}] with unit inner stride (got {tuple(qkv.shape)})")
-    rows = qkv.shape[0]
-    _kv_cache_ok(k_cache, v_cache, qkv, n_kv, head_dim)
-    for name, t in (("slot", slot), ("kv_len", kv_len)):
-        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != rows or t.device != qkv.device:
-            raise _lib.HipLibraryError(f"attn_decode: {name} is one int32 per row of qkv, on its device")
-    if out.dtype != qkv.dtype or not out.is_contiguous() or out.numel() != rows * n_heads * head_dim or out.device != qkv.device:
-        raise _lib.HipLibraryError(f"attn_decode: out must be a contiguous [rows, {n_heads * head_dim}] tensor of the dtype and device of qkv")
-    if lse is not None and (lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() < rows * n_heads or lse.device != qkv.device):
-        raise _lib.HipLibraryError("attn_decode: lse is fp32 [rows, n_heads] on the device of qkv")
-    if n_bad is not None and (n_bad.dtype != torch.int32 or n_bad.numel() != 1 or n_bad.device != qkv.device):
-        raise _lib.HipLibraryError("attn_decode: n_bad is one int32 on the device of qkv")
-    check(_lib.load().ssi_attn_decode(ptr(qkv), qkv.stride(0), ptr(k_cache), ptr(v_cache), k_cache.shape[0], k_cache.shape[1], ptr(slot),
-                                      ptr(kv_len), ptr(out), ptr(lse), rows, n_heads, n_kv, head_dim, ptr(n_bad), dtype_code(qkv.dtype),
-                                      stream_ptr()), "ssi_attn_decode")
+    args = _slot_args("attn_decode", qkv, k_cache, v_cache, slot, kv_len, out, lse, n_heads, n_kv, head_dim, n_bad)
+    check(_lib.load().ssi_attn_decode(*args, dtype_code(qkv.dtype), stream_ptr()), "ssi_attn_decode")
+
+
+def attn_decode_split(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, slot: Tensor, kv_len: Tensor, out: Tensor, lse: Tensor | None, n_heads: int,
+                      n_kv: int, head_dim: int, *, span: int, workspace: Tensor, n_bad: Tensor | None = None) -> None:
+    """``attn_decode`` with the keys of every (row, kv head) split into spans of ``span`` keys (a positive multiple of the form's round,
+    ``8 x`` the keys per load), one workgroup each, and a merge launch behind them (the header's definition).  ``n_splits = ceil(cap / span)``;
+    ``workspace``: fp32, at least ``attn_decode_split_workspace(rows, n_heads, head_dim, cap, span)`` elements, never zeroed.  A row with
+    ``kv_len <= span`` equals ``attn_decode`` by value; a row's result depends on its own inputs and ``span`` only.  ``ssi_attn_decode_split``."""
+    _split_workspace("attn_decode_split", qkv, workspace, span)
+    args = _slot_args("attn_decode_split", qkv, k_cache, v_cache, slot, kv_len, out, lse, n_heads, n_kv, head_dim, n_bad)
+    check(_lib.load().ssi_attn_decode_split(*args, int(span), max(_cdiv(k_cache.shape[1], int(span)), 1), ptr(workspace), workspace.numel() * 4,
+                                            dtype_code(qkv.dtype), stream_ptr()), "ssi_attn_decode_split")
 
 
 def _selection_rows(what: str, logits: Tensor, vocab: int, token: Tensor, logprob: Tensor | None, int32_rows, allow: Tensor | None,
@@ -363,27 +425,23 @@ def attn_decode_beam(qkv: Tensor, pk_cache: Tensor, pv_cache: Tensor, bk_cache: 
     generated position ``i`` from slot ``anc[r, i]`` (int32 ``[rows, ld_anc]``, unit inner stride).  ``prompt_slot < 0``: a zero row.  A
     ``prompt_slot`` or ``anc`` entry outside its cache is never dereferenced: its keys are skipped and the row is counted once into ``n_bad``.
     ``ssi_attn_decode_beam``: bit-equal to ``attn_decode`` on a cache that holds the row's keys contiguously."""
-    ptr(qkv)
-    if qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] < n_heads * head_dim:
-        raise _lib.HipLibraryError(f"attn_decode_beam: qkv must be [rows, >= {n_heads * head_dim}] with unit inner stride (got {tuple(qkv.shape)})")
-    rows = qkv.shape[0]
-    _kv_cache_ok(pk_cache, pv_cache, qkv, n_kv, head_dim)
-    _kv_cache_ok(bk_cache, bv_cache, qkv, n_kv, head_dim)
-    for name, t in (("prompt_slot", prompt_slot), ("prompt_len", prompt_len), ("gen_len", gen_len)):
-        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != rows or t.device != qkv.device:
-            raise _lib.HipLibraryError(f"attn_decode_beam: {name} is one int32 per row of qkv, on its device")
-    if anc.dtype != torch.int32 or anc.dim() != 2 or anc.shape[0] != rows or not anc.is_contiguous() or anc.device != qkv.device:
-        raise _lib.HipLibraryError("attn_decode_beam: anc is a contiguous int32 [rows, ld_anc] tensor on the device of qkv")
-    if out.dtype != qkv.dtype or not out.is_contiguous() or out.numel() != rows * n_heads * head_dim or out.device != qkv.device:
-        raise _lib.HipLibraryError(f"attn_decode_beam: out must be a contiguous [rows, {n_heads * head_dim}] tensor of the dtype and device of qkv")
-    if lse is not None and (lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() < rows * n_heads or lse.device != qkv.device):
-        raise _lib.HipLibraryError("attn_decode_beam: lse is fp32 [rows, n_heads] on the device of qkv")
-    if n_bad is not None and (n_bad.dtype != torch.int32 or n_bad.numel() != 1 or n_bad.device != qkv.device):
-        raise _lib.HipLibraryError("attn_decode_beam: n_bad is one int32 on the device of qkv")
-    check(_lib.load().ssi_attn_decode_beam(ptr(qkv), qkv.stride(0), ptr(pk_cache), ptr(pv_cache), pk_cache.shape[0], pk_cache.shape[1],
-                                           ptr(bk_cache), ptr(bv_cache), bk_cache.shape[0], bk_cache.shape[1], ptr(prompt_slot), ptr(prompt_len),
-                                           ptr(gen_len), ptr(anc), anc.shape[1], ptr(out), ptr(lse), rows, n_heads, n_kv, head_dim, ptr(n_bad),
-                                           dtype_code(qkv.dtype), stream_ptr()), "ssi_attn_decode_beam")
+    args = _beam_args("attn_decode_beam", qkv, pk_cache, pv_cache, bk_cache, bv_cache, prompt_slot, prompt_len, gen_len, anc, out, lse, n_heads, n_kv,
+                      head_dim, n_bad)
+    check(_lib.load().ssi_attn_decode_beam(*args, dtype_code(qkv.dtype), stream_ptr()), "ssi_attn_decode_beam")
+
+
+def attn_decode_beam_split(qkv: Tensor, pk_cache: Tensor, pv_cache: Tensor, bk_cache: Tensor, bv_cache: Tensor, prompt_slot: Tensor,
+                           prompt_len: Tensor, gen_len: Tensor, anc: Tensor, out: Tensor, lse: Tensor | None, n_heads: int, n_kv: int,
+                           head_dim: int, *, span: int, workspace: Tensor, n_bad: Tensor | None = None) -> None:
+    """``attn_decode_beam`` split as ``attn_decode_split`` splits ``attn_decode``, over the concatenated key index: ``n_splits =
+    ceil((cap_p + min(cap_b, ld_anc)) / span)``, the workspace sized for that many keys.  With equal ``span``, equal by value to
+    ``attn_decode_split`` on a cache that holds the row's keys contiguously.  ``ssi_attn_decode_beam_split``."""
+    _split_workspace("attn_decode_beam_split", qkv, workspace, span)
+    args = _beam_args("attn_decode_beam_split", qkv, pk_cache, pv_cache, bk_cache, bv_cache, prompt_slot, prompt_len, gen_len, anc, out, lse, n_heads,
+                      n_kv, head_dim, n_bad)
+    keys = pk_cache.shape[1] + min(bk_cache.shape[1], anc.shape[1])
+    check(_lib.load().ssi_attn_decode_beam_split(*args, int(span), max(_cdiv(keys, int(span)), 1), ptr(workspace), workspace.numel() * 4,
+                                                 dtype_code(qkv.dtype), stream_ptr()), "ssi_attn_decode_beam_split")
 
 
 def topk_logprob(logits: Tensor, vocab: int, k: int, idx: Tensor, lp: Tensor, lse: Tensor | None = None, *, mask: Tensor | None = None) -> None:

@@ -1,5 +1,5 @@
 """What greedy generation costs at the 1B shape (Llama-3.2-1B + 5000 DSUs, bf16, random weights): 256 prompts of about 1000 tokens, 256 new
-tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained|beam|sample|penalty|small_batch] [--json profiles/generate.json]
+tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained|beam|sample|penalty|small_batch|split_kv] [--json profiles/generate.json]
 
 run        prefill time, milliseconds per decode step (event time over all steps, host gaps included), generated tokens per second, and a
            self-check: the first generated token of every prompt against the argmax of a plain full forward of that prompt alone (with
@@ -37,14 +37,20 @@ small_batch (not part of ``all``; python tools/generate_bench.py --part small_ba
            ``ssi.prompting.probe`` call of one prompt end to end.  ``--part small_batch_steps``: a few small-batch steps and nothing else, to be
            run under a kernel trace.
 all        the three as child processes, each under its own ``timeout``, chained with ``&&``; then the results and the floor from traffic
-           alone (weights read once per step, the cache read once per step) are merged into --json."""
+           alone (weights read once per step, the cache read once per step) are merged into --json.
+split_kv   (not part of ``all``; python tools/generate_bench.py --part split_kv --json profiles/generate_split_kv.json) what splitting the keys of a
+           decode attention over workgroups buys at few rows, ONE process, the forms alternating: per launch ``ssi_attn_decode`` against walk + merge
+           at spans of 64 to 512 keys (rows 1 to 256, 256 / 1000 / 4000 keys, every layer's caches in turn; the beam pair at 8 rows), whole
+           ``decode_step``s with and without ``split_kv``, ``generate`` and ``sample`` end to end — and the two choices the numbers make by rule: the
+           default span and ``split_max_rows``.
+"""
 import argparse, csv, glob, json, os, statistics, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, 'speech-integration_amd')
 sys.path.insert(0, PKG)
 
 ap = argparse.ArgumentParser()
-ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained', 'beam', 'sample', 'penalty', 'small_batch', 'small_batch_steps'])
+ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained', 'beam', 'sample', 'penalty', 'small_batch', 'small_batch_steps', 'split_kv'])
 ap.add_argument('--rows', type=int, default=1, help='small_batch_steps: rows of the traced steps')
 ap.add_argument('--prompts', type=int, default=256)
 ap.add_argument('--penalty-generated', type=int, default=128, help='penalty: generated tokens in every row\'s history')
@@ -785,13 +791,13 @@ def part_penalty():
 SMALL_ROWS = (1, 8, 16, 32, 64)
 
 
-def _small_cache(model, rows):
-    """A cache of ``rows`` prompts of about --prompt-len tokens, prefilled, with room for the measured steps."""
+def _small_cache(model, rows, room=4096):
+    """A cache of ``rows`` prompts of about --prompt-len tokens, prefilled, with ``room`` positions for the measured steps."""
     import torch
     g = torch.Generator().manual_seed(1)
     lens = torch.randint(args.prompt_len - 100, args.prompt_len + 101, (rows,), generator=g).tolist()
     prompts = [torch.randint(0, model.vocab_size, (n,), generator=g) for n in lens]
-    cache = model.new_kv_cache(rows, max(lens) + 4096)
+    cache = model.new_kv_cache(rows, max(lens) + room)
     model.prefill(cache, prompts)
     return cache, lens
 
@@ -957,6 +963,175 @@ def part_small_batch():
     return res
 
 
+SPLIT_ROWS, SPLIT_KEYS, SPLIT_SPANS = (1, 8, 16, 32, 64, 256), (256, 1000, 4000), (64, 128, 256, 512)
+
+
+def part_split_kv():
+    import torch
+    from ssi import ops
+    from ssi.generate import generate, sample
+    model = build_model()
+    L, H, KV, hd = model.num_layers, model.num_heads, model.num_kv_heads, model.head_dim
+    dev, bf = dict(device='cuda'), torch.bfloat16
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(reps):
+            fn(i)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3        # us per call
+
+    def rounds_of(forms, reps):
+        for fn in forms.values():
+            timed(fn, 4)
+        got = {k: [] for k in forms}
+        for _ in range(args.rounds):
+            for k, fn in forms.items():
+                got[k].append(timed(fn, reps))
+        return {k: spread(v) for k, v in got.items()}
+
+    res = {'geometry': f'1B shape (32 / 8 / 64), bf16; {args.rounds} rounds alternating the forms in one process; per launch call i reads layer i % {L}\'s caches; '
+                       f'the split forms are walk + merge, two launches, timed together',
+           'hbm_TB_per_s_of_the_adamw_and_ema_passes': list(HBM_TB_S)}
+    with torch.inference_mode():
+        g = torch.Generator(device='cuda').manual_seed(11)
+        R, cap = max(SPLIT_ROWS), max(SPLIT_KEYS)
+        kc = torch.empty((L, R, cap, KV * hd), dtype=bf, **dev).normal_(generator=g)
+        vc = torch.empty((L, R, cap, KV * hd), dtype=bf, **dev).normal_(generator=g)
+        qkv = torch.randn(R, (H + 2 * KV) * hd, generator=g, **dev).to(bf)
+        out = torch.empty((R, H * hd), dtype=bf, **dev)
+        slot = torch.arange(R, dtype=torch.int32, **dev)
+        ws = torch.empty(ops.attn_decode_split_workspace(R, H, hd, cap, min(SPLIT_SPANS)), **dev)
+        per = {}
+        for rows in SPLIT_ROWS:
+            for keys in SPLIT_KEYS:
+                kv_len = torch.full((rows,), keys, dtype=torch.int32, **dev)
+                q, o, sl = qkv[:rows], out[:rows], slot[:rows]
+                forms = {'plain_us': lambda i: ops.attn_decode(q, kc[i % L], vc[i % L], sl, kv_len, o, None, H, KV, hd)}
+                for span in SPLIT_SPANS:
+                    forms[f'split_span{span}_us'] = (lambda span: lambda i: ops.attn_decode_split(q, kc[i % L], vc[i % L], sl, kv_len, o, None, H, KV, hd,
+                                                                                                   span=span, workspace=ws))(span)
+                e = rounds_of(forms, 32)
+                e['cache_MB_read'] = round(rows * keys * 2 * KV * hd * 2 / 1e6, 2)
+                e['plain_over_split'] = {f'span{span}': round(e['plain_us']['median'] / e[f'split_span{span}_us']['median'], 2) for span in SPLIT_SPANS}
+                e['best_split_TB_per_s'] = round(e['cache_MB_read'] / 1e6 / (min(e[f'split_span{span}_us']['median'] for span in SPLIT_SPANS) * 1e-6), 3)
+                per[f'rows_{rows}_keys_{keys}'] = e
+        res['per_launch'] = dict(per, note=f'the caches are [{R} slots, cap {cap}]: a launch of fewer rows and keys reads the first of them, so n_splits = ceil({cap} / span) '
+                                           'in every launch and the workgroups beyond a row\'s keys return at once')
+        # the default span: lowest median at 1 row and 1000 keys; of two spans inside each other's min..max spread, the larger
+        at = per['rows_1_keys_1000']
+        m = {span: at[f'split_span{span}_us'] for span in SPLIT_SPANS}
+        best = min(SPLIT_SPANS, key=lambda sp: m[sp]['median'])
+        inside = lambda a, b: m[b]['min'] <= m[a]['median'] <= m[b]['max'] and m[a]['min'] <= m[b]['median'] <= m[a]['max']   # noqa: E731
+        chosen = max([best] + [sp for sp in SPLIT_SPANS if sp > best and inside(sp, best)])
+        res['default_span'] = {'rule': 'the span with the lowest median at 1 row and 1000 keys; of two spans that lie inside each other\'s min..max spread the larger '
+                                       '(fewer partials, a smaller workspace)',
+                               'lowest_median': best, 'chosen': chosen, 'library_default': ops.attn_decode_split_span(hd, bf)}
+        # the beam pair at 8 rows: one prompt of --prompt-len keys, 8 hypotheses, 128 generated positions read through a random ancestry
+        W, t_mid = 8, 128
+        pk, pv = kc[:, :1, :args.prompt_len].contiguous(), vc[:, :1, :args.prompt_len].contiguous()
+        bk, bv = kc[:, :W, :t_mid + 1].contiguous(), vc[:, :W, :t_mid + 1].contiguous()
+        anc = torch.randint(0, W, (W, t_mid + 1), generator=g, **dev).to(torch.int32).contiguous()
+        pslot = torch.zeros(W, dtype=torch.int32, **dev)
+        plen, glen = torch.full((W,), args.prompt_len, dtype=torch.int32, **dev), torch.full((W,), t_mid, dtype=torch.int32, **dev)
+        forms = {'plain_us': lambda i: ops.attn_decode_beam(qkv[:W], pk[i % L], pv[i % L], bk[i % L], bv[i % L], pslot, plen, glen, anc, out[:W], None, H, KV, hd)}
+        for span in SPLIT_SPANS:
+            forms[f'split_span{span}_us'] = (lambda span: lambda i: ops.attn_decode_beam_split(qkv[:W], pk[i % L], pv[i % L], bk[i % L], bv[i % L], pslot, plen, glen,
+                                                                                                anc, out[:W], None, H, KV, hd, span=span, workspace=ws))(span)
+        e = rounds_of(forms, 32)
+        e['plain_over_split'] = {f'span{span}': round(e['plain_us']['median'] / e[f'split_span{span}_us']['median'], 2) for span in SPLIT_SPANS}
+        res['per_launch_beam_8_rows'] = dict(e, prompt_keys=args.prompt_len, generated_keys=t_mid)
+        del kc, vc, pk, pv, bk, bv, ws
+        torch.cuda.empty_cache()
+
+        # whole steps: the same cache state for both forms of a row count (the lengths are put back before every block of steps)
+        steps, st = 16, {}
+        for m_rows, small in [(r, True) for r in (1, 8, 16, 32, 64)] + [(1, False), (8, False)]:
+            cache, lens = _small_cache(model, m_rows, room=64)       # (a tight cap, as generate() opens it: n_splits follows the cap)
+            start = cache.lengths.clone()
+            tok = torch.randint(0, model.vocab_size, (m_rows,), **dev)
+            sl = torch.arange(m_rows, dtype=torch.int32, **dev)
+            model.split_max_rows = 256                       # the rule under measurement must not decide what is measured
+
+            def block(split):
+                cache.lengths.copy_(start)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    model.decode_step(cache, tok, sl, small_batch=small, split_kv=split)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / steps * 1e3      # ms per step, host clock: what a loop sees
+
+            block(True), block(False)
+            rounds = {'split_kv_ms': [], 'unsplit_ms': []}
+            for _ in range(args.rounds):
+                rounds['split_kv_ms'].append(block(True))
+                rounds['unsplit_ms'].append(block(False))
+            e = {k: spread(v, 3) for k, v in rounds.items()}
+            e['prompt_tokens_mean'] = round(sum(lens) / m_rows, 1)
+            e['unsplit_minus_split_kv_ms'] = round(e['unsplit_ms']['median'] - e['split_kv_ms']['median'], 3)
+            e['unsplit_spread_ms'] = round(e['unsplit_ms']['max'] - e['unsplit_ms']['min'], 3)
+            e['split_kv_wins_by_more_than_the_unsplit_spread'] = bool(e['unsplit_minus_split_kv_ms'] > e['unsplit_spread_ms'])
+            st[f'rows_{m_rows}' + ('' if small else '_padded_to_256')] = e
+            assert int(cache.errors) == 0
+            del cache
+        del model.split_max_rows
+        res['decode_step'] = dict(st, steps_per_block=steps, span=int(model.split_span or ops.attn_decode_split_span(hd, bf)),
+                                  clock='host, synchronised around a block of steps',
+                                  note='rows_N: small_batch steps of N unpadded rows; rows_N_padded_to_256: the tile path with N live rows')
+        winners = [r for r in (1, 8, 16, 32, 64) if st[f'rows_{r}']['split_kv_wins_by_more_than_the_unsplit_spread']]
+        res['split_max_rows'] = {'rule': 'the largest measured row count at which the split-KV step beats the unsplit step by more than the unsplit step\'s own '
+                                         'min..max spread; none: 0',
+                                 'unsplit_step': 'measured on THIS build, not on the parent commit: an inference from kernel_lint --against the parent build, '
+                                                 'which shows the plain decode kernels within a few instructions of the parent\'s, not the parent\'s own measurement',
+                                 'qualifying_rows': winners, 'chosen': max(winners) if winners else 0, 'model_attribute': model.split_max_rows}
+
+        # end to end (the model's own split_max_rows decides): generate() of 1 and 8 prompts of about --prompt-len tokens and of one long prompt, sample(n=8)
+        e2e = {}
+        long_len = model._rope.shape[0] - args.new - 40          # "about 4000": what the RoPE table of this model (4096) leaves room for
+        for name, n_p, plen_ in (('prompts_1', 1, args.prompt_len), ('prompts_8', 8, args.prompt_len), (f'prompts_1_of_{long_len}_tokens', 1, long_len)):
+            gen = torch.Generator().manual_seed(7)
+            prompts = [torch.randint(0, model.vocab_size, (plen_ - 50 + 10 * i,), generator=gen) for i in range(n_p)]
+            for small in (True, False):
+                def run(split, new=args.new):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    generate(model, prompts, max_new_tokens=new, stop_token_ids=[], pad_id=0, small_batch=small, split_kv=split)
+                    torch.cuda.synchronize()
+                    return (time.perf_counter() - t0) * 1e3
+                run(True, 2), run(False, 2)
+                rounds = {'split_kv_ms': [], 'unsplit_ms': []}
+                for _ in range(3):
+                    rounds['split_kv_ms'].append(run(True))
+                    rounds['unsplit_ms'].append(run(False))
+                e = {k: spread(v, 1) for k, v in rounds.items()}
+                e['unsplit_over_split_kv'] = round(e['unsplit_ms']['median'] / e['split_kv_ms']['median'], 3)
+                e2e[name + ('_small_batch' if small else '_padded')] = e
+        gen = torch.Generator().manual_seed(8)
+        prompt = [torch.randint(0, model.vocab_size, (args.prompt_len,), generator=gen)]
+
+        def run_sample(split, new=args.new):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            sample(model, prompt, n=8, temperature=0.8, seed=1, max_new_tokens=new, stop_token_ids=[], pad_id=0, small_batch=True, split_kv=split)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+        run_sample(True, 2), run_sample(False, 2)
+        rounds = {'split_kv_ms': [], 'unsplit_ms': []}
+        for _ in range(3):
+            rounds['split_kv_ms'].append(run_sample(True))
+            rounds['unsplit_ms'].append(run_sample(False))
+        e = {k: spread(v, 1) for k, v in rounds.items()}
+        e['unsplit_over_split_kv'] = round(e['unsplit_ms']['median'] / e['split_kv_ms']['median'], 3)
+        e2e['sample_n8_one_prompt_small_batch'] = e
+        res['end_to_end'] = dict(e2e, new_tokens=args.new, rounds=3, split_max_rows=model.split_max_rows,
+                                 note='host clock around the whole call, prefill included; with split_kv (as with small_batch) a group that takes the path prefills prompt by prompt')
+    print(json.dumps(res, indent=1))
+    return res
+
+
 def part_small_batch_steps():
     """--trace-steps small-batch decode steps of --rows rows, for a kernel trace in a run of its own."""
     import torch
@@ -998,6 +1173,8 @@ elif args.part == 'penalty':
     res = part_penalty()
 elif args.part == 'small_batch':
     res = part_small_batch()
+elif args.part == 'split_kv':
+    res = part_split_kv()
 elif args.part == 'small_batch_steps':
     part_small_batch_steps()
     res = None
