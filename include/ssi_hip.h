@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 25 /* 25: + ssi_attn_decode_split, ssi_attn_decode_beam_split, ssi_attn_decode_split_span, ssi_attn_decode_split_workspace (split-KV decode attention: the keys of a row over several workgroups, a merge launch behind them; opt-in)
+#define SSI_ABI_VERSION 26 /* 26: + ssi_kv_store_fp8, ssi_attn_decode_fp8, ssi_attn_decode_beam_fp8, ssi_attn_decode_split_fp8, ssi_attn_decode_beam_split_fp8 (a K/V cache of e4m3 codes with one power-of-two exponent per line, and decode attention over it; opt-in)
+                           * 25: + ssi_attn_decode_split, ssi_attn_decode_beam_split, ssi_attn_decode_split_span, ssi_attn_decode_split_workspace (split-KV decode attention: the keys of a row over several workgroups, a merge launch behind them; opt-in)
                            * 24: + ssi_gemm_skinny, ssi_gemm_skinny_rope, ssi_gemm_skinny_swiglu (weight-streaming bf16 GEMMs for 1 to 64 rows: small-batch decoding; opt-in)
                            * 23: + ssi_sumsq_groups, ssi_adamw_step_seg_gscale (per-group gradient norms of the flat buffer in one pass, a per-segment device gradient scale in the segmented AdamW; opt-in)
                            * 22: + ssi_decode_select_pen, ssi_decode_sample_pen (repetition, frequency and presence penalties inside the two selection kernels; opt-in)
@@ -294,6 +295,59 @@ int ssi_attn_decode_beam_split(const void* qkv, int64_t ld, const void* pk_cache
                                const int32_t* prompt_len, const int32_t* gen_len, const int32_t* anc, int64_t ld_anc, void* out, float* lse,
                                int64_t rows, int n_heads, int n_kv, int head_dim, int32_t* n_bad, int64_t span, int64_t n_splits,
                                void* workspace, int64_t workspace_bytes, int dtype, void* stream);
+
+/* ---- FP8 K/V cache (ABI v26; vLLM's kv_cache_dtype="fp8" is what the reference's users would reach for; opt-in, it changes values) -----------
+ * THE DEFINITION.  A cached LINE is the head_dim elements of one (position, kv head) of K (after RoPE, as it sits in qkv) or of V, in the
+ * model's dtype (a bf16 model's line is rounded twice, to bf16 and then to fp8: accepted).  It is stored as head_dim e4m3fn CODES (OCP: bias 7,
+ * no infinity, NaN = S.1111.111, largest finite 448; not fnuz) and one biased EXPONENT BYTE b:
+ *   exponent   a = the largest |x_i| over the line's FINITE elements.  a == 0 or no finite element: b = 127.  Otherwise a = m * 2^E with m in
+ *              [1, 2), e = E - 8 if m <= 1.75 else E - 7 (the smallest e with a * 2^-e <= 448), b = clamp(e, -127, 127) + 127.  e comes from
+ *              the bits of a (exponent field and mantissa), not from a logarithm; an fp32 subnormal a gives b = 0.
+ *   codes      code_i = RNE_e4m3(x_i * 2^-e), the scaling exact (v_ldexp_f32) and nothing above 448, so saturation is never relied on; a NaN
+ *              or infinite element stores the NaN code 0x7f (the store writes it itself, whatever the conversion would make of such an input).
+ *   value      float(code) * 2^(b - 127): exact in fp32 for every line, and exact in bf16 (four significant bits times a power of two) for every
+ *              line with a >= 2^-116 — below that, b - 127 < -124 can put the low bit of a code under bf16's smallest subnormal 2^-133.
+ * One power of two per (position, kv head), for K and V separately: neither a per-tensor scale nor an unscaled cast — K after RoPE has outlier
+ * channels and positions, and a per-line exponent keeps three mantissa bits on every line; a power of two keeps both directions exact.
+ * Storage per layer: k_codes, v_codes uint8 [n_slots, cap, n_kv * head_dim] (16-byte aligned); k_exp, v_exp uint8 [n_slots, cap, n_kv] (no
+ * alignment; 1.6 % on top of the codes at head_dim 64).
+ *
+ * ssi_kv_store_fp8 is ssi_kv_store's contract on these four arrays: dest = -1 skips the row, a dest outside [0, n_dest) is counted once into
+ * *n_bad and writes nothing.  A line lies on LPK lanes (head_dim / VEC rounded up to a power of two; VEC = 8 for bf16, 4 for fp32) of 16 bytes
+ * of qkv each; the absmax is an xor-shuffle maximum over them; every lane writes its VEC codes at once (8 bytes for bf16, 4 for fp32) and the
+ * line's first lane the exponent byte.  No LDS, no atomics on values.  Prefill attention itself runs on the unquantised K / V of the packed
+ * forward: only what decode steps read is quantised, the new token's own key included.
+ *
+ * ssi_attn_decode_fp8, ssi_attn_decode_beam_fp8, ssi_attn_decode_split_fp8 and ssi_attn_decode_beam_split_fp8 are the four entries above with
+ * (k_codes, v_codes, k_exp, v_exp) wherever those take (k_cache, v_cache); the beam forms read BOTH caches as fp8.  qkv, out, lse, the workspace,
+ * span, n_splits, slot, kv_len, anc and n_bad are unchanged, and so are the checks.  The walk is the plain kernels' (one source): a lane holds the
+ * VEC codes of its key where the plain form holds VEC elements (an 8-byte load for bf16, 4 for fp32, plus the line's exponent byte), so lanes,
+ * chunks, waves, the xor tree and every merge are the same, and the merge kernel of the split forms is the same kernel.  The value of a code is
+ * made ELEMENT BY ELEMENT before the dot product (v_cvt_pk_f32_fp8, v_ldexp_f32: both exact) rather than as one factor on the score and on p:
+ * the walk then computes on the very fp32 numbers a plain cache of the dequantised lines would hand it, overflow and subnormals included, for
+ * 2 * VEC exact instructions a key beside 2 * G * VEC fmas.  THE CONTRACT: out and lse of an _fp8 entry are BIT-EQUAL to the plain entry's on a
+ * cache that holds the dequantised values in the model's dtype (wherever those are exact in it: see "value"), and n_bad counts the same rows.
+ * Forms: 8 per attention entry (dtype x G = 1, 2, 4, 8), 2 of the store; no scratch.  A form with more loads in flight would change the bits. */
+int ssi_kv_store_fp8(const void* qkv, int64_t ld, const int64_t* dest, int64_t rows, int64_t n_dest, void* k_codes, void* v_codes,
+                     void* k_exp, void* v_exp, int n_heads, int n_kv, int head_dim, int32_t* n_bad, int dtype, void* stream);
+int ssi_attn_decode_fp8(const void* qkv, int64_t ld, const void* k_codes, const void* v_codes, const void* k_exp, const void* v_exp,
+                        int64_t n_slots, int64_t cap, const int32_t* slot, const int32_t* kv_len, void* out, float* lse, int64_t rows,
+                        int n_heads, int n_kv, int head_dim, int32_t* n_bad, int dtype, void* stream);
+int ssi_attn_decode_beam_fp8(const void* qkv, int64_t ld, const void* pk_codes, const void* pv_codes, const void* pk_exp, const void* pv_exp,
+                             int64_t n_pslots, int64_t cap_p, const void* bk_codes, const void* bv_codes, const void* bk_exp,
+                             const void* bv_exp, int64_t n_bslots, int64_t cap_b, const int32_t* prompt_slot, const int32_t* prompt_len,
+                             const int32_t* gen_len, const int32_t* anc, int64_t ld_anc, void* out, float* lse, int64_t rows, int n_heads,
+                             int n_kv, int head_dim, int32_t* n_bad, int dtype, void* stream);
+int ssi_attn_decode_split_fp8(const void* qkv, int64_t ld, const void* k_codes, const void* v_codes, const void* k_exp, const void* v_exp,
+                              int64_t n_slots, int64_t cap, const int32_t* slot, const int32_t* kv_len, void* out, float* lse, int64_t rows,
+                              int n_heads, int n_kv, int head_dim, int32_t* n_bad, int64_t span, int64_t n_splits, void* workspace,
+                              int64_t workspace_bytes, int dtype, void* stream);
+int ssi_attn_decode_beam_split_fp8(const void* qkv, int64_t ld, const void* pk_codes, const void* pv_codes, const void* pk_exp,
+                                   const void* pv_exp, int64_t n_pslots, int64_t cap_p, const void* bk_codes, const void* bv_codes,
+                                   const void* bk_exp, const void* bv_exp, int64_t n_bslots, int64_t cap_b, const int32_t* prompt_slot,
+                                   const int32_t* prompt_len, const int32_t* gen_len, const int32_t* anc, int64_t ld_anc, void* out, float* lse,
+                                   int64_t rows, int n_heads, int n_kv, int head_dim, int32_t* n_bad, int64_t span, int64_t n_splits,
+                                   void* workspace, int64_t workspace_bytes, int dtype, void* stream);
 
 /* The k best allowed continuations of every row of logits [rows, ld] with their log-probabilities (ABI v20, beam search).  Logits read only.
  * mask: ssi_decode_select's bit mask (mask_words = ceil(vocab / 32) int32 words, bit c % 32 of word c / 32), or NULL with mask_words 0 = every

@@ -4,10 +4,14 @@
 // workgroups and merge the partial softmax states in a second launch.  All of them share one walk (dec_walk, dec_merged) and one finish (dec_finish).
 //
 // The cache of one layer: k_cache and v_cache, each [n_slots, cap, n_kv * head_dim] in the model's dtype, K after RoPE (as it sits in qkv).
+// The *_fp8 entries (ABI v26) keep it as e4m3 codes with one power-of-two exponent byte per (position, kv head) instead (the header's "FP8 K/V
+// cache"): ssi_kv_store_fp8 quantises, and the four attention entries run the same walk with a storage policy that hands it dequantised values.
 #include "common_hip.h"
 #include <math.h>
 
 namespace {
+
+typedef uint32_t q8_u32x2 __attribute__((ext_vector_type(2)));   // the 8 codes of a bf16 lane
 
 // =====================================================================================================================
 // ssi_kv_store: one 16-byte vector per lane.  A row of qkv holds its k heads and, right behind them, its v heads: vector c of the
@@ -32,6 +36,82 @@ __global__ __launch_bounds__(256) void kv_store_kernel(const T* __restrict__ qkv
     const Vec16<T> x = load16<T>(qkv + r * ld + q_cols + (int64_t)c * VEC);
     T* dst = (c < half ? kc : vc) + d * kv_cols + (int64_t)(c < half ? c : c - half) * VEC;
     store16<T>(dst, x);
+}
+
+// =====================================================================================================================
+// ssi_kv_store_fp8 (ABI v26): the same scatter, every line quantised on its way (the header's "FP8 K/V cache").  A line (one kv head of k or
+// of v of one row) lies on LPK = 2^lpk_log2 >= head_dim / VEC lanes of one wave, 16 bytes of qkv each (lanes whose columns lie past head_dim
+// idle, as in the decode kernels); its absmax is an xor-shuffle maximum of the lanes' |x| bit patterns (finite magnitudes order as unsigned
+// integers), every lane then scales (v_ldexp_f32: exact), converts (v_cvt_pk_fp8_f32: RNE) and writes its VEC codes at once, and the line's first
+// lane writes the exponent byte.  What leaves the kernel early does so for whole lines, so every shuffle meets live lanes only.
+// =====================================================================================================================
+template <typename T>
+__global__ __launch_bounds__(256) void q8_store_kernel(const T* __restrict__ qkv, int64_t ld, const int64_t* __restrict__ dest, int64_t rows,
+                                                       int64_t n_dest, uint8_t* __restrict__ kc, uint8_t* __restrict__ vc, uint8_t* __restrict__ ke,
+                                                       uint8_t* __restrict__ ve, int q_cols, int n_kv, int hd, int lpk_log2,
+                                                       int32_t* __restrict__ n_bad) {
+    constexpr int VEC = Vec16<T>::N, WORDS = VEC / 4;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t line = i >> lpk_log2;                   // of rows * 2 * n_kv lines: a row's k heads, then its v heads
+    const int sub = (int)(i & ((1 << lpk_log2) - 1)), col = sub * VEC;
+    const int64_t r = line / (2 * n_kv);
+    if (r >= rows) return;
+    const int c = (int)(line - r * (2 * n_kv));
+    const int64_t d = dest[r];
+    if (d == -1) return;
+    if (d < 0 || d >= n_dest) {
+        if (c == 0 && sub == 0 && n_bad) atomicAdd(n_bad, 1);
+        return;
+    }
+    const bool active = col < hd;
+    Vec16<T> x = {};
+    if (active) x = load16<T>(qkv + r * ld + q_cols + (int64_t)c * hd + col);
+    float f[VEC];
+    uint32_t a = 0;                                       // the bits of the largest finite |x|
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+        f[v] = x.get(v);
+        const uint32_t m = __float_as_uint(f[v]) & 0x7fffffffu;
+        a = m < 0x7f800000u && m > a ? m : a;
+    }
+    for (int o = 1 << lpk_log2 >> 1; o > 0; o >>= 1) {
+        const uint32_t other = (uint32_t)__shfl_xor((int)a, o, 64);
+        a = other > a ? other : a;
+    }
+    // a = m * 2^E, m in [1, 2): e = E - 8, or E - 7 where m > 1.75, and b = max(e, -127) + 127 from a's exponent field E + 127 (a subnormal a,
+    // field 0, has E - 7 < -127: b = 0 as the formula gives it; e <= 120 never meets the upper clamp)
+    int b = (int)(a >> 23) - 8 + ((a & 0x7fffffu) > 0x600000u ? 1 : 0);
+    b = a == 0 ? 127 : b < 0 ? 0 : b;
+    if (!active) return;
+    uint32_t w[WORDS];
+#pragma unroll
+    for (int k = 0; k < WORDS; ++k) {
+        float s[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) s[v] = ldexpf(f[4 * k + v], 127 - b);
+        int p = 0;
+        p = __builtin_amdgcn_cvt_pk_fp8_f32(s[0], s[1], p, false);
+        p = __builtin_amdgcn_cvt_pk_fp8_f32(s[2], s[3], p, true);
+        uint32_t u = (uint32_t)p;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {                     // a NaN or an infinity: the NaN code 0x7f, whatever the conversion makes of it
+            const bool finite = (__float_as_uint(f[4 * k + v]) & 0x7fffffffu) < 0x7f800000u;
+            u = finite ? u : (u & ~(0xffu << (8 * v))) | (0x7fu << (8 * v));
+        }
+        w[k] = u;
+    }
+    const bool is_k = c < n_kv;
+    const int64_t at = d * n_kv + (is_k ? c : c - n_kv);
+    uint8_t* dst = (is_k ? kc : vc) + at * hd + col;
+    if constexpr (WORDS == 2) {
+        q8_u32x2 o2;
+        o2[0] = w[0];
+        o2[1] = w[1];
+        *reinterpret_cast<q8_u32x2*>(dst) = o2;
+    } else {
+        *reinterpret_cast<uint32_t*>(dst) = w[0];
+    }
+    if (sub == 0) (is_k ? ke : ve)[at] = (uint8_t)b;
 }
 
 // =====================================================================================================================
@@ -75,8 +155,9 @@ struct DecLds {
 // THE WALK of one (row, kv head) of single-query attention over the keys k0 .. n - 1, the body every decode kernel shares: the key walk, the
 // per-key update and the xor tree over a wave's key slots, up to the four waves' states in ``lds`` (behind a barrier); ``dec_merged`` then merges
 // them.  Waves and chunks are placed relative to k0.  ``keys.exists(j)`` says whether key j is there — one that is not is skipped and leaves the
-// state as it was — and ``keys.lines(j, kp, vp)`` names the lane's 16 bytes of its K and V lines.  Without CAN_SKIP the caller promises
-// n > k0 keys that all exist.  ``qrow``: the row's first query head of this kv head.
+// state as it was — and ``keys.load(j, kx, vx)`` loads the lane's VEC elements of its K and V lines as they are stored (``Keys::Raw``);
+// ``Keys::unpack`` turns them into the fp32 values the walk computes with.  Without CAN_SKIP the caller promises n > k0 keys that all exist.
+// ``qrow``: the row's first query head of this kv head.
 template <typename T, int G, bool CAN_SKIP, typename Keys>
 __device__ __forceinline__ void dec_walk(const T* __restrict__ qrow, int k0, int n, int hd, int g, const DecLane& at, float qscale, const Keys& keys,
                                          const DecLds<G>& lds) {
@@ -102,28 +183,25 @@ __device__ __forceinline__ void dec_walk(const T* __restrict__ qrow, int k0, int
 
     const int chunk = kpw * DEC_U;
     for (int base = k0 + wave * chunk; base < n; base += DEC_WAVES * chunk) {
-        Vec16<T> kx[DEC_U] = {}, vx[DEC_U] = {};
+        typename Keys::Raw kx[DEC_U] = {}, vx[DEC_U] = {};
         bool have[DEC_U];
 #pragma unroll
         for (int u = 0; u < DEC_U; ++u) {                 // every load of the chunk is issued before the first use
             const int j = base + u * kpw + kslot;
             have[u] = j < n;
             if (CAN_SKIP) have[u] = have[u] && keys.exists(j);
-            if (have[u] && active) {
-                const T *kp, *vp;
-                keys.lines(j, kp, vp);
-                kx[u] = load16_nt<T>(kp);
-                vx[u] = load16_nt<T>(vp);
-            }
+            if (have[u] && active) keys.load(j, kx[u], vx[u]);
         }
 #pragma unroll
         for (int u = 0; u < DEC_U; ++u) {
             const bool ld_ok = have[u] && active;
             float kf[VEC], vf[VEC];
+            Keys::unpack(kx[u], kf);
+            Keys::unpack(vx[u], vf);
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
-                kf[v] = ld_ok ? kx[u].get(v) : 0.f;
-                vf[v] = ld_ok ? vx[u].get(v) : 0.f;
+                kf[v] = ld_ok ? kf[v] : 0.f;
+                vf[v] = ld_ok ? vf[v] : 0.f;
             }
             float s[G];
 #pragma unroll
@@ -243,24 +321,105 @@ __device__ __forceinline__ void dec_part(const T* __restrict__ qrow, int k0, int
     }
 }
 
-// the keys of one cache slot, one behind the other
+// =====================================================================================================================
+// HOW A CACHE IS STORED.  A kernel is handed a cache (PlainCache, Q8Cache); ``lines`` gives one lane its view of one kv head from cached
+// position ``first`` on (position p of slot s is cached position s * cap + p): ``load(p, kx, vx)`` loads the lane's VEC elements of the K and
+// V lines of cached position p as they are stored, ``unpack`` makes them the fp32 values of the walk.
+// =====================================================================================================================
 template <typename T>
-struct SlotKeys {
-    const T *kbase, *vbase;                               // key 0, the lane's columns
-    int64_t kv_cols;
-    __device__ __forceinline__ bool exists(int) const { return true; }
-    __device__ __forceinline__ void lines(int j, const T*& kp, const T*& vp) const {
-        kp = kbase + (int64_t)j * kv_cols;
-        vp = vbase + (int64_t)j * kv_cols;
+struct PlainLines {
+    using Raw = Vec16<T>;
+    const T *k, *v;                                       // the cache
+    int64_t at, kv_cols;                                  // cached position 0 of the view, the kv head, the lane's columns; elements per position
+    __device__ __forceinline__ void load(int64_t p, Raw& kx, Raw& vx) const {
+        const int64_t off = p * kv_cols + at;
+        kx = load16_nt<T>(k + off);
+        vx = load16_nt<T>(v + off);
+    }
+    static __device__ __forceinline__ void unpack(const Raw& x, float (&f)[Vec16<T>::N]) {
+#pragma unroll
+        for (int i = 0; i < Vec16<T>::N; ++i) f[i] = x.get(i);
+    }
+};
+template <typename T>
+struct PlainCache {
+    using Lines = PlainLines<T>;
+    const T *k, *v;
+    __device__ __forceinline__ Lines lines(int64_t first, int n_kv, int kvh, int hd, int col) const {
+        return {k, v, (first * n_kv + kvh) * hd + col, (int64_t)n_kv * hd};
     }
 };
 
-template <typename T, int G>
-__global__ __launch_bounds__(256) void kv_decode_kernel(const T* __restrict__ qkv, int64_t ld, const T* __restrict__ kc, const T* __restrict__ vc,
-                                                        int64_t n_slots, int cap, const int32_t* __restrict__ slot,
-                                                        const int32_t* __restrict__ kv_len, T* __restrict__ out, float* __restrict__ lse,
-                                                        int n_heads, int n_kv, int hd, int g, int lpk_log2, float qscale,
-                                                        int32_t* __restrict__ n_bad) {
+// The fp8 cache (ABI v26): a lane's VEC codes are VEC / 4 words, loaded at once (8 bytes for bf16, 4 for fp32: the plain form's lane layout),
+// and the line's exponent byte b.  The value of a code is float(code) * 2^(b - 127), made ELEMENT BY ELEMENT here (v_cvt_pk_f32_fp8, then
+// v_ldexp_f32: both exact), so the walk sees the very fp32 values it sees on a plain cache that holds the dequantised lines, whatever their
+// magnitude — a scale applied to the score and to p instead would round differently where a product overflows or goes subnormal, and would
+// save only 2 * VEC v_ldexp_f32 a key beside the 2 * G * VEC v_fma_f32 the walk spends on it.
+template <typename T>
+struct Q8Lines {
+    static constexpr int VEC = Vec16<T>::N, WORDS = VEC / 4;
+    struct Raw {
+        uint32_t c[WORDS];
+        uint32_t b;
+    };
+    const uint8_t *k, *v;                                 // codes: cached position 0 of the view, the kv head, the lane's columns
+    const uint8_t *ke, *ve;                               // exponent bytes: cached position 0 of the view, the kv head
+    int64_t kv_cols;
+    int n_kv;
+    static __device__ __forceinline__ void codes(const uint8_t* p, uint32_t (&c)[WORDS]) {
+        if constexpr (WORDS == 2) {
+            const q8_u32x2 x = __builtin_nontemporal_load(reinterpret_cast<const q8_u32x2*>(p));
+            c[0] = x[0];
+            c[1] = x[1];
+        } else {
+            c[0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p));
+        }
+    }
+    __device__ __forceinline__ void load(int64_t p, Raw& kx, Raw& vx) const {
+        codes(k + p * kv_cols, kx.c);
+        codes(v + p * kv_cols, vx.c);
+        kx.b = ke[p * n_kv];
+        vx.b = ve[p * n_kv];
+    }
+    static __device__ __forceinline__ void unpack(const Raw& x, float (&f)[VEC]) {
+        const int e = (int)x.b - 127;
+#pragma unroll
+        for (int w = 0; w < WORDS; ++w) {
+            const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)x.c[w], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)x.c[w], true);
+            f[4 * w + 0] = ldexpf(lo[0], e);
+            f[4 * w + 1] = ldexpf(lo[1], e);
+            f[4 * w + 2] = ldexpf(hi[0], e);
+            f[4 * w + 3] = ldexpf(hi[1], e);
+        }
+    }
+};
+template <typename T>
+struct Q8Cache {
+    using Lines = Q8Lines<T>;
+    const uint8_t *k, *v, *ke, *ve;
+    __device__ __forceinline__ Lines lines(int64_t first, int n_kv, int kvh, int hd, int col) const {
+        const int64_t line = first * n_kv + kvh;
+        return {k + line * hd + col, v + line * hd + col, ke + line, ve + line, (int64_t)n_kv * hd, n_kv};
+    }
+};
+
+// the keys of one cache slot, one behind the other (``at``: the slot's position 0)
+template <typename L>
+struct SlotKeys {
+    using Raw = typename L::Raw;
+    L at;
+    __device__ __forceinline__ bool exists(int) const { return true; }
+    __device__ __forceinline__ void load(int j, Raw& kx, Raw& vx) const { at.load(j, kx, vx); }
+    template <int N>
+    static __device__ __forceinline__ void unpack(const Raw& x, float (&f)[N]) { L::unpack(x, f); }
+};
+
+// one (row, kv head) of ssi_attn_decode on a cache stored as ``C``
+template <typename T, int G, typename C>
+__device__ __forceinline__ void slot_decode(const T* __restrict__ qkv, int64_t ld, const C& cache, int64_t n_slots, int cap,
+                                            const int32_t* __restrict__ slot, const int32_t* __restrict__ kv_len, T* __restrict__ out,
+                                            float* __restrict__ lse, int n_heads, int n_kv, int hd, int g, int lpk_log2, float qscale,
+                                            int32_t* __restrict__ n_bad) {
     const int64_t r = blockIdx.x;
     const int kvh = blockIdx.y, tid = threadIdx.x;
     const int h0 = kvh * g;
@@ -275,10 +434,25 @@ __global__ __launch_bounds__(256) void kv_decode_kernel(const T* __restrict__ qk
         return;
     }
     const DecLane at = dec_lane<T>(lpk_log2, hd);
-    const int64_t kv_cols = (int64_t)n_kv * hd;
-    const T* kbase = kc + ((int64_t)sl * cap * n_kv + kvh) * hd + at.col;
-    const T* vbase = vc + ((int64_t)sl * cap * n_kv + kvh) * hd + at.col;
-    dec_row<T, G, false>(qkv + r * ld + (int64_t)h0 * hd, n, orow, lse, r * n_heads + h0, hd, g, at, qscale, SlotKeys<T>{kbase, vbase, kv_cols});
+    const SlotKeys<typename C::Lines> keys{cache.lines((int64_t)sl * cap, n_kv, kvh, hd, at.col)};
+    dec_row<T, G, false>(qkv + r * ld + (int64_t)h0 * hd, n, orow, lse, r * n_heads + h0, hd, g, at, qscale, keys);
+}
+
+template <typename T, int G>
+__global__ __launch_bounds__(256) void kv_decode_kernel(const T* __restrict__ qkv, int64_t ld, const T* __restrict__ kc, const T* __restrict__ vc,
+                                                        int64_t n_slots, int cap, const int32_t* __restrict__ slot,
+                                                        const int32_t* __restrict__ kv_len, T* __restrict__ out, float* __restrict__ lse,
+                                                        int n_heads, int n_kv, int hd, int g, int lpk_log2, float qscale,
+                                                        int32_t* __restrict__ n_bad) {
+    slot_decode<T, G>(qkv, ld, PlainCache<T>{kc, vc}, n_slots, cap, slot, kv_len, out, lse, n_heads, n_kv, hd, g, lpk_log2, qscale, n_bad);
+}
+
+template <typename T, int G>
+__global__ __launch_bounds__(256) void q8_decode_kernel(const T* __restrict__ qkv, int64_t ld, Q8Cache<T> cache, int64_t n_slots, int cap,
+                                                        const int32_t* __restrict__ slot, const int32_t* __restrict__ kv_len,
+                                                        T* __restrict__ out, float* __restrict__ lse, int n_heads, int n_kv, int hd, int g,
+                                                        int lpk_log2, float qscale, int32_t* __restrict__ n_bad) {
+    slot_decode<T, G>(qkv, ld, cache, n_slots, cap, slot, kv_len, out, lse, n_heads, n_kv, hd, g, lpk_log2, qscale, n_bad);
 }
 
 // =====================================================================================================================
@@ -289,12 +463,12 @@ __global__ __launch_bounds__(256) void kv_decode_kernel(const T* __restrict__ qk
 // skipped, and the row is counted once.
 // =====================================================================================================================
 // prompt keys 0 .. np - 1 of one prompt cache slot, then generated keys: position i of the beam cache slot the ancestry names
-template <typename T>
+template <typename L>
 struct BeamKeys {
-    const T *pk, *pv;                                     // prompt key 0, the lane's columns (never used when !p_ok)
-    const T *bk, *bv;                                     // the beam cache
+    using Raw = typename L::Raw;
+    L prompt;                                             // the prompt slot's position 0 (never used when !p_ok)
+    L beam;                                               // the beam cache's position 0
     const int32_t* arow;                                  // the row's ancestry
-    int64_t kv_cols, head_at;                             // elements per cached position; the lane's columns within one
     int np, cap_b, n_bslots;
     bool p_ok;
     __device__ __forceinline__ bool exists(int j) const {
@@ -302,27 +476,25 @@ struct BeamKeys {
         const int a = arow[j - np];
         return a >= 0 && a < n_bslots;                    // checked before any address is formed from it
     }
-    __device__ __forceinline__ void lines(int j, const T*& kp, const T*& vp) const {   // (only for a key that exists)
+    __device__ __forceinline__ void load(int j, Raw& kx, Raw& vx) const {   // (only for a key that exists)
         if (j < np) {
-            kp = pk + (int64_t)j * kv_cols;
-            vp = pv + (int64_t)j * kv_cols;
+            prompt.load(j, kx, vx);
         } else {
             const int i = j - np;
-            const int64_t off = ((int64_t)arow[i] * cap_b + i) * kv_cols + head_at;
-            kp = bk + off;
-            vp = bv + off;
+            beam.load((int64_t)arow[i] * cap_b + i, kx, vx);
         }
     }
+    template <int N>
+    static __device__ __forceinline__ void unpack(const Raw& x, float (&f)[N]) { L::unpack(x, f); }
 };
 
-template <typename T, int G>
-__global__ __launch_bounds__(256) void beam_decode_kernel(const T* __restrict__ qkv, int64_t ld, const T* __restrict__ pk, const T* __restrict__ pv,
-                                                          int64_t n_pslots, int cap_p, const T* __restrict__ bk, const T* __restrict__ bv,
-                                                          int64_t n_bslots, int cap_b, const int32_t* __restrict__ prompt_slot,
-                                                          const int32_t* __restrict__ prompt_len, const int32_t* __restrict__ gen_len,
-                                                          const int32_t* __restrict__ anc, int64_t ld_anc, T* __restrict__ out,
-                                                          float* __restrict__ lse, int n_heads, int n_kv, int hd, int g, int lpk_log2, float qscale,
-                                                          int32_t* __restrict__ n_bad) {
+// one (row, kv head) of ssi_attn_decode_beam on a prompt cache and a beam cache stored as ``C``
+template <typename T, int G, typename C>
+__device__ __forceinline__ void beam_decode(const T* __restrict__ qkv, int64_t ld, const C& pcache, int64_t n_pslots, int cap_p, const C& bcache,
+                                            int64_t n_bslots, int cap_b, const int32_t* __restrict__ prompt_slot,
+                                            const int32_t* __restrict__ prompt_len, const int32_t* __restrict__ gen_len,
+                                            const int32_t* __restrict__ anc, int64_t ld_anc, T* __restrict__ out, float* __restrict__ lse,
+                                            int n_heads, int n_kv, int hd, int g, int lpk_log2, float qscale, int32_t* __restrict__ n_bad) {
     const int64_t r = blockIdx.x;
     const int kvh = blockIdx.y, tid = threadIdx.x;
     const int h0 = kvh * g;
@@ -340,10 +512,9 @@ __global__ __launch_bounds__(256) void beam_decode_kernel(const T* __restrict__ 
         return;
     }
     const bool p_ok = sl < n_pslots;
-    const int64_t kv_cols = (int64_t)n_kv * hd;
     const DecLane at = dec_lane<T>(lpk_log2, hd);
-    const int64_t pbase = ((int64_t)(p_ok ? sl : 0) * cap_p * n_kv + kvh) * hd + at.col;
-    const BeamKeys<T> keys{pk + pbase, pv + pbase, bk, bv, anc + r * ld_anc, kv_cols, (int64_t)kvh * hd + at.col, np, cap_b, (int)n_bslots, p_ok};
+    const BeamKeys<typename C::Lines> keys{pcache.lines((int64_t)(p_ok ? sl : 0) * cap_p, n_kv, kvh, hd, at.col),
+                                           bcache.lines(0, n_kv, kvh, hd, at.col), anc + r * ld_anc, np, cap_b, (int)n_bslots, p_ok};
     dec_row<T, G, true>(qkv + r * ld + (int64_t)h0 * hd, np + ng, orow, lse, r * n_heads + h0, hd, g, at, qscale, keys);
     if (kvh == 0 && n_bad) {                              // once per row (every kv head meets the same indices): the ancestry alone once more
         bool bad = !p_ok && np > 0;
@@ -353,6 +524,29 @@ __global__ __launch_bounds__(256) void beam_decode_kernel(const T* __restrict__ 
     }
 }
 
+template <typename T, int G>
+__global__ __launch_bounds__(256) void beam_decode_kernel(const T* __restrict__ qkv, int64_t ld, const T* __restrict__ pk, const T* __restrict__ pv,
+                                                          int64_t n_pslots, int cap_p, const T* __restrict__ bk, const T* __restrict__ bv,
+                                                          int64_t n_bslots, int cap_b, const int32_t* __restrict__ prompt_slot,
+                                                          const int32_t* __restrict__ prompt_len, const int32_t* __restrict__ gen_len,
+                                                          const int32_t* __restrict__ anc, int64_t ld_anc, T* __restrict__ out,
+                                                          float* __restrict__ lse, int n_heads, int n_kv, int hd, int g, int lpk_log2, float qscale,
+                                                          int32_t* __restrict__ n_bad) {
+    beam_decode<T, G>(qkv, ld, PlainCache<T>{pk, pv}, n_pslots, cap_p, PlainCache<T>{bk, bv}, n_bslots, cap_b, prompt_slot, prompt_len, gen_len, anc,
+                      ld_anc, out, lse, n_heads, n_kv, hd, g, lpk_log2, qscale, n_bad);
+}
+
+template <typename T, int G>
+__global__ __launch_bounds__(256) void q8_beam_kernel(const T* __restrict__ qkv, int64_t ld, Q8Cache<T> pcache, int64_t n_pslots, int cap_p,
+                                                      Q8Cache<T> bcache, int64_t n_bslots, int cap_b, const int32_t* __restrict__ prompt_slot,
+                                                      const int32_t* __restrict__ prompt_len, const int32_t* __restrict__ gen_len,
+                                                      const int32_t* __restrict__ anc, int64_t ld_anc, T* __restrict__ out, float* __restrict__ lse,
+                                                      int n_heads, int n_kv, int hd, int g, int lpk_log2, float qscale,
+                                                      int32_t* __restrict__ n_bad) {
+    beam_decode<T, G>(qkv, ld, pcache, n_pslots, cap_p, bcache, n_bslots, cap_b, prompt_slot, prompt_len, gen_len, anc, ld_anc, out, lse, n_heads,
+                      n_kv, hd, g, lpk_log2, qscale, n_bad);
+}
+
 // =====================================================================================================================
 // ssi_attn_decode_split / ssi_attn_decode_beam_split (ABI v25): the keys of a (row, kv head) over several workgroups.  Workgroup z of a row
 // with n keys walks the keys [z * span, min((z + 1) * span, n)) as the plain kernel walks a cache that starts there, and writes its merged,
@@ -360,11 +554,10 @@ __global__ __launch_bounds__(256) void beam_decode_kernel(const T* __restrict__ 
 // merge's formula over the row's ceil(n / span) partials in the order z = 0, 1, ... and finishes.  No atomics but the error count, no flag,
 // no ticket: the kernel boundary is the only synchronisation.
 // =====================================================================================================================
-template <typename T, int G>
-__global__ __launch_bounds__(256) void split_kv_walk_kernel(const T* __restrict__ qkv, int64_t ld, const T* __restrict__ kc, const T* __restrict__ vc,
-                                                            int64_t n_slots, int cap, const int32_t* __restrict__ slot,
-                                                            const int32_t* __restrict__ kv_len, float* __restrict__ ws, int64_t span, int n_heads,
-                                                            int n_kv, int hd, int g, int lpk_log2, float qscale) {
+template <typename T, int G, typename C>
+__device__ __forceinline__ void split_slot_walk(const T* __restrict__ qkv, int64_t ld, const C& cache, int64_t n_slots, int cap,
+                                                const int32_t* __restrict__ slot, const int32_t* __restrict__ kv_len, float* __restrict__ ws,
+                                                int64_t span, int n_heads, int n_kv, int hd, int g, int lpk_log2, float qscale) {
     const int64_t r = blockIdx.x, k0 = (int64_t)blockIdx.z * span;
     const int kvh = blockIdx.y, h0 = kvh * g;
     const int sl = slot[r];
@@ -373,22 +566,33 @@ __global__ __launch_bounds__(256) void split_kv_walk_kernel(const T* __restrict_
     if (sl < 0 || sl >= n_slots || k0 >= n) return;       // (uniform over the workgroup; n <= 0 is among them: the merge writes such a row)
     const int n_end = k0 + span < n ? (int)(k0 + span) : n;
     const DecLane at = dec_lane<T>(lpk_log2, hd);
-    const int64_t kv_cols = (int64_t)n_kv * hd;
-    const T* kbase = kc + ((int64_t)sl * cap * n_kv + kvh) * hd + at.col;
-    const T* vbase = vc + ((int64_t)sl * cap * n_kv + kvh) * hd + at.col;
+    const SlotKeys<typename C::Lines> keys{cache.lines((int64_t)sl * cap, n_kv, kvh, hd, at.col)};
     float* part = ws + (((r * n_heads + h0) * gridDim.z) + blockIdx.z) * (hd + 2);
-    dec_part<T, G, false>(qkv + r * ld + (int64_t)h0 * hd, (int)k0, n_end, part, (int64_t)gridDim.z * (hd + 2), hd, g, at, qscale,
-                          SlotKeys<T>{kbase, vbase, kv_cols});
+    dec_part<T, G, false>(qkv + r * ld + (int64_t)h0 * hd, (int)k0, n_end, part, (int64_t)gridDim.z * (hd + 2), hd, g, at, qscale, keys);
 }
 
 template <typename T, int G>
-__global__ __launch_bounds__(256) void split_beam_walk_kernel(const T* __restrict__ qkv, int64_t ld, const T* __restrict__ pk, const T* __restrict__ pv,
-                                                              int64_t n_pslots, int cap_p, const T* __restrict__ bk, const T* __restrict__ bv,
-                                                              int64_t n_bslots, int cap_b, const int32_t* __restrict__ prompt_slot,
-                                                              const int32_t* __restrict__ prompt_len, const int32_t* __restrict__ gen_len,
-                                                              const int32_t* __restrict__ anc, int64_t ld_anc, float* __restrict__ ws, int64_t span,
-                                                              int n_heads, int n_kv, int hd, int g, int lpk_log2, float qscale,
-                                                              int32_t* __restrict__ n_bad) {
+__global__ __launch_bounds__(256) void split_kv_walk_kernel(const T* __restrict__ qkv, int64_t ld, const T* __restrict__ kc, const T* __restrict__ vc,
+                                                            int64_t n_slots, int cap, const int32_t* __restrict__ slot,
+                                                            const int32_t* __restrict__ kv_len, float* __restrict__ ws, int64_t span, int n_heads,
+                                                            int n_kv, int hd, int g, int lpk_log2, float qscale) {
+    split_slot_walk<T, G>(qkv, ld, PlainCache<T>{kc, vc}, n_slots, cap, slot, kv_len, ws, span, n_heads, n_kv, hd, g, lpk_log2, qscale);
+}
+
+template <typename T, int G>
+__global__ __launch_bounds__(256) void q8_split_walk_kernel(const T* __restrict__ qkv, int64_t ld, Q8Cache<T> cache, int64_t n_slots, int cap,
+                                                            const int32_t* __restrict__ slot, const int32_t* __restrict__ kv_len,
+                                                            float* __restrict__ ws, int64_t span, int n_heads, int n_kv, int hd, int g,
+                                                            int lpk_log2, float qscale) {
+    split_slot_walk<T, G>(qkv, ld, cache, n_slots, cap, slot, kv_len, ws, span, n_heads, n_kv, hd, g, lpk_log2, qscale);
+}
+
+template <typename T, int G, typename C>
+__device__ __forceinline__ void split_beam_walk(const T* __restrict__ qkv, int64_t ld, const C& pcache, int64_t n_pslots, int cap_p, const C& bcache,
+                                                int64_t n_bslots, int cap_b, const int32_t* __restrict__ prompt_slot,
+                                                const int32_t* __restrict__ prompt_len, const int32_t* __restrict__ gen_len,
+                                                const int32_t* __restrict__ anc, int64_t ld_anc, float* __restrict__ ws, int64_t span, int n_heads,
+                                                int n_kv, int hd, int g, int lpk_log2, float qscale, int32_t* __restrict__ n_bad) {
     const int64_t r = blockIdx.x, k0 = (int64_t)blockIdx.z * span;
     const int kvh = blockIdx.y, tid = threadIdx.x, h0 = kvh * g;
     const int sl = prompt_slot[r];
@@ -402,10 +606,9 @@ __global__ __launch_bounds__(256) void split_beam_walk_kernel(const T* __restric
     if (sl < 0 || k0 >= n) return;                        // (uniform over the workgroup)
     const int n_end = k0 + span < n ? (int)(k0 + span) : n;
     const bool p_ok = sl < n_pslots;
-    const int64_t kv_cols = (int64_t)n_kv * hd;
     const DecLane at = dec_lane<T>(lpk_log2, hd);
-    const int64_t pbase = ((int64_t)(p_ok ? sl : 0) * cap_p * n_kv + kvh) * hd + at.col;
-    const BeamKeys<T> keys{pk + pbase, pv + pbase, bk, bv, anc + r * ld_anc, kv_cols, (int64_t)kvh * hd + at.col, np, cap_b, (int)n_bslots, p_ok};
+    const BeamKeys<typename C::Lines> keys{pcache.lines((int64_t)(p_ok ? sl : 0) * cap_p, n_kv, kvh, hd, at.col),
+                                           bcache.lines(0, n_kv, kvh, hd, at.col), anc + r * ld_anc, np, cap_b, (int)n_bslots, p_ok};
     float* part = ws + (((r * n_heads + h0) * gridDim.z) + blockIdx.z) * (hd + 2);
     dec_part<T, G, true>(qkv + r * ld + (int64_t)h0 * hd, (int)k0, n_end, part, (int64_t)gridDim.z * (hd + 2), hd, g, at, qscale, keys);
     if (kvh == 0 && blockIdx.z == 0 && n_bad) {           // once per row, over the whole ancestry: beam_decode_kernel's count
@@ -414,6 +617,29 @@ __global__ __launch_bounds__(256) void split_beam_walk_kernel(const T* __restric
         const int any = __syncthreads_or(bad ? 1 : 0);
         if (tid == 0 && any) atomicAdd(n_bad, 1);
     }
+}
+
+template <typename T, int G>
+__global__ __launch_bounds__(256) void split_beam_walk_kernel(const T* __restrict__ qkv, int64_t ld, const T* __restrict__ pk, const T* __restrict__ pv,
+                                                              int64_t n_pslots, int cap_p, const T* __restrict__ bk, const T* __restrict__ bv,
+                                                              int64_t n_bslots, int cap_b, const int32_t* __restrict__ prompt_slot,
+                                                              const int32_t* __restrict__ prompt_len, const int32_t* __restrict__ gen_len,
+                                                              const int32_t* __restrict__ anc, int64_t ld_anc, float* __restrict__ ws, int64_t span,
+                                                              int n_heads, int n_kv, int hd, int g, int lpk_log2, float qscale,
+                                                              int32_t* __restrict__ n_bad) {
+    split_beam_walk<T, G>(qkv, ld, PlainCache<T>{pk, pv}, n_pslots, cap_p, PlainCache<T>{bk, bv}, n_bslots, cap_b, prompt_slot, prompt_len, gen_len,
+                          anc, ld_anc, ws, span, n_heads, n_kv, hd, g, lpk_log2, qscale, n_bad);
+}
+
+template <typename T, int G>
+__global__ __launch_bounds__(256) void q8_split_beam_kernel(const T* __restrict__ qkv, int64_t ld, Q8Cache<T> pcache, int64_t n_pslots, int cap_p,
+                                                            Q8Cache<T> bcache, int64_t n_bslots, int cap_b,
+                                                            const int32_t* __restrict__ prompt_slot, const int32_t* __restrict__ prompt_len,
+                                                            const int32_t* __restrict__ gen_len, const int32_t* __restrict__ anc, int64_t ld_anc,
+                                                            float* __restrict__ ws, int64_t span, int n_heads, int n_kv, int hd, int g,
+                                                            int lpk_log2, float qscale, int32_t* __restrict__ n_bad) {
+    split_beam_walk<T, G>(qkv, ld, pcache, n_pslots, cap_p, bcache, n_bslots, cap_b, prompt_slot, prompt_len, gen_len, anc, ld_anc, ws, span, n_heads,
+                          n_kv, hd, g, lpk_log2, qscale, n_bad);
 }
 
 // The merge of both forms, one workgroup per (row, kv head), one thread per (head, column).  A row has ``len_a`` keys clamped to [0, cap_a]
@@ -459,56 +685,78 @@ __global__ __launch_bounds__(256) void split_kv_merge_kernel(const float* __rest
     }
 }
 
-template <typename T, int G>
-void launch_decode(const void* qkv, int64_t ld, const void* kc, const void* vc, int64_t n_slots, int64_t cap, const int32_t* slot,
-                   const int32_t* kv_len, void* out, float* lse, int64_t rows, int n_heads, int n_kv, int hd, int32_t* n_bad, void* stream) {
-    const int lanes = hd / Vec16<T>::N;
+// A cache as an entry hands it to a launcher: the model-dtype form (k, v), or with ``q8`` codes (k, v) and exponent bytes (ke, ve).
+struct CacheArg {
+    const void *k, *v, *ke, *ve;
+    bool q8;
+    bool there() const { return k && v && (!q8 || (ke && ve)); }
+};
+template <typename T>
+Q8Cache<T> q8_cache(const CacheArg& c) {
+    return {(const uint8_t*)c.k, (const uint8_t*)c.v, (const uint8_t*)c.ke, (const uint8_t*)c.ve};
+}
+
+// lanes of a key (a power of two) and the scale of q: the same for both storage forms
+template <typename T>
+int lanes_log2(int hd) {
     int lpk_log2 = 0;
-    while ((1 << lpk_log2) < lanes) ++lpk_log2;
-    const float qscale = (float)(1.4426950408889634 / sqrt((double)hd));
-    hipLaunchKernelGGL((kv_decode_kernel<T, G>), dim3((unsigned)rows, (unsigned)n_kv), dim3(256), 0, (hipStream_t)stream, (const T*)qkv, ld,
-                       (const T*)kc, (const T*)vc, n_slots, (int)cap, slot, kv_len, (T*)out, lse, n_heads, n_kv, hd, n_heads / n_kv, lpk_log2,
-                       qscale, n_bad);
+    while ((1 << lpk_log2) < hd / Vec16<T>::N) ++lpk_log2;
+    return lpk_log2;
+}
+float decode_qscale(int hd) { return (float)(1.4426950408889634 / sqrt((double)hd)); }
+
+template <typename T, int G>
+void launch_decode(const void* qkv, int64_t ld, const CacheArg& c, int64_t n_slots, int64_t cap, const int32_t* slot, const int32_t* kv_len, void* out,
+                   float* lse, int64_t rows, int n_heads, int n_kv, int hd, int32_t* n_bad, void* stream) {
+    const dim3 grid((unsigned)rows, (unsigned)n_kv);
+    if (c.q8)
+        hipLaunchKernelGGL((q8_decode_kernel<T, G>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)qkv, ld, q8_cache<T>(c), n_slots, (int)cap, slot,
+                           kv_len, (T*)out, lse, n_heads, n_kv, hd, n_heads / n_kv, lanes_log2<T>(hd), decode_qscale(hd), n_bad);
+    else
+        hipLaunchKernelGGL((kv_decode_kernel<T, G>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)qkv, ld, (const T*)c.k, (const T*)c.v, n_slots,
+                           (int)cap, slot, kv_len, (T*)out, lse, n_heads, n_kv, hd, n_heads / n_kv, lanes_log2<T>(hd), decode_qscale(hd), n_bad);
 }
 
 template <typename T, int G>
-void launch_decode_beam(const void* qkv, int64_t ld, const void* pk, const void* pv, int64_t n_pslots, int64_t cap_p, const void* bk, const void* bv,
-                        int64_t n_bslots, int64_t cap_b, const int32_t* prompt_slot, const int32_t* prompt_len, const int32_t* gen_len,
-                        const int32_t* anc, int64_t ld_anc, void* out, float* lse, int64_t rows, int n_heads, int n_kv, int hd, int32_t* n_bad,
-                        void* stream) {
-    const int lanes = hd / Vec16<T>::N;
-    int lpk_log2 = 0;
-    while ((1 << lpk_log2) < lanes) ++lpk_log2;
-    const float qscale = (float)(1.4426950408889634 / sqrt((double)hd));
-    hipLaunchKernelGGL((beam_decode_kernel<T, G>), dim3((unsigned)rows, (unsigned)n_kv), dim3(256), 0, (hipStream_t)stream, (const T*)qkv, ld,
-                       (const T*)pk, (const T*)pv, n_pslots, (int)cap_p, (const T*)bk, (const T*)bv, n_bslots, (int)cap_b, prompt_slot, prompt_len,
-                       gen_len, anc, ld_anc, (T*)out, lse, n_heads, n_kv, hd, n_heads / n_kv, lpk_log2, qscale, n_bad);
+void launch_decode_beam(const void* qkv, int64_t ld, const CacheArg& p, int64_t n_pslots, int64_t cap_p, const CacheArg& b, int64_t n_bslots,
+                        int64_t cap_b, const int32_t* prompt_slot, const int32_t* prompt_len, const int32_t* gen_len, const int32_t* anc,
+                        int64_t ld_anc, void* out, float* lse, int64_t rows, int n_heads, int n_kv, int hd, int32_t* n_bad, void* stream) {
+    const dim3 grid((unsigned)rows, (unsigned)n_kv);
+    if (p.q8)
+        hipLaunchKernelGGL((q8_beam_kernel<T, G>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)qkv, ld, q8_cache<T>(p), n_pslots, (int)cap_p,
+                           q8_cache<T>(b), n_bslots, (int)cap_b, prompt_slot, prompt_len, gen_len, anc, ld_anc, (T*)out, lse, n_heads, n_kv, hd,
+                           n_heads / n_kv, lanes_log2<T>(hd), decode_qscale(hd), n_bad);
+    else
+        hipLaunchKernelGGL((beam_decode_kernel<T, G>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)qkv, ld, (const T*)p.k, (const T*)p.v, n_pslots,
+                           (int)cap_p, (const T*)b.k, (const T*)b.v, n_bslots, (int)cap_b, prompt_slot, prompt_len, gen_len, anc, ld_anc, (T*)out, lse,
+                           n_heads, n_kv, hd, n_heads / n_kv, lanes_log2<T>(hd), decode_qscale(hd), n_bad);
 }
 
 template <typename T, int G>
-void launch_split(const void* qkv, int64_t ld, const void* kc, const void* vc, int64_t n_slots, int64_t cap, const int32_t* slot,
-                  const int32_t* kv_len, float* ws, int64_t span, int64_t n_splits, int64_t rows, int n_heads, int n_kv, int hd, void* stream) {
-    const int lanes = hd / Vec16<T>::N;
-    int lpk_log2 = 0;
-    while ((1 << lpk_log2) < lanes) ++lpk_log2;
-    const float qscale = (float)(1.4426950408889634 / sqrt((double)hd));
-    hipLaunchKernelGGL((split_kv_walk_kernel<T, G>), dim3((unsigned)rows, (unsigned)n_kv, (unsigned)n_splits), dim3(256), 0, (hipStream_t)stream,
-                       (const T*)qkv, ld, (const T*)kc, (const T*)vc, n_slots, (int)cap, slot, kv_len, ws, span, n_heads, n_kv, hd, n_heads / n_kv,
-                       lpk_log2, qscale);
+void launch_split(const void* qkv, int64_t ld, const CacheArg& c, int64_t n_slots, int64_t cap, const int32_t* slot, const int32_t* kv_len, float* ws,
+                  int64_t span, int64_t n_splits, int64_t rows, int n_heads, int n_kv, int hd, void* stream) {
+    const dim3 grid((unsigned)rows, (unsigned)n_kv, (unsigned)n_splits);
+    if (c.q8)
+        hipLaunchKernelGGL((q8_split_walk_kernel<T, G>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)qkv, ld, q8_cache<T>(c), n_slots, (int)cap,
+                           slot, kv_len, ws, span, n_heads, n_kv, hd, n_heads / n_kv, lanes_log2<T>(hd), decode_qscale(hd));
+    else
+        hipLaunchKernelGGL((split_kv_walk_kernel<T, G>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)qkv, ld, (const T*)c.k, (const T*)c.v,
+                           n_slots, (int)cap, slot, kv_len, ws, span, n_heads, n_kv, hd, n_heads / n_kv, lanes_log2<T>(hd), decode_qscale(hd));
 }
 
 template <typename T, int G>
-void launch_split_beam(const void* qkv, int64_t ld, const void* pk, const void* pv, int64_t n_pslots, int64_t cap_p, const void* bk, const void* bv,
-                       int64_t n_bslots, int64_t cap_b, const int32_t* prompt_slot, const int32_t* prompt_len, const int32_t* gen_len,
-                       const int32_t* anc, int64_t ld_anc, float* ws, int64_t span, int64_t n_splits, int64_t rows, int n_heads, int n_kv, int hd,
-                       int32_t* n_bad, void* stream) {
-    const int lanes = hd / Vec16<T>::N;
-    int lpk_log2 = 0;
-    while ((1 << lpk_log2) < lanes) ++lpk_log2;
-    const float qscale = (float)(1.4426950408889634 / sqrt((double)hd));
-    hipLaunchKernelGGL((split_beam_walk_kernel<T, G>), dim3((unsigned)rows, (unsigned)n_kv, (unsigned)n_splits), dim3(256), 0, (hipStream_t)stream,
-                       (const T*)qkv, ld, (const T*)pk, (const T*)pv, n_pslots, (int)cap_p, (const T*)bk, (const T*)bv, n_bslots, (int)cap_b,
-                       prompt_slot, prompt_len, gen_len, anc, ld_anc, ws, span, n_heads, n_kv, hd, n_heads / n_kv, lpk_log2, qscale, n_bad);
+void launch_split_beam(const void* qkv, int64_t ld, const CacheArg& p, int64_t n_pslots, int64_t cap_p, const CacheArg& b, int64_t n_bslots,
+                       int64_t cap_b, const int32_t* prompt_slot, const int32_t* prompt_len, const int32_t* gen_len, const int32_t* anc, int64_t ld_anc,
+                       float* ws, int64_t span, int64_t n_splits, int64_t rows, int n_heads, int n_kv, int hd, int32_t* n_bad, void* stream) {
+    const dim3 grid((unsigned)rows, (unsigned)n_kv, (unsigned)n_splits);
+    if (p.q8)
+        hipLaunchKernelGGL((q8_split_beam_kernel<T, G>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)qkv, ld, q8_cache<T>(p), n_pslots,
+                           (int)cap_p, q8_cache<T>(b), n_bslots, (int)cap_b, prompt_slot, prompt_len, gen_len, anc, ld_anc, ws, span, n_heads, n_kv, hd,
+                           n_heads / n_kv, lanes_log2<T>(hd), decode_qscale(hd), n_bad);
+    else
+        hipLaunchKernelGGL((split_beam_walk_kernel<T, G>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)qkv, ld, (const T*)p.k, (const T*)p.v,
+                           n_pslots, (int)cap_p, (const T*)b.k, (const T*)b.v, n_bslots, (int)cap_b, prompt_slot, prompt_len, gen_len, anc, ld_anc, ws,
+                           span, n_heads, n_kv, hd, n_heads / n_kv, lanes_log2<T>(hd), decode_qscale(hd), n_bad);
 }
 
 template <typename T>
@@ -521,7 +769,7 @@ void launch_split_merge(const float* ws, int64_t span, int64_t n_splits, const i
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-// head geometry both entries accept
+// head geometry every entry accepts
 int check_geometry(const char* who, int n_heads, int n_kv, int head_dim) {
     if (n_heads < 1 || n_kv < 1 || head_dim < 1) { ssi_set_error("%s: n_heads, n_kv and head_dim must be positive", who); return SSI_ERR_ARG; }
     if (n_heads % n_kv || n_heads / n_kv > 8 || head_dim % 8 || head_dim > DEC_MAX_HD || n_kv > 65535) {
@@ -532,29 +780,30 @@ int check_geometry(const char* who, int n_heads, int n_kv, int head_dim) {
     return SSI_OK;
 }
 
-// what ssi_attn_decode and its split form check alike (rows > 0)
-int check_decode_args(const void* qkv, int64_t ld, const void* k_cache, const void* v_cache, int64_t n_slots, int64_t cap, const int32_t* slot,
-                      const int32_t* kv_len, const void* out, int64_t rows, int n_heads, int head_dim, int dtype) {
+// what ssi_attn_decode and its split form check alike (rows > 0); the exponent bytes of an fp8 cache need no alignment
+int check_decode_args(const void* qkv, int64_t ld, const CacheArg& c, int64_t n_slots, int64_t cap, const int32_t* slot, const int32_t* kv_len,
+                      const void* out, int64_t rows, int n_heads, int head_dim, int dtype) {
     const int64_t esize = dtype == SSI_BF16 ? 2 : 4;
     SSI_CHECK_ARG(qkv && slot && kv_len && out && rows < (1LL << 31) && ld >= (int64_t)n_heads * head_dim);
-    SSI_CHECK_ARG((k_cache && v_cache) || n_slots * cap == 0);
-    SSI_CHECK_ARG(aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache) && (ld * esize) % 16 == 0);
+    SSI_CHECK_ARG(c.there() || n_slots * cap == 0);
+    SSI_CHECK_ARG(aligned16(qkv) && aligned16(c.k) && aligned16(c.v) && (ld * esize) % 16 == 0);
     return SSI_OK;
 }
 
 // what ssi_attn_decode_beam and its split form check alike (rows > 0)
-int check_beam_args(const void* qkv, int64_t ld, const void* pk_cache, const void* pv_cache, int64_t n_pslots, int64_t cap_p, const void* bk_cache,
-                    const void* bv_cache, int64_t n_bslots, int64_t cap_b, const int32_t* prompt_slot, const int32_t* prompt_len,
-                    const int32_t* gen_len, const int32_t* anc, int64_t ld_anc, const void* out, int64_t rows, int n_heads, int head_dim, int dtype) {
+int check_beam_args(const void* qkv, int64_t ld, const CacheArg& p, int64_t n_pslots, int64_t cap_p, const CacheArg& b, int64_t n_bslots, int64_t cap_b,
+                    const int32_t* prompt_slot, const int32_t* prompt_len, const int32_t* gen_len, const int32_t* anc, int64_t ld_anc, const void* out,
+                    int64_t rows, int n_heads, int head_dim, int dtype) {
     const int64_t esize = dtype == SSI_BF16 ? 2 : 4;
     SSI_CHECK_ARG(qkv && prompt_slot && prompt_len && gen_len && out && rows < (1LL << 31) && ld >= (int64_t)n_heads * head_dim);
-    SSI_CHECK_ARG((pk_cache && pv_cache) || n_pslots * cap_p == 0);
-    SSI_CHECK_ARG((bk_cache && bv_cache && anc) || n_bslots * cap_b * ld_anc == 0);
-    SSI_CHECK_ARG(aligned16(qkv) && aligned16(pk_cache) && aligned16(pv_cache) && aligned16(bk_cache) && aligned16(bv_cache) && (ld * esize) % 16 == 0);
+    SSI_CHECK_ARG(p.there() || n_pslots * cap_p == 0);
+    SSI_CHECK_ARG((b.there() && anc) || n_bslots * cap_b * ld_anc == 0);
+    SSI_CHECK_ARG(aligned16(qkv) && aligned16(p.k) && aligned16(p.v) && aligned16(b.k) && aligned16(b.v) && (ld * esize) % 16 == 0);
     return SSI_OK;
 }
 
-// keys per round of the four waves (8 loads of 64 / LPK keys) of a form, the unit of a split's span; 0: no such form
+// keys per round of the four waves (8 loads of 64 / LPK keys) of a form, the unit of a split's span; 0: no such form.  (The fp8 forms keep the
+// lane layout of the model's dtype: theirs is the same.)
 int decode_round(int head_dim, int dtype) {
     if ((dtype != SSI_F32 && dtype != SSI_BF16) || head_dim < 1 || head_dim % 8 || head_dim > DEC_MAX_HD) return 0;
     const int lanes = head_dim * (dtype == SSI_BF16 ? 2 : 4) / 16;
@@ -584,6 +833,87 @@ int check_split_args(int64_t span, int64_t n_splits, int64_t keys, const void* w
         else LAUNCH(8);              \
     } while (0)
 
+// ---- the entries' bodies: an entry and its _fp8 form differ in the CacheArg they make of their arguments --------------------------------------
+int decode_entry(const char* who, const void* qkv, int64_t ld, const CacheArg& c, int64_t n_slots, int64_t cap, const int32_t* slot,
+                 const int32_t* kv_len, void* out, float* lse, int64_t rows, int n_heads, int n_kv, int head_dim, int32_t* n_bad, int dtype,
+                 void* stream) {
+    SSI_CHECK_ARG(rows >= 0 && n_slots >= 0 && cap >= 0 && cap < (1LL << 31) && (dtype == SSI_F32 || dtype == SSI_BF16));
+    if (int rc = check_geometry(who, n_heads, n_kv, head_dim)) return rc;
+    if (rows == 0) return SSI_OK;
+    if (int rc = check_decode_args(qkv, ld, c, n_slots, cap, slot, kv_len, out, rows, n_heads, head_dim, dtype)) return rc;
+#define SSI_DECODE_G(GG) launch_decode<T, GG>(qkv, ld, c, n_slots, cap, slot, kv_len, out, lse, rows, n_heads, n_kv, head_dim, n_bad, stream)
+    SSI_DISPATCH_DTYPE(dtype, SSI_DECODE_FORMS(n_heads / n_kv, SSI_DECODE_G));
+#undef SSI_DECODE_G
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+int beam_entry(const char* who, const void* qkv, int64_t ld, const CacheArg& p, int64_t n_pslots, int64_t cap_p, const CacheArg& b, int64_t n_bslots,
+               int64_t cap_b, const int32_t* prompt_slot, const int32_t* prompt_len, const int32_t* gen_len, const int32_t* anc, int64_t ld_anc,
+               void* out, float* lse, int64_t rows, int n_heads, int n_kv, int head_dim, int32_t* n_bad, int dtype, void* stream) {
+    SSI_CHECK_ARG(rows >= 0 && n_pslots >= 0 && cap_p >= 0 && n_bslots >= 0 && cap_b >= 0 && ld_anc >= 0 && (dtype == SSI_F32 || dtype == SSI_BF16));
+    SSI_CHECK_ARG(cap_p + cap_b < (1LL << 31) && n_bslots < (1LL << 31));
+    if (int rc = check_geometry(who, n_heads, n_kv, head_dim)) return rc;
+    if (rows == 0) return SSI_OK;
+    if (int rc = check_beam_args(qkv, ld, p, n_pslots, cap_p, b, n_bslots, cap_b, prompt_slot, prompt_len, gen_len, anc, ld_anc, out, rows, n_heads,
+                                 head_dim, dtype)) return rc;
+    const int64_t cap_b_eff = (b.there() && anc) ? cap_b : 0, n_ps_eff = p.there() ? n_pslots : 0;
+#define SSI_DECODE_G(GG)                                                                                                                          \
+    launch_decode_beam<T, GG>(qkv, ld, p, n_ps_eff, cap_p, b, n_bslots, cap_b_eff, prompt_slot, prompt_len, gen_len, anc, ld_anc, out, lse, rows, \
+                              n_heads, n_kv, head_dim, n_bad, stream)
+    SSI_DISPATCH_DTYPE(dtype, SSI_DECODE_FORMS(n_heads / n_kv, SSI_DECODE_G));
+#undef SSI_DECODE_G
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+int split_entry(const char* who, const void* qkv, int64_t ld, const CacheArg& c, int64_t n_slots, int64_t cap, const int32_t* slot,
+                const int32_t* kv_len, void* out, float* lse, int64_t rows, int n_heads, int n_kv, int head_dim, int32_t* n_bad, int64_t span,
+                int64_t n_splits, void* workspace, int64_t workspace_bytes, int dtype, void* stream) {
+    SSI_CHECK_ARG(rows >= 0 && n_slots >= 0 && cap >= 0 && cap < (1LL << 31) && (dtype == SSI_F32 || dtype == SSI_BF16));
+    if (int rc = check_geometry(who, n_heads, n_kv, head_dim)) return rc;
+    if (int rc = check_split_args(span, n_splits, cap, workspace, workspace_bytes, rows, n_heads, head_dim, dtype)) return rc;
+    if (rows == 0) return SSI_OK;
+    if (int rc = check_decode_args(qkv, ld, c, n_slots, cap, slot, kv_len, out, rows, n_heads, head_dim, dtype)) return rc;
+#define SSI_DECODE_G(GG) \
+    launch_split<T, GG>(qkv, ld, c, n_slots, cap, slot, kv_len, (float*)workspace, span, n_splits, rows, n_heads, n_kv, head_dim, stream)
+    SSI_DISPATCH_DTYPE(dtype, {
+        SSI_DECODE_FORMS(n_heads / n_kv, SSI_DECODE_G);
+        launch_split_merge<T>((const float*)workspace, span, n_splits, slot, n_slots, kv_len, cap, nullptr, 0, out, lse, rows, n_heads, n_kv, head_dim,
+                              n_bad, stream);
+    });
+#undef SSI_DECODE_G
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+int beam_split_entry(const char* who, const void* qkv, int64_t ld, const CacheArg& p, int64_t n_pslots, int64_t cap_p, const CacheArg& b,
+                     int64_t n_bslots, int64_t cap_b, const int32_t* prompt_slot, const int32_t* prompt_len, const int32_t* gen_len,
+                     const int32_t* anc, int64_t ld_anc, void* out, float* lse, int64_t rows, int n_heads, int n_kv, int head_dim, int32_t* n_bad,
+                     int64_t span, int64_t n_splits, void* workspace, int64_t workspace_bytes, int dtype, void* stream) {
+    SSI_CHECK_ARG(rows >= 0 && n_pslots >= 0 && cap_p >= 0 && n_bslots >= 0 && cap_b >= 0 && ld_anc >= 0 && (dtype == SSI_F32 || dtype == SSI_BF16));
+    SSI_CHECK_ARG(cap_p + cap_b < (1LL << 31) && n_bslots < (1LL << 31));
+    if (int rc = check_geometry(who, n_heads, n_kv, head_dim)) return rc;
+    if (int rc = check_split_args(span, n_splits, cap_p + (cap_b < ld_anc ? cap_b : ld_anc), workspace, workspace_bytes, rows, n_heads, head_dim, dtype))
+        return rc;
+    if (rows == 0) return SSI_OK;
+    if (int rc = check_beam_args(qkv, ld, p, n_pslots, cap_p, b, n_bslots, cap_b, prompt_slot, prompt_len, gen_len, anc, ld_anc, out, rows, n_heads,
+                                 head_dim, dtype)) return rc;
+    const int64_t cap_b_eff = (b.there() && anc) ? cap_b : 0, n_ps_eff = p.there() ? n_pslots : 0;
+    const int64_t gen_cap = cap_b_eff < ld_anc ? cap_b_eff : ld_anc;
+#define SSI_DECODE_G(GG)                                                                                                                       \
+    launch_split_beam<T, GG>(qkv, ld, p, n_ps_eff, cap_p, b, n_bslots, cap_b_eff, prompt_slot, prompt_len, gen_len, anc, ld_anc, (float*)workspace, \
+                             span, n_splits, rows, n_heads, n_kv, head_dim, n_bad, stream)
+    SSI_DISPATCH_DTYPE(dtype, {
+        SSI_DECODE_FORMS(n_heads / n_kv, SSI_DECODE_G);
+        launch_split_merge<T>((const float*)workspace, span, n_splits, prompt_slot, INT64_MAX, prompt_len, cap_p, gen_len, gen_cap, out, lse, rows,
+                              n_heads, n_kv, head_dim, nullptr, stream);
+    });
+#undef SSI_DECODE_G
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
 }  // namespace
 
 extern "C" int ssi_kv_store(const void* qkv, int64_t ld, const int64_t* dest, int64_t rows, int64_t n_dest, void* k_cache, void* v_cache,
@@ -602,38 +932,56 @@ extern "C" int ssi_kv_store(const void* qkv, int64_t ld, const int64_t* dest, in
     return SSI_OK;
 }
 
+extern "C" int ssi_kv_store_fp8(const void* qkv, int64_t ld, const int64_t* dest, int64_t rows, int64_t n_dest, void* k_codes, void* v_codes,
+                                void* k_exp, void* v_exp, int n_heads, int n_kv, int head_dim, int32_t* n_bad, int dtype, void* stream) {
+    SSI_CHECK_ARG(rows >= 0 && n_dest >= 0 && (dtype == SSI_F32 || dtype == SSI_BF16));
+    if (int rc = check_geometry("ssi_kv_store_fp8", n_heads, n_kv, head_dim)) return rc;
+    if (rows == 0) return SSI_OK;
+    const int64_t esize = dtype == SSI_BF16 ? 2 : 4, q_cols = (int64_t)n_heads * head_dim, kv_cols = (int64_t)n_kv * head_dim;
+    SSI_CHECK_ARG(qkv && dest && k_codes && v_codes && k_exp && v_exp && ld >= q_cols + 2 * kv_cols && rows < (1LL << 31));
+    SSI_CHECK_ARG(aligned16(qkv) && aligned16(k_codes) && aligned16(v_codes) && (ld * esize) % 16 == 0);
+    SSI_DISPATCH_DTYPE(dtype, {
+        const int lpk_log2 = lanes_log2<T>(head_dim);
+        const int64_t lanes = (rows * 2 * n_kv) << lpk_log2;
+        SSI_CHECK_ARG(ssi_cdiv(lanes, 256) < (1LL << 31));
+        hipLaunchKernelGGL(q8_store_kernel<T>, dim3((unsigned)ssi_cdiv(lanes, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)qkv, ld, dest, rows,
+                           n_dest, (uint8_t*)k_codes, (uint8_t*)v_codes, (uint8_t*)k_exp, (uint8_t*)v_exp, (int)q_cols, n_kv, head_dim, lpk_log2, n_bad);
+    });
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
 extern "C" int ssi_attn_decode(const void* qkv, int64_t ld, const void* k_cache, const void* v_cache, int64_t n_slots, int64_t cap,
                                const int32_t* slot, const int32_t* kv_len, void* out, float* lse, int64_t rows, int n_heads, int n_kv,
                                int head_dim, int32_t* n_bad, int dtype, void* stream) {
-    SSI_CHECK_ARG(rows >= 0 && n_slots >= 0 && cap >= 0 && cap < (1LL << 31) && (dtype == SSI_F32 || dtype == SSI_BF16));
-    if (int rc = check_geometry("ssi_attn_decode", n_heads, n_kv, head_dim)) return rc;
-    if (rows == 0) return SSI_OK;
-    if (int rc = check_decode_args(qkv, ld, k_cache, v_cache, n_slots, cap, slot, kv_len, out, rows, n_heads, head_dim, dtype)) return rc;
-#define SSI_DECODE_G(GG) launch_decode<T, GG>(qkv, ld, k_cache, v_cache, n_slots, cap, slot, kv_len, out, lse, rows, n_heads, n_kv, head_dim, n_bad, stream)
-    SSI_DISPATCH_DTYPE(dtype, SSI_DECODE_FORMS(n_heads / n_kv, SSI_DECODE_G));
-#undef SSI_DECODE_G
-    SSI_LAUNCH_CHECK();
-    return SSI_OK;
+    return decode_entry("ssi_attn_decode", qkv, ld, {k_cache, v_cache, nullptr, nullptr, false}, n_slots, cap, slot, kv_len, out, lse, rows, n_heads,
+                        n_kv, head_dim, n_bad, dtype, stream);
+}
+
+extern "C" int ssi_attn_decode_fp8(const void* qkv, int64_t ld, const void* k_codes, const void* v_codes, const void* k_exp, const void* v_exp,
+                                   int64_t n_slots, int64_t cap, const int32_t* slot, const int32_t* kv_len, void* out, float* lse, int64_t rows,
+                                   int n_heads, int n_kv, int head_dim, int32_t* n_bad, int dtype, void* stream) {
+    return decode_entry("ssi_attn_decode_fp8", qkv, ld, {k_codes, v_codes, k_exp, v_exp, true}, n_slots, cap, slot, kv_len, out, lse, rows, n_heads,
+                        n_kv, head_dim, n_bad, dtype, stream);
 }
 
 extern "C" int ssi_attn_decode_beam(const void* qkv, int64_t ld, const void* pk_cache, const void* pv_cache, int64_t n_pslots, int64_t cap_p,
                                     const void* bk_cache, const void* bv_cache, int64_t n_bslots, int64_t cap_b, const int32_t* prompt_slot,
                                     const int32_t* prompt_len, const int32_t* gen_len, const int32_t* anc, int64_t ld_anc, void* out, float* lse,
                                     int64_t rows, int n_heads, int n_kv, int head_dim, int32_t* n_bad, int dtype, void* stream) {
-    SSI_CHECK_ARG(rows >= 0 && n_pslots >= 0 && cap_p >= 0 && n_bslots >= 0 && cap_b >= 0 && ld_anc >= 0 && (dtype == SSI_F32 || dtype == SSI_BF16));
-    SSI_CHECK_ARG(cap_p + cap_b < (1LL << 31) && n_bslots < (1LL << 31));
-    if (int rc = check_geometry("ssi_attn_decode_beam", n_heads, n_kv, head_dim)) return rc;
-    if (rows == 0) return SSI_OK;
-    if (int rc = check_beam_args(qkv, ld, pk_cache, pv_cache, n_pslots, cap_p, bk_cache, bv_cache, n_bslots, cap_b, prompt_slot, prompt_len, gen_len,
-                                 anc, ld_anc, out, rows, n_heads, head_dim, dtype)) return rc;
-    const int64_t cap_b_eff = (bk_cache && bv_cache && anc) ? cap_b : 0, n_ps_eff = (pk_cache && pv_cache) ? n_pslots : 0;
-#define SSI_DECODE_G(GG)                                                                                                                          \
-    launch_decode_beam<T, GG>(qkv, ld, pk_cache, pv_cache, n_ps_eff, cap_p, bk_cache, bv_cache, n_bslots, cap_b_eff, prompt_slot, prompt_len, gen_len, \
-                              anc, ld_anc, out, lse, rows, n_heads, n_kv, head_dim, n_bad, stream)
-    SSI_DISPATCH_DTYPE(dtype, SSI_DECODE_FORMS(n_heads / n_kv, SSI_DECODE_G));
-#undef SSI_DECODE_G
-    SSI_LAUNCH_CHECK();
-    return SSI_OK;
+    return beam_entry("ssi_attn_decode_beam", qkv, ld, {pk_cache, pv_cache, nullptr, nullptr, false}, n_pslots, cap_p,
+                      {bk_cache, bv_cache, nullptr, nullptr, false}, n_bslots, cap_b, prompt_slot, prompt_len, gen_len, anc, ld_anc, out, lse, rows,
+                      n_heads, n_kv, head_dim, n_bad, dtype, stream);
+}
+
+extern "C" int ssi_attn_decode_beam_fp8(const void* qkv, int64_t ld, const void* pk_codes, const void* pv_codes, const void* pk_exp,
+                                        const void* pv_exp, int64_t n_pslots, int64_t cap_p, const void* bk_codes, const void* bv_codes,
+                                        const void* bk_exp, const void* bv_exp, int64_t n_bslots, int64_t cap_b, const int32_t* prompt_slot,
+                                        const int32_t* prompt_len, const int32_t* gen_len, const int32_t* anc, int64_t ld_anc, void* out, float* lse,
+                                        int64_t rows, int n_heads, int n_kv, int head_dim, int32_t* n_bad, int dtype, void* stream) {
+    return beam_entry("ssi_attn_decode_beam_fp8", qkv, ld, {pk_codes, pv_codes, pk_exp, pv_exp, true}, n_pslots, cap_p,
+                      {bk_codes, bv_codes, bk_exp, bv_exp, true}, n_bslots, cap_b, prompt_slot, prompt_len, gen_len, anc, ld_anc, out, lse, rows,
+                      n_heads, n_kv, head_dim, n_bad, dtype, stream);
 }
 
 extern "C" int ssi_attn_decode_split_span(int head_dim, int dtype) {
@@ -650,21 +998,16 @@ extern "C" int ssi_attn_decode_split(const void* qkv, int64_t ld, const void* k_
                                      const int32_t* slot, const int32_t* kv_len, void* out, float* lse, int64_t rows, int n_heads, int n_kv,
                                      int head_dim, int32_t* n_bad, int64_t span, int64_t n_splits, void* workspace, int64_t workspace_bytes,
                                      int dtype, void* stream) {
-    SSI_CHECK_ARG(rows >= 0 && n_slots >= 0 && cap >= 0 && cap < (1LL << 31) && (dtype == SSI_F32 || dtype == SSI_BF16));
-    if (int rc = check_geometry("ssi_attn_decode_split", n_heads, n_kv, head_dim)) return rc;
-    if (int rc = check_split_args(span, n_splits, cap, workspace, workspace_bytes, rows, n_heads, head_dim, dtype)) return rc;
-    if (rows == 0) return SSI_OK;
-    if (int rc = check_decode_args(qkv, ld, k_cache, v_cache, n_slots, cap, slot, kv_len, out, rows, n_heads, head_dim, dtype)) return rc;
-#define SSI_DECODE_G(GG)                                                                                                                           \
-    launch_split<T, GG>(qkv, ld, k_cache, v_cache, n_slots, cap, slot, kv_len, (float*)workspace, span, n_splits, rows, n_heads, n_kv, head_dim, stream)
-    SSI_DISPATCH_DTYPE(dtype, {
-        SSI_DECODE_FORMS(n_heads / n_kv, SSI_DECODE_G);
-        launch_split_merge<T>((const float*)workspace, span, n_splits, slot, n_slots, kv_len, cap, nullptr, 0, out, lse, rows, n_heads, n_kv, head_dim,
-                              n_bad, stream);
-    });
-#undef SSI_DECODE_G
-    SSI_LAUNCH_CHECK();
-    return SSI_OK;
+    return split_entry("ssi_attn_decode_split", qkv, ld, {k_cache, v_cache, nullptr, nullptr, false}, n_slots, cap, slot, kv_len, out, lse, rows,
+                       n_heads, n_kv, head_dim, n_bad, span, n_splits, workspace, workspace_bytes, dtype, stream);
+}
+
+extern "C" int ssi_attn_decode_split_fp8(const void* qkv, int64_t ld, const void* k_codes, const void* v_codes, const void* k_exp, const void* v_exp,
+                                         int64_t n_slots, int64_t cap, const int32_t* slot, const int32_t* kv_len, void* out, float* lse,
+                                         int64_t rows, int n_heads, int n_kv, int head_dim, int32_t* n_bad, int64_t span, int64_t n_splits,
+                                         void* workspace, int64_t workspace_bytes, int dtype, void* stream) {
+    return split_entry("ssi_attn_decode_split_fp8", qkv, ld, {k_codes, v_codes, k_exp, v_exp, true}, n_slots, cap, slot, kv_len, out, lse, rows,
+                       n_heads, n_kv, head_dim, n_bad, span, n_splits, workspace, workspace_bytes, dtype, stream);
 }
 
 extern "C" int ssi_attn_decode_beam_split(const void* qkv, int64_t ld, const void* pk_cache, const void* pv_cache, int64_t n_pslots, int64_t cap_p,
@@ -672,25 +1015,19 @@ extern "C" int ssi_attn_decode_beam_split(const void* qkv, int64_t ld, const voi
                                           const int32_t* prompt_len, const int32_t* gen_len, const int32_t* anc, int64_t ld_anc, void* out,
                                           float* lse, int64_t rows, int n_heads, int n_kv, int head_dim, int32_t* n_bad, int64_t span,
                                           int64_t n_splits, void* workspace, int64_t workspace_bytes, int dtype, void* stream) {
-    SSI_CHECK_ARG(rows >= 0 && n_pslots >= 0 && cap_p >= 0 && n_bslots >= 0 && cap_b >= 0 && ld_anc >= 0 && (dtype == SSI_F32 || dtype == SSI_BF16));
-    SSI_CHECK_ARG(cap_p + cap_b < (1LL << 31) && n_bslots < (1LL << 31));
-    if (int rc = check_geometry("ssi_attn_decode_beam_split", n_heads, n_kv, head_dim)) return rc;
-    if (int rc = check_split_args(span, n_splits, cap_p + (cap_b < ld_anc ? cap_b : ld_anc), workspace, workspace_bytes, rows, n_heads, head_dim, dtype))
-        return rc;
-    if (rows == 0) return SSI_OK;
-    if (int rc = check_beam_args(qkv, ld, pk_cache, pv_cache, n_pslots, cap_p, bk_cache, bv_cache, n_bslots, cap_b, prompt_slot, prompt_len, gen_len,
-                                 anc, ld_anc, out, rows, n_heads, head_dim, dtype)) return rc;
-    const int64_t cap_b_eff = (bk_cache && bv_cache && anc) ? cap_b : 0, n_ps_eff = (pk_cache && pv_cache) ? n_pslots : 0;
-    const int64_t gen_cap = cap_b_eff < ld_anc ? cap_b_eff : ld_anc;
-#define SSI_DECODE_G(GG)                                                                                                                          \
-    launch_split_beam<T, GG>(qkv, ld, pk_cache, pv_cache, n_ps_eff, cap_p, bk_cache, bv_cache, n_bslots, cap_b_eff, prompt_slot, prompt_len, gen_len, \
-                             anc, ld_anc, (float*)workspace, span, n_splits, rows, n_heads, n_kv, head_dim, n_bad, stream)
-    SSI_DISPATCH_DTYPE(dtype, {
-        SSI_DECODE_FORMS(n_heads / n_kv, SSI_DECODE_G);
-        launch_split_merge<T>((const float*)workspace, span, n_splits, prompt_slot, INT64_MAX, prompt_len, cap_p, gen_len, gen_cap, out, lse, rows,
-                              n_heads, n_kv, head_dim, nullptr, stream);
-    });
-#undef SSI_DECODE_G
-    SSI_LAUNCH_CHECK();
-    return SSI_OK;
+    return beam_split_entry("ssi_attn_decode_beam_split", qkv, ld, {pk_cache, pv_cache, nullptr, nullptr, false}, n_pslots, cap_p,
+                            {bk_cache, bv_cache, nullptr, nullptr, false}, n_bslots, cap_b, prompt_slot, prompt_len, gen_len, anc, ld_anc, out, lse,
+                            rows, n_heads, n_kv, head_dim, n_bad, span, n_splits, workspace, workspace_bytes, dtype, stream);
+}
+
+extern "C" int ssi_attn_decode_beam_split_fp8(const void* qkv, int64_t ld, const void* pk_codes, const void* pv_codes, const void* pk_exp,
+                                              const void* pv_exp, int64_t n_pslots, int64_t cap_p, const void* bk_codes, const void* bv_codes,
+                                              const void* bk_exp, const void* bv_exp, int64_t n_bslots, int64_t cap_b,
+                                              const int32_t* prompt_slot, const int32_t* prompt_len, const int32_t* gen_len, const int32_t* anc,
+                                              int64_t ld_anc, void* out, float* lse, int64_t rows, int n_heads, int n_kv, int head_dim,
+                                              int32_t* n_bad, int64_t span, int64_t n_splits, void* workspace, int64_t workspace_bytes, int dtype,
+                                              void* stream) {
+    return beam_split_entry("ssi_attn_decode_beam_split_fp8", qkv, ld, {pk_codes, pv_codes, pk_exp, pv_exp, true}, n_pslots, cap_p,
+                            {bk_codes, bv_codes, bk_exp, bv_exp, true}, n_bslots, cap_b, prompt_slot, prompt_len, gen_len, anc, ld_anc, out, lse, rows,
+                            n_heads, n_kv, head_dim, n_bad, span, n_splits, workspace, workspace_bytes, dtype, stream);
 }

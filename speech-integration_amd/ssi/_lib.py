@@ -20,7 +20,7 @@ SSI_F32, SSI_BF16 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 IMPL_AUTO, IMPL_GENERIC, IMPL_MFMA, IMPL_MFMA_WG8 = 0, 1, 2, 3
 TILES_STATIC, TILES_DYNAMIC = 0, 1
-ABI_VERSION = 25
+ABI_VERSION = 26
 GEMM_SKINNY_MAX_ROWS = 64
 DECODE_PENALTY_LDS_MAX = 57344
 ADAMW_MAX_SEGS = 128
@@ -80,6 +80,14 @@ PROTOTYPES = {
                                       c_int64, c_int, _P]),
     "ssi_attn_decode_beam_split": (c_int, [_P, c_int64, _P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_int64, _P, _P, c_int64,
                                            c_int, c_int, c_int, _P, c_int64, c_int64, _P, c_int64, c_int, _P]),
+    "ssi_kv_store_fp8": (c_int, [_P, c_int64, _P, c_int64, c_int64, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P]),
+    "ssi_attn_decode_fp8": (c_int, [_P, c_int64, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_int64, c_int, c_int, c_int, _P, c_int, _P]),
+    "ssi_attn_decode_beam_fp8": (c_int, [_P, c_int64, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_int64,
+                                         _P, _P, c_int64, c_int, c_int, c_int, _P, c_int, _P]),
+    "ssi_attn_decode_split_fp8": (c_int, [_P, c_int64, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_int64, c_int, c_int, c_int, _P, c_int64,
+                                          c_int64, _P, c_int64, c_int, _P]),
+    "ssi_attn_decode_beam_split_fp8": (c_int, [_P, c_int64, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P,
+                                               c_int64, _P, _P, c_int64, c_int, c_int, c_int, _P, c_int64, c_int64, _P, c_int64, c_int, _P]),
     "ssi_topk_logprob": (c_int, [_P, c_int64, c_int64, c_int64, c_int, _P, c_int64, _P, _P, _P, c_int, _P]),
     "ssi_doc_ranges": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P]),
     "ssi_swiglu_fwd": (c_int, [_P, _P, c_int64, c_int64, c_int, _P]),

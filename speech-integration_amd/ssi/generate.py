@@ -191,6 +191,20 @@ def _constraint(masks: tuple[Tensor, Tensor] | None, min_new: int, dev) -> _Cons
     return _Constraint(allow, _mask_words(masks[0]).to(dev), early if min_new else None, _mask_words(masks[1]).to(dev) if min_new else None, min_new)
 
 
+def check_kv_cache_dtype(kv_cache_dtype) -> str | None:
+    """``kv_cache_dtype`` of the three loops: None or "auto" (the model's dtype; not one launch, buffer or bit differs from a call without it) or
+    "fp8" (``HipLlamaDecoder.new_kv_cache(..., dtype="fp8")``: vLLM's ``kv_cache_dtype="fp8"``, with one power-of-two scale per cached line);
+    anything else is a ``ValueError`` before any launch.  Returns what ``new_kv_cache`` takes."""
+    if kv_cache_dtype is None or (isinstance(kv_cache_dtype, str) and kv_cache_dtype in ("auto", "fp8")):
+        return None if kv_cache_dtype in (None, "auto") else "fp8"
+    raise ValueError(f"kv_cache_dtype = {kv_cache_dtype!r}: None, 'auto' or 'fp8'")
+
+
+def _new_cache(model, n_slots: int, cap: int, kv_dtype: str | None):
+    """``model.new_kv_cache`` as it was always called, or of the kind ``check_kv_cache_dtype`` let through."""
+    return model.new_kv_cache(n_slots, cap) if kv_dtype is None else model.new_kv_cache(n_slots, cap, dtype=kv_dtype)
+
+
 def _small_batch_kw(model, rows: int, small_batch: bool, report: dict | None, split_kv: bool = False) -> tuple[dict, dict]:
     """The keywords of a group of ``rows`` rows, decided once per group: (``prefill``'s, a decode step's).  Without a flag both are empty — the
     calls are then the plain ones, argument for argument.  With ``small_batch`` every step gets ``small_batch``, and a group that decodes on the
@@ -426,7 +440,7 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
              logprobs: bool = False, device: torch.device | str | None = None, allowed_token_ids: Sequence[int] | Tensor | None = None,
              min_new_tokens: int = 0, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
              presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None,
-             split_kv: bool = False) -> list[Generation]:
+             split_kv: bool = False, kv_cache_dtype: str | None = None) -> list[Generation]:
     """Greedy continuation of every prompt (1-D integer sequences), results in INPUT order.  The token of a step is ``argmax`` over the real
     columns ``[:, :vocab_size]`` of the step's logits, with torch's first-occurrence rule.  ``pad_id`` fills the rows that have finished.
     ``logprobs=True``: the forward-only ``ops.ce_fwd_metrics`` runs on the step's logits with the chosen token as label, which gives its
@@ -447,10 +461,14 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
     attention (``HipLlamaDecoder.takes_split_kv``) and prefills prompt by prompt, and adds 1 to ``"split_kv_groups"`` of ``small_batch_report``.
     A row still depends on itself alone, but its bits depend on whether its group splits: tokens and ``cumulative_logprob`` are bit-equal among
     groups on the same side of ``split_max_rows`` (as for ``skinny_max_rows``).  ``False``: not one launch or buffer differs.
+    ``kv_cache_dtype``: None or "auto" — the caches hold the model's dtype; "fp8" — they hold e4m3 codes with one power-of-two exponent per cached
+    line (``check_kv_cache_dtype``): the store and the attention of every step are the ``_fp8`` entries, the prompt's own attention in ``prefill``
+    runs on the unquantised K / V, and values change (opt-in).  Orthogonal to ``small_batch`` and ``split_kv``.
     Refused before any launch (``ValueError``): a penalty outside its range, an empty prompt, a prompt that with ``max_new_tokens`` exceeds the model's RoPE table or
     ``max_seq_len``; ``min_new_tokens < 0``, an allowed or stop id outside the vocabulary (under a constraint), an empty allowed set,
     ``min_new_tokens > 0`` with nothing allowed besides the stop tokens."""
     max_new_tokens, batch_size, min_new_tokens = int(max_new_tokens), int(batch_size), int(min_new_tokens)
+    kv_dtype = check_kv_cache_dtype(kv_cache_dtype)
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
     masks = _constraint_masks(int(model.vocab_size), allowed_token_ids, min_new_tokens, stop_token_ids)
     if max_new_tokens < 1:
@@ -466,7 +484,7 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
         return _token_loop(choose, started, caches, refused, [int(s.numel()) for s in seqs], max_new_tokens, stop, int(pad_id))
 
     return _run_groups(model, prompts, batch_size, max_new_tokens, stop_token_ids, masks, min_new_tokens,
-                       lambda n_slots, longest: (model.new_kv_cache(n_slots, longest + max_new_tokens),), run_group)
+                       lambda n_slots, longest: (_new_cache(model, n_slots, longest + max_new_tokens, kv_dtype),), run_group)
 
 
 # ---- beam search -----------------------------------------------------------------------------------------------------------------
@@ -488,7 +506,7 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
                 length_penalty: float = 1.0, n_best: int = 1, allowed_token_ids: Sequence[int] | Tensor | None = None, min_new_tokens: int = 0,
                 batch_size: int = 256, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
                 presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None,
-             split_kv: bool = False) -> list[list[Generation]]:
+             split_kv: bool = False, kv_cache_dtype: str | None = None) -> list[list[Generation]]:
     """The ``n_best <= beam_width <= 8`` best hypotheses of every prompt, best first, in INPUT order; ``cumulative_logprob`` (the sum of the
     tokens' log-probabilities under the unconstrained distribution) and ``score`` are always set.  A group holds ``batch_size // beam_width``
     prompts, so a step is at most ``batch_size`` rows.  The rules, with ``W = beam_width``:
@@ -506,8 +524,10 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
 
     Refused before any launch (``ValueError``): the three beam arguments outside their ranges, a penalty off its neutral value (vLLM's beam
     search ignores them, and ``ssi_topk_logprob`` knows none), and everything ``generate`` refuses.
-    ``small_batch``, ``split_kv``: handed to every ``decode_step_beam`` (``generate``'s rules, on the group's ``prompts * beam_width`` rows)."""
+    ``small_batch``, ``split_kv``: handed to every ``decode_step_beam`` (``generate``'s rules, on the group's ``prompts * beam_width`` rows).
+    ``kv_cache_dtype``: ``generate``'s; the prompt cache and the beam cache are of the same kind."""
     W, length_penalty, n_best = _check_beam(beam_width, length_penalty, n_best)
+    kv_dtype = check_kv_cache_dtype(kv_cache_dtype)
     if _check_penalties(repetition_penalty, frequency_penalty, presence_penalty) is not None:
         raise ValueError("beam_search: repetition, frequency and presence penalties are not part of beam search")
     max_new_tokens, batch_size, min_new_tokens, V = int(max_new_tokens), int(batch_size), int(min_new_tokens), int(model.vocab_size)
@@ -522,7 +542,8 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
         raise ValueError(f"batch_size = {batch_size} holds no prompt of beam_width = {W}")
 
     def open_caches(n_slots: int, longest: int):
-        return model.new_kv_cache(n_slots, longest), model.new_kv_cache(n_slots * W, max_new_tokens), _mask_words(cont).to(model.device)
+        return (_new_cache(model, n_slots, longest, kv_dtype), _new_cache(model, n_slots * W, max_new_tokens, kv_dtype),
+                _mask_words(cont).to(model.device))
 
     def run_group(caches, con, seqs: list[Tensor], index: list[int], stop: Tensor) -> list[list[Generation]]:
         return _beam_group(model, *caches[:2], seqs, W, max_new_tokens, stop, int(pad_id), length_penalty, n_best, caches[2], min_new_tokens,
@@ -646,7 +667,7 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
            stop_token_ids: Sequence[int], pad_id: int, batch_size: int = 256, allowed_token_ids: Sequence[int] | Tensor | None = None,
            min_new_tokens: int = 0, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
            presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None,
-             split_kv: bool = False) -> list[list[Generation]]:
+             split_kv: bool = False, kv_cache_dtype: str | None = None) -> list[list[Generation]]:
     """``n`` (1..8) sampled continuations of every prompt, in INPUT order and per prompt in sample order; ``cumulative_logprob`` (the tokens'
     log-probabilities under the unconstrained distribution at temperature 1, what ``ssi.score`` assigns) and ``n_kept_mean`` are always set.
     The token of a step is ``ops.decode_sample``'s with ``step`` the loop index and ``sequence = prompt index * n + sample index``: a pure function
@@ -660,8 +681,10 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
     one line of the group's prompt table.  The log-probabilities stay those of the raw row.
     Refused before any launch (``ValueError``): ``n`` outside 1..8, ``temperature`` not finite or <= 0 (greedy decoding is ``generate``), ``top_p``
     outside (0, 1], a non-integer ``top_k``, a negative ``seed``, and everything ``generate`` refuses.
-    ``small_batch``, ``split_kv``: handed to every decode step (``generate``'s rules, on the group's ``prompts * n`` rows)."""
+    ``small_batch``, ``split_kv``: handed to every decode step (``generate``'s rules, on the group's ``prompts * n`` rows).
+    ``kv_cache_dtype``: ``generate``'s; with ``n > 1`` the prompt cache and the samples' cache are of the same kind."""
     n, temperature, top_k, top_p, seed = _check_sample(n, temperature, top_k, top_p, seed)
+    kv_dtype = check_kv_cache_dtype(kv_cache_dtype)
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
     max_new_tokens, batch_size, min_new_tokens, V = int(max_new_tokens), int(batch_size), int(min_new_tokens), int(model.vocab_size)
     masks = _constraint_masks(V, allowed_token_ids, min_new_tokens, stop_token_ids)
@@ -676,8 +699,8 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
 
     def open_caches(n_slots: int, longest: int):
         if n == 1:
-            return (model.new_kv_cache(n_slots, longest + max_new_tokens),)
-        return model.new_kv_cache(n_slots, longest), model.new_kv_cache(n_slots * n, max_new_tokens)
+            return (_new_cache(model, n_slots, longest + max_new_tokens, kv_dtype),)
+        return _new_cache(model, n_slots, longest, kv_dtype), _new_cache(model, n_slots * n, max_new_tokens, kv_dtype)
 
     def run_group(caches, con, seqs: list[Tensor], index: list[int], stop: Tensor) -> list[list[Generation]]:
         if n == 1:          # no prompt to share: every row on its own slot, as ``generate``
@@ -748,7 +771,11 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     their neutral values); when any is set the summary gains the three values, and on the greedy path ``"constrained_tokens"``.
     ``small_batch=True`` in ``kw`` goes to whichever loop runs, and the summary gains ``"small_batch_groups"``: the number of groups that decoded on
     the skinny path.  ``split_kv=True`` likewise, with ``"split_kv_groups"``: the groups that ran the split-KV decode attention.  ``False`` (the
-    default of both) is not passed on and adds no key."""
+    default of both) is not passed on and adds no key.
+    ``kv_cache_dtype`` in ``kw`` goes to whichever loop runs (``check_kv_cache_dtype``, refused here before a prompt is read); the summary gains
+    ``"kv_cache_dtype": "fp8"`` under fp8 alone — None and "auto" are not passed on and add no key."""
+    kv_dtype = check_kv_cache_dtype(kw.pop("kv_cache_dtype", None))
+    fp8 = {} if kv_dtype is None else {"kv_cache_dtype": kv_dtype}
     if in_path is not None:
         ids, prompts = _read_prompts(tokenizer, in_path)
     elif prompts is None:
@@ -761,11 +788,11 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     kw.setdefault("pad_id", int(getattr(tokenizer, "pad_id", 0) or 0))
     flags = {flag: True for flag in ("small_batch", "split_kv") if kw.pop(flag, False)}
     if not flags:
-        return _run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, kw)
+        return dict(_run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, dict(kw, **fp8)), **fp8)
     report = {flag + "_groups": 0 for flag in flags}          # counted by the loop, group by group, where the path is taken
     summary = _run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding,
-                        dict(kw, small_batch_report=report, **flags))
-    return dict(summary, **report)
+                        dict(kw, small_batch_report=report, **flags, **fp8))
+    return dict(summary, **report, **fp8)
 
 
 def _run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, kw: dict) -> dict[str, Any]:

@@ -102,10 +102,17 @@ class KVCache:
     """What ``HipLlamaDecoder.new_kv_cache`` returns: ``k`` and ``v`` ``[layers, n_slots, cap, n_kv * head_dim]`` in the model's dtype (K
     after RoPE), ``lengths`` (int32 ``[n_slots]`` on the device: tokens cached per slot) and ``errors`` (int32 ``[1]`` on the device: K / V
     rows or slots the kernels refused — out-of-range destinations, a slot at its cap; 0 in a correct run, read it with whatever is read
-    back anyway)."""
+    back anyway).  An FP8 cache (``new_kv_cache(..., dtype="fp8")``; the header's "FP8 K/V cache") holds e4m3 codes in ``k`` and ``v`` (uint8, the
+    same shape) and one exponent byte per (position, kv head) in ``k_exp`` and ``v_exp`` (uint8 ``[layers, n_slots, cap, n_kv]``).  ``dtype``: "fp8",
+    or the torch dtype of a cache in the model's dtype."""
 
-    def __init__(self, k: Tensor, v: Tensor, lengths: Tensor, errors: Tensor) -> None:
-        self.k, self.v, self.lengths, self.errors = k, v, lengths, errors
+    def __init__(self, k: Tensor, v: Tensor, lengths: Tensor, errors: Tensor, k_exp: Optional[Tensor] = None, v_exp: Optional[Tensor] = None) -> None:
+        self.k, self.v, self.lengths, self.errors, self.k_exp, self.v_exp = k, v, lengths, errors, k_exp, v_exp
+        self.dtype = "fp8" if k_exp is not None else k.dtype
+
+    def layer(self, l: int) -> tuple:
+        """The cache tensors of layer ``l`` as the kernels take them: ``(k, v)``, or ``(k_codes, v_codes, k_exp, v_exp)`` of an fp8 cache."""
+        return (self.k[l], self.v[l]) if self.k_exp is None else (self.k[l], self.v[l], self.k_exp[l], self.v_exp[l])
 
     @property
     def n_slots(self) -> int:
@@ -540,7 +547,7 @@ class HipLlamaDecoder(nn.Module):
 
         def attend(l: int, b: _LayerBufs) -> None:
             if kv_sink is not None:
-                ops.kv_store(b.qkv, kv_sink[1], kv_sink[0].k[l], kv_sink[0].v[l], H, KV, hd, n_bad=kv_sink[0].errors)
+                self._kv_store(kv_sink[0], l, b.qkv, kv_sink[1])
             ops.attn_fwd(b.qkv, b.att, b.lse, B, S, H, KV, hd, ds, de)
 
         layers, final = self._run_stack("train" if save else "x", tok, B, S, S, pos, attend)  # (eval, no_grad: the ".x" buffers only)
@@ -724,15 +731,24 @@ class HipLlamaDecoder(nn.Module):
         self.attach_grads()
 
     # ---- generation: K/V cache, prefill, decode step (ssi/generate.py drives them) --------------------------------------------
-    def new_kv_cache(self, n_slots: int, cap: int) -> "KVCache":
+    def new_kv_cache(self, n_slots: int, cap: int, dtype=None) -> "KVCache":
         """A K/V cache for ``n_slots`` sequences of up to ``cap`` tokens: plain tensors owned by the caller (not arena buffers; the model
-        keeps no reference).  Nothing is allocated for generation before this is called."""
+        keeps no reference).  Nothing is allocated for generation before this is called.  ``dtype``: None or "auto" — the model's dtype; "fp8" —
+        e4m3 codes with a power-of-two exponent per (position, kv head), a quarter (fp32) or half (bf16) of the bytes plus 1 / head_dim: what
+        ``prefill`` and the decode steps store is quantised, and the decode steps attend over the quantised values (opt-in: it changes values)."""
         n_slots, cap = int(n_slots), int(cap)
         if n_slots < 1 or cap < 1:
             raise ValueError(f"new_kv_cache: n_slots and cap must be >= 1 (got {n_slots}, {cap})")
+        if dtype not in (None, "auto", "fp8"):
+            raise ValueError(f"new_kv_cache: dtype is None, 'auto' or 'fp8' (got {dtype!r})")
         shape = (self.num_layers, n_slots, cap, self.num_kv_heads * self.head_dim)
+        lengths, errors = torch.zeros(n_slots, dtype=torch.int32, device=self.device), torch.zeros(1, dtype=torch.int32, device=self.device)
+        if dtype == "fp8":
+            codes, exps = (lambda: torch.zeros(shape, dtype=torch.uint8, device=self.device)), (
+                lambda: torch.full(shape[:3] + (self.num_kv_heads,), 127, dtype=torch.uint8, device=self.device))
+            return KVCache(codes(), codes(), lengths, errors, exps(), exps())
         return KVCache(torch.zeros(shape, dtype=self.dtype, device=self.device), torch.zeros(shape, dtype=self.dtype, device=self.device),
-                       torch.zeros(n_slots, dtype=torch.int32, device=self.device), torch.zeros(1, dtype=torch.int32, device=self.device))
+                       lengths, errors)
 
     def check_generation_lengths(self, prompt_lens, max_new_tokens: int, n_slots: int, cap: int) -> None:
         """The host refusals of generation, before any launch."""
@@ -797,11 +813,26 @@ class HipLlamaDecoder(nn.Module):
         cache.lengths[:n] = torch.tensor(lens, dtype=torch.int32).to(dev)
         return self._head_logits(hlast)[:n]
 
-    def _check_cache(self, cache: "KVCache") -> None:
+    def _check_cache(self, cache: "KVCache", beside: Optional["KVCache"] = None) -> None:
+        """Either kind of cache of this model's shape; ``beside``: the cache it is used with in one launch (prompt and beam cache), which must be
+        of the same kind."""
+        fp8 = cache.dtype == "fp8"
         want = (self.num_layers, cache.n_slots, cache.cap, self.num_kv_heads * self.head_dim)
+        dtype = torch.uint8 if fp8 else self.dtype
         for t in (cache.k, cache.v):
-            if tuple(t.shape) != want or t.dtype != self.dtype or t.device != self.device:
-                raise ValueError(f"the K/V cache is not this model's: {tuple(t.shape)} {t.dtype} on {t.device}, expected {want} {self.dtype} on {self.device}")
+            if tuple(t.shape) != want or t.dtype != dtype or t.device != self.device:
+                raise ValueError(f"the K/V cache is not this model's: {tuple(t.shape)} {t.dtype} on {t.device}, expected {want} {dtype} on {self.device}")
+        if fp8:
+            for t in (cache.k_exp, cache.v_exp):
+                if t is None or tuple(t.shape) != want[:3] + (self.num_kv_heads,) or t.dtype != torch.uint8 or t.device != self.device:
+                    raise ValueError(f"the fp8 K/V cache's exponents are not this model's: expected uint8 {want[:3] + (self.num_kv_heads,)} on {self.device}")
+        if beside is not None and (beside.dtype == "fp8") != fp8:
+            raise ValueError(f"a prompt cache and a beam cache of different kinds ({beside.dtype} and {cache.dtype}): both fp8 or both the model's dtype")
+
+    def _kv_store(self, cache: "KVCache", l: int, qkv: Tensor, dest: Tensor) -> None:
+        """The K / V columns of ``qkv`` rows into layer ``l`` of ``cache`` at ``dest``, by the store of the cache's kind."""
+        store = ops.kv_store_fp8 if cache.dtype == "fp8" else ops.kv_store
+        store(qkv, dest, *cache.layer(l), self.num_heads, self.num_kv_heads, self.head_dim, n_bad=cache.errors)
 
     @torch.no_grad()
     def decode_step(self, cache: "KVCache", tokens: Tensor, slots: Tensor, small_batch: bool = False, split_kv: bool = False) -> Tensor:
@@ -841,13 +872,15 @@ class HipLlamaDecoder(nn.Module):
         kv_len = torch.where(live, length + 1, torch.zeros_like(length)).contiguous()
         mode = "s" if small else "g"
         split = self._split_kv(mode, R, cache.cap) if self.takes_split_kv(n, split_kv) else None
+        fp8 = cache.dtype == "fp8"
 
         def attend(l: int, b: _LayerBufs) -> None:
-            ops.kv_store(b.qkv, dest, cache.k[l], cache.v[l], H, KV, hd, n_bad=cache.errors)
+            self._kv_store(cache, l, b.qkv, dest)
             if split:
-                ops.attn_decode_split(b.qkv, cache.k[l], cache.v[l], slot, kv_len, b.att, None, H, KV, hd, n_bad=cache.errors, **split)
+                (ops.attn_decode_split_fp8 if fp8 else ops.attn_decode_split)(b.qkv, *cache.layer(l), slot, kv_len, b.att, None, H, KV, hd,
+                                                                               n_bad=cache.errors, **split)
             else:
-                ops.attn_decode(b.qkv, cache.k[l], cache.v[l], slot, kv_len, b.att, None, H, KV, hd, n_bad=cache.errors)
+                (ops.attn_decode_fp8 if fp8 else ops.attn_decode)(b.qkv, *cache.layer(l), slot, kv_len, b.att, None, H, KV, hd, n_bad=cache.errors)
 
         logits = self._head_logits(self._run_stack(mode, tok, R, 1, R, pos, attend)[1].xn1, skinny=small)   # R rows of one position each; RoPE by ``pos``
         cache.lengths.index_add_(0, slot.clamp(min=0).long(), write.to(torch.int32))
@@ -865,7 +898,7 @@ class HipLlamaDecoder(nn.Module):
         ``small_batch``: as in ``decode_step`` (unpadded rows, skinny GEMMs, ``*.s`` buffers, where ``takes_small_batch`` holds).
         ``split_kv``: as in ``decode_step`` (``attn_decode_beam_split`` in place of ``attn_decode_beam``, where ``takes_split_kv`` holds)."""
         self._check_cache(prompt_cache)
-        self._check_cache(beam_cache)
+        self._check_cache(beam_cache, beside=prompt_cache)
         n, t = tokens.numel(), int(t)
         if tokens.dim() != 1 or tokens.dtype != torch.int64 or any(x.shape != tokens.shape or x.dtype != torch.int32 for x in (prompt_slot, prompt_len)):
             raise ValueError("decode_step_beam: tokens is int64 [rows], prompt_slot and prompt_len int32 [rows]")
@@ -892,10 +925,15 @@ class HipLlamaDecoder(nn.Module):
         split = self._split_kv(mode, R, prompt_cache.cap + min(beam_cache.cap, anc.shape[1])) if self.takes_split_kv(n, split_kv) else None
 
         def attend(l: int, b: _LayerBufs) -> None:
-            ops.kv_store(b.qkv, dest, beam_cache.k[l], beam_cache.v[l], H, KV, hd, n_bad=beam_cache.errors)
-            (ops.attn_decode_beam_split if split else ops.attn_decode_beam)(
-                b.qkv, prompt_cache.k[l], prompt_cache.v[l], beam_cache.k[l], beam_cache.v[l], slot, plen, gen_len, anc_r, b.att, None, H, KV, hd,
-                n_bad=beam_cache.errors, **(split or {}))
+            self._kv_store(beam_cache, l, b.qkv, dest)
+            if beam_cache.dtype == "fp8":
+                (ops.attn_decode_beam_split_fp8 if split else ops.attn_decode_beam_fp8)(
+                    b.qkv, prompt_cache.layer(l), beam_cache.layer(l), slot, plen, gen_len, anc_r, b.att, None, H, KV, hd, n_bad=beam_cache.errors,
+                    **(split or {}))
+            else:
+                (ops.attn_decode_beam_split if split else ops.attn_decode_beam)(
+                    b.qkv, *prompt_cache.layer(l), *beam_cache.layer(l), slot, plen, gen_len, anc_r, b.att, None, H, KV, hd,
+                    n_bad=beam_cache.errors, **(split or {}))
 
         return self._head_logits(self._run_stack(mode, tok, R, 1, R, pos, attend)[1].xn1, skinny=small)[:n]
 

@@ -12,6 +12,7 @@ from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
 __all__ = ["gemm_skinny", "gemm_skinny_rope", "gemm_skinny_swiglu", "lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "attn_decode_beam", "attn_decode_split", "attn_decode_beam_split", "attn_decode_split_span", "attn_decode_split_workspace", "decode_select", "decode_sample", "decode_select_pen", "decode_sample_pen", "decode_penalty_lds_bytes", "topk_logprob", "swiglu_fwd",
            "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "ema_update", "set_impl", "set_attn_impl", "attn_last_dispatch",
+           "kv_store_fp8", "attn_decode_fp8", "attn_decode_beam_fp8", "attn_decode_split_fp8", "attn_decode_beam_split_fp8",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
 
@@ -200,6 +201,37 @@ def kv_store(qkv: Tensor, dest: Tensor, k_cache: Tensor, v_cache: Tensor, n_head
         raise _lib.HipLibraryError("kv_store: n_bad is one int32 on the device of qkv")
     check(_lib.load().ssi_kv_store(ptr(qkv), qkv.stride(0), ptr(dest), qkv.shape[0], k_cache.shape[0] * k_cache.shape[1], ptr(k_cache), ptr(v_cache),
                                    n_heads, n_kv, head_dim, ptr(n_bad), dtype_code(qkv.dtype), stream_ptr()), "ssi_kv_store")
+
+
+def _kv_fp8_ok(what: str, k_codes: Tensor, v_codes: Tensor, k_exp: Tensor, v_exp: Tensor, like: Tensor, n_kv: int, head_dim: int) -> None:
+    """One fp8 cache (the header's "FP8 K/V cache"): codes ``[n_slots, cap, n_kv * head_dim]`` and exponent bytes ``[n_slots, cap, n_kv]``, uint8,
+    contiguous, on the device of ``like``; refused before the library is loaded."""
+    for name, t, last in (("k_codes", k_codes, n_kv * head_dim), ("v_codes", v_codes, n_kv * head_dim), ("k_exp", k_exp, n_kv), ("v_exp", v_exp, n_kv)):
+        if not isinstance(t, Tensor) or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != last or not t.is_contiguous() or t.device != like.device:
+            got = (tuple(t.shape), t.dtype, t.device) if isinstance(t, Tensor) else type(t).__name__
+            raise _lib.HipLibraryError(f"{what}: {name} is a contiguous uint8 [n_slots, cap, {last}] tensor on the device of qkv (got {got})")
+    if k_codes.shape != v_codes.shape or k_exp.shape != v_exp.shape or k_exp.shape[:2] != k_codes.shape[:2]:
+        raise _lib.HipLibraryError(f"{what}: codes {tuple(k_codes.shape)} / {tuple(v_codes.shape)} and exponents {tuple(k_exp.shape)} / "
+                                   f"{tuple(v_exp.shape)} are not one cache")
+
+
+def kv_store_fp8(qkv: Tensor, dest: Tensor, k_codes: Tensor, v_codes: Tensor, k_exp: Tensor, v_exp: Tensor, n_heads: int, n_kv: int, head_dim: int,
+                 n_bad: Tensor | None = None) -> None:
+    """``kv_store`` into an fp8 cache: every line (one kv head of k or of v of a row) as ``head_dim`` e4m3 codes and one exponent byte, by the
+    header's definition; ``dest`` and ``n_bad`` as there.  ``ssi_kv_store_fp8``."""
+    if not isinstance(qkv, Tensor) or qkv.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.HipLibraryError("kv_store_fp8: qkv is an fp32 or bf16 tensor")
+    _kv_fp8_ok("kv_store_fp8", k_codes, v_codes, k_exp, v_exp, qkv, n_kv, head_dim)
+    ptr(qkv)
+    if qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] < (n_heads + 2 * n_kv) * head_dim:
+        raise _lib.HipLibraryError(f"kv_store_fp8: qkv must be [rows, >= {(n_heads + 2 * n_kv) * head_dim}] with unit inner stride (got {tuple(qkv.shape)})")
+    if dest.dtype != torch.int64 or not dest.is_contiguous() or dest.numel() != qkv.shape[0] or dest.device != qkv.device:
+        raise _lib.HipLibraryError("kv_store_fp8: dest is one int64 per row of qkv, on its device")
+    if n_bad is not None and (n_bad.dtype != torch.int32 or n_bad.numel() != 1 or n_bad.device != qkv.device):
+        raise _lib.HipLibraryError("kv_store_fp8: n_bad is one int32 on the device of qkv")
+    check(_lib.load().ssi_kv_store_fp8(ptr(qkv), qkv.stride(0), ptr(dest), qkv.shape[0], k_codes.shape[0] * k_codes.shape[1], ptr(k_codes), ptr(v_codes),
+                                       ptr(k_exp), ptr(v_exp), n_heads, n_kv, head_dim, ptr(n_bad), dtype_code(qkv.dtype), stream_ptr()),
+          "ssi_kv_store_fp8")
 
 
 def _decode_rows(what: str, qkv: Tensor, int32_rows, out: Tensor, lse: Tensor | None, n_heads: int, head_dim: int, n_bad: Tensor | None) -> int:
@@ -442,6 +474,71 @@ def attn_decode_beam_split(qkv: Tensor, pk_cache: Tensor, pv_cache: Tensor, bk_c
     keys = pk_cache.shape[1] + min(bk_cache.shape[1], anc.shape[1])
     check(_lib.load().ssi_attn_decode_beam_split(*args, int(span), max(_cdiv(keys, int(span)), 1), ptr(workspace), workspace.numel() * 4,
                                                  dtype_code(qkv.dtype), stream_ptr()), "ssi_attn_decode_beam_split")
+
+
+def _slot_args_fp8(what: str, qkv: Tensor, cache, slot: Tensor, kv_len: Tensor, out: Tensor, lse: Tensor | None, n_heads: int, n_kv: int,
+                   head_dim: int, n_bad: Tensor | None) -> tuple:
+    """``_slot_args`` for an fp8 cache ``(k_codes, v_codes, k_exp, v_exp)``."""
+    if not isinstance(qkv, Tensor) or qkv.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.HipLibraryError(f"{what}: qkv is an fp32 or bf16 tensor")
+    _kv_fp8_ok(what, *cache, qkv, n_kv, head_dim)
+    rows = _decode_rows(what, qkv, (("slot", slot), ("kv_len", kv_len)), out, lse, n_heads, head_dim, n_bad)
+    return (ptr(qkv), qkv.stride(0), *(ptr(t) for t in cache), cache[0].shape[0], cache[0].shape[1], ptr(slot), ptr(kv_len), ptr(out), ptr(lse),
+            rows, n_heads, n_kv, head_dim, ptr(n_bad))
+
+
+def _beam_args_fp8(what: str, qkv: Tensor, pcache, bcache, prompt_slot: Tensor, prompt_len: Tensor, gen_len: Tensor, anc: Tensor, out: Tensor,
+                   lse: Tensor | None, n_heads: int, n_kv: int, head_dim: int, n_bad: Tensor | None) -> tuple:
+    """``_beam_args`` for an fp8 prompt cache and an fp8 beam cache, each ``(k_codes, v_codes, k_exp, v_exp)``."""
+    if not isinstance(qkv, Tensor) or qkv.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.HipLibraryError(f"{what}: qkv is an fp32 or bf16 tensor")
+    _kv_fp8_ok(what, *pcache, qkv, n_kv, head_dim)
+    _kv_fp8_ok(what, *bcache, qkv, n_kv, head_dim)
+    rows = _decode_rows(what, qkv, (("prompt_slot", prompt_slot), ("prompt_len", prompt_len), ("gen_len", gen_len)), out, lse, n_heads, head_dim, n_bad)
+    if anc.dtype != torch.int32 or anc.dim() != 2 or anc.shape[0] != rows or not anc.is_contiguous() or anc.device != qkv.device:
+        raise _lib.HipLibraryError(f"{what}: anc is a contiguous int32 [rows, ld_anc] tensor on the device of qkv")
+    return (ptr(qkv), qkv.stride(0), *(ptr(t) for t in pcache), pcache[0].shape[0], pcache[0].shape[1], *(ptr(t) for t in bcache),
+            bcache[0].shape[0], bcache[0].shape[1], ptr(prompt_slot), ptr(prompt_len), ptr(gen_len), ptr(anc), anc.shape[1], ptr(out), ptr(lse),
+            rows, n_heads, n_kv, head_dim, ptr(n_bad))
+
+
+def attn_decode_fp8(qkv: Tensor, k_codes: Tensor, v_codes: Tensor, k_exp: Tensor, v_exp: Tensor, slot: Tensor, kv_len: Tensor, out: Tensor,
+                    lse: Tensor | None, n_heads: int, n_kv: int, head_dim: int, n_bad: Tensor | None = None) -> None:
+    """``attn_decode`` over an fp8 cache (uint8 codes ``[n_slots, cap, n_kv * head_dim]``, exponent bytes ``[n_slots, cap, n_kv]``).
+    ``ssi_attn_decode_fp8``: bit-equal to ``attn_decode`` on a cache that holds the dequantised values in the dtype of ``qkv``."""
+    args = _slot_args_fp8("attn_decode_fp8", qkv, (k_codes, v_codes, k_exp, v_exp), slot, kv_len, out, lse, n_heads, n_kv, head_dim, n_bad)
+    check(_lib.load().ssi_attn_decode_fp8(*args, dtype_code(qkv.dtype), stream_ptr()), "ssi_attn_decode_fp8")
+
+
+def attn_decode_split_fp8(qkv: Tensor, k_codes: Tensor, v_codes: Tensor, k_exp: Tensor, v_exp: Tensor, slot: Tensor, kv_len: Tensor, out: Tensor,
+                          lse: Tensor | None, n_heads: int, n_kv: int, head_dim: int, *, span: int, workspace: Tensor,
+                          n_bad: Tensor | None = None) -> None:
+    """``attn_decode_split`` over an fp8 cache; span, splits and workspace as there.  ``ssi_attn_decode_split_fp8``."""
+    _split_workspace("attn_decode_split_fp8", qkv, workspace, span)
+    args = _slot_args_fp8("attn_decode_split_fp8", qkv, (k_codes, v_codes, k_exp, v_exp), slot, kv_len, out, lse, n_heads, n_kv, head_dim, n_bad)
+    check(_lib.load().ssi_attn_decode_split_fp8(*args, int(span), max(_cdiv(k_codes.shape[1], int(span)), 1), ptr(workspace), workspace.numel() * 4,
+                                                dtype_code(qkv.dtype), stream_ptr()), "ssi_attn_decode_split_fp8")
+
+
+def attn_decode_beam_fp8(qkv: Tensor, prompt_cache, beam_cache, prompt_slot: Tensor, prompt_len: Tensor, gen_len: Tensor, anc: Tensor, out: Tensor,
+                         lse: Tensor | None, n_heads: int, n_kv: int, head_dim: int, n_bad: Tensor | None = None) -> None:
+    """``attn_decode_beam`` over an fp8 prompt cache and an fp8 beam cache, each a ``(k_codes, v_codes, k_exp, v_exp)`` tuple.
+    ``ssi_attn_decode_beam_fp8``."""
+    args = _beam_args_fp8("attn_decode_beam_fp8", qkv, tuple(prompt_cache), tuple(beam_cache), prompt_slot, prompt_len, gen_len, anc, out, lse,
+                          n_heads, n_kv, head_dim, n_bad)
+    check(_lib.load().ssi_attn_decode_beam_fp8(*args, dtype_code(qkv.dtype), stream_ptr()), "ssi_attn_decode_beam_fp8")
+
+
+def attn_decode_beam_split_fp8(qkv: Tensor, prompt_cache, beam_cache, prompt_slot: Tensor, prompt_len: Tensor, gen_len: Tensor, anc: Tensor,
+                               out: Tensor, lse: Tensor | None, n_heads: int, n_kv: int, head_dim: int, *, span: int, workspace: Tensor,
+                               n_bad: Tensor | None = None) -> None:
+    """``attn_decode_beam_split`` over fp8 caches (tuples as in ``attn_decode_beam_fp8``).  ``ssi_attn_decode_beam_split_fp8``."""
+    _split_workspace("attn_decode_beam_split_fp8", qkv, workspace, span)
+    pc, bc = tuple(prompt_cache), tuple(beam_cache)
+    args = _beam_args_fp8("attn_decode_beam_split_fp8", qkv, pc, bc, prompt_slot, prompt_len, gen_len, anc, out, lse, n_heads, n_kv, head_dim, n_bad)
+    keys = pc[0].shape[1] + min(bc[0].shape[1], anc.shape[1])
+    check(_lib.load().ssi_attn_decode_beam_split_fp8(*args, int(span), max(_cdiv(keys, int(span)), 1), ptr(workspace), workspace.numel() * 4,
+                                                     dtype_code(qkv.dtype), stream_ptr()), "ssi_attn_decode_beam_split_fp8")
 
 
 def topk_logprob(logits: Tensor, vocab: int, k: int, idx: Tensor, lp: Tensor, lse: Tensor | None = None, *, mask: Tensor | None = None) -> None:

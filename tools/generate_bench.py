@@ -1,5 +1,5 @@
 """What greedy generation costs at the 1B shape (Llama-3.2-1B + 5000 DSUs, bf16, random weights): 256 prompts of about 1000 tokens, 256 new
-tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained|beam|sample|penalty|small_batch|split_kv] [--json profiles/generate.json]
+tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained|beam|sample|penalty|small_batch|split_kv|kv_fp8] [--json profiles/generate.json]
 
 run        prefill time, milliseconds per decode step (event time over all steps, host gaps included), generated tokens per second, and a
            self-check: the first generated token of every prompt against the argmax of a plain full forward of that prompt alone (with
@@ -43,6 +43,11 @@ split_kv   (not part of ``all``; python tools/generate_bench.py --part split_kv 
            at spans of 64 to 512 keys (rows 1 to 256, 256 / 1000 / 4000 keys, every layer's caches in turn; the beam pair at 8 rows), whole
            ``decode_step``s with and without ``split_kv``, ``generate`` and ``sample`` end to end — and the two choices the numbers make by rule: the
            default span and ``split_max_rows``.
+kv_fp8     (not part of ``all``; python tools/generate_bench.py --part kv_fp8 --json profiles/generate_kv_fp8.json) what the FP8 K/V cache buys and
+           costs, ONE process, the forms alternating: per launch ``ssi_attn_decode_fp8`` against ``ssi_attn_decode`` (1 / 8 / 64 / 256 rows x 1000 and
+           4000 keys, every layer's caches in turn), the two stores at 256 rows, the beam pair at 64 x 4; whole ``decode_step``s at 256 rows and the
+           small-batch step at 1 and 8 rows; ``generate`` end to end; and, recorded and not asserted, the share of greedy tokens equal between the two
+           caches and the largest teacher-forced logit difference (random weights: nothing about a trained checkpoint).
 """
 import argparse, csv, glob, json, os, statistics, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,7 +55,7 @@ PKG = os.path.join(ROOT, 'speech-integration_amd')
 sys.path.insert(0, PKG)
 
 ap = argparse.ArgumentParser()
-ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained', 'beam', 'sample', 'penalty', 'small_batch', 'small_batch_steps', 'split_kv'])
+ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained', 'beam', 'sample', 'penalty', 'small_batch', 'small_batch_steps', 'split_kv', 'kv_fp8'])
 ap.add_argument('--rows', type=int, default=1, help='small_batch_steps: rows of the traced steps')
 ap.add_argument('--prompts', type=int, default=256)
 ap.add_argument('--penalty-generated', type=int, default=128, help='penalty: generated tokens in every row\'s history')
@@ -791,13 +796,13 @@ def part_penalty():
 SMALL_ROWS = (1, 8, 16, 32, 64)
 
 
-def _small_cache(model, rows, room=4096):
+def _small_cache(model, rows, room=4096, dtype=None):
     """A cache of ``rows`` prompts of about --prompt-len tokens, prefilled, with ``room`` positions for the measured steps."""
     import torch
     g = torch.Generator().manual_seed(1)
     lens = torch.randint(args.prompt_len - 100, args.prompt_len + 101, (rows,), generator=g).tolist()
     prompts = [torch.randint(0, model.vocab_size, (n,), generator=g) for n in lens]
-    cache = model.new_kv_cache(rows, max(lens) + room)
+    cache = model.new_kv_cache(rows, max(lens) + room, dtype)
     model.prefill(cache, prompts)
     return cache, lens
 
@@ -1132,6 +1137,161 @@ def part_split_kv():
     return res
 
 
+def part_kv_fp8():
+    """FP8 K/V cache against the cache in the model's dtype: per launch, per step, end to end, and what it does to the values."""
+    import torch
+    from ssi import ops
+    from ssi.generate import generate
+    model = build_model()
+    L, H, KV, hd = model.num_layers, model.num_heads, model.num_kv_heads, model.head_dim
+    dev, bf, u8 = dict(device='cuda'), torch.bfloat16, torch.uint8
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(reps):
+            fn(i)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3        # us per call
+
+    def rounds_of(forms, reps):
+        for fn in forms.values():
+            timed(fn, 4)
+        got = {k: [] for k in forms}
+        for _ in range(args.rounds):
+            for k, fn in forms.items():
+                got[k].append(timed(fn, reps))
+        return {k: spread(v) for k, v in got.items()}
+
+    def verdict(e, plain, fp8):
+        """fp8 is faster than the plain form by more than the plain form's own min..max spread?"""
+        e['plain_over_fp8'] = round(e[plain]['median'] / e[fp8]['median'], 3)
+        e['plain_spread'] = round(e[plain]['max'] - e[plain]['min'], 3)
+        e['fp8_wins_by_more_than_the_plain_spread'] = bool(e[plain]['median'] - e[fp8]['median'] > e['plain_spread'])
+        return e
+
+    res = {'geometry': f'1B shape (32 / 8 / 64), bf16; {args.rounds} rounds alternating the forms in one process, median (min - max); per launch call i reads '
+                       f'layer i % {L}\'s caches',
+           'hbm_TB_per_s_of_the_adamw_and_ema_passes': list(HBM_TB_S),
+           'plain_form': 'measured on THIS build; that it stands for the parent\'s is an inference from tools/kernel_lint.py --against the parent build '
+                         '(same registers or fewer, instruction counts within 2.5 %, mostly fewer), not a measurement of the parent'}
+    with torch.inference_mode():
+        g = torch.Generator(device='cuda').manual_seed(11)
+        R, cap = 256, 4000
+        kc = torch.empty((L, R, cap, KV * hd), dtype=bf, **dev).normal_(generator=g)
+        vc = torch.empty((L, R, cap, KV * hd), dtype=bf, **dev).normal_(generator=g)
+        qc, qe = torch.empty((2, L, R, cap, KV * hd), dtype=u8, **dev), torch.empty((2, L, R, cap, KV), dtype=u8, **dev)
+        for w in range(2):
+            for l in range(L):
+                qc[w, l].random_(0, 0x7e, generator=g)                                                # any finite code
+                qe[w, l].random_(118, 128, generator=g)
+        qkv = torch.randn(R, (H + 2 * KV) * hd, generator=g, **dev).to(bf)
+        out = torch.empty((R, H * hd), dtype=bf, **dev)
+        slot = torch.arange(R, dtype=torch.int32, **dev)
+        per = {}
+        for rows in (1, 8, 64, 256):
+            for keys in (1000, 4000):
+                kv_len = torch.full((rows,), keys, dtype=torch.int32, **dev)
+                q, o, sl = qkv[:rows], out[:rows], slot[:rows]
+                forms = {'plain_us': lambda i: ops.attn_decode(q, kc[i % L], vc[i % L], sl, kv_len, o, None, H, KV, hd),
+                         'fp8_us': lambda i: ops.attn_decode_fp8(q, qc[0, i % L], qc[1, i % L], qe[0, i % L], qe[1, i % L], sl, kv_len, o, None, H, KV, hd)}
+                e = verdict(rounds_of(forms, 32), 'plain_us', 'fp8_us')
+                e['cache_MB_read'] = {'plain': round(rows * keys * 2 * KV * hd * 2 / 1e6, 2), 'fp8': round(rows * keys * 2 * KV * (hd + 1) / 1e6, 2)}
+                e['TB_per_s'] = {k: round(e['cache_MB_read'][k] / 1e6 / (e[k + '_us']['median'] * 1e-6), 3) for k in ('plain', 'fp8')}
+                per[f'rows_{rows}_keys_{keys}'] = e
+        res['per_launch_attention'] = per
+        # the store at 256 rows: one position of every slot
+        dest = (torch.arange(R, dtype=torch.int64, **dev) * cap + 17).contiguous()
+        forms = {'plain_us': lambda i: ops.kv_store(qkv, dest, kc[i % L], vc[i % L], H, KV, hd),
+                 'fp8_us': lambda i: ops.kv_store_fp8(qkv, dest, qc[0, i % L], qc[1, i % L], qe[0, i % L], qe[1, i % L], H, KV, hd)}
+        res['per_launch_store_256_rows'] = verdict(rounds_of(forms, 32), 'plain_us', 'fp8_us')
+        # the beam pair at 64 prompts x 4 beams: --prompt-len prompt keys, 128 generated positions read through a random ancestry
+        P, W, t_mid = 64, 4, 128
+        anc = torch.randint(0, P * W, (P * W, t_mid + 1), generator=g, **dev).to(torch.int32).contiguous()
+        pslot = (torch.arange(P * W, dtype=torch.int32, **dev) // W).contiguous()
+        plen, glen = torch.full((P * W,), args.prompt_len, dtype=torch.int32, **dev), torch.full((P * W,), t_mid, dtype=torch.int32, **dev)
+        bk, bv = kc[:, :, :t_mid + 1].contiguous(), vc[:, :, :t_mid + 1].contiguous()
+        bqc, bqe = qc[:, :, :, :t_mid + 1].contiguous(), qe[:, :, :, :t_mid + 1].contiguous()
+        forms = {'plain_us': lambda i: ops.attn_decode_beam(qkv, kc[i % L, :P], vc[i % L, :P], bk[i % L], bv[i % L], pslot, plen, glen, anc, out, None, H, KV, hd),
+                 'fp8_us': lambda i: ops.attn_decode_beam_fp8(qkv, (qc[0, i % L, :P], qc[1, i % L, :P], qe[0, i % L, :P], qe[1, i % L, :P]),
+                                                               (bqc[0, i % L], bqc[1, i % L], bqe[0, i % L], bqe[1, i % L]), pslot, plen, glen, anc, out,
+                                                               None, H, KV, hd)}
+        res['per_launch_beam_64x4'] = dict(verdict(rounds_of(forms, 32), 'plain_us', 'fp8_us'), prompt_keys=args.prompt_len, generated_keys=t_mid)
+        del kc, vc, qc, qe, bk, bv, bqc, bqe
+        torch.cuda.empty_cache()
+
+        # whole steps: the same prompts in a plain and an fp8 cache (the lengths are put back before every block of steps)
+        steps, st, fidelity = 16, {}, {}
+        for m_rows, small in ((256, False), (1, True), (8, True)):
+            caches = {'plain_ms': _small_cache(model, m_rows, room=64)[0], 'fp8_ms': _small_cache(model, m_rows, room=64, dtype='fp8')[0]}
+            start = caches['plain_ms'].lengths.clone()
+            tok = torch.randint(0, model.vocab_size, (m_rows,), **dev)
+            sl = torch.arange(m_rows, dtype=torch.int32, **dev)
+
+            def block(which, keep=None):
+                cache = caches[which]
+                cache.lengths.copy_(start)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    logits = model.decode_step(cache, tok, sl, small_batch=small)
+                    if keep is not None:
+                        keep.append(logits[:, :model.vocab_size].float())
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / steps * 1e3      # ms per step, host clock: what a loop sees
+
+            kept = {k: [] for k in caches}
+            for k in caches:
+                block(k, kept[k])
+            if m_rows == 256:       # teacher-forced: both caches took the same prompts and the same tokens
+                absmax = max(float(x.abs().max()) for x in kept['plain_ms'])
+                worst = max(float((a - b).abs().max()) for a, b in zip(kept['plain_ms'], kept['fp8_ms']))
+                fidelity['teacher_forced'] = {'steps': steps, 'rows': m_rows, 'max_abs_dlogit': round(worst, 4), 'logits_absmax': round(absmax, 4),
+                                              'max_abs_dlogit_over_logits_absmax': round(worst / absmax, 5)}
+            del kept
+            rounds = {k: [] for k in caches}
+            for _ in range(args.rounds):
+                for k in caches:
+                    rounds[k].append(block(k))
+            e = verdict({k: spread(v, 3) for k, v in rounds.items()}, 'plain_ms', 'fp8_ms')
+            e['cache_bytes'] = {k: sum(t.numel() * t.element_size() for t in (c.k, c.v, c.k_exp, c.v_exp) if t is not None) for k, c in caches.items()}
+            st[f'rows_{m_rows}' + ('_small_batch' if small else '')] = e
+            del caches
+            torch.cuda.empty_cache()
+        res['per_step'] = dict(st, note=f'{steps} decode steps a block on prompts of about {args.prompt_len} tokens, host clock')
+
+    # end to end: generate of --prompts prompts with --new new tokens; the caches are opened (and their bytes allocated) inside the call
+    prompts = make_prompts(model.vocab_size)
+    found = {}
+
+    def run(dtype):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        found[dtype] = generate(model, prompts, max_new_tokens=args.new, stop_token_ids=[], pad_id=0, kv_cache_dtype=dtype)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    run('auto'), run('fp8')
+    rounds = {'plain_ms': [], 'fp8_ms': []}
+    for _ in range(args.rounds):
+        rounds['plain_ms'].append(run('auto'))
+        rounds['fp8_ms'].append(run('fp8'))
+    e = verdict({k: spread(v, 1) for k, v in rounds.items()}, 'plain_ms', 'fp8_ms')
+    cap = max(p.numel() for p in prompts) + args.new
+    e['cache_GB'] = {'plain': round(2 * L * args.prompts * cap * KV * hd * 2 / 1e9, 2), 'fp8': round(2 * L * args.prompts * cap * KV * (hd + 1) / 1e9, 2)}
+    res['end_to_end_generate'] = dict(e, prompts=args.prompts, new_tokens=args.new, note='host clock around the whole call, prefill and cache allocation included')
+    same = [sum(a == b for a, b in zip(x.token_ids, y.token_ids)) for x, y in zip(found['auto'], found['fp8'])]
+    prefix = [next((i for i, (a, b) in enumerate(zip(x.token_ids, y.token_ids)) if a != b), len(x.token_ids)) for x, y in zip(found['auto'], found['fp8'])]
+    fidelity['greedy'] = {'new_tokens': args.new, 'share_of_tokens_equal_position_by_position': round(sum(same) / (len(same) * args.new), 4),
+                          'mean_tokens_before_the_first_difference': round(sum(prefix) / len(prefix), 1),
+                          'prompts_equal_throughout': sum(p == args.new for p in prefix)}
+    res['fidelity'] = dict(fidelity, note='recorded, not asserted.  The weights are random (normal, 0.02): next-token distributions are nearly flat, so a '
+                                          'greedy path flips on small changes.  Nothing here says anything about WER on a trained checkpoint.')
+    print(json.dumps(res, indent=1))
+    return res
+
+
 def part_small_batch_steps():
     """--trace-steps small-batch decode steps of --rows rows, for a kernel trace in a run of its own."""
     import torch
@@ -1175,6 +1335,8 @@ elif args.part == 'small_batch':
     res = part_small_batch()
 elif args.part == 'split_kv':
     res = part_split_kv()
+elif args.part == 'kv_fp8':
+    res = part_kv_fp8()
 elif args.part == 'small_batch_steps':
     part_small_batch_steps()
     res = None
