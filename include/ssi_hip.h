@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 26 /* 26: + ssi_kv_store_fp8, ssi_attn_decode_fp8, ssi_attn_decode_beam_fp8, ssi_attn_decode_split_fp8, ssi_attn_decode_beam_split_fp8 (a K/V cache of e4m3 codes with one power-of-two exponent per line, and decode attention over it; opt-in)
+#define SSI_ABI_VERSION 27 /* 27: + ssi_weight_quant_fp8, ssi_gemm_skinny_w8, ssi_gemm_skinny_rope_w8, ssi_gemm_skinny_swiglu_w8 (weight matrices as e4m3 codes with one power-of-two exponent per row, and the skinny GEMMs over them: FP8 weights for small-batch decoding; opt-in)
+                           * 26: + ssi_kv_store_fp8, ssi_attn_decode_fp8, ssi_attn_decode_beam_fp8, ssi_attn_decode_split_fp8, ssi_attn_decode_beam_split_fp8 (a K/V cache of e4m3 codes with one power-of-two exponent per line, and decode attention over it; opt-in)
                            * 25: + ssi_attn_decode_split, ssi_attn_decode_beam_split, ssi_attn_decode_split_span, ssi_attn_decode_split_workspace (split-KV decode attention: the keys of a row over several workgroups, a merge launch behind them; opt-in)
                            * 24: + ssi_gemm_skinny, ssi_gemm_skinny_rope, ssi_gemm_skinny_swiglu (weight-streaming bf16 GEMMs for 1 to 64 rows: small-batch decoding; opt-in)
                            * 23: + ssi_sumsq_groups, ssi_adamw_step_seg_gscale (per-group gradient norms of the flat buffer in one pass, a per-segment device gradient scale in the segmented AdamW; opt-in)
@@ -535,6 +536,36 @@ int ssi_gemm_skinny_rope(int64_t M, int64_t N, int64_t K, const void* A, int64_t
                          void* stream);
 int ssi_gemm_skinny_swiglu(int64_t M, int64_t inter, int64_t K, const void* X, int64_t ldx, const void* W13, int64_t ldw, void* GU,
                            int64_t ldgu, void* ACT, int64_t ldact, int dtype, void* stream);
+
+/* ---- FP8 weights (ABI v27; vLLM's quantization="fp8" is what the reference's users would reach for; small-batch decoding only; opt-in, it
+ * changes values) ----------------------------------------------------------------------------------------------------------------------------
+ * THE DEFINITION is the "FP8 K/V cache" rule above with "line" read as ROW OF A WEIGHT MATRIX W[N, K], the K elements of one output channel:
+ * K e4m3fn codes and one biased exponent byte b per row, the exponent, the codes and the value of a code exactly as that section says (and as
+ * one copy of device code, csrc/q8_codes.h, computes them for both).  Storage: codes uint8 [N, ld_codes] (rows on 16-byte boundaries),
+ * exps uint8 [N] (no alignment).  A dequantised weight has four significant bits, so it is EXACTLY a bf16 number whenever it is a normal bf16
+ * number or zero; rows whose non-zero values fall below the bf16 normal range (2^-126) are outside the guarantee below.
+ *
+ * ssi_weight_quant_fp8: bf16 W[N, K] at ldw -> codes, exps.  One wave per row: a pass for the row's absmax, a pass (from L2) for the codes.
+ * Nothing behind column K of a code row is written.  SSI_ERR_UNSUPPORTED: dtype != SSI_BF16, K % 64; SSI_ERR_ARG: a null pointer, a leading
+ * dimension below K, rows of W or of the codes off 16-byte boundaries.  N == 0 launches nothing.
+ *
+ * ssi_gemm_skinny_w8, ssi_gemm_skinny_rope_w8 and ssi_gemm_skinny_swiglu_w8 are the three skinny entries with (codes, ld_codes, exps) where
+ * those take (W, ldw); every other argument, the epilogues' rounding points, the refusals (ld_codes in place of ldw: >= K, 16-byte rows) and
+ * "row r has the same bits whatever M is" are unchanged.  THE CONTRACT: the output is BIT-EQUAL to the matching plain entry called on the
+ * dequantised matrix stored as bf16.  So the k of a lane slot, the wave of a 64-wide chunk, the order of the matrix instructions within a wave
+ * and the LDS merge are skinny_kernel's (the merge and the epilogues are the same code); a lane's 16 codes of a chunk and row come in ONE 16-byte
+ * load and become the two bf16x8 operands by v_cvt_pk_f32_fp8, v_ldexp_f32 and v_cvt_pk_bf16_f32, all exact: the row's exponent is applied AT
+ * THE CONVERSION, not to the fp32 sums.  Free, and used: two of a wave's chunks are in flight, which keeps the bf16 kernel's bytes in flight
+ * per lane.  exps is read at rows [0, N) only (SwiGLU: [0, 2 I)).  Forms: 12, as skinny_kernel's; no scratch.  The bf16 weights are not
+ * freed by anything here, and prefill and the 256-row tile path never read the codes. */
+int ssi_weight_quant_fp8(const void* W, int64_t ldw, int64_t N, int64_t K, void* codes, int64_t ld_codes, void* exps, int dtype, void* stream);
+int ssi_gemm_skinny_w8(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* codes, int64_t ld_codes, const void* exps,
+                       void* C, int64_t ldc, const void* R, int dtype, void* stream);
+int ssi_gemm_skinny_rope_w8(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* codes, int64_t ld_codes, const void* exps,
+                            void* C, int64_t ldc, int n_heads_rot, int head_dim, const float* rope_table, int64_t table_len,
+                            const int32_t* positions, int dtype, void* stream);
+int ssi_gemm_skinny_swiglu_w8(int64_t M, int64_t inter, int64_t K, const void* X, int64_t ldx, const void* codes13, int64_t ld_codes,
+                              const void* exps13, void* GU, int64_t ldgu, void* ACT, int64_t ldact, int dtype, void* stream);
 
 /* dst[c][r] = src[r][c] for a [rows, cols] matrix (both dims multiples of 8).  Keeps [in, out] copies of the projection
  * weights so that the data-gradient GEMMs use the k-contiguous operand form (refreshed once per optimizer step). */

@@ -7,6 +7,7 @@
 // The *_fp8 entries (ABI v26) keep it as e4m3 codes with one power-of-two exponent byte per (position, kv head) instead (the header's "FP8 K/V
 // cache"): ssi_kv_store_fp8 quantises, and the four attention entries run the same walk with a storage policy that hands it dequantised values.
 #include "common_hip.h"
+#include "q8_codes.h"
 #include <math.h>
 
 namespace {
@@ -71,35 +72,17 @@ __global__ __launch_bounds__(256) void q8_store_kernel(const T* __restrict__ qkv
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
         f[v] = x.get(v);
-        const uint32_t m = __float_as_uint(f[v]) & 0x7fffffffu;
-        a = m < 0x7f800000u && m > a ? m : a;
+        a = q8_absmax_bits(a, f[v]);
     }
     for (int o = 1 << lpk_log2 >> 1; o > 0; o >>= 1) {
         const uint32_t other = (uint32_t)__shfl_xor((int)a, o, 64);
         a = other > a ? other : a;
     }
-    // a = m * 2^E, m in [1, 2): e = E - 8, or E - 7 where m > 1.75, and b = max(e, -127) + 127 from a's exponent field E + 127 (a subnormal a,
-    // field 0, has E - 7 < -127: b = 0 as the formula gives it; e <= 120 never meets the upper clamp)
-    int b = (int)(a >> 23) - 8 + ((a & 0x7fffffu) > 0x600000u ? 1 : 0);
-    b = a == 0 ? 127 : b < 0 ? 0 : b;
+    const int b = q8_exponent_byte(a);
     if (!active) return;
     uint32_t w[WORDS];
 #pragma unroll
-    for (int k = 0; k < WORDS; ++k) {
-        float s[4];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) s[v] = ldexpf(f[4 * k + v], 127 - b);
-        int p = 0;
-        p = __builtin_amdgcn_cvt_pk_fp8_f32(s[0], s[1], p, false);
-        p = __builtin_amdgcn_cvt_pk_fp8_f32(s[2], s[3], p, true);
-        uint32_t u = (uint32_t)p;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {                     // a NaN or an infinity: the NaN code 0x7f, whatever the conversion makes of it
-            const bool finite = (__float_as_uint(f[4 * k + v]) & 0x7fffffffu) < 0x7f800000u;
-            u = finite ? u : (u & ~(0xffu << (8 * v))) | (0x7fu << (8 * v));
-        }
-        w[k] = u;
-    }
+    for (int k = 0; k < WORDS; ++k) w[k] = q8_encode4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3], b);
     const bool is_k = c < n_kv;
     const int64_t at = d * n_kv + (is_k ? c : c - n_kv);
     uint8_t* dst = (is_k ? kc : vc) + at * hd + col;
@@ -384,13 +367,7 @@ struct Q8Lines {
     static __device__ __forceinline__ void unpack(const Raw& x, float (&f)[VEC]) {
         const int e = (int)x.b - 127;
 #pragma unroll
-        for (int w = 0; w < WORDS; ++w) {
-            const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)x.c[w], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)x.c[w], true);
-            f[4 * w + 0] = ldexpf(lo[0], e);
-            f[4 * w + 1] = ldexpf(lo[1], e);
-            f[4 * w + 2] = ldexpf(hi[0], e);
-            f[4 * w + 3] = ldexpf(hi[1], e);
-        }
+        for (int w = 0; w < WORDS; ++w) q8_decode4(x.c[w], e, f + 4 * w);
     }
 };
 template <typename T>

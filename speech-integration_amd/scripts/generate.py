@@ -15,7 +15,7 @@ try:  # real Hydra if the environment has it, else the built-in composer with th
 except ImportError:
     from ssi.config import main as main_decorator
 
-from ssi.generate import check_greedy, check_kv_cache_dtype, check_penalties, check_sampling, generate_file
+from ssi.generate import check_greedy, check_kv_cache_dtype, check_penalties, check_weight_dtype, check_sampling, generate_file
 
 LOGGER = logging.getLogger(__name__)
 
@@ -90,6 +90,8 @@ def main(cfg):
         constraints["split_kv"] = True
     if check_kv_cache_dtype(cfg.gen.get("kv_cache_dtype")) is not None:   # gen.kv_cache_dtype: fp8; auto (or the key absent) is absent from the call
         constraints["kv_cache_dtype"] = "fp8"
+    if check_weight_dtype(cfg.gen.get("weight_dtype"), bool(cfg.gen.get("small_batch") or False)) is not None:   # gen.weight_dtype: fp8 (needs gen.small_batch); auto (or the key absent) is absent from the call
+        constraints["weight_dtype"] = "fp8"
     summary = generate_file(t.model, t.tokenizer, None if prompts is not None else str(cfg.gen.input), out_path,
                             max_new_tokens=int(cfg.sampling_params.max_tokens), stop_token_ids=None if stop is None else [int(s) for s in stop],
                             tokenizer_decoding={k: cfg.tokenizer_decoding[k] for k in cfg.tokenizer_decoding}, prompts=prompts, ids=ids,

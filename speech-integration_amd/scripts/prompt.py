@@ -38,6 +38,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--split-kv", action="store_true", help="split-KV decode attention: the keys of a row over several workgroups (long prompts)")
     p.add_argument("--kv-cache-dtype", choices=("auto", "fp8"), default="auto",
                    help="fp8: the K/V cache as e4m3 codes with one power-of-two scale per cached line (changes values); auto: the model's dtype")
+    p.add_argument("--weight-dtype", choices=("auto", "fp8"), default="auto",
+                   help="fp8: the decode steps read the projection weights and the head as e4m3 codes with one power-of-two scale per output "
+                        "channel, quantised once (changes values); auto: the model's weights")
     p.add_argument("--jsonl", metavar="OUT", help="also write one record per prompt (the generations file's line format)")
     return p
 
@@ -106,7 +109,7 @@ def main(argv=None) -> int:
     found = probe(model, tokenizer, prompts, max_new_tokens=args.max_new_tokens, n=args.n, temperature=args.temperature, top_k=args.top_k,
                   top_p=args.top_p, seed=args.seed, repetition_penalty=args.repetition_penalty, frequency_penalty=args.frequency_penalty,
                   presence_penalty=args.presence_penalty, tokenizer_decoding=decoding, split_kv=args.split_kv,
-                  kv_cache_dtype=args.kv_cache_dtype)
+                  kv_cache_dtype=args.kv_cache_dtype, weight_dtype=args.weight_dtype)
     for p in found:
         for text in p.texts:
             print(text)

@@ -20,7 +20,7 @@ SSI_F32, SSI_BF16 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 IMPL_AUTO, IMPL_GENERIC, IMPL_MFMA, IMPL_MFMA_WG8 = 0, 1, 2, 3
 TILES_STATIC, TILES_DYNAMIC = 0, 1
-ABI_VERSION = 26
+ABI_VERSION = 27
 GEMM_SKINNY_MAX_ROWS = 64
 DECODE_PENALTY_LDS_MAX = 57344
 ADAMW_MAX_SEGS = 128
@@ -105,6 +105,11 @@ PROTOTYPES = {
     "ssi_gemm_skinny": (c_int, [c_int64, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int, _P]),
     "ssi_gemm_skinny_rope": (c_int, [c_int64, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int, c_int, _P, c_int64, _P, c_int, _P]),
     "ssi_gemm_skinny_swiglu": (c_int, [c_int64, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int, _P]),
+    "ssi_weight_quant_fp8": (c_int, [_P, c_int64, c_int64, c_int64, _P, c_int64, _P, c_int, _P]),
+    "ssi_gemm_skinny_w8": (c_int, [c_int64, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int, _P]),
+    "ssi_gemm_skinny_rope_w8": (c_int, [c_int64, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P, c_int64, c_int, c_int, _P, c_int64, _P, c_int,
+                                        _P]),
+    "ssi_gemm_skinny_swiglu_w8": (c_int, [c_int64, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, _P]),
     "ssi_transpose": (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int64, c_int, _P]),
     "ssi_ce_fwd": (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int64, _P, _P, c_int, c_int, _P]),
     "ssi_ce_fwd_weighted": (c_int, [_P, c_int64, _P, _P, c_int64, c_int64, c_int64, _P, _P, c_int, c_int, _P]),

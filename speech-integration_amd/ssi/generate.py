@@ -200,19 +200,53 @@ def check_kv_cache_dtype(kv_cache_dtype) -> str | None:
     raise ValueError(f"kv_cache_dtype = {kv_cache_dtype!r}: None, 'auto' or 'fp8'")
 
 
+def check_weight_dtype(weight_dtype, small_batch: bool = True) -> str | None:
+    """``weight_dtype`` of the three loops: None or "auto" (the model's weights; not one launch, buffer, summary key or bit differs from a call
+    without it) or "fp8" (``HipLlamaDecoder.quantize_weights``: vLLM's ``quantization="fp8"``, with one power-of-two scale per output channel,
+    read by the small-batch decode steps alone, so "fp8" without ``small_batch=True`` is refused); anything else is a ``ValueError`` before any launch."""
+    if weight_dtype is None or (isinstance(weight_dtype, str) and weight_dtype in ("auto", "fp8")):
+        if weight_dtype == "fp8" and not small_batch:
+            raise ValueError("weight_dtype = 'fp8' without small_batch=True: FP8 weights serve the small-batch decode step alone")
+        return None if weight_dtype in (None, "auto") else "fp8"
+    raise ValueError(f"weight_dtype = {weight_dtype!r}: None, 'auto' or 'fp8'")
+
+
+def _weight_source(model, weight_dtype, weight_quant, small_batch: bool):
+    """None without FP8 weights; otherwise a function that hands out the quantised weights: the prebuilt ``weight_quant`` (checked against the
+    model here, before any launch), or what ``model.quantize_weights()`` builds ONCE, when the first group that decodes on the skinny path asks."""
+    if check_weight_dtype(weight_dtype, small_batch) is None:
+        if weight_quant is not None:
+            raise ValueError("weight_quant without weight_dtype='fp8'")
+        return None
+    if weight_quant is not None:
+        model._check_weight_quant(weight_quant)
+    built = [weight_quant]
+
+    def source():
+        if built[0] is None:
+            built[0] = model.quantize_weights()
+        return built[0]
+    return source
+
+
 def _new_cache(model, n_slots: int, cap: int, kv_dtype: str | None):
     """``model.new_kv_cache`` as it was always called, or of the kind ``check_kv_cache_dtype`` let through."""
     return model.new_kv_cache(n_slots, cap) if kv_dtype is None else model.new_kv_cache(n_slots, cap, dtype=kv_dtype)
 
 
-def _small_batch_kw(model, rows: int, small_batch: bool, report: dict | None, split_kv: bool = False) -> tuple[dict, dict]:
+def _small_batch_kw(model, rows: int, small_batch: bool, report: dict | None, split_kv: bool = False, weights=None) -> tuple[dict, dict]:
     """The keywords of a group of ``rows`` rows, decided once per group: (``prefill``'s, a decode step's).  Without a flag both are empty — the
     calls are then the plain ones, argument for argument.  With ``small_batch`` every step gets ``small_batch``, and a group that decodes on the
     skinny path prefills prompt by prompt (``separate``), so that nothing of a prompt's result depends on the prompts beside it; such a group is
     counted in ``report`` (the ``small_batch_groups`` of the run summary: what ran, counted where it ran).  ``split_kv`` likewise: every step
     gets ``split_kv``, and a group whose steps take the split-KV attention (``HipLlamaDecoder.takes_split_kv``) prefills prompt by prompt and is
-    counted as one of the ``split_kv_groups``."""
+    counted as one of the ``split_kv_groups``.  ``weights`` (``_weight_source``'s; only with ``small_batch``): a group that decodes on the skinny
+    path gets ``weight_quant`` with every step and is counted as one of the ``fp8_weight_groups``; any other group is untouched."""
     prefill_kw, step_kw = {}, {}
+    if weights is not None and model.takes_small_batch(rows, small_batch):
+        step_kw["weight_quant"] = weights()
+        if report is not None:
+            report["fp8_weight_groups"] = report.get("fp8_weight_groups", 0) + 1
     for flag, on, takes in (("small_batch", small_batch, model.takes_small_batch if small_batch else None),
                             ("split_kv", split_kv, model.takes_split_kv if split_kv else None)):
         if not on:
@@ -413,21 +447,22 @@ class _Sample(_Selection):
 
 
 # ---- the steppers: the next logits -------------------------------------------------------------------------------------------------
-def _own_slots(model, caches, seqs: list[Tensor], max_new: int, small_batch: bool, report: dict | None, split_kv: bool = False):
+def _own_slots(model, caches, seqs: list[Tensor], max_new: int, small_batch: bool, report: dict | None, split_kv: bool = False, weights=None):
     """Row ``r`` is prompt ``r`` and decodes on slot ``r`` of the one cache: ``prefill`` with room for the new tokens, then ``decode_step``.
     Returns the prefill's logits and the stepper."""
-    prefill_kw, step_kw = _small_batch_kw(model, len(seqs), small_batch, report, split_kv)
+    prefill_kw, step_kw = _small_batch_kw(model, len(seqs), small_batch, report, split_kv, weights)
     logits = model.prefill(caches[0], seqs, max_new_tokens=max_new, **prefill_kw)
     own = torch.arange(len(seqs), dtype=torch.int32, device=model.device)
     none = torch.full_like(own, -1)
     return logits, lambda t, tokens, alive: model.decode_step(caches[0], tokens, torch.where(alive, own, none), **step_kw)
 
 
-def _shared_prompt(model, caches, seqs: list[Tensor], n: int, max_new: int, small_batch: bool, report: dict | None, split_kv: bool = False):
+def _shared_prompt(model, caches, seqs: list[Tensor], n: int, max_new: int, small_batch: bool, report: dict | None, split_kv: bool = False,
+                   weights=None):
     """Row ``s * n + j`` is continuation ``j`` of prompt ``s``: the prompt is prefilled once into the prompt cache, its logits row repeated
     ``n`` times for step 0, and the rows run on ``decode_step_beam`` with the identity ancestry — a row reads its own generated positions."""
     rows, dev = len(seqs) * n, model.device
-    prefill_kw, step_kw = _small_batch_kw(model, rows, small_batch, report, split_kv)
+    prefill_kw, step_kw = _small_batch_kw(model, rows, small_batch, report, split_kv, weights)
     logits = model.prefill(caches[0], seqs, **prefill_kw)[:len(seqs)].repeat_interleave(n, dim=0)
     own = torch.arange(rows, dtype=torch.int32, device=dev)
     seq_of, none = own // n, torch.full_like(own, -1)
@@ -440,7 +475,7 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
              logprobs: bool = False, device: torch.device | str | None = None, allowed_token_ids: Sequence[int] | Tensor | None = None,
              min_new_tokens: int = 0, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
              presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None,
-             split_kv: bool = False, kv_cache_dtype: str | None = None) -> list[Generation]:
+             split_kv: bool = False, kv_cache_dtype: str | None = None, weight_dtype: str | None = None, weight_quant=None) -> list[Generation]:
     """Greedy continuation of every prompt (1-D integer sequences), results in INPUT order.  The token of a step is ``argmax`` over the real
     columns ``[:, :vocab_size]`` of the step's logits, with torch's first-occurrence rule.  ``pad_id`` fills the rows that have finished.
     ``logprobs=True``: the forward-only ``ops.ce_fwd_metrics`` runs on the step's logits with the chosen token as label, which gives its
@@ -464,11 +499,17 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
     ``kv_cache_dtype``: None or "auto" — the caches hold the model's dtype; "fp8" — they hold e4m3 codes with one power-of-two exponent per cached
     line (``check_kv_cache_dtype``): the store and the attention of every step are the ``_fp8`` entries, the prompt's own attention in ``prefill``
     runs on the unquantised K / V, and values change (opt-in).  Orthogonal to ``small_batch`` and ``split_kv``.
+    ``weight_dtype``: None or "auto" — the model's weights; "fp8" (only with ``small_batch=True``; ``check_weight_dtype``) — every group that decodes
+    on the skinny path reads the layer GEMMs' weights and the head as e4m3 codes with one power-of-two exponent per output channel
+    (``HipLlamaDecoder.quantize_weights``) and adds 1 to ``"fp8_weight_groups"`` of ``small_batch_report``; ``prefill``, the embedding gather and
+    every other group run on the bf16 weights, and values change (opt-in).  ``weight_quant``: a ``QuantWeights`` built before, to reuse it across
+    calls; without it one is built in the call, when the first such group starts.
     Refused before any launch (``ValueError``): a penalty outside its range, an empty prompt, a prompt that with ``max_new_tokens`` exceeds the model's RoPE table or
     ``max_seq_len``; ``min_new_tokens < 0``, an allowed or stop id outside the vocabulary (under a constraint), an empty allowed set,
     ``min_new_tokens > 0`` with nothing allowed besides the stop tokens."""
     max_new_tokens, batch_size, min_new_tokens = int(max_new_tokens), int(batch_size), int(min_new_tokens)
     kv_dtype = check_kv_cache_dtype(kv_cache_dtype)
+    weights = _weight_source(model, weight_dtype, weight_quant, small_batch)
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
     masks = _constraint_masks(int(model.vocab_size), allowed_token_ids, min_new_tokens, stop_token_ids)
     if max_new_tokens < 1:
@@ -479,7 +520,7 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
     refused = "generate: the K/V cache kernels refused {} rows (a destination or a slot outside the cache)"
 
     def run_group(caches, con, seqs: list[Tensor], index: list[int], stop: Tensor) -> list[Generation]:
-        started = _own_slots(model, caches, seqs, max_new_tokens, small_batch, small_batch_report, split_kv)
+        started = _own_slots(model, caches, seqs, max_new_tokens, small_batch, small_batch_report, split_kv, weights)
         choose = _Argmax(model, len(seqs), logprobs) if con is None and pen is None else _Select(model, seqs, con, pen, logprobs)
         return _token_loop(choose, started, caches, refused, [int(s.numel()) for s in seqs], max_new_tokens, stop, int(pad_id))
 
@@ -506,7 +547,8 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
                 length_penalty: float = 1.0, n_best: int = 1, allowed_token_ids: Sequence[int] | Tensor | None = None, min_new_tokens: int = 0,
                 batch_size: int = 256, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
                 presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None,
-             split_kv: bool = False, kv_cache_dtype: str | None = None) -> list[list[Generation]]:
+             split_kv: bool = False, kv_cache_dtype: str | None = None, weight_dtype: str | None = None,
+             weight_quant=None) -> list[list[Generation]]:
     """The ``n_best <= beam_width <= 8`` best hypotheses of every prompt, best first, in INPUT order; ``cumulative_logprob`` (the sum of the
     tokens' log-probabilities under the unconstrained distribution) and ``score`` are always set.  A group holds ``batch_size // beam_width``
     prompts, so a step is at most ``batch_size`` rows.  The rules, with ``W = beam_width``:
@@ -525,9 +567,11 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
     Refused before any launch (``ValueError``): the three beam arguments outside their ranges, a penalty off its neutral value (vLLM's beam
     search ignores them, and ``ssi_topk_logprob`` knows none), and everything ``generate`` refuses.
     ``small_batch``, ``split_kv``: handed to every ``decode_step_beam`` (``generate``'s rules, on the group's ``prompts * beam_width`` rows).
-    ``kv_cache_dtype``: ``generate``'s; the prompt cache and the beam cache are of the same kind."""
+    ``kv_cache_dtype``: ``generate``'s; the prompt cache and the beam cache are of the same kind.
+    ``weight_dtype``, ``weight_quant``: ``generate``'s."""
     W, length_penalty, n_best = _check_beam(beam_width, length_penalty, n_best)
     kv_dtype = check_kv_cache_dtype(kv_cache_dtype)
+    weights = _weight_source(model, weight_dtype, weight_quant, small_batch)
     if _check_penalties(repetition_penalty, frequency_penalty, presence_penalty) is not None:
         raise ValueError("beam_search: repetition, frequency and presence penalties are not part of beam search")
     max_new_tokens, batch_size, min_new_tokens, V = int(max_new_tokens), int(batch_size), int(min_new_tokens), int(model.vocab_size)
@@ -547,18 +591,19 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
 
     def run_group(caches, con, seqs: list[Tensor], index: list[int], stop: Tensor) -> list[list[Generation]]:
         return _beam_group(model, *caches[:2], seqs, W, max_new_tokens, stop, int(pad_id), length_penalty, n_best, caches[2], min_new_tokens,
-                           small_batch, small_batch_report, split_kv)
+                           small_batch, small_batch_report, split_kv, weights)
 
     return _run_groups(model, prompts, batch_size // W, max_new_tokens, stop_token_ids, None, 0, open_caches, run_group)       # (its mask is cont)
 
 
 def _beam_group(model, pcache, bcache, seqs: list[Tensor], W: int, max_new: int, stop: Tensor, pad_id: int, length_penalty: float, n_best: int,
-                cont_words: Tensor, min_new: int, small_batch: bool = False, report: dict | None = None, split_kv: bool = False) -> list[list[Generation]]:
+                cont_words: Tensor, min_new: int, small_batch: bool = False, report: dict | None = None, split_kv: bool = False,
+                weights=None) -> list[list[Generation]]:
     """One group: row ``s * W + b`` is beam ``b`` of prompt ``s``.  Everything of a step stays on the device."""
     n, dev, V, S = len(seqs), model.device, int(model.vocab_size), int(stop.numel())
     R, P, NEG = n * W, 2 * W, float("-inf")     # a pool never holds more than (W - 1) + W hypotheses; place P takes what is not stored
     i64, f32 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float32, device=dev)
-    prefill_kw, step_kw = _small_batch_kw(model, R, small_batch, report, split_kv)
+    prefill_kw, step_kw = _small_batch_kw(model, R, small_batch, report, split_kv, weights)
     logits = model.prefill(pcache, seqs, **prefill_kw)
     own = torch.arange(R, dtype=torch.int32, device=dev)
     seq_of = own // W
@@ -667,7 +712,8 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
            stop_token_ids: Sequence[int], pad_id: int, batch_size: int = 256, allowed_token_ids: Sequence[int] | Tensor | None = None,
            min_new_tokens: int = 0, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
            presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None,
-             split_kv: bool = False, kv_cache_dtype: str | None = None) -> list[list[Generation]]:
+             split_kv: bool = False, kv_cache_dtype: str | None = None, weight_dtype: str | None = None,
+             weight_quant=None) -> list[list[Generation]]:
     """``n`` (1..8) sampled continuations of every prompt, in INPUT order and per prompt in sample order; ``cumulative_logprob`` (the tokens'
     log-probabilities under the unconstrained distribution at temperature 1, what ``ssi.score`` assigns) and ``n_kept_mean`` are always set.
     The token of a step is ``ops.decode_sample``'s with ``step`` the loop index and ``sequence = prompt index * n + sample index``: a pure function
@@ -682,9 +728,11 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
     Refused before any launch (``ValueError``): ``n`` outside 1..8, ``temperature`` not finite or <= 0 (greedy decoding is ``generate``), ``top_p``
     outside (0, 1], a non-integer ``top_k``, a negative ``seed``, and everything ``generate`` refuses.
     ``small_batch``, ``split_kv``: handed to every decode step (``generate``'s rules, on the group's ``prompts * n`` rows).
-    ``kv_cache_dtype``: ``generate``'s; with ``n > 1`` the prompt cache and the samples' cache are of the same kind."""
+    ``kv_cache_dtype``: ``generate``'s; with ``n > 1`` the prompt cache and the samples' cache are of the same kind.
+    ``weight_dtype``, ``weight_quant``: ``generate``'s."""
     n, temperature, top_k, top_p, seed = _check_sample(n, temperature, top_k, top_p, seed)
     kv_dtype = check_kv_cache_dtype(kv_cache_dtype)
+    weights = _weight_source(model, weight_dtype, weight_quant, small_batch)
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
     max_new_tokens, batch_size, min_new_tokens, V = int(max_new_tokens), int(batch_size), int(min_new_tokens), int(model.vocab_size)
     masks = _constraint_masks(V, allowed_token_ids, min_new_tokens, stop_token_ids)
@@ -704,9 +752,9 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
 
     def run_group(caches, con, seqs: list[Tensor], index: list[int], stop: Tensor) -> list[list[Generation]]:
         if n == 1:          # no prompt to share: every row on its own slot, as ``generate``
-            started = _own_slots(model, caches, seqs, max_new_tokens, small_batch, small_batch_report, split_kv)
+            started = _own_slots(model, caches, seqs, max_new_tokens, small_batch, small_batch_report, split_kv, weights)
         else:
-            started = _shared_prompt(model, caches, seqs, n, max_new_tokens, small_batch, small_batch_report, split_kv)
+            started = _shared_prompt(model, caches, seqs, n, max_new_tokens, small_batch, small_batch_report, split_kv, weights)
         choose = _Sample(model, seqs, index, n, draw, con, pen)
         found = _token_loop(choose, started, caches, refused, [int(s.numel()) for s in seqs for _ in range(n)], max_new_tokens, stop, int(pad_id))
         return [found[s * n:s * n + n] for s in range(len(seqs))]
@@ -773,9 +821,16 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     the skinny path.  ``split_kv=True`` likewise, with ``"split_kv_groups"``: the groups that ran the split-KV decode attention.  ``False`` (the
     default of both) is not passed on and adds no key.
     ``kv_cache_dtype`` in ``kw`` goes to whichever loop runs (``check_kv_cache_dtype``, refused here before a prompt is read); the summary gains
-    ``"kv_cache_dtype": "fp8"`` under fp8 alone — None and "auto" are not passed on and add no key."""
+    ``"kv_cache_dtype": "fp8"`` under fp8 alone — None and "auto" are not passed on and add no key.
+    ``weight_dtype`` (and ``weight_quant``) in ``kw`` likewise (``check_weight_dtype``: "fp8" needs ``small_batch=True``); under fp8 alone the summary
+    gains ``"fp8_weight_groups"``: the groups whose steps read FP8 weights."""
     kv_dtype = check_kv_cache_dtype(kw.pop("kv_cache_dtype", None))
     fp8 = {} if kv_dtype is None else {"kv_cache_dtype": kv_dtype}
+    w8 = {} if check_weight_dtype(kw.pop("weight_dtype", None), bool(kw.get("small_batch", False))) is None else {"weight_dtype": "fp8"}
+    if not w8 and kw.get("weight_quant") is not None:
+        raise ValueError("weight_quant without weight_dtype='fp8'")
+    if not w8:
+        kw.pop("weight_quant", None)
     if in_path is not None:
         ids, prompts = _read_prompts(tokenizer, in_path)
     elif prompts is None:
@@ -790,8 +845,10 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     if not flags:
         return dict(_run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding, dict(kw, **fp8)), **fp8)
     report = {flag + "_groups": 0 for flag in flags}          # counted by the loop, group by group, where the path is taken
+    if w8:
+        report["fp8_weight_groups"] = 0
     summary = _run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_token_ids, tokenizer_decoding,
-                        dict(kw, small_batch_report=report, **flags, **fp8))
+                        dict(kw, small_batch_report=report, **flags, **fp8, **w8))
     return dict(summary, **report, **fp8)
 
 

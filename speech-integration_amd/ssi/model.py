@@ -123,6 +123,23 @@ class KVCache:
         return self.k.shape[2]
 
 
+class QuantWeights:
+    """What ``HipLlamaDecoder.quantize_weights`` returns: the projection matrices of every layer (``L{l}.wqkv``, ``.wo``, ``.w13``, ``.w2``) and,
+    with ``head``, the tied embedding (``emb``) as e4m3 codes (uint8 ``[N, K]``) with one exponent byte per row (uint8 ``[N]``) — the header's "FP8
+    weights".  ``mats``: name -> (codes, exps), plain tensors owned by the caller (not in the arena, not in the flat buffer; the model keeps no
+    reference).  A snapshot: weights trained or loaded afterwards are not in it."""
+
+    def __init__(self, mats: dict) -> None:
+        self.mats = mats
+
+    @property
+    def head(self) -> bool:
+        return "emb" in self.mats
+
+    def nbytes(self) -> int:
+        return sum(c.numel() + e.numel() for c, e in self.mats.values())
+
+
 # One decoder layer's activation tensors, views of arena storage; ``HipLlamaDecoder._layer_bufs`` names and shapes them.  The final norm is the
 # record of "layer" ``num_layers``: ``h_in`` its input, ``xn1`` its output, ``rstd1`` its rstd, the rest None.  ``lse`` is None in a decode step.
 _LayerBufs = namedtuple("_LayerBufs", "h_in xn1 rstd1 qkv att lse hmid xn2 rstd2 gu act h_out", defaults=(None,) * 9)
@@ -584,11 +601,19 @@ class HipLlamaDecoder(nn.Module):
                           A.get(nm("hmid"), (rows, D), dt), A.get(nm("xn2"), (rows, D), dt), A.get(nm("rstd2"), (rows,), f32),
                           None if mode == "s" else A.get(nm("gu"), (rows, 2 * I), dt), A.get(nm("act"), (rows, I), dt), h_out)
 
-    def _run_stack(self, mode: str, tok: Tensor, B: int, S: int, seq_len: int, pos: Optional[Tensor], attend) -> tuple[list, _LayerBufs]:
+    def _run_stack(self, mode: str, tok: Tensor, B: int, S: int, seq_len: int, pos: Optional[Tensor], attend,
+                   weight_quant: Optional["QuantWeights"] = None) -> tuple[list, _LayerBufs]:
         """Embedding, every layer, final norm on ``mode``'s buffers -> (the layers' records, the final norm's).  ``attend(l, record)``: the one step
         in which a forward and a decode step differ.  RoPE (rows of ``seq_len`` positions, or ``pos``) and SwiGLU ride in their GEMMs' epilogues.
-        Mode ``"s"``: the four GEMMs are the skinny entries (1 to ``skinny_max_rows`` unpadded rows, ``pos`` required), everything else the same."""
-        if mode == "s":
+        Mode ``"s"``: the four GEMMs are the skinny entries (1 to ``skinny_max_rows`` unpadded rows, ``pos`` required), everything else the same;
+        with ``weight_quant`` (mode ``"s"`` only) their ``_w8`` forms on that object's codes and exponents in place of the bf16 weights."""
+        weight = self._view
+        if mode == "s" and weight_quant is not None:
+            weight = lambda name: weight_quant.mats[name]  # noqa: E731
+            qkv_gemm = lambda x, w, out: ops.gemm_skinny_rope_w8(x, *w, out, self.num_heads + self.num_kv_heads, self.head_dim, self._rope, pos)  # noqa: E731
+            res_gemm = lambda x, w, out, res: ops.gemm_skinny_w8(x, *w, out, residual=res)  # noqa: E731
+            mlp_gemm = lambda x, w, gu, act: ops.gemm_skinny_swiglu_w8(x, *w, None, act)  # noqa: E731
+        elif mode == "s":
             qkv_gemm = lambda x, w, out: ops.gemm_skinny_rope(x, w, out, self.num_heads + self.num_kv_heads, self.head_dim, self._rope, pos)  # noqa: E731
             res_gemm = lambda x, w, out, res: ops.gemm_skinny(x, w, out, residual=res)  # noqa: E731
             mlp_gemm = lambda x, w, gu, act: ops.gemm_skinny_swiglu(x, w, None, act)  # noqa: E731
@@ -601,12 +626,12 @@ class HipLlamaDecoder(nn.Module):
         for l in range(self.num_layers):
             layers.append(b)
             ops.rmsnorm_fwd(b.h_in, self._view(f"L{l}.sa_norm"), b.xn1, b.rstd1, self.norm_eps)
-            qkv_gemm(b.xn1, self._view(f"L{l}.wqkv"), b.qkv)
+            qkv_gemm(b.xn1, weight(f"L{l}.wqkv"), b.qkv)
             attend(l, b)
-            res_gemm(b.att, self._view(f"L{l}.wo"), b.hmid, b.h_in)
+            res_gemm(b.att, weight(f"L{l}.wo"), b.hmid, b.h_in)
             ops.rmsnorm_fwd(b.hmid, self._view(f"L{l}.mlp_norm"), b.xn2, b.rstd2, self.norm_eps)
-            mlp_gemm(b.xn2, self._view(f"L{l}.w13"), b.gu, b.act)
-            res_gemm(b.act, self._view(f"L{l}.w2"), b.h_out, b.hmid)
+            mlp_gemm(b.xn2, weight(f"L{l}.w13"), b.gu, b.act)
+            res_gemm(b.act, weight(f"L{l}.w2"), b.h_out, b.hmid)
             b = self._layer_bufs(mode, l + 1, B * S, B, S, layers)
         ops.rmsnorm_fwd(b.h_in, self.norm.scale, b.xn1, b.rstd1, self.norm_eps)
         return layers, b
@@ -730,6 +755,39 @@ class HipLlamaDecoder(nn.Module):
         self._saved = None   # (with it go the records' references to arena storage: a buffer that grows next can be freed first, _Arena.get)
         self.attach_grads()
 
+    # ---- FP8 weights for small-batch decoding (the header's "FP8 weights") -----------------------------------------------------
+    def _quant_names(self, head: bool) -> list[str]:
+        return [f"L{l}.{m}" for l in range(self.num_layers) for m in ("wqkv", "wo", "w13", "w2")] + (["emb"] if head else [])
+
+    @torch.no_grad()
+    def quantize_weights(self, head: bool = True) -> QuantWeights:
+        """The present ``wqkv``, ``wo``, ``w13`` and ``w2`` of every layer and, with ``head``, the tied embedding as e4m3 codes with one
+        power-of-two exponent per row (``ops.weight_quant_fp8``), for ``decode_step(..., small_batch=True, weight_quant=...)``.  bf16 models on
+        the small-batch shapes only (``ValueError`` otherwise: no other step would read the codes).  The codes and exponents are tensors of
+        their own, a byte per weight on top of the bf16 weights, which stay: the embedding gather, ``prefill`` and every larger step read them."""
+        if not self.takes_small_batch(1, True):
+            raise ValueError("quantize_weights: FP8 weights serve the small-batch decode step alone (a bf16 model on the MFMA shapes with head_dim 64)")
+        mats = {}
+        for name in self._quant_names(head):
+            w = self._view(name)
+            codes = torch.empty(w.shape, dtype=torch.uint8, device=self.device)
+            exps = torch.empty((w.shape[0],), dtype=torch.uint8, device=self.device)
+            ops.weight_quant_fp8(w, codes, exps)
+            mats[name] = (codes, exps)
+        return QuantWeights(mats)
+
+    def _check_weight_quant(self, qw: Optional[QuantWeights]) -> Optional[QuantWeights]:
+        """``qw`` if it is this model's (every layer's four matrices, the head or not, in this model's shapes on its device); ``ValueError`` otherwise."""
+        if qw is None:
+            return None
+        if not isinstance(qw, QuantWeights) or set(qw.mats) != set(self._quant_names(qw.head)):
+            raise ValueError("weight_quant is not what this model's quantize_weights returns")
+        for name, (codes, exps) in qw.mats.items():
+            shape = self._slices[name][1]
+            if tuple(codes.shape) != tuple(shape) or tuple(exps.shape) != (shape[0],) or codes.device != self.device or exps.device != self.device:
+                raise ValueError(f"weight_quant is not this model's: {name} is {tuple(codes.shape)} on {codes.device}, expected {tuple(shape)} on {self.device}")
+        return qw
+
     # ---- generation: K/V cache, prefill, decode step (ssi/generate.py drives them) --------------------------------------------
     def new_kv_cache(self, n_slots: int, cap: int, dtype=None) -> "KVCache":
         """A K/V cache for ``n_slots`` sequences of up to ``cap`` tokens: plain tensors owned by the caller (not arena buffers; the model
@@ -775,6 +833,8 @@ class HipLlamaDecoder(nn.Module):
         rows of the prompts' LAST tokens alone go through the tied head.  Returns ``[n_prompts, vocab_pad]`` logits (fresh tensor) and
         sets the cache's lengths; slots beyond the prompts are emptied.  ``max_new_tokens``: what ``decode_step`` will add, checked here
         against the cap, the RoPE table and ``max_seq_len`` (``ValueError`` before any launch).
+        ``prefill`` always runs on the unquantised weights (FP8 weights, ``quantize_weights``, are read by small-batch decode steps alone), as it
+        attends over the unquantised K / V under an fp8 cache.
         ``separate`` (the small-batch loops): every prompt runs as a packed forward of its own, one row that starts at position 0.  Where a
         prompt lies in a packed row, and how many rows the forward has (which picks the K split of its GEMMs), enter the bits of its K / V
         and of its logits; prompt by prompt they are a function of the prompt alone, whatever else is in the group."""
@@ -835,7 +895,8 @@ class HipLlamaDecoder(nn.Module):
         store(qkv, dest, *cache.layer(l), self.num_heads, self.num_kv_heads, self.head_dim, n_bad=cache.errors)
 
     @torch.no_grad()
-    def decode_step(self, cache: "KVCache", tokens: Tensor, slots: Tensor, small_batch: bool = False, split_kv: bool = False) -> Tensor:
+    def decode_step(self, cache: "KVCache", tokens: Tensor, slots: Tensor, small_batch: bool = False, split_kv: bool = False,
+                    weight_quant: Optional["QuantWeights"] = None) -> Tensor:
         """One new token per live sequence: ``tokens`` (int64 ``[rows]``) and ``slots`` (int32 ``[rows]``; -1 = an inert row: no attention,
         no cache write, a zero attention row) on the device.  Row r runs at position ``cache.lengths[slots[r]]``: its K / V go there, it
         attends over the ``length + 1`` keys of its slot, and the length advances — all on the device, nothing is read back.  Returns the
@@ -848,7 +909,10 @@ class HipLlamaDecoder(nn.Module):
         ``kv_store`` and ``attn_decode`` are the same launches on fewer rows.  A row's logits do not depend on the rows beside it.
         ``split_kv`` (with 1 to ``split_max_rows`` rows; otherwise without effect): ``attn_decode_split`` in place of ``attn_decode``, on the step's
         rows, padded or not, with a span of ``split_span`` keys and a workspace ``ws.splitkv.g`` / ``.s`` from the arena.  A row's logits still
-        depend on that row alone, but differ in bits from the unsplit step's once its cache is longer than the span."""
+        depend on that row alone, but differ in bits from the unsplit step's once its cache is longer than the span.
+        ``weight_quant`` (what ``quantize_weights`` returned; where ``takes_small_batch`` holds, otherwise without effect): the four layer GEMMs and,
+        if the object has it, the head read e4m3 codes through the ``_w8`` skinny entries; the logits are bit-equal to a small-batch step of a
+        model that holds the dequantised weights.  The embedding gather, the norms, the K/V store and the attention are the same launches."""
         self._check_cache(cache)
         if tokens.dim() != 1 or tokens.dtype != torch.int64 or slots.shape != tokens.shape or slots.dtype != torch.int32:
             raise ValueError("decode_step: tokens is int64 [rows], slots int32 [rows]")
@@ -856,6 +920,7 @@ class HipLlamaDecoder(nn.Module):
             raise _lib.HipLibraryError("decode_step: tokens and slots must live on the GPU (no CPU fallback)")
         n = tokens.numel()
         small = self.takes_small_batch(n, small_batch)
+        wq = self._check_weight_quant(weight_quant) if small else None
         R = n if small else self._padded_rows(n)
         H, KV, hd, dev = self.num_heads, self.num_kv_heads, self.head_dim, self.device
         tok = torch.zeros(R, dtype=torch.int64, device=dev)          # pad rows: token 0, slot -1, position 0
@@ -882,13 +947,14 @@ class HipLlamaDecoder(nn.Module):
             else:
                 (ops.attn_decode_fp8 if fp8 else ops.attn_decode)(b.qkv, *cache.layer(l), slot, kv_len, b.att, None, H, KV, hd, n_bad=cache.errors)
 
-        logits = self._head_logits(self._run_stack(mode, tok, R, 1, R, pos, attend)[1].xn1, skinny=small)   # R rows of one position each; RoPE by ``pos``
+        logits = self._head_logits(self._run_stack(mode, tok, R, 1, R, pos, attend, wq)[1].xn1, skinny=small, weight_quant=wq)   # R rows of one position each; RoPE by ``pos``
         cache.lengths.index_add_(0, slot.clamp(min=0).long(), write.to(torch.int32))
         return logits[:n]
 
     @torch.no_grad()
     def decode_step_beam(self, prompt_cache: "KVCache", beam_cache: "KVCache", tokens: Tensor, prompt_slot: Tensor, prompt_len: Tensor,
-                         anc: Tensor, t: int, small_batch: bool = False, split_kv: bool = False) -> Tensor:
+                         anc: Tensor, t: int, small_batch: bool = False, split_kv: bool = False,
+                         weight_quant: Optional["QuantWeights"] = None) -> Tensor:
         """Step ``t`` of beam search: row ``r`` (one hypothesis) runs ``tokens[r]`` at position ``prompt_len[r] + t``.  Its K / V go to the beam
         cache at ``(r, t)``, and it attends over the ``prompt_len[r]`` keys of slot ``prompt_slot[r]`` of the prompt cache (what ``prefill``
         filled; read only here) and the generated positions ``i <= t`` of the beam cache at slots ``anc[r, i]`` — ``anc`` (int32
@@ -896,7 +962,8 @@ class HipLlamaDecoder(nn.Module):
         row.  Everything on the device; rows padded to whole tiles and activations in the ``*.g`` buffers, as ``decode_step``.  Neither cache's
         ``lengths`` are read or changed; refused indices are counted in ``beam_cache.errors``.  Returns ``[rows, vocab_pad]`` logits (fresh).
         ``small_batch``: as in ``decode_step`` (unpadded rows, skinny GEMMs, ``*.s`` buffers, where ``takes_small_batch`` holds).
-        ``split_kv``: as in ``decode_step`` (``attn_decode_beam_split`` in place of ``attn_decode_beam``, where ``takes_split_kv`` holds)."""
+        ``split_kv``: as in ``decode_step`` (``attn_decode_beam_split`` in place of ``attn_decode_beam``, where ``takes_split_kv`` holds).
+        ``weight_quant``: as in ``decode_step`` (the ``_w8`` skinny GEMMs, where ``takes_small_batch`` holds)."""
         self._check_cache(prompt_cache)
         self._check_cache(beam_cache, beside=prompt_cache)
         n, t = tokens.numel(), int(t)
@@ -910,6 +977,7 @@ class HipLlamaDecoder(nn.Module):
         if not all(x.is_cuda for x in (tokens, prompt_slot, prompt_len, anc)):
             raise _lib.HipLibraryError("decode_step_beam: tokens, prompt_slot, prompt_len and anc must live on the GPU (no CPU fallback)")
         small = self.takes_small_batch(n, small_batch)
+        wq = self._check_weight_quant(weight_quant) if small else None
         R = n if small else self._padded_rows(n)
         H, KV, hd, dev = self.num_heads, self.num_kv_heads, self.head_dim, self.device
         tok = torch.zeros(R, dtype=torch.int64, device=dev)           # pad rows: token 0, slot -1, position 0
@@ -935,10 +1003,11 @@ class HipLlamaDecoder(nn.Module):
                     b.qkv, *prompt_cache.layer(l), *beam_cache.layer(l), slot, plen, gen_len, anc_r, b.att, None, H, KV, hd,
                     n_bad=beam_cache.errors, **(split or {}))
 
-        return self._head_logits(self._run_stack(mode, tok, R, 1, R, pos, attend)[1].xn1, skinny=small)[:n]
+        return self._head_logits(self._run_stack(mode, tok, R, 1, R, pos, attend, wq)[1].xn1, skinny=small, weight_quant=wq)[:n]
 
     # ---- tied LM head ------------------------------------------------------------------------------------------------
-    def _head_logits(self, hn: Tensor, arena_name: Optional[str] = None, skinny: bool = False) -> Tensor:
+    def _head_logits(self, hn: Tensor, arena_name: Optional[str] = None, skinny: bool = False,
+                     weight_quant: Optional["QuantWeights"] = None) -> Tensor:
         """logits [T, vocab_pad] = hn E^T.  Callers of the public ``forward`` get a FRESH tensor (as torchtune returns): logits kept
         from one batch must survive the next forward.  Only the fused loss passes an arena name (its buffer never leaves the model)."""
         T = hn.shape[0]
@@ -946,7 +1015,9 @@ class HipLlamaDecoder(nn.Module):
             logits = torch.empty((T, self.vocab_pad), dtype=self.dtype, device=self.device)
         else:
             logits = self._arena.get(arena_name, (T, self.vocab_pad), self.dtype)
-        if skinny:   # (a small-batch decode step: 1 to skinny_max_rows rows)
+        if skinny and weight_quant is not None and weight_quant.head:   # (a small-batch decode step on FP8 weights whose object holds the head)
+            ops.gemm_skinny_w8(hn, *weight_quant.mats["emb"], logits)
+        elif skinny:   # (a small-batch decode step: 1 to skinny_max_rows rows)
             ops.gemm_skinny(hn, self._view("emb"), logits)
         else:
             ops.gemm(GEMM_NT, hn, self._view("emb"), logits)

@@ -10,7 +10,7 @@ from torch import Tensor
 from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
-__all__ = ["gemm_skinny", "gemm_skinny_rope", "gemm_skinny_swiglu", "lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "attn_decode_beam", "attn_decode_split", "attn_decode_beam_split", "attn_decode_split_span", "attn_decode_split_workspace", "decode_select", "decode_sample", "decode_select_pen", "decode_sample_pen", "decode_penalty_lds_bytes", "topk_logprob", "swiglu_fwd",
+__all__ = ["gemm_skinny", "gemm_skinny_rope", "gemm_skinny_swiglu", "weight_quant_fp8", "gemm_skinny_w8", "gemm_skinny_rope_w8", "gemm_skinny_swiglu_w8", "lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "attn_decode_beam", "attn_decode_split", "attn_decode_beam_split", "attn_decode_split_span", "attn_decode_split_workspace", "decode_select", "decode_sample", "decode_select_pen", "decode_sample_pen", "decode_penalty_lds_bytes", "topk_logprob", "swiglu_fwd",
            "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "ema_update", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "kv_store_fp8", "attn_decode_fp8", "attn_decode_beam_fp8", "attn_decode_split_fp8", "attn_decode_beam_split_fp8",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
@@ -709,6 +709,60 @@ def gemm_skinny_swiglu(x: Tensor, w13: Tensor, gu: Tensor | None, act: Tensor) -
     assert x.dtype == w13.dtype == act.dtype
     check(_lib.load().ssi_gemm_skinny_swiglu(M, inter, K, ptr(x), x.stride(0), ptr(w13), w13.stride(0), ptr(gu), 0 if gu is None else gu.stride(0),
                                              ptr(act), act.stride(0), dtype_code(x.dtype), stream_ptr()), "ssi_gemm_skinny_swiglu")
+
+
+def _w8_rows(codes: Tensor, exps: Tensor, like: Tensor) -> tuple[int, int]:
+    """(N, K) of a quantised weight matrix as the ``_w8`` entries take it: uint8 ``codes`` [N, K] (rows may be pitched) and ``exps`` [N]."""
+    assert codes.dim() == 2 and codes.dtype == torch.uint8 and codes.stride(1) == 1 and like.dtype == torch.bfloat16
+    assert exps.dtype == torch.uint8 and exps.shape == (codes.shape[0],) and exps.is_contiguous() and exps.device == codes.device == like.device
+    return codes.shape
+
+
+def weight_quant_fp8(w: Tensor, codes: Tensor, exps: Tensor) -> None:
+    """bf16 ``w`` [N, K] -> e4m3 ``codes`` (uint8 [N, K], rows may be pitched) and one exponent byte per row in ``exps`` (uint8 [N]): the header's
+    "FP8 weights" (the "FP8 K/V cache" rule with a row of ``w`` as the line)."""
+    assert w.dim() == 2 and w.stride(1) == 1
+    N, K = _w8_rows(codes, exps, w)
+    assert w.shape == (N, K)
+    check(_lib.load().ssi_weight_quant_fp8(ptr(w), w.stride(0), N, K, ptr(codes), codes.stride(0), ptr(exps), dtype_code(w.dtype), stream_ptr()),
+          "ssi_weight_quant_fp8")
+
+
+def gemm_skinny_w8(a: Tensor, codes: Tensor, exps: Tensor, c: Tensor, *, residual: Tensor | None = None) -> None:
+    """``gemm_skinny`` on a weight matrix quantised by ``weight_quant_fp8``: bit-equal to ``gemm_skinny`` on the dequantised matrix in bf16."""
+    assert a.dim() == 2 and c.dim() == 2 and a.stride(1) == 1 and c.stride(1) == 1
+    M, K = a.shape
+    N = _w8_rows(codes, exps, a)[0]
+    assert codes.shape[1] == K and c.shape == (M, N) and a.dtype == c.dtype
+    if residual is not None:
+        assert residual.shape == c.shape and residual.stride() == c.stride() and residual.dtype == c.dtype
+    check(_lib.load().ssi_gemm_skinny_w8(M, N, K, ptr(a), a.stride(0), ptr(codes), codes.stride(0), ptr(exps), ptr(c), c.stride(0), ptr(residual),
+                                         dtype_code(c.dtype), stream_ptr()), "ssi_gemm_skinny_w8")
+
+
+def gemm_skinny_rope_w8(a: Tensor, codes: Tensor, exps: Tensor, c: Tensor, n_heads_rot: int, head_dim: int, table: Tensor, positions: Tensor) -> None:
+    """``gemm_skinny_rope`` on a quantised weight matrix."""
+    assert a.dim() == 2 and c.dim() == 2 and a.stride(1) == 1 and c.stride(1) == 1
+    M, K = a.shape
+    N = _w8_rows(codes, exps, a)[0]
+    assert codes.shape[1] == K and c.shape == (M, N) and a.dtype == c.dtype
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.shape[1] * 2 == head_dim
+    assert positions.dtype == torch.int32 and positions.numel() == M and positions.is_contiguous()
+    check(_lib.load().ssi_gemm_skinny_rope_w8(M, N, K, ptr(a), a.stride(0), ptr(codes), codes.stride(0), ptr(exps), ptr(c), c.stride(0), n_heads_rot,
+                                              head_dim, ptr(table), table.shape[0], ptr(positions), dtype_code(a.dtype), stream_ptr()),
+          "ssi_gemm_skinny_rope_w8")
+
+
+def gemm_skinny_swiglu_w8(x: Tensor, codes13: Tensor, exps13: Tensor, gu: Tensor | None, act: Tensor) -> None:
+    """``gemm_skinny_swiglu`` on a quantised ``w13`` = [gate rows | up rows]."""
+    M, K = x.shape
+    inter = act.shape[1]
+    assert _w8_rows(codes13, exps13, x) == (2 * inter, K) and act.shape[0] == M and x.stride(1) == 1 and act.stride(1) == 1
+    assert gu is None or (gu.shape == (M, 2 * inter) and gu.stride(1) == 1 and gu.dtype == x.dtype)
+    assert x.dtype == act.dtype
+    check(_lib.load().ssi_gemm_skinny_swiglu_w8(M, inter, K, ptr(x), x.stride(0), ptr(codes13), codes13.stride(0), ptr(exps13), ptr(gu),
+                                                0 if gu is None else gu.stride(0), ptr(act), act.stride(0), dtype_code(x.dtype), stream_ptr()),
+          "ssi_gemm_skinny_swiglu_w8")
 
 
 def transpose(src: Tensor, dst: Tensor) -> None:

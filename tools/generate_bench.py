@@ -1,5 +1,5 @@
 """What greedy generation costs at the 1B shape (Llama-3.2-1B + 5000 DSUs, bf16, random weights): 256 prompts of about 1000 tokens, 256 new
-tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained|beam|sample|penalty|small_batch|split_kv|kv_fp8] [--json profiles/generate.json]
+tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained|beam|sample|penalty|small_batch|split_kv|kv_fp8|weight_fp8] [--json profiles/generate.json]
 
 run        prefill time, milliseconds per decode step (event time over all steps, host gaps included), generated tokens per second, and a
            self-check: the first generated token of every prompt against the argmax of a plain full forward of that prompt alone (with
@@ -48,6 +48,12 @@ kv_fp8     (not part of ``all``; python tools/generate_bench.py --part kv_fp8 --
            4000 keys, every layer's caches in turn), the two stores at 256 rows, the beam pair at 64 x 4; whole ``decode_step``s at 256 rows and the
            small-batch step at 1 and 8 rows; ``generate`` end to end; and, recorded and not asserted, the share of greedy tokens equal between the two
            caches and the largest teacher-forced logit difference (random weights: nothing about a trained checkpoint).
+weight_fp8 (not part of ``all``; python tools/generate_bench.py --part weight_fp8 --json profiles/generate_weight_fp8.json) what FP8 weights buy and
+           cost on the small-batch path, ONE process, the forms alternating: each of the five GEMMs at 1, 16 and 64 rows, ``_w8`` entry against plain
+           skinny entry, with the weight bytes per second of both; the quantiser over the whole model; the small-batch ``decode_step`` at 1, 8, 16,
+           32 and 64 rows with and without ``weight_quant``; ``generate`` of 1 and 8 prompts end to end (the object built inside the call, and
+           prebuilt); the added bytes; and, recorded and not asserted, the teacher-forced logit difference with and without the quantised head and
+           the share of equal greedy tokens (random weights: nothing about a trained checkpoint).
 """
 import argparse, csv, glob, json, os, statistics, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,7 +61,7 @@ PKG = os.path.join(ROOT, 'speech-integration_amd')
 sys.path.insert(0, PKG)
 
 ap = argparse.ArgumentParser()
-ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained', 'beam', 'sample', 'penalty', 'small_batch', 'small_batch_steps', 'split_kv', 'kv_fp8'])
+ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained', 'beam', 'sample', 'penalty', 'small_batch', 'small_batch_steps', 'split_kv', 'kv_fp8', 'weight_fp8'])
 ap.add_argument('--rows', type=int, default=1, help='small_batch_steps: rows of the traced steps')
 ap.add_argument('--prompts', type=int, default=256)
 ap.add_argument('--penalty-generated', type=int, default=128, help='penalty: generated tokens in every row\'s history')
@@ -1292,6 +1298,179 @@ def part_kv_fp8():
     return res
 
 
+def part_weight_fp8():
+    """FP8 weights against the bf16 weights on the small-batch path: per GEMM, the quantiser, per step, end to end, memory, fidelity."""
+    import torch
+    from ssi import ops
+    from ssi.generate import generate
+    model = build_model()
+    D, I, L, dev, bf = model.embed_dim, model.intermediate_dim, model.num_layers, dict(device='cuda'), torch.bfloat16
+    ROWS = (1, 16, 64)
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(reps):
+            fn(i)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3        # us per call
+
+    def verdict(e, plain, fp8):
+        """fp8 is faster than the plain form by more than the plain form's own min..max spread?"""
+        e['plain_over_fp8'] = round(e[plain]['median'] / e[fp8]['median'], 3)
+        e['plain_spread'] = round(e[plain]['max'] - e[plain]['min'], 3)
+        e['fp8_wins_by_more_than_the_plain_spread'] = bool(e[plain]['median'] - e[fp8]['median'] > e['plain_spread'])
+        return e
+
+    res = {'geometry': f'1B shape, bf16; {args.rounds} rounds alternating the forms in one process, median (min - max); the layer GEMMs walk the {L} '
+                       f'layers\' weights in turn (call i reads layer i % {L}), the head reads the one table',
+           'hbm_TB_per_s_of_the_adamw_and_ema_passes': list(HBM_TB_S),
+           'plain_form': 'the plain small-batch form measured on THIS build; it stands for the parent commit by tools/kernel_lint.py --against the parent '
+                         'build (every kernel this part launches without fp8 is instruction-identical), not by a measurement of the parent'}
+    with torch.inference_mode():
+        # the quantiser over the whole model (the object the rest of the part reads)
+        qw = model.quantize_weights()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(args.rounds):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            again = model.quantize_weights()
+            torch.cuda.synchronize()
+            times.append((time.perf_counter() - t0) * 1e3)
+            del again
+        wbytes = sum(model._view(n).numel() * 2 for n in qw.mats)
+        res['quantiser_whole_model'] = {'call_ms': spread(times, 2), 'matrices': len(qw.mats), 'bf16_GB_read_twice': round(wbytes / 1e9, 3),
+                                        'note': 'host clock around quantize_weights(): the allocations and one launch per matrix included'}
+        res['memory'] = {'added_bytes': qw.nbytes(), 'added_GB': round(qw.nbytes() / 1e9, 3), 'bf16_weights_GB': round(model._flat_numel * 2 / 1e9, 3),
+                         'note': 'the bf16 weights stay (the embedding gather, prefill and every larger step read them): nothing is saved, a byte per weight is added'}
+
+        g = torch.Generator(device='cuda').manual_seed(5)
+        x = {k: torch.randn(64, k, generator=g, **dev).mul_(0.5).to(bf) for k in (D, I)}
+        pos = torch.randint(0, 1000, (64,), generator=g, **dev).to(torch.int32)
+        W = lambda name: [model._view(f'L{l}.{name}') for l in range(L)]   # noqa: E731
+        Q = lambda name: [qw.mats[f'L{l}.{name}'] for l in range(L)]       # noqa: E731
+        wqkv, wo, w13, w2, emb = W('wqkv'), W('wo'), W('w13'), W('w2'), model._view('emb')
+        qqkv, qo, q13, q2, qemb = Q('wqkv'), Q('wo'), Q('w13'), Q('w2'), qw.mats['emb']
+        H = model.num_heads + model.num_kv_heads
+        out = {n: torch.empty(64, n, **dev, dtype=bf) for n in (model.qkv_dim, D, I, model.vocab_pad)}
+        res_in = torch.randn(64, D, generator=g, **dev).to(bf)
+        shapes = {
+            'qkv_rope_3072x2048': (model.qkv_dim * D,
+                                   lambda m: (lambda i: ops.gemm_skinny_rope(x[D][:m], wqkv[i % L], out[model.qkv_dim][:m], H, 64, model._rope, pos[:m])),
+                                   lambda m: (lambda i: ops.gemm_skinny_rope_w8(x[D][:m], *qqkv[i % L], out[model.qkv_dim][:m], H, 64, model._rope, pos[:m]))),
+            'wo_residual_2048x2048': (D * D,
+                                      lambda m: (lambda i: ops.gemm_skinny(x[D][:m], wo[i % L], out[D][:m], residual=res_in[:m])),
+                                      lambda m: (lambda i: ops.gemm_skinny_w8(x[D][:m], *qo[i % L], out[D][:m], residual=res_in[:m]))),
+            'w13_swiglu_16384x2048': (2 * I * D,
+                                      lambda m: (lambda i: ops.gemm_skinny_swiglu(x[D][:m], w13[i % L], None, out[I][:m])),
+                                      lambda m: (lambda i: ops.gemm_skinny_swiglu_w8(x[D][:m], *q13[i % L], None, out[I][:m]))),
+            'w2_residual_2048x8192': (D * I,
+                                      lambda m: (lambda i: ops.gemm_skinny(x[I][:m], w2[i % L], out[D][:m], residual=res_in[:m])),
+                                      lambda m: (lambda i: ops.gemm_skinny_w8(x[I][:m], *q2[i % L], out[D][:m], residual=res_in[:m]))),
+            'head_133376x2048': (model.vocab_pad * D,
+                                 lambda m: (lambda i: ops.gemm_skinny(x[D][:m], emb, out[model.vocab_pad][:m])),
+                                 lambda m: (lambda i: ops.gemm_skinny_w8(x[D][:m], *qemb, out[model.vocab_pad][:m]))),
+        }
+        gemms = {}
+        for name, (welems, plain_of, fp8_of) in shapes.items():
+            reps = 8 if name.startswith('head') else 64
+            entry = {'weight_MB': {'plain': round(welems * 2 / 1e6, 2), 'fp8': round((welems + welems // (D if 'x2048' in name else I)) / 1e6, 2)}}
+            for m in ROWS:
+                forms = {'plain_us': plain_of(m), 'fp8_us': fp8_of(m)}
+                for fn in forms.values():
+                    timed(fn, 4)
+                got = {k: [] for k in forms}
+                for _ in range(args.rounds):
+                    for k, fn in forms.items():
+                        got[k].append(timed(fn, reps))
+                e = verdict({k: spread(v) for k, v in got.items()}, 'plain_us', 'fp8_us')
+                e['weight_TB_per_s'] = {k: round(entry['weight_MB'][k] / e[k + '_us']['median'], 2) for k in ('plain', 'fp8')}
+                entry[f'M{m}'] = e
+            gemms[name] = entry
+        res['gemms'] = gemms
+        per_step = lambda k, m: L * sum(gemms[n][f'M{m}'][k]['median'] for n in gemms if not n.startswith('head')) + gemms['head_133376x2048'][f'M{m}'][k]['median']  # noqa: E731
+        res['gemm_us_per_step_from_the_parts'] = {f'M{m}': {'plain': round(per_step('plain_us', m), 1), 'fp8': round(per_step('fp8_us', m), 1)} for m in ROWS}
+        del x, out, res_in
+
+        # whole small-batch steps on the same cache state (the lengths are put back before every block of steps)
+        steps, st, fidelity = 16, {}, {}
+        qn = model.quantize_weights(head=False)
+        for m in SMALL_ROWS:
+            cache, lens = _small_cache(model, m)
+            start = cache.lengths.clone()
+            tok = torch.randint(0, model.vocab_size, (m,), **dev)
+            slot = torch.arange(m, dtype=torch.int32, **dev)
+
+            def block(weights, keep=None):
+                cache.lengths.copy_(start)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    logits = model.decode_step(cache, tok, slot, small_batch=True, weight_quant=weights)
+                    if keep is not None:
+                        keep.append(logits[:, :model.vocab_size].float())
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / steps * 1e3      # ms per step, host clock: what a loop sees
+
+            kept = {'plain': [], 'fp8': [], 'fp8_bf16_head': []}
+            block(None, kept['plain']), block(qw, kept['fp8'])
+            if m == 8:      # teacher-forced: the same cache, the same tokens
+                block(qn, kept['fp8_bf16_head'])
+                absmax = max(float(t.abs().max()) for t in kept['plain'])
+                for k in ('fp8', 'fp8_bf16_head'):
+                    worst = max(float((a - b).abs().max()) for a, b in zip(kept['plain'], kept[k]))
+                    same = sum(int((a.argmax(-1) == b.argmax(-1)).sum()) for a, b in zip(kept['plain'], kept[k]))
+                    fidelity['teacher_forced_' + k] = {'steps': steps, 'rows': m, 'max_abs_dlogit': round(worst, 4), 'logits_absmax': round(absmax, 4),
+                                                       'max_abs_dlogit_over_logits_absmax': round(worst / absmax, 5),
+                                                       'share_of_equal_greedy_tokens': round(same / (steps * m), 4)}
+            del kept
+            rounds = {'plain_ms': [], 'fp8_ms': []}
+            for _ in range(args.rounds):
+                rounds['plain_ms'].append(block(None))
+                rounds['fp8_ms'].append(block(qw))
+            e = verdict({k: spread(v, 3) for k, v in rounds.items()}, 'plain_ms', 'fp8_ms')
+            e['prompt_tokens_mean'] = round(sum(lens) / m, 1)
+            st[f'rows_{m}'] = e
+            assert int(cache.errors) == 0
+            del cache
+        del qn
+        res['decode_step'] = dict(st, steps_per_block=steps, clock='host, synchronised around a block of steps')
+
+    # end to end: generate() of 1 and 8 prompts, small_batch both ways; the object built inside the call, and prebuilt
+    e2e, found = {}, {}
+    for n_p in (1, 8):
+        gen = torch.Generator().manual_seed(7)
+        lens = torch.randint(args.prompt_len - 100, args.prompt_len + 101, (n_p,), generator=gen).tolist()
+        prompts = [torch.randint(0, model.vocab_size, (n,), generator=gen) for n in lens]
+
+        def run(key, **kw):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            found[key] = generate(model, prompts, max_new_tokens=args.new, stop_token_ids=[], pad_id=0, small_batch=True, **kw)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        forms = {'plain_ms': dict(), 'fp8_built_in_the_call_ms': dict(weight_dtype='fp8'), 'fp8_prebuilt_ms': dict(weight_dtype='fp8', weight_quant=qw)}
+        for k, kw in forms.items():
+            run(k, **kw)
+        rounds = {k: [] for k in forms}
+        for _ in range(3):
+            for k, kw in forms.items():
+                rounds[k].append(run(k, **kw))
+        e = verdict({k: spread(v, 1) for k, v in rounds.items()}, 'plain_ms', 'fp8_prebuilt_ms')
+        same = [sum(a == b for a, b in zip(x.token_ids, y.token_ids)) for x, y in zip(found['plain_ms'], found['fp8_prebuilt_ms'])]
+        e['share_of_greedy_tokens_equal_position_by_position'] = round(sum(same) / (len(same) * args.new), 4)
+        e2e[f'prompts_{n_p}'] = e
+    res['generate_end_to_end'] = dict(e2e, new_tokens=args.new, rounds=3,
+                                      note='generate(small_batch=True) of n prompts of about --prompt-len tokens, --new new tokens, host clock, prefill included')
+    res['fidelity'] = dict(fidelity, note='recorded, not asserted.  The weights are random (normal, 0.02): next-token distributions are nearly flat, so a '
+                                          'greedy path flips on small changes.  Nothing here says anything about WER on a trained checkpoint.')
+    print(json.dumps(res, indent=1))
+    return res
+
+
 def part_small_batch_steps():
     """--trace-steps small-batch decode steps of --rows rows, for a kernel trace in a run of its own."""
     import torch
@@ -1337,6 +1516,8 @@ elif args.part == 'split_kv':
     res = part_split_kv()
 elif args.part == 'kv_fp8':
     res = part_kv_fp8()
+elif args.part == 'weight_fp8':
+    res = part_weight_fp8()
 elif args.part == 'small_batch_steps':
     part_small_batch_steps()
     res = None
