@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 27 /* 27: + ssi_weight_quant_fp8, ssi_gemm_skinny_w8, ssi_gemm_skinny_rope_w8, ssi_gemm_skinny_swiglu_w8 (weight matrices as e4m3 codes with one power-of-two exponent per row, and the skinny GEMMs over them: FP8 weights for small-batch decoding; opt-in)
+#define SSI_ABI_VERSION 28 /* 28: + ssi_decode_sample_rows, ssi_decode_sample_pen_rows (the two sampling entries with the step and the draw parameters per row, from device arrays: rows of different ages and requests in one launch; opt-in)
+                           * 27: + ssi_weight_quant_fp8, ssi_gemm_skinny_w8, ssi_gemm_skinny_rope_w8, ssi_gemm_skinny_swiglu_w8 (weight matrices as e4m3 codes with one power-of-two exponent per row, and the skinny GEMMs over them: FP8 weights for small-batch decoding; opt-in)
                            * 26: + ssi_kv_store_fp8, ssi_attn_decode_fp8, ssi_attn_decode_beam_fp8, ssi_attn_decode_split_fp8, ssi_attn_decode_beam_split_fp8 (a K/V cache of e4m3 codes with one power-of-two exponent per line, and decode attention over it; opt-in)
                            * 25: + ssi_attn_decode_split, ssi_attn_decode_beam_split, ssi_attn_decode_split_span, ssi_attn_decode_split_workspace (split-KV decode attention: the keys of a row over several workgroups, a merge launch behind them; opt-in)
                            * 24: + ssi_gemm_skinny, ssi_gemm_skinny_rope, ssi_gemm_skinny_swiglu (weight-streaming bf16 GEMMs for 1 to 64 rows: small-batch decoding; opt-in)
@@ -471,6 +472,31 @@ int ssi_decode_sample_pen(const void* logits, int64_t ld, int64_t rows, int64_t 
                           const int32_t* prompt_ids, int64_t ld_prompt, const int32_t* prompt_len, const int32_t* prompt_row, int64_t n_prompts,
                           const int64_t* gen_ids, int64_t ld_gen, double repetition_penalty, double frequency_penalty, double presence_penalty,
                           int32_t* n_bad, int dtype, void* stream);
+
+/* ssi_decode_sample and ssi_decode_sample_pen with the step and the draw parameters PER ROW (ABI v28): rows of one launch that are at different
+ * steps of their sequences (a refilled pool) or belong to requests with different settings.  Four device arrays of one entry per row:
+ *   step              uint32, required;
+ *   temperature_rows  double, NULL ok: the scalar `temperature` then holds for all rows;
+ *   top_k_rows        int64,  NULL ok: the scalar `top_k`;
+ *   top_p_rows        double, NULL ok: the scalar `top_p`.
+ * THE DEFINITION: row r has the bits of row r of the scalar entry launched with (temperature[r], top_k[r], top_p[r], step[r]) — token, logprob
+ * and n_kept.  fl(1 / T) and fl(log2 e / T) are formed on the device by the scalar entry's host expression, an IEEE fp64 quotient rounded once
+ * to fp32.  One workgroup owns one row, so whether the radix passes run is uniform over it.
+ * A row whose temperature is not finite and > 0, or whose top_p lies outside (0, 1], fails by itself: it writes what a row with nothing allowed
+ * writes (token -1, logprob 0, n_kept -1) and, in the penalised form, builds no history and counts nothing into *n_bad; no other row changes.
+ * SSI_ERR_ARG before any launch: a NULL step; a scalar outside its range where its array is NULL (with the array, the scalar is not read);
+ * and everything the scalar entry refuses otherwise. */
+int ssi_decode_sample_rows(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow, const uint32_t* allow_early,
+                           const int32_t* n_generated, int32_t min_new, double temperature, int64_t top_k, double top_p, uint64_t seed,
+                           const uint32_t* step, const double* temperature_rows, const int64_t* top_k_rows, const double* top_p_rows,
+                           const uint32_t* sequence, int64_t* token, float* logprob, int32_t* n_kept, int dtype, void* stream);
+int ssi_decode_sample_pen_rows(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow, const uint32_t* allow_early,
+                               const int32_t* n_generated, int32_t min_new, double temperature, int64_t top_k, double top_p, uint64_t seed,
+                               const uint32_t* step, const double* temperature_rows, const int64_t* top_k_rows, const double* top_p_rows,
+                               const uint32_t* sequence, int64_t* token, float* logprob, int32_t* n_kept,
+                               const int32_t* prompt_ids, int64_t ld_prompt, const int32_t* prompt_len, const int32_t* prompt_row, int64_t n_prompts,
+                               const int64_t* gen_ids, int64_t ld_gen, double repetition_penalty, double frequency_penalty, double presence_penalty,
+                               int32_t* n_bad, int dtype, void* stream);
 
 /* ---- K7  SwiGLU elementwise (torchtune FeedForward: w2(silu(w1 x) * w3 x)) ------------------------------------------ */
 /* gu: [rows, 2*inter] = [gate | up]; act[rows, inter] = silu(gate) * up */

@@ -369,6 +369,95 @@ __global__ __launch_bounds__(SEL_THREADS) void sample_pen_kernel(const T* __rest
                   logprob, n_kept, vec_ok, pen);
 }
 
+// ssi_decode_sample_rows / ssi_decode_sample_pen_rows (ABI v28): the draw parameters and the step of row r come from device arrays (a NULL
+// array: the launch's scalar).  One workgroup owns one row, so what it reads here is uniform over it, as the scalars are over a launch.
+struct SmpRows {
+    const uint32_t* step;
+    const double* temperature;
+    const int64_t* top_k;
+    const double* top_p;
+};
+
+struct SmpDraw {
+    float inv_t, sc;
+    int top_k;
+    double top_p;
+    uint32_t step;
+    bool ok;
+};
+
+// Row r's parameters, by the host expressions of the scalar entries: fl(1 / T) and fl(log2 e / T) are fp64 quotients rounded once to fp32
+// (IEEE division and conversion on the device as on the host), top_k outside (0, vocab) is "off".  ok: T finite and > 0, top_p in (0, 1].
+__device__ __forceinline__ SmpDraw smp_row_draw(const SmpRows& rw, int64_t r, int vocab, double temperature, int64_t top_k, double top_p) {
+    const double t = rw.temperature ? rw.temperature[r] : temperature;
+    const double p = rw.top_p ? rw.top_p[r] : top_p;
+    const int64_t k = rw.top_k ? rw.top_k[r] : top_k;
+    SmpDraw d;
+    d.ok = t > 0.0 && t < (double)INFINITY && p > 0.0 && p <= 1.0;
+    d.inv_t = (float)(1.0 / t);
+    d.sc = (float)(1.44269504088896340736 / t);
+    d.top_k = k <= 0 || k >= (int64_t)vocab ? 0 : (int)k;
+    d.top_p = p;
+    d.step = rw.step[r];
+    return d;
+}
+
+// A row whose own parameters are refused fails alone: what a row with nothing allowed writes.
+__device__ __forceinline__ void smp_row_refused(int64_t r, int64_t* token, float* logprob, int32_t* n_kept) {
+    if (threadIdx.x == 0) {
+        token[r] = -1;
+        if (logprob) logprob[r] = 0.f;
+        if (n_kept) n_kept[r] = -1;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(SEL_THREADS) void sample_rows_kernel(const T* __restrict__ logits, int64_t ld, int vocab,
+                                                                  const uint32_t* __restrict__ allow, const uint32_t* __restrict__ allow_early,
+                                                                  const int32_t* __restrict__ n_generated, int32_t min_new, double temperature,
+                                                                  int64_t top_k, double top_p, uint32_t seed_lo, uint32_t seed_hi, SmpRows rw,
+                                                                  const uint32_t* __restrict__ sequence, int64_t* __restrict__ token,
+                                                                  float* __restrict__ logprob, int32_t* __restrict__ n_kept, int vec_ok) {
+    const SmpDraw d = smp_row_draw(rw, blockIdx.x, vocab, temperature, top_k, top_p);
+    if (!d.ok) {
+        smp_row_refused(blockIdx.x, token, logprob, n_kept);
+        return;
+    }
+    sample_row<T>(logits, ld, vocab, allow, allow_early, n_generated, min_new, d.inv_t, d.sc, d.top_k, d.top_p, seed_lo, seed_hi, d.step, sequence,
+                  token, logprob, n_kept, vec_ok, PenNone{});
+}
+
+template <typename T>
+__global__ __launch_bounds__(SEL_THREADS) void sample_rows_pen_kernel(const T* __restrict__ logits, int64_t ld, int vocab,
+                                                                      const uint32_t* __restrict__ allow, const uint32_t* __restrict__ allow_early,
+                                                                      const int32_t* __restrict__ n_generated, int32_t min_new, double temperature,
+                                                                      int64_t top_k, double top_p, uint32_t seed_lo, uint32_t seed_hi, SmpRows rw,
+                                                                      const uint32_t* __restrict__ sequence, int64_t* __restrict__ token,
+                                                                      float* __restrict__ logprob, int32_t* __restrict__ n_kept, int vec_ok,
+                                                                      PenArgs pa) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t pen_lds[];
+    const SmpDraw d = smp_row_draw(rw, blockIdx.x, vocab, temperature, top_k, top_p);
+    if (!d.ok) {                                          // (before the history is built: a refused row counts nothing into n_bad)
+        smp_row_refused(blockIdx.x, token, logprob, n_kept);
+        return;
+    }
+    const PenOn pen = pen_build(pa, n_generated, blockIdx.x, vocab, threadIdx.x, pen_lds);
+    sample_row<T>(logits, ld, vocab, allow, allow_early, n_generated, min_new, d.inv_t, d.sc, d.top_k, d.top_p, seed_lo, seed_hi, d.step, sequence,
+                  token, logprob, n_kept, vec_ok, pen);
+}
+
+// What the two _rows entries refuse before a launch: the plain entry's checks, with a scalar checked only where no array stands for it.
+int smp_rows_check(const void* logits, int64_t ld, int64_t rows, int64_t vocab, int32_t min_new, double temperature, double top_p,
+                   const uint32_t* step, const double* temperature_rows, const double* top_p_rows, const uint32_t* sequence,
+                   const int64_t* token, int dtype) {
+    SSI_CHECK_ARG(rows >= 0 && rows < (1LL << 31) && (dtype == SSI_F32 || dtype == SSI_BF16));
+    SSI_CHECK_ARG(logits && token && vocab >= 1 && ld >= vocab && vocab < (1LL << 31) && min_new >= 0);
+    SSI_CHECK_ARG(temperature_rows != nullptr || (temperature > 0.0 && temperature < (double)INFINITY));
+    SSI_CHECK_ARG(top_p_rows != nullptr || (top_p > 0.0 && top_p <= 1.0));
+    SSI_CHECK_ARG(sequence != nullptr && step != nullptr);
+    return SSI_OK;
+}
+
 }  // namespace
 
 extern "C" int ssi_decode_sample(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow, const uint32_t* allow_early,
@@ -416,6 +505,50 @@ extern "C" int ssi_decode_sample_pen(const void* logits, int64_t ld, int64_t row
                                                  (size_t)pen_lds_bytes(vocab, ld_gen), (hipStream_t)stream, (const T*)logits, ld, (int)vocab, allow,
                                                  allow_early, n_generated, min_new, inv_t, sc, k, top_p, (uint32_t)seed, (uint32_t)(seed >> 32), step,
                                                  sequence, token, logprob, n_kept, vec_ok, pa));
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+extern "C" int ssi_decode_sample_rows(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow,
+                                      const uint32_t* allow_early, const int32_t* n_generated, int32_t min_new, double temperature, int64_t top_k,
+                                      double top_p, uint64_t seed, const uint32_t* step, const double* temperature_rows, const int64_t* top_k_rows,
+                                      const double* top_p_rows, const uint32_t* sequence, int64_t* token, float* logprob, int32_t* n_kept,
+                                      int dtype, void* stream) {
+    const int rc = smp_rows_check(logits, ld, rows, vocab, min_new, temperature, top_p, step, temperature_rows, top_p_rows, sequence, token, dtype);
+    if (rc != SSI_OK) return rc;
+    if (rows == 0) return SSI_OK;
+    const int64_t esize = dtype == SSI_BF16 ? 2 : 4;
+    const int vec_ok = ((uintptr_t)logits & 15) == 0 && (ld * esize) % 16 == 0;
+    const SmpRows rw{step, temperature_rows, top_k_rows, top_p_rows};
+    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(sample_rows_kernel<T>, dim3((unsigned)rows), dim3(SEL_THREADS), 0, (hipStream_t)stream,
+                                                 (const T*)logits, ld, (int)vocab, allow, allow_early, n_generated, min_new, temperature, top_k,
+                                                 top_p, (uint32_t)seed, (uint32_t)(seed >> 32), rw, sequence, token, logprob, n_kept, vec_ok));
+    SSI_LAUNCH_CHECK();
+    return SSI_OK;
+}
+
+extern "C" int ssi_decode_sample_pen_rows(const void* logits, int64_t ld, int64_t rows, int64_t vocab, const uint32_t* allow,
+                                          const uint32_t* allow_early, const int32_t* n_generated, int32_t min_new, double temperature,
+                                          int64_t top_k, double top_p, uint64_t seed, const uint32_t* step, const double* temperature_rows,
+                                          const int64_t* top_k_rows, const double* top_p_rows, const uint32_t* sequence, int64_t* token,
+                                          float* logprob, int32_t* n_kept, const int32_t* prompt_ids, int64_t ld_prompt, const int32_t* prompt_len,
+                                          const int32_t* prompt_row, int64_t n_prompts, const int64_t* gen_ids, int64_t ld_gen,
+                                          double repetition_penalty, double frequency_penalty, double presence_penalty, int32_t* n_bad, int dtype,
+                                          void* stream) {
+    int rc = smp_rows_check(logits, ld, rows, vocab, min_new, temperature, top_p, step, temperature_rows, top_p_rows, sequence, token, dtype);
+    if (rc != SSI_OK) return rc;
+    PenArgs pa;
+    rc = pen_check(pa, vocab, n_generated, prompt_ids, ld_prompt, prompt_len, prompt_row, n_prompts, gen_ids, ld_gen, repetition_penalty,
+                   frequency_penalty, presence_penalty, n_bad);
+    if (rc != SSI_OK) return rc;
+    if (rows == 0) return SSI_OK;
+    const int64_t esize = dtype == SSI_BF16 ? 2 : 4;
+    const int vec_ok = ((uintptr_t)logits & 15) == 0 && (ld * esize) % 16 == 0;
+    const SmpRows rw{step, temperature_rows, top_k_rows, top_p_rows};
+    SSI_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(sample_rows_pen_kernel<T>, dim3((unsigned)rows), dim3(SEL_THREADS),
+                                                 (size_t)pen_lds_bytes(vocab, ld_gen), (hipStream_t)stream, (const T*)logits, ld, (int)vocab, allow,
+                                                 allow_early, n_generated, min_new, temperature, top_k, top_p, (uint32_t)seed,
+                                                 (uint32_t)(seed >> 32), rw, sequence, token, logprob, n_kept, vec_ok, pa));
     SSI_LAUNCH_CHECK();
     return SSI_OK;
 }

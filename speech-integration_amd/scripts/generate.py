@@ -15,7 +15,7 @@ try:  # real Hydra if the environment has it, else the built-in composer with th
 except ImportError:
     from ssi.config import main as main_decorator
 
-from ssi.generate import check_greedy, check_kv_cache_dtype, check_penalties, check_weight_dtype, check_sampling, generate_file
+from ssi.generate import check_continuous, check_greedy, check_kv_cache_dtype, check_penalties, check_weight_dtype, check_sampling, generate_file
 
 LOGGER = logging.getLogger(__name__)
 
@@ -59,6 +59,7 @@ def main(cfg):
     draw = dict(check_sampling(params), sample=True, seed=int(cfg.gen.get("seed") or 0)) if sampled else {}
     if not sampled:
         check_greedy(params)
+    pool = check_continuous(cfg.gen.get("continuous"), cfg.gen.get("admit_min"), int(cfg.gen.get("beam_width") or 1), int(draw.get("n", 1)))
     from ssi.model import get_device, get_dtype
     from ssi.train_utils import resolve_n_dsus
     from ssi.trainer import Trainer
@@ -92,6 +93,7 @@ def main(cfg):
         constraints["kv_cache_dtype"] = "fp8"
     if check_weight_dtype(cfg.gen.get("weight_dtype"), bool(cfg.gen.get("small_batch") or False)) is not None:   # gen.weight_dtype: fp8 (needs gen.small_batch); auto (or the key absent) is absent from the call
         constraints["weight_dtype"] = "fp8"
+    constraints.update(pool)          # gen.continuous: batch_size is a pool of rows that is refilled; false (or the key absent) is absent from the call
     summary = generate_file(t.model, t.tokenizer, None if prompts is not None else str(cfg.gen.input), out_path,
                             max_new_tokens=int(cfg.sampling_params.max_tokens), stop_token_ids=None if stop is None else [int(s) for s in stop],
                             tokenizer_decoding={k: cfg.tokenizer_decoding[k] for k in cfg.tokenizer_decoding}, prompts=prompts, ids=ids,

@@ -20,7 +20,7 @@ SSI_F32, SSI_BF16 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 IMPL_AUTO, IMPL_GENERIC, IMPL_MFMA, IMPL_MFMA_WG8 = 0, 1, 2, 3
 TILES_STATIC, TILES_DYNAMIC = 0, 1
-ABI_VERSION = 27
+ABI_VERSION = 28
 GEMM_SKINNY_MAX_ROWS = 64
 DECODE_PENALTY_LDS_MAX = 57344
 ADAMW_MAX_SEGS = 128
@@ -72,6 +72,10 @@ PROTOTYPES = {
                                       c_double, c_double, c_double, _P, c_int, _P]),
     "ssi_decode_sample_pen": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, c_int32, c_double, c_int64, c_double, c_uint64, c_uint32, _P, _P, _P,
                                       _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_double, c_double, c_double, _P, c_int, _P]),
+    "ssi_decode_sample_rows": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, c_int32, c_double, c_int64, c_double, c_uint64, _P, _P, _P, _P, _P,
+                                       _P, _P, _P, c_int, _P]),
+    "ssi_decode_sample_pen_rows": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, c_int32, c_double, c_int64, c_double, c_uint64, _P, _P, _P, _P,
+                                           _P, _P, _P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_double, c_double, c_double, _P, c_int, _P]),
     "ssi_attn_decode_beam": (c_int, [_P, c_int64, _P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_int64, _P, _P, c_int64,
                                      c_int, c_int, c_int, _P, c_int, _P]),
     "ssi_attn_decode_split_span": (c_int, [c_int, c_int]),

@@ -33,9 +33,16 @@ Penalties (vLLM's ``repetition_penalty``, ``frequency_penalty`` and ``presence_p
 ``ssi_decode_sample_pen``, which choose on the penalised row — built in the kernel from the group's prompt table and the loop's own output
 tensor, never stored — and report the log-probability (and the rank) of the raw one.  With all three neutral nothing of this runs.
 
-Out of scope: per-request sampling parameters within one launch, ``n > 8`` and ``best_of``, sampling
+Continuous batching (``continuous=True`` of ``generate`` and of ``sample`` with ``n = 1``; ``gen.continuous`` in ``conf/generate.yaml``):
+``batch_size`` rows and cache slots form a pool; at a read-back the finished rows are harvested and queued prompts prefilled into their
+slots (``prefill(slots=...)``), by a schedule that is host code (``PoolSchedule``).  The rows of a step then have different ages, so the
+sampler runs on ``ssi_decode_sample_rows`` / ``ssi_decode_sample_pen_rows``, which take the step (and the draw parameters) per row; the same
+entries serve per-prompt ``temperature`` / ``top_k`` / ``top_p`` lists in either mode.  Without the flag nothing of this runs.
+
+Out of scope: per-row penalties, per-line parameters in the prompts JSONL, ``n > 8`` and ``best_of``, sampling
 inside beam search, ``beam_width > 8``, sharing the prompt's K / V read among a prompt's beams, beam
-search under data parallelism, continuous batching (refilling freed slots), paged caches, generation under data parallelism, and WER
+search under data parallelism, pools for ``n > 1`` and for beams, paged caches, prefill rows mixed into a decode step (chunked prefill),
+moving a draining pool of few live rows onto the skinny path, HIP graphs, generation under data parallelism, and WER
 itself (its text normaliser is the reference's dependency; the JSONL written here is what its ``wer.py`` reads)."""
 
 from __future__ import annotations
@@ -55,11 +62,13 @@ from .constants import CROSS_ENTROPY_IGNORE_IDX
 LOGGER = logging.getLogger(__name__)
 
 __all__ = ["Generation", "READBACK_EVERY", "MAX_BEAM_WIDTH", "MAX_SAMPLES", "plan_groups", "allowed_mask", "generate", "beam_search", "sample",
-           "generate_file", "output_record", "check_greedy", "check_sampling", "check_penalties"]
+           "generate_file", "output_record", "check_greedy", "check_sampling", "check_penalties", "check_continuous", "ADMIT_MIN_DEFAULT", "PoolSchedule", "simulate_pool",
+           "static_steps"]
 
 READBACK_EVERY = 8    # decode steps between two read-backs of "has every row of the group finished?"
 MAX_BEAM_WIDTH = 8    # the k of ssi_topk_logprob
 MAX_SAMPLES = 8       # samples per prompt of ``sample``: the rows of a prompt in ``decode_step_beam``, as many as beams
+ADMIT_MIN_DEFAULT = 32   # ``admit_min=None`` of the pool loop: the free rows an admission waits for (how it was chosen: README, "Continuous batching")
 
 
 @dataclass
@@ -320,6 +329,206 @@ def _token_loop(choose, started, caches, refused: str, prompt_len: list[int], ma
                        stop_reason=host_stop[r] if host_stop[r] >= 0 else None, prompt_len=prompt_len[r], **extras[r]) for r in range(rows)]
 
 
+# ---- continuous batching: the pool of rows, refilled as sequences finish -------------------------------------------------------------
+class PoolSchedule:
+    """The schedule of a pool of ``pool`` rows (and cache slots), host only: which queued prompt enters which free row, and when.  The pool
+    loop drives it with what the device reported; ``simulate_pool`` drives it with generated lengths known after the fact.
+
+    ``order``: the queue, prompt numbers in the order they are admitted (``plan_groups``' order).  One decode step is one choice of a token by
+    every live row.  After a step the host reads the device back (``reads_back``) every ``cadence`` steps, and also at the step by which every
+    owned row must have ended (``max_new`` steps after its admission: a read-back that cannot come too early).  At a read-back the finished
+    rows are released, and ``admit`` hands queued prompts the lowest free rows when ``free >= min(admit_min, queued)`` or no row is alive.
+    ``report``: ``decode_steps``, ``row_steps_live`` (one per generated token), ``row_steps_total = decode_steps * pool``, ``admissions``."""
+
+    def __init__(self, order: Sequence[int], pool: int, admit_min: int, max_new: int, cadence: int = READBACK_EVERY):
+        pool, admit_min, max_new, cadence = int(pool), int(admit_min), int(max_new), int(cadence)
+        if pool < 1 or admit_min < 1 or max_new < 1 or cadence < 1:
+            raise ValueError(f"PoolSchedule: pool, admit_min, max_new and cadence must be >= 1 (got {pool}, {admit_min}, {max_new}, {cadence})")
+        self.queue, self.pool, self.admit_min, self.max_new, self.cadence = [int(i) for i in order], pool, admit_min, max_new, cadence
+        if len(set(self.queue)) != len(self.queue):
+            raise ValueError("PoolSchedule: a prompt is queued twice")
+        self.next = 0                                   # the queue's head
+        self.owner = [-1] * pool                        # the prompt of a row; -1: free
+        self.deadline = [0] * pool                      # the step count by which an owned row has ended
+        self.decode_steps, self.row_steps_live = 0, 0
+        self.admissions: list[list[tuple[int, int]]] = []      # per admission: (prompt, row)
+        self.slot_of: dict[int, int] = {}
+
+    @property
+    def queued(self) -> int:
+        return len(self.queue) - self.next
+
+    def owned(self) -> list[int]:
+        return [r for r, o in enumerate(self.owner) if o >= 0]
+
+    def done(self) -> bool:
+        return self.queued == 0 and not self.owned()
+
+    def admit(self) -> list[tuple[int, int]]:
+        free = [r for r, o in enumerate(self.owner) if o < 0]
+        if self.queued == 0 or not free or (len(free) < min(self.admit_min, self.queued) and len(free) < self.pool):
+            return []
+        pairs = []
+        for r in free[:self.queued]:
+            i = self.queue[self.next]
+            self.next += 1
+            self.owner[r], self.deadline[r], self.slot_of[i] = i, self.decode_steps + self.max_new, r
+            pairs.append((i, r))
+        self.admissions.append(pairs)
+        return pairs
+
+    def stepped(self) -> None:
+        self.decode_steps += 1
+
+    def reads_back(self) -> bool:
+        owned = self.owned()
+        return self.decode_steps % self.cadence == 0 or (bool(owned) and self.decode_steps >= max(self.deadline[r] for r in owned))
+
+    def release(self, row: int, n_generated: int) -> int:
+        i = self.owner[row]
+        if i < 0:
+            raise ValueError(f"PoolSchedule: row {row} is free")
+        self.owner[row] = -1
+        self.row_steps_live += int(n_generated)
+        return i
+
+    def report(self) -> dict[str, int]:
+        return {"decode_steps": self.decode_steps, "row_steps_live": self.row_steps_live, "row_steps_total": self.decode_steps * self.pool,
+                "admissions": len(self.admissions)}
+
+
+def simulate_pool(generated: Sequence[int], order: Sequence[int], pool: int, admit_min: int, max_new: int,
+                  cadence: int = READBACK_EVERY) -> PoolSchedule:
+    """The pool loop's schedule on the host: ``generated[i]`` (1 .. ``max_new``) is the number of tokens prompt ``i`` turns out to generate.
+    Returns the finished ``PoolSchedule``: its ``admissions``, ``slot_of`` and ``report()`` are what the loop on the device arrives at."""
+    sched = PoolSchedule(order, pool, admit_min, max_new, cadence)
+    left = [0] * sched.pool
+    for i, r in sched.admit():
+        left[r] = int(generated[i])
+    while not sched.done():
+        sched.stepped()
+        for r in sched.owned():
+            left[r] = max(left[r] - 1, 0)
+        if sched.reads_back():
+            for r in sched.owned():
+                if left[r] == 0:
+                    sched.release(r, generated[sched.owner[r]])
+            for i, r in sched.admit():
+                left[r] = int(generated[i])
+    return sched
+
+
+def static_steps(generated: Sequence[int], groups: Sequence[Sequence[int]], max_new: int, cadence: int = READBACK_EVERY) -> int:
+    """The decode steps of the static groups for the same lengths: a group runs until a read-back (every ``cadence`` steps) finds every row
+    finished, ``max_new`` at the most — ``_token_loop``'s rule."""
+    return sum(min(-(-max(generated[i] for i in g) // cadence) * cadence, max_new) for g in groups)
+
+
+def _run_pool(model, prompts: Sequence[Any], pool: int, max_new: int, stop_token_ids: Sequence[int], masks, min_new: int, kv_dtype, admit_min,
+              make_choose, refused: str, pad_id: int, small_batch: bool, report: dict | None, split_kv: bool, weights,
+              stats: dict | None) -> list[Generation]:
+    """``generate`` and ``sample`` (``n == 1``) under ``continuous=True``: ONE cache of ``pool`` slots, row ``r`` of every step is whatever
+    sequence owns slot ``r`` (a free row is inert), and at a read-back the finished rows are harvested and queued prompts admitted into the
+    free rows by ``PoolSchedule`` — one ``prefill(slots=...)``, whose logits rows replace those rows of the step's logits; the rows' state is
+    reset, and their next choice is their step 0.  ``make_choose(seqs, pool, con)`` builds the chooser over the call's prompts.  Results in
+    INPUT order; ``stats`` (a dict, or None) receives the schedule's report."""
+    seqs = [torch.as_tensor(p, dtype=torch.int64).reshape(-1) for p in prompts]
+    lens = [int(s.numel()) for s in seqs]
+    if stats is not None:
+        stats.update(continuous=True, decode_steps=0, row_steps_live=0, row_steps_total=0, admissions=0)
+    if not seqs:
+        return []
+    pool = min(int(pool), len(seqs))
+    sched = PoolSchedule([i for g in plan_groups(lens, pool) for i in g], pool, ADMIT_MIN_DEFAULT if admit_min is None else admit_min, max_new)
+    model.check_generation_lengths(lens, max_new, len(seqs), max(lens) + max_new)
+    dev = model.device
+    stop = torch.tensor(sorted({int(t) for t in stop_token_ids}), dtype=torch.int64, device=dev)
+    results: list = [None] * len(seqs)
+    was_training = bool(model.training)
+    model.eval()
+    try:
+        with torch.inference_mode():
+            cache, con = _new_cache(model, pool, max(lens) + max_new, kv_dtype), _constraint(masks, min_new, dev)
+            prefill_kw, step_kw = _small_batch_kw(model, pool, small_batch, report, split_kv, weights)
+            choose = make_choose(seqs, pool, con)
+            own = torch.arange(pool, dtype=torch.int32, device=dev)
+            none = torch.full_like(own, -1)
+            alive = torch.zeros(pool, dtype=torch.bool, device=dev)
+            out = torch.full((pool, max_new), pad_id, dtype=torch.int64, device=dev)
+            n_gen = torch.zeros(pool, dtype=torch.int32, device=dev)
+            stop_tok = torch.full((pool,), -1, dtype=torch.int64, device=dev)
+            logits = None
+
+            def admit(pairs: list[tuple[int, int]]) -> None:
+                nonlocal logits
+                rows = torch.tensor([r for _, r in pairs], dtype=torch.int64, device=dev)
+                new = model.prefill(cache, [seqs[i] for i, _ in pairs], max_new_tokens=max_new, slots=[r for _, r in pairs], **prefill_kw)
+                if logits is None:
+                    logits = new.new_zeros((pool, new.shape[1]))
+                logits[rows] = new
+                n_gen[rows], stop_tok[rows], out[rows], alive[rows] = 0, -1, pad_id, True
+                choose.admit(rows, [i for i, _ in pairs])
+
+            def harvest(host_alive: list[int], host_n: list[int]) -> None:
+                done = [r for r in sched.owned() if not host_alive[r]]
+                if not done:
+                    return
+                rows = torch.tensor(done, dtype=torch.int64, device=dev)
+                host_out, host_stop = out[rows].cpu(), stop_tok[rows].cpu().tolist()
+                extras = choose.harvest(rows, [host_n[r] for r in done])
+                for j, r in enumerate(done):
+                    i = sched.release(r, host_n[r])
+                    results[i] = Generation(token_ids=host_out[j, :host_n[r]].tolist(), finish_reason="stop" if host_stop[j] >= 0 else "length",
+                                            stop_reason=host_stop[j] if host_stop[j] >= 0 else None, prompt_len=lens[i], **extras[j])
+
+            admit(sched.admit())
+            limit = (len(seqs) + 1) * (max_new + sched.cadence)      # (every admitted row ends within max_new steps: never reached)
+            while True:
+                tok = choose(sched.decode_steps, logits, alive, n_gen, out)
+                at = n_gen.long().clamp(max=max_new - 1)[:, None]
+                out.scatter_(1, at, torch.where(alive, tok, out.gather(1, at)[:, 0])[:, None])
+                n_gen += alive
+                stopped = alive & torch.isin(tok, stop)
+                stop_tok = torch.where(stopped, tok, stop_tok)
+                alive = alive & ~stopped & (n_gen < max_new)
+                sched.stepped()
+                pairs, idle = [], False
+                if sched.reads_back():                      # the read-back: one copy
+                    host = torch.stack([alive.to(torch.int32), n_gen]).cpu().tolist()
+                    harvest(*host)
+                    if sched.done():
+                        break
+                    idle = not sched.owned()
+                    pairs = sched.admit()
+                if sched.decode_steps > limit:
+                    raise RuntimeError("continuous batching: the pool did not drain (a row outlived max_new_tokens)")
+                if not idle:                                # (nothing alive: the admitted rows' logits are all the next step reads)
+                    logits = model.decode_step(cache, torch.where(alive, tok, torch.zeros_like(tok)), torch.where(alive, own, none), **step_kw)
+                if pairs:
+                    admit(pairs)
+            errors = int(cache.errors)
+            if errors != 0:
+                raise RuntimeError(refused.format(errors))
+            choose.close()
+    finally:
+        if was_training:
+            model.train()
+    if stats is not None:
+        stats.update(sched.report())
+    return results
+
+
+def _check_continuous(who: str, continuous, admit_min) -> bool:
+    """``continuous`` a bool, ``admit_min`` None (``ADMIT_MIN_DEFAULT``) or an integer >= 1 and only with ``continuous`` (``ValueError``)."""
+    if not isinstance(continuous, bool):
+        raise ValueError(f"{who}: continuous = {continuous!r}: True or False")
+    if admit_min is not None and (isinstance(admit_min, bool) or not isinstance(admit_min, int) or admit_min < 1):
+        raise ValueError(f"{who}: admit_min = {admit_min!r}: None or an integer >= 1")
+    if admit_min is not None and not continuous:
+        raise ValueError(f"{who}: admit_min without continuous=True")
+    return continuous
+
+
 # ---- the choosers: the token of a step ---------------------------------------------------------------------------------------------
 class _Argmax:
     """``generate`` without constraint or penalty: ``argmax`` over the real columns, torch's first-occurrence rule.  With ``logprobs`` the
@@ -344,10 +553,21 @@ class _Argmax:
         return tok
 
     def finish(self, host_n: list[int]) -> list[dict]:
-        if int(self.not_top) != 0:
-            raise RuntimeError(f"generate: on {int(self.not_top)} rows the chosen token was not ranked first by ce_fwd_metrics")
+        self.close()
         host_cum = self.cum.cpu().tolist() if self.logprobs else [None] * self.rows
         return [dict(cumulative_logprob=c) for c in host_cum]
+
+    # the pool loop (``continuous=True``): a row starts a new sequence, a finished row hands over its fields, the end-of-call check runs once
+    def admit(self, rows: Tensor, prompts: list[int]) -> None:
+        self.cum[rows] = 0.0
+
+    def harvest(self, rows: Tensor, host_n: list[int]) -> list[dict]:
+        host_cum = self.cum[rows].cpu().tolist() if self.logprobs else [None] * len(host_n)
+        return [dict(cumulative_logprob=c) for c in host_cum]
+
+    def close(self) -> None:
+        if int(self.not_top) != 0:
+            raise RuntimeError(f"generate: on {int(self.not_top)} rows the chosen token was not ranked first by ce_fwd_metrics")
 
 
 class _Selection:
@@ -383,6 +603,16 @@ class _Selection:
             return none
         return none | ~(con.allow[at] if con.early is None else torch.where(n_gen < con.min_new, con.early[at], con.allow[at]))
 
+    def admit(self, rows: Tensor, prompts: list[int]) -> None:
+        """The pool loop: ``rows`` start the sequences of ``prompts`` (their places in the input, which are the lines of the call's one prompt
+        table); a chooser resets its own per-row sums on top."""
+        self.cum[rows] = 0.0
+        if self.hist is not None:
+            self.hist["prompt_row"][rows] = torch.tensor(prompts, dtype=torch.int32).to(rows.device)
+
+    def close(self) -> None:
+        self.check()
+
     def check(self) -> None:
         if self.hist is not None and int(self.n_bad) != 0:
             raise RuntimeError(f"{self.who}: on {int(self.n_bad)} row-steps the penalised selection met an id outside the vocabulary in the row's history")
@@ -395,10 +625,13 @@ class _Select(_Selection):
     log-probability over ALL columns and its rank in the raw row (not 0: the mask or the penalties changed the choice)."""
     refusal = "decode_select chose no token or one that is not allowed"
 
-    def __init__(self, model, seqs: list[Tensor], con: _Constraint | None, pen: _Penalty | None, logprobs: bool):
-        super().__init__("generate", model, seqs, len(seqs), con, pen, logprobs)
-        self.row_rank = torch.empty(len(seqs), dtype=torch.int32, device=model.device)
-        self.n_con = torch.zeros(len(seqs), dtype=torch.int64, device=model.device)
+    def __init__(self, model, seqs: list[Tensor], con: _Constraint | None, pen: _Penalty | None, logprobs: bool, pool: int | None = None):
+        """``pool`` (the pool loop): that many rows over the prompt table of the whole call, the line of a row set when it is admitted."""
+        rows = len(seqs) if pool is None else pool
+        line = torch.zeros(rows, dtype=torch.int32, device=model.device) if pool is not None and pen is not None else None
+        super().__init__("generate", model, seqs, rows, con, pen, logprobs, prompt_row=line)
+        self.row_rank = torch.empty(rows, dtype=torch.int32, device=model.device)
+        self.n_con = torch.zeros(rows, dtype=torch.int64, device=model.device)
 
     def __call__(self, t: int, logits: Tensor, alive: Tensor, n_gen: Tensor, out: Tensor) -> Tensor:
         select = ops.decode_select if self.hist is None else ops.decode_select_pen
@@ -415,6 +648,14 @@ class _Select(_Selection):
         host_cum = self.cum.cpu().tolist() if self.row_lp is not None else [None] * len(host_n)
         return [dict(cumulative_logprob=c, n_constrained=k) for c, k in zip(host_cum, self.n_con.cpu().tolist())]
 
+    def admit(self, rows: Tensor, prompts: list[int]) -> None:
+        super().admit(rows, prompts)
+        self.n_con[rows] = 0
+
+    def harvest(self, rows: Tensor, host_n: list[int]) -> list[dict]:
+        host_cum = self.cum[rows].cpu().tolist() if self.row_lp is not None else [None] * len(host_n)
+        return [dict(cumulative_logprob=c, n_constrained=k) for c, k in zip(host_cum, self.n_con[rows].cpu().tolist())]
+
 
 class _Sample(_Selection):
     """``sample``: ``ops.decode_sample`` / ``ops.decode_sample_pen`` with ``step`` the loop index and ``sequence`` the rows' numbers — row
@@ -422,18 +663,40 @@ class _Sample(_Selection):
     at least one column"."""
     refusal = "decode_sample chose no token, one that is not allowed, or kept no column"
 
-    def __init__(self, model, seqs: list[Tensor], index: list[int], n: int, draw: dict, con: _Constraint | None, pen: _Penalty | None):
-        dev, rows = model.device, len(seqs) * n
-        super().__init__("sample", model, seqs, rows, con, pen, prompt_row=torch.arange(rows, dtype=torch.int32, device=dev) // n if pen is not None else None)
-        number = (torch.tensor(index, dtype=torch.int64) * n).repeat_interleave(n) + torch.arange(n, dtype=torch.int64).repeat(len(seqs))
-        self.sequence = torch.where(number >= 2 ** 31, number - 2 ** 32, number).to(torch.int32).to(dev)      # (the kernel reads it as unsigned)
-        self.draw = draw
+    def __init__(self, model, seqs: list[Tensor], index: list[int], n: int, draw: dict, con: _Constraint | None, pen: _Penalty | None,
+                 pool: int | None = None):
+        """``draw``: what ``_check_draws`` returned — with scalars alone (and no ``pool``) the launches are the scalar entries', argument for
+        argument; a per-prompt value (a float64 / int64 tensor over ALL prompts of the call, on the CPU) or ``pool`` takes the ``_rows``
+        entries, with ``step = n_gen`` per row.  ``pool`` (the pool loop; ``n == 1``): that many rows over the prompt table of the whole call;
+        a row's sequence number, prompt line and draw parameters are set when it is admitted (``index`` is not read)."""
+        dev, rows = model.device, (len(seqs) * n if pool is None else pool)
+        if pool is None:
+            line = torch.arange(rows, dtype=torch.int32, device=dev) // n if pen is not None else None
+            number = (torch.tensor(index, dtype=torch.int64) * n).repeat_interleave(n) + torch.arange(n, dtype=torch.int64).repeat(len(seqs))
+        else:
+            line = torch.zeros(rows, dtype=torch.int32, device=dev) if pen is not None else None
+            number = torch.zeros(rows, dtype=torch.int64)
+        super().__init__("sample", model, seqs, rows, con, pen, prompt_row=line)
+        self.sequence = self._words(number).to(dev)
+        self.per_prompt = {k: v.to(dev) for k, v in draw.items() if isinstance(v, Tensor)}
+        self.by_row = pool is not None or bool(self.per_prompt)
+        self.draw = dict(draw)
+        for k, v in self.per_prompt.items():              # the row's own value: of its prompt in a static group, set on admission in a pool
+            self.draw[k] = v[torch.tensor(index, dtype=torch.int64, device=dev)].repeat_interleave(n) if pool is None else torch.ones(rows, dtype=v.dtype, device=dev)
         self.row_kept = torch.empty(rows, dtype=torch.int32, device=dev)
         self.kept_sum = torch.zeros(rows, dtype=torch.int64, device=dev)
 
+    @staticmethod
+    def _words(number: Tensor) -> Tensor:
+        return torch.where(number >= 2 ** 31, number - 2 ** 32, number).to(torch.int32)      # (the kernel reads it as unsigned)
+
     def __call__(self, t: int, logits: Tensor, alive: Tensor, n_gen: Tensor, out: Tensor) -> Tensor:
-        sample = ops.decode_sample if self.hist is None else ops.decode_sample_pen
-        sample(logits, self.V, self.tok, self.row_lp, self.row_kept, step=t, sequence=self.sequence, **self.launch_kw(n_gen, out), **self.draw)
+        if self.by_row:     # a live row of a static group is at step t == n_gen; the rows of a pool have their own ages
+            sample = ops.decode_sample_rows if self.hist is None else ops.decode_sample_pen_rows
+            sample(logits, self.V, self.tok, self.row_lp, self.row_kept, step=n_gen, sequence=self.sequence, **self.launch_kw(n_gen, out), **self.draw)
+        else:
+            sample = ops.decode_sample if self.hist is None else ops.decode_sample_pen
+            sample(logits, self.V, self.tok, self.row_lp, self.row_kept, step=t, sequence=self.sequence, **self.launch_kw(n_gen, out), **self.draw)
         at = self.tok.clamp(min=0)                      # (a new tensor per step; never a negative embedding index)
         self.bad += (alive & (self.refused(at, n_gen) | (self.row_kept < 1))).sum()
         self.cum += torch.where(alive, self.row_lp, torch.zeros_like(self.row_lp)).double()
@@ -443,6 +706,18 @@ class _Sample(_Selection):
     def finish(self, host_n: list[int]) -> list[dict]:
         host_cum, host_kept = self.cum.cpu().tolist(), self.kept_sum.cpu().tolist()
         self.check()
+        return [dict(cumulative_logprob=c, n_kept_mean=k / max(m, 1)) for c, k, m in zip(host_cum, host_kept, host_n)]
+
+    def admit(self, rows: Tensor, prompts: list[int]) -> None:
+        super().admit(rows, prompts)
+        self.kept_sum[rows] = 0
+        at = torch.tensor(prompts, dtype=torch.int64)
+        self.sequence[rows] = self._words(at).to(rows.device)
+        for k, v in self.per_prompt.items():
+            self.draw[k][rows] = v[at.to(rows.device)]
+
+    def harvest(self, rows: Tensor, host_n: list[int]) -> list[dict]:
+        host_cum, host_kept = self.cum[rows].cpu().tolist(), self.kept_sum[rows].cpu().tolist()
         return [dict(cumulative_logprob=c, n_kept_mean=k / max(m, 1)) for c, k, m in zip(host_cum, host_kept, host_n)]
 
 
@@ -475,7 +750,8 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
              logprobs: bool = False, device: torch.device | str | None = None, allowed_token_ids: Sequence[int] | Tensor | None = None,
              min_new_tokens: int = 0, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
              presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None,
-             split_kv: bool = False, kv_cache_dtype: str | None = None, weight_dtype: str | None = None, weight_quant=None) -> list[Generation]:
+             split_kv: bool = False, kv_cache_dtype: str | None = None, weight_dtype: str | None = None, weight_quant=None,
+             continuous: bool = False, admit_min: int | None = None, continuous_report: dict | None = None) -> list[Generation]:
     """Greedy continuation of every prompt (1-D integer sequences), results in INPUT order.  The token of a step is ``argmax`` over the real
     columns ``[:, :vocab_size]`` of the step's logits, with torch's first-occurrence rule.  ``pad_id`` fills the rows that have finished.
     ``logprobs=True``: the forward-only ``ops.ce_fwd_metrics`` runs on the step's logits with the chosen token as label, which gives its
@@ -504,6 +780,15 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
     (``HipLlamaDecoder.quantize_weights``) and adds 1 to ``"fp8_weight_groups"`` of ``small_batch_report``; ``prefill``, the embedding gather and
     every other group run on the bf16 weights, and values change (opt-in).  ``weight_quant``: a ``QuantWeights`` built before, to reuse it across
     calls; without it one is built in the call, when the first such group starts.
+    ``continuous`` (continuous batching; opt-in): ``batch_size`` is then a POOL of that many rows and cache slots over one cache of
+    ``max(lens) + max_new_tokens`` positions; the queue is ``plan_groups``' order, a finished row is harvested at the next read-back and a
+    queued prompt prefilled into its slot (``prefill(slots=...)``; ``PoolSchedule``), so a row of a step is whatever sequence owns its slot.
+    ``admit_min`` (None: ``ADMIT_MIN_DEFAULT``): an admission waits for ``min(admit_min, queued)`` free rows, or for the pool to be empty.
+    A pool that takes the small-batch path (``batch_size <= skinny_max_rows`` with ``small_batch=True``) admits prompt by prompt, and a
+    prompt's tokens and ``cumulative_logprob`` are then bit-equal to the static ``small_batch`` run's whatever the pool size, ``admit_min`` and
+    the input order (with ``split_kv``: against static groups on the same side of ``split_max_rows``); a larger pool admits packed, and packing
+    enters a prompt's bits as it does in a static group.  ``continuous_report`` (a dict, or None) receives ``continuous``, ``decode_steps``,
+    ``row_steps_live``, ``row_steps_total`` and ``admissions``.  ``False``: not one launch, buffer or bit differs.
     Refused before any launch (``ValueError``): a penalty outside its range, an empty prompt, a prompt that with ``max_new_tokens`` exceeds the model's RoPE table or
     ``max_seq_len``; ``min_new_tokens < 0``, an allowed or stop id outside the vocabulary (under a constraint), an empty allowed set,
     ``min_new_tokens > 0`` with nothing allowed besides the stop tokens."""
@@ -518,6 +803,15 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
     if device != model.device:
         raise ValueError(f"generate: device {device} is not the model's ({model.device})")
     refused = "generate: the K/V cache kernels refused {} rows (a destination or a slot outside the cache)"
+    if _check_continuous("generate", continuous, admit_min):
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
+
+        def make_choose(seqs, pool, con):
+            return _Argmax(model, pool, logprobs) if con is None and pen is None else _Select(model, seqs, con, pen, logprobs, pool=pool)
+
+        return _run_pool(model, prompts, batch_size, max_new_tokens, stop_token_ids, masks, min_new_tokens, kv_dtype, admit_min, make_choose,
+                         refused, int(pad_id), small_batch, small_batch_report, split_kv, weights, continuous_report)
 
     def run_group(caches, con, seqs: list[Tensor], index: list[int], stop: Tensor) -> list[Generation]:
         started = _own_slots(model, caches, seqs, max_new_tokens, small_batch, small_batch_report, split_kv, weights)
@@ -548,7 +842,7 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
                 batch_size: int = 256, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
                 presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None,
              split_kv: bool = False, kv_cache_dtype: str | None = None, weight_dtype: str | None = None,
-             weight_quant=None) -> list[list[Generation]]:
+             weight_quant=None, continuous: bool = False, admit_min: int | None = None) -> list[list[Generation]]:
     """The ``n_best <= beam_width <= 8`` best hypotheses of every prompt, best first, in INPUT order; ``cumulative_logprob`` (the sum of the
     tokens' log-probabilities under the unconstrained distribution) and ``score`` are always set.  A group holds ``batch_size // beam_width``
     prompts, so a step is at most ``batch_size`` rows.  The rules, with ``W = beam_width``:
@@ -568,8 +862,11 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
     search ignores them, and ``ssi_topk_logprob`` knows none), and everything ``generate`` refuses.
     ``small_batch``, ``split_kv``: handed to every ``decode_step_beam`` (``generate``'s rules, on the group's ``prompts * beam_width`` rows).
     ``kv_cache_dtype``: ``generate``'s; the prompt cache and the beam cache are of the same kind.
-    ``weight_dtype``, ``weight_quant``: ``generate``'s."""
+    ``weight_dtype``, ``weight_quant``: ``generate``'s.
+    ``continuous=True`` is refused (``ValueError``): the beams of a prompt share its slot, and refilling that is not built."""
     W, length_penalty, n_best = _check_beam(beam_width, length_penalty, n_best)
+    if _check_continuous("beam_search", continuous, admit_min):
+        raise ValueError("beam_search: continuous batching is not built for beam search (the beams of a prompt share its slot)")
     kv_dtype = check_kv_cache_dtype(kv_cache_dtype)
     weights = _weight_source(model, weight_dtype, weight_quant, small_batch)
     if _check_penalties(repetition_penalty, frequency_penalty, presence_penalty) is not None:
@@ -708,12 +1005,40 @@ def _check_sample(n, temperature, top_k, top_p, seed) -> tuple[int, float, int, 
     return n, float(temperature), top_k, float(top_p), seed
 
 
+def _check_draws(n, temperature, top_k, top_p, seed, n_prompts: int) -> tuple[int, dict]:
+    """``sample``'s draw arguments, each of ``temperature``, ``top_k`` and ``top_p`` a number or a list / tuple of one per prompt, every value
+    by ``_check_sample``'s rules (``ValueError``).  Returns ``n`` and the keywords of a sampling launch: a number stays the scalar it was, a
+    list becomes a CPU tensor over the prompts (float64; int64 for ``top_k``, clamped as ``ops`` clamps the scalar)."""
+    given = {"temperature": temperature, "top_k": top_k, "top_p": top_p}
+    lists = {k: list(v) for k, v in given.items() if isinstance(v, (list, tuple))}
+    for k, v in lists.items():
+        if len(v) != n_prompts:
+            raise ValueError(f"{k}: {len(v)} values for {n_prompts} prompts (one per prompt, or one number)")
+    one = {k: (lists[k][0] if k in lists and lists[k] else (v if k not in lists else {"temperature": 1.0, "top_k": -1, "top_p": 1.0}[k]))
+           for k, v in given.items()}
+    n, t, k, p, seed = _check_sample(n, one["temperature"], one["top_k"], one["top_p"], seed)
+    draw: dict = dict(temperature=t, top_k=k, top_p=p, seed=seed)
+    for i in range(n_prompts if lists else 0):
+        try:
+            got = _check_sample(n, *(lists[name][i] if name in lists else draw[name] for name in ("temperature", "top_k", "top_p")), seed)
+        except ValueError as e:
+            raise ValueError(f"prompt {i}: {e}") from None
+        for name, v in zip(("temperature", "top_k", "top_p"), got[1:4]):
+            if name in lists:
+                lists[name][i] = v
+    for name, v in lists.items():
+        draw[name] = (torch.tensor([max(-1, min(x, 2 ** 62)) for x in v], dtype=torch.int64) if name == "top_k"
+                      else torch.tensor(v, dtype=torch.float64))
+    return n, draw
+
+
 def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top_k: int = -1, top_p: float = 1.0, seed: int, max_new_tokens: int,
            stop_token_ids: Sequence[int], pad_id: int, batch_size: int = 256, allowed_token_ids: Sequence[int] | Tensor | None = None,
            min_new_tokens: int = 0, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
            presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None,
              split_kv: bool = False, kv_cache_dtype: str | None = None, weight_dtype: str | None = None,
-             weight_quant=None) -> list[list[Generation]]:
+             weight_quant=None, continuous: bool = False, admit_min: int | None = None,
+             continuous_report: dict | None = None) -> list[list[Generation]]:
     """``n`` (1..8) sampled continuations of every prompt, in INPUT order and per prompt in sample order; ``cumulative_logprob`` (the tokens'
     log-probabilities under the unconstrained distribution at temperature 1, what ``ssi.score`` assigns) and ``n_kept_mean`` are always set.
     The token of a step is ``ops.decode_sample``'s with ``step`` the loop index and ``sequence = prompt index * n + sample index``: a pure function
@@ -729,8 +1054,14 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
     outside (0, 1], a non-integer ``top_k``, a negative ``seed``, and everything ``generate`` refuses.
     ``small_batch``, ``split_kv``: handed to every decode step (``generate``'s rules, on the group's ``prompts * n`` rows).
     ``kv_cache_dtype``: ``generate``'s; with ``n > 1`` the prompt cache and the samples' cache are of the same kind.
-    ``weight_dtype``, ``weight_quant``: ``generate``'s."""
-    n, temperature, top_k, top_p, seed = _check_sample(n, temperature, top_k, top_p, seed)
+    ``weight_dtype``, ``weight_quant``: ``generate``'s.
+    ``temperature``, ``top_k`` and ``top_p`` may each be a list or tuple with one value per prompt (every value by the rules above; another
+    length is a ``ValueError``): the step's token then comes from ``ops.decode_sample_rows`` / ``ops.decode_sample_pen_rows``, whose row ``r`` has
+    the bits of the scalar entry launched with the row's own values.  With scalars the static path launches what it always launched.
+    ``continuous``, ``admit_min``, ``continuous_report``: ``generate``'s, for ``n == 1`` (``n > 1`` with ``continuous=True`` is a ``ValueError``:
+    the samples of a prompt share its slot); the pool's steps go through the ``_rows`` entries with ``step`` = the row's own token count, so a
+    sample stays the pure function of ``(seed, sequence, step)`` and the row that it is in a static group."""
+    n, draw = _check_draws(n, temperature, top_k, top_p, seed, len(prompts))
     kv_dtype = check_kv_cache_dtype(kv_cache_dtype)
     weights = _weight_source(model, weight_dtype, weight_quant, small_batch)
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
@@ -742,8 +1073,14 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
         raise ValueError(f"batch_size = {batch_size} holds no prompt of n = {n}")
     if len(prompts) * n > 2 ** 32:
         raise ValueError(f"{len(prompts)} prompts x {n} samples do not fit the 32-bit sequence number")
-    draw = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
     refused = "sample: the K/V cache kernels refused {} rows (a destination, a slot or an ancestry entry outside its cache)"
+    if _check_continuous("sample", continuous, admit_min):
+        if n != 1:
+            raise ValueError(f"sample: continuous batching is built for n = 1 (got n = {n}: the samples of a prompt share its slot)")
+        found = _run_pool(model, prompts, batch_size, max_new_tokens, stop_token_ids, masks, min_new_tokens, kv_dtype, admit_min,
+                          lambda seqs, pool, con: _Sample(model, seqs, [], 1, draw, con, pen, pool=pool), refused, int(pad_id), small_batch,
+                          small_batch_report, split_kv, weights, continuous_report)
+        return [[g] for g in found]
 
     def open_caches(n_slots: int, longest: int):
         if n == 1:
@@ -823,7 +1160,10 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     ``kv_cache_dtype`` in ``kw`` goes to whichever loop runs (``check_kv_cache_dtype``, refused here before a prompt is read); the summary gains
     ``"kv_cache_dtype": "fp8"`` under fp8 alone — None and "auto" are not passed on and add no key.
     ``weight_dtype`` (and ``weight_quant``) in ``kw`` likewise (``check_weight_dtype``: "fp8" needs ``small_batch=True``); under fp8 alone the summary
-    gains ``"fp8_weight_groups"``: the groups whose steps read FP8 weights."""
+    gains ``"fp8_weight_groups"``: the groups whose steps read FP8 weights.
+    ``continuous=True`` (and ``admit_min``) in ``kw`` go to ``generate`` / ``sample`` (``n > 1`` and ``beam_width > 1`` refuse it), and the summary
+    gains ``"continuous": True``, ``"decode_steps"``, ``"row_steps_live"``, ``"row_steps_total"`` and ``"admissions"``; ``False`` (the default) and
+    a null ``admit_min`` are not passed on and add no key."""
     kv_dtype = check_kv_cache_dtype(kw.pop("kv_cache_dtype", None))
     fp8 = {} if kv_dtype is None else {"kv_cache_dtype": kv_dtype}
     w8 = {} if check_weight_dtype(kw.pop("weight_dtype", None), bool(kw.get("small_batch", False))) is None else {"weight_dtype": "fp8"}
@@ -875,7 +1215,11 @@ def _run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_tok
         device = kw.pop("device", None)
         if device is not None and torch.device(device) != model.device:
             raise ValueError(f"generate: device {device} is not the model's ({model.device})")
-    found = run(model, prompts, max_new_tokens=max_new_tokens, stop_token_ids=stop_token_ids, **mode, **kw)
+    pool = {k: v for k, v in (("continuous", kw.pop("continuous", False)), ("admit_min", kw.pop("admit_min", None))) if v not in (False, None)}
+    stats: dict = {}
+    if pool.get("continuous") is True and not beams:      # (beam search refuses the flag itself)
+        pool["continuous_report"] = stats
+    found = run(model, prompts, max_new_tokens=max_new_tokens, stop_token_ids=stop_token_ids, **mode, **kw, **pool)
     with open(out_path, "w", encoding="utf-8") as f:
         for item_id, p, g in zip(ids, prompts, found):
             f.write(json.dumps(output_record(item_id, p, g, tokenizer, tokenizer_decoding), ensure_ascii=False) + "\n")
@@ -889,7 +1233,7 @@ def _run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_tok
         summary["beam_width"] = int(beam["beam_width"])
     elif kw.get("allowed_token_ids") is not None or int(kw.get("min_new_tokens", 0)) != 0 or pen is not None:
         summary["constrained_tokens"] = sum(g.n_constrained or 0 for g in gens)
-    return dict(summary, **pen_summary)       # (empty under beam search, which refuses a set penalty)
+    return dict(summary, **pen_summary, **stats)       # (pen_summary: empty under beam search, which refuses a set penalty)
 
 
 # ---- what the script accepts of the reference's sampling_params ------------------------------------------------------------------
@@ -937,6 +1281,25 @@ def check_penalties(sampling_params) -> dict[str, float]:
     except ValueError as e:
         raise ValueError(f"sampling_params.{e}") from None
     return {k: float(v) for k, v in got.items()}
+
+
+def check_continuous(continuous, admit_min, beam_width: int = 1, n: int = 1) -> dict[str, Any]:
+    """What ``gen.continuous`` and ``gen.admit_min`` accept, before anything is loaded: ``continuous`` null or a bool, ``admit_min`` null or an
+    integer >= 1 and only with ``continuous: true``; ``continuous: true`` not with ``gen.beam_width > 1`` or ``sampling_params.n > 1``
+    (``ValueError``).  Returns the keyword arguments of ``generate_file``: none at all without the flag."""
+    if continuous is not None and not isinstance(continuous, bool):
+        raise ValueError(f"gen.continuous = {continuous!r}: true or false")
+    if admit_min is not None and (isinstance(admit_min, bool) or not isinstance(admit_min, int) or admit_min < 1):
+        raise ValueError(f"gen.admit_min = {admit_min!r}: null or an integer >= 1")
+    if not continuous:
+        if admit_min is not None:
+            raise ValueError("gen.admit_min without gen.continuous=true")
+        return {}
+    if int(beam_width) != 1:
+        raise ValueError("gen.continuous=true together with gen.beam_width > 1: continuous batching is not built for beam search")
+    if int(n) != 1:
+        raise ValueError("gen.continuous=true together with sampling_params.n > 1: continuous batching is not built for several samples of a prompt")
+    return {"continuous": True} if admit_min is None else {"continuous": True, "admit_min": int(admit_min)}
 
 
 def check_sampling(sampling_params) -> dict[str, Any]:

@@ -826,7 +826,7 @@ class HipLlamaDecoder(nn.Module):
     PREFILL_ROWS_PER_BATCH = 8    # ... and run this many rows at a time
 
     @torch.no_grad()
-    def prefill(self, cache: "KVCache", prompts, max_new_tokens: int = 0, separate: bool = False) -> Tensor:
+    def prefill(self, cache: "KVCache", prompts, max_new_tokens: int = 0, separate: bool = False, slots=None) -> Tensor:
         """Prompt ``i`` (a 1-D integer sequence) fills slot ``i`` of ``cache``: the prompts are packed into rows on the host
         (``ssi.score.prefill_batches``: first-fit decreasing, ``input_pos`` restarting with every prompt), the packed forward the dev
         loss and ``ssi.score`` use runs block-causal over them with every layer's K / V scattered into the cache, and the final norm's
@@ -837,12 +837,25 @@ class HipLlamaDecoder(nn.Module):
         attends over the unquantised K / V under an fp8 cache.
         ``separate`` (the small-batch loops): every prompt runs as a packed forward of its own, one row that starts at position 0.  Where a
         prompt lies in a packed row, and how many rows the forward has (which picks the K split of its GEMMs), enter the bits of its K / V
-        and of its logits; prompt by prompt they are a function of the prompt alone, whatever else is in the group."""
+        and of its logits; prompt by prompt they are a function of the prompt alone, whatever else is in the group.
+        ``slots`` (continuous batching: a prompt enters a cache that holds live sequences): a list of distinct slot numbers, one per prompt;
+        prompt ``i`` fills slot ``slots[i]``, every other slot's K / V, exponents and length are left exactly as they were, and the logits
+        come in prompt order.  A slot number outside the cache or given twice is a ``ValueError`` before any launch.  ``None``: slots
+        ``0 .. n - 1`` and the emptying of the rest, launch for launch as before."""
         from .score import prefill_batches
         seqs = [torch.as_tensor(p, dtype=torch.int64).reshape(-1) for p in prompts]
         lens = [int(s.numel()) for s in seqs]
         n, cap = len(seqs), cache.cap
         self._check_cache(cache)
+        if slots is not None:
+            slots = [int(v) for v in slots]
+            if len(slots) != n:
+                raise ValueError(f"prefill: {len(slots)} slots for {n} prompts")
+            bad = [v for v in slots if not 0 <= v < cache.n_slots]
+            if bad:
+                raise ValueError(f"prefill: slots outside the cache's {cache.n_slots}: {bad[:8]}")
+            if len(set(slots)) != n:
+                raise ValueError(f"prefill: a slot is given twice: {sorted(v for v in set(slots) if slots.count(v) > 1)[:8]}")
         self.check_generation_lengths(lens, max_new_tokens, cache.n_slots, cap)
         if n == 0:
             raise ValueError("prefill: no prompts")
@@ -851,13 +864,19 @@ class HipLlamaDecoder(nn.Module):
         dev = self.device
         hlast = torch.zeros((self._padded_rows(n), self.embed_dim), dtype=self.dtype, device=dev)   # (pad rows: zeros)
 
+        slot_of = None if slots is None else torch.tensor(slots, dtype=torch.int64)
+
         def batches():
             if not separate:
-                yield from prefill_batches(seqs, cap, row_len, self.PREFILL_ROWS_PER_BATCH)
+                for tokens, input_pos, dest, last_at, last_of in prefill_batches(seqs, cap, row_len, self.PREFILL_ROWS_PER_BATCH):
+                    if slot_of is not None:   # slot i of the plan is slot slots[i] of the cache
+                        dest = torch.where(dest >= 0, slot_of[dest.clamp(min=0) // cap] * cap + dest % cap, dest)
+                    yield tokens, input_pos, dest, last_at, last_of
                 return
-            for i, s in enumerate(seqs):   # slot 0 of a one-prompt plan is slot i of the cache
+            for i, s in enumerate(seqs):   # slot 0 of a one-prompt plan is slot i of the cache, or the slot chosen for prompt i
+                at = i if slots is None else slots[i]
                 for tokens, input_pos, dest, last_at, last_of in prefill_batches([s], cap, min(lens[i], self._rope.shape[0]), 1):
-                    yield tokens, input_pos, torch.where(dest >= 0, dest + i * cap, dest), last_at, last_of + i
+                    yield tokens, input_pos, torch.where(dest >= 0, dest + at * cap, dest), last_at, last_of + i
 
         for tokens, input_pos, dest, last_at, last_of in batches():
             row_len = tokens.shape[1]
@@ -869,8 +888,11 @@ class HipLlamaDecoder(nn.Module):
                 last_at = last_at + last_at // row_len * (S - row_len)
             hn = self._forward_hidden(tokens, save=False, input_pos=input_pos, kv_sink=(cache, dest.reshape(-1).contiguous()))
             hlast.index_copy_(0, last_of.to(dev), hn.index_select(0, last_at.to(dev)))
-        cache.lengths.zero_()
-        cache.lengths[:n] = torch.tensor(lens, dtype=torch.int32).to(dev)
+        if slots is None:
+            cache.lengths.zero_()
+            cache.lengths[:n] = torch.tensor(lens, dtype=torch.int32).to(dev)
+        else:
+            cache.lengths[slot_of.to(dev)] = torch.tensor(lens, dtype=torch.int32).to(dev)
         return self._head_logits(hlast)[:n]
 
     def _check_cache(self, cache: "KVCache", beside: Optional["KVCache"] = None) -> None:

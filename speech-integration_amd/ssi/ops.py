@@ -449,6 +449,61 @@ def decode_sample_pen(logits: Tensor, vocab: int, token: Tensor, logprob: Tensor
                                             ptr(logprob), ptr(n_kept), *tail, dtype_code(logits.dtype), stream_ptr()), "ssi_decode_sample_pen")
 
 
+def _row_draw_args(what: str, logits: Tensor, seed: int, step: Tensor, temperature, top_k, top_p):
+    """The draw arguments of the two ``_rows`` wrappers as the C entries take them: the three scalars (a neutral one where a tensor stands for
+    it, which the entry then does not read), ``seed``, and the four array pointers.  ``step``: int32 per row, read as unsigned; a tensor for
+    ``temperature`` / ``top_p`` is float64 per row, for ``top_k`` int64 per row; a number is the scalar for all rows."""
+    rows, dev = logits.shape[0], logits.device
+    if not 0 <= int(seed) < 2 ** 64:
+        raise _lib.HipLibraryError(f"{what}: seed is in [0, 2^64) (got {seed})")
+    scalars, ptrs = [], []
+    for name, v, dtype, neutral in (("step", step, torch.int32, None), ("temperature", temperature, torch.float64, 1.0),
+                                    ("top_k", top_k, torch.int64, -1), ("top_p", top_p, torch.float64, 1.0)):
+        if isinstance(v, Tensor):
+            if v.dtype != dtype or not v.is_contiguous() or v.numel() != rows or v.device != dev:
+                raise _lib.HipLibraryError(f"{what}: {name} as a tensor is one {dtype} per row of logits, on its device")
+            scalars.append(neutral)
+            ptrs.append(ptr(v))
+        elif neutral is None:
+            raise _lib.HipLibraryError(f"{what}: step is an int32 tensor, one entry per row (read as unsigned)")
+        else:
+            scalars.append(max(-1, min(int(v), 2 ** 62)) if name == "top_k" else float(v))
+            ptrs.append(None)
+    return (scalars[1], scalars[2], scalars[3], int(seed), *ptrs)
+
+
+def decode_sample_rows(logits: Tensor, vocab: int, token: Tensor, logprob: Tensor | None = None, n_kept: Tensor | None = None, *,
+                       temperature: float | Tensor, top_k: int | Tensor = -1, top_p: float | Tensor = 1.0, seed: int, step: Tensor,
+                       sequence: Tensor, allow: Tensor | None = None, allow_early: Tensor | None = None, n_generated: Tensor | None = None,
+                       min_new: int = 0) -> None:
+    """``decode_sample`` with the step and the draw parameters per row: ``step`` is an int32 tensor (one per row, read as unsigned), and
+    ``temperature`` / ``top_p`` (float64) and ``top_k`` (int64) may each be a tensor of one value per row or a number for all rows.  Row ``r``
+    has the bits of row ``r`` of ``decode_sample`` launched with its own four values.  A row whose temperature is not finite and > 0, or whose
+    ``top_p`` lies outside (0, 1], writes -1 / 0 / -1 and changes no other row.  ``ssi_decode_sample_rows``."""
+    rows = _selection_rows("decode_sample_rows", logits, vocab, token, logprob, (("n_kept", n_kept), ("n_generated", n_generated), ("sequence", sequence)), allow, allow_early)
+    draw = _row_draw_args("decode_sample_rows", logits, seed, step, temperature, top_k, top_p)
+    check(_lib.load().ssi_decode_sample_rows(ptr(logits), logits.stride(0), rows, int(vocab), ptr(allow), ptr(allow_early), ptr(n_generated),
+                                             int(min_new), *draw, ptr(sequence), ptr(token), ptr(logprob), ptr(n_kept),
+                                             dtype_code(logits.dtype), stream_ptr()), "ssi_decode_sample_rows")
+
+
+def decode_sample_pen_rows(logits: Tensor, vocab: int, token: Tensor, logprob: Tensor | None = None, n_kept: Tensor | None = None, *,
+                           temperature: float | Tensor, top_k: int | Tensor = -1, top_p: float | Tensor = 1.0, seed: int, step: Tensor,
+                           sequence: Tensor, prompt_ids: Tensor | None, prompt_len: Tensor, prompt_row: Tensor | None = None,
+                           gen_ids: Tensor | None, n_generated: Tensor, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
+                           presence_penalty: float = 0.0, n_bad: Tensor | None = None, allow: Tensor | None = None,
+                           allow_early: Tensor | None = None, min_new: int = 0) -> None:
+    """``decode_sample_pen`` with the step and the draw parameters per row (``decode_sample_rows``'s arguments); the penalties stay one
+    setting for the launch.  A refused row builds no history and counts nothing into ``n_bad``.  ``ssi_decode_sample_pen_rows``."""
+    rows = _selection_rows("decode_sample_pen_rows", logits, vocab, token, logprob, (("n_kept", n_kept), ("n_generated", n_generated), ("sequence", sequence)), allow, allow_early)
+    draw = _row_draw_args("decode_sample_pen_rows", logits, seed, step, temperature, top_k, top_p)
+    tail = _penalty_args("decode_sample_pen_rows", logits, int(vocab), n_generated, prompt_ids, prompt_len, prompt_row, gen_ids, repetition_penalty,
+                         frequency_penalty, presence_penalty, n_bad)
+    check(_lib.load().ssi_decode_sample_pen_rows(ptr(logits), logits.stride(0), rows, int(vocab), ptr(allow), ptr(allow_early), ptr(n_generated),
+                                                 int(min_new), *draw, ptr(sequence), ptr(token), ptr(logprob), ptr(n_kept), *tail,
+                                                 dtype_code(logits.dtype), stream_ptr()), "ssi_decode_sample_pen_rows")
+
+
 def attn_decode_beam(qkv: Tensor, pk_cache: Tensor, pv_cache: Tensor, bk_cache: Tensor, bv_cache: Tensor, prompt_slot: Tensor, prompt_len: Tensor,
                      gen_len: Tensor, anc: Tensor, out: Tensor, lse: Tensor | None, n_heads: int, n_kv: int, head_dim: int,
                      n_bad: Tensor | None = None) -> None:

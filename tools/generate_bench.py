@@ -1,5 +1,5 @@
 """What greedy generation costs at the 1B shape (Llama-3.2-1B + 5000 DSUs, bf16, random weights): 256 prompts of about 1000 tokens, 256 new
-tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained|beam|sample|penalty|small_batch|split_kv|kv_fp8|weight_fp8] [--json profiles/generate.json]
+tokens each.  python tools/generate_bench.py [--part all|run|steps|recompute|constrained|beam|sample|penalty|small_batch|split_kv|kv_fp8|weight_fp8|continuous] [--json profiles/generate.json]
 
 run        prefill time, milliseconds per decode step (event time over all steps, host gaps included), generated tokens per second, and a
            self-check: the first generated token of every prompt against the argmax of a plain full forward of that prompt alone (with
@@ -48,6 +48,13 @@ kv_fp8     (not part of ``all``; python tools/generate_bench.py --part kv_fp8 --
            4000 keys, every layer's caches in turn), the two stores at 256 rows, the beam pair at 64 x 4; whole ``decode_step``s at 256 rows and the
            small-batch step at 1 and 8 rows; ``generate`` end to end; and, recorded and not asserted, the share of greedy tokens equal between the two
            caches and the largest teacher-forced logit difference (random weights: nothing about a trained checkpoint).
+continuous (not part of ``all``; python tools/generate_bench.py --part continuous --prompts 1024 --rounds 3 --json profiles/generate_continuous.json) what
+           refilling finished rows buys end to end, ONE process: ``sample(n=1, temperature=1.0)`` with ``--new`` new tokens at the most and every
+           100th id a stop token (on the near-flat distribution of random weights the lengths come out roughly geometric with mean about 100; the
+           histogram that came out is recorded), static groups against ``continuous=True`` at every ``--admit-mins`` value, the forms alternating
+           over ``--rounds`` rounds, median and min..max of the call's wall time (host clock around a call that ends in a synchronise), decode
+           steps, the live share of the row-steps, admissions and prompts per admission; then the same without a stop set, where both schedules
+           take the same steps and the difference is the pool's bookkeeping.  The static run of the same build is the baseline.
 weight_fp8 (not part of ``all``; python tools/generate_bench.py --part weight_fp8 --json profiles/generate_weight_fp8.json) what FP8 weights buy and
            cost on the small-batch path, ONE process, the forms alternating: each of the five GEMMs at 1, 16 and 64 rows, ``_w8`` entry against plain
            skinny entry, with the weight bytes per second of both; the quantiser over the whole model; the small-batch ``decode_step`` at 1, 8, 16,
@@ -61,7 +68,7 @@ PKG = os.path.join(ROOT, 'speech-integration_amd')
 sys.path.insert(0, PKG)
 
 ap = argparse.ArgumentParser()
-ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained', 'beam', 'sample', 'penalty', 'small_batch', 'small_batch_steps', 'split_kv', 'kv_fp8', 'weight_fp8'])
+ap.add_argument('--part', default='all', choices=['all', 'run', 'steps', 'recompute', 'constrained', 'beam', 'sample', 'penalty', 'small_batch', 'small_batch_steps', 'split_kv', 'kv_fp8', 'weight_fp8', 'continuous'])
 ap.add_argument('--rows', type=int, default=1, help='small_batch_steps: rows of the traced steps')
 ap.add_argument('--prompts', type=int, default=256)
 ap.add_argument('--penalty-generated', type=int, default=128, help='penalty: generated tokens in every row\'s history')
@@ -73,6 +80,8 @@ ap.add_argument('--allowed-types', default='text,special_text', help='constraine
 ap.add_argument('--min-new-tokens', type=int, default=0, help='constrained: rows below it take the mask without the stop tokens')
 ap.add_argument('--rounds', type=int, default=7)
 ap.add_argument('--beam-width', type=int, default=4)
+ap.add_argument('--admit-mins', default='1,8,16,32,64', help='continuous: the admit_min values to run')
+ap.add_argument('--workload', default='both', choices=['both', 'stops', 'full'], help='continuous: the workload with the stop set, the one without, or both')
 ap.add_argument('--workdir', default=os.path.join(ROOT, 'prof_out', 'generate_bench'))
 args = ap.parse_args()
 HBM_TB_S = (5.4, 6.4)   # what the README records for the AdamW and EMA passes
@@ -1471,6 +1480,70 @@ def part_weight_fp8():
     return res
 
 
+def part_continuous():
+    import torch
+    from ssi.generate import ADMIT_MIN_DEFAULT, READBACK_EVERY, plan_groups, sample, static_steps
+    model = build_model()
+    prompts = make_prompts(model.vocab_size)
+    lens = [p.numel() for p in prompts]
+    n, pool = len(prompts), 256
+    admit_mins = [int(v) for v in args.admit_mins.split(',')]
+    kw = dict(temperature=1.0, seed=11, max_new_tokens=args.new, pad_id=0, batch_size=pool)
+
+    def run(stops, admit_min):
+        """One call: (wall seconds, the schedule's numbers, the generated lengths)."""
+        stats = {}
+        mode = {} if admit_min is None else dict(continuous=True, admit_min=admit_min, continuous_report=stats)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        gens = sample(model, prompts, stop_token_ids=stops, **mode, **kw)
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        got = [len(gs[0].token_ids) for gs in gens]
+        if admit_min is None:
+            steps = static_steps(got, plan_groups(lens, pool), args.new, READBACK_EVERY)
+            stats = {'decode_steps': steps, 'row_steps_live': sum(got), 'row_steps_total': steps * pool, 'admissions': -(-n // pool)}
+        return wall, stats, got
+
+    def workload(stops, forms):
+        walls, last = {f: [] for f in forms}, {}
+        for r in range(args.rounds):
+            for f in forms:                               # the forms alternate within a round
+                wall, stats, got = run(stops, forms[f])
+                walls[f].append(wall)
+                last[f] = (stats, got)
+                print(f'round {r} {f}: {wall:.2f} s, {stats["decode_steps"]} steps', flush=True)
+        out = {}
+        for f in forms:
+            stats, got = last[f]
+            out[f] = {'wall_s': spread(walls[f]), 'decode_steps': stats['decode_steps'], 'admissions': stats['admissions'],
+                      'prompts_per_admission': round(n / max(stats['admissions'], 1), 1),
+                      'live_share_of_row_steps': round(stats['row_steps_live'] / max(stats['row_steps_total'], 1), 3),
+                      'generated_tokens': sum(got), 'generated_tokens_per_s': round(sum(got) / statistics.median(walls[f]))}
+        hist = [0] * (args.new // 32 + 1)
+        for g in last['static'][1]:
+            hist[g // 32] += 1
+        out['generated_lengths_static'] = {'mean': round(sum(last['static'][1]) / n, 1), 'ended_by_length': sum(g == args.new for g in last['static'][1]),
+                                           'histogram_by_32': hist}
+        return out
+
+    with torch.inference_mode():
+        warm = dict(kw, max_new_tokens=24)                # warm-up: library, arena, the packed prefill of a group and of an admission
+        sample(model, prompts[:pool + 40], stop_token_ids=list(range(0, model.vocab_size, 10)), **warm)
+        sample(model, prompts[:pool + 40], stop_token_ids=list(range(0, model.vocab_size, 10)), continuous=True, admit_min=8, **warm)
+        res = {'geometry': f'Llama-3.2-1B + 5000 DSUs, bf16, random weights; {n} prompts of {min(lens)}..{max(lens)} tokens (mean {sum(lens) / n:.0f}); '
+                           f'sample(n=1, temperature=1.0), at most {args.new} new tokens, batch_size (static group / pool) {pool}; {args.rounds} rounds, '
+                           f'the forms alternating in one process; wall_s: median [min, max] of the call',
+               'admit_min_default': ADMIT_MIN_DEFAULT, 'sum_prompt_tokens': sum(lens)}
+        forms = {'static': None, **{f'continuous_admit_min_{a}': a for a in admit_mins}}
+        if args.workload in ('both', 'stops'):
+            res['every_100th_id_stops'] = workload(list(range(0, model.vocab_size, 100)), forms)
+        if args.workload in ('both', 'full'):
+            res['no_stop_set'] = workload([], {'static': None, f'continuous_admit_min_{ADMIT_MIN_DEFAULT}': ADMIT_MIN_DEFAULT})
+    print(json.dumps(res, indent=1), flush=True)
+    return res
+
+
 def part_small_batch_steps():
     """--trace-steps small-batch decode steps of --rows rows, for a kernel trace in a run of its own."""
     import torch
@@ -1518,6 +1591,8 @@ elif args.part == 'kv_fp8':
     res = part_kv_fp8()
 elif args.part == 'weight_fp8':
     res = part_weight_fp8()
+elif args.part == 'continuous':
+    res = part_continuous()
 elif args.part == 'small_batch_steps':
     part_small_batch_steps()
     res = None
