@@ -28,13 +28,15 @@
 #ifndef SSI_HIP_H
 #define SSI_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 28 /* 28: + ssi_decode_sample_rows, ssi_decode_sample_pen_rows (the two sampling entries with the step and the draw parameters per row, from device arrays: rows of different ages and requests in one launch; opt-in)
+#define SSI_ABI_VERSION 29 /* 29: + ssi_edit_distance, ssi_edit_distance_workspace_bytes (edit distance with substitution, deletion and insertion counts between spans of int32 ids, many pairs per launch: error rates and minimum-Bayes-risk selection; opt-in)
+                           * 28: + ssi_decode_sample_rows, ssi_decode_sample_pen_rows (the two sampling entries with the step and the draw parameters per row, from device arrays: rows of different ages and requests in one launch; opt-in)
                            * 27: + ssi_weight_quant_fp8, ssi_gemm_skinny_w8, ssi_gemm_skinny_rope_w8, ssi_gemm_skinny_swiglu_w8 (weight matrices as e4m3 codes with one power-of-two exponent per row, and the skinny GEMMs over them: FP8 weights for small-batch decoding; opt-in)
                            * 26: + ssi_kv_store_fp8, ssi_attn_decode_fp8, ssi_attn_decode_beam_fp8, ssi_attn_decode_split_fp8, ssi_attn_decode_beam_split_fp8 (a K/V cache of e4m3 codes with one power-of-two exponent per line, and decode attention over it; opt-in)
                            * 25: + ssi_attn_decode_split, ssi_attn_decode_beam_split, ssi_attn_decode_split_span, ssi_attn_decode_split_workspace (split-KV decode attention: the keys of a row over several workgroups, a merge launch behind them; opt-in)
@@ -697,6 +699,37 @@ int ssi_ce_metrics_reduce(const float* row_nll, const int32_t* row_rank, const i
  * a null pointer beside a non-zero size. */
 int ssi_seq_score_reduce(const float* row_nll, const int32_t* row_rank, int64_t rows, const int64_t* seq_start, const int64_t* seq_end,
                          int64_t n_seq, int topk, double* out, void* stream);
+
+/* ---- Edit distance between integer sequences (ABI v29; what the reference's scripts/wer.py gets from `evaluate`'s wer, and what picks
+ * among samples or beams by minimum Bayes risk; opt-in, nothing else calls it) ----
+ * THE DEFINITION.  For a reference r[0..m) and a hypothesis h[0..n) of int32 ids — compared by equality only, so any int32 value is an id —
+ * the cell (i, j), 0 <= i <= m, 0 <= j <= n, holds (cost, S, D, I):
+ *   row 0 is (j, 0, 0, j); column 0 is (i, 0, i, 0);
+ *   for i, j >= 1 there are three candidates, taken in this order, a later one replacing an earlier one only on STRICTLY lower cost:
+ *     1. the diagonal, from (i-1, j-1): + 0 if r[i-1] == h[j-1], else + 1 cost and + 1 S;
+ *     2. up, from (i-1, j): + 1 cost and + 1 D (a reference id the hypothesis lacks);
+ *     3. left, from (i, j-1): + 1 cost and + 1 I.
+ * The result is the cell (m, n), written as int32[4] = {dist, S, D, I}.  It follows that dist == S + D + I, that m - S - D == n - S - I >= 0
+ * (the hits), and that dist is symmetric in its two arguments (the counts are not).
+ *
+ * Sequences are spans of ONE flat device buffer tokens[n_tokens]: pair p compares tokens[ref_start[p] .. + ref_len[p]) with
+ * tokens[hyp_start[p] .. + hyp_len[p]).  Spans may overlap, repeat and lie in any order; the four span arrays are device arrays of n_pairs
+ * entries that the host never reads.  max_len is the caller's bound on every length, at most SSI_EDIT_MAX_LEN (more: SSI_ERR_UNSUPPORTED
+ * before any launch).  A span is BAD if its length is negative or above max_len, its start negative, or start + len > n_tokens; the kernel
+ * checks this before it forms any address from the span, and a pair with a bad span gets {-1, -1, -1, -1} while every other pair is
+ * unaffected (as ssi_attn_decode_beam treats an ancestry index outside its cache).
+ * One wave per pair, four per workgroup: the hypothesis columns in strips of SSI_EDIT_COLS per lane, the reference rows as a wavefront
+ * through the lanes, hypotheses beyond 64 * SSI_EDIT_COLS columns in column blocks whose boundary column stays in LDS.  Integers only, no
+ * atomics: a pair's four numbers depend on its two spans alone — not on n_pairs, not on where the pair lies, not on its neighbours.
+ * ssi_edit_distance_workspace_bytes is 0 (nothing needs a workspace) and the entry accepts workspace == NULL; a workspace_bytes below it
+ * would be SSI_ERR_WORKSPACE.  n_pairs == 0 launches nothing.  SSI_ERR_ARG: a null pointer beside a non-zero size, a negative size,
+ * n_pairs >= 2^31. */
+#define SSI_EDIT_MAX_LEN 4096 /* the RoPE table of the benchmark model: no generation is longer */
+#define SSI_EDIT_COLS 4       /* hypothesis columns per lane */
+size_t ssi_edit_distance_workspace_bytes(int64_t n_pairs, int32_t max_len);
+int ssi_edit_distance(const int32_t* tokens, int64_t n_tokens, const int64_t* ref_start, const int32_t* ref_len, const int64_t* hyp_start,
+                      const int32_t* hyp_len, int64_t n_pairs, int32_t max_len, int32_t* out /* [n_pairs][4] */, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 /* ---- K8 + K9 as one entry per direction: tied LM head (TiedLinear over tok_embeddings, ssi/loss.py:8-14) + chunked CE (trainer.py:300) ----
  * fwd: logits_ws[rows, vocab_pad] = hidden[rows, dim] table[vocab_pad, dim]^T (table rows >= vocab are zero padding), then ssi_ce_fwd

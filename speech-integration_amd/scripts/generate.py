@@ -59,6 +59,8 @@ def main(cfg):
     draw = dict(check_sampling(params), sample=True, seed=int(cfg.gen.get("seed") or 0)) if sampled else {}
     if not sampled:
         check_greedy(params)
+    if bool(cfg.gen.get("mbr") or False) and int(draw.get("n", 1)) < 2 and min(int(cfg.gen.get("beam_width") or 1), int(cfg.gen.get("n_best") or 1)) < 2:
+        raise ValueError("gen.mbr=true needs candidates to choose among: gen.sample=true with sampling_params.n >= 2, or gen.beam_width > 1 with gen.n_best >= 2")
     pool = check_continuous(cfg.gen.get("continuous"), cfg.gen.get("admit_min"), int(cfg.gen.get("beam_width") or 1), int(draw.get("n", 1)))
     from ssi.model import get_device, get_dtype
     from ssi.train_utils import resolve_n_dsus
@@ -93,6 +95,8 @@ def main(cfg):
         constraints["kv_cache_dtype"] = "fp8"
     if check_weight_dtype(cfg.gen.get("weight_dtype"), bool(cfg.gen.get("small_batch") or False)) is not None:   # gen.weight_dtype: fp8 (needs gen.small_batch); auto (or the key absent) is absent from the call
         constraints["weight_dtype"] = "fp8"
+    if bool(cfg.gen.get("mbr") or False):                  # gen.mbr: outputs in minimum-Bayes-risk order; absent from the call otherwise
+        constraints["mbr"] = True
     constraints.update(pool)          # gen.continuous: batch_size is a pool of rows that is refilled; false (or the key absent) is absent from the call
     summary = generate_file(t.model, t.tokenizer, None if prompts is not None else str(cfg.gen.input), out_path,
                             max_new_tokens=int(cfg.sampling_params.max_tokens), stop_token_ids=None if stop is None else [int(s) for s in stop],

@@ -41,6 +41,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--weight-dtype", choices=("auto", "fp8"), default="auto",
                    help="fp8: the decode steps read the projection weights and the head as e4m3 codes with one power-of-two scale per output "
                         "channel, quantised once (changes values); auto: the model's weights")
+    p.add_argument("--mbr", action="store_true",
+                   help="print a prompt's samples in minimum-Bayes-risk order (by expected token error rate against each other); needs -n >= 2")
     p.add_argument("--jsonl", metavar="OUT", help="also write one record per prompt (the generations file's line format)")
     return p
 
@@ -81,6 +83,8 @@ def check_sampling_options(args) -> None:
         raise ValueError("-n, --top-k and --top-p need --temperature > 0 (temperature 0 is greedy decoding: one sample, no top-k, no top-p)")
     if args.template is None and (args.var or args.units is not None or args.dedup):
         raise ValueError("--var, --units and --dedup belong to --template")
+    if getattr(args, "mbr", False) and args.n < 2:
+        raise ValueError("--mbr chooses among a prompt's samples: -n >= 2 (and --temperature > 0)")
 
 
 def load(args):
@@ -109,7 +113,7 @@ def main(argv=None) -> int:
     found = probe(model, tokenizer, prompts, max_new_tokens=args.max_new_tokens, n=args.n, temperature=args.temperature, top_k=args.top_k,
                   top_p=args.top_p, seed=args.seed, repetition_penalty=args.repetition_penalty, frequency_penalty=args.frequency_penalty,
                   presence_penalty=args.presence_penalty, tokenizer_decoding=decoding, split_kv=args.split_kv,
-                  kv_cache_dtype=args.kv_cache_dtype, weight_dtype=args.weight_dtype)
+                  kv_cache_dtype=args.kv_cache_dtype, weight_dtype=args.weight_dtype, **({"mbr": True} if args.mbr else {}))
     for p in found:
         for text in p.texts:
             print(text)

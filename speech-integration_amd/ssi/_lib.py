@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 import torch
 
@@ -20,7 +20,8 @@ SSI_F32, SSI_BF16 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 IMPL_AUTO, IMPL_GENERIC, IMPL_MFMA, IMPL_MFMA_WG8 = 0, 1, 2, 3
 TILES_STATIC, TILES_DYNAMIC = 0, 1
-ABI_VERSION = 28
+ABI_VERSION = 29
+EDIT_MAX_LEN, EDIT_COLS = 4096, 4
 GEMM_SKINNY_MAX_ROWS = 64
 DECODE_PENALTY_LDS_MAX = 57344
 ADAMW_MAX_SEGS = 128
@@ -124,6 +125,8 @@ PROTOTYPES = {
     "ssi_ce_fwd_metrics": (c_int, [_P, c_int64, _P, _P, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_int, _P]),
     "ssi_ce_metrics_reduce": (c_int, [_P, _P, _P, c_int64, _P, c_int, c_int, c_int, _P, _P]),
     "ssi_seq_score_reduce": (c_int, [_P, _P, c_int64, _P, _P, c_int64, c_int, _P, _P]),
+    "ssi_edit_distance_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "ssi_edit_distance": (c_int, [_P, c_int64, _P, _P, _P, _P, c_int64, c_int32, _P, _P, c_size_t, _P]),
     "ssi_lmhead_ce_fwd": (c_int,[_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, c_int64, _P, c_int64, _P, _P, c_int, c_int, _P]),
     "ssi_lmhead_ce_bwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int64, _P, c_int64, _P, c_int64, c_int, c_int, _P]),
     "ssi_count_tokens": (c_int, [_P, _P, c_int64, _P, c_int, c_int64, c_int64, _P, _P]),

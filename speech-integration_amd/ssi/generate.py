@@ -39,11 +39,15 @@ slots (``prefill(slots=...)``), by a schedule that is host code (``PoolSchedule`
 sampler runs on ``ssi_decode_sample_rows`` / ``ssi_decode_sample_pen_rows``, which take the step (and the draw parameters) per row; the same
 entries serve per-prompt ``temperature`` / ``top_k`` / ``top_p`` lists in either mode.  Without the flag nothing of this runs.
 
+Minimum-Bayes-risk selection (``mbr_select``; ``mbr=True`` of ``sample`` with ``n >= 2`` and of ``beam_search`` with ``n_best >= 2``;
+``gen.mbr`` in ``conf/generate.yaml``): a prompt's candidates are reordered by their expected token error rate against each other, from the
+edit distances of every unordered pair (``ssi_edit_distance``, one launch and one read-back per call).  Without the flag nothing of this runs.
+
 Out of scope: per-row penalties, per-line parameters in the prompts JSONL, ``n > 8`` and ``best_of``, sampling
 inside beam search, ``beam_width > 8``, sharing the prompt's K / V read among a prompt's beams, beam
 search under data parallelism, pools for ``n > 1`` and for beams, paged caches, prefill rows mixed into a decode step (chunked prefill),
-moving a draining pool of few live rows onto the skinny path, HIP graphs, generation under data parallelism, and WER
-itself (its text normaliser is the reference's dependency; the JSONL written here is what its ``wer.py`` reads)."""
+moving a draining pool of few live rows onto the skinny path, HIP graphs, generation under data parallelism; for MBR selection posterior
+weights from ``cumulative_logprob``, word-level MBR and MBR under ``continuous``.  WER itself is ``ssi.wer`` and ``scripts/wer.py``."""
 
 from __future__ import annotations
 
@@ -53,6 +57,7 @@ from collections.abc import Sequence
 from dataclasses import dataclass
 from typing import Any
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -79,7 +84,10 @@ class Generation:
     choice (the chosen token was not the row's unconstrained first), None when no constraint was given — penalties count there: under
     ``generate`` with a penalty set it is the steps at which the mask OR the penalties changed the choice; ``score`` (``beam_search`` only):
     ``cumulative_logprob / len(token_ids) ** length_penalty``, what the hypotheses of a prompt are ordered by; ``n_kept_mean`` (``sample``
-    only): the mean over the generated tokens of the size of the set each was drawn from (after the mask, top-k and top-p)."""
+    only): the mean over the generated tokens of the size of the set each was drawn from (after the mask, top-k and top-p); ``mbr_risk``
+    (``sample`` / ``beam_search`` with ``mbr=True`` only, None otherwise): the candidate's risk under ``mbr_select``.  It is set on the
+    instance and is deliberately NOT a dataclass field: ``dataclasses.asdict`` of a Generation, which recorded results are compared by,
+    stays what it was."""
     token_ids: list[int]
     finish_reason: str
     stop_reason: int | None
@@ -88,6 +96,8 @@ class Generation:
     n_constrained: int | None = None
     score: float | None = None
     n_kept_mean: float | None = None
+    mbr_risk = None
+    mbr_index = None          # with mbr_risk: the candidate's position before the reorder
 
 
 def plan_groups(lengths: Sequence[int], batch_size: int) -> list[list[int]]:
@@ -822,6 +832,76 @@ def generate(model, prompts: Sequence[Any], *, max_new_tokens: int, stop_token_i
                        lambda n_slots, longest: (_new_cache(model, n_slots, longest + max_new_tokens, kv_dtype),), run_group)
 
 
+# ---- minimum-Bayes-risk selection ------------------------------------------------------------------------------------------------
+def mbr_select(candidates: Sequence[Sequence[Sequence[int]]], device) -> tuple[list[list[int]], list[list[float]]]:
+    """Minimum-Bayes-risk order of every prompt's candidates (``candidates[p][k]``: the token ids of candidate ``k`` of prompt ``p``, at
+    least two per prompt).  ``risk_k = (1 / (n - 1)) * sum_{j != k} dist(c_j, c_k) / max(1, len(c_j))``: the expected token error rate of
+    ``c_k`` with the other candidates as equally weighted pseudo-references.  ``dist`` is symmetric, so every unordered pair is computed
+    once, all prompts in one ``ssi_edit_distance`` launch; the sum is taken in float64 on the device, over ``j`` in index order (one add per
+    candidate position, so the bits do not depend on a reduction's shape), and read back once.
+    Returns ``(order, risk)``: ``order[p]`` the candidate indices by rising risk, then by index (``order[p][0]`` is the first minimum);
+    ``risk[p][k]`` the risk of candidate ``k`` (input order)."""
+    from .wer import edit_distance_pairs
+    cands = [list(cs) for cs in candidates]
+    if any(len(cs) < 2 for cs in cands):
+        raise ValueError("mbr_select: every prompt needs at least two candidates (the risk of one candidate against no other is undefined)")
+    if not cands:
+        return [], []
+    dev = torch.device(device)
+    seqs = [c for cs in cands for c in cs]
+    base, pairs, width = 0, [], max(len(cs) for cs in cands)
+    other = np.full((len(seqs), width), -1, dtype=np.int64)                # [candidate k, position j] -> its pair, -1 where j == k or absent
+    ref_of = np.zeros((len(seqs), width), dtype=np.int64)                  # ... -> the flat index of candidate j
+    for cs in cands:
+        n = len(cs)
+        for j in range(n):
+            ref_of[base:base + n, j] = base + j
+            for k in range(j + 1, n):
+                other[base + k, j] = other[base + j, k] = len(pairs)
+                pairs.append((base + j, base + k))
+        base += n
+    dist = edit_distance_pairs(seqs, pairs, dev)[:, 0].to(torch.float64)
+    length = torch.tensor([max(1, len(c)) for c in seqs], dtype=torch.float64).to(dev)
+    count = torch.tensor([len(cs) - 1 for cs in cands for _ in cs], dtype=torch.float64).to(dev)
+    other, ref_of = torch.from_numpy(other).to(dev), torch.from_numpy(ref_of).to(dev)
+    term = torch.where(other >= 0, dist[other.clamp(min=0)] / length[ref_of], torch.zeros((), dtype=torch.float64, device=dev))
+    risk = torch.zeros(len(seqs), dtype=torch.float64, device=dev)
+    for j in range(width):
+        risk = risk + term[:, j]
+    flat = (risk / count).tolist()                                         # the read-back
+    order, risks, base = [], [], 0
+    for cs in cands:
+        r = flat[base:base + len(cs)]
+        base += len(cs)
+        risks.append(r)
+        order.append(sorted(range(len(cs)), key=lambda k: (r[k], k)))
+    return order, risks
+
+
+def mbr_candidate(gen: Generation) -> list[int]:
+    """What MBR compares: the generated ids up to and without the stop token."""
+    return list(gen.token_ids[:-1] if gen.finish_reason == "stop" else gen.token_ids)
+
+
+def _mbr_reorder(found: list[list[Generation]], device) -> list[list[Generation]]:
+    """Every prompt's Generations in ``mbr_select``'s order, ``mbr_risk`` set and ``mbr_index`` (the position before the reorder) beside it."""
+    order, risks = mbr_select([[mbr_candidate(g) for g in gs] for gs in found], device)
+    out = []
+    for gs, o, r in zip(found, order, risks):
+        for k, g in enumerate(gs):
+            g.mbr_risk, g.mbr_index = r[k], k
+        out.append([gs[k] for k in o])
+    return out
+
+
+def _check_mbr(who: str, mbr, n: int, what: str) -> bool:
+    if not isinstance(mbr, bool):
+        raise ValueError(f"{who}: mbr = {mbr!r}: True or False")
+    if mbr and n < 2:
+        raise ValueError(f"{who}: mbr=True needs at least two candidates per prompt ({what} = {n})")
+    return mbr
+
+
 # ---- beam search -----------------------------------------------------------------------------------------------------------------
 def _check_beam(beam_width, length_penalty, n_best) -> tuple[int, float, int]:
     """The ranges of the three beam arguments (``ValueError``): ``1 <= n_best <= beam_width <= MAX_BEAM_WIDTH``, ``length_penalty`` finite, >= 0."""
@@ -842,7 +922,7 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
                 batch_size: int = 256, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
                 presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None,
              split_kv: bool = False, kv_cache_dtype: str | None = None, weight_dtype: str | None = None,
-             weight_quant=None, continuous: bool = False, admit_min: int | None = None) -> list[list[Generation]]:
+             weight_quant=None, continuous: bool = False, admit_min: int | None = None, mbr: bool = False) -> list[list[Generation]]:
     """The ``n_best <= beam_width <= 8`` best hypotheses of every prompt, best first, in INPUT order; ``cumulative_logprob`` (the sum of the
     tokens' log-probabilities under the unconstrained distribution) and ``score`` are always set.  A group holds ``batch_size // beam_width``
     prompts, so a step is at most ``batch_size`` rows.  The rules, with ``W = beam_width``:
@@ -863,8 +943,11 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
     ``small_batch``, ``split_kv``: handed to every ``decode_step_beam`` (``generate``'s rules, on the group's ``prompts * beam_width`` rows).
     ``kv_cache_dtype``: ``generate``'s; the prompt cache and the beam cache are of the same kind.
     ``weight_dtype``, ``weight_quant``: ``generate``'s.
-    ``continuous=True`` is refused (``ValueError``): the beams of a prompt share its slot, and refilling that is not built."""
+    ``continuous=True`` is refused (``ValueError``): the beams of a prompt share its slot, and refilling that is not built.
+    ``mbr=True`` (``n_best >= 2``, else a ``ValueError`` before any launch): every prompt's ``n_best`` hypotheses come back in
+    ``mbr_select``'s order instead of by score, each with its ``mbr_risk``."""
     W, length_penalty, n_best = _check_beam(beam_width, length_penalty, n_best)
+    mbr = _check_mbr("beam_search", mbr, n_best, "n_best")
     if _check_continuous("beam_search", continuous, admit_min):
         raise ValueError("beam_search: continuous batching is not built for beam search (the beams of a prompt share its slot)")
     kv_dtype = check_kv_cache_dtype(kv_cache_dtype)
@@ -890,7 +973,8 @@ def beam_search(model, prompts: Sequence[Any], *, beam_width: int, max_new_token
         return _beam_group(model, *caches[:2], seqs, W, max_new_tokens, stop, int(pad_id), length_penalty, n_best, caches[2], min_new_tokens,
                            small_batch, small_batch_report, split_kv, weights)
 
-    return _run_groups(model, prompts, batch_size // W, max_new_tokens, stop_token_ids, None, 0, open_caches, run_group)       # (its mask is cont)
+    found = _run_groups(model, prompts, batch_size // W, max_new_tokens, stop_token_ids, None, 0, open_caches, run_group)      # (its mask is cont)
+    return _mbr_reorder(found, model.device) if mbr else found
 
 
 def _beam_group(model, pcache, bcache, seqs: list[Tensor], W: int, max_new: int, stop: Tensor, pad_id: int, length_penalty: float, n_best: int,
@@ -1038,7 +1122,7 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
            presence_penalty: float = 0.0, small_batch: bool = False, small_batch_report: dict | None = None,
              split_kv: bool = False, kv_cache_dtype: str | None = None, weight_dtype: str | None = None,
              weight_quant=None, continuous: bool = False, admit_min: int | None = None,
-             continuous_report: dict | None = None) -> list[list[Generation]]:
+             continuous_report: dict | None = None, mbr: bool = False) -> list[list[Generation]]:
     """``n`` (1..8) sampled continuations of every prompt, in INPUT order and per prompt in sample order; ``cumulative_logprob`` (the tokens'
     log-probabilities under the unconstrained distribution at temperature 1, what ``ssi.score`` assigns) and ``n_kept_mean`` are always set.
     The token of a step is ``ops.decode_sample``'s with ``step`` the loop index and ``sequence = prompt index * n + sample index``: a pure function
@@ -1060,8 +1144,11 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
     the bits of the scalar entry launched with the row's own values.  With scalars the static path launches what it always launched.
     ``continuous``, ``admit_min``, ``continuous_report``: ``generate``'s, for ``n == 1`` (``n > 1`` with ``continuous=True`` is a ``ValueError``:
     the samples of a prompt share its slot); the pool's steps go through the ``_rows`` entries with ``step`` = the row's own token count, so a
-    sample stays the pure function of ``(seed, sequence, step)`` and the row that it is in a static group."""
+    sample stays the pure function of ``(seed, sequence, step)`` and the row that it is in a static group.
+    ``mbr=True`` (``n >= 2``, else a ``ValueError`` before any launch): the same ``n`` samples of every prompt, in ``mbr_select``'s order
+    instead of sample order, each with its ``mbr_risk``."""
     n, draw = _check_draws(n, temperature, top_k, top_p, seed, len(prompts))
+    mbr = _check_mbr("sample", mbr, n, "n")
     kv_dtype = check_kv_cache_dtype(kv_cache_dtype)
     weights = _weight_source(model, weight_dtype, weight_quant, small_batch)
     pen = _check_penalties(repetition_penalty, frequency_penalty, presence_penalty)
@@ -1096,7 +1183,8 @@ def sample(model, prompts: Sequence[Any], *, n: int = 1, temperature: float, top
         found = _token_loop(choose, started, caches, refused, [int(s.numel()) for s in seqs for _ in range(n)], max_new_tokens, stop, int(pad_id))
         return [found[s * n:s * n + n] for s in range(len(seqs))]
 
-    return _run_groups(model, prompts, batch_size // n, max_new_tokens, stop_token_ids, masks, min_new_tokens, open_caches, run_group)
+    found = _run_groups(model, prompts, batch_size // n, max_new_tokens, stop_token_ids, masks, min_new_tokens, open_caches, run_group)
+    return _mbr_reorder(found, model.device) if mbr else found
 
 
 # ---- JSONL in, JSONL out ---------------------------------------------------------------------------------------------------------
@@ -1107,10 +1195,12 @@ def output_record(item_id: Any, prompt_ids: Sequence[int], gen: "Generation | Se
     decoding = dict(decoding or {})
     special = {v: k for k, v in getattr(tokenizer, "special_tokens", {}).items()}
     gens = [gen] if isinstance(gen, Generation) else list(gen)
+    mbr = [{} if g.mbr_risk is None else {"index": g.mbr_index, "mbr_risk": g.mbr_risk} for g in gens]   # risk order: ``index`` is the original one
     return {"id": item_id, "prompt_token_ids": [int(t) for t in prompt_ids], "prompt": tokenizer.decode(list(prompt_ids), **decoding),
-            "outputs": [{"index": j, "text": tokenizer.decode(g.token_ids, **decoding), "token_ids": g.token_ids,
-                         "cumulative_logprob": g.cumulative_logprob, "finish_reason": g.finish_reason, "stop_reason": g.stop_reason,
-                         "stop_reason_text": special.get(g.stop_reason) if g.stop_reason is not None else None} for j, g in enumerate(gens)]}
+            "outputs": [dict({"index": j, "text": tokenizer.decode(g.token_ids, **decoding), "token_ids": g.token_ids,
+                              "cumulative_logprob": g.cumulative_logprob, "finish_reason": g.finish_reason, "stop_reason": g.stop_reason,
+                              "stop_reason_text": special.get(g.stop_reason) if g.stop_reason is not None else None}, **m)
+                        for j, (g, m) in enumerate(zip(gens, mbr))]}
 
 
 def _read_prompts(tokenizer, in_path: str) -> tuple[list[Any], list[list[int]]]:
@@ -1163,7 +1253,12 @@ def generate_file(model, tokenizer, in_path: str | None, out_path: str, *, max_n
     gains ``"fp8_weight_groups"``: the groups whose steps read FP8 weights.
     ``continuous=True`` (and ``admit_min``) in ``kw`` go to ``generate`` / ``sample`` (``n > 1`` and ``beam_width > 1`` refuse it), and the summary
     gains ``"continuous": True``, ``"decode_steps"``, ``"row_steps_live"``, ``"row_steps_total"`` and ``"admissions"``; ``False`` (the default) and
-    a null ``admit_min`` are not passed on and add no key."""
+    a null ``admit_min`` are not passed on and add no key.
+    ``mbr=True`` in ``kw`` goes to ``sample`` / ``beam_search`` (greedy decoding has one candidate and refuses it): ``outputs`` are then in risk
+    order — ``outputs[0]`` is the MBR choice, what ``scripts/wer.py`` scores — each with ``mbr_risk`` and its original ``index``, and the summary
+    gains ``"mbr_changed"``: the prompts whose first output is not candidate 0.  ``False`` (the default) is not passed on and adds no key."""
+    if not kw.get("mbr", False):
+        kw.pop("mbr", None)
     kv_dtype = check_kv_cache_dtype(kw.pop("kv_cache_dtype", None))
     fp8 = {} if kv_dtype is None else {"kv_cache_dtype": kv_dtype}
     w8 = {} if check_weight_dtype(kw.pop("weight_dtype", None), bool(kw.get("small_batch", False))) is None else {"weight_dtype": "fp8"}
@@ -1209,6 +1304,8 @@ def _run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_tok
         raise ValueError("generate_file: sample together with beam_width > 1 (sampling inside beam search is not built)")
     if not (sampled or beams):
         _check_beam(1, beam.get("length_penalty", 1.0), beam.get("n_best", 1))      # (n_best > 1 needs a beam)
+        if "mbr" in kw:
+            raise ValueError("generate_file: mbr=True needs candidates to choose among: sample=True with n >= 2, or beam_width > 1 with n_best >= 2")
     run, mode = (sample, draw) if sampled else (beam_search, beam) if beams else (generate, {})
     if sampled or beams:
         kw.pop("logprobs", None)
@@ -1233,6 +1330,8 @@ def _run_file(model, tokenizer, ids, prompts, out_path, max_new_tokens, stop_tok
         summary["beam_width"] = int(beam["beam_width"])
     elif kw.get("allowed_token_ids") is not None or int(kw.get("min_new_tokens", 0)) != 0 or pen is not None:
         summary["constrained_tokens"] = sum(g.n_constrained or 0 for g in gens)
+    if kw.get("mbr"):
+        summary["mbr_changed"] = sum(gs[0].mbr_index != 0 for gs in found)
     return dict(summary, **pen_summary, **stats)       # (pen_summary: empty under beam search, which refuses a set penalty)
 
 

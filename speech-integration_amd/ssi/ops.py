@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
 __all__ = ["gemm_skinny", "gemm_skinny_rope", "gemm_skinny_swiglu", "weight_quant_fp8", "gemm_skinny_w8", "gemm_skinny_rope_w8", "gemm_skinny_swiglu_w8", "lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "attn_decode_beam", "attn_decode_split", "attn_decode_beam_split", "attn_decode_split_span", "attn_decode_split_workspace", "decode_select", "decode_sample", "decode_select_pen", "decode_sample_pen", "decode_penalty_lds_bytes", "topk_logprob", "swiglu_fwd",
-           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "ema_update", "set_impl", "set_attn_impl", "attn_last_dispatch",
+           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "edit_distance", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "ema_update", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "kv_store_fp8", "attn_decode_fp8", "attn_decode_beam_fp8", "attn_decode_split_fp8", "attn_decode_beam_split_fp8",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
@@ -933,6 +933,23 @@ def seq_score_reduce(row_nll: Tensor, row_rank: Tensor, rows: int, seq_start: Te
     assert seq_end.numel() == n_seq and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= 4 * n_seq
     check(_lib.load().ssi_seq_score_reduce(ptr(row_nll), ptr(row_rank), int(rows), ptr(seq_start), ptr(seq_end), n_seq, int(topk), ptr(out),
                                            stream_ptr()), "ssi_seq_score_reduce")
+
+
+def edit_distance(tokens: Tensor, ref_start: Tensor, ref_len: Tensor, hyp_start: Tensor, hyp_len: Tensor, out: Tensor, max_len: int) -> None:
+    """``out`` (int32 ``[n_pairs, 4]``, overwritten) = ``{dist, S, D, I}`` of the edit distance between the spans
+    ``tokens[ref_start[p] : + ref_len[p]]`` and ``tokens[hyp_start[p] : + hyp_len[p]]`` of one flat int32 device buffer (starts int64, lengths
+    int32, device tensors the host never reads).  ``max_len`` (at most ``_lib.EDIT_MAX_LEN``) bounds every length; a pair with a span that is
+    longer, negative or outside ``tokens`` gets four -1.  The definition is in ``include/ssi_hip.h``."""
+    lib = _lib.load()
+    n_pairs = ref_start.numel()
+    assert tokens.dtype == torch.int32 and tokens.is_contiguous() and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= 4 * n_pairs
+    for start, length in ((ref_start, ref_len), (hyp_start, hyp_len)):
+        assert start.dtype == torch.int64 and start.is_contiguous() and length.dtype == torch.int32 and length.is_contiguous()
+        assert start.numel() == n_pairs and length.numel() == n_pairs
+    need = lib.ssi_edit_distance_workspace_bytes(n_pairs, int(max_len))
+    workspace = _byte_ws(need, tokens) if need else None
+    check(lib.ssi_edit_distance(ptr(tokens), tokens.numel(), ptr(ref_start), ptr(ref_len), ptr(hyp_start), ptr(hyp_len), n_pairs, int(max_len),
+                                ptr(out), ptr(workspace), need, stream_ptr()), "ssi_edit_distance")
 
 
 def lmhead_ce_fwd(hidden: Tensor, table: Tensor, labels: Tensor, vocab: int, ignore_index: int, logits_ws: Tensor, row_loss: Tensor,

@@ -79,14 +79,17 @@ class Probe:
 def probe(model, tokenizer, prompts: Sequence[Sequence[int]], *, max_new_tokens: int = 128, n: int = 1, temperature: float = 0.0, top_k: int = -1,
           top_p: float = 1.0, seed: int = 0, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0, presence_penalty: float = 0.0,
           stop_token_ids: Sequence[int] | None = None, tokenizer_decoding: Mapping[str, Any] | None = None, batch_size: int = 64,
-          split_kv: bool = False, kv_cache_dtype: str | None = None, weight_dtype: str | None = None, weight_quant=None) -> list[Probe]:
+          split_kv: bool = False, kv_cache_dtype: str | None = None, weight_dtype: str | None = None, weight_quant=None, mbr: bool = False) -> list[Probe]:
     """Continue every prompt (token ids, as ``render_prompt`` gives them): greedily (``generate``, with log-probabilities) at ``temperature``
     0, where ``n`` must be 1, else ``n`` samples (``sample``) — both with ``small_batch=True`` and groups of at most ``batch_size`` rows, so a few
     prompts never pay a 256-row step.  ``split_kv``: handed on to the loop (the split-KV decode attention).  ``kv_cache_dtype``: None, "auto" or
     "fp8", handed on to the loop when it is "fp8" (``ssi.generate.check_kv_cache_dtype``).  ``weight_dtype``: None, "auto" or "fp8"
     (``ssi.generate.check_weight_dtype``); under "fp8" the model's weights are quantised ONCE for the whole call (``model.quantize_weights()``, or the
-    ``weight_quant`` built before and handed in to reuse it across calls) and every group reads the same object.  ``stop_token_ids`` default to the tokenizer's ``[eom_id, eot_id, eos_id]``."""
+    ``weight_quant`` built before and handed in to reuse it across calls) and every group reads the same object.  ``stop_token_ids`` default to the tokenizer's ``[eom_id, eot_id, eos_id]``.
+    ``mbr=True`` (``n >= 2`` samples, else a ``ValueError``): every prompt's samples in minimum-Bayes-risk order (``sample(mbr=True)``)."""
     prompts = [[int(t) for t in p] for p in prompts]
+    if mbr and (float(temperature) == 0.0 or int(n) < 2):
+        raise ValueError("probe: mbr=True chooses among samples: a temperature > 0 and n >= 2")
     stop = default_stop_token_ids(tokenizer) if stop_token_ids is None else [int(t) for t in stop_token_ids]
     kw = dict(max_new_tokens=int(max_new_tokens), stop_token_ids=stop, pad_id=int(getattr(tokenizer, "pad_id", 0) or 0), batch_size=int(batch_size),
               repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, small_batch=True,
@@ -98,7 +101,8 @@ def probe(model, tokenizer, prompts: Sequence[Sequence[int]], *, max_new_tokens:
             raise ValueError("probe: temperature 0 is greedy decoding: one sample, no top-k, no top-p (set a temperature to draw)")
         found = [[g] for g in generate(model, prompts, logprobs=True, **kw)]
     else:
-        found = sample(model, prompts, n=int(n), temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed), **kw)
+        found = sample(model, prompts, n=int(n), temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed), **kw,
+                       **({"mbr": True} if mbr else {}))
     decoding = dict(tokenizer_decoding or {})
     return [Probe(p, list(gs), [tokenizer.decode(g.token_ids, **decoding) for g in gs]) for p, gs in zip(prompts, found)]
 

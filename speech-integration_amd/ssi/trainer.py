@@ -173,6 +173,7 @@ class Trainer:
         self._lag_buffers: list[Tensor] = []                   # page-locked buffers of finished read-backs, reused
         self._t_last_arrival = 0.0                             # when the previous window's results were seen on the host
         self.dev_metrics: dict[str, Any] | None = None         # per-token-type keys of the last evaluation (``eval_token_metrics``)
+        self.dev_wer: dict[str, Any] | None = None             # dev_ter, dev_wer, dev_wer_n of the last evaluation (``eval_wer``)
         self.dev_pairs: dict[str, Any] | None = None           # dev_pair_acc, dev_pair_acc_mean, dev_pair_n of the last evaluation (``eval_pairs``)
         self.z_loss_coeff = 0.0                                # ``z_loss_coeff`` of the config (``setup``); 0: no z-loss anywhere
         self.label_smoothing = 0.0                             # ``label_smoothing`` of the config (``setup``); 0: plain cross-entropy
@@ -776,10 +777,14 @@ class Trainer:
 
     def _evaluate(self) -> float:
         """The dev loss; with ``eval_token_metrics`` the per-token-type keys of the same pass are left in ``self.dev_metrics`` for the log record;
-        with ``eval_pairs`` (a JSONL file of scored pairs, ``ssi.score.score_file``) the pair accuracies in ``self.dev_pairs``."""
+        with ``eval_pairs`` (a JSONL file of scored pairs, ``ssi.score.score_file``) the pair accuracies in ``self.dev_pairs``; with ``eval_wer``
+        (a JSONL file of prompts and references) the error rates of what the model generates in ``self.dev_wer``."""
         self.dev_pairs = None
         if self.cfg.get("eval_pairs"):
             self.dev_pairs = self._score_pairs(str(self.cfg.eval_pairs))
+        self.dev_wer = None
+        if self.cfg.get("eval_wer"):
+            self.dev_wer = self._generate_error_rates(str(self.cfg.eval_wer))
         kwargs = self._eval_kwargs()
         self.dev_metrics = None
         if not self.cfg.get("eval_token_metrics", False):
@@ -820,6 +825,48 @@ class Trainer:
         if out["dev_pair_n"]:  # a file without pairs reports its count alone: no NaN reaches the log record
             out.update(dev_pair_acc=summary["pair_acc"], dev_pair_acc_mean=summary["pair_acc_mean"])
         LOGGER.info(f"Global Step {self.global_step} | Dev pairs: " + " | ".join(f"{k}: {v}" for k, v in out.items()))
+        return out
+
+    def _generate_error_rates(self, path: str) -> dict[str, Any]:
+        """(not in the reference) ``eval_wer``: greedy generations from the prompts of a JSONL file — every line ``id``, one of ``tokens`` and
+        ``text`` (the prompt) and one of ``reference_tokens`` and ``reference`` — scored against their references by ``ssi.wer``:
+        ``dev_ter``, the corpus token error rate (generated ids up to and without the stop token against ``reference_tokens``, or against the
+        tokenised ``reference``); ``dev_wer``, on "basic"-normalised words of the decoded text, when every line carries ``reference`` text; and
+        ``dev_wer_n``, the number of utterances.  ``generate`` runs under ``inference_mode`` in ``eval()`` and puts the mode back; greedy
+        decoding draws no random number, so the dev loss that follows is the one of a run without the key.  Every rank generates the whole
+        file, as ``_score_pairs`` scores it (no collective)."""
+        import json
+        from . import wer
+        from .generate import generate, mbr_candidate
+        tok = self.tokenizer
+        prompts, ref_tokens, ref_texts = [], [], []
+        with open(path, encoding="utf-8") as f:
+            for ln, line in enumerate(f, 1):
+                if not line.strip():
+                    continue
+                item = json.loads(line)
+                if ("tokens" in item) == ("text" in item) or ("reference_tokens" in item) == ("reference" in item):
+                    raise ValueError(f"{path}:{ln}: an item needs exactly one of 'tokens' / 'text' and one of 'reference_tokens' / 'reference'")
+                prompts.append([int(t) for t in item["tokens"]] if "tokens" in item else list(tok.encode(item["text"], add_bos=True, add_eos=False)))
+                ref_texts.append(item.get("reference"))
+                ref_tokens.append([int(t) for t in item["reference_tokens"]] if "reference_tokens" in item
+                                  else list(tok.encode(item["reference"], add_bos=False, add_eos=False)))
+        out: dict[str, Any] = {"dev_wer_n": len(prompts)}
+        if prompts:
+            special = getattr(tok, "special_tokens", {})
+            stop = [int(getattr(tok, attr, special.get(name))) for attr, name in
+                    (("eom_id", "<|eom_id|>"), ("eot_id", "<|eot_id|>"), ("eos_id", "<|end_of_text|>"))]
+            found = generate(self.model, prompts, max_new_tokens=int(self.cfg.get("eval_wer_max_new_tokens", 256) or 256), stop_token_ids=stop,
+                             pad_id=int(getattr(tok, "pad_id", 0) or 0), batch_size=256)
+            hyps = [mbr_candidate(g) for g in found]
+            ter = wer.error_rate(ref_tokens, hyps, level="token", device=self.device)
+            if ter["wer"] is not None:      # a file of empty references reports its count alone: no NaN reaches the log record
+                out["dev_ter"] = ter["wer"]
+            if all(t is not None for t in ref_texts):
+                words = wer.error_rate(ref_texts, [tok.decode(h) for h in hyps], level="word", normalizer="basic", device=self.device)
+                if words["wer"] is not None:
+                    out["dev_wer"] = words["wer"]
+        LOGGER.info(f"Global Step {self.global_step} | Dev error rates: " + " | ".join(f"{k}: {v}" for k, v in out.items()))
         return out
 
     def _log_metrics(self, epoch: int, iter_idx: int, loss_to_log: float, snapshot: dict[str, Any] | None = None,
@@ -869,6 +916,8 @@ class Trainer:
                 record.update(self.dev_metrics)
             if self.dev_pairs is not None:  # eval_pairs: dev_pair_acc, dev_pair_acc_mean, dev_pair_n
                 record.update(self.dev_pairs)
+            if self.dev_wer is not None:  # eval_wer: dev_ter, dev_wer, dev_wer_n
+                record.update(self.dev_wer)
             if dev_loss_ema is not None:  # ema_decay + ema_eval: the same dev loss on the averaged weights
                 record["dev_loss_ema"] = dev_loss_ema
         if self.rank == 0:
