@@ -35,7 +35,8 @@
 extern "C" {
 #endif
 
-#define SSI_ABI_VERSION 29 /* 29: + ssi_edit_distance, ssi_edit_distance_workspace_bytes (edit distance with substitution, deletion and insertion counts between spans of int32 ids, many pairs per launch: error rates and minimum-Bayes-risk selection; opt-in)
+#define SSI_ABI_VERSION 30 /* 30: + ssi_bpe_pair_count, ssi_bpe_train_workspace_bytes, ssi_bpe_train_begin, ssi_bpe_merge, ssi_bpe_encode (byte-pair encoding over discrete speech units: a trainer whose state stays on the device, and an encoder for many sequences per launch; opt-in)
+                           * 29: + ssi_edit_distance, ssi_edit_distance_workspace_bytes (edit distance with substitution, deletion and insertion counts between spans of int32 ids, many pairs per launch: error rates and minimum-Bayes-risk selection; opt-in)
                            * 28: + ssi_decode_sample_rows, ssi_decode_sample_pen_rows (the two sampling entries with the step and the draw parameters per row, from device arrays: rows of different ages and requests in one launch; opt-in)
                            * 27: + ssi_weight_quant_fp8, ssi_gemm_skinny_w8, ssi_gemm_skinny_rope_w8, ssi_gemm_skinny_swiglu_w8 (weight matrices as e4m3 codes with one power-of-two exponent per row, and the skinny GEMMs over them: FP8 weights for small-batch decoding; opt-in)
                            * 26: + ssi_kv_store_fp8, ssi_attn_decode_fp8, ssi_attn_decode_beam_fp8, ssi_attn_decode_split_fp8, ssi_attn_decode_beam_split_fp8 (a K/V cache of e4m3 codes with one power-of-two exponent per line, and decode attention over it; opt-in)
@@ -730,6 +731,59 @@ size_t ssi_edit_distance_workspace_bytes(int64_t n_pairs, int32_t max_len);
 int ssi_edit_distance(const int32_t* tokens, int64_t n_tokens, const int64_t* ref_start, const int32_t* ref_len, const int64_t* hyp_start,
                       const int32_t* hyp_len, int64_t n_pairs, int32_t max_len, int32_t* out /* [n_pairs][4] */, void* workspace,
                       size_t workspace_bytes, void* stream);
+
+/* ---- Byte-pair encoding over discrete speech units (ABI v30; produces the "compressed speech representations obtained using BPE" of the
+ * reference's plans/MASTER PLAN.md; opt-in, nothing else calls it) ----
+ * THE DEFINITION (restated in plain Python in tests/unit_bpe_ref.py).
+ * Corpus: one flat int32 buffer of symbols in [0, V); sequences are divided by the in-band separator SSI_BPE_SEP (-1).  A PAIR is two
+ *   neighbouring symbols of one sequence; a pair never includes a separator.  c(a, b) is the number of positions i with
+ *   (x[i], x[i+1]) == (a, b); overlapping positions count: a a a holds two (a, a).
+ * Merge m: the pair with the largest count, ties broken by the smallest a, then the smallest b; it gets the id n_base + m.  Training stops
+ *   before merge m if the largest count is below min_frequency (>= 1, default 2) or m == n_merges.
+ * Applying (a, b) -> z: within each sequence from left to right, where (x[i], x[i+1]) == (a, b) write z and continue at i + 2; for a == b a
+ *   run of k equal symbols becomes k / 2 times z, followed by one a if k is odd.  Then the buffer is closed up; separators stay.
+ * Encoding a sequence with a merge list applies merges 0, 1, ... in order.  Equivalently: repeatedly apply the lowest-numbered merge that has
+ *   an adjacent pair present — the same, because a merge that contains n_base + r is numbered above r: applying merge r creates only pairs
+ *   that hold n_base + r, which no merge numbered r or below contains, so the lowest number present never decreases.  Decoding expands ids
+ *   >= n_base recursively; decode(encode(u)) == u.
+ * Bad ids: an id outside [0, V) other than -1 is checked before any address is formed from it and acts as a separator (as ssi_attn_decode_beam
+ *   treats an index outside its cache).  ssi_bpe_pair_count and ssi_bpe_train_begin count each once into *n_bad; ssi_bpe_train_begin writes the
+ *   separator in its place into the working buffer; ssi_bpe_encode leaves it where it is.
+ *
+ * ssi_bpe_pair_count ADDS c(a, b) of ids[0..n) to table[a * stride + b] (uint32; the caller clears it; stride >= V, at most
+ * SSI_BPE_MAX_VOCAB) with integer atomics, equal addresses combined within a wave first: integer adds commute, so the table is exact whatever
+ * the order.  n_bad may be NULL.
+ *
+ * The trainer keeps its state on the device: two id buffers of n ids that swap roles per merge (merge m reads buffer m & 1), the table
+ * uint32[v_cap * v_cap] with v_cap = n_base + n_merges <= SSI_BPE_MAX_VOCAB (16 384: 1 GiB; more is SSI_ERR_UNSUPPORTED before any launch),
+ * the merge list int32[n_merges][3] = {a, b, count}, and int32 state[SSI_BPE_STATE_WORDS] (indices SSI_BPE_ST_*: done, merges made, the last
+ * pair and its count, n_bad, and at SSI_BPE_ST_LEN + (m & 1) the length of buffer m & 1).  ssi_bpe_train_begin clears the table, copies the
+ * corpus into buf0 with bad ids replaced, counts, and sets the state.  ssi_bpe_merge launches merge m: best pair (reads (n_base + m)^2
+ * entries), mark, scan, close up and an INCREMENTAL count update (only pairs beside a merged window change; a pair is owned by its right-hand
+ * position).  Its kernels read the pair and `done` from the state, and after done they do nothing: the host launches merge after merge and
+ * reads the state back at a cadence of its choice; the result is in buffer state[SSI_BPE_ST_M] & 1.  n_upper is the host's bound on the current
+ * length (the last length it read; the grid).  Whether a position of a run of a starts an (a, a) merge depends on the parity of its offset from
+ * the run's start, which may lie any number of SSI_BPE_TILE-id tiles to the left: it is carried as a prefix maximum through the same three
+ * launches that compute the closed-up offsets.  The kernel boundary is the only synchronisation between workgroups.  n < 2^31.
+ *
+ * ssi_bpe_encode: sequences are spans of one flat buffer (as ssi_edit_distance), one workgroup per sequence with the sequence and its pair
+ * ranks in LDS (three int32 arrays: 4096 ids is 51 KiB of the 64 KiB a workgroup may declare, hence SSI_BPE_ENCODE_MAX_LEN; a larger max_len
+ * is SSI_ERR_UNSUPPORTED).  rank_table is int32[V * V], -1 meaning no merge, built by the host from the merge list; V = n_base + n_merges.
+ * Sequence s is written to out[seq_start[s] .. + out_len[s]); a bad span (negative, longer than max_len, outside tokens) gives out_len -1 for
+ * that sequence alone.  A sequence's result depends on that sequence and the table only. */
+#define SSI_BPE_SEP (-1)
+#define SSI_BPE_TILE 4096           /* ids per workgroup of the trainer's tile kernels */
+#define SSI_BPE_MAX_VOCAB 16384     /* n_base + n_merges */
+#define SSI_BPE_ENCODE_MAX_LEN 4096
+#define SSI_BPE_STATE_WORDS 8
+enum { SSI_BPE_ST_DONE = 0, SSI_BPE_ST_M = 1, SSI_BPE_ST_A = 2, SSI_BPE_ST_B = 3, SSI_BPE_ST_COUNT = 4, SSI_BPE_ST_NBAD = 5, SSI_BPE_ST_LEN = 6 };
+int ssi_bpe_pair_count(const int32_t* ids, int64_t n, int32_t V, int32_t stride, uint32_t* table, int32_t* n_bad, void* stream);
+size_t ssi_bpe_train_workspace_bytes(int64_t n);
+int ssi_bpe_train_begin(const int32_t* ids, int64_t n, int32_t n_base, int32_t v_cap, int32_t* buf0, uint32_t* table, int32_t* state, void* stream);
+int ssi_bpe_merge(int32_t* buf0, int32_t* buf1, int64_t n_cap, int64_t n_upper, int32_t n_base, int32_t v_cap, int32_t m, int32_t min_frequency,
+                  uint32_t* table, int32_t* merges, int32_t* state, void* workspace, size_t workspace_bytes, void* stream);
+int ssi_bpe_encode(const int32_t* tokens, int64_t n_tokens, const int64_t* seq_start, const int32_t* seq_len, int64_t n_seq, int32_t max_len,
+                   const int32_t* rank_table, int32_t V, int32_t n_base, int32_t* out, int32_t* out_len, void* stream);
 
 /* ---- K8 + K9 as one entry per direction: tied LM head (TiedLinear over tok_embeddings, ssi/loss.py:8-14) + chunked CE (trainer.py:300) ----
  * fwd: logits_ws[rows, vocab_pad] = hidden[rows, dim] table[vocab_pad, dim]^T (table rows >= vocab are zero padding), then ssi_ce_fwd

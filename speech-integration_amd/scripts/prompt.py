@@ -26,6 +26,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--var", action="append", default=[], metavar="K=V", help="a template variable (may be repeated)")
     p.add_argument("--units", help="speech units for the template's speech_units variable, separated by spaces or commas")
     p.add_argument("--dedup", action="store_true", help="collapse runs of equal speech units before they are rendered")
+    p.add_argument("--unit-bpe", metavar="FILE", help="a merges file of scripts/unit_bpe.py train: the --units are BPE-encoded (after --dedup); "
+                                                      "--n-dsus is then its n_base + n_merges")
     p.add_argument("--max-new-tokens", type=int, default=128)
     p.add_argument("-n", type=int, default=1, help="samples per prompt (needs --temperature > 0)")
     p.add_argument("--temperature", type=float, default=0.0, help="0: greedy decoding")
@@ -66,10 +68,12 @@ def template_variables(args) -> dict:
 def prompts_of(args, tokenizer) -> list[list[int]]:
     """The prompts' token ids from the parsed arguments (``ValueError`` for --var / --units / --dedup without --template)."""
     from ssi.prompting import render_prompt
-    if args.template is None and (args.var or args.units is not None or args.dedup):
-        raise ValueError("--var, --units and --dedup belong to --template")
+    unit_bpe = getattr(args, "unit_bpe", None)
+    if args.template is None and (args.var or args.units is not None or args.dedup or unit_bpe is not None):
+        raise ValueError("--var, --units, --dedup and --unit-bpe belong to --template")
     if args.template is not None:
-        return [render_prompt(tokenizer, template=args.template, variables=template_variables(args), deduplicate=args.dedup)]
+        return [render_prompt(tokenizer, template=args.template, variables=template_variables(args), deduplicate=args.dedup,
+                              **({} if unit_bpe is None else {"unit_bpe": unit_bpe}))]
     if args.tokens is not None:
         return [render_prompt(tokenizer, token_ids=ints(t)) for t in args.tokens]
     return [render_prompt(tokenizer, text=t) for t in args.prompt]
@@ -95,7 +99,7 @@ def load(args):
     from ssi.trainer import Trainer
     conf = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "conf")
     cfg = compose(conf, "generate", [f"speech.n_dsus={args.n_dsus}", f"checkpointer.checkpoint_dir={args.checkpoint_dir}", f"dtype={args.dtype}",
-                                     "gen.output_dir=."])
+                                     "gen.output_dir=."] + ([f"speech.unit_bpe={args.unit_bpe}"] if getattr(args, "unit_bpe", None) else []))
     resolve_n_dsus(cfg)
     t = Trainer(cfg)
     t.device, t.dtype = get_device(cfg.device), get_dtype(cfg.dtype)

@@ -20,7 +20,9 @@ SSI_F32, SSI_BF16 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 IMPL_AUTO, IMPL_GENERIC, IMPL_MFMA, IMPL_MFMA_WG8 = 0, 1, 2, 3
 TILES_STATIC, TILES_DYNAMIC = 0, 1
-ABI_VERSION = 29
+ABI_VERSION = 30
+BPE_SEP, BPE_TILE, BPE_MAX_VOCAB, BPE_ENCODE_MAX_LEN, BPE_STATE_WORDS = -1, 4096, 16384, 4096, 8
+BPE_ST_DONE, BPE_ST_M, BPE_ST_A, BPE_ST_B, BPE_ST_COUNT, BPE_ST_NBAD, BPE_ST_LEN = 0, 1, 2, 3, 4, 5, 6
 EDIT_MAX_LEN, EDIT_COLS = 4096, 4
 GEMM_SKINNY_MAX_ROWS = 64
 DECODE_PENALTY_LDS_MAX = 57344
@@ -127,6 +129,11 @@ PROTOTYPES = {
     "ssi_seq_score_reduce": (c_int, [_P, _P, c_int64, _P, _P, c_int64, c_int, _P, _P]),
     "ssi_edit_distance_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "ssi_edit_distance": (c_int, [_P, c_int64, _P, _P, _P, _P, c_int64, c_int32, _P, _P, c_size_t, _P]),
+    "ssi_bpe_pair_count": (c_int, [_P, c_int64, c_int32, c_int32, _P, _P, _P]),
+    "ssi_bpe_train_workspace_bytes": (c_size_t, [c_int64]),
+    "ssi_bpe_train_begin": (c_int, [_P, c_int64, c_int32, c_int32, _P, _P, _P, _P]),
+    "ssi_bpe_merge": (c_int, [_P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_size_t, _P]),
+    "ssi_bpe_encode": (c_int, [_P, c_int64, _P, _P, c_int64, c_int32, _P, c_int32, c_int32, _P, _P, _P]),
     "ssi_lmhead_ce_fwd": (c_int,[_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, c_int64, _P, c_int64, _P, _P, c_int, c_int, _P]),
     "ssi_lmhead_ce_bwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int64, _P, c_int64, _P, c_int64, c_int, c_int, _P]),
     "ssi_count_tokens": (c_int, [_P, _P, c_int64, _P, c_int, c_int64, c_int64, _P, _P]),

@@ -52,7 +52,7 @@ def get_span_idxs_binomial(n: int, p: float, seq_len: int, rng: np.random.Genera
 
 def interleave(sample: Mapping[str, Any], deduplicate: bool, use_modality_tokens: bool, *, rng: np.random.Generator, sampling_rate: int,
                downsampling_ratio: int, mean_seq_len_tokens: float, binom_prob: float, keys: tuple[str, str, str, str] | None = None,
-               modality_tokens: tuple[str, str] = (MODALITY_TOKEN_TEXT, MODALITY_TOKEN_SPEECH)) -> str:
+               modality_tokens: tuple[str, str] = (MODALITY_TOKEN_TEXT, MODALITY_TOKEN_SPEECH), unit_bpe: Any = None) -> str:
     k_tok, k_t0, k_t1, k_sp = keys or (TOKENIZED_KEY, ALIGNMENT_START_TIME_KEY, ALIGNMENT_END_TIME_KEY, SPEECH_TOKENS_KEY)
     start_with_text = rng.choice([True, False], p=[0.5, 0.5])      # first draw, then the span lengths: the order is part of the format
     words, t_starts, t_ends, units = sample[k_tok], sample[k_t0], sample[k_t1], sample[k_sp]
@@ -67,6 +67,8 @@ def interleave(sample: Mapping[str, Any], deduplicate: bool, use_modality_tokens
         span = units[lo:hi]
         if deduplicate:
             span = deduplicate_units(span)
+        if unit_bpe is not None:   # span by span: a merge never crosses a text boundary
+            span = unit_bpe.encode(span)
         dsu_spans.append(units_to_text(span))
     if use_modality_tokens:
         text_spans = [" ".join((modality_tokens[0], s)) for s in text_spans]
@@ -77,11 +79,13 @@ def interleave(sample: Mapping[str, Any], deduplicate: bool, use_modality_tokens
 
 def concatenate_speech_text(sample: Mapping[str, Any], deduplicate: bool, use_modality_tokens: bool, *, rng: np.random.Generator,
                             start_with_text: bool, keys: tuple[str, str, str, str] | None = None,
-                            modality_tokens: tuple[str, str] = (MODALITY_TOKEN_TEXT, MODALITY_TOKEN_SPEECH)) -> str:
+                            modality_tokens: tuple[str, str] = (MODALITY_TOKEN_TEXT, MODALITY_TOKEN_SPEECH), unit_bpe: Any = None) -> str:
     k_tok, _, _, k_sp = keys or (TOKENIZED_KEY, ALIGNMENT_START_TIME_KEY, ALIGNMENT_END_TIME_KEY, SPEECH_TOKENS_KEY)
     units = sample[k_sp]
     if deduplicate:
         units = deduplicate_units(units)
+    if unit_bpe is not None:
+        units = unit_bpe.encode(units)
     text, dsus = " ".join(sample[k_tok]), units_to_text(units)
     if use_modality_tokens:
         text, dsus = " ".join((modality_tokens[0], text)), " ".join((modality_tokens[1], dsus))
@@ -93,7 +97,7 @@ class TextCompletionDataset(Dataset):
                  use_modality_tokens: bool, add_eos: bool = True, n_samples: int | None = None, tokenized_key: str | None = None,
                  alignment_start_time_key: str | None = None, alignment_end_time_key: str | None = None,
                  speech_tokens_key: str | None = None, filter_fn: Callable | None = None,
-                 interleave_kwargs: dict[str, Any] | None = None, **load_dataset_kwargs: Any) -> None:
+                 interleave_kwargs: dict[str, Any] | None = None, unit_bpe: Any = None, **load_dataset_kwargs: Any) -> None:
         self._tokenizer = tokenizer
         if split is not None:
             load_dataset_kwargs["split"] = split
@@ -104,6 +108,9 @@ class TextCompletionDataset(Dataset):
         common: dict[str, Any] = {"keys": keys}
         if getattr(tokenizer, "modality_tokens", None) is not None:
             common["modality_tokens"] = tuple(tokenizer.modality_tokens)
+        if unit_bpe is not None:   # a merges file (or a UnitBPE): speech.unit_bpe; null imports nothing and changes nothing
+            from ..tokenizer.unit_bpe import load_unit_bpe
+            common["unit_bpe"] = load_unit_bpe(unit_bpe)
         self.sequence_type = CompletionSequenceType(sequence_type)
         if self.sequence_type is CompletionSequenceType.INTERLEAVED:
             if not interleave_kwargs:

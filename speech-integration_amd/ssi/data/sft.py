@@ -19,7 +19,9 @@ from .sources import open_source
 
 class InputOutputToMessages:
     def __init__(self, train_on_input: bool, column_map: dict[str, str] | None = None, new_system_prompt: str | None = None,
-                 image_dir: Path | None = None, modality_tokens: tuple[str, str] = (MODALITY_TOKEN_TEXT, MODALITY_TOKEN_SPEECH)):
+                 image_dir: Path | None = None, modality_tokens: tuple[str, str] = (MODALITY_TOKEN_TEXT, MODALITY_TOKEN_SPEECH),
+                 unit_bpe: Any = None):
+        self.unit_bpe = unit_bpe   # None, or a ssi.tokenizer.unit_bpe.UnitBPE: the units are encoded after deduplication
         self.train_on_input = train_on_input
         self.new_system_prompt = new_system_prompt
         if column_map is not None:
@@ -41,6 +43,8 @@ class InputOutputToMessages:
         sp_tkns = sample[self.column_map["input"]]
         if deduplicate:
             sp_tkns = deduplicate_units(sp_tkns)
+        if self.unit_bpe is not None:
+            sp_tkns = self.unit_bpe.encode(sp_tkns)
         sp_span = units_to_text(sp_tkns)
         if use_modality_tokens:   # text follows: the next tokens are the assistant header
             sp_span = self.modality_token_speech + sp_span + self.modality_token_text
@@ -56,8 +60,11 @@ class SFTDataset(Dataset):
     def __init__(self, *, source: Any, model_tokenizer: Any, inference: bool = False, deduplicate: bool, use_modality_tokens: bool,
                  n_samples: int | None = None, filter_fn: Callable | None = None, train_on_input: bool,
                  column_map: dict[str, str] | None = None, new_system_prompt: str | None = None, image_dir: Path | None = None,
-                 additional_keys: list[str] | None = None, **load_dataset_kwargs: Any) -> None:
+                 additional_keys: list[str] | None = None, unit_bpe: Any = None, **load_dataset_kwargs: Any) -> None:
         extra = {}
+        if unit_bpe is not None:   # a merges file (or a UnitBPE): speech.unit_bpe; null imports nothing and changes nothing
+            from ..tokenizer.unit_bpe import load_unit_bpe
+            extra["unit_bpe"] = load_unit_bpe(unit_bpe)
         if getattr(model_tokenizer, "modality_tokens", None) is not None:
             extra["modality_tokens"] = tuple(model_tokenizer.modality_tokens)
         self._message_transform = InputOutputToMessages(train_on_input=train_on_input, column_map=column_map,

@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, check, dtype_code, ptr, stream_ptr
 
 __all__ = ["gemm_skinny", "gemm_skinny_rope", "gemm_skinny_swiglu", "weight_quant_fp8", "gemm_skinny_w8", "gemm_skinny_rope_w8", "gemm_skinny_swiglu_w8", "lmhead_ce_fwd", "lmhead_ce_bwd", "doc_ranges", "embed_fwd", "embed_bwd", "rmsnorm_fwd", "rmsnorm_bwd", "rope_", "attn_fwd", "attn_bwd", "attn_bwd_workspace_bytes", "kv_store", "attn_decode", "attn_decode_beam", "attn_decode_split", "attn_decode_beam_split", "attn_decode_split_span", "attn_decode_split_workspace", "decode_select", "decode_sample", "decode_select_pen", "decode_sample_pen", "decode_penalty_lds_bytes", "topk_logprob", "swiglu_fwd",
-           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "edit_distance", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "ema_update", "set_impl", "set_attn_impl", "attn_last_dispatch",
+           "swiglu_bwd", "gemm", "gemm_splitk", "splitk_choice", "gemm_swiglu_fwd", "gemm_swiglu_bwd", "transpose", "ce_fwd", "ce_fwd_z", "ce_fwd_smooth", "ce_fwd_kl", "ce_reduce", "ce_fwd_metrics", "ce_metrics_reduce", "seq_score_reduce", "edit_distance", "bpe_pair_count", "bpe_train_workspace_bytes", "bpe_train_begin", "bpe_merge", "bpe_encode", "count_tokens", "scale_", "sumsq", "adamw_step", "adamw_step_seg", "round_bf16_sr", "ema_update", "set_impl", "set_attn_impl", "attn_last_dispatch",
            "kv_store_fp8", "attn_decode_fp8", "attn_decode_beam_fp8", "attn_decode_split_fp8", "attn_decode_beam_split_fp8",
            "GEMM_NT", "GEMM_NN", "GEMM_TN"]
 
@@ -950,6 +950,57 @@ def edit_distance(tokens: Tensor, ref_start: Tensor, ref_len: Tensor, hyp_start:
     workspace = _byte_ws(need, tokens) if need else None
     check(lib.ssi_edit_distance(ptr(tokens), tokens.numel(), ptr(ref_start), ptr(ref_len), ptr(hyp_start), ptr(hyp_len), n_pairs, int(max_len),
                                 ptr(out), ptr(workspace), need, stream_ptr()), "ssi_edit_distance")
+
+
+def _bpe_i32(*tensors: Tensor) -> None:
+    for t in tensors:
+        assert t.dtype == torch.int32 and t.is_contiguous(), "unit BPE buffers are contiguous int32 device tensors"
+
+
+def bpe_pair_count(ids: Tensor, V: int, stride: int, table: Tensor, n_bad: Tensor | None = None) -> None:
+    """``table[a * stride + b] += c(a, b)`` over the flat int32 buffer ``ids`` (separator -1; ``table`` int32 of at least ``V * stride`` entries,
+    cleared by the caller).  An id outside ``[0, V)`` other than -1 acts as a separator and is counted once into ``n_bad`` (int32 ``[1]``, added
+    to).  The definition is in ``include/ssi_hip.h``."""
+    _bpe_i32(ids, table, *([n_bad] if n_bad is not None else []))
+    assert 0 < V <= stride and table.numel() >= (V - 1) * stride + V
+    check(_lib.load().ssi_bpe_pair_count(ptr(ids), ids.numel(), int(V), int(stride), ptr(table), ptr(n_bad), stream_ptr()), "ssi_bpe_pair_count")
+
+
+def bpe_train_workspace_bytes(n: int) -> int:
+    return int(_lib.load().ssi_bpe_train_workspace_bytes(int(n)))
+
+
+def bpe_train_begin(ids: Tensor, n_base: int, v_cap: int, buf0: Tensor, table: Tensor, state: Tensor) -> None:
+    """Start a training: ``table`` (int32 ``[v_cap * v_cap]``) cleared and filled with the pair counts of ``ids``, ``buf0`` = ``ids`` with bad ids
+    replaced by -1, ``state`` (int32 ``[_lib.BPE_STATE_WORDS]``) set: length of buffer 0, ``n_bad``, everything else zero."""
+    _bpe_i32(ids, buf0, table, state)
+    assert buf0.numel() >= ids.numel() and table.numel() >= v_cap * v_cap and state.numel() >= _lib.BPE_STATE_WORDS
+    check(_lib.load().ssi_bpe_train_begin(ptr(ids), ids.numel(), int(n_base), int(v_cap), ptr(buf0), ptr(table), ptr(state), stream_ptr()),
+          "ssi_bpe_train_begin")
+
+
+def bpe_merge(buf0: Tensor, buf1: Tensor, n_upper: int, n_base: int, v_cap: int, m: int, min_frequency: int, table: Tensor, merges: Tensor,
+              state: Tensor, workspace: Tensor) -> None:
+    """Launch merge ``m`` (it reads buffer ``m & 1`` and writes the other; the pair, the lengths and ``done`` are read from ``state`` on the
+    device, and after ``done`` the launches do nothing).  ``n_upper``: the host's bound on the current length.  Nothing is read back."""
+    _bpe_i32(buf0, buf1, table, merges, state)
+    assert buf0.numel() == buf1.numel() and table.numel() >= v_cap * v_cap and merges.numel() >= 3 * (v_cap - n_base)
+    assert state.numel() >= _lib.BPE_STATE_WORDS and workspace.dtype == torch.uint8
+    check(_lib.load().ssi_bpe_merge(ptr(buf0), ptr(buf1), buf0.numel(), int(n_upper), int(n_base), int(v_cap), int(m), int(min_frequency), ptr(table),
+                                    ptr(merges), ptr(state), ptr(workspace), workspace.numel(), stream_ptr()), "ssi_bpe_merge")
+
+
+def bpe_encode(tokens: Tensor, seq_start: Tensor, seq_len: Tensor, max_len: int, rank_table: Tensor, V: int, n_base: int, out: Tensor,
+               out_len: Tensor) -> None:
+    """Encode the spans ``tokens[seq_start[s] : + seq_len[s]]`` (starts int64, lengths int32) with the merges of ``rank_table`` (int32
+    ``[V * V]``, -1: no merge): ``out[seq_start[s] : + out_len[s]]`` holds the result, ``out_len[s]`` is -1 for a bad span.  ``max_len`` (at most
+    ``_lib.BPE_ENCODE_MAX_LEN``) bounds every length."""
+    _bpe_i32(tokens, seq_len, rank_table, out, out_len)
+    n_seq = seq_start.numel()
+    assert seq_start.dtype == torch.int64 and seq_start.is_contiguous() and seq_len.numel() == n_seq and out_len.numel() >= n_seq
+    assert out.numel() >= tokens.numel() and rank_table.numel() >= V * V
+    check(_lib.load().ssi_bpe_encode(ptr(tokens), tokens.numel(), ptr(seq_start), ptr(seq_len), n_seq, int(max_len), ptr(rank_table), int(V), int(n_base),
+                                     ptr(out), ptr(out_len), stream_ptr()), "ssi_bpe_encode")
 
 
 def lmhead_ce_fwd(hidden: Tensor, table: Tensor, labels: Tensor, vocab: int, ignore_index: int, logits_ws: Tensor, row_loss: Tensor,

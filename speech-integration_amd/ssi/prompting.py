@@ -25,10 +25,11 @@ def _jinja2():
     return jinja2
 
 
-def render_template(template: str, variables: Mapping[str, Any] | None = None, *, deduplicate: bool = False) -> str:
+def render_template(template: str, variables: Mapping[str, Any] | None = None, *, deduplicate: bool = False, unit_bpe: Any = None) -> str:
     """The text of a Jinja2 ``template`` (a path to a file, or the template itself).  ``MODALITY_TOKEN_SPEECH`` and ``MODALITY_TOKEN_TEXT`` are
     supplied (a caller's value of the same name wins); ``speech_units``, a list of ints, is rendered as the units' private-use characters
-    (``units_to_text``), after ``deduplicate_units`` when ``deduplicate``.  An undefined variable is an error, not an empty string."""
+    (``units_to_text``), after ``deduplicate_units`` when ``deduplicate`` and after ``unit_bpe`` (a merges file or a ``UnitBPE``; None: nothing is
+    imported) has encoded them.  An undefined variable is an error, not an empty string."""
     jinja2 = _jinja2()
     source = template
     if os.path.isfile(template):
@@ -39,21 +40,25 @@ def render_template(template: str, variables: Mapping[str, Any] | None = None, *
     units = values.get("speech_units")
     if units is not None and not isinstance(units, str):
         units = [int(u) for u in units]
-        values["speech_units"] = units_to_text(deduplicate_units(units) if deduplicate else units)
+        units = deduplicate_units(units) if deduplicate else units
+        if unit_bpe is not None:
+            from .tokenizer.unit_bpe import load_unit_bpe
+            units = load_unit_bpe(unit_bpe).encode(units)
+        values["speech_units"] = units_to_text(units)
     env = jinja2.Environment(undefined=jinja2.StrictUndefined, keep_trailing_newline=False, autoescape=False)
     return env.from_string(source).render(**values)
 
 
 def render_prompt(tokenizer, *, text: str | None = None, token_ids: Sequence[int] | None = None, template: str | None = None,
-                  variables: Mapping[str, Any] | None = None, deduplicate: bool = False) -> list[int]:
+                  variables: Mapping[str, Any] | None = None, deduplicate: bool = False, unit_bpe: Any = None) -> list[int]:
     """Token ids of a prompt given as exactly one of ``text`` (the tokenizer's ``encode`` with BOS, without EOS), ``token_ids`` (taken as they
     are; each must lie in ``[0, tokenizer.vocab_size)``) and ``template`` (``render_template`` with ``variables``, then as ``text``).
     ``ValueError``: none or several of the three, ``variables`` without a template, an empty prompt, an id outside the vocabulary."""
     given = [k for k, v in (("text", text), ("token_ids", token_ids), ("template", template)) if v is not None]
     if len(given) != 1:
         raise ValueError(f"render_prompt: exactly one of text, token_ids and template (got {given or 'none'})")
-    if (variables or deduplicate) and template is None:
-        raise ValueError("render_prompt: variables and deduplicate belong to a template")
+    if (variables or deduplicate or unit_bpe is not None) and template is None:
+        raise ValueError("render_prompt: variables, deduplicate and unit_bpe belong to a template")
     if token_ids is not None:
         ids = [int(t) for t in token_ids]
         vocab = getattr(tokenizer, "vocab_size", None)
@@ -61,7 +66,8 @@ def render_prompt(tokenizer, *, text: str | None = None, token_ids: Sequence[int
         if bad:
             raise ValueError(f"render_prompt: token ids {bad[:8]} lie outside the vocabulary [0, {vocab})")
     else:
-        ids = [int(t) for t in tokenizer.encode(text if text is not None else render_template(template, variables, deduplicate=deduplicate),
+        ids = [int(t) for t in tokenizer.encode(text if text is not None else render_template(template, variables, deduplicate=deduplicate,
+                                                                                                  **({} if unit_bpe is None else {"unit_bpe": unit_bpe})),
                                                 add_bos=True, add_eos=False)]
     if not ids:
         raise ValueError("render_prompt: the prompt is empty")

@@ -73,6 +73,7 @@ def resolve_n_dsus(cfg) -> None:
     ``n_dsus`` (every ``conf/data/*`` child names its tokenizer's codebook size) is copied in.  Behaviour of the reference's
     helper of the same name (``train_utils.py:37-59``)."""
     if cfg.speech.n_dsus is not None:
+        check_unit_bpe_n_dsus(cfg)
         return
     data_node = cfg.get("data")
     from_data = data_node.get("n_dsus") if data_node is not None else None
@@ -81,6 +82,20 @@ def resolve_n_dsus(cfg) -> None:
                          "data config that sets n_dsus")
     cfg.speech.n_dsus = from_data
     LOGGER.info(f"speech.n_dsus={from_data} (taken from the data config)")
+    check_unit_bpe_n_dsus(cfg)
+
+
+def check_unit_bpe_n_dsus(cfg) -> None:
+    """With ``speech.unit_bpe`` (a merges file of ``scripts/unit_bpe.py train``) every merged unit is one more unit id, so ``speech.n_dsus`` must be
+    the file's ``n_base + n_merges``.  Null (the default): nothing is read or imported."""
+    path = cfg.speech.get("unit_bpe")
+    if path is None:
+        return
+    from .tokenizer.unit_bpe import load_unit_bpe
+    bpe = load_unit_bpe(path)
+    if int(cfg.speech.n_dsus) != bpe.vocab_size:
+        raise ValueError(f"speech.n_dsus={cfg.speech.n_dsus} but speech.unit_bpe={str(path)!r} holds n_base + n_merges = {bpe.n_base} + {bpe.n_merges} = "
+                         f"{bpe.vocab_size} unit ids: pass speech.n_dsus={bpe.vocab_size} (and a tokenizer file and checkpoint extended to that count)")
 
 
 _POSITIVE_INT_FIELDS = ("gradient_accumulation_steps", "max_steps", "log_interval", "eval_steps", "save_steps")
@@ -90,6 +105,7 @@ def validate_train_cfg(cfg) -> None:
     """Refuse a run config the trainer cannot execute; every problem is a ``ValueError`` naming the field."""
     if cfg.speech.n_dsus is None:
         raise ValueError("speech.n_dsus is null: call resolve_n_dsus(cfg) before validate_train_cfg(cfg)")
+    check_unit_bpe_n_dsus(cfg)
     if PRECISION_STR_TO_DTYPE.get(cfg.dtype) not in SUPPORTED_DTYPES:
         raise ValueError(f"dtype {cfg.dtype!r} is not supported (supported: {SUPPORTED_DTYPES})")
     unset = _missing_keys(cfg)

@@ -35,7 +35,8 @@ NO_SCRATCH = ("attn_bwd_dq2_kernel", "attn_bwd_dkv2_kernel", "attn_fwd_kernel", 
               "ce_row_bf16_metrics_kernel", "ce_fwd_metrics_kernel", "ce_row_bf16_z_kernel", "ce_fwd_z_kernel", "ce_row_bf16_smooth_kernel", "ce_fwd_smooth_kernel", "ce_kl_row_bf16_kernel", "ce_kl_generic_kernel", "adamw_sr_kernel", "round_bf16_sr_kernel", "seq_score_reduce_kernel", "edit_distance_kernel",
               "adamw_seg_kernel", "adamw_seg_sr_kernel", "ema_update_kernel", "kv_store_kernel", "kv_decode_kernel", "beam_decode_kernel", "q8_store_kernel", "q8_decode_kernel", "q8_beam_kernel", "q8_split_walk_kernel", "q8_split_beam_kernel","topk_logprob_kernel", "decode_sample_kernel", "select_pen_kernel", "sample_pen_kernel", "sample_rows_kernel", "sample_rows_pen_kernel",
               "sumsq_groups_partial_kernel", "sumsq_groups_final_kernel", "adamw_gscale_kernel", "adamw_gscale_sr_kernel", "skinny_kernel", "wq8_gemm_kernel", "wq8_quant_kernel",
-              "split_kv_walk_kernel", "split_beam_walk_kernel", "split_kv_merge_kernel")
+              "split_kv_walk_kernel", "split_beam_walk_kernel", "split_kv_merge_kernel",
+              "bpe_pair_count_kernel", "bpe_sanitise_kernel", "bpe_state_init_kernel", "bpe_best_partial_kernel", "bpe_best_final_kernel", "bpe_mark_kernel", "bpe_scan_kernel", "bpe_apply_kernel", "bpe_encode_kernel")
 PINNED_LOOPS = ("attn_bwd_dq2_kernel", "attn_bwd_dkv2_kernel")   # kernels whose main loops are inline-asm MFMAs on pinned register classes
 MAIN_LOOP_MFMAS = 32
 
