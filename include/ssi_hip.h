@@ -582,7 +582,7 @@ int ssi_gemm_skinny_swiglu(int64_t M, int64_t inter, int64_t K, const void* X, i
  * those take (W, ldw); every other argument, the epilogues' rounding points, the refusals (ld_codes in place of ldw: >= K, 16-byte rows) and
  * "row r has the same bits whatever M is" are unchanged.  THE CONTRACT: the output is BIT-EQUAL to the matching plain entry called on the
  * dequantised matrix stored as bf16.  So the k of a lane slot, the wave of a 64-wide chunk, the order of the matrix instructions within a wave
- * and the LDS merge are skinny_kernel's (the merge and the epilogues are the same code); a lane's 16 codes of a chunk and row come in ONE 16-byte
+ * and the LDS merge are skinny_kernel's (the merge, the epilogues and the refusals are one copy of code, csrc/gemm_skinny.h); a lane's 16 codes of a chunk and row come in ONE 16-byte
  * load and become the two bf16x8 operands by v_cvt_pk_f32_fp8, v_ldexp_f32 and v_cvt_pk_bf16_f32, all exact: the row's exponent is applied AT
  * THE CONVERSION, not to the fp32 sums.  Free, and used: two of a wave's chunks are in flight, which keeps the bf16 kernel's bytes in flight
  * per lane.  exps is read at rows [0, N) only (SwiGLU: [0, 2 I)).  Forms: 12, as skinny_kernel's; no scratch.  The bf16 weights are not

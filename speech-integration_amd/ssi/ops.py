@@ -731,46 +731,66 @@ def gemm_swiglu_bwd(layout: int, dy: Tensor, w2: Tensor, gu: Tensor, dgu: Tensor
           "ssi_gemm_swiglu_bwd")
 
 
-def gemm_skinny(a: Tensor, w: Tensor, c: Tensor, *, residual: Tensor | None = None) -> None:
-    """c = a @ w^T (+ residual) for 1 to 64 rows of bf16: the weight-streaming kernel of small-batch decoding (``ssi_gemm``'s rounding points)."""
-    assert a.dim() == 2 and w.dim() == 2 and c.dim() == 2 and a.stride(1) == 1 and w.stride(1) == 1 and c.stride(1) == 1
+def _w8_rows(codes: Tensor, exps: Tensor, like: Tensor) -> tuple[int, int]:
+    """(N, K) of a quantised weight matrix as the ``_w8`` entries take it: uint8 ``codes`` [N, K] (rows may be pitched) and ``exps`` [N]."""
+    assert codes.dim() == 2 and codes.dtype == torch.uint8 and codes.stride(1) == 1 and like.dtype == torch.bfloat16
+    assert exps.dtype == torch.uint8 and exps.shape == (codes.shape[0],) and exps.is_contiguous() and exps.device == codes.device == like.device
+    return codes.shape
+
+
+def _skinny_weight(w: Tensor, exps: Tensor | None, like: Tensor) -> tuple[int, int]:
+    """(N, K) of a skinny GEMM's weight matrix: bf16 ``w`` [N, K] of ``like``'s dtype, or, with ``exps``, the codes of ``_w8_rows``."""
+    if exps is not None:
+        return _w8_rows(w, exps, like)
+    assert w.dim() == 2 and w.stride(1) == 1 and w.dtype == like.dtype
+    return w.shape
+
+
+def _skinny_shapes(a: Tensor, w: Tensor, exps: Tensor | None, c: Tensor, *, residual: Tensor | None = None, rope: tuple | None = None) -> tuple[int, int, int]:
+    """(M, N, K) of ``c = a @ w^T`` on a skinny entry, plain (``exps`` None) or ``_w8``: what the plain and the RoPE wrappers ask of ``a``, the weights,
+    ``c``, the residual and ``rope`` = (table, positions, head_dim)."""
+    assert a.dim() == 2 and c.dim() == 2 and a.stride(1) == 1 and c.stride(1) == 1
     M, K = a.shape
-    N = w.shape[0]
-    assert w.shape[1] == K and c.shape == (M, N) and a.dtype == w.dtype == c.dtype
+    N, wk = _skinny_weight(w, exps, a)
+    assert wk == K and c.shape == (M, N) and a.dtype == c.dtype
     if residual is not None:
         assert residual.shape == c.shape and residual.stride() == c.stride() and residual.dtype == c.dtype
+    if rope is not None:
+        table, positions, head_dim = rope
+        assert table.dtype == torch.float32 and table.is_contiguous() and table.shape[1] * 2 == head_dim
+        assert positions.dtype == torch.int32 and positions.numel() == M and positions.is_contiguous()
+    return M, N, K
+
+
+def _skinny_swiglu_shapes(x: Tensor, w13: Tensor, exps13: Tensor | None, gu: Tensor | None, act: Tensor) -> tuple[int, int, int]:
+    """(M, I, K) of the SwiGLU form, plain or ``_w8``: ``w13`` = [gate rows | up rows] is [2 I, K], ``act`` [M, I], ``gu`` None or [M, 2 I]."""
+    M, K = x.shape
+    inter = act.shape[1]
+    assert _skinny_weight(w13, exps13, x) == (2 * inter, K) and act.shape[0] == M and x.stride(1) == 1 and act.stride(1) == 1
+    assert gu is None or (gu.shape == (M, 2 * inter) and gu.stride(1) == 1 and gu.dtype == x.dtype)
+    assert x.dtype == act.dtype
+    return M, inter, K
+
+
+def gemm_skinny(a: Tensor, w: Tensor, c: Tensor, *, residual: Tensor | None = None) -> None:
+    """c = a @ w^T (+ residual) for 1 to 64 rows of bf16: the weight-streaming kernel of small-batch decoding (``ssi_gemm``'s rounding points)."""
+    M, N, K = _skinny_shapes(a, w, None, c, residual=residual)
     check(_lib.load().ssi_gemm_skinny(M, N, K, ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(c), c.stride(0), ptr(residual),
                                       dtype_code(c.dtype), stream_ptr()), "ssi_gemm_skinny")
 
 
 def gemm_skinny_rope(a: Tensor, w: Tensor, c: Tensor, n_heads_rot: int, head_dim: int, table: Tensor, positions: Tensor) -> None:
     """``gemm_skinny`` followed by ``rope_`` on the first ``n_heads_rot`` heads of every row, by ``positions`` (required), in one launch."""
-    assert a.dim() == 2 and w.dim() == 2 and c.dim() == 2 and a.stride(1) == 1 and w.stride(1) == 1 and c.stride(1) == 1
-    M, K = a.shape
-    N = w.shape[0]
-    assert w.shape[1] == K and c.shape == (M, N) and a.dtype == w.dtype == c.dtype
-    assert table.dtype == torch.float32 and table.is_contiguous() and table.shape[1] * 2 == head_dim
-    assert positions.dtype == torch.int32 and positions.numel() == M and positions.is_contiguous()
+    M, N, K = _skinny_shapes(a, w, None, c, rope=(table, positions, head_dim))
     check(_lib.load().ssi_gemm_skinny_rope(M, N, K, ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(c), c.stride(0), n_heads_rot, head_dim,
                                            ptr(table), table.shape[0], ptr(positions), dtype_code(a.dtype), stream_ptr()), "ssi_gemm_skinny_rope")
 
 
 def gemm_skinny_swiglu(x: Tensor, w13: Tensor, gu: Tensor | None, act: Tensor) -> None:
     """act = silu(gate) * up of ``x @ w13^T`` = [gate | up] for 1 to 64 rows, one launch; ``gu`` (``None``: not written) gets [gate | up]."""
-    M, K = x.shape
-    inter = act.shape[1]
-    assert w13.shape == (2 * inter, K) and act.shape[0] == M and x.stride(1) == 1 and w13.stride(1) == 1 and act.stride(1) == 1
-    assert gu is None or (gu.shape == (M, 2 * inter) and gu.stride(1) == 1 and gu.dtype == x.dtype)
-    assert x.dtype == w13.dtype == act.dtype
+    M, inter, K = _skinny_swiglu_shapes(x, w13, None, gu, act)
     check(_lib.load().ssi_gemm_skinny_swiglu(M, inter, K, ptr(x), x.stride(0), ptr(w13), w13.stride(0), ptr(gu), 0 if gu is None else gu.stride(0),
                                              ptr(act), act.stride(0), dtype_code(x.dtype), stream_ptr()), "ssi_gemm_skinny_swiglu")
-
-
-def _w8_rows(codes: Tensor, exps: Tensor, like: Tensor) -> tuple[int, int]:
-    """(N, K) of a quantised weight matrix as the ``_w8`` entries take it: uint8 ``codes`` [N, K] (rows may be pitched) and ``exps`` [N]."""
-    assert codes.dim() == 2 and codes.dtype == torch.uint8 and codes.stride(1) == 1 and like.dtype == torch.bfloat16
-    assert exps.dtype == torch.uint8 and exps.shape == (codes.shape[0],) and exps.is_contiguous() and exps.device == codes.device == like.device
-    return codes.shape
 
 
 def weight_quant_fp8(w: Tensor, codes: Tensor, exps: Tensor) -> None:
@@ -785,24 +805,14 @@ def weight_quant_fp8(w: Tensor, codes: Tensor, exps: Tensor) -> None:
 
 def gemm_skinny_w8(a: Tensor, codes: Tensor, exps: Tensor, c: Tensor, *, residual: Tensor | None = None) -> None:
     """``gemm_skinny`` on a weight matrix quantised by ``weight_quant_fp8``: bit-equal to ``gemm_skinny`` on the dequantised matrix in bf16."""
-    assert a.dim() == 2 and c.dim() == 2 and a.stride(1) == 1 and c.stride(1) == 1
-    M, K = a.shape
-    N = _w8_rows(codes, exps, a)[0]
-    assert codes.shape[1] == K and c.shape == (M, N) and a.dtype == c.dtype
-    if residual is not None:
-        assert residual.shape == c.shape and residual.stride() == c.stride() and residual.dtype == c.dtype
+    M, N, K = _skinny_shapes(a, codes, exps, c, residual=residual)
     check(_lib.load().ssi_gemm_skinny_w8(M, N, K, ptr(a), a.stride(0), ptr(codes), codes.stride(0), ptr(exps), ptr(c), c.stride(0), ptr(residual),
                                          dtype_code(c.dtype), stream_ptr()), "ssi_gemm_skinny_w8")
 
 
 def gemm_skinny_rope_w8(a: Tensor, codes: Tensor, exps: Tensor, c: Tensor, n_heads_rot: int, head_dim: int, table: Tensor, positions: Tensor) -> None:
     """``gemm_skinny_rope`` on a quantised weight matrix."""
-    assert a.dim() == 2 and c.dim() == 2 and a.stride(1) == 1 and c.stride(1) == 1
-    M, K = a.shape
-    N = _w8_rows(codes, exps, a)[0]
-    assert codes.shape[1] == K and c.shape == (M, N) and a.dtype == c.dtype
-    assert table.dtype == torch.float32 and table.is_contiguous() and table.shape[1] * 2 == head_dim
-    assert positions.dtype == torch.int32 and positions.numel() == M and positions.is_contiguous()
+    M, N, K = _skinny_shapes(a, codes, exps, c, rope=(table, positions, head_dim))
     check(_lib.load().ssi_gemm_skinny_rope_w8(M, N, K, ptr(a), a.stride(0), ptr(codes), codes.stride(0), ptr(exps), ptr(c), c.stride(0), n_heads_rot,
                                               head_dim, ptr(table), table.shape[0], ptr(positions), dtype_code(a.dtype), stream_ptr()),
           "ssi_gemm_skinny_rope_w8")
@@ -810,11 +820,7 @@ def gemm_skinny_rope_w8(a: Tensor, codes: Tensor, exps: Tensor, c: Tensor, n_hea
 
 def gemm_skinny_swiglu_w8(x: Tensor, codes13: Tensor, exps13: Tensor, gu: Tensor | None, act: Tensor) -> None:
     """``gemm_skinny_swiglu`` on a quantised ``w13`` = [gate rows | up rows]."""
-    M, K = x.shape
-    inter = act.shape[1]
-    assert _w8_rows(codes13, exps13, x) == (2 * inter, K) and act.shape[0] == M and x.stride(1) == 1 and act.stride(1) == 1
-    assert gu is None or (gu.shape == (M, 2 * inter) and gu.stride(1) == 1 and gu.dtype == x.dtype)
-    assert x.dtype == act.dtype
+    M, inter, K = _skinny_swiglu_shapes(x, codes13, exps13, gu, act)
     check(_lib.load().ssi_gemm_skinny_swiglu_w8(M, inter, K, ptr(x), x.stride(0), ptr(codes13), codes13.stride(0), ptr(exps13), ptr(gu),
                                                 0 if gu is None else gu.stride(0), ptr(act), act.stride(0), dtype_code(x.dtype), stream_ptr()),
           "ssi_gemm_skinny_swiglu_w8")

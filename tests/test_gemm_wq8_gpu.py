@@ -178,10 +178,19 @@ def test_a_nan_code_makes_its_own_column_nan_and_moves_no_other(ops, N, K, n, k)
         assert bool((c1[M] == SENTINEL).all())
 
 
-def test_refusals_are_the_plain_entries(ops):
+def test_refusals_are_the_plain_entries(ops, table):
     codes, exps, deq = weights(64, 64)
     a = acts(64)
     c = out(64, 64)
+    # the RoPE refusals, one body for both entries (csrc/gemm_skinny.h): each entry under its own name, before any launch
+    pos = torch.zeros(4, dtype=torch.int32, device=DEV)
+    for heads, hd, tab in ((1, 128, torch.zeros((TLEN, 64, 2), dtype=torch.float32, device=DEV)),   # head_dim 128 (a table of 64 columns)
+                           (2, 64, table)):                                                           # n_heads_rot * 64 > N = 64
+        with pytest.raises(RuntimeError, match="ssi_gemm_skinny_rope_w8: head_dim 64"):
+            ops.gemm_skinny_rope_w8(a[:4], codes, exps, c[:4, :64], heads, hd, tab, pos)
+        with pytest.raises(RuntimeError, match="ssi_gemm_skinny_rope: head_dim 64"):
+            ops.gemm_skinny_rope(a[:4], deq, c[:4, :64], heads, hd, tab, pos)
+    assert bool((c == SENTINEL).all())
     with pytest.raises(RuntimeError, match="ssi_gemm_skinny_w8"):          # 65 rows
         ops.gemm_skinny_w8(a, codes, exps, torch.empty((65, 64), dtype=BF, device=DEV))
     pitched = torch.zeros((64, 72), dtype=torch.uint8, device=DEV)[:, :64]  # code rows off 16-byte boundaries

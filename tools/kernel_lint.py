@@ -18,7 +18,9 @@ runs the same checks in the CPU suite.
 ``python tools/kernel_lint.py [lib] --against OTHER_LIB`` compares the two libraries' gfx950 kernels instead (has a change MOVED device
 code or CHANGED it?): the same kernel names on both sides, per kernel the same instruction stream (mnemonic and operands; branch targets as
 offsets within the kernel, the literals of pc-relative address computations as "pc-relative") and the same VGPR / AGPR / SGPR counts, LDS bytes and private segment size in the code-object notes.  Exits 1 on
-any difference.  Which translation unit a kernel sits in is not compared."""
+any difference.  Which translation unit a kernel sits in is not compared.  For a kernel whose streams differ it also says where they part against
+the kernel's K loops (the loops that hold matrix instructions): the loops' code equal and every difference behind the last of them — an epilogue
+moved — or a loop itself or the code ahead of it changed."""
 from __future__ import annotations
 
 import os
@@ -251,6 +253,31 @@ def stream(k: Kernel) -> list[tuple]:
     return out
 
 
+def k_loops(k: Kernel) -> list[tuple[int, int]]:
+    """Loops that hold matrix instructions, as [first, last] instruction indices: from the target of a backward branch to the last branch back to
+    it.  R2's main loops (one basic block that loops to itself) are the simplest case; a loop whose body branches (the skinny GEMMs load rows
+    under exec masks) spans several blocks."""
+    index = {i.addr: n for n, i in enumerate(k.ins)}
+    last: dict[int, int] = {}
+    for n, i in enumerate(k.ins):
+        a = index.get(i.target) if i.target is not None else None
+        if a is not None and a <= n:
+            last[a] = n
+    return [(a, b) for a, b in sorted(last.items()) if any(i.op.startswith("v_mfma") for i in k.ins[a:b + 1])]
+
+
+def where_against_k_loop(ka: Kernel, kb: Kernel, first: int) -> str:
+    """Where two differing streams part, told against the kernels' K loops: a change behind the last loop (an epilogue) leaves the loops alone."""
+    la, lb = k_loops(ka), k_loops(kb)
+    if not la or not lb:
+        return "no loop with matrix instructions on one side"
+    sa, sb = stream(ka), stream(kb)
+    if [sa[a:b + 1] for a, b in la] != [sb[a:b + 1] for a, b in lb]:
+        return "K LOOP DIFFERS"
+    end = max(la[-1][1], lb[-1][1])
+    return f"K loops equal, every difference after them (the last ends at instruction {end})" if first > end else "DIFFERENCE AHEAD OF THE K LOOP"
+
+
 def compare(lib: str, other: str) -> tuple[list[str], int]:
     """Differences between the gfx950 kernels of two libraries, and how many kernels `lib` has."""
     def load(path: str) -> dict[str, Kernel]:
@@ -268,7 +295,8 @@ def compare(lib: str, other: str) -> tuple[list[str], int]:
         if sa != sb:
             first = next((j for j, (x, y) in enumerate(zip(sa, sb)) if x != y), min(len(sa), len(sb)))
             diffs.append(f"{n}: {len(sa)} against {len(sb)} instructions, first difference at instruction {first}: "
-                         f"{sa[first] if first < len(sa) else None} against {sb[first] if first < len(sb) else None}")
+                         f"{sa[first] if first < len(sa) else None} against {sb[first] if first < len(sb) else None}; "
+                         f"{where_against_k_loop(a[n], b[n], first)}")
     return diffs, len(a)
 
 
